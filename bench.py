@@ -26,6 +26,12 @@ Every N > 1 line carries `rccl_ranks` (launcher mode: == N, an all_reduce over t
 N = 1 of the benchmark being configs[1]), `cpu_baseline` (the reference binary on a bounded sample of the same-shaped mesh) and a
 `roofline` whose kernel is the measured maximum of the step's kernels.
 
+A plain run sets up, warms up, times the steps and prints the line (headline, step times, stage and kernel times of the timed steps,
+the roofline of their dominant kernel).  Everything that takes runs of its own -- the checks of the merged container, the same
+workload through one context, the end-to-end, compat, OBJ and larger-configuration legs, the CPU baselines, the in-process leg of a
+launcher run -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed (the .hry container and the
+decoded mesh) as DIR/<name>.npy, float32 where every value is exact in it, float64 otherwise.
+
 Prints ONE JSON line on rank 0; its LAST key, `summary`, is a compact digest (< 1.5 KB) of the sub-records.
 """
 from __future__ import annotations
@@ -319,12 +325,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--side", type=int, default=708, help="torus grid side; 708 -> 1 002 528 triangles (configs[1])")
     ap.add_argument("--profile", default="auto", choices=["auto", "compat", "chunked"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-large", action="store_true", help="skip the cfg3 / cfg4_share sub-records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-large", action="store_true", help="with --full: skip the cfg3 / cfg4_share sub-records")
     ap.add_argument("--launcher", action="store_true", help="(default since round 5) --gpus N without a launcher starts N ranks")
     ap.add_argument("--inprocess", action="store_true", help="--gpus N as ONE process with N device contexts (no torch.distributed, no collective)")
     ap.add_argument("--comps-per-gpu", type=int, default=CFG4_PER_GPU[0], help="N > 1: components per GPU of the configs[3]-shaped mesh")
     ap.add_argument("--share-device", action="store_true", help="rehearsal on a box with fewer GPUs: ranks / contexts share device 0 (ranks: gloo instead of RCCL)")
+    ap.add_argument("--full", action="store_true", help="also the checks, baselines and legs beyond the headline (sub-records of the same line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -416,8 +424,9 @@ def main():
     except hc.HryError:
         can_decode = False
 
-    def one_step():
-        """returns (container bytes, merged container on rank 0, timings); inputs are resident in HBM before the timed region"""
+    def one_step(keep=False):
+        """returns (container bytes, merged container on rank 0, timings, decoded mesh if `keep`); inputs are resident in HBM before
+        the timed region"""
         m = raw.clone()
         cx.upload(m)                                     # float records + connectivity resident in HBM
         torch.cuda.synchronize()
@@ -433,16 +442,18 @@ def main():
         tm_e["requant_ms"] = (t_q - t0) * 1e3
         gather = sharding.SegmentGather(out, comm_dev, as_buffer=True) if world > 1 else None    # segments -> rank 0, overlapping the decode below
         t_g = time.perf_counter()
-        tm_d = {}
+        tm_d, dec = {}, None
         if can_decode:
-            cx.read_hry(out, partial=world > 1)          # every rank decodes its own segment
+            dec = cx.read_hry(out, partial=world > 1)    # every rank decodes its own segment
+            if not keep:
+                dec = None                               # (released here, as before --dump-outputs kept the last one)
             tm_d = cx.timing()
         t2 = time.perf_counter()
         merged = gather.finish() if gather else None     # rank 0: hry_merge -> ONE container
         t3 = time.perf_counter()
         tm_e.update({"dec_" + k: v for k, v in tm_d.items()})
         tm_e["gather_merge_ms"] = (t_g - t1 + t3 - t2) * 1e3
-        return out, merged, t1 - t0, t2 - t_g, t_g - t1 + t3 - t2, tm_e
+        return out, merged, t1 - t0, t2 - t_g, t_g - t1 + t3 - t2, tm_e, dec
 
     def barrier():
         if world > 1:
@@ -454,9 +465,9 @@ def main():
     barrier()
     enc_s = dec_s = comm_s = 0.0
     timings = []
-    out, merged = b"", None
-    for _ in range(args.steps):
-        out, merged, te, td, tg, tm = one_step()
+    out, merged, dec = b"", None, None
+    for i in range(args.steps):
+        out, merged, te, td, tg, tm, dec = one_step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         enc_s += te
         dec_s += td
         comm_s += tg
@@ -468,6 +479,8 @@ def main():
         dist.all_reduce(total, op=dist.ReduceOp.MAX)
     t_all, t_enc, t_dec, t_comm = (float(x) for x in total.tolist())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(merged if world > 1 else out, dec))
     if rank == 0:
         ntri = mesh.ntri                                  # the whole mesh
         step_ms = t_all / args.steps * 1e3
@@ -529,16 +542,17 @@ def main():
             # the merged container: decode it whole on this GPU and compare with the single-GPU path on the whole mesh
             # (outside the timed region)
             ok = None
-            try:
-                got = cx.read_hry(merged)
-                one = whole.clone()
-                cx.requant(one, quant)
-                ref = cx.read_hry(cx.write_hry(one, profile=pid))
-                ok = bool(got.nv == ref.nv and np.array_equal(got.face_offsets(), ref.face_offsets()) and np.array_equal(got.org(), ref.org())
-                          and np.array_equal(got.twin(), ref.twin()) and np.array_equal(got.list_data(1), ref.list_data(1)))
-            except Exception as exc:
-                sys.stderr.write(f"merged-container check failed: {exc}\n")
-                ok = False
+            if args.full:
+                try:
+                    got = cx.read_hry(merged)
+                    one = whole.clone()
+                    cx.requant(one, quant)
+                    ref = cx.read_hry(cx.write_hry(one, profile=pid))
+                    ok = bool(got.nv == ref.nv and np.array_equal(got.face_offsets(), ref.face_offsets()) and np.array_equal(got.org(), ref.org())
+                              and np.array_equal(got.twin(), ref.twin()) and np.array_equal(got.list_data(1), ref.list_data(1)))
+                except Exception as exc:
+                    sys.stderr.write(f"merged-container check failed: {exc}\n")
+                    ok = False
             line["mode"] = "launcher: one process per GPU (torch.distributed, backend below)"
             line["rccl_ranks"] = rccl_ranks
             incl = t_all + args.steps * (plan_ms + extract_ms) * 1e-3
@@ -554,133 +568,135 @@ def main():
                                "collectives": "all_gather(bounds, 96 B/rank) + all_gather(sizes) + gather(segments, asynchronous: overlaps the decode) per step"}
             if ok is False:
                 line["error"] = "merged container does not decode to the single-GPU result"
-            # the same workload through ONE context, unsharded (rank 0's GPU): what the driver's per-N efficiency should be read against,
-            # since N = 1 of this benchmark is configs[1], another workload
-            try:
-                share = build_cfg4(1, args.comps_per_gpu)
-                sm = hc.Mesh.from_arrays(share.verts, share.degrees, share.indices)
-                ts = []
-                for _ in range(3):
-                    a = sm.clone(); cx.upload(a); torch.cuda.synchronize()
-                    t0 = time.perf_counter(); ob = cx.write_hry(a, profile=pid); cx.read_hry(ob); ts.append(time.perf_counter() - t0)
-                line["sharded"]["one_gpu_same_shape_mtri_s"] = round(share.ntri / min(ts[1:]) / 1e6, 3)
-                line["sharded"]["weak_scaling_efficiency_vs_same_shape"] = round(value / (world * line["sharded"]["one_gpu_same_shape_mtri_s"]), 4)
-                del sm, share
-                # ... and the SAME mesh (all N x 128 components) through this one context: what N devices are to be compared with
-                ts = []
-                for _ in range(2):
-                    a = whole.clone(); cx.upload(a); torch.cuda.synchronize()
-                    t0 = time.perf_counter(); ob = cx.write_hry(a, profile=pid, as_buffer=True); cx.read_hry(ob); ts.append(time.perf_counter() - t0)
-                line["sharded"]["one_context_same_mesh_mtri_s"] = round(ntri / ts[-1] / 1e6, 3)
-                line["sharded"]["efficiency_vs_one_context"] = round(value / (world * line["sharded"]["one_context_same_mesh_mtri_s"]), 4)
-                line["sharded"]["speedup_vs_one_context"] = round(value / line["sharded"]["one_context_same_mesh_mtri_s"], 3)
-                line["n1_same_workload_value"] = line["sharded"]["one_context_same_mesh_mtri_s"]
-                line["n1_same_workload_note"] = ("the SAME mesh (all N x components) through ONE context on rank 0's GPU, unsharded, inputs resident, encode + decode: "
-                                                 "read this line's scaling against it -- N = 1 of this benchmark is configs[1], another workload")
-            except Exception as exc:
-                sys.stderr.write(f"same-shape single-GPU leg failed: {exc}\n")
-        # end to end, as the `harry in.ply out.hry -l1 -q14` / `harry out.hry back.ply` command lines see it: PLY bytes ->
-        # parse + twin matching -> upload -> quantisation -> .hry bytes, and .hry bytes -> mesh -> binary PLY bytes.  Outside the timed
-        # region; not part of `value`.
-        try:
-            if world != 1:
-                raise RuntimeError("skipped on multi-GPU runs (rank 0 only work would hold the other ranks at shutdown)")
-            ply_bytes = mesh.to_ply()
-            e2e_e, e2e_d = [], []
-            for _ in range(3):
-                t0 = time.perf_counter()
-                mm = hc.Mesh.from_ply(ply_bytes)
-                cx.requant(mm, quant)
-                hb = cx.write_hry(mm, profile=pid)
-                t1 = time.perf_counter()
-                back = cx.read_hry(hb).to_ply() if can_decode else b""
-                t2 = time.perf_counter()
-                e2e_e.append(t1 - t0); e2e_d.append(t2 - t1)
-            line["end_to_end"] = {"encode_ms": round(float(np.median(e2e_e)) * 1e3, 3), "decode_ms": round(float(np.median(e2e_d)) * 1e3, 3),
-                                  "encode_mtri_s": round(ntri / float(np.median(e2e_e)) / 1e6, 3),
-                                  "decode_mtri_s": round(ntri / float(np.median(e2e_d)) / 1e6, 3) if can_decode else None,
-                                  "ply_bytes": len(ply_bytes), "what": "PLY bytes -> .hry bytes (parse, twin matching, upload, quantisation, encode); .hry bytes -> PLY bytes"}
-        except Exception as exc:
-            if world == 1:
-                sys.stderr.write(f"end-to-end leg failed: {exc}\n")
-        if world == 1:
-            # the reference's "encode" starts from a host mesh (main.cc:104-117): the same step with the upload inside
-            try:
-                ts = []
-                for _ in range(4):
-                    m = raw.clone()
-                    t0 = time.perf_counter()
-                    cx.requant(m, quant)                 # uploads the records + connectivity first
-                    cx.write_hry(m, profile=pid)
-                    ts.append(time.perf_counter() - t0)
-                line["encode_from_host_mtri_s"] = round(ntri / float(np.median(ts[1:])) / 1e6, 4)
-                line["encode_from_host_ms"] = round(float(np.median(ts[1:])) * 1e3, 3)
-            except Exception as exc:
-                sys.stderr.write(f"encode-from-host leg failed: {exc}\n")
-        if world == 1 and not args.no_large and args.side == 708:
-            for name, leg in (("cfg3", cfg3_leg), ("cfg4_share", cfg4_share_leg), ("cfg4_end_to_end", cfg4_end_to_end_leg), ("cfg4_full", cfg4_full_leg)):
+            if args.full:
+                # the same workload through ONE context, unsharded (rank 0's GPU): what the driver's per-N efficiency should be read against,
+                # since N = 1 of this benchmark is configs[1], another workload
                 try:
-                    line[name] = leg(cx)
+                    share = build_cfg4(1, args.comps_per_gpu)
+                    sm = hc.Mesh.from_arrays(share.verts, share.degrees, share.indices)
+                    ts = []
+                    for _ in range(3):
+                        a = sm.clone(); cx.upload(a); torch.cuda.synchronize()
+                        t0 = time.perf_counter(); ob = cx.write_hry(a, profile=pid); cx.read_hry(ob); ts.append(time.perf_counter() - t0)
+                    line["sharded"]["one_gpu_same_shape_mtri_s"] = round(share.ntri / min(ts[1:]) / 1e6, 3)
+                    line["sharded"]["weak_scaling_efficiency_vs_same_shape"] = round(value / (world * line["sharded"]["one_gpu_same_shape_mtri_s"]), 4)
+                    del sm, share
+                    # ... and the SAME mesh (all N x 128 components) through this one context: what N devices are to be compared with
+                    ts = []
+                    for _ in range(2):
+                        a = whole.clone(); cx.upload(a); torch.cuda.synchronize()
+                        t0 = time.perf_counter(); ob = cx.write_hry(a, profile=pid, as_buffer=True); cx.read_hry(ob); ts.append(time.perf_counter() - t0)
+                    line["sharded"]["one_context_same_mesh_mtri_s"] = round(ntri / ts[-1] / 1e6, 3)
+                    line["sharded"]["efficiency_vs_one_context"] = round(value / (world * line["sharded"]["one_context_same_mesh_mtri_s"]), 4)
+                    line["sharded"]["speedup_vs_one_context"] = round(value / line["sharded"]["one_context_same_mesh_mtri_s"], 3)
+                    line["n1_same_workload_value"] = line["sharded"]["one_context_same_mesh_mtri_s"]
+                    line["n1_same_workload_note"] = ("the SAME mesh (all N x components) through ONE context on rank 0's GPU, unsharded, inputs resident, encode + decode: "
+                                                     "read this line's scaling against it -- N = 1 of this benchmark is configs[1], another workload")
                 except Exception as exc:
-                    sys.stderr.write(f"{name} leg failed: {exc}\n")
-        if not args.no_cpu_baseline and world == 1:
-            cb, ref_hry = cpu_baseline(mesh, quant, budget_s=8.0)
-            ref = cpu_baseline_reference(mesh, budget_s=12.0)
-            if ref is not None:
-                line["cpu_baseline"] = ref            # the reference itself
-                line["cpu_baseline_port"] = cb        # the oracle (CPU restatement) in memory, same workload
-                line["reference_bytes_equal_port"] = bool(ref["hry_bytes"] == len(ref_hry))
-            else:
-                line["cpu_baseline"] = cb
-            line["bits_per_vertex_cpu_ref"] = round(8 * len(ref_hry) / base.nv, 4)
-            if profile == "compat":
-                line["byte_identical_to_cpu_ref"] = bool(out == ref_hry)
-            # the drop-in number next to the headline: the reference's own single stream (compat profile, .hry v0.1) from the same
-            # resident mesh -- byte-identical to the CPU reference's file, the serial range recurrence on a host core behind the kernels
+                    sys.stderr.write(f"same-shape single-GPU leg failed: {exc}\n")
+        if args.full:
+            # end to end, as the `harry in.ply out.hry -l1 -q14` / `harry out.hry back.ply` command lines see it: PLY bytes ->
+            # parse + twin matching -> upload -> quantisation -> .hry bytes, and .hry bytes -> mesh -> binary PLY bytes.  Outside the timed
+            # region; not part of `value`.
             try:
-                ts, tds, cb_out, tms = [], [], b"", []
-                for _ in range(1 + 3):
-                    m = raw.clone()
-                    cx.upload(m)
-                    torch.cuda.synchronize()
+                if world != 1:
+                    raise RuntimeError("skipped on multi-GPU runs (rank 0 only work would hold the other ranks at shutdown)")
+                ply_bytes = mesh.to_ply()
+                e2e_e, e2e_d = [], []
+                for _ in range(3):
                     t0 = time.perf_counter()
-                    cx.requant(m, quant)
-                    cb_out = cx.write_hry(m, profile=hc.PROFILE_COMPAT)
-                    ts.append(time.perf_counter() - t0)
-                    tms.append(cx.timing())
-                    t0 = time.perf_counter()
-                    cx.read_hry(cb_out)
-                    tds.append(time.perf_counter() - t0)
-                t_c, t_d = float(np.median(ts[1:])), float(np.median(tds[1:]))
-                line["compat"] = {"encode_mtri_s": round(ntri / t_c / 1e6, 4), "encode_ms": round(t_c * 1e3, 3), "hry_bytes": len(cb_out),
-                                  "decode_mtri_s": round(ntri / t_d / 1e6, 4), "decode_ms": round(t_d * 1e3, 3),
-                                  "value": round(ntri / (t_c + t_d) / 1e6, 4),
-                                  "vs_reference_binary_decode": round(ntri / t_d / 1e6 / line["cpu_baseline"]["decode_mtri_s"], 3) if line["cpu_baseline"].get("decode_mtri_s") else None,
-                                  "byte_identical_to_cpu_ref": bool(cb_out == ref_hry),
-                                  "vs_reference_binary_encode": round(ntri / t_c / 1e6 / line["cpu_baseline"]["encode_mtri_s"], 3),
-                                  "stage_ms": {k: round(float(np.median([t[k] for t in tms[1:]])), 3) for k in ("host_walk_ms", "k_predict_ms", "k_model_ms", "k_rchain_ms", "device_ms", "total_ms")},
-                                  "what": "quantisation + .hry v0.1 from the resident mesh; k_rchain_ms = the serial recurrence (host core, streamed behind the kernels)"}
+                    mm = hc.Mesh.from_ply(ply_bytes)
+                    cx.requant(mm, quant)
+                    hb = cx.write_hry(mm, profile=pid)
+                    t1 = time.perf_counter()
+                    back = cx.read_hry(hb).to_ply() if can_decode else b""
+                    t2 = time.perf_counter()
+                    e2e_e.append(t1 - t0); e2e_d.append(t2 - t1)
+                line["end_to_end"] = {"encode_ms": round(float(np.median(e2e_e)) * 1e3, 3), "decode_ms": round(float(np.median(e2e_d)) * 1e3, 3),
+                                      "encode_mtri_s": round(ntri / float(np.median(e2e_e)) / 1e6, 3),
+                                      "decode_mtri_s": round(ntri / float(np.median(e2e_d)) / 1e6, 3) if can_decode else None,
+                                      "ply_bytes": len(ply_bytes), "what": "PLY bytes -> .hry bytes (parse, twin matching, upload, quantisation, encode); .hry bytes -> PLY bytes"}
             except Exception as exc:
-                sys.stderr.write(f"compat leg failed: {exc}\n")
-            # SURVEY.md section 8 row f3 next to it: an OBJ scene (positions per vertex, texture coordinates and normals per corner,
-            # shared between corners) through the same reference stream; checked against the oracle, timed beside the reference binary
-            try:
-                line["obj"] = obj_leg(cx)
-            except Exception as exc:
-                sys.stderr.write(f"obj leg failed: {exc}\n")
-        if world == 1 and "cfg4_full" in line:
-            line["cfg4_full"] = line.pop("cfg4_full")     # (the named size last before the digest)
-        if world > 1:
-            # with the other ranks idle (they wait on the host-side barrier below): the same mesh through the in-process executor
-            # over all N devices -- ONE process, plan + upload inside the timed call (rehearsal: the contexts share device 0 too)
-            try:
-                line["inprocess"] = inprocess_leg(hc, whole, [0] * world if share_gpu else list(range(world)), quant, mesh.ntri, reps=2 if share_gpu else 3)
-            except Exception as exc:
-                sys.stderr.write(f"in-process leg failed: {exc}\n")
-            if not args.no_cpu_baseline:
-                cb = cpu_baseline_cfg4_sample(min(12, args.comps_per_gpu * world))
-                if cb is not None:
+                if world == 1:
+                    sys.stderr.write(f"end-to-end leg failed: {exc}\n")
+            if world == 1:
+                # the reference's "encode" starts from a host mesh (main.cc:104-117): the same step with the upload inside
+                try:
+                    ts = []
+                    for _ in range(4):
+                        m = raw.clone()
+                        t0 = time.perf_counter()
+                        cx.requant(m, quant)                 # uploads the records + connectivity first
+                        cx.write_hry(m, profile=pid)
+                        ts.append(time.perf_counter() - t0)
+                    line["encode_from_host_mtri_s"] = round(ntri / float(np.median(ts[1:])) / 1e6, 4)
+                    line["encode_from_host_ms"] = round(float(np.median(ts[1:])) * 1e3, 3)
+                except Exception as exc:
+                    sys.stderr.write(f"encode-from-host leg failed: {exc}\n")
+            if world == 1 and not args.no_large and args.side == 708:
+                for name, leg in (("cfg3", cfg3_leg), ("cfg4_share", cfg4_share_leg), ("cfg4_end_to_end", cfg4_end_to_end_leg), ("cfg4_full", cfg4_full_leg)):
+                    try:
+                        line[name] = leg(cx)
+                    except Exception as exc:
+                        sys.stderr.write(f"{name} leg failed: {exc}\n")
+            if not args.no_cpu_baseline and world == 1:
+                cb, ref_hry = cpu_baseline(mesh, quant, budget_s=8.0)
+                ref = cpu_baseline_reference(mesh, budget_s=12.0)
+                if ref is not None:
+                    line["cpu_baseline"] = ref            # the reference itself
+                    line["cpu_baseline_port"] = cb        # the oracle (CPU restatement) in memory, same workload
+                    line["reference_bytes_equal_port"] = bool(ref["hry_bytes"] == len(ref_hry))
+                else:
                     line["cpu_baseline"] = cb
+                line["bits_per_vertex_cpu_ref"] = round(8 * len(ref_hry) / base.nv, 4)
+                if profile == "compat":
+                    line["byte_identical_to_cpu_ref"] = bool(out == ref_hry)
+                # the drop-in number next to the headline: the reference's own single stream (compat profile, .hry v0.1) from the same
+                # resident mesh -- byte-identical to the CPU reference's file, the serial range recurrence on a host core behind the kernels
+                try:
+                    ts, tds, cb_out, tms = [], [], b"", []
+                    for _ in range(1 + 3):
+                        m = raw.clone()
+                        cx.upload(m)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        cx.requant(m, quant)
+                        cb_out = cx.write_hry(m, profile=hc.PROFILE_COMPAT)
+                        ts.append(time.perf_counter() - t0)
+                        tms.append(cx.timing())
+                        t0 = time.perf_counter()
+                        cx.read_hry(cb_out)
+                        tds.append(time.perf_counter() - t0)
+                    t_c, t_d = float(np.median(ts[1:])), float(np.median(tds[1:]))
+                    line["compat"] = {"encode_mtri_s": round(ntri / t_c / 1e6, 4), "encode_ms": round(t_c * 1e3, 3), "hry_bytes": len(cb_out),
+                                      "decode_mtri_s": round(ntri / t_d / 1e6, 4), "decode_ms": round(t_d * 1e3, 3),
+                                      "value": round(ntri / (t_c + t_d) / 1e6, 4),
+                                      "vs_reference_binary_decode": round(ntri / t_d / 1e6 / line["cpu_baseline"]["decode_mtri_s"], 3) if line["cpu_baseline"].get("decode_mtri_s") else None,
+                                      "byte_identical_to_cpu_ref": bool(cb_out == ref_hry),
+                                      "vs_reference_binary_encode": round(ntri / t_c / 1e6 / line["cpu_baseline"]["encode_mtri_s"], 3),
+                                      "stage_ms": {k: round(float(np.median([t[k] for t in tms[1:]])), 3) for k in ("host_walk_ms", "k_predict_ms", "k_model_ms", "k_rchain_ms", "device_ms", "total_ms")},
+                                      "what": "quantisation + .hry v0.1 from the resident mesh; k_rchain_ms = the serial recurrence (host core, streamed behind the kernels)"}
+                except Exception as exc:
+                    sys.stderr.write(f"compat leg failed: {exc}\n")
+                # SURVEY.md section 8 row f3 next to it: an OBJ scene (positions per vertex, texture coordinates and normals per corner,
+                # shared between corners) through the same reference stream; checked against the oracle, timed beside the reference binary
+                try:
+                    line["obj"] = obj_leg(cx)
+                except Exception as exc:
+                    sys.stderr.write(f"obj leg failed: {exc}\n")
+            if world == 1 and "cfg4_full" in line:
+                line["cfg4_full"] = line.pop("cfg4_full")     # (the named size last before the digest)
+            if world > 1:
+                # with the other ranks idle (they wait on the host-side barrier below): the same mesh through the in-process executor
+                # over all N devices -- ONE process, plan + upload inside the timed call (rehearsal: the contexts share device 0 too)
+                try:
+                    line["inprocess"] = inprocess_leg(hc, whole, [0] * world if share_gpu else list(range(world)), quant, mesh.ntri, reps=2 if share_gpu else 3)
+                except Exception as exc:
+                    sys.stderr.write(f"in-process leg failed: {exc}\n")
+                if not args.no_cpu_baseline:
+                    cb = cpu_baseline_cfg4_sample(min(12, args.comps_per_gpu * world))
+                    if cb is not None:
+                        line["cpu_baseline"] = cb
         emit(line)
     cx.close()
     if world > 1:
@@ -772,6 +788,49 @@ def emit(line):
     sys.stdout.flush()
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: the arrays' data in all (under 64 MB with the .npy headers)
+
+
+def step_outputs(container, dec):
+    """What a caller of the timed path receives from one step: the .hry container (one value per byte) and, where the step
+    decodes, the decoded mesh -- connectivity and the records of every list, one column per component."""
+    data = container.view() if hasattr(container, "view") else container
+    arrays = {"hry": np.frombuffer(data, dtype=np.uint8)}
+    if dec is not None:
+        arrays["decoded_face_offsets"] = dec.face_offsets()
+        arrays["decoded_org"] = dec.org()
+        arrays["decoded_twin"] = dec.twin()
+        for l, name in ((1, "decoded_vertex_records"), (0, "decoded_face_records")):
+            if dec.list_count(l) and dec.list_fmt(l):
+                cols = [dec.component(l, c) for c in range(len(dec.list_fmt(l)))]
+                exact32 = all(_exact_in_float32(c) for c in cols)
+                arrays[name] = np.stack([c.astype(np.float32 if exact32 else np.float64) for c in cols], axis=1)
+    return arrays
+
+
+def _exact_in_float32(a):
+    if a.dtype == np.float32 or (a.dtype.kind in "iu" and a.itemsize <= 2):
+        return True
+    if a.dtype.kind in "iu":
+        return a.size == 0 or (int(a.max()) < 2**24 and int(a.min()) > -2**24)
+    return False
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy, float32 where every value is exact in it, float64 otherwise.  Beyond
+    DUMP_BYTES in all, every array keeps the same fixed, seeded sample of its rows (in their order)."""
+    os.makedirs(directory, exist_ok=True)
+    types = {k: np.float32 if _exact_in_float32(a) else np.float64 for k, a in arrays.items()}
+    total = sum(a.size * np.dtype(types[k]).itemsize for k, a in arrays.items())
+    keep = DUMP_BYTES / total if total > DUMP_BYTES else 1.0
+    for k, a in arrays.items():
+        if keep < 1.0 and len(a) > 1:
+            rows = np.unique(np.random.default_rng(0).integers(0, len(a), max(1, int(len(a) * keep))))
+            a = a[rows]
+            sys.stderr.write(f"--dump-outputs: {k}: {len(rows)} rows of {len(arrays[k])} (numpy default_rng(0))\n")
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a, dtype=types[k]))
+
+
 def inprocess_leg(hc, whole, devices, quant, ntri, reps=3):
     """ONE process, one context per entry of `devices`: the whole job from the host mesh (hry_encode_sharded: plan, extract,
     upload, bounds, quantisation, encode, merge) and back (hry_decode_sharded: every segment on its device, one mesh out)"""
@@ -846,6 +905,8 @@ def inprocess_main(args):
         k_chain.append(max(t["k_chain_ms"] for t in tim_d)); k_entropy.append(max(t["k_entropy_ms"] for t in tim_e)); k_dentropy.append(max(t["k_entropy_ms"] for t in tim_d))
         per_ctx.append([(e["host_walk_ms"], e["k_entropy_ms"], d["host_walk_ms"], d["k_chain_ms"], d["k_entropy_ms"]) for e, d in zip(tim_e, tim_d)])
     t_all = time.perf_counter() - t_begin
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(merged, dec))
     medk = lambda L, k: round(float(np.median([x[k] for x in L])), 2)
     value = ntri * args.steps / t_all / 1e6
     # dominant kernel: the measured maximum over the step's kernels (HIP events inside the library, the slowest context's); algorithmic
@@ -858,33 +919,35 @@ def inprocess_main(args):
             "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(dom_ms, 4),
             "note": "per context: its share of the mesh, its own launches (k_unpredict2<float>: summed over the batches of a decode; k_chunk_decode: both decoder kernels' launches)"}
     roof["frac"] = round(roof["achieved"] / HBM_PEAK_GBS, 6) if roof["achieved"] else None
-    # check: the merged container decodes like the single-context path on the whole mesh
+    # check (--full): the merged container decodes like the single-context path on the whole mesh
     ok = None
-    try:
-        cx = hc.Codec(devices[0])
-        ref = cx.read_hry(cx.write_hry(whole.clone(), profile=hc.PROFILE_CHUNKED))
-        ok = bool(np.array_equal(dec.face_offsets(), ref.face_offsets()) and np.array_equal(dec.org(), ref.org()) and np.array_equal(dec.twin(), ref.twin())
-                  and np.array_equal(dec.list_data(1), ref.list_data(1)))
-        cx.close()
-    except Exception as exc:
-        sys.stderr.write(f"merged-container check failed: {exc}\n")
-        ok = False
+    if args.full:
+        try:
+            cx = hc.Codec(devices[0])
+            ref = cx.read_hry(cx.write_hry(whole.clone(), profile=hc.PROFILE_CHUNKED))
+            ok = bool(np.array_equal(dec.face_offsets(), ref.face_offsets()) and np.array_equal(dec.org(), ref.org()) and np.array_equal(dec.twin(), ref.twin())
+                      and np.array_equal(dec.list_data(1), ref.list_data(1)))
+            cx.close()
+        except Exception as exc:
+            sys.stderr.write(f"merged-container check failed: {exc}\n")
+            ok = False
     # every context's own numbers (medians over the steps): the record shows that N devices worked
     pc = np.median(np.array(per_ctx, dtype=np.float64), axis=0)
     contexts = [{"context": i, "device": int(devices[i]), "encode_host_walk_ms": round(float(pc[i][0]), 2), "k_chunk_encode_ms": round(float(pc[i][1]), 3),
                  "decode_host_replay_ms": round(float(pc[i][2]), 2), "k_unpredict2_float_ms": round(float(pc[i][3]), 3), "k_chunk_decode_ms": round(float(pc[i][4]), 3)} for i in range(world)]
-    # the same mesh through ONE context on the first device: what the N contexts are to be compared with
+    # the same mesh through ONE context on the first device (--full): what the N contexts are to be compared with
     one_ctx = None
-    try:
-        cx1 = hc.Codec(devices[0])
-        ts = []
-        for _ in range(2):
-            a = whole.clone()
-            t0 = time.perf_counter(); ob = cx1.write_hry(a, profile=hc.PROFILE_CHUNKED, as_buffer=True); t1 = time.perf_counter(); cx1.read_hry(ob); ts.append((t1 - t0, time.perf_counter() - t1))
-        cx1.close()
-        one_ctx = {"value": round(ntri / sum(ts[-1]) / 1e6, 3), "encode_from_host_mtri_s": round(ntri / ts[-1][0] / 1e6, 3), "decode_mtri_s": round(ntri / ts[-1][1] / 1e6, 3)}
-    except Exception as exc:
-        sys.stderr.write(f"one-context leg failed: {exc}\n")
+    if args.full:
+        try:
+            cx1 = hc.Codec(devices[0])
+            ts = []
+            for _ in range(2):
+                a = whole.clone()
+                t0 = time.perf_counter(); ob = cx1.write_hry(a, profile=hc.PROFILE_CHUNKED, as_buffer=True); t1 = time.perf_counter(); cx1.read_hry(ob); ts.append((t1 - t0, time.perf_counter() - t1))
+            cx1.close()
+            one_ctx = {"value": round(ntri / sum(ts[-1]) / 1e6, 3), "encode_from_host_mtri_s": round(ntri / ts[-1][0] / 1e6, 3), "decode_mtri_s": round(ntri / ts[-1][1] / 1e6, 3)}
+        except Exception as exc:
+            sys.stderr.write(f"one-context leg failed: {exc}\n")
     line = {"metric": "Mtriangles/s encode+decode", "value": round(value, 4), "unit": "Mtriangles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(t_all / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "mode": "in-process (--inprocess; NOT the default for N > 1): ONE process, one worker thread + device context per GPU (hry_encode_sharded / hry_decode_sharded); no torch.distributed, no collective -- rccl_ranks 0",
@@ -912,7 +975,7 @@ def inprocess_main(args):
                         "groups": int(te_l[-1]["n_groups"]), "merged_decode_equals_single_gpu": ok, "collectives": "none: the segments meet in host memory"}}
     if ok is False:
         line["error"] = "merged container does not decode to the single-GPU result"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cb = cpu_baseline_cfg4_sample(min(12, args.comps_per_gpu * world))
         if cb is not None:
             line["cpu_baseline"] = cb

@@ -13,10 +13,10 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py > $OUT/chunked_bench.json 2> $OUT/chunked_bench.err
-python3 $ROOT/bench.py --profile compat --steps 2 --warmup 1 --no-large > $OUT/compat_bench.json 2> $OUT/compat_bench.err
+python3 $ROOT/bench.py --full > $OUT/chunked_bench.json 2> $OUT/chunked_bench.err
+python3 $ROOT/bench.py --full --profile compat --steps 2 --warmup 1 --no-large > $OUT/compat_bench.json 2> $OUT/compat_bench.err
 mkdir -p $OUT/bench
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench/kstats -- python3 $ROOT/bench.py --no-cpu-baseline --no-large > $OUT/bench/kstats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench/kstats -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-large > $OUT/bench/kstats.log 2>&1
 leg() {
 	name=$1; shift
 	mkdir -p $OUT/$name
@@ -65,8 +65,8 @@ python3 $ROOT/scripts/obj_time.py 300 12 > $OUT/obj_time_12bits.txt 2>&1
 mkdir -p $OUT/obj
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/obj/kstats -- python3 $ROOT/scripts/obj_time.py 300 > $OUT/obj/kstats.log 2>&1
 # both bench modes rehearsed with ranks / contexts sharing this box's one GPU (code paths, not measurements)
-python3 $ROOT/bench.py --gpus 2 --inprocess --share-device --comps-per-gpu 16 --steps 3 --warmup 1 > $OUT/rehearsal_inprocess_2ctx_one_gpu.json 2> $OUT/rehearsal_inprocess.err
-python3 $ROOT/bench.py --gpus 2 --share-device --comps-per-gpu 16 --steps 2 --warmup 1 2> $OUT/rehearsal_ranks.err | grep '^{' > $OUT/rehearsal_2ranks_one_gpu.json
+python3 $ROOT/bench.py --full --gpus 2 --inprocess --share-device --comps-per-gpu 16 --steps 3 --warmup 1 > $OUT/rehearsal_inprocess_2ctx_one_gpu.json 2> $OUT/rehearsal_inprocess.err
+python3 $ROOT/bench.py --full --gpus 2 --share-device --comps-per-gpu 16 --steps 2 --warmup 1 2> $OUT/rehearsal_ranks.err | grep '^{' > $OUT/rehearsal_2ranks_one_gpu.json
 cd $ROOT
 # passes of the workload per run (what traffic.json divides by): quick_chunked 3 encode + decode; float_chain_time 1 encode + 4
 # decodes (divide by the decodes: the decode kernels are the subject); cfg4_check 2; cfg0_time 3 per profile

@@ -5,7 +5,7 @@ import json, os, subprocess, sys, threading, time
 import psutil
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 n = int(sys.argv[1]); comps = int(sys.argv[2]) if len(sys.argv) > 2 else 128; steps = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--share-device", "--comps-per-gpu", str(comps), "--steps", str(steps), "--warmup", "1"]
+cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(n), "--share-device", "--comps-per-gpu", str(comps), "--steps", str(steps), "--warmup", "1"]
 t0 = time.time()
 p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root)
 peak = {"sum_rss": 0, "max_one": 0, "n_procs": 0}

@@ -7,7 +7,6 @@ so these reference-generated vectors are the pin.  CPU only.
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -162,22 +161,22 @@ def test_kat_range_coder_32bit_registers(kat):
         assert op.range_encode_lht(np.array(triples, dtype=np.uint64), bits=32) == bytes.fromhex(code)
 
 
-# ---------------------------------------------------------------- live reference (where its binary exists)
-@pytest.mark.skipif(not os.path.exists(util.REF_BIN), reason="reference binary not built (oracle/_ref)")
+# ---------------------------------------------------------------- the reference on seeded random meshes
+@pytest.fixture(scope="module")
+def random_answers(golden_dir):
+    with open(os.path.join(golden_dir, "random.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("seed", range(4))
-def test_live_reference_random_meshes(tmp_path, seed):
-    rng = np.random.default_rng(100 + seed)
-    nu, nv = int(rng.integers(6, 40)), int(rng.integers(3, 20)) * 2
-    polys = ["tri", "quad", "mixed"][seed % 3]
-    m = mg.torus(nu, nv, seed=seed, polys=polys, normals=bool(seed & 1))
-    if seed == 3:
-        m = mg.with_nonmanifold(mg.concat([m, mg.torus(7, 8, seed=9, polys=polys, normals=bool(seed & 1), center=(5, 0, 0))]), 4, 3)
-    ply = m.to_ply()
-    p = tmp_path / "in.ply"
-    p.write_bytes(ply)
-    for flags in ([], ["-l1", f"-q{int(rng.integers(2, 17))}"]):
-        out = tmp_path / "out.hry"
-        subprocess.run([util.REF_BIN, str(p), str(out)] + flags, check=True, capture_output=True)
-        quant, clear = util.flags_to_quant(flags)
+def test_live_reference_random_meshes(random_answers, seed):
+    """beyond the fixed fixtures: seeded random meshes (tests/util.py: random_ply_case), the oracle's bytes against what the
+    unmodified reference binary wrote from the same input (tests/golden/random.json, by tests/golden/make_golden_random.py)"""
+    ply, variants = util.random_ply_case(seed)
+    e = random_answers["ply"][str(seed)]
+    assert hashlib.sha256(ply).hexdigest() == e["ply_sha256"], "the seeded input is not the one the reference answered (make_golden_random.py)"
+    assert [v["flags"] for v in e["variants"]] == variants
+    for v in e["variants"]:
+        quant, clear = util.flags_to_quant(v["flags"])
         _, res = op.encode_ply(ply, quant, clear)
-        assert res.data == out.read_bytes(), (seed, flags)
+        assert (len(res.data), hashlib.sha256(res.data).hexdigest()) == (v["hry_bytes"], v["hry_sha256"]), (seed, v["flags"])

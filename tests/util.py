@@ -88,6 +88,45 @@ def canonical_faces(vrec: np.ndarray, degs: np.ndarray, idx: np.ndarray):
     return out
 
 
+def random_ply_case(seed: int):
+    """Seeded random PLY input beyond the committed fixtures: (PLY bytes, the two flag sets it is encoded with).  The reference's
+    answers on these inputs are recorded in tests/golden/random.json (tests/golden/make_golden_random.py)."""
+    from harry_amd import meshgen as mg
+    rng = np.random.default_rng(100 + seed)
+    nu, nv = int(rng.integers(6, 40)), int(rng.integers(3, 20)) * 2
+    polys = ["tri", "quad", "mixed"][seed % 3]
+    m = mg.torus(nu, nv, seed=seed, polys=polys, normals=bool(seed & 1))
+    if seed == 3:
+        m = mg.with_nonmanifold(mg.concat([m, mg.torus(7, 8, seed=9, polys=polys, normals=bool(seed & 1), center=(5, 0, 0))]), 4, 3)
+    return m.to_ply(), [[], ["-l1", f"-q{int(rng.integers(2, 17))}"]]
+
+
+def random_scene_cases():
+    """Seeded random OBJ scenes and PLY meshes beyond the committed fixtures: yields (file name, source bytes, flags).  The
+    reference's answers on these inputs are recorded in tests/golden/random.json (tests/golden/make_golden_random.py)."""
+    from harry_amd import meshgen as mg
+    from harry_amd import objgen as og
+    rng = np.random.default_rng(23)
+    for it in range(16):
+        polys = ["tri", "quad", "mixed"][int(rng.integers(0, 3))]
+        base = [lambda: mg.torus(int(rng.integers(5, 22)), int(rng.integers(5, 22)), polys=polys, seed=int(rng.integers(1, 99))),
+                lambda: mg.icosphere(int(rng.integers(1, 4))),
+                lambda: mg.with_nonmanifold(mg.multi_component(int(rng.integers(2, 5)), 8, 9, polys=polys), int(rng.integers(1, 5)), int(rng.integers(1, 3)), seed=int(rng.integers(1, 99)))][int(rng.integers(0, 3))]()
+        flags = []
+        if it % 2 == 0:
+            sc = og.scene(base, normals=[None, "smooth", "flat"][int(rng.integers(0, 3))], tex=[None, "atlas", "corner"][int(rng.integers(0, 3))],
+                          charts=int(rng.integers(1, 7)), colors=[None, "all", "some"][int(rng.integers(0, 3))], tex3=bool(rng.integers(0, 2)),
+                          interleave=bool(rng.integers(0, 2)), negative=bool(rng.integers(0, 2)), seed=int(rng.integers(1, 99)))
+            name, src = f"s{it}.obj", sc.obj
+            if rng.integers(0, 2):
+                flags = ["-l0", f"-q{int(rng.integers(6, 17))}"]
+        else:
+            name, src = f"s{it}.ply", base.to_ply(["binary_little_endian", "binary_big_endian", "ascii"][int(rng.integers(0, 3))])
+            if rng.integers(0, 2):
+                flags = ["-l1", f"-q{int(rng.integers(6, 17))}"]
+        yield name, src, flags
+
+
 def oracle_shard(shard, whole_oracle):
     """The CPU oracle's copy of a product shard (harry_amd.codec.Mesh from ShardPlan.extract): same elements in the same
     order (through PLY), the whole mesh's bounds and polygon degrees, the shard's seeds and runs."""
