@@ -30,6 +30,10 @@
 #include <vector>
 
 #include "../../../include/harry_amd.h"
+#include "../host/env.hpp"
+
+using hry::env_on;
+using hry::trace_on;
 
 namespace {
 
@@ -225,7 +229,7 @@ int run(const Args &args)
 		}
 	});
 	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{ ctx_thread };
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	auto contexts = [&] {
 		if (ctx_thread.joinable()) { ctx_thread.join(); if (trace) std::cerr << "[harry] " << since_start_ms() << " ms  contexts ready" << std::endl; }
 		if (!ctx_error.empty()) throw std::runtime_error(ctx_error);
@@ -310,7 +314,7 @@ int run(const Args &args)
 	// Everything is written.  Gigabytes of host arrays, the device contexts and the runtime itself would now be taken apart piece by
 	// piece (0.5 s for the configs[3] mesh) only for the process to end: it ends here instead, and the system takes it all back at
 	// once.  HRY_ORDERLY_EXIT=1 keeps the long way (leak checkers, tests of the destructors).
-	if (!getenv("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
+	if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 	return EXIT_SUCCESS;
 }
 
@@ -321,7 +325,7 @@ int main(int argc, const char **argv)
 	const Args args = parse(argc, argv);
 	try {
 		const int rc = run(args);
-		if (getenv("HRY_TRACE")) std::cerr << "[harry] " << since_start_ms() << " ms  handles released" << std::endl;
+		if (trace_on()) std::cerr << "[harry] " << since_start_ms() << " ms  handles released" << std::endl;
 		return rc;
 	} catch (const std::exception &e) {
 		// what the reference's uncaught exception prints through std::terminate, and the status abort() leaves

@@ -19,7 +19,7 @@ namespace hry {
 void device_component_analysis(Context &cx, const Mesh &m, ComponentAnalysis &A)
 {
 	HIP_OK(hipSetDevice(cx.device));
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	const auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) {
 		if (trace) fprintf(stderr, "[hry walk] %8.2f ms  (device) %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what);

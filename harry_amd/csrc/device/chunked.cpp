@@ -27,8 +27,6 @@ namespace hry {
 using namespace dev;
 typedef std::chrono::steady_clock Clock;
 static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-// HRY_TRACE=1: wall-clock marks of the encode on stderr (development aid; the decode's are in unchunk.cpp)
-static bool trace_on() { static const bool on = getenv("HRY_TRACE") != nullptr; return on; }
 #define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "[hry enc] %8.3f ms  %s\n", ms_since(t0), what); } while (0)
 
 void build_init_tables(const Mesh &m, std::vector<uint32_t> &tabs)
@@ -73,11 +71,9 @@ static uint32_t stream_words(uint32_t n, uint32_t t0)
 // sequential walk of the first component and the host's passes over the rest cost less than the launches and round trips
 static uint32_t device_analysis_min_faces()
 {
-	const char *e = getenv("HRY_DEVICE_ANALYSIS_MIN_FACES");   // (read per call: the tests change it)
-	return e ? (uint32_t)strtoul(e, nullptr, 10) : (4u << 20);
+	return (uint32_t)env_uint("HRY_DEVICE_ANALYSIS_MIN_FACES", 4u << 20);   // (read per call: the tests change it)
 }
 
-namespace dev { void launch_scatter_u32(hipStream_t st, const uint32_t *pairs, uint32_t n, uint32_t *dst); }
 
 // ---------------------------------------------------------------------------------------------------------
 // The device side of an encode BESIDE the walk (round 5).  A mesh of many components is walked on the host threads group by
@@ -144,16 +140,14 @@ struct EncodePipeline : WalkProgress {
 		if (registered[0] || registered[1] || registered[2]) (void)hipStreamSynchronize(cx.pipe_stream);   // (an error path: no copy may still read the arrays)
 		unregister_arrays();
 	}
-	static bool wanted() { const char *e = getenv("HRY_NO_ENCODE_PIPELINE"); return !(e && *e && *e != '0'); }
+	static bool wanted() { return !env_on("HRY_NO_ENCODE_PIPELINE"); }
 
 	void prepare_slots()
 	{
-		const char *e = getenv("HRY_ENCODE_PIPELINE_BATCH");   // vertices per batch at least (tests: 1)
-		min_batch = e ? strtoull(e, nullptr, 10) : std::max<uint64_t>(1u << 16, vc / 48);
-		const char *se = getenv("HRY_ENCODE_PIPELINE_SLOT");   // entries per gathered region (tests: small, so that groups outgrow it)
-		elems = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(se ? strtoull(se, nullptr, 10) : (1u << 18), 64), 2u << 20);
-		const char *de = getenv("HRY_ENCODE_PIPELINE_DIRECT");   // shortest run copied from where it lies (tests: 1 = every run, 0 = none)
-		if (de) direct_min = (uint32_t)strtoul(de, nullptr, 10);
+		min_batch = env_uint("HRY_ENCODE_PIPELINE_BATCH", std::max<uint64_t>(1u << 16, vc / 48));   // vertices per batch at least (tests: 1)
+		// entries per gathered region (tests: small, so that groups outgrow it)
+		elems = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_uint("HRY_ENCODE_PIPELINE_SLOT", 1u << 18), 64), 2u << 20);
+		direct_min = (uint32_t)env_uint("HRY_ENCODE_PIPELINE_DIRECT", direct_min);   // shortest run copied from where it lies (tests: 1 = every run, 0 = none)
 		if (direct_min == 0) direct_min = 0xffffffffu;
 		size_t at = 0;
 		for (int t = 0; t < kTables; ++t) { off_start[t] = at; at += kRuns + 2; off_first[t] = at; at += kRuns; }
@@ -609,8 +603,6 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		if (arrays_err) std::rethrow_exception(arrays_err);
 	};
 	if (in_place) {
-		if (in_place->before_walk) in_place->before_walk();   // (its turn among the executor's workers, and the turn's thread budget)
-		struct After { const std::function<void()> &f; ~After() { if (f) f(); } } after{ in_place->after_walk };
 		start_pipeline(*in_place->part, shard_arrays_ready);
 		cut_border_walk_in_place(*in_place->whole, *in_place->part, in_place->eface, *in_place->marks, w);
 		walked = true;
@@ -862,8 +854,8 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		uint32_t longest = 0;
 		for (uint32_t i = 0; i < ns; ++i) longest = std::max(longest, jobs[i].n);
 		const double one = std::max(longest * 0.09e-3, (double)nsym_total * 0.04e-6), two = longest * 0.207e-3 + (double)nsym_total * 0.0057e-6;   // ms
-		const char *e = getenv("HRY_ENCODE_SPLIT_MIN_STREAMS");
-		split_kernels = e ? (strtoul(e, nullptr, 10) != 0 && ns >= strtoul(e, nullptr, 10)) : (ns >= 64 && two < 0.9 * one);
+		const uint64_t min_streams = env_uint("HRY_ENCODE_SPLIT_MIN_STREAMS", ~0ull);   // (~0: unset)
+		split_kernels = min_streams != ~0ull ? min_streams != 0 && ns >= min_streams : ns >= 64 && two < 0.9 * one;
 	}
 	for (uint32_t i = 0; i < ns && split_kernels; ++i) split_kernels = (uint64_t)jobs[i].t0 + jobs[i].n <= 65535u;   // (its records hold 16-bit counts)
 	std::vector<uint64_t> tab;   // (lives until the stream is waited for below)

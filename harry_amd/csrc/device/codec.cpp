@@ -218,16 +218,14 @@ void check_codable(const Mesh &m)
 // memory and copies it out on the calling thread, 20 - 22 GB/s -- the rate of one core's memcpy, not of the link (292 MB of the
 // 100 M-triangle mesh's container: 13 - 14 ms).  Here the DMA writes a ring of pinned slots and helper threads copy finished slots
 // out while the next ones are in flight; this thread only issues copies and waits for their events (the helpers make no runtime
-// call).  Small results, or HRY_NO_STAGED_FETCH: the runtime's path.
+// call).  Small results: the runtime's path.
 void fetch_to_host(Context &cx, void *dst, const void *d_src, size_t bytes)
 {
-	static const bool off = getenv("HRY_NO_STAGED_FETCH") != nullptr;
-	static const size_t min_bytes = [] { const char *e = getenv("HRY_STAGED_FETCH_MIN"); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)48 << 20; }();
+	static const size_t min_bytes = env_uint("HRY_STAGED_FETCH_MIN", (size_t)48 << 20);
 	constexpr int kSlots = 8;
-	static const size_t slot_bytes = [] { const char *e = getenv("HRY_STAGED_FETCH_SLOT"); const size_t v = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)4 << 20; return v < 4096 ? (size_t)4096 : v; }();
-	static const unsigned max_helpers = [] { const char *e = getenv("HRY_STAGED_FETCH_THREADS"); const int v = e ? atoi(e) : 3; return (unsigned)(v < 1 ? 1 : v > 16 ? 16 : v); }();
-	const unsigned n_helpers = std::min(max_helpers, host_threads() > 1 ? host_threads() - 1 : 0u);
-	if (off || bytes < min_bytes || n_helpers == 0) {
+	static const size_t slot_bytes = std::max<size_t>(4096, env_uint("HRY_STAGED_FETCH_SLOT", (size_t)4 << 20));
+	const unsigned n_helpers = std::min(3u, host_threads() > 1 ? host_threads() - 1 : 0u);
+	if (bytes < min_bytes || n_helpers == 0) {
 		if (bytes) HIP_OK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, cx.stream));
 		HIP_OK(hipStreamSynchronize(cx.stream));
 		return;
@@ -456,7 +454,6 @@ dev::RequantPlan requant_plan(const AttrList &L, const std::vector<uint8_t> &to)
 
 uint64_t test_extra(const char *name) { const char *e = getenv(name); return e ? (uint64_t)strtoull(e, nullptr, 10) : 0ull; }
 
-namespace dev { void launch_scatter_u32(hipStream_t st, const uint32_t *pairs, uint32_t n, uint32_t *dst); }
 // A walk repairs a handful of twins (non-manifold edges, neighbours consumed from the other side) -- the whole array went up for
 // them: 1.2 GB for the configs[3] mesh.  Now the entries the walk names go up as (half-edge, twin) pairs and are scattered.
 // patches_only: `host` is a mesh other threads are walking other parts of (a shard coded in place) -- never the whole array,

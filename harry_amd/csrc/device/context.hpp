@@ -62,10 +62,10 @@ struct Context {
 	hipStream_t stream = nullptr;
 	hipStream_t stream2 = nullptr;   // uploads and connectivity-only kernels of the pipelined decode (created on first use)
 	hipStream_t stream3 = nullptr;   // attribute streams' entropy decode, next to the connectivity streams' (created on first use)
-	static constexpr int kUploadStreams = 3;
+	static constexpr int kUploadStreams = 2;
 	hipStream_t up_stream[kUploadStreams] = {};   // further uploaders of finished spans beside stream2 (unchunk.cpp: SpanUploader; created on first use)
 	hipEvent_t up_ev[kUploadStreams] = {};
-	hipEvent_t ev_x[3] = {};         // cross-stream ordering events (created with stream3)
+	hipEvent_t ev_x[2] = {};         // cross-stream ordering events (created with stream3)
 	hipEvent_t ev_payload = nullptr; // chunked decode: the attribute streams' part of a large payload is on the device (created with stream3)
 	// chunked decode: the attribute streams are launched in groups by how far into their plane they end (unchunk.cpp); group g
 	// runs on attr_stream[g] and raises attr_ev[g]
@@ -196,7 +196,6 @@ struct InPlaceShard {
 	const std::vector<std::pair<uint32_t, uint32_t>> *face_intervals;   // the shard's faces, as uploaded (repaired twins go up over the same intervals)
 	std::function<void()> arrays_ready;                              // called after the walk, before anything touches the device: returns when the
 	                                                                 // shard's intervals are in HBM (and quantised, if the caller quantises)
-	std::function<void()> before_walk, after_walk;                   // around the walk on the host threads (the executor takes the workers' walks in turn)
 };
 void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const InPlaceShard *in_place = nullptr);   // (bytes that are not zero-filled first and go to the caller as they are)
 void encode_general(Context &cx, Mesh &m, std::vector<uint8_t> &out);   // general.cpp: regions, shared records, corner lists (reference stream only)

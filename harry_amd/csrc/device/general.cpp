@@ -29,27 +29,6 @@ using namespace dev;
 typedef std::chrono::steady_clock Clock;
 static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-namespace dev {
-void launch_face_rank(hipStream_t st, const ConnView &cv, const uint32_t *order_f, uint32_t n, uint32_t *frank);
-void launch_gen_vtx_resid(hipStream_t st, const ConnView &cv, const GenView &gv, const uint32_t *rank, const uint32_t *ev_he, const uint8_t *ev_slot,
-                          const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
-void launch_gen_face_resid(hipStream_t st, const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
-void launch_gen_corner_resid(hipStream_t st, const ConnView &cv, const GenView &gv, const uint32_t *frank, const uint32_t *ev_he, const uint8_t *ev_slot,
-                             const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
-constexpr int kSrcCap = 24;   // general.hip
-struct GenChainJob {
-	int32_t kind, comp;
-	uint32_t n, pad2;
-	uint8_t *rec;
-	const uint32_t *src, *ev_he;
-	const uint8_t *nsrc, *ev_slot;
-	ListDesc ld;
-};
-void launch_gen_sources(hipStream_t st, int kind, const ConnView &cv, const GenView &gv, const uint32_t *rank, const uint32_t *ev_he, const uint8_t *ev_slot,
-                        uint32_t n, uint32_t *src, uint8_t *nsrc);
-void launch_gen_chain(hipStream_t st, int kind, int stype, const ConnView &cv, const GenView &gv, const uint32_t *rank, const GenChainJob *jobs, uint32_t njobs);
-void launch_faces_unfold(hipStream_t st, uint32_t n, const ListDesc &ld, uint8_t *rec);
-}
 bool reconstruct_vertex_list_fast(Context &cx, Mesh &m, int l, const OrderVec &order_v, const std::vector<uint32_t> &seg_start,
                                   const std::vector<uint32_t> &seg_level, const std::vector<uint8_t> &vplanes, const uint8_t *d_vplanes = nullptr);   // unchunk.cpp
 bool vertex_list_fast_applicable(const Mesh &m, int l, size_t n_order);                                                                             // unchunk.cpp
@@ -146,8 +125,6 @@ struct Arena {
 };
 
 }   // namespace
-
-void finish_stream(Context &cx, uint32_t ns, std::vector<uint8_t> &payload);
 
 void encode_general(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 {
@@ -456,7 +433,7 @@ Mesh *decode_general(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	std::vector<uint8_t> vplanes;
 	// one vertex region with one list (every OBJ whose "v" lines have the same number of values): candidate for the vertex chains
 	int fast_l = -1;
-	if (m->bind.nregs_vtx() == 1 && m->bind.nvtxlists(0) == 1 && !getenv("HRY_GENERIC_VERTEX")) fast_l = m->bind.vtxlist(0, 0);
+	if (m->bind.nregs_vtx() == 1 && m->bind.nvtxlists(0) == 1 && !env_on("HRY_GENERIC_VERTEX")) fast_l = m->bind.vtxlist(0, 0);
 	read_general_stream(p + hdr, n - hdr, *m, order_v, ev, seg_start, seg_level, fast_l, vplanes);
 	cx.timing.host_walk_ms = ms_since(t_walk);
 	double fast_ms = 0;
@@ -509,7 +486,7 @@ void general_planes_encode(Context &cx, Mesh &m, const WalkResult &w, std::vecto
 	ConnView cv = cx.conn_view();
 	const GenView gv = gen_view(cx, m);
 	const Bindings &b = m.bind;
-	static const bool host_events_env = getenv("HRY_HOST_EVENTS") != nullptr;
+	static const bool host_events_env = env_on("HRY_HOST_EVENTS");
 	bool host_events = host_events_env;
 	Events E;   // (the host's arrays live until the arena has been copied into pinned memory: Arena::send)
 again:
@@ -517,7 +494,7 @@ again:
 		const auto t_events = Clock::now();
 		collect_events(m, w, 0, false, E);
 		cx.timing.host_walk_ms += ms_since(t_events);   // (host bookkeeping along the coding order, like the walk: it was missing from the record)
-		if (getenv("HRY_TRACE")) fprintf(stderr, "[hry enc] %8.3f ms  which record every element names (host)\n", ms_since(t_events));
+		if (trace_on()) fprintf(stderr, "[hry enc] %8.3f ms  which record every element names (host)\n", ms_since(t_events));
 		Arena A;
 		struct At { size_t type_sym, gh_vals, gh, lh_vals, lh, d_idx, d_he, d_slot, planes; };
 		std::vector<At> at(nl);
@@ -667,7 +644,6 @@ again:
 	}
 }
 
-namespace dev { void launch_residuals_to_rec(hipStream_t st, const uint8_t *planes, uint32_t n, const ListDesc &ld, uint8_t *rec); }
 
 void general_planes_decode(Context &cx, Mesh &m, const OrderVec &order_v, const std::vector<uint32_t> &seg_start,
                            const std::vector<uint32_t> &seg_level, const uint8_t *d_syms, const std::vector<uint64_t> &plane_off,
@@ -711,7 +687,7 @@ void general_planes_decode(Context &cx, Mesh &m, const OrderVec &order_v, const 
 	// thread reads the planes.  Whether the list qualifies is known from the planes' lengths (one residual symbol in the list's first
 	// data plane per record coded as data).
 	int fast_l = -1;
-	if (m.bind.nregs_vtx() == 1 && m.bind.nvtxlists(0) == 1 && !getenv("HRY_GENERIC_VERTEX") && !order_v.empty()) {
+	if (m.bind.nregs_vtx() == 1 && m.bind.nvtxlists(0) == 1 && !env_on("HRY_GENERIC_VERTEX") && !order_v.empty()) {
 		const int l = m.bind.vtxlist(0, 0);
 		if (hp.lists[l].n_data == order_v.size() && m.lists[l].coded_bytes() > 0 && vertex_list_fast_applicable(m, l, order_v.size())) fast_l = l;
 		// ... and from its reference kinds: every vertex must create its record (kind DATA).  A damaged stream whose data plane merely

@@ -178,7 +178,7 @@ template <typename T> __device__ __forceinline__ void store_g(HRY_GLOBAL uint8_t
 // KIND 0: vertex records (the three records of every parallelogram, in fan order), 1: corner records (one record per already
 // decoded face of the region around the vertex).  Connectivity only, so every record at once: src[k * n + i] = k-th source id of
 // record i, nsrc[i] = their number, kSrcOverflow when the fan has more than SrcCap<KIND> rows (the chain walks that fan itself).
-template <int KIND> struct SrcCap { static constexpr int value = KIND == 0 ? 24 : 12; };   // 8 parallelograms / 12 faces around a vertex
+template <int KIND> struct SrcCap { static constexpr int value = KIND == 0 ? kSrcCap : 12; };   // 8 parallelograms / 12 faces around a vertex
 constexpr uint8_t kSrcOverflow = 255;
 
 template <int KIND, typename F>
@@ -219,14 +219,7 @@ __global__ __launch_bounds__(256) void k_gen_sources(ConnView cv, GenView gv, co
 // whose in-batch sources are final becomes final; at most 64 rounds (a batch in which every record reads its predecessor), one
 // round when no record reads inside the batch (texture atlases, smooth normals).  Same arithmetic, same order of the parts as
 // the encoder (combine_parts above).  Records whose fan did not fit the source table are done by their lane alone, walking the fan.
-struct GenChainJob {
-	int32_t kind, comp;        // one job = one component of one list (the components of a record are predicted independently)
-	uint32_t n, pad2;
-	uint8_t *rec;
-	const uint32_t *src, *ev_he;
-	const uint8_t *nsrc, *ev_slot;
-	ListDesc ld;
-};
+// (one job: GenChainJob, kernels.hpp)
 
 // largest value of the wavefront, for small non-negative values (five ballots)
 __device__ __forceinline__ int wave_max_small(int v)

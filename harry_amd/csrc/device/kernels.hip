@@ -972,8 +972,7 @@ void launch_carry(hipStream_t st, const uint64_t *acc, uint32_t nw, uint64_t *v,
 	unsigned nb = blocks_for(nw, kCarryBlock);
 	(void)v;   // (the folded words are formed inside the kernels)
 	uint8_t *used = nullptr;
-	static const bool sweep_all = [] { const char *e = getenv("HRY_CARRY_SWEEP_ALL"); return e && *e && *e != '0'; }();
-	if (jobs && stream_bits && ns > 1 && !sweep_all) {
+	if (jobs && stream_bits && ns > 1) {
 		used = (uint8_t*)(summary + nb + 1);   // (a mark per wavefront: 4 nb bytes behind the nb words of the pairs; summary has nw / 1024 + 2 words)
 		(void)hipMemsetAsync(used, 0, (size_t)nb * 4, st);
 		hipLaunchKernelGGL(k_carry_mark_used, dim3(blocks_for(ns, 256)), dim3(256), 0, st, jobs, stream_bits, ns, nw, used);

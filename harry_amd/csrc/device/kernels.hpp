@@ -46,6 +46,45 @@ struct PullRanges { uint32_t *dst[4]; const uint32_t *src[4]; uint32_t words[4];
 void launch_pull_ranges(hipStream_t st, const PullRanges &r);
 void launch_carry(hipStream_t st, const uint64_t *acc, uint32_t nw, uint64_t *v, uint32_t *summary, uint8_t *bytes, const StreamJob *jobs = nullptr, const uint32_t *stream_bits = nullptr, uint32_t ns = 0);
 
+// attribute records from the decoded residual planes (unpredict.hip; driver: unchunk.cpp)
+void launch_residuals_to_rec(hipStream_t st, const uint8_t *planes, uint32_t n, const ListDesc &ld, uint8_t *rec);
+void launch_faces_unfold(hipStream_t st, uint32_t n, const ListDesc &ld, uint8_t *rec);
+bool unpredict2_applicable(const ListDesc &ld);
+void launch_chain_records(hipStream_t st, const uint32_t *cand, const uint8_t *ncand, uint32_t nvtx, const uint32_t *seg_start, uint32_t nseg, void *crec);
+bool unpredict3_wanted(const ListDesc &ld);
+void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand, const void *crec,
+                       const uint8_t *planes, const ListDesc &ld, uint8_t *rec, const uint32_t *segs, const uint32_t *list_off, uint32_t n_lists,
+                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done);
+void launch_candidates_ids(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand);
+bool unpredict3_covers(const ListDesc &ld);
+void launch_slice_prepare(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, uint32_t *cand, uint8_t *ncand, void *crec);
+size_t cand_table_words(uint32_t nvtx);
+void cand_table_reset(hipStream_t st, uint32_t *cand, uint32_t nvtx);
+void launch_slice_chain(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, const uint32_t *cand, const uint8_t *ncand,
+                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec);
+void launch_scatter_u32(hipStream_t st, const uint32_t *pairs, uint32_t n, uint32_t *dst);
+uint32_t chain_timeout_flags(hipStream_t st, const uint32_t *gave_up = nullptr);
+
+// records of a mesh with general bindings (general.hip; driver: general.cpp)
+constexpr int kSrcCap = 24;   // most sources a vertex record keeps (general.hip: SrcCap)
+struct GenChainJob {
+	int32_t kind, comp;        // one job = one component of one list (the components of a record are predicted independently)
+	uint32_t n, pad2;
+	uint8_t *rec;
+	const uint32_t *src, *ev_he;
+	const uint8_t *nsrc, *ev_slot;
+	ListDesc ld;
+};
+void launch_face_rank(hipStream_t st, const ConnView &cv, const uint32_t *order_f, uint32_t n, uint32_t *frank);
+void launch_gen_vtx_resid(hipStream_t st, const ConnView &cv, const GenView &gv, const uint32_t *rank, const uint32_t *ev_he, const uint8_t *ev_slot,
+                          const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
+void launch_gen_face_resid(hipStream_t st, const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
+void launch_gen_corner_resid(hipStream_t st, const ConnView &cv, const GenView &gv, const uint32_t *frank, const uint32_t *ev_he, const uint8_t *ev_slot,
+                             const uint32_t *ev_idx, uint32_t n, const uint8_t *rec, const ListDesc &ld, uint8_t *planes);
+void launch_gen_sources(hipStream_t st, int kind, const ConnView &cv, const GenView &gv, const uint32_t *rank, const uint32_t *ev_he, const uint8_t *ev_slot,
+                        uint32_t n, uint32_t *src, uint8_t *nsrc);
+void launch_gen_chain(hipStream_t st, int kind, int stype, const ConnView &cv, const GenView &gv, const uint32_t *rank, const GenChainJob *jobs, uint32_t njobs);
+
 // half-edge twin matching (twins.hip): conn.org / foff (/ eface) resident, twin = output; ws: twin_workspace_bytes
 size_t twin_workspace_bytes(uint32_t nv, uint32_t ne);
 uint32_t twin_overflow_capacity();

@@ -21,7 +21,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <mutex>
 #include <cstdio>
 #include <cstring>
@@ -95,30 +94,6 @@ template <typename F> void run_workers(Context *const *cxs, int n, F &&body)
 	if (err) std::rethrow_exception(err);
 }
 
-// Workers that share something take turns at it, in the order of their shards: the CPUs of a memory node (the walks) and the
-// link to a device (the interval copies).  A walk is bound by the CPUs it gets and a copy by its link, so sharing them evenly
-// makes every worker finish at the same time -- and the device phases that follow (planes, streams, container) pile up behind
-// the last walk.  One after the other, each with all of the shared resource, the total is the same and the first shard's
-// device phase starts after an eighth of it: the workers' device phases hide behind each other's walks.
-struct Turnstile {
-	std::mutex mu;
-	std::condition_variable cv;
-	std::vector<int> order;   // the shards that pass here, ascending
-	size_t next = 0;
-	bool open = false;        // a worker failed: nobody waits any more
-	void enter(int s)
-	{
-		std::unique_lock<std::mutex> g(mu);
-		cv.wait(g, [&] { return open || (next < order.size() && order[next] == s); });
-	}
-	void leave(int s)
-	{
-		{ std::lock_guard<std::mutex> g(mu); if (next < order.size() && order[next] == s) ++next; }
-		cv.notify_all();
-	}
-	void abort() { { std::lock_guard<std::mutex> g(mu); open = true; } cv.notify_all(); }
-};
-
 // segments of a merged container (a shard without a group contributes none: its part holds a zero count)
 uint32_t merged_segments(const ByteSink &out)
 {
@@ -158,8 +133,7 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
                                     ByteSink &out, hry_shard_timing &st, bool store_bounds)
 {
 	const auto t_all = Clock::now();
-	const bool trace = getenv("HRY_TRACE") != nullptr;
-	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry shards] %8.2f ms  %s\n", ms_since(t_all), what); };
+	auto mark = [&](const char *what) { if (trace_on()) fprintf(stderr, "[hry shards] %8.2f ms  %s\n", ms_since(t_all), what); };
 	auto t0 = Clock::now();
 	const int nl = (int)m.lists.size();
 	std::vector<char> had(nl, 0);
@@ -185,13 +159,8 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 	// THAT device read the first context's arrays (an allocation belongs to the device, not to a stream) instead of bringing their
 	// intervals up again -- eight contexts rehearsing on one device had 2.9 GB of interval copies from pageable memory beside
 	// their walks (140 - 170 ms, every pin a round of TLB shootdowns for sixteen walking threads).  Contexts on other devices
-	// bring their intervals up as before, over their own links.  HRY_SHARD_HOST_PLAN=1: the host's analysis (round 4).
-	bool device_plan = false;
-	{
-		const char *e = getenv("HRY_DEVICE_ANALYSIS_MIN_FACES");
-		const uint32_t min_faces = e ? (uint32_t)strtoul(e, nullptr, 10) : (4u << 20);
-		device_plan = m.nf >= min_faces && getenv("HRY_SHARD_HOST_PLAN") == nullptr && host_threads() > 1;
-	}
+	// bring their intervals up as before, over their own links.
+	bool device_plan = m.nf >= (uint32_t)env_uint("HRY_DEVICE_ANALYSIS_MIN_FACES", 4u << 20) && host_threads() > 1;
 	double bounds_ms = 0;
 	bool bounds_done = false;
 	if (device_plan) {
@@ -282,43 +251,8 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 
 	std::unique_ptr<ByteSink[]> parts(new ByteSink[(size_t)n_shards]);
 	std::vector<double> w_upload(n_ctx, 0.0), w_encode(n_ctx, 0.0);
-	// ---- turns (Turnstile above): the walks of the workers on one memory node, the copies to one device.  Measured on the
-	// configs[3] mesh, eight contexts on one device and 16 CPUs, and NOT the default: a shard's walk with all sixteen threads takes
-	// 20 - 25 ms where an eighth of the parallel walks would be 17 (128 groups over sixteen threads leave some idle at the end, and
-	// every walk has its sequential ends), the eight of them 194 ms against 133 side by side -- more than the device phases that hide
-	// behind them (encode 317 against 262 ms).  HRY_SHARD_TURNS=1 takes turns.
-	const bool turns = n_ctx > 1 && getenv("HRY_SHARD_TURNS") != nullptr;
-	// (the copies in turn were measured on one device: each shard's 360 MB of intervals took 30 ms alone -- pageable memory that
-	// sixteen walking threads are reading, every pin a round of TLB shootdowns -- 240 ms one after the other against 150 ms for
-	// eight staging threads at once; HRY_SHARD_COPY_TURNS=1 for the comparison)
-	const bool copy_turns = turns && getenv("HRY_SHARD_COPY_TURNS") != nullptr;
-	std::vector<int> walk_group(n_ctx, 0), copy_group(n_ctx, 0);
-	std::vector<unsigned> walk_budget(n_ctx, 0);
-	std::vector<std::unique_ptr<Turnstile>> walk_turn, copy_turn;
-	if (turns) {
-		std::vector<const void*> cpus((size_t)n_ctx);
-		for (int w = 0; w < n_ctx; ++w) cpus[w] = device_cpus(cxs[w]->device);
-		const unsigned allowed = cpu_allowance(), cap = host_threads();
-		std::vector<const void*> wkeys;
-		std::vector<int> ckeys;
-		for (int w = 0; w < n_ctx; ++w) {
-			size_t g = std::find(wkeys.begin(), wkeys.end(), cpus[w]) - wkeys.begin();
-			if (g == wkeys.size()) { wkeys.push_back(cpus[w]); walk_turn.emplace_back(new Turnstile()); }
-			walk_group[w] = (int)g;
-			size_t c = std::find(ckeys.begin(), ckeys.end(), cxs[w]->device) - ckeys.begin();
-			if (c == ckeys.size()) { ckeys.push_back(cxs[w]->device); copy_turn.emplace_back(new Turnstile()); }
-			copy_group[w] = (int)c;
-		}
-		for (int w = 0; w < n_ctx; ++w) {
-			unsigned members = 0;
-			for (int x = 0; x < n_ctx; ++x) members += walk_group[x] == walk_group[w];
-			const unsigned avail = cpus[w] ? (unsigned)CPU_COUNT((const cpu_set_t*)cpus[w]) : allowed;
-			// the node's CPUs, and the group's share of what the process may keep busy
-			walk_budget[w] = std::max(1u, std::min(cap, std::min(avail, std::max(1u, allowed * members / (unsigned)n_ctx))));
-		}
-		for (int sh = 0; sh < n_shards; ++sh) { walk_turn[walk_group[sh % n_ctx]]->order.push_back(sh); copy_turn[copy_group[sh % n_ctx]]->order.push_back(sh); }
-	}
-	auto abort_turns = [&] { for (auto &t : walk_turn) t->abort(); for (auto &t : copy_turn) t->abort(); };
+	// (the workers walk and copy side by side: taking turns at a memory node's CPUs and a device's link, one shard after the other,
+	// was measured on the configs[3] mesh with eight contexts on one device -- encode 317 against 262 ms side by side)
 	// ---- (device plan) the whole mesh is resident on the first context: quantisation happens there once, over whole lists -- the
 	// intervals of different shards overlap where they were merged, and a record must be quantised exactly once
 	if (device_plan && (nq || clear)) {
@@ -349,7 +283,7 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 	for (int w = 0; w < n_ctx; ++w) cxs[w]->inplace_twin_patches.clear();
 	// (HRY_SHARD_FOREIGN_CONTEXTS=1, for tests on a one-GPU box: every context but the first behaves as one on another device --
 	// it brings its own intervals up and repairs its own copy of the twins)
-	const bool foreign_ctx = getenv("HRY_SHARD_FOREIGN_CONTEXTS") != nullptr;
+	const bool foreign_ctx = env_on("HRY_SHARD_FOREIGN_CONTEXTS");
 	auto on_first_device = [&](int w) { return w == 0 || (!foreign_ctx && cxs[w]->device == cxs[0]->device); };
 	run_workers(cxs, n_ctx, [&](int w) {
 	  // (device plan) a context on the first context's device reads that context's arrays: lent for the length of this call
@@ -357,12 +291,11 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 	  struct Lent { DevBuf *b; void *p; size_t cap; };
 	  std::vector<Lent> lent;
 	  struct GiveBack { std::vector<Lent> &l; ~GiveBack() { for (const Lent &x : l) { x.b->p = x.p; x.b->cap = x.cap; } } } give_back{ lent };
-	  try {
+	  {
 		Context &cx = *cxs[w];
 		HIP_OK(hipSetDevice(cx.device));
 		hry_timing acc{};
 		bool arrays_ready = false;
-		const unsigned own_budget = host_threads();   // (run_workers: this worker's share)
 		for (int s = w; s < n_shards; s += n_ctx) {
 			// ---- the shard: its components, its runs, the intervals it lies in
 			ComponentAnalysis part;
@@ -429,9 +362,7 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 			double up_ms = 0;
 			std::thread uploader;
 			if (!shares0) uploader = std::thread([&] {
-				struct Turn { Turnstile *t; int s; ~Turn() { if (t) t->leave(s); } } turn{ copy_turns ? copy_turn[copy_group[w]].get() : nullptr, s };
 				try {
-					if (turn.t) turn.t->enter(s);   // (the link to this device: one shard's intervals after the other)
 					const auto tu = Clock::now();
 					HIP_OK(hipSetDevice(cx.device));
 					hipStream_t us = cx.stream2;
@@ -453,31 +384,18 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 					for (const ListPlan &rp : rplans)
 						for (const auto &iv : rp.l == 0 ? fiv : viv)
 							dev::launch_requant(us, cx.d_rec[rp.l].as<uint8_t>() + iv.first * rp.stride, iv.second - iv.first, (int)rp.stride, rp.plan);
-					if (turn.t) { turn.t->leave(s); turn.t = nullptr; }   // (every copy is staged: the next shard's may start while the last of these land)
 					HIP_OK(hipStreamSynchronize(us));
 					up_ms = ms_since(tu);
 				} catch (...) { up_err = std::current_exception(); }
 			});
 			struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join{ uploader };
 			t = Clock::now();
-			bool walk_entered = false, walk_left = false;
-			Turnstile *wt = turns ? walk_turn[walk_group[w]].get() : nullptr;
 			const InPlaceShard ip{ &m, &part, eface, &marks, &fiv, [&] {
 				if (uploader.joinable()) uploader.join();
 				if (up_err) std::rethrow_exception(up_err);
 				w_upload[w] += up_ms;
-			}, [&] {   // before the walk: this shard's turn at the node's CPUs, all of them
-				if (!wt) return;
-				wt->enter(s); walk_entered = true;
-				set_thread_budget(walk_budget[w]);
-			}, [&] {   // after it
-				if (!wt) return;
-				set_thread_budget(own_budget);
-				wt->leave(s); walk_left = true;
 			} };
-			struct Pass { Turnstile *t; int s; bool &left; ~Pass() { if (t && !left) { t->enter(s); t->leave(s); } } } pass{ wt, s, walk_left };   // (a shard that never walked passes its turn on)
 			encode_chunked(cx, sk, chunk_syms, parts[s], &ip);
-			(void)walk_entered;
 			w_encode[w] += ms_since(t);
 			const hry_timing &tm = cx.timing;
 			acc.host_walk_ms += tm.host_walk_ms; acc.h2d_ms += tm.h2d_ms; acc.device_ms += tm.device_ms; acc.d2h_ms += tm.d2h_ms;
@@ -485,7 +403,7 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 			acc.total_ms += tm.total_ms;
 		}
 		cx.timing = acc;
-	  } catch (...) { abort_turns(); throw; }
+	  }
 	});
 	// (device plan) the whole mesh stays resident on the first context.  Workers on its device repaired their twins in its arrays;
 	// workers on OTHER devices repaired the host array and their own copies only -- their (half-edge, twin) pairs go to the resident
@@ -529,7 +447,7 @@ void encode_sharded(Context *const *cxs, int n_ctx, Mesh &m, const hry_quant *q,
 	check_contexts(cxs, n_ctx);
 	if (n_shards <= 0) n_shards = n_ctx;
 	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh");
-	if (!m.general && !getenv("HRY_SHARD_EXTRACT")) { encode_sharded_in_place(cxs, n_ctx, m, q, nq, clear, n_shards, chunk_syms, out, st, store_bounds); return; }
+	if (!m.general) { encode_sharded_in_place(cxs, n_ctx, m, q, nq, clear, n_shards, chunk_syms, out, st, store_bounds); return; }
 	// ---- plan, once
 	auto t0 = Clock::now();
 	// a freshly read mesh: its half-edge twins are matched on the first context's device (twins.hip: 0.3 ms per million triangles

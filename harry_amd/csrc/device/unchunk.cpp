@@ -24,30 +24,8 @@ namespace hry {
 using namespace dev;
 typedef std::chrono::steady_clock Clock;
 static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-// HRY_TRACE=1: wall-clock marks of the decode pipeline on stderr (development aid)
-static bool trace_on() { static const bool on = getenv("HRY_TRACE") != nullptr; return on; }
 static thread_local Clock::time_point g_t0;
 #define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  %s\n", ms_since(t0), what); } while (0)
-
-namespace dev {
-void launch_residuals_to_rec(hipStream_t st, const uint8_t *planes, uint32_t n, const ListDesc &ld, uint8_t *rec);
-void launch_faces_unfold(hipStream_t st, uint32_t n, const ListDesc &ld, uint8_t *rec);
-bool unpredict2_applicable(const ListDesc &ld);
-void launch_chain_records(hipStream_t st, const uint32_t *cand, const uint8_t *ncand, uint32_t nvtx, const uint32_t *seg_start, uint32_t nseg, void *crec);
-bool unpredict3_wanted(const ListDesc &ld);
-void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand, const void *crec,
-                       const uint8_t *planes, const ListDesc &ld, uint8_t *rec, const uint32_t *segs, const uint32_t *list_off, uint32_t n_lists,
-                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done);
-void launch_candidates_ids(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand);
-bool unpredict3_covers(const ListDesc &ld);
-void launch_slice_prepare(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, uint32_t *cand, uint8_t *ncand, void *crec);
-size_t cand_table_words(uint32_t nvtx);
-void cand_table_reset(hipStream_t st, uint32_t *cand, uint32_t nvtx);
-void launch_slice_chain(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, const uint32_t *cand, const uint8_t *ncand,
-                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec);
-void launch_scatter_u32(hipStream_t st, const uint32_t *pairs, uint32_t n, uint32_t *dst);
-uint32_t chain_timeout_flags(hipStream_t st, const uint32_t *gave_up = nullptr);
-}
 
 static const int kConnPlanes = 21;
 
@@ -62,10 +40,9 @@ static int conn_init_kind(int i) { return i == 0 ? INIT_IOP : i == 11 ? INIT_NT0
 static void group_chain_lists(const uint32_t *triples, uint32_t n, uint32_t first_index, std::vector<uint32_t> &starts)
 {
 	constexpr uint32_t kTiny = 64, kTinyRun = 64;
-	static const bool merge = getenv("HRY_CHAIN_NO_LIST_MERGE") == nullptr;
 	uint32_t run = 0;   // tiny components in the list at hand (0: the next component starts a list)
 	for (uint32_t i = 0; i < n; ++i) {
-		const bool tiny = merge && triples[3 * i + 1] - triples[3 * i] < kTiny;
+		const bool tiny = triples[3 * i + 1] - triples[3 * i] < kTiny;
 		if (!tiny || run == 0 || run >= kTinyRun) { starts.push_back(first_index + i); run = 0; }
 		run = tiny ? run + 1 : 0;
 	}
@@ -356,7 +333,6 @@ struct SpanUploader : SpanDone {
 	static constexpr int kWorkers = Context::kUploadStreams + 1;
 	std::thread worker[kWorkers];
 	hipStream_t up_stream[kWorkers] = {};
-	int n_workers = 3;
 	std::mutex mu_prefix;                  // after_upload / launch_pending: one worker at a time
 	Clock::time_point t_origin = g_t0;     // (the decode's clock: g_t0 is per thread)
 	uint32_t eface_upto = 0;               // faces whose half-edge -> face entries are computed on the device
@@ -378,17 +354,15 @@ struct SpanUploader : SpanDone {
 			HIP_OK(hipMemsetAsync(cx.d_foff.p, 0, 4, cx.stream2));
 			batches->init(cx.stream2, m);
 		}
-		static const int wanted = [] { const char *e = getenv("HRY_SPAN_UPLOADERS"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : v > kWorkers ? kWorkers : v; }();
-		n_workers = wanted;
 		up_stream[0] = cx.stream2;
-		for (int k = 1; k < n_workers; ++k) {
+		for (int k = 1; k < kWorkers; ++k) {
 			if (!cx.up_stream[k - 1]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[k - 1], hipStreamNonBlocking));
 			if (!cx.up_ev[k - 1]) HIP_OK(hipEventCreateWithFlags(&cx.up_ev[k - 1], hipEventDisableTiming));
 			up_stream[k] = cx.up_stream[k - 1];
 		}
 		const void *node = callers_node_cpus();
 		HRY_MARK(t_origin, "span uploaders' arrays and streams ready");
-		for (int k = 0; k < n_workers; ++k) worker[k] = std::thread([this, node, k] {
+		for (int k = 0; k < kWorkers; ++k) worker[k] = std::thread([this, node, k] {
 			try {
 				stay_on_node(node);
 				HIP_OK(hipSetDevice(cx.device));
@@ -447,8 +421,7 @@ struct SpanUploader : SpanDone {
 			}
 		}
 		if (!planes_done) planes_done = hipEventQuery(planes_ready) == hipSuccess;
-		static const uint32_t parts = [] { const char *e = getenv("HRY_CHAIN_BATCH_PARTS"); const int v = e ? atoi(e) : 4; return (uint32_t)(v < 1 ? 1 : v); }();
-		if (planes_done && prefix < have.size() && !pending_first.empty() && pending_v_end - batches->v_done >= std::max(1u, m.nv / parts)) launch_pending();
+		if (planes_done && prefix < have.size() && !pending_first.empty() && pending_v_end - batches->v_done >= std::max(1u, m.nv / 4)) launch_pending();
 	}
 	void launch_pending()
 	{
@@ -456,20 +429,20 @@ struct SpanUploader : SpanDone {
 		// itself the copies of the later spans would queue behind tens of milliseconds of chains
 		cx.res_nv = m.nv; cx.res_nf = m.nf; cx.res_ne = m.declared_ne;   // (what conn_view reports: the arrays are that large from the start)
 		const uint32_t f_end = arrived[prefix - 1].f1;   // the faces of the prefix: their offsets are complete on the device
-		for (int k = 1; k < n_workers; ++k) {   // (the prefix' spans went up on any of the streams: the first waits for the others)
+		for (int k = 1; k < kWorkers; ++k) {   // (the prefix' spans went up on any of the streams: the first waits for the others)
 			HIP_OK(hipEventRecord(cx.up_ev[k - 1], up_stream[k]));
 			HIP_OK(hipStreamWaitEvent(cx.stream2, cx.up_ev[k - 1], 0));
 		}
 		if (cx.res_has_eface && f_end > eface_upto) dev::launch_edge_faces(cx.stream2, cx.d_foff.as<uint32_t>(), f_end, cx.d_eface.as<uint32_t>(), eface_upto);
 		eface_upto = f_end;
-		HIP_OK(hipEventRecord(cx.ev_x[2], cx.stream2));
-		HIP_OK(hipStreamWaitEvent(cx.stream, cx.ev_x[2], 0));
+		HIP_OK(hipEventRecord(cx.ev_x[1], cx.stream2));
+		HIP_OK(hipStreamWaitEvent(cx.stream, cx.ev_x[1], 0));
 		batches->launch(cx.stream, pending_first.data(), (uint32_t)pending_first.size(), pending_v_end);
 		HIP_OK(hipEventRecord(cx.attr_ev[0], cx.stream));   // (the attribute groups' events are free by now: the planes are decoded)
 		batches->first_done = cx.attr_ev[0]; batches->v_first_batch = pending_v_end;
 		pending_first.clear();
 		++batches_launched;
-		if (getenv("HRY_TRACE")) fprintf(stderr, "[hry] %8.3f ms  chains of the components up to vertex %u launched beside the replay\n", ms_since(t_origin), pending_v_end);
+		if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  chains of the components up to vertex %u launched beside the replay\n", ms_since(t_origin), pending_v_end);
 	}
 	// everything is on the device (true) or the caller uploads as usual (false: the replay ran as one sequence, or a copy failed)
 	bool finish()
@@ -524,10 +497,9 @@ struct SpanUploader : SpanDone {
 static bool pipelined_decode_applicable(const Mesh &m, const std::vector<RestartPoint> &restarts, const PlaneView *conn,
                                         const ListDesc &ldv, uint32_t vc)
 {
-	if (getenv("HRY_NO_PIPELINE")) return false;
+	if (env_on("HRY_NO_PIPELINE")) return false;
 	int ud = 0;
-	uint32_t min_nv = 1u << 17;
-	if (const char *e = getenv("HRY_PIPELINE_MIN_VERTICES")) min_nv = (uint32_t)strtoul(e, nullptr, 10);
+	const uint32_t min_nv = (uint32_t)env_uint("HRY_PIPELINE_MIN_VERTICES", 1u << 17);
 	return restarts.empty() && conn[7].empty() && m.uniform_degree(ud) && unpredict3_covers(ldv) && vc == m.nv && m.nv >= min_nv && m.declared_ne != 0;
 }
 
@@ -568,26 +540,24 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	// first one and publishes as before, the stretches behind the snapshots run on helper threads meanwhile and are joined when
 	// all have finished (cbm_replay.hpp SnapshotSpans) -- the replay of ONE component on several cores
 	std::unique_ptr<SnapshotSpans> spans;
-	if (ud == 3 && !snaps_in.empty() && host_threads() > 1 && !getenv("HRY_NO_SNAPSHOT_REPLAY") && !getenv("HRY_GENERIC_REPLAY")) spans.reset(new SnapshotSpans(*m, conn, snaps_in, order_v.data()));   // (sizes m->twin)
+	if (ud == 3 && !snaps_in.empty() && host_threads() > 1 && !env_on("HRY_NO_SNAPSHOT_REPLAY") && !env_on("HRY_GENERIC_REPLAY")) spans.reset(new SnapshotSpans(*m, conn, snaps_in, order_v.data()));   // (sizes m->twin)
 	else m->twin.resize(ne);
 	BigVec<uint16_t> seen(nv, 0);
 	ReplayLive live;
 	live.on_border.assign(nv, 0);
 	live.pending.reserve(1 << 16);
 	HRY_MARK(g_t0, "host arrays allocated");
-	if (const char *e = getenv("HRY_PIPELINE_FACES")) live.interval = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));
+	live.interval = std::max(1u, (uint32_t)env_uint("HRY_PIPELINE_FACES", live.interval));
 
 	std::exception_ptr consumer_error;
 	std::vector<SliceClock> clocks;
-	uint32_t min_slice = 1u << 15;   // replay and chain take about the same time per vertex: what is left behind the replay is the last slice (16 Ki: the consumer's launches become the longer path)
-	if (const char *e = getenv("HRY_PIPELINE_SLICE")) min_slice = std::max(64u, (uint32_t)strtoul(e, nullptr, 10));
+	// replay and chain take about the same time per vertex: what is left behind the replay is the last slice (16 Ki: the consumer's launches become the longer path)
+	const uint32_t min_slice = std::max(64u, (uint32_t)env_uint("HRY_PIPELINE_SLICE", 1u << 15));
 	// ... but the first slices are small and double up to that size: the chain is the longer path, what counts is how early it
 	// starts, and the early chunks of the vertex planes are short for exactly that (attr_chunk_len)
-	uint32_t first_slice = 1u << 13;
-	if (const char *e = getenv("HRY_PIPELINE_FIRST_SLICE")) first_slice = std::max(64u, (uint32_t)strtoul(e, nullptr, 10));
-	first_slice = std::min(first_slice, min_slice);
-	uint32_t last_piece = 1u << 16;   // pieces of what is left when the replay is done (HRY_PIPELINE_LAST_PIECE; tests: small)
-	if (const char *e = getenv("HRY_PIPELINE_LAST_PIECE")) last_piece = std::max(64u, (uint32_t)strtoul(e, nullptr, 10) & ~63u);
+	const uint32_t first_slice = std::min(1u << 13, min_slice);
+	// pieces of what is left when the replay is done (tests: small)
+	const uint32_t last_piece = std::max(64u, (uint32_t)env_uint("HRY_PIPELINE_LAST_PIECE", 1u << 16) & ~63u);
 	int attr_waited = 0;   // groups of attribute streams the chain's stream has been told to wait for
 	const Clock::time_point t_begin = g_t0;
 	// vertex records come back slice by slice into pinned memory and are copied into the mesh by the consumer as they land
@@ -628,8 +598,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			// The consumer acts on a publication only when `lag` newer ones exist: the newest part of the arrays is still hot
 			// in the replay thread's cache (twins of the last ring keep changing), copying it there would slow the replay down.
 			std::deque<ReplayLive::Pub> hist;
-			uint32_t lag = 2;
-			if (const char *e = getenv("HRY_PIPELINE_LAG")) lag = (uint32_t)strtoul(e, nullptr, 10);
+			constexpr uint32_t lag = 2;
 			auto drain = [&](bool wait) {
 				while (!landing.empty()) {
 					Landing &L = landing.front();
@@ -664,22 +633,13 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 					hipEvent_t rev = nullptr;
 					if (r.mirrored) {   // (the helper left a pinned copy: four transfers, no copy on this thread)
 						const uint32_t *mf = cx.h_mirror.as<uint32_t>(), *mo = mf + (size_t)nf + 1, *mt = mo + ne, *mv = mt + ne;
-						static const bool pull = !getenv("HRY_NO_PULL");
-						if (pull) {   // one kernel reads the four ranges from the pinned mirrors (HRY_NO_PULL=1: four transfers, as until round 6)
-							PullRanges pr{};
-							pr.dst[0] = cx.d_foff.as<uint32_t>() + r.f0 + 1; pr.src[0] = mf + r.f0 + 1; pr.words[0] = r.f1 - r.f0;
-							pr.dst[1] = cx.d_org.as<uint32_t>() + r.h0; pr.src[1] = mo + r.h0; pr.words[1] = r.h1 - r.h0;
-							pr.dst[2] = cx.d_twin.as<uint32_t>() + r.h0; pr.src[2] = mt + r.h0; pr.words[2] = r.h1 - r.h0;
-							pr.dst[3] = cx.d_order_v.as<uint32_t>() + r.v0; pr.src[3] = mv + r.v0; pr.words[3] = r.v1 - r.v0;
-							launch_pull_ranges(mir_stream, pr);
-						} else {
-						if (r.f1 > r.f0) HIP_OK(hipMemcpyAsync(cx.d_foff.as<uint32_t>() + r.f0 + 1, mf + r.f0 + 1, ((size_t)r.f1 - r.f0) * 4, hipMemcpyHostToDevice, mir_stream));
-						if (r.h1 > r.h0) {
-							HIP_OK(hipMemcpyAsync(cx.d_org.as<uint32_t>() + r.h0, mo + r.h0, ((size_t)r.h1 - r.h0) * 4, hipMemcpyHostToDevice, mir_stream));
-							HIP_OK(hipMemcpyAsync(cx.d_twin.as<uint32_t>() + r.h0, mt + r.h0, ((size_t)r.h1 - r.h0) * 4, hipMemcpyHostToDevice, mir_stream));
-						}
-						if (r.v1 > r.v0) HIP_OK(hipMemcpyAsync(cx.d_order_v.as<uint32_t>() + r.v0, mv + r.v0, ((size_t)r.v1 - r.v0) * 4, hipMemcpyHostToDevice, mir_stream));
-						}
+						// one kernel reads the four ranges from the pinned mirrors
+						PullRanges pr{};
+						pr.dst[0] = cx.d_foff.as<uint32_t>() + r.f0 + 1; pr.src[0] = mf + r.f0 + 1; pr.words[0] = r.f1 - r.f0;
+						pr.dst[1] = cx.d_org.as<uint32_t>() + r.h0; pr.src[1] = mo + r.h0; pr.words[1] = r.h1 - r.h0;
+						pr.dst[2] = cx.d_twin.as<uint32_t>() + r.h0; pr.src[2] = mt + r.h0; pr.words[2] = r.h1 - r.h0;
+						pr.dst[3] = cx.d_order_v.as<uint32_t>() + r.v0; pr.src[3] = mv + r.v0; pr.words[3] = r.v1 - r.v0;
+						launch_pull_ranges(mir_stream, pr);
 						HIP_OK(hipEventCreateWithFlags(&rev, hipEventDisableTiming));
 						HIP_OK(hipEventRecord(rev, mir_stream));
 					} else {
@@ -697,7 +657,6 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				ranges.clear();
 				if (newest.n_pub == seen_pub) continue;   // (a helper's announcement only: no new publication of the replaying thread)
 				seen_pub = newest.n_pub;
-				if (trace_on() && getenv("HRY_TRACE_CONSUMER")) fprintf(stderr, "[hry] %8.3f ms    consumer: publication %llu (faces %u, vertices final up to %u)\n", ms_since(t_begin), (unsigned long long)newest.seq, newest.faces, newest.upto);
 				hist.push_back(newest);
 				if (!newest.done && !newest.joined && hist.size() <= lag) continue;
 				const ReplayLive::Pub P = newest.done || newest.joined ? newest : hist.front();
@@ -705,12 +664,11 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				// (a publication behind the replaying thread's own stretch rests on the helpers' stretches: their transfers first)
 				// (only those that lie below the publication's faces: the fans of its final vertices end there.  Waiting for every
 				// transfer under way -- they arrive in the order the helpers finish, 24 MB within 0.3 ms of each other, a millisecond
-				// on the link -- kept the chain idle until the LAST stretch was up: HRY_MIRROR_WAIT_ALL=1)
+				// on the link -- kept the chain idle until the LAST stretch was up)
 				if (P.joined || P.done) {
-					static const bool wait_all = getenv("HRY_MIRROR_WAIT_ALL") != nullptr;
 					mir_waited.resize(mir_ev.size(), 0);
 					for (size_t i = 0; i < mir_ev.size(); ++i)
-						if (!mir_waited[i] && mir_ev[i] && (wait_all || P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
+						if (!mir_waited[i] && mir_ev[i] && (P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
 				}
 				// finished part of the connectivity -- but for what the helpers' stretches have brought up already
 				if (P.faces > f_up) {
@@ -823,7 +781,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 		const RestartCounters none;
 		std::vector<uint32_t> comp_first;
 		std::vector<std::pair<uint32_t, uint32_t>> refs;
-		const bool count = getenv("HRY_PERF") != nullptr;
+		const bool count = env_on("HRY_PERF");
 		PerfCounters pc;
 		if (count) pc.start();
 		if (spans) {
@@ -832,8 +790,8 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				// 30 bytes a triangle, 840 MB for the 28 M triangles of configs[2], kept by the context.  Without them the consumer
 				// thread stages every byte itself: 10 GB/s, 80 ms for that mesh, in front of a chain that the replay no longer holds up
 				const size_t words = (size_t)nf + 1 + 2 * (size_t)ne + nv;
-				static const size_t max_mb = [] { const char *e = getenv("HRY_MIRROR_MAX_MB"); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1024; }();
-				if (words * 4 <= (max_mb << 20) && !getenv("HRY_NO_MIRRORS")) {
+				static const size_t max_mb = env_uint("HRY_MIRROR_MAX_MB", 1024);
+				if (words * 4 <= (max_mb << 20)) {
 					cx.h_mirror.ensure(words * 4);
 					uint32_t *p0 = cx.h_mirror.as<uint32_t>();
 					spans->mirror_foff = p0; spans->mirror_org = p0 + (size_t)nf + 1; spans->mirror_twin = spans->mirror_org + ne; spans->mirror_order = spans->mirror_twin + ne;
@@ -847,7 +805,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			HRY_MARK(g_t0, "replay: the first stretch has reached its snapshot");
 			spans->finish(cur, cur_end0, std::move(end0), eom0, &live);
 		}
-		else if (onlydeg == 3 && !getenv("HRY_GENERIC_REPLAY")) replay_triangles<true>(*m, conn, seen.data(), order_v.data(), cur, comp_first, refs, &live);   // the lean loop
+		else if (onlydeg == 3 && !env_on("HRY_GENERIC_REPLAY")) replay_triangles<true>(*m, conn, seen.data(), order_v.data(), cur, comp_first, refs, &live);   // the lean loop
 		else replay_span(*m, rd, seen.data(), order_v.data(), cur, replay_detail::NONE32, 0, none, comp_first, refs, &live);
 		if (count) { pc.stop(); pc.report("cut-border replay (pipelined decode, publishing)", (double)cur.he - 2.0 * cur.face); }
 		if (cur.face != nf) throw Error(HRY_E_FORMAT, "corrupt stream (face count)");
@@ -886,7 +844,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 		float t = 0;
 		if (hipEventElapsedTime(&t, c.a, c.b) == hipSuccess) chain_ms += t;
 		if (hipEventElapsedTime(&t, c.p0, c.p1) == hipSuccess) prep_ms += t;
-		static const bool slices_only = getenv("HRY_TRACE_SLICES") != nullptr;   // (these lines alone: nothing of the trace's own waits inside the decode)
+		static const bool slices_only = env_on("HRY_TRACE_SLICES");   // (these lines alone: nothing of the trace's own waits inside the decode)
 		if (trace_on() || slices_only) {   // where the slices' kernels lay on the device's clock, from the decode's first event (the payload's upload)
 			float a = 0, b = 0, p0 = 0, p1 = 0;
 			(void)hipEventElapsedTime(&a, cx.ev[1], c.a); (void)hipEventElapsedTime(&b, cx.ev[1], c.b);
@@ -1035,19 +993,14 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	// walks the vertices in order -- waits only for the groups it has reached.  Jobs, offsets and sizes are permuted alike.
 	uint32_t n_conn_streams = 0;
 	for (int k = 0; k < kConnPlanes; ++k) n_conn_streams += (uint32_t)((nsym[k] + (uint64_t)CHC - 1) / CHC);
-	uint64_t kGroupEnd[Context::kAttrGroups] = { 1u << 15, 1u << 17, ~0ull };
-	if (const char *e = getenv("HRY_ATTR_GROUPS")) {   // 1: one launch for all attribute streams, 2: two groups (measurements)
-		const int ng = atoi(e);
-		if (ng == 1) kGroupEnd[0] = kGroupEnd[1] = ~0ull;
-		else if (ng == 2) { kGroupEnd[0] = 1u << 17; kGroupEnd[1] = ~0ull; }
-	}
+	const uint64_t kGroupEnd[Context::kAttrGroups] = { 1u << 15, 1u << 17, ~0ull };
 	// A large payload goes up in two parts: the connectivity streams (the container's first streams) in front of their kernel, the
 	// attribute streams -- nine tenths of it -- while that kernel runs (the copy is from the caller's pageable buffer and keeps this
 	// thread, which has nothing else to do until the connectivity planes are back): 289 MB of the 100 M-triangle mesh were 7.4 ms
-	// in front of everything.  HRY_NO_SPLIT_UPLOAD: one copy as before; HRY_SPLIT_UPLOAD_MIN: from how many bytes (32 MB).
+	// in front of everything.  HRY_SPLIT_UPLOAD_MIN: from how many bytes (32 MB).
 	const uint64_t conn_bytes = offs[std::min<size_t>(n_conn_streams, nstreams)];
-	static const uint64_t split_min = [] { const char *e = getenv("HRY_SPLIT_UPLOAD_MIN"); return e ? (uint64_t)strtoull(e, nullptr, 10) : (uint64_t)32 << 20; }();   // (tests: 1)
-	const bool split_upload = payload_bytes >= split_min && conn_bytes < payload_bytes && !getenv("HRY_NO_SPLIT_UPLOAD");
+	static const uint64_t split_min = env_uint("HRY_SPLIT_UPLOAD_MIN", (uint64_t)32 << 20);   // (tests: 1)
+	const bool split_upload = payload_bytes >= split_min && conn_bytes < payload_bytes;
 	uint32_t group_n[Context::kAttrGroups] = { 0, 0, 0 };
 	// ... and inside a launch the streams a lane can decode (k_chunk_decode_lanes: t0 > 128) come first; lanes_n: how many
 	uint32_t conn_lanes_n = 0, group_lanes_n[Context::kAttrGroups] = { 0, 0, 0 };
@@ -1097,22 +1050,21 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 		for (auto &e : cx.attr_ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 		HIP_OK(hipEventCreateWithFlags(&cx.ev_payload, hipEventDisableTiming));
 	}
-	HIP_OK(hipEventRecord(cx.ev_x[0], cx.stream));          // payload (its connectivity part at least), jobs and tables are on the device
 	HIP_OK(hipEventRecord(cx.ev[1], cx.stream));
 	// A launch takes the lane-per-stream kernel for the streams it can where that is the faster of the two (HRY_DECODE_LANES: 0
-	// never, 1 always).  Measured on MI355X: a wavefront alone on its SIMD issues an instruction every ~5.5 cycles, so a lane-per-
+	// never, 1 always, unset: whichever is faster).  Measured on MI355X: a wavefront alone on its SIMD issues an instruction every ~5.5 cycles, so a lane-per-
 	// stream wave takes ~1 900 cycles per step of 64 symbols however many waves there are (up to one per SIMD), and the wave-per-
 	// stream kernel ~420 cycles per symbol of a stream, ~190 per symbol and SIMD once several waves share a SIMD (scalar port):
 	// many short streams (the 53 000 streams of 16 Ki symbols of configs[3] under the default chunk policy, chunked.cpp) go to the
 	// lanes, a few thousand long ones (a container written with 128 Ki-symbol chunks: 5 200 attribute streams) stay with a wave each.
-	static const int lanes_mode = [] { const char *e = getenv("HRY_DECODE_LANES"); return e ? atoi(e) : -1; }();
+	static const uint64_t lanes_mode = env_uint("HRY_DECODE_LANES", 2);
 	auto decode_streams = [&](hipStream_t st, uint32_t first, uint32_t n, uint32_t n_for_lanes) {
-		bool lanes = lanes_mode > 0;
+		bool lanes = lanes_mode == 1;
 		// (16-bit counts where no stream's total passes 65535: 32 KB a lane-wave, five of them a compute unit; HRY_DECODE_COUNTS32: never)
-		static const bool wide_only = getenv("HRY_DECODE_COUNTS32") != nullptr;
+		static const bool wide_only = env_on("HRY_DECODE_COUNTS32");
 		bool counts16 = !wide_only;
 		for (uint32_t j = first; j < first + n_for_lanes && counts16; ++j) counts16 = (uint64_t)jobs[j].t0 + jobs[j].n <= 65535u;
-		if (lanes_mode < 0 && n_for_lanes >= 256u) {
+		if (lanes_mode > 1 && n_for_lanes >= 256u) {
 			uint64_t total = 0, longest = 0;
 			for (uint32_t j = first; j < first + n_for_lanes; ++j) { total += jobs[j].n; longest = std::max<uint64_t>(longest, jobs[j].n); }
 			const double simds = 1024.0, lane_waves = (n_for_lanes + 63) / 64;
@@ -1142,22 +1094,15 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 			if (nsym[k]) HIP_OK(hipMemcpyAsync(dst, cx.d_csyms.as<uint8_t>() + plane_off[k], nsym[k], hipMemcpyDeviceToHost, cx.stream));
 		}
 	}
-	HIP_OK(hipEventRecord(cx.ev_x[2], cx.stream));        // the connectivity planes are on their way to the host
+	HIP_OK(hipEventRecord(cx.ev_x[1], cx.stream));        // the connectivity planes are on their way to the host
 	// the attribute streams wait for the connectivity streams' kernel: launched side by side, the long attribute waves took
 	// the SIMD slots the short connectivity waves needed (15 ms instead of 1 ms on a 12 M-triangle mesh), and the host replay
-	// -- the critical path -- waits for exactly those
-	// ... unless the mesh takes the pipelined decode (one large component, triangles replayed at ~6 ns each): there the device
-	// chain, not the replay, ends the decode, and it can start only when the attribute streams are done -- side by side then
-	const bool chain_bound = !m->general && restarts.empty() && nsym[7] == 0 && vc == m->nv && unpredict3_covers(ldv);
-	// (round 5: not by default there either -- beside the attribute waves the 28 M-triangle torus' 30 MB of connectivity planes came
-	// down in 7.4 ms instead of 1.5, in front of the replay, and its chain waits for the replay most of the time: decode 213 -> 206 ms,
-	// the 1 M-triangle torus the same either way; HRY_ATTR_SIDE_BY_SIDE=1: the old order)
-	(void)chain_bound;
-	const bool side_by_side = getenv("HRY_ATTR_SIDE_BY_SIDE") ? atoi(getenv("HRY_ATTR_SIDE_BY_SIDE")) != 0 : false;
+	// -- the critical path -- waits for exactly those.  The pipelined decode too (round 5: beside the attribute waves the
+	// 28 M-triangle torus' 30 MB of connectivity planes came down in 7.4 ms instead of 1.5, in front of the replay, and its chain
+	// waits for the replay most of the time: decode 213 -> 206 ms).
 	// ... and for the planes' copy to the host: beside 10^5 attribute waves the copy of the configs[3] mesh's 110 MB of connectivity
-	// planes took 20 ms instead of 5, in front of the replay (HRY_CONN_COPY_FIRST=0: the old order)
-	static const bool copy_first = !getenv("HRY_CONN_COPY_FIRST") || atoi(getenv("HRY_CONN_COPY_FIRST")) != 0;
-	hipEvent_t attr_after = side_by_side ? cx.ev_x[0] : copy_first ? cx.ev_x[2] : cx.ev[2];
+	// planes took 20 ms instead of 5, in front of the replay
+	const hipEvent_t attr_after = cx.ev_x[1];
 	if (split_upload) {   // the rest of the payload, beside the connectivity streams' kernel (on the uploads' stream)
 		cx.ensure_second_stream();
 		HIP_OK(hipMemcpyAsync(cx.d_cout.as<uint8_t>() + conn_bytes, payload + conn_bytes, payload_bytes - conn_bytes, hipMemcpyHostToDevice, cx.stream2));
@@ -1180,11 +1125,11 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 		for (int g = 1; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamWaitEvent(cx.stream3, cx.attr_ev[g], 0));
 	}
 	HIP_OK(hipEventRecord(cx.ev[6], cx.stream3));
-	HIP_OK(hipEventRecord(cx.ev_x[1], cx.stream3));
+	HIP_OK(hipEventRecord(cx.ev_x[0], cx.stream3));
 	if (trace_on()) { HIP_OK(hipEventSynchronize(cx.ev[2])); HRY_MARK(g_t0, "connectivity streams decoded"); }
 	HIP_OK(hipStreamSynchronize(cx.stream));
 	const bool take_pipeline = !m->general && pipelined_decode_applicable(*m, restarts, conn, ldv, vc);
-	if (!take_pipeline) HIP_OK(hipStreamWaitEvent(cx.stream, cx.ev_x[1], 0));   // attribute planes before anything that reads them (the pipelined decode waits group by group)
+	if (!take_pipeline) HIP_OK(hipStreamWaitEvent(cx.stream, cx.ev_x[0], 0));   // attribute planes before anything that reads them (the pipelined decode waits group by group)
 
 	HRY_MARK(g_t0, "connectivity planes on the host");
 	// ---- replay the cut-border machine on the host
@@ -1206,18 +1151,17 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	} else {
 		bool conn_resident = false;
 		std::unique_ptr<ChainBatches> batches;
-		if (!restarts.empty() && rcounters.size() == restarts.size() && m->nf >= (1u << 20) && !getenv("HRY_NO_SPAN_UPLOAD")) {
+		if (!restarts.empty() && rcounters.size() == restarts.size() && m->nf >= (1u << 20) && !env_on("HRY_NO_SPAN_UPLOAD")) {
 			// float / 32-bit vertex components: their chains start beside the replay, batch by batch (ChainBatches)
 			// ... where that pays: a batch is a launch of its own on the main stream, and a launch takes as long as its longest
 			// chain (one wavefront, one component: 7 - 14 ms for the 49 000 vertices of a configs[3] component), so three batches of a
 			// mesh whose chains all fit on the device at once (the 12.6 M-triangle share: 384 chains) took 36 ms where one launch takes 15;
 			// the 100 M-triangle mesh's 3 072 chains need two rounds anyway and finish 25 ms earlier in batches.
 			// HRY_CHAIN_BATCH_MIN_VERTICES: the threshold (tests run small meshes in batches).
-			const char *bm = getenv("HRY_CHAIN_BATCH_MIN_VERTICES");
-			const uint32_t batch_min = bm ? (uint32_t)strtoul(bm, nullptr, 10) : 20000000u;
-			const bool in_batches = ldv.nplanes && unpredict2_applicable(ldv) && !unpredict3_wanted(ldv) && vc == m->nv && vc >= batch_min && !getenv("HRY_NO_CHAIN_BATCHES");
+			const uint32_t batch_min = (uint32_t)env_uint("HRY_CHAIN_BATCH_MIN_VERTICES", 20000000u);
+			const bool in_batches = ldv.nplanes && unpredict2_applicable(ldv) && !unpredict3_wanted(ldv) && vc == m->nv && vc >= batch_min;
 			if (in_batches) batches.reset(new ChainBatches(cx, ldv, cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes], vc, nsym[0]));
-			SpanUploader up(cx, *m, order_v, batches.get(), cx.ev_x[1]);
+			SpanUploader up(cx, *m, order_v, batches.get(), cx.ev_x[0]);
 			cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, &up, &snaps);
 			conn_resident = up.finish();
 			if (up.error) std::rethrow_exception(up.error);

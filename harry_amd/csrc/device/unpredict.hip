@@ -18,6 +18,7 @@
 #include "codec_math.hpp"
 #include "dev_types.hpp"
 #include "kernels.hpp"
+#include "../host/env.hpp"
 
 namespace hry {
 namespace dev {
@@ -1257,17 +1258,8 @@ __global__ __launch_bounds__(64) void k_unpredict2(ConnView cv, const uint32_t *
 struct alignas(16) ChainRec { uint16_t slot[6]; uint16_t flags; uint16_t pad; };
 constexpr uint32_t kRing3 = 16384;          // ring entries (32 KB of LDS for 16-bit values)
 constexpr uint32_t kRing3Near = kRing3 - 64;   // a source this close to its vertex is still in the ring when the run is prepared
-#ifndef HRY_CHAIN_POLL_PAUSE_ASM
-#define HRY_CHAIN_POLL_PAUSE_ASM
-#endif
-#ifndef HRY_CHAIN_MAX_HEADS
-#define HRY_CHAIN_MAX_HEADS 8
-#endif
-constexpr uint32_t kMaxHeads = HRY_CHAIN_MAX_HEADS;   // heads per prepared tile
-#ifndef HRY_CHAIN_MAX_HEADS_LATE
-#define HRY_CHAIN_MAX_HEADS_LATE 12
-#endif
-constexpr uint32_t kMaxHeadsLate = HRY_CHAIN_MAX_HEADS_LATE;   // heads of a tile that is prepared when its turn has come
+constexpr uint32_t kMaxHeads = 8;   // heads per prepared tile
+constexpr uint32_t kMaxHeadsLate = 12;   // heads of a tile that is prepared when its turn has come
 constexpr uint32_t kHand0 = 2, kHand = 64;     // hand-over words of the chain's wavefront team behind its two control words
 enum { CR_NC = 3, CR_BIG = 3, CR_POS_SHIFT = 2, CR_POS_NONE = 7, CR_FAR = 1 << 5, CR_NEED_SHIFT = 6 };
 
@@ -1552,7 +1544,6 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 			             "s_lshr_b32 %[t], %[w], 16\n\t"
 			             "s_cmp_eq_u32 %[t], %[want]\n\t"
 			             "s_cbranch_scc1 2f\n\t"
-			             HRY_CHAIN_POLL_PAUSE_ASM
 			             "s_sub_u32 %[left], %[left], 1\n\t"
 			             "s_cmp_lg_u32 %[left], 0\n\t"
 			             "s_cbranch_scc1 1b\n\t"
@@ -1730,14 +1721,12 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 			build_maps(valid && !hd, tb + lo, 64u);
 			Map3 F = g;
 			if (!valid || hd) { F.k = 0; F.A = 0; F.D = 0; }
-#ifndef HRY_CHAIN_FULL_SCANS
 			// (the usual tile: every map is of a lone candidate or of the mean of two -- k = 0 or 1 -- and mostly there is no head)
 			if (!__ballot(F.k > 1)) {
 				if (hm == 0ull) return scan3_t<true>(F);   // one run (the lanes before it hold the identity): no runs' flags either
 				if ((uint32_t)lane == lo || hd || ((hm << 1) >> lane) & 1ull) F.k |= kRunStart;
 				return scan3_runs_t<true>(F);
 			}
-#endif
 			if ((uint32_t)lane == lo || hd || ((hm << 1) >> lane) & 1ull) F.k |= kRunStart;
 			return scan3_runs(F);
 		};
@@ -1801,9 +1790,6 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 				uint32_t d = 0;
 #pragma nounroll
 				for (uint32_t dd = W - 1u; dd >= 1u; --dd) if (!__ballot(back < dd)) { d = dd; break; }
-#ifdef HRY_CHAIN_NO_LATE_OVERLAP
-				d = 0;
-#endif
 				if (d == 0u) wait_prev();
 				else if (tile_idx > d) wait_tile(tile_idx - 1u - d);
 				HRY_LOG(log_kind = 3u | ((uint32_t)__builtin_popcountll(innermask) << 4) | (d << 10);)
@@ -1814,7 +1800,6 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 			Map3 Fm = compose_runs(hm);
 			asm volatile("" : "+v"(Fm.k), "+v"(Fm.A), "+v"(Fm.D));   // the scan is computed before the wait below, not sunk behind it
 			HRY_CLK(++ck_early;)
-#ifndef HRY_CHAIN_NO_FAST_TILES
 			// A tile without heads is ONE run, and whether its speculation holds is a question about the predecessor's value alone:
 			// lane l's form (parallelogram inside [0, top], residual code near: prediction.h:58-63) holds iff the value before it
 			// lies in an interval [a, b]; that value is the composed map of the lanes before it -- monotone in x, the value handed
@@ -1828,11 +1813,7 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 			int32_t x_lo = 0x7fffffff, x1_lo = 0, x2_lo = 0;   // (x_lo: no interval yet -- no 16-bit value passes the test behind the wait)
 			uint32_t x_width = 0, x1_width = 0, x2_width = 0, hs = 0;
 			int32_t end_k = 0, end_A = 0, end_D = 0;
-#ifndef HRY_CHAIN_NO_ONE_HEAD
 			const bool one_cand = (hm & (hm - 1ull)) == 0ull && (hm & alone) == 0ull;
-#else
-			const bool one_cand = false;
-#endif
 			if (hm == 0ull || one_cand) {
 				const int32_t hf = (int32_t)uf.half, tp_ = (int32_t)top;
 				int32_t a = two ? max(0, 2 * hf + 1 - (int32_t)p1c) - bo0 : hf + 1 - bo0;
@@ -1904,11 +1885,6 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 				}
 				HRY_LOG(log_kind = 6u | (log_kind & ~0xfu);)
 			} else { HRY_LOG(if (prepared) log_kind = 2u | (nheads << 4) | ((uint32_t)__builtin_popcountll(rowheads) << 10);) serial_part(hm, alone, pfm, Fm); }
-#else
-			wait_prev();
-			x = x_prev;   // the first vertex of a slice is never chained
-			serial_part(hm, alone, pfm, Fm);
-#endif
 		} else {
 			// ---- a tile whose vertices need each other: runs are cut where a vertex needs a source inside the run, and prepared
 			// when the vertices before them are final
@@ -1938,9 +1914,7 @@ __device__ void unpredict3_segment(const TopoD &tp, const uint32_t *order_v, uin
 		wait_prev();
 		asm volatile("" ::: "memory");   // the ring writes of this tile are issued before the word that announces them (LDS runs a wavefront's accesses in order)
 		__hip_atomic_store(&sync[kHand0 + (tile_idx & (kHand - 1u))], ((tile_idx + 1u) << 16) | (x_out & 0xffffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // every lane, the same word: no exec juggling
-#ifndef HRY_CHAIN_NO_SCHED_BARRIER
 		__builtin_amdgcn_sched_barrier(0);   // (the loop's bookkeeping and the flush's test stay behind the store that everybody waits for: the scheduler had put nine of their instructions in front of it)
-#endif
 		HRY_MARK(if (comp == 0 && lane == 0) { const unsigned long long mk3 = __builtin_amdgcn_s_memtime(); auto d = [&](unsigned long long a, unsigned long long b) { return a && b && b > a ? (b - a > 0xffffull ? 0xffffull : b - a) : 0ull; };
 			g_chain_marks[(tb >> 6) & ((1u << 18) - 1u)] = d(mk0, mk1) | (d(mk0, mk2) << 16) | (d(mk0, mk3) << 32); })
 		HRY_LOG(if (comp == 0 && lane == 0) g_chain_log[(tb >> 6) & ((1u << 18) - 1u)] = ((unsigned long long)__builtin_amdgcn_s_memtime() << 16) | log_kind;)
@@ -2090,7 +2064,7 @@ void launch_candidates_ids(hipStream_t st, const ConnView &cv, const uint32_t *o
 // waits for it --: the 28 M-triangle torus 98.7 ms with eight, 81.4 with twelve, 80.6 with sixteen: twelve), 4 otherwise
 static uint32_t chain_waves(uint32_t nvtx)
 {
-	static const uint32_t forced = [] { const char *e = getenv("HRY_CHAIN_WAVES"); int v = e ? atoi(e) : 0; return (uint32_t)(v < 0 ? 0 : v > 16 ? 16 : v); }();
+	static const uint32_t forced = (uint32_t)std::min<uint64_t>(16, env_uint("HRY_CHAIN_WAVES", 0));
 	return forced ? forced : nvtx >= (1u << 18) ? 12u : nvtx >= (1u << 16) ? 8u : 4u;   // (90 000 vertices: 1.08 ms with four, 1.00 with eight or twelve; 202 000: 2.16 / 1.77 / 1.88; 32 000 and below: the same with four and eight)
 }
 // ---- pipelined decode: one slice [v_begin, v_end) of the vertex chain
@@ -2162,9 +2136,8 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 	// queue made it 58 KB and two)
 	// ... when there are more chains than that gives places for (256 compute units x 4), a ring of half the size lets seven share a
 	// compute unit: a chain is a lone wavefront that issues an instruction every five or six cycles, two of them on a SIMD hardly
-	// slow each other, and a source older than the ring is simply read from the records (HRY_CHAIN_RING_KB: 8, 16 or 32)
-	static const uint32_t ring_kb_env = [] { const char *e = getenv("HRY_CHAIN_RING_KB"); const int v = e ? atoi(e) : 0; return v == 8 || v == 16 || v == 32 ? (uint32_t)v : 0u; }();
-	const uint32_t ring_bytes = (ring_kb_env ? ring_kb_env : (uint64_t)n_lists * (uint32_t)ld.ncomp > 1024u ? 16u : 32u) * 1024u, lds_bytes = ring_bytes + 64 * kCandMax * 3 * 4 + 64;   // ring, rows, remembered owners
+	// slow each other, and a source older than the ring is simply read from the records
+	const uint32_t ring_bytes = ((uint64_t)n_lists * (uint32_t)ld.ncomp > 1024u ? 16u : 32u) * 1024u, lds_bytes = ring_bytes + 64 * kCandMax * 3 * 4 + 64;   // ring, rows, remembered owners
 	auto go = [&](auto kern, int stype) {
 		CompSel sel{};
 		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype) sel.comp[sel.n++] = c;

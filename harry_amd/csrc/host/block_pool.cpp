@@ -11,6 +11,7 @@
 #include <new>
 #include <unordered_map>
 
+#include "env.hpp"
 #include "mesh.hpp"
 
 namespace hry {
@@ -25,15 +26,14 @@ struct Pool {
 		// HRY_POOL_MB: how much freed memory the pool may keep (0 disables recycling).  Default: an eighth of the machine's memory,
 		// at least 2 GiB, at most 64 GiB -- a 100 M-triangle mesh frees 5 GB of per-call arrays per encode, and fresh ones cost
 		// a page fault per 4 KiB (or per 2 MiB) under the process-wide mmap lock, which is what N concurrent workers then queue on
-		const char *e = getenv("HRY_POOL_MB");
 		size_t def = 2048;
 		const long pages = sysconf(_SC_PHYS_PAGES), psz = sysconf(_SC_PAGE_SIZE);
 		if (pages > 0 && psz > 0) def = std::min<size_t>(65536, std::max<size_t>(2048, ((size_t)pages * (size_t)psz >> 20) / 8));
-		limit = (size_t)(e ? strtoull(e, nullptr, 10) : def) << 20;
+		limit = (size_t)env_uint("HRY_POOL_MB", def) << 20;
 	}
 	~Pool() { for (auto &kv : free_blocks) free(kv.second); }
 };
-bool huge_pages_wanted() { static const bool on = getenv("HRY_NO_HUGEPAGES") == nullptr; return on; }
+bool huge_pages_wanted() { static const bool on = !env_on("HRY_NO_HUGEPAGES"); return on; }
 Pool &pool() { static Pool *p = new Pool(); return *p; }   // never destroyed: vectors in static objects may outlive any order
 }   // namespace
 
@@ -87,7 +87,7 @@ struct NodeTable {
 	std::vector<cpu_set_t> nodes;
 	NodeTable()
 	{
-		if (getenv("HRY_NO_NUMA_BIND")) return;
+		if (env_on("HRY_NO_NUMA_BIND")) return;
 		cpu_set_t allowed;
 		CPU_ZERO(&allowed);
 		if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return;
@@ -123,7 +123,7 @@ const void *callers_cache_cpus(unsigned *n_cpus)
 	static std::mutex mu;
 	static std::unordered_map<int, cpu_set_t> *by_cpu = new std::unordered_map<int, cpu_set_t>();
 	if (n_cpus) *n_cpus = 0;
-	if (getenv("HRY_NO_NUMA_BIND")) return nullptr;
+	if (env_on("HRY_NO_NUMA_BIND")) return nullptr;
 	const int cpu = sched_getcpu();
 	if (cpu < 0) return nullptr;
 	std::lock_guard<std::mutex> g(mu);
@@ -160,7 +160,7 @@ const void *callers_neighbour_cpus()
 {
 	static std::mutex mu;
 	static std::unordered_map<int, cpu_set_t> *by_cpu = new std::unordered_map<int, cpu_set_t>();
-	if (getenv("HRY_NO_NUMA_BIND")) return nullptr;
+	if (env_on("HRY_NO_NUMA_BIND")) return nullptr;
 	const int cpu = sched_getcpu();
 	if (cpu < 0) return nullptr;
 	const void *base = callers_cache_cpus(nullptr);

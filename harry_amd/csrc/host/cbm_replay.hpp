@@ -822,7 +822,7 @@ void cut_border_replay_with(Mesh &m, RD &rd, OrderVec &order_v, std::vector<uint
 	const RestartCounters none;
 	std::vector<std::pair<uint32_t, uint32_t>> refs;
 	seg_start.clear();
-	if (getenv("HRY_PERF")) {
+	if (env_on("HRY_PERF")) {
 		PerfCounters pc;
 		pc.start();
 		replay_span(m, rd, seen.data(), order_v.data(), cur, replay_detail::NONE32, 0, none, seg_start, refs);

@@ -443,7 +443,7 @@ SnapshotSpans::SnapshotSpans(Mesh &mesh, const PlaneView *planes, const std::vec
 void SnapshotSpans::start(unsigned n_threads)
 {
 	const void *node = callers_node_cpus();
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	const auto t_start = std::chrono::steady_clock::now();
 	if (trace) fprintf(stderr, "[hry replay]   the caller sets the helpers off on cpu %d\n", sched_getcpu());
 	auto work = [this, trace, t_start] {
@@ -457,7 +457,7 @@ void SnapshotSpans::start(unsigned n_threads)
 				SeenOfSpan own(m.nv);
 				const ReplayCursor c0 = sp.cur;
 				PerfCounters pc;
-				const bool count = getenv("HRY_PERF") != nullptr;
+				const bool count = env_on("HRY_PERF");
 				if (count) pc.start();
 				sp.eom = replay_triangles<false>(m, conn, own.p, order_v, sp.cur, sp.first, sp.refs, nullptr, sp.cur0, sp.cur1, sp.stop_face, sp.stop_mid, &sp.seed, &ends[k], sp.cur_end);
 				if (count) { pc.stop(); char what[64]; snprintf(what, sizeof what, "replay, stretch %zu on a helper thread", k); pc.report(what, (double)(sp.cur.face - c0.face)); }
@@ -535,14 +535,13 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 {
 	using replay_detail::NONE32;
 	static const std::vector<SnapshotPoint> no_snaps;
-	const std::vector<SnapshotPoint> &snaps = snaps_in && !getenv("HRY_NO_SNAPSHOT_REPLAY") && !getenv("HRY_GENERIC_REPLAY") ? *snaps_in : no_snaps;
+	const std::vector<SnapshotPoint> &snaps = snaps_in && !env_on("HRY_NO_SNAPSHOT_REPLAY") && !env_on("HRY_GENERIC_REPLAY") ? *snaps_in : no_snaps;
 	int ndeg = 0, onlydeg = 0;
 	for (size_t d = 0; d < m.have_degree.size(); ++d) if (m.have_degree[d]) { ++ndeg; onlydeg = (int)d; }
 	const int fixed_numtri = ndeg <= 1 ? onlydeg - 2 : -1;
 	unsigned n_threads = host_threads();
-	if (const char *e = getenv("HRY_REPLAY_THREADS")) { const int v = atoi(e); if (v > 0) n_threads = (unsigned)v; }   // (development: the spans' threads beside the uploaders')
 	if ((restarts.empty() && snaps.empty()) || n_threads < 2 || m.nf < parallel_min_faces() || counters.size() != restarts.size()) {
-		if (fixed_numtri == 1 && !getenv("HRY_GENERIC_REPLAY")) {
+		if (fixed_numtri == 1 && !env_on("HRY_GENERIC_REPLAY")) {
 			// triangles only: the lean loop (cbm_replay.hpp: replay_triangles), same results
 			m.face_off.resize((size_t)m.nf + 1); m.face_off[0] = 0;
 			m.org.resize(m.declared_ne);
@@ -553,7 +552,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 			std::vector<std::pair<uint32_t, uint32_t>> refs;
 			seg_start.clear();
 			PerfCounters pc;
-			const bool count = getenv("HRY_PERF") != nullptr;
+			const bool count = env_on("HRY_PERF");
 			if (count) pc.start();
 			replay_triangles<false>(m, conn_planes, seen.data(), order_v.data(), cur, seg_start, refs, nullptr);
 			if (count) { pc.stop(); pc.report("cut-border replay (triangles)", (double)cur.he - 2.0 * cur.face); }
@@ -565,7 +564,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 			return;
 		}
 		Planes rd{ conn_planes, { 0 }, fixed_numtri };
-		if (!getenv("HRY_GENERIC_REPLAY")) {   // polygons: the lean loop as one span from the start of the stream
+		if (!env_on("HRY_GENERIC_REPLAY")) {   // polygons: the lean loop as one span from the start of the stream
 			m.face_off.resize((size_t)m.nf + 1); m.face_off[0] = 0;
 			m.org.resize(m.declared_ne);
 			m.twin.resize(m.declared_ne);
@@ -576,7 +575,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 			std::vector<std::pair<uint32_t, uint32_t>> refs;
 			seg_start.clear();
 			PerfCounters pc;
-			const bool count = getenv("HRY_PERF") != nullptr;
+			const bool count = env_on("HRY_PERF");
 			if (count) pc.start();
 			replay_polygons(m, rd, seen.data(), order_v.data(), cur, NONE32, 0, none, seg_start, refs);
 			if (count) { pc.stop(); pc.report("cut-border replay (polygons)", (double)cur.he - 2.0 * cur.face); }
@@ -644,7 +643,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 		else for (int p = 0; p < 21; ++p) sp.cur1[p] = conn_planes[p].size();
 	}
 	if ((uint64_t)m.declared_ne + n_sym >= 0xffffffffull) throw Error(HRY_E_UNSUPPORTED, "border snapshots: the placeholders do not fit behind the half-edges");
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	const auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry replay] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	if (trace) fprintf(stderr, "[hry replay] %zu spans\n", ns);
@@ -679,7 +678,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 		if (!ok) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart point does not match the stream)");
 	};
 	std::atomic<size_t> next{ 0 };
-	const bool lean = !getenv("HRY_GENERIC_REPLAY");
+	const bool lean = !env_on("HRY_GENERIC_REPLAY");
 	parallel_for((unsigned)std::min<size_t>(n_threads, ns), [&](unsigned) {
 		for (;;) {
 			size_t k = next.fetch_add(1, std::memory_order_relaxed);

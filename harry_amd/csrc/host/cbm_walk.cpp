@@ -410,7 +410,6 @@ struct Emitter {
 template <int DEG>
 static void walk_component(Mesh &m, WalkState &st, const uint32_t *eface_tab, uint32_t f, Border &cb, Emitter &em, uint32_t &next_id, uint32_t &consumed)
 {
-	static const bool kWalkPrefetch = [] { const char *e = getenv("HRY_WALK_PREFETCH"); return !e || atoi(e) != 0; }();
 	WalkResult &w = em.w;
 	const uint32_t *foff = m.face_off.data();
 	const uint32_t *org = m.org.data();
@@ -485,12 +484,10 @@ static void walk_component(Mesh &m, WalkState &st, const uint32_t *eface_tab, ui
 			// the faces behind this polygon's other edges are the next gates' neighbours: their lines (twins, origins, the
 			// half-edge -> face table) are asked for now -- a component is walked once, every line of it is a miss the first time
 			// (hardware counters on the configs[3] share: 0.44 last-level misses per triangle, IPC 1.6)
-			if (kWalkPrefetch) {
-				for (uint32_t h = foff[f], he = foff[f + 1]; h < he; ++h) {
-					const uint32_t o = twin[h];
-					__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
-					if (!DEG) __builtin_prefetch(eface_tab + o);
-				}
+			for (uint32_t h = foff[f], he = foff[f + 1]; h < he; ++h) {
+				const uint32_t o = twin[h];
+				__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
+				if (!DEG) __builtin_prefetch(eface_tab + o);
 			}
 		} else e1 = nxt(e1);
 		e2 = nxt(e1);
@@ -564,9 +561,8 @@ static void walk_component_tri(Mesh &m, WalkState &st, uint32_t f, Border &cb, E
 	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_ops = 0;
 	bool changed = false;
 	std::vector<uint32_t> &tp = w.twin_patches;   // half-edges whose twin this walk changes (rare: non-manifold edges, consumed neighbours)
-	// HRY_WALK_PREFETCH: 0 none, 1 the twins of the triangle's other edges, 2 (default) + the faces behind them, 3 + their marks
-	// (1 M triangles: 7.8 -> 7.4 ms; 28 M, beyond the caches: 293 -> 237 ms)
-	static const int pf_level = [] { const char *e = getenv("HRY_WALK_PREFETCH"); return e ? atoi(e) : 2; }();
+	// prefetch: the twins of the triangle's other edges and the faces behind them (1 M triangles: 7.8 -> 7.4 ms; 28 M, beyond the
+	// caches: 293 -> 237 ms)
 	auto emit = [&](uint32_t s, uint32_t order) {
 		if (MODEL) { em.op(s, (int)order); return; }
 		uint32_t k = order == 0 ? 0u : order > 8u ? 7u : order - 1u;   // models.h:101-105
@@ -624,12 +620,11 @@ static void walk_component_tri(Mesh &m, WalkState &st, uint32_t f, Border &cb, E
 		const uint32_t base = 3u * fc, kk = t - base;
 		const uint32_t e0 = t, e1 = base + (kk == 2u ? 0u : kk + 1u), e2 = base + (kk == 0u ? 2u : kk - 1u);
 		const uint32_t v2 = org[e2];
-		if (pf_level >= 1) {
+		{
 			// the next gate is one of this triangle's other two edges: their twins (this face's line of the twin array) and,
 			// one step further, the faces behind them
 			const uint32_t t1 = twin[e1], t2 = twin[e2];
-			if (pf_level >= 2) { __builtin_prefetch(org + t1); __builtin_prefetch(org + t2); }
-			if (pf_level >= 3) { __builtin_prefetch(gone + t1 / 3u); __builtin_prefetch(gone + t2 / 3u); }
+			__builtin_prefetch(org + t1); __builtin_prefetch(org + t2);
 		}
 		const bool fresh = sent[v2] == NONE32;
 		if (fresh || on[v2] == 0) {
@@ -721,8 +716,9 @@ static std::unique_ptr<WalkTrace> take_walk_trace()
 {
 	std::unique_ptr<WalkTrace> t;
 	{ std::lock_guard<std::mutex> g(g_trace_mu); t = std::move(g_trace_spare); }
-	size_t want = WalkTrace::kRing;
-	if (const char *e = getenv("HRY_WALK_RING")) { const size_t v = (size_t)strtoull(e, nullptr, 10); want = 1024; while (want < v && want < WalkTrace::kRing) want <<= 1; }
+	const uint64_t v = env_uint("HRY_WALK_RING", WalkTrace::kRing);
+	size_t want = 1024;
+	while (want < v && want < WalkTrace::kRing) want <<= 1;
 	if (t && t->ring != want) t.reset();
 	if (!t) { t.reset(new WalkTrace()); t->ring = want; t->mask = want - 1; t->rec.resize(want); }
 	t->head.store(0, std::memory_order_relaxed); t->tail.store(0, std::memory_order_relaxed); t->done.store(0, std::memory_order_relaxed); t->failed.store(0, std::memory_order_relaxed);
@@ -745,7 +741,6 @@ static void walk_component_tri_a(Mesh &m, WalkState &st, uint32_t f, Border &cb,
 	uint32_t next_id = next_id_io, consumed = consumed_io;
 	bool changed = false;
 	std::vector<uint32_t> &tp = w.twin_patches;
-	static const int pf_level = [] { const char *e = getenv("HRY_WALK_PREFETCH"); return e ? atoi(e) : 2; }();
 	uint64_t *rec = tr.rec.data();
 	size_t at = at_io, published = at_io;
 	const size_t ring = tr.ring, rmask = tr.mask;
@@ -814,10 +809,9 @@ static void walk_component_tri_a(Mesh &m, WalkState &st, uint32_t f, Border &cb,
 		const uint32_t base = 3u * fc, kk = t - base;
 		const uint32_t e1 = base + (kk == 2u ? 0u : kk + 1u), e2 = base + (kk == 0u ? 2u : kk - 1u);
 		const uint32_t v2 = org[e2];
-		if (pf_level >= 1) {
+		{
 			const uint32_t t1 = twin[e1], t2 = twin[e2];
-			if (pf_level >= 2) { __builtin_prefetch(org + t1); __builtin_prefetch(org + t2); }
-			if (pf_level >= 3) { __builtin_prefetch(gone + t1 / 3u); __builtin_prefetch(gone + t2 / 3u); }
+			__builtin_prefetch(org + t1); __builtin_prefetch(org + t2);
 		}
 		const bool fresh = sent[v2] == NONE32;
 		if (fresh || on[v2] == 0) {
@@ -983,7 +977,6 @@ static void walk_trace_expand(const Mesh &m, WalkState &st, Emitter &em, WalkTra
 template <int DEG>
 static void walk_component_poly(Mesh &m, WalkState &st, const uint32_t *eface_tab, uint32_t f, Border &cb, Emitter &em, uint32_t &next_id_io, uint32_t &consumed_io)
 {
-	static const bool kWalkPrefetch = [] { const char *e = getenv("HRY_WALK_PREFETCH"); return !e || atoi(e) != 0; }();
 	WalkResult &w = em.w;
 	const uint32_t *foff = m.face_off.data();
 	const uint32_t *org = m.org.data();
@@ -1066,12 +1059,10 @@ static void walk_component_poly(Mesh &m, WalkState &st, const uint32_t *eface_ta
 			e1 = t + 1 == fe ? fb : t + 1;
 			// the faces behind this polygon's other edges are the next gates' neighbours: their lines (twins, origins, the
 			// half-edge -> face table) are asked for now -- a component is walked once, every line of it is a miss the first time
-			if (kWalkPrefetch) {
-				for (uint32_t h = fb; h < fe; ++h) {
-					const uint32_t o = twin[h];
-					__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
-					if (!DEG) __builtin_prefetch(eface_tab + o);
-				}
+			for (uint32_t h = fb; h < fe; ++h) {
+				const uint32_t o = twin[h];
+				__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
+				if (!DEG) __builtin_prefetch(eface_tab + o);
 			}
 		} else e1 = e1 + 1 == fe ? fb : e1 + 1;
 		e2 = e1 + 1 == fe ? fb : e1 + 1;
@@ -1159,7 +1150,7 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 template <int DEG>
 static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, bool eval_op_model, unsigned n_threads)
 {
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry walk] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	WalkState st(m.nv, m.nf);
@@ -1177,7 +1168,7 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 	if (w.snapshot_faces) w.snapshots.reserve(w.snapshots.size() + (size_t)m.nf / w.snapshot_faces + 2);   // (the two-core walk appends while its second thread reads: no growth)
 	mark("(sequential part) start faces and output planes");
 	uint32_t next_id = 0, consumed = 0;
-	const bool count = getenv("HRY_PERF") != nullptr;   // hardware counters of this thread around the first component's walk
+	const bool count = env_on("HRY_PERF");   // hardware counters of this thread around the first component's walk
 	// the triangle walk on two cores (walk_component_tri_a / walk_trace_expand above): large triangle meshes of the chunked profile
 	struct Split {
 		std::unique_ptr<WalkTrace> trace;
@@ -1191,17 +1182,18 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 			const auto t_stop = std::chrono::steady_clock::now();
 			trace->done.store(1, std::memory_order_release);
 			expander.join();
-			if (getenv("HRY_TRACE")) fprintf(stderr, "[hry walk] the expanding thread was %zu records behind the walk's %zu, joined after %.2f ms\n", behind,
+			if (trace_on()) fprintf(stderr, "[hry walk] the expanding thread was %zu records behind the walk's %zu, joined after %.2f ms\n", behind,
 			                                 trace->head.load(std::memory_order_relaxed), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stop).count());
 		}
 		~Split() { stop(); if (trace) keep_walk_trace(std::move(trace)); }
 	} split;
-	const uint32_t split_min_faces = [] { const char *e = getenv("HRY_WALK_SPLIT"); return e ? (atoi(e) > 0 ? (uint32_t)atoi(e) : 0xffffffffu) : (1u << 17); }();   // 0: never; n: from n faces (read per call: the tests change it)
-	const bool want_split = DEG == 3 && !eval_op_model && !getenv("HRY_GENERIC_WALK") && !count && n_threads > 1 && m.nf >= split_min_faces;
+	const uint64_t split_env = env_uint("HRY_WALK_SPLIT", 1u << 17);   // 0: never; n: from n faces (read per call: the tests change it)
+	const uint32_t split_min_faces = split_env == 0 ? 0xffffffffu : (uint32_t)std::min<uint64_t>(split_env, 0xffffffffu);
+	const bool want_split = DEG == 3 && !eval_op_model && !env_on("HRY_GENERIC_WALK") && !count && n_threads > 1 && m.nf >= split_min_faces;
 	do {
 		uint32_t f = pool.next();
-		const bool lean = DEG == 3 && !getenv("HRY_GENERIC_WALK");
-		const bool lean_poly = DEG != 3 && !eval_op_model && !getenv("HRY_GENERIC_WALK");   // (the generic loop evaluates the operation model)
+		const bool lean = DEG == 3 && !env_on("HRY_GENERIC_WALK");
+		const bool lean_poly = DEG != 3 && !eval_op_model && !env_on("HRY_GENERIC_WALK");   // (the generic loop evaluates the operation model)
 		if (count && consumed == 0) {
 			PerfCounters pc;
 			pc.start();
@@ -1261,7 +1253,7 @@ void set_thread_budget(unsigned n) { t_thread_budget = n; }
 unsigned host_threads()
 {
 	if (t_thread_budget) return t_thread_budget;
-	if (const char *e = getenv("HRY_HOST_THREADS")) { int v = atoi(e); return v > 0 ? (unsigned)v : 1u; }
+	if (const uint64_t v = env_uint("HRY_HOST_THREADS", kEnvUnset); v != kEnvUnset) return v > 0 ? (unsigned)v : 1u;
 	// what the process may keep busy (affinity mask, control-group quota: thread_pool.cpp), shared with the other ranks of a
 	// one-process-per-GPU launch on this node (LOCAL_WORLD_SIZE, torch.distributed.run); up to 32, and at most an eighth of a
 	// large unshared node's CPUs: eight processes (one per GPU) share the node
@@ -1272,8 +1264,7 @@ unsigned host_threads()
 // below this many remaining faces the analysis passes cost more than they save (HRY_PARALLEL_MIN_FACES overrides, tests)
 uint32_t parallel_min_faces()
 {
-	if (const char *e = getenv("HRY_PARALLEL_MIN_FACES")) return (uint32_t)strtoul(e, nullptr, 10);
-	return 1u << 16;
+	return (uint32_t)env_uint("HRY_PARALLEL_MIN_FACES", 1u << 16);
 }
 namespace {
 // lock-free union-find on atomics: a root is always the smallest index of its set's links, so links never form a cycle
@@ -1347,7 +1338,7 @@ static void analyse_impl(const Mesh &m, const uint32_t *eface_tab, const uint8_t
 	auto face_of = [&](uint32_t e) -> uint32_t { return DEG ? e / (uint32_t)(DEG ? DEG : 1) : eface_tab[e]; };
 	auto is_gone = [&](uint32_t f) -> bool { return gone && gone[f]; };
 	auto split = [&](uint32_t n, unsigned t, uint32_t &b, uint32_t &e) { b = (uint32_t)((uint64_t)n * t / n_threads); e = (uint32_t)((uint64_t)n * (t + 1) / n_threads); };
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry walk] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	// (a) components of the remaining faces
@@ -1558,7 +1549,7 @@ static void analyse_impl(const Mesh &m, const uint32_t *eface_tab, const uint8_t
 template <int DEG>
 static void walk_rest_parallel(Mesh &m, WalkState &st, const uint32_t *eface_tab, Emitter &em0, uint32_t first_id, unsigned n_threads)
 {
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry walk] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	ComponentAnalysis A;
@@ -1591,7 +1582,7 @@ template <int DEG>
 static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *eface_tab, Emitter &em0, uint32_t first_id, unsigned n_threads, const ComponentAnalysis &A)
 {
 	WalkResult &w = em0.w;
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry walk] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	const uint32_t ncomp = A.ncomp;
@@ -1625,7 +1616,7 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 	for (uint32_t k = 0; k < ncomp; ++k) { off_v[k + 1] = off_v[k] + A.fresh[k]; off_f[k + 1] = off_f[k] + A.n_faces[k]; off_he[k + 1] = off_he[k] + A.n_halfedges[k]; }
 	w.order_v.resize(off_v[ncomp]); w.order_f.resize(off_f[ncomp]);
 	// the polygons' triangle counts: one per coded face, so they have their place like order_f (positions: thread-local, moved below)
-	const bool generic = getenv("HRY_GENERIC_WALK") != nullptr;
+	const bool generic = env_on("HRY_GENERIC_WALK");
 	const size_t nt0 = w.grp_val[G_NUMTRI].size();
 	const bool nt_pos = w.numtri_coded && w.numtri_positions;
 	if (w.numtri_coded) { w.grp_val[G_NUMTRI].resize(nt0 + (off_f[ncomp] - off_f[0])); if (nt_pos) w.grp_pos[G_NUMTRI].resize(nt0 + (off_f[ncomp] - off_f[0])); }
@@ -1760,7 +1751,7 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 		}
 	};
 	std::thread marks_thread;
-	if (ncomp >= (getenv("HRY_PARALLEL_MIN_FACES") ? 1u : 4096u) && n_threads > 1) marks_thread =   // (the tests' switch for "small inputs on threads too")
+	if (ncomp >= (env_uint("HRY_PARALLEL_MIN_FACES", kEnvUnset) != kEnvUnset ? 1u : 4096u) && n_threads > 1) marks_thread =   // (the tests' switch for "small inputs on threads too")
 		 std::thread([&] { try { marks_in_order(); } catch (...) { marks_failed = std::current_exception(); } });
 	try {
 		parallel_for(n_threads, [&](unsigned t) {
@@ -1817,11 +1808,10 @@ static void walk_impl(Mesh &m, WalkResult &w, bool eval_op_model, bool one_seque
 
 uint32_t snapshot_spacing(uint32_t nf)
 {
-	if (getenv("HRY_NO_SNAPSHOTS")) return 0;
-	if (const char *e = getenv("HRY_SNAPSHOT_FACES")) return (uint32_t)strtoul(e, nullptr, 10);
+	if (env_on("HRY_NO_SNAPSHOTS")) return 0;
 	uint32_t sp = kSnapshotMinFaces;
 	while ((uint64_t)sp * 64u < nf) sp <<= 1;
-	return sp;
+	return (uint32_t)env_uint("HRY_SNAPSHOT_FACES", sp);
 }
 
 std::vector<RestartPoint> select_restart_points(const std::vector<ComponentMark> &marks, const std::vector<NamedVertex> &named,
@@ -1958,7 +1948,7 @@ void op_position_table(const WalkResult &w, std::vector<uint32_t> &thr, std::vec
 	size_t total = 0;
 	for (int g = 0; g < G_COUNT; ++g) total += w.grp_pos[g].size();
 	thr.resize(total); cum.resize(total);
-	const unsigned nt = total >= (getenv("HRY_PARALLEL_MIN_FACES") ? (size_t)parallel_min_faces() : (size_t)1 << 20) ? std::max(1u, host_threads()) : 1u;   // (the tests' switch for "small inputs on threads too")
+	const unsigned nt = total >= (env_uint("HRY_PARALLEL_MIN_FACES", kEnvUnset) != kEnvUnset ? (size_t)parallel_min_faces() : (size_t)1 << 20) ? std::max(1u, host_threads()) : 1u;   // (the tests' switch for "small inputs on threads too")
 	uint32_t pmax = 0;
 	for (int g = 0; g < G_COUNT; ++g) if (!w.grp_pos[g].empty()) pmax = std::max(pmax, w.grp_pos[g].back());
 	parallel_for(nt, [&](unsigned t) {
@@ -2003,7 +1993,7 @@ void cut_border_walk(Mesh &m, WalkResult &w, bool eval_op_model, bool one_sequen
 	try { run(one_sequence); }
 	catch (const WalkMismatch &) {
 		// (host.hpp WalkMismatch) the twins as the matching leaves them, a fresh result, one thread: the reference's own order
-		if (getenv("HRY_TRACE")) fprintf(stderr, "[hry walk] a repaired twin split a component: the mesh is walked again on one thread\n");
+		if (trace_on()) fprintf(stderr, "[hry walk] a repaired twin split a component: the mesh is walked again on one thread\n");
 		build_twins(m);
 		WalkResult fresh;
 		fresh.progress = nullptr;   // (whoever listened to the groups of the first attempt has to start over: see chunked.cpp)

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/harry_amd.h"
+#include "env.hpp"
 #include "mesh.hpp"
 
 namespace hry {

@@ -50,7 +50,7 @@ void shard_plan(const Mesh &m, uint32_t n_shards, ShardPlan &plan, bool light)
 	ComponentAnalysis &A = plan.A;
 	plan.light = light && !m.general;
 	A.want_vertex_owner = !plan.light;
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	const auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry plan] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	analyse_components(m, A);
@@ -83,7 +83,7 @@ void shard_plan_from_analysis(const Mesh &m, uint32_t n_shards, ComponentAnalysi
 void shard_plan_finish(const Mesh &m, uint32_t n_shards, ShardPlan &plan)
 {
 	ComponentAnalysis &A = plan.A;
-	const bool trace = getenv("HRY_TRACE") != nullptr;
+	const bool trace = trace_on();
 	const auto t0 = std::chrono::steady_clock::now();
 	auto mark = [&](const char *what) { if (trace) fprintf(stderr, "[hry plan] %8.2f ms  (finish) %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); };
 	const uint32_t nc = A.ncomp;

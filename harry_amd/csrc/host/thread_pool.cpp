@@ -102,7 +102,7 @@ void run_on_fresh_threads(unsigned n, void (*fn)(void*, unsigned), void *arg, co
 unsigned cpu_allowance()
 {
 	static const unsigned n = [] {
-		if (const char *e = getenv("HRY_CPUS")) { int v = atoi(e); if (v > 0) return (unsigned)v; }
+		if (const uint64_t v = env_uint("HRY_CPUS", 0)) return (unsigned)v;
 		cpu_set_t cs;
 		CPU_ZERO(&cs);
 		unsigned hw = sched_getaffinity(0, sizeof cs, &cs) == 0 ? (unsigned)CPU_COUNT(&cs) : std::thread::hardware_concurrency();

@@ -64,14 +64,18 @@ def test_random_obj_scenes_against_the_oracle(seed):
 
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("waves,whole", [("12", False), ("16", False), ("5", False), ("1", True), ("8", True)])
+@pytest.mark.parametrize("waves,whole", [("12", False), ("16", False), ("5", False), ("1", True), ("8", True), ("8", "unmirrored")])
 def test_headline_mesh_with_every_team_size(waves, whole):
     """Round 6: the chain's team got late tiles prepared beside their neighbours, a one-head path, tile-by-tile stores and up to
     sixteen wavefronts -- the full-size mesh (every kind of tile) with several team sizes, in slices beside the replay and as one
-    launch, against the reference-format decode."""
+    launch, against the reference-format decode.  "unmirrored": in slices, the stretches of the replay's helper threads left
+    without pinned copies (HRY_MIRROR_MAX_MB=0, read once per process), so the consumer stages them itself."""
     env = dict(os.environ, HRY_CHAIN_WAVES=waves)
     env.pop("HRY_NO_PIPELINE", None)
-    if whole:
+    env.pop("HRY_MIRROR_MAX_MB", None)
+    if whole is True:
         env["HRY_NO_PIPELINE"] = "1"
+    elif whole == "unmirrored":
+        env["HRY_MIRROR_MAX_MB"] = "0"
     r = _run("team_sizes.py", ["708"], env)
     assert r.returncode == 0 and r.stdout.strip().endswith("all equal"), (r.stdout + r.stderr)[-3000:]
