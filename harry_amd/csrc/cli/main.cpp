@@ -31,9 +31,11 @@
 
 #include "../../../include/harry_amd.h"
 #include "../host/env.hpp"
+#include "../host/side_threads.hpp"
 
 using hry::env_on;
 using hry::trace_on;
+using hry::SideThreads;
 
 namespace {
 
@@ -181,7 +183,6 @@ void write_file(const std::string &path, const uint8_t *p, size_t n)
 	if (fd < 0) throw std::runtime_error("cannot write " + path);
 	const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
 	const unsigned nt = n >= ((size_t)64 << 20) ? std::min(8u, hw) : 1u;
-	std::vector<std::thread> th;
 	std::vector<char> failed(nt, 0);
 	auto part = [&](unsigned t) {
 		size_t at = n * t / nt;
@@ -192,9 +193,10 @@ void write_file(const std::string &path, const uint8_t *p, size_t n)
 			at += (size_t)k;
 		}
 	};
-	for (unsigned t = 1; t < nt; ++t) th.emplace_back(part, t);
+	SideThreads th;
+	for (unsigned t = 1; t < nt; ++t) th.spawn([&part, t] { part(t); });
 	part(0);
-	for (auto &x : th) x.join();
+	th.join();
 	const bool bad = std::find(failed.begin(), failed.end(), (char)1) != failed.end();
 	if (close(fd) != 0 || bad) throw std::runtime_error("cannot write " + path);
 }
@@ -220,19 +222,19 @@ int run(const Args &args)
 	const int n_dev = hry_device_count();
 	// The device contexts come up (runtime start, code objects: a few hundred milliseconds) while the input is read and parsed on the
 	// host; whoever needs one first waits for them.
-	std::string ctx_error;
-	std::thread ctx_thread([&] {
+	SideThreads ctx_thread;
+	ctx_thread.spawn([&] {
 		for (int i = 0; i < n_ctx; ++i) {
 			hry_ctx *c = nullptr;
-			if (hry_ctx_create(n_dev > 0 && i > 0 ? (args.device + i) % n_dev : args.device, &c) != HRY_OK) { ctx_error = hry_last_error(); return; }
+			if (hry_ctx_create(n_dev > 0 && i > 0 ? (args.device + i) % n_dev : args.device, &c) != HRY_OK) throw std::runtime_error(hry_last_error());
 			h.cx.push_back(c);
 		}
 	});
-	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{ ctx_thread };
 	const bool trace = trace_on();
+	bool ctx_ready = false;
 	auto contexts = [&] {
-		if (ctx_thread.joinable()) { ctx_thread.join(); if (trace) std::cerr << "[harry] " << since_start_ms() << " ms  contexts ready" << std::endl; }
-		if (!ctx_error.empty()) throw std::runtime_error(ctx_error);
+		if (!ctx_ready) { ctx_ready = true; ctx_thread.join(); if (trace) std::cerr << "[harry] " << since_start_ms() << " ms  contexts ready" << std::endl; }
+		ctx_thread.rethrow();
 	};
 	if (trace) std::cerr << "[harry] " << since_start_ms() << " ms  arguments parsed" << std::endl;
 	const bool sharded = n_ctx > 1 || args.shards > 1;

@@ -127,8 +127,6 @@ struct EncodePipeline : WalkProgress {
 	std::mutex mu;
 	std::condition_variable cond_sender;
 	bool closing = false;
-	std::thread th;
-	std::exception_ptr err;
 	bool kernels_ok = false, registered[3] = { false, false, false };
 	uint32_t n_sent = 0;
 
@@ -136,7 +134,7 @@ struct EncodePipeline : WalkProgress {
 	    : cx(c), cv(c.conn_view()), ldv(v), ldf(f), vc(n_v), fc(n_f), dev_nv(nv_dev), arrays_ready(std::move(ready)), t0(origin) {}
 	~EncodePipeline()
 	{
-		if (th.joinable()) { { std::lock_guard<std::mutex> g(mu); closing = true; } cond_sender.notify_all(); th.join(); }
+		{ std::lock_guard<std::mutex> g(mu); closing = true; } cond_sender.notify_all(); sender.join();
 		if (registered[0] || registered[1] || registered[2]) (void)hipStreamSynchronize(cx.pipe_stream);   // (an error path: no copy may still read the arrays)
 		unregister_arrays();
 	}
@@ -165,7 +163,7 @@ struct EncodePipeline : WalkProgress {
 		ov = order_v; of = order_f; nt = numtri;
 		want_f = ldf.nplanes > 0 || nt != nullptr;
 		began = true;
-		th = std::thread([this] { try { run(); } catch (...) { std::lock_guard<std::mutex> g(mu); if (!err) err = std::current_exception(); } });
+		sender.spawn([this] { run(); });
 	}
 	// the walk's arrays become readable by the copy engines where they lie (sending thread, first thing); where the runtime
 	// refuses, every run is gathered
@@ -207,7 +205,7 @@ struct EncodePipeline : WalkProgress {
 	int slot_with_room(const Need &q, int mode)
 	{
 		for (;;) {
-			if (err) std::rethrow_exception(err);
+			if (std::exception_ptr e = sender.error()) std::rethrow_exception(e);
 			if (open_slot >= 0) {
 				Slot &s = slot[open_slot];
 				if (s.mode == mode && fits(s, q)) return open_slot;
@@ -290,9 +288,9 @@ struct EncodePipeline : WalkProgress {
 		if (began) {
 			{ std::lock_guard<std::mutex> g(mu); closing = true; if (open_slot >= 0) { slot[open_slot].state = CLOSED; open_slot = -1; } }
 			cond_sender.notify_all();
-			th.join();
+			sender.join();
 			unregister_arrays();
-			if (err) std::rethrow_exception(err);
+			sender.rethrow();
 		}
 		HIP_OK(hipEventRecord(cx.pipe_ev, cx.pipe_stream));
 		HIP_OK(hipStreamWaitEvent(cx.stream, cx.pipe_ev, 0));
@@ -513,6 +511,7 @@ struct EncodePipeline : WalkProgress {
 		}
 		HIP_OK(hipStreamSynchronize(cx.pipe_stream));
 	}
+	SideThreads sender;   // run(), from begin() on (last: joined before anything above goes)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -614,32 +613,17 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		ComponentAnalysis A;
 		// (beside it, on a host thread of its own: what the walk loops need whatever the analysis says.  The device calls stay on
 		// this thread: a short-lived thread that has used the runtime leaves the next pageable copy of this one 25 ms slower)
-		int ud = 0;
-		const bool uniform = m.uniform_degree(ud) && (ud == 3 || ud == 4);
 		BigVec<uint32_t> eface;   // mixed degrees: the face of every half-edge
 		std::unique_ptr<WalkState> marks;
-		std::exception_ptr failed;
 		const unsigned nt = host_threads();
-		std::thread tables([&] {
-			try {
-				set_thread_budget(nt);
-				if (!uniform) {
-					eface.resize(m.ne());
-					parallel_for(nt, [&](unsigned t) {
-						const uint32_t b = (uint32_t)((uint64_t)m.nf * t / nt), e = (uint32_t)((uint64_t)m.nf * (t + 1) / nt);
-						for (uint32_t f = b; f < e; ++f) for (uint32_t h = m.face_off[f]; h < m.face_off[f + 1]; ++h) eface[h] = f;
-					});
-				}
-				marks.reset(new WalkState(m.nv, m.nf, nt));
-			} catch (...) { failed = std::current_exception(); }
-		});
-		try { device_component_analysis(cx, m, A); } catch (...) { tables.join(); throw; }
-		tables.join();
-		if (failed) std::rethrow_exception(failed);
+		SideThreads tables;
+		tables.spawn([&] { set_thread_budget(nt); marks = walk_tables(m, nt, eface); });
+		device_component_analysis(cx, m, A);
+		tables.rethrow();
 		if (A.ncomp > 1) {
 			try {
 				start_pipeline(A, nullptr);
-				cut_border_walk_in_place(m, A, uniform ? nullptr : eface.data(), *marks, w);
+				cut_border_walk_in_place(m, A, eface.empty() ? nullptr : eface.data(), *marks, w);
 				walked = true;
 				HRY_MARK(t_all, "  walk returned");
 			} catch (const WalkMismatch &) {
@@ -679,13 +663,9 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		}
 		if (!w.snapshots.empty()) write_snapshot_section(w.snapshot_faces, w.snapshots, scounters, snap_dir);
 	};
-	struct Helper {   // (joined on every way out)
-		std::thread th; std::exception_ptr failed;
-		void wait() { if (th.joinable()) th.join(); if (failed) { std::exception_ptr e = failed; failed = nullptr; std::rethrow_exception(e); } }
-		~Helper() { if (th.joinable()) th.join(); }
-	} dir_helper;
 	const bool dir_beside = w.marks.size() >= 4096 && host_threads() > 1;
-	if (dir_beside) dir_helper.th = std::thread([&] { try { select_restarts(); } catch (...) { dir_helper.failed = std::current_exception(); } });
+	SideThreads dir_helper;
+	if (dir_beside) dir_helper.spawn(select_restarts);
 
 	const uint32_t vc = (uint32_t)w.order_v.size(), fc = (uint32_t)w.order_f.size();
 	if (piped && (vc != pipe->vc || fc != pipe->fc)) throw Error(HRY_E_INTERNAL, "encode pipeline: sizes changed under the walk");
@@ -888,7 +868,7 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	HRY_MARK(t_all, "  stream kernels launched");
 	// directory: chunk sizes, plane lengths, restart points of the connectivity replay (while the device codes the streams, unless
 	// a thread has been at them since the walk), stream lengths
-	if (dir_beside) dir_helper.wait(); else select_restarts();
+	if (dir_beside) dir_helper.rethrow(); else select_restarts();
 	const uint32_t nrs = (uint32_t)restarts.size();
 	HRY_MARK(t_all, "  restart points selected");
 	HIP_OK(hipStreamSynchronize(cx.stream));

@@ -238,12 +238,11 @@ void fetch_to_host(Context &cx, void *dst, const void *d_src, size_t bytes)
 	size_t landed = 0, taken = 0, copied[kSlots];   // chunks whose DMA has finished / that a helper has taken; per slot: chunks copied out of it
 	for (auto &c : copied) c = 0;
 	bool stop = false;
-	std::vector<std::thread> helpers;
+	SideThreads helpers;
 	const void *node = callers_node_cpus();
-	helpers.reserve(n_helpers);   // (no growth -- and so no destruction of a joinable thread -- between two creations)
-	auto finish = [&] { { std::lock_guard<std::mutex> g(mu); stop = true; } cv.notify_all(); for (auto &h : helpers) h.join(); };
+	auto finish = [&] { { std::lock_guard<std::mutex> g(mu); stop = true; } cv.notify_all(); helpers.join(); };
 	try {
-	for (unsigned t = 0; t < n_helpers; ++t) helpers.emplace_back([&, node] {
+	for (unsigned t = 0; t < n_helpers; ++t) helpers.spawn([&, node] {
 		stay_on_node(node);
 		for (;;) {
 			size_t c;

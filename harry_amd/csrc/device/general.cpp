@@ -709,17 +709,15 @@ void general_planes_decode(Context &cx, Mesh &m, const OrderVec &order_v, const 
 			t.lists[1] = m.lists[fast_l];      // the description; the records move
 			t.lists[1].data.swap(held);
 		}
-		std::exception_ptr chain_error, reader_error;
+		std::exception_ptr reader_error;
 		const long long origin = trace_origin_ns();
-		std::thread chain([&] {
-			try { reconstruct_vertex_list_detached(cx, t, m, order_v, seg_start, seg_level, d_syms + plane_off[data_plane0[fast_l]], origin); }
-			catch (...) { chain_error = std::current_exception(); }
-		});
+		SideThreads chain;
+		chain.spawn([&] { reconstruct_vertex_list_detached(cx, t, m, order_v, seg_start, seg_level, d_syms + plane_off[data_plane0[fast_l]], origin); });
 		try { read_general_planes(m, order_v, hp, ev); } catch (...) { reader_error = std::current_exception(); }
 		chain.join();
 		t.lists[1].data.swap(m.lists[fast_l].data);
-		if (reader_error) std::rethrow_exception(reader_error);
-		if (chain_error) std::rethrow_exception(chain_error);
+		if (reader_error) std::rethrow_exception(reader_error);   // (the reader's error wins over the chain's)
+		chain.rethrow();
 		ev[fast_l].he.clear(); ev[fast_l].slot.clear();
 	}
 	reconstruct_general(cx, m, order_v, ev, [&] {

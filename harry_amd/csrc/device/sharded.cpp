@@ -79,19 +79,14 @@ template <typename F> void run_workers(Context *const *cxs, int n, F &&body)
 	std::vector<const void*> cpus((size_t)n);
 	for (int w = 0; w < n; ++w) cpus[w] = device_cpus(cxs[w]->device);
 	const std::vector<unsigned> budget = worker_thread_budgets(cpus);
-	std::vector<std::thread> th;
-	std::exception_ptr err;
-	std::mutex mu;
+	SideThreads th;
 	for (int w = 0; w < n; ++w)
-		th.emplace_back([&, w] {
-			try {
-				stay_on_node(cpus[w]);
-				set_thread_budget(budget[w]);
-				body(w);
-			} catch (...) { std::lock_guard<std::mutex> g(mu); if (!err) err = std::current_exception(); }
+		th.spawn([&, w] {
+			stay_on_node(cpus[w]);
+			set_thread_budget(budget[w]);
+			body(w);
 		});
-	for (auto &t : th) t.join();
-	if (err) std::rethrow_exception(err);
+	th.rethrow();
 }
 
 // segments of a merged container (a shard without a group contributes none: its part holds a zero count)
@@ -170,36 +165,19 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 		st.twins_ms = ms_since(t0);
 		mark("the whole mesh on the first context's device");
 		BigVec<uint32_t> eface_tab;
-		std::exception_ptr failed;
 		const unsigned nt = host_threads();
-		int ud0 = 0;
-		const bool uniform = m.uniform_degree(ud0) && (ud0 == 3 || ud0 == 4);
-		std::thread tables([&] {
-			try {
-				set_thread_budget(nt);
-				if (!uniform) {
-					eface_tab.resize(m.ne());
-					parallel_for(nt, [&](unsigned t) {
-						const uint32_t fb = (uint32_t)((uint64_t)m.nf * t / nt), fe = (uint32_t)((uint64_t)m.nf * (t + 1) / nt);
-						for (uint32_t f = fb; f < fe; ++f) for (uint32_t h = m.face_off[f]; h < m.face_off[f + 1]; ++h) eface_tab[h] = f;
-					});
-				}
-				marks_p.reset(new WalkState(m.nv, m.nf, nt));
-			} catch (...) { failed = std::current_exception(); }
-		});
 		ComponentAnalysis A;
-		try {
-			if (need_bounds) {
-				const auto tb = Clock::now();
-				bounds_formats();
-				device_bounds(cx0, bm, &m);   // (the records are resident: the scan alone)
-				bounds_ms = ms_since(tb);
-				bounds_done = true;
-			}
-			device_component_analysis(cx0, m, A);
-		} catch (...) { tables.join(); throw; }
-		tables.join();
-		if (failed) std::rethrow_exception(failed);
+		SideThreads tables;
+		tables.spawn([&] { set_thread_budget(nt); marks_p = walk_tables(m, nt, eface_tab); });
+		if (need_bounds) {
+			const auto tb = Clock::now();
+			bounds_formats();
+			device_bounds(cx0, bm, &m);   // (the records are resident: the scan alone)
+			bounds_ms = ms_since(tb);
+			bounds_done = true;
+		}
+		device_component_analysis(cx0, m, A);
+		tables.rethrow();
 		if (A.ncomp >= 2) {
 			shard_plan_from_analysis(m, (uint32_t)n_shards, std::move(A), plan);
 			plan.A.eface = std::move(eface_tab);
@@ -210,25 +188,19 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 	ensure_twins(m);
 	st.twins_ms = ms_since(t0);
 	// ---- the bounds of the whole mesh on the first context, beside the plan on the host threads
-	std::exception_ptr bounds_err;
-	std::thread bounds_thread;
+	SideThreads bounds_thread;
 	if (need_bounds && !bounds_done) {
-		bounds_thread = std::thread([&] {
-			try {
-				const auto tb = Clock::now();
-				Context &cx = *cxs[0];
-				HIP_OK(hipSetDevice(cx.device));
-				bounds_formats();
-				device_bounds(cx, bm, &m);
-				bounds_ms = ms_since(tb);
-			} catch (...) { bounds_err = std::current_exception(); }
+		bounds_thread.spawn([&] {
+			const auto tb = Clock::now();
+			Context &cx = *cxs[0];
+			HIP_OK(hipSetDevice(cx.device));
+			bounds_formats();
+			device_bounds(cx, bm, &m);
+			bounds_ms = ms_since(tb);
 		});
 	}
-	std::exception_ptr plan_err;
-	try { shard_plan(m, (uint32_t)n_shards, plan, true); } catch (...) { plan_err = std::current_exception(); }
-	if (bounds_thread.joinable()) bounds_thread.join();
-	if (plan_err) std::rethrow_exception(plan_err);
-	if (bounds_err) std::rethrow_exception(bounds_err);
+	shard_plan(m, (uint32_t)n_shards, plan, true);
+	bounds_thread.rethrow();
 	}
 	st.plan_ms = ms_since(t0);
 	st.bounds_ms = bounds_ms;
@@ -358,41 +330,36 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 				}
 			}
 			if (shares0) rplans.clear();   // (quantised above, once for the whole lists)
-			std::exception_ptr up_err;
 			double up_ms = 0;
-			std::thread uploader;
-			if (!shares0) uploader = std::thread([&] {
-				try {
-					const auto tu = Clock::now();
-					HIP_OK(hipSetDevice(cx.device));
-					hipStream_t us = cx.stream2;
-					// (the twins go up while this worker's and the others' walks repair some of them in the host array: whichever value
-					// a repaired entry arrives with, every repaired entry is sent again as a (half-edge, twin) pair once its group is
-					// walked -- by the encode's pipeline, or by upload_repaired_twins(patches_only) -- and both wait for these copies)
-					for (const auto &iv : fiv) {
-						const size_t h0 = m.face_off[iv.first], h1 = m.face_off[iv.second];
-						HIP_OK(hipMemcpyAsync(cx.d_foff.as<uint32_t>() + iv.first, m.face_off.data() + iv.first, ((size_t)iv.second - iv.first + 1) * 4, hipMemcpyHostToDevice, us));
-						if (h1 > h0) {
-							HIP_OK(hipMemcpyAsync(cx.d_org.as<uint32_t>() + h0, m.org.data() + h0, (h1 - h0) * 4, hipMemcpyHostToDevice, us));
-							HIP_OK(hipMemcpyAsync(cx.d_twin.as<uint32_t>() + h0, m.twin.data() + h0, (h1 - h0) * 4, hipMemcpyHostToDevice, us));
-						}
-						if (st0) HIP_OK(hipMemcpyAsync(cx.d_rec[0].as<uint8_t>() + iv.first * st0, m.lists[0].data.data() + iv.first * st0, ((size_t)iv.second - iv.first) * st0, hipMemcpyHostToDevice, us));
-						if (cx.res_has_eface) dev::launch_edge_faces(us, cx.d_foff.as<uint32_t>(), iv.second, cx.d_eface.as<uint32_t>(), iv.first);
+			SideThreads uploader;
+			if (!shares0) uploader.spawn([&] {
+				const auto tu = Clock::now();
+				HIP_OK(hipSetDevice(cx.device));
+				hipStream_t us = cx.stream2;
+				// (the twins go up while this worker's and the others' walks repair some of them in the host array: whichever value
+				// a repaired entry arrives with, every repaired entry is sent again as a (half-edge, twin) pair once its group is
+				// walked -- by the encode's pipeline, or by upload_repaired_twins(patches_only) -- and both wait for these copies)
+				for (const auto &iv : fiv) {
+					const size_t h0 = m.face_off[iv.first], h1 = m.face_off[iv.second];
+					HIP_OK(hipMemcpyAsync(cx.d_foff.as<uint32_t>() + iv.first, m.face_off.data() + iv.first, ((size_t)iv.second - iv.first + 1) * 4, hipMemcpyHostToDevice, us));
+					if (h1 > h0) {
+						HIP_OK(hipMemcpyAsync(cx.d_org.as<uint32_t>() + h0, m.org.data() + h0, (h1 - h0) * 4, hipMemcpyHostToDevice, us));
+						HIP_OK(hipMemcpyAsync(cx.d_twin.as<uint32_t>() + h0, m.twin.data() + h0, (h1 - h0) * 4, hipMemcpyHostToDevice, us));
 					}
-					if (st1) for (const auto &iv : viv)
-						HIP_OK(hipMemcpyAsync(cx.d_rec[1].as<uint8_t>() + iv.first * st1, m.lists[1].data.data() + iv.first * st1, ((size_t)iv.second - iv.first) * st1, hipMemcpyHostToDevice, us));
-					for (const ListPlan &rp : rplans)
-						for (const auto &iv : rp.l == 0 ? fiv : viv)
-							dev::launch_requant(us, cx.d_rec[rp.l].as<uint8_t>() + iv.first * rp.stride, iv.second - iv.first, (int)rp.stride, rp.plan);
-					HIP_OK(hipStreamSynchronize(us));
-					up_ms = ms_since(tu);
-				} catch (...) { up_err = std::current_exception(); }
+					if (st0) HIP_OK(hipMemcpyAsync(cx.d_rec[0].as<uint8_t>() + iv.first * st0, m.lists[0].data.data() + iv.first * st0, ((size_t)iv.second - iv.first) * st0, hipMemcpyHostToDevice, us));
+					if (cx.res_has_eface) dev::launch_edge_faces(us, cx.d_foff.as<uint32_t>(), iv.second, cx.d_eface.as<uint32_t>(), iv.first);
+				}
+				if (st1) for (const auto &iv : viv)
+					HIP_OK(hipMemcpyAsync(cx.d_rec[1].as<uint8_t>() + iv.first * st1, m.lists[1].data.data() + iv.first * st1, ((size_t)iv.second - iv.first) * st1, hipMemcpyHostToDevice, us));
+				for (const ListPlan &rp : rplans)
+					for (const auto &iv : rp.l == 0 ? fiv : viv)
+						dev::launch_requant(us, cx.d_rec[rp.l].as<uint8_t>() + iv.first * rp.stride, iv.second - iv.first, (int)rp.stride, rp.plan);
+				HIP_OK(hipStreamSynchronize(us));
+				up_ms = ms_since(tu);
 			});
-			struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join{ uploader };
 			t = Clock::now();
 			const InPlaceShard ip{ &m, &part, eface, &marks, &fiv, [&] {
-				if (uploader.joinable()) uploader.join();
-				if (up_err) std::rethrow_exception(up_err);
+				uploader.rethrow();
 				w_upload[w] += up_ms;
 			} };
 			encode_chunked(cx, sk, chunk_syms, parts[s], &ip);

@@ -325,17 +325,16 @@ struct SpanUploader : SpanDone {
 	std::deque<Range> todo;
 	bool closing = false;
 	uint64_t faces_up = 0, he_up = 0, v_up = 0;
-	std::exception_ptr error;
 	// Three threads take spans off the list, each with a stream of its own: a copy from pageable memory holds its thread until the
 	// runtime has staged it (10 GB/s a thread), and one thread was 16 - 20 ms behind the replay of the configs[3] mesh at its end
 	// (2.7 GB in 125 ms; 249 spans still queued), two 13 ms (165 spans), three none: decode 175 -> 163 -> 149 ms; a fourth thread, or
 	// replay threads given up for them, gain nothing (16 CPUs of quota: `profiles/r4/decode_uploaders.txt`)
 	static constexpr int kWorkers = Context::kUploadStreams + 1;
-	std::thread worker[kWorkers];
 	hipStream_t up_stream[kWorkers] = {};
 	std::mutex mu_prefix;                  // after_upload / launch_pending: one worker at a time
 	Clock::time_point t_origin = g_t0;     // (the decode's clock: g_t0 is per thread)
 	uint32_t eface_upto = 0;               // faces whose half-edge -> face entries are computed on the device
+	SideThreads workers;                   // (last: joined before anything above goes)
 	SpanUploader(Context &c, Mesh &mesh, const OrderVec &ov, ChainBatches *cb = nullptr, hipEvent_t planes = nullptr) : cx(c), m(mesh), order_v(ov), batches(cb), planes_ready(planes)
 	{
 		cx.ensure_second_stream();
@@ -362,8 +361,8 @@ struct SpanUploader : SpanDone {
 		}
 		const void *node = callers_node_cpus();
 		HRY_MARK(t_origin, "span uploaders' arrays and streams ready");
-		for (int k = 0; k < kWorkers; ++k) worker[k] = std::thread([this, node, k] {
-			try {
+		try {
+			for (int k = 0; k < kWorkers; ++k) workers.spawn([this, node, k] {
 				stay_on_node(node);
 				HIP_OK(hipSetDevice(cx.device));
 				for (;;) {
@@ -380,8 +379,8 @@ struct SpanUploader : SpanDone {
 					if (batches && !ending) { std::lock_guard<std::mutex> g(mu_prefix); after_upload(std::move(r)); }   // (once the replay has ended the caller launches the rest)
 				}
 				HIP_OK(hipStreamSynchronize(up_stream[k]));
-			} catch (...) { std::lock_guard<std::mutex> g(mu); if (!error) error = std::current_exception(); }
-		});
+			});
+		} catch (...) { close(); throw; }   // (the workers that did start go home)
 	}
 	void copy_range(const Range &r, hipStream_t st)
 	{
@@ -454,27 +453,23 @@ struct SpanUploader : SpanDone {
 		// The replay is over and its thread has nothing to do: it takes spans off the list too, on the stream the attribute planes
 		// were decoded on (idle by now) -- the one uploader used to be 25 - 30 ms behind at this point on the configs[3] mesh.
 		// (No more batches from here on: the caller launches what is left.)
-		bool failed;
-		{ std::lock_guard<std::mutex> g(mu); failed = (bool)error; }   // (the uploaders set it under the same lock)
-		if (!failed) {
-			try {
-				for (;;) {
-					Range r;
-					{
-						std::lock_guard<std::mutex> g(mu);
-						if (todo.empty()) break;
-						r = std::move(todo.back()); todo.pop_back();
-					}
-					copy_range(r, cx.stream3 ? cx.stream3 : cx.stream2);
+		if (!workers.error()) {
+			for (;;) {
+				Range r;
+				{
 					std::lock_guard<std::mutex> g(mu);
-					faces_up += r.f1 - r.f0; he_up += r.h1 - r.h0; v_up += r.v1 - r.v0;
+					if (todo.empty()) break;
+					r = std::move(todo.back()); todo.pop_back();
 				}
-				if (cx.stream3) HIP_OK(hipStreamSynchronize(cx.stream3));
-			} catch (...) { for (auto &w : worker) if (w.joinable()) w.join(); throw; }
+				copy_range(r, cx.stream3 ? cx.stream3 : cx.stream2);
+				std::lock_guard<std::mutex> g(mu);
+				faces_up += r.f1 - r.f0; he_up += r.h1 - r.h0; v_up += r.v1 - r.v0;
+			}
+			if (cx.stream3) HIP_OK(hipStreamSynchronize(cx.stream3));
 		}
-		for (auto &w : worker) if (w.joinable()) w.join();
+		workers.join();
 		if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  every span is on the device\n", ms_since(t_origin));
-		if (error) return false;
+		if (workers.error()) return false;
 		if (faces_up != m.nf || he_up != m.declared_ne || v_up != order_v.size() || order_v.size() != m.nv) return false;
 		if (batches) return true;   // (the first offset went up before the first span; the main stream may still be running a batch of chains: no wait)
 		const uint32_t zero = 0;
@@ -491,7 +486,9 @@ struct SpanUploader : SpanDone {
 		m.twins_pending = false;
 		cx.resident_token = 0;
 	}
-	~SpanUploader() { { std::lock_guard<std::mutex> g(mu); closing = true; todo.clear(); } cv.notify_all(); for (auto &w : worker) if (w.joinable()) w.join(); }
+	// the workers stop at the next range (the caller's way out); the member's destructor joins them
+	void close() { { std::lock_guard<std::mutex> g(mu); closing = true; todo.clear(); } cv.notify_all(); }
+	~SpanUploader() { close(); }
 };
 
 static bool pipelined_decode_applicable(const Mesh &m, const std::vector<RestartPoint> &restarts, const PlaneView *conn,
@@ -539,17 +536,16 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	// Round 6: border snapshots in the directory (restart points inside the component): this thread replays the stretch up to the
 	// first one and publishes as before, the stretches behind the snapshots run on helper threads meanwhile and are joined when
 	// all have finished (cbm_replay.hpp SnapshotSpans) -- the replay of ONE component on several cores
-	std::unique_ptr<SnapshotSpans> spans;
-	if (ud == 3 && !snaps_in.empty() && host_threads() > 1 && !env_on("HRY_NO_SNAPSHOT_REPLAY") && !env_on("HRY_GENERIC_REPLAY")) spans.reset(new SnapshotSpans(*m, conn, snaps_in, order_v.data()));   // (sizes m->twin)
-	else m->twin.resize(ne);
 	BigVec<uint16_t> seen(nv, 0);
 	ReplayLive live;
+	std::unique_ptr<SnapshotSpans> spans;   // (after `live`: its helpers announce there until they are joined)
+	if (ud == 3 && !snaps_in.empty() && host_threads() > 1 && !env_on("HRY_NO_SNAPSHOT_REPLAY") && !env_on("HRY_GENERIC_REPLAY")) spans.reset(new SnapshotSpans(*m, conn, snaps_in, order_v.data()));   // (sizes m->twin)
+	else m->twin.resize(ne);
 	live.on_border.assign(nv, 0);
 	live.pending.reserve(1 << 16);
 	HRY_MARK(g_t0, "host arrays allocated");
 	live.interval = std::max(1u, (uint32_t)env_uint("HRY_PIPELINE_FACES", live.interval));
 
-	std::exception_ptr consumer_error;
 	std::vector<SliceClock> clocks;
 	// replay and chain take about the same time per vertex: what is left behind the replay is the last slice (16 Ki: the consumer's launches become the longer path)
 	const uint32_t min_slice = std::max(64u, (uint32_t)env_uint("HRY_PIPELINE_SLICE", 1u << 15));
@@ -573,191 +569,190 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	const int vstride = ldv.stride;
 	const void *near = callers_neighbour_cpus();   // the consumer polls: near the replay's caches, but not on its core
 	const void *node = near ? near : callers_node_cpus();
-	std::thread consumer([&, node] {
-		try {
-			stay_on_node(node);
-			HIP_OK(hipSetDevice(cx.device));
-			uint32_t f_up = 0, he_up = 0, v_done = 0, v_up = 0;   // v_up: decode order on the device up to this vertex
-			uint64_t seen_seq = 0, seen_pub = 0;
-			std::vector<uint32_t> patches;
-			std::vector<ReplayLive::Range> ranges, ranges_up;   // stretches of helper threads: announced / on the device (round 6)
-			// the helpers' pinned copies go up on a stream of their own -- on the uploads' stream (stream2) the candidates of the next
-			// slice of the FIRST stretch sat behind a millisecond of the other stretches' transfers -- with an event each, which
-			// stream2 waits for when a publication reaches into them
-			std::vector<hipEvent_t> mir_ev;        // per entry of ranges_up (nullptr: came through stream2)
-			std::vector<char> mir_waited;          // per entry of mir_ev: the second stream waits for it already
-			if (!cx.up_stream[0]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[0], hipStreamNonBlocking));
-			const hipStream_t mir_stream = cx.up_stream[0];
-			if (!cx.up_stream[1]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[1], hipStreamNonBlocking));
-			const hipStream_t down_stream = cx.up_stream[1];   // the slices' records on their way down
-			struct DropEvents { std::vector<hipEvent_t> &v; ~DropEvents() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } drop_events{ mir_ev };
-			DevBuf &d_patch = cx.d_patch;   // persistent and sized before the pipeline starts: growing it here would synchronise the device (hipFree / hipMalloc) in mid-flight
-			Stager up(cx, cx.stream2);
-			hipEvent_t prepared;
-			HIP_OK(hipEventCreateWithFlags(&prepared, hipEventDisableTiming));
-			// The consumer acts on a publication only when `lag` newer ones exist: the newest part of the arrays is still hot
-			// in the replay thread's cache (twins of the last ring keep changing), copying it there would slow the replay down.
-			std::deque<ReplayLive::Pub> hist;
-			constexpr uint32_t lag = 2;
-			auto drain = [&](bool wait) {
-				while (!landing.empty()) {
-					Landing &L = landing.front();
-					if (wait) HIP_OK(hipEventSynchronize(L.ev));
-					else if (hipEventQuery(L.ev) != hipSuccess) break;
-					memcpy(m->lists[1].data.data() + L.off, (const uint8_t*)cx.h_down + L.off, L.len);
-					if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  records of vertices [%zu, %zu) landed\n", ms_since(t_begin), L.off / vstride, (L.off + L.len) / vstride);
-					(void)hipEventDestroy(L.ev);
-					landing.pop_front();
+	SideThreads consumer;
+	consumer.spawn([&, node] {
+		stay_on_node(node);
+		HIP_OK(hipSetDevice(cx.device));
+		uint32_t f_up = 0, he_up = 0, v_done = 0, v_up = 0;   // v_up: decode order on the device up to this vertex
+		uint64_t seen_seq = 0, seen_pub = 0;
+		std::vector<uint32_t> patches;
+		std::vector<ReplayLive::Range> ranges, ranges_up;   // stretches of helper threads: announced / on the device (round 6)
+		// the helpers' pinned copies go up on a stream of their own -- on the uploads' stream (stream2) the candidates of the next
+		// slice of the FIRST stretch sat behind a millisecond of the other stretches' transfers -- with an event each, which
+		// stream2 waits for when a publication reaches into them
+		std::vector<hipEvent_t> mir_ev;        // per entry of ranges_up (nullptr: came through stream2)
+		std::vector<char> mir_waited;          // per entry of mir_ev: the second stream waits for it already
+		if (!cx.up_stream[0]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[0], hipStreamNonBlocking));
+		const hipStream_t mir_stream = cx.up_stream[0];
+		if (!cx.up_stream[1]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[1], hipStreamNonBlocking));
+		const hipStream_t down_stream = cx.up_stream[1];   // the slices' records on their way down
+		struct DropEvents { std::vector<hipEvent_t> &v; ~DropEvents() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } drop_events{ mir_ev };
+		DevBuf &d_patch = cx.d_patch;   // persistent and sized before the pipeline starts: growing it here would synchronise the device (hipFree / hipMalloc) in mid-flight
+		Stager up(cx, cx.stream2);
+		hipEvent_t prepared;
+		HIP_OK(hipEventCreateWithFlags(&prepared, hipEventDisableTiming));
+		// The consumer acts on a publication only when `lag` newer ones exist: the newest part of the arrays is still hot
+		// in the replay thread's cache (twins of the last ring keep changing), copying it there would slow the replay down.
+		std::deque<ReplayLive::Pub> hist;
+		constexpr uint32_t lag = 2;
+		auto drain = [&](bool wait) {
+			while (!landing.empty()) {
+				Landing &L = landing.front();
+				if (wait) HIP_OK(hipEventSynchronize(L.ev));
+				else if (hipEventQuery(L.ev) != hipSuccess) break;
+				memcpy(m->lists[1].data.data() + L.off, (const uint8_t*)cx.h_down + L.off, L.len);
+				if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  records of vertices [%zu, %zu) landed\n", ms_since(t_begin), L.off / vstride, (L.off + L.len) / vstride);
+				(void)hipEventDestroy(L.ev);
+				landing.pop_front();
+			}
+		};
+		for (;;) {
+			ReplayLive::Pub newest;
+			drain(false);
+			{
+				// polled: the chain's hand-over of the next slice should not wait for a wake-up either (a decode lasts milliseconds)
+				for (uint32_t spins = 0; live.announced.load(std::memory_order_acquire) == seen_seq; ++spins) {
+					if (spins < 2000) __builtin_ia32_pause();
+					else { drain(false); std::this_thread::sleep_for(std::chrono::microseconds(20)); }
 				}
-			};
-			for (;;) {
-				ReplayLive::Pub newest;
-				drain(false);
-				{
-					// polled: the chain's hand-over of the next slice should not wait for a wake-up either (a decode lasts milliseconds)
-					for (uint32_t spins = 0; live.announced.load(std::memory_order_acquire) == seen_seq; ++spins) {
-						if (spins < 2000) __builtin_ia32_pause();
-						else { drain(false); std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-					}
-					std::unique_lock<std::mutex> lk(live.mu);
-					newest = live.pub;
-					patches.insert(patches.end(), live.patches.begin(), live.patches.end());
-					live.patches.clear();
-					ranges.insert(ranges.end(), live.ranges.begin(), live.ranges.end());
-					live.ranges.clear();
-					seen_seq = newest.seq;
+				std::unique_lock<std::mutex> lk(live.mu);
+				newest = live.pub;
+				patches.insert(patches.end(), live.patches.begin(), live.patches.end());
+				live.patches.clear();
+				ranges.insert(ranges.end(), live.ranges.begin(), live.ranges.end());
+				live.ranges.clear();
+				seen_seq = newest.seq;
+			}
+			if (newest.failed) break;
+			// a helper thread's finished stretch goes up at once (nobody is writing there any more)
+			for (const ReplayLive::Range &r : ranges) {
+				hipEvent_t rev = nullptr;
+				if (r.mirrored) {   // (the helper left a pinned copy: four transfers, no copy on this thread)
+					const uint32_t *mf = cx.h_mirror.as<uint32_t>(), *mo = mf + (size_t)nf + 1, *mt = mo + ne, *mv = mt + ne;
+					// one kernel reads the four ranges from the pinned mirrors
+					PullRanges pr{};
+					pr.dst[0] = cx.d_foff.as<uint32_t>() + r.f0 + 1; pr.src[0] = mf + r.f0 + 1; pr.words[0] = r.f1 - r.f0;
+					pr.dst[1] = cx.d_org.as<uint32_t>() + r.h0; pr.src[1] = mo + r.h0; pr.words[1] = r.h1 - r.h0;
+					pr.dst[2] = cx.d_twin.as<uint32_t>() + r.h0; pr.src[2] = mt + r.h0; pr.words[2] = r.h1 - r.h0;
+					pr.dst[3] = cx.d_order_v.as<uint32_t>() + r.v0; pr.src[3] = mv + r.v0; pr.words[3] = r.v1 - r.v0;
+					launch_pull_ranges(mir_stream, pr);
+					HIP_OK(hipEventCreateWithFlags(&rev, hipEventDisableTiming));
+					HIP_OK(hipEventRecord(rev, mir_stream));
+				} else {
+				if (r.f1 > r.f0) up.put(cx.d_foff.as<uint32_t>() + r.f0 + 1, m->face_off.data() + r.f0 + 1, ((size_t)r.f1 - r.f0) * 4);
+				if (r.h1 > r.h0) {
+					up.put(cx.d_org.as<uint32_t>() + r.h0, m->org.data() + r.h0, ((size_t)r.h1 - r.h0) * 4);
+					up.put(cx.d_twin.as<uint32_t>() + r.h0, m->twin.data() + r.h0, ((size_t)r.h1 - r.h0) * 4);
 				}
-				if (newest.failed) break;
-				// a helper thread's finished stretch goes up at once (nobody is writing there any more)
-				for (const ReplayLive::Range &r : ranges) {
-					hipEvent_t rev = nullptr;
-					if (r.mirrored) {   // (the helper left a pinned copy: four transfers, no copy on this thread)
-						const uint32_t *mf = cx.h_mirror.as<uint32_t>(), *mo = mf + (size_t)nf + 1, *mt = mo + ne, *mv = mt + ne;
-						// one kernel reads the four ranges from the pinned mirrors
-						PullRanges pr{};
-						pr.dst[0] = cx.d_foff.as<uint32_t>() + r.f0 + 1; pr.src[0] = mf + r.f0 + 1; pr.words[0] = r.f1 - r.f0;
-						pr.dst[1] = cx.d_org.as<uint32_t>() + r.h0; pr.src[1] = mo + r.h0; pr.words[1] = r.h1 - r.h0;
-						pr.dst[2] = cx.d_twin.as<uint32_t>() + r.h0; pr.src[2] = mt + r.h0; pr.words[2] = r.h1 - r.h0;
-						pr.dst[3] = cx.d_order_v.as<uint32_t>() + r.v0; pr.src[3] = mv + r.v0; pr.words[3] = r.v1 - r.v0;
-						launch_pull_ranges(mir_stream, pr);
-						HIP_OK(hipEventCreateWithFlags(&rev, hipEventDisableTiming));
-						HIP_OK(hipEventRecord(rev, mir_stream));
-					} else {
-					if (r.f1 > r.f0) up.put(cx.d_foff.as<uint32_t>() + r.f0 + 1, m->face_off.data() + r.f0 + 1, ((size_t)r.f1 - r.f0) * 4);
-					if (r.h1 > r.h0) {
-						up.put(cx.d_org.as<uint32_t>() + r.h0, m->org.data() + r.h0, ((size_t)r.h1 - r.h0) * 4);
-						up.put(cx.d_twin.as<uint32_t>() + r.h0, m->twin.data() + r.h0, ((size_t)r.h1 - r.h0) * 4);
-					}
-					if (r.v1 > r.v0) up.put(cx.d_order_v.as<uint32_t>() + r.v0, order_v.data() + r.v0, ((size_t)r.v1 - r.v0) * 4);
-					}
-					if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  a helper's stretch (faces %u .. %u) is on its way up\n", ms_since(t_begin), r.f0, r.f1);
-					ranges_up.push_back(r);
-					mir_ev.push_back(rev);
+				if (r.v1 > r.v0) up.put(cx.d_order_v.as<uint32_t>() + r.v0, order_v.data() + r.v0, ((size_t)r.v1 - r.v0) * 4);
 				}
-				ranges.clear();
-				if (newest.n_pub == seen_pub) continue;   // (a helper's announcement only: no new publication of the replaying thread)
-				seen_pub = newest.n_pub;
-				hist.push_back(newest);
-				if (!newest.done && !newest.joined && hist.size() <= lag) continue;
-				const ReplayLive::Pub P = newest.done || newest.joined ? newest : hist.front();
-				while (!hist.empty() && hist.front().n_pub <= P.n_pub) hist.pop_front();
-				// (a publication behind the replaying thread's own stretch rests on the helpers' stretches: their transfers first)
-				// (only those that lie below the publication's faces: the fans of its final vertices end there.  Waiting for every
-				// transfer under way -- they arrive in the order the helpers finish, 24 MB within 0.3 ms of each other, a millisecond
-				// on the link -- kept the chain idle until the LAST stretch was up)
-				if (P.joined || P.done) {
-					mir_waited.resize(mir_ev.size(), 0);
-					for (size_t i = 0; i < mir_ev.size(); ++i)
-						if (!mir_waited[i] && mir_ev[i] && (P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
+				if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  a helper's stretch (faces %u .. %u) is on its way up\n", ms_since(t_begin), r.f0, r.f1);
+				ranges_up.push_back(r);
+				mir_ev.push_back(rev);
+			}
+			ranges.clear();
+			if (newest.n_pub == seen_pub) continue;   // (a helper's announcement only: no new publication of the replaying thread)
+			seen_pub = newest.n_pub;
+			hist.push_back(newest);
+			if (!newest.done && !newest.joined && hist.size() <= lag) continue;
+			const ReplayLive::Pub P = newest.done || newest.joined ? newest : hist.front();
+			while (!hist.empty() && hist.front().n_pub <= P.n_pub) hist.pop_front();
+			// (a publication behind the replaying thread's own stretch rests on the helpers' stretches: their transfers first)
+			// (only those that lie below the publication's faces: the fans of its final vertices end there.  Waiting for every
+			// transfer under way -- they arrive in the order the helpers finish, 24 MB within 0.3 ms of each other, a millisecond
+			// on the link -- kept the chain idle until the LAST stretch was up)
+			if (P.joined || P.done) {
+				mir_waited.resize(mir_ev.size(), 0);
+				for (size_t i = 0; i < mir_ev.size(); ++i)
+					if (!mir_waited[i] && mir_ev[i] && (P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
+			}
+			// finished part of the connectivity -- but for what the helpers' stretches have brought up already
+			if (P.faces > f_up) {
+				std::vector<ReplayLive::Range> by_face(ranges_up);
+				std::sort(by_face.begin(), by_face.end(), [](const ReplayLive::Range &a, const ReplayLive::Range &b) { return a.f0 < b.f0; });
+				uint32_t f = f_up, h = he_up;
+				auto copy_upto = [&](uint32_t f_to, uint32_t he_to) {
+					if (f_to <= f) return;
+					up.put(cx.d_foff.as<uint32_t>() + f, m->face_off.data() + f, ((size_t)f_to - f + 1) * 4);
+					up.put(cx.d_org.as<uint32_t>() + h, m->org.data() + h, ((size_t)he_to - h) * 4);
+					up.put(cx.d_twin.as<uint32_t>() + h, m->twin.data() + h, ((size_t)he_to - h) * 4);
+				};
+				for (const ReplayLive::Range &r : by_face) {
+					if (r.f1 <= f || r.f0 >= P.faces) continue;
+					copy_upto(std::min(r.f0, P.faces), std::min(r.h0, P.he));
+					f = std::max(f, r.f1); h = std::max(h, r.h1);
 				}
-				// finished part of the connectivity -- but for what the helpers' stretches have brought up already
-				if (P.faces > f_up) {
+				copy_upto(P.faces, P.he);
+				f_up = P.faces; he_up = P.he;
+			}
+			// vertices that can no longer change: whole tiles, slices of a useful size
+			const uint32_t v_hi = P.done ? nv : (P.upto & ~63u);
+			if (v_hi > v_done && (P.done || P.joined || v_hi - v_done >= std::min(min_slice, std::max(first_slice, v_done)))) {
+				// late links of edges that were copied before (a patch of an edge that is copied later is harmless: the copy
+				// carries the final value too)
+				if (!patches.empty()) {
+					d_patch.ensure(patches.size() * 4);
+					up.put(d_patch.p, patches.data(), patches.size() * 4);
+					launch_scatter_u32(cx.stream2, d_patch.as<uint32_t>(), (uint32_t)(patches.size() / 2), cx.d_twin.as<uint32_t>());
+					patches.clear();
+				}
+				{   // the decode order of the slice's vertices (the helpers' stretches brought theirs)
 					std::vector<ReplayLive::Range> by_face(ranges_up);
 					std::sort(by_face.begin(), by_face.end(), [](const ReplayLive::Range &a, const ReplayLive::Range &b) { return a.f0 < b.f0; });
-					uint32_t f = f_up, h = he_up;
-					auto copy_upto = [&](uint32_t f_to, uint32_t he_to) {
-						if (f_to <= f) return;
-						up.put(cx.d_foff.as<uint32_t>() + f, m->face_off.data() + f, ((size_t)f_to - f + 1) * 4);
-						up.put(cx.d_org.as<uint32_t>() + h, m->org.data() + h, ((size_t)he_to - h) * 4);
-						up.put(cx.d_twin.as<uint32_t>() + h, m->twin.data() + h, ((size_t)he_to - h) * 4);
-					};
+					uint32_t v = std::max(v_done, v_up);
 					for (const ReplayLive::Range &r : by_face) {
-						if (r.f1 <= f || r.f0 >= P.faces) continue;
-						copy_upto(std::min(r.f0, P.faces), std::min(r.h0, P.he));
-						f = std::max(f, r.f1); h = std::max(h, r.h1);
+						if (r.v1 <= v || r.v0 >= v_hi) continue;
+						if (r.v0 > v) up.put(cx.d_order_v.as<uint32_t>() + v, order_v.data() + v, ((size_t)std::min(r.v0, v_hi) - v) * 4);
+						v = std::max(v, r.v1);
 					}
-					copy_upto(P.faces, P.he);
-					f_up = P.faces; he_up = P.he;
+					if (v_hi > v) up.put(cx.d_order_v.as<uint32_t>() + v, order_v.data() + v, ((size_t)v_hi - v) * 4);
+					v_up = std::max(v_up, v_hi);
 				}
-				// vertices that can no longer change: whole tiles, slices of a useful size
-				const uint32_t v_hi = P.done ? nv : (P.upto & ~63u);
-				if (v_hi > v_done && (P.done || P.joined || v_hi - v_done >= std::min(min_slice, std::max(first_slice, v_done)))) {
-					// late links of edges that were copied before (a patch of an edge that is copied later is harmless: the copy
-					// carries the final value too)
-					if (!patches.empty()) {
-						d_patch.ensure(patches.size() * 4);
-						up.put(d_patch.p, patches.data(), patches.size() * 4);
-						launch_scatter_u32(cx.stream2, d_patch.as<uint32_t>(), (uint32_t)(patches.size() / 2), cx.d_twin.as<uint32_t>());
-						patches.clear();
+				// what the kernels of this slice may follow: the half-edges that are on the device now (a link into the part
+				// that is not -- made after the publication this slice rests on -- reads as a border, which is what it was then)
+				ConnView cvs = cv;
+				cvs.ne = he_up;
+				// (round 6: what is left when the replay is done -- since its stretches run side by side, most of the mesh -- goes in
+				// pieces: a piece's records come down while the next piece's chain runs, and its candidates are found beside the chain
+				// of the piece before)
+				const uint32_t piece = (P.done || P.joined) && v_hi - v_done > 3 * last_piece ? last_piece : v_hi - v_done;
+				for (uint32_t v_lo = v_done; v_lo < v_hi;) {
+					const uint32_t v_to = v_hi - v_lo <= piece + piece / 2 ? v_hi : v_lo + piece;
+					SliceClock ck;
+					HIP_OK(hipEventCreate(&ck.a)); HIP_OK(hipEventCreate(&ck.b)); HIP_OK(hipEventCreate(&ck.p0)); HIP_OK(hipEventCreate(&ck.p1));
+					HIP_OK(hipEventRecord(ck.p0, cx.stream2));
+					launch_slice_prepare(cx.stream2, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec);
+					HIP_OK(hipEventRecord(ck.p1, cx.stream2));
+					HIP_OK(hipEventRecord(prepared, cx.stream2));
+					HIP_OK(hipStreamWaitEvent(cx.stream, prepared, 0));
+					// the residual codes of this slice: the groups of attribute streams that end inside it or before
+					while (attr_waited < Context::kAttrGroups && (attr_waited == 0 || attr_upto[attr_waited - 1] < v_to)) HIP_OK(hipStreamWaitEvent(cx.stream, cx.attr_ev[attr_waited++], 0));
+					HIP_OK(hipEventRecord(ck.a, cx.stream));
+					launch_slice_chain(cx.stream, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>());
+					HIP_OK(hipEventRecord(ck.b, cx.stream));
+					clocks.push_back(ck);
+					{
+						// (the records come down on a stream of their own, behind the slice's chain: on the chain's stream the next
+						// slice's chain waited for the copy -- 0.1 ms a slice, 30 ms of the 28 M-triangle mesh's 214 slices)
+						Landing L;
+						L.off = (size_t)v_lo * vstride; L.len = ((size_t)v_to - v_lo) * vstride;
+						HIP_OK(hipStreamWaitEvent(down_stream, ck.b, 0));
+						HIP_OK(hipMemcpyAsync((uint8_t*)cx.h_down + L.off, cx.d_rec[1].as<uint8_t>() + L.off, L.len, hipMemcpyDeviceToHost, down_stream));
+						HIP_OK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
+						HIP_OK(hipEventRecord(L.ev, down_stream));
+						landing.push_back(L);
 					}
-					{   // the decode order of the slice's vertices (the helpers' stretches brought theirs)
-						std::vector<ReplayLive::Range> by_face(ranges_up);
-						std::sort(by_face.begin(), by_face.end(), [](const ReplayLive::Range &a, const ReplayLive::Range &b) { return a.f0 < b.f0; });
-						uint32_t v = std::max(v_done, v_up);
-						for (const ReplayLive::Range &r : by_face) {
-							if (r.v1 <= v || r.v0 >= v_hi) continue;
-							if (r.v0 > v) up.put(cx.d_order_v.as<uint32_t>() + v, order_v.data() + v, ((size_t)std::min(r.v0, v_hi) - v) * 4);
-							v = std::max(v, r.v1);
-						}
-						if (v_hi > v) up.put(cx.d_order_v.as<uint32_t>() + v, order_v.data() + v, ((size_t)v_hi - v) * 4);
-						v_up = std::max(v_up, v_hi);
-					}
-					// what the kernels of this slice may follow: the half-edges that are on the device now (a link into the part
-					// that is not -- made after the publication this slice rests on -- reads as a border, which is what it was then)
-					ConnView cvs = cv;
-					cvs.ne = he_up;
-					// (round 6: what is left when the replay is done -- since its stretches run side by side, most of the mesh -- goes in
-					// pieces: a piece's records come down while the next piece's chain runs, and its candidates are found beside the chain
-					// of the piece before)
-					const uint32_t piece = (P.done || P.joined) && v_hi - v_done > 3 * last_piece ? last_piece : v_hi - v_done;
-					for (uint32_t v_lo = v_done; v_lo < v_hi;) {
-						const uint32_t v_to = v_hi - v_lo <= piece + piece / 2 ? v_hi : v_lo + piece;
-						SliceClock ck;
-						HIP_OK(hipEventCreate(&ck.a)); HIP_OK(hipEventCreate(&ck.b)); HIP_OK(hipEventCreate(&ck.p0)); HIP_OK(hipEventCreate(&ck.p1));
-						HIP_OK(hipEventRecord(ck.p0, cx.stream2));
-						launch_slice_prepare(cx.stream2, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec);
-						HIP_OK(hipEventRecord(ck.p1, cx.stream2));
-						HIP_OK(hipEventRecord(prepared, cx.stream2));
-						HIP_OK(hipStreamWaitEvent(cx.stream, prepared, 0));
-						// the residual codes of this slice: the groups of attribute streams that end inside it or before
-						while (attr_waited < Context::kAttrGroups && (attr_waited == 0 || attr_upto[attr_waited - 1] < v_to)) HIP_OK(hipStreamWaitEvent(cx.stream, cx.attr_ev[attr_waited++], 0));
-						HIP_OK(hipEventRecord(ck.a, cx.stream));
-						launch_slice_chain(cx.stream, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>());
-						HIP_OK(hipEventRecord(ck.b, cx.stream));
-						clocks.push_back(ck);
-						{
-							// (the records come down on a stream of their own, behind the slice's chain: on the chain's stream the next
-							// slice's chain waited for the copy -- 0.1 ms a slice, 30 ms of the 28 M-triangle mesh's 214 slices)
-							Landing L;
-							L.off = (size_t)v_lo * vstride; L.len = ((size_t)v_to - v_lo) * vstride;
-							HIP_OK(hipStreamWaitEvent(down_stream, ck.b, 0));
-							HIP_OK(hipMemcpyAsync((uint8_t*)cx.h_down + L.off, cx.d_rec[1].as<uint8_t>() + L.off, L.len, hipMemcpyDeviceToHost, down_stream));
-							HIP_OK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
-							HIP_OK(hipEventRecord(L.ev, down_stream));
-							landing.push_back(L);
-						}
-						if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  slice [%u, %u) enqueued (replay at face %u)\n", ms_since(t_begin), v_lo, v_to, newest.faces);
-						v_lo = v_to;
-						drain(false);
-					}
-					v_done = v_hi;
+					if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  slice [%u, %u) enqueued (replay at face %u)\n", ms_since(t_begin), v_lo, v_to, newest.faces);
+					v_lo = v_to;
+					drain(false);
 				}
-				if (P.done) break;
+				v_done = v_hi;
 			}
-			up.flush();
-			drain(true);
-			(void)hipEventDestroy(prepared);
-		} catch (...) { consumer_error = std::current_exception(); }
+			if (P.done) break;
+		}
+		up.flush();
+		drain(true);
+		(void)hipEventDestroy(prepared);
 	});
 
 	// ---- the replay itself (this thread)
@@ -821,12 +816,12 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	if (trace_on()) fprintf(stderr, "[hry] %u publications, %.3f ms inside publish()\n", live.n_publish, live.t_publish_ms);
 	consumer.join();
 	auto drop_clocks = [&] { for (auto &c : clocks) { (void)hipEventDestroy(c.a); (void)hipEventDestroy(c.b); (void)hipEventDestroy(c.p0); (void)hipEventDestroy(c.p1); } };
-	if (replay_error || consumer_error) {
+	if (const std::exception_ptr failed = replay_error ? replay_error : consumer.error()) {
 		(void)hipStreamSynchronize(cx.stream); (void)hipStreamSynchronize(cx.stream2);
 		for (auto &u : cx.up_stream) if (u) (void)hipStreamSynchronize(u);
 		drop_clocks();
 		for (auto &L : landing) (void)hipEventDestroy(L.ev);
-		std::rethrow_exception(replay_error ? replay_error : consumer_error);
+		std::rethrow_exception(failed);
 	}
 	order_v.resize(cur.next_id);
 	for (; attr_waited < Context::kAttrGroups; ++attr_waited) HIP_OK(hipStreamWaitEvent(cx.stream, cx.attr_ev[attr_waited], 0));
@@ -1164,7 +1159,7 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 			SpanUploader up(cx, *m, order_v, batches.get(), cx.ev_x[0]);
 			cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, &up, &snaps);
 			conn_resident = up.finish();
-			if (up.error) std::rethrow_exception(up.error);
+			up.workers.rethrow();
 			if (batches && conn_resident) { up.finish_edge_faces(cx.stream); batches->conn_adopted = true; }
 		} else cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, nullptr, &snaps);
 		cx.timing.host_walk_ms = ms_since(t_walk);

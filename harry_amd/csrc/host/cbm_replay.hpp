@@ -161,11 +161,11 @@ struct SnapshotSpans {
 	std::vector<const SnapshotPoint*> seeds;
 	std::vector<uint32_t> sym_base;
 	std::vector<BorderEnd> ends;
-	std::vector<std::thread> helpers;
 	std::atomic<size_t> next{ 1 };
 	std::mutex mu;
 	std::condition_variable cv;
-	std::exception_ptr failed;
+	bool failed = false;      // (under mu) a helper has thrown: finish() wakes and rethrows it
+	bool cancelled = false;   // (under mu) cancel(): no helper starts a stretch or announces one from then on
 	// checks the snapshots against the header's sizes, sizes m.twin for the placeholders (m.org / m.twin / m.face_off are
 	// allocated by the caller before) -- start() then sets the helpers off
 	SnapshotSpans(Mesh &mesh, const PlaneView *planes, const std::vector<SnapshotPoint> &points, uint32_t *ov);
@@ -175,10 +175,13 @@ struct SnapshotSpans {
 	// for the helpers, checks every stretch's end against the next snapshot, joins them (twin links into published half-edges become
 	// patches of `live`) and leaves the last stretch's cursor in `cur`
 	void finish(ReplayCursor &cur, const size_t *cur_end0, BorderEnd &&end0, bool eom0, ReplayLive *live);
+	// (the destructor, every throwing path of finish()) a stretch already running runs to its end, but leaves no copy and no announcement
+	void cancel();
 	ReplayLive *announce_to = nullptr;   // (set before start(): finished stretches are announced there)
 	// (set before start(), or nullptr) pinned mirrors of face offsets (nf + 1 words), origins, twins (declared_ne words each) and the
 	// decode order (nv words): a helper copies its finished stretch there itself -- the consumer then only starts the transfers
 	uint32_t *mirror_foff = nullptr, *mirror_org = nullptr, *mirror_twin = nullptr, *mirror_order = nullptr;
+	SideThreads helpers;   // (last: joined before anything above goes)
 };
 constexpr uint32_t kContinues = 0xffffffffu;   // refs of a span that starts inside a component: "the component the span before me ended in"
 

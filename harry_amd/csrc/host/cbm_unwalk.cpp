@@ -449,7 +449,7 @@ void SnapshotSpans::start(unsigned n_threads)
 	auto work = [this, trace, t_start] {
 		try {
 			for (;;) {
-				{ std::lock_guard<std::mutex> g(mu); if (failed) return; }
+				{ std::lock_guard<std::mutex> g(mu); if (failed || cancelled) return; }
 				const size_t k = next.fetch_add(1, std::memory_order_relaxed);
 				if (k >= n_spans) return;
 				Span &sp = spans[k];
@@ -461,6 +461,7 @@ void SnapshotSpans::start(unsigned n_threads)
 				if (count) pc.start();
 				sp.eom = replay_triangles<false>(m, conn, own.p, order_v, sp.cur, sp.first, sp.refs, nullptr, sp.cur0, sp.cur1, sp.stop_face, sp.stop_mid, &sp.seed, &ends[k], sp.cur_end);
 				if (count) { pc.stop(); char what[64]; snprintf(what, sizeof what, "replay, stretch %zu on a helper thread", k); pc.report(what, (double)(sp.cur.face - c0.face)); }
+				{ std::lock_guard<std::mutex> g(mu); if (cancelled) return; }
 				if (announce_to) {
 					const bool mir = mirror_org != nullptr;
 					if (mir) {   // (placeholders in the twins included: the join's patches follow)
@@ -475,15 +476,15 @@ void SnapshotSpans::start(unsigned n_threads)
 				if (trace) fprintf(stderr, "[hry replay]   stretch %zu: %.3f .. %.3f ms after the helpers were set off, on cpu %d\n", k, std::chrono::duration<double, std::milli>(t_a - t_start).count(),
 				                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), sched_getcpu());
 			}
-		} catch (...) { { std::lock_guard<std::mutex> g(mu); if (!failed) failed = std::current_exception(); } cv.notify_all(); }
+		} catch (...) { { std::lock_guard<std::mutex> g(mu); failed = true; } cv.notify_all(); throw; }
 	};
 	const size_t nt = std::min<size_t>(std::max(1u, n_threads), n_spans - 1);
-	helpers.reserve(nt);
-	for (size_t t = 0; t < nt; ++t) helpers.emplace_back([work, node] { stay_on_node(node); work(); });
+	for (size_t t = 0; t < nt; ++t) helpers.spawn([work, node] { stay_on_node(node); work(); });
 }
-SnapshotSpans::~SnapshotSpans() { next.store(n_spans, std::memory_order_relaxed); for (auto &h : helpers) if (h.joinable()) h.join(); }
+SnapshotSpans::~SnapshotSpans() { cancel(); }   // (helpers, the last member, is joined first)
+void SnapshotSpans::cancel() { std::lock_guard<std::mutex> g(mu); cancelled = true; }
 void SnapshotSpans::finish(ReplayCursor &cur, const size_t *cur_end0, BorderEnd &&end0, bool eom0, ReplayLive *live)
-{
+try {
 	spans[0].cur = cur; spans[0].eom = eom0;
 	for (int p = 0; p < 21; ++p) spans[0].cur_end[p] = cur_end0[p];
 	ends[0] = std::move(end0);
@@ -497,7 +498,7 @@ void SnapshotSpans::finish(ReplayCursor &cur, const size_t *cur_end0, BorderEnd 
 		if (k > 0) {
 			std::unique_lock<std::mutex> lk(mu);
 			cv.wait(lk, [&] { return spans[k].done || failed; });
-			if (failed) { lk.unlock(); for (auto &h : helpers) if (h.joinable()) h.join(); std::rethrow_exception(failed); }
+			if (failed) { lk.unlock(); cancel(); helpers.rethrow(); }
 		}
 		const Span &sp = spans[k];
 		if (k > 0) {
@@ -516,10 +517,10 @@ void SnapshotSpans::finish(ReplayCursor &cur, const size_t *cur_end0, BorderEnd 
 			live->publish_at(sp.cur.face, sp.cur.he, upto);
 		}
 	}
-	for (auto &h : helpers) if (h.joinable()) h.join();
+	helpers.join();
 	m.twin.resize(m.declared_ne);
 	cur = spans.back().cur;
-}
+} catch (...) { cancel(); throw; }
 
 // planes: 21 connectivity planes in container order.  Fills m.face_off / org / twin and returns the decode order
 // (one half-edge per vertex; vertex ids are assigned in this order, cbm/decoder.h:48-75,145).

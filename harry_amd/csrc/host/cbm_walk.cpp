@@ -1172,12 +1172,13 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 	// the triangle walk on two cores (walk_component_tri_a / walk_trace_expand above): large triangle meshes of the chunked profile
 	struct Split {
 		std::unique_ptr<WalkTrace> trace;
-		std::thread expander;
-		std::exception_ptr err;
 		size_t at = 0;
+		bool running = false;
+		SideThreads expander;
 		void stop()
 		{
-			if (!expander.joinable()) return;
+			if (!running) return;
+			running = false;
 			const size_t behind = trace->head.load(std::memory_order_relaxed) - trace->tail.load(std::memory_order_relaxed);
 			const auto t_stop = std::chrono::steady_clock::now();
 			trace->done.store(1, std::memory_order_release);
@@ -1210,13 +1211,13 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 				split.trace = take_walk_trace();   // (the ring of the call before, where there was one)
 				const void *near_cpus = callers_neighbour_cpus();   // (this thread's cache domain without its own core)
 				WalkTrace *trp = split.trace.get();
-				std::exception_ptr *errp = &split.err;
-				split.expander = std::thread([&m, &st, &em, trp, errp, near_cpus] {
-					try { stay_on_node(near_cpus); walk_trace_expand(m, st, em, *trp); } catch (...) { *errp = std::current_exception(); trp->failed.store(1, std::memory_order_release); }
+				split.expander.spawn([&m, &st, &em, trp, near_cpus] {
+					try { stay_on_node(near_cpus); walk_trace_expand(m, st, em, *trp); } catch (...) { trp->failed.store(1, std::memory_order_release); throw; }
 				});
+				split.running = true;
 			}
 			try { walk_component_tri_a(m, st, f, cb, w, *split.trace, split.at, next_id, consumed); }
-			catch (...) { split.stop(); if (split.err) std::rethrow_exception(split.err); throw; }   // (the expanding thread's failure is the cause, where there is one)
+			catch (...) { split.stop(); split.expander.rethrow(); throw; }   // (the expanding thread's failure is the cause, where there is one)
 		}
 		else if (lean && eval_op_model) walk_component_tri<true>(m, st, f, cb, em, next_id, consumed);
 		else if (lean) walk_component_tri<false>(m, st, f, cb, em, next_id, consumed);
@@ -1227,7 +1228,7 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 		// several threads once the first one shows that the mesh has more than one.
 		if (n_threads > 1 && !eval_op_model && m.nf - consumed >= parallel_min_faces()) {
 			split.stop();   // (the expander owns the Emitter until the trace is complete)
-			if (split.err) std::rethrow_exception(split.err);
+			split.expander.rethrow();
 			em.detach();
 			mark("(sequential part) first component walked");
 			walk_rest_parallel<DEG>(m, st, eface_tab, em, next_id, n_threads);
@@ -1235,7 +1236,7 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 		}
 	} while (consumed != m.nf);
 	split.stop();
-	if (split.err) std::rethrow_exception(split.err);
+	split.expander.rethrow();
 	mark("(sequential part) back");
 	em.detach();
 	em.finish_marks();
@@ -1717,7 +1718,6 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 	w.op_sc.resize(off_op[ncomp]);
 	for (int g = 0; g < G_COUNT; ++g) if (g != G_NUMTRI) { w.grp_val[g].resize(off_g[g][ncomp]); w.grp_pos[g].resize(off_g[g][ncomp]); }
 	// (the marks -- one thread's loop over the components, 4 ms for the 151 741 of the configs[3] mesh -- beside the copies)
-	std::exception_ptr marks_failed;
 	auto marks_in_order = [&] {
 		for (const PerThread &T : per_thread) {
 			if (T.w.twins_changed) w.twins_changed = true;
@@ -1750,37 +1750,44 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 			for (int i = 0; i < 8; ++i) em0.n_op[i] = nop[i];
 		}
 	};
-	std::thread marks_thread;
-	if (ncomp >= (env_uint("HRY_PARALLEL_MIN_FACES", kEnvUnset) != kEnvUnset ? 1u : 4096u) && n_threads > 1) marks_thread =   // (the tests' switch for "small inputs on threads too")
-		 std::thread([&] { try { marks_in_order(); } catch (...) { marks_failed = std::current_exception(); } });
-	try {
-		parallel_for(n_threads, [&](unsigned t) {
-			// ranges of components with about the same number of operation bytes each
-			const uint64_t lo = off_op[0] + (off_op[ncomp] - off_op[0]) * t / n_threads, hi = off_op[0] + (off_op[ncomp] - off_op[0]) * (t + 1) / n_threads;
-			uint32_t kb = (uint32_t)(std::lower_bound(off_op.begin(), off_op.begin() + ncomp, lo) - off_op.begin());
-			uint32_t ke = t + 1 == n_threads ? ncomp : (uint32_t)(std::lower_bound(off_op.begin(), off_op.begin() + ncomp, hi) - off_op.begin());
-			for (uint32_t k = kb; k < ke; ++k) {
-				const Piece &pc = piece[k];
-				if (pc.n_ops) memcpy(w.op_sc.data() + off_op[k], pc.ops, pc.n_ops);
-				const WalkResult &tw = per_thread[pc.thread].w;
-				const uint32_t add = (uint32_t)off_sym[k] - pc.sym0;   // (modulo 2^32: thread-local position -> position in the sequence)
-				if (nt_pos) { uint32_t *q = w.grp_pos[G_NUMTRI].data() + off_g[G_NUMTRI][k]; for (uint32_t i = 0, nn = A.n_faces[k]; i < nn; ++i) q[i] += add; }
-				for (int g = 0; g < G_COUNT; ++g) {
-					if (!pc.gn[g]) continue;
-					memcpy(w.grp_val[g].data() + off_g[g][k], tw.grp_val[g].data() + pc.g0[g], (size_t)pc.gn[g] * 4);
-					uint32_t *dst = w.grp_pos[g].data() + off_g[g][k];
-					const uint32_t *src = tw.grp_pos[g].data() + pc.g0[g];
-					for (uint32_t i = 0; i < pc.gn[g]; ++i) dst[i] = src[i] + add;
-				}
+	const bool marks_beside = ncomp >= (env_uint("HRY_PARALLEL_MIN_FACES", kEnvUnset) != kEnvUnset ? 1u : 4096u) && n_threads > 1;   // (the tests' switch for "small inputs on threads too")
+	SideThreads marks_thread;
+	if (marks_beside) marks_thread.spawn(marks_in_order);
+	parallel_for(n_threads, [&](unsigned t) {
+		// ranges of components with about the same number of operation bytes each
+		const uint64_t lo = off_op[0] + (off_op[ncomp] - off_op[0]) * t / n_threads, hi = off_op[0] + (off_op[ncomp] - off_op[0]) * (t + 1) / n_threads;
+		uint32_t kb = (uint32_t)(std::lower_bound(off_op.begin(), off_op.begin() + ncomp, lo) - off_op.begin());
+		uint32_t ke = t + 1 == n_threads ? ncomp : (uint32_t)(std::lower_bound(off_op.begin(), off_op.begin() + ncomp, hi) - off_op.begin());
+		for (uint32_t k = kb; k < ke; ++k) {
+			const Piece &pc = piece[k];
+			if (pc.n_ops) memcpy(w.op_sc.data() + off_op[k], pc.ops, pc.n_ops);
+			const WalkResult &tw = per_thread[pc.thread].w;
+			const uint32_t add = (uint32_t)off_sym[k] - pc.sym0;   // (modulo 2^32: thread-local position -> position in the sequence)
+			if (nt_pos) { uint32_t *q = w.grp_pos[G_NUMTRI].data() + off_g[G_NUMTRI][k]; for (uint32_t i = 0, nn = A.n_faces[k]; i < nn; ++i) q[i] += add; }
+			for (int g = 0; g < G_COUNT; ++g) {
+				if (!pc.gn[g]) continue;
+				memcpy(w.grp_val[g].data() + off_g[g][k], tw.grp_val[g].data() + pc.g0[g], (size_t)pc.gn[g] * 4);
+				uint32_t *dst = w.grp_pos[g].data() + off_g[g][k];
+				const uint32_t *src = tw.grp_pos[g].data() + pc.g0[g];
+				for (uint32_t i = 0; i < pc.gn[g]; ++i) dst[i] = src[i] + add;
 			}
-		});
-	} catch (...) { if (marks_thread.joinable()) marks_thread.join(); throw; }
+		}
+	});
 	mark("operations and rare groups in coding order");
-	if (marks_thread.joinable()) marks_thread.join(); else marks_in_order();
-	if (marks_failed) std::rethrow_exception(marks_failed);
+	if (marks_beside) marks_thread.rethrow(); else marks_in_order();
 	em0.n = (uint32_t)off_sym[ncomp];
 	em0.min_ref = w.marks.empty() ? NONE32 : w.marks.back().min_ref;   // the caller's finish_marks() writes it back into the last mark
 	mark("marks in coding order");
+}
+
+// the face of every half-edge (mixed polygon degrees), on nt threads
+static void edge_faces(const Mesh &m, unsigned nt, BigVec<uint32_t> &eface)
+{
+	eface.resize(m.ne());   // (pooled, not value-initialised: 4 bytes per half-edge, every entry written below)
+	parallel_for(nt, [&](unsigned t) {
+		const uint32_t b = (uint32_t)((uint64_t)m.nf * t / nt), e = (uint32_t)((uint64_t)m.nf * (t + 1) / nt);
+		for (uint32_t f = b; f < e; ++f) for (uint32_t h = m.face_off[f]; h < m.face_off[f + 1]; ++h) eface[h] = f;
+	});
 }
 
 template <int DEG>
@@ -1788,15 +1795,8 @@ static void walk_impl(Mesh &m, WalkResult &w, bool eval_op_model, bool one_seque
 {
 	const uint32_t nf = m.nf;
 	if (nf == 0) throw Error(HRY_E_UNSUPPORTED, "mesh without faces");
-	BigVec<uint32_t> eface_tab;   // (pooled, not value-initialised: 4 bytes per half-edge, every entry written below)
-	if (DEG == 0) {
-		eface_tab.resize(m.ne());
-		const unsigned nt = nf >= (1u << 20) ? host_threads() : 1u;
-		parallel_for(nt, [&](unsigned t) {
-			const uint32_t b = (uint32_t)((uint64_t)nf * t / nt), e = (uint32_t)((uint64_t)nf * (t + 1) / nt);
-			for (uint32_t f = b; f < e; ++f) for (uint32_t h = m.face_off[f]; h < m.face_off[f + 1]; ++h) eface_tab[h] = f;
-		});
-	}
+	BigVec<uint32_t> eface_tab;
+	if (DEG == 0) edge_faces(m, nf >= (1u << 20) ? host_threads() : 1u, eface_tab);
 	int ndeg = 0;
 	for (uint8_t d : m.have_degree) ndeg += d ? 1 : 0;
 	w.numtri_coded = ndeg > 1;   // one degree => conn_numtri holds a single symbol of count == total: l = 0, h = t, coder state unchanged
@@ -1891,13 +1891,8 @@ void analyse_components(const Mesh &m, ComponentAnalysis &A)
 	const unsigned nt = m.nf >= (1u << 16) ? host_threads() : 1u;
 	if (udeg == 3) { analyse_impl<3>(m, nullptr, nullptr, nullptr, nt, A); return; }
 	if (udeg == 4) { analyse_impl<4>(m, nullptr, nullptr, nullptr, nt, A); return; }
-	BigVec<uint32_t> &eface_tab = A.eface;   // (pooled, not value-initialised: every entry is written below)
-	eface_tab.resize(m.ne());
-	parallel_for(nt, [&](unsigned t) {
-		const uint32_t b = (uint32_t)((uint64_t)m.nf * t / nt), e = (uint32_t)((uint64_t)m.nf * (t + 1) / nt);
-		for (uint32_t f = b; f < e; ++f) for (uint32_t h = m.face_off[f]; h < m.face_off[f + 1]; ++h) eface_tab[h] = f;
-	});
-	analyse_impl<0>(m, eface_tab.data(), nullptr, nullptr, nt, A);
+	edge_faces(m, nt, A.eface);
+	analyse_impl<0>(m, A.eface.data(), nullptr, nullptr, nt, A);
 }
 
 WalkState::WalkState(uint32_t nv, uint32_t nf, unsigned n_threads)
@@ -1909,6 +1904,13 @@ WalkState::WalkState(uint32_t nv, uint32_t nf, unsigned n_threads)
 		if (fe > fb) memset((void*)(gone.data() + fb), 0, fe - fb);
 		if (ve > vb) { memset(on.data() + vb, 0, (ve - vb) * sizeof(OnCount)); memset(sent.data() + vb, 0xff, (ve - vb) * 4); memset(seen.data() + vb, 0, (ve - vb) * 2); }
 	});
+}
+
+std::unique_ptr<WalkState> walk_tables(const Mesh &m, unsigned nt, BigVec<uint32_t> &eface)
+{
+	int ud = 0;
+	if (!(m.uniform_degree(ud) && (ud == 3 || ud == 4))) edge_faces(m, nt, eface);
+	return std::unique_ptr<WalkState>(new WalkState(m.nv, m.nf, nt));
 }
 
 void cut_border_walk_in_place(Mesh &m, const ComponentAnalysis &part, const uint32_t *eface, WalkState &st, WalkResult &w)

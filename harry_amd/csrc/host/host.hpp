@@ -11,6 +11,7 @@
 
 #include "../../../include/harry_amd.h"
 #include "env.hpp"
+#include "side_threads.hpp"
 #include "mesh.hpp"
 
 namespace hry {
@@ -195,6 +196,9 @@ void start_face_spans(uint32_t nf, std::vector<uint32_t> &spans);   // (lowest f
 // shard of m codes (shard.cpp: shard_components).  `st` may be shared with other calls walking OTHER groups of the same mesh at
 // the same time; eface: the face of every half-edge for mixed polygon degrees (ComponentAnalysis::eface), else nullptr.
 void cut_border_walk_in_place(Mesh &m, const ComponentAnalysis &part, const uint32_t *eface, WalkState &st, WalkResult &out);
+// what the walk in place needs whatever the component analysis finds (device/chunked.cpp, device/sharded.cpp: built beside it on
+// nt threads): the face of every half-edge into eface where the mesh mixes polygon degrees (else eface stays as it is), and the marks
+std::unique_ptr<WalkState> walk_tables(const Mesh &m, unsigned nt, BigVec<uint32_t> &eface);
 
 // ---- general_events.cpp: which record every element of a mesh with general bindings names, along the coding order
 // (attrcode.h:321-393).  Kinds and slots are enumerations of a byte's width, not character types (see OpByte)

@@ -149,21 +149,22 @@ int main(int argc, char **argv)
 						// stretch up to the first snapshot and publishes its progress, helper threads the stretches behind the snapshots
 						// (SnapshotSpans), joined one after the other as they finish; a reader thread plays the consumer
 						int udeg = 0;
-						if (!snaps.empty() && rs.empty() && planes[7].empty() && m2->uniform_degree(udeg) && udeg == 3) {
-							Mesh live_m;
+						const bool pipelined = !snaps.empty() && rs.empty() && planes[7].empty() && m2->uniform_degree(udeg) && udeg == 3;
+						auto replay_publishing = [&](const std::vector<SnapshotPoint> &sn, Mesh &live_m, OrderVec &ov_live) {   // returns the stretches announced
 							skeleton(live_m);
 							live_m.face_off.resize((size_t)live_m.nf + 1); live_m.face_off[0] = 0;
 							live_m.org.resize(live_m.declared_ne);
-							OrderVec ov_live;
 							ov_live.assign(live_m.nv, 0);
-							SnapshotSpans spans(live_m, views, snaps, ov_live.data());   // (sizes the twins)
+							// (declared in this order: the helpers, then the consumer, are joined before anything they touch goes)
 							BigVec<uint16_t> seen(live_m.nv, 0);
 							ReplayLive live;
 							live.on_border.assign(live_m.nv, 0);
 							live.interval = 64;
+							SnapshotSpans spans(live_m, views, sn, ov_live.data());   // (sizes the twins)
 							std::atomic<bool> stop{ false };
 							uint64_t n_ranges = 0, n_pubs = 0;
-							std::thread consumer([&] {
+							SideThreads consumer;
+							consumer.spawn([&] {
 								uint64_t seen_seq = 0;
 								for (;;) {
 									while (live.announced.load(std::memory_order_acquire) == seen_seq && !stop.load()) std::this_thread::yield();
@@ -188,9 +189,15 @@ int main(int argc, char **argv)
 								if (!eom0) live.publish(cur.face, cur.he, cur.next_id, false);
 								spans.finish(cur, cur_end0, std::move(end0), eom0, &live);
 								live.publish(cur.face, cur.he, cur.next_id, true);
-							} catch (...) { stop.store(true); live.publish(cur.face, cur.he, cur.next_id, true, true); consumer.join(); throw; }
+							} catch (...) { stop.store(true); live.publish(cur.face, cur.he, cur.next_id, true, true); throw; }
 							consumer.join();
 							ov_live.resize(cur.next_id);
+							return n_ranges;
+						};
+						if (pipelined) {
+							Mesh live_m;
+							OrderVec ov_live;
+							const uint64_t n_ranges = replay_publishing(snaps, live_m, ov_live);
 							if (live_m.org != seq.org || live_m.twin != seq.twin || live_m.face_off != seq.face_off || ov_live != ov_seq || n_ranges != snaps.size())
 								throw Error(HRY_E_INTERNAL, "publishing replay with stretches on helper threads differs from the sequential replay");
 						}
@@ -209,6 +216,27 @@ int main(int argc, char **argv)
 								cut_border_replay(d, views, rs, rc, ov, a, b, nullptr, &sn2);
 							} catch (const Error &) {
 							}
+						}
+						// ... and the pipelined decode's host half from a directory whose first border snapshot the reader accepts but the
+						// stream does not match (its first half-edge one too low): finish() throws while the helpers may still be
+						// replaying the later stretches into the mesh and announcing them to `live`
+						if (pipelined) {
+							std::vector<BorderSnapshot> damaged = w2.snapshots;
+							damaged[0].first_halfedge -= 1;
+							std::vector<uint8_t> sec2;
+							write_snapshot_section(w2.snapshot_faces, damaged, sc, sec2);
+							std::vector<SnapshotPoint> sn2;
+							uint32_t spacing = 0;
+							if (read_snapshot_section(sec2.data(), sec2.size(), m2->nv, spacing, sn2) != sec2.size()) throw Error(HRY_E_INTERNAL, "snapshots: the damaged section does not read back");
+							bool failed = false;
+							try {
+								Mesh live_m;
+								OrderVec ov_live;
+								replay_publishing(sn2, live_m, ov_live);
+							} catch (const Error &) {
+								failed = true;
+							}
+							if (!failed) throw Error(HRY_E_INTERNAL, "a border snapshot that does not match the stream was accepted");
 						}
 #endif
 					}
