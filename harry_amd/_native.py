@@ -137,6 +137,14 @@ def load():
     L.hry_decode_sharded.restype = C.c_int
     L.hry_decode_sharded.argtypes = [C.POINTER(vp), C.c_int, vp, sz, C.POINTER(Opts), C.POINTER(vp), C.POINTER(ShardTiming)]
     L.hry_container_check.restype = C.c_int; L.hry_container_check.argtypes = [vp, sz, C.POINTER(C.c_int)]
+    L.hry_render_build.restype = C.c_int; L.hry_render_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hry_render_nverts.restype = C.c_uint32; L.hry_render_nverts.argtypes = [vp]
+    L.hry_render_ntris.restype = C.c_uint64; L.hry_render_ntris.argtypes = [vp]
+    L.hry_render_get.restype = C.c_int
+    L.hry_render_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hry_render_copy.restype = C.c_int; L.hry_render_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
+    L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hry_render_free.argtypes = [vp]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

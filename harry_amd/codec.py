@@ -362,6 +362,58 @@ class Codec:
         nat.check(nat.load().hry_decode(self.h, data, len(data), C.byref(o), C.byref(h)))
         return Mesh(h)
 
+    # ---- render-ready device buffers (include/harry_amd.h: hry_render_build)
+    RENDER_FIXED = ("indices", "tri_face", "vertex_source", "corner_source", "face_region")
+    _RENDER_NP = {0: np.float32, 4: np.uint32, 6: np.uint16}
+
+    def _render(self, mesh: Mesh, fill) -> dict:
+        """build, hand every buffer to fill(name, rows, width, type, handle), free the handle"""
+        L = nat.load()
+        r = C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            out = {}
+            for name in self.RENDER_FIXED + tuple(f"list{l}" for l in range(mesh.nlists)):
+                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                nat.check(L.hry_render_get(r, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                if rows.value:
+                    out[name] = fill(name, rows.value, width.value, typ.value, r)
+            d, up = C.c_double(), C.c_uint64()
+            nat.check(L.hry_render_stat(r, C.byref(d), C.byref(up)))
+            self._render_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "nverts": L.hry_render_nverts(r), "ntris": L.hry_render_ntris(r)}
+            return out
+        finally:
+            L.hry_render_free(r)
+
+    def render_numpy(self, mesh: Mesh) -> dict:
+        """the mesh as render-ready buffers (hry_render_build), copied to host arrays: indices u32 [T, 3], tri_face u32 [T],
+        vertex_source u32 [U], corner_source u32 [U] (unwelded meshes), face_region u16 [nf] (general bindings), list<l> f32 [rows, ncomp]"""
+        def fill(name, rows, width, typ, r):
+            a = np.empty((rows, width) if name == "indices" or name.startswith("list") else (rows,), self._RENDER_NP[typ])
+            nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), a.ctypes.data, 0))
+            return a
+        return self._render(mesh, fill)
+
+    def render(self, mesh: Mesh) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: indices / tri_face / vertex_source /
+        corner_source int32, face_region int16, list<l> float32.  They stay valid after close()."""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+        dtypes = {0: torch.float32, 4: torch.int32, 6: torch.int16}
+        if max(mesh.nv, mesh.ne, mesh.ntri) >= 2 ** 31:   # (every u32 value is below one of them: U <= max(nv, ne))
+            raise HryError(nat.E_ARG, "vertex, corner or triangle numbers of this mesh do not fit int32 tensors")
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+
+        def fill(name, rows, width, typ, r):
+            t = torch.empty((rows, width) if name == "indices" or name.startswith("list") else (rows,), dtype=dtypes[typ], device=dev)
+            nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), t.data_ptr(), 1))
+            return t
+        return self._render(mesh, fill)
+
+    def render_stat(self) -> dict:
+        """of the last render / render_numpy: device_ms (render kernels), uploaded_bytes (host to device), nverts (U), ntris (T)"""
+        return dict(getattr(self, "_render_stat", {}))
+
     def timing(self) -> dict:
         t = nat.Timing()
         nat.check(nat.load().hry_ctx_timing(self.h, C.byref(t)))

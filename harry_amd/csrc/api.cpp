@@ -10,6 +10,7 @@ using namespace hry;
 struct hry_ctx { Context cx; explicit hry_ctx(int d) : cx(d) {} };
 struct hry_mesh { Mesh m; };
 struct hry_plan { ShardPlan p; };
+struct hry_render { RenderResult r; };
 struct hry_walk {
 	WalkResult w; uint32_t info[2]; std::vector<uint8_t> vplanes, fplanes; std::vector<uint32_t> seg_start, seg_level;
 	mutable std::vector<uint8_t> op_sym, op_class;   // unpacked from w.op_sc on first request
@@ -33,6 +34,11 @@ struct hry_walk {
 };
 
 static thread_local std::string g_last_error;
+
+// the decode's buffers in HBM stop being the mesh's for hry_render_build (render.cpp) at the next call on the context, and at
+// every call that changes the mesh
+static void touched(hry_ctx *ctx) { if (ctx) ctx->cx.render_token = 0; }
+static void touched(hry_mesh *m) { if (m) m->m.render_token = 0; }
 
 template <typename F> static int guarded(F &&f)
 {
@@ -162,7 +168,7 @@ void hry_mesh_free(hry_mesh *m) { delete m; }
 hry_mesh *hry_mesh_clone(const hry_mesh *m)
 {
 	if (!m) return nullptr;
-	try { hry_mesh *c = new hry_mesh{ m->m }; c->m.device_token = 0; return c; }
+	try { hry_mesh *c = new hry_mesh{ m->m }; c->m.device_token = 0; c->m.render_token = 0; return c; }
 	catch (...) { g_last_error = "out of memory"; return nullptr; }
 }
 
@@ -191,22 +197,26 @@ const uint8_t *hry_list_max(const hry_mesh *m, int l) { return m->m.lists[l].hav
 int hry_bounds(hry_ctx *ctx, hry_mesh *m)
 {
 	if (!ctx || !m) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx); touched(m);
 	return guarded([&] { device_bounds(ctx->cx, m->m); });
 }
 int hry_requant(hry_ctx *ctx, hry_mesh *m, const hry_quant *q, size_t nq, int clear)
 {
 	if (!ctx || !m || (nq && !q)) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx); touched(m);
 	return guarded([&] { device_requant(ctx->cx, m->m, q, nq, clear != 0); });
 }
 int hry_mesh_upload(hry_ctx *ctx, hry_mesh *m)
 {
 	if (!ctx || !m) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx); touched(m);
 	return guarded([&] { if (m->m.general) upload_general(ctx->cx, m->m); else ctx->cx.upload_mesh(m->m); });
 }
 int hry_encode(hry_ctx *ctx, hry_mesh *m, const hry_opts *opts, uint8_t **out, size_t *out_len)
 {
 	if (!ctx || !m || !out || !out_len) { g_last_error = "null argument"; return HRY_E_ARG; }
 	*out = nullptr; *out_len = 0;
+	touched(ctx); touched(m);
 	return guarded([&] {
 		hry_opts o = opts ? *opts : hry_opts{};
 		ctx->cx.keep_stages = o.keep_stages != 0;
@@ -231,6 +241,7 @@ int hry_decode(hry_ctx *ctx, const uint8_t *hry, size_t n, const hry_opts *opts,
 {
 	if (!ctx || !hry || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
 	*out = nullptr;
+	touched(ctx);   // (the decode marks what it leaves in HBM: mark_decoded)
 	return guarded([&] {
 		hry_opts o = opts ? *opts : hry_opts{};
 		ctx->cx.keep_stages = o.keep_stages != 0;
@@ -244,6 +255,8 @@ int hry_encode_sharded(hry_ctx *const *ctx, int n_ctx, hry_mesh *m, const hry_qu
 {
 	if (!ctx || n_ctx <= 0 || !m || !out || !out_len || (n_quant && !quant)) { g_last_error = "null argument"; return HRY_E_ARG; }
 	*out = nullptr; *out_len = 0;
+	for (int i = 0; i < n_ctx; ++i) touched(ctx[i]);
+	touched(m);
 	return guarded([&] {
 		hry_opts o = opts ? *opts : hry_opts{};
 		o.profile = opts ? o.profile : HRY_PROFILE_CHUNKED;
@@ -261,6 +274,7 @@ int hry_decode_sharded(hry_ctx *const *ctx, int n_ctx, const uint8_t *hry, size_
 {
 	if (!ctx || n_ctx <= 0 || !hry || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
 	*out = nullptr;
+	for (int i = 0; i < n_ctx; ++i) touched(ctx[i]);
 	return guarded([&] {
 		hry_opts o = opts ? *opts : hry_opts{};
 		std::vector<Context*> cxs;
@@ -364,6 +378,7 @@ int hry_walk_run_shard(hry_mesh *m, const hry_plan *p, int shard, hry_walk **out
 int hry_analysis_check(hry_ctx *ctx, hry_mesh *m)
 {
 	if (!ctx || !m) { g_last_error = "invalid argument"; return HRY_E_ARG; }
+	touched(ctx); touched(m);
 	return guarded([&] {
 		check_codable(m->m);
 		if (m->m.general || !m->m.shard.seeds.empty()) throw Error(HRY_E_ARG, "analysis check: a mesh in the PLY layout that is not a shard");
@@ -433,6 +448,7 @@ size_t hry_shard_elements(const hry_mesh *m, int which, const uint32_t **idx)
 }
 int hry_list_set_bounds(hry_mesh *m, int l, const uint8_t *min_rec, const uint8_t *max_rec)
 {
+	touched(m);
 	if (!m || l < 0 || (size_t)l >= m->m.lists.size() || !min_rec || !max_rec) { g_last_error = "invalid argument"; return HRY_E_ARG; }
 	AttrList &L = m->m.lists[l];
 	for (int c = 0; c < L.ncomp(); ++c) if (L.quant[c]) { g_last_error = "bounds of an already quantised list come from its header"; return HRY_E_ARG; }
@@ -579,6 +595,7 @@ int hry_walk_replay(const hry_mesh *src, const hry_walk *walk, int use_restart_p
 int hry_range_encode_lht(hry_ctx *ctx, const uint64_t *lht, size_t n, uint8_t **out, size_t *out_len)
 {
 	if (!ctx || (n && !lht) || !out || !out_len) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx);
 	return guarded([&] {
 		std::vector<uint8_t> v;
 		range_encode_lht(ctx->cx, lht, n, v);
@@ -586,5 +603,42 @@ int hry_range_encode_lht(hry_ctx *ctx, const uint64_t *lht, size_t n, uint8_t **
 		*out_len = v.size();
 	});
 }
+
+// ---- render-ready device buffers (render.cpp)
+int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out)
+{
+	if (!ctx || !m || !out) { g_last_error = "null argument"; if (out) *out = nullptr; return HRY_E_ARG; }
+	*out = nullptr;
+	return guarded([&] {
+		std::unique_ptr<hry_render> r(new hry_render());
+		render_build(ctx->cx, m->m, r->r);
+		*out = r.release();
+	});
+}
+uint32_t hry_render_nverts(const hry_render *r) { return r ? r->r.nverts : 0; }
+uint64_t hry_render_ntris(const hry_render *r) { return r ? r->r.ntris : 0; }
+int hry_render_get(const hry_render *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
+{
+	if (!r || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const RenderBuf *b = r->r.find(name);
+	*rows = b ? b->rows : 0;
+	if (dev) *dev = b ? b->p : nullptr;
+	if (width) *width = b ? b->width : 0;
+	if (type) *type = b ? b->type : 0;
+	return HRY_OK;
+}
+int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !r || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { render_copy(ctx->cx, r->r, name, dst, dst_is_device != 0); });
+}
+int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!r) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = r->r.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = r->r.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_render_free(hry_render *r) { delete r; }
 
 }   // extern "C"

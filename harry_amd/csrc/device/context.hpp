@@ -91,6 +91,12 @@ struct Context {
 	// resident mesh (hry_mesh_upload): attribute records and connectivity stay in HBM across encodes
 	uint64_t resident_token = 0;
 	uint64_t gen_token = 0;          // the mesh whose binding tables (d_vreg .. d_cattr) are in HBM (general.cpp: upload_general)
+	uint64_t render_token = 0;       // the mesh the last hry_decode returned, while d_rec / d_foff / d_org (and the binding tables) still
+	                                 // hold it: hry_render_build reads them instead of uploading (render.cpp); any other call clears it.
+	                                 // Drawn from ONE counter of the process (mark_decoded): no two contexts ever hand out the same token
+	bool render_whole = false;       // ... the mesh is a sharded container decoded here: its records and connectivity are in d_whole_*
+	uint32_t render_nf = 0, render_ne = 0;
+	DevBuf d_whole_rec[2], d_whole_foff, d_whole_org, d_whole_runs;   // decode_sharded on ONE context, PLY layout: the segments' device results placed into the whole numbering (render.cpp: place_segment)
 	uint64_t next_token = 1;
 	DevBuf d_rec[kMaxLists], d_org, d_twin, d_foff, d_eface;
 	DevBuf d_vreg, d_freg, d_vattr, d_cattr, d_fattr, d_gen;   // general bindings (general.cpp): region and record tables, event arena
@@ -106,6 +112,7 @@ struct Context {
 	       d_rec_sym, d_sym_l, d_r, d_s, d_state, d_acc, d_v, d_summary, d_bytes, d_small;
 	// chunked profile
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
+	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
 	DevBuf d_split;   // chunked encode in two kernels: per stream the place of its records and the streams' order, longest first (the records: d_rec_sym)
 	DevBuf d_pipe, d_nt_val, d_nt_planes;   // EncodePipeline: run tables and twin pairs of the batches; the polygons' triangle counts and their two byte planes
 	std::vector<uint32_t> h_twin_patch;   // (half-edge, twin) pairs on their way to d_patch (upload_repaired_twins)
@@ -208,6 +215,31 @@ void encode_sharded(Context *const *cxs, int n_ctx, Mesh &m, const hry_quant *q,
 Mesh *decode_sharded(Context *const *cxs, int n_ctx, const uint8_t *p, size_t n, size_t hdr, std::unique_ptr<Mesh> g, int shard_index, int shard_count,
                      bool allow_partial, hry_shard_timing *st);
 void range_encode_lht(Context &cx, const uint64_t *lht, size_t n, std::vector<uint8_t> &out);
+
+// render.cpp: a mesh as device buffers a GPU program draws (include/harry_amd.h: hry_render_build); the result owns its memory
+struct RenderBuf { std::string name; void *p = nullptr; uint64_t rows = 0; int width = 0, type = 0; size_t bytes() const; };
+struct RenderResult {
+	int device = 0;
+	void *block = nullptr;   // every buffer lies in this one allocation
+	uint32_t nverts = 0;
+	uint64_t ntris = 0;
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+	std::vector<RenderBuf> bufs;
+	RenderResult() = default;
+	RenderResult(const RenderResult&) = delete;
+	RenderResult &operator=(const RenderResult&) = delete;
+	~RenderResult();
+	const RenderBuf *find(const char *name) const;
+};
+// marks m as what cx holds in HBM after a decode (unchunk.cpp, general.cpp; whole: sharded.cpp, the mesh is in d_whole_*), with a
+// token unique in the process; a mesh whose connectivity the context does not hold stays unmarked
+void mark_decoded(Context &cx, Mesh &m, bool whole = false);
+// decode_sharded on one context (PLY layout): the segment just decoded (cx's d_rec / d_foff / d_org, the segment's numbering) into
+// d_whole_* at its runs' places in the whole numbering; false (nothing placed) when the context does not hold the segment
+bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne);
+void render_build(Context &cx, const Mesh &m, RenderResult &out);
+void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
 
 dev::ListDesc make_list_desc(const AttrList &L);
 void check_codable(const Mesh &m);

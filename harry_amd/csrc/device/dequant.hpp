@@ -1,0 +1,39 @@
+// Rescaling of quantised values (structs/quant.h:98-112) and the dequantisation into a component's original type
+// (quant.h:180-212), on the device.  Shared by k_requant (kernels.hip, in place) and k_render_gather (render.hip, to f32).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "codec_math.hpp"
+#include "dev_types.hpp"
+
+namespace hry {
+namespace dev {
+
+template <typename T> __device__ __forceinline__ T rescale_int(T val, T from, T to) { return val / from * to + val % from * to / from; }   // quant.h:103-107
+
+template <typename T> __device__ __forceinline__ T rescale_fp(T val, T from, T to) { return val / from * to; }   // quant.h:98-102 (every operation rounded on its own)
+
+// q (c.src_bits quantisation bits) -> rescale(q, 2^bits - 1, extent) + min in c.dst_type; the raw bits of that value, in the low
+// bytes of the word (what the original-width slot holds)
+__device__ __forceinline__ uint64_t dequantise_bits(uint64_t q, const RequantComp &c)
+{
+	const int sl = (1 << (uint32_t)c.src_bits) - 1;
+	switch (c.dst_type) {
+	case 0: return cm::bits<uint32_t>(rescale_fp<float>((float)q, (float)sl, cm::bits<float>((uint32_t)c.scale)) + cm::bits<float>((uint32_t)c.mn));
+	case 1: return cm::bits<uint64_t>(rescale_fp<double>((double)q, (double)sl, cm::bits<double>(c.scale)) + cm::bits<double>(c.mn));
+	case 2: return rescale_int<uint64_t>(q, (uint64_t)sl, c.scale) + c.mn;
+	case 3: return (uint64_t)(rescale_int<int64_t>((int64_t)q, (int64_t)sl, (int64_t)c.scale) + (int64_t)c.mn);
+	case 4: return (uint32_t)(rescale_int<uint32_t>((uint32_t)q, (uint32_t)sl, (uint32_t)c.scale) + (uint32_t)c.mn);
+	case 5: return (uint32_t)(rescale_int<int32_t>((int32_t)q, (int32_t)sl, (int32_t)c.scale) + (int32_t)c.mn);
+	case 6: return (uint16_t)(rescale_int<uint16_t>((uint16_t)q, (uint16_t)sl, (uint16_t)c.scale) + (uint16_t)c.mn);
+	case 7: return (uint16_t)(rescale_int<int16_t>((int16_t)q, (int16_t)sl, (int16_t)c.scale) + (int16_t)c.mn);
+	case 8: return (uint8_t)(rescale_int<uint8_t>((uint8_t)q, (uint8_t)sl, (uint8_t)c.scale) + (uint8_t)c.mn);
+	case 9: return (uint8_t)(rescale_int<int8_t>((int8_t)q, (int8_t)sl, (int8_t)c.scale) + (int8_t)c.mn);
+	default: return 0;
+	}
+}
+
+}   // namespace dev
+}   // namespace hry

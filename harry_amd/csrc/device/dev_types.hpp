@@ -39,6 +39,31 @@ struct EvRegions {
 	int32_t nb_face;
 };
 
+// render.hip: the corner keys of the unweld (general bindings with corner lists); cslot[r * nlists + k] = slot of the k-th corner
+// list in face region r's corner slots, -1 where the region does not bind it; table: mask + 1 slots, kNone = empty
+struct UnweldView {
+	const uint32_t *org, *eface, *corner_attr;
+	const uint16_t *face_reg;
+	const int32_t *cslot;
+	uint32_t ne, nf, nregs, nlists, nb_corner, mask;
+	uint32_t *table;
+};
+// render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]
+// (or of the element) -> slot[region] (-1: unbound) -> attr[element * nb + slot]
+struct RowsView {
+	const uint32_t *src, *efc, *attr;
+	const uint16_t *reg;
+	const int32_t *slot;
+	uint32_t nelem, nowner, nregs, nb, count;
+};
+
+// render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
+// per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
+struct RunPlace {
+	const uint32_t *lv, *lf, *lh, *gv, *gf, *gh;
+	uint32_t nr, gnv, gnf, gne;
+};
+
 // per-symbol record consumed by the serial range recurrence (16 bytes, one dwordx4 per lane)
 struct alignas(16) SymRec {
 	uint64_t magic;    // reciprocal of the context total t (round-up method, 65-bit magic with implicit top bit)

@@ -447,6 +447,7 @@ Mesh *decode_general(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	cx.timing.payload_bytes = n - hdr;
 	cx.timing.total_ms = ms_since(t_all);
 	m->device_token = 0;
+	mark_decoded(cx, *m);
 	return m.release();
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "codec_math.hpp"
+#include "dequant.hpp"
 #include "dev_types.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
@@ -162,10 +163,7 @@ __global__ __launch_bounds__(64) void k_bounds_final(const uint8_t *part_min, co
 // float / 1-2-4 byte integers, or an already quantised value (q -> q').  src and dst alias the same slot
 // (attr.h:95-98); the destination is written in its storage type into the low bytes of the slot.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T rescale_int(T val, T from, T to) { return val / from * to + val % from * to / from; }   // quant.h:103-107
-
-template <typename T> __device__ __forceinline__ T rescale_fp(T val, T from, T to) { return val / from * to; }   // quant.h:98-102 (every operation rounded on its own)
-
+// (rescale_int / rescale_fp / dequantise_bits: dequant.hpp)
 __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, int stride, RequantPlan plan)
 {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
@@ -205,18 +203,12 @@ __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, i
 				continue;
 			}
 			// dequantisation into the original type (quant.h:180-212): rescale(q, 2^bits - 1, extent) + min, in that type
-			const int sl = (1 << (uint32_t)c.src_bits) - 1;
+			const uint64_t v = dequantise_bits(q, c);
 			switch (c.dst_type) {
-			case 0: stg<float>(slot, rescale_fp<float>((float)q, (float)sl, cm::bits<float>((uint32_t)c.scale)) + cm::bits<float>((uint32_t)c.mn)); break;
-			case 1: stg<double>(slot, rescale_fp<double>((double)q, (double)sl, cm::bits<double>(c.scale)) + cm::bits<double>(c.mn)); break;
-			case 2: stg<uint64_t>(slot, rescale_int<uint64_t>(q, (uint64_t)sl, c.scale) + c.mn); break;
-			case 3: stg<int64_t>(slot, rescale_int<int64_t>((int64_t)q, (int64_t)sl, (int64_t)c.scale) + (int64_t)c.mn); break;
-			case 4: stg<uint32_t>(slot, rescale_int<uint32_t>((uint32_t)q, (uint32_t)sl, (uint32_t)c.scale) + (uint32_t)c.mn); break;
-			case 5: stg<int32_t>(slot, rescale_int<int32_t>((int32_t)q, (int32_t)sl, (int32_t)c.scale) + (int32_t)c.mn); break;
-			case 6: stg<uint16_t>(slot, (uint16_t)(rescale_int<uint16_t>((uint16_t)q, (uint16_t)sl, (uint16_t)c.scale) + (uint16_t)c.mn)); break;
-			case 7: stg<int16_t>(slot, (int16_t)(rescale_int<int16_t>((int16_t)q, (int16_t)sl, (int16_t)c.scale) + (int16_t)c.mn)); break;
-			case 8: stg<uint8_t>(slot, (uint8_t)(rescale_int<uint8_t>((uint8_t)q, (uint8_t)sl, (uint8_t)c.scale) + (uint8_t)c.mn)); break;
-			case 9: stg<int8_t>(slot, (int8_t)(rescale_int<int8_t>((int8_t)q, (int8_t)sl, (int8_t)c.scale) + (int8_t)c.mn)); break;
+			case 0: case 4: case 5: stg<uint32_t>(slot, (uint32_t)v); break;
+			case 1: case 2: case 3: stg<uint64_t>(slot, v); break;
+			case 6: case 7: stg<uint16_t>(slot, (uint16_t)v); break;
+			case 8: case 9: stg<uint8_t>(slot, (uint8_t)v); break;
 			default: break;
 			}
 		}

@@ -136,5 +136,23 @@ void launch_list_kinds(hipStream_t st, int kind, uint32_t list_count, const Conn
                        uint32_t *counts, uint32_t *err);
 void launch_region_symbols(hipStream_t st, int kind, const ConnView &cv, const GenView &gv, const uint32_t *order, uint32_t n, uint8_t *out);
 
+// render-ready buffers (render.hip; driver: render.cpp).  launch_fan: tri_face[T] and indices[3T] of the fan triangulation,
+// corners mapped through vmap (org, or the unweld's corner -> output vertex map)
+void launch_fan(hipStream_t st, const uint32_t *foff, uint32_t nf, uint64_t ntri, const uint32_t *vmap, uint32_t ne, uint32_t *tri_face, uint32_t *indices);
+void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);
+size_t unweld_table_slots(uint32_t ne);   // a power of two >= 2 ne
+// u.table filled with 0xff first; first_of[ne], masks / counts[(ne + 63) / 64], wave_start[(ne + 63) / 64 + 1] (last: the output vertices)
+void launch_unweld_count(hipStream_t st, const UnweldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start);
+void launch_unweld_assign(hipStream_t st, const uint32_t *org, uint32_t ne, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
+                          uint32_t nout, uint32_t *cmap, uint32_t *vertex_source, uint32_t *corner_source);
+void launch_rows_of(hipStream_t st, const RowsView &v, uint32_t rows, uint32_t *idx);
+// plan: every component of the list (dst_bits 0; src_bits = its quantisation), idx == nullptr: row u is record u
+// a decoded segment into the whole numbering (render.cpp: place_segment): records (stride bytes each) of nl local vertices / faces,
+// origins of ne local half-edges (vertex ids mapped too), face offsets of nf local faces
+void launch_place_segment(hipStream_t st, const RunPlace &r, const uint8_t *vrec, uint32_t nlv, uint32_t vstride, uint8_t *whole_vrec,
+                          const uint8_t *frec, uint32_t nlf, uint32_t fstride, uint8_t *whole_frec, const uint32_t *org, uint32_t nle, uint32_t *whole_org,
+                          const uint32_t *foff, uint32_t *whole_foff);
+void launch_render_gather(hipStream_t st, const uint8_t *rec, int stride, uint32_t count, const uint32_t *idx, uint64_t rows, const RequantPlan &plan, float *out);
+
 }   // namespace dev
 }   // namespace hry

@@ -1,0 +1,318 @@
+// A mesh as device buffers a GPU program draws: fan triangles, float attributes after the reference's `-c` dequantisation, and
+// for general bindings with corner lists (OBJ vt / vn) one vertex per distinct corner key (include/harry_amd.h: hry_render_build;
+// kernels: render.hip; DESIGN.md "Render-ready buffers").
+//
+// Residency: hry_decode leaves the decoded records (d_rec), the connectivity (d_foff / d_org) and the binding tables in HBM and
+// marks the mesh and the context with one token (mark_decoded).  While both still carry it -- every other call on the context
+// clears the context's, every call that changes the mesh clears the mesh's (api.cpp) -- the build reads them where they are.
+// Otherwise it uploads what it needs into its own working buffer (d_render): the encoder's resident_token / gen_token are
+// neither read nor written here.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstring>
+
+#include "context.hpp"
+#include "kernels.hpp"
+
+namespace hry {
+
+using namespace dev;
+
+size_t RenderBuf::bytes() const { return (size_t)rows * (size_t)width * (type == HRY_USHORT ? 2u : 4u); }
+RenderResult::~RenderResult()
+{
+	if (block) { (void)hipSetDevice(device); (void)hipFree(block); }
+}
+const RenderBuf *RenderResult::find(const char *name) const
+{
+	for (const RenderBuf &b : bufs) if (b.name == name) return &b;
+	return nullptr;
+}
+
+namespace {
+
+constexpr size_t kAlign = 256;
+inline size_t align_up(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
+
+// carves one device allocation into aligned pieces: reserve() while sizing, then take() in the same order
+struct Carve {
+	std::vector<size_t> at;
+	size_t total = 0;
+	size_t reserve(size_t bytes) { at.push_back(total); total += align_up(std::max<size_t>(bytes, 4)); return at.size() - 1; }
+	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
+};
+
+// every component of list L, dequantised as hry_requant(clear) would (requant_plan: the quantised ones), the others as they are
+RequantPlan gather_plan(const AttrList &L)
+{
+	if (L.ncomp() > dev::kMaxComp) throw Error(HRY_E_UNSUPPORTED, "more than 32 components in a list");
+	bool quantised = false;
+	for (int c = 0; c < L.ncomp(); ++c) quantised |= L.quant[c] != 0;
+	if (quantised && !L.have_bounds) throw Error(HRY_E_ARG, "quantised list without bounds");
+	const RequantPlan q = quantised ? requant_plan(L, std::vector<uint8_t>(L.ncomp(), 0)) : RequantPlan{};
+	RequantPlan p{};
+	p.n = L.ncomp();
+	int k = 0;
+	for (int c = 0; c < L.ncomp(); ++c) {
+		RequantComp &rc = p.c[c];
+		if (L.quant[c]) { rc = q.c[k++]; continue; }
+		rc.off = L.offset[c]; rc.src_type = L.type[c]; rc.src_bits = 0; rc.dst_bits = 0; rc.dst_type = L.type[c];
+	}
+	return p;
+}
+
+bool rendered(const AttrList &L) { return L.ncomp() > 0 && L.target <= 2; }
+
+}   // namespace
+
+void render_build(Context &cx, const Mesh &m, RenderResult &out)
+{
+	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
+	if (m.lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
+	for (size_t d = 0; d < 3 && d < m.have_degree.size(); ++d)
+		if (m.have_degree[d]) throw Error(HRY_E_INTERNAL, "a face with fewer than three corners (no reader or constructor builds one)");
+	const uint32_t nv = m.nv, nf = m.nf, ne = m.ne();
+	if (m.face_off.size() != (size_t)nf + 1 || m.org.size() < ne) throw Error(HRY_E_ARG, "mesh without its connectivity");
+	const uint64_t ntri = m.ntri();
+	HIP_OK(hipSetDevice(cx.device));
+	out.device = cx.device;
+	const size_t nl = m.lists.size();
+	const bool general = m.general;
+	const Bindings &b = m.bind;
+	for (size_t l = 0; l < nl; ++l)
+		if (m.lists[l].data.size() < (size_t)m.lists[l].count * m.lists[l].stride()) throw Error(HRY_E_ARG, "list without its records");
+
+	// ---- unwelded or not, and the small tables of the general bindings: which slot of a region binds a list
+	std::vector<int> cpos(nl, -1);   // corner-target list -> its place among them
+	uint32_t ncl = 0;
+	for (size_t l = 0; l < nl; ++l) if (m.lists[l].target == 2) cpos[l] = (int)ncl++;
+	bool unweld = false;
+	std::vector<int32_t> small;   // cslot (face regions x corner lists), then per list its slot per region
+	std::vector<size_t> slot_at(nl, 0);
+	size_t cslot_at = 0;
+	if (general) {
+		for (int r = 0; r < b.nregs_face(); ++r) unweld |= b.ncornerlists(r) > 0;
+		if (b.face_reg.size() < nf || b.vtx_reg.size() < nv || b.face_attr.size() < (size_t)nf * b.nb_face || b.vtx_attr.size() < (size_t)nv * b.nb_vtx ||
+		    b.corner_attr.size() < (size_t)ne * b.nb_corner)
+			throw Error(HRY_E_ARG, "mesh without its binding tables");
+		cslot_at = small.size();
+		small.resize(small.size() + (size_t)b.nregs_face() * ncl, -1);
+		for (int r = 0; r < b.nregs_face(); ++r)
+			for (int a = 0; a < b.ncornerlists(r); ++a) {
+				const int l = b.cornerlist(r, a);
+				if (l >= 0 && (size_t)l < nl && cpos[l] >= 0) small[cslot_at + (size_t)r * ncl + cpos[l]] = a;
+			}
+		for (size_t l = 0; l < nl; ++l) {
+			const int t = m.lists[l].target;
+			slot_at[l] = small.size();
+			const int nr = t == 1 ? b.nregs_vtx() : b.nregs_face();
+			small.resize(small.size() + (size_t)std::max(nr, 1), -1);
+			for (int r = 0; r < nr; ++r) {
+				const int n = t == 0 ? b.nfacelists(r) : t == 1 ? b.nvtxlists(r) : t == 2 ? b.ncornerlists(r) : 0;
+				for (int a = 0; a < n; ++a) {
+					const int bl = t == 0 ? b.facelist(r, a) : t == 1 ? b.vtxlist(r, a) : b.cornerlist(r, a);
+					if ((size_t)bl == l) small[slot_at[l] + r] = a;
+				}
+			}
+		}
+	}
+
+	// ---- where the mesh is read: the decode's buffers, or uploads
+	// (a sharded container decoded here: d_whole_*, PLY layout only -- place_segment)
+	const bool whole = cx.render_whole;
+	const DevBuf &r_foff = whole ? cx.d_whole_foff : cx.d_foff, &r_org = whole ? cx.d_whole_org : cx.d_org;
+	auto r_rec = [&](size_t l) -> const DevBuf & { return whole ? cx.d_whole_rec[l] : cx.d_rec[l]; };
+	bool resident = m.render_token != 0 && m.render_token == cx.render_token && cx.render_nf == nf && cx.render_ne == ne && !(whole && (general || nl > 2)) &&
+	                r_foff.cap >= ((size_t)nf + 1) * 4 && r_org.cap >= (size_t)ne * 4;
+	for (size_t l = 0; l < nl && resident; ++l) resident = !rendered(m.lists[l]) || r_rec(l).cap >= m.lists[l].data.size();
+	if (general && resident)
+		resident = cx.d_freg.cap >= (size_t)nf * 2 && cx.d_vreg.cap >= (size_t)nv * 2 && cx.d_fattr.cap >= b.face_attr.size() * 4 &&
+		           cx.d_vattr.cap >= b.vtx_attr.size() * 4 && cx.d_cattr.cap >= b.corner_attr.size() * 4;
+
+	Carve W;   // the working buffer
+	const size_t w_foff = W.reserve(resident ? 0 : ((size_t)nf + 1) * 4), w_org = W.reserve(resident ? 0 : (size_t)ne * 4);
+	std::vector<size_t> w_rec(nl);
+	for (size_t l = 0; l < nl; ++l) w_rec[l] = W.reserve(resident || !rendered(m.lists[l]) ? 0 : m.lists[l].data.size());
+	const bool tables = general && !resident;
+	const size_t w_freg = W.reserve(tables ? b.face_reg.size() * 2 : 0), w_vreg = W.reserve(tables ? b.vtx_reg.size() * 2 : 0);
+	const size_t w_fattr = W.reserve(tables ? b.face_attr.size() * 4 : 0), w_vattr = W.reserve(tables ? b.vtx_attr.size() * 4 : 0);
+	const size_t w_cattr = W.reserve(tables ? b.corner_attr.size() * 4 : 0);
+	const size_t w_small = W.reserve(small.size() * 4);
+	const uint32_t nw = (ne + 63) / 64;
+	const size_t slots = unweld ? unweld_table_slots(ne) : 0;
+	const size_t w_eface = W.reserve(unweld ? (size_t)ne * 4 : 0), w_table = W.reserve(slots * 4), w_first = W.reserve(unweld ? (size_t)ne * 4 : 0);
+	const size_t w_masks = W.reserve(unweld ? (size_t)nw * 8 : 0), w_counts = W.reserve(unweld ? (size_t)nw * 4 : 0);
+	const size_t w_wstart = W.reserve(unweld ? ((size_t)nw + 1) * 4 : 0), w_cmap = W.reserve(unweld ? (size_t)ne * 4 : 0);
+	const size_t w_idx = W.reserve(general ? (size_t)std::max(std::max(nf, nv), ne) * 4 : 0);
+	cx.d_render.ensure(W.total);
+	void *wb = cx.d_render.p;
+
+	hipStream_t st = cx.stream;
+	uint64_t up = 0;
+	auto put = [&](size_t i, const void *src, size_t bytes) {
+		if (!bytes) return;
+		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, i), src, bytes, hipMemcpyHostToDevice, st));
+		up += bytes;
+	};
+	const uint32_t *foff, *org;
+	const uint8_t *rec[kMaxLists] = {};
+	const uint16_t *freg = nullptr, *vreg = nullptr;
+	const uint32_t *fattr = nullptr, *vattr = nullptr, *cattr = nullptr;
+	if (resident) {
+		foff = r_foff.as<uint32_t>(); org = r_org.as<uint32_t>();
+		for (size_t l = 0; l < nl; ++l) rec[l] = r_rec(l).as<uint8_t>();
+		if (general) {
+			freg = cx.d_freg.as<uint16_t>(); vreg = cx.d_vreg.as<uint16_t>();
+			fattr = cx.d_fattr.as<uint32_t>(); vattr = cx.d_vattr.as<uint32_t>(); cattr = cx.d_cattr.as<uint32_t>();
+		}
+	} else {
+		put(w_foff, m.face_off.data(), ((size_t)nf + 1) * 4);
+		put(w_org, m.org.data(), (size_t)ne * 4);
+		foff = W.ptr<uint32_t>(wb, w_foff); org = W.ptr<uint32_t>(wb, w_org);
+		for (size_t l = 0; l < nl; ++l) {
+			if (rendered(m.lists[l])) put(w_rec[l], m.lists[l].data.data(), m.lists[l].data.size());
+			rec[l] = W.ptr<uint8_t>(wb, w_rec[l]);
+		}
+		if (general) {
+			put(w_freg, b.face_reg.data(), b.face_reg.size() * 2); put(w_vreg, b.vtx_reg.data(), b.vtx_reg.size() * 2);
+			put(w_fattr, b.face_attr.data(), b.face_attr.size() * 4); put(w_vattr, b.vtx_attr.data(), b.vtx_attr.size() * 4);
+			put(w_cattr, b.corner_attr.data(), b.corner_attr.size() * 4);
+			freg = W.ptr<uint16_t>(wb, w_freg); vreg = W.ptr<uint16_t>(wb, w_vreg);
+			fattr = W.ptr<uint32_t>(wb, w_fattr); vattr = W.ptr<uint32_t>(wb, w_vattr); cattr = W.ptr<uint32_t>(wb, w_cattr);
+		}
+	}
+	put(w_small, small.data(), small.size() * 4);
+	const int32_t *d_small = W.ptr<int32_t>(wb, w_small);
+
+	hipEvent_t ev[4] = {};
+	struct Events { hipEvent_t *e; ~Events() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ ev };
+	for (hipEvent_t &e : ev) HIP_OK(hipEventCreate(&e));
+
+	// ---- unweld: the number of output vertices comes down before the outputs are allocated (no corners: none).  The events
+	// enclose kernels only: the table's fill and every copy lie outside them
+	uint32_t nout = unweld ? 0 : nv;
+	uint32_t *eface = W.ptr<uint32_t>(wb, w_eface);
+	UnweldView u{};
+	if (unweld && ne) {
+		u.org = org; u.eface = eface; u.corner_attr = cattr; u.face_reg = freg; u.cslot = d_small + cslot_at;
+		u.ne = ne; u.nf = nf; u.nregs = (uint32_t)b.nregs_face(); u.nlists = ncl; u.nb_corner = (uint32_t)b.nb_corner;
+		u.mask = (uint32_t)(slots - 1); u.table = W.ptr<uint32_t>(wb, w_table);
+		HIP_OK(hipMemsetAsync(u.table, 0xff, slots * 4, st));
+	}
+	HIP_OK(hipEventRecord(ev[0], st));
+	if (unweld && ne) {
+		launch_edge_faces(st, foff, nf, eface);
+		launch_unweld_count(st, u, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_counts), W.ptr<uint32_t>(wb, w_wstart));
+	}
+	HIP_OK(hipEventRecord(ev[1], st));
+	if (unweld && ne) HIP_OK(hipMemcpyAsync(&nout, W.ptr<uint32_t>(wb, w_wstart) + nw, 4, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	if (nout > ne && unweld) throw Error(HRY_E_INTERNAL, "unweld: more output vertices than corners");
+
+	// ---- the outputs, in one allocation
+	Carve O;
+	struct Plan { std::string name; uint64_t rows; int width, type; size_t slot; };
+	std::vector<Plan> plan;
+	auto add = [&](const std::string &name, uint64_t rows, int width, int type) {
+		plan.push_back(Plan{ name, rows, width, type, O.reserve((size_t)rows * width * (type == HRY_USHORT ? 2 : 4)) });
+	};
+	add("indices", ntri, 3, HRY_UINT);
+	add("tri_face", ntri, 1, HRY_UINT);
+	add("vertex_source", nout, 1, HRY_UINT);
+	if (unweld) add("corner_source", nout, 1, HRY_UINT);
+	if (general) add("face_region", nf, 1, HRY_USHORT);
+	for (size_t l = 0; l < nl; ++l)
+		if (rendered(m.lists[l])) add("list" + std::to_string(l), m.lists[l].target == 0 ? nf : nout, m.lists[l].ncomp(), HRY_FLOAT);
+	HIP_OK(hipMalloc(&out.block, O.total));
+	for (const Plan &p : plan) out.bufs.push_back(RenderBuf{ p.name, O.ptr<void>(out.block, p.slot), p.rows, p.width, p.type });
+	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+
+	HIP_OK(hipEventRecord(ev[2], st));
+	uint32_t *vsrc = dst("vertex_source");
+	if (unweld && ne) launch_unweld_assign(st, org, ne, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_wstart), nout,
+	                                 W.ptr<uint32_t>(wb, w_cmap), vsrc, dst("corner_source"));
+	else if (!unweld) launch_iota(st, nv, vsrc);
+	launch_fan(st, foff, nf, ntri, unweld ? W.ptr<uint32_t>(wb, w_cmap) : org, ne, dst("tri_face"), dst("indices"));
+	uint32_t *idx = W.ptr<uint32_t>(wb, w_idx);
+	for (size_t l = 0; l < nl; ++l) {
+		const AttrList &L = m.lists[l];
+		if (!rendered(L)) continue;
+		const uint32_t rows = L.target == 0 ? nf : nout;
+		const uint32_t *rows_idx = nullptr;
+		if (general) {
+			RowsView v{};
+			v.slot = d_small + slot_at[l]; v.count = L.count;
+			if (L.target == 0) { v.reg = freg; v.nowner = nf; v.nregs = (uint32_t)b.nregs_face(); v.attr = fattr; v.nb = (uint32_t)b.nb_face; v.nelem = nf; }
+			else if (L.target == 1) { v.src = unweld ? vsrc : nullptr; v.reg = vreg; v.nowner = nv; v.nregs = (uint32_t)b.nregs_vtx(); v.attr = vattr; v.nb = (uint32_t)b.nb_vtx; v.nelem = nv; }
+			else if (unweld) { v.src = dst("corner_source"); v.efc = eface; v.reg = freg; v.nowner = nf; v.nregs = (uint32_t)b.nregs_face(); v.attr = cattr; v.nb = (uint32_t)b.nb_corner; v.nelem = ne; }
+			// (a corner list no region binds, identity layout: nelem 0, every row without a record)
+			launch_rows_of(st, v, rows, idx);
+			rows_idx = idx;
+		}
+		launch_render_gather(st, rec[l], L.stride(), L.count, rows_idx, rows, gather_plan(L), (float*)dst(("list" + std::to_string(l)).c_str()));
+	}
+	HIP_OK(hipEventRecord(ev[3], st));
+	if (general && nf) HIP_OK(hipMemcpyAsync(dst("face_region"), freg, (size_t)nf * 2, hipMemcpyDeviceToDevice, st));
+	HIP_OK(hipStreamSynchronize(st));
+	float a = 0, c = 0;
+	HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+	HIP_OK(hipEventElapsedTime(&c, ev[2], ev[3]));
+	out.device_ms = (double)a + (double)c;
+	out.uploaded_bytes = up;
+	out.nverts = nout;
+	out.ntris = ntri;
+}
+
+// one counter for the whole process: a token names one decode on one context, whatever other contexts do
+static std::atomic<uint64_t> g_render_tokens{ 1 };
+
+void mark_decoded(Context &cx, Mesh &m, bool whole)
+{
+	m.render_token = 0;
+	cx.render_token = 0;
+	if (!whole && (cx.res_nf != m.nf || cx.res_ne != m.ne())) return;   // (the context's connectivity is not this mesh's)
+	m.render_token = cx.render_token = g_render_tokens.fetch_add(1, std::memory_order_relaxed);
+	cx.render_whole = whole;
+	cx.render_nf = m.nf; cx.render_ne = m.ne();
+}
+
+bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne)
+{
+	const uint32_t nlv = seg.nv, nlf = seg.nf, nle = seg.ne(), nr = (uint32_t)runs.size();
+	const size_t vstride = (size_t)seg.lists[1].stride(), fstride = (size_t)seg.lists[0].stride();
+	if (seg.general || seg.lists.size() != 2 || cx.res_nf != nlf || cx.res_ne != nle || cx.d_foff.cap < ((size_t)nlf + 1) * 4 || cx.d_org.cap < (size_t)nle * 4 ||
+	    cx.d_rec[1].cap < (size_t)nlv * vstride || cx.d_rec[0].cap < (size_t)nlf * fstride)
+		return false;
+	std::vector<uint32_t> tab((size_t)6 * nr);
+	uint32_t lv = 0, lf = 0, lh = 0;
+	for (uint32_t j = 0; j < nr; ++j) {
+		const ShardRun &r = runs[j];
+		tab[j] = lv; tab[nr + j] = lf; tab[2 * nr + j] = lh;
+		tab[3 * nr + j] = r.first_vertex; tab[4 * nr + j] = r.first_face; tab[5 * nr + j] = r.first_halfedge;
+		lv += r.n_vertices; lf += r.n_faces; lh += r.n_halfedges;
+	}
+	if (lv != nlv || lf != nlf || lh != nle) return false;
+	cx.d_whole_runs.ensure(std::max<size_t>(tab.size() * 4, 16));
+	HIP_OK(hipMemcpyAsync(cx.d_whole_runs.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, cx.stream));
+	const uint32_t *t = cx.d_whole_runs.as<uint32_t>();
+	const RunPlace rp{ t, t + nr, t + 2 * nr, t + 3 * nr, t + 4 * nr, t + 5 * nr, nr, gnv, gnf, gne };
+	launch_place_segment(cx.stream, rp, cx.d_rec[1].as<uint8_t>(), nlv, (uint32_t)vstride, cx.d_whole_rec[1].as<uint8_t>(),
+	                     cx.d_rec[0].as<uint8_t>(), nlf, (uint32_t)fstride, cx.d_whole_rec[0].as<uint8_t>(), cx.d_org.as<uint32_t>(), nle, cx.d_whole_org.as<uint32_t>(),
+	                     cx.d_foff.as<uint32_t>(), cx.d_whole_foff.as<uint32_t>());
+	HIP_OK(hipStreamSynchronize(cx.stream));   // (the next segment's decode reuses d_rec / d_foff / d_org, on other streams too)
+	return true;
+}
+
+void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device)
+{
+	const RenderBuf *b = r.find(name);
+	if (!b) throw Error(HRY_E_ARG, std::string("no such render buffer: ") + name);
+	if (!b->bytes()) return;
+	if (!dst) throw Error(HRY_E_ARG, "null destination");
+	HIP_OK(hipSetDevice(cx.device));
+	HIP_OK(hipMemcpyAsync(dst, b->p, b->bytes(), dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
+	HIP_OK(hipStreamSynchronize(cx.stream));
+}
+
+}   // namespace hry

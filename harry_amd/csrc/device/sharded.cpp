@@ -549,6 +549,20 @@ Mesh *decode_sharded(Context *const *cxs, int n_ctx, const uint8_t *p, size_t n,
 	}
 	g->covered.clear(); g->covered_records.clear();
 	const size_t vstride = general ? 0 : (size_t)g->lists[1].stride(), fstride = general ? 0 : (size_t)g->lists[0].stride();
+	// the whole mesh decoded on ONE context (PLY layout): every segment's device results also go to their places in d_whole_*, so
+	// that hry_render_build reads the mesh where it is (render.cpp: place_segment, mark_decoded)
+	const bool place = n_ctx == 1 && everything && !general && nl == 2;
+	bool placed = place;
+	if (place) {
+		Context &c0 = *cxs[0];
+		HIP_OK(hipSetDevice(c0.device));
+		auto zeroed = [&](DevBuf &d, size_t bytes) {
+			d.ensure(std::max<size_t>(bytes, 16));
+			HIP_OK(hipMemsetAsync(d.p, 0, std::max<size_t>(bytes, 16), c0.stream));   // (vertices no run covers keep zero records, as in *g)
+		};
+		zeroed(c0.d_whole_rec[1], (size_t)gnv * vstride); zeroed(c0.d_whole_rec[0], (size_t)gnf * fstride);
+		zeroed(c0.d_whole_foff, ((size_t)gnf + 1) * 4); zeroed(c0.d_whole_org, (size_t)gne * 4);
+	}
 
 	std::vector<double> w_decode(n_ctx, 0.0), w_place(n_ctx, 0.0);
 	t0 = Clock::now();
@@ -647,6 +661,7 @@ Mesh *decode_sharded(Context *const *cxs, int n_ctx, const uint8_t *p, size_t n,
 			run_tasks(0, n_vf_tasks);               // the vertex map first: half-edges of one run may name vertices of another
 			run_tasks(n_vf_tasks, tasks.size());
 			if (bad.load()) throw Error(HRY_E_FORMAT, "corrupt segment (runs do not match the connectivity)");
+			if (placed && !place_segment(cx, *dm, runs, gnv, gnf, gne)) placed = false;
 			if (general) {
 				// the records of every list into the numbering of the whole (creation order over all components: run j's records
 				// of list l sit at its first_record), then every element's region and slots
@@ -743,6 +758,7 @@ Mesh *decode_sharded(Context *const *cxs, int n_ctx, const uint8_t *p, size_t n,
 	for (int w = 0; w < n_ctx; ++w) cxs[w]->timing.total_ms = st.total_ms;
 	if (st_out) *st_out = st;
 	g->device_token = 0;
+	if (placed) mark_decoded(*cxs[0], *g, true);
 	return g.release();
 }
 

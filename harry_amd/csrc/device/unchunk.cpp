@@ -1179,6 +1179,7 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	cx.timing.payload_bytes = payload_bytes;
 	cx.timing.total_ms = ms_since(t_all);
 	m->device_token = 0;   // the resident copy belongs to this context only until the next upload
+	mark_decoded(cx, *m);   // ... but hry_render_build may read it (render.cpp)
 	return m.release();
 }
 
@@ -1257,6 +1258,7 @@ Mesh *decode_compat(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::un
 	cx.timing.payload_bytes = n - hdr;
 	cx.timing.total_ms = ms_since(t_all);
 	m->device_token = 0;
+	mark_decoded(cx, *m);
 	return m.release();
 }
 

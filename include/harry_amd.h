@@ -13,6 +13,7 @@
  *   hry_encode          <- hry::writer::write(std::ostream&, mesh::Mesh&)         formats/hry/writer.h:19, writer.cc:200-218
  *   hry_decode          <- hry::reader::read(std::istream&, mesh::Mesh&)          formats/hry/reader.h:19, reader.cc:179-193
  *   hry_bounds          <- quant::set_bounds(Attrs&)                              structs/quant.h:30-44 (called by ply/reader.cc:428)
+ *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -185,6 +186,46 @@ void hry_free(void *p);
  * [1] header bytes, [2] vertices, [3] faces, [4] half-edges, [5] symbols per chunk and plane (first segment; 0 for v0.1),
  * [6] the same for the connectivity planes, [7] segments (v0.3; else 1) */
 int hry_container_info(const uint8_t *hry, size_t n, uint32_t info[8]);
+
+/* ---- render-ready device buffers ---------------------------------------------------------------------------------------
+ * hry_render_build turns a mesh (decoded, or read from PLY / OBJ) into buffers on ctx's device that a GPU program draws or trains
+ * on.  Let U be the number of output vertices and T = hry_mesh_ntri = sum(deg - 2) triangles (structs/conn.h:87).  Buffers by name:
+ *   "indices"        u32 [T, 3]  fan triangulation: triangle k of face f with corners c0 .. c(d-1) is (c0, c(k+1), c(k+2)), mapped to
+ *                                output vertices; faces in mesh order
+ *   "tri_face"       u32 [T]     source face of every triangle
+ *   "vertex_source"  u32 [U]     decoded vertex of every output vertex
+ *   "corner_source"  u32 [U]     unwelded meshes only: the first corner (half-edge) that produced the output vertex
+ *   "face_region"    u16 [nf]    general bindings only: the face region (material) of every face
+ *   "list<l>"        f32 [rows, ncomp(l)]  every component of list l (l in decimal: "list0", "list1", ...), row-major; vertex and
+ *                                corner lists have U rows, face lists nf; lists without components or without a target are absent
+ * A value of list l is (float) of what hry_requant(..., clear = 1) gives for that component (the reference's -c dequantisation,
+ * structs/quant.h:98-112,215-242): lossless floats bit for bit (-0.0 included), integers as their value, quantised doubles rounded
+ * once, to nearest.  An element whose region does not bind list l gets 0 in that list.
+ * U depends on the input only:
+ *   identity (U = nv, output vertex u = vertex u): the PLY layout, and general bindings where no face region binds a corner list;
+ *   unwelded: general bindings with corner lists (OBJ vt / vn).  The key of corner c is (org[c], then for every list with corner target,
+ *     in list order, the record c names, or 0xFFFFFFFF where the region of c's face does not bind that list); corners with equal keys
+ *     share one output vertex, numbered in order of first occurrence over the corners in half-edge order (deterministic).
+ * A partial mesh (hry_mesh_partial) is refused with HRY_E_ARG.  (Every mesh the library builds has polygons of 3 .. 255 corners:
+ * the readers, hry_mesh_from_arrays and the .hry header refuse others, so T = sum(deg - 2) counts every triangle.)
+ * Residency: when m is the mesh hry_decode (or hry_decode_sharded with one context) just returned on ctx and no other call has
+ * touched ctx or m since, the build reads the decoded records, connectivity and binding tables where the decode left them in HBM:
+ * for the PLY layout nothing goes up, in every profile (v0.1, v0.2, and a v0.3 container decoded whole on one context).  Otherwise
+ * -- another context, a call in between, a mesh read from PLY / OBJ -- it uploads what it needs.  Either way the results are the
+ * same, and the encoder's resident mesh (hry_mesh_upload) is left alone.
+ * The handle owns its device memory: its buffers stay valid whatever later calls do on the context; free it before the context. */
+typedef struct hry_render hry_render;
+int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out);
+uint32_t hry_render_nverts(const hry_render *r);   /* U */
+uint64_t hry_render_ntris(const hry_render *r);    /* T */
+/* a buffer by name: *rows (0: absent), and per row *width values of *type (HRY_UINT / HRY_USHORT / HRY_FLOAT) at device address *dev */
+int hry_render_get(const hry_render *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+/* the whole buffer to dst (device memory: dst_is_device = 1, else host memory) on ctx's stream; returns when it is there */
+int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *dst, int dst_is_device);
+/* device_ms: the render kernels alone, measured with HIP events (the hash table's fill and every copy lie outside);
+ * uploaded_bytes: host-to-device bytes the build needed */
+int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes);
+void hry_render_free(hry_render *r);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
