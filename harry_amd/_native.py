@@ -30,6 +30,11 @@ class Opts(C.Structure):
                 ("shard_index", C.c_int32), ("shard_count", C.c_int32)]
 
 
+class DevColumn(C.Structure):
+    """hry_dev_column: one component read from device memory, row i at data + i * stride"""
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_uint64), ("name", C.c_char_p), ("type", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("host_walk_ms", C.c_double), ("h2d_ms", C.c_double), ("device_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("total_ms", C.c_double), ("k_rchain_ms", C.c_double), ("k_model_ms", C.c_double), ("k_predict_ms", C.c_double),
@@ -54,6 +59,7 @@ FLAG_HOST_RECURRENCE = 1
 FLAG_DEVICE_RECURRENCE = 2
 FLAG_PARTIAL = 4
 FLAG_KEEP_MESH = 8
+INGEST_WELD = 1
 
 _lib = None
 
@@ -145,6 +151,10 @@ def load():
     L.hry_render_copy.restype = C.c_int; L.hry_render_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_render_free.argtypes = [vp]
+    L.hry_mesh_from_device.restype = C.c_int
+    L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),
+                                       C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.hry_mesh_resident.restype = C.c_int; L.hry_mesh_resident.argtypes = [vp, vp]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

@@ -410,6 +410,81 @@ class Codec:
             return t
         return self._render(mesh, fill)
 
+    # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
+    def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
+        """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the
+        encoder uploads nothing for it).  indices: int32 / int64, [T, 3] (every face a triangle) or 1-D with degrees (uint8 [nf]);
+        vertex / faces: [(names, tensor)], names one per column ("x y z"), tensor [n] for one name or [n, k] for k names, passed
+        with its own strides (views need no copy).  weld: vertices whose records are equal byte for byte become one, numbered in
+        order of first occurrence; return_remap: also the output vertex of every input row (int32 [nv] on this device)."""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+        types = {torch.float32: 0, torch.float64: 1, torch.int64: 3, torch.int32: 5, torch.int16: 7, torch.uint8: 8, torch.int8: 9}
+        for name, t in (("uint64", 2), ("uint32", 4), ("uint16", 6)):
+            if hasattr(torch, name):
+                types[getattr(torch, name)] = t
+
+        def refuse(msg):
+            return HryError(nat.E_ARG, msg)
+
+        def tensor(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise refuse(f"{what}: not a tensor on {dev}")
+            return t
+
+        def columns(spec, what):
+            cols, rows = [], None
+            for names, t in spec or ():
+                tensor(t, what)
+                names = names.split() if isinstance(names, str) else list(names)
+                if t.dtype not in types:
+                    raise refuse(f"{what} {' '.join(names)}: unsupported dtype {t.dtype}")
+                if not ((t.dim() == 1 and len(names) == 1) or (t.dim() == 2 and t.shape[1] == len(names))):
+                    raise refuse(f"{what} {' '.join(names)}: shape {tuple(t.shape)} does not fit {len(names)} names")
+                if rows is not None and t.shape[0] != rows:
+                    raise refuse(f"{what} {' '.join(names)}: {t.shape[0]} rows, the others have {rows}")
+                rows, item = t.shape[0], t.element_size()
+                for j, name in enumerate(names):
+                    off = j * t.stride(1) * item if t.dim() == 2 else 0
+                    cols.append(nat.DevColumn(t.data_ptr() + off, t.stride(0) * item, name.encode(), types[t.dtype]))
+            return cols, rows or 0
+
+        tensor(indices, "indices")
+        if indices.dtype not in (torch.int32, torch.int64):
+            raise refuse(f"indices: dtype {indices.dtype} (int32 or int64)")
+        if degrees is None:
+            if indices.dim() != 2 or indices.shape[1] != 3:
+                raise refuse("indices: [T, 3] without degrees")
+            nf = indices.shape[0]
+        else:
+            tensor(degrees, "degrees")
+            if degrees.dtype != torch.uint8 or degrees.dim() != 1 or indices.dim() != 1:
+                raise refuse("degrees: uint8 [nf] with 1-D indices")
+            degrees = degrees.contiguous()
+            nf = degrees.shape[0]
+        indices = indices.contiguous()
+        vcols, nv = columns(vertex, "vertex")
+        fcols, nff = columns(faces, "face")
+        if fcols and nff != nf:
+            raise refuse(f"face columns: {nff} rows for {nf} faces")
+        if max(nv, nf, indices.numel()) >= 2 ** 32:
+            raise refuse("more than 2^32 - 1 vertices, faces or indices")
+        remap = torch.empty(nv, dtype=torch.int32, device=dev) if return_remap else None
+        torch.cuda.current_stream(dev).synchronize()   # (the tensors may still be being written by torch's stream)
+        h = C.c_void_p()
+        va = (nat.DevColumn * max(len(vcols), 1))(*vcols)
+        fa = (nat.DevColumn * max(len(fcols), 1))(*fcols)
+        nat.check(nat.load().hry_mesh_from_device(
+            self.h, nv, va, len(vcols), nf, degrees.data_ptr() if degrees is not None else None, indices.data_ptr() if indices.numel() else None,
+            4 if indices.dtype == torch.int32 else 3, indices.numel(), fa, len(fcols), nat.INGEST_WELD if weld else 0,
+            remap.data_ptr() if remap is not None and nv else None, C.byref(h)))
+        mesh = Mesh(h)
+        return (mesh, remap) if return_remap else mesh
+
+    def resident(self, mesh: Mesh) -> bool:
+        """hry_mesh_resident: this context holds the mesh's records and connectivity in HBM (an encode uploads nothing for it)"""
+        return bool(nat.load().hry_mesh_resident(self.h, mesh.h))
+
     def render_stat(self) -> dict:
         """of the last render / render_numpy: device_ms (render kernels), uploaded_bytes (host to device), nverts (U), ntris (T)"""
         return dict(getattr(self, "_render_stat", {}))

@@ -641,4 +641,22 @@ int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_b
 }
 void hry_render_free(hry_render *r) { delete r; }
 
+// ---- meshes from device buffers (ingest.cpp)
+int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,
+                         const void *d_indices, int index_type, uint64_t n_indices, const hry_dev_column *fcols, int f_ncomp, int flags,
+                         uint32_t *d_remap, hry_mesh **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !out || (v_ncomp > 0 && !vcols) || (f_ncomp > 0 && !fcols) || (n_indices && !d_indices)) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx);
+	return guarded([&] {
+		std::unique_ptr<Mesh> m(mesh_from_device(ctx->cx, nv, vcols, v_ncomp, nf, d_degrees, d_indices, index_type, n_indices, fcols, f_ncomp, flags, d_remap));
+		*out = new hry_mesh{ std::move(*m) };
+	});
+}
+int hry_mesh_resident(const hry_ctx *ctx, const hry_mesh *m)
+{
+	return ctx && m && m->m.device_token != 0 && m->m.device_token == ctx->cx.resident_token ? 1 : 0;
+}
+
 }   // extern "C"

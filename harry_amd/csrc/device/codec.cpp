@@ -8,6 +8,7 @@
 //   k_low_accumulate, k_carry_*                       low register as one big number    -> payload bytes
 //
 // Reference: formats/hry/writer.cc:200-214 (compress), attrcode.h:395-416 (encode), arith/coder.h:58-112.
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
@@ -115,6 +116,17 @@ void Context::upload_mesh(Mesh &m, bool with_records)
 	HIP_OK(hipMemcpyAsync(d_org.p, m.org.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
 	if (!m.twins_pending) HIP_OK(hipMemcpyAsync(d_twin.p, m.twin.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
 	HIP_OK(hipMemcpyAsync(d_foff.p, m.face_off.data(), ((size_t)m.nf + 1) * 4, hipMemcpyHostToDevice, stream));
+	conn_state(m);
+	if (m.twins_pending && ne && m.nv)   // a freshly read mesh: its twins are matched on the device
+		for (uint32_t v : m.org) if (v >= m.nv) throw Error(HRY_E_ARG, "vertex index out of range");
+	match_twins(m);
+	HIP_OK(hipStreamSynchronize(stream));
+	if (!with_records) { resident_token = 0; return; }   // connectivity only (twin matching for a caller that shards the mesh): nothing stays resident
+	make_resident(m);
+}
+void Context::conn_state(const Mesh &m)
+{
+	const uint32_t ne = m.ne();
 	int ud = 0;
 	res_has_eface = !m.uniform_degree(ud);
 	res_udeg = (uint32_t)ud;
@@ -123,32 +135,37 @@ void Context::upload_mesh(Mesh &m, bool with_records)
 		dev::launch_edge_faces(stream, d_foff.as<uint32_t>(), m.nf, d_eface.as<uint32_t>());
 	}
 	res_nv = m.nv; res_nf = m.nf; res_ne = ne;
-	if (m.twins_pending) {   // a freshly read mesh: half-edge twin matching on the device (twins.hip), and down for the host's walk
-		if (ne && m.nv) {
-			for (uint32_t v : m.org) if (v >= m.nv) throw Error(HRY_E_ARG, "vertex index out of range");
-			d_cscratch.ensure(dev::twin_workspace_bytes(m.nv, ne));
-			const uint32_t *d_over = nullptr;
-			dev::launch_twins(stream, conn_view(), m.nv, d_twin.as<uint32_t>(), d_cscratch.p, &d_over);
-			m.twin.resize(ne);
-			std::vector<uint32_t> over(1 + dev::twin_overflow_capacity(), 0);
-			HIP_OK(hipMemcpyAsync(m.twin.data(), d_twin.p, (size_t)ne * 4, hipMemcpyDeviceToHost, stream));
-			HIP_OK(hipMemcpyAsync(over.data(), d_over, over.size() * 4, hipMemcpyDeviceToHost, stream));
-			HIP_OK(hipStreamSynchronize(stream));
-			if (over[0] > dev::twin_overflow_capacity()) {   // a mesh of hubs: the host's matcher does all of it
-				m.twins_pending = true;
-				ensure_twins(m);
-				HIP_OK(hipMemcpyAsync(d_twin.p, m.twin.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
-			} else if (over[0]) {
-				match_twins_at(m, over.data() + 1, over[0]);   // the few hubs, with the reference's rule, on the host
-				HIP_OK(hipMemcpyAsync(d_twin.p, m.twin.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
-			}
-		} else m.twin.resize(ne);
+}
+void Context::match_twins(Mesh &m)
+{
+	if (!m.twins_pending) return;
+	const uint32_t ne = m.ne();
+	if (ne && m.nv) {   // half-edge twin matching on the device (twins.hip), and down for the host's walk
+		d_cscratch.ensure(dev::twin_workspace_bytes(m.nv, ne));
+		const uint32_t *d_over = nullptr;
+		dev::launch_twins(stream, conn_view(), m.nv, d_twin.as<uint32_t>(), d_cscratch.p, &d_over);
+		m.twin.resize(ne);
+		std::vector<uint32_t> over(1 + dev::twin_overflow_capacity(), 0);
+		HIP_OK(hipMemcpyAsync(m.twin.data(), d_twin.p, (size_t)ne * 4, hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipMemcpyAsync(over.data(), d_over, over.size() * 4, hipMemcpyDeviceToHost, stream));
 		HIP_OK(hipStreamSynchronize(stream));
-		m.twins_pending = false;
-	}
+		if (over[0] > dev::twin_overflow_capacity()) {   // a mesh of hubs: the host's matcher does all of it
+			m.twins_pending = true;
+			ensure_twins(m);
+			HIP_OK(hipMemcpyAsync(d_twin.p, m.twin.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
+		} else if (over[0]) {
+			match_twins_at(m, over.data() + 1, over[0]);   // the few hubs, with the reference's rule, on the host
+			HIP_OK(hipMemcpyAsync(d_twin.p, m.twin.data(), (size_t)ne * 4, hipMemcpyHostToDevice, stream));
+		}
+	} else m.twin.resize(ne);
 	HIP_OK(hipStreamSynchronize(stream));
-	if (!with_records) { resident_token = 0; return; }   // connectivity only (twin matching for a caller that shards the mesh): nothing stays resident
-	m.device_token = next_token++;
+	m.twins_pending = false;
+}
+// one counter for the whole process: a token names one mesh on one context, whatever other contexts do
+static std::atomic<uint64_t> g_device_tokens{ 1 };
+void Context::make_resident(Mesh &m)
+{
+	m.device_token = g_device_tokens.fetch_add(1, std::memory_order_relaxed);
 	resident_token = m.device_token;
 }
 void Context::ensure_second_stream()
@@ -161,15 +178,7 @@ void Context::adopt_conn(Mesh &m)
 {
 	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
 	HIP_OK(hipSetDevice(device));
-	const uint32_t ne = m.ne();
-	int ud = 0;
-	res_has_eface = !m.uniform_degree(ud);
-	res_udeg = (uint32_t)ud;
-	if (res_has_eface) {
-		d_eface.ensure(std::max<size_t>((size_t)ne * 4, 16));
-		dev::launch_edge_faces(stream, d_foff.as<uint32_t>(), m.nf, d_eface.as<uint32_t>());
-	}
-	res_nv = m.nv; res_nf = m.nf; res_ne = ne;
+	conn_state(m);
 	m.twins_pending = false;
 	HIP_OK(hipStreamSynchronize(stream));
 	resident_token = 0;

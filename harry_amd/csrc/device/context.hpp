@@ -97,7 +97,6 @@ struct Context {
 	bool render_whole = false;       // ... the mesh is a sharded container decoded here: its records and connectivity are in d_whole_*
 	uint32_t render_nf = 0, render_ne = 0;
 	DevBuf d_whole_rec[2], d_whole_foff, d_whole_org, d_whole_runs;   // decode_sharded on ONE context, PLY layout: the segments' device results placed into the whole numbering (render.cpp: place_segment)
-	uint64_t next_token = 1;
 	DevBuf d_rec[kMaxLists], d_org, d_twin, d_foff, d_eface;
 	DevBuf d_vreg, d_freg, d_vattr, d_cattr, d_fattr, d_gen;   // general bindings (general.cpp): region and record tables, event arena
 	uint32_t res_nv = 0, res_nf = 0, res_ne = 0, res_udeg = 0;
@@ -113,6 +112,7 @@ struct Context {
 	// chunked profile
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
+	DevBuf d_ingest;   // hry_mesh_from_device: status word, scans, the weld's keys and table (ingest.cpp)
 	DevBuf d_split;   // chunked encode in two kernels: per stream the place of its records and the streams' order, longest first (the records: d_rec_sym)
 	DevBuf d_pipe, d_nt_val, d_nt_planes;   // EncodePipeline: run tables and twin pairs of the batches; the polygons' triangle counts and their two byte planes
 	std::vector<uint32_t> h_twin_patch;   // (half-edge, twin) pairs on their way to d_patch (upload_repaired_twins)
@@ -137,6 +137,11 @@ struct Context {
 	void ensure_magic(uint32_t n);
 	void upload_mesh(Mesh &m, bool with_records = true);
 	void adopt_conn(Mesh &m);        // the connectivity is in d_foff / d_org / d_twin already (unchunk.cpp: SpanUploader): the rest of upload_mesh
+	void conn_state(const Mesh &m);  // d_foff / d_org hold m's connectivity: the face of every half-edge (mixed degrees) and res_*
+	// m.twins_pending, its connectivity in d_foff / d_org (conn_state done) and every index below nv: the twins matched on the
+	// device (twins.hip; hubs on the host, from m's host arrays) into d_twin and m.twin
+	void match_twins(Mesh &m);
+	void make_resident(Mesh &m);     // m and this context share a new token (drawn from one counter of the process): m is resident here
 	void ensure_second_stream();
 	dev::ConnView conn_view() const;
 	float elapsed(int a, int b);
@@ -240,6 +245,11 @@ void mark_decoded(Context &cx, Mesh &m, bool whole = false);
 bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne);
 void render_build(Context &cx, const Mesh &m, RenderResult &out);
 void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
+
+// ingest.cpp: hry_mesh_from_device (include/harry_amd.h); the result is resident on cx
+Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,
+                       const void *d_indices, int index_type, uint64_t n_indices, const hry_dev_column *fcols, int f_ncomp, int flags,
+                       uint32_t *d_remap);
 
 dev::ListDesc make_list_desc(const AttrList &L);
 void check_codable(const Mesh &m);

@@ -1,0 +1,174 @@
+// A mesh from device buffers (include/harry_amd.h: hry_mesh_from_device; kernels: ingest.hip; DESIGN.md "7b. Meshes from device
+// buffers").  The result is what hry_mesh_from_arrays builds from the same values, and it is resident on the context exactly as after
+// hry_mesh_upload: the kernels write the records, org and face offsets straight into d_rec / d_org / d_foff, the twins are matched
+// there (Context::match_twins, the code an upload runs), and the host copies come down once.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "context.hpp"
+#include "kernels.hpp"
+
+namespace hry {
+
+using namespace dev;
+
+namespace {
+
+// the caller's buffer: device memory of the context's device, and (where the runtime can say) [p, p + bytes) inside one allocation
+void check_device_memory(const Context &cx, const void *p, uint64_t bytes, const std::string &what)
+{
+	hipPointerAttribute_t a{};
+	const hipError_t e = hipPointerGetAttributes(&a, p);
+	if (e != hipSuccess) (void)hipGetLastError();
+	if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != cx.device)
+		throw Error(HRY_E_ARG, what + ": not device memory of the context's device");
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return; }
+	if ((const uint8_t*)p + bytes > (const uint8_t*)base + size) throw Error(HRY_E_ARG, what + ": extends past the end of its allocation");
+}
+
+// the layout of one list (layout_attr_list, as hry_mesh_from_arrays) and where each byte of its records comes from
+PackCols list_from_columns(const Context &cx, AttrList &L, int target, const hry_dev_column *cols, int ncomp, uint32_t rows, const char *what)
+{
+	std::vector<std::string> nm;
+	std::vector<CompType> ty;
+	std::vector<bool> isl;
+	for (int i = 0; i < ncomp; ++i) {
+		const hry_dev_column &c = cols[i];
+		if (c.type < 0 || c.type >= C_NONE) throw Error(HRY_E_ARG, "bad component type");
+		if (!c.name) throw Error(HRY_E_ARG, "null component name");
+		const std::string where = std::string(what) + " column " + c.name;
+		const uint64_t sz = (uint64_t)kTypeSize[c.type];
+		if (c.stride == 0 || c.stride % sz) throw Error(HRY_E_ARG, where + ": the stride is not a non-zero multiple of the type's size");
+		if ((uintptr_t)c.data % sz) throw Error(HRY_E_ARG, where + ": misaligned");
+		if (rows) check_device_memory(cx, c.data, (uint64_t)(rows - 1) * c.stride + sz, where);
+		nm.push_back(c.name); ty.push_back((CompType)c.type); isl.push_back(false);
+	}
+	std::vector<int> slot;
+	L.target = target;
+	layout_attr_list(nm, ty, isl, L, slot);
+	L.count = rows;
+	PackCols p{};
+	p.rec_stride = (uint32_t)L.stride();
+	for (int i = 0; i < ncomp; ++i) {
+		const int c = slot[i];
+		p.src[c] = (const uint8_t*)cols[i].data;
+		p.stride[c] = cols[i].stride;
+		for (int b = 0; b < kTypeSize[ty[i]]; ++b) { p.comp_of[L.offset[c] + b] = (uint8_t)c; p.byte_of[L.offset[c] + b] = (uint8_t)b; }
+	}
+	return p;
+}
+
+}   // namespace
+
+Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,
+                       const void *d_indices, int index_type, uint64_t n_indices, const hry_dev_column *fcols, int f_ncomp, int flags,
+                       uint32_t *d_remap)
+{
+	HIP_OK(hipSetDevice(cx.device));
+	const bool weld = (flags & HRY_INGEST_WELD) != 0;
+	if (flags & ~HRY_INGEST_WELD) throw Error(HRY_E_ARG, "unknown flags");
+	if (index_type != HRY_UINT && index_type != HRY_LONG) throw Error(HRY_E_ARG, "index type must be HRY_UINT or HRY_LONG");
+	if (v_ncomp < 0 || f_ncomp < 0) throw Error(HRY_E_ARG, "negative component count");
+	if (weld && v_ncomp == 0) throw Error(HRY_E_ARG, "weld: vertices without components have no key");
+	if (n_indices > 0xffffffffull) throw Error(HRY_E_UNSUPPORTED, "more than 2^32-1 half-edges");
+	if (!d_degrees && n_indices != 3ull * nf) throw Error(HRY_E_ARG, "sum of degrees differs from the number of indices");
+	const uint32_t ne = (uint32_t)n_indices;
+	const bool idx64 = index_type == HRY_LONG;
+	if (nf && d_degrees) check_device_memory(cx, d_degrees, nf, "degrees");
+	if (ne) check_device_memory(cx, d_indices, (uint64_t)ne * (idx64 ? 8 : 4), "indices");
+	if (d_remap && nv) check_device_memory(cx, d_remap, (uint64_t)nv * 4, "remap");
+
+	std::unique_ptr<Mesh> m(new Mesh());
+	const PackCols pf = list_from_columns(cx, m->lists[0], 0, fcols, f_ncomp, nf, "face");
+	const PackCols pv = list_from_columns(cx, m->lists[1], 1, vcols, v_ncomp, nv, "vertex");
+	const size_t sv = pv.rec_stride, sfc = pf.rec_stride;
+
+	// ---- the context's resident buffers are rewritten from here on: whatever mesh they held is no longer resident
+	cx.resident_token = 0;
+	hipStream_t st = cx.stream;
+	cx.d_foff.ensure(((size_t)nf + 1) * 4);
+	cx.d_org.ensure(std::max<size_t>((size_t)ne * 4, 16));
+	cx.d_twin.ensure(std::max<size_t>((size_t)ne * 4, 16));
+	cx.d_rec[0].ensure(std::max<size_t>((size_t)nf * sfc, 16));
+	cx.d_rec[1].ensure(std::max<size_t>((size_t)nv * sv, 16));
+
+	// working arrays: 256-byte aligned pieces of one buffer
+	std::vector<size_t> at;
+	size_t total = 0;
+	auto reserve = [&](size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at.size() - 1; };
+	auto ptr = [&](size_t i) { return (void*)(cx.d_ingest.as<uint8_t>() + at[i]); };
+	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64), nwv = (uint32_t)(((uint64_t)nv + 63) / 64);
+	const size_t slots = weld ? unweld_table_slots(nv) : 0;
+	const size_t status_bytes = sizeof(IngestStatus) + 8;   // (+ the number of welded vertices)
+	const size_t w_status = reserve(status_bytes);
+	const size_t w_fsum = reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	const size_t w_keys = reserve(weld ? (size_t)nv * sv : 0), w_table = reserve(slots * 4), w_first = reserve(weld ? (size_t)nv * 4 : 0);
+	const size_t w_masks = reserve(weld ? (size_t)nwv * 8 : 0), w_counts = reserve(weld ? (size_t)nwv * 4 : 0);
+	const size_t w_vstart = reserve(weld ? ((size_t)nwv + 1) * 4 : 0), w_remap = reserve(weld ? (size_t)nv * 4 : 0);
+	const size_t w_frow = reserve(weld ? (size_t)nv * 4 : 0);
+	cx.d_ingest.ensure(total);
+	IngestStatus *status = (IngestStatus*)ptr(w_status);
+	uint32_t *d_nout = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));
+	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
+
+	// ---- every kernel up to the checks, then ONE read-back of the status word (and the welded count)
+	launch_ingest_offsets(st, d_degrees, nf, (uint32_t*)ptr(w_fsum), (uint32_t*)ptr(w_fstart), cx.d_foff.as<uint32_t>(), status);
+	const uint32_t *remap = nullptr;
+	if (weld) {
+		uint8_t *keys = (uint8_t*)ptr(w_keys);
+		launch_ingest_pack(st, pv, nv, nullptr, nv, keys);
+		const WeldView u{ keys, (uint32_t)sv, nv, (uint32_t)(slots - 1), (uint32_t*)ptr(w_table) };
+		HIP_OK(hipMemsetAsync(u.table, 0xff, slots * 4, st));
+		launch_weld_count(st, u, (uint32_t*)ptr(w_first), (uint64_t*)ptr(w_masks), (uint32_t*)ptr(w_counts), (uint32_t*)ptr(w_vstart));
+		launch_weld_assign(st, nv, (const uint32_t*)ptr(w_first), (const uint64_t*)ptr(w_masks), (const uint32_t*)ptr(w_vstart), (uint32_t*)ptr(w_remap),
+		                   (uint32_t*)ptr(w_frow));
+		if (nv) HIP_OK(hipMemcpyAsync(d_nout, (const uint32_t*)ptr(w_vstart) + nwv, 4, hipMemcpyDeviceToDevice, st));
+		remap = (const uint32_t*)ptr(w_remap);
+	} else launch_ingest_pack(st, pv, nv, nullptr, nv, cx.d_rec[1].as<uint8_t>());
+	launch_ingest_org(st, d_indices, idx64, ne, nv, remap, cx.d_org.as<uint32_t>(), status);
+	launch_ingest_pack(st, pf, nf, nullptr, nf, cx.d_rec[0].as<uint8_t>());
+	cx.h_small.ensure(4096);
+	HIP_OK(hipMemcpyAsync(cx.h_small.p, status, status_bytes, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	IngestStatus s;
+	uint32_t nout = nv;
+	memcpy(&s, cx.h_small.p, sizeof s);
+	if (weld) memcpy(&nout, cx.h_small.as<uint8_t>() + sizeof(IngestStatus), 4);
+	if (s.err & kIngestBadDegree) throw Error(HRY_E_UNSUPPORTED, "polygon degree outside 3..255");
+	if (d_degrees && s.total != n_indices) throw Error(HRY_E_ARG, "sum of degrees differs from the number of indices");
+	if (s.err & kIngestBadIndex) throw Error(HRY_E_ARG, "vertex index out of range");
+	if (nout > nv) throw Error(HRY_E_INTERNAL, "weld: more vertices than rows");
+
+	// ---- welded: the records of the output vertices, gathered from the columns at each one's first row
+	if (weld) {
+		launch_ingest_pack(st, pv, nout, (const uint32_t*)ptr(w_frow), nv, cx.d_rec[1].as<uint8_t>());
+		if (d_remap && nv) HIP_OK(hipMemcpyAsync(d_remap, remap, (size_t)nv * 4, hipMemcpyDeviceToDevice, st));
+	}
+	m->nv = nout; m->nf = nf;
+	m->lists[1].count = nout;
+	if (d_degrees) {
+		for (int d = 0; d < 256; ++d)
+			if ((s.degmask[d >> 5] >> (d & 31)) & 1) { if (d >= (int)m->have_degree.size()) m->have_degree.resize(d + 1, 0); m->have_degree[d] = 1; }
+	} else if (nf) {
+		m->have_degree.assign(4, 0);
+		m->have_degree[3] = 1;
+	}
+
+	// ---- the host copies, then the twins (hubs are matched on the host, from its connectivity)
+	m->face_off.resize((size_t)nf + 1);
+	m->org.resize(ne);
+	for (int k = 0; k < 2; ++k) m->lists[k].data.resize((size_t)m->lists[k].count * m->lists[k].stride());
+	fetch_to_host(cx, m->face_off.data(), cx.d_foff.p, ((size_t)nf + 1) * 4);
+	fetch_to_host(cx, m->org.data(), cx.d_org.p, (size_t)ne * 4);
+	for (int k = 0; k < 2; ++k) fetch_to_host(cx, m->lists[k].data.data(), cx.d_rec[k].p, m->lists[k].data.size());
+	cx.conn_state(*m);
+	m->twins_pending = true;
+	cx.match_twins(*m);
+	cx.make_resident(*m);
+	return m.release();
+}
+
+}   // namespace hry

@@ -1,0 +1,230 @@
+// Meshes from device buffers (driver: ingest.cpp; contract: include/harry_amd.h, hry_mesh_from_device).  Streaming kernels, wave64,
+// one element per lane and consecutive lanes on consecutive output words (coalesced stores):
+//   k_ingest_degrees   a lane per face: degree check, the set of degrees, per wavefront the sum of its 64 degrees, a 64-bit total
+//   k_ingest_foff      a lane per face: face_off[f + 1] = scanned wave sum + the prefix of the degrees inside the wavefront
+//   k_ingest_foff_tri  every face a triangle: face_off[f] = 3f
+//   k_ingest_org       a lane per half-edge: the index, range-checked, through the weld map when welding
+//   k_ingest_pack      a lane per 4-byte word of a list's AoS records: strided columns gathered into the list's layout
+//   k_weld_*           one output vertex per distinct packed record, in first-occurrence order over the input rows
+// The checks of the input raise bits of one status word (vector atomics, once per wavefront); the host reads it back once.  Offsets
+// computed from bad degrees are stored but never used for an address: the host refuses the mesh first.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+namespace hry {
+namespace dev {
+
+constexpr uint32_t kNone = 0xffffffffu;
+
+// exclusive scan of n counts by one block (render.hip)
+__global__ void k_scan_counts(const uint32_t *counts, uint32_t n, uint32_t *out);
+
+// ---------------------------------------------------------------------------------------------------------
+// face offsets from uint8 degrees: per wavefront of 64 faces the sum of its degrees (at most 64 x 255, a u32), scanned by
+// k_scan_counts, then the prefix inside the wavefront.  The 64-bit total is summed separately (per block in LDS, then one atomic
+// per block): the host compares it with n_indices before it trusts any u32 offset, so degrees whose sum passes 2^32 cannot wrap.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ingest_degrees(const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, IngestStatus *st)
+{
+	__shared__ uint32_t mask[8];
+	__shared__ unsigned long long bsum;
+	if (threadIdx.x < 8) mask[threadIdx.x] = 0;
+	if (threadIdx.x == 0) bsum = 0;
+	__syncthreads();
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t d = f < nf ? deg[f] : 0;
+	if (f < nf) atomicOr(&mask[d >> 5], 1u << (d & 31));
+	const uint64_t bad = __ballot(f < nf && d < 3);
+	uint32_t s = d;
+	for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+	if ((threadIdx.x & 63) == 0) {
+		if (bad) atomicOr(&st->err, kIngestBadDegree);
+		if (f < nf) { wave_sums[f >> 6] = s; atomicAdd(&bsum, (unsigned long long)s); }
+	}
+	__syncthreads();
+	if (threadIdx.x < 8 && mask[threadIdx.x]) atomicOr(&st->degmask[threadIdx.x], mask[threadIdx.x]);
+	if (threadIdx.x == 0 && bsum) atomicAdd(&st->total, bsum);
+}
+
+__global__ __launch_bounds__(256) void k_ingest_foff(const uint8_t *deg, uint32_t nf, const uint32_t *wave_start, uint32_t *foff)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+	uint32_t s = f < nf ? deg[f] : 0;
+	for (int o = 1; o < 64; o <<= 1) {   // inclusive prefix inside the wavefront
+		const uint32_t t = __shfl_up(s, o);
+		if (lane >= (uint32_t)o) s += t;
+	}
+	if (f < nf) foff[f + 1] = wave_start[f >> 6] + s;
+	if (f == 0) foff[0] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_ingest_foff_tri(uint32_t nf, uint32_t *foff)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f <= nf) foff[f] = 3u * f;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// indices -> org: u32 or i64 in; an index outside [0, nv) raises kIngestBadIndex and stores 0 (nothing is read at it)
+// ---------------------------------------------------------------------------------------------------------
+template <typename I>
+__global__ __launch_bounds__(256) void k_ingest_org(const I *idx, uint32_t ne, uint32_t nv, const uint32_t *remap, uint32_t *org, IngestStatus *st)
+{
+	const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+	for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < ne; h += step) {
+		const I v = idx[h];
+		const bool ok = v >= 0 && (uint64_t)v < nv;
+		org[h] = ok ? (remap ? remap[(uint32_t)v] : (uint32_t)v) : 0u;
+		const uint64_t bad = __ballot(!ok);
+		if (bad && (threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)bad) - 1) atomicOr(&st->err, kIngestBadIndex);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_ingest_pack: record r of the output is row (rows ? rows[r] : r) of every column, byte k of a record coming from byte byte_of[k]
+// of column comp_of[k].  A block writes 256 records (256 x stride bytes: a multiple of 4, so every block starts on a word), a lane
+// a 4-byte word of them; the word's first record and byte take one 32-bit division.  The partial word at the end of the output is
+// stored byte by byte.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ingest_pack(PackCols p, uint32_t n, const uint32_t *rows, uint32_t nsrc, uint8_t *out)
+{
+	const uint32_t S = p.rec_stride;
+	const uint64_t r0 = (uint64_t)blockIdx.x * 256;
+	if (r0 >= n || S == 0) return;
+	const uint32_t bytes = (uint32_t)min<uint64_t>(256, n - r0) * S;
+	uint8_t *dst = out + r0 * S;
+	for (uint32_t w = threadIdx.x; w * 4 < bytes; w += blockDim.x) {
+		uint32_t rr = w * 4 / S, k = w * 4 - rr * S, word = 0;
+		const uint32_t nb = min(4u, bytes - w * 4);
+		for (uint32_t j = 0; j < nb; ++j) {
+			const uint32_t sr = rows ? rows[r0 + rr] : (uint32_t)(r0 + rr);
+			uint32_t x = 0;
+			if (sr < nsrc) {
+				const uint32_t c = p.comp_of[k];
+				x = p.src[c][(uint64_t)sr * p.stride[c] + p.byte_of[k]];
+			}
+			word |= x << (8 * j);
+			if (++k == S) { k = 0; ++rr; }
+		}
+		if (nb == 4) *(uint32_t*)(dst + w * 4) = word;
+		else for (uint32_t j = 0; j < nb; ++j) dst[w * 4 + j] = (uint8_t)(word >> (8 * j));
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// weld: the key of row r is its packed record (stride bytes at rec + r * stride).  Keys are never stored: a slot of the
+// open-addressing table holds a row, and keys are compared by reading both records.  A slot belongs to the key of the row that
+// claimed it (atomicCAS from EMPTY) for good; atomicMin then leaves the smallest row of that key in it.  So after k_weld_insert every
+// distinct key owns exactly one slot holding its first row -- whatever order the atomics completed in (k_unweld_*, render.hip).
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rec_hash(const uint8_t *a, uint32_t S)
+{
+	uint32_t h = 0x811c9dc5u;   // FNV-1a over the bytes, then murmur3's finaliser
+	for (uint32_t k = 0; k < S; ++k) h = (h ^ a[k]) * 0x01000193u;
+	h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+	return h;
+}
+__device__ __forceinline__ bool same_rec(const uint8_t *a, const uint8_t *b, uint32_t S)
+{
+	for (uint32_t k = 0; k < S; ++k)
+		if (a[k] != b[k]) return false;
+	return true;
+}
+
+__global__ __launch_bounds__(256) void k_weld_insert(WeldView u)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= u.n) return;
+	const uint8_t *a = u.rec + (size_t)r * u.stride;
+	uint32_t s = rec_hash(a, u.stride) & u.mask;
+	for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {   // more slots than rows: an empty one is met
+		uint32_t cur = __hip_atomic_load(&u.table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (cur == kNone) {
+			cur = atomicCAS(&u.table[s], kNone, r);
+			if (cur == kNone) return;
+		}
+		if (cur < u.n && same_rec(a, u.rec + (size_t)cur * u.stride, u.stride)) { atomicMin(&u.table[s], r); return; }
+	}
+}
+
+// per row: the first row of its key; per wavefront of 64 rows: the mask of first rows and their count
+__global__ __launch_bounds__(256) void k_weld_find(WeldView u, uint32_t *first_of, uint64_t *masks, uint32_t *counts)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	bool first = false;
+	if (r < u.n) {
+		const uint8_t *a = u.rec + (size_t)r * u.stride;
+		uint32_t s = rec_hash(a, u.stride) & u.mask, e = r;
+		for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {
+			const uint32_t cur = u.table[s];
+			if (cur == kNone) break;   // (cannot happen: r itself was inserted)
+			if (cur == r || (cur < u.n && same_rec(a, u.rec + (size_t)cur * u.stride, u.stride))) { e = cur; break; }
+		}
+		first_of[r] = e;
+		first = e == r;
+	}
+	const uint64_t b = __ballot(first);
+	if ((threadIdx.x & 63) == 0 && (uint64_t)(r >> 6) < ((uint64_t)u.n + 63) / 64) {
+		masks[r >> 6] = b;
+		counts[r >> 6] = (uint32_t)__popcll(b);
+	}
+}
+
+// remap[r] = output vertex of row r (rank of its first row among the first rows); first_row[id] = the row that defines vertex id
+__global__ __launch_bounds__(256) void k_weld_assign(uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
+                                                     uint32_t *remap, uint32_t *first_row)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= n) return;
+	const uint32_t e = first_of[r];
+	if (e >= n) { remap[r] = 0; return; }
+	const uint32_t id = wave_start[e >> 6] + (uint32_t)__popcll(masks[e >> 6] & ((1ull << (e & 63)) - 1));
+	remap[r] = id;
+	if (e == r && id < n) first_row[id] = r;
+}
+
+// ---- launchers
+static inline unsigned grid_for(uint64_t n, unsigned per) { const uint64_t b = (n + per - 1) / per; return (unsigned)(b < (1u << 20) ? b : (1u << 20)); }
+
+void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out)
+{
+	hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, counts, n, out);
+}
+void launch_ingest_offsets(hipStream_t st, const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, uint32_t *wave_start, uint32_t *foff, IngestStatus *status)
+{
+	if (!deg) {
+		hipLaunchKernelGGL(k_ingest_foff_tri, dim3(((uint64_t)nf + 1 + 255) / 256), dim3(256), 0, st, nf, foff);
+		return;
+	}
+	if (!nf) { hipLaunchKernelGGL(k_ingest_foff_tri, dim3(1), dim3(256), 0, st, 0u, foff); return; }
+	const unsigned nb = (unsigned)(((uint64_t)nf + 255) / 256);
+	hipLaunchKernelGGL(k_ingest_degrees, dim3(nb), dim3(256), 0, st, deg, nf, wave_sums, status);
+	launch_scan_counts(st, wave_sums, (uint32_t)(((uint64_t)nf + 63) / 64), wave_start);
+	hipLaunchKernelGGL(k_ingest_foff, dim3(nb), dim3(256), 0, st, deg, nf, (const uint32_t*)wave_start, foff);
+}
+void launch_ingest_org(hipStream_t st, const void *idx, bool idx64, uint32_t ne, uint32_t nv, const uint32_t *remap, uint32_t *org, IngestStatus *status)
+{
+	if (!ne) return;
+	if (idx64) hipLaunchKernelGGL(k_ingest_org<int64_t>, dim3(grid_for(ne, 256)), dim3(256), 0, st, (const int64_t*)idx, ne, nv, remap, org, status);
+	else hipLaunchKernelGGL(k_ingest_org<uint32_t>, dim3(grid_for(ne, 256)), dim3(256), 0, st, (const uint32_t*)idx, ne, nv, remap, org, status);
+}
+void launch_ingest_pack(hipStream_t st, const PackCols &p, uint32_t n, const uint32_t *rows, uint32_t nsrc, uint8_t *out)
+{
+	if (n && p.rec_stride) hipLaunchKernelGGL(k_ingest_pack, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, p, n, rows, nsrc, out);
+}
+void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start)
+{
+	if (!u.n) return;
+	const unsigned nb = (u.n + 255) / 256;
+	hipLaunchKernelGGL(k_weld_insert, dim3(nb), dim3(256), 0, st, u);
+	hipLaunchKernelGGL(k_weld_find, dim3(nb), dim3(256), 0, st, u, first_of, masks, counts);
+	launch_scan_counts(st, counts, (u.n + 63) / 64, wave_start);
+}
+void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row)
+{
+	if (n) hipLaunchKernelGGL(k_weld_assign, dim3((n + 255) / 256), dim3(256), 0, st, n, first_of, masks, wave_start, remap, first_row);
+}
+
+}   // namespace dev
+}   // namespace hry

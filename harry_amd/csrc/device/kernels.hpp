@@ -154,5 +154,27 @@ void launch_place_segment(hipStream_t st, const RunPlace &r, const uint8_t *vrec
                           const uint32_t *foff, uint32_t *whole_foff);
 void launch_render_gather(hipStream_t st, const uint8_t *rec, int stride, uint32_t count, const uint32_t *idx, uint64_t rows, const RequantPlan &plan, float *out);
 
+// meshes from device buffers (ingest.hip; driver: ingest.cpp).  The checks raise bits of err; total = sum of the degrees (64-bit),
+// degmask = the set of degrees present (bit d)
+constexpr uint32_t kIngestBadDegree = 1, kIngestBadIndex = 2;
+struct IngestStatus { uint32_t err, pad; unsigned long long total; uint32_t degmask[8]; };
+// the columns of one list and where their bytes go in its records: byte k of a record is byte byte_of[k] of column comp_of[k]
+struct PackCols {
+	const uint8_t *src[kMaxComp];
+	uint64_t stride[kMaxComp];
+	uint8_t comp_of[8 * kMaxComp], byte_of[8 * kMaxComp];
+	uint32_t rec_stride;
+};
+struct WeldView { const uint8_t *rec; uint32_t stride, n, mask; uint32_t *table; };   // table: mask + 1 slots, filled with 0xff first
+void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out);   // k_scan_counts: out[n + 1], out[n] = total
+// face_off[nf + 1] into foff; deg == nullptr: every face a triangle.  wave_sums / wave_start: (nf + 63) / 64 (+ 1) words
+void launch_ingest_offsets(hipStream_t st, const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, uint32_t *wave_start, uint32_t *foff, IngestStatus *status);
+void launch_ingest_org(hipStream_t st, const void *idx, bool idx64, uint32_t ne, uint32_t nv, const uint32_t *remap, uint32_t *org, IngestStatus *status);
+// n records of p.rec_stride bytes into out; record r from row rows[r] (rows == nullptr: row r) of columns with nsrc rows
+void launch_ingest_pack(hipStream_t st, const PackCols &p, uint32_t n, const uint32_t *rows, uint32_t nsrc, uint8_t *out);
+// first_of[n], masks / counts[(n + 63) / 64], wave_start[(n + 63) / 64 + 1] (last: the output vertices)
+void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start);
+void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row);
+
 }   // namespace dev
 }   // namespace hry

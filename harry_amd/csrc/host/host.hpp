@@ -22,6 +22,9 @@ Mesh *mesh_from_arrays(uint32_t nv, const uint8_t *vrec, int v_ncomp, const uint
                        uint32_t nf, const uint8_t *degrees, const uint32_t *indices,
                        const uint8_t *frec, int f_ncomp, const uint8_t *f_types, const char *const *f_names);
 void mesh_to_ply(const Mesh &m, bool ascii, ByteSink &out, bool packed = false);
+// scalar properties -> components of L (well-known names first, in canonical order); slot_of[i] = component of property i or -1
+void layout_attr_list(const std::vector<std::string> &names, const std::vector<CompType> &types, const std::vector<bool> &is_list,
+                      AttrList &L, std::vector<int> &slot_of);
 void build_twins(Mesh &m);
 // the readers leave the twin matching pending (Mesh::twins_pending); a context does it on the device when the mesh is first
 // uploaded (device/twins.hip), host-only entry points do it here

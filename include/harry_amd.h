@@ -14,6 +14,7 @@
  *   hry_decode          <- hry::reader::read(std::istream&, mesh::Mesh&)          formats/hry/reader.h:19, reader.cc:179-193
  *   hry_bounds          <- quant::set_bounds(Attrs&)                              structs/quant.h:30-44 (called by ply/reader.cc:428)
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
+ *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -226,6 +227,45 @@ int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *d
  * uploaded_bytes: host-to-device bytes the build needed */
 int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes);
 void hry_render_free(hry_render *r);
+
+/* ---- meshes from device buffers --------------------------------------------------------------------------------------
+ * hry_mesh_from_device is hry_mesh_from_arrays for data that already lives on ctx's device (the other direction of
+ * hry_render_build).  A component is a strided column: row i's value of `type` at (const uint8_t*)data + i * stride, where data is
+ * device memory of ctx's device aligned to the type's size and stride a non-zero multiple of it.  `name` and `type` mean what
+ * v_names / v_types of hry_mesh_from_arrays mean.  d_degrees: nf uint8 (NULL: every face a triangle); d_indices: n_indices entries
+ * of index_type (HRY_UINT or HRY_LONG), faces in order, corners in order; fcols: f_ncomp columns of nf rows (the face list).
+ *   Equal to the host constructor: without HRY_INGEST_WELD the mesh is the one hry_mesh_from_arrays builds from the same values --
+ *     lists, component order, names and types, degrees, half-edge order (org is the flattened index list).  Twins are matched on the
+ *     device by the code hry_mesh_upload uses (hubs on the host, as there), so they equal what an upload computes.
+ *   Residency: on return ctx holds the records, org, twins and face offsets in HBM; the mesh and ctx share one token exactly as after
+ *     hry_mesh_upload (the earlier resident mesh of ctx is displaced), so hry_bounds / hry_requant / hry_encode on ctx upload nothing
+ *     for it.  The host copies (connectivity and records) are filled too: the result is an ordinary PLY-layout mesh.
+ *   Input buffers: read on ctx's stream (hry_ctx_stream) and not kept; the caller has finished writing them before the call.
+ *   Refusals, with the host path's code and text where it has one: an index out of range (a negative HRY_LONG too): HRY_E_ARG,
+ *     "vertex index out of range"; a degree outside 3..255, more than 32 components in a list, more than 2^32 - 1 half-edges:
+ *     HRY_E_UNSUPPORTED; sum(degrees) != n_indices, a pointer that is not device memory of ctx's device, a misaligned column, a
+ *     zero stride, a bad type or index_type: HRY_E_ARG.  *out stays NULL and ctx stays usable.  The checks run on the device into
+ *     one status word (vector atomics) that is read back once; nothing is written out of bounds on the way.
+ *   HRY_INGEST_WELD merges vertices whose records are equal byte for byte: the key of a row is every component as stored (-0.0 and
+ *     +0.0 stay apart, identical NaN bit patterns merge).  Output vertices are numbered in order of first occurrence over input rows
+ *     0 .. nv - 1, deterministically.  Face indices go through the map; faces, face records and corners are kept as they are (an
+ *     unreferenced row stays a vertex, a face that collapses keeps its corners).  d_remap (NULL, or nv u32 of device memory) receives
+ *     the output vertex of every input row; hry_mesh_nv is the welded count.  The result equals hry_mesh_from_arrays of the welded
+ *     arrays.  Welding with v_ncomp == 0 is HRY_E_ARG.
+ * General bindings (OBJ regions, corner lists) are out of scope: the result always has the PLY layout. */
+typedef struct hry_dev_column {
+    const void *data;     /* device memory of ctx's device, aligned to the type's size */
+    uint64_t stride;      /* bytes between rows: a non-zero multiple of the type's size */
+    const char *name;     /* PLY component name ("x", "nx", "red", ...), interpreted as hry_mesh_from_arrays does */
+    int32_t type;         /* HRY_FLOAT .. HRY_CHAR: the stored type */
+} hry_dev_column;
+#define HRY_INGEST_WELD 1
+int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp,
+                         uint32_t nf, const uint8_t *d_degrees, const void *d_indices, int index_type, uint64_t n_indices,
+                         const hry_dev_column *fcols, int f_ncomp, int flags, uint32_t *d_remap, hry_mesh **out);
+/* 1: ctx holds m's records and connectivity in HBM (hry_mesh_from_device or hry_mesh_upload, nothing on ctx since that displaced
+ * them), so hry_bounds / hry_requant / hry_encode on ctx upload nothing for m */
+int hry_mesh_resident(const hry_ctx *ctx, const hry_mesh *m);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
