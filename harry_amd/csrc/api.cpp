@@ -553,17 +553,8 @@ int hry_walk_replay(const hry_mesh *src, const hry_walk *walk, int use_restart_p
 	*mesh = nullptr; *out = nullptr;
 	return guarded([&] {
 		const WalkResult &r = walk->w;
-		// the 21 connectivity planes of the chunked container, built on the host: groups split into little-endian bytes,
-		// operations split by order class
-		std::vector<uint8_t> planes[21];
-		static const int first_plane[G_COUNT] = { 0, 1, 5, 7, 11 };
-		for (int g = 0; g < G_COUNT; ++g)
-			for (int b = 0; b < kGroupBytes[g]; ++b) {
-				std::vector<uint8_t> &pl = planes[first_plane[g] + b];
-				pl.resize(r.grp_val[g].size());
-				for (size_t i = 0; i < pl.size(); ++i) pl[i] = (uint8_t)(r.grp_val[g][i] >> (8 * b));
-			}
-		for (size_t i = 0; i < r.op_sc.size(); ++i) planes[13 + (op_u8(r.op_sc[i]) >> 3)].push_back(op_u8(r.op_sc[i]) & 7);
+		std::vector<uint8_t> planes[kConnPlanes];   // the chunked container's connectivity planes, built on the host
+		walk_conn_planes(r, planes);
 		std::unique_ptr<hry_mesh> m(new hry_mesh());
 		std::unique_ptr<hry_walk> w(new hry_walk());
 		m->m.nv = src->m.nv; m->m.nf = src->m.nf; m->m.declared_ne = src->m.ne(); m->m.have_degree = src->m.have_degree;
@@ -582,8 +573,8 @@ int hry_walk_replay(const hry_mesh *src, const hry_walk *walk, int use_restart_p
 			if (read_snapshot_section(sec.data(), sec.size(), m->m.nv, spacing, snaps) != sec.size() || spacing != r.snapshot_faces) throw Error(HRY_E_INTERNAL, "border snapshots: the section does not read back");
 		}
 		OrderVec order_v;
-		PlaneView views[21];
-		for (int k = 0; k < 21; ++k) views[k] = PlaneView(planes[k]);
+		PlaneView views[kConnPlanes];
+		for (int k = 0; k < kConnPlanes; ++k) views[k] = PlaneView(planes[k]);
 		cut_border_replay(m->m, views, restarts, rcounters, order_v, w->seg_start, w->seg_level, nullptr, with_snaps ? &snaps : nullptr);
 		w->w.order_v.assign(order_v.begin(), order_v.end());
 		w->info[0] = (uint32_t)restarts.size(); w->info[1] = (uint32_t)snaps.size();

@@ -1,9 +1,7 @@
 // Chunked profile (.hry v0.2) pipeline: encode and decode.
 //
-// Container (after the v0.1-compatible header with minor version 2):
-//     u32 chunk_syms, u32 conn_chunk_syms, u32 n_planes, n_planes x u32 n_symbols, n_planes x static prior, restart points,
-//     n_streams x u32 n_bytes, streams back to back
-// Plane order: iop, elem[4], part[2], vertid[4], numtri[2], op class[8], vertex data bytes, face data bytes.
+// Container (after the v0.1-compatible header with minor version 2): its planes and directory are defined once, in host/host.hpp
+// (container_planes, ChunkedDirectory).
 // Every (plane, chunk of chunk_syms symbols) is one stream: fresh adaptive model (the reference's initial counts,
 // models.h:197-218 / model.h:38-55), fresh coder with 32-bit registers (arith::Encoder<uint32_t>), 32-bit flush (arith/coder.h).  Symbols that carry no
 // information are not stored (reg_face / reg_vtx with a single region, attr_type == DATA, numtri with one degree).
@@ -25,40 +23,12 @@
 namespace hry {
 
 using namespace dev;
-typedef std::chrono::steady_clock Clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-#define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "[hry enc] %8.3f ms  %s\n", ms_since(t0), what); } while (0)
-
-void build_init_tables(const Mesh &m, std::vector<uint32_t> &tabs)
-{
-	tabs.assign((size_t)INIT_KINDS * 256, 0);
-	for (int i = 0; i < 256; ++i) tabs[INIT_ONES * 256 + i] = 1;
-	for (int i = 0; i < 9; ++i) tabs[INIT_IOP * 256 + i] = 1;
-	for (size_t d = 3; d < m.have_degree.size(); ++d)
-		if (m.have_degree[d]) { ++tabs[INIT_NT0 * 256 + ((d - 2) & 0xff)]; ++tabs[INIT_NT1 * 256 + ((d - 2) >> 8)]; }
-	for (int i = 0; i < 7; ++i) tabs[INIT_OP * 256 + i] = 1;
-	if (m.general) {   // models.h:201-203,212-217
-		for (int r = 0; r < m.bind.nregs_vtx() && r < 256; ++r) tabs[INIT_REGV * 256 + r] = 1;
-		for (int r = 0; r < m.bind.nregs_face() && r < 256; ++r) tabs[INIT_REGF * 256 + r] = 1;
-	}
-	tabs[INIT_TYPE2 * 256 + 0] = tabs[INIT_TYPE2 * 256 + 1] = 1;
-	tabs[INIT_TYPE3 * 256 + 0] = tabs[INIT_TYPE3 * 256 + 1] = tabs[INIT_TYPE3 * 256 + 2] = 1;
-}
+static const char kMarkPrefix[] = "[hry enc]";
 
 static constexpr int kDefaultChunk = 8192;   // with static priors a fresh table per chunk costs little: short chunks = short serial chains
 static constexpr uint32_t kMaxChunk = 1u << 20;   // totals stay below 2^21: far inside the 32-bit coder's t <= 2^30 (oracle: same clamp)
 
 
-// the plane list of a mesh in container order; device pointers are filled by the caller
-static const int kConnPlanes = 1 + 4 + 2 + 4 + 2 + 8;
-static int plane_init_kind(int conn_index)
-{
-	if (conn_index == 0) return INIT_IOP;
-	if (conn_index == 11) return INIT_NT0;
-	if (conn_index == 12) return INIT_NT1;
-	if (conn_index >= 13) return INIT_OP;
-	return INIT_ONES;
-}
 static uint32_t stream_words(uint32_t n, uint32_t t0)
 {
 	uint32_t tmax = t0 + n, lg = 0;
@@ -514,6 +484,18 @@ struct EncodePipeline : WalkProgress {
 	SideThreads sender;   // run(), from begin() on (last: joined before anything above goes)
 };
 
+// The container behind the header: the directory (header.cpp: write_chunked_directory), then the stream lengths and the streams
+// straight from the device into their places in `out` (everything on cx.stream has happened when it returns)
+static void write_container(Context &cx, const ChunkedDirectory &dir, const std::vector<uint8_t> &restart_sec, uint32_t ns, const uint32_t *d_nbytes, uint64_t total_bytes,
+                            ByteSink &out)
+{
+	const size_t at = write_chunked_directory(dir, out, total_bytes, &restart_sec);
+	if (out.size() - at != 4 * (size_t)ns + total_bytes) throw Error(HRY_E_INTERNAL, "chunked encode: the directory counts other streams than the planes have");
+	uint8_t *o = out.data() + at;
+	if (ns) HIP_OK(hipMemcpyAsync(o, d_nbytes, (size_t)ns * 4, hipMemcpyDeviceToHost, cx.stream));
+	fetch_to_host(cx, o + 4 * (size_t)ns, cx.d_cout.p, total_bytes);   // (returns when everything on the stream has happened)
+}
+
 // ---------------------------------------------------------------------------------------------------------
 void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const InPlaceShard *in_place)
 {
@@ -650,18 +632,13 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	// directory, part one: the restart points of the connectivity replay come from the walk's marks alone -- for a mesh of many
 	// components on a thread of its own from here on (17 ms for the 151 741 components of the configs[3] mesh: beside the stream
 	// kernels until round 5, which the carry kernels' rewrite left shorter than that)
-	std::vector<RestartCounters> rcounters;
-	std::vector<RestartPoint> restarts;
-	std::vector<uint32_t> counter_dir;   // per restart point: n, then n x (vertex, counter)
-	std::vector<uint8_t> snap_dir;       // the border snapshots' section (host/header.cpp: write_snapshot_section), empty without any
+	ChunkedDirectory dir;
+	std::vector<uint8_t> restart_sec;   // the directory's restart points, their counters and the border snapshots (write_restart_section)
 	auto select_restarts = [&] {
 		std::vector<RestartCounters> scounters;
-		restarts = select_restart_points(w.marks, w.named, rcounters, &w.snapshots, &scounters);
-		for (const RestartCounters &cs : rcounters) {
-			counter_dir.push_back((uint32_t)cs.size());
-			for (const auto &c : cs) { counter_dir.push_back(c.first); counter_dir.push_back(c.second); }
-		}
-		if (!w.snapshots.empty()) write_snapshot_section(w.snapshot_faces, w.snapshots, scounters, snap_dir);
+		dir.restarts = select_restart_points(w.marks, w.named, dir.counters, &w.snapshots, &scounters);
+		if (!w.snapshots.empty()) write_snapshot_section(w.snapshot_faces, w.snapshots, scounters, dir.snapshot_section);
+		write_restart_section(dir, restart_sec);
 	};
 	const bool dir_beside = w.marks.size() >= 4096 && host_threads() > 1;
 	SideThreads dir_helper;
@@ -712,28 +689,31 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	uint8_t *d_opraw = d_opplanes + nopb;
 	if (nopb) HIP_OK(hipMemcpyAsync(d_opraw, w.op_sc.data(), nopb, hipMemcpyHostToDevice, cx.stream));
 
-	// ---- plane list in container order
+	// ---- plane list in container order (host.hpp container_planes), with the device pointers of the planes
+	const std::vector<GenPlane> layout = container_planes(m);
 	std::vector<PlaneRef> planes;
+	auto add_plane = [&](const uint8_t *at, uint32_t n) { planes.push_back(PlaneRef{ at, n, layout.at(planes.size()).init }); };
 	{
 		size_t poff = 0;
-		int ci = 0;
 		for (int g = 0; g < G_COUNT; ++g) {
 			uint32_t n = (uint32_t)w.grp_val[g].size();
 			const uint8_t *at = g == G_NUMTRI && nt_piped ? cx.d_nt_planes.as<uint8_t>() : cx.d_connplanes.as<uint8_t>() + poff;   // (the pipeline split the triangle counts into planes of their own)
-			for (int b = 0; b < kGroupBytes[g]; ++b, ++ci) planes.push_back(PlaneRef{ at + (size_t)b * n, n, plane_init_kind(ci) });
+			for (int b = 0; b < kGroupBytes[g]; ++b) add_plane(at + (size_t)b * n, n);
 			poff += (size_t)n * kGroupBytes[g];
 		}
 		size_t o = 0;
-		for (int k = 0; k < 8; ++k, ++ci) { planes.push_back(PlaneRef{ d_opplanes + o, (uint32_t)op_plane_n[k], INIT_OP }); o += op_plane_n[k]; }
-		for (int p = 0; p < ldv.nplanes; ++p) planes.push_back(PlaneRef{ cx.d_vplanes.as<uint8_t>() + (size_t)p * vc, vc, INIT_ONES });
-		for (int p = 0; p < ldf.nplanes; ++p) planes.push_back(PlaneRef{ cx.d_fplanes.as<uint8_t>() + (size_t)p * fc, fc, INIT_ONES });
+		for (int k = 0; k < kOpClasses; ++k) { add_plane(d_opplanes + o, (uint32_t)op_plane_n[k]); o += op_plane_n[k]; }
+		for (int p = 0; p < ldv.nplanes; ++p) add_plane(cx.d_vplanes.as<uint8_t>() + (size_t)p * vc, vc);
+		for (int p = 0; p < ldf.nplanes; ++p) add_plane(cx.d_fplanes.as<uint8_t>() + (size_t)p * fc, fc);
 	}
 	// general bindings: which record every element names is settled on the host, the residuals of the records coded as data are
 	// computed by general.hip; the planes join the list like any other (kernels are enqueued here, behind the uploads above)
 	if (m.general) general_planes_encode(cx, m, w, planes);
+	if (planes.size() != layout.size()) throw Error(HRY_E_INTERNAL, "chunked encode: the planes do not match the container's layout");
 	std::vector<uint32_t> kind_tabs;
 	build_init_tables(m, kind_tabs);
 	const uint32_t CHC = std::min(CH, std::max(CH / 8, 512u));
+	dir.CH = CH; dir.CHC = CHC;
 	const uint32_t npl = (uint32_t)planes.size();
 	// slices of the planes for the histogram pass
 	std::vector<HistSlice> slices;
@@ -779,15 +759,17 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	HRY_MARK(t_all, "planes and their histograms");
 
 	// ---- initial table of every plane: its static prior, or the reference's initial counts for short planes
-	std::vector<uint32_t> inits((size_t)npl * 256);
+	dir.tables.assign((size_t)npl * 256, 0);
+	dir.has_prior.assign(npl, 0);
+	dir.nsym.resize(npl);
 	std::vector<uint32_t> totals(npl, 0);
-	std::vector<uint8_t> prior_dir;
 	for (uint32_t pi = 0; pi < npl; ++pi) {
-		uint32_t *tab = inits.data() + (size_t)pi * 256;
+		uint32_t *tab = dir.tables.data() + (size_t)pi * 256;
 		const bool use = plane_prior_from_hist(hist.data() + (size_t)pi * 256, planes[pi].n, tab);
 		if (!use) memcpy(tab, kind_tabs.data() + (size_t)planes[pi].init * 256, 1024);
 		for (int i = 0; i < 256; ++i) totals[pi] += tab[i];
-		write_prior(prior_dir, use, tab);
+		dir.has_prior[pi] = use ? 1 : 0;
+		dir.nsym[pi] = planes[pi].n;
 	}
 	std::vector<StreamJob> jobs;
 	uint64_t words = 0;
@@ -799,19 +781,17 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		const PlaneRef &pl = planes[pi];
 		nsym_total += pl.n;
 		max_t0 = std::max(max_t0, totals[pi]);
-		for (uint32_t f = 0, step; f < pl.n; f += step) {
-			step = pi < (uint32_t)kConnPlanes ? CHC : attr_chunk_len(f, CH);
-			uint32_t n = std::min(step, pl.n - f);
+		for_plane_streams(pi, pl.n, CH, CHC, [&](uint64_t f, uint32_t n) {
 			if (words >= (1ull << 32) - (1u << 24)) throw Error(HRY_E_UNSUPPORTED, "chunked stream accumulator exceeds 2^32 words");
 			jobs.push_back(StreamJob{ pl.dptr + f, n, pi, totals[pi], (uint32_t)words });
 			words += stream_words(n, totals[pi]);
-		}
+		});
 	}
 	const uint32_t ns = (uint32_t)jobs.size();
 	const uint32_t nw = (uint32_t)words + 2;
 	HRY_MARK(t_all, "  priors and stream jobs (host)");
-	cx.d_init.ensure(std::max<size_t>(inits.size() * 4, 16));
-	if (!inits.empty()) HIP_OK(hipMemcpyAsync(cx.d_init.p, inits.data(), inits.size() * 4, hipMemcpyHostToDevice, cx.stream));
+	cx.d_init.ensure(std::max<size_t>(dir.tables.size() * 4, 16));
+	if (!dir.tables.empty()) HIP_OK(hipMemcpyAsync(cx.d_init.p, dir.tables.data(), dir.tables.size() * 4, hipMemcpyHostToDevice, cx.stream));
 	cx.d_cjobs.ensure(std::max<size_t>((size_t)ns * sizeof(StreamJob), 16));
 	if (ns) HIP_OK(hipMemcpyAsync(cx.d_cjobs.p, jobs.data(), (size_t)ns * sizeof(StreamJob), hipMemcpyHostToDevice, cx.stream));
 	cx.ensure_magic(max_t0 + CH + 16);
@@ -869,7 +849,6 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	// directory: chunk sizes, plane lengths, restart points of the connectivity replay (while the device codes the streams, unless
 	// a thread has been at them since the walk), stream lengths
 	if (dir_beside) dir_helper.rethrow(); else select_restarts();
-	const uint32_t nrs = (uint32_t)restarts.size();
 	HRY_MARK(t_all, "  restart points selected");
 	HIP_OK(hipStreamSynchronize(cx.stream));
 	const uint64_t total_bytes = *total_bytes_p;
@@ -879,26 +858,7 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	HIP_OK(hipEventRecord(cx.ev[5], cx.stream));
 
 	// ---- container
-	static_assert(sizeof(RestartPoint) == kRestartWords * 4, "restart points are written as they lie in memory");
-	const size_t dir_prior = 12 + 4 * planes.size();
-	const size_t dir_restart = dir_prior + prior_dir.size();
-	const size_t dir_counters = dir_restart + 4 + sizeof(RestartPoint) * (size_t)nrs;
-	const size_t dir_snaps = dir_counters + 4 * counter_dir.size();   // (round 6: the border snapshots, announced by the top bit of the restart points' count)
-	const size_t dir_streams = dir_snaps + snap_dir.size();
-	size_t dir = dir_streams + 4 * (size_t)ns;
-	size_t base = out.size();
-	out.resize(base + dir + total_bytes);
-	uint8_t *o = out.data() + base;
-	uint32_t np = (uint32_t)planes.size();
-	memcpy(o, &CH, 4); memcpy(o + 4, &CHC, 4); memcpy(o + 8, &np, 4);
-	for (size_t i = 0; i < planes.size(); ++i) memcpy(o + 12 + 4 * i, &planes[i].n, 4);
-	if (!prior_dir.empty()) memcpy(o + dir_prior, prior_dir.data(), prior_dir.size());
-	{ const uint32_t nrs_word = nrs | (snap_dir.empty() ? 0u : 0x80000000u); memcpy(o + dir_restart, &nrs_word, 4); }
-	if (nrs) memcpy(o + dir_restart + 4, restarts.data(), sizeof(RestartPoint) * (size_t)nrs);
-	if (!counter_dir.empty()) memcpy(o + dir_counters, counter_dir.data(), 4 * counter_dir.size());
-	if (!snap_dir.empty()) memcpy(o + dir_snaps, snap_dir.data(), snap_dir.size());
-	if (ns) HIP_OK(hipMemcpyAsync(o + dir_streams, d_nbytes, (size_t)ns * 4, hipMemcpyDeviceToHost, cx.stream));
-	fetch_to_host(cx, o + dir, cx.d_cout.p, total_bytes);   // (returns when everything on the stream has happened)
+	write_container(cx, dir, restart_sec, ns, d_nbytes, total_bytes, out);
 	HRY_MARK(t_all, "container on the host");
 	if (sharded) { const uint64_t seg_len = out.size() - seg_begin; memcpy(out.data() + seg_len_at, &seg_len, 8); }
 

@@ -26,8 +26,6 @@
 namespace hry {
 
 using namespace dev;
-typedef std::chrono::steady_clock Clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 // ---------------------------------------------------------------------------------------------------------
 Context::Context(int dev) : device(dev)

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <cstdio>
 #include <functional>
 #include <map>
 #include <string>
@@ -17,6 +19,11 @@ inline void hip_check(hipError_t e, const char *what)
 	if (e != hipSuccess) throw Error(HRY_E_NODEVICE, std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
 }
 #define HIP_OK(x) ::hry::hip_check((x), #x)
+
+typedef std::chrono::steady_clock Clock;
+inline double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+// HRY_TRACE's time line: ms since t0, after the prefix the file names (kMarkPrefix: "[hry enc]" for the encoder, "[hry]" for the decoder)
+#define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "%s %8.3f ms  %s\n", kMarkPrefix, ms_since(t0), what); } while (0)
 
 struct DevBuf {
 	void *p = nullptr;
@@ -147,29 +154,8 @@ struct Context {
 	float elapsed(int a, int b);
 };
 
-// ---- planes of the chunked container (chunked.cpp, unchunk.cpp, general.cpp)
-// initial counts of a plane that carries no static prior (the reference's initial model of that context, models.h:197-218)
-enum { INIT_ONES = 0, INIT_IOP = 1, INIT_NT0 = 2, INIT_NT1 = 3, INIT_OP = 4, INIT_REGV = 5, INIT_REGF = 6, INIT_TYPE2 = 7, INIT_TYPE3 = 8, INIT_KINDS = 9 };
-void build_init_tables(const Mesh &m, std::vector<uint32_t> &tabs);   // INIT_KINDS x 256
+// ---- planes of the chunked container (chunked.cpp, unchunk.cpp, general.cpp; their layout: host.hpp)
 struct PlaneRef { const uint8_t *dptr; uint32_t n; int init; };
-// Chunks of an attribute plane grow with their position: 1 Ki symbols each up to symbol 32 Ki, 2 Ki up to 64 Ki, 4 Ki up to 128 Ki
-// ... (length = position / 16 rounded down to a power of two, at least 1 Ki, at most the container's chunk size).  A stream is one
-// serial wavefront, 0.26 us per symbol: the decoder's reconstruction chain walks the vertices in order at 16 ns each and finds
-// every chunk decoded when it gets there, instead of waiting for the first full-size chunk (2.1 ms at 8 Ki symbols).
-// Connectivity planes keep one size (they are needed whole, first).  The oracle restates the same rule.
-inline uint32_t attr_chunk_len(uint64_t pos, uint32_t chunk_syms)
-{
-	uint32_t len = 1024;
-	while (len < chunk_syms && (uint64_t)len * 2 <= pos / 16) len *= 2;
-	return len < chunk_syms ? len : chunk_syms;
-}
-// general bindings: the attribute planes that follow the 21 connectivity planes, in container order (the oracle restates it):
-// the region of every vertex / face (low byte; only with more than one region), then per list a region binds, in list order:
-// the kind of every reference, the creation-order distances (4 planes), at corner lists the per-vertex distances (2 planes),
-// the residual bytes of the records coded as data
-enum { GP_REGV = 0, GP_REGF, GP_TYPE, GP_GHIST, GP_LHIST, GP_DATA };
-struct GenPlane { int what, list, byte, init; };
-std::vector<GenPlane> general_plane_layout(const Mesh &m);
 // encode: collects the references on the host, computes the residuals on the device, returns the planes (device pointers into
 // cx.d_gen) in layout order; order_v / order_f / repaired twins must be resident (d_order_v, d_order_f, d_twin)
 void general_planes_encode(Context &cx, Mesh &m, const WalkResult &w, std::vector<PlaneRef> &planes);

@@ -26,8 +26,6 @@
 namespace hry {
 
 using namespace dev;
-typedef std::chrono::steady_clock Clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 bool reconstruct_vertex_list_fast(Context &cx, Mesh &m, int l, const OrderVec &order_v, const std::vector<uint32_t> &seg_start,
                                   const std::vector<uint32_t> &seg_level, const std::vector<uint8_t> &vplanes, const uint8_t *d_vplanes = nullptr);   // unchunk.cpp
@@ -455,22 +453,6 @@ Mesh *decode_general(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 // ---------------------------------------------------------------------------------------------------------
 // chunked container (.hry v0.2) with general bindings
 // ---------------------------------------------------------------------------------------------------------
-std::vector<GenPlane> general_plane_layout(const Mesh &m)
-{
-	std::vector<GenPlane> p;
-	if (m.bind.nregs_vtx() > 1) p.push_back(GenPlane{ GP_REGV, -1, 0, INIT_REGV });
-	if (m.bind.nregs_face() > 1) p.push_back(GenPlane{ GP_REGF, -1, 0, INIT_REGF });
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		const AttrList &L = m.lists[l];
-		if (L.target == 3) continue;
-		p.push_back(GenPlane{ GP_TYPE, (int)l, 0, L.target == 2 ? INIT_TYPE3 : INIT_TYPE2 });
-		for (int k = 0; k < 4; ++k) p.push_back(GenPlane{ GP_GHIST, (int)l, k, INIT_ONES });
-		if (L.target == 2) for (int k = 0; k < 2; ++k) p.push_back(GenPlane{ GP_LHIST, (int)l, k, INIT_ONES });
-		for (int k = 0; k < L.coded_bytes(); ++k) p.push_back(GenPlane{ GP_DATA, (int)l, k, INIT_ONES });
-	}
-	return p;
-}
-
 // The planes of a mesh with general bindings in the parallel container: which record every element names -- on the device
 // (events.hip; HRY_HOST_EVENTS: the host's loop and an arena of its arrays, as until round 5) -- and the residuals of the records
 // coded as data (general.hip).  Per list: kinds (one byte a reference), four planes of creation-order distances, two of per-vertex

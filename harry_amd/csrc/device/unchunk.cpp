@@ -22,14 +22,8 @@
 namespace hry {
 
 using namespace dev;
-typedef std::chrono::steady_clock Clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 static thread_local Clock::time_point g_t0;
-#define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  %s\n", ms_since(t0), what); } while (0)
-
-static const int kConnPlanes = 21;
-
-static int conn_init_kind(int i) { return i == 0 ? INIT_IOP : i == 11 ? INIT_NT0 : i == 12 ? INIT_NT1 : i >= 13 ? INIT_OP : INIT_ONES; }
+static const char kMarkPrefix[] = "[hry]";
 
 // Work lists of the chain kernel (k_unpredict2: one wavefront per list and attribute component walks the list's components one
 // after the other).  A component is a list of its own -- unless it is tiny: the slivers that non-manifold edges and vertices
@@ -497,7 +491,7 @@ static bool pipelined_decode_applicable(const Mesh &m, const std::vector<Restart
 	if (env_on("HRY_NO_PIPELINE")) return false;
 	int ud = 0;
 	const uint32_t min_nv = (uint32_t)env_uint("HRY_PIPELINE_MIN_VERTICES", 1u << 17);
-	return restarts.empty() && conn[7].empty() && m.uniform_degree(ud) && unpredict3_covers(ldv) && vc == m.nv && m.nv >= min_nv && m.declared_ne != 0;
+	return restarts.empty() && conn[group_first_plane(G_VERT)].empty() && m.uniform_degree(ud) && unpredict3_covers(ldv) && vc == m.nv && m.nv >= min_nv && m.declared_ne != 0;
 }
 
 // attr_upto[g]: the vertex planes are decoded up to this vertex once cx.attr_ev[g] has fired (the last entry covers everything)
@@ -760,19 +754,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	ReplayCursor cur;
 	try {
 		int onlydeg = ud;
-		struct PlanesRd {   // bare cursors: the replay reads a byte or two per operation
-			const uint8_t *cur[21], *end[21]; int fixed_numtri;
-			uint32_t byte(int plane) { if (cur[plane] == end[plane]) throw Error(HRY_E_FORMAT, "corrupt stream (connectivity plane exhausted)"); return *cur[plane]++; }
-			uint32_t iop() { return byte(0); }
-			uint32_t u32(int first) { uint32_t v = byte(first); v |= byte(first + 1) << 8; v |= byte(first + 2) << 16; v |= byte(first + 3) << 24; return v; }
-			int elem() { uint32_t z = u32(1); return (int)((z >> 1) ^ ((z & 1) ? 0xffffffffu : 0u)); }
-			int part() { uint32_t v = byte(5); v |= byte(6) << 8; return (int)v; }
-			uint32_t vertid() { return u32(7); }
-			int numtri() { return fixed_numtri; }
-			uint32_t op(int order) { int k = order - 1; if (k > 7) k = 7; if (k < 0) k = 0; return byte(13 + k); }
-		} rd;
-		for (int k = 0; k < 21; ++k) { rd.cur[k] = conn[k].data(); rd.end[k] = conn[k].data() + conn[k].size(); }
-		rd.fixed_numtri = onlydeg - 2;
+		Planes rd{ conn, { 0 }, onlydeg - 2 };   // (the generic replay: the checked reader, cbm_replay.hpp)
 		const RestartCounters none;
 		std::vector<uint32_t> comp_first;
 		std::vector<std::pair<uint32_t, uint32_t>> refs;
@@ -794,7 +776,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			}
 			spans->start(host_threads() - 1);
 			BorderEnd end0;
-			size_t cur_end0[21];
+			size_t cur_end0[kConnPlanes];
 			const bool eom0 = replay_triangles<true>(*m, conn, seen.data(), order_v.data(), cur, comp_first, refs, &live, nullptr, spans->spans[0].cur1, spans->spans[0].stop_face, true, nullptr, &end0, cur_end0);
 			if (!eom0) live.publish(cur.face, cur.he, cur.next_id, false);   // (what this stretch has finished: the consumer goes on while the others are waited for)
 			HRY_MARK(g_t0, "replay: the first stretch has reached its snapshot");
@@ -857,186 +839,90 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	}
 }
 
-Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::unique_ptr<Mesh> m)
+// ---- the chunked decode's steps (decode_chunked below)
+// The attribute streams are launched in groups by where in their plane they END (32 Ki, 128 Ki symbols, the rest): the early
+// chunks are short (attr_chunk_len) and done within a fraction of a millisecond, and the reconstruction chain -- which walks the
+// vertices in order -- waits only for the groups it has reached.
+static const uint64_t kGroupEnd[Context::kAttrGroups] = { 1u << 15, 1u << 17, ~0ull };
+struct StreamPlan {
+	std::vector<StreamJob> jobs;             // connectivity streams first, then the attribute streams group by group
+	std::vector<uint32_t> nbytes;            // ... their lengths and offsets in the payload, permuted alike
+	std::vector<uint64_t> offs;
+	std::vector<uint64_t> plane_off;         // per plane + end: where its symbols land in cx.d_csyms
+	uint32_t n_conn_streams = 0, conn_lanes_n = 0;
+	uint32_t group_n[Context::kAttrGroups] = { 0, 0, 0 }, group_lanes_n[Context::kAttrGroups] = { 0, 0, 0 };   // lanes_n: streams a lane can decode (first in their launch)
+	uint64_t conn_bytes = 0;                 // the connectivity streams' part of the payload
+	bool split_upload = false;
+};
+
+// the stream jobs built, grouped and permuted, then uploaded with the tables and (the first part of) the payload
+static void upload_streams(Context &cx, const ChunkedDirectory &dir, const uint8_t *payload, StreamPlan &sp)
 {
-	auto t_all = Clock::now();
-	g_t0 = t_all;
-	cx.timing = hry_timing{};
-	const ListDesc ldv = m->general ? ListDesc{} : make_list_desc(m->lists[1]), ldf = m->general ? ListDesc{} : make_list_desc(m->lists[0]);
-	if (m->lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
-	for (const AttrList &L : m->lists)
-		for (int c = 0; c < L.ncomp(); ++c) {
-			if (L.stype(c) == C_DOUBLE) throw Error(HRY_E_UNSUPPORTED, "lossless double components are outside the supported subset");
-			if (m->general && kTypeSize[L.stype(c)] == 8) throw Error(HRY_E_UNSUPPORTED, "8-byte storage types are outside the supported subset");
-		}
-	// ---- directory
-	auto need = [&](size_t off, size_t k) { if (off + k > n) throw Error(HRY_E_FORMAT, "truncated chunked directory"); };
-	size_t off = hdr;
-	need(off, 12);
-	uint32_t CH, CHC, np;
-	memcpy(&CH, p + off, 4); memcpy(&CHC, p + off + 4, 4); memcpy(&np, p + off + 8, 4);
-	off += 12;
-	const std::vector<GenPlane> gen_layout = m->general ? general_plane_layout(*m) : std::vector<GenPlane>();
-	const uint32_t expect_planes = (uint32_t)(kConnPlanes + (m->general ? (int)gen_layout.size() : ldv.nplanes + ldf.nplanes));
-	if (CH == 0 || CHC == 0 || CH > (1u << 20) || CHC > CH || np != expect_planes) throw Error(HRY_E_FORMAT, "chunked directory does not match the header");
-	need(off, 4ull * np);
-	std::vector<uint32_t> nsym(np);
-	memcpy(nsym.data(), p + off, 4ull * np);
-	off += 4ull * np;
-	uint64_t nstreams = 0, total_syms = 0;
-	auto step_of = [&](uint32_t k, uint64_t pos) { return k < (uint32_t)kConnPlanes ? CHC : attr_chunk_len(pos, CH); };
-	for (uint32_t k = 0; k < np; ++k) {
-		if (k < (uint32_t)kConnPlanes) nstreams += (nsym[k] + (uint64_t)CHC - 1) / CHC;
-		else for (uint64_t f = 0; f < nsym[k]; f += step_of(k, f)) ++nstreams;
-		total_syms += nsym[k];
-	}
-	// static prior of every plane (or none: the reference's initial counts)
-	std::vector<uint32_t> prior((size_t)np * 256, 0);
-	std::vector<uint8_t> has_prior(np, 0);
-	for (uint32_t k = 0; k < np; ++k) {
-		bool use = false;
-		off += read_prior(p + off, n - off, use, prior.data() + (size_t)k * 256);
-		has_prior[k] = use ? 1 : 0;
-	}
-	need(off, 4);
-	uint32_t nrs;
-	memcpy(&nrs, p + off, 4);
-	off += 4;
-	const bool has_snapshots = (nrs & 0x80000000u) != 0;   // (round 6: a section of border snapshots follows the restart points' counters)
-	nrs &= 0x7fffffffu;
-	if ((uint64_t)nrs * sizeof(RestartPoint) > n) throw Error(HRY_E_FORMAT, "truncated chunked directory");
-	need(off, sizeof(RestartPoint) * (size_t)nrs);
-	std::vector<RestartPoint> restarts(nrs);
-	if (nrs) memcpy(restarts.data(), p + off, sizeof(RestartPoint) * (size_t)nrs);
-	off += sizeof(RestartPoint) * (size_t)nrs;
-	std::vector<RestartCounters> rcounters(nrs);
-	for (uint32_t k = 0; k < nrs; ++k) {
-		need(off, 4);
-		uint32_t nc;
-		memcpy(&nc, p + off, 4);
-		off += 4;
-		if ((uint64_t)nc * 8 > n) throw Error(HRY_E_FORMAT, "truncated chunked directory");
-		need(off, 8ull * nc);
-		rcounters[k].resize(nc);
-		for (uint32_t j = 0; j < nc; ++j) { uint32_t v[2]; memcpy(v, p + off + 8ull * j, 8); rcounters[k][j] = { v[0], v[1] }; }
-		off += 8ull * nc;
-	}
-	std::vector<SnapshotPoint> snaps;   // restart points inside components (host.hpp BorderSnapshot)
-	if (has_snapshots) { uint32_t spacing = 0; off += read_snapshot_section(p + off, n - off, m->nv, spacing, snaps); }
-	need(off, 4 * nstreams);
-	std::vector<uint32_t> nbytes((size_t)nstreams);
-	if (nstreams) memcpy(nbytes.data(), p + off, 4 * (size_t)nstreams);
-	off += 4 * (size_t)nstreams;
-	std::vector<uint64_t> offs((size_t)nstreams + 1, 0);
-	for (size_t i = 0; i < nstreams; ++i) offs[i + 1] = offs[i] + nbytes[i];
-	if (off + offs[nstreams] > n) throw Error(HRY_E_FORMAT, "truncated chunked payload");
-	const uint8_t *payload = p + off;
-	const uint64_t payload_bytes = offs[nstreams];
-	// plausibility of the plane sizes against the header: at most one vertex / face record per element
-	const uint32_t vc = !m->general && ldv.nplanes ? nsym[kConnPlanes] : 0;
-	if (!m->general) {
-		for (int q = 0; q < ldv.nplanes; ++q) if (nsym[kConnPlanes + q] != vc) throw Error(HRY_E_FORMAT, "vertex planes of different length");
-		for (int q = 0; q < ldf.nplanes; ++q) if (nsym[kConnPlanes + ldv.nplanes + q] != m->nf) throw Error(HRY_E_FORMAT, "face planes of wrong length");
-		if (vc > m->nv) throw Error(HRY_E_FORMAT, "more coded vertices than vertices");
-	} else {
-		// at most one reference per vertex / face / corner slot, at most one record per reference
-		const uint64_t most = (uint64_t)m->nv * m->bind.nb_vtx + (uint64_t)m->nf * m->bind.nb_face + (uint64_t)m->declared_ne * m->bind.nb_corner + 16;
-		for (size_t q = 0; q < gen_layout.size(); ++q) {
-			if (nsym[kConnPlanes + q] > most) throw Error(HRY_E_FORMAT, "implausible plane length");
-			if (gen_layout[q].what == GP_DATA && nsym[kConnPlanes + q] > m->lists[gen_layout[q].list].count) throw Error(HRY_E_FORMAT, "more records than the header announces");
-		}
-	}
-	if (total_syms > (1ull << 33)) throw Error(HRY_E_FORMAT, "implausible symbol count");
-
-	// ---- model tables: one per plane (its prior, or the reference's initial counts of its kind)
-	std::vector<uint32_t> kind_tabs;
-	build_init_tables(*m, kind_tabs);
-	std::vector<uint32_t> tabs((size_t)np * 256, 0);
-	std::vector<uint32_t> totals(np, 0);
-	uint32_t max_t0 = 256;
-	for (uint32_t k = 0; k < np; ++k) {
-		const int kind = k < (uint32_t)kConnPlanes ? conn_init_kind((int)k) : m->general ? gen_layout[k - kConnPlanes].init : INIT_ONES;
-		memcpy(tabs.data() + (size_t)k * 256, has_prior[k] ? prior.data() + (size_t)k * 256 : kind_tabs.data() + (size_t)kind * 256, 1024);
-		uint64_t t = 0;
-		for (int i = 0; i < 256; ++i) t += tabs[(size_t)k * 256 + i];
-		if (t == 0 && nsym[k]) throw Error(HRY_E_FORMAT, "corrupt chunked directory (empty model)");
-		if (t > (1u << 24)) throw Error(HRY_E_FORMAT, "corrupt chunked directory (prior total)");
-		totals[k] = (uint32_t)t;
-		max_t0 = std::max(max_t0, totals[k]);
-	}
-
-	// ---- device: entropy decode of every stream
-	auto t_h2d = Clock::now();
-	cx.d_csyms.ensure(std::max<size_t>(total_syms + 64, 16));
+	const uint32_t np = (uint32_t)dir.nsym.size();
+	const size_t nstreams = dir.stream_bytes.size();
+	const uint64_t payload_bytes = dir.stream_off[nstreams];
+	cx.d_csyms.ensure(std::max<size_t>(dir.total_syms + 64, 16));
 	cx.d_cout.ensure(std::max<size_t>(payload_bytes + 16, 16));
-	cx.d_cjobs.ensure(std::max<size_t>((size_t)nstreams * sizeof(StreamJob), 16));
-	cx.d_coffs.ensure(((size_t)nstreams + 1) * 8);
-	cx.d_csizes.ensure(std::max<size_t>((size_t)nstreams * 4, 16));
-	cx.d_init.ensure(tabs.size() * 4);
+	cx.d_cjobs.ensure(std::max<size_t>(nstreams * sizeof(StreamJob), 16));
+	cx.d_coffs.ensure((nstreams + 1) * 8);
+	cx.d_csizes.ensure(std::max<size_t>(nstreams * 4, 16));
+	cx.d_init.ensure(dir.tables.size() * 4);
 	std::vector<StreamJob> jobs;
-	jobs.reserve((size_t)nstreams);
-	std::vector<uint64_t> plane_off(np + 1, 0);
+	jobs.reserve(nstreams);
+	sp.plane_off.assign(np + 1, 0);
 	for (uint32_t k = 0; k < np; ++k) {
-		for (uint64_t f = 0, step; f < nsym[k]; f += step) {
-			step = step_of(k, f);
-			jobs.push_back(StreamJob{ cx.d_csyms.as<uint8_t>() + plane_off[k] + f, (uint32_t)std::min<uint64_t>(step, nsym[k] - f), k, totals[k], 0 });
-		}
-		plane_off[k + 1] = plane_off[k] + nsym[k];
+		for_plane_streams(k, dir.nsym[k], dir.CH, dir.CHC, [&](uint64_t f, uint32_t n) {
+			jobs.push_back(StreamJob{ cx.d_csyms.as<uint8_t>() + sp.plane_off[k] + f, n, k, dir.totals[k], 0 });
+		});
+		sp.plane_off[k + 1] = sp.plane_off[k] + dir.nsym[k];
 	}
-	// The attribute streams are launched in groups by where in their plane they END (32 Ki, 128 Ki symbols, the rest): the
-	// early chunks are short (attr_chunk_len) and done within a fraction of a millisecond, and the reconstruction chain -- which
-	// walks the vertices in order -- waits only for the groups it has reached.  Jobs, offsets and sizes are permuted alike.
-	uint32_t n_conn_streams = 0;
-	for (int k = 0; k < kConnPlanes; ++k) n_conn_streams += (uint32_t)((nsym[k] + (uint64_t)CHC - 1) / CHC);
-	const uint64_t kGroupEnd[Context::kAttrGroups] = { 1u << 15, 1u << 17, ~0ull };
+	for (int k = 0; k < kConnPlanes; ++k) sp.n_conn_streams += (uint32_t)plane_stream_count(k, dir.nsym[k], dir.CH, dir.CHC);
 	// A large payload goes up in two parts: the connectivity streams (the container's first streams) in front of their kernel, the
 	// attribute streams -- nine tenths of it -- while that kernel runs (the copy is from the caller's pageable buffer and keeps this
 	// thread, which has nothing else to do until the connectivity planes are back): 289 MB of the 100 M-triangle mesh were 7.4 ms
 	// in front of everything.  HRY_SPLIT_UPLOAD_MIN: from how many bytes (32 MB).
-	const uint64_t conn_bytes = offs[std::min<size_t>(n_conn_streams, nstreams)];
+	sp.conn_bytes = dir.stream_off[std::min<size_t>(sp.n_conn_streams, nstreams)];
 	static const uint64_t split_min = env_uint("HRY_SPLIT_UPLOAD_MIN", (uint64_t)32 << 20);   // (tests: 1)
-	const bool split_upload = payload_bytes >= split_min && conn_bytes < payload_bytes;
-	uint32_t group_n[Context::kAttrGroups] = { 0, 0, 0 };
-	// ... and inside a launch the streams a lane can decode (k_chunk_decode_lanes: t0 > 128) come first; lanes_n: how many
-	uint32_t conn_lanes_n = 0, group_lanes_n[Context::kAttrGroups] = { 0, 0, 0 };
+	sp.split_upload = payload_bytes >= split_min && sp.conn_bytes < payload_bytes;
+	// ... and inside a launch the streams a lane can decode (k_chunk_decode_lanes: t0 > 128) come first
 	{
 		std::vector<uint32_t> perm(jobs.size());
 		std::vector<uint8_t> grp(jobs.size(), 0);   // 2 * group + (not for a lane)
 		for (size_t j = 0; j < jobs.size(); ++j) {
 			perm[j] = (uint32_t)j;
 			const uint8_t slow = jobs[j].t0 > 128u ? 0 : 1;
-			if (j < n_conn_streams) { grp[j] = slow; conn_lanes_n += !slow; continue; }
-			const uint64_t end = (uint64_t)(jobs[j].sym - (cx.d_csyms.as<uint8_t>() + plane_off[jobs[j].init])) + jobs[j].n;   // (init holds the plane index)
+			if (j < sp.n_conn_streams) { grp[j] = slow; sp.conn_lanes_n += !slow; continue; }
+			const uint64_t end = (uint64_t)(jobs[j].sym - (cx.d_csyms.as<uint8_t>() + sp.plane_off[jobs[j].init])) + jobs[j].n;   // (init holds the plane index)
 			int g = 0;
 			while (end > kGroupEnd[g]) ++g;
 			grp[j] = (uint8_t)(2 * g + slow);
-			++group_n[g];
-			group_lanes_n[g] += !slow;
+			++sp.group_n[g];
+			sp.group_lanes_n[g] += !slow;
 		}
-		std::stable_sort(perm.begin(), perm.begin() + n_conn_streams, [&](uint32_t a, uint32_t b) { return grp[a] < grp[b]; });
-		std::stable_sort(perm.begin() + n_conn_streams, perm.end(), [&](uint32_t a, uint32_t b) { return grp[a] < grp[b]; });
-		std::vector<StreamJob> pj(jobs.size());
-		std::vector<uint32_t> pn(nbytes.size());
-		std::vector<uint64_t> po(offs.size());
-		for (size_t j = 0; j < jobs.size(); ++j) { pj[j] = jobs[perm[j]]; pn[j] = nbytes[perm[j]]; po[j] = offs[perm[j]]; }
-		po[jobs.size()] = offs[jobs.size()];
-		jobs.swap(pj); nbytes.swap(pn); offs.swap(po);
+		std::stable_sort(perm.begin(), perm.begin() + sp.n_conn_streams, [&](uint32_t a, uint32_t b) { return grp[a] < grp[b]; });
+		std::stable_sort(perm.begin() + sp.n_conn_streams, perm.end(), [&](uint32_t a, uint32_t b) { return grp[a] < grp[b]; });
+		sp.jobs.resize(jobs.size()); sp.nbytes.resize(nstreams); sp.offs.resize(nstreams + 1);
+		for (size_t j = 0; j < jobs.size(); ++j) { sp.jobs[j] = jobs[perm[j]]; sp.nbytes[j] = dir.stream_bytes[perm[j]]; sp.offs[j] = dir.stream_off[perm[j]]; }
+		sp.offs[jobs.size()] = dir.stream_off[jobs.size()];
 	}
-	HIP_OK(hipMemcpyAsync(cx.d_init.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice, cx.stream));
-	if (payload_bytes) HIP_OK(hipMemcpyAsync(cx.d_cout.p, payload, split_upload ? conn_bytes : payload_bytes, hipMemcpyHostToDevice, cx.stream));
+	HIP_OK(hipMemcpyAsync(cx.d_init.p, dir.tables.data(), dir.tables.size() * 4, hipMemcpyHostToDevice, cx.stream));
+	if (payload_bytes) HIP_OK(hipMemcpyAsync(cx.d_cout.p, payload, sp.split_upload ? sp.conn_bytes : payload_bytes, hipMemcpyHostToDevice, cx.stream));
 	if (nstreams) {
-		HIP_OK(hipMemcpyAsync(cx.d_cjobs.p, jobs.data(), jobs.size() * sizeof(StreamJob), hipMemcpyHostToDevice, cx.stream));
-		HIP_OK(hipMemcpyAsync(cx.d_csizes.p, nbytes.data(), nbytes.size() * 4, hipMemcpyHostToDevice, cx.stream));
+		HIP_OK(hipMemcpyAsync(cx.d_cjobs.p, sp.jobs.data(), sp.jobs.size() * sizeof(StreamJob), hipMemcpyHostToDevice, cx.stream));
+		HIP_OK(hipMemcpyAsync(cx.d_csizes.p, sp.nbytes.data(), sp.nbytes.size() * 4, hipMemcpyHostToDevice, cx.stream));
 	}
-	HIP_OK(hipMemcpyAsync(cx.d_coffs.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, cx.stream));
-	cx.ensure_magic(max_t0 + std::max(CH, CHC) + 16);
+	HIP_OK(hipMemcpyAsync(cx.d_coffs.p, sp.offs.data(), sp.offs.size() * 8, hipMemcpyHostToDevice, cx.stream));
+	cx.ensure_magic(dir.max_total + std::max(dir.CH, dir.CHC) + 16);
 	HIP_OK(hipStreamSynchronize(cx.stream));
-	cx.timing.h2d_ms = ms_since(t_h2d);
-	HRY_MARK(g_t0, "payload on the device");
-	// The connectivity streams go first: their planes return to the host for the replay, which then runs while the
-	// attribute streams (the bulk of the payload) are still being decoded on the device.
-	// ... and the attribute streams start at the same time on a stream of their own (every stream is one wavefront: the two
-	// launches share the device without noticing each other); everything later on the main stream waits for them.
+}
+
+// The connectivity streams go first: their planes return to the host (into conn) for the replay, which then runs while the
+// attribute streams (the bulk of the payload) are still being decoded on the device.
+// ... and the attribute streams start at the same time on a stream of their own (every stream is one wavefront: the two
+// launches share the device without noticing each other); everything later on the main stream waits for them.
+static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, const StreamPlan &sp, const uint8_t *payload, PlaneView *conn)
+{
+	const uint64_t payload_bytes = dir.stream_off[dir.stream_bytes.size()];
 	if (!cx.stream3) {
 		HIP_OK(hipStreamCreateWithFlags(&cx.stream3, hipStreamNonBlocking));
 		for (auto &e : cx.ev_x) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1053,6 +939,7 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	// many short streams (the 53 000 streams of 16 Ki symbols of configs[3] under the default chunk policy, chunked.cpp) go to the
 	// lanes, a few thousand long ones (a container written with 128 Ki-symbol chunks: 5 200 attribute streams) stay with a wave each.
 	static const uint64_t lanes_mode = env_uint("HRY_DECODE_LANES", 2);
+	const std::vector<StreamJob> &jobs = sp.jobs;
 	auto decode_streams = [&](hipStream_t st, uint32_t first, uint32_t n, uint32_t n_for_lanes) {
 		bool lanes = lanes_mode == 1;
 		// (16-bit counts where no stream's total passes 65535: 32 KB a lane-wave, five of them a compute unit; HRY_DECODE_COUNTS32: never)
@@ -1074,19 +961,18 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 		if (n > nl) launch_chunk_decode(st, cx.d_cjobs.as<StreamJob>() + first + nl, n - nl, cx.d_init.as<uint32_t>(), cx.d_magic.as<MagicEnt>(), cx.d_cout.as<uint8_t>(),
 		                                cx.d_coffs.as<uint64_t>() + first + nl, cx.d_csizes.as<uint32_t>() + first + nl);
 	};
-	decode_streams(cx.stream, 0, n_conn_streams, conn_lanes_n);
+	decode_streams(cx.stream, 0, sp.n_conn_streams, sp.conn_lanes_n);
 	HIP_OK(hipEventRecord(cx.ev[2], cx.stream));
 	// the connectivity planes come down into the context's pinned memory (one block, reused: fresh pageable vectors cost a zero
 	// fill, a page fault per 4 KiB and a staged copy -- 7 ms of a 51 ms decode on the configs[3] share)
-	PlaneView conn[kConnPlanes];
 	{
 		size_t at[kConnPlanes + 1] = { 0 };
-		for (int k = 0; k < kConnPlanes; ++k) at[k + 1] = at[k] + ((nsym[k] + 63) & ~(size_t)63);
+		for (int k = 0; k < kConnPlanes; ++k) at[k + 1] = at[k] + ((dir.nsym[k] + 63) & ~(size_t)63);
 		cx.h_conn.ensure(std::max<size_t>(at[kConnPlanes], 64));
 		for (int k = 0; k < kConnPlanes; ++k) {
 			uint8_t *dst = cx.h_conn.as<uint8_t>() + at[k];
-			conn[k] = PlaneView(dst, nsym[k]);
-			if (nsym[k]) HIP_OK(hipMemcpyAsync(dst, cx.d_csyms.as<uint8_t>() + plane_off[k], nsym[k], hipMemcpyDeviceToHost, cx.stream));
+			conn[k] = PlaneView(dst, dir.nsym[k]);
+			if (dir.nsym[k]) HIP_OK(hipMemcpyAsync(dst, cx.d_csyms.as<uint8_t>() + sp.plane_off[k], dir.nsym[k], hipMemcpyDeviceToHost, cx.stream));
 		}
 	}
 	HIP_OK(hipEventRecord(cx.ev_x[1], cx.stream));        // the connectivity planes are on their way to the host
@@ -1098,9 +984,9 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	// ... and for the planes' copy to the host: beside 10^5 attribute waves the copy of the configs[3] mesh's 110 MB of connectivity
 	// planes took 20 ms instead of 5, in front of the replay
 	const hipEvent_t attr_after = cx.ev_x[1];
-	if (split_upload) {   // the rest of the payload, beside the connectivity streams' kernel (on the uploads' stream)
+	if (sp.split_upload) {   // the rest of the payload, beside the connectivity streams' kernel (on the uploads' stream)
 		cx.ensure_second_stream();
-		HIP_OK(hipMemcpyAsync(cx.d_cout.as<uint8_t>() + conn_bytes, payload + conn_bytes, payload_bytes - conn_bytes, hipMemcpyHostToDevice, cx.stream2));
+		HIP_OK(hipMemcpyAsync(cx.d_cout.as<uint8_t>() + sp.conn_bytes, payload + sp.conn_bytes, payload_bytes - sp.conn_bytes, hipMemcpyHostToDevice, cx.stream2));
 		HIP_OK(hipEventRecord(cx.ev_payload, cx.stream2));
 		for (int g = 0; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamWaitEvent(cx.attr_stream[g], cx.ev_payload, 0));
 		HRY_MARK(g_t0, "attribute streams on the device");
@@ -1108,13 +994,13 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	HIP_OK(hipStreamWaitEvent(cx.stream3, attr_after, 0));
 	HIP_OK(hipEventRecord(cx.ev[5], cx.stream3));
 	{
-		uint32_t first = n_conn_streams;
+		uint32_t first = sp.n_conn_streams;
 		for (int g = 0; g < Context::kAttrGroups; ++g) {
 			hipStream_t st = cx.attr_stream[g];
 			if (g) HIP_OK(hipStreamWaitEvent(st, attr_after, 0));
-			decode_streams(st, first, group_n[g], group_lanes_n[g]);
+			decode_streams(st, first, sp.group_n[g], sp.group_lanes_n[g]);
 			HIP_OK(hipEventRecord(cx.attr_ev[g], st));
-			first += group_n[g];
+			first += sp.group_n[g];
 		}
 		// everything joins on stream3: "all attribute planes decoded"
 		for (int g = 1; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamWaitEvent(cx.stream3, cx.attr_ev[g], 0));
@@ -1123,60 +1009,95 @@ Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::u
 	HIP_OK(hipEventRecord(cx.ev_x[0], cx.stream3));
 	if (trace_on()) { HIP_OK(hipEventSynchronize(cx.ev[2])); HRY_MARK(g_t0, "connectivity streams decoded"); }
 	HIP_OK(hipStreamSynchronize(cx.stream));
-	const bool take_pipeline = !m->general && pipelined_decode_applicable(*m, restarts, conn, ldv, vc);
+}
+
+// the cut-border machine replayed on the host, then the attributes reconstructed: general bindings, the pipelined decode, or the
+// replay (finished spans uploaded beside it where that pays) followed by the reconstruction.  Returns whether it was pipelined
+static bool replay_and_reconstruct(Context &cx, Mesh &m, const ChunkedDirectory &dir, const std::vector<uint64_t> &plane_off, const PlaneView *conn,
+                                   const ListDesc &ldv, const ListDesc &ldf)
+{
+	const uint32_t vc = !m.general && ldv.nplanes ? dir.nsym[kConnPlanes] : 0;   // coded vertices
+	const uint8_t *d_vplanes = cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes], *d_fplanes = cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes + ldv.nplanes];
+	const bool take_pipeline = !m.general && pipelined_decode_applicable(m, dir.restarts, conn, ldv, vc);
 	if (!take_pipeline) HIP_OK(hipStreamWaitEvent(cx.stream, cx.ev_x[0], 0));   // attribute planes before anything that reads them (the pipelined decode waits group by group)
 
 	HRY_MARK(g_t0, "connectivity planes on the host");
-	// ---- replay the cut-border machine on the host
 	auto t_walk = Clock::now();
 	OrderVec order_v;
 	std::vector<uint32_t> seg_start, seg_level;
-	bool pipelined = false;
-	if (m->general) {
-		cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, nullptr, &snaps);
+	if (m.general) {
+		cut_border_replay(m, conn, dir.restarts, dir.counters, order_v, seg_start, seg_level, nullptr, &dir.snapshots);
 		cx.timing.host_walk_ms = ms_since(t_walk);
 		HRY_MARK(g_t0, "replay done");
-		general_planes_decode(cx, *m, order_v, seg_start, seg_level, cx.d_csyms.as<uint8_t>(), plane_off, nsym, (uint32_t)kConnPlanes);
-	} else if (take_pipeline) {
-		pipelined = true;
+		general_planes_decode(cx, m, order_v, seg_start, seg_level, cx.d_csyms.as<uint8_t>(), plane_off, dir.nsym, (uint32_t)kConnPlanes);
+		return false;
+	}
+	if (take_pipeline) {
 		uint32_t attr_upto[Context::kAttrGroups];
 		for (int g = 0; g < Context::kAttrGroups; ++g) attr_upto[g] = (uint32_t)std::min<uint64_t>(kGroupEnd[g], 0xffffffffull);
-		decode_pipelined(cx, *m, conn, cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes], cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes + ldv.nplanes], ldv, ldf, order_v, attr_upto, snaps);
+		decode_pipelined(cx, m, conn, d_vplanes, d_fplanes, ldv, ldf, order_v, attr_upto, dir.snapshots);
 		cx.timing.host_walk_ms = cx.timing.host_walk_ms - std::chrono::duration<double, std::milli>(t_walk - g_t0).count();
-	} else {
-		bool conn_resident = false;
-		std::unique_ptr<ChainBatches> batches;
-		if (!restarts.empty() && rcounters.size() == restarts.size() && m->nf >= (1u << 20) && !env_on("HRY_NO_SPAN_UPLOAD")) {
-			// float / 32-bit vertex components: their chains start beside the replay, batch by batch (ChainBatches)
-			// ... where that pays: a batch is a launch of its own on the main stream, and a launch takes as long as its longest
-			// chain (one wavefront, one component: 7 - 14 ms for the 49 000 vertices of a configs[3] component), so three batches of a
-			// mesh whose chains all fit on the device at once (the 12.6 M-triangle share: 384 chains) took 36 ms where one launch takes 15;
-			// the 100 M-triangle mesh's 3 072 chains need two rounds anyway and finish 25 ms earlier in batches.
-			// HRY_CHAIN_BATCH_MIN_VERTICES: the threshold (tests run small meshes in batches).
-			const uint32_t batch_min = (uint32_t)env_uint("HRY_CHAIN_BATCH_MIN_VERTICES", 20000000u);
-			const bool in_batches = ldv.nplanes && unpredict2_applicable(ldv) && !unpredict3_wanted(ldv) && vc == m->nv && vc >= batch_min;
-			if (in_batches) batches.reset(new ChainBatches(cx, ldv, cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes], vc, nsym[0]));
-			SpanUploader up(cx, *m, order_v, batches.get(), cx.ev_x[0]);
-			cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, &up, &snaps);
-			conn_resident = up.finish();
-			up.workers.rethrow();
-			if (batches && conn_resident) { up.finish_edge_faces(cx.stream); batches->conn_adopted = true; }
-		} else cut_border_replay(*m, conn, restarts, rcounters, order_v, seg_start, seg_level, nullptr, &snaps);
-		cx.timing.host_walk_ms = ms_since(t_walk);
-		HRY_MARK(g_t0, "replay done");
-		if (order_v.size() != vc && ldv.nplanes) throw Error(HRY_E_FORMAT, "vertex plane length does not match the connectivity");
-		reconstruct_attributes(cx, *m, order_v, seg_start, seg_level, cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes],
-		                       cx.d_csyms.as<uint8_t>() + plane_off[kConnPlanes + ldv.nplanes], ldv, ldf, conn_resident, nullptr, batches.get());
+		return true;
 	}
+	bool conn_resident = false;
+	std::unique_ptr<ChainBatches> batches;
+	if (!dir.restarts.empty() && dir.counters.size() == dir.restarts.size() && m.nf >= (1u << 20) && !env_on("HRY_NO_SPAN_UPLOAD")) {
+		// float / 32-bit vertex components: their chains start beside the replay, batch by batch (ChainBatches)
+		// ... where that pays: a batch is a launch of its own on the main stream, and a launch takes as long as its longest
+		// chain (one wavefront, one component: 7 - 14 ms for the 49 000 vertices of a configs[3] component), so three batches of a
+		// mesh whose chains all fit on the device at once (the 12.6 M-triangle share: 384 chains) took 36 ms where one launch takes 15;
+		// the 100 M-triangle mesh's 3 072 chains need two rounds anyway and finish 25 ms earlier in batches.
+		// HRY_CHAIN_BATCH_MIN_VERTICES: the threshold (tests run small meshes in batches).
+		const uint32_t batch_min = (uint32_t)env_uint("HRY_CHAIN_BATCH_MIN_VERTICES", 20000000u);
+		const bool in_batches = ldv.nplanes && unpredict2_applicable(ldv) && !unpredict3_wanted(ldv) && vc == m.nv && vc >= batch_min;
+		if (in_batches) batches.reset(new ChainBatches(cx, ldv, d_vplanes, vc, dir.nsym[0]));
+		SpanUploader up(cx, m, order_v, batches.get(), cx.ev_x[0]);
+		cut_border_replay(m, conn, dir.restarts, dir.counters, order_v, seg_start, seg_level, &up, &dir.snapshots);
+		conn_resident = up.finish();
+		up.workers.rethrow();
+		if (batches && conn_resident) { up.finish_edge_faces(cx.stream); batches->conn_adopted = true; }
+	} else cut_border_replay(m, conn, dir.restarts, dir.counters, order_v, seg_start, seg_level, nullptr, &dir.snapshots);
+	cx.timing.host_walk_ms = ms_since(t_walk);
+	HRY_MARK(g_t0, "replay done");
+	if (order_v.size() != vc && ldv.nplanes) throw Error(HRY_E_FORMAT, "vertex plane length does not match the connectivity");
+	reconstruct_attributes(cx, m, order_v, seg_start, seg_level, d_vplanes, d_fplanes, ldv, ldf, conn_resident, nullptr, batches.get());
+	return false;
+}
+
+Mesh *decode_chunked(Context &cx, const uint8_t *p, size_t n, size_t hdr, std::unique_ptr<Mesh> m)
+{
+	auto t_all = Clock::now();
+	g_t0 = t_all;
+	cx.timing = hry_timing{};
+	const ListDesc ldv = m->general ? ListDesc{} : make_list_desc(m->lists[1]), ldf = m->general ? ListDesc{} : make_list_desc(m->lists[0]);
+	if (m->lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
+	for (const AttrList &L : m->lists)
+		for (int c = 0; c < L.ncomp(); ++c) {
+			if (L.stype(c) == C_DOUBLE) throw Error(HRY_E_UNSUPPORTED, "lossless double components are outside the supported subset");
+			if (m->general && kTypeSize[L.stype(c)] == 8) throw Error(HRY_E_UNSUPPORTED, "8-byte storage types are outside the supported subset");
+		}
+	ChunkedDirectory dir;   // (validated whole before anything is allocated on the device)
+	read_chunked_directory(p, n, hdr, *m, dir);
+	const uint8_t *payload = p + dir.payload_at;
+
+	auto t_h2d = Clock::now();
+	StreamPlan sp;
+	upload_streams(cx, dir, payload, sp);
+	cx.timing.h2d_ms = ms_since(t_h2d);
+	HRY_MARK(g_t0, "payload on the device");
+	PlaneView conn[kConnPlanes];
+	decode_streams_conn_first(cx, dir, sp, payload, conn);
+	const bool pipelined = replay_and_reconstruct(cx, *m, dir, sp.plane_off, conn, ldv, ldf);
+
 	if (cx.keep_stages) {
-		cx.stage_put("dec_syms", cx.d_csyms.p, total_syms);
-		cx.stage_put_host("dec_nsym", nsym.data(), nsym.size() * 4);
+		cx.stage_put("dec_syms", cx.d_csyms.p, dir.total_syms);
+		cx.stage_put_host("dec_nsym", dir.nsym.data(), dir.nsym.size() * 4);
 	}
 	cx.timing.k_entropy_ms = cx.elapsed(1, 2) + cx.elapsed(5, 6);
 	if (!pipelined) cx.timing.k_predict_ms = cx.elapsed(3, 4);
 	cx.timing.device_ms = cx.timing.k_entropy_ms + cx.timing.k_predict_ms;
-	cx.timing.n_symbols = total_syms;
-	cx.timing.payload_bytes = payload_bytes;
+	cx.timing.n_symbols = dir.total_syms;
+	cx.timing.payload_bytes = dir.stream_off.back();
 	cx.timing.total_ms = ms_since(t_all);
 	m->device_token = 0;   // the resident copy belongs to this context only until the next upload
 	mark_decoded(cx, *m);   // ... but hry_render_build may read it (render.cpp)

@@ -116,6 +116,25 @@ struct Ring {
 //   comp_first    : out, first vertex id of every component of this span
 //   refs          : out, (component of this span, older vertex it names) pairs -- the caller derives the dependency levels of
 //                   the reconstruction from them (replay_levels) once every span is known
+// the checked reader of the connectivity planes, an RD of replay_span below
+struct Planes {
+	const PlaneView *pl;   // container order: iop, elem[4], part[2], vertid[4], numtri[2], op[8]
+	size_t cur[kConnPlanes] = { 0 };
+	int fixed_numtri;
+	uint32_t byte(int plane)
+	{
+		const PlaneView &v = pl[plane];
+		if (cur[plane] >= v.size()) throw Error(HRY_E_FORMAT, "corrupt stream (connectivity plane exhausted)");
+		return v[cur[plane]++];
+	}
+	uint32_t iop() { return byte(group_first_plane(G_IOP)); }
+	uint32_t u32(int first) { uint32_t v = byte(first); v |= byte(first + 1) << 8; v |= byte(first + 2) << 16; v |= byte(first + 3) << 24; return v; }
+	int elem() { uint32_t z = u32(group_first_plane(G_ELEM)); return (int)((z >> 1) ^ ((z & 1) ? 0xffffffffu : 0u)); }   // transform.h:31-36
+	int part() { uint32_t v = byte(group_first_plane(G_PART)); v |= byte(group_first_plane(G_PART) + 1) << 8; return (int)v; }
+	uint32_t vertid() { return u32(group_first_plane(G_VERT)); }
+	int numtri() { if (fixed_numtri >= 0) return fixed_numtri; uint32_t v = byte(kNumtriPlane); v |= byte(kNumtriPlane + 1) << 8; return (int)v; }
+	uint32_t op(int order) { int k = order - 1; if (k > 7) k = 7; if (k < 0) k = 0; return byte(kOpPlane0 + k); }
+};
 // RD provides: iop(), vertid(), elem(), part(), numtri(), op(order)
 struct ReplayCursor { uint32_t next_id = 0, face = 0, he = 0; };
 
@@ -156,7 +175,7 @@ struct SnapshotSpans {
 	uint32_t *order_v;
 	size_t n_spans = 0;
 	uint64_t n_sym = 0;
-	struct Span { ReplayCursor cur; size_t cur0[21], cur1[21], cur_end[21]; uint32_t stop_face = 0xffffffffu; bool stop_mid = false, eom = false, done = false; BorderSeed seed; std::vector<uint32_t> first; std::vector<std::pair<uint32_t, uint32_t>> refs; };
+	struct Span { ReplayCursor cur; size_t cur0[kConnPlanes], cur1[kConnPlanes], cur_end[kConnPlanes]; uint32_t stop_face = 0xffffffffu; bool stop_mid = false, eom = false, done = false; BorderSeed seed; std::vector<uint32_t> first; std::vector<std::pair<uint32_t, uint32_t>> refs; };
 	std::vector<Span> spans;
 	std::vector<const SnapshotPoint*> seeds;
 	std::vector<uint32_t> sym_base;
@@ -476,7 +495,7 @@ bool replay_span(Mesh &m, RD &rd, uint16_t *seen_shared, uint32_t *order_v, Repl
 // part through bare pointers, the order counters in the shared array only.  Same checks against a corrupt stream as
 // replay_span, same results (the tests run both on the same inputs).
 // ---------------------------------------------------------------------------------------------------------
-// A span of it (round 6): cur0 / cur1 = where the 21 planes' cursors stand at its start and (at most) at its end (nullptr: the planes'
+// A span of it (round 6): cur0 / cur1 = where the kConnPlanes planes' cursors stand at its start and (at most) at its end (nullptr: the planes'
 // own ends); stop_face / stop_mid: it ends in front of the component that would start at face stop_face, or -- stop_mid -- inside a
 // component, between two operations, as soon as stop_face faces exist (`end` receives the border); seed: it starts inside a
 // component (`seen` then is the span's own array: the counts at the border's vertices are entered here).
@@ -501,21 +520,22 @@ bool replay_triangles(Mesh &m, const PlaneView *conn, uint16_t *seen, uint32_t *
 	std::vector<uint8_t> opl[8];
 	const uint8_t *opc[8];
 	for (int k = 0; k < 8; ++k) {
-		const size_t b = cur0 ? cur0[13 + k] : 0, e = cur1 ? cur1[13 + k] : conn[13 + k].size();
-		if (b > e || e > conn[13 + k].size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
+		const PlaneView &pl = conn[kOpPlane0 + k];
+		const size_t b = cur0 ? cur0[kOpPlane0 + k] : 0, e = cur1 ? cur1[kOpPlane0 + k] : pl.size();
+		if (b > e || e > pl.size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
 		opl[k].reserve(e - b + 1);
-		opl[k].assign(conn[13 + k].begin() + b, conn[13 + k].begin() + e);
+		opl[k].assign(pl.begin() + b, pl.begin() + e);
 		opl[k].push_back(0xff);
 		opc[k] = opl[k].data();
 	}
 	// the other connectivity planes are read a few times per mesh: checked cursors
-	size_t rc[13] = { 0 };
-	if (cur0) for (int k = 0; k < 13; ++k) rc[k] = cur0[k];
+	size_t rc[kOpPlane0] = { 0 };
+	if (cur0) for (int k = 0; k < kOpPlane0; ++k) rc[k] = cur0[k];
 	auto rbyte = [&](int p) -> uint32_t { if (rc[p] >= conn[p].size()) throw Error(HRY_E_FORMAT, "corrupt stream (connectivity plane exhausted)"); return conn[p][rc[p]++]; };
 	auto ru32 = [&](int first) -> uint32_t { uint32_t v = rbyte(first); v |= rbyte(first + 1) << 8; v |= rbyte(first + 2) << 16; v |= rbyte(first + 3) << 24; return v; };
-	auto r_elem = [&]() -> int { uint32_t z = ru32(1); return (int)((z >> 1) ^ ((z & 1) ? 0xffffffffu : 0u)); };
-	auto r_part = [&]() -> int { uint32_t v = rbyte(5); v |= rbyte(6) << 8; return (int)v; };
-	auto r_vertid = [&]() -> uint32_t { return ru32(7); };
+	auto r_elem = [&]() -> int { uint32_t z = ru32(group_first_plane(G_ELEM)); return (int)((z >> 1) ^ ((z & 1) ? 0xffffffffu : 0u)); };
+	auto r_part = [&]() -> int { uint32_t v = rbyte(group_first_plane(G_PART)); v |= rbyte(group_first_plane(G_PART) + 1) << 8; return (int)v; };
+	auto r_vertid = [&]() -> uint32_t { return ru32(group_first_plane(G_VERT)); };
 
 	std::vector<Node> pool;
 	pool.reserve(1 << 14);
@@ -607,7 +627,7 @@ bool replay_triangles(Mesh &m, const PlaneView *conn, uint16_t *seen, uint32_t *
 		if (resume) resume = false;   // (inside the component the span before this one ended in)
 		else {
 		if (!stop_mid && stop_face != NONE32 && face >= stop_face) break;
-		const uint32_t iop = rbyte(0);
+		const uint32_t iop = rbyte(group_first_plane(G_IOP));
 		if (iop == I_EOM) { eom = true; break; }
 		comp_first.push_back(seg_first_id);
 		comp_idx = (uint32_t)comp_first.size() - 1;
@@ -789,8 +809,8 @@ bool replay_triangles(Mesh &m, const PlaneView *conn, uint16_t *seen, uint32_t *
 stopped:
 	cur.next_id = next_id; cur.face = face; cur.he = he;
 	if (cur_out) {
-		for (int k = 0; k < 13; ++k) cur_out[k] = rc[k];
-		for (int k = 0; k < 8; ++k) cur_out[13 + k] = (cur0 ? cur0[13 + k] : 0) + (size_t)(opc[k] - opl[k].data());
+		for (int k = 0; k < kOpPlane0; ++k) cur_out[k] = rc[k];
+		for (int k = 0; k < 8; ++k) cur_out[kOpPlane0 + k] = (cur0 ? cur0[kOpPlane0 + k] : 0) + (size_t)(opc[k] - opl[k].data());
 	}
 	return eom;
 }

@@ -13,24 +13,6 @@
 
 namespace hry {
 namespace {
-struct Planes {
-	const PlaneView *pl;   // container order: iop, elem[4], part[2], vertid[4], numtri[2], op[8]
-	size_t cur[21] = { 0 };
-	int fixed_numtri;
-	uint32_t byte(int plane)
-	{
-		const PlaneView &v = pl[plane];
-		if (cur[plane] >= v.size()) throw Error(HRY_E_FORMAT, "corrupt stream (connectivity plane exhausted)");
-		return v[cur[plane]++];
-	}
-	uint32_t iop() { return byte(0); }
-	uint32_t u32(int first) { uint32_t v = byte(first); v |= byte(first + 1) << 8; v |= byte(first + 2) << 16; v |= byte(first + 3) << 24; return v; }
-	int elem() { uint32_t z = u32(1); return (int)((z >> 1) ^ ((z & 1) ? 0xffffffffu : 0u)); }   // transform.h:31-36
-	int part() { uint32_t v = byte(5); v |= byte(6) << 8; return (int)v; }
-	uint32_t vertid() { return u32(7); }
-	int numtri() { if (fixed_numtri >= 0) return fixed_numtri; uint32_t v = byte(11); v |= byte(12) << 8; return (int)v; }
-	uint32_t op(int order) { int k = order - 1; if (k > 7) k = 7; if (k < 0) k = 0; return byte(13 + k); }
-};
 
 
 // One span of the replay for meshes with polygons, written like replay_triangles (cbm_replay.hpp) for few instructions -- the
@@ -55,16 +37,17 @@ bool replay_polygons(Mesh &m, Planes &rd, uint16_t *seen_shared, uint32_t *order
 	uint32_t *const org = m.org.data(), *const twin = m.twin.data(), *const foff = m.face_off.data();
 	const uint8_t *opc[8], *ope[8];
 	for (int k = 0; k < 8; ++k) {
-		const PlaneView &v = rd.pl[13 + k];
-		if (rd.cur[13 + k] > v.size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
-		opc[k] = v.data() + rd.cur[13 + k]; ope[k] = v.data() + v.size();
+		const PlaneView &v = rd.pl[kOpPlane0 + k];
+		if (rd.cur[kOpPlane0 + k] > v.size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
+		opc[k] = v.data() + rd.cur[kOpPlane0 + k]; ope[k] = v.data() + v.size();
 	}
 	const int fixed = rd.fixed_numtri;
 	const uint8_t *nt0 = nullptr, *nt1 = nullptr, *nt0e = nullptr, *nt1e = nullptr;
 	if (fixed < 0) {
-		if (rd.cur[11] > rd.pl[11].size() || rd.cur[12] > rd.pl[12].size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
-		nt0 = rd.pl[11].data() + rd.cur[11]; nt0e = rd.pl[11].data() + rd.pl[11].size();
-		nt1 = rd.pl[12].data() + rd.cur[12]; nt1e = rd.pl[12].data() + rd.pl[12].size();
+		const int p0 = kNumtriPlane, p1 = kNumtriPlane + 1;
+		if (rd.cur[p0] > rd.pl[p0].size() || rd.cur[p1] > rd.pl[p1].size()) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart points)");
+		nt0 = rd.pl[p0].data() + rd.cur[p0]; nt0e = rd.pl[p0].data() + rd.pl[p0].size();
+		nt1 = rd.pl[p1].data() + rd.cur[p1]; nt1e = rd.pl[p1].data() + rd.pl[p1].size();
 	}
 	auto numtri = [&]() -> uint32_t {   // io.h:228-231
 		if (fixed >= 0) return (uint32_t)fixed;
@@ -345,8 +328,8 @@ bool replay_polygons(Mesh &m, Planes &rd, uint16_t *seen_shared, uint32_t *order
 	}
 stopped:
 	cur.next_id = next_id; cur.face = face; cur.he = he;
-	for (int k = 0; k < 8; ++k) rd.cur[13 + k] = (size_t)(opc[k] - rd.pl[13 + k].data());
-	if (fixed < 0) { rd.cur[11] = (size_t)(nt0 - rd.pl[11].data()); rd.cur[12] = (size_t)(nt1 - rd.pl[12].data()); }
+	for (int k = 0; k < 8; ++k) rd.cur[kOpPlane0 + k] = (size_t)(opc[k] - rd.pl[kOpPlane0 + k].data());
+	if (fixed < 0) { rd.cur[kNumtriPlane] = (size_t)(nt0 - rd.pl[kNumtriPlane].data()); rd.cur[kNumtriPlane + 1] = (size_t)(nt1 - rd.pl[kNumtriPlane + 1].data()); }
 	return eom;
 }
 }   // namespace
@@ -413,14 +396,9 @@ SnapshotSpans::SnapshotSpans(Mesh &mesh, const PlaneView *planes, const std::vec
 {
 	n_spans = snaps.size() + 1;
 	spans.resize(n_spans); seeds.assign(n_spans, nullptr); sym_base.assign(n_spans, 0); ends.resize(n_spans);
-	static const int first_plane[G_COUNT] = { 0, 1, 5, 7, 11 };
-	auto cursors_of = [&](const RestartPoint &r, size_t *cur) {
-		for (int g = 0; g < G_COUNT; ++g) for (int b = 0; b < kGroupBytes[g]; ++b) cur[first_plane[g] + b] = r.n_grp[g];
-		for (int i = 0; i < 8; ++i) cur[13 + i] = r.n_op[i];
-	};
 	for (size_t k = 0; k < n_spans; ++k) {
 		Span &sp = spans[k];
-		for (int p = 0; p < 21; ++p) { sp.cur0[p] = 0; sp.cur1[p] = conn[p].size(); sp.cur_end[p] = 0; }
+		for (int p = 0; p < kConnPlanes; ++p) { sp.cur0[p] = 0; sp.cur1[p] = conn[p].size(); sp.cur_end[p] = 0; }
 		if (k > 0) {
 			const SnapshotPoint &S = snaps[k - 1];
 			const RestartPoint &r = S.at;
@@ -428,14 +406,14 @@ SnapshotSpans::SnapshotSpans(Mesh &mesh, const PlaneView *planes, const std::vec
 			if (r.first_face <= prev_face || r.first_face > m.nf || r.first_vertex > m.nv || r.first_halfedge > m.declared_ne || !S.counters.empty())
 				throw Error(HRY_E_FORMAT, "corrupt chunked directory (border snapshots)");
 			sp.cur.next_id = r.first_vertex; sp.cur.face = r.first_face; sp.cur.he = r.first_halfedge;
-			cursors_of(r, sp.cur0);
-			for (int p = 0; p < 21; ++p) if (sp.cur0[p] > conn[p].size() && !((p == 11 || p == 12) && conn[p].empty())) throw Error(HRY_E_FORMAT, "corrupt chunked directory (border snapshots)");
+			plane_cursors(r, sp.cur0);
+			for (int p = 0; p < kConnPlanes; ++p) if (sp.cur0[p] > conn[p].size() && !(is_numtri_plane(p) && conn[p].empty())) throw Error(HRY_E_FORMAT, "corrupt chunked directory (border snapshots)");
 			seeds[k] = &S;
 			sym_base[k] = (uint32_t)(m.declared_ne + n_sym);
 			n_sym += S.vtx.size();
 			sp.seed = BorderSeed{ &S, sym_base[k] };
 		}
-		if (k + 1 < n_spans) { sp.stop_face = snaps[k].at.first_face; sp.stop_mid = true; cursors_of(snaps[k].at, sp.cur1); }
+		if (k + 1 < n_spans) { sp.stop_face = snaps[k].at.first_face; sp.stop_mid = true; plane_cursors(snaps[k].at, sp.cur1); }
 	}
 	if ((uint64_t)m.declared_ne + n_sym >= 0xffffffffull) throw Error(HRY_E_UNSUPPORTED, "border snapshots: the placeholders do not fit behind the half-edges");
 	m.twin.resize((size_t)m.declared_ne + n_sym);
@@ -486,7 +464,7 @@ void SnapshotSpans::cancel() { std::lock_guard<std::mutex> g(mu); cancelled = tr
 void SnapshotSpans::finish(ReplayCursor &cur, const size_t *cur_end0, BorderEnd &&end0, bool eom0, ReplayLive *live)
 try {
 	spans[0].cur = cur; spans[0].eom = eom0;
-	for (int p = 0; p < 21; ++p) spans[0].cur_end[p] = cur_end0[p];
+	for (int p = 0; p < kConnPlanes; ++p) spans[0].cur_end[p] = cur_end0[p];
 	ends[0] = std::move(end0);
 	SpanJoiner J(m);
 	static const BorderEnd none;
@@ -505,7 +483,7 @@ try {
 			const Span &sb = spans[k - 1];
 			const RestartPoint &r = snaps[k - 1].at;
 			bool ok = !sb.eom && sb.cur.face == r.first_face && sb.cur.next_id == r.first_vertex && sb.cur.he == r.first_halfedge && !ends[k - 1].parts.empty();
-			for (int p = 0; p < 21 && ok; ++p) if (p != 11 && p != 12) ok = sb.cur_end[p] == sp.cur0[p];   // (triangles: no counts of triangles per polygon)
+			for (int p = 0; p < kConnPlanes && ok; ++p) if (!is_numtri_plane(p)) ok = sb.cur_end[p] == sp.cur0[p];   // (triangles: no counts of triangles per polygon)
 			if (!ok) throw Error(HRY_E_FORMAT, "corrupt chunked directory (a border snapshot does not match the stream)");
 			J.step(k, seeds[k], seeds[k - 1], sym_base[k], sym_base[k - 1], ends[k - 1], live);
 		}
@@ -522,7 +500,7 @@ try {
 	cur = spans.back().cur;
 } catch (...) { cancel(); throw; }
 
-// planes: 21 connectivity planes in container order.  Fills m.face_off / org / twin and returns the decode order
+// planes: the connectivity planes in container order (host.hpp kConnPlanes).  Fills m.face_off / org / twin and returns the decode order
 // (one half-edge per vertex; vertex ids are assigned in this order, cbm/decoder.h:48-75,145).
 //
 // Restart points of the container directory cut the replay into spans that start at a component boundary with a known
@@ -542,52 +520,29 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 	const int fixed_numtri = ndeg <= 1 ? onlydeg - 2 : -1;
 	unsigned n_threads = host_threads();
 	if ((restarts.empty() && snaps.empty()) || n_threads < 2 || m.nf < parallel_min_faces() || counters.size() != restarts.size()) {
-		if (fixed_numtri == 1 && !env_on("HRY_GENERIC_REPLAY")) {
-			// triangles only: the lean loop (cbm_replay.hpp: replay_triangles), same results
-			m.face_off.resize((size_t)m.nf + 1); m.face_off[0] = 0;
-			m.org.resize(m.declared_ne);
-			m.twin.resize(m.declared_ne);
-			order_v.assign(m.nv, 0);
-			BigVec<uint16_t> seen(m.nv, 0);
-			ReplayCursor cur;
-			std::vector<std::pair<uint32_t, uint32_t>> refs;
-			seg_start.clear();
-			PerfCounters pc;
-			const bool count = env_on("HRY_PERF");
-			if (count) pc.start();
-			replay_triangles<false>(m, conn_planes, seen.data(), order_v.data(), cur, seg_start, refs, nullptr);
-			if (count) { pc.stop(); pc.report("cut-border replay (triangles)", (double)cur.he - 2.0 * cur.face); }
-			if (cur.face != m.nf) throw Error(HRY_E_FORMAT, "corrupt stream (face count)");
-			if (cur.he != m.declared_ne) throw Error(HRY_E_FORMAT, "corrupt stream (polygon edge count)");
-			order_v.resize(cur.next_id);
-			replay_levels(seg_start, refs, seg_level);
-			seg_start.push_back(cur.next_id);
-			return;
-		}
 		Planes rd{ conn_planes, { 0 }, fixed_numtri };
-		if (!env_on("HRY_GENERIC_REPLAY")) {   // polygons: the lean loop as one span from the start of the stream
-			m.face_off.resize((size_t)m.nf + 1); m.face_off[0] = 0;
-			m.org.resize(m.declared_ne);
-			m.twin.resize(m.declared_ne);
-			order_v.assign(m.nv, 0);
-			BigVec<uint16_t> seen(m.nv, 0);
-			ReplayCursor cur;
-			const RestartCounters none;
-			std::vector<std::pair<uint32_t, uint32_t>> refs;
-			seg_start.clear();
-			PerfCounters pc;
-			const bool count = env_on("HRY_PERF");
-			if (count) pc.start();
-			replay_polygons(m, rd, seen.data(), order_v.data(), cur, NONE32, 0, none, seg_start, refs);
-			if (count) { pc.stop(); pc.report("cut-border replay (polygons)", (double)cur.he - 2.0 * cur.face); }
-			if (cur.face != m.nf) throw Error(HRY_E_FORMAT, "corrupt stream (face count)");
-			if (cur.he != m.declared_ne) throw Error(HRY_E_FORMAT, "corrupt stream (polygon edge count)");
-			order_v.resize(cur.next_id);
-			replay_levels(seg_start, refs, seg_level);
-			seg_start.push_back(cur.next_id);
-			return;
-		}
-		cut_border_replay_with(m, rd, order_v, seg_start, seg_level);
+		if (env_on("HRY_GENERIC_REPLAY")) { cut_border_replay_with(m, rd, order_v, seg_start, seg_level); return; }
+		// the lean loop as one span from the start of the stream: triangles only (cbm_replay.hpp: replay_triangles) or polygons, same results
+		m.face_off.resize((size_t)m.nf + 1); m.face_off[0] = 0;
+		m.org.resize(m.declared_ne);
+		m.twin.resize(m.declared_ne);
+		order_v.assign(m.nv, 0);
+		BigVec<uint16_t> seen(m.nv, 0);
+		ReplayCursor cur;
+		const RestartCounters none;
+		std::vector<std::pair<uint32_t, uint32_t>> refs;
+		seg_start.clear();
+		PerfCounters pc;
+		const bool count = env_on("HRY_PERF");
+		if (count) pc.start();
+		if (fixed_numtri == 1) replay_triangles<false>(m, conn_planes, seen.data(), order_v.data(), cur, seg_start, refs, nullptr);
+		else replay_polygons(m, rd, seen.data(), order_v.data(), cur, NONE32, 0, none, seg_start, refs);
+		if (count) { pc.stop(); pc.report(fixed_numtri == 1 ? "cut-border replay (triangles)" : "cut-border replay (polygons)", (double)cur.he - 2.0 * cur.face); }
+		if (cur.face != m.nf) throw Error(HRY_E_FORMAT, "corrupt stream (face count)");
+		if (cur.he != m.declared_ne) throw Error(HRY_E_FORMAT, "corrupt stream (polygon edge count)");
+		order_v.resize(cur.next_id);
+		replay_levels(seg_start, refs, seg_level);
+		seg_start.push_back(cur.next_id);
 		return;
 	}
 	// spans: [start state, stop face); the points of both kinds in stream order -- faces ascending, and of a snapshot and a restart
@@ -604,7 +559,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 	}
 	const size_t ns = pts.size() + 1;
 	struct Span {
-		ReplayCursor cur; uint32_t stop_face; bool stop_mid = false; Planes rd; size_t cur1[21]; std::vector<uint32_t> first; std::vector<std::pair<uint32_t, uint32_t>> refs; bool eom = false;
+		ReplayCursor cur; uint32_t stop_face; bool stop_mid = false; Planes rd; size_t cur1[kConnPlanes]; std::vector<uint32_t> first; std::vector<std::pair<uint32_t, uint32_t>> refs; bool eom = false;
 		BorderSeed seed; uint32_t own_first = 0, f0 = 0, h0 = 0, v0 = 0;
 	};
 	std::vector<Span> spans(ns);
@@ -612,11 +567,6 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 	std::vector<uint32_t> sym_base(ns, 0);
 	std::vector<BorderEnd> ends(ns);
 	uint64_t n_sym = 0;
-	static const int first_plane[G_COUNT] = { 0, 1, 5, 7, 11 };
-	auto cursors_of = [&](const RestartPoint &r, size_t *cur) {
-		for (int g = 0; g < G_COUNT; ++g) for (int b = 0; b < kGroupBytes[g]; ++b) cur[first_plane[g] + b] = r.n_grp[g];
-		for (int i = 0; i < 8; ++i) cur[13 + i] = r.n_op[i];
-	};
 	for (size_t k = 0; k < ns; ++k) {
 		Span &sp = spans[k];
 		sp.rd = Planes{ conn_planes, { 0 }, fixed_numtri };
@@ -630,7 +580,7 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 			for (const auto &c : *pts[k - 1].c) if (c.first >= r.first_vertex) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart counters)");
 			sp.cur.next_id = r.first_vertex; sp.cur.face = r.first_face; sp.cur.he = r.first_halfedge;
 			sp.own_first = r.first_vertex;
-			cursors_of(r, sp.rd.cur);
+			plane_cursors(r, sp.rd.cur);
 			if (pts[k - 1].s) {
 				seeds[k] = pts[k - 1].s;
 				sym_base[k] = (uint32_t)(m.declared_ne + n_sym);
@@ -640,8 +590,8 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 		}
 		sp.stop_face = k + 1 < ns ? pts[k].r->first_face : NONE32;
 		sp.stop_mid = k + 1 < ns && pts[k].s != nullptr;
-		if (k + 1 < ns) cursors_of(*pts[k].r, sp.cur1);
-		else for (int p = 0; p < 21; ++p) sp.cur1[p] = conn_planes[p].size();
+		if (k + 1 < ns) plane_cursors(*pts[k].r, sp.cur1);
+		else for (int p = 0; p < kConnPlanes; ++p) sp.cur1[p] = conn_planes[p].size();
 	}
 	if ((uint64_t)m.declared_ne + n_sym >= 0xffffffffull) throw Error(HRY_E_UNSUPPORTED, "border snapshots: the placeholders do not fit behind the half-edges");
 	const bool trace = trace_on();
@@ -671,10 +621,11 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 		const RestartPoint &r = *pts[k].r;
 		bool ok = !sp.eom && sp.cur.face == r.first_face && sp.cur.next_id == r.first_vertex && sp.cur.he == r.first_halfedge;
 		ok = ok && (ends[k].parts.empty() == (pts[k].s == nullptr));   // (it stopped inside a component exactly where a snapshot says so)
-		for (int p = 0; p < 21 && ok; ++p) {
-			size_t want = p == 0 ? r.n_grp[0] : p < 5 ? r.n_grp[1] : p < 7 ? r.n_grp[2] : p < 11 ? r.n_grp[3] : p < 13 ? r.n_grp[4] : r.n_op[p - 13];
-			if (fixed_numtri >= 0 && (p == 11 || p == 12)) continue;   // numtri is not stored for a single polygon degree
-			ok = sp.rd.cur[p] == want;
+		size_t want[kConnPlanes];
+		plane_cursors(r, want);
+		for (int p = 0; p < kConnPlanes && ok; ++p) {
+			if (fixed_numtri >= 0 && is_numtri_plane(p)) continue;   // numtri is not stored for a single polygon degree
+			ok = sp.rd.cur[p] == want[p];
 		}
 		if (!ok) throw Error(HRY_E_FORMAT, "corrupt chunked directory (restart point does not match the stream)");
 	};
@@ -693,10 +644,10 @@ void cut_border_replay(Mesh &m, const PlaneView *conn_planes, const std::vector<
 			uint16_t *sn = own ? own->p : seen.data();
 			// triangles: the lean loop where the span needs no counters of older vertices from a table (none named, or all of them in its own array)
 			if (lean && fixed_numtri == 1 && old_counts.empty()) {
-				size_t cur_end[21];
+				size_t cur_end[kConnPlanes];
 				sp.eom = replay_triangles<false>(m, conn_planes, sn, order_v.data(), sp.cur, sp.first, sp.refs, nullptr, sp.rd.cur, sp.cur1, sp.stop_face, sp.stop_mid,
 				                                 seeds[k] ? &sp.seed : nullptr, &ends[k], cur_end);
-				for (int p = 0; p < 21; ++p) sp.rd.cur[p] = cur_end[p];
+				for (int p = 0; p < kConnPlanes; ++p) sp.rd.cur[p] = cur_end[p];
 			}
 			else if (lean) sp.eom = replay_polygons(m, sp.rd, sn, order_v.data(), sp.cur, sp.stop_face, sp.own_first, old_counts, sp.first, sp.refs, sp.stop_mid, seeds[k] ? &sp.seed : nullptr, &ends[k]);
 			else sp.eom = replay_span(m, sp.rd, seen.data(), order_v.data(), sp.cur, sp.stop_face, sp.own_first, old_counts, sp.first, sp.refs);

@@ -331,4 +331,196 @@ size_t read_snapshot_section(const uint8_t *p, size_t avail, uint32_t nv, uint32
 	return total;
 }
 
+// ---- the chunked container's planes and directory (host.hpp ChunkedDirectory; the oracle restates the form) ---------------
+
+void walk_conn_planes(const WalkResult &w, std::vector<uint8_t> planes[kConnPlanes])
+{
+	for (int g = 0; g < G_COUNT; ++g)
+		for (int b = 0; b < kGroupBytes[g]; ++b) {
+			std::vector<uint8_t> &pl = planes[group_first_plane(g) + b];
+			pl.resize(w.grp_val[g].size());
+			for (size_t i = 0; i < pl.size(); ++i) pl[i] = (uint8_t)(w.grp_val[g][i] >> (8 * b));
+		}
+	for (int k = 0; k < kOpClasses; ++k) planes[kOpPlane0 + k].clear();
+	for (size_t i = 0; i < w.op_sc.size(); ++i) planes[kOpPlane0 + (op_u8(w.op_sc[i]) >> 3)].push_back(op_u8(w.op_sc[i]) & 7);
+}
+
+std::vector<GenPlane> general_plane_layout(const Mesh &m)
+{
+	std::vector<GenPlane> p;
+	if (m.bind.nregs_vtx() > 1) p.push_back(GenPlane{ GP_REGV, -1, 0, INIT_REGV });
+	if (m.bind.nregs_face() > 1) p.push_back(GenPlane{ GP_REGF, -1, 0, INIT_REGF });
+	for (size_t l = 0; l < m.lists.size(); ++l) {
+		const AttrList &L = m.lists[l];
+		if (L.target == 3) continue;
+		p.push_back(GenPlane{ GP_TYPE, (int)l, 0, L.target == 2 ? INIT_TYPE3 : INIT_TYPE2 });
+		for (int k = 0; k < 4; ++k) p.push_back(GenPlane{ GP_GHIST, (int)l, k, INIT_ONES });
+		if (L.target == 2) for (int k = 0; k < 2; ++k) p.push_back(GenPlane{ GP_LHIST, (int)l, k, INIT_ONES });
+		for (int k = 0; k < L.coded_bytes(); ++k) p.push_back(GenPlane{ GP_DATA, (int)l, k, INIT_ONES });
+	}
+	return p;
+}
+
+std::vector<GenPlane> container_planes(const Mesh &m)
+{
+	std::vector<GenPlane> p;
+	for (int k = 0; k < kConnPlanes; ++k) p.push_back(GenPlane{ GP_CONN, -1, k, conn_plane_init(k) });
+	if (m.general) {
+		const std::vector<GenPlane> g = general_plane_layout(m);
+		p.insert(p.end(), g.begin(), g.end());
+		return p;
+	}
+	for (int b = 0; b < m.lists[1].coded_bytes(); ++b) p.push_back(GenPlane{ GP_VERTEX, 1, b, INIT_ONES });
+	for (int b = 0; b < m.lists[0].coded_bytes(); ++b) p.push_back(GenPlane{ GP_FACE, 0, b, INIT_ONES });
+	return p;
+}
+
+void build_init_tables(const Mesh &m, std::vector<uint32_t> &tabs)
+{
+	tabs.assign((size_t)INIT_KINDS * 256, 0);
+	for (int i = 0; i < 256; ++i) tabs[INIT_ONES * 256 + i] = 1;
+	for (int i = 0; i < 9; ++i) tabs[INIT_IOP * 256 + i] = 1;
+	for (size_t d = 3; d < m.have_degree.size(); ++d)
+		if (m.have_degree[d]) { ++tabs[INIT_NT0 * 256 + ((d - 2) & 0xff)]; ++tabs[INIT_NT1 * 256 + ((d - 2) >> 8)]; }
+	for (int i = 0; i < 7; ++i) tabs[INIT_OP * 256 + i] = 1;
+	if (m.general) {   // models.h:201-203,212-217
+		for (int r = 0; r < m.bind.nregs_vtx() && r < 256; ++r) tabs[INIT_REGV * 256 + r] = 1;
+		for (int r = 0; r < m.bind.nregs_face() && r < 256; ++r) tabs[INIT_REGF * 256 + r] = 1;
+	}
+	tabs[INIT_TYPE2 * 256 + 0] = tabs[INIT_TYPE2 * 256 + 1] = 1;
+	tabs[INIT_TYPE3 * 256 + 0] = tabs[INIT_TYPE3 * 256 + 1] = tabs[INIT_TYPE3 * 256 + 2] = 1;
+}
+
+// Everything is validated here, before a decoder allocates anything on the device: the directory against the header, every length
+// against the bytes there are, the plane lengths against the mesh's sizes, every plane's table.
+void read_chunked_directory(const uint8_t *p, size_t n, size_t hdr, const Mesh &m, ChunkedDirectory &d)
+{
+	auto need = [&](size_t off, size_t k) { if (off + k > n) throw Error(HRY_E_FORMAT, "truncated chunked directory"); };
+	size_t off = hdr;
+	need(off, 12);
+	uint32_t np;
+	memcpy(&d.CH, p + off, 4); memcpy(&d.CHC, p + off + 4, 4); memcpy(&np, p + off + 8, 4);
+	off += 12;
+	const std::vector<GenPlane> layout = container_planes(m);
+	if (d.CH == 0 || d.CHC == 0 || d.CH > (1u << 20) || d.CHC > d.CH || np != layout.size()) throw Error(HRY_E_FORMAT, "chunked directory does not match the header");
+	need(off, 4ull * np);
+	d.nsym.resize(np);
+	memcpy(d.nsym.data(), p + off, 4ull * np);
+	off += 4ull * np;
+	uint64_t nstreams = 0;
+	d.total_syms = 0;
+	for (uint32_t k = 0; k < np; ++k) {
+		nstreams += plane_stream_count(k, d.nsym[k], d.CH, d.CHC);
+		d.total_syms += d.nsym[k];
+	}
+	// static prior of every plane (or none: the reference's initial counts)
+	d.tables.assign((size_t)np * 256, 0);
+	d.has_prior.assign(np, 0);
+	for (uint32_t k = 0; k < np; ++k) {
+		bool use = false;
+		off += read_prior(p + off, n - off, use, d.tables.data() + (size_t)k * 256);
+		d.has_prior[k] = use ? 1 : 0;
+	}
+	need(off, 4);
+	uint32_t nrs;
+	memcpy(&nrs, p + off, 4);
+	off += 4;
+	const bool has_snapshots = (nrs & 0x80000000u) != 0;   // (round 6: a section of border snapshots follows the restart points' counters)
+	nrs &= 0x7fffffffu;
+	if ((uint64_t)nrs * sizeof(RestartPoint) > n) throw Error(HRY_E_FORMAT, "truncated chunked directory");
+	need(off, sizeof(RestartPoint) * (size_t)nrs);
+	d.restarts.resize(nrs);
+	if (nrs) memcpy(d.restarts.data(), p + off, sizeof(RestartPoint) * (size_t)nrs);
+	off += sizeof(RestartPoint) * (size_t)nrs;
+	d.counters.assign(nrs, RestartCounters());
+	for (uint32_t k = 0; k < nrs; ++k) {
+		need(off, 4);
+		uint32_t nc;
+		memcpy(&nc, p + off, 4);
+		off += 4;
+		if ((uint64_t)nc * 8 > n) throw Error(HRY_E_FORMAT, "truncated chunked directory");
+		need(off, 8ull * nc);
+		d.counters[k].resize(nc);
+		for (uint32_t j = 0; j < nc; ++j) { uint32_t v[2]; memcpy(v, p + off + 8ull * j, 8); d.counters[k][j] = { v[0], v[1] }; }
+		off += 8ull * nc;
+	}
+	d.snapshots.clear(); d.snapshot_section.clear();
+	if (has_snapshots) {
+		uint32_t spacing = 0;
+		const size_t used = read_snapshot_section(p + off, n - off, m.nv, spacing, d.snapshots);
+		d.snapshot_section.assign(p + off, p + off + used);
+		off += used;
+	}
+	need(off, 4 * nstreams);
+	d.stream_bytes.resize((size_t)nstreams);
+	if (nstreams) memcpy(d.stream_bytes.data(), p + off, 4 * (size_t)nstreams);
+	off += 4 * (size_t)nstreams;
+	d.stream_off.assign((size_t)nstreams + 1, 0);
+	for (size_t i = 0; i < nstreams; ++i) d.stream_off[i + 1] = d.stream_off[i] + d.stream_bytes[i];
+	if (off + d.stream_off[nstreams] > n) throw Error(HRY_E_FORMAT, "truncated chunked payload");
+	d.payload_at = off;
+	// plausibility of the plane sizes against the header: at most one vertex / face record per element
+	if (!m.general) {
+		const uint32_t vc = np > (uint32_t)kConnPlanes && layout[kConnPlanes].what == GP_VERTEX ? d.nsym[kConnPlanes] : 0;
+		for (uint32_t k = kConnPlanes; k < np; ++k) if (layout[k].what == GP_VERTEX && d.nsym[k] != vc) throw Error(HRY_E_FORMAT, "vertex planes of different length");
+		for (uint32_t k = kConnPlanes; k < np; ++k) if (layout[k].what == GP_FACE && d.nsym[k] != m.nf) throw Error(HRY_E_FORMAT, "face planes of wrong length");
+		if (vc > m.nv) throw Error(HRY_E_FORMAT, "more coded vertices than vertices");
+	} else {
+		// at most one reference per vertex / face / corner slot, at most one record per reference
+		const uint64_t most = (uint64_t)m.nv * m.bind.nb_vtx + (uint64_t)m.nf * m.bind.nb_face + (uint64_t)m.declared_ne * m.bind.nb_corner + 16;
+		for (uint32_t k = kConnPlanes; k < np; ++k) {
+			if (d.nsym[k] > most) throw Error(HRY_E_FORMAT, "implausible plane length");
+			if (layout[k].what == GP_DATA && d.nsym[k] > m.lists[layout[k].list].count) throw Error(HRY_E_FORMAT, "more records than the header announces");
+		}
+	}
+	if (d.total_syms > (1ull << 33)) throw Error(HRY_E_FORMAT, "implausible symbol count");
+	// model tables: one per plane (its prior, or the reference's initial counts of its kind)
+	std::vector<uint32_t> kind_tabs;
+	build_init_tables(m, kind_tabs);
+	d.totals.assign(np, 0);
+	d.max_total = 256;
+	for (uint32_t k = 0; k < np; ++k) {
+		uint32_t *tab = d.tables.data() + (size_t)k * 256;
+		if (!d.has_prior[k]) memcpy(tab, kind_tabs.data() + (size_t)layout[k].init * 256, 1024);
+		uint64_t t = 0;
+		for (int i = 0; i < 256; ++i) t += tab[i];
+		if (t == 0 && d.nsym[k]) throw Error(HRY_E_FORMAT, "corrupt chunked directory (empty model)");
+		if (t > (1u << 24)) throw Error(HRY_E_FORMAT, "corrupt chunked directory (prior total)");
+		d.totals[k] = (uint32_t)t;
+		d.max_total = std::max(d.max_total, d.totals[k]);
+	}
+}
+
+void write_restart_section(const ChunkedDirectory &d, std::vector<uint8_t> &out)
+{
+	static_assert(sizeof(RestartPoint) == kRestartWords * 4, "restart points are written as they lie in memory");
+	Out w{ out };
+	out.reserve(out.size() + 4 + sizeof(RestartPoint) * d.restarts.size() + 4 * d.counters.size() + d.snapshot_section.size());
+	w.v<uint32_t>((uint32_t)d.restarts.size() | (d.snapshot_section.empty() ? 0u : 0x80000000u));
+	w.raw(d.restarts.data(), sizeof(RestartPoint) * d.restarts.size());
+	for (const RestartCounters &cs : d.counters) { w.v<uint32_t>((uint32_t)cs.size()); for (const auto &c : cs) { w.v<uint32_t>(c.first); w.v<uint32_t>(c.second); } }
+	w.raw(d.snapshot_section.data(), d.snapshot_section.size());
+}
+
+size_t write_chunked_directory(const ChunkedDirectory &d, ByteSink &out, uint64_t payload_bytes, const std::vector<uint8_t> *restart_section)
+{
+	const uint32_t np = (uint32_t)d.nsym.size();
+	std::vector<uint8_t> head;
+	Out w{ head };
+	w.v<uint32_t>(d.CH); w.v<uint32_t>(d.CHC); w.v<uint32_t>(np);
+	w.raw(d.nsym.data(), 4 * (size_t)np);
+	for (uint32_t k = 0; k < np; ++k) write_prior(head, d.has_prior[k] != 0, d.tables.data() + (size_t)k * 256);
+	std::vector<uint8_t> own;
+	if (!restart_section) { write_restart_section(d, own); restart_section = &own; }
+	uint64_t ns = 0;
+	for (uint32_t k = 0; k < np; ++k) ns += plane_stream_count(k, d.nsym[k], d.CH, d.CHC);
+	if (!d.stream_bytes.empty() && d.stream_bytes.size() != ns) throw Error(HRY_E_INTERNAL, "chunked directory: stream lengths that do not match the planes");
+	const size_t base = out.size(), at = base + head.size() + restart_section->size();
+	out.resize(at + 4 * (size_t)ns + payload_bytes);
+	memcpy(out.data() + base, head.data(), head.size());
+	if (!restart_section->empty()) memcpy(out.data() + base + head.size(), restart_section->data(), restart_section->size());
+	if (!d.stream_bytes.empty()) memcpy(out.data() + at, d.stream_bytes.data(), 4 * (size_t)ns);
+	return at;
+}
+
 }   // namespace hry

@@ -1,5 +1,6 @@
 // Host-side declarations of the product (PLY I/O, cut-border walk, .hry header).
 #pragma once
+#include <algorithm>
 #include <exception>
 #include <memory>
 #include <mutex>
@@ -48,6 +49,21 @@ enum ConnGroup { G_IOP = 0, G_ELEM, G_PART, G_VERT, G_NUMTRI, G_COUNT };
 static constexpr int kGroupBytes[G_COUNT] = { 1, 4, 2, 4, 2 };
 static constexpr int kGroupCtx[G_COUNT] = { CTX_IOP, CTX_ELEM, CTX_PART, CTX_VERT, CTX_NUMTRI };
 
+// ---- the chunked container's connectivity planes (.hry v0.2; the oracle restates them): every group's bytes, low byte first, in
+// group order, then one plane of operations per order class -- iop, elem[4], part[2], vertid[4], numtri[2], op class[8]
+constexpr int group_first_plane(int g) { return g == 0 ? 0 : group_first_plane(g - 1) + kGroupBytes[g - 1]; }
+constexpr int kNumtriPlane = group_first_plane(G_NUMTRI);              // and kNumtriPlane + 1 (absent with one polygon degree)
+constexpr int kOpClasses = 8;
+constexpr int kOpPlane0 = group_first_plane(G_COUNT - 1) + kGroupBytes[G_COUNT - 1];   // operation class k: plane kOpPlane0 + k
+constexpr int kConnPlanes = kOpPlane0 + kOpClasses;
+inline bool is_numtri_plane(int k) { return k == kNumtriPlane || k == kNumtriPlane + 1; }
+// initial counts of a plane that carries no static prior (the reference's initial model of that context, models.h:197-218)
+enum { INIT_ONES = 0, INIT_IOP = 1, INIT_NT0 = 2, INIT_NT1 = 3, INIT_OP = 4, INIT_REGV = 5, INIT_REGF = 6, INIT_TYPE2 = 7, INIT_TYPE3 = 8, INIT_KINDS = 9 };
+constexpr int conn_plane_init(int k)
+{
+	return k == 0 ? INIT_IOP : k == kNumtriPlane ? INIT_NT0 : k == kNumtriPlane + 1 ? INIT_NT1 : k >= kOpPlane0 ? INIT_OP : INIT_ONES;
+}
+
 // Output of the host-side cut-border walk (the inputs the device path needs)
 // State of the connectivity coding at the start of a connected component: how many symbols of every connectivity plane group
 // and of every operation class precede it, and the first vertex index / face / half-edge it will create.
@@ -65,6 +81,12 @@ struct RestartPoint {
 	uint32_t first_vertex, first_face, first_halfedge;
 	uint32_t flags;
 };
+// where the cursors of the connectivity planes stand at a restart point
+inline void plane_cursors(const RestartPoint &r, size_t cur[kConnPlanes])
+{
+	for (int g = 0; g < G_COUNT; ++g) for (int b = 0; b < kGroupBytes[g]; ++b) cur[group_first_plane(g) + b] = r.n_grp[g];
+	for (int i = 0; i < kOpClasses; ++i) cur[kOpPlane0 + i] = r.n_op[i];
+}
 // An explicit naming of a vertex (TRIxxx start, NM operation) with the number of triangles seen at it so far (the "order"
 // the operation planes are split by, models.h:69-72) and the component (index into marks) that names it.
 // snap: how many border snapshots (below) its component had taken when the vertex was named -- 0 = before the first
@@ -359,6 +381,75 @@ struct SnapshotPoint {
 };
 void write_snapshot_section(uint32_t spacing, const std::vector<BorderSnapshot> &snaps, const std::vector<RestartCounters> &counters, std::vector<uint8_t> &out);
 size_t read_snapshot_section(const uint8_t *p, size_t avail, uint32_t nv, uint32_t &spacing, std::vector<SnapshotPoint> &out);   // returns bytes consumed; throws on damage
+
+// ---- the chunked container's planes and directory (header.cpp; the oracle restates them)
+// the connectivity planes of a walk, built on the host: groups split into little-endian bytes, operations split by order class
+void walk_conn_planes(const WalkResult &w, std::vector<uint8_t> planes[kConnPlanes]);
+// Chunks of an attribute plane grow with their position: 1 Ki symbols each up to symbol 32 Ki, 2 Ki up to 64 Ki, 4 Ki up to 128 Ki
+// ... (length = position / 16 rounded down to a power of two, at least 1 Ki, at most the container's chunk size).  A stream is one
+// serial wavefront, 0.26 us per symbol: the decoder's reconstruction chain walks the vertices in order at 16 ns each and finds
+// every chunk decoded when it gets there, instead of waiting for the first full-size chunk (2.1 ms at 8 Ki symbols).
+// Connectivity planes keep one size, CHC (they are needed whole, first).
+inline uint32_t attr_chunk_len(uint64_t pos, uint32_t chunk_syms)
+{
+	uint32_t len = 1024;
+	while (len < chunk_syms && (uint64_t)len * 2 <= pos / 16) len *= 2;
+	return len < chunk_syms ? len : chunk_syms;
+}
+// the streams plane k of nsym symbols is cut into under chunk sizes CH / CHC: f(first symbol, symbols) for each, in order
+template <typename F> inline void for_plane_streams(uint32_t k, uint64_t nsym, uint32_t CH, uint32_t CHC, F &&f)
+{
+	for (uint64_t pos = 0, step; pos < nsym; pos += step) {
+		step = k < (uint32_t)kConnPlanes ? CHC : attr_chunk_len(pos, CH);
+		f(pos, (uint32_t)std::min<uint64_t>(step, nsym - pos));
+	}
+}
+inline uint64_t plane_stream_count(uint32_t k, uint64_t nsym, uint32_t CH, uint32_t CHC)
+{
+	if (k < (uint32_t)kConnPlanes) return (nsym + CHC - 1) / CHC;
+	uint64_t n = 0;
+	for_plane_streams(k, nsym, CH, CHC, [&](uint64_t, uint32_t) { ++n; });
+	return n;
+}
+// Every plane of a mesh's container in container order: the connectivity planes, then -- PLY layout -- the bytes of the vertex
+// records' components, then those of the face records; or -- general bindings -- the region of every vertex / face (low byte; only
+// with more than one region), then per list a region binds, in list order: the kind of every reference, the creation-order
+// distances (4 planes), at corner lists the per-vertex distances (2 planes), the residual bytes of the records coded as data.
+// list / byte: which list, which byte of the plane's values; init: the initial counts of a plane without a static prior.
+enum { GP_REGV = 0, GP_REGF, GP_TYPE, GP_GHIST, GP_LHIST, GP_DATA, GP_CONN, GP_VERTEX, GP_FACE };
+struct GenPlane { int what, list, byte, init; };
+std::vector<GenPlane> container_planes(const Mesh &m);
+std::vector<GenPlane> general_plane_layout(const Mesh &m);   // general bindings: the planes behind the connectivity's
+void build_init_tables(const Mesh &m, std::vector<uint32_t> &tabs);   // INIT_KINDS x 256
+
+// The directory of a chunked container (behind the header; a segment of a sharded container has one behind its runs):
+//     u32 chunk_syms (CH), u32 conn_chunk_syms (CHC), u32 n_planes, n_planes x u32 n_symbols, n_planes x static prior (write_prior),
+//     u32 n_restarts (top bit: a border snapshot section follows), n_restarts x RestartPoint as it lies in memory, per restart point
+//     u32 n and n x (vertex, counter), the border snapshot section (write_snapshot_section), n_streams x u32 n_bytes; the streams
+//     follow back to back, every plane's cut as for_plane_streams says.
+struct ChunkedDirectory {
+	uint32_t CH = 0, CHC = 0;
+	std::vector<uint32_t> nsym;              // per plane
+	std::vector<uint8_t> has_prior;          // per plane: 1 = its static prior, 0 = the initial counts of its kind
+	std::vector<uint32_t> tables;            // per plane 256 counts: the table every stream of the plane starts from
+	std::vector<uint32_t> totals;            // per plane: the table's total (reader only)
+	uint32_t max_total = 256;                // (reader only)
+	uint64_t total_syms = 0;                 // (reader only)
+	std::vector<RestartPoint> restarts;
+	std::vector<RestartCounters> counters;   // per restart point
+	std::vector<uint8_t> snapshot_section;   // the border snapshots as they lie in the directory (empty: none)
+	std::vector<SnapshotPoint> snapshots;    // ... parsed (reader only)
+	std::vector<uint32_t> stream_bytes;      // per stream (the writer leaves their place to its caller when this is empty)
+	std::vector<uint64_t> stream_off;        // per stream + end: offset in the payload (reader only)
+	size_t payload_at = 0;                   // (reader only) where the streams begin in the container
+};
+// parses and validates the directory against the header's mesh skeleton; throws HRY_E_FORMAT on damage
+void read_chunked_directory(const uint8_t *p, size_t n, size_t hdr, const Mesh &m, ChunkedDirectory &d);
+// the restart points, their counters and the snapshot section as they lie in the directory
+void write_restart_section(const ChunkedDirectory &d, std::vector<uint8_t> &out);
+// appends the directory to out and makes room behind it for the stream lengths and payload_bytes of streams; returns where the
+// stream lengths go (the streams follow them).  restart_section: what write_restart_section made of d (nullptr: made here)
+size_t write_chunked_directory(const ChunkedDirectory &d, ByteSink &out, uint64_t payload_bytes, const std::vector<uint8_t> *restart_section = nullptr);
 
 // ---- header.cpp (formats/hry/writer.cc:104-198 / reader.cc:60-177)
 // reference single-stream format (compat_read.cpp): serial entropy decode + replay on the host; residual byte planes

@@ -1,8 +1,10 @@
 // Host-only pieces of the product under AddressSanitizer / UBSan (CPU build, no HIP): PLY and OBJ readers and writers, twin
-// matching, the cut-border walk, the reference-stream reader with its replay, header parsing of arbitrary bytes, sharding.
+// matching, the cut-border walk, the reference-stream reader with its replay, header parsing of arbitrary bytes, the chunked
+// container's directory, sharding.
 // Built and run by tests/test_host_cpu.py::test_host_code_under_sanitizers.  Usage: driver FILE...  (.ply .obj .hry)
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <ctime>
 #include <fstream>
 #include <iterator>
@@ -25,7 +27,7 @@ static std::vector<uint8_t> slurp(const std::string &fn)
 
 int main(int argc, char **argv)
 {
-	int done = 0;
+	int done = 0, n_dirs = 0, n_damaged = 0;
 	for (int i = 1; i < argc; ++i) {
 		const std::string fn = argv[i];
 		const std::vector<uint8_t> data = slurp(fn);
@@ -115,17 +117,10 @@ int main(int argc, char **argv)
 					{
 						// the decoder's replay of what the walk wrote: as one sequence, and from the restart points and border snapshots of the
 						// directory on the host threads (spans joined afterwards) -- the same arrays; then the snapshots' section damaged
-						std::vector<uint8_t> planes[21];
-						static const int first_plane[G_COUNT] = { 0, 1, 5, 7, 11 };
-						for (int g = 0; g < G_COUNT; ++g)
-							for (int b = 0; b < kGroupBytes[g]; ++b) {
-								std::vector<uint8_t> &pl = planes[first_plane[g] + b];
-								pl.resize(w2.grp_val[g].size());
-								for (size_t q = 0; q < pl.size(); ++q) pl[q] = (uint8_t)(w2.grp_val[g][q] >> (8 * b));
-							}
-						for (size_t q = 0; q < w2.op_sc.size(); ++q) planes[13 + (op_u8(w2.op_sc[q]) >> 3)].push_back(op_u8(w2.op_sc[q]) & 7);
-						PlaneView views[21];
-						for (int k = 0; k < 21; ++k) views[k] = PlaneView(planes[k]);
+						std::vector<uint8_t> planes[kConnPlanes];
+						walk_conn_planes(w2, planes);
+						PlaneView views[kConnPlanes];
+						for (int k = 0; k < kConnPlanes; ++k) views[k] = PlaneView(planes[k]);
 						auto skeleton = [&](Mesh &d) { d.nv = m2->nv; d.nf = m2->nf; d.declared_ne = m2->ne(); d.have_degree = m2->have_degree; };
 						Mesh seq, par;
 						skeleton(seq); skeleton(par);
@@ -149,7 +144,7 @@ int main(int argc, char **argv)
 						// stretch up to the first snapshot and publishes its progress, helper threads the stretches behind the snapshots
 						// (SnapshotSpans), joined one after the other as they finish; a reader thread plays the consumer
 						int udeg = 0;
-						const bool pipelined = !snaps.empty() && rs.empty() && planes[7].empty() && m2->uniform_degree(udeg) && udeg == 3;
+						const bool pipelined = !snaps.empty() && rs.empty() && planes[group_first_plane(G_VERT)].empty() && m2->uniform_degree(udeg) && udeg == 3;
 						auto replay_publishing = [&](const std::vector<SnapshotPoint> &sn, Mesh &live_m, OrderVec &ov_live) {   // returns the stretches announced
 							skeleton(live_m);
 							live_m.face_off.resize((size_t)live_m.nf + 1); live_m.face_off[0] = 0;
@@ -278,6 +273,27 @@ int main(int argc, char **argv)
 				Mesh m;
 				int minor = 0;
 				const size_t h = read_hry_header(data.data(), data.size(), m, minor);
+				if (minor == 2) {
+					// the chunked container's directory: read, written back byte for byte, then read again with bytes flipped inside it
+					// (the header intact): a directory or an hry::Error
+					ChunkedDirectory d;
+					read_chunked_directory(data.data(), data.size(), h, m, d);
+					ByteSink again;
+					write_chunked_directory(d, again, 0);
+					const size_t dir_bytes = d.payload_at - h;
+					if (again.size() != dir_bytes || memcmp(again.data(), data.data() + h, dir_bytes) != 0) throw Error(HRY_E_INTERNAL, "chunked directory: written back, it differs from the file's");
+					++n_dirs;
+					for (int k = 0; k < 256; ++k) {
+						std::vector<uint8_t> bad = data;
+						for (int j = 0; j < 1 + k % 3; ++j) bad[h + (size_t)(1103515245u * (unsigned)(k * 3 + j + 1) + 12345u) % dir_bytes] ^= (uint8_t)(1u << ((k + j) & 7));
+						try {
+							ChunkedDirectory d2;
+							read_chunked_directory(bad.data(), bad.size(), h, m, d2);
+						} catch (const Error &) {
+						}
+						++n_damaged;
+					}
+				}
 				if (minor == 1) {
 					OrderVec order_v;
 					std::vector<uint32_t> seg_start, seg_level;
@@ -325,6 +341,7 @@ int main(int argc, char **argv)
 			return 2;
 		}
 	}
+	fprintf(stderr, "chunked directories: %d read and written back byte for byte, %d damaged copies read\n", n_dirs, n_damaged);
 	printf("ok %d files\n", done);
 	return 0;
 }

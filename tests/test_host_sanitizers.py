@@ -1,6 +1,6 @@
 """The product's host-only code (PLY / OBJ readers and writers, twin matching, the cut-border walk, the reference-stream readers
-with their replay, header parsing, sharding) built with gcc's AddressSanitizer and UBSan and run over every golden input, and over
-damaged copies of them.  The GPU pool has no sanitizer runs; this is the CPU build the task's environment notes ask for."""
+with their replay, header parsing, the chunked container's directory, sharding) built with gcc's AddressSanitizer and UBSan and run
+over every golden input, a few chunked containers of the oracle's, and over damaged copies of them.  The GPU pool has no sanitizer runs; this is the CPU build the task's environment notes ask for."""
 import glob
 import os
 import shutil
@@ -35,12 +35,39 @@ def test_host_code_under_sanitizers(tmp_path):
     g = os.path.join(ROOT, "tests", "golden")
     files = [f for f in sorted(glob.glob(g + "/*.ply") + glob.glob(g + "/obj/*.obj")) if ".dec." not in f]   # the reference's own
     files += sorted(glob.glob(g + "/*.hry") + glob.glob(g + "/obj/*.hry"))                                   # outputs do not all re-read
+    chunked = _chunked_containers(tmp_path)
+    files += chunked
     # (the walks of the chunked profile and of a shard in place run on four host threads whatever the mesh's size)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", HRY_PARALLEL_MIN_FACES="1", HRY_HOST_THREADS="4", HRY_WALK_SPLIT="1", HRY_WALK_RING="1024")   # (... and a triangle mesh's first component on two cores)
     env.pop("LD_PRELOAD", None)
     r = subprocess.run([exe, *files], capture_output=True, text=True, env=env, timeout=800)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (r.stdout + r.stderr)[-4000:]
     assert r.stdout.strip() == "ok %d files" % len(files)
+    # every chunked container's directory was read, written back byte for byte and read again damaged
+    assert "chunked directories: %d read and written back byte for byte, %d damaged copies read" % (len(chunked), 256 * len(chunked)) in r.stderr, r.stderr[-4000:]
+
+
+def _chunked_containers(tmp_path):
+    """A few chunked containers (.hry v0.2) from the CPU oracle: the PLY layout with restart points and their counters, one with
+    border snapshots, one with general bindings"""
+    from harry_amd import meshgen as mg
+    from oracle import oracle_py as op
+    g = os.path.join(ROOT, "tests", "golden")
+    many = mg.with_nonmanifold(mg.multi_component(12, 30, 31, seed=5, polys="mixed"), 40, 20, seed=4).to_ply()
+    with open(os.path.join(g, "grid50.ply"), "rb") as f:
+        grid = f.read()
+    with open(os.path.join(g, "obj", "mixedfmt.obj"), "rb") as f:
+        obj = f.read()
+    made = {"chunked_many.hry": op.Mesh.from_ply(many).encode_chunked(1000).data,
+            "chunked_snapshots.hry": op.Mesh.from_ply(grid).encode_chunked(1000, 256).data,
+            "chunked_general.hry": op.Mesh.from_obj(obj, os.path.join(g, "obj")).encode_chunked(512).data}
+    out = []
+    for name, data in made.items():
+        assert data[4:6] == bytes([0, 2])
+        out.append(str(tmp_path / name))
+        with open(out[-1], "wb") as f:
+            f.write(data)
+    return out
 
 
 @pytest.mark.timeout(900)
