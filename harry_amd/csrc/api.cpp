@@ -78,7 +78,7 @@ int hry_ctx_timing(const hry_ctx *ctx, hry_timing *out)
 	*out = ctx->cx.timing;
 	return HRY_OK;
 }
-void *hry_ctx_stream(const hry_ctx *ctx) { return ctx ? (void*)ctx->cx.stream : nullptr; }
+void *hry_ctx_stream(const hry_ctx *ctx) { return ctx ? (void*)ctx->cx.stream.s : nullptr; }   // (there since the context exists)
 
 int hry_mesh_from_ply(const uint8_t *ply, size_t n, hry_mesh **out)
 {

@@ -97,7 +97,8 @@ struct EncodePipeline : WalkProgress {
 	std::mutex mu;
 	std::condition_variable cond_sender;
 	bool closing = false;
-	bool kernels_ok = false, registered[3] = { false, false, false };
+	bool kernels_ok = false;
+	HostRegistration registered[3];   // the walk's arrays: vertex order, face order, triangle counts
 	uint32_t n_sent = 0;
 
 	EncodePipeline(Context &c, const ListDesc &v, const ListDesc &f, uint32_t n_v, uint32_t n_f, uint32_t nv_dev, std::function<void()> ready, Clock::time_point origin)
@@ -105,8 +106,7 @@ struct EncodePipeline : WalkProgress {
 	~EncodePipeline()
 	{
 		{ std::lock_guard<std::mutex> g(mu); closing = true; } cond_sender.notify_all(); sender.join();
-		if (registered[0] || registered[1] || registered[2]) (void)hipStreamSynchronize(cx.pipe_stream);   // (an error path: no copy may still read the arrays)
-		unregister_arrays();
+		if (registered[0].p || registered[1].p || registered[2].p) cx.pipe_stream.wait();   // (an error path: no copy may still read the arrays; they are released behind this)
 	}
 	static bool wanted() { return !env_on("HRY_NO_ENCODE_PIPELINE"); }
 
@@ -122,7 +122,7 @@ struct EncodePipeline : WalkProgress {
 		off_pairs = at; off_a = off_pairs + kPairWords; off_b = off_a + elems; off_c = off_b + elems; slot_words = off_c + elems;
 		cx.h_pipe.ensure(slot_words * 4 * Context::kPipeSlots);
 		cx.d_pipe.ensure(slot_words * 4 * Context::kPipeSlots);
-		for (auto &ev : cx.pipe_slot_ev) if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+		for (Event &ev : cx.pipe_slot_ev) ev.get();   // (here, not on the sending thread)
 	}
 	uint32_t *host_slot(int i) const { return cx.h_pipe.as<uint32_t>() + (size_t)i * slot_words; }
 	uint32_t *dev_slot(int i) const { return cx.d_pipe.as<uint32_t>() + (size_t)i * slot_words; }
@@ -144,14 +144,9 @@ struct EncodePipeline : WalkProgress {
 		const size_t n[3] = { (size_t)vc * 4, (size_t)fc * 4, (size_t)fc * 4 };
 		bool ok = true;
 		for (int i = 0; i < 3 && ok; ++i)
-			if (p[i] && n[i]) { ok = hipHostRegister(const_cast<void*>(p[i]), n[i], hipHostRegisterPortable) == hipSuccess; registered[i] = ok; }
-		if (!ok) { (void)hipGetLastError(); unregister_arrays(); std::lock_guard<std::mutex> g(mu); direct_min = 0xffffffffu; }
+			if (p[i] && n[i]) ok = registered[i].pin(p[i], n[i]);
+		if (!ok) { for (HostRegistration &r : registered) r.release(); std::lock_guard<std::mutex> g(mu); direct_min = 0xffffffffu; }
 		if (trace_on()) fprintf(stderr, "[hry enc] %8.3f ms    pipeline: the walk's arrays %s\n", ms_since(t0), ok ? "registered" : "could not be registered: every run is gathered");
-	}
-	void unregister_arrays()
-	{
-		const void *p[3] = { ov, of, nt };
-		for (int i = 0; i < 3; ++i) if (registered[i]) { (void)hipHostUnregister(const_cast<void*>(p[i])); registered[i] = false; }
 	}
 
 	// what a list of runs asks of a slot: per table the runs and (gathered tables) the entries
@@ -259,7 +254,7 @@ struct EncodePipeline : WalkProgress {
 			{ std::lock_guard<std::mutex> g(mu); closing = true; if (open_slot >= 0) { slot[open_slot].state = CLOSED; open_slot = -1; } }
 			cond_sender.notify_all();
 			sender.join();
-			unregister_arrays();
+			for (HostRegistration &r : registered) r.release();
 			sender.rethrow();
 		}
 		HIP_OK(hipEventRecord(cx.pipe_ev, cx.pipe_stream));
@@ -562,7 +557,6 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		if (nvc == 0 || nvc >= (1ull << 32) || nfc >= (1ull << 32)) return;
 		int ndeg = 0;
 		for (uint8_t d : m.have_degree) ndeg += d ? 1 : 0;
-		if (!cx.pipe_stream) { HIP_OK(hipStreamCreateWithFlags(&cx.pipe_stream, hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&cx.pipe_ev, hipEventDisableTiming)); }
 		// (every allocation before the walk starts: hipMalloc waits for the device)
 		cx.d_order_v.ensure(std::max<size_t>((size_t)nvc * 4, 16));
 		cx.d_order_f.ensure(std::max<size_t>((size_t)nfc * 4, 16));

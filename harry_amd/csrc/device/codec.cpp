@@ -38,31 +38,15 @@ Context::Context(int dev) : device(dev)
 	// chain) must not queue behind the tens of thousands of attribute-stream workgroups on stream3
 	int prio_lo = 0, prio_hi = 0;
 	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-	HIP_OK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_hi));
-	for (auto &e : ev) HIP_OK(hipEventCreate(&e));
+	stream.create(prio_hi);
 }
+// every stream is drained before the members go: the buffers below are freed while nothing runs on them, whatever their order
 Context::~Context()
 {
 	(void)hipSetDevice(device);
-	if (stream) (void)hipStreamSynchronize(stream);
-	for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-	for (auto &e : slice_ev) if (e) (void)hipEventDestroy(e);
-	for (auto &e : chain_ev) if (e) (void)hipEventDestroy(e);
-	if (pipe_stream) { (void)hipStreamSynchronize(pipe_stream); (void)hipStreamDestroy(pipe_stream); }
-	if (pipe_ev) (void)hipEventDestroy(pipe_ev);
-	for (auto &e : pipe_slot_ev) if (e) (void)hipEventDestroy(e);
-	for (auto &e : stage_ev) if (e) (void)hipEventDestroy(e);
-	if (stream) (void)hipStreamDestroy(stream);
-	if (stream2) { (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }
-	if (stream3) { (void)hipStreamSynchronize(stream3); (void)hipStreamDestroy(stream3); }
-	for (auto &u : up_stream) if (u) { (void)hipStreamSynchronize(u); (void)hipStreamDestroy(u); }
-	for (auto &e : up_ev) if (e) (void)hipEventDestroy(e);
-	for (auto &e : ev_x) if (e) (void)hipEventDestroy(e);
-	if (ev_payload) (void)hipEventDestroy(ev_payload);
-	for (auto &e : attr_ev) if (e) (void)hipEventDestroy(e);
-	for (int g = 1; g < kAttrGroups; ++g) if (attr_stream[g]) { (void)hipStreamSynchronize(attr_stream[g]); (void)hipStreamDestroy(attr_stream[g]); }   // [0] is stream3
-	if (h_stage) (void)hipHostFree(h_stage);
-	if (h_down) (void)hipHostFree(h_down);
+	for (const Stream *st : { &stream, &stream2, &stream3, &pipe_stream }) st->wait();
+	for (const Stream &st : up_stream) st.wait();
+	for (const Stream &st : attr_more) st.wait();
 }
 void Context::stage_put(const char *name, const void *dptr, size_t bytes)
 {
@@ -166,11 +150,6 @@ void Context::make_resident(Mesh &m)
 	m.device_token = g_device_tokens.fetch_add(1, std::memory_order_relaxed);
 	resident_token = m.device_token;
 }
-void Context::ensure_second_stream()
-{
-	HIP_OK(hipSetDevice(device));
-	if (!stream2) HIP_OK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-}
 // what upload_mesh does besides the three copies
 void Context::adopt_conn(Mesh &m)
 {
@@ -238,7 +217,6 @@ void fetch_to_host(Context &cx, void *dst, const void *d_src, size_t bytes)
 		return;
 	}
 	cx.h_fetch.ensure(slot_bytes * kSlots);
-	for (auto &e : cx.stage_ev) if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 	const size_t n_chunks = (bytes + slot_bytes - 1) / slot_bytes;
 	std::mutex mu;
 	std::condition_variable cv;
@@ -531,7 +509,7 @@ void finish_stream(Context &cx, uint32_t ns, std::vector<uint8_t> &payload)
 		const uint32_t nsl = (ns + SL - 1) / SL;
 		const size_t slot = std::min<size_t>(ns, SL);
 		cx.h_rec.ensure(slot * kRing * sizeof(SymRec)); cx.h_r.ensure(slot * kRing * 8); cx.h_s.ensure(slot * kRing * 4);
-		while (cx.slice_ev.size() < kRing) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); cx.slice_ev.push_back(e); }
+		if (cx.slice_ev.size() < kRing) cx.slice_ev.resize(kRing);
 		SymRec *rec = cx.h_rec.as<SymRec>();
 		uint64_t *rr = cx.h_r.as<uint64_t>();
 		uint32_t *ss = cx.h_s.as<uint32_t>();

@@ -1,7 +1,5 @@
 // Device context of the codec: HIP device, one stream, grow-only workspace buffers, resident mesh.
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <chrono>
 #include <cstdio>
 #include <functional>
@@ -11,88 +9,48 @@
 
 #include "../host/host.hpp"
 #include "dev_types.hpp"
+#include "hip_handles.hpp"
 
 namespace hry {
-
-inline void hip_check(hipError_t e, const char *what)
-{
-	if (e != hipSuccess) throw Error(HRY_E_NODEVICE, std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
-#define HIP_OK(x) ::hry::hip_check((x), #x)
 
 typedef std::chrono::steady_clock Clock;
 inline double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 // HRY_TRACE's time line: ms since t0, after the prefix the file names (kMarkPrefix: "[hry enc]" for the encoder, "[hry]" for the decoder)
 #define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "%s %8.3f ms  %s\n", kMarkPrefix, ms_since(t0), what); } while (0)
 
-struct DevBuf {
-	void *p = nullptr;
-	size_t cap = 0;
-	DevBuf() = default;
-	DevBuf(const DevBuf&) = delete;
-	DevBuf &operator=(const DevBuf&) = delete;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	void ensure(size_t n)
-	{
-		if (n <= cap) return;
-		if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-		size_t want = n + n / 8 + 256;
-		HIP_OK(hipMalloc(&p, want));
-		cap = want;
-	}
-	template <typename T> T *as() const { return (T*)p; }
-};
-
-// pinned host memory, grow-only (persistent across calls: fresh pinned or pageable blocks cost a page fault per 4 KiB)
-struct PinBuf {
-	void *p = nullptr;
-	size_t cap = 0;
-	PinBuf() = default;
-	PinBuf(const PinBuf&) = delete;
-	PinBuf &operator=(const PinBuf&) = delete;
-	~PinBuf() { if (p) (void)hipHostFree(p); }
-	void ensure(size_t n)
-	{
-		if (n <= cap) return;
-		if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-		size_t want = n + n / 8 + 4096;
-		HIP_OK(hipHostMalloc(&p, want, hipHostMallocDefault));
-		cap = want;
-	}
-	template <typename T> T *as() const { return (T*)p; }
-};
-
 constexpr int kMaxLists = 16;   // attribute lists of one mesh kept in HBM (the OBJ reader creates at most 8)
 
 struct Context {
 	int device = 0;
-	hipStream_t stream = nullptr;
-	hipStream_t stream2 = nullptr;   // uploads and connectivity-only kernels of the pipelined decode (created on first use)
-	hipStream_t stream3 = nullptr;   // attribute streams' entropy decode, next to the connectivity streams' (created on first use)
+	// Streams and events own themselves (hip_handles.hpp) and, but for the main stream, are created when they are first used --
+	// by the thread that drives the context: a handle that a side thread uses is touched before that thread starts
+	Stream stream;    // (created with the context, at the highest priority)
+	Stream stream2;   // uploads and connectivity-only kernels of the pipelined decode
+	Stream stream3;   // attribute streams' entropy decode, next to the connectivity streams'
 	static constexpr int kUploadStreams = 2;
-	hipStream_t up_stream[kUploadStreams] = {};   // further uploaders of finished spans beside stream2 (unchunk.cpp: SpanUploader; created on first use)
-	hipEvent_t up_ev[kUploadStreams] = {};
-	hipEvent_t ev_x[2] = {};         // cross-stream ordering events (created with stream3)
-	hipEvent_t ev_payload = nullptr; // chunked decode: the attribute streams' part of a large payload is on the device (created with stream3)
+	Stream up_stream[kUploadStreams];   // further uploaders of finished spans beside stream2 (unchunk.cpp: SpanUploader)
+	Event up_ev[kUploadStreams];
+	Event ev_x[2];                   // cross-stream ordering events
+	Event ev_payload;                // chunked decode: the attribute streams' part of a large payload is on the device
 	// chunked decode: the attribute streams are launched in groups by how far into their plane they end (unchunk.cpp); group g
-	// runs on attr_stream[g] and raises attr_ev[g]
+	// runs on attr_stream(g) -- stream3 for the first group -- and raises attr_ev[g]
 	static constexpr int kAttrGroups = 3;   // (+ the codec's three streams: more streams than hardware queues serialise)
-	hipStream_t attr_stream[kAttrGroups] = {};
-	hipEvent_t attr_ev[kAttrGroups] = {};
-	void *h_down = nullptr;          // pinned landing buffer for the vertex records of the pipelined decode (device -> host per slice)
-	size_t h_down_cap = 0;
+	Stream attr_more[kAttrGroups - 1];
+	hipStream_t attr_stream(int g) { return g ? attr_more[g - 1].get() : stream3.get(); }
+	Event attr_ev[kAttrGroups];
+	PinBuf h_down;                   // pinned landing buffer for the vertex records of the pipelined decode (device -> host per slice)
 	PinBuf h_mirror;                 // pipelined decode with border snapshots: pinned copies of the helper threads' stretches (face offsets, origins, twins, decode order), made by the helpers themselves
-	void *h_stage = nullptr;         // pinned staging memory for uploads that run next to a busy host thread (copies from
-	size_t h_stage_cap = 0;          // pageable memory make the runtime pin and unpin pages: TLB shootdowns for every thread)
-	hipStream_t pipe_stream = nullptr;   // chunked encode: what finished groups of a walk on several threads have coded goes to the planes beside the walk (chunked.cpp: EncodePipeline; created on first use)
-	hipEvent_t pipe_ev = nullptr;
+	PinBuf h_stage;                  // pinned staging memory for uploads that run next to a busy host thread (copies from pageable
+	                                 // memory make the runtime pin and unpin pages: TLB shootdowns for every thread; unchunk.cpp: Stager)
+	Stream pipe_stream;              // chunked encode: what finished groups of a walk on several threads have coded goes to the planes beside the walk (chunked.cpp: EncodePipeline)
+	Event pipe_ev;
 	static constexpr int kPipeSlots = 3;
-	hipEvent_t pipe_slot_ev[kPipeSlots] = {};   // a slot of h_pipe / d_pipe is free again
-	hipEvent_t ev[8] = {};
+	Event pipe_slot_ev[kPipeSlots];   // a slot of h_pipe / d_pipe is free again
+	TimedEvent ev[8];
 	// the float chains of a large mesh run in batches (unchunk.cpp: ChainBatches): a pair of timing events around every batch's
-	// launches, so that hry_timing.k_chain_ms is the sum over the batches of a decode (created on first use)
+	// launches, so that hry_timing.k_chain_ms is the sum over the batches of a decode
 	static constexpr int kChainBatchEvents = 16;
-	hipEvent_t chain_ev[2 * kChainBatchEvents] = {};
+	TimedEvent chain_ev[2 * kChainBatchEvents];
 	hry_timing timing{};
 
 	// resident mesh (hry_mesh_upload): attribute records and connectivity stay in HBM across encodes
@@ -129,12 +87,12 @@ struct Context {
 	bool device_recurrence = false; // HRY_FLAG_DEVICE_RECURRENCE: k_rchain instead of the host core
 	PinBuf h_pipe;                  // chunked encode: the pipeline's staging slots (run tables + the runs' entries, gathered)
 	PinBuf h_fetch;                 // large results on their way down: a ring of pinned slots (fetch_to_host, codec.cpp)
-	hipEvent_t stage_ev[8] = {};    // ... and an event per slot
+	Event stage_ev[8];              // ... and an event per slot
 	PinBuf h_gen;                   // general bindings: the events' arena on its way up (general.cpp)
 	PinBuf h_small;                 // a few words that come down asynchronously (a copy into pageable memory keeps its caller until it has happened)
 	PinBuf h_conn;                  // chunked decode: the connectivity planes, down for the host's replay
 	PinBuf h_rec, h_r, h_s;         // compat: symbol records down, (r, S) up, slice by slice (codec.cpp finish_stream)
-	std::vector<hipEvent_t> slice_ev;
+	std::vector<Event> slice_ev;
 	std::map<std::string, std::vector<uint8_t>> stages;
 
 	explicit Context(int dev);
@@ -149,7 +107,6 @@ struct Context {
 	// device (twins.hip; hubs on the host, from m's host arrays) into d_twin and m.twin
 	void match_twins(Mesh &m);
 	void make_resident(Mesh &m);     // m and this context share a new token (drawn from one counter of the process): m is resident here
-	void ensure_second_stream();
 	dev::ConnView conn_view() const;
 	float elapsed(int a, int b);
 };

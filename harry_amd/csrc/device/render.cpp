@@ -185,9 +185,7 @@ void render_build(Context &cx, const Mesh &m, RenderResult &out)
 	put(w_small, small.data(), small.size() * 4);
 	const int32_t *d_small = W.ptr<int32_t>(wb, w_small);
 
-	hipEvent_t ev[4] = {};
-	struct Events { hipEvent_t *e; ~Events() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ ev };
-	for (hipEvent_t &e : ev) HIP_OK(hipEventCreate(&e));
+	TimedEvent ev[4];
 
 	// ---- unweld: the number of output vertices comes down before the outputs are allocated (no corners: none).  The events
 	// enclose kernels only: the table's fill and every copy lie outside them

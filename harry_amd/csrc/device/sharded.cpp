@@ -314,7 +314,7 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 			// until it is staged -- 126 ms per shard of the configs[3] mesh with eight workers on one link -- and the walk does not
 			// need the device; the main stream waits for the event before the kernels of this shard, see encode_chunked)
 			const size_t st0 = (size_t)m.lists[0].stride(), st1 = (size_t)m.lists[1].stride();
-			cx.ensure_second_stream();
+			const hipStream_t us = cx.stream2;   // (created here, not on the uploader's thread)
 			// quantisation of the records happens on the device, over the same intervals, behind the copies; the skeleton announces it
 			struct ListPlan { int l; size_t stride; dev::RequantPlan plan; };
 			std::vector<ListPlan> rplans;
@@ -333,7 +333,6 @@ static void encode_sharded_in_place(Context *const *cxs, int n_ctx, Mesh &m, con
 			if (!shares0) uploader.spawn([&] {
 				const auto tu = Clock::now();
 				HIP_OK(hipSetDevice(cx.device));
-				hipStream_t us = cx.stream2;
 				// (the twins go up while this worker's and the others' walks repair some of them in the host array: whichever value
 				// a repaired entry arrives with, every repaired entry is sent again as a (half-edge, twin) pair once its group is
 				// walked -- by the encode's pipeline, or by upload_repaired_twins(patches_only) -- and both wait for these copies)

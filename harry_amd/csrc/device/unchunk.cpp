@@ -112,10 +112,7 @@ struct ChainBatches {
 		const ConnView cv = cx.conn_view();
 		launch_slice_prepare(st, cv, cx.d_order_v.as<uint32_t>(), nvc, v_done, v_end, d_cand, d_ncand, nullptr);
 		const bool timed = n_timed < Context::kChainBatchEvents;
-		if (timed) {
-			for (int k = 0; k < 2; ++k) if (!cx.chain_ev[2 * n_timed + k]) HIP_OK(hipEventCreate(&cx.chain_ev[2 * n_timed + k]));
-			HIP_OK(hipEventRecord(cx.chain_ev[2 * n_timed], st));
-		}
+		if (timed) HIP_OK(hipEventRecord(cx.chain_ev[2 * n_timed], st));
 		for (uint32_t done = 0; done < n_lists; done += 65535)   // a launch holds at most 65535 x 8 lists' worth of workgroups
 			launch_unpredict2(st, cv, cx.d_order_v.as<uint32_t>(), nvc, d_cand, d_ncand, nullptr, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>(),
 			                  d_lists, d_off + lists_done + done, std::min(65535u, n_lists - done), d_segstart, ncomp_max, d_flags);
@@ -186,7 +183,7 @@ static void reconstruct_attributes(Context &cx, Mesh &mesh, const OrderVec &orde
 		chain_timed = true;
 		// the records of the batches that ran beside the replay come down while the last batch runs (their chains are done
 		// when the event behind them is reached; vertex v's record is record v: vertex ids are handed out in decode order)
-		if (batches->first_done && cx.stream3 && batches->v_first_batch && !m->lists[1].data.empty()) {
+		if (batches->first_done && cx.stream3.made() && batches->v_first_batch && !m->lists[1].data.empty()) {
 			const size_t bytes = (size_t)batches->v_first_batch * m->lists[1].stride();
 			HIP_OK(hipStreamWaitEvent(cx.stream3, batches->first_done, 0));
 			HIP_OK(hipMemcpyAsync(m->lists[1].data.data(), cx.d_rec[1].p, bytes, hipMemcpyDeviceToHost, cx.stream3));
@@ -268,31 +265,24 @@ static void reconstruct_attributes(Context &cx, Mesh &mesh, const OrderVec &orde
 // When the replay ends only the last slice is left.  Results are those of the sequential pipeline: the candidates of a
 // complete vertex are final, and the chain is evaluated in the same order with the same arithmetic.
 // ---------------------------------------------------------------------------------------------------------
-struct SliceClock { hipEvent_t a, b, p0, p1; };   // chain on the main stream; candidates + chain records on the second one
+struct SliceClock { TimedEvent a, b, p0, p1; };   // chain on the main stream; candidates + chain records on the second one
 // host -> device through the context's pinned staging buffer (one stream; flush() = everything has left the buffer)
 struct Stager {
 	Context &cx;
 	hipStream_t st;
+	static constexpr size_t kRing = 16u << 20;   // what is staged between two flushes (the buffer itself may be larger)
 	size_t used = 0;
-	Stager(Context &c, hipStream_t s) : cx(c), st(s)
-	{
-		const size_t want = 16u << 20;
-		if (cx.h_stage_cap < want) {
-			if (cx.h_stage) { (void)hipHostFree(cx.h_stage); cx.h_stage = nullptr; cx.h_stage_cap = 0; }
-			HIP_OK(hipHostMalloc(&cx.h_stage, want, hipHostMallocDefault));
-			cx.h_stage_cap = want;
-		}
-	}
+	Stager(Context &c, hipStream_t s) : cx(c), st(s) { cx.h_stage.ensure(kRing); }
 	void flush() { HIP_OK(hipStreamSynchronize(st)); used = 0; }
 	void put(void *dst, const void *src, size_t n)
 	{
 		const uint8_t *s = (const uint8_t*)src;
 		uint8_t *d = (uint8_t*)dst;
 		while (n) {
-			if (used == cx.h_stage_cap) flush();
-			const size_t k = std::min(n, cx.h_stage_cap - used);
-			memcpy((uint8_t*)cx.h_stage + used, s, k);
-			HIP_OK(hipMemcpyAsync(d, (uint8_t*)cx.h_stage + used, k, hipMemcpyHostToDevice, st));
+			if (used == kRing) flush();
+			const size_t k = std::min(n, kRing - used);
+			memcpy(cx.h_stage.as<uint8_t>() + used, s, k);
+			HIP_OK(hipMemcpyAsync(d, cx.h_stage.as<uint8_t>() + used, k, hipMemcpyHostToDevice, st));
 			used += k; s += k; d += k; n -= k;
 		}
 	}
@@ -331,7 +321,6 @@ struct SpanUploader : SpanDone {
 	SideThreads workers;                   // (last: joined before anything above goes)
 	SpanUploader(Context &c, Mesh &mesh, const OrderVec &ov, ChainBatches *cb = nullptr, hipEvent_t planes = nullptr) : cx(c), m(mesh), order_v(ov), batches(cb), planes_ready(planes)
 	{
-		cx.ensure_second_stream();
 		cx.d_org.ensure(std::max<size_t>((size_t)m.declared_ne * 4, 16));
 		cx.d_twin.ensure(std::max<size_t>((size_t)m.declared_ne * 4, 16));
 		cx.d_foff.ensure(((size_t)m.nf + 1) * 4);
@@ -349,9 +338,8 @@ struct SpanUploader : SpanDone {
 		}
 		up_stream[0] = cx.stream2;
 		for (int k = 1; k < kWorkers; ++k) {
-			if (!cx.up_stream[k - 1]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[k - 1], hipStreamNonBlocking));
-			if (!cx.up_ev[k - 1]) HIP_OK(hipEventCreateWithFlags(&cx.up_ev[k - 1], hipEventDisableTiming));
 			up_stream[k] = cx.up_stream[k - 1];
+			cx.up_ev[k - 1].get();   // (here, not on a worker's thread)
 		}
 		const void *node = callers_node_cpus();
 		HRY_MARK(t_origin, "span uploaders' arrays and streams ready");
@@ -455,11 +443,11 @@ struct SpanUploader : SpanDone {
 					if (todo.empty()) break;
 					r = std::move(todo.back()); todo.pop_back();
 				}
-				copy_range(r, cx.stream3 ? cx.stream3 : cx.stream2);
+				copy_range(r, cx.stream3.made() ? cx.stream3 : cx.stream2);
 				std::lock_guard<std::mutex> g(mu);
 				faces_up += r.f1 - r.f0; he_up += r.h1 - r.h0; v_up += r.v1 - r.v0;
 			}
-			if (cx.stream3) HIP_OK(hipStreamSynchronize(cx.stream3));
+			if (cx.stream3.made()) HIP_OK(hipStreamSynchronize(cx.stream3));
 		}
 		workers.join();
 		if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  every span is on the device\n", ms_since(t_origin));
@@ -501,7 +489,6 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 {
 	Mesh *m = &mesh;
 	const uint32_t nv = m->nv, nf = m->nf, ne = m->declared_ne;
-	if (!cx.stream2) HIP_OK(hipStreamCreateWithFlags(&cx.stream2, hipStreamNonBlocking));
 	HRY_MARK(g_t0, "pipelined decode: begin");
 	// device arrays at their final size; records start as zeros (host records are zero-filled by the header reader)
 	for (int l = 0; l < 2; ++l) {
@@ -552,17 +539,18 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	const Clock::time_point t_begin = g_t0;
 	// vertex records come back slice by slice into pinned memory and are copied into the mesh by the consumer as they land
 	const size_t vrec_bytes = m->lists[1].data.size();
-	if (cx.h_down_cap < vrec_bytes) {
-		if (cx.h_down) { (void)hipHostFree(cx.h_down); cx.h_down = nullptr; cx.h_down_cap = 0; }
-		HIP_OK(hipHostMalloc(&cx.h_down, vrec_bytes + (vrec_bytes >> 3) + 4096, hipHostMallocDefault));
-		cx.h_down_cap = vrec_bytes + (vrec_bytes >> 3) + 4096;
-	}
+	cx.h_down.ensure(vrec_bytes);
 	cx.d_patch.ensure(std::max<size_t>(4u << 20, (size_t)nv));   // late twin links of a slice: (edge, twin) pairs, a few thousand per slice
-	struct Landing { hipEvent_t ev; size_t off, len; };
+	struct Landing { Event ev; size_t off, len; };
 	std::deque<Landing> landing;
 	const int vstride = ldv.stride;
 	const void *near = callers_neighbour_cpus();   // the consumer polls: near the replay's caches, but not on its core
 	const void *node = near ? near : callers_node_cpus();
+	// the helpers' pinned copies go up on a stream of their own -- on the uploads' stream (stream2) the candidates of the next
+	// slice of the FIRST stretch sat behind a millisecond of the other stretches' transfers -- with an event each, which
+	// stream2 waits for when a publication reaches into them.  (Both streams are the consumer's; a first decode creates them here)
+	const hipStream_t mir_stream = cx.up_stream[0];
+	const hipStream_t down_stream = cx.up_stream[1];   // the slices' records on their way down
 	SideThreads consumer;
 	consumer.spawn([&, node] {
 		stay_on_node(node);
@@ -571,20 +559,11 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 		uint64_t seen_seq = 0, seen_pub = 0;
 		std::vector<uint32_t> patches;
 		std::vector<ReplayLive::Range> ranges, ranges_up;   // stretches of helper threads: announced / on the device (round 6)
-		// the helpers' pinned copies go up on a stream of their own -- on the uploads' stream (stream2) the candidates of the next
-		// slice of the FIRST stretch sat behind a millisecond of the other stretches' transfers -- with an event each, which
-		// stream2 waits for when a publication reaches into them
-		std::vector<hipEvent_t> mir_ev;        // per entry of ranges_up (nullptr: came through stream2)
+		std::vector<Event> mir_ev;             // per entry of ranges_up (never made: came through stream2)
 		std::vector<char> mir_waited;          // per entry of mir_ev: the second stream waits for it already
-		if (!cx.up_stream[0]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[0], hipStreamNonBlocking));
-		const hipStream_t mir_stream = cx.up_stream[0];
-		if (!cx.up_stream[1]) HIP_OK(hipStreamCreateWithFlags(&cx.up_stream[1], hipStreamNonBlocking));
-		const hipStream_t down_stream = cx.up_stream[1];   // the slices' records on their way down
-		struct DropEvents { std::vector<hipEvent_t> &v; ~DropEvents() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } drop_events{ mir_ev };
 		DevBuf &d_patch = cx.d_patch;   // persistent and sized before the pipeline starts: growing it here would synchronise the device (hipFree / hipMalloc) in mid-flight
 		Stager up(cx, cx.stream2);
-		hipEvent_t prepared;
-		HIP_OK(hipEventCreateWithFlags(&prepared, hipEventDisableTiming));
+		Event prepared;
 		// The consumer acts on a publication only when `lag` newer ones exist: the newest part of the arrays is still hot
 		// in the replay thread's cache (twins of the last ring keep changing), copying it there would slow the replay down.
 		std::deque<ReplayLive::Pub> hist;
@@ -594,9 +573,8 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				Landing &L = landing.front();
 				if (wait) HIP_OK(hipEventSynchronize(L.ev));
 				else if (hipEventQuery(L.ev) != hipSuccess) break;
-				memcpy(m->lists[1].data.data() + L.off, (const uint8_t*)cx.h_down + L.off, L.len);
+				memcpy(m->lists[1].data.data() + L.off, cx.h_down.as<uint8_t>() + L.off, L.len);
 				if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  records of vertices [%zu, %zu) landed\n", ms_since(t_begin), L.off / vstride, (L.off + L.len) / vstride);
-				(void)hipEventDestroy(L.ev);
 				landing.pop_front();
 			}
 		};
@@ -620,7 +598,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			if (newest.failed) break;
 			// a helper thread's finished stretch goes up at once (nobody is writing there any more)
 			for (const ReplayLive::Range &r : ranges) {
-				hipEvent_t rev = nullptr;
+				Event rev;
 				if (r.mirrored) {   // (the helper left a pinned copy: four transfers, no copy on this thread)
 					const uint32_t *mf = cx.h_mirror.as<uint32_t>(), *mo = mf + (size_t)nf + 1, *mt = mo + ne, *mv = mt + ne;
 					// one kernel reads the four ranges from the pinned mirrors
@@ -630,7 +608,6 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 					pr.dst[2] = cx.d_twin.as<uint32_t>() + r.h0; pr.src[2] = mt + r.h0; pr.words[2] = r.h1 - r.h0;
 					pr.dst[3] = cx.d_order_v.as<uint32_t>() + r.v0; pr.src[3] = mv + r.v0; pr.words[3] = r.v1 - r.v0;
 					launch_pull_ranges(mir_stream, pr);
-					HIP_OK(hipEventCreateWithFlags(&rev, hipEventDisableTiming));
 					HIP_OK(hipEventRecord(rev, mir_stream));
 				} else {
 				if (r.f1 > r.f0) up.put(cx.d_foff.as<uint32_t>() + r.f0 + 1, m->face_off.data() + r.f0 + 1, ((size_t)r.f1 - r.f0) * 4);
@@ -642,7 +619,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				}
 				if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  a helper's stretch (faces %u .. %u) is on its way up\n", ms_since(t_begin), r.f0, r.f1);
 				ranges_up.push_back(r);
-				mir_ev.push_back(rev);
+				mir_ev.push_back(std::move(rev));
 			}
 			ranges.clear();
 			if (newest.n_pub == seen_pub) continue;   // (a helper's announcement only: no new publication of the replaying thread)
@@ -658,7 +635,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			if (P.joined || P.done) {
 				mir_waited.resize(mir_ev.size(), 0);
 				for (size_t i = 0; i < mir_ev.size(); ++i)
-					if (!mir_waited[i] && mir_ev[i] && (P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
+					if (!mir_waited[i] && mir_ev[i].made() && (P.done || ranges_up[i].f0 < P.faces)) { HIP_OK(hipStreamWaitEvent(cx.stream2, mir_ev[i], 0)); mir_waited[i] = 1; }
 			}
 			// finished part of the connectivity -- but for what the helpers' stretches have brought up already
 			if (P.faces > f_up) {
@@ -712,8 +689,8 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 				const uint32_t piece = (P.done || P.joined) && v_hi - v_done > 3 * last_piece ? last_piece : v_hi - v_done;
 				for (uint32_t v_lo = v_done; v_lo < v_hi;) {
 					const uint32_t v_to = v_hi - v_lo <= piece + piece / 2 ? v_hi : v_lo + piece;
-					SliceClock ck;
-					HIP_OK(hipEventCreate(&ck.a)); HIP_OK(hipEventCreate(&ck.b)); HIP_OK(hipEventCreate(&ck.p0)); HIP_OK(hipEventCreate(&ck.p1));
+					clocks.emplace_back();
+					SliceClock &ck = clocks.back();
 					HIP_OK(hipEventRecord(ck.p0, cx.stream2));
 					launch_slice_prepare(cx.stream2, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec);
 					HIP_OK(hipEventRecord(ck.p1, cx.stream2));
@@ -724,17 +701,15 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 					HIP_OK(hipEventRecord(ck.a, cx.stream));
 					launch_slice_chain(cx.stream, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>());
 					HIP_OK(hipEventRecord(ck.b, cx.stream));
-					clocks.push_back(ck);
 					{
 						// (the records come down on a stream of their own, behind the slice's chain: on the chain's stream the next
 						// slice's chain waited for the copy -- 0.1 ms a slice, 30 ms of the 28 M-triangle mesh's 214 slices)
 						Landing L;
 						L.off = (size_t)v_lo * vstride; L.len = ((size_t)v_to - v_lo) * vstride;
 						HIP_OK(hipStreamWaitEvent(down_stream, ck.b, 0));
-						HIP_OK(hipMemcpyAsync((uint8_t*)cx.h_down + L.off, cx.d_rec[1].as<uint8_t>() + L.off, L.len, hipMemcpyDeviceToHost, down_stream));
-						HIP_OK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
+						HIP_OK(hipMemcpyAsync(cx.h_down.as<uint8_t>() + L.off, cx.d_rec[1].as<uint8_t>() + L.off, L.len, hipMemcpyDeviceToHost, down_stream));
 						HIP_OK(hipEventRecord(L.ev, down_stream));
-						landing.push_back(L);
+						landing.push_back(std::move(L));
 					}
 					if (trace_on()) fprintf(stderr, "[hry] %8.3f ms  slice [%u, %u) enqueued (replay at face %u)\n", ms_since(t_begin), v_lo, v_to, newest.faces);
 					v_lo = v_to;
@@ -746,7 +721,6 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 		}
 		up.flush();
 		drain(true);
-		(void)hipEventDestroy(prepared);
 	});
 
 	// ---- the replay itself (this thread)
@@ -797,13 +771,10 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	HRY_MARK(g_t0, "replay done");
 	if (trace_on()) fprintf(stderr, "[hry] %u publications, %.3f ms inside publish()\n", live.n_publish, live.t_publish_ms);
 	consumer.join();
-	auto drop_clocks = [&] { for (auto &c : clocks) { (void)hipEventDestroy(c.a); (void)hipEventDestroy(c.b); (void)hipEventDestroy(c.p0); (void)hipEventDestroy(c.p1); } };
 	if (const std::exception_ptr failed = replay_error ? replay_error : consumer.error()) {
 		(void)hipStreamSynchronize(cx.stream); (void)hipStreamSynchronize(cx.stream2);
-		for (auto &u : cx.up_stream) if (u) (void)hipStreamSynchronize(u);
-		drop_clocks();
-		for (auto &L : landing) (void)hipEventDestroy(L.ev);
-		std::rethrow_exception(failed);
+		for (const Stream &u : cx.up_stream) u.wait();
+		std::rethrow_exception(failed);   // (the slices' events go with `clocks` and `landing`, behind these waits)
 	}
 	order_v.resize(cur.next_id);
 	for (; attr_waited < Context::kAttrGroups; ++attr_waited) HIP_OK(hipStreamWaitEvent(cx.stream, cx.attr_ev[attr_waited], 0));
@@ -814,7 +785,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	if (!m->lists[0].data.empty()) HIP_OK(hipMemcpyAsync(m->lists[0].data.data(), cx.d_rec[0].p, m->lists[0].data.size(), hipMemcpyDeviceToHost, cx.stream));
 	HIP_OK(hipStreamSynchronize(cx.stream));
 	HRY_MARK(g_t0, "records on the host");
-	if (uint32_t tf = chain_timeout_flags(cx.stream)) { drop_clocks(); throw Error(HRY_E_INTERNAL, "reconstruction chain: hand-over between wavefronts timed out (flags " + std::to_string(tf) + ")"); }
+	if (uint32_t tf = chain_timeout_flags(cx.stream)) throw Error(HRY_E_INTERNAL, "reconstruction chain: hand-over between wavefronts timed out (flags " + std::to_string(tf) + ")");
 	double chain_ms = 0, prep_ms = 0;
 	(void)hipStreamSynchronize(cx.stream2);
 	for (auto &c : clocks) {
@@ -829,7 +800,6 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 			fprintf(stderr, "[hry]   on the device: a slice's candidates %.3f .. %.3f ms, its chain %.3f .. %.3f ms after the connectivity kernel's start\n", p0, p1, a, b);
 		}
 	}
-	drop_clocks();
 	cx.timing.k_chain_ms = chain_ms;
 	cx.timing.k_predict_ms = prep_ms + chain_ms;   // candidates, chain records (second stream, beside the chain of the slice before) + the chain
 	if (cx.keep_stages) {
@@ -923,14 +893,6 @@ static void upload_streams(Context &cx, const ChunkedDirectory &dir, const uint8
 static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, const StreamPlan &sp, const uint8_t *payload, PlaneView *conn)
 {
 	const uint64_t payload_bytes = dir.stream_off[dir.stream_bytes.size()];
-	if (!cx.stream3) {
-		HIP_OK(hipStreamCreateWithFlags(&cx.stream3, hipStreamNonBlocking));
-		for (auto &e : cx.ev_x) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		cx.attr_stream[0] = cx.stream3;
-		for (int g = 1; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamCreateWithFlags(&cx.attr_stream[g], hipStreamNonBlocking));
-		for (auto &e : cx.attr_ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		HIP_OK(hipEventCreateWithFlags(&cx.ev_payload, hipEventDisableTiming));
-	}
 	HIP_OK(hipEventRecord(cx.ev[1], cx.stream));
 	// A launch takes the lane-per-stream kernel for the streams it can where that is the faster of the two (HRY_DECODE_LANES: 0
 	// never, 1 always, unset: whichever is faster).  Measured on MI355X: a wavefront alone on its SIMD issues an instruction every ~5.5 cycles, so a lane-per-
@@ -985,10 +947,9 @@ static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, 
 	// planes took 20 ms instead of 5, in front of the replay
 	const hipEvent_t attr_after = cx.ev_x[1];
 	if (sp.split_upload) {   // the rest of the payload, beside the connectivity streams' kernel (on the uploads' stream)
-		cx.ensure_second_stream();
 		HIP_OK(hipMemcpyAsync(cx.d_cout.as<uint8_t>() + sp.conn_bytes, payload + sp.conn_bytes, payload_bytes - sp.conn_bytes, hipMemcpyHostToDevice, cx.stream2));
 		HIP_OK(hipEventRecord(cx.ev_payload, cx.stream2));
-		for (int g = 0; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamWaitEvent(cx.attr_stream[g], cx.ev_payload, 0));
+		for (int g = 0; g < Context::kAttrGroups; ++g) HIP_OK(hipStreamWaitEvent(cx.attr_stream(g), cx.ev_payload, 0));
 		HRY_MARK(g_t0, "attribute streams on the device");
 	}
 	HIP_OK(hipStreamWaitEvent(cx.stream3, attr_after, 0));
@@ -996,7 +957,7 @@ static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, 
 	{
 		uint32_t first = sp.n_conn_streams;
 		for (int g = 0; g < Context::kAttrGroups; ++g) {
-			hipStream_t st = cx.attr_stream[g];
+			hipStream_t st = cx.attr_stream(g);
 			if (g) HIP_OK(hipStreamWaitEvent(st, attr_after, 0));
 			decode_streams(st, first, sp.group_n[g], sp.group_lanes_n[g]);
 			HIP_OK(hipEventRecord(cx.attr_ev[g], st));

@@ -1,0 +1,142 @@
+// The contract of harry_amd/csrc/device/hip_handles.hpp, against a counting stand-in for the runtime (fake_hip/), under
+// AddressSanitizer / UBSan.  These are the paths a device error takes: no test provokes one on a device.
+// Built and run by tests/test_hip_handles_cpu.py.  Prints "ok" and exits 0 when every check holds.
+#include <cstdio>
+#include <deque>
+#include <utility>
+#include <vector>
+
+#include "../../harry_amd/csrc/device/hip_handles.hpp"
+
+using namespace hry;
+using fake_hip::calls;
+using fake_hip::count;
+
+static int failures = 0;
+static void check(bool ok, const char *what)
+{
+	if (!ok) { fprintf(stderr, "FAILED: %s (calls so far: \"%s\")\n", what, calls.c_str()); ++failures; }
+}
+template <typename F> static bool throws_error(F &&f)
+{
+	try { f(); } catch (const Error &e) { return e.code == HRY_E_NODEVICE; }
+	return false;
+}
+// what decode_streams_conn_first used to build behind one guard: a stream, two ordering events, two more streams, three events
+struct Group { Stream first; Event order[2]; Stream more[2]; Event done[3]; };
+static void use(hipStream_t) {}
+static void use(hipEvent_t) {}
+
+int main()
+{
+	{   // nothing is created until first use; one creation however often it is used; one destroy; a stream is waited for first
+		{
+			Stream s; Event e; TimedEvent t; Group g;
+			check(calls.empty() && !s.made() && !e.made() && !t.made(), "nothing is created until first use");
+			s.wait();
+			check(calls.empty(), "waiting for a stream that was never used does nothing");
+			use(s); use(s); use(e); use(e); use(t); use(t);
+			check(calls == "set" && s.made() && e.made() && t.made(), "each handle is created once, events with their own flag");
+			hipStream_t raw = s;
+			check(raw == s.s && raw == s.get(), "the owner stands for its handle");
+		}
+		check(calls == "setyySx", "each handle is destroyed once, a stream after it was synchronised");
+	}
+	calls.clear();
+	{   // the main stream: created at once, with its priority
+		Stream s;
+		s.create(-3);
+		use(s);
+		check(calls == "s" && fake_hip::last_priority == -3, "create(priority) makes the stream, a later use does not make another");
+	}
+	check(calls == "sSx", "the stream's destructor synchronises before it destroys");
+	calls.clear();
+	{   // a moved-from handle destroys nothing; containers of owners move them
+		{
+			Event a;
+			use(a);
+			Event b(std::move(a));
+			check(!a.made() && b.made(), "a move empties its source");
+			Stream s;
+			use(s);
+			Stream s2(std::move(s));
+			check(!s.made() && s2.made(), "a move empties its source (stream)");
+		}
+		check(calls == "esSxy", "a moved-from handle destroys nothing");
+		calls.clear();
+		{
+			std::vector<Event> v;
+			for (int i = 0; i < 9; ++i) { Event e; if (i % 3) use(e); v.push_back(std::move(e)); }   // (grows several times)
+			std::deque<TimedEvent> d;
+			for (int i = 0; i < 5; ++i) { d.emplace_back(); use(d.back()); }
+			d.pop_front();
+			check(count('e') == 6 && count('t') == 5 && count('y') == 1 && v[0].made() == false && v[1].made(), "owners in containers: created where used, destroyed with their element");
+			v.resize(12);
+			check(count('e') == 6, "a resize creates nothing");
+		}
+		check(count('y') == 11, "a container destroys exactly what was created");
+	}
+	calls.clear();
+	{   // a failed creation throws Error, leaves the owner empty, and the next use tries again
+		{
+			Stream s; Event e;
+			fake_hip::fail_in = 1;
+			check(throws_error([&] { use(s); }) && !s.made(), "a failed stream creation throws and leaves the owner empty");
+			fake_hip::fail_in = 1;
+			check(throws_error([&] { use(e); }) && !e.made(), "a failed event creation throws and leaves the owner empty");
+			check(calls.empty(), "nothing was created");
+			use(s); use(e);
+			check(calls == "se" && s.made() && e.made(), "a later use retries the creation");
+			Stream p;
+			fake_hip::fail_in = 1;
+			check(throws_error([&] { p.create(0); }) && !p.made(), "a failed create(priority) leaves the owner empty");
+		}
+		check(calls == "seySx", "what the retries created is destroyed once");
+	}
+	calls.clear();
+	{   // a group in which one creation fails destroys exactly what was created -- and is whole after the next use
+		{
+			Group g;
+			fake_hip::fail_in = 4;   // first, order[0], order[1] succeed; more[0] fails
+			check(throws_error([&] { use(g.first); for (Event &e : g.order) use(e); for (Stream &s : g.more) use(s); for (Event &e : g.done) use(e); }), "the failing creation of a group throws");
+			check(calls == "see" && g.first.made() && g.order[1].made() && !g.more[0].made() && !g.more[1].made() && !g.done[0].made(), "the group holds what was created before the failure");
+			use(g.more[0]);
+			check(calls == "sees", "the handle whose creation failed is created by its next use: no half-built group for good");
+		}
+		check(count('x') == 2 && count('S') == 2 && count('y') == 2, "a group destroys exactly those that were created");
+	}
+	calls.clear();
+	{   // registered host ranges
+		int a[4], b[4], c[4];
+		{
+			HostRegistration r[3];
+			check(r[0].pin(a, sizeof a) && r[0].p == a, "a registration is kept");
+			fake_hip::fail_in = 1;
+			check(!r[1].pin(b, sizeof b) && r[1].p == nullptr, "a refused registration is a soft failure");
+			check(calls == "rg", "... whose error is cleared");
+			check(r[2].pin(c, sizeof c), "a registration is kept");
+			r[2].release(); r[2].release();
+			check(calls == "rgru", "release() unregisters once");
+		}
+		check(calls == "rgruu" && fake_hip::ranges.empty(), "the owner unregisters only what it registered");
+	}
+	calls.clear();
+	{   // device and pinned memory: grow-only, the old block freed first, everything freed at the end
+		{
+			DevBuf d; PinBuf p;
+			d.ensure(0); p.ensure(0);
+			check(calls.empty(), "no memory until some is asked for");
+			d.ensure(100); d.ensure(50); p.ensure(100); p.ensure(100);
+			check(calls == "mp" && d.cap >= 100 && p.cap >= 100, "one block each");
+			d.ensure(d.cap + 1); p.ensure(p.cap + 1);
+			check(calls == "mpfmqp", "growing frees the old block first");
+			fake_hip::fail_in = 1;
+			check(throws_error([&] { d.ensure(d.cap + 1); }) && d.p == nullptr && d.cap == 0, "a failed allocation leaves the buffer empty");
+		}
+		check(count('m') == count('f') && count('p') == count('q'), "every block is freed");
+	}
+	check(fake_hip::live.empty() && fake_hip::ranges.empty() && calls.find('!') == std::string::npos, "the counts balance at exit");
+	if (failures) return 1;
+	printf("ok\n");
+	return 0;
+}
