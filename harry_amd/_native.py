@@ -144,6 +144,7 @@ def load():
     L.hry_decode_sharded.argtypes = [C.POINTER(vp), C.c_int, vp, sz, C.POINTER(Opts), C.POINTER(vp), C.POINTER(ShardTiming)]
     L.hry_container_check.restype = C.c_int; L.hry_container_check.argtypes = [vp, sz, C.POINTER(C.c_int)]
     L.hry_render_build.restype = C.c_int; L.hry_render_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hry_render_build_ex.restype = C.c_int; L.hry_render_build_ex.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
     L.hry_render_nverts.restype = C.c_uint32; L.hry_render_nverts.argtypes = [vp]
     L.hry_render_ntris.restype = C.c_uint64; L.hry_render_ntris.argtypes = [vp]
     L.hry_render_get.restype = C.c_int

@@ -366,14 +366,24 @@ class Codec:
     RENDER_FIXED = ("indices", "tri_face", "vertex_source", "corner_source", "face_region")
     _RENDER_NP = {0: np.float32, 4: np.uint32, 6: np.uint16}
 
-    def _render(self, mesh: Mesh, fill) -> dict:
+    RENDER_VERTEX_NORMALS, RENDER_FACE_NORMALS, RENDER_ANGLE_WEIGHTED = 1, 2, 4
+    RENDER_NORMALS = ("normals", "face_normals")
+
+    @classmethod
+    def _render_flags(cls, normals, face_normals) -> int:
+        if normals not in (None, "area", "angle"):
+            raise ValueError('normals is one of None, "area", "angle"')
+        flags = 0 if normals is None else cls.RENDER_VERTEX_NORMALS | (cls.RENDER_ANGLE_WEIGHTED if normals == "angle" else 0)
+        return flags | (cls.RENDER_FACE_NORMALS if face_normals else 0)
+
+    def _render(self, mesh: Mesh, fill, flags: int = 0) -> dict:
         """build, hand every buffer to fill(name, rows, width, type, handle), free the handle"""
         L = nat.load()
         r = C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        nat.check(L.hry_render_build_ex(self.h, mesh.h, flags, C.byref(r)) if flags else L.hry_render_build(self.h, mesh.h, C.byref(r)))
         try:
             out = {}
-            for name in self.RENDER_FIXED + tuple(f"list{l}" for l in range(mesh.nlists)):
+            for name in self.RENDER_FIXED + tuple(f"list{l}" for l in range(mesh.nlists)) + (self.RENDER_NORMALS if flags else ()):
                 rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
                 nat.check(L.hry_render_get(r, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
                 if rows.value:
@@ -385,18 +395,20 @@ class Codec:
         finally:
             L.hry_render_free(r)
 
-    def render_numpy(self, mesh: Mesh) -> dict:
+    def render_numpy(self, mesh: Mesh, normals=None, face_normals: bool = False) -> dict:
         """the mesh as render-ready buffers (hry_render_build), copied to host arrays: indices u32 [T, 3], tri_face u32 [T],
-        vertex_source u32 [U], corner_source u32 [U] (unwelded meshes), face_region u16 [nf] (general bindings), list<l> f32 [rows, ncomp]"""
+        vertex_source u32 [U], corner_source u32 [U] (unwelded meshes), face_region u16 [nf] (general bindings), list<l> f32 [rows, ncomp].
+        normals "area" / "angle": also normals f32 [U, 3], computed on the device from the positions (hry_render_build_ex), weighted
+        by face area / corner angle; face_normals: also face_normals f32 [nf, 3]"""
         def fill(name, rows, width, typ, r):
-            a = np.empty((rows, width) if name == "indices" or name.startswith("list") else (rows,), self._RENDER_NP[typ])
+            a = np.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), self._RENDER_NP[typ])
             nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), a.ctypes.data, 0))
             return a
-        return self._render(mesh, fill)
+        return self._render(mesh, fill, self._render_flags(normals, face_normals))
 
-    def render(self, mesh: Mesh) -> dict:
+    def render(self, mesh: Mesh, normals=None, face_normals: bool = False) -> dict:
         """the same buffers as torch tensors on this codec's device, copied device to device: indices / tri_face / vertex_source /
-        corner_source int32, face_region int16, list<l> float32.  They stay valid after close()."""
+        corner_source int32, face_region int16, list<l> / normals / face_normals float32.  They stay valid after close()."""
         import torch   # only here: the rest of the package does not need torch
         dev = torch.device("cuda", self.device)
         dtypes = {0: torch.float32, 4: torch.int32, 6: torch.int16}
@@ -405,10 +417,10 @@ class Codec:
         torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
 
         def fill(name, rows, width, typ, r):
-            t = torch.empty((rows, width) if name == "indices" or name.startswith("list") else (rows,), dtype=dtypes[typ], device=dev)
+            t = torch.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), dtype=dtypes[typ], device=dev)
             nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), t.data_ptr(), 1))
             return t
-        return self._render(mesh, fill)
+        return self._render(mesh, fill, self._render_flags(normals, face_normals))
 
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):

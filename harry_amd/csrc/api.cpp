@@ -596,13 +596,14 @@ int hry_range_encode_lht(hry_ctx *ctx, const uint64_t *lht, size_t n, uint8_t **
 }
 
 // ---- render-ready device buffers (render.cpp)
-int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out)
+int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out) { return hry_render_build_ex(ctx, m, 0, out); }
+int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_render **out)
 {
 	if (!ctx || !m || !out) { g_last_error = "null argument"; if (out) *out = nullptr; return HRY_E_ARG; }
 	*out = nullptr;
 	return guarded([&] {
 		std::unique_ptr<hry_render> r(new hry_render());
-		render_build(ctx->cx, m->m, r->r);
+		render_build(ctx->cx, m->m, flags, r->r);
 		*out = r.release();
 	});
 }

@@ -186,7 +186,7 @@ void mark_decoded(Context &cx, Mesh &m, bool whole = false);
 // decode_sharded on one context (PLY layout): the segment just decoded (cx's d_rec / d_foff / d_org, the segment's numbering) into
 // d_whole_* at its runs' places in the whole numbering; false (nothing placed) when the context does not hold the segment
 bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne);
-void render_build(Context &cx, const Mesh &m, RenderResult &out);
+void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out);   // flags: HRY_RENDER_*
 void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
 
 // ingest.cpp: hry_mesh_from_device (include/harry_amd.h); the result is resident on cx

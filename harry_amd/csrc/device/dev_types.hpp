@@ -57,6 +57,15 @@ struct RowsView {
 	uint32_t nelem, nowner, nregs, nb, count;
 };
 
+// normals.hip: what the normals of a render build read.  pos: float rows of pos_stride floats whose first three are a vertex's
+// position; eface == nullptr: every face is a triangle (corner c belongs to face c / 3, foff is not read); angle: corner-angle weights
+struct NrmView {
+	const uint32_t *foff, *org, *eface;
+	const float *pos;
+	uint32_t pos_stride, nv, nf, ne;
+	int32_t angle;
+};
+
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
 struct RunPlace {

@@ -90,6 +90,9 @@ size_t twin_workspace_bytes(uint32_t nv, uint32_t ne);
 uint32_t twin_overflow_capacity();
 // *over: device pointer (inside ws) of the list of vertices with too many half-edges for the kernel: count, then vertex ids
 void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twin, void *ws, const uint32_t **over);
+// exclusive scan of n counters in three launches (k_scan_*): out[n + 1], out[n] = total; sums: scan_sums_words(n) words of scratch
+size_t scan_sums_words(uint32_t n);
+void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out);
 // connected components of the faces and their tables for the walk on several host threads (twins.hip; driver: analysis.cpp)
 size_t components_workspace_bytes(uint32_t nv, uint32_t nf);
 // where the workspace's parts lie (twins.hip decides; nobody else computes an offset into it): per face the component label (a
@@ -153,6 +156,15 @@ void launch_place_segment(hipStream_t st, const RunPlace &r, const uint8_t *vrec
                           const uint8_t *frec, uint32_t nlf, uint32_t fstride, uint8_t *whole_frec, const uint32_t *org, uint32_t nle, uint32_t *whole_org,
                           const uint32_t *foff, uint32_t *whole_foff);
 void launch_render_gather(hipStream_t st, const uint8_t *rec, int stride, uint32_t count, const uint32_t *idx, uint64_t rows, const RequantPlan &plan, float *out);
+
+// normals of a render build (normals.hip; driver: render.cpp).  fn: 3 doubles per face (working buffer); count / fill: nv zeroed
+// counters each; start: nv + 1; sums: scan_sums_words(nv); seg: ne; hubs: 1 + normals_hub_capacity(ne) words, the first zeroed;
+// out: nv rows of 3 floats, every row written
+uint32_t normals_hub_capacity(uint32_t ne);
+void launch_face_normals(hipStream_t st, const NrmView &n, double *fn, float *face_normals /* nf x 3, or nullptr */);
+void launch_vertex_normals(hipStream_t st, const NrmView &n, const double *fn, uint32_t *count, uint32_t *fill, uint32_t *start, uint32_t *sums, uint32_t *seg,
+                           uint32_t *hubs, float *out);
+void launch_normals_expand(hipStream_t st, const float *vn, const uint32_t *vsrc, uint32_t nout, uint32_t nv, float *out);   // out[u] = vn[vsrc[u]]
 
 // meshes from device buffers (ingest.hip; driver: ingest.cpp).  The checks raise bits of err; total = sum of the degrees (64-bit),
 // degmask = the set of degrees present (bit d)

@@ -66,8 +66,34 @@ bool rendered(const AttrList &L) { return L.ncomp() > 0 && L.target <= 2; }
 
 }   // namespace
 
-void render_build(Context &cx, const Mesh &m, RenderResult &out)
+// the list whose first three POS components (mixing.h interpretation 0) are the positions the normals are computed from
+static size_t position_list(const Mesh &m)
 {
+	auto npos = [](const AttrList &L) { return L.interp_len.empty() ? 0 : L.interp_len[0]; };
+	if (!m.general) {
+		if (m.lists.size() < 2 || npos(m.lists[1]) < 3) throw Error(HRY_E_UNSUPPORTED, "normals: the vertex list has fewer than three position components");
+		return 1;
+	}
+	size_t pl = m.lists.size();
+	for (size_t l = 0; l < m.lists.size(); ++l) {
+		if (m.lists[l].target != 1 || npos(m.lists[l]) < 3) continue;
+		if (pl != m.lists.size()) throw Error(HRY_E_UNSUPPORTED, "normals: several vertex lists with three position components");
+		pl = l;
+	}
+	if (pl == m.lists.size()) throw Error(HRY_E_UNSUPPORTED, "normals: no vertex list with three position components");
+	for (int r = 0; r < m.bind.nregs_vtx(); ++r) {
+		bool bound = false;
+		for (int a = 0; a < m.bind.nvtxlists(r); ++a) bound |= (size_t)m.bind.vtxlist(r, a) == pl;
+		if (!bound) throw Error(HRY_E_UNSUPPORTED, "normals: a vertex region that does not bind the position list");
+	}
+	return pl;
+}
+
+void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
+{
+	if (flags & ~(uint32_t)(HRY_RENDER_VERTEX_NORMALS | HRY_RENDER_FACE_NORMALS | HRY_RENDER_ANGLE_WEIGHTED)) throw Error(HRY_E_ARG, "unknown render flag");
+	if ((flags & HRY_RENDER_ANGLE_WEIGHTED) && !(flags & HRY_RENDER_VERTEX_NORMALS)) throw Error(HRY_E_ARG, "HRY_RENDER_ANGLE_WEIGHTED without HRY_RENDER_VERTEX_NORMALS");
+	const bool want_vn = flags & HRY_RENDER_VERTEX_NORMALS, want_fn = flags & HRY_RENDER_FACE_NORMALS, want_n = want_vn || want_fn;
 	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
 	if (m.lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
 	for (size_t d = 0; d < 3 && d < m.have_degree.size(); ++d)
@@ -80,6 +106,7 @@ void render_build(Context &cx, const Mesh &m, RenderResult &out)
 	const size_t nl = m.lists.size();
 	const bool general = m.general;
 	const Bindings &b = m.bind;
+	const size_t pl = want_n ? position_list(m) : 0;
 	for (size_t l = 0; l < nl; ++l)
 		if (m.lists[l].data.size() < (size_t)m.lists[l].count * m.lists[l].stride()) throw Error(HRY_E_ARG, "list without its records");
 
@@ -145,6 +172,19 @@ void render_build(Context &cx, const Mesh &m, RenderResult &out)
 	const size_t w_masks = W.reserve(unweld ? (size_t)nw * 8 : 0), w_counts = W.reserve(unweld ? (size_t)nw * 4 : 0);
 	const size_t w_wstart = W.reserve(unweld ? ((size_t)nw + 1) * 4 : 0), w_cmap = W.reserve(unweld ? (size_t)ne * 4 : 0);
 	const size_t w_idx = W.reserve(general ? (size_t)std::max(std::max(nf, nv), ne) * 4 : 0);
+	// normals (normals.hip): N_f per face; per vertex its corners (counters, cursors, segment starts, the scan's sums, the segments,
+	// the list of hubs); a corner -> face table for mixed degrees (the unweld's where there is one); unwelded meshes: the position
+	// list per vertex and the normals per vertex
+	bool all_tri = true;
+	for (size_t d = 4; d < m.have_degree.size(); ++d) all_tri &= !m.have_degree[d];
+	all_tri &= (uint64_t)ne == 3ull * nf;
+	const bool n_eface = want_n && !all_tri && !unweld;
+	const size_t pos_w = want_n ? (size_t)m.lists[pl].ncomp() : 0;
+	const size_t w_fn = W.reserve(want_n ? (size_t)nf * 24 : 0), w_neface = W.reserve(n_eface ? (size_t)ne * 4 : 0);
+	const size_t w_ncount = W.reserve(want_vn ? (size_t)nv * 4 : 0), w_nfill = W.reserve(want_vn ? (size_t)nv * 4 : 0);
+	const size_t w_nstart = W.reserve(want_vn ? ((size_t)nv + 1) * 4 : 0), w_nsums = W.reserve(want_vn ? scan_sums_words(nv) * 4 : 0);
+	const size_t w_nseg = W.reserve(want_vn ? (size_t)ne * 4 : 0), w_nhubs = W.reserve(want_vn ? ((size_t)normals_hub_capacity(ne) + 1) * 4 : 0);
+	const size_t w_npos = W.reserve(want_n && unweld ? (size_t)nv * pos_w * 4 : 0), w_nvn = W.reserve(want_vn && unweld ? (size_t)nv * 12 : 0);
 	cx.d_render.ensure(W.total);
 	void *wb = cx.d_render.p;
 
@@ -222,10 +262,17 @@ void render_build(Context &cx, const Mesh &m, RenderResult &out)
 	if (general) add("face_region", nf, 1, HRY_USHORT);
 	for (size_t l = 0; l < nl; ++l)
 		if (rendered(m.lists[l])) add("list" + std::to_string(l), m.lists[l].target == 0 ? nf : nout, m.lists[l].ncomp(), HRY_FLOAT);
+	if (want_vn) add("normals", nout, 3, HRY_FLOAT);
+	if (want_fn) add("face_normals", nf, 3, HRY_FLOAT);
 	HIP_OK(hipMalloc(&out.block, O.total));
 	for (const Plan &p : plan) out.bufs.push_back(RenderBuf{ p.name, O.ptr<void>(out.block, p.slot), p.rows, p.width, p.type });
 	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
 
+	if (want_vn && nv) {   // (the counters' fill lies outside the events, like the table's)
+		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_ncount), 0, (size_t)nv * 4, st));
+		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nfill), 0, (size_t)nv * 4, st));
+		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nhubs), 0, 4, st));
+	}
 	HIP_OK(hipEventRecord(ev[2], st));
 	uint32_t *vsrc = dst("vertex_source");
 	if (unweld && ne) launch_unweld_assign(st, org, ne, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_wstart), nout,
@@ -249,6 +296,33 @@ void render_build(Context &cx, const Mesh &m, RenderResult &out)
 			rows_idx = idx;
 		}
 		launch_render_gather(st, rec[l], L.stride(), L.count, rows_idx, rows, gather_plan(L), (float*)dst(("list" + std::to_string(l)).c_str()));
+	}
+	if (want_n) {
+		const AttrList &L = m.lists[pl];
+		NrmView n{};
+		n.foff = foff; n.org = org; n.nv = nv; n.nf = nf; n.ne = ne; n.angle = (flags & HRY_RENDER_ANGLE_WEIGHTED) ? 1 : 0;
+		n.pos_stride = (uint32_t)pos_w;
+		const size_t pos_at = (size_t)L.interp_off[0];
+		if (unweld) {   // the position list once more, a row per decoded vertex
+			RowsView v{};
+			v.slot = d_small + slot_at[pl]; v.count = L.count;
+			v.reg = vreg; v.nowner = nv; v.nregs = (uint32_t)b.nregs_vtx(); v.attr = vattr; v.nb = (uint32_t)b.nb_vtx; v.nelem = nv;
+			launch_rows_of(st, v, nv, idx);
+			launch_render_gather(st, rec[pl], L.stride(), L.count, idx, nv, gather_plan(L), W.ptr<float>(wb, w_npos));
+			n.pos = W.ptr<float>(wb, w_npos) + pos_at;
+		} else n.pos = (const float*)dst(("list" + std::to_string(pl)).c_str()) + pos_at;   // identity layout: row v is vertex v
+		if (!all_tri) {
+			if (n_eface) launch_edge_faces(st, foff, nf, W.ptr<uint32_t>(wb, w_neface));
+			n.eface = n_eface ? W.ptr<uint32_t>(wb, w_neface) : eface;
+		}
+		double *fn = W.ptr<double>(wb, w_fn);
+		launch_face_normals(st, n, fn, want_fn ? (float*)dst("face_normals") : nullptr);
+		if (want_vn) {
+			float *vn = unweld ? W.ptr<float>(wb, w_nvn) : (float*)dst("normals");
+			launch_vertex_normals(st, n, fn, W.ptr<uint32_t>(wb, w_ncount), W.ptr<uint32_t>(wb, w_nfill), W.ptr<uint32_t>(wb, w_nstart), W.ptr<uint32_t>(wb, w_nsums),
+			                      W.ptr<uint32_t>(wb, w_nseg), W.ptr<uint32_t>(wb, w_nhubs), vn);
+			if (unweld) launch_normals_expand(st, vn, vsrc, nout, nv, (float*)dst("normals"));
+		}
 	}
 	HIP_OK(hipEventRecord(ev[3], st));
 	if (general && nf) HIP_OK(hipMemcpyAsync(dst("face_region"), freg, (size_t)nf * 2, hipMemcpyDeviceToDevice, st));

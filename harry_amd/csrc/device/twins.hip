@@ -156,6 +156,16 @@ void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twi
 	hipLaunchKernelGGL(k_twin_match, dim3(blocks_for(nv, 256)), dim3(256), 0, st, cv, nv, start, ent, twin, over);
 }
 
+size_t scan_sums_words(uint32_t n) { return (size_t)blocks_for(n, kScanBlock) + 2; }
+void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out)
+{
+	if (!n) { (void)hipMemsetAsync(out, 0, 4, st); return; }
+	const unsigned nb = blocks_for(n, kScanBlock);
+	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, in, n, sums);
+	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
+	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, in, n, (const uint32_t*)sums, out);
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The connected components of the faces and what the walk on several host threads needs to know of them before it starts

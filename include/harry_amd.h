@@ -228,6 +228,40 @@ int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *d
 int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes);
 void hry_render_free(hry_render *r);
 
+/* ---- normals of a render build ------------------------------------------------------------------------------------------
+ * hry_render_build_ex is hry_render_build with flags; hry_render_build(ctx, m, out) is hry_render_build_ex(ctx, m, 0, out), and with
+ * flags == 0 the buffers, their bytes, the kernels launched and hry_render_stat are the same.  The flags add buffers, found through
+ * hry_render_get / hry_render_copy like the others and absent (rows 0) when not asked for:
+ *   "normals"        f32 [U, 3]   HRY_RENDER_VERTEX_NORMALS: unit normal of the decoded vertex of every output vertex
+ *   "face_normals"   f32 [nf, 3]  HRY_RENDER_FACE_NORMALS: unit normal of every face
+ * Unknown flag bits, and HRY_RENDER_ANGLE_WEIGHTED without HRY_RENDER_VERTEX_NORMALS, are refused with HRY_E_ARG.
+ * Positions: P[v] = the first three components of interpretation POS (mixing.h id 0) of the vertex-target list, as the floats the
+ *   build's "list<l>" buffer holds for that vertex (after the -c dequantisation; lossless floats bit for bit), widened to double.  PLY
+ *   layout: list 1.  General bindings: the one vertex-target list with at least three POS components, which every vertex region must
+ *   bind.  Fewer than three position components, several such lists, or a vertex region that binds none: HRY_E_UNSUPPORTED with a
+ *   text that says which; *out stays NULL and ctx stays usable.  A partial mesh is refused as by hry_render_build.  Normals a file
+ *   stored (nx ny nz, OBJ vn) stay in their "list<l>"; they are not read here.
+ * Arithmetic: every operation is an individually rounded IEEE double operation, in the written order.
+ *   N_f = sum over k = 1 .. d-2 of (P[c_k] - P[c_0]) x (P[c_(k+1)] - P[c_0]) for face f with corners c_0 .. c_(d-1): the cross products
+ *     of the fan triangles of "indices", relative to c_0 (a mesh far from the origin does not cancel); a x b = (a.y b.z - a.z b.y,
+ *     a.z b.x - a.x b.z, a.x b.y - a.y b.x); |a| = sqrt((a.x a.x + a.y a.y) + a.z a.z).
+ *   face_normals[f] = (float)(N_f / |N_f|) per component; where |N_f| is 0 or not finite the row is (0, 0, 0) and the face
+ *     contributes nothing to any vertex.
+ *   S_v, area weights (default): the sum of N_f over the corners c with org[c] == v, f the face of c.
+ *   S_v, HRY_RENDER_ANGLE_WEIGHTED: the sum of theta_c * (N_f / |N_f|), theta_c = atan2(|a x b|, a . b) with a = P[next corner] - P[v]
+ *     and b = P[previous corner] - P[v] within the face, a . b = (a.x b.x + a.y b.y) + a.z b.z.
+ *   normals[u] = (float)(S_v / |S_v|) for v = vertex_source[u], (0, 0, 0) where |S_v| is 0 or not finite (an isolated vertex, a NaN
+ *     position, exactly opposed faces).  Output vertices of one decoded vertex get the same bits: the unweld does not crease shading.
+ * Determinism: the bits of both buffers depend on the mesh alone -- not on the run, on residency, or on the order atomics complete
+ *   in (there are no floating-point atomics).  A vertex's sum starts from +0 and runs over its corners in ascending half-edge id, one
+ *   after the other.  A vertex with more than 32 corners (n of them) instead sums 256 consecutive ranges of ceil(n / 256) corners each in
+ *   that way and adds the 256 partial sums in range order: an association n alone determines.  All of it runs on the device.
+ * The timing of hry_render_stat encloses the normals' kernels. */
+#define HRY_RENDER_VERTEX_NORMALS 1u   /* buffer "normals"      f32 [U, 3]  */
+#define HRY_RENDER_FACE_NORMALS   2u   /* buffer "face_normals" f32 [nf, 3] */
+#define HRY_RENDER_ANGLE_WEIGHTED 4u   /* vertex normals weighted by corner angle instead of face area */
+int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_render **out);
+
 /* ---- meshes from device buffers --------------------------------------------------------------------------------------
  * hry_mesh_from_device is hry_mesh_from_arrays for data that already lives on ctx's device (the other direction of
  * hry_render_build).  A component is a strided column: row i's value of `type` at (const uint8_t*)data + i * stride, where data is

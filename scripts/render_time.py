@@ -2,7 +2,11 @@
 bench's 80 000-triangle OBJ scene.  Prints ONE JSON line: per workload the decode's wall time, the render kernels' device_ms (HIP
 events), the wall time of hry_render_build plus the copies of every buffer (device to device, into preallocated device memory) and
 the bytes the build uploaded.  Each measurement follows a fresh decode (residency holds for the mesh the decode just returned);
-warm-up runs first, then medians over the repeats."""
+warm-up runs first, then medians over the repeats.
+
+--normals: configs[1] only, through Codec.render: the render kernels' device_ms without normals, with area-weighted vertex normals,
+with face normals too and with angle weights (hry_render_build_ex), beside a plain torch restatement on the same tensors (float32
+fan cross products, index_add_, normalise; torch.cuda events) and the largest component difference between the two results."""
 import argparse
 import ctypes as C
 import json
@@ -53,11 +57,63 @@ def measure(cx, data, warmup, repeats, dst):
     return out
 
 
+def normals_report(warmup, repeats):
+    import torch
+    torch.cuda.init()   # torch holds the device before the codec starts
+    cx = hc.Codec(0)
+    try:
+        m = hc.Mesh.from_ply(mg.torus(708, 708, seed=2, sigma=1e-4).to_ply())
+        cx.requant(m, [(1, -1, 14)])
+        cfg1 = cx.write_hry(m, profile=hc.PROFILE_CHUNKED)
+        res, got = {}, None
+        for key, kw in (("plain", {}), ("area", {"normals": "area"}), ("area_and_faces", {"normals": "area", "face_normals": True}),
+                        ("angle", {"normals": "angle"})):
+            ms = []
+            for i in range(warmup + repeats):
+                out = cx.render(cx.read_hry(cfg1), **kw)   # (a fresh decode each time: resident)
+                assert cx.render_stat()["uploaded_bytes"] == 0
+                if i >= warmup:
+                    ms.append(cx.render_stat()["device_ms"])
+                if key == "area":
+                    got = out
+            res["device_ms_" + key] = statistics.median(ms)
+        res["ntris"] = cx.render_stat()["ntris"]
+
+        P, idx = got["list1"][:, :3].contiguous(), got["indices"].long()
+
+        def restated():
+            p0 = P[idx[:, 0]]
+            n = torch.cross(P[idx[:, 1]] - p0, P[idx[:, 2]] - p0, dim=1)
+            s = torch.zeros_like(P)
+            for k in range(3):
+                s.index_add_(0, idx[:, k], n)
+            return torch.nn.functional.normalize(s, dim=1)
+
+        ms = []
+        for i in range(warmup + repeats):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ref = restated()
+            b.record()
+            b.synchronize()
+            if i >= warmup:
+                ms.append(a.elapsed_time(b))
+        res["torch_index_add_ms"] = statistics.median(ms)
+        res["largest_difference"] = float((ref - got["normals"]).abs().max())
+        return res
+    finally:
+        cx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--normals", action="store_true", help="configs[1]: device_ms with and without normals, against a torch index_add_ pass")
     args = ap.parse_args()
+    if args.normals:
+        print(json.dumps({"configs1_normals": normals_report(args.warmup, args.repeats)}))
+        return
     cx = hc.Codec(0)
     m = hc.Mesh.from_ply(mg.torus(708, 708, seed=2, sigma=1e-4).to_ply())
     cx.requant(m, [(1, -1, 14)])
