@@ -35,6 +35,11 @@ class DevColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_uint64), ("name", C.c_char_p), ("type", C.c_int32)]
 
 
+class DevRows(C.Structure):
+    """hry_dev_rows: the rows of one list of hry_mesh_from_device_corners (float columns) and the row every corner names"""
+    _fields_ = [("cols", C.POINTER(DevColumn)), ("ncomp", C.c_int32), ("rows", C.c_uint32), ("indices", C.c_void_p)]
+
+
 class Timing(C.Structure):
     _fields_ = [("host_walk_ms", C.c_double), ("h2d_ms", C.c_double), ("device_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("total_ms", C.c_double), ("k_rchain_ms", C.c_double), ("k_model_ms", C.c_double), ("k_predict_ms", C.c_double),
@@ -155,6 +160,9 @@ def load():
     L.hry_mesh_from_device.restype = C.c_int
     L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),
                                        C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.hry_mesh_from_device_corners.restype = C.c_int
+    L.hry_mesh_from_device_corners.argtypes = [vp, C.POINTER(DevRows), C.POINTER(DevRows), C.POINTER(DevRows), C.c_uint32, vp, C.c_int, C.c_uint64, vp,
+                                               C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.hry_mesh_resident.restype = C.c_int; L.hry_mesh_resident.argtypes = [vp, vp]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")

@@ -493,6 +493,81 @@ class Codec:
         mesh = Mesh(h)
         return (mesh, remap) if return_remap else mesh
 
+    def corner_mesh_from_tensors(self, positions, pos_idx, uv=None, uv_idx=None, normals=None, normal_idx=None, degrees=None,
+                                 materials=None, weld: bool = False, return_remap: bool = False):
+        """hry_mesh_from_device_corners: the mesh Mesh.from_obj builds from the text of the same arrays, from tensors on this codec's
+        device and resident here.  positions [n, 3 | 4 | 6 | 7 | 8], uv [n, 2 | 3], normals [n, 3]: float32, passed with their own
+        strides.  pos_idx / uv_idx / normal_idx: the row every corner names, int32 [T, 3] or 1-D int32 / int64 with degrees (uint8
+        [nf]); uv_idx / normal_idx None: pos_idx (the layout Codec.render returns).  materials: int16 (or uint16) [nf], one region
+        per distinct value in order of first occurrence.  weld: every list on its own, rows equal byte for byte become one record;
+        return_remap: also (pos, uv, normal) int32 tensors with the output record of every input row, None for absent lists."""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+
+        def refuse(msg):
+            return HryError(nat.E_ARG, msg)
+
+        def tensor(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise refuse(f"{what}: not a tensor on {dev}")
+            return t
+
+        tensor(pos_idx, "pos_idx")
+        if pos_idx.dtype not in (torch.int32, torch.int64):
+            raise refuse(f"pos_idx: dtype {pos_idx.dtype} (int32 or int64)")
+        if degrees is None:
+            if pos_idx.dim() != 2 or pos_idx.shape[1] != 3:
+                raise refuse("pos_idx: [T, 3] without degrees")
+            nf = pos_idx.shape[0]
+        else:
+            tensor(degrees, "degrees")
+            if degrees.dtype != torch.uint8 or degrees.dim() != 1 or pos_idx.dim() != 1:
+                raise refuse("degrees: uint8 [nf] with 1-D indices")
+            degrees = degrees.contiguous()
+            nf = degrees.shape[0]
+        pos_idx = pos_idx.contiguous()
+        keep, rows, remaps = [], [], []
+        for what, t, idx in (("positions", positions, pos_idx), ("uv", uv, uv_idx), ("normals", normals, normal_idx)):
+            if t is None:
+                if idx is not None and what != "positions":
+                    raise refuse(f"{what}: indices without rows")
+                rows.append(None)
+                remaps.append(None)
+                continue
+            tensor(t, what)
+            if t.dtype != torch.float32 or t.dim() != 2:
+                raise refuse(f"{what}: float32 [n, k], not {t.dtype} {tuple(t.shape)}")
+            if idx is None:
+                idx = pos_idx
+            elif idx is not pos_idx:
+                tensor(idx, what + " indices")
+                if idx.dtype != pos_idx.dtype or idx.shape != pos_idx.shape:
+                    raise refuse(f"{what} indices: {idx.dtype} {tuple(idx.shape)}, pos_idx is {pos_idx.dtype} {tuple(pos_idx.shape)}")
+                idx = idx.contiguous()
+            if t.shape[0] >= 2 ** 32:
+                raise refuse("more than 2^32 - 1 rows")
+            cols = (nat.DevColumn * t.shape[1])(*[nat.DevColumn(t.data_ptr() + j * t.stride(1) * 4, t.stride(0) * 4, None, 0) for j in range(t.shape[1])])
+            remap = torch.empty(t.shape[0], dtype=torch.int32, device=dev) if return_remap else None
+            keep += [cols, idx]
+            rows.append(nat.DevRows(cols, t.shape[1], t.shape[0], idx.data_ptr() if idx.numel() else None))
+            remaps.append(remap)
+        if materials is not None:
+            tensor(materials, "materials")
+            if materials.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or materials.dim() != 1 or materials.shape[0] != nf:
+                raise refuse(f"materials: int16 [{nf}], not {materials.dtype} {tuple(materials.shape)}")
+            materials = materials.contiguous()
+        if max(nf, pos_idx.numel()) >= 2 ** 32:
+            raise refuse("more than 2^32 - 1 faces or indices")
+        torch.cuda.current_stream(dev).synchronize()   # (the tensors may still be being written by torch's stream)
+        h = C.c_void_p()
+        out_remap = (C.c_void_p * 3)(*[r.data_ptr() if r is not None and r.numel() else None for r in remaps])
+        nat.check(nat.load().hry_mesh_from_device_corners(
+            self.h, *[C.byref(r) if r is not None else None for r in rows], nf, degrees.data_ptr() if degrees is not None else None,
+            4 if pos_idx.dtype == torch.int32 else 3, pos_idx.numel(), materials.data_ptr() if materials is not None and nf else None,
+            nat.INGEST_WELD if weld else 0, out_remap if return_remap else None, C.byref(h)))
+        mesh = Mesh(h)
+        return (mesh, tuple(remaps)) if return_remap else mesh
+
     def resident(self, mesh: Mesh) -> bool:
         """hry_mesh_resident: this context holds the mesh's records and connectivity in HBM (an encode uploads nothing for it)"""
         return bool(nat.load().hry_mesh_resident(self.h, mesh.h))

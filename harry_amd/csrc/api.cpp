@@ -646,6 +646,18 @@ int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols,
 		*out = new hry_mesh{ std::move(*m) };
 	});
 }
+int hry_mesh_from_device_corners(hry_ctx *ctx, const hry_dev_rows *pos, const hry_dev_rows *tex, const hry_dev_rows *nrm, uint32_t nf,
+                                 const uint8_t *d_degrees, int index_type, uint64_t n_indices, const uint16_t *d_face_material, int flags,
+                                 uint32_t *const d_remap[3], hry_mesh **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !out || !pos) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx);
+	return guarded([&] {
+		std::unique_ptr<Mesh> m(mesh_from_device_corners(ctx->cx, pos, tex, nrm, nf, d_degrees, index_type, n_indices, d_face_material, flags, d_remap));
+		*out = new hry_mesh{ std::move(*m) };
+	});
+}
 int hry_mesh_resident(const hry_ctx *ctx, const hry_mesh *m)
 {
 	return ctx && m && m->m.device_token != 0 && m->m.device_token == ctx->cx.resident_token ? 1 : 0;

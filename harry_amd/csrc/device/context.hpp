@@ -193,6 +193,11 @@ void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst
 Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,
                        const void *d_indices, int index_type, uint64_t n_indices, const hry_dev_column *fcols, int f_ncomp, int flags,
                        uint32_t *d_remap);
+// ... hry_mesh_from_device_corners: general bindings as the OBJ reader creates them, resident with their tables (as after upload_general)
+Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_dev_rows *tex, const hry_dev_rows *nrm, uint32_t nf,
+                               const uint8_t *d_degrees, int index_type, uint64_t n_indices, const uint16_t *d_face_material, int flags,
+                               uint32_t *const d_remap[3]);
+constexpr const char *kTooManyRegionsText = "more than 128 regions: the reference seeds its region models out of bounds (model.h:49-55)";   // check_general
 
 dev::ListDesc make_list_desc(const AttrList &L);
 void check_codable(const Mesh &m);

@@ -38,7 +38,7 @@ void check_general(const Mesh &m)
 {
 	const Bindings &b = m.bind;
 	if (m.lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
-	if (b.nregs_face() > 128 || b.nregs_vtx() > 128) throw Error(HRY_E_UNSUPPORTED, "more than 128 regions: the reference seeds its region models out of bounds (model.h:49-55)");
+	if (b.nregs_face() > 128 || b.nregs_vtx() > 128) throw Error(HRY_E_UNSUPPORTED, kTooManyRegionsText);
 	if (b.nb_face > 255 || b.nb_vtx > 255 || b.nb_corner > 255) throw Error(HRY_E_UNSUPPORTED, "more than 255 lists bound to one region");
 	if (b.face_reg.size() != m.nf || b.vtx_reg.size() != m.nv || b.face_attr.size() != (size_t)m.nf * b.nb_face ||
 	    b.vtx_attr.size() != (size_t)m.nv * b.nb_vtx || b.corner_attr.size() != (size_t)m.ne() * b.nb_corner)

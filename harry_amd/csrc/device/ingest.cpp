@@ -171,4 +171,219 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 	return m.release();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// hry_mesh_from_device_corners: the mesh hry_mesh_from_obj builds from the text of the same arrays (obj_io.cpp Loader), its tables
+// written where upload_general puts them: d_rec[l], d_org, d_twin, d_foff, d_vreg, d_freg, d_vattr, d_cattr (d_fattr stays empty).
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+struct RowsIn {
+	const hry_dev_rows *in = nullptr;
+	const char *bad_index = "";   // the refusal's text for an index outside the rows
+	int k = 0;                    // 0 pos, 1 tex, 2 nrm: d_remap's entry
+	uint32_t bad_bit = 0;
+	PackCols pack{};
+	size_t keys = 0, table = 0, first = 0, masks = 0, counts = 0, vstart = 0, remap = 0, frow = 0, slots = 0;   // pieces of d_ingest (weld)
+};
+
+PackCols float_rows(const Context &cx, const hry_dev_rows &r, const char *what)
+{
+	if (r.ncomp > 0 && !r.cols) throw Error(HRY_E_ARG, std::string(what) + " rows: null columns");
+	PackCols p{};
+	p.rec_stride = 4u * (uint32_t)r.ncomp;
+	for (int i = 0; i < r.ncomp; ++i) {
+		const hry_dev_column &c = r.cols[i];
+		const std::string where = std::string(what) + " column " + std::to_string(i);
+		if (c.type != HRY_FLOAT) throw Error(HRY_E_ARG, where + ": the type must be HRY_FLOAT");
+		if (c.stride == 0 || c.stride % 4) throw Error(HRY_E_ARG, where + ": the stride is not a non-zero multiple of the type's size");
+		if ((uintptr_t)c.data % 4) throw Error(HRY_E_ARG, where + ": misaligned");
+		if (r.rows) check_device_memory(cx, c.data, (uint64_t)(r.rows - 1) * c.stride + 4, where);
+		p.src[i] = (const uint8_t*)c.data;
+		p.stride[i] = c.stride;
+		for (int b = 0; b < 4; ++b) { p.comp_of[4 * i + b] = (uint8_t)i; p.byte_of[4 * i + b] = (uint8_t)b; }
+	}
+	return p;
+}
+
+}   // namespace
+
+Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_dev_rows *tex, const hry_dev_rows *nrm, uint32_t nf,
+                               const uint8_t *d_degrees, int index_type, uint64_t n_indices, const uint16_t *d_face_material, int flags,
+                               uint32_t *const d_remap[3])
+{
+	HIP_OK(hipSetDevice(cx.device));
+	const bool weld = (flags & HRY_INGEST_WELD) != 0;
+	if (flags & ~HRY_INGEST_WELD) throw Error(HRY_E_ARG, "unknown flags");
+	if (!pos) throw Error(HRY_E_ARG, "null position rows");
+	if (index_type != HRY_UINT && index_type != HRY_LONG) throw Error(HRY_E_ARG, "index type must be HRY_UINT or HRY_LONG");
+	if (n_indices > 0xffffffffull) throw Error(HRY_E_UNSUPPORTED, "more than 2^32-1 half-edges");
+	if (!d_degrees && n_indices != 3ull * nf) throw Error(HRY_E_ARG, "sum of degrees differs from the number of indices");
+	const uint32_t ne = (uint32_t)n_indices;
+	const bool idx64 = index_type == HRY_LONG;
+	const int pn = pos->ncomp;
+	if (!(pn == 3 || pn == 4 || (pn >= 6 && pn <= 8))) throw Error(HRY_E_ARG, "position rows: 3, 4, 6, 7 or 8 components");
+	if (tex && tex->ncomp != 2 && tex->ncomp != 3) throw Error(HRY_E_ARG, "texture rows: 2 or 3 components");
+	if (nrm && nrm->ncomp != 3) throw Error(HRY_E_ARG, "normal rows: 3 components");
+
+	std::unique_ptr<Mesh> m(new Mesh());
+	m->lists.clear();
+	m->general = true;
+	m->bind.nb_face = 0; m->bind.nb_vtx = 1; m->bind.nb_corner = 2;   // as the reader sets them
+	RowsIn in[3];
+	int nl = 0;
+	auto add = [&](const hry_dev_rows *r, int kind, int k, const char *what, const char *bad_index, uint32_t bit) {
+		if (!r) return;
+		RowsIn &R = in[nl];
+		R.in = r; R.k = k; R.bad_index = bad_index; R.bad_bit = bit;
+		R.pack = float_rows(cx, *r, what);
+		if (ne) {
+			if (!r->indices) throw Error(HRY_E_ARG, std::string(what) + " indices: null");
+			if ((uintptr_t)r->indices % (idx64 ? 8 : 4)) throw Error(HRY_E_ARG, std::string(what) + " indices: misaligned");
+			check_device_memory(cx, r->indices, (uint64_t)ne * (idx64 ? 8 : 4), std::string(what) + " indices");
+		}
+		if (d_remap && d_remap[k] && r->rows) check_device_memory(cx, d_remap[k], (uint64_t)r->rows * 4, std::string(what) + " remap");
+		m->lists.push_back(obj_list_layout(kind, r->ncomp));
+		m->lists.back().count = r->rows;
+		++nl;
+	};
+	add(pos, OBJ_VERTEX, 0, "position", "vertex index out of range", kIngestBadIndex);
+	add(tex, OBJ_TEX, 1, "texture", "texture index out of range", kIngestBadTexIndex);
+	add(nrm, OBJ_NORMAL, 2, "normal", "normal index out of range", kIngestBadNormalIndex);
+	if (nf && d_degrees) check_device_memory(cx, d_degrees, nf, "degrees");
+	if (nf && d_face_material) {
+		if ((uintptr_t)d_face_material % 2) throw Error(HRY_E_ARG, "face materials: misaligned");
+		check_device_memory(cx, d_face_material, (uint64_t)nf * 2, "face materials");
+	}
+	const uint32_t rows0 = pos->rows;
+
+	// ---- the context's resident buffers are rewritten from here on: whatever mesh they held is no longer resident
+	cx.resident_token = 0;
+	cx.gen_token = 0;
+	hipStream_t st = cx.stream;
+	cx.d_foff.ensure(((size_t)nf + 1) * 4);
+	cx.d_org.ensure(std::max<size_t>((size_t)ne * 4, 16));
+	cx.d_twin.ensure(std::max<size_t>((size_t)ne * 4, 16));
+	for (int l = 0; l < nl; ++l) cx.d_rec[l].ensure(std::max<size_t>((size_t)in[l].in->rows * in[l].pack.rec_stride, 16));
+	cx.d_vreg.ensure(std::max<size_t>((size_t)rows0 * 2, 16));
+	cx.d_vattr.ensure(std::max<size_t>((size_t)rows0 * 4, 16));
+	cx.d_freg.ensure(std::max<size_t>((size_t)nf * 2, 16));
+	cx.d_cattr.ensure(std::max<size_t>((size_t)ne * 8, 16));
+	cx.d_fattr.ensure(16);
+
+	// working arrays: 256-byte aligned pieces of one buffer
+	std::vector<size_t> at;
+	size_t total = 0;
+	auto reserve = [&](size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at.size() - 1; };
+	auto ptr = [&](size_t i) { return (void*)(cx.d_ingest.as<uint8_t>() + at[i]); };
+	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64);
+	const size_t status_bytes = sizeof(IngestStatus) + 16;   // (+ the records of the three lists after the weld, the face regions)
+	const size_t w_status = reserve(status_bytes);
+	const size_t w_fsum = reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	const size_t w_mfirst = reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0), w_mrank = reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0);
+	for (int l = 0; l < nl && weld; ++l) {   // every welded list has its own keys and table
+		RowsIn &R = in[l];
+		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
+		R.slots = unweld_table_slots(n);
+		R.keys = reserve((size_t)n * R.pack.rec_stride); R.table = reserve(R.slots * 4); R.first = reserve((size_t)n * 4);
+		R.masks = reserve((size_t)nw * 8); R.counts = reserve((size_t)nw * 4); R.vstart = reserve(((size_t)nw + 1) * 4);
+		R.remap = reserve((size_t)n * 4); R.frow = reserve((size_t)n * 4);
+	}
+	cx.d_ingest.ensure(total);
+	IngestStatus *status = (IngestStatus*)ptr(w_status);
+	uint32_t *d_counts = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));   // [k]: records of list k after the weld; [3]: face regions
+	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
+
+	// ---- every kernel up to the checks, then ONE read-back: the status word, the welded counts, the number of regions
+	launch_ingest_offsets(st, d_degrees, nf, (uint32_t*)ptr(w_fsum), (uint32_t*)ptr(w_fstart), cx.d_foff.as<uint32_t>(), status);
+	for (int l = 0; l < nl; ++l) {
+		RowsIn &R = in[l];
+		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
+		if (!weld) { launch_ingest_pack(st, R.pack, n, nullptr, n, cx.d_rec[l].as<uint8_t>()); continue; }
+		uint8_t *keys = (uint8_t*)ptr(R.keys);
+		launch_ingest_pack(st, R.pack, n, nullptr, n, keys);
+		const WeldView u{ keys, R.pack.rec_stride, n, (uint32_t)(R.slots - 1), (uint32_t*)ptr(R.table) };
+		HIP_OK(hipMemsetAsync(u.table, 0xff, R.slots * 4, st));
+		launch_weld_count(st, u, (uint32_t*)ptr(R.first), (uint64_t*)ptr(R.masks), (uint32_t*)ptr(R.counts), (uint32_t*)ptr(R.vstart));
+		launch_weld_assign(st, n, (const uint32_t*)ptr(R.first), (const uint64_t*)ptr(R.masks), (const uint32_t*)ptr(R.vstart), (uint32_t*)ptr(R.remap),
+		                   (uint32_t*)ptr(R.frow));
+		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, (const uint32_t*)ptr(R.vstart) + nw, 4, hipMemcpyDeviceToDevice, st));
+	}
+	auto remap_of = [&](const RowsIn &R) { return weld ? (const uint32_t*)ptr(R.remap) : nullptr; };
+	launch_ingest_org(st, pos->indices, idx64, ne, rows0, remap_of(in[0]), cx.d_org.as<uint32_t>(), status);
+	CornerSlots cs{};
+	for (int l = 1; l < nl; ++l) {   // slots are compacted: tex, then nrm, whichever are given
+		cs.idx[l - 1] = in[l].in->indices; cs.remap[l - 1] = remap_of(in[l]); cs.rows[l - 1] = in[l].in->rows; cs.bad[l - 1] = in[l].bad_bit;
+	}
+	launch_ingest_corner_attr(st, cs, idx64, ne, cx.d_cattr.as<uint32_t>(), status);
+	HIP_OK(hipMemsetAsync(cx.d_vreg.p, 0, std::max<size_t>((size_t)rows0 * 2, 16), st));   // one vertex region
+	launch_ingest_iota(st, rows0, cx.d_vattr.as<uint32_t>());                                // vertex v owns record v
+	if (d_face_material) {
+		HIP_OK(hipMemsetAsync(ptr(w_mfirst), 0xff, (size_t)kIngestMaterials * 4, st));
+		HIP_OK(hipMemsetAsync(ptr(w_mrank), 0, (size_t)kIngestMaterials * 4, st));
+		launch_ingest_regions(st, d_face_material, nf, (uint32_t*)ptr(w_mfirst), (uint32_t*)ptr(w_mrank), d_counts + 3, cx.d_freg.as<uint16_t>(), status);
+	} else HIP_OK(hipMemsetAsync(cx.d_freg.p, 0, std::max<size_t>((size_t)nf * 2, 16), st));
+	cx.h_small.ensure(4096);
+	HIP_OK(hipMemcpyAsync(cx.h_small.p, status, status_bytes, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	IngestStatus s;
+	uint32_t counts[4];
+	memcpy(&s, cx.h_small.p, sizeof s);
+	memcpy(counts, cx.h_small.as<uint8_t>() + sizeof(IngestStatus), sizeof counts);
+	if (s.err & kIngestBadDegree) throw Error(HRY_E_UNSUPPORTED, "polygon degree outside 3..255");
+	if (d_degrees && s.total != n_indices) throw Error(HRY_E_ARG, "sum of degrees differs from the number of indices");
+	for (int l = 0; l < nl; ++l) if (s.err & in[l].bad_bit) throw Error(HRY_E_ARG, in[l].bad_index);
+	if (s.err & kIngestManyRegions) throw Error(HRY_E_UNSUPPORTED, kTooManyRegionsText);
+	const uint32_t nreg = d_face_material ? counts[3] : (nf ? 1u : 0u);
+	for (int l = 0; l < nl; ++l) {
+		RowsIn &R = in[l];
+		const uint32_t n = R.in->rows, nout = weld ? counts[R.k] : n;
+		if (nout > n) throw Error(HRY_E_INTERNAL, "weld: more records than rows");
+		m->lists[l].count = nout;
+		// ---- welded: the records of the output, gathered from the columns at each one's first row
+		if (weld) launch_ingest_pack(st, R.pack, nout, (const uint32_t*)ptr(R.frow), n, cx.d_rec[l].as<uint8_t>());
+		if (d_remap && d_remap[R.k] && n) {
+			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], ptr(R.remap), (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+			else launch_ingest_iota(st, n, d_remap[R.k]);
+		}
+	}
+	const uint32_t nv = m->lists[0].count;
+	m->nv = nv; m->nf = nf;
+	if (d_degrees) {
+		for (int d = 0; d < 256; ++d)
+			if ((s.degmask[d >> 5] >> (d & 31)) & 1) { if (d >= (int)m->have_degree.size()) m->have_degree.resize(d + 1, 0); m->have_degree[d] = 1; }
+	} else if (nf) {
+		m->have_degree.assign(4, 0);
+		m->have_degree[3] = 1;
+	}
+
+	// ---- the regions' tables (the reader's: one vertex region on list 0, every face region on the corner lists given)
+	Bindings &b = m->bind;
+	if (nv) { const int r = b.add_vtx_region(1); b.reg_vtxlist[b.off_vtxlist[r]] = 0; }
+	for (uint32_t r = 0; r < nreg; ++r) {
+		const int q = b.add_face_region(0, nl - 1);
+		for (int l = 1; l < nl; ++l) b.reg_cornerlist[b.off_cornerlist[q] + l - 1] = (uint16_t)l;
+	}
+
+	// ---- the host copies, then the twins (hubs are matched on the host, from its connectivity)
+	m->face_off.resize((size_t)nf + 1);
+	m->org.resize(ne);
+	b.face_reg.resize(nf);
+	b.corner_attr.resize((size_t)ne * 2);
+	b.vtx_reg.assign(nv, 0);
+	b.vtx_attr.resize(nv);
+	for (int l = 0; l < nl; ++l) m->lists[l].data.resize((size_t)m->lists[l].count * m->lists[l].stride());
+	fetch_to_host(cx, m->face_off.data(), cx.d_foff.p, ((size_t)nf + 1) * 4);
+	fetch_to_host(cx, m->org.data(), cx.d_org.p, (size_t)ne * 4);
+	fetch_to_host(cx, b.face_reg.data(), cx.d_freg.p, (size_t)nf * 2);
+	fetch_to_host(cx, b.corner_attr.data(), cx.d_cattr.p, (size_t)ne * 8);
+	fetch_to_host(cx, b.vtx_attr.data(), cx.d_vattr.p, (size_t)nv * 4);
+	for (int l = 0; l < nl; ++l) fetch_to_host(cx, m->lists[l].data.data(), cx.d_rec[l].p, m->lists[l].data.size());
+	cx.conn_state(*m);
+	m->twins_pending = true;
+	cx.match_twins(*m);
+	cx.make_resident(*m);
+	cx.gen_token = m->device_token;   // the binding tables are there too: upload_general finds nothing to do
+	return m.release();
+}
+
 }   // namespace hry

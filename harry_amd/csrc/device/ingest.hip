@@ -6,6 +6,10 @@
 //   k_ingest_org       a lane per half-edge: the index, range-checked, through the weld map when welding
 //   k_ingest_pack      a lane per 4-byte word of a list's AoS records: strided columns gathered into the list's layout
 //   k_weld_*           one output vertex per distinct packed record, in first-occurrence order over the input rows
+// and for meshes with corner lists (hry_mesh_from_device_corners):
+//   k_ingest_corner_attr  a lane per word of corner_attr: the corner's row in the slot's list, range-checked, through that list's weld map
+//   k_ingest_iota         vtx_attr[v] = v
+//   k_region_first / k_region_rank / k_ingest_face_region   a material per face -> regions numbered by first occurrence
 // The checks of the input raise bits of one status word (vector atomics, once per wavefront); the host reads it back once.  Offsets
 // computed from bad degrees are stored but never used for an address: the host refuses the mesh first.
 #include <hip/hip_runtime.h>
@@ -184,6 +188,88 @@ __global__ __launch_bounds__(256) void k_weld_assign(uint32_t n, const uint32_t 
 	if (e == r && id < n) first_row[id] = r;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// corner_attr: word 2c + s is corner c's record in the list of slot s -- its index in that list's buffer, through the list's weld
+// map when welding; 0 in an unused slot.  An index outside [0, rows) raises the list's bit (one atomic per wavefront) and stores 0:
+// nothing is read or written at it.
+// ---------------------------------------------------------------------------------------------------------
+template <typename I>
+__global__ __launch_bounds__(256) void k_ingest_corner_attr(CornerSlots cs, uint32_t ne, uint32_t *cattr, IngestStatus *st)
+{
+	const uint64_t n = 2ull * ne, step = (uint64_t)gridDim.x * blockDim.x;
+	for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += step) {
+		const uint32_t s = (uint32_t)(w & 1);
+		const I *idx = (const I*)cs.idx[s];
+		uint32_t out = 0, raise = 0;
+		if (idx) {
+			const I v = idx[w >> 1];
+			const bool ok = v >= 0 && (uint64_t)v < cs.rows[s];
+			if (ok) out = cs.remap[s] ? cs.remap[s][(uint32_t)v] : (uint32_t)v;
+			else raise = cs.bad[s];
+		}
+		cattr[w] = out;
+		const uint64_t b0 = __ballot(raise == cs.bad[0] && raise != 0), b1 = __ballot(raise == cs.bad[1] && raise != 0);
+		const uint64_t any = b0 | b1;
+		if (any && (threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)any) - 1) atomicOr(&st->err, (b0 ? cs.bad[0] : 0u) | (b1 ? cs.bad[1] : 0u));
+	}
+}
+
+__global__ __launch_bounds__(256) void k_ingest_iota(uint32_t n, uint32_t *out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) out[i] = i;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// face regions: the distinct materials, numbered in order of their first face.  k_region_first: only the first face of a run of
+// equal materials can be a material's first face, so only those lanes issue atomicMin(first[material], face) -- as many atomics as
+// runs, and a minimum does not depend on the order they complete in.  k_region_rank (ONE block): the materials whose entry is not
+// EMPTY are compacted into LDS (in any order: LDS atomic counter) and each one's region is the number of present materials with an
+// earlier first face (first faces are distinct, at most 128 x 128 comparisons).  More than 128: the bit, and the count for the text.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_region_first(const uint16_t *mat, uint32_t nf, uint32_t *first)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f >= nf) return;
+	const uint16_t m = mat[f];
+	if (f == 0 || mat[f - 1] != m) atomicMin(&first[m], f);
+}
+
+__global__ __launch_bounds__(256) void k_region_rank(const uint32_t *first, uint32_t *rank, uint32_t *n_regions, IngestStatus *st)
+{
+	__shared__ uint32_t s_n, s_mat[kIngestMaxRegions], s_first[kIngestMaxRegions];
+	if (threadIdx.x == 0) s_n = 0;
+	__syncthreads();
+	for (uint32_t m = threadIdx.x; m < kIngestMaterials; m += blockDim.x) {
+		const uint32_t f = first[m];
+		if (f == kNone) continue;
+		const uint32_t at = atomicAdd(&s_n, 1u);
+		if (at < kIngestMaxRegions) { s_mat[at] = m; s_first[at] = f; }
+	}
+	__syncthreads();
+	const uint32_t n = s_n, k = min(n, kIngestMaxRegions);
+	if (threadIdx.x == 0) {
+		*n_regions = n;
+		if (n > kIngestMaxRegions) atomicOr(&st->err, kIngestManyRegions);
+	}
+	if (threadIdx.x < k) {
+		const uint32_t mine = s_first[threadIdx.x];
+		uint32_t r = 0;
+		for (uint32_t j = 0; j < k; ++j) r += s_first[j] < mine;
+		rank[s_mat[threadIdx.x]] = r;
+	}
+}
+
+// a lane per word of face_reg (two faces); the odd face at the end is stored on its own
+__global__ __launch_bounds__(256) void k_ingest_face_region(const uint16_t *mat, uint32_t nf, const uint32_t *rank, uint16_t *face_reg)
+{
+	const uint32_t f = 2 * (blockIdx.x * blockDim.x + threadIdx.x);
+	if (f >= nf) return;
+	const uint32_t a = rank[mat[f]];
+	if (f + 1 < nf) ((uint32_t*)face_reg)[f >> 1] = a | rank[mat[f + 1]] << 16;
+	else face_reg[f] = (uint16_t)a;
+}
+
 // ---- launchers
 static inline unsigned grid_for(uint64_t n, unsigned per) { const uint64_t b = (n + per - 1) / per; return (unsigned)(b < (1u << 20) ? b : (1u << 20)); }
 
@@ -224,6 +310,23 @@ void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, ui
 void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row)
 {
 	if (n) hipLaunchKernelGGL(k_weld_assign, dim3((n + 255) / 256), dim3(256), 0, st, n, first_of, masks, wave_start, remap, first_row);
+}
+void launch_ingest_corner_attr(hipStream_t st, const CornerSlots &cs, bool idx64, uint32_t ne, uint32_t *corner_attr, IngestStatus *status)
+{
+	if (!ne) return;
+	if (idx64) hipLaunchKernelGGL(k_ingest_corner_attr<int64_t>, dim3(grid_for(2ull * ne, 256)), dim3(256), 0, st, cs, ne, corner_attr, status);
+	else hipLaunchKernelGGL(k_ingest_corner_attr<uint32_t>, dim3(grid_for(2ull * ne, 256)), dim3(256), 0, st, cs, ne, corner_attr, status);
+}
+void launch_ingest_iota(hipStream_t st, uint32_t n, uint32_t *out)
+{
+	if (n) hipLaunchKernelGGL(k_ingest_iota, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, n, out);
+}
+void launch_ingest_regions(hipStream_t st, const uint16_t *mat, uint32_t nf, uint32_t *first, uint32_t *rank, uint32_t *n_regions, uint16_t *face_reg,
+                           IngestStatus *status)
+{
+	if (nf) hipLaunchKernelGGL(k_region_first, dim3((unsigned)(((uint64_t)nf + 255) / 256)), dim3(256), 0, st, mat, nf, first);
+	hipLaunchKernelGGL(k_region_rank, dim3(1), dim3(256), 0, st, (const uint32_t*)first, rank, n_regions, status);
+	if (nf) hipLaunchKernelGGL(k_ingest_face_region, dim3((unsigned)(((uint64_t)nf + 511) / 512)), dim3(256), 0, st, mat, nf, (const uint32_t*)rank, face_reg);
 }
 
 }   // namespace dev

@@ -187,6 +187,18 @@ void launch_ingest_pack(hipStream_t st, const PackCols &p, uint32_t n, const uin
 // first_of[n], masks / counts[(n + 63) / 64], wave_start[(n + 63) / 64 + 1] (last: the output vertices)
 void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start);
 void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row);
+// ... with corner lists (hry_mesh_from_device_corners): further bits of IngestStatus::err
+constexpr uint32_t kIngestBadTexIndex = 4, kIngestBadNormalIndex = 8, kIngestManyRegions = 16;
+constexpr uint32_t kIngestMaterials = 65536, kIngestMaxRegions = 128;
+// the two slots of corner_attr: the index buffer of the slot's list (nullptr: unused, the slot holds 0), its rows, the weld's map of
+// the list (or nullptr) and the bit an index outside [0, rows) raises
+struct CornerSlots { const void *idx[2]; const uint32_t *remap[2]; uint32_t rows[2], bad[2]; };
+void launch_ingest_corner_attr(hipStream_t st, const CornerSlots &cs, bool idx64, uint32_t ne, uint32_t *corner_attr, IngestStatus *status);
+void launch_ingest_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
+// face regions from a material per face: first[kIngestMaterials] filled with 0xff and rank[kIngestMaterials] zeroed before; the
+// number of distinct materials goes to *n_regions, more than kIngestMaxRegions raises kIngestManyRegions
+void launch_ingest_regions(hipStream_t st, const uint16_t *mat, uint32_t nf, uint32_t *first, uint32_t *rank, uint32_t *n_regions, uint16_t *face_reg,
+                           IngestStatus *status);
 
 }   // namespace dev
 }   // namespace hry

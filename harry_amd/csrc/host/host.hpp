@@ -38,6 +38,10 @@ void print_component(std::string &o, const AttrList &L, const uint8_t *rec, int 
 // ---- obj_io.cpp (formats/obj/reader.rl:108-299, writer.cc:20-132): meshes with general bindings (mesh.hpp Bindings)
 Mesh *mesh_from_obj(const uint8_t *buf, size_t n, const char *directory);   // directory: where "mtllib" files are looked up
 void mesh_to_obj(const Mesh &m, ByteSink &out);
+// the list the reader creates for "v" / "vt" / "vn" lines of n values: float components, POS (+ COLOR from component 3 on when n > 4) /
+// TEX / NORMAL, vertex or corner target -- shared with the constructor from device buffers (device/ingest.cpp)
+enum { OBJ_VERTEX = 0, OBJ_TEX = 1, OBJ_NORMAL = 2 };
+AttrList obj_list_layout(int kind, int n);
 
 // ---- context numbering of a .hry stream (formats/hry/models.h:183-237), shared with the device code
 enum {

@@ -26,10 +26,23 @@
 #include "host.hpp"
 
 namespace hry {
-namespace {
 
 enum { I_POS = 0, I_NORMAL = 1, I_COLOR = 2, I_TEX = 16 };   // structs/mixing.h:20-39
-enum { K_VERTEX = 0, K_TEX = 1, K_NORMAL = 2, NO_LIST = 9 };
+enum { K_VERTEX = OBJ_VERTEX, K_TEX = OBJ_TEX, K_NORMAL = OBJ_NORMAL, NO_LIST = 9 };
+
+AttrList obj_list_layout(int kind, int n)   // reader.rl:132-148
+{
+	AttrList L;
+	L.target = kind == K_VERTEX ? 1 : 2;
+	static const int base[3] = { I_POS, I_TEX, I_NORMAL };
+	for (int i = 0; i < n; ++i) {
+		L.add_comp(C_FLOAT);
+		L.add_interp(kind == K_VERTEX && n > 4 && i >= 3 ? I_COLOR : base[kind], i);
+	}
+	return L;
+}
+
+namespace {
 
 [[noreturn]] void syntax() { throw Error(HRY_E_FORMAT, "Unable to parse this OBJ file"); }
 
@@ -113,18 +126,11 @@ struct Loader {
 		m.bind = Bindings();
 		m.bind.nb_face = 0; m.bind.nb_vtx = 1; m.bind.nb_corner = 2;   // reader.rl:257
 	}
-	int list_for(int kind, int n)   // reader.rl:132-148
+	int list_for(int kind, int n)
 	{
 		int &l = list_of[kind][n];
 		if (l != NO_LIST) return l;
-		AttrList L;
-		L.target = kind == K_VERTEX ? 1 : 2;
-		static const int base[3] = { I_POS, I_TEX, I_NORMAL };
-		for (int i = 0; i < n; ++i) {
-			L.add_comp(C_FLOAT);
-			L.add_interp(kind == K_VERTEX && n > 4 && i >= 3 ? I_COLOR : base[kind], i);
-		}
-		m.lists.push_back(std::move(L));
+		m.lists.push_back(obj_list_layout(kind, n));
 		rec.emplace_back();
 		return l = (int)m.lists.size() - 1;
 	}

@@ -15,6 +15,7 @@
  *   hry_bounds          <- quant::set_bounds(Attrs&)                              structs/quant.h:30-44 (called by ply/reader.cc:428)
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
+ *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -286,7 +287,7 @@ int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_ren
  *     unreferenced row stays a vertex, a face that collapses keeps its corners).  d_remap (NULL, or nv u32 of device memory) receives
  *     the output vertex of every input row; hry_mesh_nv is the welded count.  The result equals hry_mesh_from_arrays of the welded
  *     arrays.  Welding with v_ncomp == 0 is HRY_E_ARG.
- * General bindings (OBJ regions, corner lists) are out of scope: the result always has the PLY layout. */
+ * The result always has the PLY layout; general bindings (OBJ regions, corner lists) are hry_mesh_from_device_corners' below. */
 typedef struct hry_dev_column {
     const void *data;     /* device memory of ctx's device, aligned to the type's size */
     uint64_t stride;      /* bytes between rows: a non-zero multiple of the type's size */
@@ -297,7 +298,55 @@ typedef struct hry_dev_column {
 int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp,
                          uint32_t nf, const uint8_t *d_degrees, const void *d_indices, int index_type, uint64_t n_indices,
                          const hry_dev_column *fcols, int f_ncomp, int flags, uint32_t *d_remap, hry_mesh **out);
-/* 1: ctx holds m's records and connectivity in HBM (hry_mesh_from_device or hry_mesh_upload, nothing on ctx since that displaced
+
+/* hry_mesh_from_device_corners is hry_mesh_from_obj for data that already lives on ctx's device: positions per vertex, texture
+ * coordinates and normals per corner with index buffers of their own, a material per face (the other direction of hry_render_build
+ * for meshes with general bindings).  pos / tex / nrm: the rows of one list as float columns (hry_dev_column as above; type must be
+ * HRY_FLOAT, name is not read) and, per corner, the row it names: `indices` holds n_indices entries of index_type (HRY_UINT or
+ * HRY_LONG), faces in order, corners in order.  tex and nrm may be NULL.  d_degrees: nf uint8 (NULL: every face a triangle);
+ * d_face_material: nf uint16 (NULL: one region).
+ *   Result: a mesh with general bindings of exactly the shape hry_mesh_from_obj creates.  List 0: the positions, vertex target,
+ *     pos->ncomp one of 3, 4, 6, 7, 8 with the reader's interpretations (POS; COLOR from component 3 on when ncomp > 4).  Then tex,
+ *     if given (corner target, TEX, ncomp 2 or 3), then nrm, if given (corner target, NORMAL, ncomp 3).  All components HRY_FLOAT,
+ *     unquantised.  One vertex region binding list 0, vertex v naming record v.  Slots per face / vertex / corner: 0 / 1 / 2, as the
+ *     reader sets them.  Every face region binds the corner lists given, compacted: slot 0 is tex and the next nrm, normals alone sit
+ *     in slot 0; an unused slot of a corner holds 0.  org[c] = pos->indices[c]; slot s of corner c holds the corner's row in that
+ *     slot's list.  Degrees, face offsets and half-edge order as hry_mesh_from_device.
+ *   Face regions: the distinct values of d_face_material, numbered in order of first occurrence over faces 0 .. nf - 1 (what the
+ *     reader does with "usemtl" when every face carries the same kinds of index).  More than 128: HRY_E_UNSUPPORTED.
+ *   Equal to the reader: without HRY_INGEST_WELD the mesh is the one hry_mesh_from_obj builds from the plain text of the same arrays
+ *     ("v" / "vt" / "vn" lines in row order, "f a/b/c" lines, "usemtl" where the material changes), array for array; twins are matched
+ *     on the device by the code hry_mesh_upload uses, so they equal what an upload computes.
+ *   HRY_INGEST_WELD welds every list given on its own: rows equal byte for byte merge (-0.0 and +0.0 stay apart, identical NaN bit
+ *     patterns merge), output records are numbered in order of first occurrence over the list's rows, the corners' indices go through
+ *     the list's map; unreferenced rows stay records (of positions: vertices), faces are kept as they are.  The result equals the
+ *     unwelded constructor applied to the welded arrays.  With all three `indices` equal this inverts hry_render_build's unweld:
+ *     indices into one table of (position, uv, normal) rows become one connectivity plus shared corner records.
+ *   d_remap: NULL, or three pointers (0 pos, 1 tex, 2 nrm; each NULL or `rows` u32 of device memory) that receive the output record
+ *     of every input row (the identity without HRY_INGEST_WELD).
+ *   Residency: on return ctx holds what hry_mesh_upload would have put there for this mesh -- the records of every list, org, twins,
+ *     face offsets and the binding tables -- under one token shared with the mesh, so hry_mesh_resident is 1 and hry_bounds /
+ *     hry_requant / hry_encode on ctx upload nothing for it, in both profiles.  The host copies are filled too.  Input buffers are
+ *     read on ctx's stream and not kept.
+ *   Refusals (*out stays NULL, ctx stays usable; its earlier resident mesh may be displaced): a row index out of range, a negative
+ *     HRY_LONG too: HRY_E_ARG, "vertex index out of range" / "texture index out of range" / "normal index out of range" by the
+ *     list; sum(degrees) != n_indices, a pointer that is not device memory of ctx's device, a misaligned or zero-stride column, a
+ *     column type other than HRY_FLOAT, an ncomp outside the sets above, pos == NULL, a bad index_type, unknown flags: HRY_E_ARG; a
+ *     degree outside 3..255, more than 2^32 - 1 half-edges: HRY_E_UNSUPPORTED.  The checks run on the device into one status word
+ *     that is read back once, with the welded counts and the number of regions; nothing is written out of bounds on the way.
+ * Out of scope: several vertex lists or regions (the reader's "v" lines of different widths), face lists, components that are not
+ * floats, faces that differ in the kinds of index they carry. */
+typedef struct hry_dev_rows {
+    const hry_dev_column *cols;   /* ncomp columns; type must be HRY_FLOAT; name is not read (may be NULL) */
+    int32_t ncomp;
+    uint32_t rows;
+    const void *indices;          /* n_indices entries of index_type, faces in order, corners in order */
+} hry_dev_rows;                   /* 24 bytes */
+int hry_mesh_from_device_corners(hry_ctx *ctx, const hry_dev_rows *pos, const hry_dev_rows *tex /* or NULL */,
+                                 const hry_dev_rows *nrm /* or NULL */, uint32_t nf, const uint8_t *d_degrees,
+                                 int index_type, uint64_t n_indices, const uint16_t *d_face_material /* or NULL */,
+                                 int flags, uint32_t *const d_remap[3] /* or NULL; entries may be NULL */, hry_mesh **out);
+/* 1: ctx holds m's records and connectivity in HBM (hry_mesh_from_device[_corners] or hry_mesh_upload, nothing on ctx since that displaced
  * them), so hry_bounds / hry_requant / hry_encode on ctx upload nothing for m */
 int hry_mesh_resident(const hry_ctx *ctx, const hry_mesh *m);
 

@@ -7,7 +7,12 @@
            constructor + upload of the unwelded soup (the host path has no weld)
 and the chunked encode (-l1 -q14) after either path (encode_ms; the soup: after the ingest only), with the check that both paths give
 the same container.  Warm-up runs
-first.  Nothing is gated on these numbers."""
+first.  Nothing is gated on these numbers.
+
+--obj: a textured scene instead (hry_mesh_from_device_corners, Codec.corner_mesh_from_tensors): og.scene(mg.torus(200, 200, seed=2),
+normals="smooth", tex="atlas", charts=7) -- 40 000 vertices, 80 000 triangles, a texture and a normal index per corner -- built from
+tensors that hold the reader's own arrays, unwelded (same_container: the chunked container equals the reader's mesh's) and welded
+(every list on its own; records: what is left of every list), against Mesh.from_obj of the text + Codec.upload on the host (host_ms; obj_bytes: the size of the text)."""
 import argparse
 import json
 import os
@@ -22,6 +27,7 @@ import torch  # noqa: E402
 
 from harry_amd import codec as hc  # noqa: E402
 from harry_amd import meshgen as mg  # noqa: E402
+from harry_amd import objgen as og  # noqa: E402
 
 QUANT = [(1, -1, 14)]
 
@@ -67,12 +73,54 @@ def measure(cx, to_device, to_host, warmup, repeats, encode_host=True):
     return out
 
 
+def obj_mode(args, dev):
+    sc = og.scene(mg.torus(200, 200, seed=2), normals="smooth", tex="atlas", charts=7)
+    ref = hc.Mesh.from_obj(sc.obj, "")
+    cattr = ref.bindings(2)
+    rows = [torch.from_numpy(ref.list_data(l).view(np.float32).copy()).to(dev) for l in range(3)]
+    idx = [torch.from_numpy(a.astype(np.int32).reshape(-1, 3)).to(dev) for a in (ref.org(), cattr[:, 0], cattr[:, 1])]
+    torch.cuda.synchronize()
+    cx = hc.Codec(0)
+
+    def device(weld):
+        return cx.corner_mesh_from_tensors(rows[0], idx[0], uv=rows[1], uv_idx=idx[1], normals=rows[2], normal_idx=idx[2], weld=weld)
+    try:
+        want = cx.write_hry(ref, profile=hc.PROFILE_CHUNKED)
+        out = {"nv": ref.nv, "nf": ref.nf, "obj_bytes": len(sc.obj), "repeats": args.repeats}
+        for name, weld in (("unwelded", False), ("welded", True)):
+            ev, wall = [], []
+            for i in range(args.warmup + args.repeats):
+                mesh, e, w = timed(cx, lambda: device(weld))
+                if i >= args.warmup:
+                    ev.append(e); wall.append(w)
+            out[name] = {"ingest_ms": statistics.median(ev), "ingest_wall_ms": statistics.median(wall), "ingest_ms_min": min(ev),
+                         "records": [mesh.list_count(l) for l in range(3)]}
+            if not weld:   # (the weld merges what the six-digit text made equal: another mesh, checked by its decode only)
+                out[name]["same_container"] = cx.write_hry(mesh, profile=hc.PROFILE_CHUNKED) == want
+            else:
+                back = cx.read_hry(cx.write_hry(mesh, profile=hc.PROFILE_CHUNKED))
+                out[name]["decodes"] = (back.nv, back.nf, back.ne) == (mesh.nv, mesh.nf, mesh.ne)
+        host = []
+        for i in range(args.warmup + args.repeats):
+            t0 = time.perf_counter()
+            cx.upload(hc.Mesh.from_obj(sc.obj, ""))
+            if i >= args.warmup:
+                host.append((time.perf_counter() - t0) * 1e3)
+        out["host_ms"] = statistics.median(host)
+    finally:
+        cx.close()
+    print(json.dumps({"obj_scene_torus200": out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--obj", action="store_true", help="the textured scene through hry_mesh_from_device_corners instead")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if args.obj:
+        return obj_mode(args, dev)
     m = mg.cfg2_torus_1m()
     pos_np = np.ascontiguousarray(np.stack([m.verts[k] for k in "xyz"], axis=1))
     tri_np = m.indices.reshape(-1, 3)
