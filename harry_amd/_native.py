@@ -64,6 +64,9 @@ FLAG_HOST_RECURRENCE = 1
 FLAG_DEVICE_RECURRENCE = 2
 FLAG_PARTIAL = 4
 FLAG_KEEP_MESH = 8
+FLAG_ORDER = 16
+NO_ELEMENT = 0xFFFFFFFF
+ORDER_TO_DECODED, ORDER_TO_SOURCE = 0, 1
 INGEST_WELD = 1
 
 _lib = None
@@ -164,6 +167,12 @@ def load():
     L.hry_mesh_from_device_corners.argtypes = [vp, C.POINTER(DevRows), C.POINTER(DevRows), C.POINTER(DevRows), C.c_uint32, vp, C.c_int, C.c_uint64, vp,
                                                C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.hry_mesh_resident.restype = C.c_int; L.hry_mesh_resident.argtypes = [vp, vp]
+    L.hry_order_take.restype = C.c_int; L.hry_order_take.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hry_order_get.restype = C.c_int; L.hry_order_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.hry_order_copy.restype = C.c_int; L.hry_order_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
+    L.hry_order_apply.restype = C.c_int
+    L.hry_order_apply.argtypes = [vp, vp, C.c_char_p, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.hry_order_free.argtypes = [vp]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

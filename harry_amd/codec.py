@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
-from ._native import FLAG_DEVICE_RECURRENCE, FLAG_HOST_RECURRENCE, FLAG_KEEP_MESH, FLAG_PARTIAL, HryError, PROFILE_CHUNKED, PROFILE_COMPAT  # noqa: F401
+from ._native import FLAG_DEVICE_RECURRENCE, FLAG_HOST_RECURRENCE, FLAG_KEEP_MESH, FLAG_ORDER, FLAG_PARTIAL, NO_ELEMENT, HryError, PROFILE_CHUNKED, PROFILE_COMPAT  # noqa: F401
 
 TYPE_NP = {0: "<f4", 1: "<f8", 2: "<u8", 3: "<i8", 4: "<u4", 5: "<i4", 6: "<u2", 7: "<i2", 8: "u1", 9: "i1"}
 TYPE_SIZE = {0: 4, 1: 8, 2: 8, 3: 8, 4: 4, 5: 4, 6: 2, 7: 2, 8: 1, 9: 1}
@@ -347,12 +347,21 @@ class Codec:
     def upload(self, mesh: Mesh):
         nat.check(nat.load().hry_mesh_upload(self.h, mesh.h))
 
-    def write_hry(self, mesh: Mesh, profile: int = PROFILE_COMPAT, chunk_syms: int = 0, keep_stages: bool = False, flags: int = 0, as_buffer: bool = False):
-        """as_buffer: return the library's buffer as it is (nat.NativeBuffer: what a C caller of hry_encode holds) instead of bytes"""
-        o = nat.Opts(profile, chunk_syms, int(keep_stages), flags, 0, 0)
+    def write_hry(self, mesh: Mesh, profile: int = PROFILE_COMPAT, chunk_syms: int = 0, keep_stages: bool = False, flags: int = 0, as_buffer: bool = False,
+                  return_order: bool = False):
+        """as_buffer: return the library's buffer as it is (nat.NativeBuffer: what a C caller of hry_encode holds) instead of bytes.
+        return_order: return (data, Order) -- the numbering maps between `mesh` and what read_hry(data) gives (HRY_FLAG_ORDER)"""
+        o = nat.Opts(profile, chunk_syms, int(keep_stages), flags | (FLAG_ORDER if return_order else 0), 0, 0)
         p, n = C.c_void_p(), C.c_size_t()
         nat.check(nat.load().hry_encode(self.h, mesh.h, C.byref(o), C.byref(p), C.byref(n)))
-        return nat.take(p, n.value, as_buffer)
+        data = nat.take(p, n.value, as_buffer)
+        return (data, self.take_order(mesh)) if return_order else data
+
+    def take_order(self, mesh: Mesh) -> "Order":
+        """the numbering maps of the write_hry(mesh, flags=FLAG_ORDER) that was the last call on this codec (hry_order_take)"""
+        h = C.c_void_p()
+        nat.check(nat.load().hry_order_take(self.h, mesh.h, C.byref(h)))
+        return Order(self, h, mesh.nlists if mesh.general else 0)
 
     def read_hry(self, data: bytes, keep_stages: bool = False, shard=(0, 0), partial: bool = False) -> Mesh:
         """shard = (index, count): of a sharded container decode only the segments i with i % count == index.
@@ -596,6 +605,88 @@ class Codec:
         return nat.take_bytes(p, n.value)
 
 
+class Order:
+    """The numbering maps of one encode (include/harry_amd.h: hry_order_take): which element of read_hry(write_hry(mesh)) every
+    vertex, face, half-edge ("corner") and -- with general bindings -- record of list l ("list<l>") of `mesh` becomes, and the inverses
+    ("<name>_inv": source element of every decoded element).  u32 tables in HBM, NO_ELEMENT where an element was never coded (a
+    vertex no face names) or a decoded row is filler.  The tables stay valid whatever the codec does later, until close()."""
+
+    KINDS = ("vertex", "face", "corner")
+
+    def __init__(self, codec: "Codec", handle, nlists: int = 0):
+        self.codec, self.h = codec, handle
+        self.names = tuple(n + sfx for n in self.KINDS + tuple(f"list{l}" for l in range(nlists)) for sfx in ("", "_inv"))
+
+    def close(self):
+        if getattr(self, "h", None):
+            nat.load().hry_order_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def rows(self, name: str) -> int:
+        """rows of a map; 0: there is no such map"""
+        rows = C.c_uint64()
+        nat.check(nat.load().hry_order_get(self.h, name.encode(), None, C.byref(rows)))
+        return rows.value
+
+    def data_ptr(self, name: str) -> int:
+        """device address of a map (u32 [rows]); 0 when absent"""
+        dev, rows = C.c_void_p(), C.c_uint64()
+        nat.check(nat.load().hry_order_get(self.h, name.encode(), C.byref(dev), C.byref(rows)))
+        return dev.value or 0
+
+    def numpy(self, name: str) -> np.ndarray:
+        """a map as a host array (uint32)"""
+        a = np.empty(self.rows(name), np.uint32)
+        nat.check(nat.load().hry_order_copy(self.codec.h, self.h, name.encode(), a.ctypes.data, 0))
+        return a
+
+    def tensor(self, name: str):
+        """a map as a torch int64 tensor on the codec's device, ready for indexing; NO_ELEMENT becomes -1"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+        t = torch.empty((self.rows(name),), dtype=torch.int32, device=dev)
+        nat.check(nat.load().hry_order_copy(self.codec.h, self.h, name.encode(), t.data_ptr(), 1))
+        w = t.to(torch.int64)
+        return torch.where(t == -1, w, w & 0xFFFFFFFF)
+
+    def _apply(self, t, kind: str, direction: int, out):
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+
+        def rows_of(x, what):
+            if not isinstance(x, torch.Tensor) or x.device != dev or x.dim() < 1:
+                raise HryError(nat.E_ARG, f"{what}: a torch tensor on {dev} with at least one dimension")
+            if x.shape[0] > 1 and x.dim() > 1 and not x[0].is_contiguous():
+                raise HryError(nat.E_ARG, f"{what}: the inner dimensions must be contiguous")
+            return x.stride(0) * x.element_size() if x.shape[0] > 1 else max(x[0].numel(), 1) * x.element_size()
+        src_stride = rows_of(t, "t")
+        if out is None:
+            out = torch.empty(t.shape, dtype=t.dtype, device=dev)
+        elif out.shape != t.shape or out.dtype != t.dtype:
+            raise HryError(nat.E_ARG, "out: the shape and dtype of t")
+        dst_stride = rows_of(out, "out")
+        row_bytes = (t[0].numel() if t.shape[0] else 1) * t.element_size()
+        if t.shape[0] == 0 and self.rows(kind) == 0:
+            return out
+        torch.cuda.current_stream(dev).synchronize()   # (the caller's tensors may still be written by torch's own stream)
+        nat.check(nat.load().hry_order_apply(self.codec.h, self.h, kind.encode(), direction, t.data_ptr(), src_stride, out.data_ptr(), dst_stride,
+                                             row_bytes, t.shape[0]))
+        return out
+
+    def to_decoded(self, t, kind: str = "vertex", out=None):
+        """rows in source order -> rows in decoded order: result[j] = t[kind_inv[j]], zero bytes where the decoded row is filler.
+        t: a torch tensor on the codec's device of any dtype, one row per source element, inner dimensions contiguous, any row
+        stride; out: a tensor of the same shape and dtype to fill instead of a new one (only its rows' own bytes are written)"""
+        return self._apply(t, kind, nat.ORDER_TO_DECODED, out)
+
+    def to_source(self, t, kind: str = "vertex", out=None):
+        """rows in decoded order -> rows in source order: result[i] = t[kind[i]], zero bytes where element i was never coded"""
+        return self._apply(t, kind, nat.ORDER_TO_SOURCE, out)
+
+
 class MultiCodec:
     """Several device contexts driven from this one process (include/harry_amd.h: hry_encode_sharded / hry_decode_sharded): the
     reference's single entry with N devices behind it.  devices: one index per context; an index may repeat (contexts that share
@@ -615,12 +706,13 @@ class MultiCodec:
     def _handles(self):
         return (C.c_void_p * len(self.ctx))(*[c.h for c in self.ctx])
 
-    def write_hry(self, mesh: Mesh, quants=(), clear: bool = False, n_shards: int = 0, chunk_syms: int = 0, keep_mesh: bool = False, as_buffer: bool = False):
+    def write_hry(self, mesh: Mesh, quants=(), clear: bool = False, n_shards: int = 0, chunk_syms: int = 0, keep_mesh: bool = False, as_buffer: bool = False,
+                  return_order: bool = False):
         """plan + extract + bounds of the whole mesh + quantisation + encode of every shard on its context + merge: ONE .hry v0.3.
-        keep_mesh: do not store the combined bounds in `mesh`"""
+        keep_mesh: do not store the combined bounds in `mesh`; return_order: refused (E_UNSUPPORTED): a sharded encode builds no numbering maps"""
         qs = list(quants)
         arr = (nat.Quant * max(len(qs), 1))(*[nat.Quant(int(l), int(c), int(b)) for l, c, b in qs])
-        o = nat.Opts(PROFILE_CHUNKED, chunk_syms, 0, FLAG_KEEP_MESH if keep_mesh else 0, 0, int(n_shards))
+        o = nat.Opts(PROFILE_CHUNKED, chunk_syms, 0, (FLAG_KEEP_MESH if keep_mesh else 0) | (FLAG_ORDER if return_order else 0), 0, int(n_shards))
         p, n, t = C.c_void_p(), C.c_size_t(), nat.ShardTiming()
         nat.check(nat.load().hry_encode_sharded(self._handles(), len(self.ctx), mesh.h, arr, len(qs), int(clear), C.byref(o), C.byref(p), C.byref(n), C.byref(t)))
         self.last = t.asdict()

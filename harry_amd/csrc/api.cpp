@@ -1,4 +1,5 @@
 // C ABI of libharry_amd.so (include/harry_amd.h).  Thin: argument checks, exception -> status translation.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -11,6 +12,7 @@ struct hry_ctx { Context cx; explicit hry_ctx(int d) : cx(d) {} };
 struct hry_mesh { Mesh m; };
 struct hry_plan { ShardPlan p; };
 struct hry_render { RenderResult r; };
+struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_walk {
 	WalkResult w; uint32_t info[2]; std::vector<uint8_t> vplanes, fplanes; std::vector<uint32_t> seg_start, seg_level;
 	mutable std::vector<uint8_t> op_sym, op_class;   // unpacked from w.op_sc on first request
@@ -37,8 +39,11 @@ static thread_local std::string g_last_error;
 
 // the decode's buffers in HBM stop being the mesh's for hry_render_build (render.cpp) at the next call on the context, and at
 // every call that changes the mesh
-static void touched(hry_ctx *ctx) { if (ctx) ctx->cx.render_token = 0; }
-static void touched(hry_mesh *m) { if (m) m->m.render_token = 0; }
+// ... and the numbering maps of an encode with HRY_FLAG_ORDER stop being hry_order_take's in the same way (order.cpp)
+static void order_lost(hry_ctx *ctx) { if (ctx) { ctx->cx.order_token = 0; ctx->cx.want_order = false; ctx->cx.order.reset(); ctx->cx.order_lists.clear(); } }
+static void touched(hry_ctx *ctx) { if (ctx) { ctx->cx.render_token = 0; order_lost(ctx); } }
+static void touched(hry_mesh *m) { if (m) { m->m.render_token = 0; m->m.order_token = 0; } }
+static std::atomic<uint64_t> g_order_tokens{ 1 };
 
 template <typename F> static int guarded(F &&f)
 {
@@ -168,7 +173,7 @@ void hry_mesh_free(hry_mesh *m) { delete m; }
 hry_mesh *hry_mesh_clone(const hry_mesh *m)
 {
 	if (!m) return nullptr;
-	try { hry_mesh *c = new hry_mesh{ m->m }; c->m.device_token = 0; c->m.render_token = 0; return c; }
+	try { hry_mesh *c = new hry_mesh{ m->m }; c->m.device_token = 0; c->m.render_token = 0; c->m.order_token = 0; return c; }
 	catch (...) { g_last_error = "out of memory"; return nullptr; }
 }
 
@@ -222,12 +227,29 @@ int hry_encode(hry_ctx *ctx, hry_mesh *m, const hry_opts *opts, uint8_t **out, s
 		ctx->cx.keep_stages = o.keep_stages != 0;
 		ctx->cx.device_recurrence = (o.flags & HRY_FLAG_DEVICE_RECURRENCE) != 0;
 		ctx->cx.stages.clear();
+		if (o.flags & HRY_FLAG_ORDER) {
+			if (m->m.shard.active() || !m->m.shard.seeds.empty()) throw Error(HRY_E_UNSUPPORTED, "HRY_FLAG_ORDER on a shard: the numbering maps describe a whole mesh");
+			ctx->cx.want_order = true;
+		}
+		// the maps are the last thing an encode with the flag builds (order_build): on success ctx and m share a token until the next
+		// call on either; an encode that throws leaves none
+		struct OrderMark {
+			hry_ctx *ctx; hry_mesh *m; bool ok = false;
+			~OrderMark()
+			{
+				if (ok && ctx->cx.order) ctx->cx.order_token = m->m.order_token = g_order_tokens.fetch_add(1, std::memory_order_relaxed);
+				else order_lost(ctx);
+				ctx->cx.want_order = false;
+				ctx->cx.order_lists.clear();
+			}
+		} mark{ ctx, m };
 		if (o.profile == HRY_PROFILE_CHUNKED) {
 			// straight into the buffer the caller gets: a vector first cost a zero fill, a second set of fresh pages and a copy --
 			// 10 ms of a 75 ms encode of the 12.6 M-triangle share of configs[3] (39 MB of container)
 			ByteSink sink;
 			encode_chunked(ctx->cx, m->m, o.chunk_syms, sink);
 			*out = sink.release(out_len);
+			mark.ok = true;
 			return;
 		}
 		std::vector<uint8_t> v;
@@ -235,6 +257,7 @@ int hry_encode(hry_ctx *ctx, hry_mesh *m, const hry_opts *opts, uint8_t **out, s
 		else throw Error(HRY_E_ARG, "unknown profile");
 		*out = dup_bytes(v);
 		*out_len = v.size();
+		mark.ok = true;
 	});
 }
 int hry_decode(hry_ctx *ctx, const uint8_t *hry, size_t n, const hry_opts *opts, hry_mesh **out)
@@ -260,6 +283,7 @@ int hry_encode_sharded(hry_ctx *const *ctx, int n_ctx, hry_mesh *m, const hry_qu
 	return guarded([&] {
 		hry_opts o = opts ? *opts : hry_opts{};
 		o.profile = opts ? o.profile : HRY_PROFILE_CHUNKED;
+		if (o.flags & HRY_FLAG_ORDER) throw Error(HRY_E_UNSUPPORTED, "HRY_FLAG_ORDER with hry_encode_sharded: the numbering maps of a sharded encode are not built");
 		if (o.profile != HRY_PROFILE_CHUNKED) throw Error(HRY_E_UNSUPPORTED, "the reference's single stream (compat) does not shard: one recurrence over the whole file");
 		std::vector<Context*> cxs;
 		for (int i = 0; i < n_ctx; ++i) { if (!ctx[i]) throw Error(HRY_E_ARG, "null context"); ctx[i]->cx.keep_stages = false; ctx[i]->cx.stages.clear(); cxs.push_back(&ctx[i]->cx); }
@@ -601,6 +625,7 @@ int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_ren
 {
 	if (!ctx || !m || !out) { g_last_error = "null argument"; if (out) *out = nullptr; return HRY_E_ARG; }
 	*out = nullptr;
+	order_lost(ctx);
 	return guarded([&] {
 		std::unique_ptr<hry_render> r(new hry_render());
 		render_build(ctx->cx, m->m, flags, r->r);
@@ -632,6 +657,43 @@ int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_b
 	return HRY_OK;
 }
 void hry_render_free(hry_render *r) { delete r; }
+
+// ---- numbering maps of an encode (order.cpp)
+int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (!ctx->cx.order || ctx->cx.order_token == 0 || ctx->cx.order_token != m->m.order_token) {
+		g_last_error = "hry_order_take: the last call on this context was not a successful hry_encode of this mesh with HRY_FLAG_ORDER (or its maps have been taken)";
+		return HRY_E_ARG;
+	}
+	return guarded([&] {
+		std::unique_ptr<hry_order> o(new hry_order());
+		o->o = std::move(ctx->cx.order);
+		ctx->cx.order_token = 0;
+		*out = o.release();
+	});
+}
+int hry_order_get(const hry_order *o, const char *name, const void **dev, uint64_t *rows)
+{
+	if (!o || !o->o || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const OrderMap *b = o->o->find(name);
+	*rows = b ? b->rows : 0;
+	if (dev) *dev = b && b->rows ? b->p : nullptr;
+	return HRY_OK;
+}
+int hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !o || !o->o || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { order_copy(ctx->cx, *o->o, name, dst, dst_is_device != 0); });
+}
+int hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
+                    uint64_t row_bytes, uint64_t dst_rows)
+{
+	if (!ctx || !o || !o->o || !kind || !d_src || !d_dst) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { order_apply(ctx->cx, *o->o, kind, direction, d_src, src_stride, d_dst, dst_stride, row_bytes, dst_rows); });
+}
+void hry_order_free(hry_order *o) { delete o; }
 
 // ---- meshes from device buffers (ingest.cpp)
 int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,

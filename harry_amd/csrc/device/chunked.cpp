@@ -855,6 +855,12 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 	write_container(cx, dir, restart_sec, ns, d_nbytes, total_bytes, out);
 	HRY_MARK(t_all, "container on the host");
 	if (sharded) { const uint64_t seg_len = out.size() - seg_begin; memcpy(out.data() + seg_len_at, &seg_len, 8); }
+	// HRY_FLAG_ORDER (order.cpp): the orders are whole in HBM where this function copied them up itself -- the pipeline sends them run
+	// by run inside its batches, and order_f stays on the host when no face plane reads it: those go up with the maps
+	if (cx.want_order) {
+		if (sharded || in_place) throw Error(HRY_E_UNSUPPORTED, "HRY_FLAG_ORDER on a shard");
+		order_build(cx, m, w, !piped ? cx.d_order_v.as<uint32_t>() : nullptr, !piped && (ldf.nplanes || m.general) ? cx.d_order_f.as<uint32_t>() : nullptr);
+	}
 
 	if (cx.keep_stages) {
 		cx.stage_put_host("order_v", w.order_v.data(), (size_t)vc * 4);

@@ -767,6 +767,7 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	(void)t_fin;
 	out.insert(out.end(), payload.begin(), payload.end());
 	cx.stage_put_host("payload", payload.data(), payload.size());
+	if (cx.want_order) order_build(cx, m, w, cx.d_order_v.as<uint32_t>(), cx.d_order_f.as<uint32_t>());   // HRY_FLAG_ORDER (order.cpp)
 
 	cx.timing.k_predict_ms = cx.elapsed(1, 2);
 	cx.timing.k_model_ms = cx.elapsed(2, 3);

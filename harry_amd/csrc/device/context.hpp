@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,18 @@ inline double ms_since(Clock::time_point t0) { return std::chrono::duration<doub
 #define HRY_MARK(t0, what) do { if (trace_on()) fprintf(stderr, "%s %8.3f ms  %s\n", kMarkPrefix, ms_since(t0), what); } while (0)
 
 constexpr int kMaxLists = 16;   // attribute lists of one mesh kept in HBM (the OBJ reader creates at most 8)
+
+// order.cpp: the numbering maps of one encode (include/harry_amd.h: hry_order_take); every map lies in the one allocation
+struct OrderMap { std::string name; uint32_t *p = nullptr; uint64_t rows = 0; };
+struct OrderResult {
+	int device = 0;
+	DevBuf block;
+	std::vector<OrderMap> maps;
+	const OrderMap *find(const std::string &name) const { for (const OrderMap &m : maps) if (m.name == name) return &m; return nullptr; }
+	~OrderResult() { if (block.p) (void)hipSetDevice(device); }   // (then the block is freed, on its device)
+};
+// general bindings: where an encode left the records of a list that it coded as data, in creation order (d_idx, in cx.d_gen)
+struct OrderListSource { const uint32_t *d_idx = nullptr; uint32_t nd = 0; };
 
 struct Context {
 	int device = 0;
@@ -82,6 +95,14 @@ struct Context {
 	DevBuf d_pipe, d_nt_val, d_nt_planes;   // EncodePipeline: run tables and twin pairs of the batches; the polygons' triangle counts and their two byte planes
 	std::vector<uint32_t> h_twin_patch;   // (half-edge, twin) pairs on their way to d_patch (upload_repaired_twins)
 	std::vector<uint32_t> inplace_twin_patches;   // a shard coded in place: the half-edges whose twins its walks repaired in the WHOLE mesh's host array (sharded.cpp brings them to the resident copy on another device)
+
+	// HRY_FLAG_ORDER: the running hry_encode builds the numbering maps behind its own work (order.cpp: order_build) and leaves them
+	// in `order` under order_token, which the mesh shares until any other call on the context or the mesh clears it (api.cpp)
+	bool want_order = false;
+	uint64_t order_token = 0;
+	std::unique_ptr<OrderResult> order;
+	std::vector<OrderListSource> order_lists;   // general bindings: filled by the encode's reference pass, read by order_build
+	DevBuf d_order_ws;                          // order_build: orders that the encode did not bring up, degrees, offsets, scan sums
 
 	bool keep_stages = false;
 	bool device_recurrence = false; // HRY_FLAG_DEVICE_RECURRENCE: k_rchain instead of the host core
@@ -189,7 +210,17 @@ bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &ru
 void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out);   // flags: HRY_RENDER_*
 void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
 
+// order.cpp.  order_build: at the end of an encode with cx.want_order -- m's connectivity is in d_foff / d_org (conn_view), w is the
+// encode's walk; d_order_v / d_order_f: the walk's orders where the encode has them whole in HBM, else nullptr (they go up from w);
+// general bindings: cx.order_lists names every list's records in creation order.  Leaves the maps in cx.order, waited for.
+void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t *d_order_v, const uint32_t *d_order_f);
+void order_copy(Context &cx, const OrderResult &o, const char *name, void *dst, bool dst_is_device);
+void order_apply(Context &cx, const OrderResult &o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
+                 uint64_t row_bytes, uint64_t dst_rows);
+
 // ingest.cpp: hry_mesh_from_device (include/harry_amd.h); the result is resident on cx
+// a caller's buffer is device memory of cx's device and, where the runtime can say, [p, p + bytes) lies inside one allocation: else HRY_E_ARG
+void check_device_memory(const Context &cx, const void *p, uint64_t bytes, const std::string &what);
 Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,
                        const void *d_indices, int index_type, uint64_t n_indices, const hry_dev_column *fcols, int f_ncomp, int flags,
                        uint32_t *d_remap);

@@ -326,6 +326,11 @@ void encode_general(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	std::vector<uint8_t> payload;
 	finish_stream(cx, ns, payload);
 	out.insert(out.end(), payload.begin(), payload.end());
+	if (cx.want_order) {   // HRY_FLAG_ORDER (order.cpp): the creation order of every list's records is the host's (collect_events), uploaded with the arena above
+		cx.order_lists.assign(m.lists.size(), OrderListSource{});
+		for (size_t l = 0; l < m.lists.size(); ++l) cx.order_lists[l] = OrderListSource{ (const uint32_t*)(arena + at[l].d_idx), (uint32_t)E.ls[l].d_idx.size() };
+		order_build(cx, m, w, cx.d_order_v.as<uint32_t>(), cx.d_order_f.as<uint32_t>());
+	}
 
 	cx.timing.k_predict_ms = cx.elapsed(1, 2);
 	cx.timing.k_model_ms = cx.elapsed(2, 3);
@@ -595,6 +600,10 @@ again:
 			L.d_idx = (const uint32_t*)(arena + at[l].d_idx); L.d_he = (const uint32_t*)(arena + at[l].d_he); L.d_slot = arena + at[l].d_slot;
 			L.gh = arena + at[l].gh; L.lh = arena + at[l].lh; L.data = arena + at[l].planes;
 		}
+	}
+	if (cx.want_order) {   // HRY_FLAG_ORDER (order.cpp): every list's records in creation order stay where they are in the arena until the encode ends
+		cx.order_lists.assign(nl, OrderListSource{});
+		for (size_t l = 0; l < nl; ++l) cx.order_lists[l] = OrderListSource{ ls[l].d_idx, ls[l].nd };
 	}
 	for (size_t l = 0; l < nl; ++l) {
 		launch_split_bytes(cx.stream, ls[l].gh_vals, ls[l].ng, 4, ls[l].gh);

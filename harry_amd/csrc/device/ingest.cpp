@@ -13,8 +13,6 @@ namespace hry {
 
 using namespace dev;
 
-namespace {
-
 // the caller's buffer: device memory of the context's device, and (where the runtime can say) [p, p + bytes) inside one allocation
 void check_device_memory(const Context &cx, const void *p, uint64_t bytes, const std::string &what)
 {
@@ -28,6 +26,8 @@ void check_device_memory(const Context &cx, const void *p, uint64_t bytes, const
 	if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return; }
 	if ((const uint8_t*)p + bytes > (const uint8_t*)base + size) throw Error(HRY_E_ARG, what + ": extends past the end of its allocation");
 }
+
+namespace {
 
 // the layout of one list (layout_attr_list, as hry_mesh_from_arrays) and where each byte of its records comes from
 PackCols list_from_columns(const Context &cx, AttrList &L, int target, const hry_dev_column *cols, int ncomp, uint32_t rows, const char *what)

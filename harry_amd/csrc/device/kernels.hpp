@@ -93,6 +93,16 @@ void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twi
 // exclusive scan of n counters in three launches (k_scan_*): out[n + 1], out[n] = total; sums: scan_sums_words(n) words of scratch
 size_t scan_sums_words(uint32_t n);
 void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out);
+
+// order.hip: the numbering maps of an encode; every table pre-filled with 0xFF (kNoRank) by the caller
+void launch_order_vertex(hipStream_t st, const uint32_t *order_v, uint32_t n, const uint32_t *org, uint32_t nv, uint32_t *vertex, uint32_t *vertex_inv);
+// deg: the coded faces' degrees in coding order (mixed degrees), or nullptr
+void launch_order_face(hipStream_t st, const ConnView &cv, const uint32_t *order_f, uint32_t n, uint32_t *face, uint32_t *face_inv, uint32_t *deg);
+// doff: exclusive scan of deg (mixed degrees), or nullptr: decoded face j begins at j * cv.udeg
+void launch_order_corner(hipStream_t st, const ConnView &cv, const uint32_t *order_f, const uint32_t *face, const uint32_t *doff, uint32_t *corner, uint32_t *corner_inv);
+void launch_order_records(hipStream_t st, const uint32_t *d_idx, uint32_t nd, uint32_t count, uint32_t *list, uint32_t *list_inv);
+// dst row i = src row map[i] (zero where map[i] is kNoRank), row_bytes of every row; false: more words than one launch covers
+bool launch_order_rows(hipStream_t st, const uint32_t *map, uint64_t rows, const void *src, uint64_t src_stride, void *dst, uint64_t dst_stride, uint64_t row_bytes);
 // connected components of the faces and their tables for the walk on several host threads (twins.hip; driver: analysis.cpp)
 size_t components_workspace_bytes(uint32_t nv, uint32_t nf);
 // where the workspace's parts lie (twins.hip decides; nobody else computes an offset into it): per face the component label (a

@@ -1,0 +1,129 @@
+// Numbering maps of an encode (include/harry_amd.h: hry_order_take; kernels: order.hip).  An encode with HRY_FLAG_ORDER calls
+// order_build once its container is written: everything the maps need is in HBM by then -- the connectivity (d_foff / d_org / d_eface),
+// the walk's orders where the encode's own kernels read them, and, with general bindings, every list's records in creation order
+// (d_idx in the events' arena, whether the host's loop or events.hip made it).  What a path did not bring up whole goes up here from
+// the walk's host arrays: order_f when no face plane reads it, both orders behind the pipelined chunked encode (which sends them
+// run by run inside its batches).  The vertex map is computed from order_v like k_rank's table, not adopted from d_rank: the
+// general paths keep the faces' ranks behind it and the pipelined path fills it by runs, and a scatter of 4 bytes a vertex is not
+// worth a dependency on either.  The result owns one allocation (DevBuf) that no later call on the context touches.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "context.hpp"
+#include "kernels.hpp"
+
+namespace hry {
+
+using namespace dev;
+
+namespace {
+
+constexpr size_t kAlign = 256;
+size_t aligned(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
+
+}   // namespace
+
+void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t *d_order_v, const uint32_t *d_order_f)
+{
+	HIP_OK(hipSetDevice(cx.device));
+	cx.order.reset();
+	const uint32_t nv = m.nv, nf = m.nf, ne = m.ne();
+	const uint32_t vc = (uint32_t)w.order_v.size(), fc = (uint32_t)w.order_f.size();
+	const ConnView cv = cx.conn_view();
+	if (cv.nf != nf || cv.ne != ne) throw Error(HRY_E_INTERNAL, "numbering maps: the context's connectivity is not the encoded mesh's");
+	if (vc > nv || fc > nf) throw Error(HRY_E_INTERNAL, "numbering maps: more coded elements than the mesh has");
+	if (m.general && cx.order_lists.size() != m.lists.size()) throw Error(HRY_E_INTERNAL, "numbering maps: the encode left no record tables");
+	const bool mixed = cv.eface != nullptr;
+
+	// ---- the result: every map and its inverse in one block, filled with HRY_NO_ELEMENT
+	std::unique_ptr<OrderResult> R(new OrderResult());
+	R->device = cx.device;
+	size_t bytes = 0;
+	std::vector<size_t> at;
+	auto add = [&](const std::string &name, uint64_t rows) {
+		for (int inv = 0; inv < 2; ++inv) {
+			OrderMap om;
+			om.name = inv ? name + "_inv" : name; om.rows = rows;
+			R->maps.push_back(om);
+			at.push_back(bytes);
+			bytes += aligned((size_t)rows * 4);
+		}
+	};
+	add("vertex", nv); add("face", nf); add("corner", ne);
+	if (m.general) for (size_t l = 0; l < m.lists.size(); ++l) add("list" + std::to_string(l), m.lists[l].count);
+	R->block.ensure(std::max<size_t>(bytes, 16));
+	for (size_t k = 0; k < R->maps.size(); ++k) R->maps[k].p = (uint32_t*)(R->block.as<uint8_t>() + at[k]);
+	HIP_OK(hipMemsetAsync(R->block.p, 0xff, std::max<size_t>(bytes, 16), cx.stream));
+	uint32_t *vertex = R->maps[0].p, *vertex_inv = R->maps[1].p, *face = R->maps[2].p, *face_inv = R->maps[3].p, *corner = R->maps[4].p, *corner_inv = R->maps[5].p;
+
+	// ---- working arrays: the orders the encode did not leave whole in HBM, the coded faces' degrees, their scan
+	const size_t a_ov = 0, a_of = a_ov + (d_order_v ? 0 : aligned((size_t)vc * 4)), a_deg = a_of + (d_order_f ? 0 : aligned((size_t)fc * 4));
+	const size_t a_doff = a_deg + (mixed ? aligned((size_t)fc * 4) : 0), a_sums = a_doff + (mixed ? aligned(((size_t)fc + 1) * 4) : 0);
+	const size_t ws_bytes = a_sums + (mixed ? aligned(scan_sums_words(fc) * 4) : 0);
+	cx.d_order_ws.ensure(std::max<size_t>(ws_bytes, 16));
+	uint8_t *ws = cx.d_order_ws.as<uint8_t>();
+	if (!d_order_v) {
+		if (vc) HIP_OK(hipMemcpyAsync(ws + a_ov, w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_v = (const uint32_t*)(ws + a_ov);
+	}
+	if (!d_order_f) {
+		if (fc) HIP_OK(hipMemcpyAsync(ws + a_of, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_f = (const uint32_t*)(ws + a_of);
+	}
+	uint32_t *deg = mixed ? (uint32_t*)(ws + a_deg) : nullptr, *doff = mixed ? (uint32_t*)(ws + a_doff) : nullptr;
+
+	launch_order_vertex(cx.stream, d_order_v, vc, cv.org, nv, vertex, vertex_inv);
+	launch_order_face(cx.stream, cv, d_order_f, fc, face, face_inv, deg);
+	if (mixed && fc) launch_excl_scan(cx.stream, deg, fc, (uint32_t*)(ws + a_sums), doff);
+	if (fc) launch_order_corner(cx.stream, cv, d_order_f, face, doff, corner, corner_inv);
+	if (m.general)
+		for (size_t l = 0; l < m.lists.size(); ++l) {
+			const OrderListSource &S = cx.order_lists[l];
+			if (S.nd > m.lists[l].count) throw Error(HRY_E_INTERNAL, "numbering maps: more records created than the list has");
+			launch_order_records(cx.stream, S.d_idx, S.nd, m.lists[l].count, R->maps[6 + 2 * l].p, R->maps[7 + 2 * l].p);
+		}
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipStreamSynchronize(cx.stream));   // (the pageable host arrays above are the walk's: they go with the encode)
+	cx.order = std::move(R);
+}
+
+void order_copy(Context &cx, const OrderResult &o, const char *name, void *dst, bool dst_is_device)
+{
+	const OrderMap *b = o.find(name);
+	if (!b) throw Error(HRY_E_ARG, std::string("no such numbering map: ") + name);
+	if (!b->rows) return;
+	if (!dst) throw Error(HRY_E_ARG, "null destination");
+	if (o.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
+	HIP_OK(hipSetDevice(cx.device));
+	HIP_OK(hipMemcpyAsync(dst, b->p, (size_t)b->rows * 4, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
+	HIP_OK(hipStreamSynchronize(cx.stream));
+}
+
+void order_apply(Context &cx, const OrderResult &o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
+                 uint64_t row_bytes, uint64_t dst_rows)
+{
+	if (direction != HRY_ORDER_TO_DECODED && direction != HRY_ORDER_TO_SOURCE) throw Error(HRY_E_ARG, "unknown direction: HRY_ORDER_TO_DECODED or HRY_ORDER_TO_SOURCE");
+	const std::string k(kind);
+	if (k.size() >= 4 && k.compare(k.size() - 4, 4, "_inv") == 0) throw Error(HRY_E_ARG, "unknown kind: " + k + " (the direction selects the inverse)");
+	// TO_DECODED: dst is indexed by decoded elements, dst row j = src row kind_inv[j]; TO_SOURCE: dst row i = src row kind[i]
+	const OrderMap *map = o.find(direction == HRY_ORDER_TO_DECODED ? k + "_inv" : k);
+	if (!map) throw Error(HRY_E_ARG, "unknown kind: " + k);
+	if (o.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
+	if (row_bytes == 0) throw Error(HRY_E_ARG, "row_bytes is 0");
+	if (src_stride < row_bytes || dst_stride < row_bytes) throw Error(HRY_E_ARG, "a stride below row_bytes");
+	if (dst_rows != map->rows) throw Error(HRY_E_ARG, "dst_rows is " + std::to_string(dst_rows) + ", the map \"" + map->name + "\" has " + std::to_string(map->rows) + " rows");
+	if (!dst_rows) return;
+	if (src_stride > (1ull << 31) || dst_stride > (1ull << 31)) throw Error(HRY_E_ARG, "a stride above 2^31 bytes");   // (rows x stride stays below 2^63)
+	HIP_OK(hipSetDevice(cx.device));
+	const uint64_t src_span = (dst_rows - 1) * src_stride + row_bytes, dst_span = (dst_rows - 1) * dst_stride + row_bytes;
+	check_device_memory(cx, d_src, src_span, "src");
+	check_device_memory(cx, d_dst, dst_span, "dst");
+	const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+	if (s0 < d0 + dst_span && d0 < s0 + src_span) throw Error(HRY_E_ARG, "src and dst overlap");
+	if (!launch_order_rows(cx.stream, map->p, dst_rows, d_src, src_stride, d_dst, dst_stride, row_bytes)) throw Error(HRY_E_UNSUPPORTED, "more than 2^39 words in one move");
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipStreamSynchronize(cx.stream));
+}
+
+}   // namespace hry

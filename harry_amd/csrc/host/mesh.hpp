@@ -210,6 +210,7 @@ struct Mesh {
 	Bindings bind;
 	uint64_t device_token = 0;           // identity of the HBM-resident copy, 0 = none
 	uint64_t render_token = 0;           // identity of the copy a decode left in HBM (Context::render_token), 0 = none
+	uint64_t order_token = 0;            // identity of the numbering maps an encode left on a context (Context::order_token), 0 = none
 	uint32_t declared_ne = 0;            // half-edge count announced by a .hry header (the connectivity follows later)
 	ShardInfo shard;                     // set by shard_extract: this mesh is a shard of a larger one
 	std::vector<ShardRun> covered;       // set by the decoder of a sharded container: the runs of the whole numbering that were decoded

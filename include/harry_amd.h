@@ -16,6 +16,7 @@
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
+ *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -349,6 +350,51 @@ int hry_mesh_from_device_corners(hry_ctx *ctx, const hry_dev_rows *pos, const hr
 /* 1: ctx holds m's records and connectivity in HBM (hry_mesh_from_device[_corners] or hry_mesh_upload, nothing on ctx since that displaced
  * them), so hry_bounds / hry_requant / hry_encode on ctx upload nothing for m */
 int hry_mesh_resident(const hry_ctx *ctx, const hry_mesh *m);
+
+/* ---- numbering maps of an encode: source order <-> decoded order -----------------------------------------------------
+ * The decoder numbers vertices, faces and half-edges in traversal order (cbm/decoder.h:48,75,145,162), and with general bindings
+ * the records of every list in creation order: hry_decode(hry_encode(m)) is m up to a permutation of vertices, of faces, of every
+ * list's records, and a rotation of every face.  hry_encode with HRY_FLAG_ORDER keeps those permutations on ctx's device, and
+ * hry_order_take hands them out as a handle that owns its memory.  Maps by name, each u32 in HBM:
+ *   "vertex"    [nv]  decoded vertex of every source vertex
+ *   "face"      [nf]  decoded face of every source face
+ *   "corner"    [ne]  decoded half-edge of every source half-edge
+ *   "list<l>"   [records of list l]  general bindings only (l in decimal): decoded record of every source record.  In the PLY layout
+ *                     list 1 is "vertex" and list 0 is "face", and the "list" names are absent
+ *   "<name>_inv"      the inverse: its rows are the decoded mesh's elements as its header declares them, its values source elements
+ * Contract, with D = hry_decode(hry_encode(m)) in either profile and m's twins as hry_encode left them:
+ *   D.org[corner[c]] == vertex[m.org[c]] and D.twin[corner[c]] == corner[m.twin[c]] for every half-edge c; the corners of source
+ *   face f are the corners of decoded face face[f], same degree, same cyclic order, another start; the record bytes of D at
+ *   vertex[v] / face[f] / list<l>[r] are m's at v / f / r (m holds the quantised values already); every binding table of D at a
+ *   mapped element holds the mapped record; D's face region at face[f] is m's at f.
+ * A vertex no face names and a record no element names are never coded: they map to HRY_NO_ELEMENT, and so do the decoded mesh's
+ * filler rows in the inverse.  Everywhere else the maps are bijections: x_inv[x[i]] == i.  Both profiles give the same maps, and
+ * the flag changes neither the container's bytes nor the mesh's twins.
+ *   hry_order_take   valid when the last call on ctx was a successful hry_encode of m with HRY_FLAG_ORDER; anything else -- no flag,
+ *                    another call on ctx in between, a second take -- is HRY_E_ARG.  The handle's one device allocation stays valid
+ *                    whatever the context does later; free it before the context.
+ *   hry_order_get    a map by name: device address and rows (rows 0: absent)
+ *   hry_order_copy   the whole map to dst (device or host memory) on ctx's stream; returns when it is there
+ *   hry_order_apply  moves rows of row_bytes bytes through the map `kind` ("vertex", "face", "corner", "list<l>") on ctx's stream and
+ *                    returns when it is done.  HRY_ORDER_TO_DECODED: dst row j = src row kind_inv[j]; HRY_ORDER_TO_SOURCE: dst row
+ *                    i = src row kind[i]; a row whose map entry is HRY_NO_ELEMENT becomes zero bytes.  Row r of a buffer starts
+ *                    r * stride bytes behind its pointer; only the row_bytes of each dst row are written.  dst_rows must be the row
+ *                    count of the map that indexes dst, and src holds as many rows.  A stride below row_bytes, row_bytes 0, a null
+ *                    pointer, a pointer that is not memory of ctx's device, overlapping src and dst ranges, an unknown kind or
+ *                    direction: HRY_E_ARG, and ctx stays usable.
+ * HRY_FLAG_ORDER on a shard (a mesh that carries runs) and in hry_encode_sharded is HRY_E_UNSUPPORTED. */
+#define HRY_FLAG_ORDER 16            /* hry_encode: keep the numbering maps of this encode for hry_order_take */
+#define HRY_NO_ELEMENT 0xFFFFFFFFu
+typedef struct hry_order hry_order;
+int  hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out);
+int  hry_order_get(const hry_order *o, const char *name, const void **dev, uint64_t *rows);   /* u32 [rows] in HBM; rows 0: absent */
+int  hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst, int dst_is_device);
+#define HRY_ORDER_TO_DECODED 0
+#define HRY_ORDER_TO_SOURCE  1
+int  hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int direction,
+                     const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
+                     uint64_t row_bytes, uint64_t dst_rows);
+void hry_order_free(hry_order *o);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
