@@ -40,6 +40,17 @@ class DevRows(C.Structure):
     _fields_ = [("cols", C.POINTER(DevColumn)), ("ncomp", C.c_int32), ("rows", C.c_uint32), ("indices", C.c_void_p)]
 
 
+class CompError(C.Structure):
+    """hry_comp_error: the error of one component of a comparison (hry_distortion_component)"""
+    _fields_ = [("max_abs", C.c_double), ("sum_sq", C.c_double), ("a_min", C.c_double), ("a_max", C.c_double), ("compared", C.c_uint64),
+                ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("changed", C.c_uint64), ("argmax", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PosError(C.Structure):
+    """hry_pos_error: the Euclidean displacement of the positions (hry_distortion_position)"""
+    _fields_ = [("max_dist", C.c_double), ("sum_sq_dist", C.c_double), ("compared", C.c_uint64), ("argmax", C.c_uint32), ("list", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("host_walk_ms", C.c_double), ("h2d_ms", C.c_double), ("device_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("total_ms", C.c_double), ("k_rchain_ms", C.c_double), ("k_model_ms", C.c_double), ("k_predict_ms", C.c_double),
@@ -68,6 +79,7 @@ FLAG_ORDER = 16
 NO_ELEMENT = 0xFFFFFFFF
 ORDER_TO_DECODED, ORDER_TO_SOURCE = 0, 1
 INGEST_WELD = 1
+DISTORTION_ROWS = 1
 
 _lib = None
 
@@ -173,6 +185,14 @@ def load():
     L.hry_order_apply.restype = C.c_int
     L.hry_order_apply.argtypes = [vp, vp, C.c_char_p, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64]
     L.hry_order_free.argtypes = [vp]
+    L.hry_distortion_build.restype = C.c_int; L.hry_distortion_build.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.hry_distortion_component.restype = C.c_int; L.hry_distortion_component.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CompError)]
+    L.hry_distortion_position.restype = C.c_int; L.hry_distortion_position.argtypes = [vp, C.POINTER(PosError)]
+    L.hry_distortion_position_component.restype = C.c_int; L.hry_distortion_position_component.argtypes = [vp]
+    L.hry_distortion_get.restype = C.c_int; L.hry_distortion_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.hry_distortion_copy.restype = C.c_int; L.hry_distortion_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
+    L.hry_distortion_stat.restype = C.c_int; L.hry_distortion_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hry_distortion_free.argtypes = [vp]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

@@ -12,6 +12,7 @@ All computation happens in libharry_amd.so (host C++ for the walk / PLY I/O, HIP
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -577,6 +578,15 @@ class Codec:
         mesh = Mesh(h)
         return (mesh, tuple(remaps)) if return_remap else mesh
 
+    def distortion(self, src: Mesh, other: Mesh, order: "Order | None" = None, rows: bool = False) -> "Distortion":
+        """hry_distortion_build: the error of `other` against `src`, component by component, on the device.  order: the numbering
+        maps of the encode that relates them (write_hry(..., return_order=True)), None: row i against row i.  rows: also one error
+        value per row of every compared list ("error<l>", float32 in HBM)"""
+        h = C.c_void_p()
+        nat.check(nat.load().hry_distortion_build(self.h, src.h, other.h, order.h if order is not None else None,
+                                                  nat.DISTORTION_ROWS if rows else 0, C.byref(h)))
+        return Distortion(self, h)
+
     def resident(self, mesh: Mesh) -> bool:
         """hry_mesh_resident: this context holds the mesh's records and connectivity in HBM (an encode uploads nothing for it)"""
         return bool(nat.load().hry_mesh_resident(self.h, mesh.h))
@@ -685,6 +695,80 @@ class Order:
     def to_source(self, t, kind: str = "vertex", out=None):
         """rows in decoded order -> rows in source order: result[i] = t[kind[i]], zero bytes where element i was never coded"""
         return self._apply(t, kind, nat.ORDER_TO_SOURCE, out)
+
+
+class Distortion:
+    """The error of one mesh against another (include/harry_amd.h: hry_distortion_build): per component the largest error and where
+    it is, the sum of squared errors, the range of the source's values and the counts; the Euclidean displacement of the positions;
+    with rows=True one error value per row ("error<l>") in HBM.  Valid until close(), whatever the codec does later."""
+
+    def __init__(self, codec: "Codec", handle):
+        self.codec, self.h = codec, handle
+
+    def close(self):
+        if getattr(self, "h", None):
+            nat.load().hry_distortion_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def component(self, l: int, c: int) -> dict:
+        """hry_comp_error of component c of list l, plus rms = sqrt(sum_sq / compared) (0 when nothing was compared)"""
+        e = nat.CompError()
+        nat.check(nat.load().hry_distortion_component(self.h, l, c, C.byref(e)))
+        out = {k: getattr(e, k) for k, _ in e._fields_ if k != "reserved"}
+        out["rms"] = math.sqrt(e.sum_sq / e.compared) if e.compared else 0.0
+        return out
+
+    def position(self) -> dict:
+        """hry_pos_error, plus rms, diagonal (of the box of the source's compared positions) and psnr = 20 log10(diagonal / rms),
+        inf when rms is 0; list -1: the meshes have no positions"""
+        p = nat.PosError()
+        nat.check(nat.load().hry_distortion_position(self.h, C.byref(p)))
+        out = {k: getattr(p, k) for k, _ in p._fields_}
+        out["rms"] = math.sqrt(p.sum_sq_dist / p.compared) if p.compared else 0.0
+        out["diagonal"], out["psnr"] = 0.0, math.inf
+        if p.list >= 0:
+            first = nat.load().hry_distortion_position_component(self.h)
+            comps = [self.component(p.list, first + k) for k in range(3)]
+            ext = [max(c["a_max"] - c["a_min"], 0.0) if c["compared"] else 0.0 for c in comps]
+            out["diagonal"] = math.sqrt(sum(x * x for x in ext))
+            if out["rms"] > 0:
+                out["psnr"] = 20.0 * math.log10(out["diagonal"] / out["rms"]) if out["diagonal"] > 0 else -math.inf
+        return out
+
+    def rows(self, name: str) -> int:
+        """rows of a per-row buffer; 0: there is no such buffer"""
+        rows = C.c_uint64()
+        nat.check(nat.load().hry_distortion_get(self.h, name.encode(), None, C.byref(rows)))
+        return rows.value
+
+    def data_ptr(self, name: str) -> int:
+        """device address of a per-row buffer (f32 [rows]); 0 when absent"""
+        dev, rows = C.c_void_p(), C.c_uint64()
+        nat.check(nat.load().hry_distortion_get(self.h, name.encode(), C.byref(dev), C.byref(rows)))
+        return dev.value or 0
+
+    def numpy(self, name: str) -> np.ndarray:
+        """a per-row buffer as a host array (float32)"""
+        a = np.empty(self.rows(name), np.float32)
+        nat.check(nat.load().hry_distortion_copy(self.codec.h, self.h, name.encode(), a.ctypes.data, 0))
+        return a
+
+    def tensor(self, name: str):
+        """a per-row buffer as a torch float32 tensor on the codec's device, copied device to device"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+        t = torch.empty((self.rows(name),), dtype=torch.float32, device=dev)
+        nat.check(nat.load().hry_distortion_copy(self.codec.h, self.h, name.encode(), t.data_ptr(), 1))
+        return t
+
+    def stat(self) -> dict:
+        """device_ms (the two kernels, by events), uploaded_bytes (records that were not resident)"""
+        d, up = C.c_double(), C.c_uint64()
+        nat.check(nat.load().hry_distortion_stat(self.h, C.byref(d), C.byref(up)))
+        return {"device_ms": d.value, "uploaded_bytes": up.value}
 
 
 class MultiCodec:

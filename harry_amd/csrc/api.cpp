@@ -13,6 +13,7 @@ struct hry_mesh { Mesh m; };
 struct hry_plan { ShardPlan p; };
 struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
+struct hry_distortion { DistortionResult d; };
 struct hry_walk {
 	WalkResult w; uint32_t info[2]; std::vector<uint8_t> vplanes, fplanes; std::vector<uint32_t> seg_start, seg_level;
 	mutable std::vector<uint8_t> op_sym, op_class;   // unpacked from w.op_sc on first request
@@ -694,6 +695,56 @@ int hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int dire
 	return guarded([&] { order_apply(ctx->cx, *o->o, kind, direction, d_src, src_stride, d_dst, dst_stride, row_bytes, dst_rows); });
 }
 void hry_order_free(hry_order *o) { delete o; }
+
+// ---- per-component error of one mesh against another (distortion.cpp).  Like hry_render_build it leaves the decode's token
+// alone: b stays what the context holds, for this build and for a render build after it
+int hry_distortion_build(hry_ctx *ctx, const hry_mesh *a, const hry_mesh *b, const hry_order *o, uint32_t flags, hry_distortion **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !a || !b || !out || (o && !o->o)) { g_last_error = "null argument"; return HRY_E_ARG; }
+	order_lost(ctx);
+	return guarded([&] {
+		std::unique_ptr<hry_distortion> d(new hry_distortion());
+		distortion_build(ctx->cx, a->m, b->m, o ? o->o.get() : nullptr, flags, d->d);
+		*out = d.release();
+	});
+}
+int hry_distortion_component(const hry_distortion *d, int l, int c, hry_comp_error *out)
+{
+	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (l < 0 || (size_t)l >= d->d.comp.size() || d->d.comp[l].empty()) { g_last_error = "no such compared list"; return HRY_E_ARG; }
+	if (c < 0 || (size_t)c >= d->d.comp[l].size()) { g_last_error = "no such component"; return HRY_E_ARG; }
+	*out = d->d.comp[l][c];
+	return HRY_OK;
+}
+int hry_distortion_position(const hry_distortion *d, hry_pos_error *out)
+{
+	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	*out = d->d.pos;
+	return HRY_OK;
+}
+int hry_distortion_position_component(const hry_distortion *d) { return d ? d->d.pos_comp : -1; }
+int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows)
+{
+	if (!d || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const DistortionBuf *b = d->d.find(name);
+	*rows = b ? b->rows : 0;
+	if (dev) *dev = b && b->rows ? b->p : nullptr;
+	return HRY_OK;
+}
+int hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !d || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { distortion_copy(ctx->cx, d->d, name, dst, dst_is_device != 0); });
+}
+int hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!d) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = d->d.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = d->d.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_distortion_free(hry_distortion *d) { delete d; }
 
 // ---- meshes from device buffers (ingest.cpp)
 int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,

@@ -11,9 +11,12 @@
 // worker thread of its own, one sharded container comes out; hry_encode_sharded / hry_decode_sharded), --shards N (number of
 // shards, default one per context; both imply --profile chunked, the reference's single stream does not shard), --ply-packed
 // (binary PLY of a quantised mesh with every value in the width its header declares; the reference's writer dumps the
-// original-width records, formats/ply/writer.cc:72-75).
+// original-width records, formats/ply/writer.cc:72-75), --report (after the quantisation phase, what it cost: one line per component,
+// "Distortion: list L attr C bits Q max M rms R changed N", the quantised mesh against a clone taken before -- hry_distortion_build
+// with the identity map, since a decode returns the quantised values exactly).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,7 +48,7 @@ struct QuantArg { int l, o, q; };
 struct Args {
 	std::string in, out, fmt, profile;   // profile empty: compat, unless --gpus / --shards ask for the sharded container
 	std::vector<QuantArg> quant;
-	bool clearquant = false, ply_ascii = false, ply_packed = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -55,7 +58,7 @@ const Opt kOpts[] = {
 	{ 'a', "attr", "Select attribute", true }, { 'q', "quant", "Quantization bits", true }, { 'c', "clear-quant", "Clear all quantization first", false },
 	{ 0, "ply-ascii", "PLY writer: Use ASCII format", false }, { 0, "ply-packed", "PLY writer: quantised values in their declared width", false }, { 0, "profile", "compat (reference stream, default) or chunked", true },
 	{ 0, "chunk", "chunked: symbols per chunk", true }, { 0, "device", "GPU index (first one with --gpus)", true }, { 0, "gpus", "N device contexts, one worker thread each", true },
-	{ 0, "shards", "chunked: code as N shards (default: one per context)", true } };
+	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false } };
 
 void usage(const char *argv0)
 {
@@ -127,6 +130,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "device") a.device = to_int(argv[0], val);
 		else if (n == "shards") a.shards = to_int(argv[0], val);
 		else if (n == "gpus") a.gpus = to_int(argv[0], val);
+		else if (n == "report") a.report = true;
 	}
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
@@ -203,11 +207,14 @@ void write_file(const std::string &path, const uint8_t *p, size_t n)
 
 struct Handles {   // released on every path
 	std::vector<hry_ctx*> cx;   // [0]: the context of every single-device step
-	hry_mesh *mesh = nullptr;
+	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
+	hry_distortion *dist = nullptr;
 	std::vector<uint8_t*> bufs;
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
+		if (dist) hry_distortion_free(dist);
+		if (before) hry_mesh_free(before);
 		if (mesh) hry_mesh_free(mesh);
 		for (hry_ctx *c : cx) hry_ctx_destroy(c);
 	}
@@ -281,10 +288,26 @@ int run(const Args &args)
 	const bool quant_phase = (!q.empty() || args.clearquant) && !quant_in_encode;
 	if (quant_phase) {
 		std::cout << "Quantization..." << std::endl;
+		if (args.report && !(h.before = hry_mesh_clone(h.mesh))) throw std::runtime_error(hry_last_error());
 		ok(hry_requant(h.cx[0], h.mesh, q.data(), q.size(), args.clearquant ? 1 : 0));   // validation and texts of main.cc:74-91 inside
 	}
 	Clock::time_point t2 = Clock::now();
 	if (quant_phase) std::cout << "Quantization took " << ms(t1, t2) << " ms." << std::endl;
+	if (h.before) {
+		ok(hry_distortion_build(h.cx[0], h.before, h.mesh, nullptr, 0, &h.dist));
+		for (int l = 0; l < hry_mesh_nlists(h.mesh); ++l)
+			for (int c = 0; c < hry_list_ncomp(h.mesh, l); ++c) {
+				hry_comp_error e;
+				if (hry_distortion_component(h.dist, l, c, &e) != HRY_OK) continue;   // (a list that is not compared)
+				char line[256];
+				snprintf(line, sizeof line, "Distortion: list %d attr %d bits %d max %.9g rms %.9g changed %llu", l, c, hry_list_quant(h.mesh, l, c), e.max_abs,
+				         e.compared ? std::sqrt(e.sum_sq / (double)e.compared) : 0.0, (unsigned long long)e.changed);
+				std::cout << line << std::endl;
+			}
+		hry_distortion_free(h.dist); h.dist = nullptr;
+		hry_mesh_free(h.before); h.before = nullptr;
+		t2 = Clock::now();   // (the report is no part of the writing phase)
+	}
 
 	std::cout << "Writing output..." << std::endl;
 	if (type.empty()) throw std::runtime_error("Unknown file extension");

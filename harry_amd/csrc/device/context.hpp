@@ -90,6 +90,7 @@ struct Context {
 	// chunked profile
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
+	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
 	DevBuf d_ingest;   // hry_mesh_from_device: status word, scans, the weld's keys and table (ingest.cpp)
 	DevBuf d_split;   // chunked encode in two kernels: per stream the place of its records and the streams' order, longest first (the records: d_rec_sym)
 	DevBuf d_pipe, d_nt_val, d_nt_planes;   // EncodePipeline: run tables and twin pairs of the batches; the polygons' triangle counts and their two byte planes
@@ -209,6 +210,28 @@ void mark_decoded(Context &cx, Mesh &m, bool whole = false);
 bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne);
 void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out);   // flags: HRY_RENDER_*
 void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
+
+// every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
+// quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG
+dev::RequantPlan dequant_plan(const AttrList &L);
+
+// distortion.cpp: per-component error of one mesh against another (include/harry_amd.h: hry_distortion_build).  The result owns the
+// per-row buffers (one allocation) and the host copy of the statistics
+struct DistortionBuf { std::string name; float *p = nullptr; uint64_t rows = 0; };
+struct DistortionResult {
+	int device = 0;
+	DevBuf block;
+	std::vector<DistortionBuf> bufs;                 // "error<l>", with HRY_DISTORTION_ROWS
+	std::vector<std::vector<hry_comp_error>> comp;   // per list; empty: the list is not compared
+	hry_pos_error pos{};
+	int pos_comp = -1;                               // the first of the three position components in list pos.list
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+	const DistortionBuf *find(const std::string &name) const { for (const DistortionBuf &b : bufs) if (b.name == name) return &b; return nullptr; }
+	~DistortionResult() { if (block.p) (void)hipSetDevice(device); }   // (then the block is freed, on its device)
+};
+void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out);
+void distortion_copy(Context &cx, const DistortionResult &d, const char *name, void *dst, bool dst_is_device);
 
 // order.cpp.  order_build: at the end of an encode with cx.want_order -- m's connectivity is in d_foff / d_org (conn_view), w is the
 // encode's walk; d_order_v / d_order_f: the walk's orders where the encode has them whole in HBM, else nullptr (they go up from w);

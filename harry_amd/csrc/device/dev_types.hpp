@@ -118,5 +118,33 @@ struct BoundsPlan { int32_t n, stride; uint16_t off[kMaxComp]; uint8_t type[kMax
 struct RequantComp { int32_t off, src_type, src_bits, dst_bits, dst_type, pad; uint64_t mn, scale; };   // dst_bits 0: dequantise into dst_type
 struct RequantPlan { int32_t n; int32_t pad; RequantComp c[kMaxComp]; };
 
+// distortion.hip: what one block of k_distortion_rows leaves per component (and, one slot behind the components, for the
+// positions: mx = the largest distance, sum = the squared distances), and what k_distortion_fold makes of the blocks' records --
+// the layout of hry_comp_error (include/harry_amd.h)
+struct alignas(16) DistPart {
+	double mx, sum, mn, mxa;
+	uint32_t row, compared, skipped, nonfinite, changed, pad[3];
+};   // 64 bytes
+struct DistFinal {
+	double mx, sum, mn, mxa;
+	uint64_t compared, skipped, nonfinite, changed;
+	uint32_t row, reserved;
+};   // 72 bytes
+// one list of a comparison: rows of a (stride sa) against rows map[i] of b (stride sb; map == nullptr: row i); pos: the first of
+// the three position components, or -1; err: the per-row buffer, or nullptr
+struct DistList {
+	const uint8_t *a, *b;
+	const uint32_t *map;
+	float *err;
+	DistPart *part;
+	uint32_t rows, b_rows, sa, sb;
+	int32_t pos, pad;
+};
+struct DistFold {
+	const DistPart *part[16];
+	uint32_t nblocks[16], nslots[16], out_at[16];   // out_at: the list's first record in the results
+	int32_t n, pad;
+};
+
 }   // namespace dev
 }   // namespace hry

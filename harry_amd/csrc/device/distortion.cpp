@@ -1,0 +1,199 @@
+// Per-component error of one mesh against another (include/harry_amd.h: hry_distortion_build; kernels: distortion.hip; DESIGN.md
+// 7d).  Everything the comparison reads is usually in HBM already: the records a decode left (d_rec, under the token hry_render_build
+// tests), the records of the context's resident mesh, and the numbering maps of the encode (a handle of their own).  What is not
+// goes up into the build's own working buffer (d_distortion), next to the blocks' partial records, the results and the status word:
+// neither the encoder's resident_token nor the decode's render_token is read for anything but the test, and neither is written.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "context.hpp"
+#include "kernels.hpp"
+
+namespace hry {
+
+using namespace dev;
+
+namespace {
+
+constexpr size_t kAlign = 256;
+struct Carve {   // one allocation in aligned pieces: reserve() while sizing, ptr() afterwards
+	std::vector<size_t> at;
+	size_t total = 0;
+	size_t reserve(size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 4) + kAlign - 1) & ~(kAlign - 1); return at.size() - 1; }
+	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
+};
+
+bool compared(const Mesh &m, size_t l) { return m.lists[l].ncomp() > 0 && m.lists[l].target <= 2 && (m.general || l < 2); }
+int npos(const AttrList &L) { return L.interp_len.empty() ? 0 : L.interp_len[0]; }
+
+// the list whose first three POS components (mixing.h interpretation 0) are the positions, or -1
+int position_list(const Mesh &m)
+{
+	if (!m.general) return m.lists.size() >= 2 && compared(m, 1) && npos(m.lists[1]) >= 3 ? 1 : -1;
+	for (size_t l = 0; l < m.lists.size(); ++l)
+		if (m.lists[l].target == 1 && compared(m, l) && npos(m.lists[l]) >= 3) return (int)l;
+	return -1;
+}
+
+}   // namespace
+
+void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out)
+{
+	if (flags & ~(uint32_t)HRY_DISTORTION_ROWS) throw Error(HRY_E_ARG, "unknown distortion flag");
+	const bool want_rows = (flags & HRY_DISTORTION_ROWS) != 0;
+	if (a.partial || b.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
+	if (a.lists.size() != b.lists.size()) throw Error(HRY_E_ARG, "the meshes have different numbers of lists");
+	if (a.lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
+	if (a.general != b.general) throw Error(HRY_E_ARG, "one mesh has the PLY layout, the other general bindings");
+	const size_t nl = a.lists.size();
+	const bool general = a.general;
+	std::vector<RequantPlan> pa(nl), pb(nl);
+	for (size_t l = 0; l < nl; ++l) {
+		const AttrList &A = a.lists[l], &B = b.lists[l];
+		if (A.target != B.target || A.ncomp() != B.ncomp() || A.type != B.type)
+			throw Error(HRY_E_ARG, "list " + std::to_string(l) + ": the meshes differ in target, component count or component types");
+		if (!compared(a, l)) continue;
+		pa[l] = dequant_plan(A);
+		pb[l] = dequant_plan(B);
+		if (A.data.size() < (size_t)A.count * A.stride() || B.data.size() < (size_t)B.count * B.stride()) throw Error(HRY_E_ARG, "list without its records");
+	}
+	// ---- the maps
+	std::vector<const uint32_t*> map(nl, nullptr);
+	if (o && o->device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
+	for (size_t l = 0; l < nl; ++l) {
+		if (!compared(a, l)) continue;
+		if (!o) {
+			if (a.lists[l].count != b.lists[l].count) throw Error(HRY_E_ARG, "list " + std::to_string(l) + ": different counts and no order to pair the rows");
+			continue;
+		}
+		const OrderMap *m = o->find(general ? "list" + std::to_string(l) : l == 1 ? "vertex" : "face");
+		if (!m || m->rows != a.lists[l].count) throw Error(HRY_E_ARG, "order does not fit the meshes");
+		map[l] = m->p;
+	}
+	const int pl = position_list(a);
+	int pos_comp = -1;
+	if (pl >= 0) {
+		pos_comp = a.lists[pl].interp_off[0];
+		if (pos_comp < 0 || pos_comp + 3 > a.lists[pl].ncomp()) throw Error(HRY_E_INTERNAL, "position components outside their list");
+	}
+
+	HIP_OK(hipSetDevice(cx.device));
+	out.device = cx.device;
+	// ---- where the records are read: the decode's buffers (render.cpp's test), the resident mesh's, or uploads
+	const bool whole = cx.render_whole;
+	auto r_rec = [&](size_t l) -> const DevBuf & { return whole ? cx.d_whole_rec[l] : cx.d_rec[l]; };
+	bool b_res = b.render_token != 0 && b.render_token == cx.render_token && cx.render_nf == b.nf && cx.render_ne == b.ne() && !(whole && (general || nl > 2));
+	for (size_t l = 0; l < nl && b_res; ++l) b_res = !compared(b, l) || r_rec(l).cap >= b.lists[l].data.size();
+	bool a_res = !b_res && cx.render_token == 0 && a.device_token != 0 && a.device_token == cx.resident_token;   // (d_rec holds one mesh at a time)
+	for (size_t l = 0; l < nl && a_res; ++l) a_res = !compared(a, l) || cx.d_rec[l].cap >= a.lists[l].data.size();
+
+	Carve W;
+	size_t nslots_all = 0;
+	std::vector<size_t> w_a(nl), w_b(nl), w_part(nl), slot_at(nl, 0), nslots(nl, 0);
+	for (size_t l = 0; l < nl; ++l) {
+		if (!compared(a, l)) continue;
+		nslots[l] = (size_t)a.lists[l].ncomp() + ((int)l == pl ? 1 : 0);
+		slot_at[l] = nslots_all;
+		nslots_all += nslots[l];
+		w_a[l] = W.reserve(a_res ? 0 : a.lists[l].data.size());
+		w_b[l] = W.reserve(b_res ? 0 : b.lists[l].data.size());
+		w_part[l] = W.reserve((size_t)distortion_blocks(a.lists[l].count) * nslots[l] * sizeof(DistPart));
+	}
+	const size_t res_bytes = nslots_all * sizeof(DistFinal);
+	const size_t w_res = W.reserve(res_bytes + 8);   // the results, then the status word: one copy brings both down
+	cx.d_distortion.ensure(W.total);
+	void *wb = cx.d_distortion.p;
+
+	Carve O;
+	std::vector<size_t> o_err(nl, 0);
+	if (want_rows) for (size_t l = 0; l < nl; ++l) if (compared(a, l)) o_err[l] = O.reserve((size_t)a.lists[l].count * 4);
+	out.block.ensure(std::max<size_t>(O.total, 16));
+
+	hipStream_t st = cx.stream;
+	uint64_t up = 0;
+	auto put = [&](size_t i, const void *src, size_t bytes) {
+		if (!bytes) return;
+		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, i), src, bytes, hipMemcpyHostToDevice, st));
+		up += bytes;
+	};
+	uint8_t *d_res = W.ptr<uint8_t>(wb, w_res);
+	uint32_t *d_status = (uint32_t*)(d_res + res_bytes);
+	HIP_OK(hipMemsetAsync(d_status, 0, 8, st));
+	DistFold fold{};
+	std::vector<DistList> jobs;
+	std::vector<size_t> job_list;
+	for (size_t l = 0; l < nl; ++l) {
+		if (!compared(a, l)) continue;
+		const AttrList &A = a.lists[l], &B = b.lists[l];
+		DistList J{};
+		if (a_res) J.a = cx.d_rec[l].as<uint8_t>(); else { put(w_a[l], A.data.data(), A.data.size()); J.a = W.ptr<uint8_t>(wb, w_a[l]); }
+		if (b_res) J.b = r_rec(l).as<uint8_t>(); else { put(w_b[l], B.data.data(), B.data.size()); J.b = W.ptr<uint8_t>(wb, w_b[l]); }
+		J.map = map[l];
+		J.err = want_rows ? O.ptr<float>(out.block.p, o_err[l]) : nullptr;
+		J.part = W.ptr<DistPart>(wb, w_part[l]);
+		J.rows = A.count; J.b_rows = B.count; J.sa = (uint32_t)A.stride(); J.sb = (uint32_t)B.stride();
+		J.pos = (int)l == pl ? pos_comp : -1;
+		jobs.push_back(J);
+		job_list.push_back(l);
+		const int k = fold.n++;
+		fold.part[k] = J.part; fold.nblocks[k] = distortion_blocks(A.count); fold.nslots[k] = (uint32_t)nslots[l]; fold.out_at[k] = (uint32_t)slot_at[l];
+	}
+
+	TimedEvent ev[2];
+	HIP_OK(hipEventRecord(ev[0], st));
+	for (size_t k = 0; k < jobs.size(); ++k) launch_distortion_rows(st, jobs[k], pa[job_list[k]], pb[job_list[k]], d_status);
+	launch_distortion_fold(st, fold, (DistFinal*)d_res);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipEventRecord(ev[1], st));
+	std::vector<uint8_t> res(res_bytes + 8);
+	HIP_OK(hipMemcpyAsync(res.data(), d_res, res.size(), hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	uint32_t status = 0;
+	memcpy(&status, res.data() + res_bytes, 4);
+	if (status) throw Error(HRY_E_ARG, "order does not fit the meshes");
+	float ms = 0;
+	HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+
+	static_assert(sizeof(DistFinal) == sizeof(hry_comp_error) && sizeof(hry_comp_error) == 72, "the results are hry_comp_error records");
+	out.comp.assign(nl, std::vector<hry_comp_error>());
+	out.pos = hry_pos_error{};
+	out.pos.list = -1;
+	out.pos_comp = pos_comp;
+	for (size_t l = 0; l < nl; ++l) {
+		if (!compared(a, l)) continue;
+		const int nc = a.lists[l].ncomp();
+		out.comp[l].resize(nc);
+		for (int c = 0; c < nc; ++c) {
+			DistFinal f;
+			memcpy(&f, res.data() + (slot_at[l] + c) * sizeof(DistFinal), sizeof f);
+			hry_comp_error &e = out.comp[l][c];
+			e.max_abs = f.mx; e.sum_sq = f.sum; e.a_min = f.mn; e.a_max = f.mxa;
+			e.compared = f.compared; e.skipped = f.skipped; e.nonfinite = f.nonfinite; e.changed = f.changed;
+			e.argmax = f.row; e.reserved = 0;
+		}
+		if ((int)l == pl) {
+			DistFinal f;
+			memcpy(&f, res.data() + (slot_at[l] + nc) * sizeof(DistFinal), sizeof f);
+			out.pos.max_dist = f.mx; out.pos.sum_sq_dist = f.sum; out.pos.compared = f.compared; out.pos.argmax = f.row; out.pos.list = pl;
+		}
+		if (want_rows) out.bufs.push_back(DistortionBuf{ "error" + std::to_string(l), O.ptr<float>(out.block.p, o_err[l]), a.lists[l].count });
+	}
+	out.device_ms = (double)ms;
+	out.uploaded_bytes = up;
+}
+
+void distortion_copy(Context &cx, const DistortionResult &d, const char *name, void *dst, bool dst_is_device)
+{
+	const DistortionBuf *b = d.find(name);
+	if (!b) throw Error(HRY_E_ARG, std::string("no such distortion buffer: ") + name);
+	if (!b->rows) return;
+	if (!dst) throw Error(HRY_E_ARG, "null destination");
+	if (d.device != cx.device) throw Error(HRY_E_ARG, "the distortion buffers live on another device than the context's");
+	HIP_OK(hipSetDevice(cx.device));
+	HIP_OK(hipMemcpyAsync(dst, b->p, (size_t)b->rows * 4, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
+	HIP_OK(hipStreamSynchronize(cx.stream));
+}
+
+}   // namespace hry

@@ -176,6 +176,15 @@ void launch_vertex_normals(hipStream_t st, const NrmView &n, const double *fn, u
                            uint32_t *hubs, float *out);
 void launch_normals_expand(hipStream_t st, const float *vn, const uint32_t *vsrc, uint32_t nout, uint32_t nv, float *out);   // out[u] = vn[vsrc[u]]
 
+// per-component error of one mesh against another (distortion.hip; driver: distortion.cpp).  launch_distortion_rows: one DistPart
+// per block of kDistBlockRows rows and slot (pa.n components, then the positions when L.pos >= 0) into L.part; a map entry at or
+// above L.b_rows raises *status (nothing is read there).  launch_distortion_fold: the blocks' records in block order, one block per
+// list, into out[f.out_at[l] + slot]
+constexpr uint32_t kDistBlockRows = 1024;
+inline uint32_t distortion_blocks(uint32_t rows) { return (uint32_t)(((uint64_t)rows + kDistBlockRows - 1) / kDistBlockRows); }
+void launch_distortion_rows(hipStream_t st, const DistList &L, const RequantPlan &pa, const RequantPlan &pb, uint32_t *status);
+void launch_distortion_fold(hipStream_t st, const DistFold &f, DistFinal *out);
+
 // meshes from device buffers (ingest.hip; driver: ingest.cpp).  The checks raise bits of err; total = sum of the degrees (64-bit),
 // degmask = the set of degrees present (bit d)
 constexpr uint32_t kIngestBadDegree = 1, kIngestBadIndex = 2;

@@ -66,6 +66,8 @@ bool rendered(const AttrList &L) { return L.ncomp() > 0 && L.target <= 2; }
 
 }   // namespace
 
+dev::RequantPlan dequant_plan(const AttrList &L) { return gather_plan(L); }
+
 // the list whose first three POS components (mixing.h interpretation 0) are the positions the normals are computed from
 static size_t position_list(const Mesh &m)
 {

@@ -17,6 +17,7 @@
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
+ *   hry_distortion_build (no counterpart: the per-component error of a decode against its source, reduced on the device)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -395,6 +396,73 @@ int  hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int dir
                      const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
                      uint64_t row_bytes, uint64_t dst_rows);
 void hry_order_free(hry_order *o);
+
+/* ---- what a quantisation cost: per-component error of one mesh against another, on the device -------------------------
+ * hry_distortion_build compares mesh a (the source) with mesh b -- typically hry_decode(hry_encode(m)) for a clone m of a after
+ * hry_requant -- component by component, through the numbering map of the encode that relates them, and keeps the statistics
+ * (and, with HRY_DISTORTION_ROWS, one error value per row in HBM: a heat map next to hry_render_build's buffers).
+ *   Meshes: the same number of lists (more than 16: HRY_E_UNSUPPORTED), the same layout (PLY or general bindings), and per list
+ *     the same target, component count (more than 32: HRY_E_UNSUPPORTED) and ORIGINAL component types: HRY_E_ARG otherwise.  The
+ *     quantisation bits may differ on either side.  A quantised list without bounds and a partial mesh are HRY_E_ARG, as in
+ *     hry_render_build.  Lists without components or without a target are not compared; in the PLY layout lists 0 and 1 are.
+ *   Rows: row i of list l of a is paired with row map_l[i] of b.  o == NULL: the identity, and the lists' counts must be equal
+ *     (HRY_E_ARG).  With o: "vertex" for list 1 and "face" for list 0 in the PLY layout, "list<l>" with general bindings; the
+ *     map's rows must equal a's count, and every entry other than HRY_NO_ELEMENT must be below b's count: HRY_E_ARG, "order does
+ *     not fit the meshes".  The entries are checked on the device into one status word (vector atomics) that is read back once;
+ *     nothing is read out of bounds on the way.  A row whose entry is HRY_NO_ELEMENT counts in `skipped`.
+ *   Value: x (of a) and y (of b) are what hry_requant(..., clear = 1) gives for the component in its original type (the reference's
+ *     -c; unquantised components as stored), converted to double: floats widen exactly, 64-bit integers round to nearest.
+ *     e = y - x, one rounded double subtraction.  A pair is compared when x and y are both finite; otherwise it counts in
+ *     `nonfinite` and enters no maximum, sum or range.
+ *   max_abs, argmax (ties: the lowest row of a, whatever the grid), a_min and a_max are exact.  sum_sq adds the individually
+ *     rounded e*e in a reduction tree that is fixed by the row count alone, without floating-point atomics: the same bits from
+ *     run to run and whether the inputs were resident or uploaded.  The association itself is not part of the contract.
+ *   Positions: the position list is list 1 in the PLY layout, with general bindings the lowest-numbered vertex-target list, when
+ *     it has at least three POS components.  Over its first three: d2 = (ex*ex + ey*ey) + ez*ez, dist = sqrt(d2); a row is
+ *     compared when all three pairs are finite; sum_sq_dist sums d2 under the same rule as sum_sq.
+ *   HRY_DISTORTION_ROWS: for every compared list a buffer "error<l>", f32, one value per row of a:
+ *     (float) sqrt(sum over the list's components, in component order, of e*e of the compared pairs); a skipped row holds 0.
+ *   Unknown flag bits: HRY_E_ARG.
+ *   Residency: when b is the mesh hry_decode just returned on ctx and nothing has touched ctx or b since (hry_render_build's
+ *     test), b's records are read where the decode left them; when a is ctx's resident mesh (hry_mesh_resident), its records are
+ *     read in place.  Whatever is not resident is uploaded (uploaded_bytes: the records that went up); the results are the same
+ *     either way.  Neither the encoder's resident mesh nor the decode's buffers are disturbed: hry_render_build of b afterwards
+ *     still finds them.  On any refusal *out stays NULL and ctx stays usable.
+ *   The handle owns its one device allocation and the host copy of the statistics; free it before the context.
+ *   hry_distortion_component  the record of component c of list l; an uncompared list, a bad l or c: HRY_E_ARG
+ *   hry_distortion_position   the Euclidean displacement of the positions; list -1 (everything else 0): the meshes have none
+ *   hry_distortion_position_component  where the position components begin in that list
+ *   hry_distortion_get / _copy / _stat  as hry_render_get / _copy / _stat; device_ms: the two kernels, by events */
+typedef struct hry_distortion hry_distortion;
+#define HRY_DISTORTION_ROWS 1u      /* also build the per-row buffers "error<l>" */
+int  hry_distortion_build(hry_ctx *ctx, const hry_mesh *a, const hry_mesh *b, const hry_order *o /* or NULL */,
+                          uint32_t flags, hry_distortion **out);
+typedef struct hry_comp_error {
+    double   max_abs;      /* max |e| over the compared pairs; 0 when there is none */
+    double   sum_sq;       /* sum of e*e over the compared pairs */
+    double   a_min, a_max; /* range of a's finite values among the compared pairs (+inf / -inf when there is none) */
+    uint64_t compared;     /* pairs with both values finite */
+    uint64_t skipped;      /* rows of a whose map entry is HRY_NO_ELEMENT */
+    uint64_t nonfinite;    /* mapped pairs with a NaN or infinity on either side */
+    uint64_t changed;      /* compared pairs with e != 0, plus non-finite pairs whose two doubles differ in bits */
+    uint32_t argmax;       /* lowest row of a that attains max_abs; HRY_NO_ELEMENT when compared == 0 */
+    uint32_t reserved;
+} hry_comp_error;          /* 72 bytes */
+int  hry_distortion_component(const hry_distortion *d, int l, int c, hry_comp_error *out);
+typedef struct hry_pos_error {
+    double   max_dist, sum_sq_dist;
+    uint64_t compared;
+    uint32_t argmax;       /* lowest row attaining max_dist, HRY_NO_ELEMENT when compared == 0 */
+    int32_t  list;         /* the position list, -1: the meshes have none (everything else 0) */
+} hry_pos_error;
+int  hry_distortion_position(const hry_distortion *d, hry_pos_error *out);
+/* the first of the three position components within that list (they are consecutive), -1: the meshes have none -- what names the
+ * hry_comp_error records whose a_min / a_max span the positions' bounding box */
+int  hry_distortion_position_component(const hry_distortion *d);
+int  hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows);  /* "error<l>": f32 [rows] in HBM; rows 0: absent */
+int  hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device);
+int  hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes);
+void hry_distortion_free(hry_distortion *d);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
