@@ -615,50 +615,75 @@ class Codec:
         return nat.take_bytes(p, n.value)
 
 
-class Order:
+class _NamedBuffers:
+    """A native handle whose buffers lie in HBM and are found by name (hry_<_PREFIX>_get / _copy / _free), rows of one
+    component of _NP / _TORCH each.  Order and Distortion say what each accessor gives for them"""
+
+    _PREFIX, _NP, _TORCH = "", None, ""
+
+    def _fn(self, what: str):
+        return getattr(nat.load(), f"hry_{self._PREFIX}_{what}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("free")(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def rows(self, name: str) -> int:
+        rows = C.c_uint64()
+        nat.check(self._fn("get")(self.h, name.encode(), None, C.byref(rows)))
+        return rows.value
+
+    def data_ptr(self, name: str) -> int:
+        dev, rows = C.c_void_p(), C.c_uint64()
+        nat.check(self._fn("get")(self.h, name.encode(), C.byref(dev), C.byref(rows)))
+        return dev.value or 0
+
+    def numpy(self, name: str) -> np.ndarray:
+        a = np.empty(self.rows(name), self._NP)
+        nat.check(self._fn("copy")(self.codec.h, self.h, name.encode(), a.ctypes.data, 0))
+        return a
+
+    def tensor(self, name: str):
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+        t = torch.empty((self.rows(name),), dtype=getattr(torch, self._TORCH), device=dev)
+        nat.check(self._fn("copy")(self.codec.h, self.h, name.encode(), t.data_ptr(), 1))
+        return t
+
+
+class Order(_NamedBuffers):
     """The numbering maps of one encode (include/harry_amd.h: hry_order_take): which element of read_hry(write_hry(mesh)) every
     vertex, face, half-edge ("corner") and -- with general bindings -- record of list l ("list<l>") of `mesh` becomes, and the inverses
     ("<name>_inv": source element of every decoded element).  u32 tables in HBM, NO_ELEMENT where an element was never coded (a
     vertex no face names) or a decoded row is filler.  The tables stay valid whatever the codec does later, until close()."""
 
     KINDS = ("vertex", "face", "corner")
+    _PREFIX, _NP, _TORCH = "order", np.uint32, "int32"
 
     def __init__(self, codec: "Codec", handle, nlists: int = 0):
         self.codec, self.h = codec, handle
         self.names = tuple(n + sfx for n in self.KINDS + tuple(f"list{l}" for l in range(nlists)) for sfx in ("", "_inv"))
 
-    def close(self):
-        if getattr(self, "h", None):
-            nat.load().hry_order_free(self.h)
-            self.h = None
-
-    __del__ = close
-
     def rows(self, name: str) -> int:
         """rows of a map; 0: there is no such map"""
-        rows = C.c_uint64()
-        nat.check(nat.load().hry_order_get(self.h, name.encode(), None, C.byref(rows)))
-        return rows.value
+        return super().rows(name)
 
     def data_ptr(self, name: str) -> int:
         """device address of a map (u32 [rows]); 0 when absent"""
-        dev, rows = C.c_void_p(), C.c_uint64()
-        nat.check(nat.load().hry_order_get(self.h, name.encode(), C.byref(dev), C.byref(rows)))
-        return dev.value or 0
+        return super().data_ptr(name)
 
     def numpy(self, name: str) -> np.ndarray:
         """a map as a host array (uint32)"""
-        a = np.empty(self.rows(name), np.uint32)
-        nat.check(nat.load().hry_order_copy(self.codec.h, self.h, name.encode(), a.ctypes.data, 0))
-        return a
+        return super().numpy(name)
 
     def tensor(self, name: str):
         """a map as a torch int64 tensor on the codec's device, ready for indexing; NO_ELEMENT becomes -1"""
         import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.codec.device)
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-        t = torch.empty((self.rows(name),), dtype=torch.int32, device=dev)
-        nat.check(nat.load().hry_order_copy(self.codec.h, self.h, name.encode(), t.data_ptr(), 1))
+        t = super().tensor(name)
         w = t.to(torch.int64)
         return torch.where(t == -1, w, w & 0xFFFFFFFF)
 
@@ -697,20 +722,15 @@ class Order:
         return self._apply(t, kind, nat.ORDER_TO_SOURCE, out)
 
 
-class Distortion:
+class Distortion(_NamedBuffers):
     """The error of one mesh against another (include/harry_amd.h: hry_distortion_build): per component the largest error and where
     it is, the sum of squared errors, the range of the source's values and the counts; the Euclidean displacement of the positions;
     with rows=True one error value per row ("error<l>") in HBM.  Valid until close(), whatever the codec does later."""
 
+    _PREFIX, _NP, _TORCH = "distortion", np.float32, "float32"
+
     def __init__(self, codec: "Codec", handle):
         self.codec, self.h = codec, handle
-
-    def close(self):
-        if getattr(self, "h", None):
-            nat.load().hry_distortion_free(self.h)
-            self.h = None
-
-    __del__ = close
 
     def component(self, l: int, c: int) -> dict:
         """hry_comp_error of component c of list l, plus rms = sqrt(sum_sq / compared) (0 when nothing was compared)"""
@@ -739,30 +759,19 @@ class Distortion:
 
     def rows(self, name: str) -> int:
         """rows of a per-row buffer; 0: there is no such buffer"""
-        rows = C.c_uint64()
-        nat.check(nat.load().hry_distortion_get(self.h, name.encode(), None, C.byref(rows)))
-        return rows.value
+        return super().rows(name)
 
     def data_ptr(self, name: str) -> int:
         """device address of a per-row buffer (f32 [rows]); 0 when absent"""
-        dev, rows = C.c_void_p(), C.c_uint64()
-        nat.check(nat.load().hry_distortion_get(self.h, name.encode(), C.byref(dev), C.byref(rows)))
-        return dev.value or 0
+        return super().data_ptr(name)
 
     def numpy(self, name: str) -> np.ndarray:
         """a per-row buffer as a host array (float32)"""
-        a = np.empty(self.rows(name), np.float32)
-        nat.check(nat.load().hry_distortion_copy(self.codec.h, self.h, name.encode(), a.ctypes.data, 0))
-        return a
+        return super().numpy(name)
 
     def tensor(self, name: str):
         """a per-row buffer as a torch float32 tensor on the codec's device, copied device to device"""
-        import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.codec.device)
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-        t = torch.empty((self.rows(name),), dtype=torch.float32, device=dev)
-        nat.check(nat.load().hry_distortion_copy(self.codec.h, self.h, name.encode(), t.data_ptr(), 1))
-        return t
+        return super().tensor(name)
 
     def stat(self) -> dict:
         """device_ms (the two kernels, by events), uploaded_bytes (records that were not resident)"""

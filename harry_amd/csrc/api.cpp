@@ -620,6 +620,16 @@ int hry_range_encode_lht(hry_ctx *ctx, const uint64_t *lht, size_t n, uint8_t **
 	});
 }
 
+// ---- the named buffers of a result handle (context.hpp: DeviceResult).  *rows 0: no such buffer; *dev: its address, of a buffer
+// without rows only where empty_has_address (hry_render_get gives it, the other two give NULL: DESIGN.md 7e)
+static const NamedBuf *result_get(const DeviceResult &r, const char *name, const void **dev, uint64_t *rows, bool empty_has_address)
+{
+	const NamedBuf *b = r.find(name);
+	*rows = b ? b->rows : 0;
+	if (dev) *dev = b && (b->rows || empty_has_address) ? b->p : nullptr;
+	return b;
+}
+
 // ---- render-ready device buffers (render.cpp)
 int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out) { return hry_render_build_ex(ctx, m, 0, out); }
 int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_render **out)
@@ -638,9 +648,7 @@ uint64_t hry_render_ntris(const hry_render *r) { return r ? r->r.ntris : 0; }
 int hry_render_get(const hry_render *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
 {
 	if (!r || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const RenderBuf *b = r->r.find(name);
-	*rows = b ? b->rows : 0;
-	if (dev) *dev = b ? b->p : nullptr;
+	const NamedBuf *b = result_get(r->r, name, dev, rows, true);
 	if (width) *width = b ? b->width : 0;
 	if (type) *type = b ? b->type : 0;
 	return HRY_OK;
@@ -648,7 +656,7 @@ int hry_render_get(const hry_render *r, const char *name, const void **dev, uint
 int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *dst, int dst_is_device)
 {
 	if (!ctx || !r || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { render_copy(ctx->cx, r->r, name, dst, dst_is_device != 0); });
+	return guarded([&] { result_copy(ctx->cx, r->r, name, "render buffer", dst, dst_is_device != 0, false); });
 }
 int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes)
 {
@@ -678,15 +686,13 @@ int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)
 int hry_order_get(const hry_order *o, const char *name, const void **dev, uint64_t *rows)
 {
 	if (!o || !o->o || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const OrderMap *b = o->o->find(name);
-	*rows = b ? b->rows : 0;
-	if (dev) *dev = b && b->rows ? b->p : nullptr;
+	result_get(*o->o, name, dev, rows, false);
 	return HRY_OK;
 }
 int hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst, int dst_is_device)
 {
 	if (!ctx || !o || !o->o || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { order_copy(ctx->cx, *o->o, name, dst, dst_is_device != 0); });
+	return guarded([&] { result_copy(ctx->cx, *o->o, name, "numbering map", dst, dst_is_device != 0, true); });
 }
 int hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
                     uint64_t row_bytes, uint64_t dst_rows)
@@ -727,15 +733,13 @@ int hry_distortion_position_component(const hry_distortion *d) { return d ? d->d
 int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows)
 {
 	if (!d || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const DistortionBuf *b = d->d.find(name);
-	*rows = b ? b->rows : 0;
-	if (dev) *dev = b && b->rows ? b->p : nullptr;
+	result_get(d->d, name, dev, rows, false);
 	return HRY_OK;
 }
 int hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device)
 {
 	if (!ctx || !d || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { distortion_copy(ctx->cx, d->d, name, dst, dst_is_device != 0); });
+	return guarded([&] { result_copy(ctx->cx, d->d, name, "distortion buffer", dst, dst_is_device != 0, true); });
 }
 int hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes)
 {

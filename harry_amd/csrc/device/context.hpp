@@ -21,15 +21,27 @@ inline double ms_since(Clock::time_point t0) { return std::chrono::duration<doub
 
 constexpr int kMaxLists = 16;   // attribute lists of one mesh kept in HBM (the OBJ reader creates at most 8)
 
-// order.cpp: the numbering maps of one encode (include/harry_amd.h: hry_order_take); every map lies in the one allocation
-struct OrderMap { std::string name; uint32_t *p = nullptr; uint64_t rows = 0; };
-struct OrderResult {
-	int device = 0;
-	DevBuf block;
-	std::vector<OrderMap> maps;
-	const OrderMap *find(const std::string &name) const { for (const OrderMap &m : maps) if (m.name == name) return &m; return nullptr; }
-	~OrderResult() { if (block.p) (void)hipSetDevice(device); }   // (then the block is freed, on its device)
+// A result handle's buffers (render.cpp, order.cpp, distortion.cpp): pieces (hip_handles.hpp: Carve) of the one allocation the
+// handle owns, found by name
+struct NamedBuf {
+	std::string name;
+	void *p = nullptr;
+	uint64_t rows = 0;
+	int width = 0, type = 0;   // components a row, HRY_FLOAT / HRY_UINT / HRY_USHORT
+	size_t bytes() const { return (size_t)rows * (size_t)width * (type == HRY_USHORT ? 2u : 4u); }
 };
+struct DeviceResult {
+	DeviceBlock block;
+	std::vector<NamedBuf> bufs;
+	const NamedBuf *find(const std::string &name) const { for (const NamedBuf &b : bufs) if (b.name == name) return &b; return nullptr; }
+};
+// a named buffer of any of the three results to dst (device or host memory), on cx's stream, waited for (defined in render.cpp).
+// what: what the handle calls a buffer ("numbering map"), for the refusals.  same_device: refuse a result that lives on another
+// device than cx's -- hry_order_copy and hry_distortion_copy ask for it, hry_render_copy does not
+struct Context;
+void result_copy(Context &cx, const DeviceResult &r, const char *name, const char *what, void *dst, bool dst_is_device, bool same_device);
+// order.cpp: the numbering maps of one encode (include/harry_amd.h: hry_order_take), width 1 HRY_UINT
+typedef DeviceResult OrderResult;
 // general bindings: where an encode left the records of a list that it coded as data, in creation order (d_idx, in cx.d_gen)
 struct OrderListSource { const uint32_t *d_idx = nullptr; uint32_t nd = 0; };
 
@@ -187,20 +199,11 @@ Mesh *decode_sharded(Context *const *cxs, int n_ctx, const uint8_t *p, size_t n,
 void range_encode_lht(Context &cx, const uint64_t *lht, size_t n, std::vector<uint8_t> &out);
 
 // render.cpp: a mesh as device buffers a GPU program draws (include/harry_amd.h: hry_render_build); the result owns its memory
-struct RenderBuf { std::string name; void *p = nullptr; uint64_t rows = 0; int width = 0, type = 0; size_t bytes() const; };
-struct RenderResult {
-	int device = 0;
-	void *block = nullptr;   // every buffer lies in this one allocation
+struct RenderResult : DeviceResult {
 	uint32_t nverts = 0;
 	uint64_t ntris = 0;
 	double device_ms = 0;
 	uint64_t uploaded_bytes = 0;
-	std::vector<RenderBuf> bufs;
-	RenderResult() = default;
-	RenderResult(const RenderResult&) = delete;
-	RenderResult &operator=(const RenderResult&) = delete;
-	~RenderResult();
-	const RenderBuf *find(const char *name) const;
 };
 // marks m as what cx holds in HBM after a decode (unchunk.cpp, general.cpp; whole: sharded.cpp, the mesh is in d_whole_*), with a
 // token unique in the process; a mesh whose connectivity the context does not hold stays unmarked
@@ -208,8 +211,11 @@ void mark_decoded(Context &cx, Mesh &m, bool whole = false);
 // decode_sharded on one context (PLY layout): the segment just decoded (cx's d_rec / d_foff / d_org, the segment's numbering) into
 // d_whole_* at its runs' places in the whole numbering; false (nothing placed) when the context does not hold the segment
 bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne);
+// cx still holds the decode of m (mark_decoded's token on both, the same connectivity; of a sharded container only the PLY layout
+// is placed whole); then list l's records are in decoded_records(cx, l) -- whose capacity the caller checks for the lists it reads
+bool holds_decode(const Context &cx, const Mesh &m);
+inline const DevBuf &decoded_records(const Context &cx, size_t l) { return cx.render_whole ? cx.d_whole_rec[l] : cx.d_rec[l]; }
 void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out);   // flags: HRY_RENDER_*
-void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device);
 
 // every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
 // quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG
@@ -217,27 +223,19 @@ dev::RequantPlan dequant_plan(const AttrList &L);
 
 // distortion.cpp: per-component error of one mesh against another (include/harry_amd.h: hry_distortion_build).  The result owns the
 // per-row buffers (one allocation) and the host copy of the statistics
-struct DistortionBuf { std::string name; float *p = nullptr; uint64_t rows = 0; };
-struct DistortionResult {
-	int device = 0;
-	DevBuf block;
-	std::vector<DistortionBuf> bufs;                 // "error<l>", with HRY_DISTORTION_ROWS
+struct DistortionResult : DeviceResult {             // bufs: "error<l>" with HRY_DISTORTION_ROWS, width 1 HRY_FLOAT
 	std::vector<std::vector<hry_comp_error>> comp;   // per list; empty: the list is not compared
 	hry_pos_error pos{};
 	int pos_comp = -1;                               // the first of the three position components in list pos.list
 	double device_ms = 0;
 	uint64_t uploaded_bytes = 0;
-	const DistortionBuf *find(const std::string &name) const { for (const DistortionBuf &b : bufs) if (b.name == name) return &b; return nullptr; }
-	~DistortionResult() { if (block.p) (void)hipSetDevice(device); }   // (then the block is freed, on its device)
 };
 void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out);
-void distortion_copy(Context &cx, const DistortionResult &d, const char *name, void *dst, bool dst_is_device);
 
 // order.cpp.  order_build: at the end of an encode with cx.want_order -- m's connectivity is in d_foff / d_org (conn_view), w is the
 // encode's walk; d_order_v / d_order_f: the walk's orders where the encode has them whole in HBM, else nullptr (they go up from w);
 // general bindings: cx.order_lists names every list's records in creation order.  Leaves the maps in cx.order, waited for.
 void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t *d_order_v, const uint32_t *d_order_f);
-void order_copy(Context &cx, const OrderResult &o, const char *name, void *dst, bool dst_is_device);
 void order_apply(Context &cx, const OrderResult &o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
                  uint64_t row_bytes, uint64_t dst_rows);
 

@@ -17,14 +17,6 @@ using namespace dev;
 
 namespace {
 
-constexpr size_t kAlign = 256;
-struct Carve {   // one allocation in aligned pieces: reserve() while sizing, ptr() afterwards
-	std::vector<size_t> at;
-	size_t total = 0;
-	size_t reserve(size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 4) + kAlign - 1) & ~(kAlign - 1); return at.size() - 1; }
-	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
-};
-
 bool compared(const Mesh &m, size_t l) { return m.lists[l].ncomp() > 0 && m.lists[l].target <= 2 && (m.general || l < 2); }
 int npos(const AttrList &L) { return L.interp_len.empty() ? 0 : L.interp_len[0]; }
 
@@ -61,16 +53,16 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 	}
 	// ---- the maps
 	std::vector<const uint32_t*> map(nl, nullptr);
-	if (o && o->device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
+	if (o && o->block.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
 	for (size_t l = 0; l < nl; ++l) {
 		if (!compared(a, l)) continue;
 		if (!o) {
 			if (a.lists[l].count != b.lists[l].count) throw Error(HRY_E_ARG, "list " + std::to_string(l) + ": different counts and no order to pair the rows");
 			continue;
 		}
-		const OrderMap *m = o->find(general ? "list" + std::to_string(l) : l == 1 ? "vertex" : "face");
+		const NamedBuf *m = o->find(general ? "list" + std::to_string(l) : l == 1 ? "vertex" : "face");
 		if (!m || m->rows != a.lists[l].count) throw Error(HRY_E_ARG, "order does not fit the meshes");
-		map[l] = m->p;
+		map[l] = (const uint32_t*)m->p;
 	}
 	const int pl = position_list(a);
 	int pos_comp = -1;
@@ -80,12 +72,9 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 	}
 
 	HIP_OK(hipSetDevice(cx.device));
-	out.device = cx.device;
-	// ---- where the records are read: the decode's buffers (render.cpp's test), the resident mesh's, or uploads
-	const bool whole = cx.render_whole;
-	auto r_rec = [&](size_t l) -> const DevBuf & { return whole ? cx.d_whole_rec[l] : cx.d_rec[l]; };
-	bool b_res = b.render_token != 0 && b.render_token == cx.render_token && cx.render_nf == b.nf && cx.render_ne == b.ne() && !(whole && (general || nl > 2));
-	for (size_t l = 0; l < nl && b_res; ++l) b_res = !compared(b, l) || r_rec(l).cap >= b.lists[l].data.size();
+	// ---- where the records are read: the decode's buffers (holds_decode), the resident mesh's, or uploads
+	bool b_res = holds_decode(cx, b);
+	for (size_t l = 0; l < nl && b_res; ++l) b_res = !compared(b, l) || decoded_records(cx, l).cap >= b.lists[l].data.size();
 	bool a_res = !b_res && cx.render_token == 0 && a.device_token != 0 && a.device_token == cx.resident_token;   // (d_rec holds one mesh at a time)
 	for (size_t l = 0; l < nl && a_res; ++l) a_res = !compared(a, l) || cx.d_rec[l].cap >= a.lists[l].data.size();
 
@@ -109,7 +98,7 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 	Carve O;
 	std::vector<size_t> o_err(nl, 0);
 	if (want_rows) for (size_t l = 0; l < nl; ++l) if (compared(a, l)) o_err[l] = O.reserve((size_t)a.lists[l].count * 4);
-	out.block.ensure(std::max<size_t>(O.total, 16));
+	out.block.alloc(cx.device, std::max<size_t>(O.total, 16));   // (without HRY_DISTORTION_ROWS there is no piece)
 
 	hipStream_t st = cx.stream;
 	uint64_t up = 0;
@@ -129,7 +118,7 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 		const AttrList &A = a.lists[l], &B = b.lists[l];
 		DistList J{};
 		if (a_res) J.a = cx.d_rec[l].as<uint8_t>(); else { put(w_a[l], A.data.data(), A.data.size()); J.a = W.ptr<uint8_t>(wb, w_a[l]); }
-		if (b_res) J.b = r_rec(l).as<uint8_t>(); else { put(w_b[l], B.data.data(), B.data.size()); J.b = W.ptr<uint8_t>(wb, w_b[l]); }
+		if (b_res) J.b = decoded_records(cx, l).as<uint8_t>(); else { put(w_b[l], B.data.data(), B.data.size()); J.b = W.ptr<uint8_t>(wb, w_b[l]); }
 		J.map = map[l];
 		J.err = want_rows ? O.ptr<float>(out.block.p, o_err[l]) : nullptr;
 		J.part = W.ptr<DistPart>(wb, w_part[l]);
@@ -178,22 +167,10 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 			memcpy(&f, res.data() + (slot_at[l] + nc) * sizeof(DistFinal), sizeof f);
 			out.pos.max_dist = f.mx; out.pos.sum_sq_dist = f.sum; out.pos.compared = f.compared; out.pos.argmax = f.row; out.pos.list = pl;
 		}
-		if (want_rows) out.bufs.push_back(DistortionBuf{ "error" + std::to_string(l), O.ptr<float>(out.block.p, o_err[l]), a.lists[l].count });
+		if (want_rows) out.bufs.push_back(NamedBuf{ "error" + std::to_string(l), O.ptr<void>(out.block.p, o_err[l]), a.lists[l].count, 1, HRY_FLOAT });
 	}
 	out.device_ms = (double)ms;
 	out.uploaded_bytes = up;
-}
-
-void distortion_copy(Context &cx, const DistortionResult &d, const char *name, void *dst, bool dst_is_device)
-{
-	const DistortionBuf *b = d.find(name);
-	if (!b) throw Error(HRY_E_ARG, std::string("no such distortion buffer: ") + name);
-	if (!b->rows) return;
-	if (!dst) throw Error(HRY_E_ARG, "null destination");
-	if (d.device != cx.device) throw Error(HRY_E_ARG, "the distortion buffers live on another device than the context's");
-	HIP_OK(hipSetDevice(cx.device));
-	HIP_OK(hipMemcpyAsync(dst, b->p, (size_t)b->rows * 4, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
-	HIP_OK(hipStreamSynchronize(cx.stream));
 }
 
 }   // namespace hry

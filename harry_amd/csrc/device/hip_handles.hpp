@@ -1,11 +1,13 @@
 // Owners of what the HIP runtime hands out: streams, events, device and pinned memory, registered host ranges.  Nothing else in
-// the library creates or destroys one of these (tests/test_hip_handles_cpu.py).  Streams and events are created when they are
-// first used; a creation that fails throws and leaves the owner empty, so the next use tries again.  Not thread-safe: whoever
-// shares an owner with a side thread touches it (get()) before the thread starts.
+// the library creates or destroys one of these, a result handle's device memory included (tests/test_hip_handles_cpu.py).  Streams
+// and events are created when they are first used; a creation that fails throws and leaves the owner empty, so the next use tries
+// again.  Not thread-safe: whoever shares an owner with a side thread touches it (get()) before the thread starts.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../../include/harry_amd.h"
 #include "../host/mesh.hpp"
@@ -86,6 +88,36 @@ struct DevBuf {
 		cap = want;
 	}
 	template <typename T> T *as() const { return (T*)p; }
+};
+
+// the one allocation a result handle owns (context.hpp: DeviceResult): exactly the bytes asked for -- it is sized once and kept as
+// long as the caller keeps the handle, so DevBuf's slack for growth would never be used -- and freed on its own device, whichever
+// device the thread that drops the handle has selected
+struct DeviceBlock {
+	int device = 0;
+	void *p = nullptr;
+	size_t bytes = 0;
+	DeviceBlock() = default;
+	DeviceBlock(const DeviceBlock&) = delete;
+	DeviceBlock &operator=(const DeviceBlock&) = delete;
+	~DeviceBlock() { if (p) { (void)hipSetDevice(device); (void)hipFree(p); } }
+	void alloc(int dev, size_t n)   // (once; dev: the device the caller has selected)
+	{
+		if (p) throw Error(HRY_E_INTERNAL, "a device block is allocated once");
+		void *q = nullptr;
+		HIP_OK(hipMalloc(&q, n));
+		device = dev; p = q; bytes = n;
+	}
+};
+
+// one allocation in 256-byte aligned pieces: reserve() every piece while sizing, allocate `total` bytes, then ptr() into the block.
+// A piece of 0 bytes takes one unit all the same, so no two pieces share an address (nobody depends on the smallest piece's size)
+struct Carve {
+	static constexpr size_t kAlign = 256;
+	std::vector<size_t> at;
+	size_t total = 0;
+	size_t reserve(size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 1) + kAlign - 1) & ~(kAlign - 1); return at.size() - 1; }
+	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
 };
 
 // pinned host memory, grow-only (persistent across calls: fresh pinned or pageable blocks cost a page fault per 4 KiB)

@@ -95,38 +95,35 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 	cx.d_rec[0].ensure(std::max<size_t>((size_t)nf * sfc, 16));
 	cx.d_rec[1].ensure(std::max<size_t>((size_t)nv * sv, 16));
 
-	// working arrays: 256-byte aligned pieces of one buffer
-	std::vector<size_t> at;
-	size_t total = 0;
-	auto reserve = [&](size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at.size() - 1; };
-	auto ptr = [&](size_t i) { return (void*)(cx.d_ingest.as<uint8_t>() + at[i]); };
+	Carve W;   // the working arrays, pieces of d_ingest
 	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64), nwv = (uint32_t)(((uint64_t)nv + 63) / 64);
 	const size_t slots = weld ? unweld_table_slots(nv) : 0;
 	const size_t status_bytes = sizeof(IngestStatus) + 8;   // (+ the number of welded vertices)
-	const size_t w_status = reserve(status_bytes);
-	const size_t w_fsum = reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
-	const size_t w_keys = reserve(weld ? (size_t)nv * sv : 0), w_table = reserve(slots * 4), w_first = reserve(weld ? (size_t)nv * 4 : 0);
-	const size_t w_masks = reserve(weld ? (size_t)nwv * 8 : 0), w_counts = reserve(weld ? (size_t)nwv * 4 : 0);
-	const size_t w_vstart = reserve(weld ? ((size_t)nwv + 1) * 4 : 0), w_remap = reserve(weld ? (size_t)nv * 4 : 0);
-	const size_t w_frow = reserve(weld ? (size_t)nv * 4 : 0);
-	cx.d_ingest.ensure(total);
-	IngestStatus *status = (IngestStatus*)ptr(w_status);
+	const size_t w_status = W.reserve(status_bytes);
+	const size_t w_fsum = W.reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = W.reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	const size_t w_keys = W.reserve(weld ? (size_t)nv * sv : 0), w_table = W.reserve(slots * 4), w_first = W.reserve(weld ? (size_t)nv * 4 : 0);
+	const size_t w_masks = W.reserve(weld ? (size_t)nwv * 8 : 0), w_counts = W.reserve(weld ? (size_t)nwv * 4 : 0);
+	const size_t w_vstart = W.reserve(weld ? ((size_t)nwv + 1) * 4 : 0), w_remap = W.reserve(weld ? (size_t)nv * 4 : 0);
+	const size_t w_frow = W.reserve(weld ? (size_t)nv * 4 : 0);
+	cx.d_ingest.ensure(W.total);
+	void *wb = cx.d_ingest.p;
+	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
 	uint32_t *d_nout = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
 
 	// ---- every kernel up to the checks, then ONE read-back of the status word (and the welded count)
-	launch_ingest_offsets(st, d_degrees, nf, (uint32_t*)ptr(w_fsum), (uint32_t*)ptr(w_fstart), cx.d_foff.as<uint32_t>(), status);
+	launch_ingest_offsets(st, d_degrees, nf, W.ptr<uint32_t>(wb, w_fsum), W.ptr<uint32_t>(wb, w_fstart), cx.d_foff.as<uint32_t>(), status);
 	const uint32_t *remap = nullptr;
 	if (weld) {
-		uint8_t *keys = (uint8_t*)ptr(w_keys);
+		uint8_t *keys = W.ptr<uint8_t>(wb, w_keys);
 		launch_ingest_pack(st, pv, nv, nullptr, nv, keys);
-		const WeldView u{ keys, (uint32_t)sv, nv, (uint32_t)(slots - 1), (uint32_t*)ptr(w_table) };
+		const WeldView u{ keys, (uint32_t)sv, nv, (uint32_t)(slots - 1), W.ptr<uint32_t>(wb, w_table) };
 		HIP_OK(hipMemsetAsync(u.table, 0xff, slots * 4, st));
-		launch_weld_count(st, u, (uint32_t*)ptr(w_first), (uint64_t*)ptr(w_masks), (uint32_t*)ptr(w_counts), (uint32_t*)ptr(w_vstart));
-		launch_weld_assign(st, nv, (const uint32_t*)ptr(w_first), (const uint64_t*)ptr(w_masks), (const uint32_t*)ptr(w_vstart), (uint32_t*)ptr(w_remap),
-		                   (uint32_t*)ptr(w_frow));
-		if (nv) HIP_OK(hipMemcpyAsync(d_nout, (const uint32_t*)ptr(w_vstart) + nwv, 4, hipMemcpyDeviceToDevice, st));
-		remap = (const uint32_t*)ptr(w_remap);
+		launch_weld_count(st, u, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_counts), W.ptr<uint32_t>(wb, w_vstart));
+		launch_weld_assign(st, nv, W.ptr<const uint32_t>(wb, w_first), W.ptr<const uint64_t>(wb, w_masks), W.ptr<const uint32_t>(wb, w_vstart), W.ptr<uint32_t>(wb, w_remap),
+		                   W.ptr<uint32_t>(wb, w_frow));
+		if (nv) HIP_OK(hipMemcpyAsync(d_nout, W.ptr<const uint32_t>(wb, w_vstart) + nwv, 4, hipMemcpyDeviceToDevice, st));
+		remap = W.ptr<const uint32_t>(wb, w_remap);
 	} else launch_ingest_pack(st, pv, nv, nullptr, nv, cx.d_rec[1].as<uint8_t>());
 	launch_ingest_org(st, d_indices, idx64, ne, nv, remap, cx.d_org.as<uint32_t>(), status);
 	launch_ingest_pack(st, pf, nf, nullptr, nf, cx.d_rec[0].as<uint8_t>());
@@ -144,7 +141,7 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 
 	// ---- welded: the records of the output vertices, gathered from the columns at each one's first row
 	if (weld) {
-		launch_ingest_pack(st, pv, nout, (const uint32_t*)ptr(w_frow), nv, cx.d_rec[1].as<uint8_t>());
+		launch_ingest_pack(st, pv, nout, W.ptr<const uint32_t>(wb, w_frow), nv, cx.d_rec[1].as<uint8_t>());
 		if (d_remap && nv) HIP_OK(hipMemcpyAsync(d_remap, remap, (size_t)nv * 4, hipMemcpyDeviceToDevice, st));
 	}
 	m->nv = nout; m->nf = nf;
@@ -270,45 +267,42 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	cx.d_cattr.ensure(std::max<size_t>((size_t)ne * 8, 16));
 	cx.d_fattr.ensure(16);
 
-	// working arrays: 256-byte aligned pieces of one buffer
-	std::vector<size_t> at;
-	size_t total = 0;
-	auto reserve = [&](size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at.size() - 1; };
-	auto ptr = [&](size_t i) { return (void*)(cx.d_ingest.as<uint8_t>() + at[i]); };
+	Carve W;   // the working arrays, pieces of d_ingest
 	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64);
 	const size_t status_bytes = sizeof(IngestStatus) + 16;   // (+ the records of the three lists after the weld, the face regions)
-	const size_t w_status = reserve(status_bytes);
-	const size_t w_fsum = reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
-	const size_t w_mfirst = reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0), w_mrank = reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0);
+	const size_t w_status = W.reserve(status_bytes);
+	const size_t w_fsum = W.reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = W.reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	const size_t w_mfirst = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0), w_mrank = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0);
 	for (int l = 0; l < nl && weld; ++l) {   // every welded list has its own keys and table
 		RowsIn &R = in[l];
 		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
 		R.slots = unweld_table_slots(n);
-		R.keys = reserve((size_t)n * R.pack.rec_stride); R.table = reserve(R.slots * 4); R.first = reserve((size_t)n * 4);
-		R.masks = reserve((size_t)nw * 8); R.counts = reserve((size_t)nw * 4); R.vstart = reserve(((size_t)nw + 1) * 4);
-		R.remap = reserve((size_t)n * 4); R.frow = reserve((size_t)n * 4);
+		R.keys = W.reserve((size_t)n * R.pack.rec_stride); R.table = W.reserve(R.slots * 4); R.first = W.reserve((size_t)n * 4);
+		R.masks = W.reserve((size_t)nw * 8); R.counts = W.reserve((size_t)nw * 4); R.vstart = W.reserve(((size_t)nw + 1) * 4);
+		R.remap = W.reserve((size_t)n * 4); R.frow = W.reserve((size_t)n * 4);
 	}
-	cx.d_ingest.ensure(total);
-	IngestStatus *status = (IngestStatus*)ptr(w_status);
+	cx.d_ingest.ensure(W.total);
+	void *wb = cx.d_ingest.p;
+	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
 	uint32_t *d_counts = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));   // [k]: records of list k after the weld; [3]: face regions
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
 
 	// ---- every kernel up to the checks, then ONE read-back: the status word, the welded counts, the number of regions
-	launch_ingest_offsets(st, d_degrees, nf, (uint32_t*)ptr(w_fsum), (uint32_t*)ptr(w_fstart), cx.d_foff.as<uint32_t>(), status);
+	launch_ingest_offsets(st, d_degrees, nf, W.ptr<uint32_t>(wb, w_fsum), W.ptr<uint32_t>(wb, w_fstart), cx.d_foff.as<uint32_t>(), status);
 	for (int l = 0; l < nl; ++l) {
 		RowsIn &R = in[l];
 		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
 		if (!weld) { launch_ingest_pack(st, R.pack, n, nullptr, n, cx.d_rec[l].as<uint8_t>()); continue; }
-		uint8_t *keys = (uint8_t*)ptr(R.keys);
+		uint8_t *keys = W.ptr<uint8_t>(wb, R.keys);
 		launch_ingest_pack(st, R.pack, n, nullptr, n, keys);
-		const WeldView u{ keys, R.pack.rec_stride, n, (uint32_t)(R.slots - 1), (uint32_t*)ptr(R.table) };
+		const WeldView u{ keys, R.pack.rec_stride, n, (uint32_t)(R.slots - 1), W.ptr<uint32_t>(wb, R.table) };
 		HIP_OK(hipMemsetAsync(u.table, 0xff, R.slots * 4, st));
-		launch_weld_count(st, u, (uint32_t*)ptr(R.first), (uint64_t*)ptr(R.masks), (uint32_t*)ptr(R.counts), (uint32_t*)ptr(R.vstart));
-		launch_weld_assign(st, n, (const uint32_t*)ptr(R.first), (const uint64_t*)ptr(R.masks), (const uint32_t*)ptr(R.vstart), (uint32_t*)ptr(R.remap),
-		                   (uint32_t*)ptr(R.frow));
-		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, (const uint32_t*)ptr(R.vstart) + nw, 4, hipMemcpyDeviceToDevice, st));
+		launch_weld_count(st, u, W.ptr<uint32_t>(wb, R.first), W.ptr<uint64_t>(wb, R.masks), W.ptr<uint32_t>(wb, R.counts), W.ptr<uint32_t>(wb, R.vstart));
+		launch_weld_assign(st, n, W.ptr<const uint32_t>(wb, R.first), W.ptr<const uint64_t>(wb, R.masks), W.ptr<const uint32_t>(wb, R.vstart), W.ptr<uint32_t>(wb, R.remap),
+		                   W.ptr<uint32_t>(wb, R.frow));
+		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, W.ptr<const uint32_t>(wb, R.vstart) + nw, 4, hipMemcpyDeviceToDevice, st));
 	}
-	auto remap_of = [&](const RowsIn &R) { return weld ? (const uint32_t*)ptr(R.remap) : nullptr; };
+	auto remap_of = [&](const RowsIn &R) { return weld ? W.ptr<const uint32_t>(wb, R.remap) : nullptr; };
 	launch_ingest_org(st, pos->indices, idx64, ne, rows0, remap_of(in[0]), cx.d_org.as<uint32_t>(), status);
 	CornerSlots cs{};
 	for (int l = 1; l < nl; ++l) {   // slots are compacted: tex, then nrm, whichever are given
@@ -318,9 +312,9 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	HIP_OK(hipMemsetAsync(cx.d_vreg.p, 0, std::max<size_t>((size_t)rows0 * 2, 16), st));   // one vertex region
 	launch_ingest_iota(st, rows0, cx.d_vattr.as<uint32_t>());                                // vertex v owns record v
 	if (d_face_material) {
-		HIP_OK(hipMemsetAsync(ptr(w_mfirst), 0xff, (size_t)kIngestMaterials * 4, st));
-		HIP_OK(hipMemsetAsync(ptr(w_mrank), 0, (size_t)kIngestMaterials * 4, st));
-		launch_ingest_regions(st, d_face_material, nf, (uint32_t*)ptr(w_mfirst), (uint32_t*)ptr(w_mrank), d_counts + 3, cx.d_freg.as<uint16_t>(), status);
+		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mfirst), 0xff, (size_t)kIngestMaterials * 4, st));
+		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mrank), 0, (size_t)kIngestMaterials * 4, st));
+		launch_ingest_regions(st, d_face_material, nf, W.ptr<uint32_t>(wb, w_mfirst), W.ptr<uint32_t>(wb, w_mrank), d_counts + 3, cx.d_freg.as<uint16_t>(), status);
 	} else HIP_OK(hipMemsetAsync(cx.d_freg.p, 0, std::max<size_t>((size_t)nf * 2, 16), st));
 	cx.h_small.ensure(4096);
 	HIP_OK(hipMemcpyAsync(cx.h_small.p, status, status_bytes, hipMemcpyDeviceToHost, st));
@@ -340,9 +334,9 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 		if (nout > n) throw Error(HRY_E_INTERNAL, "weld: more records than rows");
 		m->lists[l].count = nout;
 		// ---- welded: the records of the output, gathered from the columns at each one's first row
-		if (weld) launch_ingest_pack(st, R.pack, nout, (const uint32_t*)ptr(R.frow), n, cx.d_rec[l].as<uint8_t>());
+		if (weld) launch_ingest_pack(st, R.pack, nout, W.ptr<const uint32_t>(wb, R.frow), n, cx.d_rec[l].as<uint8_t>());
 		if (d_remap && d_remap[R.k] && n) {
-			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], ptr(R.remap), (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], W.ptr<void>(wb, R.remap), (size_t)n * 4, hipMemcpyDeviceToDevice, st));
 			else launch_ingest_iota(st, n, d_remap[R.k]);
 		}
 	}

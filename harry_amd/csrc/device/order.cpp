@@ -5,7 +5,7 @@
 // the walk's host arrays: order_f when no face plane reads it, both orders behind the pipelined chunked encode (which sends them
 // run by run inside its batches).  The vertex map is computed from order_v like k_rank's table, not adopted from d_rank: the
 // general paths keep the faces' ranks behind it and the pipelined path fills it by runs, and a scatter of 4 bytes a vertex is not
-// worth a dependency on either.  The result owns one allocation (DevBuf) that no later call on the context touches.
+// worth a dependency on either.  The result owns one allocation (DeviceBlock) that no later call on the context touches.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -16,13 +16,6 @@
 namespace hry {
 
 using namespace dev;
-
-namespace {
-
-constexpr size_t kAlign = 256;
-size_t aligned(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
-
-}   // namespace
 
 void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t *d_order_v, const uint32_t *d_order_f)
 {
@@ -38,66 +31,51 @@ void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t
 
 	// ---- the result: every map and its inverse in one block, filled with HRY_NO_ELEMENT
 	std::unique_ptr<OrderResult> R(new OrderResult());
-	R->device = cx.device;
-	size_t bytes = 0;
-	std::vector<size_t> at;
+	Carve O;   // piece k is bufs[k]
 	auto add = [&](const std::string &name, uint64_t rows) {
 		for (int inv = 0; inv < 2; ++inv) {
-			OrderMap om;
-			om.name = inv ? name + "_inv" : name; om.rows = rows;
-			R->maps.push_back(om);
-			at.push_back(bytes);
-			bytes += aligned((size_t)rows * 4);
+			R->bufs.push_back(NamedBuf{ inv ? name + "_inv" : name, nullptr, rows, 1, HRY_UINT });
+			O.reserve((size_t)rows * 4);
 		}
 	};
 	add("vertex", nv); add("face", nf); add("corner", ne);
 	if (m.general) for (size_t l = 0; l < m.lists.size(); ++l) add("list" + std::to_string(l), m.lists[l].count);
-	R->block.ensure(std::max<size_t>(bytes, 16));
-	for (size_t k = 0; k < R->maps.size(); ++k) R->maps[k].p = (uint32_t*)(R->block.as<uint8_t>() + at[k]);
-	HIP_OK(hipMemsetAsync(R->block.p, 0xff, std::max<size_t>(bytes, 16), cx.stream));
-	uint32_t *vertex = R->maps[0].p, *vertex_inv = R->maps[1].p, *face = R->maps[2].p, *face_inv = R->maps[3].p, *corner = R->maps[4].p, *corner_inv = R->maps[5].p;
+	R->block.alloc(cx.device, O.total);
+	for (size_t k = 0; k < R->bufs.size(); ++k) R->bufs[k].p = O.ptr<void>(R->block.p, k);
+	HIP_OK(hipMemsetAsync(R->block.p, 0xff, O.total, cx.stream));
+	auto map = [&](size_t k) { return (uint32_t*)R->bufs[k].p; };
+	uint32_t *vertex = map(0), *vertex_inv = map(1), *face = map(2), *face_inv = map(3), *corner = map(4), *corner_inv = map(5);
 
 	// ---- working arrays: the orders the encode did not leave whole in HBM, the coded faces' degrees, their scan
-	const size_t a_ov = 0, a_of = a_ov + (d_order_v ? 0 : aligned((size_t)vc * 4)), a_deg = a_of + (d_order_f ? 0 : aligned((size_t)fc * 4));
-	const size_t a_doff = a_deg + (mixed ? aligned((size_t)fc * 4) : 0), a_sums = a_doff + (mixed ? aligned(((size_t)fc + 1) * 4) : 0);
-	const size_t ws_bytes = a_sums + (mixed ? aligned(scan_sums_words(fc) * 4) : 0);
-	cx.d_order_ws.ensure(std::max<size_t>(ws_bytes, 16));
-	uint8_t *ws = cx.d_order_ws.as<uint8_t>();
+	Carve W;
+	const size_t w_ov = W.reserve(d_order_v ? 0 : (size_t)vc * 4), w_of = W.reserve(d_order_f ? 0 : (size_t)fc * 4);
+	const size_t w_deg = W.reserve(mixed ? (size_t)fc * 4 : 0), w_doff = W.reserve(mixed ? ((size_t)fc + 1) * 4 : 0);
+	const size_t w_sums = W.reserve(mixed ? scan_sums_words(fc) * 4 : 0);
+	cx.d_order_ws.ensure(W.total);
+	void *ws = cx.d_order_ws.p;
 	if (!d_order_v) {
-		if (vc) HIP_OK(hipMemcpyAsync(ws + a_ov, w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
-		d_order_v = (const uint32_t*)(ws + a_ov);
+		if (vc) HIP_OK(hipMemcpyAsync(W.ptr<void>(ws, w_ov), w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_v = W.ptr<uint32_t>(ws, w_ov);
 	}
 	if (!d_order_f) {
-		if (fc) HIP_OK(hipMemcpyAsync(ws + a_of, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
-		d_order_f = (const uint32_t*)(ws + a_of);
+		if (fc) HIP_OK(hipMemcpyAsync(W.ptr<void>(ws, w_of), w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_f = W.ptr<uint32_t>(ws, w_of);
 	}
-	uint32_t *deg = mixed ? (uint32_t*)(ws + a_deg) : nullptr, *doff = mixed ? (uint32_t*)(ws + a_doff) : nullptr;
+	uint32_t *deg = mixed ? W.ptr<uint32_t>(ws, w_deg) : nullptr, *doff = mixed ? W.ptr<uint32_t>(ws, w_doff) : nullptr;
 
 	launch_order_vertex(cx.stream, d_order_v, vc, cv.org, nv, vertex, vertex_inv);
 	launch_order_face(cx.stream, cv, d_order_f, fc, face, face_inv, deg);
-	if (mixed && fc) launch_excl_scan(cx.stream, deg, fc, (uint32_t*)(ws + a_sums), doff);
+	if (mixed && fc) launch_excl_scan(cx.stream, deg, fc, W.ptr<uint32_t>(ws, w_sums), doff);
 	if (fc) launch_order_corner(cx.stream, cv, d_order_f, face, doff, corner, corner_inv);
 	if (m.general)
 		for (size_t l = 0; l < m.lists.size(); ++l) {
 			const OrderListSource &S = cx.order_lists[l];
 			if (S.nd > m.lists[l].count) throw Error(HRY_E_INTERNAL, "numbering maps: more records created than the list has");
-			launch_order_records(cx.stream, S.d_idx, S.nd, m.lists[l].count, R->maps[6 + 2 * l].p, R->maps[7 + 2 * l].p);
+			launch_order_records(cx.stream, S.d_idx, S.nd, m.lists[l].count, map(6 + 2 * l), map(7 + 2 * l));
 		}
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipStreamSynchronize(cx.stream));   // (the pageable host arrays above are the walk's: they go with the encode)
 	cx.order = std::move(R);
-}
-
-void order_copy(Context &cx, const OrderResult &o, const char *name, void *dst, bool dst_is_device)
-{
-	const OrderMap *b = o.find(name);
-	if (!b) throw Error(HRY_E_ARG, std::string("no such numbering map: ") + name);
-	if (!b->rows) return;
-	if (!dst) throw Error(HRY_E_ARG, "null destination");
-	if (o.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
-	HIP_OK(hipSetDevice(cx.device));
-	HIP_OK(hipMemcpyAsync(dst, b->p, (size_t)b->rows * 4, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
-	HIP_OK(hipStreamSynchronize(cx.stream));
 }
 
 void order_apply(Context &cx, const OrderResult &o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
@@ -107,9 +85,9 @@ void order_apply(Context &cx, const OrderResult &o, const char *kind, int direct
 	const std::string k(kind);
 	if (k.size() >= 4 && k.compare(k.size() - 4, 4, "_inv") == 0) throw Error(HRY_E_ARG, "unknown kind: " + k + " (the direction selects the inverse)");
 	// TO_DECODED: dst is indexed by decoded elements, dst row j = src row kind_inv[j]; TO_SOURCE: dst row i = src row kind[i]
-	const OrderMap *map = o.find(direction == HRY_ORDER_TO_DECODED ? k + "_inv" : k);
+	const NamedBuf *map = o.find(direction == HRY_ORDER_TO_DECODED ? k + "_inv" : k);
 	if (!map) throw Error(HRY_E_ARG, "unknown kind: " + k);
-	if (o.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
+	if (o.block.device != cx.device) throw Error(HRY_E_ARG, "the numbering maps live on another device than the context's");
 	if (row_bytes == 0) throw Error(HRY_E_ARG, "row_bytes is 0");
 	if (src_stride < row_bytes || dst_stride < row_bytes) throw Error(HRY_E_ARG, "a stride below row_bytes");
 	if (dst_rows != map->rows) throw Error(HRY_E_ARG, "dst_rows is " + std::to_string(dst_rows) + ", the map \"" + map->name + "\" has " + std::to_string(map->rows) + " rows");
@@ -121,7 +99,7 @@ void order_apply(Context &cx, const OrderResult &o, const char *kind, int direct
 	check_device_memory(cx, d_dst, dst_span, "dst");
 	const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
 	if (s0 < d0 + dst_span && d0 < s0 + src_span) throw Error(HRY_E_ARG, "src and dst overlap");
-	if (!launch_order_rows(cx.stream, map->p, dst_rows, d_src, src_stride, d_dst, dst_stride, row_bytes)) throw Error(HRY_E_UNSUPPORTED, "more than 2^39 words in one move");
+	if (!launch_order_rows(cx.stream, (const uint32_t*)map->p, dst_rows, d_src, src_stride, d_dst, dst_stride, row_bytes)) throw Error(HRY_E_UNSUPPORTED, "more than 2^39 words in one move");
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipStreamSynchronize(cx.stream));
 }

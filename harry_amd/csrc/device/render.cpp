@@ -19,29 +19,7 @@ namespace hry {
 
 using namespace dev;
 
-size_t RenderBuf::bytes() const { return (size_t)rows * (size_t)width * (type == HRY_USHORT ? 2u : 4u); }
-RenderResult::~RenderResult()
-{
-	if (block) { (void)hipSetDevice(device); (void)hipFree(block); }
-}
-const RenderBuf *RenderResult::find(const char *name) const
-{
-	for (const RenderBuf &b : bufs) if (b.name == name) return &b;
-	return nullptr;
-}
-
 namespace {
-
-constexpr size_t kAlign = 256;
-inline size_t align_up(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
-
-// carves one device allocation into aligned pieces: reserve() while sizing, then take() in the same order
-struct Carve {
-	std::vector<size_t> at;
-	size_t total = 0;
-	size_t reserve(size_t bytes) { at.push_back(total); total += align_up(std::max<size_t>(bytes, 4)); return at.size() - 1; }
-	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
-};
 
 // every component of list L, dequantised as hry_requant(clear) would (requant_plan: the quantised ones), the others as they are
 RequantPlan gather_plan(const AttrList &L)
@@ -104,7 +82,6 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	if (m.face_off.size() != (size_t)nf + 1 || m.org.size() < ne) throw Error(HRY_E_ARG, "mesh without its connectivity");
 	const uint64_t ntri = m.ntri();
 	HIP_OK(hipSetDevice(cx.device));
-	out.device = cx.device;
 	const size_t nl = m.lists.size();
 	const bool general = m.general;
 	const Bindings &b = m.bind;
@@ -151,10 +128,8 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	// (a sharded container decoded here: d_whole_*, PLY layout only -- place_segment)
 	const bool whole = cx.render_whole;
 	const DevBuf &r_foff = whole ? cx.d_whole_foff : cx.d_foff, &r_org = whole ? cx.d_whole_org : cx.d_org;
-	auto r_rec = [&](size_t l) -> const DevBuf & { return whole ? cx.d_whole_rec[l] : cx.d_rec[l]; };
-	bool resident = m.render_token != 0 && m.render_token == cx.render_token && cx.render_nf == nf && cx.render_ne == ne && !(whole && (general || nl > 2)) &&
-	                r_foff.cap >= ((size_t)nf + 1) * 4 && r_org.cap >= (size_t)ne * 4;
-	for (size_t l = 0; l < nl && resident; ++l) resident = !rendered(m.lists[l]) || r_rec(l).cap >= m.lists[l].data.size();
+	bool resident = holds_decode(cx, m) && r_foff.cap >= ((size_t)nf + 1) * 4 && r_org.cap >= (size_t)ne * 4;
+	for (size_t l = 0; l < nl && resident; ++l) resident = !rendered(m.lists[l]) || decoded_records(cx, l).cap >= m.lists[l].data.size();
 	if (general && resident)
 		resident = cx.d_freg.cap >= (size_t)nf * 2 && cx.d_vreg.cap >= (size_t)nv * 2 && cx.d_fattr.cap >= b.face_attr.size() * 4 &&
 		           cx.d_vattr.cap >= b.vtx_attr.size() * 4 && cx.d_cattr.cap >= b.corner_attr.size() * 4;
@@ -203,7 +178,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	const uint32_t *fattr = nullptr, *vattr = nullptr, *cattr = nullptr;
 	if (resident) {
 		foff = r_foff.as<uint32_t>(); org = r_org.as<uint32_t>();
-		for (size_t l = 0; l < nl; ++l) rec[l] = r_rec(l).as<uint8_t>();
+		for (size_t l = 0; l < nl; ++l) rec[l] = decoded_records(cx, l).as<uint8_t>();
 		if (general) {
 			freg = cx.d_freg.as<uint16_t>(); vreg = cx.d_vreg.as<uint16_t>();
 			fattr = cx.d_fattr.as<uint32_t>(); vattr = cx.d_vattr.as<uint32_t>(); cattr = cx.d_cattr.as<uint32_t>();
@@ -266,8 +241,8 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 		if (rendered(m.lists[l])) add("list" + std::to_string(l), m.lists[l].target == 0 ? nf : nout, m.lists[l].ncomp(), HRY_FLOAT);
 	if (want_vn) add("normals", nout, 3, HRY_FLOAT);
 	if (want_fn) add("face_normals", nf, 3, HRY_FLOAT);
-	HIP_OK(hipMalloc(&out.block, O.total));
-	for (const Plan &p : plan) out.bufs.push_back(RenderBuf{ p.name, O.ptr<void>(out.block, p.slot), p.rows, p.width, p.type });
+	out.block.alloc(cx.device, O.total);
+	for (const Plan &p : plan) out.bufs.push_back(NamedBuf{ p.name, O.ptr<void>(out.block.p, p.slot), p.rows, p.width, p.type });
 	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
 
 	if (want_vn && nv) {   // (the counters' fill lies outside the events, like the table's)
@@ -351,6 +326,12 @@ void mark_decoded(Context &cx, Mesh &m, bool whole)
 	cx.render_nf = m.nf; cx.render_ne = m.ne();
 }
 
+bool holds_decode(const Context &cx, const Mesh &m)
+{
+	return m.render_token != 0 && m.render_token == cx.render_token && cx.render_nf == m.nf && cx.render_ne == m.ne() &&
+	       !(cx.render_whole && (m.general || m.lists.size() > 2));
+}
+
 bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &runs, uint32_t gnv, uint32_t gnf, uint32_t gne)
 {
 	const uint32_t nlv = seg.nv, nlf = seg.nf, nle = seg.ne(), nr = (uint32_t)runs.size();
@@ -378,12 +359,13 @@ bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &ru
 	return true;
 }
 
-void render_copy(Context &cx, const RenderResult &r, const char *name, void *dst, bool dst_is_device)
+void result_copy(Context &cx, const DeviceResult &r, const char *name, const char *what, void *dst, bool dst_is_device, bool same_device)
 {
-	const RenderBuf *b = r.find(name);
-	if (!b) throw Error(HRY_E_ARG, std::string("no such render buffer: ") + name);
+	const NamedBuf *b = r.find(name);
+	if (!b) throw Error(HRY_E_ARG, std::string("no such ") + what + ": " + name);
 	if (!b->bytes()) return;
 	if (!dst) throw Error(HRY_E_ARG, "null destination");
+	if (same_device && r.block.device != cx.device) throw Error(HRY_E_ARG, std::string("the ") + what + "s live on another device than the context's");
 	HIP_OK(hipSetDevice(cx.device));
 	HIP_OK(hipMemcpyAsync(dst, b->p, b->bytes(), dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cx.stream));
 	HIP_OK(hipStreamSynchronize(cx.stream));

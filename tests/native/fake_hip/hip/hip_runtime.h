@@ -16,8 +16,10 @@ enum { hipStreamNonBlocking = 1, hipEventDefault = 0, hipEventDisableTiming = 2,
 
 namespace fake_hip {
 inline std::string calls;          // s S x: stream created, synchronised, destroyed; e t y: event created (untimed, timed), destroyed;
-                                   // m f: device memory; p q: pinned memory; r u: host range registered, unregistered; g: error cleared
-inline int fail_in = 0, last_priority = 0;
+                                   // m f: device memory; p q: pinned memory; r u: host range registered, unregistered; g: error cleared;
+                                   // d: device selected
+inline int fail_in = 0, last_priority = 0, device = 0;
+inline size_t last_malloc = 0;     // bytes asked of the last hipMalloc
 inline std::set<void*> live, ranges;
 inline int count(char c) { return (int)std::count(calls.begin(), calls.end(), c); }
 inline hipError_t make(void **out, char c)
@@ -45,7 +47,8 @@ inline hipError_t hipStreamSynchronize(hipStream_t s) { if (!fake_hip::live.coun
 inline hipError_t hipStreamDestroy(hipStream_t s) { return fake_hip::drop(s, 'x'); }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags) { return fake_hip::make((void**)e, flags == hipEventDisableTiming ? 'e' : 't'); }
 inline hipError_t hipEventDestroy(hipEvent_t e) { return fake_hip::drop(e, 'y'); }
-inline hipError_t hipMalloc(void **p, size_t) { return fake_hip::make(p, 'm'); }
+inline hipError_t hipSetDevice(int d) { fake_hip::device = d; fake_hip::calls += 'd'; return hipSuccess; }
+inline hipError_t hipMalloc(void **p, size_t n) { fake_hip::last_malloc = n; return fake_hip::make(p, 'm'); }
 inline hipError_t hipFree(void *p) { return fake_hip::drop(p, 'f'); }
 inline hipError_t hipHostMalloc(void **p, size_t, unsigned) { return fake_hip::make(p, 'p'); }
 inline hipError_t hipHostFree(void *p) { return fake_hip::drop(p, 'q'); }

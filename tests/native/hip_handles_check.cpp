@@ -1,6 +1,7 @@
 // The contract of harry_amd/csrc/device/hip_handles.hpp, against a counting stand-in for the runtime (fake_hip/), under
 // AddressSanitizer / UBSan.  These are the paths a device error takes: no test provokes one on a device.
 // Built and run by tests/test_hip_handles_cpu.py.  Prints "ok" and exits 0 when every check holds.
+#include <cstdint>
 #include <cstdio>
 #include <deque>
 #include <utility>
@@ -134,6 +135,41 @@ int main()
 			check(throws_error([&] { d.ensure(d.cap + 1); }) && d.p == nullptr && d.cap == 0, "a failed allocation leaves the buffer empty");
 		}
 		check(count('m') == count('f') && count('p') == count('q'), "every block is freed");
+	}
+	calls.clear();
+	{   // a result's block: nothing until alloc, exactly the bytes asked for, freed once on its own device
+		{
+			DeviceBlock b;
+			check(calls.empty() && b.p == nullptr && b.bytes == 0, "no block until alloc");
+			b.alloc(3, 1000);
+			check(calls == "m" && fake_hip::last_malloc == 1000 && b.p && b.bytes == 1000 && b.device == 3, "alloc asks for exactly n bytes");
+			fake_hip::device = 0;
+		}
+		check(calls == "mdf" && fake_hip::device == 3, "the block's device is selected, then the block is freed: once each");
+		calls.clear();
+		{
+			DeviceBlock b;
+			fake_hip::fail_in = 1;
+			check(throws_error([&] { b.alloc(1, 64); }) && b.p == nullptr && b.bytes == 0, "a failed alloc throws and leaves the owner empty");
+		}
+		check(calls.empty(), "an empty block selects no device and frees nothing");
+	}
+	{   // the carver: 256-byte aligned pieces in order, a piece of its own even for 0 bytes
+		const size_t sizes[] = { 0, 1, 255, 256, 257, 0, 0, 1000, 256, 0 };
+		Carve c;
+		check(c.total == 0, "an empty carve has no bytes");
+		std::vector<size_t> piece;
+		for (size_t n : sizes) piece.push_back(c.reserve(n));
+		alignas(256) static uint8_t base[16 * 256];
+		bool ok = c.total <= sizeof base;
+		for (size_t i = 0; i < piece.size() && ok; ++i) {
+			const size_t at = (size_t)(c.ptr<uint8_t>(base, piece[i]) - base), end = at + sizes[i];
+			const size_t next = i + 1 < piece.size() ? (size_t)(c.ptr<uint8_t>(base, piece[i + 1]) - base) : c.total;
+			ok = piece[i] == i && at % 256 == 0 && end <= next && at < next && (uintptr_t)c.ptr<uint32_t>(base, piece[i]) % 256 == 0;
+		}
+		check(ok, "every piece is 256-byte aligned, begins at or after the end of the one before, and has an address of its own");
+		check(c.total % 256 == 0 && c.total == (size_t)(c.ptr<uint8_t>(base, piece.back()) - base) + 256, "total is the end of the last piece");
+		check(c.total == 256 * (1 + 1 + 1 + 1 + 2 + 1 + 1 + 4 + 1 + 1), "an empty piece takes one unit, the others their size rounded up");
 	}
 	check(fake_hip::live.empty() && fake_hip::ranges.empty() && calls.find('!') == std::string::npos, "the counts balance at exit");
 	if (failures) return 1;

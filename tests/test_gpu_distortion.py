@@ -10,6 +10,7 @@ and hry_list_set_bounds refuses a quantised list.  Lossless `double` components 
 them), so mg.doubles round-trips at -q12 only."""
 import ctypes as C
 import math
+import os
 import subprocess
 
 import numpy as np
@@ -20,6 +21,7 @@ from harry_amd import cli
 from harry_amd import codec as hc
 from harry_amd import meshgen as mg
 from tests import distortion_ref as dref
+from tests import util
 from tests.test_order_cpu import MESHES, SCENES, load_scene
 
 pytestmark = pytest.mark.gpu
@@ -351,3 +353,155 @@ def test_cli_report(cx, tmp_path):
         for got, ref in ((float(w[8]), want["max_abs"]), (float(w[10]), want["rms"])):
             assert abs(got - ref) <= 1e-8 * abs(ref), (c, got, ref)
     d.close()
+
+
+# ---- 8. the buffers of a render, an order and a distortion handle: found by name in one allocation, owned by the handle
+GOLD = os.path.join(util.ROOT, "tests", "golden")
+ELEMENT_BYTES = {0: 4, 4: 4, 6: 2}   # HRY_FLOAT, HRY_UINT, HRY_USHORT
+TORCH_OF = {0: torch.float32, 4: torch.int32, 6: torch.int16}
+
+
+def _read(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def _one_triangle():
+    v = np.zeros(3, np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    v["x"], v["y"] = [0, 1, 0], [0, 0, 1]
+    return hc.Mesh.from_arrays(v, np.array([3], np.uint8), np.array([0, 1, 2], np.uint32))
+
+
+HANDLE_MESHES = {
+    "one_triangle": _one_triangle,
+    "torus_mixed": lambda: hc.Mesh.from_ply(_read(os.path.join(GOLD, "torus_mixed.ply"))),                           # mixed degrees, PLY layout
+    "smooth_obj": lambda: hc.Mesh.from_obj(_read(os.path.join(GOLD, "obj", "smooth.obj")), os.path.join(GOLD, "obj")),   # corner lists: the unweld, "list<l>" maps
+}
+
+
+class Handles:
+    """of one mesh on cx: its encode's order handle, a render handle of the decode with both normals flags and a distortion handle
+    with HRY_DISTORTION_ROWS, each read through the C interface alone"""
+
+    def __init__(self, cx, src: hc.Mesh):
+        L = nat.load()
+        self.cx, self.src = cx, src
+        data, self.order = cx.write_hry(src.clone(), profile=hc.PROFILE_CHUNKED, return_order=True)
+        self.dec = cx.read_hry(data)
+        self.dist = cx.distortion(src, self.dec, self.order, rows=True)
+        self.render = C.c_void_p()
+        nat.check(L.hry_render_build_ex(cx.h, self.dec.h, hc.Codec.RENDER_VERTEX_NORMALS | hc.Codec.RENDER_FACE_NORMALS, C.byref(self.render)))
+        lists = tuple(f"list{l}" for l in range(src.nlists))
+        self.h = {"render": self.render, "order": self.order.h, "distortion": self.dist.h}
+        self.names = {"render": hc.Codec.RENDER_FIXED + lists + hc.Codec.RENDER_NORMALS,
+                      "order": tuple(n + sfx for n in hc.Order.KINDS + lists for sfx in ("", "_inv")),
+                      "distortion": tuple(f"error{l}" for l in range(src.nlists))}
+
+    def close(self):
+        nat.load().hry_render_free(self.render)
+        self.dist.close()
+        self.order.close()
+
+    def get(self, kind: str, name: str) -> tuple:
+        """(device address, rows, width, component type) of a buffer; rows 0: the handle has none of that name"""
+        L = nat.load()
+        dev, rows, width, typ = C.c_void_p(), C.c_uint64(), C.c_int(1), C.c_int(4 if kind == "order" else 0)
+        if kind == "render":
+            nat.check(L.hry_render_get(self.h[kind], name.encode(), C.byref(dev), C.byref(rows), C.byref(width), C.byref(typ)))
+        else:
+            nat.check(getattr(L, f"hry_{kind}_get")(self.h[kind], name.encode(), C.byref(dev), C.byref(rows)))
+        return dev.value or 0, rows.value, width.value, typ.value
+
+    def copy(self, kind: str, name: str, dst, on_device: bool) -> int:
+        return getattr(nat.load(), f"hry_{kind}_copy")(self.cx.h, self.h[kind], name.encode(), dst, int(on_device))
+
+    def present(self, kind: str) -> list:
+        return [n for n in self.names[kind] if self.get(kind, n)[1]]
+
+    def host_bytes(self, kind: str, name: str) -> bytes:
+        _, rows, width, typ = self.get(kind, name)
+        a = np.empty(rows * width * ELEMENT_BYTES[typ], np.uint8)
+        assert self.copy(kind, name, a.ctypes.data, False) == nat.OK, (kind, name)
+        return a.tobytes()
+
+    def results(self) -> dict:
+        """every buffer of the three handles as host bytes and what else a build computes: the same from every build of one mesh"""
+        L = nat.load()
+        out = {(kind, n): self.host_bytes(kind, n) for kind in self.h for n in self.present(kind)}
+        out["render counts"] = (L.hry_render_nverts(self.render), L.hry_render_ntris(self.render))
+        out["distortion"] = _snapshot(self.dist, self.src)[:2]
+        return out
+
+    def snapshot(self) -> dict:
+        """... and the statistics, which hold the build's own times"""
+        d, up = C.c_double(), C.c_uint64()
+        nat.check(nat.load().hry_render_stat(self.render, C.byref(d), C.byref(up)))
+        return dict(self.results(), render_stat=(d.value, up.value), distortion_stat=tuple(sorted(self.dist.stat().items())))
+
+
+@pytest.mark.parametrize("name", sorted(HANDLE_MESHES))
+def test_buffers_of_a_handle_are_disjoint_and_copy_both_ways(cx, name):
+    src = HANDLE_MESHES[name]()
+    H = Handles(cx, src)
+    L = nat.load()
+    dev = torch.device("cuda", 0)
+
+    def usable():   # the context builds good results again: those of the first build
+        again = Handles(cx, src)
+        try:
+            assert again.results() == first
+        finally:
+            again.close()
+
+    try:
+        first = H.results()
+        assert H.present("render")[:3] == ["indices", "tri_face", "vertex_source"] and {"normals", "face_normals"} <= set(H.present("render"))
+        assert {"vertex", "vertex_inv", "face", "face_inv", "corner", "corner_inv"} <= set(H.present("order"))
+        assert H.present("distortion") == [f"error{l}" for l in compared_lists(src)] and H.present("distortion")
+        if src.general:
+            assert "corner_source" in H.present("render") and "face_region" in H.present("render") and "list1_inv" in H.present("order")
+        for kind in H.h:
+            spans = []
+            for n in H.present(kind):
+                addr, rows, width, typ = H.get(kind, n)
+                assert addr != 0 and width >= 1, (kind, n)
+                spans.append((addr, addr + rows * width * ELEMENT_BYTES[typ], n))
+                torch.cuda.current_stream(dev).synchronize()
+                t = torch.empty((rows * width,), dtype=TORCH_OF[typ], device=dev)
+                assert H.copy(kind, n, t.data_ptr(), True) == nat.OK, (kind, n)
+                assert t.cpu().numpy().tobytes() == first[(kind, n)], (kind, n)   # device to device, then down through torch
+            spans.sort()
+            for (_, end, n0), (start, _, n1) in zip(spans, spans[1:]):
+                assert end <= start, (kind, n0, n1, [(hex(a), e - a, n) for a, e, n in spans])
+            # an absent name, then a NULL destination for a buffer that has rows
+            host = np.zeros(16, np.uint8)
+            assert H.get(kind, "no_such_buffer")[:2] == (0, 0)
+            assert H.copy(kind, "no_such_buffer", host.ctypes.data, False) == nat.E_ARG and L.hry_last_error()
+            usable()
+            for on_device in (False, True):
+                assert H.copy(kind, H.present(kind)[0], None, on_device) == nat.E_ARG and L.hry_last_error()
+            usable()
+        assert H.results() == first
+    finally:
+        H.close()
+
+
+def test_render_and_distortion_handles_outlive_the_contexts_work(cx, tmp_path):
+    """(tests/test_gpu_order.py: test_handle_outlives_the_contexts_work, for the other two handles)"""
+    H = Handles(cx, HANDLE_MESHES["smooth_obj"]())
+    P = Handles(cx, HANDLE_MESHES["torus_mixed"]())
+    try:
+        before = H.snapshot(), P.snapshot()
+        big = hc.Mesh.from_ply(mg.torus(90, 80, polys="mixed", normals=True).to_ply())   # (larger than either: the context's buffers grow, and are reused)
+        for profile in (hc.PROFILE_COMPAT, hc.PROFILE_CHUNKED):
+            data, order = cx.write_hry(big.clone(), profile=profile, return_order=True)
+            dec = cx.read_hry(data)
+            assert len(cx.render_numpy(dec, normals="area", face_normals=True)["normals"]) == big.nv
+            cx.distortion(big, dec, order, rows=True).close()
+            order.close()
+        sc = load_scene(SCENES["uv_normals_materials"](), tmp_path)
+        assert "corner_source" in cx.render_numpy(cx.read_hry(cx.write_hry(sc, profile=hc.PROFILE_CHUNKED)))
+        assert (H.snapshot(), P.snapshot()) == before
+    finally:
+        H.close()
+        P.close()

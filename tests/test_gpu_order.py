@@ -1,7 +1,9 @@
 """Numbering maps of an encode on the GPU (include/harry_amd.h: hry_order_take; kernels: harry_amd/csrc/device/order.hip) through
 Codec.write_hry(..., return_order=True): the device's maps against the restatement of tests/order_ref.py (pinned to the oracle by
 tests/test_order_cpu.py), the source permuted by them against the product's own decode array for array, both profiles, general
-bindings, rows moved through the maps, the composition with the ingest's weld, and the refusals.  Every comparison is exact."""
+bindings, rows moved through the maps, the composition with the ingest's weld, and the refusals.  Every comparison is exact.
+(That an order handle's maps do not overlap and copy alike to host and device is checked with the other two handles in
+tests/test_gpu_distortion.py, section 8.)"""
 import ctypes as C
 
 import numpy as np

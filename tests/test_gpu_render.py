@@ -1,6 +1,8 @@
 """Render-ready device buffers (include/harry_amd.h: hry_render_build; kernels: harry_amd/csrc/device/render.hip) against the
 numpy restatement of tests/render_ref.py: fan triangulation, float columns after the reference's `-c` dequantisation (pinned to the
-reference's own dequantised goldens), the unweld of general bindings, residency after a decode, and the torch interface."""
+reference's own dequantised goldens), the unweld of general bindings, residency after a decode, and the torch interface.
+(That a render handle's buffers do not overlap, copy alike to host and device and outlive the context's later work is checked
+with the other two handles in tests/test_gpu_distortion.py, section 8.)"""
 import ctypes as C
 import json
 import os

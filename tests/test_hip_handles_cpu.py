@@ -1,6 +1,7 @@
 """What the HIP runtime hands out -- streams, events, device and pinned memory, registered host ranges -- is owned by the types
 of harry_amd/csrc/device/hip_handles.hpp.  No other source creates or destroys one, and the header's contract (created on first
-use, destroyed once, a failed creation leaves the owner empty) holds against a counting stand-in for the runtime under
+use, destroyed once, a failed creation leaves the owner empty; a result's block exactly as large as asked, freed on its own device;
+one allocation carved into aligned pieces that never share an address) holds against a counting stand-in for the runtime under
 AddressSanitizer / UBSan: the paths a device error would take, which no test provokes on a device."""
 import glob
 import os
@@ -14,7 +15,6 @@ from tests import util
 
 CSRC = os.path.join(util.ROOT, "harry_amd", "csrc")
 OWNERS = os.path.join(CSRC, "device", "hip_handles.hpp")
-RENDER = os.path.join(CSRC, "device", "render.cpp")   # RenderResult owns the one block its buffers lie in
 NATIVE = os.path.join(util.ROOT, "tests", "native")
 CHECK = os.path.join(NATIVE, "hip_handles_check.cpp")
 
@@ -39,7 +39,7 @@ def _found(pattern, allowed):
 def test_handles_have_one_owner():
     assert os.path.isfile(OWNERS) and len(sources()) > 30
     assert _found(HANDLES, {OWNERS}) == [], "streams, events, pinned memory and registrations are made and dropped in device/hip_handles.hpp only"
-    assert _found(DEVICE_MEMORY, {OWNERS, RENDER}) == [], "hipMalloc / hipFree outside DevBuf (device/hip_handles.hpp) and RenderResult (device/render.cpp)"
+    assert _found(DEVICE_MEMORY, {OWNERS}) == [], "hipMalloc / hipFree outside DevBuf and DeviceBlock (device/hip_handles.hpp)"
 
 
 @pytest.mark.timeout(300)
