@@ -39,13 +39,13 @@ struct EvRegions {
 	int32_t nb_face;
 };
 
-// render.hip: the corner keys of the unweld (general bindings with corner lists); cslot[r * nlists + k] = slot of the k-th corner
-// list in face region r's corner slots, -1 where the region does not bind it; table: mask + 1 slots, kNone = empty
+// dedup.hip (UnweldKey): the corner keys of the render build's unweld (general bindings with corner lists); cslot[r * nlists + k] = slot of the k-th corner
+// list in face region r's corner slots, -1 where the region does not bind it; n, mask and table (mask + 1 slots, kNone = empty) are the launcher's, from its DedupPlan
 struct UnweldView {
 	const uint32_t *org, *eface, *corner_attr;
 	const uint16_t *face_reg;
 	const int32_t *cslot;
-	uint32_t ne, nf, nregs, nlists, nb_corner, mask;
+	uint32_t n, nf, nregs, nlists, nb_corner, mask;   // n: corners
 	uint32_t *table;
 };
 // render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]

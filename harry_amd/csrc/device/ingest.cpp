@@ -96,17 +96,17 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 	cx.d_rec[1].ensure(std::max<size_t>((size_t)nv * sv, 16));
 
 	Carve W;   // the working arrays, pieces of d_ingest
-	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64), nwv = (uint32_t)(((uint64_t)nv + 63) / 64);
-	const size_t slots = weld ? unweld_table_slots(nv) : 0;
+	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64);
 	const size_t status_bytes = sizeof(IngestStatus) + 8;   // (+ the number of welded vertices)
 	const size_t w_status = W.reserve(status_bytes);
 	const size_t w_fsum = W.reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = W.reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
-	const size_t w_keys = W.reserve(weld ? (size_t)nv * sv : 0), w_table = W.reserve(slots * 4), w_first = W.reserve(weld ? (size_t)nv * 4 : 0);
-	const size_t w_masks = W.reserve(weld ? (size_t)nwv * 8 : 0), w_counts = W.reserve(weld ? (size_t)nwv * 4 : 0);
-	const size_t w_vstart = W.reserve(weld ? ((size_t)nwv + 1) * 4 : 0), w_remap = W.reserve(weld ? (size_t)nv * 4 : 0);
+	const size_t w_keys = W.reserve(weld ? (size_t)nv * sv : 0);
+	DedupPlan D;   // the weld's numbering of the rows (dedup.hip); D.ids: row -> output vertex
+	if (weld) D.reserve(W, nv);
 	const size_t w_frow = W.reserve(weld ? (size_t)nv * 4 : 0);
 	cx.d_ingest.ensure(W.total);
 	void *wb = cx.d_ingest.p;
+	if (weld) D.bind(W, wb);
 	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
 	uint32_t *d_nout = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
@@ -117,13 +117,11 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 	if (weld) {
 		uint8_t *keys = W.ptr<uint8_t>(wb, w_keys);
 		launch_ingest_pack(st, pv, nv, nullptr, nv, keys);
-		const WeldView u{ keys, (uint32_t)sv, nv, (uint32_t)(slots - 1), W.ptr<uint32_t>(wb, w_table) };
-		HIP_OK(hipMemsetAsync(u.table, 0xff, slots * 4, st));
-		launch_weld_count(st, u, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_counts), W.ptr<uint32_t>(wb, w_vstart));
-		launch_weld_assign(st, nv, W.ptr<const uint32_t>(wb, w_first), W.ptr<const uint64_t>(wb, w_masks), W.ptr<const uint32_t>(wb, w_vstart), W.ptr<uint32_t>(wb, w_remap),
-		                   W.ptr<uint32_t>(wb, w_frow));
-		if (nv) HIP_OK(hipMemcpyAsync(d_nout, W.ptr<const uint32_t>(wb, w_vstart) + nwv, 4, hipMemcpyDeviceToDevice, st));
-		remap = W.ptr<const uint32_t>(wb, w_remap);
+		HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));
+		launch_dedup_count(st, WeldView{ keys, (uint32_t)sv }, D);
+		launch_dedup_assign(st, D, nv, W.ptr<uint32_t>(wb, w_frow));
+		if (nv) HIP_OK(hipMemcpyAsync(d_nout, D.total(), 4, hipMemcpyDeviceToDevice, st));
+		remap = D.ids;
 	} else launch_ingest_pack(st, pv, nv, nullptr, nv, cx.d_rec[1].as<uint8_t>());
 	launch_ingest_org(st, d_indices, idx64, ne, nv, remap, cx.d_org.as<uint32_t>(), status);
 	launch_ingest_pack(st, pf, nf, nullptr, nf, cx.d_rec[0].as<uint8_t>());
@@ -180,7 +178,8 @@ struct RowsIn {
 	int k = 0;                    // 0 pos, 1 tex, 2 nrm: d_remap's entry
 	uint32_t bad_bit = 0;
 	PackCols pack{};
-	size_t keys = 0, table = 0, first = 0, masks = 0, counts = 0, vstart = 0, remap = 0, frow = 0, slots = 0;   // pieces of d_ingest (weld)
+	size_t keys = 0, frow = 0;   // pieces of d_ingest (weld), with the numbering's
+	DedupPlan dedup;
 };
 
 PackCols float_rows(const Context &cx, const hry_dev_rows &r, const char *what)
@@ -275,14 +274,14 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	const size_t w_mfirst = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0), w_mrank = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0);
 	for (int l = 0; l < nl && weld; ++l) {   // every welded list has its own keys and table
 		RowsIn &R = in[l];
-		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
-		R.slots = unweld_table_slots(n);
-		R.keys = W.reserve((size_t)n * R.pack.rec_stride); R.table = W.reserve(R.slots * 4); R.first = W.reserve((size_t)n * 4);
-		R.masks = W.reserve((size_t)nw * 8); R.counts = W.reserve((size_t)nw * 4); R.vstart = W.reserve(((size_t)nw + 1) * 4);
-		R.remap = W.reserve((size_t)n * 4); R.frow = W.reserve((size_t)n * 4);
+		const uint32_t n = R.in->rows;
+		R.keys = W.reserve((size_t)n * R.pack.rec_stride);
+		R.dedup.reserve(W, n);
+		R.frow = W.reserve((size_t)n * 4);
 	}
 	cx.d_ingest.ensure(W.total);
 	void *wb = cx.d_ingest.p;
+	for (int l = 0; l < nl && weld; ++l) in[l].dedup.bind(W, wb);
 	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
 	uint32_t *d_counts = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));   // [k]: records of list k after the weld; [3]: face regions
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
@@ -291,18 +290,16 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	launch_ingest_offsets(st, d_degrees, nf, W.ptr<uint32_t>(wb, w_fsum), W.ptr<uint32_t>(wb, w_fstart), cx.d_foff.as<uint32_t>(), status);
 	for (int l = 0; l < nl; ++l) {
 		RowsIn &R = in[l];
-		const uint32_t n = R.in->rows, nw = (uint32_t)(((uint64_t)n + 63) / 64);
+		const uint32_t n = R.in->rows;
 		if (!weld) { launch_ingest_pack(st, R.pack, n, nullptr, n, cx.d_rec[l].as<uint8_t>()); continue; }
 		uint8_t *keys = W.ptr<uint8_t>(wb, R.keys);
 		launch_ingest_pack(st, R.pack, n, nullptr, n, keys);
-		const WeldView u{ keys, R.pack.rec_stride, n, (uint32_t)(R.slots - 1), W.ptr<uint32_t>(wb, R.table) };
-		HIP_OK(hipMemsetAsync(u.table, 0xff, R.slots * 4, st));
-		launch_weld_count(st, u, W.ptr<uint32_t>(wb, R.first), W.ptr<uint64_t>(wb, R.masks), W.ptr<uint32_t>(wb, R.counts), W.ptr<uint32_t>(wb, R.vstart));
-		launch_weld_assign(st, n, W.ptr<const uint32_t>(wb, R.first), W.ptr<const uint64_t>(wb, R.masks), W.ptr<const uint32_t>(wb, R.vstart), W.ptr<uint32_t>(wb, R.remap),
-		                   W.ptr<uint32_t>(wb, R.frow));
-		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, W.ptr<const uint32_t>(wb, R.vstart) + nw, 4, hipMemcpyDeviceToDevice, st));
+		HIP_OK(hipMemsetAsync(R.dedup.table, 0xff, R.dedup.table_bytes(), st));
+		launch_dedup_count(st, WeldView{ keys, R.pack.rec_stride }, R.dedup);
+		launch_dedup_assign(st, R.dedup, n, W.ptr<uint32_t>(wb, R.frow));
+		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, R.dedup.total(), 4, hipMemcpyDeviceToDevice, st));
 	}
-	auto remap_of = [&](const RowsIn &R) { return weld ? W.ptr<const uint32_t>(wb, R.remap) : nullptr; };
+	auto remap_of = [&](const RowsIn &R) { return weld ? (const uint32_t*)R.dedup.ids : nullptr; };
 	launch_ingest_org(st, pos->indices, idx64, ne, rows0, remap_of(in[0]), cx.d_org.as<uint32_t>(), status);
 	CornerSlots cs{};
 	for (int l = 1; l < nl; ++l) {   // slots are compacted: tex, then nrm, whichever are given
@@ -310,7 +307,7 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	}
 	launch_ingest_corner_attr(st, cs, idx64, ne, cx.d_cattr.as<uint32_t>(), status);
 	HIP_OK(hipMemsetAsync(cx.d_vreg.p, 0, std::max<size_t>((size_t)rows0 * 2, 16), st));   // one vertex region
-	launch_ingest_iota(st, rows0, cx.d_vattr.as<uint32_t>());                                // vertex v owns record v
+	launch_iota(st, rows0, cx.d_vattr.as<uint32_t>());                                // vertex v owns record v
 	if (d_face_material) {
 		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mfirst), 0xff, (size_t)kIngestMaterials * 4, st));
 		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mrank), 0, (size_t)kIngestMaterials * 4, st));
@@ -336,8 +333,8 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 		// ---- welded: the records of the output, gathered from the columns at each one's first row
 		if (weld) launch_ingest_pack(st, R.pack, nout, W.ptr<const uint32_t>(wb, R.frow), n, cx.d_rec[l].as<uint8_t>());
 		if (d_remap && d_remap[R.k] && n) {
-			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], W.ptr<void>(wb, R.remap), (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-			else launch_ingest_iota(st, n, d_remap[R.k]);
+			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], R.dedup.ids, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+			else launch_iota(st, n, d_remap[R.k]);
 		}
 	}
 	const uint32_t nv = m->lists[0].count;

@@ -5,11 +5,11 @@
 //   k_ingest_foff_tri  every face a triangle: face_off[f] = 3f
 //   k_ingest_org       a lane per half-edge: the index, range-checked, through the weld map when welding
 //   k_ingest_pack      a lane per 4-byte word of a list's AoS records: strided columns gathered into the list's layout
-//   k_weld_*           one output vertex per distinct packed record, in first-occurrence order over the input rows
 // and for meshes with corner lists (hry_mesh_from_device_corners):
 //   k_ingest_corner_attr  a lane per word of corner_attr: the corner's row in the slot's list, range-checked, through that list's weld map
-//   k_ingest_iota         vtx_attr[v] = v
 //   k_region_first / k_region_rank / k_ingest_face_region   a material per face -> regions numbered by first occurrence
+// The weld (one output record per distinct packed record, in first-occurrence order over the input rows) is dedup.hip's numbering
+// over a WeldView's keys, the one-block scan of the wave sums its k_scan_counts, vtx_attr[v] = v its k_iota.
 // The checks of the input raise bits of one status word (vector atomics, once per wavefront); the host reads it back once.  Offsets
 // computed from bad degrees are stored but never used for an address: the host refuses the mesh first.
 #include <hip/hip_runtime.h>
@@ -21,12 +21,9 @@ namespace dev {
 
 constexpr uint32_t kNone = 0xffffffffu;
 
-// exclusive scan of n counts by one block (render.hip)
-__global__ void k_scan_counts(const uint32_t *counts, uint32_t n, uint32_t *out);
-
 // ---------------------------------------------------------------------------------------------------------
 // face offsets from uint8 degrees: per wavefront of 64 faces the sum of its degrees (at most 64 x 255, a u32), scanned by
-// k_scan_counts, then the prefix inside the wavefront.  The 64-bit total is summed separately (per block in LDS, then one atomic
+// launch_scan_counts (dedup.hip), then the prefix inside the wavefront.  The 64-bit total is summed separately (per block in LDS, then one atomic
 // per block): the host compares it with n_indices before it trusts any u32 offset, so degrees whose sum passes 2^32 cannot wrap.
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ingest_degrees(const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, IngestStatus *st)
@@ -117,78 +114,6 @@ __global__ __launch_bounds__(256) void k_ingest_pack(PackCols p, uint32_t n, con
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// weld: the key of row r is its packed record (stride bytes at rec + r * stride).  Keys are never stored: a slot of the
-// open-addressing table holds a row, and keys are compared by reading both records.  A slot belongs to the key of the row that
-// claimed it (atomicCAS from EMPTY) for good; atomicMin then leaves the smallest row of that key in it.  So after k_weld_insert every
-// distinct key owns exactly one slot holding its first row -- whatever order the atomics completed in (k_unweld_*, render.hip).
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rec_hash(const uint8_t *a, uint32_t S)
-{
-	uint32_t h = 0x811c9dc5u;   // FNV-1a over the bytes, then murmur3's finaliser
-	for (uint32_t k = 0; k < S; ++k) h = (h ^ a[k]) * 0x01000193u;
-	h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-	return h;
-}
-__device__ __forceinline__ bool same_rec(const uint8_t *a, const uint8_t *b, uint32_t S)
-{
-	for (uint32_t k = 0; k < S; ++k)
-		if (a[k] != b[k]) return false;
-	return true;
-}
-
-__global__ __launch_bounds__(256) void k_weld_insert(WeldView u)
-{
-	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-	if (r >= u.n) return;
-	const uint8_t *a = u.rec + (size_t)r * u.stride;
-	uint32_t s = rec_hash(a, u.stride) & u.mask;
-	for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {   // more slots than rows: an empty one is met
-		uint32_t cur = __hip_atomic_load(&u.table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (cur == kNone) {
-			cur = atomicCAS(&u.table[s], kNone, r);
-			if (cur == kNone) return;
-		}
-		if (cur < u.n && same_rec(a, u.rec + (size_t)cur * u.stride, u.stride)) { atomicMin(&u.table[s], r); return; }
-	}
-}
-
-// per row: the first row of its key; per wavefront of 64 rows: the mask of first rows and their count
-__global__ __launch_bounds__(256) void k_weld_find(WeldView u, uint32_t *first_of, uint64_t *masks, uint32_t *counts)
-{
-	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-	bool first = false;
-	if (r < u.n) {
-		const uint8_t *a = u.rec + (size_t)r * u.stride;
-		uint32_t s = rec_hash(a, u.stride) & u.mask, e = r;
-		for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {
-			const uint32_t cur = u.table[s];
-			if (cur == kNone) break;   // (cannot happen: r itself was inserted)
-			if (cur == r || (cur < u.n && same_rec(a, u.rec + (size_t)cur * u.stride, u.stride))) { e = cur; break; }
-		}
-		first_of[r] = e;
-		first = e == r;
-	}
-	const uint64_t b = __ballot(first);
-	if ((threadIdx.x & 63) == 0 && (uint64_t)(r >> 6) < ((uint64_t)u.n + 63) / 64) {
-		masks[r >> 6] = b;
-		counts[r >> 6] = (uint32_t)__popcll(b);
-	}
-}
-
-// remap[r] = output vertex of row r (rank of its first row among the first rows); first_row[id] = the row that defines vertex id
-__global__ __launch_bounds__(256) void k_weld_assign(uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
-                                                     uint32_t *remap, uint32_t *first_row)
-{
-	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-	if (r >= n) return;
-	const uint32_t e = first_of[r];
-	if (e >= n) { remap[r] = 0; return; }
-	const uint32_t id = wave_start[e >> 6] + (uint32_t)__popcll(masks[e >> 6] & ((1ull << (e & 63)) - 1));
-	remap[r] = id;
-	if (e == r && id < n) first_row[id] = r;
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // corner_attr: word 2c + s is corner c's record in the list of slot s -- its index in that list's buffer, through the list's weld
 // map when welding; 0 in an unused slot.  An index outside [0, rows) raises the list's bit (one atomic per wavefront) and stores 0:
 // nothing is read or written at it.
@@ -212,12 +137,6 @@ __global__ __launch_bounds__(256) void k_ingest_corner_attr(CornerSlots cs, uint
 		const uint64_t any = b0 | b1;
 		if (any && (threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)any) - 1) atomicOr(&st->err, (b0 ? cs.bad[0] : 0u) | (b1 ? cs.bad[1] : 0u));
 	}
-}
-
-__global__ __launch_bounds__(256) void k_ingest_iota(uint32_t n, uint32_t *out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) out[i] = i;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -273,10 +192,6 @@ __global__ __launch_bounds__(256) void k_ingest_face_region(const uint16_t *mat,
 // ---- launchers
 static inline unsigned grid_for(uint64_t n, unsigned per) { const uint64_t b = (n + per - 1) / per; return (unsigned)(b < (1u << 20) ? b : (1u << 20)); }
 
-void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out)
-{
-	hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, counts, n, out);
-}
 void launch_ingest_offsets(hipStream_t st, const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, uint32_t *wave_start, uint32_t *foff, IngestStatus *status)
 {
 	if (!deg) {
@@ -299,27 +214,11 @@ void launch_ingest_pack(hipStream_t st, const PackCols &p, uint32_t n, const uin
 {
 	if (n && p.rec_stride) hipLaunchKernelGGL(k_ingest_pack, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, p, n, rows, nsrc, out);
 }
-void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start)
-{
-	if (!u.n) return;
-	const unsigned nb = (u.n + 255) / 256;
-	hipLaunchKernelGGL(k_weld_insert, dim3(nb), dim3(256), 0, st, u);
-	hipLaunchKernelGGL(k_weld_find, dim3(nb), dim3(256), 0, st, u, first_of, masks, counts);
-	launch_scan_counts(st, counts, (u.n + 63) / 64, wave_start);
-}
-void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row)
-{
-	if (n) hipLaunchKernelGGL(k_weld_assign, dim3((n + 255) / 256), dim3(256), 0, st, n, first_of, masks, wave_start, remap, first_row);
-}
 void launch_ingest_corner_attr(hipStream_t st, const CornerSlots &cs, bool idx64, uint32_t ne, uint32_t *corner_attr, IngestStatus *status)
 {
 	if (!ne) return;
 	if (idx64) hipLaunchKernelGGL(k_ingest_corner_attr<int64_t>, dim3(grid_for(2ull * ne, 256)), dim3(256), 0, st, cs, ne, corner_attr, status);
 	else hipLaunchKernelGGL(k_ingest_corner_attr<uint32_t>, dim3(grid_for(2ull * ne, 256)), dim3(256), 0, st, cs, ne, corner_attr, status);
-}
-void launch_ingest_iota(hipStream_t st, uint32_t n, uint32_t *out)
-{
-	if (n) hipLaunchKernelGGL(k_ingest_iota, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, n, out);
 }
 void launch_ingest_regions(hipStream_t st, const uint16_t *mat, uint32_t nf, uint32_t *first, uint32_t *rank, uint32_t *n_regions, uint16_t *face_reg,
                            IngestStatus *status)

@@ -8,6 +8,7 @@
 #include "dev_types.hpp"
 
 namespace hry {
+struct Carve;   // hip_handles.hpp
 namespace dev {
 
 // every component of a list in two launches; out: 24 bytes per component { u64 min, u64 max, u32 min_at, u32 max_at }
@@ -149,15 +150,34 @@ void launch_list_kinds(hipStream_t st, int kind, uint32_t list_count, const Conn
                        uint32_t *counts, uint32_t *err);
 void launch_region_symbols(hipStream_t st, int kind, const ConnView &cv, const GenView &gv, const uint32_t *order, uint32_t n, uint8_t *out);
 
+// first-occurrence numbering (dedup.hip): item i gets the id of its key, ids numbered by the key's first item.  The keys of the
+// unweld are an UnweldView's corners (dev_types.hpp), the weld's the packed records of a WeldView
+struct WeldView { const uint8_t *rec; uint32_t stride, n, mask; uint32_t *table; };
+// the working arrays of one numbering of n items: reserve() its pieces in a Carve while sizing, bind() after the allocation.
+// table: mask + 1 slots (a power of two >= 2 n), filled with 0xff by the caller before launch_dedup_count; first_of / ids[n],
+// masks / counts[nw], wave_start[nw + 1]; *total(): the number of distinct keys, on the device
+struct DedupPlan {
+	uint32_t n = 0, nw = 0, mask = 0;
+	uint32_t *table = nullptr, *first_of = nullptr, *counts = nullptr, *wave_start = nullptr, *ids = nullptr;
+	uint64_t *masks = nullptr;
+	size_t at_table = 0, at_first_of = 0, at_masks = 0, at_counts = 0, at_wave_start = 0, at_ids = 0;   // pieces of the Carve
+	size_t table_bytes() const { return ((size_t)mask + 1) * 4; }
+	const uint32_t *total() const { return wave_start + nw; }
+	void reserve(Carve &W, uint32_t items);
+	void bind(const Carve &W, void *base);
+};
+// insert, find, scan over the keys of u; the launcher takes u's table, mask and item count from the plan.  Fills first_of, masks,
+// counts, wave_start
+void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p);
+void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p);
+// p.ids[i] = id of item i; per id below nout: first_item[id] = its first item, via_out[id] = via[that item] (via == nullptr: none)
+void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via = nullptr, uint32_t *via_out = nullptr);
+void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out);   // k_scan_counts (one block): out[n + 1], out[n] = total
+void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
+
 // render-ready buffers (render.hip; driver: render.cpp).  launch_fan: tri_face[T] and indices[3T] of the fan triangulation,
 // corners mapped through vmap (org, or the unweld's corner -> output vertex map)
 void launch_fan(hipStream_t st, const uint32_t *foff, uint32_t nf, uint64_t ntri, const uint32_t *vmap, uint32_t ne, uint32_t *tri_face, uint32_t *indices);
-void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);
-size_t unweld_table_slots(uint32_t ne);   // a power of two >= 2 ne
-// u.table filled with 0xff first; first_of[ne], masks / counts[(ne + 63) / 64], wave_start[(ne + 63) / 64 + 1] (last: the output vertices)
-void launch_unweld_count(hipStream_t st, const UnweldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start);
-void launch_unweld_assign(hipStream_t st, const uint32_t *org, uint32_t ne, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
-                          uint32_t nout, uint32_t *cmap, uint32_t *vertex_source, uint32_t *corner_source);
 void launch_rows_of(hipStream_t st, const RowsView &v, uint32_t rows, uint32_t *idx);
 // plan: every component of the list (dst_bits 0; src_bits = its quantisation), idx == nullptr: row u is record u
 // a decoded segment into the whole numbering (render.cpp: place_segment): records (stride bytes each) of nl local vertices / faces,
@@ -196,16 +216,11 @@ struct PackCols {
 	uint8_t comp_of[8 * kMaxComp], byte_of[8 * kMaxComp];
 	uint32_t rec_stride;
 };
-struct WeldView { const uint8_t *rec; uint32_t stride, n, mask; uint32_t *table; };   // table: mask + 1 slots, filled with 0xff first
-void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out);   // k_scan_counts: out[n + 1], out[n] = total
 // face_off[nf + 1] into foff; deg == nullptr: every face a triangle.  wave_sums / wave_start: (nf + 63) / 64 (+ 1) words
 void launch_ingest_offsets(hipStream_t st, const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, uint32_t *wave_start, uint32_t *foff, IngestStatus *status);
 void launch_ingest_org(hipStream_t st, const void *idx, bool idx64, uint32_t ne, uint32_t nv, const uint32_t *remap, uint32_t *org, IngestStatus *status);
 // n records of p.rec_stride bytes into out; record r from row rows[r] (rows == nullptr: row r) of columns with nsrc rows
 void launch_ingest_pack(hipStream_t st, const PackCols &p, uint32_t n, const uint32_t *rows, uint32_t nsrc, uint8_t *out);
-// first_of[n], masks / counts[(n + 63) / 64], wave_start[(n + 63) / 64 + 1] (last: the output vertices)
-void launch_weld_count(hipStream_t st, const WeldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start);
-void launch_weld_assign(hipStream_t st, uint32_t n, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start, uint32_t *remap, uint32_t *first_row);
 // ... with corner lists (hry_mesh_from_device_corners): further bits of IngestStatus::err
 constexpr uint32_t kIngestBadTexIndex = 4, kIngestBadNormalIndex = 8, kIngestManyRegions = 16;
 constexpr uint32_t kIngestMaterials = 65536, kIngestMaxRegions = 128;
@@ -213,7 +228,6 @@ constexpr uint32_t kIngestMaterials = 65536, kIngestMaxRegions = 128;
 // the list (or nullptr) and the bit an index outside [0, rows) raises
 struct CornerSlots { const void *idx[2]; const uint32_t *remap[2]; uint32_t rows[2], bad[2]; };
 void launch_ingest_corner_attr(hipStream_t st, const CornerSlots &cs, bool idx64, uint32_t ne, uint32_t *corner_attr, IngestStatus *status);
-void launch_ingest_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
 // face regions from a material per face: first[kIngestMaterials] filled with 0xff and rank[kIngestMaterials] zeroed before; the
 // number of distinct materials goes to *n_regions, more than kIngestMaxRegions raises kIngestManyRegions
 void launch_ingest_regions(hipStream_t st, const uint16_t *mat, uint32_t nf, uint32_t *first, uint32_t *rank, uint32_t *n_regions, uint16_t *face_reg,

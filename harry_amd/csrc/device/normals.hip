@@ -6,7 +6,7 @@
 //                   buffer (24 B per face: N_f in area mode, N_f / |N_f| in angle mode, zeros for a face that contributes nothing)
 //                   and, where asked for, the unit normal as floats
 //   k_nrm_count     one counter per vertex: its corners (integer atomics)
-//   k_scan_*        exclusive scan of the counters (twins.hip)
+//   k_scan_*        exclusive scan of the counters (twins.hip, through its launch_excl_scan)
 //   k_nrm_scatter   corners into their vertex's segment, in any order
 //   k_nrm_vertices  a lane per vertex: sorts its segment by corner id (insertion sort: a handful of entries), sums the corners'
 //                   contributions in that order, normalises.  Segments of more than kNrmSegMax corners are listed for k_nrm_hubs

@@ -2,7 +2,7 @@
 // inverses, and the kernel that moves a caller's rows through a map.  Integer work only, wave64, a lane per output word.
 //   k_order_vertex   vertex[org[order_v[j]]] = j, vertex_inv[j] = the vertex                  (what k_rank computes, with its inverse)
 //   k_order_face     face[face_of(order_f[j])] = j, face_inv[j] = the face, and the face's degree in coding order (mixed degrees)
-//   k_scan_*         (twins.hip) exclusive scan of those degrees: where every decoded face begins.  Uniform degree: j * degree
+//   k_scan_*         (twins.hip: launch_excl_scan, from order.cpp) exclusive scan of those degrees: where every decoded face begins.  Uniform degree: j * degree
 //   k_order_corner   the decoder makes the half-edge a face is entered through the face's first (cbm/decoder.h:75-77 for a
 //                    component's first face, :162-164 for the rest, where e0 is the twin of the gate) and keeps the cyclic order: the
 //                    corner k places behind order_f[j] round source face f becomes decoded half-edge doff[j] + k

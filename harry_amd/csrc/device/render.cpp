@@ -143,11 +143,9 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	const size_t w_fattr = W.reserve(tables ? b.face_attr.size() * 4 : 0), w_vattr = W.reserve(tables ? b.vtx_attr.size() * 4 : 0);
 	const size_t w_cattr = W.reserve(tables ? b.corner_attr.size() * 4 : 0);
 	const size_t w_small = W.reserve(small.size() * 4);
-	const uint32_t nw = (ne + 63) / 64;
-	const size_t slots = unweld ? unweld_table_slots(ne) : 0;
-	const size_t w_eface = W.reserve(unweld ? (size_t)ne * 4 : 0), w_table = W.reserve(slots * 4), w_first = W.reserve(unweld ? (size_t)ne * 4 : 0);
-	const size_t w_masks = W.reserve(unweld ? (size_t)nw * 8 : 0), w_counts = W.reserve(unweld ? (size_t)nw * 4 : 0);
-	const size_t w_wstart = W.reserve(unweld ? ((size_t)nw + 1) * 4 : 0), w_cmap = W.reserve(unweld ? (size_t)ne * 4 : 0);
+	const size_t w_eface = W.reserve(unweld ? (size_t)ne * 4 : 0);
+	DedupPlan D;   // the unweld's numbering of the corners (dedup.hip); D.ids: corner -> output vertex
+	if (unweld) D.reserve(W, ne);
 	const size_t w_idx = W.reserve(general ? (size_t)std::max(std::max(nf, nv), ne) * 4 : 0);
 	// normals (normals.hip): N_f per face; per vertex its corners (counters, cursors, segment starts, the scan's sums, the segments,
 	// the list of hubs); a corner -> face table for mixed degrees (the unweld's where there is one); unwelded meshes: the position
@@ -164,6 +162,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	const size_t w_npos = W.reserve(want_n && unweld ? (size_t)nv * pos_w * 4 : 0), w_nvn = W.reserve(want_vn && unweld ? (size_t)nv * 12 : 0);
 	cx.d_render.ensure(W.total);
 	void *wb = cx.d_render.p;
+	if (unweld) D.bind(W, wb);
 
 	hipStream_t st = cx.stream;
 	uint64_t up = 0;
@@ -211,17 +210,16 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	UnweldView u{};
 	if (unweld && ne) {
 		u.org = org; u.eface = eface; u.corner_attr = cattr; u.face_reg = freg; u.cslot = d_small + cslot_at;
-		u.ne = ne; u.nf = nf; u.nregs = (uint32_t)b.nregs_face(); u.nlists = ncl; u.nb_corner = (uint32_t)b.nb_corner;
-		u.mask = (uint32_t)(slots - 1); u.table = W.ptr<uint32_t>(wb, w_table);
-		HIP_OK(hipMemsetAsync(u.table, 0xff, slots * 4, st));
+		u.nf = nf; u.nregs = (uint32_t)b.nregs_face(); u.nlists = ncl; u.nb_corner = (uint32_t)b.nb_corner;
+		HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));   // (launch_dedup_count gives u the plan's table, mask and count)
 	}
 	HIP_OK(hipEventRecord(ev[0], st));
 	if (unweld && ne) {
 		launch_edge_faces(st, foff, nf, eface);
-		launch_unweld_count(st, u, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_counts), W.ptr<uint32_t>(wb, w_wstart));
+		launch_dedup_count(st, u, D);
 	}
 	HIP_OK(hipEventRecord(ev[1], st));
-	if (unweld && ne) HIP_OK(hipMemcpyAsync(&nout, W.ptr<uint32_t>(wb, w_wstart) + nw, 4, hipMemcpyDeviceToHost, st));
+	if (unweld && ne) HIP_OK(hipMemcpyAsync(&nout, D.total(), 4, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
 	if (nout > ne && unweld) throw Error(HRY_E_INTERNAL, "unweld: more output vertices than corners");
 
@@ -252,10 +250,9 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	}
 	HIP_OK(hipEventRecord(ev[2], st));
 	uint32_t *vsrc = dst("vertex_source");
-	if (unweld && ne) launch_unweld_assign(st, org, ne, W.ptr<uint32_t>(wb, w_first), W.ptr<uint64_t>(wb, w_masks), W.ptr<uint32_t>(wb, w_wstart), nout,
-	                                 W.ptr<uint32_t>(wb, w_cmap), vsrc, dst("corner_source"));
+	if (unweld && ne) launch_dedup_assign(st, D, nout, dst("corner_source"), org, vsrc);   // vertex_source = org of the first corner
 	else if (!unweld) launch_iota(st, nv, vsrc);
-	launch_fan(st, foff, nf, ntri, unweld ? W.ptr<uint32_t>(wb, w_cmap) : org, ne, dst("tri_face"), dst("indices"));
+	launch_fan(st, foff, nf, ntri, unweld ? D.ids : org, ne, dst("tri_face"), dst("indices"));
 	uint32_t *idx = W.ptr<uint32_t>(wb, w_idx);
 	for (size_t l = 0; l < nl; ++l) {
 		const AttrList &L = m.lists[l];

@@ -2,9 +2,11 @@
 // kernels, wave64, one element per lane and consecutive lanes on consecutive output words (coalesced stores):
 //   k_tri_face       fan triangulation, a face per lane: the source face of each of its deg - 2 triangles
 //   k_fan_indices    a lane per index WORD (3 per triangle): corner c0 / c(k+1) / c(k+2) of its triangle, through the vertex map
-//   k_unweld_*       general bindings with corner lists: one output vertex per distinct corner key, in first-occurrence order
 //   k_rows_of        the record every output row names in one list (general bindings)
 //   k_render_gather  a lane per f32 of a list's output: the component's value, dequantised (dequant.hpp), as float
+//   k_place_*        a decoded segment of a sharded container into the whole mesh's numbering
+// The unweld of general bindings with corner lists (one output vertex per distinct corner key) is dedup.hip's numbering over an
+// UnweldView's keys; the identity vertex_source is its k_iota.
 #include <hip/hip_runtime.h>
 
 #include "codec_math.hpp"
@@ -52,118 +54,6 @@ __global__ __launch_bounds__(256) void k_fan_indices(const uint32_t *foff, uint3
 		}
 		out[w] = v;
 	}
-}
-
-__global__ __launch_bounds__(256) void k_iota(uint32_t n, uint32_t *out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) out[i] = i;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// unweld: the key of corner c is (org[c], then per corner-target list in list order the record c names, or kNone where the
-// region of c's face does not bind the list).  Keys are never stored: a slot of the open-addressing table holds a corner, and
-// keys are compared by deriving both again.  A slot belongs to the key of the corner that claimed it (atomicCAS from EMPTY) for
-// good; atomicMin then leaves the smallest corner of that key in it.  So after k_unweld_insert every distinct key owns exactly one
-// slot holding its first corner -- whatever order the atomics completed in.
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t region_of(const UnweldView &u, uint32_t c)
-{
-	const uint32_t f = u.eface[c];
-	return f < u.nf ? u.face_reg[f] : kNone;
-}
-__device__ __forceinline__ uint32_t key_part(const UnweldView &u, uint32_t c, uint32_t r, uint32_t i)
-{
-	if (i == 0) return u.org[c];
-	const int32_t s = r < u.nregs ? u.cslot[(size_t)r * u.nlists + (i - 1)] : -1;
-	return s < 0 ? kNone : u.corner_attr[(size_t)c * u.nb_corner + (uint32_t)s];
-}
-__device__ __forceinline__ uint32_t key_hash(const UnweldView &u, uint32_t c, uint32_t r)
-{
-	uint32_t h = 0x9e3779b9u;
-	for (uint32_t i = 0; i <= u.nlists; ++i) {   // murmur3's finaliser over the running value
-		h ^= key_part(u, c, r, i) + 0x7f4a7c15u + (h << 6) + (h >> 2);
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-	}
-	return h;
-}
-__device__ __forceinline__ bool same_key(const UnweldView &u, uint32_t c, uint32_t rc, uint32_t e)
-{
-	const uint32_t re = region_of(u, e);
-	for (uint32_t i = 0; i <= u.nlists; ++i)
-		if (key_part(u, c, rc, i) != key_part(u, e, re, i)) return false;
-	return true;
-}
-
-__global__ __launch_bounds__(256) void k_unweld_insert(UnweldView u)
-{
-	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= u.ne) return;
-	const uint32_t r = region_of(u, c);
-	uint32_t s = key_hash(u, c, r) & u.mask;
-	for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {   // the table has more slots than corners: an empty one is met
-		uint32_t cur = __hip_atomic_load(&u.table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (cur == kNone) {
-			cur = atomicCAS(&u.table[s], kNone, c);
-			if (cur == kNone) return;
-		}
-		if (same_key(u, c, r, cur)) { atomicMin(&u.table[s], c); return; }
-	}
-}
-
-// per corner: the first corner of its key; per wavefront of 64 corners: the mask of first corners and their count
-__global__ __launch_bounds__(256) void k_unweld_find(UnweldView u, uint32_t *first_of, uint64_t *masks, uint32_t *counts)
-{
-	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-	bool first = false;
-	if (c < u.ne) {
-		const uint32_t r = region_of(u, c);
-		uint32_t s = key_hash(u, c, r) & u.mask, e = c;
-		for (uint32_t probe = 0; probe <= u.mask; ++probe, s = (s + 1) & u.mask) {
-			const uint32_t cur = u.table[s];
-			if (cur == kNone) break;   // (cannot happen: c itself was inserted)
-			if (cur == c || same_key(u, c, r, cur)) { e = cur; break; }
-		}
-		first_of[c] = e;
-		first = e == c;
-	}
-	const uint64_t b = __ballot(first);
-	if ((threadIdx.x & 63) == 0 && (uint64_t)(c >> 6) < ((uint64_t)u.ne + 63) / 64) {
-		masks[c >> 6] = b;
-		counts[c >> 6] = (uint32_t)__popcll(b);
-	}
-}
-
-// exclusive scan of n counts by one block (out: n + 1 entries, out[n] = total)
-__global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t *counts, uint32_t n, uint32_t *out)
-{
-	__shared__ uint32_t part[1024];
-	const uint32_t per = (n + 1023) / 1024, b = threadIdx.x * per, e = min(n, b + per);
-	uint32_t sum = 0;
-	for (uint32_t i = b; i < e; ++i) sum += counts[i];
-	part[threadIdx.x] = sum;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024; d <<= 1) {   // Hillis-Steele over the threads' sums
-		const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += add;
-		__syncthreads();
-	}
-	uint32_t run = part[threadIdx.x] - sum;
-	for (uint32_t i = b; i < e; ++i) { out[i] = run; run += counts[i]; }
-	if (threadIdx.x == 1023) out[n] = part[1023];
-}
-
-__global__ __launch_bounds__(256) void k_unweld_assign(const uint32_t *org, uint32_t ne, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
-                                                       uint32_t nout, uint32_t *cmap, uint32_t *vertex_source, uint32_t *corner_source)
-{
-	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= ne) return;
-	const uint32_t e = first_of[c];
-	if (e >= ne) { cmap[c] = 0; return; }
-	const uint32_t id = wave_start[e >> 6] + (uint32_t)__popcll(masks[e >> 6] & ((1ull << (e & 63)) - 1));
-	cmap[c] = id;
-	if (e == c && id < nout) { vertex_source[id] = org[c]; corner_source[id] = c; }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -286,29 +176,6 @@ void launch_fan(hipStream_t st, const uint32_t *foff, uint32_t nf, uint64_t ntri
 	if (!nf || !ntri) return;
 	hipLaunchKernelGGL(k_tri_face, dim3((nf + 255) / 256), dim3(256), 0, st, foff, nf, ntri, tri_face);
 	hipLaunchKernelGGL(k_fan_indices, dim3(grid_for(3 * ntri, 256)), dim3(256), 0, st, foff, nf, (const uint32_t*)tri_face, vmap, ne, 3 * ntri, indices);
-}
-void launch_iota(hipStream_t st, uint32_t n, uint32_t *out)
-{
-	if (n) hipLaunchKernelGGL(k_iota, dim3((n + 255) / 256), dim3(256), 0, st, n, out);
-}
-size_t unweld_table_slots(uint32_t ne)
-{
-	size_t s = 64;
-	while (s < 2 * (size_t)ne) s <<= 1;
-	return s;
-}
-void launch_unweld_count(hipStream_t st, const UnweldView &u, uint32_t *first_of, uint64_t *masks, uint32_t *counts, uint32_t *wave_start)
-{
-	if (!u.ne) return;
-	const unsigned nb = (u.ne + 255) / 256;
-	hipLaunchKernelGGL(k_unweld_insert, dim3(nb), dim3(256), 0, st, u);
-	hipLaunchKernelGGL(k_unweld_find, dim3(nb), dim3(256), 0, st, u, first_of, masks, counts);
-	hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, (u.ne + 63) / 64, wave_start);
-}
-void launch_unweld_assign(hipStream_t st, const uint32_t *org, uint32_t ne, const uint32_t *first_of, const uint64_t *masks, const uint32_t *wave_start,
-                          uint32_t nout, uint32_t *cmap, uint32_t *vertex_source, uint32_t *corner_source)
-{
-	if (ne) hipLaunchKernelGGL(k_unweld_assign, dim3((ne + 255) / 256), dim3(256), 0, st, org, ne, first_of, masks, wave_start, nout, cmap, vertex_source, corner_source);
 }
 void launch_rows_of(hipStream_t st, const RowsView &v, uint32_t rows, uint32_t *idx)
 {

@@ -3,7 +3,7 @@
 // otherwise becomes pending itself -- unless an (a, b) is pending already, in which case it stays unmatched for good
 // (conn.h:201-214).  Only half-edges over the same undirected edge interact, in the order of their indices, so:
 //   k_twin_count    one counter per vertex: half-edges whose smaller endpoint it is          (atomics, 4 B per half-edge)
-//   k_scan_*        exclusive scan of the counters
+//   k_scan_*        exclusive scan of the counters, in three launches (launch_excl_scan: also the components below, normals.hip, order.cpp)
 //   k_twin_scatter  (larger endpoint, half-edge) pairs into the segment of the smaller endpoint (any order)
 //   k_twin_match    one thread per vertex: sorts its segment (a handful of entries) by (larger endpoint, half-edge) and
 //                   replays the reference's rule over every run of equal larger endpoints
@@ -133,6 +133,17 @@ __global__ __launch_bounds__(256) void k_twin_match(ConnView cv, uint32_t nv, co
 
 static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
+// the one launcher of k_scan_*: out[n + 1], out[n] = total (no counters: out[0] = 0); sums: scan_sums_words(n) words of scratch
+size_t scan_sums_words(uint32_t n) { return (size_t)blocks_for(n, kScanBlock) + 2; }
+void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out)
+{
+	if (!n) { (void)hipMemsetAsync(out, 0, 4, st); return; }
+	const unsigned nb = blocks_for(n, kScanBlock);
+	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, in, n, sums);
+	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
+	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, in, n, (const uint32_t*)sums, out);
+}
+
 // ws: (2 * nv + 2 + blocks) * 4 bytes of counters + ne * 8 bytes of entries (8-byte aligned first) + the overflow list
 size_t twin_workspace_bytes(uint32_t nv, uint32_t ne) { return (size_t)ne * 8 + ((size_t)2 * nv + 2 + blocks_for(nv, kScanBlock) + 2 + kTwinOverMax + 1) * 4; }
 uint32_t twin_overflow_capacity() { return kTwinOverMax; }
@@ -145,25 +156,12 @@ void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twi
 	uint32_t *over = sums + blocks_for(nv, kScanBlock) + 2;
 	(void)hipMemsetAsync(over, 0, 4, st);
 	*over_out = over;
-	const unsigned nb = blocks_for(nv, kScanBlock);
 	(void)hipMemsetAsync(count, 0, (size_t)nv * 4, st);
 	hipLaunchKernelGGL(k_twin_count, dim3(blocks_for(cv.ne, 256)), dim3(256), 0, st, cv, twin, count);
-	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, count, nv, sums);
-	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
-	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, count, nv, sums, start);
+	launch_excl_scan(st, count, nv, sums, start);
 	(void)hipMemsetAsync(count, 0, (size_t)nv * 4, st);   // reused as the fill cursors
 	hipLaunchKernelGGL(k_twin_scatter, dim3(blocks_for(cv.ne, 256)), dim3(256), 0, st, cv, start, count, ent);
 	hipLaunchKernelGGL(k_twin_match, dim3(blocks_for(nv, 256)), dim3(256), 0, st, cv, nv, start, ent, twin, over);
-}
-
-size_t scan_sums_words(uint32_t n) { return (size_t)blocks_for(n, kScanBlock) + 2; }
-void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out)
-{
-	if (!n) { (void)hipMemsetAsync(out, 0, 4, st); return; }
-	const unsigned nb = blocks_for(n, kScanBlock);
-	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, in, n, sums);
-	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
-	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, in, n, (const uint32_t*)sums, out);
 }
 
 
@@ -471,16 +469,13 @@ void launch_components_label(hipStream_t st, const ConnView &cv, const Component
 {
 	uint32_t *label = w.label, *flag = w.flag, *num = w.num, *sums = w.sums;
 	if (!cv.nf) return;
-	const unsigned nb = blocks_for(cv.nf, kScanBlock);
 	if (cv.ne) {
 		hipLaunchKernelGGL(k_cc_hook_local, dim3(blocks_for(cv.nf, kHookFaces)), dim3(kHookThreads), 0, st, cv, label);
 		hipLaunchKernelGGL(k_cc_hook, dim3(blocks_for(cv.nf, 256)), dim3(256), 0, st, cv, label);
 	} else hipLaunchKernelGGL(k_cc_init, dim3(blocks_for(cv.nf, 256)), dim3(256), 0, st, label, cv.nf);
 	hipLaunchKernelGGL(k_cc_flatten, dim3(blocks_for(cv.nf, 256)), dim3(256), 0, st, label, cv.nf);
 	hipLaunchKernelGGL(k_cc_roots, dim3(blocks_for(cv.nf, 256)), dim3(256), 0, st, label, cv.nf, flag);
-	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, flag, cv.nf, sums);
-	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
-	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, flag, cv.nf, sums, num);
+	launch_excl_scan(st, flag, cv.nf, sums, num);
 }
 // stage 2: per component (numbered in face order of the roots; tables zeroed / set to their neutral values by the caller)
 void launch_components_faces(hipStream_t st, const ConnView &cv, uint32_t *label, const uint32_t *num, const uint32_t *spans, uint32_t nspans,

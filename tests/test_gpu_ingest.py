@@ -181,6 +181,23 @@ def test_weld_signed_zero_and_nan(cx):
     assert remap.cpu().tolist() == [0, 1, 2, 3, 2, 0]
 
 
+# The edges of the shared first-occurrence numbering (dedup.hip): fewer rows than a wavefront, one row either side of a wavefront
+# and of a block of 256, and 65 601 rows -- 1026 wavefront counts, so every thread of the one-block scan takes more than one.
+# "distinct": every probe claims a slot.  "tail_equal": rows 0, 1, 2 distinct and every later row equal to row 2, so n - 2 lanes
+# meet in one slot (the losers of the compare-and-swap, then atomicMin); the rows past 2 are unreferenced, the face is (0, 1, 2).
+@pytest.mark.parametrize("pattern", ["distinct", "tail_equal"])
+@pytest.mark.parametrize("n", [3, 63, 64, 65, 256, 257, 65601])
+def test_weld_numbering_edges(cx, n, pattern):
+    x = np.arange(n, dtype=np.float32)
+    if pattern == "tail_equal":
+        x[3:] = x[2]
+    want_remap, first = ir.weld(ir.packed_records([x]))
+    assert len(first) == (n if pattern == "distinct" else 3)
+    mesh, remap = cx.mesh_from_tensors(_t(np.array([[0, 1, 2]], np.int32)), [("x", _t(x))], weld=True, return_remap=True)
+    assert mesh.nv == len(first)
+    assert np.array_equal(remap.cpu().numpy().view(np.uint32), want_remap)
+
+
 # ---- 3. round trip with render
 def test_round_trip_with_render(cx):
     m = mg.torus(26, 28)

@@ -342,6 +342,18 @@ def test_unweld_scenes(cx, tmp_path, name):
     check_unweld(cx, cx.read_hry(cx.write_hry(_scene_mesh(tmp_path, sc), profile=hc.PROFILE_CHUNKED)))
 
 
+# corner counts at the edges of a wavefront of 64 (dedup.hip: one ballot per wavefront): 54 below one, 72 just above, 192 on a
+# multiple; "flat": every corner of a face has a key of its own, "smooth_atlas": corners share keys
+@pytest.mark.parametrize("kw", [dict(normals="flat"), dict(normals="smooth", tex="atlas")], ids=["flat", "smooth_atlas"])
+@pytest.mark.parametrize("nu,nv,corners", [(3, 3, 54), (3, 4, 72), (4, 8, 192)])
+def test_unweld_wavefront_edges(cx, tmp_path, nu, nv, corners, kw):
+    mesh = _scene_mesh(tmp_path, og.scene(mg.torus(nu, nv), **kw))
+    assert mesh.ne == corners and rr.unwelded(mesh)
+    cmap, vsrc, csrc = rr.vertex_map(mesh)   # the reference handles the size, on the CPU, before the GPU is asked
+    assert len(cmap) == corners and len(vsrc) == len(csrc) == len(np.unique(rr.corner_keys(mesh), axis=0))
+    check_unweld(cx, mesh)
+
+
 # ---- 7. scale
 def test_scale_configs1(cx):
     ply = mg.torus(708, 708, seed=2, sigma=1e-4).to_ply()
