@@ -19,21 +19,10 @@
 #include "codec_math.hpp"
 #include "dev_types.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace hry {
 namespace dev {
-
-__device__ __forceinline__ uint32_t wscan_excl(uint32_t v, uint32_t &total)
-{
-	uint32_t inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		uint32_t o = __shfl_up(inc, d, 64);
-		if ((int)(threadIdx.x & 63) >= d) inc += o;
-	}
-	total = __shfl(inc, 63, 64);
-	return inc - v;
-}
 
 constexpr int kWin = 72;   // LDS accumulation window in 32-bit words (64 symbols x <= 31 shifts = 62 words + 2)
 
@@ -57,7 +46,7 @@ __global__ __launch_bounds__(64) void k_chunk_encode(const StreamJob *jobs, cons
 	{
 		const uint32_t *st = inits + (size_t)jb.init * 256 + 4 * lane;
 		uint32_t a = st[0], b = st[1], c = st[2], d = st[3], tot;
-		uint32_t ex = wscan_excl(a + b + c + d, tot);
+		uint32_t ex = wave_excl_scan(a + b + c + d, tot);
 		cnt[4 * lane] = a; cnt[4 * lane + 1] = b; cnt[4 * lane + 2] = c; cnt[4 * lane + 3] = d;
 		cum[4 * lane] = ex; cum[4 * lane + 1] = ex + a; cum[4 * lane + 2] = ex + a + b; cum[4 * lane + 3] = ex + a + b + c;
 		if (lane == 0) { cnt[256] = 0; cum[256] = 0; }
@@ -128,7 +117,7 @@ __global__ __launch_bounds__(64) void k_chunk_encode(const StreamJob *jobs, cons
 		}
 		// adaptive update of the tables by the whole batch (stat_adaptive.h:77-82)
 		uint32_t a0 = bh[4 * lane], a1 = bh[4 * lane + 1], a2 = bh[4 * lane + 2], a3 = bh[4 * lane + 3], tot;
-		uint32_t ex = wscan_excl(a0 + a1 + a2 + a3, tot);
+		uint32_t ex = wave_excl_scan(a0 + a1 + a2 + a3, tot);
 		cnt[4 * lane] += a0; cnt[4 * lane + 1] += a1; cnt[4 * lane + 2] += a2; cnt[4 * lane + 3] += a3;
 		cum[4 * lane] += ex; cum[4 * lane + 1] += ex + a0; cum[4 * lane + 2] += ex + a0 + a1; cum[4 * lane + 3] += ex + a0 + a1 + a2;
 		__syncthreads();
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(64) void k_chunk_model(const StreamJob *jobs, const
 	{
 		const uint32_t *st = inits + (size_t)jb.init * 256 + 4 * lane;
 		uint32_t a = st[0], b = st[1], c = st[2], d = st[3], tot;
-		uint32_t ex = wscan_excl(a + b + c + d, tot);
+		uint32_t ex = wave_excl_scan(a + b + c + d, tot);
 		cnt[4 * lane] = a; cnt[4 * lane + 1] = b; cnt[4 * lane + 2] = c; cnt[4 * lane + 3] = d;
 		cum[4 * lane] = ex; cum[4 * lane + 1] = ex + a; cum[4 * lane + 2] = ex + a + b; cum[4 * lane + 3] = ex + a + b + c;
 		if (lane == 0) { cnt[256] = 0; cum[256] = 0; }
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(64) void k_chunk_model(const StreamJob *jobs, const
 		if (valid) atomicAdd(&bh[s], 1u);
 		__syncthreads();
 		uint32_t a0 = bh[4 * lane], a1 = bh[4 * lane + 1], a2 = bh[4 * lane + 2], a3 = bh[4 * lane + 3], tot;
-		uint32_t ex = wscan_excl(a0 + a1 + a2 + a3, tot);
+		uint32_t ex = wave_excl_scan(a0 + a1 + a2 + a3, tot);
 		cnt[4 * lane] += a0; cnt[4 * lane + 1] += a1; cnt[4 * lane + 2] += a2; cnt[4 * lane + 3] += a3;
 		cum[4 * lane] += ex; cum[4 * lane + 1] += ex + a0; cum[4 * lane + 2] += ex + a0 + a1; cum[4 * lane + 3] += ex + a0 + a1 + a2;
 		__syncthreads();
@@ -224,10 +213,7 @@ __global__ __launch_bounds__(64) void k_chunk_ranges(const StreamJob *jobs, uint
 	const uint32_t n = have ? jb.n : 0u;
 	const uint2 *in = rec + (have ? rec_off[job] : 0ull);
 	unsigned long long *dst = acc + jb.word_base;
-	uint32_t nmax = n;
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-	nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmax);
+	const uint32_t nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(n));
 	const uint32_t in_lo = (uint32_t)(uintptr_t)in, in_hi = (uint32_t)((uintptr_t)in >> 32);
 	uint2 nxt[64];
 	// the records step0 .. step0 + 63 of every stream of the wavefront, one coalesced load a stream
@@ -285,30 +271,18 @@ __global__ __launch_bounds__(64) void k_chunk_ranges(const StreamJob *jobs, uint
 	}
 }
 
-// byte length of every stream and exclusive prefix (one workgroup; wave scans + LDS for the wave totals)
+// byte length of every stream and exclusive prefix (one workgroup, 1024 streams a pass, the passes before in `carry`)
 __global__ __launch_bounds__(1024) void k_stream_offsets(const uint32_t *stream_bits, uint32_t n, uint32_t *nbytes, unsigned long long *offsets)
 {
-	__shared__ unsigned long long wave_tot[16];
-	__shared__ unsigned long long carry;
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	__shared__ unsigned long long s_wave[17];
+	unsigned long long carry = 0;
 	for (uint32_t base = 0; base < n; base += 1024) {
-		uint32_t i = base + threadIdx.x;
-		uint32_t nb = i < n ? (stream_bits[i] + 7) >> 3 : 0;
-		unsigned long long inc = nb;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			unsigned long long o = __shfl_up(inc, d, 64);
-			if (lane >= d) inc += o;
-		}
-		if (lane == 63) wave_tot[wv] = inc;
-		__syncthreads();
-		unsigned long long pre = carry;
-		for (int k = 0; k < wv; ++k) pre += wave_tot[k];
-		if (i < n) { nbytes[i] = nb; offsets[i] = pre + inc - nb; }
-		__syncthreads();
-		if (threadIdx.x == 1023) carry = pre + inc;
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t nb = i < n ? (stream_bits[i] + 7) >> 3 : 0;
+		unsigned long long total;
+		const unsigned long long ex = block_excl_scan<unsigned long long>(nb, s_wave, total);
+		if (i < n) { nbytes[i] = nb; offsets[i] = carry + ex; }
+		carry += total;
 		__syncthreads();
 	}
 	if (threadIdx.x == 0) offsets[n] = carry;
@@ -350,13 +324,10 @@ __global__ __launch_bounds__(64) void k_chunk_decode(const StreamJob *jobs, cons
 	{
 		const uint32_t *st = inits + (size_t)jb.init * 256 + 4 * lane;
 		const uint32_t c0 = st[0], c1 = st[1], c2 = st[2], c3 = st[3];
-		uint32_t tot, ex = wscan_excl(c0 + c1 + c2 + c3, tot);
+		uint32_t tot, ex = wave_excl_scan(c0 + c1 + c2 + c3, tot);
 		i0 = ex + c0; i1 = i0 + c1; i2 = i1 + c2; i3 = i2 + c3;
 		const uint32_t top = c3 ? 4 * lane + 3 : c2 ? 4 * lane + 2 : c1 ? 4 * lane + 1 : c0 ? 4 * lane : 0u;
-		uint32_t mx = top;   // largest symbol with a non-zero count
-#pragma unroll
-		for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-		sym_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+		sym_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(top));   // largest symbol with a non-zero count
 	}
 	const uint8_t *src = payload + offsets[blockIdx.x];
 	const uint32_t nby = nbytes[blockIdx.x];
@@ -489,10 +460,7 @@ __global__ __launch_bounds__(64) void k_chunk_decode_lanes(const StreamJob *jobs
 	uint32_t R = 1u << 31, t = jb.t0;
 	typedef __attribute__((address_space(1))) uint8_t gbyte;   // (global, not generic: a flat store also counts as an LDS operation)
 	gbyte *out = (gbyte*)const_cast<uint8_t*>(jb.sym);
-	uint32_t nmax = jb.n;
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-	nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmax);
+	const uint32_t nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(jb.n));
 	MagicEnt me = magic[t];    // reciprocal of t, fetched a symbol ahead (t is known: t0 + position)
 	// decoded symbols leave sixteen at a time: a store per symbol has every later wait for a load wait for the store as well (one
 	// counter for both, in order) -- a round trip to memory per symbol, 124 ms for the configs[3] mesh's attribute planes instead of 30
@@ -602,8 +570,7 @@ __global__ __launch_bounds__(64) void k_split_count(const uint8_t *ops, uint32_t
 	}
 #pragma unroll
 	for (int j = 0; j < 8; ++j) {
-		uint32_t v = c[j];
-		for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+		const uint32_t v = wave_sum(c[j]);
 		if (lane == 0) cnt[u * 8 + j] = v;
 	}
 }
@@ -615,10 +582,10 @@ __global__ __launch_bounds__(64) void k_split_scan(uint32_t *cnt, uint32_t nunit
 	for (uint32_t u0 = 0; u0 < nunits; u0 += 64) {
 		const uint32_t u = u0 + lane;
 		const uint32_t c = u < nunits ? cnt[u * 8 + j] : 0u;
-		uint32_t inc = c;
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d); if ((int)lane >= d) inc += o; }
-		if (u < nunits) cnt[u * 8 + j] = run + inc - c;
-		run += __shfl(inc, 63);
+		uint32_t tot;
+		const uint32_t ex = wave_excl_scan(c, tot);
+		if (u < nunits) cnt[u * 8 + j] = run + ex;
+		run += tot;
 	}
 }
 __global__ __launch_bounds__(64) void k_split_place(const uint8_t *ops, uint32_t n, const uint32_t *cnt, uint8_t *planes)

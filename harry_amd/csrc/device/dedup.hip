@@ -3,7 +3,7 @@
 // wave64, an item per lane:
 //   k_dedup_insert<Key>  every item into an open-addressing table of item indices (at least 2 n slots, linear probing)
 //   k_dedup_find<Key>    per item the first item of its key; per wavefront of 64 items the mask of first items and their count
-//   k_scan_counts        exclusive scan of the wavefront counts by one block (also the ingest's face offsets)
+//   k_scan_counts        exclusive scan of the wavefront counts by one block (scan.hip: launch_scan_counts)
 //   k_dedup_assign       id = dedup_id(first item), and per id its first item (and what `via` holds for it)
 //   k_iota               out[i] = i: the numbering where nothing is merged
 //
@@ -129,26 +129,6 @@ __global__ __launch_bounds__(256) void k_dedup_find(typename Key::View u, uint32
 	}
 }
 
-// exclusive scan of n counts by one block (out: n + 1 entries, out[n] = total)
-__global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t *counts, uint32_t n, uint32_t *out)
-{
-	__shared__ uint32_t part[1024];
-	const uint32_t per = (n + 1023) / 1024, b = threadIdx.x * per, e = min(n, b + per);
-	uint32_t sum = 0;
-	for (uint32_t i = b; i < e; ++i) sum += counts[i];
-	part[threadIdx.x] = sum;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024; d <<= 1) {   // Hillis-Steele over the threads' sums
-		const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-		__syncthreads();
-		part[threadIdx.x] += add;
-		__syncthreads();
-	}
-	uint32_t run = part[threadIdx.x] - sum;
-	for (uint32_t i = b; i < e; ++i) { out[i] = run; run += counts[i]; }
-	if (threadIdx.x == 1023) out[n] = part[1023];
-}
-
 // the id of the key whose first item is e: the first items before e's wavefront, plus those below e inside it
 __device__ __forceinline__ uint32_t dedup_id(uint32_t e, const uint64_t *masks, const uint32_t *wave_start)
 {
@@ -178,12 +158,6 @@ __global__ __launch_bounds__(256) void k_iota(uint32_t n, uint32_t *out)
 }
 
 // ---- launchers
-static inline unsigned blocks_of(uint32_t n) { return (unsigned)(((uint64_t)n + 255) / 256); }
-
-void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out)
-{
-	hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, counts, n, out);
-}
 void DedupPlan::reserve(Carve &W, uint32_t items)
 {
 	n = items; nw = (uint32_t)(((uint64_t)n + 63) / 64);
@@ -203,20 +177,20 @@ static void dedup_count(hipStream_t st, typename Key::View u, const DedupPlan &p
 {
 	if (!p.n) return;
 	u.n = p.n; u.table = p.table; u.mask = p.mask;   // the kernels' bounds and the grid come from one place
-	hipLaunchKernelGGL(k_dedup_insert<Key>, dim3(blocks_of(p.n)), dim3(256), 0, st, u);
-	hipLaunchKernelGGL(k_dedup_find<Key>, dim3(blocks_of(p.n)), dim3(256), 0, st, u, p.first_of, p.masks, p.counts);
+	hipLaunchKernelGGL(k_dedup_insert<Key>, dim3(blocks_for(p.n, 256)), dim3(256), 0, st, u);
+	hipLaunchKernelGGL(k_dedup_find<Key>, dim3(blocks_for(p.n, 256)), dim3(256), 0, st, u, p.first_of, p.masks, p.counts);
 	launch_scan_counts(st, p.counts, p.nw, p.wave_start);
 }
 void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p) { dedup_count<UnweldKey>(st, u, p); }
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p) { dedup_count<WeldKey>(st, u, p); }
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via, uint32_t *via_out)
 {
-	if (p.n) hipLaunchKernelGGL(k_dedup_assign, dim3(blocks_of(p.n)), dim3(256), 0, st, p.n, (const uint32_t*)p.first_of, (const uint64_t*)p.masks,
+	if (p.n) hipLaunchKernelGGL(k_dedup_assign, dim3(blocks_for(p.n, 256)), dim3(256), 0, st, p.n, (const uint32_t*)p.first_of, (const uint64_t*)p.masks,
 	                            (const uint32_t*)p.wave_start, nout, p.ids, first_item, via, via_out);
 }
 void launch_iota(hipStream_t st, uint32_t n, uint32_t *out)
 {
-	if (n) hipLaunchKernelGGL(k_iota, dim3(blocks_of(n)), dim3(256), 0, st, n, out);
+	if (n) hipLaunchKernelGGL(k_iota, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, out);
 }
 
 }   // namespace dev

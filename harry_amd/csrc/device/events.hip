@@ -9,7 +9,8 @@
 // slot, vertex).  Both are answers to "who was FIRST", and first-of is a minimum over positions in the coding order:
 //   k_ev_count / scan / k_ev_expand    the references of ONE list in coding order: element (half-edge of the vertex / face / corner),
 //                                      slot, record.  Position p of a reference = exclusive scan of what every coded vertex / face
-//                                      contributes (its region may bind the list at no slot, or at several)
+//                                      contributes (its region may bind the list at no slot, or at several).  Every scan here is
+//                                      scan.hip's launch_excl_scan with its total in a word of its own
 //   k_ev_names (corner lists)          per (slot, vertex) a lock-free list of the records named there, each with the SMALLEST position
 //                                      that names it (insert by compare-and-swap, atomic minimum on a hit)
 //   k_ev_first                         a corner reference is answered by the vertex' names unless it is that smallest position; the
@@ -48,69 +49,6 @@ template <typename F> __device__ __forceinline__ void slots_of(const EvRegions &
 	for (int a = b; a < e; ++a) if (lists[a] == l) visit((uint32_t)(a - b));
 }
 __device__ __forceinline__ uint32_t face_of(const ConnView &cv, uint32_t h) { return cv.eface ? cv.eface[h] : h / cv.udeg; }
-
-// ---- exclusive scan (block sums, scan of the sums by one block, apply), as twins.hip has it
-constexpr int kScanBlock = 1024;
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave, uint32_t &block_total)
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-	if (lane == 63) s_wave[wave] = inc;
-	__syncthreads();
-	if (wave == 0) {
-		uint32_t w = lane < kScanBlock / 64 ? s_wave[lane] : 0u, wi = w;
-#pragma unroll
-		for (int d = 1; d < 16; d <<= 1) { uint32_t o = __shfl_up(wi, d, 64); if (lane >= d) wi += o; }
-		if (lane < kScanBlock / 64) s_wave[lane] = wi - w;
-		if (lane == kScanBlock / 64 - 1) s_wave[16] = wi;
-	}
-	__syncthreads();
-	block_total = s_wave[16];
-	return s_wave[wave] + inc - v;
-}
-__global__ __launch_bounds__(kScanBlock) void k_ev_scan_sums(const uint32_t *in, uint32_t n, uint32_t *sums)
-{
-	__shared__ uint32_t s_wave[17];
-	const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-	uint32_t total;
-	block_excl_scan(i < n ? in[i] : 0u, s_wave, total);
-	if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kScanBlock) void k_ev_scan_top(uint32_t *sums, uint32_t nb)
-{
-	__shared__ uint32_t s_wave[17];
-	uint32_t carry = 0;
-	for (uint32_t base = 0; base < nb; base += kScanBlock) {
-		const uint32_t i = base + threadIdx.x;
-		const uint32_t v = i < nb ? sums[i] : 0u;
-		uint32_t total;
-		const uint32_t ex = block_excl_scan(v, s_wave, total);
-		if (i < nb) sums[i] = carry + ex;
-		carry += total;
-		__syncthreads();
-	}
-}
-// out[i] = exclusive prefix; *total_out = the sum (n >= 1)
-__global__ __launch_bounds__(kScanBlock) void k_ev_scan_apply(const uint32_t *in, uint32_t n, const uint32_t *sums, uint32_t *out, uint32_t *total_out)
-{
-	__shared__ uint32_t s_wave[17];
-	const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-	const uint32_t v = i < n ? in[i] : 0u;
-	uint32_t total;
-	const uint32_t ex = block_excl_scan(v, s_wave, total) + sums[blockIdx.x];
-	if (i < n) out[i] = ex;
-	if (i == n - 1) *total_out = ex + v;
-}
-void exclusive_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out, uint32_t *total_out)
-{
-	if (!n) { (void)hipMemsetAsync(total_out, 0, 4, st); return; }
-	const unsigned nb = (n + kScanBlock - 1) / kScanBlock;
-	hipLaunchKernelGGL(k_ev_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, in, n, sums);
-	hipLaunchKernelGGL(k_ev_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
-	hipLaunchKernelGGL(k_ev_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, in, n, (const uint32_t*)sums, out, total_out);
-}
 
 // ---- the references of one list ----------------------------------------------------------------------------------------------------
 // kind: 0 face list, 1 vertex list, 2 corner list.  order: order_v (kind 1) or order_f; one thread per coded vertex / face
@@ -272,7 +210,6 @@ __global__ __launch_bounds__(256) void k_ev_regions(int kind, ConnView cv, GenVi
 	const uint32_t h = order[i];
 	out[i] = (uint8_t)(kind == 1 ? gv.vtx_reg[cv.org[h]] : gv.face_reg[face_of(cv, h)]);
 }
-inline unsigned blocks(uint32_t n) { return (n + 255u) / 256u; }
 }   // namespace
 
 namespace {
@@ -280,7 +217,7 @@ struct ListWs {   // one list's arrays between the two phases
 	uint32_t *cnt, *base, *sums, *r_elem, *r_idx, *r_q, *f_data, *f_hist, *f_lhist, *at_data, *at_hist, *at_lhist, *first_pos, *rank_of;
 	uint8_t *r_slot, *is_first;
 };
-size_t sums_words(uint32_t n_order, uint32_t max_refs) { return (std::max<size_t>(max_refs, n_order) + kScanBlock - 1) / kScanBlock + 8; }
+size_t sums_words(uint32_t n_order, uint32_t max_refs) { return scan_sums_words(std::max(max_refs, n_order)); }   // one scratch for the scans over either
 ListWs carve(void *ws, uint32_t n_order, uint32_t max_refs, uint32_t list_count)
 {
 	const size_t r = max_refs;
@@ -331,8 +268,8 @@ void launch_corner_places(hipStream_t st, const ConnView &cv, const GenView &gv,
 	(void)hipMemsetAsync(nm.head, 0xff, (size_t)head_words * 4, st);
 	(void)hipMemsetAsync(nm.n_nodes, 0, 16, st);
 	if (!fc) return;
-	hipLaunchKernelGGL(k_ev_corner_count, dim3(blocks(fc)), dim3(256), 0, st, cv, gv, rg, order_f, fc, corner_cnt);
-	exclusive_scan(st, corner_cnt, fc, sums, corner_base, nm.n_nodes + 1);   // (the total: not used)
+	hipLaunchKernelGGL(k_ev_corner_count, dim3(blocks_for(fc, 256)), dim3(256), 0, st, cv, gv, rg, order_f, fc, corner_cnt);
+	launch_excl_scan(st, corner_cnt, fc, sums, corner_base, nm.n_nodes + 1);   // (the total: not used)
 }
 // phase 1 of a list: its references in coding order (counts[0] = how many); a corner list also enters them in the vertices' names
 void launch_list_refs(hipStream_t st, int kind, uint32_t list, uint32_t list_count, const ConnView &cv, const GenView &gv, const EvRegions &rg,
@@ -345,15 +282,15 @@ void launch_list_refs(hipStream_t st, int kind, uint32_t list, uint32_t list_cou
 	uint32_t *corner_base, *corner_cnt, *sums;
 	Names nm = names_of(names_ws, fc, corner_refs_max, head_words, nv, &corner_base, &corner_cnt, &sums);
 	nm.err = err;
-	hipLaunchKernelGGL(k_ev_count, dim3(blocks(n_order)), dim3(256), 0, st, kind, list, cv, gv, rg, order, n_order, L.cnt);
-	exclusive_scan(st, L.cnt, n_order, L.sums, L.base, counts + 0);
-	hipLaunchKernelGGL(k_ev_expand, dim3(blocks(n_order)), dim3(256), 0, st, kind, list, list_count, cv, gv, rg, order, n_order, (const uint32_t*)L.base, (const uint32_t*)corner_base,
+	hipLaunchKernelGGL(k_ev_count, dim3(blocks_for(n_order, 256)), dim3(256), 0, st, kind, list, cv, gv, rg, order, n_order, L.cnt);
+	launch_excl_scan(st, L.cnt, n_order, L.sums, L.base, counts + 0);
+	hipLaunchKernelGGL(k_ev_expand, dim3(blocks_for(n_order, 256)), dim3(256), 0, st, kind, list, list_count, cv, gv, rg, order, n_order, (const uint32_t*)L.base, (const uint32_t*)corner_base,
 	                   L.r_elem, L.r_slot, L.r_idx, L.r_q, err);
 	(void)hipMemsetAsync(L.first_pos, 0xff, ((size_t)list_count + 1) * 4, st);
 	// (the kernels over references start max_refs threads -- an upper bound the host knows -- and stop at the references there are:
 	// their number stays on the device, counts[0])
 	if (kind == 2)
-		hipLaunchKernelGGL(k_ev_names, dim3(blocks(max_refs)), dim3(256), 0, st, cv, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, (const uint32_t*)L.r_q,
+		hipLaunchKernelGGL(k_ev_names, dim3(blocks_for(max_refs, 256)), dim3(256), 0, st, cv, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, (const uint32_t*)L.r_q,
 		                   (const uint32_t*)counts, nm);
 }
 // phase 2 (every corner list has been through phase 1): the kinds (type_sym, one byte a reference: the list's first plane as it
@@ -369,20 +306,20 @@ void launch_list_kinds(hipStream_t st, int kind, uint32_t list_count, const Conn
 	nm.err = err;
 	const uint32_t *n_refs = counts + 0;
 	const uint32_t nr = max_refs;
-	hipLaunchKernelGGL(k_ev_first, dim3(blocks(nr)), dim3(256), 0, st, kind, cv, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, (const uint32_t*)L.r_q, n_refs, nm,
+	hipLaunchKernelGGL(k_ev_first, dim3(blocks_for(nr, 256)), dim3(256), 0, st, kind, cv, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, (const uint32_t*)L.r_q, n_refs, nm,
 	                   L.is_first, L.first_pos);
-	hipLaunchKernelGGL(k_ev_kind, dim3(blocks(nr)), dim3(256), 0, st, (const uint32_t*)L.r_idx, (const uint8_t*)L.is_first, (const uint32_t*)L.first_pos, n_refs, nr, type_sym, L.f_data, L.f_hist, L.f_lhist);
-	exclusive_scan(st, L.f_hist, nr, L.sums, L.at_hist, counts + 1);
-	exclusive_scan(st, L.f_lhist, nr, L.sums, L.at_lhist, counts + 2);
-	exclusive_scan(st, L.f_data, nr, L.sums, L.at_data, counts + 3);
-	hipLaunchKernelGGL(k_ev_data, dim3(blocks(nr)), dim3(256), 0, st, (const uint8_t*)type_sym, (const uint32_t*)L.at_data, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, n_refs,
+	hipLaunchKernelGGL(k_ev_kind, dim3(blocks_for(nr, 256)), dim3(256), 0, st, (const uint32_t*)L.r_idx, (const uint8_t*)L.is_first, (const uint32_t*)L.first_pos, n_refs, nr, type_sym, L.f_data, L.f_hist, L.f_lhist);
+	launch_excl_scan(st, L.f_hist, nr, L.sums, L.at_hist, counts + 1);
+	launch_excl_scan(st, L.f_lhist, nr, L.sums, L.at_lhist, counts + 2);
+	launch_excl_scan(st, L.f_data, nr, L.sums, L.at_data, counts + 3);
+	hipLaunchKernelGGL(k_ev_data, dim3(blocks_for(nr, 256)), dim3(256), 0, st, (const uint8_t*)type_sym, (const uint32_t*)L.at_data, (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, n_refs,
 	                   d_idx, d_he, d_slot, L.rank_of);
-	hipLaunchKernelGGL(k_ev_hist, dim3(blocks(nr)), dim3(256), 0, st, cv, (const uint8_t*)type_sym, (const uint32_t*)L.at_data, (const uint32_t*)L.at_hist, (const uint32_t*)L.at_lhist,
+	hipLaunchKernelGGL(k_ev_hist, dim3(blocks_for(nr, 256)), dim3(256), 0, st, cv, (const uint8_t*)type_sym, (const uint32_t*)L.at_data, (const uint32_t*)L.at_hist, (const uint32_t*)L.at_lhist,
 	                   (const uint32_t*)L.r_elem, (const uint8_t*)L.r_slot, (const uint32_t*)L.r_idx, (const uint32_t*)L.r_q, n_refs, (const uint32_t*)L.rank_of, nm, gh_val, lh_val, err);
 }
 void launch_region_symbols(hipStream_t st, int kind, const ConnView &cv, const GenView &gv, const uint32_t *order, uint32_t n, uint8_t *out)
 {
-	if (n) hipLaunchKernelGGL(k_ev_regions, dim3(blocks(n)), dim3(256), 0, st, kind, cv, gv, order, n, out);
+	if (n) hipLaunchKernelGGL(k_ev_regions, dim3(blocks_for(n, 256)), dim3(256), 0, st, kind, cv, gv, order, n, out);
 }
 
 }   // namespace dev

@@ -685,8 +685,6 @@ __global__ __launch_bounds__(64) void k_gen_chain(ConnView cv, GenView gv, const
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
 void launch_face_rank(hipStream_t st, const ConnView &cv, const uint32_t *order_f, uint32_t n, uint32_t *frank)
 {
 	if (n) hipLaunchKernelGGL(k_face_rank, dim3(blocks_for(n, 256)), dim3(256), 0, st, cv, order_f, n, frank);

@@ -9,12 +9,14 @@
 //   k_ingest_corner_attr  a lane per word of corner_attr: the corner's row in the slot's list, range-checked, through that list's weld map
 //   k_region_first / k_region_rank / k_ingest_face_region   a material per face -> regions numbered by first occurrence
 // The weld (one output record per distinct packed record, in first-occurrence order over the input rows) is dedup.hip's numbering
-// over a WeldView's keys, the one-block scan of the wave sums its k_scan_counts, vtx_attr[v] = v its k_iota.
+// over a WeldView's keys, vtx_attr[v] = v its k_iota; the one-block scan of the wave sums is scan.hip's launch_scan_counts, the sums
+// and prefixes inside a wavefront wave.hpp's.
 // The checks of the input raise bits of one status word (vector atomics, once per wavefront); the host reads it back once.  Offsets
 // computed from bad degrees are stored but never used for an address: the host refuses the mesh first.
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace hry {
 namespace dev {
@@ -23,7 +25,7 @@ constexpr uint32_t kNone = 0xffffffffu;
 
 // ---------------------------------------------------------------------------------------------------------
 // face offsets from uint8 degrees: per wavefront of 64 faces the sum of its degrees (at most 64 x 255, a u32), scanned by
-// launch_scan_counts (dedup.hip), then the prefix inside the wavefront.  The 64-bit total is summed separately (per block in LDS, then one atomic
+// launch_scan_counts (scan.hip), then the prefix inside the wavefront.  The 64-bit total is summed separately (per block in LDS, then one atomic
 // per block): the host compares it with n_indices before it trusts any u32 offset, so degrees whose sum passes 2^32 cannot wrap.
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ingest_degrees(const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, IngestStatus *st)
@@ -37,8 +39,7 @@ __global__ __launch_bounds__(256) void k_ingest_degrees(const uint8_t *deg, uint
 	const uint32_t d = f < nf ? deg[f] : 0;
 	if (f < nf) atomicOr(&mask[d >> 5], 1u << (d & 31));
 	const uint64_t bad = __ballot(f < nf && d < 3);
-	uint32_t s = d;
-	for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+	const uint32_t s = wave_sum(d);
 	if ((threadIdx.x & 63) == 0) {
 		if (bad) atomicOr(&st->err, kIngestBadDegree);
 		if (f < nf) { wave_sums[f >> 6] = s; atomicAdd(&bsum, (unsigned long long)s); }
@@ -50,12 +51,8 @@ __global__ __launch_bounds__(256) void k_ingest_degrees(const uint8_t *deg, uint
 
 __global__ __launch_bounds__(256) void k_ingest_foff(const uint8_t *deg, uint32_t nf, const uint32_t *wave_start, uint32_t *foff)
 {
-	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
-	uint32_t s = f < nf ? deg[f] : 0;
-	for (int o = 1; o < 64; o <<= 1) {   // inclusive prefix inside the wavefront
-		const uint32_t t = __shfl_up(s, o);
-		if (lane >= (uint32_t)o) s += t;
-	}
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t s = wave_incl_scan<uint32_t>(f < nf ? deg[f] : 0);
 	if (f < nf) foff[f + 1] = wave_start[f >> 6] + s;
 	if (f == 0) foff[0] = 0;
 }
@@ -190,8 +187,6 @@ __global__ __launch_bounds__(256) void k_ingest_face_region(const uint16_t *mat,
 }
 
 // ---- launchers
-static inline unsigned grid_for(uint64_t n, unsigned per) { const uint64_t b = (n + per - 1) / per; return (unsigned)(b < (1u << 20) ? b : (1u << 20)); }
-
 void launch_ingest_offsets(hipStream_t st, const uint8_t *deg, uint32_t nf, uint32_t *wave_sums, uint32_t *wave_start, uint32_t *foff, IngestStatus *status)
 {
 	if (!deg) {

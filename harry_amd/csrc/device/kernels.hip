@@ -9,6 +9,7 @@
 #include "dev_types.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace hry {
 namespace dev {
@@ -540,18 +541,6 @@ __global__ __launch_bounds__(256) void k_model_scan(const PlaneJob *jobs, uint32
 	}
 }
 
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total)
-{
-	uint32_t inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		uint32_t o = __shfl_up(inc, d, 64);
-		if ((int)(threadIdx.x & 63) >= d) inc += o;
-	}
-	total = __shfl(inc, 63, 64);
-	return inc - v;
-}
-
 __global__ __launch_bounds__(64) void k_model_lht(const PlaneJob *jobs, const ChunkRef *chunks, const uint32_t *hist, const MagicEnt *magic,
                                                   SymRec *rec, uint32_t *sym_l)
 {
@@ -829,8 +818,6 @@ __global__ __launch_bounds__(256) void k_carry_apply(const unsigned long long *a
 // ---------------------------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------------------------
-static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
 void launch_bounds(hipStream_t st, const uint8_t *rec, uint32_t count, const BoundsPlan &plan,
                    uint8_t *part_min, uint8_t *part_max, uint32_t *part_idx, int nparts, uint8_t *out)
 {

@@ -1,4 +1,4 @@
-// Launch wrappers of the HIP kernels (kernels.hip, chunked.hip).  Everything is enqueued on the given stream.
+// Launch wrappers of the HIP kernels (kernels.hip, chunked.hip, ...).  Everything is enqueued on the given stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,10 @@
 namespace hry {
 struct Carve;   // hip_handles.hpp
 namespace dev {
+
+// grids: blocks of `per` items that cover n; grid_for: at most 2^20 of them, for kernels that stride over the grid
+inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+inline unsigned grid_for(uint64_t n, unsigned per) { return (unsigned)std::min<uint64_t>((n + per - 1) / per, 1u << 20); }
 
 // every component of a list in two launches; out: 24 bytes per component { u64 min, u64 max, u32 min_at, u32 max_at }
 void launch_bounds(hipStream_t st, const uint8_t *rec, uint32_t count, const BoundsPlan &plan,
@@ -91,9 +95,13 @@ size_t twin_workspace_bytes(uint32_t nv, uint32_t ne);
 uint32_t twin_overflow_capacity();
 // *over: device pointer (inside ws) of the list of vertices with too many half-edges for the kernel: count, then vertex ids
 void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twin, void *ws, const uint32_t **over);
-// exclusive scan of n counters in three launches (k_scan_*): out[n + 1], out[n] = total; sums: scan_sums_words(n) words of scratch
+
+// the grid-level exclusive scans (scan.hip; the wavefront and block levels under them: wave.hpp).  launch_excl_scan: n counters in
+// three launches, sums: scan_sums_words(n) words of scratch.  total_out == nullptr: out[n + 1], out[n] = total; otherwise out[n]
+// and *total_out = total.  No counters: the total alone, 0
 size_t scan_sums_words(uint32_t n);
-void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out);
+void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out, uint32_t *total_out = nullptr);
+void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out);   // k_scan_counts (one block): out[n + 1], out[n] = total
 
 // order.hip: the numbering maps of an encode; every table pre-filled with 0xFF (kNoRank) by the caller
 void launch_order_vertex(hipStream_t st, const uint32_t *order_v, uint32_t n, const uint32_t *org, uint32_t nv, uint32_t *vertex, uint32_t *vertex_inv);
@@ -172,7 +180,6 @@ void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p);
 // p.ids[i] = id of item i; per id below nout: first_item[id] = its first item, via_out[id] = via[that item] (via == nullptr: none)
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via = nullptr, uint32_t *via_out = nullptr);
-void launch_scan_counts(hipStream_t st, const uint32_t *counts, uint32_t n, uint32_t *out);   // k_scan_counts (one block): out[n + 1], out[n] = total
 void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
 
 // render-ready buffers (render.hip; driver: render.cpp).  launch_fan: tri_face[T] and indices[3T] of the fan triangulation,

@@ -6,7 +6,7 @@
 //                   buffer (24 B per face: N_f in area mode, N_f / |N_f| in angle mode, zeros for a face that contributes nothing)
 //                   and, where asked for, the unit normal as floats
 //   k_nrm_count     one counter per vertex: its corners (integer atomics)
-//   k_scan_*        exclusive scan of the counters (twins.hip, through its launch_excl_scan)
+//   k_scan_*        exclusive scan of the counters (scan.hip: launch_excl_scan)
 //   k_nrm_scatter   corners into their vertex's segment, in any order
 //   k_nrm_vertices  a lane per vertex: sorts its segment by corner id (insertion sort: a handful of entries), sums the corners'
 //                   contributions in that order, normalises.  Segments of more than kNrmSegMax corners are listed for k_nrm_hubs
@@ -202,8 +202,6 @@ __global__ __launch_bounds__(256) void k_nrm_expand(const float *vn, const uint3
 }
 
 // ---- launchers
-static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
 uint32_t normals_hub_capacity(uint32_t ne) { return ne / (kNrmSegMax + 1) + 1; }
 
 void launch_face_normals(hipStream_t st, const NrmView &n, double *fn, float *face_normals)

@@ -2,7 +2,7 @@
 // inverses, and the kernel that moves a caller's rows through a map.  Integer work only, wave64, a lane per output word.
 //   k_order_vertex   vertex[org[order_v[j]]] = j, vertex_inv[j] = the vertex                  (what k_rank computes, with its inverse)
 //   k_order_face     face[face_of(order_f[j])] = j, face_inv[j] = the face, and the face's degree in coding order (mixed degrees)
-//   k_scan_*         (twins.hip: launch_excl_scan, from order.cpp) exclusive scan of those degrees: where every decoded face begins.  Uniform degree: j * degree
+//   k_scan_*         (scan.hip: launch_excl_scan, from order.cpp) exclusive scan of those degrees: where every decoded face begins.  Uniform degree: j * degree
 //   k_order_corner   the decoder makes the half-edge a face is entered through the face's first (cbm/decoder.h:75-77 for a
 //                    component's first face, :162-164 for the rest, where e0 is the twin of the gate) and keeps the cyclic order: the
 //                    corner k places behind order_f[j] round source face f becomes decoded half-edge doff[j] + k
@@ -86,23 +86,21 @@ __global__ __launch_bounds__(256) void k_order_rows(const uint32_t *map, uint64_
 	*(T*)(dst + row * dst_stride + (uint64_t)u * sizeof(T)) = v;
 }
 
-static inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 void launch_order_vertex(hipStream_t st, const uint32_t *order_v, uint32_t n, const uint32_t *org, uint32_t nv, uint32_t *vertex, uint32_t *vertex_inv)
 {
-	if (n) hipLaunchKernelGGL(k_order_vertex, dim3(blocks_of(n)), dim3(256), 0, st, order_v, n, org, nv, vertex, vertex_inv);
+	if (n) hipLaunchKernelGGL(k_order_vertex, dim3(blocks_for(n, 256)), dim3(256), 0, st, order_v, n, org, nv, vertex, vertex_inv);
 }
 void launch_order_face(hipStream_t st, const ConnView &cv, const uint32_t *order_f, uint32_t n, uint32_t *face, uint32_t *face_inv, uint32_t *deg)
 {
-	if (n) hipLaunchKernelGGL(k_order_face, dim3(blocks_of(n)), dim3(256), 0, st, cv, order_f, n, face, face_inv, deg);
+	if (n) hipLaunchKernelGGL(k_order_face, dim3(blocks_for(n, 256)), dim3(256), 0, st, cv, order_f, n, face, face_inv, deg);
 }
 void launch_order_corner(hipStream_t st, const ConnView &cv, const uint32_t *order_f, const uint32_t *face, const uint32_t *doff, uint32_t *corner, uint32_t *corner_inv)
 {
-	if (cv.ne) hipLaunchKernelGGL(k_order_corner, dim3(blocks_of(cv.ne)), dim3(256), 0, st, cv, order_f, face, doff, corner, corner_inv);
+	if (cv.ne) hipLaunchKernelGGL(k_order_corner, dim3(blocks_for(cv.ne, 256)), dim3(256), 0, st, cv, order_f, face, doff, corner, corner_inv);
 }
 void launch_order_records(hipStream_t st, const uint32_t *d_idx, uint32_t nd, uint32_t count, uint32_t *list, uint32_t *list_inv)
 {
-	if (nd) hipLaunchKernelGGL(k_order_records, dim3(blocks_of(nd)), dim3(256), 0, st, d_idx, nd, count, list, list_inv);
+	if (nd) hipLaunchKernelGGL(k_order_records, dim3(blocks_for(nd, 256)), dim3(256), 0, st, d_idx, nd, count, list, list_inv);
 }
 bool launch_order_rows(hipStream_t st, const uint32_t *map, uint64_t rows, const void *src, uint64_t src_stride, void *dst, uint64_t dst_stride, uint64_t row_bytes)
 {
@@ -112,7 +110,7 @@ bool launch_order_rows(hipStream_t st, const uint32_t *map, uint64_t rows, const
 	const uint64_t upr = row_bytes / unit;
 	if (upr > 0xffffffffull || rows > (0x7fffffffull * 256) / upr) return false;   // (more lanes than one launch has)
 	const uint64_t total = rows * upr;
-	const dim3 grid(blocks_of(total)), block(256);
+	const dim3 grid(blocks_for(total, 256)), block(256);
 	const uint8_t *s8 = (const uint8_t*)src;
 	uint8_t *d8 = (uint8_t*)dst;
 	if (unit == 16) hipLaunchKernelGGL(k_order_rows<Quad>, grid, block, 0, st, map, rows, s8, src_stride, d8, dst_stride, (uint32_t)upr, total);

@@ -169,8 +169,6 @@ __global__ __launch_bounds__(256) void k_place_foff(RunPlace r, const uint32_t *
 }
 
 // ---- launchers
-static inline unsigned grid_for(uint64_t n, unsigned per) { const uint64_t b = (n + per - 1) / per; return (unsigned)(b < (1u << 20) ? b : (1u << 20)); }
-
 void launch_fan(hipStream_t st, const uint32_t *foff, uint32_t nf, uint64_t ntri, const uint32_t *vmap, uint32_t ne, uint32_t *tri_face, uint32_t *indices)
 {
 	if (!nf || !ntri) return;

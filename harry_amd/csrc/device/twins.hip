@@ -3,7 +3,7 @@
 // otherwise becomes pending itself -- unless an (a, b) is pending already, in which case it stays unmatched for good
 // (conn.h:201-214).  Only half-edges over the same undirected edge interact, in the order of their indices, so:
 //   k_twin_count    one counter per vertex: half-edges whose smaller endpoint it is          (atomics, 4 B per half-edge)
-//   k_scan_*        exclusive scan of the counters, in three launches (launch_excl_scan: also the components below, normals.hip, order.cpp)
+//   k_scan_*        exclusive scan of the counters, in three launches (scan.hip: launch_excl_scan; also the components below)
 //   k_twin_scatter  (larger endpoint, half-edge) pairs into the segment of the smaller endpoint (any order)
 //   k_twin_match    one thread per vertex: sorts its segment (a handful of entries) by (larger endpoint, half-edge) and
 //                   replays the reference's rule over every run of equal larger endpoints
@@ -13,6 +13,7 @@
 #include "dev_types.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace hry {
 namespace dev {
@@ -25,60 +26,6 @@ __global__ __launch_bounds__(256) void k_twin_count(ConnView cv, uint32_t *twin,
 	const uint32_t a = cv.org[h], c = cv.org[tp.next(h)];
 	twin[h] = h;
 	atomicAdd(&count[min(a, c)], 1u);
-}
-
-// ---- exclusive scan over n counters: block sums, scan of the sums by one block, apply --------------------------------------
-constexpr int kScanBlock = 1024;
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave, uint32_t &block_total)   // 1024 threads
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-	if (lane == 63) s_wave[wave] = inc;
-	__syncthreads();
-	if (wave == 0) {
-		uint32_t w = lane < kScanBlock / 64 ? s_wave[lane] : 0u, wi = w;
-#pragma unroll
-		for (int d = 1; d < 16; d <<= 1) { uint32_t o = __shfl_up(wi, d, 64); if (lane >= d) wi += o; }
-		if (lane < kScanBlock / 64) s_wave[lane] = wi - w;
-		if (lane == kScanBlock / 64 - 1) s_wave[16] = wi;
-	}
-	__syncthreads();
-	block_total = s_wave[16];
-	return s_wave[wave] + inc - v;
-}
-__global__ __launch_bounds__(kScanBlock) void k_scan_sums(const uint32_t *in, uint32_t n, uint32_t *sums)
-{
-	__shared__ uint32_t s_wave[17];
-	const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-	uint32_t total;
-	block_excl_scan(i < n ? in[i] : 0u, s_wave, total);
-	if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kScanBlock) void k_scan_top(uint32_t *sums, uint32_t nb)   // one block: exclusive scan in place, any nb
-{
-	__shared__ uint32_t s_wave[17];
-	uint32_t carry = 0;
-	for (uint32_t base = 0; base < nb; base += kScanBlock) {
-		const uint32_t i = base + threadIdx.x;
-		const uint32_t v = i < nb ? sums[i] : 0u;
-		uint32_t total;
-		const uint32_t ex = block_excl_scan(v, s_wave, total);
-		if (i < nb) sums[i] = carry + ex;
-		carry += total;
-		__syncthreads();
-	}
-}
-__global__ __launch_bounds__(kScanBlock) void k_scan_apply(const uint32_t *in, uint32_t n, const uint32_t *sums, uint32_t *out)   // out[n] = total
-{
-	__shared__ uint32_t s_wave[17];
-	const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-	const uint32_t v = i < n ? in[i] : 0u;
-	uint32_t total;
-	const uint32_t ex = block_excl_scan(v, s_wave, total) + sums[blockIdx.x];
-	if (i < n) out[i] = ex;
-	if (i == n - 1) out[n] = ex + v;
 }
 
 __global__ __launch_bounds__(256) void k_twin_scatter(ConnView cv, const uint32_t *start, uint32_t *fill, unsigned long long *ent)
@@ -131,21 +78,8 @@ __global__ __launch_bounds__(256) void k_twin_match(ConnView cv, uint32_t nv, co
 	}
 }
 
-static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
-// the one launcher of k_scan_*: out[n + 1], out[n] = total (no counters: out[0] = 0); sums: scan_sums_words(n) words of scratch
-size_t scan_sums_words(uint32_t n) { return (size_t)blocks_for(n, kScanBlock) + 2; }
-void launch_excl_scan(hipStream_t st, const uint32_t *in, uint32_t n, uint32_t *sums, uint32_t *out)
-{
-	if (!n) { (void)hipMemsetAsync(out, 0, 4, st); return; }
-	const unsigned nb = blocks_for(n, kScanBlock);
-	hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(kScanBlock), 0, st, in, n, sums);
-	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
-	hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kScanBlock), 0, st, in, n, (const uint32_t*)sums, out);
-}
-
-// ws: (2 * nv + 2 + blocks) * 4 bytes of counters + ne * 8 bytes of entries (8-byte aligned first) + the overflow list
-size_t twin_workspace_bytes(uint32_t nv, uint32_t ne) { return (size_t)ne * 8 + ((size_t)2 * nv + 2 + blocks_for(nv, kScanBlock) + 2 + kTwinOverMax + 1) * 4; }
+// ws: ne * 8 bytes of entries (8-byte aligned first) + (2 * nv + 2) * 4 bytes of counters (count[nv], start[nv + 1], a spare word) + the scan's sums + the overflow list
+size_t twin_workspace_bytes(uint32_t nv, uint32_t ne) { return (size_t)ne * 8 + ((size_t)2 * nv + 2 + scan_sums_words(nv) + kTwinOverMax + 1) * 4; }
 uint32_t twin_overflow_capacity() { return kTwinOverMax; }
 // over_out: device pointer of the overflow list (count, then vertex ids) inside ws
 void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twin, void *ws, const uint32_t **over_out)
@@ -153,7 +87,7 @@ void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twi
 	if (!cv.ne) return;
 	unsigned long long *ent = (unsigned long long*)ws;
 	uint32_t *count = (uint32_t*)(ent + cv.ne), *start = count + nv, *sums = start + nv + 1;
-	uint32_t *over = sums + blocks_for(nv, kScanBlock) + 2;
+	uint32_t *over = sums + scan_sums_words(nv);
 	(void)hipMemsetAsync(over, 0, 4, st);
 	*over_out = over;
 	(void)hipMemsetAsync(count, 0, (size_t)nv * 4, st);
@@ -295,12 +229,6 @@ __global__ __launch_bounds__(256) void k_cc_roots(const uint32_t *label, uint32_
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) flag[i] = label[i] == i ? 1u : 0u;
 }
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
-{
-	for (int d = 32; d; d >>= 1) { const unsigned long long o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-	return v;
-}
 // spans: the start-face sequence as (lowest face, highest face, position of the span's first face, ascending?) sorted by the
 // lowest face (host/cbm_walk.cpp: StartFaces::index_blocks); label[] holds a face's root on entry, its component number on exit
 __global__ __launch_bounds__(256) void k_cc_face_stats(ConnView cv, uint32_t *label, const uint32_t *num, const uint32_t *spans, uint32_t nspans,
@@ -335,7 +263,7 @@ __global__ __launch_bounds__(256) void k_cc_face_stats(ConnView cv, uint32_t *la
 		const bool mine = valid && c == c0;
 		const unsigned long long mask = __ballot(mine);
 		const uint32_t n = (uint32_t)__popcll(mask), sdeg = wave_sum(mine ? deg : 0u);
-		const unsigned long long kmin = wave_min64(mine ? key : ~0ull);
+		const unsigned long long kmin = wave_min(mine ? key : ~0ull);
 		const int last = 63 - __clzll((long long)mask);
 		const uint32_t f_first = (uint32_t)__shfl((int)f, leader, 64), f_last = (uint32_t)__shfl((int)f, last, 64);
 		if (lane == leader) {
@@ -386,8 +314,7 @@ __global__ __launch_bounds__(256) void k_cc_vertex_ties(ConnView cv, const uint3
 	const uint32_t k = live ? rank_of[comp[f]] : 0u;
 	const uint32_t h0 = !live ? 0u : cv.eface ? cv.foff[f] : f * cv.udeg, h1 = !live ? 0u : cv.eface ? cv.foff[f + 1] : h0 + cv.udeg;
 	const int lane = threadIdx.x & 63;
-	uint32_t rounds = h1 - h0;
-	for (int d = 32; d; d >>= 1) rounds = max(rounds, (uint32_t)__shfl_xor((int)rounds, d, 64));
+	const uint32_t rounds = wave_max(h1 - h0);
 	for (uint32_t i = 0; i < rounds; ++i) {
 		const uint32_t h = h0 + i;
 		const uint32_t first = h < h1 ? vfirst[cv.org[h]] : k;
@@ -452,13 +379,13 @@ __global__ __launch_bounds__(256) void k_cc_vertex_stats(const uint32_t *vfirst,
 }
 
 constexpr uint32_t kTiePairs = 1u << 22;   // capacity of the tie list (8 bytes each; the configs[3] mesh at 100 M triangles notes 0.9 M)
-size_t components_workspace_bytes(uint32_t nv, uint32_t nf) { return ((size_t)3 * nf + nv + blocks_for(nf, kScanBlock) + 16) * 4 + (size_t)kTiePairs * 8 + kTieLists * 4 + 64; }
+size_t components_workspace_bytes(uint32_t nv, uint32_t nf) { return ((size_t)3 * nf + nv + scan_sums_words(nf) + 16) * 4 + (size_t)kTiePairs * 8 + kTieLists * 4 + 64; }
 // where everything lies in that workspace -- the ONE place that knows (the driver, analysis.cpp, asks here)
 ComponentsWorkspace components_workspace(void *ws, uint32_t nv, uint32_t nf)
 {
 	ComponentsWorkspace w;
 	w.label = (uint32_t*)ws; w.flag = w.label + nf; w.num = w.flag + nf; w.sums = w.num + nf + 1;
-	w.vfirst = w.sums + blocks_for(nf, kScanBlock) + 8;
+	w.vfirst = w.sums + scan_sums_words(nf);
 	// the tie lists behind the vertex words, 8-byte aligned; their counters (kTieLists words) in front of them
 	w.tie_count = (uint32_t*)(((uintptr_t)(w.vfirst + nv) + 7) & ~(uintptr_t)7);
 	w.tie_pairs = w.tie_count + kTieLists;
