@@ -868,6 +868,11 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		cx.stage_put("vplanes", cx.d_vplanes.p, (size_t)vc * ldv.nplanes);
 		cx.stage_put("fplanes", cx.d_fplanes.p, (size_t)fc * ldf.nplanes);
 		cx.stage_put("d_twin", cx.d_twin.p, (size_t)(in_place ? in_place->whole->ne() : m.ne()) * 4);   // the twins the prediction's fan walks followed
+		// which coder ran: streams, k_chunk_model + k_chunk_ranges (1) or k_chunk_encode (0), the largest total a stream reaches
+		uint64_t top = 0;
+		for (uint32_t i = 0; i < ns; ++i) top = std::max(top, (uint64_t)jobs[i].t0 + jobs[i].n);
+		const uint32_t plan[3] = { ns, split_kernels ? 1u : 0u, (uint32_t)top };
+		cx.stage_put_host("enc_plan", plan, sizeof plan);
 	}
 	cx.timing.k_predict_ms = cx.elapsed(1, 2);
 	cx.timing.k_entropy_ms = cx.elapsed(3, 4);

@@ -902,6 +902,7 @@ static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, 
 	// lanes, a few thousand long ones (a container written with 128 Ki-symbol chunks: 5 200 attribute streams) stay with a wave each.
 	static const uint64_t lanes_mode = env_uint("HRY_DECODE_LANES", 2);
 	const std::vector<StreamJob> &jobs = sp.jobs;
+	std::vector<uint32_t> plan;   // keep_stages: a row per decode_streams -- streams, streams given to the lanes, their counts 16 bits wide
 	auto decode_streams = [&](hipStream_t st, uint32_t first, uint32_t n, uint32_t n_for_lanes) {
 		bool lanes = lanes_mode == 1;
 		// (16-bit counts where no stream's total passes 65535: 32 KB a lane-wave, five of them a compute unit; HRY_DECODE_COUNTS32: never)
@@ -918,6 +919,7 @@ static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, 
 			lanes = t_lanes < t_waves;
 		}
 		const uint32_t nl = lanes ? n_for_lanes : 0u;
+		if (cx.keep_stages) plan.insert(plan.end(), { n, nl, nl && counts16 ? 1u : 0u });
 		if (nl) launch_chunk_decode_lanes(st, cx.d_cjobs.as<StreamJob>() + first, nl, cx.d_init.as<uint32_t>(), cx.d_magic.as<MagicEnt>(), cx.d_cout.as<uint8_t>(),
 		                                  cx.d_coffs.as<uint64_t>() + first, cx.d_csizes.as<uint32_t>() + first, counts16);
 		if (n > nl) launch_chunk_decode(st, cx.d_cjobs.as<StreamJob>() + first + nl, n - nl, cx.d_init.as<uint32_t>(), cx.d_magic.as<MagicEnt>(), cx.d_cout.as<uint8_t>(),
@@ -970,6 +972,7 @@ static void decode_streams_conn_first(Context &cx, const ChunkedDirectory &dir, 
 	HIP_OK(hipEventRecord(cx.ev_x[0], cx.stream3));
 	if (trace_on()) { HIP_OK(hipEventSynchronize(cx.ev[2])); HRY_MARK(g_t0, "connectivity streams decoded"); }
 	HIP_OK(hipStreamSynchronize(cx.stream));
+	cx.stage_put_host("dec_plan", plan.data(), plan.size() * 4);   // (the first row: the connectivity streams' launch)
 }
 
 // the cut-border machine replayed on the host, then the attributes reconstructed: general bindings, the pipelined decode, or the

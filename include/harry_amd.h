@@ -542,7 +542,8 @@ int hry_decode_sharded(hry_ctx *const *ctx, int n_ctx, const uint8_t *hry, size_
 int hry_container_check(const uint8_t *hry, size_t n, int *complete);
 
 /* ---- stage-level access for parity tests (valid after hry_encode/hry_decode with keep_stages) ----- */
-/* names: "order_v","order_f","twin","vplanes","fplanes","rec","sym_l","r","S","payload", ... */
+/* names: "order_v","order_f","twin","vplanes","fplanes","rec","sym_l","r","S","payload","dec_syms","dec_nsym","enc_plan","dec_plan",
+ * ... */
 int hry_stage_get(hry_ctx *ctx, const char *name, void **host_copy, size_t *bytes);
 
 /* host-only: the sequential cut-border walk of the encoder (cbm::encode, cbm/encoder.h:54-217) with a recording
