@@ -42,7 +42,11 @@ struct Border {
 	Part &top() { return parts.back(); }
 	Node &N(int32_t i) { return P[i]; }
 
-	int32_t make(uint32_t v, uint32_t a)
+	// (forced inline: the compiler's own choice was to inline it into the walking thread's loop of the two-core walk and nowhere else,
+	// and it stopped doing that when the lean loops became one template.  Single-stepped walks of a 30 x 30 torus, 1 799 operations,
+	// instructions with the call / inlined -- triangles 287 437 / 271 657, with the operation model 490 419 / 466 392, two-core walking
+	// thread 299 070 / 271 540, quads 320 956 / 286 079, mixed polygons 445 988 / 414 034)
+	__attribute__((always_inline)) int32_t make(uint32_t v, uint32_t a)
 	{
 		int32_t i = free_head;
 		if (i >= 0) free_head = P[i].next;
@@ -539,160 +543,128 @@ static void walk_component(Mesh &m, WalkState &st, const uint32_t *eface_tab, ui
 	}
 }
 
-// The same component walk for the case that carries the headline workload: every polygon is a triangle and the operation model
-// is not evaluated (chunked profile).  Hardware counters on the generic loop (EPYC 9575F, HRY_PERF=1): 228 instructions per
-// triangle at 3.9 per cycle, 0.005 branch misses, 0.4 last-level misses -- mostly instruction count.  This loop keeps its
-// cursors and counters in locals (the mark arrays and the operation stream are not character types, so their stores do not
-// force reloads), derives the triangle's edges from one division, loads the gate's neighbours only where an operation needs
-// them, tests connect-forward / -backward before searching the border, and writes the Emitter back once per component.
+// ---------------------------------------------------------------------------------------------------------------------
+// The lean walk: ONE automaton (walk_lean) for the loops that carry the workloads, and sinks for everything the automaton does
+// not decide with.  Hardware counters on the generic loop above (EPYC 9575F, HRY_PERF=1): 228 instructions per triangle at 3.9
+// per cycle, 0.005 branch misses, 0.4 last-level misses -- mostly instruction count; 240 instructions and 108 cycles per triangle
+// on the polygons of the configs[3] share.  The lean loop keeps its cursors and counters in locals (the mark arrays and the
+// operation stream are not character types, so their stores do not force reloads), loads the gate's neighbours only where an
+// operation needs them, tests connect-forward / -backward before searching the border, and writes the Emitter back once per
+// component: 132 instructions per triangle at 3.5 per cycle for triangles.
+//
+// The automaton owns what it decides with: the border, the face marks (gone), which vertices are coded under which number (sent,
+// next_id), how many border elements hold a vertex (on), the twins and their repairs (twin_patches / twins_changed), the number of
+// faces consumed, and when a border snapshot is due.  Everything else -- the operation byte and its model class from the triangle
+// counts per vertex (seen: three read-modify-writes per triangle that only select a class, models.h:101-105), order_v / order_f,
+// the per-class counters, the polygons' triangle counts, the operands of the rare operations, the component marks -- is the
+// sink's: DirectSink writes it where it goes, TraceSink writes an 8-byte record per operation for a second core.
+#define WALK_INLINE inline __attribute__((always_inline))   // (a sink is a local of its loop, all of it in registers: no member may keep its address)
+
+// The eight ways a component starts (encoder.h:68-131), indexed by which of the first face's vertices a, b, c were coded before
+// (bit 2, 1, 0): the initial operation, then a, b, c (0, 1, 2) in the order the stream takes them -- the first n_named are named
+// explicitly, the others are recorded as new.  The automaton numbers the new ones from it, the sink emits from it.
+struct StartCase { uint8_t iop, n_named, order[3]; };
+constexpr StartCase kStartCases[8] = {
+	{ I_INIT, 0, { 0, 1, 2 } },   { I_TRI001, 1, { 2, 0, 1 } }, { I_TRI010, 1, { 1, 2, 0 } }, { I_TRI011, 2, { 1, 2, 0 } },
+	{ I_TRI100, 1, { 0, 1, 2 } }, { I_TRI101, 2, { 2, 0, 1 } }, { I_TRI110, 2, { 0, 1, 2 } }, { I_TRI111, 3, { 0, 1, 2 } },
+};
+
+// The outputs of a walk, written where they go.  Symbol order: operation, its operands, the polygon's triangle count (io.h:162-165:
+// it follows the first operation of the polygon), then the triangle counts per vertex, then order_f.
 template <bool MODEL>   // MODEL: the operation model of the reference stream is evaluated per operation (compat profile), through the Emitter
-static void walk_component_tri(Mesh &m, WalkState &st, uint32_t f, Border &cb, Emitter &em, uint32_t &next_id_io, uint32_t &consumed_io)
-{
-	WalkResult &w = em.w;
-	const uint32_t *org = m.org.data();
-	uint32_t *twin = m.twin.data();
-	Gone *gone = st.gone.data();
-	uint32_t *sent = st.sent.data();
-	uint16_t *seen = st.seen.data();
-	OnCount *on = st.on.data();
-	uint32_t next_id = next_id_io, consumed = consumed_io;
-	OpByte *opc = em.op_cur;
-	uint32_t *ovc = em.ov_cur, *ofc = em.of_cur;
-	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_ops = 0;
-	bool changed = false;
-	std::vector<uint32_t> &tp = w.twin_patches;   // half-edges whose twin this walk changes (rare: non-manifold edges, consumed neighbours)
-	// prefetch: the twins of the triangle's other edges and the faces behind them (1 M triangles: 7.8 -> 7.4 ms; 28 M, beyond the
-	// caches: 293 -> 237 ms)
-	auto emit = [&](uint32_t s, uint32_t order) {
+struct DirectSink {
+	Emitter &em;
+	// read only for vertices that had their number before the call that names them (named start vertices, O_NM), never for the one an
+	// O_NEWVTX introduces.  On the expanding thread that is what makes the reads safe: the walking thread numbers a vertex BEFORE it
+	// writes the record of its operation, and a record is published (release) after everything written before it
+	const uint32_t *const sent;
+	uint16_t *const seen;
+	const bool nt_coded;
+	OpByte *opc;
+	uint32_t *ovc, *ofc, *ntc, *ntp;
+	// since begin(): operations per class, and symbols the Emitter has not counted yet.  The eight counters are an array of the sink's
+	// USER (all zero when the sink is made; end() adds them to the Emitter's and zeroes them again): an array inside the sink, indexed
+	// by the class, keeps the compiler from taking the sink apart into registers -- every cursor then lives in memory, and the walk of
+	// mixed polygons ran 9 instructions per triangle longer (single-stepped: 451 283 against the parent's 435 252 for 1 799 operations)
+	uint32_t *const n_op;
+	uint32_t n_ops = 0;
+
+	WALK_INLINE DirectSink(Emitter &e, WalkState &st, uint32_t (&n_op_)[8]) : em(e), sent(st.sent.data()), seen(st.seen.data()), nt_coded(e.w.numtri_coded), n_op(n_op_) { load(); }
+	WALK_INLINE void load() { opc = em.op_cur; ovc = em.ov_cur; ofc = em.of_cur; ntc = em.nt_cur; ntp = em.ntp_cur; }
+	WALK_INLINE void emit(uint32_t s, uint32_t order)
+	{
 		if (MODEL) { em.op(s, (int)order); return; }
-		uint32_t k = order == 0 ? 0u : order > 8u ? 7u : order - 1u;   // models.h:101-105
+		const uint32_t k = order == 0 ? 0u : order > 8u ? 7u : order - 1u;   // models.h:101-105
 		++n_op[k]; ++n_ops;
 		*opc++ = (OpByte)(s | (k << 3));
-	};
-	// rare symbols go through the Emitter (its symbol counter is brought up to date first)
-	auto sync_n = [&] { em.n += n_ops; n_ops = 0; };
-
-	em.mark_component(next_id);
-	gone[f] = Gone::yes; ++consumed;
-	{
-		const uint32_t e0 = 3 * f, e1 = e0 + 1, e2 = e0 + 2;
-		const uint32_t a = org[e0], b = org[e1], c = org[e2];
-		auto rec = [&](uint32_t e) { *ovc++ = e; sent[org[e]] = next_id++; };
-		unsigned mask = (sent[a] != NONE32 ? 4u : 0u) | (sent[b] != NONE32 ? 2u : 0u) | (sent[c] != NONE32 ? 1u : 0u);
-		switch (mask) {   // encoder.h:68-131 (numtri is not coded: one polygon degree)
-		case 7: em.iop(I_TRI111); em.vert(sent[a], seen[a]); em.vert(sent[b], seen[b]); em.vert(sent[c], seen[c]); break;
-		case 6: em.iop(I_TRI110); em.vert(sent[a], seen[a]); em.vert(sent[b], seen[b]); rec(e2); break;
-		case 3: em.iop(I_TRI011); em.vert(sent[b], seen[b]); em.vert(sent[c], seen[c]); rec(e0); break;
-		case 5: em.iop(I_TRI101); em.vert(sent[c], seen[c]); em.vert(sent[a], seen[a]); rec(e1); break;
-		case 4: em.iop(I_TRI100); em.vert(sent[a], seen[a]); rec(e1); rec(e2); break;
-		case 2: em.iop(I_TRI010); em.vert(sent[b], seen[b]); rec(e2); rec(e0); break;
-		case 1: em.iop(I_TRI001); em.vert(sent[c], seen[c]); rec(e0); rec(e1); break;
-		default: em.iop(I_INIT); rec(e0); rec(e1); rec(e2); break;
-		}
-		*ofc++ = e0;
-		++seen[a]; ++seen[b]; ++seen[c];
-		cb.start(a, e0, b, e1, c, e2);
 	}
-	Border::Node *P = cb.P;
-	const uint32_t snap_every = MODEL ? 0u : w.snapshot_faces;
-	uint64_t next_snap = snap_every ? (uint64_t)consumed_io + snap_every : ~0ull;   // (host.hpp BorderSnapshot)
-	while (!cb.parts.empty()) {
-		if (consumed >= next_snap) {
-			next_snap += snap_every;
-			w.snapshots.emplace_back();
-			Emitter::snapshot_border(cb, sent, seen, w.snapshots.back());
-			em.snapshot_cursors(w.snapshots.back(), next_id, consumed - consumed_io, 3u * (consumed - consumed_io), n_op, em.nt_cur);
-		}
-		Border::Part &pt = cb.parts.back();
-		const int32_t tn = pt.tail, hn = pt.head;
-		const uint32_t v0 = P[tn].v, gate = P[tn].a, v1 = P[hn].v;
-		const uint32_t order = seen[v1];
-		const uint32_t t = twin[gate];
-		uint32_t fc = t / 3u;
-		if (t == gate || gone[fc] != Gone::no) {   // writer.cc:48-58: mesh border or neighbour already consumed
-			const Op bop = cb.border();
-			P = cb.P;
-			if (t != gate) { twin[gate] = gate; changed = true; tp.push_back(gate); }   // one-sided split (writer.cc:81-84)
-			emit(bop, order);
-			continue;
-		}
-		gone[fc] = Gone::yes; ++consumed;
-		const uint32_t base = 3u * fc, kk = t - base;
-		const uint32_t e0 = t, e1 = base + (kk == 2u ? 0u : kk + 1u), e2 = base + (kk == 0u ? 2u : kk - 1u);
-		const uint32_t v2 = org[e2];
-		{
-			// the next gate is one of this triangle's other two edges: their twins (this face's line of the twin array) and,
-			// one step further, the faces behind them
-			const uint32_t t1 = twin[e1], t2 = twin[e2];
-			__builtin_prefetch(org + t1); __builtin_prefetch(org + t2);
-		}
-		const bool fresh = sent[v2] == NONE32;
-		if (fresh || on[v2] == 0) {
-			// NEWVTX, or a vertex that was coded before but left the border (non-manifold): encoder.h:167-181
-			P[tn].a = e1;
-			const int32_t nn = cb.make(v2, e2);
-			P = cb.P;
-			cb.append(cb.parts.back(), nn);
-			if (fresh) { emit(O_NEWVTX, order); *ovc++ = e2; sent[v2] = next_id++; }
-			else { emit(O_NM, order); sync_n(); em.vert(sent[v2], seen[v2]); }
-		} else if (pt.edge_begin && P[P[hn].next].v == v2) {
-			// connect forward (or close: the part is exactly this triangle); the triangle's last edge meets the next border edge
-			const bool close = pt.size == 3;
-			const uint32_t gatenext = P[hn].a;
-			if (twin[gatenext] != e2) { twin[gatenext] = e2; twin[e2] = gatenext; changed = true; tp.push_back(gatenext); tp.push_back(e2); }
-			if (close) {
-				const uint32_t gateprev = P[P[tn].prev].a;
-				if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
-				cb.discard_top();
-			} else { cb.drop(cb.unlink_head(pt)); P[pt.tail].a = e1; }
-			emit(O_CONNFWD, order);
-		} else if (P[P[tn].prev].v == v2) {
-			const uint32_t gateprev = P[P[tn].prev].a;
-			if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
-			cb.drop(cb.unlink_tail(pt));
-			P[pt.tail].a = e2;
-			emit(O_CONNBWD, order);
-		} else {
-			int i, p;
-			const int32_t hit = cb.locate(v2, i, p);
-			int32_t g, cp;
-			if (p > 0) {
-				cb.unite(hit, p, g, cp);
-				P = cb.P;
-				emit(O_UNION, order); sync_n(); em.elem(i); em.part(p);
-			} else {
-				cb.split(hit, i, g, cp);
-				P = cb.P;
-				emit(O_SPLIT, order); sync_n(); em.elem(i);
+	// rare symbols go through the Emitter (its symbol counter is brought up to date first)
+	WALK_INLINE void sync_n() { em.n += n_ops; n_ops = 0; }
+
+	// a component starts at face f with the half-edges e and the vertices v; ntri: the first polygon's triangles (0: not coded)
+	WALK_INLINE void begin(uint32_t, unsigned mask, uint32_t next_id, const uint32_t (&e)[3], const uint32_t (&v)[3], uint32_t ntri)
+	{
+		em.mark_component(next_id);
+		const StartCase &sc = kStartCases[mask];
+		em.iop(sc.iop);
+		for (unsigned k = 0; k < sc.n_named; ++k) em.vert(sent[v[sc.order[k]]], seen[v[sc.order[k]]]);
+		em.numtri((int)ntri);
+		load();
+		for (unsigned k = sc.n_named; k < 3; ++k) *ovc++ = e[sc.order[k]];
+		*ofc++ = e[0];
+		++seen[v[0]]; ++seen[v[1]]; ++seen[v[2]];
+	}
+	WALK_INLINE void border(uint32_t v1, uint32_t op) { emit(op, seen[v1]); }
+	// the triangle (v0, v1, v2) behind the gate v0 -> v1, entered through e0 (e1, e2: its other half-edges, e2 starts at v2); i, p:
+	// where a split / union found v2; first: the first triangle of its polygon, which has ntri of them (0: triangles, nothing to code)
+	WALK_INLINE void tri(uint32_t e0, uint32_t, uint32_t e2, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t op, int i, int p, bool first, uint32_t ntri)
+	{
+		emit(op, seen[v1]);
+		if (op == O_NEWVTX) *ovc++ = e2;
+		else if (op == O_NM) { sync_n(); em.vert(sent[v2], seen[v2]); }
+		else if (op == O_UNION) { sync_n(); em.elem(i); em.part(p); }
+		else if (op == O_SPLIT) { sync_n(); em.elem(i); }
+		if (first) {
+			if (ntri && nt_coded) {
+				*ntc++ = (uint32_t)(uint16_t)ntri;
+				if (ntp) { sync_n(); *ntp++ = em.n; }
+				n_ops += kGroupBytes[G_NUMTRI];   // (two places in the symbol sequence)
 			}
-			P[g].a = e1; P[cp].a = e2;
+			*ofc++ = e0;
 		}
 		++seen[v0]; ++seen[v1]; ++seen[v2];
-		*ofc++ = e0;
 	}
-	sync_n();
-	for (int i = 0; i < 8; ++i) em.n_op[i] += n_op[i];
-	em.halfedges += 3 * (consumed - consumed_io);
-	if (!MODEL) em.op_cur = opc;
-	em.ov_cur = ovc; em.of_cur = ofc;
-	if (changed) w.twins_changed = true;
-	next_id_io = next_id; consumed_io = consumed;
-}
+	// the cursors of a border snapshot; the counts since the component's start are relative to its mark (Emitter::snapshot_cursors)
+	WALK_INLINE void cursors(BorderSnapshot &sn, uint32_t next_id, uint32_t faces, uint32_t halfedges) { em.snapshot_cursors(sn, next_id, faces, halfedges, n_op, ntc); }
+	WALK_INLINE void snapshot(const Border &cb, uint32_t next_id, uint32_t faces, uint32_t halfedges)
+	{
+		em.w.snapshots.emplace_back();
+		Emitter::snapshot_border(cb, sent, seen, em.w.snapshots.back());
+		cursors(em.w.snapshots.back(), next_id, faces, halfedges);
+	}
+	// the Emitter's own view of the cursors and counters again (its mark of the next component reads them)
+	WALK_INLINE void end(uint32_t halfedges)
+	{
+		sync_n();
+		for (int i = 0; i < 8; ++i) { em.n_op[i] += n_op[i]; n_op[i] = 0; }
+		em.halfedges += halfedges;
+		if (!MODEL) em.op_cur = opc;
+		em.ov_cur = ovc; em.of_cur = ofc; em.nt_cur = ntc; em.ntp_cur = ntp;
+	}
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The triangle walk on TWO cores (round 5).  The loop above is bound by its instructions (132 per triangle at 3.5 per cycle, no
-// misses to speak of), and a quarter of them decide nothing: the triangle counts per vertex (three read-modify-writes per
-// triangle: they only select an operation's model class, models.h:101-105), the operation byte, the coded-vertex and coded-face
-// entries, the per-class counters.  So the walking thread (A) keeps what the automaton needs -- the border, the face marks, which
-// vertices are coded, the twins -- and writes ONE 8-byte record per operation into a trace: (half-edge the triangle was entered
+// The triangle walk on TWO cores (round 5).  The lean loop is bound by its instructions (132 per triangle at 3.5 per cycle, no
+// misses to speak of), and a quarter of them decide nothing: they are the sink's.  So the walking thread (A) runs the automaton
+// with a TraceSink, which writes ONE 8-byte record per operation into a trace: (half-edge the triangle was entered
 // through | operation) or (head vertex | border operation), plus the rare operands (the split / union position).  A second thread
-// (B) on a core next to it (same last-level cache, not the sibling hardware thread) follows the trace and expands it: the vertices
-// of a triangle are the origins of the entered half-edge's face, in order (the entered half-edge runs against the gate: from its
-// head to its tail), the model class from its own count table, then the operation byte, order_v / order_f, and everything that
-// goes through the Emitter (component marks, initial operations, explicitly named vertices).  The output is what the one-thread
-// loop writes, entry for entry (tests/test_host_cpu.py compares them); A alone measured 7.9 -> 6.0 - 6.4 ms per million
-// triangles on the boxes' EPYC 9575F before B existed (a ring that stays in its cache; 6.9 with one that does not).
-// HRY_WALK_SPLIT=0: the one-thread loop.
+// (B) on a core next to it (same last-level cache, not the sibling hardware thread) follows the trace and hands every record to
+// the DirectSink of the one-thread loop: the vertices of a triangle are the origins of the entered half-edge's face, in order
+// (the entered half-edge runs against the gate: from its head to its tail), the model class from its own count table, then the
+// operation byte, order_v / order_f, and everything that goes through the Emitter (component marks, initial operations,
+// explicitly named vertices).  The output is what the one-thread loop writes, entry for entry (tests/test_host_cpu.py compares
+// them); A alone measured 7.9 -> 6.0 - 6.4 ms per million triangles on the boxes' EPYC 9575F before B existed (a ring that
+// stays in its cache; 6.9 with one that does not).  HRY_WALK_SPLIT=0: the one-thread loop.
 struct WalkTrace {
 	enum { T_TRI = 0, T_BORDER = 1, T_START = 2, T_NEXTID = 3, T_ELEM = 4, T_PART = 5, T_SNAP = 6 };   // code in bits 8..15 of the high word, operation in bits 0..7
 	// a RING of kRing records (8 MB: stays in the two cores' shared cache; until late in round 5 one array for the whole walk,
@@ -730,22 +702,22 @@ static void keep_walk_trace(std::unique_ptr<WalkTrace> t)
 	if (!g_trace_spare) g_trace_spare = std::move(t);
 }
 
-// A: the automaton (the loop of walk_component_tri<false> without what B does)
-static void walk_component_tri_a(Mesh &m, WalkState &st, uint32_t f, Border &cb, WalkResult &w, WalkTrace &tr, size_t &at_io, uint32_t &next_id_io, uint32_t &consumed_io)
-{
-	const uint32_t *org = m.org.data();
-	uint32_t *twin = m.twin.data();
-	Gone *gone = st.gone.data();
-	uint32_t *sent = st.sent.data();
-	OnCount *on = st.on.data();
-	uint32_t next_id = next_id_io, consumed = consumed_io;
-	bool changed = false;
-	std::vector<uint32_t> &tp = w.twin_patches;
-	uint64_t *rec = tr.rec.data();
-	size_t at = at_io, published = at_io;
-	const size_t ring = tr.ring, rmask = tr.mask;
-	size_t room_upto = tr.tail.load(std::memory_order_acquire) + ring;   // records below it may be written
-	auto put = [&](uint64_t r) {
+// A's sink: one component's records into the ring from position `at` on (the walk keeps it between components)
+struct TraceSink {
+	WalkResult &w;
+	WalkTrace &tr;
+	const uint32_t *const sent;
+	uint64_t *const rec;
+	size_t &at_io;
+	size_t at, published;
+	const size_t ring, rmask;
+	size_t room_upto;   // records below it may be written
+	uint32_t next_id0 = 0;
+
+	WALK_INLINE TraceSink(WalkResult &w_, WalkState &st, WalkTrace &t, size_t &at_) : w(w_), tr(t), sent(st.sent.data()), rec(t.rec.data()), at_io(at_), at(at_), published(at_),
+		ring(t.ring), rmask(t.mask), room_upto(t.tail.load(std::memory_order_acquire) + t.ring) {}
+	WALK_INLINE void put(uint64_t r)
+	{
 		if (at >= room_upto) {   // (a ring ahead of the expanding thread)
 			tr.head.store(at, std::memory_order_release); published = at;
 			while (at >= (room_upto = tr.tail.load(std::memory_order_acquire) + ring)) {
@@ -755,88 +727,162 @@ static void walk_component_tri_a(Mesh &m, WalkState &st, uint32_t f, Border &cb,
 		}
 		rec[at++ & rmask] = r;
 		if (at - published >= 256) { tr.head.store(at, std::memory_order_release); published = at; }
-	};
-	gone[f] = Gone::yes; ++consumed;
+	}
+	WALK_INLINE void begin(uint32_t f, unsigned mask, uint32_t next_id, const uint32_t (&)[3], const uint32_t (&)[3], uint32_t)
 	{
-		const uint32_t e0 = 3 * f, e1 = e0 + 1, e2 = e0 + 2;
-		const uint32_t a = org[e0], b = org[e1], c = org[e2];
-		const unsigned mask = (sent[a] != NONE32 ? 4u : 0u) | (sent[b] != NONE32 ? 2u : 0u) | (sent[c] != NONE32 ? 1u : 0u);
+		next_id0 = next_id;
 		put(WalkTrace::make(f, WalkTrace::T_START, 0, mask));
 		put(WalkTrace::make(next_id, WalkTrace::T_NEXTID, 0));
-		auto fresh = [&](uint32_t v) { sent[v] = next_id++; };
-		switch (mask) {   // the order in which the one-thread loop numbers the new vertices (encoder.h:68-131)
-		case 7: break;
-		case 6: fresh(c); break;
-		case 3: fresh(a); break;
-		case 5: fresh(b); break;
-		case 4: fresh(b); fresh(c); break;
-		case 2: fresh(c); fresh(a); break;
-		case 1: fresh(a); fresh(b); break;
-		default: fresh(a); fresh(b); fresh(c); break;
-		}
-		cb.start(a, e0, b, e1, c, e2);
+	}
+	WALK_INLINE void border(uint32_t v1, uint32_t op) { put(WalkTrace::make(v1, WalkTrace::T_BORDER, op)); }
+	WALK_INLINE void tri(uint32_t e0, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t op, int i, int p, bool, uint32_t)
+	{
+		put(WalkTrace::make(e0, WalkTrace::T_TRI, op));
+		if (op == O_UNION || op == O_SPLIT) put(WalkTrace::make((uint32_t)i, WalkTrace::T_ELEM, 0));
+		if (op == O_UNION) put(WalkTrace::make((uint32_t)p, WalkTrace::T_PART, 0));
+	}
+	WALK_INLINE void snapshot(const Border &cb, uint32_t next_id, uint32_t faces, uint32_t halfedges)
+	{
+		// the border is this thread's, the triangle counts and the cursors are the expanding thread's: it completes the
+		// snapshot when it gets to the record (the array does not move: walk_sequential reserved it)
+		if (w.snapshots.size() == w.snapshots.capacity()) throw Error(HRY_E_INTERNAL, "walk: more border snapshots than faces allow");
+		const uint32_t idx = (uint32_t)w.snapshots.size();
+		w.snapshots.emplace_back();
+		BorderSnapshot &sn = w.snapshots.back();
+		Emitter::snapshot_border(cb, sent, nullptr, sn);
+		sn.first_vertex = next_id - next_id0; sn.first_face = faces; sn.first_halfedge = halfedges;
+		put(WalkTrace::make(idx, WalkTrace::T_SNAP, 0));
+	}
+	WALK_INLINE void end(uint32_t)
+	{
+		tr.head.store(at, std::memory_order_release);
+		at_io = at;
+	}
+};
+
+// One connected component, starting at face f: the automaton of walk_component, for a sink.  DEG == 3 (the headline workload):
+// the triangle's edges from one division, no face table, no position inside a polygon.  Other degrees (DEG == 0: mixed, with
+// the half-edge -> face table): a polygon is a fan of triangles around the vertex its gate starts at (encoder.h:133-166); the
+// face's half-edge range stays in locals while its triangles are coded, so "next edge" is a compare instead of two table lookups
+// per step.
+template <int DEG, class Sink>
+static WALK_INLINE void walk_lean(Mesh &m, WalkState &st, const uint32_t *eface_tab, uint32_t f, Border &cb, WalkResult &w, Sink &sink, uint32_t &next_id_io, uint32_t &consumed_io)
+{
+	constexpr bool TRI = DEG == 3;
+	const uint32_t *org = m.org.data();
+	uint32_t *twin = m.twin.data();
+	Gone *gone = st.gone.data();
+	uint32_t *sent = st.sent.data();
+	OnCount *on = st.on.data();
+	uint32_t next_id = next_id_io, consumed = consumed_io;
+	bool changed = false;
+	std::vector<uint32_t> &tp = w.twin_patches;   // half-edges whose twin this walk changes (rare: non-manifold edges, consumed neighbours)
+	auto pair_up = [&](uint32_t x, uint32_t y) __attribute__((always_inline)) { if (twin[x] != y) { twin[x] = y; twin[y] = x; changed = true; tp.push_back(x); tp.push_back(y); } };
+
+	// polygons only (DEG != 3): the face table, the half-edges fb .. fe of the polygon at hand, which of its ntri triangles is next, the
+	// half-edges of the faces coded so far.  For triangles none of it exists: every answer below is a constant.
+	[[maybe_unused]] const uint32_t *foff = nullptr;
+	[[maybe_unused]] uint32_t fb = 0, fe = 0, ntri = 0, curtri = 0, halfedges = 0;
+	auto face_of = [&](uint32_t e) -> uint32_t { if constexpr (DEG != 0) return e / (uint32_t)DEG; else return eface_tab[e]; };
+	auto at_first = [&] { if constexpr (TRI) return true; else return curtri == ntri; };       // the polygon before is finished: the gate leads into the next one
+	auto at_last = [&] { if constexpr (TRI) return true; else return curtri + 1 == ntri; };     // the polygon's last triangle
+	auto ntri_to_code = [&] { if constexpr (TRI) return 0u; else return ntri; };                    // the triangle count to code with a polygon's first operation
+	auto halfedges_now = [&] { if constexpr (TRI) return 3u * (consumed - consumed_io); else return halfedges; };
+
+	gone[f] = Gone::yes; ++consumed;
+	uint32_t e0, e1, e2;
+	if constexpr (TRI) e0 = 3u * f;
+	else {
+		foff = m.face_off.data();
+		fb = foff[f]; fe = foff[f + 1];
+		halfedges = fe - fb;
+		ntri = fe - fb - 2; curtri = 1;
+		e0 = fb;
+	}
+	e1 = e0 + 1; e2 = e0 + 2;
+	{
+		const uint32_t e[3] = { e0, e1, e2 }, v[3] = { org[e0], org[e1], org[e2] };
+		const unsigned mask = (sent[v[0]] != NONE32 ? 4u : 0u) | (sent[v[1]] != NONE32 ? 2u : 0u) | (sent[v[2]] != NONE32 ? 1u : 0u);
+		sink.begin(f, mask, next_id, e, v, ntri_to_code());
+		const StartCase &sc = kStartCases[mask];
+		for (unsigned k = sc.n_named; k < 3; ++k) sent[v[sc.order[k]]] = next_id++;
+		cb.start(v[0], e0, v[1], e1, v[2], e2);
 	}
 	Border::Node *P = cb.P;
 	const uint32_t snap_every = w.snapshot_faces;
 	uint64_t next_snap = snap_every ? (uint64_t)consumed_io + snap_every : ~0ull;   // (host.hpp BorderSnapshot)
 	while (!cb.parts.empty()) {
-		if (consumed >= next_snap) {
-			// the border is this thread's, the triangle counts and the cursors are the expanding thread's: it completes the
-			// snapshot when it gets to the record (the array does not move: walk_sequential reserved it)
+		if (consumed >= next_snap && at_first()) {
 			next_snap += snap_every;
-			if (w.snapshots.size() == w.snapshots.capacity()) throw Error(HRY_E_INTERNAL, "walk: more border snapshots than faces allow");
-			const uint32_t idx = (uint32_t)w.snapshots.size();
-			w.snapshots.emplace_back();
-			BorderSnapshot &sn = w.snapshots.back();
-			Emitter::snapshot_border(cb, sent, nullptr, sn);
-			sn.first_vertex = next_id - next_id_io; sn.first_face = consumed - consumed_io; sn.first_halfedge = 3u * (consumed - consumed_io);
-			put(WalkTrace::make(idx, WalkTrace::T_SNAP, 0));
+			sink.snapshot(cb, next_id, consumed - consumed_io, halfedges_now());
 		}
 		Border::Part &pt = cb.parts.back();
 		const int32_t tn = pt.tail, hn = pt.head;
-		const uint32_t gate = P[tn].a;
-		const uint32_t t = twin[gate];
-		uint32_t fc = t / 3u;
-		if (t == gate || gone[fc] != Gone::no) {   // writer.cc:48-58: mesh border or neighbour already consumed
-			const uint32_t v1 = P[hn].v;
-			const Op bop = cb.border();
-			P = cb.P;
-			if (t != gate) { twin[gate] = gate; changed = true; tp.push_back(gate); }   // one-sided split (writer.cc:81-84)
-			put(WalkTrace::make(v1, WalkTrace::T_BORDER, (uint32_t)bop));
-			continue;
-		}
-		gone[fc] = Gone::yes; ++consumed;
-		const uint32_t base = 3u * fc, kk = t - base;
-		const uint32_t e1 = base + (kk == 2u ? 0u : kk + 1u), e2 = base + (kk == 0u ? 2u : kk - 1u);
+		const uint32_t v0 = P[tn].v, gate = P[tn].a, v1 = P[hn].v;
+		const bool first = at_first();
+		if (first) {
+			const uint32_t t = twin[gate];
+			uint32_t fc;
+			if constexpr (TRI) fc = t / 3u; else fc = t == gate ? 0u : face_of(t);
+			if (t == gate || gone[fc] != Gone::no) {   // writer.cc:48-58: mesh border or neighbour already consumed
+				const Op bop = cb.border();
+				P = cb.P;
+				if (t != gate) { twin[gate] = gate; changed = true; tp.push_back(gate); }   // one-sided split (writer.cc:81-84)
+				sink.border(v1, bop);
+				continue;
+			}
+			gone[fc] = Gone::yes; ++consumed;
+			e0 = t;
+			if constexpr (TRI) {
+				const uint32_t base = 3u * fc, kk = t - base;
+				e1 = base + (kk == 2u ? 0u : kk + 1u); e2 = base + (kk == 0u ? 2u : kk - 1u);
+			} else {
+				fb = foff[fc]; fe = foff[fc + 1];
+				halfedges += fe - fb;
+				ntri = fe - fb - 2; curtri = 0;
+				e1 = t + 1 == fe ? fb : t + 1;
+				// the faces behind this polygon's other edges are the next gates' neighbours: their lines (twins, origins, the
+				// half-edge -> face table) are asked for now -- a component is walked once, every line of it is a miss the first time
+				// (hardware counters on the configs[3] share: 0.44 last-level misses per triangle, IPC 1.6)
+				for (uint32_t h = fb; h < fe; ++h) {
+					const uint32_t o = twin[h];
+					__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
+					if constexpr (DEG == 0) __builtin_prefetch(eface_tab + o);
+				}
+			}
+		} else if constexpr (!TRI) e1 = e1 + 1 == fe ? fb : e1 + 1;
+		if constexpr (!TRI) e2 = e1 + 1 == fe ? fb : e1 + 1;
 		const uint32_t v2 = org[e2];
-		{
+		if constexpr (TRI) {
+			// the next gate is one of this triangle's other two edges: their twins (this face's line of the twin array) and,
+			// one step further, the faces behind them (1 M triangles: 7.8 -> 7.4 ms; 28 M, beyond the caches: 293 -> 237 ms)
 			const uint32_t t1 = twin[e1], t2 = twin[e2];
 			__builtin_prefetch(org + t1); __builtin_prefetch(org + t2);
 		}
+		const uint32_t nt = ntri_to_code();
 		const bool fresh = sent[v2] == NONE32;
 		if (fresh || on[v2] == 0) {
+			// NEWVTX, or a vertex that was coded before but left the border (non-manifold): encoder.h:167-181
 			P[tn].a = e1;
 			const int32_t nn = cb.make(v2, e2);
 			P = cb.P;
 			cb.append(cb.parts.back(), nn);
-			if (fresh) { sent[v2] = next_id++; put(WalkTrace::make(t, WalkTrace::T_TRI, O_NEWVTX)); }
-			else put(WalkTrace::make(t, WalkTrace::T_TRI, O_NM));
+			if (fresh) { sent[v2] = next_id++; sink.tri(e0, e1, e2, v0, v1, v2, O_NEWVTX, 0, 0, first, nt); }   // (numbered before the sink hears of it)
+			else sink.tri(e0, e1, e2, v0, v1, v2, O_NM, 0, 0, first, nt);
 		} else if (pt.edge_begin && P[P[hn].next].v == v2) {
+			// connect forward (or close: the part is exactly this triangle)
 			const bool close = pt.size == 3;
-			const uint32_t gatenext = P[hn].a;
-			if (twin[gatenext] != e2) { twin[gatenext] = e2; twin[e2] = gatenext; changed = true; tp.push_back(gatenext); tp.push_back(e2); }
+			if (at_last()) pair_up(P[hn].a, e2);   // the polygon's last edge meets the next border edge
 			if (close) {
-				const uint32_t gateprev = P[P[tn].prev].a;
-				if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
+				pair_up(P[P[tn].prev].a, e1);
 				cb.discard_top();
 			} else { cb.drop(cb.unlink_head(pt)); P[pt.tail].a = e1; }
-			put(WalkTrace::make(t, WalkTrace::T_TRI, O_CONNFWD));
+			sink.tri(e0, e1, e2, v0, v1, v2, O_CONNFWD, 0, 0, first, nt);
 		} else if (P[P[tn].prev].v == v2) {
-			const uint32_t gateprev = P[P[tn].prev].a;
-			if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
+			pair_up(P[P[tn].prev].a, e1);
 			cb.drop(cb.unlink_tail(pt));
 			P[pt.tail].a = e2;
-			put(WalkTrace::make(t, WalkTrace::T_TRI, O_CONNBWD));
+			sink.tri(e0, e1, e2, v0, v1, v2, O_CONNBWD, 0, 0, first, nt);
 		} else {
 			int i, p;
 			const int32_t hit = cb.locate(v2, i, p);
@@ -844,42 +890,32 @@ static void walk_component_tri_a(Mesh &m, WalkState &st, uint32_t f, Border &cb,
 			if (p > 0) {
 				cb.unite(hit, p, g, cp);
 				P = cb.P;
-				put(WalkTrace::make(t, WalkTrace::T_TRI, O_UNION));
-				put(WalkTrace::make((uint32_t)i, WalkTrace::T_ELEM, 0));
-				put(WalkTrace::make((uint32_t)p, WalkTrace::T_PART, 0));
+				sink.tri(e0, e1, e2, v0, v1, v2, O_UNION, i, p, first, nt);
 			} else {
 				cb.split(hit, i, g, cp);
 				P = cb.P;
-				put(WalkTrace::make(t, WalkTrace::T_TRI, O_SPLIT));
-				put(WalkTrace::make((uint32_t)i, WalkTrace::T_ELEM, 0));
+				sink.tri(e0, e1, e2, v0, v1, v2, O_SPLIT, i, 0, first, nt);
 			}
 			P[g].a = e1; P[cp].a = e2;
 		}
+		if constexpr (!TRI) ++curtri;
 	}
-	tr.head.store(at, std::memory_order_release);
-	at_io = at;
+	sink.end(halfedges_now());
 	if (changed) w.twins_changed = true;
 	next_id_io = next_id; consumed_io = consumed;
 }
 
-// B: follows the trace until A says it is complete; owns the Emitter and the per-vertex triangle counts meanwhile
+// B: follows the trace until A says it is complete and hands every record to the one-thread loop's sink; owns the Emitter and the
+// per-vertex triangle counts meanwhile
 static void walk_trace_expand(const Mesh &m, WalkState &st, Emitter &em, WalkTrace &tr)
 {
 	const uint32_t *org = m.org.data();
-	const uint32_t *sent = st.sent.data();   // (read for vertices that were coded before the record was written: final by then)
-	uint16_t *seen = st.seen.data();
 	const uint64_t *rec = tr.rec.data();
 	const size_t rmask = tr.mask;
 	BorderSnapshot *const snaps = em.w.snapshots.data();   // (reserved before the walk: the walking thread appends, the array stays where it is)
-	OpByte *opc = em.op_cur;
-	uint32_t *ovc = em.ov_cur, *ofc = em.of_cur;
-	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_ops = 0, faces = 0;
-	auto emit = [&](uint32_t s, uint32_t order) {
-		const uint32_t k = order == 0 ? 0u : order > 8u ? 7u : order - 1u;   // models.h:101-105
-		++n_op[k]; ++n_ops;
-		*opc++ = (OpByte)(s | (k << 3));
-	};
-	auto sync_n = [&] { em.n += n_ops; n_ops = 0; };
+	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	DirectSink<false> sink(em, st, n_op);
+	uint32_t faces = 0;   // of the component in hand
 	size_t pos = 0, tail_said = 0;
 	for (;;) {
 		size_t h = tr.head.load(std::memory_order_acquire);
@@ -906,229 +942,66 @@ static void walk_trace_expand(const Mesh &m, WalkState &st, Emitter &em, WalkTra
 				const uint32_t base = 3u * (a / 3u), kk = a - base;
 				const uint32_t e1 = base + (kk == 2u ? 0u : kk + 1u), e2 = base + (kk == 0u ? 2u : kk - 1u);
 				const uint32_t v1 = org[a], v0 = org[e1], v2 = org[e2];
-				const uint32_t order = seen[v1];
-				emit(op, order);
-				if (op == O_NEWVTX) *ovc++ = e2;
-				else if (op == O_NM) { sync_n(); em.vert(sent[v2], seen[v2]); }
-				else if (op == O_UNION) {
-					need(pos + 2);
-					sync_n(); em.elem((int)(int32_t)(uint32_t)rec[pos & rmask]); em.part((int)(uint32_t)rec[(pos + 1) & rmask]);
-					pos += 2;
-				} else if (op == O_SPLIT) {
-					need(pos + 1);
-					sync_n(); em.elem((int)(int32_t)(uint32_t)rec[pos & rmask]);
-					pos += 1;
+				int i = 0, p = 0;
+				if (op == O_UNION || op == O_SPLIT) {
+					const size_t n = op == O_UNION ? 2 : 1;
+					need(pos + n);
+					i = (int)(int32_t)(uint32_t)rec[pos & rmask];
+					if (op == O_UNION) p = (int)(uint32_t)rec[(pos + 1) & rmask];
+					pos += n;
 				}
-				++seen[v0]; ++seen[v1]; ++seen[v2];
-				*ofc++ = a;
+				sink.tri(a, e1, e2, v0, v1, v2, op, i, p, true, 0);
 				++faces;
 			} else if (code == WalkTrace::T_BORDER) {
-				emit(op, seen[a]);
+				sink.border(a, op);
 			} else if (code == WalkTrace::T_START) {
 				need(pos + 1);
 				const uint32_t next_id = (uint32_t)rec[pos++ & rmask];
 				const unsigned mask = (hi >> 16) & 0xffu;
-				// the Emitter's own view of the cursors and counters (its mark of the new component reads them)
-				sync_n();
-				for (int i = 0; i < 8; ++i) { em.n_op[i] += n_op[i]; n_op[i] = 0; }
-				em.halfedges += 3 * faces; faces = 0;
-				em.op_cur = opc; em.ov_cur = ovc; em.of_cur = ofc;
-				em.mark_component(next_id);
-				const uint32_t e0 = 3 * a, e1 = e0 + 1, e2 = e0 + 2;
-				const uint32_t va = org[e0], vb = org[e1], vc = org[e2];
-				auto recv = [&](uint32_t e) { *ovc++ = e; };
-				switch (mask) {   // encoder.h:68-131 (numtri is not coded: one polygon degree)
-				case 7: em.iop(I_TRI111); em.vert(sent[va], seen[va]); em.vert(sent[vb], seen[vb]); em.vert(sent[vc], seen[vc]); break;
-				case 6: em.iop(I_TRI110); em.vert(sent[va], seen[va]); em.vert(sent[vb], seen[vb]); recv(e2); break;
-				case 3: em.iop(I_TRI011); em.vert(sent[vb], seen[vb]); em.vert(sent[vc], seen[vc]); recv(e0); break;
-				case 5: em.iop(I_TRI101); em.vert(sent[vc], seen[vc]); em.vert(sent[va], seen[va]); recv(e1); break;
-				case 4: em.iop(I_TRI100); em.vert(sent[va], seen[va]); recv(e1); recv(e2); break;
-				case 2: em.iop(I_TRI010); em.vert(sent[vb], seen[vb]); recv(e2); recv(e0); break;
-				case 1: em.iop(I_TRI001); em.vert(sent[vc], seen[vc]); recv(e0); recv(e1); break;
-				default: em.iop(I_INIT); recv(e0); recv(e1); recv(e2); break;
-				}
-				*ofc++ = e0;
-				++seen[va]; ++seen[vb]; ++seen[vc];
-				++faces;
+				sink.end(3 * faces);
+				const uint32_t e[3] = { 3 * a, 3 * a + 1, 3 * a + 2 }, v[3] = { org[e[0]], org[e[1]], org[e[2]] };
+				sink.begin(a, mask, next_id, e, v, 0);   // (numtri is not coded: one polygon degree)
+				faces = 1;
 			} else if (code == WalkTrace::T_SNAP) {
 				// a border snapshot of the walking thread: the counts at its vertices and the cursors are this thread's
 				BorderSnapshot &sn = snaps[a];
 				sn.seen.reserve(sn.orig.size());
-				for (const uint32_t v : sn.orig) sn.seen.push_back((uint8_t)std::min<uint32_t>(seen[v], 9u));
+				for (const uint32_t v : sn.orig) sn.seen.push_back((uint8_t)std::min<uint32_t>(sink.seen[v], 9u));
 				std::vector<uint32_t>().swap(sn.orig);
 				if (sn.first_face != faces) throw Error(HRY_E_INTERNAL, "walk trace: a snapshot out of step");
-				em.snapshot_cursors(sn, em.w.marks.back().first_vertex + sn.first_vertex, sn.first_face, sn.first_halfedge, n_op, em.nt_cur);
+				sink.cursors(sn, em.w.marks.back().first_vertex + sn.first_vertex, sn.first_face, sn.first_halfedge);
 			} else throw Error(HRY_E_INTERNAL, "walk trace: stray record");
 		}
 		tr.tail.store(pos, std::memory_order_release);   // (everything below pos has been read: the walking thread may write over it)
 		tail_said = pos;
 	}
-	sync_n();
-	for (int i = 0; i < 8; ++i) em.n_op[i] += n_op[i];
-	em.halfedges += 3 * faces;
-	em.op_cur = opc; em.ov_cur = ovc; em.of_cur = ofc;
+	sink.end(3 * faces);
 }
 
-// The component walk for polygons, written like the triangle loop above (round 4; hardware counters of the generic loop on the
-// configs[3] share: 240 instructions and 108 cycles per triangle).  A polygon is a fan of triangles around the vertex its gate
-// starts at (encoder.h:133-166): the face's half-edge range stays in locals while its triangles are coded, so "next edge" is a
-// compare instead of two table lookups per step; cursors and counters are locals; the gate's neighbours are loaded only by the
-// operations that use them; the triangle count of a polygon goes through a bare cursor (one per coded face, Emitter::nt_cur).
+// Which loop walks a component -- the one place that decides.  generic: the reference-shaped loop (HRY_GENERIC_WALK; polygons
+// whenever the operation model is evaluated: only that loop evaluates it for them); lean_model: triangles with the operation model.
+enum class WalkLoop { generic, lean, lean_model };
 template <int DEG>
-static void walk_component_poly(Mesh &m, WalkState &st, const uint32_t *eface_tab, uint32_t f, Border &cb, Emitter &em, uint32_t &next_id_io, uint32_t &consumed_io)
+static WalkLoop pick_walk_loop(bool eval_op_model)
 {
-	WalkResult &w = em.w;
-	const uint32_t *foff = m.face_off.data();
-	const uint32_t *org = m.org.data();
-	uint32_t *twin = m.twin.data();
-	Gone *gone = st.gone.data();
-	uint32_t *sent = st.sent.data();
-	uint16_t *seen = st.seen.data();
-	OnCount *on = st.on.data();
-	uint32_t next_id = next_id_io, consumed = consumed_io, halfedges = em.halfedges;
-	OpByte *opc = em.op_cur;
-	uint32_t *ovc = em.ov_cur, *ofc = em.of_cur;
-	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_ops = 0;
-	bool changed = false;
-	std::vector<uint32_t> &tp = w.twin_patches;   // half-edges whose twin this walk changes (rare: non-manifold edges, consumed neighbours)
-	const bool nt_coded = w.numtri_coded;
-	auto face_of = [&](uint32_t e) -> uint32_t { return DEG ? e / (uint32_t)(DEG ? DEG : 1) : eface_tab[e]; };
-	auto emit = [&](uint32_t s, uint32_t order) {
-		uint32_t k = order == 0 ? 0u : order > 8u ? 7u : order - 1u;   // models.h:101-105
-		++n_op[k]; ++n_ops;
-		*opc++ = (OpByte)(s | (k << 3));
-	};
-	// rare symbols go through the Emitter (its symbol counter is brought up to date first)
-	auto sync_n = [&] { em.n += n_ops; n_ops = 0; };
-
-	em.mark_component(next_id);
-	gone[f] = Gone::yes; ++consumed;
-	uint32_t fb = foff[f], fe = foff[f + 1];   // the half-edges of the polygon at hand
-	halfedges += fe - fb;
-	uint32_t ntri = fe - fb - 2, curtri = 1;
-	uint32_t e0 = fb, e1 = fb + 1, e2 = fb + 2;
-	{
-		const uint32_t a = org[e0], b = org[e1], c = org[e2];
-		auto rec = [&](uint32_t e) { *ovc++ = e; sent[org[e]] = next_id++; };
-		unsigned mask = (sent[a] != NONE32 ? 4u : 0u) | (sent[b] != NONE32 ? 2u : 0u) | (sent[c] != NONE32 ? 1u : 0u);
-		switch (mask) {   // encoder.h:68-131
-		case 7: em.iop(I_TRI111); em.vert(sent[a], seen[a]); em.vert(sent[b], seen[b]); em.vert(sent[c], seen[c]); em.numtri((int)ntri); break;
-		case 6: em.iop(I_TRI110); em.vert(sent[a], seen[a]); em.vert(sent[b], seen[b]); em.numtri((int)ntri); rec(e2); break;
-		case 3: em.iop(I_TRI011); em.vert(sent[b], seen[b]); em.vert(sent[c], seen[c]); em.numtri((int)ntri); rec(e0); break;
-		case 5: em.iop(I_TRI101); em.vert(sent[c], seen[c]); em.vert(sent[a], seen[a]); em.numtri((int)ntri); rec(e1); break;
-		case 4: em.iop(I_TRI100); em.vert(sent[a], seen[a]); em.numtri((int)ntri); rec(e1); rec(e2); break;
-		case 2: em.iop(I_TRI010); em.vert(sent[b], seen[b]); em.numtri((int)ntri); rec(e2); rec(e0); break;
-		case 1: em.iop(I_TRI001); em.vert(sent[c], seen[c]); em.numtri((int)ntri); rec(e0); rec(e1); break;
-		default: em.iop(I_INIT); em.numtri((int)ntri); rec(e0); rec(e1); rec(e2); break;
-		}
-		*ofc++ = e0;
-		++seen[a]; ++seen[b]; ++seen[c];
-		cb.start(a, e0, b, e1, c, e2);
-	}
-	uint32_t *ntc = em.nt_cur, *ntp = em.ntp_cur;
-	Border::Node *P = cb.P;
-	const uint32_t snap_every = w.snapshot_faces, halfedges0 = em.halfedges;
-	uint64_t next_snap = snap_every ? (uint64_t)consumed_io + snap_every : ~0ull;   // (host.hpp BorderSnapshot)
-	while (!cb.parts.empty()) {
-		if (consumed >= next_snap && curtri == ntri) {
-			next_snap += snap_every;
-			w.snapshots.emplace_back();
-			Emitter::snapshot_border(cb, sent, seen, w.snapshots.back());
-			em.snapshot_cursors(w.snapshots.back(), next_id, consumed - consumed_io, halfedges - halfedges0, n_op, ntc);
-		}
-		Border::Part &pt = cb.parts.back();
-		const int32_t tn = pt.tail, hn = pt.head;
-		const uint32_t v0 = P[tn].v, gate = P[tn].a, v1 = P[hn].v;
-		const uint32_t order = seen[v1];
-		const bool first = curtri == ntri;   // the polygon before is finished: the gate leads into the next one
-		if (first) {
-			const uint32_t t = twin[gate];
-			const uint32_t fc = t == gate ? 0u : face_of(t);
-			if (t == gate || gone[fc] != Gone::no) {   // writer.cc:48-58: mesh border or neighbour already consumed
-				const Op bop = cb.border();
-				P = cb.P;
-				if (t != gate) { twin[gate] = gate; changed = true; tp.push_back(gate); }   // one-sided split (writer.cc:81-84)
-				emit(bop, order);
-				continue;
-			}
-			gone[fc] = Gone::yes; ++consumed;
-			fb = foff[fc]; fe = foff[fc + 1];
-			halfedges += fe - fb;
-			ntri = fe - fb - 2; curtri = 0;
-			e0 = t;
-			e1 = t + 1 == fe ? fb : t + 1;
-			// the faces behind this polygon's other edges are the next gates' neighbours: their lines (twins, origins, the
-			// half-edge -> face table) are asked for now -- a component is walked once, every line of it is a miss the first time
-			for (uint32_t h = fb; h < fe; ++h) {
-				const uint32_t o = twin[h];
-				__builtin_prefetch(twin + o); __builtin_prefetch(org + o);
-				if (!DEG) __builtin_prefetch(eface_tab + o);
-			}
-		} else e1 = e1 + 1 == fe ? fb : e1 + 1;
-		e2 = e1 + 1 == fe ? fb : e1 + 1;
-		const uint32_t v2 = org[e2];
-		const bool fresh = sent[v2] == NONE32;
-		if (fresh || on[v2] == 0) {
-			// NEWVTX, or a vertex that was coded before but left the border (non-manifold): encoder.h:167-181
-			P[tn].a = e1;
-			const int32_t nn = cb.make(v2, e2);
-			P = cb.P;
-			cb.append(cb.parts.back(), nn);
-			if (fresh) { emit(O_NEWVTX, order); *ovc++ = e2; sent[v2] = next_id++; }
-			else { emit(O_NM, order); sync_n(); em.vert(sent[v2], seen[v2]); }
-		} else if (pt.edge_begin && P[P[hn].next].v == v2) {
-			// connect forward (or close: the part is exactly this triangle)
-			const bool close = pt.size == 3;
-			if (curtri + 1 == ntri) {   // the polygon's last triangle: its last edge meets the next border edge
-				const uint32_t gatenext = P[hn].a;
-				if (twin[gatenext] != e2) { twin[gatenext] = e2; twin[e2] = gatenext; changed = true; tp.push_back(gatenext); tp.push_back(e2); }
-			}
-			if (close) {
-				const uint32_t gateprev = P[P[tn].prev].a;
-				if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
-				cb.discard_top();
-			} else { cb.drop(cb.unlink_head(pt)); P[pt.tail].a = e1; }
-			emit(O_CONNFWD, order);
-		} else if (P[P[tn].prev].v == v2) {
-			const uint32_t gateprev = P[P[tn].prev].a;
-			if (twin[gateprev] != e1) { twin[gateprev] = e1; twin[e1] = gateprev; changed = true; tp.push_back(gateprev); tp.push_back(e1); }
-			cb.drop(cb.unlink_tail(pt));
-			P[pt.tail].a = e2;
-			emit(O_CONNBWD, order);
-		} else {
-			int i, p;
-			const int32_t hit = cb.locate(v2, i, p);
-			int32_t g, cp;
-			if (p > 0) {
-				cb.unite(hit, p, g, cp);
-				P = cb.P;
-				emit(O_UNION, order); sync_n(); em.elem(i); em.part(p);
-			} else {
-				cb.split(hit, i, g, cp);
-				P = cb.P;
-				emit(O_SPLIT, order); sync_n(); em.elem(i);
-			}
-			P[g].a = e1; P[cp].a = e2;
-		}
-		if (first) {
-			if (nt_coded) {   // io.h:162-165: the triangle count follows the first operation of the polygon and its operands
-				*ntc++ = (uint32_t)(uint16_t)ntri;
-				if (ntp) { sync_n(); *ntp++ = em.n; }
-				n_ops += kGroupBytes[G_NUMTRI];   // (two places in the symbol sequence)
-			}
-			*ofc++ = e0;
-		}
-		++seen[v0]; ++seen[v1]; ++seen[v2];
-		++curtri;
-	}
-	sync_n();
-	for (int i = 0; i < 8; ++i) em.n_op[i] += n_op[i];
-	em.halfedges = halfedges;
-	em.op_cur = opc; em.ov_cur = ovc; em.of_cur = ofc;
-	em.nt_cur = ntc; em.ntp_cur = ntp;
-	if (changed) w.twins_changed = true;
-	next_id_io = next_id; consumed_io = consumed;
+	if (env_on("HRY_GENERIC_WALK")) return WalkLoop::generic;
+	if (!eval_op_model) return WalkLoop::lean;
+	return DEG == 3 ? WalkLoop::lean_model : WalkLoop::generic;
 }
+// trace: the ring of the walk on two cores (triangles, WalkLoop::lean), *trace_at: how far it has been written
+template <int DEG>
+static void walk_one_component(WalkLoop loop, Mesh &m, WalkState &st, const uint32_t *eface_tab, uint32_t f, Border &cb, Emitter &em, WalkTrace *trace, size_t *trace_at,
+                               uint32_t &next_id, uint32_t &consumed)
+{
+	uint32_t n_op[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // (DirectSink's)
+	if constexpr (DEG == 3) {
+		if (loop == WalkLoop::lean && trace) { TraceSink sink(em.w, st, *trace, *trace_at); walk_lean<3>(m, st, nullptr, f, cb, em.w, sink, next_id, consumed); return; }
+		if (loop == WalkLoop::lean_model) { DirectSink<true> sink(em, st, n_op); walk_lean<3>(m, st, nullptr, f, cb, em.w, sink, next_id, consumed); return; }
+	}
+	if (loop == WalkLoop::lean) { DirectSink<false> sink(em, st, n_op); walk_lean<DEG>(m, st, eface_tab, f, cb, em.w, sink, next_id, consumed); }
+	else walk_component<DEG>(m, st, eface_tab, f, cb, em, next_id, consumed);
+}
+#undef WALK_INLINE
 
 // the walk is over, every mark has its final counts: the snapshots' cursors from "since my component's mark" to absolute
 static void finish_snapshots(WalkResult &w)
@@ -1169,7 +1042,7 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 	mark("(sequential part) start faces and output planes");
 	uint32_t next_id = 0, consumed = 0;
 	const bool count = env_on("HRY_PERF");   // hardware counters of this thread around the first component's walk
-	// the triangle walk on two cores (walk_component_tri_a / walk_trace_expand above): large triangle meshes of the chunked profile
+	// the triangle walk on two cores (TraceSink / walk_trace_expand above): large triangle meshes of the chunked profile
 	struct Split {
 		std::unique_ptr<WalkTrace> trace;
 		size_t at = 0;
@@ -1190,18 +1063,14 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 	} split;
 	const uint64_t split_env = env_uint("HRY_WALK_SPLIT", 1u << 17);   // 0: never; n: from n faces (read per call: the tests change it)
 	const uint32_t split_min_faces = split_env == 0 ? 0xffffffffu : (uint32_t)std::min<uint64_t>(split_env, 0xffffffffu);
-	const bool want_split = DEG == 3 && !eval_op_model && !env_on("HRY_GENERIC_WALK") && !count && n_threads > 1 && m.nf >= split_min_faces;
+	const WalkLoop loop = pick_walk_loop<DEG>(eval_op_model);
+	const bool want_split = DEG == 3 && loop == WalkLoop::lean && !count && n_threads > 1 && m.nf >= split_min_faces;
 	do {
 		uint32_t f = pool.next();
-		const bool lean = DEG == 3 && !env_on("HRY_GENERIC_WALK");
-		const bool lean_poly = DEG != 3 && !eval_op_model && !env_on("HRY_GENERIC_WALK");   // (the generic loop evaluates the operation model)
 		if (count && consumed == 0) {
 			PerfCounters pc;
 			pc.start();
-			if (lean && eval_op_model) walk_component_tri<true>(m, st, f, cb, em, next_id, consumed);
-			else if (lean) walk_component_tri<false>(m, st, f, cb, em, next_id, consumed);
-			else if (lean_poly) walk_component_poly<DEG>(m, st, eface_tab, f, cb, em, next_id, consumed);
-			else walk_component<DEG>(m, st, eface_tab, f, cb, em, next_id, consumed);
+			walk_one_component<DEG>(loop, m, st, eface_tab, f, cb, em, nullptr, nullptr, next_id, consumed);
 			pc.stop();
 			pc.report(eval_op_model ? "cut-border walk (with the operation model)" : "cut-border walk", (double)(em.halfedges - 2.0 * consumed));
 			continue;
@@ -1216,13 +1085,10 @@ static void walk_sequential(Mesh &m, WalkResult &w, const uint32_t *eface_tab, b
 				});
 				split.running = true;
 			}
-			try { walk_component_tri_a(m, st, f, cb, w, *split.trace, split.at, next_id, consumed); }
+			try { walk_one_component<DEG>(loop, m, st, eface_tab, f, cb, em, split.trace.get(), &split.at, next_id, consumed); }
 			catch (...) { split.stop(); split.expander.rethrow(); throw; }   // (the expanding thread's failure is the cause, where there is one)
 		}
-		else if (lean && eval_op_model) walk_component_tri<true>(m, st, f, cb, em, next_id, consumed);
-		else if (lean) walk_component_tri<false>(m, st, f, cb, em, next_id, consumed);
-		else if (lean_poly) walk_component_poly<DEG>(m, st, eface_tab, f, cb, em, next_id, consumed);
-		else walk_component<DEG>(m, st, eface_tab, f, cb, em, next_id, consumed);
+		else walk_one_component<DEG>(loop, m, st, eface_tab, f, cb, em, nullptr, nullptr, next_id, consumed);
 		// The operation model of the reference stream adapts across the whole file (models.h:49-120), so a walk that evaluates
 		// it is one sequence.  Without it (chunked profile: symbol + order class only) the remaining components are walked on
 		// several threads once the first one shows that the mesh has more than one.
@@ -1617,7 +1483,7 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 	for (uint32_t k = 0; k < ncomp; ++k) { off_v[k + 1] = off_v[k] + A.fresh[k]; off_f[k + 1] = off_f[k] + A.n_faces[k]; off_he[k + 1] = off_he[k] + A.n_halfedges[k]; }
 	w.order_v.resize(off_v[ncomp]); w.order_f.resize(off_f[ncomp]);
 	// the polygons' triangle counts: one per coded face, so they have their place like order_f (positions: thread-local, moved below)
-	const bool generic = env_on("HRY_GENERIC_WALK");
+	const WalkLoop loop = pick_walk_loop<DEG>(false);   // (components on several threads: the operation model is not evaluated)
 	const size_t nt0 = w.grp_val[G_NUMTRI].size();
 	const bool nt_pos = w.numtri_coded && w.numtri_positions;
 	if (w.numtri_coded) { w.grp_val[G_NUMTRI].resize(nt0 + (off_f[ncomp] - off_f[0])); if (nt_pos) w.grp_pos[G_NUMTRI].resize(nt0 + (off_f[ncomp] - off_f[0])); }
@@ -1672,9 +1538,7 @@ static void walk_components_parallel(Mesh &m, WalkState &st, const uint32_t *efa
 				}
 				em.halfedges = (uint32_t)off_he[k];
 				uint32_t next_id = id_base[k], consumed = 0;
-				if (DEG == 3 && !generic) walk_component_tri<false>(m, st, A.seed[k], cb, em, next_id, consumed);
-				else if (!generic) walk_component_poly<DEG>(m, st, eface_tab, A.seed[k], cb, em, next_id, consumed);
-				else walk_component<DEG>(m, st, eface_tab, A.seed[k], cb, em, next_id, consumed);
+				walk_one_component<DEG>(loop, m, st, eface_tab, A.seed[k], cb, em, nullptr, nullptr, next_id, consumed);
 				if (next_id != id_base[k + 1] || consumed != nfc || em.ov_cur != em.ov_begin + off_v[k + 1] || em.of_cur != em.of_begin + off_f[k + 1] ||
 				    em.halfedges != (uint32_t)off_he[k + 1] || (size_t)(em.op_cur - T.cur) > cap ||
 				    (w.numtri_coded && em.nt_cur != em.nt_begin + nt0 + (off_f[k + 1] - off_f[0])))

@@ -441,28 +441,34 @@ def test_lean_triangle_replay_equals_generic_replay(case, threads, monkeypatch):
 @pytest.mark.parametrize("case", ["torus", "open_grid", "ico", "multi_nm", "tiny"] + list(POLY_CASES))
 @pytest.mark.parametrize("threads", [1, 4])
 def test_lean_triangle_walk_equals_generic_walk(case, threads, monkeypatch):
-    """cbm_walk.cpp: walk_component_tri (the headline encode's loop) against the generic walk_component: same order, same
-    symbols, same repaired twins."""
+    """cbm_walk.cpp: walk_lean with a DirectSink (triangles: the headline encode's loop; polygons) against the generic
+    walk_component: same order, same symbols, same repaired twins.  The triangle cases also with the operation model of the
+    reference stream (DirectSink<true>): every array, op_l / op_h / op_t / op_pos included."""
     mesh = {"torus": lambda: mg.torus(40, 36), "open_grid": lambda: mg.grid(31, 17), "ico": lambda: mg.icosphere(4),
             "multi_nm": lambda: mg.with_nonmanifold(mg.multi_component(6, 9, 10, polys="tri"), 7, 4), "tiny": lambda: mg.grid(2), **POLY_CASES}[case]()
     monkeypatch.setenv("HRY_HOST_THREADS", str(threads))
     monkeypatch.setenv("HRY_PARALLEL_MIN_FACES", "1")
-    out = []
-    for generic in (False, True):
-        if generic:
-            monkeypatch.setenv("HRY_GENERIC_WALK", "1")
-        m = hc.Mesh.from_arrays(mesh.verts, mesh.degrees, mesh.indices)
-        w = m.host_walk(plain=True)
-        out.append((w, m.twin()))
-    for k in out[0][0]:
-        assert np.array_equal(out[0][0][k], out[1][0][k]), k
-    assert np.array_equal(out[0][1], out[1][1])
+    for plain in (True,) if case in POLY_CASES else (True, False):
+        monkeypatch.delenv("HRY_GENERIC_WALK", raising=False)
+        out = []
+        for generic in (False, True):
+            if generic:
+                monkeypatch.setenv("HRY_GENERIC_WALK", "1")
+            m = hc.Mesh.from_arrays(mesh.verts, mesh.degrees, mesh.indices)
+            w = m.host_walk(plain=plain)
+            out.append((w, m.twin()))
+        for k in out[0][0]:
+            assert np.array_equal(out[0][0][k], out[1][0][k]), (plain, k)
+        assert np.array_equal(out[0][1], out[1][1]), plain
+        if not plain:
+            assert all(len(out[0][0][k]) == len(out[0][0]["op_sym"]) > 0 for k in ("op_l", "op_h", "op_t", "op_pos"))
 
 
 @pytest.mark.parametrize("case", ["torus", "open_grid", "ico", "multi_nm", "multi_shared", "tiny", "torus_big"])
 def test_triangle_walk_on_two_cores_equals_the_one_thread_loop(case, monkeypatch):
-    """cbm_walk.cpp, round 5: the walking thread writes a trace of its decisions, a second thread expands it into the operation
-    bytes, order_v / order_f, the marks and the explicitly named vertices -- entry for entry what the one-thread loop writes
+    """cbm_walk.cpp, round 5: the walking thread runs walk_lean with a TraceSink (a record per decision), a second thread
+    (walk_trace_expand) hands the records to the one-thread loop's DirectSink: the operation bytes, order_v / order_f, the marks
+    and the explicitly named vertices -- entry for entry what the one-thread loop writes
     (meshes with borders, non-manifold edges and vertices, several components one after the other, components that name each
     other's vertices, splits and unions of the cut-border)."""
     def shared():
