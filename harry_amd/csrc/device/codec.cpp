@@ -432,6 +432,10 @@ dev::RequantPlan requant_plan(const AttrList &L, const std::vector<uint8_t> &to)
 		memcpy(&rc.mn, L.bmin.data() + L.offset[c], kTypeSize[L.type[c]]);
 		memcpy(&rc.scale, scale.data() + L.offset[c], kTypeSize[L.type[c]]);
 		if (L.type[c] != C_FLOAT && L.type[c] != C_DOUBLE && rc.scale == 0) throw Error(HRY_E_UNSUPPORTED, "constant integer component: the reference divides by a zero extent (quant.h:106)");
+		// int / long from the type's least to its greatest value: max - min wraps to -1, and the value 0 (its distance to min wraps to the
+		// type's least value) makes the reference's division overflow: it dies of SIGFPE
+		const bool minus_one = (L.type[c] == C_INT && (int32_t)rc.scale == -1) || (L.type[c] == C_LONG && (int64_t)rc.scale == -1);
+		if (sq == 0 && minus_one) throw Error(HRY_E_UNSUPPORTED, "signed component over its type's whole range: the reference divides by an extent of -1 (quant.h:106)");
 	}
 	return plan;
 }

@@ -44,10 +44,55 @@ HRY_HD float f32_from_ordered(uint32_t o) { return bits<float>(o ^ ((uint32_t)(0
 template <typename T> HRY_HD int width_bits(int q) { return q == 0 ? (int)sizeof(T) * 8 : q; }
 template <typename T> HRY_HD T ones(int nbits) { return nbits == (int)(sizeof(T) * 8) ? T(-1) : T((1 << nbits) - 1); }   // prediction.h:27-31
 
+// ---- the signed integer types (char, short, int, long) ----------------------------------------------------
+// The reference evaluates the expressions below in T itself; for int and long they overflow at the ends of the type, and what
+// its build computes there is the two's-complement wrapped result (tests/golden/kat.json: delta_s, predict_s).  A compiler is
+// free to assume that signed arithmetic does not overflow -- it folds `v0 + d < v0` into `d < 0` -- so sums, differences and
+// shifts are taken in the unsigned type of the same width and converted back; comparisons stay signed.
+template <typename T> struct is_signed_int { static constexpr bool value = !is_fp<T>::value && (T(-1) < T(0)); };
+template <typename T> HRY_HD T wrap_add(T a, T b) { typedef typename word<sizeof(T)>::u U; return (T)(U)((U)a + (U)b); }
+template <typename T> HRY_HD T wrap_sub(T a, T b) { typedef typename word<sizeof(T)>::u U; return (T)(U)((U)a - (U)b); }
+template <typename T> HRY_HD T wrap_twice(T a) { typedef typename word<sizeof(T)>::u U; return (T)(U)((U)a << 1); }
+template <typename T> HRY_HD T fold_signed(const T raw, const T pred, const T top)
+{
+	const T room = wrap_sub(top, pred);
+	if (pred == T(0)) return raw;
+	const T bal = pred < room ? pred : room;
+	const bool below = raw < pred;
+	const T d = below ? wrap_sub(pred, raw) : wrap_sub(raw, pred);
+	if (d > bal) return wrap_add(d, bal);
+	return below ? wrap_sub(wrap_twice(d), T(1)) : wrap_twice(d);
+}
+template <typename T> HRY_HD T unfold_signed(const T code, const T pred, const T top)
+{
+	const T room = wrap_sub(top, pred);
+	if (pred == T(0)) return code;
+	const T pm1 = wrap_sub(pred, T(1));
+	const T bal = pm1 < room ? pm1 : room;
+	if (T(code >> 1) > bal) {
+		if (room >= pred) return wrap_sub(wrap_sub(wrap_add(pred, code), bal), T(1));
+		return wrap_add(wrap_sub(pred, code), bal);
+	}
+	const T flip = (code & 1) ? T(~T(0)) : T(0);
+	return wrap_add(pred, T(T(code >> 1) ^ flip));
+}
+template <typename T> HRY_HD T parallelogram_signed(const T v0, const T v1, const T v2, const T top)
+{
+	if (v1 < v2) {
+		const T d = wrap_sub(v2, v1);
+		if (d > v0) return T(0);
+		return wrap_sub(v0, d);
+	}
+	const T v = wrap_add(v0, wrap_sub(v1, v2));
+	if ((v > top) || (v < v0)) return top;
+	return v;
+}
+
 // balanced residual code of an integer against its prediction (prediction.h:81-99); expressions keep the
 // reference's operand types so that promotion and truncation are identical for every width
 template <typename T> HRY_HD T fold_int(const T raw, const T pred, int nbits)
 {
+	if constexpr (is_signed_int<T>::value) return fold_signed<T>(raw, pred, ones<T>(nbits));
 	const T room = ones<T>(nbits) - pred;
 	if (pred == T(0)) return raw;
 	const T bal = T(pred) < room ? T(pred) : room;
@@ -63,6 +108,7 @@ template <typename T> HRY_HD T fold_int(const T raw, const T pred, int nbits)
 // inverse (prediction.h:46-64)
 template <typename T> HRY_HD T unfold_int(const T code, const T pred, int nbits)
 {
+	if constexpr (is_signed_int<T>::value) return unfold_signed<T>(code, pred, ones<T>(nbits));
 	const T room = ones<T>(nbits) - pred;
 	if (pred == T(0)) return code;
 	const T pm1 = T(pred - T(1));
@@ -102,6 +148,8 @@ template <typename T> HRY_HD T parallelogram(const T v0, const T v1, const T v2,
 {
 	if constexpr (is_fp<T>::value) {
 		return v0 + (v1 - v2);
+	} else if constexpr (is_signed_int<T>::value) {
+		return parallelogram_signed<T>(v0, v1, v2, ones<T>(width_bits<T>(q)));
 	} else {
 		const T top = ones<T>(width_bits<T>(q));
 		if (v1 < v2) {

@@ -11,7 +11,19 @@
 namespace hry {
 namespace dev {
 
-template <typename T> __device__ __forceinline__ T rescale_int(T val, T from, T to) { return val / from * to + val % from * to / from; }   // quant.h:103-107
+// quant.h:103-107: val / from * to + val % from * to / from, in the type C++ evaluates it in (int for the 1- and 2-byte types).
+// The products and the sum overflow that type for `ushort` at 16 bits (65 534 * 65 535 in int) and for `int` / `long` over most of
+// their range; the reference's build wraps them and divides the wrapped product as a signed number.  A compiler that takes signed
+// overflow for impossible divides it unsigned, so they are taken in the unsigned type and converted back.
+template <typename T> __device__ __forceinline__ T rescale_int(T val, T from, T to)
+{
+	typedef decltype(val * to) P;
+	typedef typename cm::word<sizeof(P)>::u U;
+	const P v = val, f = from, t = to;
+	const P whole = (P)((U)(v / f) * (U)t);
+	const P part = (P)((U)(v % f) * (U)t) / f;
+	return (T)(P)((U)whole + (U)part);
+}
 
 template <typename T> __device__ __forceinline__ T rescale_fp(T val, T from, T to) { return val / from * to; }   // quant.h:98-102 (every operation rounded on its own)
 
@@ -24,9 +36,9 @@ __device__ __forceinline__ uint64_t dequantise_bits(uint64_t q, const RequantCom
 	case 0: return cm::bits<uint32_t>(rescale_fp<float>((float)q, (float)sl, cm::bits<float>((uint32_t)c.scale)) + cm::bits<float>((uint32_t)c.mn));
 	case 1: return cm::bits<uint64_t>(rescale_fp<double>((double)q, (double)sl, cm::bits<double>(c.scale)) + cm::bits<double>(c.mn));
 	case 2: return rescale_int<uint64_t>(q, (uint64_t)sl, c.scale) + c.mn;
-	case 3: return (uint64_t)(rescale_int<int64_t>((int64_t)q, (int64_t)sl, (int64_t)c.scale) + (int64_t)c.mn);
+	case 3: return (uint64_t)rescale_int<int64_t>((int64_t)q, (int64_t)sl, (int64_t)c.scale) + c.mn;   // (the sum wraps)
 	case 4: return (uint32_t)(rescale_int<uint32_t>((uint32_t)q, (uint32_t)sl, (uint32_t)c.scale) + (uint32_t)c.mn);
-	case 5: return (uint32_t)(rescale_int<int32_t>((int32_t)q, (int32_t)sl, (int32_t)c.scale) + (int32_t)c.mn);
+	case 5: return (uint32_t)rescale_int<int32_t>((int32_t)q, (int32_t)sl, (int32_t)c.scale) + (uint32_t)c.mn;
 	case 6: return (uint16_t)(rescale_int<uint16_t>((uint16_t)q, (uint16_t)sl, (uint16_t)c.scale) + (uint16_t)c.mn);
 	case 7: return (uint16_t)(rescale_int<int16_t>((int16_t)q, (int16_t)sl, (int16_t)c.scale) + (int16_t)c.mn);
 	case 8: return (uint8_t)(rescale_int<uint8_t>((uint8_t)q, (uint8_t)sl, (uint8_t)c.scale) + (uint8_t)c.mn);

@@ -187,9 +187,9 @@ __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, i
 				case 0: q = cm::quantise_f32(ldg<float>(slot), cm::bits<float>((uint32_t)c.mn), cm::bits<float>((uint32_t)c.scale), c.dst_bits); break;
 				case 1: q = (uint64_t)(rescale_fp<double>(ldg<double>(slot) - cm::bits<double>(c.mn), cm::bits<double>(c.scale), (double)lv) + 0.5); break;
 				case 2: q = rescale_int<uint64_t>(ldg<uint64_t>(slot) - c.mn, c.scale, (uint64_t)lv); break;
-				case 3: q = (uint64_t)rescale_int<int64_t>(ldg<int64_t>(slot) - (int64_t)c.mn, (int64_t)c.scale, (int64_t)lv); break;
+				case 3: q = (uint64_t)rescale_int<int64_t>((int64_t)(ldg<uint64_t>(slot) - c.mn), (int64_t)c.scale, (int64_t)lv); break;   // (the distance to the minimum wraps)
 				case 4: q = rescale_int<uint32_t>(ldg<uint32_t>(slot) - (uint32_t)c.mn, (uint32_t)c.scale, (uint32_t)lv); break;
-				case 5: q = (uint64_t)rescale_int<int32_t>(ldg<int32_t>(slot) - (int32_t)c.mn, (int32_t)c.scale, (int32_t)lv); break;
+				case 5: q = (uint64_t)rescale_int<int32_t>((int32_t)(ldg<uint32_t>(slot) - (uint32_t)c.mn), (int32_t)c.scale, (int32_t)lv); break;
 				case 6: q = rescale_int<uint16_t>((uint16_t)(ldg<uint16_t>(slot) - (uint16_t)c.mn), (uint16_t)c.scale, (uint16_t)lv); break;
 				case 7: q = (uint64_t)rescale_int<int16_t>((int16_t)(ldg<int16_t>(slot) - (int16_t)c.mn), (int16_t)c.scale, (int16_t)lv); break;
 				case 8: q = rescale_int<uint8_t>((uint8_t)(ldg<uint8_t>(slot) - (uint8_t)c.mn), (uint8_t)c.scale, (uint8_t)lv); break;

@@ -259,7 +259,7 @@ __device__ __forceinline__ T chain_predict_n(uint32_t pk)
 // ---- per-lane evaluation of one vertex with at most two candidates: six source bit patterns -> value bit pattern.
 // Three tiers: unsigned components of at most 16 bits (quantised attributes, the headline case) in trimmed 32-bit
 // arithmetic, float / 32-bit unsigned branch-free, every other type through the generic functions of codec_math.hpp.
-template <typename T> struct LaneEval {
+template <typename T> struct LaneEvalGeneric {
 	typedef typename cm::word<sizeof(T)>::u U;
 	int q;
 	uint32_t nc, code;
@@ -298,6 +298,11 @@ struct UnfoldPre {
 	}
 };
 
+template <typename T> struct LaneEval : LaneEvalGeneric<T> {};
+
+// Stored values in [0, top] only: what the quantiser writes for float and unsigned sources.  (A quantised SIGNED source is
+// different -- the reference rescales it in the signed type, quant.h:149-163, and leaves values above top in the storage word;
+// such components take LaneEvalGeneric: k_unpredict2<T, true>.)
 template <typename T> struct LaneEvalSmall {   // uint8_t / uint16_t
 	uint32_t top;
 	UnfoldPre uf;
@@ -502,7 +507,7 @@ __device__ __forceinline__ uint32_t dense_step(uint32_t (&d)[6], const uint32_t 
 	return out;
 }
 
-template <typename T>
+template <typename T, bool kExact = false>
 __device__ void unpredict2_component(const TopoD &tp, const uint32_t *order_v, uint32_t nvtx_total, uint32_t seg_begin, uint32_t nvtx, const uint32_t *cand, const uint8_t *ncand,
                                      const uint8_t *planes, uint8_t *rec, int stride, int off, int q, int plane0,
                                      typename cm::word<sizeof(T)>::u *ring, uint32_t ring_n, uint32_t *queue, const CrossSync &xs, int comp, uint32_t seg_idx)
@@ -512,7 +517,8 @@ __device__ void unpredict2_component(const TopoD &tp, const uint32_t *order_v, u
 	typedef typename cm::word<sizeof(T)>::u U;
 	typedef typename cm::wide<T>::type W;
 	static_assert(sizeof(T) <= 4, "8-byte components use the generic kernel");
-	constexpr bool kSmallUnsigned = !cm::is_fp<T>::value && sizeof(T) <= 2 && !(T(-1) < T(0));
+	constexpr bool kSmallUnsigned = !kExact && !cm::is_fp<T>::value && sizeof(T) <= 2 && !(T(-1) < T(0));
+	typedef typename std::conditional<kExact, LaneEvalGeneric<T>, LaneEval<T>>::type Eval;
 	const int lane = threadIdx.x;
 	const uint32_t mask = ring_n - 1;
 	// Per-vertex inputs (the ids of the first two candidates, candidate count, residual code) live in REGISTERS, one 64-vertex tile
@@ -690,7 +696,7 @@ __device__ void unpredict2_component(const TopoD &tp, const uint32_t *order_v, u
 					}
 					__builtin_amdgcn_s_waitcnt(0);
 				}
-				LaneEval<T> dev;
+				Eval dev;
 				dev.setup(nc2, code, q);
 				if (nc2 == 1) {   // a lone candidate is both candidates of the short form (the mean of p and p is p)
 #pragma unroll
@@ -838,7 +844,7 @@ __device__ void unpredict2_component(const TopoD &tp, const uint32_t *order_v, u
 				for (int j = 0; j < 3; ++j) { src[3 + j] = lone1 ? src[j] : src[3 + j]; tag[3 + j] = lone1 ? tag[j] : tag[3 + j]; }
 			}
 		}
-		LaneEval<T> ev;
+		Eval ev;
 		ev.setup(nc, code, q);
 		HRY_CLK({ asm volatile("" :: "v"(src[0]), "v"(src[5]), "v"(tag[0])); const unsigned long long n = __builtin_amdgcn_s_memtime(); ck_p2 += n - ck_t; })
 		// ---- chain
@@ -1194,7 +1200,8 @@ struct CompSel { int32_t n; int32_t comp[kMaxComp]; };
 // work lists: block y reconstructs the segments segs[list_off[y] .. list_off[y+1]) one after the other
 
 // one kernel per component type (keeps each instantiation's register allocation to itself: no scratch in the chain)
-template <typename T>
+// kExact: 8- / 16-bit unsigned storage whose values may exceed 2^q - 1, through the generic arithmetic of codec_math.hpp
+template <typename T, bool kExact = false>
 __global__ __launch_bounds__(64) void k_unpredict2(ConnView cv, const uint32_t *order_v, uint32_t nvtx, const uint32_t *cand, const uint8_t *ncand,
                                                    const uint8_t *planes, ListDesc ld, uint8_t *rec, uint32_t ring_bytes, CompSel sel,
                                                    const uint32_t *segs, const uint32_t *list_off, CrossSync xs, uint32_t n_lists)
@@ -1219,7 +1226,7 @@ __global__ __launch_bounds__(64) void k_unpredict2(ConnView cv, const uint32_t *
 		// a chain of this device gave up a wait: no further component is started (the result is an error on the host either way)
 		if (xs.gave_up && __builtin_amdgcn_readfirstlane(__hip_atomic_load(xs.gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) return;
 		if (b < e)
-			unpredict2_component<T>(tp, order_v, nvtx, b, e, cand, ncand, planes, rec, ld.stride, ld.off[c], ld.quant[c], ld.plane[c],
+			unpredict2_component<T, kExact>(tp, order_v, nvtx, b, e, cand, ncand, planes, rec, ld.stride, ld.off[c], ld.quant[c], ld.plane[c],
 			                        (typename cm::word<sizeof(T)>::u*)ring_raw2, ring_bytes / (uint32_t)sizeof(T),
 			                        (uint32_t*)((uint8_t*)ring_raw2 + ring_bytes), xl, c, segs[3 * k + 2]);
 		raise_flag(xs, c, segs[3 * k + 2], e);
@@ -2080,9 +2087,11 @@ uint32_t chain_timeout_flags(hipStream_t st, const uint32_t *gave_up)
 	return f | own;
 }
 uint32_t chain_ring_floor(uint32_t v_begin) { return v_begin > kRing3Near ? v_begin - kRing3Near : 0u; }
+// a quantised component whose source type is signed (long, int, short, char): its stored values are not bounded by 2^q - 1
+static bool beyond_top(const ListDesc &ld, int c) { return ld.quant[c] != 0 && (ld.otype[c] == 3 || ld.otype[c] == 5 || ld.otype[c] == 7 || ld.otype[c] == 9); }
 bool unpredict3_covers(const ListDesc &ld)
 {
-	for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] != 6 && ld.stype[c] != 8) return false;
+	for (int c = 0; c < ld.ncomp; ++c) if ((ld.stype[c] != 6 && ld.stype[c] != 8) || beyond_top(ld, c)) return false;
 	return ld.ncomp > 0;
 }
 void launch_slice_prepare(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, uint32_t *cand, uint8_t *ncand, void *crec)
@@ -2127,7 +2136,7 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 	const CrossSync xs{ seg_start, nseg, done, nullptr, done ? done + (size_t)ld.ncomp * nseg : nullptr };
 	auto go3 = [&](auto kern, int stype) {
 		CompSel sel{};
-		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype) sel.comp[sel.n++] = c;
+		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype && !beyond_top(ld, c)) sel.comp[sel.n++] = c;
 		if (!sel.n) return;
 		hipLaunchKernelGGL(kern, dim3(((n_lists + 7) / 8) * 8 * (uint32_t)sel.n), dim3(64 * std::min(8u, chain_waves(nvtx))), 0, st,   /* (the kernel of many chains keeps its 512 threads: with 1 024 it would not fit its registers) */ cv, order_v, nvtx, (const uint32_t*)cand, (const uint8_t*)ncand, (const ChainRec*)crec, planes, ld, rec, sel,
 		                   segs, list_off, xs, n_lists);
@@ -2138,9 +2147,9 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 	// compute unit: a chain is a lone wavefront that issues an instruction every five or six cycles, two of them on a SIMD hardly
 	// slow each other, and a source older than the ring is simply read from the records
 	const uint32_t ring_bytes = ((uint64_t)n_lists * (uint32_t)ld.ncomp > 1024u ? 16u : 32u) * 1024u, lds_bytes = ring_bytes + 64 * kCandMax * 3 * 4 + 64;   // ring, rows, remembered owners
-	auto go = [&](auto kern, int stype) {
+	auto go = [&](auto kern, int stype, bool exact = false) {
 		CompSel sel{};
-		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype) sel.comp[sel.n++] = c;
+		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype && ((stype == 6 || stype == 8) && beyond_top(ld, c)) == exact) sel.comp[sel.n++] = c;   // exact: 8- / 16-bit storage of a signed source
 		if (!sel.n) return;
 		(void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 		hipLaunchKernelGGL(kern, dim3(((n_lists + 7) / 8) * 8 * (uint32_t)sel.n), dim3(64), lds_bytes, st, cv, order_v, nvtx, (const uint32_t*)cand, (const uint8_t*)ncand, planes, ld, rec, ring_bytes, sel,
@@ -2151,6 +2160,8 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 	go(k_unpredict2<int16_t>, 7); go(k_unpredict2<int8_t>, 9);
 	if (crec) { go3(k_unpredict3<uint16_t>, 6); go3(k_unpredict3<uint8_t>, 8); }
 	else { go(k_unpredict2<uint16_t>, 6); go(k_unpredict2<uint8_t>, 8); }
+	// (32-bit storage of a signed source needs no form of its own: LaneEval<uint32_t> is the reference's arithmetic modulo 2^32)
+	go(k_unpredict2<uint16_t, true>, 6, true); go(k_unpredict2<uint8_t, true>, 8, true);
 }
 }   // namespace dev
 }   // namespace hry

@@ -347,6 +347,64 @@ def with_face_props(m: Mesh, seed: int = 11) -> Mesh:
     return Mesh(m.verts, m.degrees, m.indices, fp)
 
 
+INT_PROPS = (("pi32", "<i4"), ("pu32", "<u4"), ("pi16", "<i2"), ("pu16", "<u2"), ("pi8", "i1"), ("pu8", "u1"))
+
+
+def _int_values(rng, dt: np.dtype, n: int, values: str) -> np.ndarray:
+    """n values of integer type dt: "full" = uniform over the whole type; "edges" = a seeded draw from {min, min+1, -1 (signed) or
+    max/2 (unsigned), 0, 1, max-1, max}; "half" = uniform over half the type's range, its two ends in the first two places."""
+    lo, hi = int(np.iinfo(dt).min), int(np.iinfo(dt).max)
+    if values == "full":
+        return rng.integers(lo, hi, n, dtype=np.int64, endpoint=True).astype(dt)
+    if values == "edges":
+        pick = np.array([lo, lo + 1, -1 if lo < 0 else hi // 2, 0, 1, hi - 1, hi], np.int64)
+        return pick[rng.integers(0, len(pick), n)].astype(dt)
+    if values == "half":
+        a, b = (lo // 2, hi // 2) if lo < 0 else (hi // 4, hi // 4 + hi // 2)
+        v = rng.integers(a, b, n, dtype=np.int64, endpoint=True)
+        v[:2] = (a, b)
+        return v.astype(dt)
+    raise ValueError(values)
+
+
+def with_integer_props(m: Mesh, seed=7, values: str = "smooth", face: bool = False, byte_first: bool = False) -> Mesh:
+    """Integer-valued vertex properties of every PLY integer type next to the float coordinates.
+    values: "smooth" (follow the coordinates, far from the types' limits), "full", "edges", "half" (see _int_values)
+    face: the same six properties on the face list as well
+    byte_first: pu8 leads the record, so that every wider component lies at an odd offset"""
+    rng = np.random.default_rng(seed)
+    names = list(m.verts.dtype.names)
+    props = list(INT_PROPS)
+    if byte_first:
+        props = props[-1:] + props[:-1]
+    coords = [(n, m.verts.dtype[n]) for n in names]
+    dt = ([props[0]] + coords + props[1:]) if byte_first else (coords + props)
+    v = np.zeros(m.nv, dtype=dt)
+    for n in names:
+        v[n] = m.verts[n]
+    base = (m.verts["x"].astype(np.float64) * 900 + m.verts["y"].astype(np.float64) * 300)
+
+    def fill(out, base, count):
+        if values != "smooth":
+            for n, t in INT_PROPS:
+                out[n] = _int_values(rng, np.dtype(t), count, values)
+            return
+        out["pi32"] = (base * 1000).astype(np.int64).astype(np.int32) + rng.integers(-3, 4, count, dtype=np.int32)
+        out["pu32"] = (base * 1000 + 3_000_000_000).astype(np.int64).astype(np.uint32)
+        out["pi16"] = np.clip(base * 10, -32000, 32000).astype(np.int16) + rng.integers(-2, 3, count).astype(np.int16)
+        out["pu16"] = (np.clip(base * 10, -32000, 32000) + 32768).astype(np.uint16)
+        out["pi8"] = np.clip(base / 12, -120, 120).astype(np.int8)
+        out["pu8"] = (np.clip(base / 12, -120, 120) + 128).astype(np.uint8)
+
+    fill(v, base, m.nv)
+    fp = m.face_props
+    if face:
+        fp = np.zeros(m.nf, dtype=props)
+        first = np.concatenate(([0], np.cumsum(m.degrees.astype(np.int64))))[:-1]
+        fill(fp, base[m.indices[first]], m.nf)   # (smooth: a face follows its first corner)
+    return Mesh(v, m.degrees, m.indices, fp)
+
+
 def negated(m: Mesh) -> Mesh:
     """All coordinates strictly negative (exercises SURVEY App. B-2: max initialised with FLT_MIN)."""
     v = m.verts.copy()

@@ -3199,6 +3199,30 @@ uint32_t ho_kat_predict_u(uint32_t v0, uint32_t v1, uint32_t v2, int bytes, int 
 	default: return ho::paral_predict<uint32_t>(v0, v1, v2, q, std::false_type());
 	}
 }
+int32_t ho_kat_encode_delta_s(int32_t raw, int32_t pred, int bytes, int q)
+{
+	switch (bytes) {
+	case 1: return ho::fold_residual<int8_t>((int8_t)raw, (int8_t)pred, q, std::false_type());
+	case 2: return ho::fold_residual<int16_t>((int16_t)raw, (int16_t)pred, q, std::false_type());
+	default: return ho::fold_residual<int32_t>(raw, pred, q, std::false_type());
+	}
+}
+int32_t ho_kat_decode_delta_s(int32_t d, int32_t pred, int bytes, int q)
+{
+	switch (bytes) {
+	case 1: return ho::unfold_residual<int8_t>((int8_t)d, (int8_t)pred, q, std::false_type());
+	case 2: return ho::unfold_residual<int16_t>((int16_t)d, (int16_t)pred, q, std::false_type());
+	default: return ho::unfold_residual<int32_t>(d, pred, q, std::false_type());
+	}
+}
+int32_t ho_kat_predict_s(int32_t v0, int32_t v1, int32_t v2, int bytes, int q)
+{
+	switch (bytes) {
+	case 1: return ho::paral_predict<int8_t>((int8_t)v0, (int8_t)v1, (int8_t)v2, q, std::false_type());
+	case 2: return ho::paral_predict<int16_t>((int16_t)v0, (int16_t)v1, (int16_t)v2, q, std::false_type());
+	default: return ho::paral_predict<int32_t>(v0, v1, v2, q, std::false_type());
+	}
+}
 uint32_t ho_kat_predict_f32(uint32_t v0, uint32_t v1, uint32_t v2)
 {
 	using ho::bitcast;

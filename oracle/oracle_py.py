@@ -89,6 +89,10 @@ def lib():
     L.ho_kat_decode_delta_u.restype = u32; L.ho_kat_decode_delta_u.argtypes = [u32, u32, i, i]
     L.ho_kat_predict_u.restype = u32; L.ho_kat_predict_u.argtypes = [u32, u32, u32, i, i]
     L.ho_kat_predict_f32.restype = u32; L.ho_kat_predict_f32.argtypes = [u32, u32, u32]
+    i32 = C.c_int32
+    L.ho_kat_encode_delta_s.restype = i32; L.ho_kat_encode_delta_s.argtypes = [i32, i32, i, i]
+    L.ho_kat_decode_delta_s.restype = i32; L.ho_kat_decode_delta_s.argtypes = [i32, i32, i, i]
+    L.ho_kat_predict_s.restype = i32; L.ho_kat_predict_s.argtypes = [i32, i32, i32, i, i]
     L.ho_kat_requant_f32.restype = C.c_uint64; L.ho_kat_requant_f32.argtypes = [u32, u32, u32, i]
     L.ho_kat_range_encode_bytes.restype = sz; L.ho_kat_range_encode_bytes.argtypes = [C.c_char_p, sz, C.c_char_p, sz]
     L.ho_kat_range_decode_bytes.restype = sz; L.ho_kat_range_decode_bytes.argtypes = [C.c_char_p, sz, C.c_char_p, sz]

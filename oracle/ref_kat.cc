@@ -168,6 +168,39 @@ int main()
 		for (size_t i = 0; i < tr.size(); ++i) printf("%llu%s", (unsigned long long)tr[i], i + 1 < tr.size() ? "," : "");
 		printf("], \"%s\"]%s\n", hex(os.str()).c_str(), k < 5 ? "," : "");
 	}
-	printf(" ]\n}\n");
+	printf(" ],\n \"delta_s\": [\n");
+	// the signed integer types, lossless (q = 0): [bytes, q, raw, pred, enc, dec(enc)] -- every pair of the values at the ends and the
+	// middle of the type, and seeded random pairs.  (Appended behind every older section: no earlier draw of rng moves.)
+	first = true;
+	auto emit_s = [&](int bytes, int32_t raw, int32_t pred) {
+		int32_t e, d;
+		if (bytes == 1) { e = hry::pred::encodeDelta<int8_t>(raw, pred, 0); d = hry::pred::decodeDelta<int8_t>(e, pred, 0); }
+		else if (bytes == 2) { e = hry::pred::encodeDelta<int16_t>(raw, pred, 0); d = hry::pred::decodeDelta<int16_t>(e, pred, 0); }
+		else { e = hry::pred::encodeDelta<int32_t>(raw, pred, 0); d = hry::pred::decodeDelta<int32_t>(e, pred, 0); }
+		printf("%s  [%d, 0, %d, %d, %d, %d]", first ? "" : ",\n", bytes, raw, pred, e, d);
+		first = false;
+	};
+	auto draw_s = [&](int bytes) { int64_t lo = -(1ll << (8 * bytes - 1)); return (int32_t)(lo + (int64_t)(rng() % (1ull << (8 * bytes)))); };
+	for (int bytes : { 1, 2, 4 }) {
+		int64_t lo = -(1ll << (8 * bytes - 1)), hi = -lo - 1;
+		int32_t edge[] = { (int32_t)lo, (int32_t)(lo + 1), -1, 0, 1, (int32_t)(hi - 1), (int32_t)hi };
+		for (int32_t a : edge) for (int32_t b : edge) emit_s(bytes, a, b);
+		for (int i = 0; i < 24; ++i) { int32_t a = draw_s(bytes), b = draw_s(bytes); emit_s(bytes, a, b); }
+	}
+	printf("\n ],\n \"predict_s\": [\n");
+	first = true;
+	auto emit_ps = [&](int bytes, int32_t a, int32_t b, int32_t c) {
+		int32_t r;
+		if (bytes == 1) r = hry::pred::predict<int8_t>(a, b, c, 0); else if (bytes == 2) r = hry::pred::predict<int16_t>(a, b, c, 0); else r = hry::pred::predict<int32_t>(a, b, c, 0);
+		printf("%s  [%d, 0, %d, %d, %d, %d]", first ? "" : ",\n", bytes, a, b, c, r);
+		first = false;
+	};
+	for (int bytes : { 1, 2, 4 }) {
+		int64_t lo = -(1ll << (8 * bytes - 1)), hi = -lo - 1;
+		int32_t edge[] = { (int32_t)lo, (int32_t)(lo + 1), -1, 0, 1, (int32_t)(hi - 1), (int32_t)hi };
+		for (int32_t a : edge) for (int32_t b : edge) for (int32_t c : edge) emit_ps(bytes, a, b, c);
+		for (int i = 0; i < 32; ++i) { int32_t a = draw_s(bytes), b = draw_s(bytes), c = draw_s(bytes); emit_ps(bytes, a, b, c); }
+	}
+	printf("\n ]\n}\n");
 	return 0;
 }

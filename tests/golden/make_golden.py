@@ -6,7 +6,11 @@ Run in the build container only (needs oracle/_ref/harry_ref, built by `make -C 
 the reference's decoded PLY outputs, function-level known answers, and a manifest with sizes/hashes for
 larger regenerated cases.  No reference source text is copied.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                 every entry afresh
+    python tests/golden/make_golden.py NAME [NAME...]   only the named entries (of any section), merged into the manifest: the
+                                                        way to ADD cases, since start-face order depends on the libstdc++ the
+                                                        reference was built with (see the manifest's note) and the existing
+                                                        fixtures must not move
 """
 from __future__ import annotations
 
@@ -21,10 +25,26 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 from harry_amd import meshgen as mg  # noqa: E402
+from tests import util  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref", "harry_ref")
 
+# integer attributes (mg.with_integer_props): components 3..8 of the vertex list are pi32 pu32 pi16 pu16 pi8 pu8
+INT_MIXED = ["-l1", "-a3", "-q20", "-a4", "-q17", "-a5", "-q9", "-a6", "-q12", "-a7", "-q3", "-a8", "-q7"]
+INT_REQ = ["-l1", "-a3", "-q11", "-a4", "-q9", "-a5", "-q6", "-a6", "-q14", "-a7", "-q5", "-a8", "-q4"]
+
+
+def _int_width(q):
+    """one width for every integer component that can hold it (main.cc:80,87 refuses a width beyond the type's)"""
+    comps = [c for c, (_, t) in enumerate(mg.INT_PROPS, 3) if q <= 8 * int(t[-1])]
+    return ["-l1"] + [f for c in comps for f in (f"-a{c}", f"-q{q}")]
+
+
 POSNRM = ["-l1", "-a0", "-q14", "-a1", "-q14", "-a2", "-q14", "-a3", "-q10", "-a4", "-q10", "-a5", "-q10"]
+
+
+def _int_base():
+    return mg.torus(9, 11, seed=5)
 
 
 def small_cases():
@@ -43,6 +63,14 @@ def small_cases():
         "faceprops": (mg.with_face_props(mg.grid(9, 7)), "binary_little_endian", [("ll", []), ("q", ["-l0", "-q6", "-l1", "-q11"])]),
         "negative": (mg.negated(mg.grid(11)), "binary_little_endian", [("ll", []), ("q14", ["-l1", "-q14"])]),
         "tiny_tri": (mg.grid(2), "ascii", [("ll", []), ("q4", ["-l1", "-q4"])]),
+        # every PLY integer type at the limits of its range (lossless), and through the integer quantiser (quant.h:140-163): one
+        # width per storage class of each type, and mixed widths
+        "int_full": (mg.with_integer_props(_int_base(), values="full"), "binary_little_endian", [("ll", []), ("q6", ["-l1", "-q6"])]),
+        "int_edges": (mg.with_integer_props(_int_base(), values="edges"), "binary_little_endian", [("ll", [])]),
+        "int_half": (mg.with_integer_props(_int_base(), values="half"), "binary_little_endian",
+                     [("ll", []), ("mixed", INT_MIXED)] + [(f"q{q}", _int_width(q)) for q in (5, 8, 9, 16, 17, 24)]),
+        "int_face": (mg.with_integer_props(_int_base(), values="full", face=True), "binary_little_endian", [("ll", []), ("q", ["-l0", "-q5"])]),
+        "int_bytefirst": (mg.with_integer_props(_int_base(), values="full", byte_first=True), "binary_little_endian", [("ll", [])]),
         # 8-byte sources of the quantiser (quant.h:137-139); lossless doubles are outside the reference's own defined behaviour
         "grid_double": (mg.doubles(mg.grid(12, 9, seed=3)), "binary_little_endian", [("q14", ["-l1", "-q14"]), ("q30", ["-l1", "-q30"])]),
     }
@@ -58,12 +86,16 @@ def requant_cases():
         "colors_normals.posnrm_c_q8": ("colors_normals.posnrm.hry", ["-c", "-l1", "-a6", "-q5", "-a3", "-q8"]),
         "faceprops.q_c": ("faceprops.q.hry", ["-c"]),
         "grid_double.q14_to_q9": ("grid_double.q14.hry", ["-l1", "-q9"]),
+        "int_half.mixed_c": ("int_half.mixed.hry", ["-c"]),
+        "int_half.mixed_to_q": ("int_half.mixed.hry", INT_REQ),
     }
 
 
 def big_cases():
     """Regenerated, not committed: only size + sha256 of the reference output go into the manifest."""
+    ints = {name: (make, [("ll", [])]) for name, make in util.INT_BIG_CASES.items()}
     return {
+        **ints,
         "torus150": (lambda: mg.torus(150, 150, seed=2), [("ll", []), ("q14", ["-l1", "-q14"])]),
         "multi40": (lambda: mg.multi_component(40, 20, 22), [("ll", [])]),
         "ico5": (lambda: mg.icosphere(5), [("ll", []), ("q12", ["-l1", "-q12"])]),
@@ -84,10 +116,20 @@ def sha(b: bytes) -> str:
 def main():
     if not os.path.exists(REF):
         sys.exit("build the reference first: make -C oracle ref")
+    only = set(sys.argv[1:])
+    unknown = only - set(small_cases()) - set(requant_cases()) - set(big_cases())
+    if unknown:
+        sys.exit(f"no such entry: {sorted(unknown)}")
+    want = lambda name: not only or name in only
     manifest = {"libstdcxx_note": "start-face order depends on std::unordered_set iteration order (SURVEY App. B-1); "
                                   "generated with g++ 11 / libstdc++ GLIBCXX_3.4.30", "small": {}, "big": {}, "requant_of_hry": {}}
+    if only:
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
     with tempfile.TemporaryDirectory() as tmp:
         for name, (mesh, fmt, variants) in small_cases().items():
+            if not want(name):
+                continue
             ply = mesh.to_ply(fmt)
             with open(os.path.join(HERE, name + ".ply"), "wb") as f:
                 f.write(ply)
@@ -103,11 +145,15 @@ def main():
             manifest["small"][name] = entry
         # re-quantisation / dequantisation of an already quantised .hry (quant.h:169-212)
         for name, (src_name, flags) in requant_cases().items():
+            if not want(name):
+                continue
             src = os.path.join(HERE, src_name)
             dst = os.path.join(HERE, name + ".hry")
             run_ref([src, dst] + flags)
             manifest["requant_of_hry"][name] = {"src": src_name, "flags": flags, "hry_sha256": sha(open(dst, "rb").read())}
         for name, (make, variants) in big_cases().items():
+            if not want(name):
+                continue
             mesh = make()
             p = os.path.join(tmp, name + ".ply")
             with open(p, "wb") as f:

@@ -12,6 +12,7 @@ from harry_amd import _native as nat
 from harry_amd import codec as hc
 from harry_amd import meshgen as mg
 from harry_amd import objgen as og
+from oracle import oracle_py as op
 
 pytestmark = pytest.mark.gpu
 
@@ -90,3 +91,30 @@ def test_general_lists_with_8_byte_storage_are_refused(cx):
         data[at + 1] = 40                      # 40 bits: an 8-byte quantised type
         with pytest.raises(hc.HryError, match="8-byte|outside the supported subset|unsupported"):
             cx.read_hry(bytes(data))
+
+
+def _four_vertices(dtype, values):
+    v = np.zeros(4, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("p", dtype)])
+    v["x"], v["y"], v["p"] = [0, 1, 1, 0], [0, 0, 1, 1], values
+    return v, np.full(2, 3, np.uint8), np.array([0, 1, 2, 0, 2, 3], np.uint32)
+
+
+def test_signed_extent_of_minus_one_is_refused_at_the_boundary(cx):
+    """`int` / `long` from the type's least to its greatest value: the extent wraps to -1, and the reference divides the distance
+    of the value 0 to the minimum -- the type's least value -- by it (quant.h:106: SIGFPE).  Refused; one value short of the whole
+    type (extent -2) the request goes through and equals the oracle's."""
+    lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
+    m = hc.Mesh.from_arrays(*_four_vertices("<i4", [lo, hi, 0, 5]))
+    with pytest.raises(hc.HryError, match="extent of -1") as err:
+        cx.requant(m, [(1, 3, 8)])
+    assert err.value.code == nat.E_UNSUPPORTED
+    m = hc.Mesh.from_arrays(*_four_vertices("<i8", [np.iinfo(np.int64).min, np.iinfo(np.int64).max, 0, 5]))
+    with pytest.raises(hc.HryError, match="extent of -1") as err:
+        cx.requant(m, [(1, 3, 8)])
+    assert err.value.code == nat.E_UNSUPPORTED
+    near = mg.Mesh(*_four_vertices("<i4", [lo, hi - 1, 0, 5]))
+    a, o = hc.Mesh.from_ply(near.to_ply()), op.Mesh.from_ply(near.to_ply())
+    cx.requant(a, [(1, 3, 8)])
+    o.requant([(1, 3, 8)])
+    assert np.array_equal(a.list_data(1), o.list_data(1))
+    assert cx.write_hry(a) == o.encode().data

@@ -262,7 +262,11 @@ def test_recurrence_on_host_core_or_on_one_wavefront_gives_identical_bytes(cx):
 # ---------------------------------------------------------------- reading files written by the reference binary
 @pytest.mark.parametrize("name,tag,v", SMALL, ids=[f"{n}.{t}" for n, t, _ in SMALL])
 def test_decode_reference_file_identical_to_reference_decode(cx, name, tag, v):
-    """.hry written by the reference -> arrays identical to the PLY the reference itself decoded from it."""
+    """.hry written by the reference -> arrays identical to the PLY the reference itself decoded from it.
+
+    [int_full.q6]: `char` values over the whole type quantised to 6 bits -- the reference's quantiser rescales in int8_t
+    (quant.h:162) and leaves values ABOVE 2^q - 1 in the storage byte (183, 210, 173, 132 ...); the chain takes such components
+    through the generic arithmetic (k_unpredict2<T, true>), not through the forms that rest on values <= 2^q - 1."""
     hry = open(os.path.join(GOLD, f"{name}.{tag}.hry"), "rb").read()
     dec = open(os.path.join(GOLD, f"{name}.{tag}.dec.ply"), "rb").read()
     m = cx.read_hry(hry)

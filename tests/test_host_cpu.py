@@ -572,3 +572,39 @@ def test_range_reciprocal_equals_division(tmp_path):
     subprocess.run([cxx, "-O2", "-std=c++17", "-I", os.path.join(root, "harry_amd", "csrc", "device"), os.path.join(root, "tests", "tools", "magic_check.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 bad" in r.stdout, r.stdout + r.stderr
+
+
+def _rocm_clang():
+    import shutil
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for c in (os.path.join(rocm, "llvm", "bin", "clang++"), os.path.join(rocm, "lib", "llvm", "bin", "clang++")):
+        if os.path.exists(c):
+            return c
+    return shutil.which("amdclang++")
+
+
+@pytest.mark.parametrize("compiler", ["g++", "rocm-clang++", "g++-ubsan"])
+def test_codec_math_answers_the_reference_rows(tmp_path, compiler):
+    """codec_math.hpp -- what the kernels compute residuals, values and parallelogram predictions with -- against every delta_* and
+    predict_* row the reference's headers answered (tests/golden/kat.json; the signed types at the ends of their ranges included,
+    where int arithmetic wraps), compiled by the host compiler and by the compiler of the device code at the Makefile's -O3; and
+    by the host compiler with UBSan: no row may depend on undefined behaviour."""
+    import json
+    import shutil
+    import subprocess
+    cxx, opt = (_rocm_clang(), ["-O3"]) if compiler == "rocm-clang++" else (shutil.which("g++") or shutil.which("c++"), ["-O2"])
+    if compiler == "g++-ubsan":
+        opt = ["-O1", "-g1", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"]
+    if not cxx:
+        pytest.skip(f"no {compiler}")
+    with open(os.path.join(GOLD, "kat.json")) as f:
+        kat = json.load(f)
+    rows = []
+    for sec, kind in (("delta_f32", "df"), ("delta_u", "du"), ("delta_s", "ds"), ("predict_f32", "pf"), ("predict_u", "pu"), ("predict_s", "ps")):
+        assert kat[sec]
+        rows += [kind + " " + " ".join(str(x) for x in r) for r in kat[sec]]
+    exe = str(tmp_path / "codec_math_kat")
+    subprocess.run([cxx, *opt, "-std=c++17", "-ffp-contract=off", "-I", os.path.join(util.ROOT, "harry_amd", "csrc", "device"),
+                    os.path.join(util.ROOT, "tests", "tools", "codec_math_kat.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], input="\n".join(rows) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0 and f"{len(rows)} checked, 0 bad" in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr

@@ -54,15 +54,33 @@ def test_decode_array_identical(golden_dir, name, tag, v):
     assert np.array_equal(m.list_data(0), frec)
 
 
+SIGNED_TYPES = (3, 5, 7, 9)   # long, int, short, char
+
+
+def _records_without_signed(m, l=1):
+    """the records of list l with the signed integer components blanked"""
+    rec = m.list_data(l).reshape(m.nv if l == 1 else m.nf, -1).copy()
+    fmt = m.list_fmt(l)
+    ends = [off for _, _, off in fmt[1:]] + [rec.shape[1]]
+    for (t, _, off), end in zip(fmt, ends):
+        if t in SIGNED_TYPES:
+            rec[:, off:end] = 0
+    return rec
+
+
 @pytest.mark.parametrize("name,tag,v", [s for s in SMALL if s[1] == "ll"], ids=[n for n, t, _ in SMALL if t == "ll"])
 def test_lossless_roundtrip_up_to_permutation(golden_dir, name, tag, v):
-    """decode(encode(x)) == x as a multiset of faces over vertex records (SURVEY finding 0-4)."""
+    """decode(encode(x)) == x as a multiset of faces over vertex records (SURVEY finding 0-4).
+    Float and unsigned components only: the reference's residual code of a SIGNED component is not invertible once values or
+    predictions are negative (prediction.h:27-31 gives the mask -1, so that balanced_max of :54,88 is negative and the far
+    branches of :55-60,91,96 take nearly every value) -- its own decode of tests/golden/int_*.ll.hry differs from the input in
+    about half of the signed values.  What the reference decodes there is pinned by test_decode_array_identical."""
     ply = open(os.path.join(golden_dir, name + ".ply"), "rb").read()
     src = op.Mesh.from_ply(ply)
-    src_faces = util.canonical_faces(src.list_data(1), np.diff(src.face_offsets()), src.org())
+    src_faces = util.canonical_faces(_records_without_signed(src), np.diff(src.face_offsets()), src.org())
     res = src.encode()
     dec = op.Mesh.from_hry(res.data)
-    dec_faces = util.canonical_faces(dec.list_data(1), np.diff(dec.face_offsets()), dec.org())
+    dec_faces = util.canonical_faces(_records_without_signed(dec), np.diff(dec.face_offsets()), dec.org())
     assert src_faces == dec_faces
 
 
@@ -77,7 +95,8 @@ def test_requant_of_quantised_hry(golden_dir, manifest):
 
 
 BIG = {"torus150": lambda: mg.torus(150, 150, seed=2), "multi40": lambda: mg.multi_component(40, 20, 22),
-       "ico5": lambda: mg.icosphere(5), "nm_big": lambda: mg.with_nonmanifold(mg.torus(60, 64, polys="mixed"), 30, 12)}
+       "ico5": lambda: mg.icosphere(5), "nm_big": lambda: mg.with_nonmanifold(mg.torus(60, 64, polys="mixed"), 30, 12),
+       **util.INT_BIG_CASES}
 
 
 @pytest.mark.parametrize("name", sorted(BIG))
@@ -133,6 +152,18 @@ def test_kat_predict(kat):
         assert L.ho_kat_predict_u(v0, v1, v2, b, q) == r
     for v0, v1, v2, r in kat["predict_f32"]:
         assert L.ho_kat_predict_f32(v0, v1, v2) == r
+
+
+def test_kat_signed_types(kat):
+    """char, short, int, lossless: the ends of every type against each other, where the clamps of the predictor, pred == 0 and
+    the far branches of the residual code are taken and int arithmetic wraps (the reference's answers: oracle/ref_kat.cc)"""
+    L = op.lib()
+    assert {r[0] for r in kat["delta_s"]} == {r[0] for r in kat["predict_s"]} == {1, 2, 4}
+    for b, q, raw, pred, enc, dec in kat["delta_s"]:
+        assert L.ho_kat_encode_delta_s(raw, pred, b, q) == enc, (b, q, raw, pred)
+        assert L.ho_kat_decode_delta_s(enc, pred, b, q) == dec, (b, q, raw, pred)
+    for b, q, v0, v1, v2, r in kat["predict_s"]:
+        assert L.ho_kat_predict_s(v0, v1, v2, b, q) == r, (b, q, v0, v1, v2)
 
 
 def test_kat_requant(kat):

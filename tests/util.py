@@ -9,6 +9,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "harry_ref")
 
 
+def _int_big_cases():
+    from harry_amd import meshgen as mg
+    t5250 = lambda: mg.torus(70, 75, seed=5)
+    return {
+        "int_full_5250": lambda: mg.with_integer_props(t5250(), values="full"),
+        "int_edges_mixed": lambda: mg.with_integer_props(mg.with_nonmanifold(mg.torus(50, 56, polys="mixed", seed=6), 20, 8), values="edges"),
+        # more vertices than the 16 384 entries of k_unpredict3's ring, which lossless uchar / ushort ride: the smallest torus past one wrap
+        "int_full_17161": lambda: mg.with_integer_props(mg.torus(131, 131), values="full"),
+        "int_bytefirst_5250": lambda: mg.with_integer_props(t5250(), values="full", byte_first=True),
+        "int_face_5250": lambda: mg.with_integer_props(t5250(), values="full", face=True),
+    }
+
+
+# integer attributes of every PLY type on meshes too large to commit: name -> generator; the reference's answers (size and hash
+# of its lossless stream) are in tests/golden/manifest.json under "big" (tests/golden/make_golden.py)
+INT_BIG_CASES = _int_big_cases()
+
+
 def flags_to_quant(flags):
     """Emulate the reference CLI's -l/-a/-q/-c state machine (main.cc:47-71): returns (triples, clear)."""
     cur_l, cur_a, out, clear = None, -1, [], False
