@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "dev_types.hpp"
 
@@ -55,18 +56,22 @@ void launch_carry(hipStream_t st, const uint64_t *acc, uint32_t nw, uint64_t *v,
 void launch_residuals_to_rec(hipStream_t st, const uint8_t *planes, uint32_t n, const ListDesc &ld, uint8_t *rec);
 void launch_faces_unfold(hipStream_t st, uint32_t n, const ListDesc &ld, uint8_t *rec);
 bool unpredict2_applicable(const ListDesc &ld);
+// plan (keep_stages: the stage "chain_plan"): a row of six words per chain kernel launched -- kind (2 k_unpredict2, 3 k_unpredict3,
+// 4 k_unpredict3_range, 5 k_unpredict2 in its exact form for signed sources), storage type, work lists, components of that type,
+// wavefronts per chain, bytes of the LDS ring.  Filled on the host where the launch is decided; the kernels know nothing of it.
+constexpr uint32_t kChainPlanWords = 6;
 void launch_chain_records(hipStream_t st, const uint32_t *cand, const uint8_t *ncand, uint32_t nvtx, const uint32_t *seg_start, uint32_t nseg, void *crec);
 bool unpredict3_wanted(const ListDesc &ld);
 void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand, const void *crec,
                        const uint8_t *planes, const ListDesc &ld, uint8_t *rec, const uint32_t *segs, const uint32_t *list_off, uint32_t n_lists,
-                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done);
+                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done, std::vector<uint32_t> *plan = nullptr);
 void launch_candidates_ids(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand);
 bool unpredict3_covers(const ListDesc &ld);
 void launch_slice_prepare(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, uint32_t *cand, uint8_t *ncand, void *crec);
 size_t cand_table_words(uint32_t nvtx);
 void cand_table_reset(hipStream_t st, uint32_t *cand, uint32_t nvtx);
 void launch_slice_chain(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, const uint32_t *cand, const uint8_t *ncand,
-                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec);
+                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec, std::vector<uint32_t> *plan = nullptr);
 void launch_scatter_u32(hipStream_t st, const uint32_t *pairs, uint32_t n, uint32_t *dst);
 uint32_t chain_timeout_flags(hipStream_t st, const uint32_t *gave_up = nullptr);
 

@@ -131,6 +131,18 @@ struct ChainBatches {
 	}
 };
 
+// keep_stages: the candidate table's overflow area as k_candidates_ids left it -- its 16 header words (word 0: rows handed out) and
+// the rows handed out, 24 words each -- beside "cand" (the compact rows) and "ncand"
+static void stage_cand_over(Context &cx, const uint32_t *d_cand, uint32_t nv)
+{
+	if (!cx.keep_stages) return;
+	HIP_OK(hipStreamSynchronize(cx.stream));
+	const uint32_t *d_over = d_cand + (size_t)nv * 6;   // (behind the compact rows)
+	uint32_t rows = 0;
+	HIP_OK(hipMemcpy(&rows, d_over, 4, hipMemcpyDeviceToHost));
+	cx.stage_put("cand_over", d_over, (16 + (size_t)std::min(rows, nv) * 24) * 4);
+}
+
 // Attribute reconstruction on the device, shared by both formats: connectivity + decode order + residual byte planes
 // (already in HBM) -> attribute records.  Events 3/4 bracket the kernels.
 // conn_from: the connectivity (face offsets, origins, twins) is read from that mesh instead -- one that another thread may be
@@ -145,6 +157,7 @@ static void reconstruct_attributes(Context &cx, Mesh &mesh, const OrderVec &orde
 {
 	Mesh *m = &mesh;
 	const uint32_t nvc = (uint32_t)order_v.size();
+	std::vector<uint32_t> chain_plan;   // keep_stages: a row per chain kernel launched (kernels.hpp: kChainPlanWords)
 	bool chain_timed = false;
 	size_t early_bytes = 0;
 	const uint32_t *d_gave_up = nullptr;   // the chains' give-up word of this decode (behind their flag table)
@@ -227,7 +240,7 @@ static void reconstruct_attributes(Context &cx, Mesh &mesh, const OrderVec &orde
 			// a 2-D grid holds at most 65535 rows: very many components go in several launches, still in coding order
 			for (uint32_t done = 0; done < n_lists; done += 65535)
 				launch_unpredict2(cx.stream, cv, cx.d_order_v.as<uint32_t>(), nvc, d_cand, d_ncand, scan_chain ? d_crec : nullptr, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>(),
-				                  d_tab, d_tab + off_at + done, std::min(65535u, n_lists - done), d_tab + segstart_at, nseg, d_tab + done_at);
+				                  d_tab, d_tab + off_at + done, std::min(65535u, n_lists - done), d_tab + segstart_at, nseg, d_tab + done_at, cx.keep_stages ? &chain_plan : nullptr);
 			HIP_OK(hipEventRecord(cx.ev[0], cx.stream));
 			chain_timed = true;
 			HIP_OK(hipStreamSynchronize(cx.stream));   // the table lives in host memory until the copy has been consumed
@@ -253,6 +266,8 @@ static void reconstruct_attributes(Context &cx, Mesh &mesh, const OrderVec &orde
 		cx.stage_put_host("order_v", order_v.data(), order_v.size() * 4);
 		cx.stage_put("ncand", d_ncand, nvc);
 		cx.stage_put("cand", d_cand, (size_t)nvc * 6 * 4);
+		stage_cand_over(cx, d_cand, nvc);
+		cx.stage_put_host("chain_plan", chain_plan.data(), chain_plan.size() * 4);
 	}
 }
 
@@ -528,6 +543,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 	live.interval = std::max(1u, (uint32_t)env_uint("HRY_PIPELINE_FACES", live.interval));
 
 	std::vector<SliceClock> clocks;
+	std::vector<uint32_t> chain_plan;   // keep_stages: a row per slice's chain kernel (written by the consumer thread, read behind its join)
 	// replay and chain take about the same time per vertex: what is left behind the replay is the last slice (16 Ki: the consumer's launches become the longer path)
 	const uint32_t min_slice = std::max(64u, (uint32_t)env_uint("HRY_PIPELINE_SLICE", 1u << 15));
 	// ... but the first slices are small and double up to that size: the chain is the longer path, what counts is how early it
@@ -699,7 +715,7 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 					// the residual codes of this slice: the groups of attribute streams that end inside it or before
 					while (attr_waited < Context::kAttrGroups && (attr_waited == 0 || attr_upto[attr_waited - 1] < v_to)) HIP_OK(hipStreamWaitEvent(cx.stream, cx.attr_ev[attr_waited++], 0));
 					HIP_OK(hipEventRecord(ck.a, cx.stream));
-					launch_slice_chain(cx.stream, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>());
+					launch_slice_chain(cx.stream, cvs, cx.d_order_v.as<uint32_t>(), nv, v_lo, v_to, d_cand, d_ncand, d_crec, d_vplanes, ldv, cx.d_rec[1].as<uint8_t>(), cx.keep_stages ? &chain_plan : nullptr);
 					HIP_OK(hipEventRecord(ck.b, cx.stream));
 					{
 						// (the records come down on a stream of their own, behind the slice's chain: on the chain's stream the next
@@ -806,6 +822,8 @@ static void decode_pipelined(Context &cx, Mesh &mesh, const PlaneView *conn, con
 		cx.stage_put_host("order_v", order_v.data(), order_v.size() * 4);
 		cx.stage_put("ncand", d_ncand, nv);
 		cx.stage_put("cand", d_cand, (size_t)nv * 6 * 4);
+		stage_cand_over(cx, d_cand, nv);
+		cx.stage_put_host("chain_plan", chain_plan.data(), chain_plan.size() * 4);
 	}
 }
 

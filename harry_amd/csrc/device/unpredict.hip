@@ -2102,13 +2102,14 @@ void launch_slice_prepare(hipStream_t st, const ConnView &cv, const uint32_t *or
 	hipLaunchKernelGGL(k_candidates_ids, dim3(per * 8), dim3(256), 0, st, cv, order_v, v_begin, v_end, cand, ncand, per, nvtx, (ChainRec*)crec, chain_ring_floor(v_begin));
 }
 void launch_slice_chain(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t v_begin, uint32_t v_end, const uint32_t *cand, const uint8_t *ncand,
-                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec)
+                        const void *crec, const uint8_t *planes, const ListDesc &ld, uint8_t *rec, std::vector<uint32_t> *plan)
 {
 	if (v_end <= v_begin) return;
 	auto go3 = [&](auto kern, int stype) {
 		CompSel sel{};
 		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype) sel.comp[sel.n++] = c;
 		if (!sel.n) return;
+		if (plan) plan->insert(plan->end(), { 4u, (uint32_t)stype, 1u, (uint32_t)sel.n, chain_waves(nvtx), kRing3 * (stype == 6 ? 2u : 1u) });
 		hipLaunchKernelGGL(kern, dim3((sel.n - 1) * 8 + 1), dim3(64 * chain_waves(nvtx)), 0, st, cv, order_v, nvtx, cand, ncand, (const ChainRec*)crec, planes, ld, rec, sel, v_begin, v_end, chain_ring_floor(v_begin));
 	};
 	go3(k_unpredict3_range<uint16_t>, 6); go3(k_unpredict3_range<uint8_t>, 8);
@@ -2129,7 +2130,7 @@ bool unpredict3_wanted(const ListDesc &ld)
 // (ld.ncomp x nseg flags, zeroed) let a chain wait for the component that owns an older vertex it reads.
 void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t nvtx, uint32_t *cand, uint8_t *ncand, const void *crec,
                        const uint8_t *planes, const ListDesc &ld, uint8_t *rec, const uint32_t *segs, const uint32_t *list_off, uint32_t n_lists,
-                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done)
+                       const uint32_t *seg_start, uint32_t nseg, uint32_t *done, std::vector<uint32_t> *plan)
 {
 	if (!nvtx || !ld.ncomp || !n_lists) return;
 	// (the callers' flag tables hold ld.ncomp x nseg progress words and one more behind them, zeroed with them: the give-up word)
@@ -2138,6 +2139,7 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 		CompSel sel{};
 		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype && !beyond_top(ld, c)) sel.comp[sel.n++] = c;
 		if (!sel.n) return;
+		if (plan) plan->insert(plan->end(), { 3u, (uint32_t)stype, n_lists, (uint32_t)sel.n, std::min(8u, chain_waves(nvtx)), kRing3 * (stype == 6 ? 2u : 1u) });
 		hipLaunchKernelGGL(kern, dim3(((n_lists + 7) / 8) * 8 * (uint32_t)sel.n), dim3(64 * std::min(8u, chain_waves(nvtx))), 0, st,   /* (the kernel of many chains keeps its 512 threads: with 1 024 it would not fit its registers) */ cv, order_v, nvtx, (const uint32_t*)cand, (const uint8_t*)ncand, (const ChainRec*)crec, planes, ld, rec, sel,
 		                   segs, list_off, xs, n_lists);
 	};
@@ -2151,6 +2153,7 @@ void launch_unpredict2(hipStream_t st, const ConnView &cv, const uint32_t *order
 		CompSel sel{};
 		for (int c = 0; c < ld.ncomp; ++c) if (ld.stype[c] == stype && ((stype == 6 || stype == 8) && beyond_top(ld, c)) == exact) sel.comp[sel.n++] = c;   // exact: 8- / 16-bit storage of a signed source
 		if (!sel.n) return;
+		if (plan) plan->insert(plan->end(), { exact ? 5u : 2u, (uint32_t)stype, n_lists, (uint32_t)sel.n, 1u, ring_bytes });
 		(void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 		hipLaunchKernelGGL(kern, dim3(((n_lists + 7) / 8) * 8 * (uint32_t)sel.n), dim3(64), lds_bytes, st, cv, order_v, nvtx, (const uint32_t*)cand, (const uint8_t*)ncand, planes, ld, rec, ring_bytes, sel,
 		                   segs, list_off, xs, n_lists);

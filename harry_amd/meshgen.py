@@ -422,6 +422,114 @@ def doubles(m: Mesh) -> Mesh:
     return Mesh(v, m.degrees, m.indices, m.face_props)
 
 
+def _disc_faces(centre: int, rings, centre_faces: str = "tri", quads: bool = False):
+    """Faces of a polar disc, the outermost ring first and the centre's own faces last (so a walk that starts at face 0 meets
+    the centre after everything around it).  rings: arrays of vertex ids from the inside out; "tri": a triangle fan around the
+    centre over rings[0]; "pent": pentagons (centre, r[3i], r[3i+1], r[3i+2], r[3i+3]) -- len(rings[0]) a multiple of 3."""
+    deg, idx = [], []
+    for k in range(len(rings) - 1, 0, -1):
+        p, r = np.asarray(rings[k - 1], np.int64), np.asarray(rings[k], np.int64)
+        assert len(p) == len(r)
+        p1, r1 = np.roll(p, -1), np.roll(r, -1)
+        if quads:
+            f = np.stack([p1, p, r, r1], 1)
+        else:
+            f = np.stack([np.stack([p1, p, r], 1), np.stack([p1, r, r1], 1)], 1).reshape(-1, 3)
+        deg.append(np.full(len(f), f.shape[1], np.uint8)); idx.append(f.reshape(-1))
+    p = np.asarray(rings[0], np.int64)
+    if centre_faces == "pent":
+        assert len(p) % 3 == 0
+        a = p.reshape(-1, 3)
+        f = np.stack([np.full(len(a), centre), a[:, 0], a[:, 1], a[:, 2], np.roll(a[:, 0], -1)], 1)
+    else:
+        f = np.stack([np.full(len(p), centre), p, np.roll(p, -1)], 1)
+    deg.append(np.full(len(f), f.shape[1], np.uint8)); idx.append(f.reshape(-1))
+    return np.concatenate(deg), np.concatenate(idx).astype(np.uint32)
+
+
+def hub_discs(valences, rings: int = 2, centre_faces: str = "tri", quads: bool = False, seed: int = 3, sigma: float = 1e-3) -> Mesh:
+    """One open polar disc per entry of `valences`, each a component of its own: a centre with that many faces around it and
+    `rings` rings of vertices, faces listed from the outside in.  The centre is the last vertex its component codes, with every
+    parallelogram around it complete: valence candidates for a triangle fan, twice the valence for pentagons (the (a, b, b) offer
+    of a polygon of degree above 4, attrcode.h:155-171)."""
+    rng = np.random.default_rng(seed)
+    xs, ys, zs, deg, idx = [], [], [], [], []
+    base = 0
+    for i, n in enumerate(valences):
+        per = 3 * n if centre_faces == "pent" else n
+        ang = 2 * np.pi * np.arange(per) / per
+        rad = np.arange(1, rings + 1)[:, None] * 0.1
+        cx, cy = 3.0 * (i % 16), 3.0 * (i // 16)
+        x = np.concatenate([[0.0], (rad * np.cos(ang)[None, :]).ravel()]) + cx
+        y = np.concatenate([[0.0], (rad * np.sin(ang)[None, :]).ravel()]) + cy
+        z = 0.3 - 0.5 * (x - cx) ** 2 - 0.4 * (y - cy) ** 2
+        ids = [base + 1 + k * per + np.arange(per) for k in range(rings)]
+        d, f = _disc_faces(base, ids, centre_faces, quads)
+        xs.append(x); ys.append(y); zs.append(z); deg.append(d); idx.append(f)
+        base += 1 + rings * per
+    cols = {k: np.concatenate(a).astype(np.float32) + _noise(rng, base, sigma) for k, a in (("x", xs), ("y", ys), ("z", zs))}
+    return Mesh(_vtx_struct(cols), np.concatenate(deg), np.concatenate(idx))
+
+
+def with_shared_discs(m: Mesh, valences, seed: int = 17) -> Mesh:
+    """Glue one polar disc per entry of `valences` onto m: its two rings are EXISTING vertices of m (drawn at random: no edge of a
+    disc is an edge of m, so every disc is a component of its own that names vertices of an earlier one) around one new centre
+    vertex.  The centre has `valence` candidates, whatever their number, and every source of them belongs to the earlier component."""
+    rng = np.random.default_rng(seed)
+    names = m.verts.dtype.names
+    new_v, deg, idx = [], [m.degrees], [m.indices]
+    for i, valence in enumerate(valences):
+        pick = rng.choice(m.nv, 2 * valence, replace=False).astype(np.int64)
+        row = np.zeros(1, m.verts.dtype)
+        for k in names:
+            row[k] = m.verts[k][pick[:valence]].astype(np.float64).mean()
+        new_v.append(row)
+        d, f = _disc_faces(m.nv + i, [pick[:valence], pick[valence:]])
+        deg.append(d); idx.append(f)
+    return Mesh(np.concatenate([m.verts] + new_v), np.concatenate(deg), np.concatenate(idx))
+
+
+def ribbon(length: int, width: int = 3, seed: int = 5, sigma: float = 1e-4, closed: bool = True) -> Mesh:
+    """A long narrow band of triangles, `width` vertices across, closed into a ring: a walk that starts across it runs along both
+    directions and meets itself again after `length` steps, so its last rows read vertices coded about width x length earlier."""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(length), np.arange(width), indexing="ij")
+    u = 2 * np.pi * i.ravel() / length
+    w = j.ravel() / max(width - 1, 1) - 0.5
+    cols = {"x": ((1.0 + 0.1 * w) * np.cos(u)).astype(np.float32) + _noise(rng, length * width, sigma),
+            "y": ((1.0 + 0.1 * w) * np.sin(u)).astype(np.float32) + _noise(rng, length * width, sigma),
+            "z": (0.2 * w + 0.05 * np.sin(7 * u)).astype(np.float32) + _noise(rng, length * width, sigma)}
+    rows = length if closed else length - 1
+    ii, jj = np.meshgrid(np.arange(rows), np.arange(width - 1), indexing="ij")
+    a = (ii * width + jj).ravel()
+    b = a + 1
+    d = (((ii + 1) % length) * width + jj).ravel()
+    c = d + 1
+    tris = np.stack([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 1).reshape(-1, 3)
+    return _tri_mesh(cols, tris)
+
+
+def with_holes(m: Mesh, n: int, seed: int = 3) -> Mesh:
+    """m without n of its faces, drawn at random: small holes whose borders a walk has to go round (irregular stretches in an
+    otherwise regular coding order; the mesh stays one component)"""
+    rng = np.random.default_rng(seed)
+    keep = np.ones(m.nf, bool)
+    keep[rng.choice(m.nf, n, replace=False)] = False
+    offs = np.concatenate(([0], np.cumsum(m.degrees.astype(np.int64))))
+    idx = np.concatenate([m.indices[offs[f]:offs[f + 1]] for f in np.flatnonzero(keep)]) if not (m.degrees == m.degrees[0]).all() else \
+        m.indices.reshape(m.nf, -1)[keep].reshape(-1)
+    return Mesh(m.verts, m.degrees[keep], idx, None if m.face_props is None else m.face_props[keep])
+
+
+def snapped(m: Mesh, step: float = 1.0 / 64) -> Mesh:
+    """the coordinates rounded to a lattice of `step` (a power of two: sums and differences of them are exact in float, so the two
+    parallelograms of a vertex often lie at the same distance from their mean)"""
+    v = m.verts.copy()
+    for k in ("x", "y", "z"):
+        v[k] = (np.round(v[k].astype(np.float64) / step) * step).astype(np.float32)
+    return Mesh(v, m.degrees, m.indices, m.face_props)
+
+
 # the named configurations of BASELINE.json / SURVEY.md 8(d)
 def cfg1_bunny_class() -> Mesh:
     return icosphere(6, seed=1, sigma=1e-3, extra_props=True)          # 81 920 tris

@@ -29,6 +29,7 @@
 #include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
+#include <memory>
 #include <vector>
 
 namespace ho {
@@ -104,6 +105,15 @@ struct List {   // structs/attr.h:24-99
 
 typedef uint32_t he_t;   // flat half-edge id = face_offset[f] + local edge
 
+// What every decoded vertex demanded of the predictor (decode of a reference-format stream in the PLY layout, on request): rows in
+// decode numbering -- vertex v's record is record v.  Recording reads the predictor's state and changes nothing of it.
+struct VtxTrace {
+	std::vector<uint32_t> count;        // candidates the fan offered and use_paral kept (attrcode.h:117-134), not capped
+	std::vector<uint32_t> triples;      // 8 x (v0, v1, vo) per vertex in the fan's order (attrcode.h:83-106,155-171), zero padded
+	std::vector<uint64_t> pred;         // per vertex and component: the prediction's bits in the storage type (attrcode.h:182-208)
+	std::vector<uint32_t> comp_first;   // first vertex of every component (cbm/decoder.h:46-77: the ids an initial operation hands out)
+};
+
 struct Mesh {
 	// connectivity (structs/conn.h:72-170, structs/faces.h:18-98)
 	std::vector<uint32_t> foff{0};
@@ -116,6 +126,7 @@ struct Mesh {
 	// one face region bound to list 0, one vertex region bound to list 1, identity element->attribute maps
 	std::vector<List> lists;
 	uint32_t nv = 0, nf = 0;
+	std::shared_ptr<VtxTrace> vtrace;   // decode only, on request
 	// a shard of a larger mesh (sharded container .hry v0.3 of this implementation, see "sharded container" below): sizes of
 	// the whole mesh for the header, the start face of every component in coding order, and the place of every run of
 	// consecutive components in the numbering of the whole decoded mesh
@@ -1324,6 +1335,7 @@ static void cbm_decode(Mesh &m, SymReader &rd, std::vector<uint32_t> &order_v)
 	for (;;) {
 		uint32_t iop = rd.iop();
 		if (iop == IOP_EOM) break;
+		if (m.vtrace) m.vtrace->comp_first.push_back(next_id);
 		uint32_t a = 0, b = 0, c = 0;
 		curtri = 0;
 		switch (iop) {   // decoder.h:46-77
@@ -1433,6 +1445,12 @@ static void decode_attrs(Mesh &m, SymReader &rd, const std::vector<uint32_t> &or
 	pr.vtx_attr = &vattr;
 	const int LV = 1, LF = 0;
 	uint32_t cur = 0;
+	VtxTrace *tr = m.vtrace.get();
+	if (tr) {
+		tr->count.assign(m.lists[LV].count, 0);
+		tr->triples.assign((size_t)m.lists[LV].count * 24, 0);
+		tr->pred.assign((size_t)m.lists[LV].count * m.lists[LV].fmt.size(), 0);
+	}
 	{
 		List &L = m.lists[LV];
 		for (he_t e : order_v) {   // attrcode.h:443-470
@@ -1450,10 +1468,18 @@ static void decode_attrs(Mesh &m, SymReader &rd, const std::vector<uint32_t> &or
 				ctx += nb;
 			}
 			vattr[v] = idx;
+			if (tr) {
+				tr->count[idx] = (uint32_t)pr.cands.size();
+				for (size_t k = 0; k < pr.cands.size() && k < 8; ++k) {
+					uint32_t *t = &tr->triples[(size_t)idx * 24 + 3 * k];
+					t[0] = pr.attr_of(pr.cands[k].v0); t[1] = pr.attr_of(pr.cands[k].v1); t[2] = pr.attr_of(pr.cands[k].vo);
+				}
+			}
 			for (int c = 0; c < L.fmt.size(); ++c) {
 				with_type(L.fmt.stype[c], [&](auto tag) {
 					typedef decltype(tag) T;
 					T pred = pr.predict_component<T>(L, c, L.fmt.quant[c]);
+					if (tr) tr->pred[(size_t)idx * L.fmt.size() + c] = (uint64_t)bitcast<T, typename ints<sizeof(T)>::u>(pred);
 					T d = ld<T>(L.rec(idx) + L.fmt.off[c]);
 					st<T>(L.rec(idx) + L.fmt.off[c], unfold_residual<T>(d, pred, L.fmt.quant[c], std::is_floating_point<T>()));
 				});
@@ -1780,10 +1806,11 @@ static void decode_attrs_general(Mesh &m, SymReader &rd, const std::vector<uint3
 	}
 }
 
-static Mesh *decode(const uint8_t *p, size_t n)
+static Mesh *decode(const uint8_t *p, size_t n, bool trace = false)
 {
 	Mesh *m = new Mesh();
 	try {
+		if (trace) m->vtrace = std::make_shared<VtxTrace>();
 		ByteReader br{ p, p + n };
 		read_header(br, *m);
 		RangeDecoder rc(br.p, p + n);
@@ -1796,6 +1823,7 @@ static Mesh *decode(const uint8_t *p, size_t n)
 		cbm_decode(*m, rd, order_v);
 		m->have_deg = hdr_deg;
 		if (m->num_face() != m->nf) throw std::runtime_error("oracle: face count mismatch");
+		if (m->bind.on && trace) throw std::runtime_error("oracle: the vertex trace covers the PLY layout only");
 		if (m->bind.on) decode_attrs_general(*m, rd, order_v);
 		else decode_attrs(*m, rd, order_v);
 	} catch (...) { delete m; throw; }
@@ -3050,6 +3078,19 @@ ho_mesh *ho_mesh_from_hry(const uint8_t *hry, size_t n)
 	return h;
 	HO_CATCH(nullptr)
 }
+ho_mesh *ho_mesh_from_hry_traced(const uint8_t *hry, size_t n)
+{
+	HO_TRY
+	ho::Mesh *m = ho::decode(hry, n, true);
+	ho_mesh *h = new ho_mesh{ std::move(*m) };
+	delete m;
+	return h;
+	HO_CATCH(nullptr)
+}
+size_t ho_mesh_vtrace_counts(const ho_mesh *m, const uint32_t **out) { const auto &t = m->m.vtrace; *out = t ? t->count.data() : nullptr; return t ? t->count.size() : 0; }
+size_t ho_mesh_vtrace_triples(const ho_mesh *m, const uint32_t **out) { const auto &t = m->m.vtrace; *out = t ? t->triples.data() : nullptr; return t ? t->triples.size() : 0; }
+size_t ho_mesh_vtrace_preds(const ho_mesh *m, const uint64_t **out) { const auto &t = m->m.vtrace; *out = t ? t->pred.data() : nullptr; return t ? t->pred.size() : 0; }
+size_t ho_mesh_vtrace_comp_first(const ho_mesh *m, const uint32_t **out) { const auto &t = m->m.vtrace; *out = t ? t->comp_first.data() : nullptr; return t ? t->comp_first.size() : 0; }
 ho_mesh *ho_mesh_from_obj(const uint8_t *obj, size_t n, const char *dir)
 {
 	HO_TRY

@@ -41,6 +41,10 @@ def lib():
     L.ho_mesh_from_ply.restype = vp; L.ho_mesh_from_ply.argtypes = [C.c_char_p, sz]
     L.ho_mesh_from_hry.restype = vp; L.ho_mesh_from_hry.argtypes = [C.c_char_p, sz]
     L.ho_mesh_clone.restype = vp; L.ho_mesh_clone.argtypes = [vp]
+    L.ho_mesh_from_hry_traced.restype = vp; L.ho_mesh_from_hry_traced.argtypes = [C.c_char_p, sz]
+    for name in ("counts", "triples", "comp_first"):
+        f = getattr(L, "ho_mesh_vtrace_" + name); f.restype = sz; f.argtypes = [vp, C.POINTER(u32p)]
+    L.ho_mesh_vtrace_preds.restype = sz; L.ho_mesh_vtrace_preds.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64))]
     L.ho_mesh_from_obj.restype = vp; L.ho_mesh_from_obj.argtypes = [C.c_char_p, sz, C.c_char_p]
     L.ho_mesh_general.restype = C.c_int; L.ho_mesh_general.argtypes = [vp]
     L.ho_mesh_make_general.argtypes = [vp]
@@ -170,6 +174,26 @@ class Mesh:
     @classmethod
     def from_hry(cls, data: bytes) -> "Mesh":
         return cls(lib().ho_mesh_from_hry(data, len(data)))
+
+    @classmethod
+    def from_hry_traced(cls, data: bytes) -> "Mesh":
+        """from_hry that also records what every vertex demanded of the predictor: see vertex_trace()"""
+        return cls(lib().ho_mesh_from_hry_traced(data, len(data)))
+
+    def vertex_trace(self) -> dict:
+        """of a mesh made by from_hry_traced, rows in decode numbering (vertex v's record is record v):
+        count u32[nv]: candidates of the vertex, not capped; triples u32[nv, 8, 3]: the first eight (v0, v1, vo) in the
+        reference's fan order, zero padded; pred u64[nv, ncomp]: the prediction every component used, its bits in the storage
+        type; comp_first u32[ncomponents]: every component's first vertex, in coding order"""
+        out = {}
+        for name, shape in (("counts", (-1,)), ("triples", (-1, 8, 3)), ("comp_first", (-1,))):
+            p = C.POINTER(C.c_uint32)()
+            n = getattr(lib(), "ho_mesh_vtrace_" + name)(self.h, C.byref(p))
+            out["count" if name == "counts" else name] = _arr(p, n, np.uint32).reshape(shape)
+        p = C.POINTER(C.c_uint64)()
+        n = lib().ho_mesh_vtrace_preds(self.h, C.byref(p))
+        out["pred"] = _arr(p, n, np.uint64).reshape(len(out["count"]), -1) if n else np.zeros((len(out["count"]), 0), np.uint64)
+        return out
 
     @classmethod
     def from_hry_chunked(cls, data: bytes) -> "Mesh":

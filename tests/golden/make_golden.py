@@ -71,6 +71,9 @@ def small_cases():
                      [("ll", []), ("mixed", INT_MIXED)] + [(f"q{q}", _int_width(q)) for q in (5, 8, 9, 16, 17, 24)]),
         "int_face": (mg.with_integer_props(_int_base(), values="full", face=True), "binary_little_endian", [("ll", []), ("q", ["-l0", "-q5"])]),
         "int_bytefirst": (mg.with_integer_props(_int_base(), values="full", byte_first=True), "binary_little_endian", [("ll", [])]),
+        # float sources at the widths next to the storage boundaries and at the narrow end (1, 2; 15 below 16; 17 and 24 in 32-bit
+        # storage): noise heavy enough for clamped parallelograms and far residual codes at every one of them
+        "float_widths": (mg.torus(9, 11, seed=6, sigma=0.03), "binary_little_endian", [(f"q{q}", ["-l1", f"-q{q}"]) for q in (1, 2, 15, 17, 24)]),
         # 8-byte sources of the quantiser (quant.h:137-139); lossless doubles are outside the reference's own defined behaviour
         "grid_double": (mg.doubles(mg.grid(12, 9, seed=3)), "binary_little_endian", [("q14", ["-l1", "-q14"]), ("q30", ["-l1", "-q30"])]),
     }

@@ -36,7 +36,7 @@ for it in range(n_meshes):
     seed = int(rng.integers(1, 99))
     polys = ["tri", "quad", "mixed"][int(rng.integers(0, 3))]
     dims = [int(x) for x in rng.integers(0, 1 << 30, 4)]
-    q = int(rng.integers(2, 17))
+    q = int(rng.integers(2, 25))   # (17 .. 24: 32-bit storage, k_unpredict2<uint32_t>)
     lossless = bool(rng.integers(0, 4) == 0) or bool(os.environ.get("STRESS_LOSSLESS"))
     scale_pow = float(rng.uniform(-43, 37)) if rng.integers(0, 3) == 0 else 0.0   # lossless: magnitudes where float sums overflow or go denormal
     flat_axis = int(rng.integers(0, 6))                                            # lossless: 0 - 2: that coordinate is 0 everywhere (every prediction is 0)
