@@ -46,6 +46,11 @@ class CompError(C.Structure):
                 ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("changed", C.c_uint64), ("argmax", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Tolerance(C.Structure):
+    """hry_tolerance: what hry_quant_choose is to meet on a component (comp -1: every swept component of the list)"""
+    _fields_ = [("list", C.c_int32), ("comp", C.c_int32), ("metric", C.c_int32), ("reserved", C.c_int32), ("value", C.c_double)]
+
+
 class PosError(C.Structure):
     """hry_pos_error: the Euclidean displacement of the positions (hry_distortion_position)"""
     _fields_ = [("max_dist", C.c_double), ("sum_sq_dist", C.c_double), ("compared", C.c_uint64), ("argmax", C.c_uint32), ("list", C.c_int32)]
@@ -80,6 +85,7 @@ NO_ELEMENT = 0xFFFFFFFF
 ORDER_TO_DECODED, ORDER_TO_SOURCE = 0, 1
 INGEST_WELD = 1
 DISTORTION_ROWS = 1
+TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST = 0, 1, 2, 3
 
 _lib = None
 
@@ -193,6 +199,14 @@ def load():
     L.hry_distortion_copy.restype = C.c_int; L.hry_distortion_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_distortion_stat.restype = C.c_int; L.hry_distortion_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_distortion_free.argtypes = [vp]
+    L.hry_quant_sweep_build.restype = C.c_int; L.hry_quant_sweep_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hry_quant_sweep_bits.restype = C.c_int; L.hry_quant_sweep_bits.argtypes = [vp, C.c_int, C.c_int]
+    L.hry_quant_sweep_component.restype = C.c_int; L.hry_quant_sweep_component.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(CompError)]
+    L.hry_quant_sweep_position.restype = C.c_int; L.hry_quant_sweep_position.argtypes = [vp, C.c_int, C.POINTER(PosError)]
+    L.hry_quant_sweep_stat.restype = C.c_int; L.hry_quant_sweep_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hry_quant_sweep_free.argtypes = [vp]
+    L.hry_quant_choose.restype = C.c_int; L.hry_quant_choose.argtypes = [vp, C.POINTER(Tolerance), sz, C.POINTER(Quant), sz, C.POINTER(sz)]
+    L.hry_quant_pick.restype = C.c_int; L.hry_quant_pick.argtypes = [C.POINTER(CompError), C.c_int, C.c_int, C.c_double, C.c_double]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

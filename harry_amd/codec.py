@@ -587,6 +587,13 @@ class Codec:
                                                   nat.DISTORTION_ROWS if rows else 0, C.byref(h)))
         return Distortion(self, h)
 
+    def quant_sweep(self, mesh: Mesh) -> "QuantSweep":
+        """hry_quant_sweep_build: the error of every quantisation width of every unquantised component of `mesh`, in one pass on the
+        device; QuantSweep.choose turns tolerances into the requests for requant"""
+        h = C.c_void_p()
+        nat.check(nat.load().hry_quant_sweep_build(self.h, mesh.h, C.byref(h)))
+        return QuantSweep(h)
+
     def resident(self, mesh: Mesh) -> bool:
         """hry_mesh_resident: this context holds the mesh's records and connectivity in HBM (an encode uploads nothing for it)"""
         return bool(nat.load().hry_mesh_resident(self.h, mesh.h))
@@ -777,6 +784,77 @@ class Distortion(_NamedBuffers):
         """device_ms (the two kernels, by events), uploaded_bytes (records that were not resident)"""
         d, up = C.c_double(), C.c_uint64()
         nat.check(nat.load().hry_distortion_stat(self.h, C.byref(d), C.byref(up)))
+        return {"device_ms": d.value, "uploaded_bytes": up.value}
+
+
+class QuantSweep:
+    """The error at every quantisation width (include/harry_amd.h: hry_quant_sweep_build): per swept component and width the record
+    Distortion.component gives after a requant of a clone to that width, and per width the positions' displacement.  A host table:
+    valid until close(), whatever becomes of the codec."""
+
+    METRICS = {"max_abs": nat.TOL_MAX_ABS, "max_rel": nat.TOL_MAX_REL, "rms": nat.TOL_RMS, "pos_dist": nat.TOL_POS_DIST}
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def close(self):
+        if getattr(self, "h", None):
+            nat.load().hry_quant_sweep_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def bits(self, l: int, c: int) -> int:
+        """the widest width component c of list l was swept at; 0: it was not swept (reason(l, c) says why)"""
+        n = nat.load().hry_quant_sweep_bits(self.h, l, c)
+        if n < 0:
+            nat.check(n)
+        return n
+
+    def reason(self, l: int, c: int) -> str:
+        """why component c of list l was not swept; '' when it was"""
+        return "" if self.bits(l, c) else nat.load().hry_last_error().decode(errors="replace")
+
+    def component(self, l: int, c: int, bits: int) -> dict:
+        """hry_comp_error of component c of list l at `bits`, plus rms: the keys of Distortion.component"""
+        e = nat.CompError()
+        nat.check(nat.load().hry_quant_sweep_component(self.h, l, c, bits, C.byref(e)))
+        out = {k: getattr(e, k) for k, _ in e._fields_ if k != "reserved"}
+        out["rms"] = math.sqrt(e.sum_sq / e.compared) if e.compared else 0.0
+        return out
+
+    def table(self, l: int, c: int) -> list:
+        """component(l, c, bits) for bits = 1 .. bits(l, c): entry bits - 1"""
+        return [self.component(l, c, q) for q in range(1, self.bits(l, c) + 1)]
+
+    def position(self, bits: int) -> dict:
+        """hry_pos_error with the three position components at `bits`, plus rms; list -1: no swept positions"""
+        p = nat.PosError()
+        nat.check(nat.load().hry_quant_sweep_position(self.h, bits, C.byref(p)))
+        out = {k: getattr(p, k) for k, _ in p._fields_}
+        out["rms"] = math.sqrt(p.sum_sq_dist / p.compared) if p.compared else 0.0
+        return out
+
+    def choose(self, tolerances) -> list:
+        """tolerances: iterable of (list, component or -1, metric, value); metric: "max_abs", "max_rel", "rms", "pos_dist" or a
+        nat.TOL_* number.  Returns [(list, component, bits), ...] for Codec.requant: per named component the smallest width that
+        meets its tolerances, 0 (lossless) when none does"""
+        ts = []
+        for l, c, m, v in tolerances:
+            if isinstance(m, str) and m not in self.METRICS:
+                raise HryError(nat.E_ARG, f"unknown tolerance metric {m!r}")
+            ts.append(nat.Tolerance(int(l), int(c), self.METRICS[m] if isinstance(m, str) else int(m), 0, float(v)))
+        arr = (nat.Tolerance * max(len(ts), 1))(*ts)
+        n = C.c_size_t()
+        cap = 32 * 16 + 16
+        out = (nat.Quant * cap)()
+        nat.check(nat.load().hry_quant_choose(self.h, arr, len(ts), out, cap, C.byref(n)))
+        return [(out[i].list, out[i].comp, out[i].bits) for i in range(n.value)]
+
+    def stat(self) -> dict:
+        """device_ms (the two kernels, by events), uploaded_bytes (records that were not resident)"""
+        d, up = C.c_double(), C.c_uint64()
+        nat.check(nat.load().hry_quant_sweep_stat(self.h, C.byref(d), C.byref(up)))
         return {"device_ms": d.value, "uploaded_bytes": up.value}
 
 

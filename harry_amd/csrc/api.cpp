@@ -14,6 +14,7 @@ struct hry_plan { ShardPlan p; };
 struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_distortion { DistortionResult d; };
+struct hry_sweep { SweepResult s; };
 struct hry_walk {
 	WalkResult w; uint32_t info[2]; std::vector<uint8_t> vplanes, fplanes; std::vector<uint32_t> seg_start, seg_level;
 	mutable std::vector<uint8_t> op_sym, op_class;   // unpacked from w.op_sc on first request
@@ -749,6 +750,83 @@ int hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *up
 	return HRY_OK;
 }
 void hry_distortion_free(hry_distortion *d) { delete d; }
+
+// ---- the error of every quantisation width, and widths from tolerances (sweep.cpp).  With the bounds known it leaves the
+// resident mesh and the decode's buffers alone, like hry_distortion_build; without, it computes them as hry_requant does
+int hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	order_lost(ctx);
+	for (const AttrList &L : m->m.lists) if (!L.have_bounds && L.ncomp() && !m->m.partial) { touched(ctx); touched(m); break; }
+	return guarded([&] {
+		std::unique_ptr<hry_sweep> s(new hry_sweep());
+		quant_sweep_build(ctx->cx, m->m, s->s);
+		*out = s.release();
+	});
+}
+static const SweepResult::Comp *sweep_comp(const hry_sweep *s, int l, int c)
+{
+	if (!s) { g_last_error = "null argument"; return nullptr; }
+	if (l < 0 || (size_t)l >= s->s.comp.size()) { g_last_error = "Invalid list index"; return nullptr; }
+	if (c < 0 || (size_t)c >= s->s.comp[l].size()) { g_last_error = "Invalid attribute index"; return nullptr; }
+	return &s->s.comp[l][c];
+}
+int hry_quant_sweep_bits(const hry_sweep *s, int l, int c)
+{
+	const SweepResult::Comp *C = sweep_comp(s, l, c);
+	if (!C) return HRY_E_ARG;
+	if (!C->qmax) g_last_error = C->why;
+	return C->qmax;
+}
+int hry_quant_sweep_component(const hry_sweep *s, int l, int c, int bits, hry_comp_error *out)
+{
+	const SweepResult::Comp *C = sweep_comp(s, l, c);
+	if (!C) return HRY_E_ARG;
+	if (!out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (!C->qmax) { g_last_error = "list " + std::to_string(l) + " attr " + std::to_string(c) + " was not swept: " + C->why; return HRY_E_UNSUPPORTED; }
+	if (bits < 1 || bits > C->qmax) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
+	*out = C->by_bits[bits - 1];
+	return HRY_OK;
+}
+int hry_quant_sweep_position(const hry_sweep *s, int bits, hry_pos_error *out)
+{
+	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (s->s.pos.empty()) {   // no positions, or their three components are not all swept
+		if (bits < 1 || bits > 30) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
+		*out = hry_pos_error{};
+		out->list = -1;
+		return HRY_OK;
+	}
+	if (bits < 1 || (size_t)bits > s->s.pos.size()) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
+	*out = s->s.pos[bits - 1];
+	return HRY_OK;
+}
+int hry_quant_sweep_stat(const hry_sweep *s, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = s->s.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = s->s.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_quant_sweep_free(hry_sweep *s) { delete s; }
+int hry_quant_choose(const hry_sweep *s, const hry_tolerance *t, size_t nt, hry_quant *out, size_t cap, size_t *n_out)
+{
+	if (n_out) *n_out = 0;
+	if (!s || (nt && !t) || !n_out || (cap && !out)) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] {
+		const std::vector<hry_quant> q = quant_choose(s->s, t, nt);
+		*n_out = q.size();
+		if (q.size() > cap) throw Error(HRY_E_ARG, "room for " + std::to_string(cap) + " requests, " + std::to_string(q.size()) + " chosen");
+		for (size_t i = 0; i < q.size(); ++i) out[i] = q[i];
+	});
+}
+int hry_quant_pick(const hry_comp_error *by_bits, int n_bits, int metric, double extent, double value)
+{
+	int bits = 0;
+	const int rc = guarded([&] { bits = quant_pick(by_bits, n_bits, metric, extent, value); });
+	return rc == HRY_OK ? bits : rc;
+}
 
 // ---- meshes from device buffers (ingest.cpp)
 int hry_mesh_from_device(hry_ctx *ctx, uint32_t nv, const hry_dev_column *vcols, int v_ncomp, uint32_t nf, const uint8_t *d_degrees,

@@ -13,7 +13,12 @@
 // (binary PLY of a quantised mesh with every value in the width its header declares; the reference's writer dumps the
 // original-width records, formats/ply/writer.cc:72-75), --report (after the quantisation phase, what it cost: one line per component,
 // "Distortion: list L attr C bits Q max M rms R changed N", the quantised mesh against a clone taken before -- hry_distortion_build
-// with the identity map, since a decode returns the quantised values exactly).
+// with the identity map, since a decode returns the quantised values exactly), --max-error V / --max-error-rel V (a tolerance in
+// place of -q, bound to the preceding -l / -a the same way: the largest error of the component, absolute or as a fraction of its
+// shared extent; the mesh is swept once -- hry_quant_sweep_build -- and the smallest width that meets the tolerance is applied,
+// "Chosen: list L attr C bits Q max M" per component; with -c the mesh is cleared first, swept, and every width is applied to the
+// cleared values; without -a every component of the list is named, as by -q, and one that cannot take a tolerance -- quantised
+// already and no -c, a constant integer -- ends the run with its reason).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -45,9 +50,11 @@ namespace {
 const std::chrono::steady_clock::time_point g_start = std::chrono::steady_clock::now();   // (static initialisation: as early as this program can look)
 long long since_start_ms() { return (long long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - g_start).count(); }
 struct QuantArg { int l, o, q; };
+struct ToleranceArg { int l, o, metric; double value; };
 struct Args {
 	std::string in, out, fmt, profile;   // profile empty: compat, unless --gpus / --shards ask for the sharded container
 	std::vector<QuantArg> quant;
+	std::vector<ToleranceArg> tolerance;
 	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
@@ -58,7 +65,8 @@ const Opt kOpts[] = {
 	{ 'a', "attr", "Select attribute", true }, { 'q', "quant", "Quantization bits", true }, { 'c', "clear-quant", "Clear all quantization first", false },
 	{ 0, "ply-ascii", "PLY writer: Use ASCII format", false }, { 0, "ply-packed", "PLY writer: quantised values in their declared width", false }, { 0, "profile", "compat (reference stream, default) or chunked", true },
 	{ 0, "chunk", "chunked: symbols per chunk", true }, { 0, "device", "GPU index (first one with --gpus)", true }, { 0, "gpus", "N device contexts, one worker thread each", true },
-	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false } };
+	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false },
+	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true } };
 
 void usage(const char *argv0)
 {
@@ -84,6 +92,14 @@ int to_int(const char *argv0, const std::string &v)
 	long x = strtol(v.c_str(), &end, 10);
 	if (v.empty() || *end) arg_error(argv0, "Invalid cast");
 	return (int)x;
+}
+
+double to_double(const char *argv0, const std::string &v)
+{
+	char *end = nullptr;
+	const double x = strtod(v.c_str(), &end);
+	if (v.empty() || *end) arg_error(argv0, "Invalid cast");
+	return x;
 }
 
 Args parse(int argc, const char **argv)
@@ -131,7 +147,18 @@ Args parse(int argc, const char **argv)
 		else if (n == "shards") a.shards = to_int(argv[0], val);
 		else if (n == "gpus") a.gpus = to_int(argv[0], val);
 		else if (n == "report") a.report = true;
+		else if (n == "max-error" || n == "max-error-rel") {
+			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
+			const double v = to_double(argv[0], val);
+			if (!(v >= 0.0)) arg_error(argv[0], "Invalid tolerance");
+			a.tolerance.push_back(ToleranceArg{ cur_l, cur_a, n == "max-error" ? HRY_TOL_MAX_ABS : HRY_TOL_MAX_REL, v });
+			cur_a = -1;
+		}
 	}
+	for (const ToleranceArg &t : a.tolerance)
+		for (const QuantArg &q : a.quant)
+			if (t.l == q.l && (t.o == q.o || t.o == -1 || q.o == -1))
+				arg_error(argv[0], "Invalid option: list " + std::to_string(t.l) + " attr " + std::to_string(t.o == -1 ? q.o : t.o) + " has both -q and a tolerance");
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
@@ -209,11 +236,13 @@ struct Handles {   // released on every path
 	std::vector<hry_ctx*> cx;   // [0]: the context of every single-device step
 	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
 	hry_distortion *dist = nullptr;
+	hry_sweep *sweep = nullptr;
 	std::vector<uint8_t*> bufs;
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
 		if (dist) hry_distortion_free(dist);
+		if (sweep) hry_quant_sweep_free(sweep);
 		if (before) hry_mesh_free(before);
 		if (mesh) hry_mesh_free(mesh);
 		for (hry_ctx *c : cx) hry_ctx_destroy(c);
@@ -285,11 +314,40 @@ int run(const Args &args)
 	// a sharded .hry quantises shard by shard on the workers (the bounds of the whole mesh are combined from the shards'): the
 	// whole mesh never sits on one device
 	const bool quant_in_encode = sharded && type == "hry";
-	const bool quant_phase = (!q.empty() || args.clearquant) && !quant_in_encode;
+	if (!args.tolerance.empty() && quant_in_encode) throw std::runtime_error("--max-error sweeps the whole mesh on one context: not with --gpus / --shards");
+	const bool quant_phase = (!q.empty() || !args.tolerance.empty() || args.clearquant) && !quant_in_encode;
 	if (quant_phase) {
 		std::cout << "Quantization..." << std::endl;
 		if (args.report && !(h.before = hry_mesh_clone(h.mesh))) throw std::runtime_error(hry_last_error());
-		ok(hry_requant(h.cx[0], h.mesh, q.data(), q.size(), args.clearquant ? 1 : 0));   // validation and texts of main.cc:74-91 inside
+		bool cleared = false;
+		if (!args.tolerance.empty()) {
+			// the widths the tolerances need, from one sweep of the mesh as the quantisation finds it.  With -c that is the cleared mesh:
+			// it is cleared here, on its own, and every width -- chosen or explicit -- is then applied to the cleared values, so what is
+			// applied is what was swept (a direct q -> q' rescale of a quantised source truncates: up to a whole step, not the table's)
+			if (args.clearquant) { ok(hry_requant(h.cx[0], h.mesh, nullptr, 0, 1)); cleared = true; }
+			ok(hry_quant_sweep_build(h.cx[0], h.mesh, &h.sweep));
+			std::vector<hry_tolerance> tol;
+			// a tolerance without -a names every component of its list, as -q does: one that cannot take it (quantised already, a
+			// constant integer) is an error with its reason, where the library's comp -1 would leave it out
+			for (const ToleranceArg &t : args.tolerance) {
+				const bool all = t.o == -1 && t.l >= 0 && t.l < hry_mesh_nlists(h.mesh);
+				if (!all) tol.push_back(hry_tolerance{ t.l, t.o, t.metric, 0, t.value });
+				else for (int c = 0; c < hry_list_ncomp(h.mesh, t.l); ++c) tol.push_back(hry_tolerance{ t.l, c, t.metric, 0, t.value });
+			}
+			size_t n = 0;
+			std::vector<hry_quant> chosen((size_t)16 * 32);
+			ok(hry_quant_choose(h.sweep, tol.data(), tol.size(), chosen.data(), chosen.size(), &n));
+			for (size_t i = 0; i < n; ++i) {
+				hry_comp_error e{};
+				if (chosen[i].bits) ok(hry_quant_sweep_component(h.sweep, chosen[i].list, chosen[i].comp, chosen[i].bits, &e));
+				char line[160];
+				snprintf(line, sizeof line, "Chosen: list %d attr %d bits %d max %.9g", chosen[i].list, chosen[i].comp, chosen[i].bits, e.max_abs);
+				std::cout << line << std::endl;
+				q.push_back(chosen[i]);
+			}
+			hry_quant_sweep_free(h.sweep); h.sweep = nullptr;
+		}
+		ok(hry_requant(h.cx[0], h.mesh, q.data(), q.size(), args.clearquant && !cleared ? 1 : 0));   // validation and texts of main.cc:74-91 inside
 	}
 	Clock::time_point t2 = Clock::now();
 	if (quant_phase) std::cout << "Quantization took " << ms(t1, t2) << " ms." << std::endl;

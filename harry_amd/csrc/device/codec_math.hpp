@@ -237,5 +237,25 @@ HRY_HD uint32_t div_by_magic32(uint32_t n, uint32_t m, uint32_t sh)
 #endif
 }
 
+// the raw bits v of a value of component type `type` (mixing::Type; in the low bytes of the word) as a double: floats widen exactly,
+// 64-bit integers round to nearest.  The one statement of the rule for the error statistics (dist_reduce.hpp) and the extent of
+// a tolerance (sweep.cpp)
+HRY_HD double value_f64(uint64_t v, int type)
+{
+	switch (type) {
+	case 0: return (double)bits<float>((uint32_t)v);
+	case 1: return bits<double>(v);
+	case 2: return (double)v;
+	case 3: return (double)(int64_t)v;
+	case 4: return (double)(uint32_t)v;
+	case 5: return (double)(int32_t)(uint32_t)v;
+	case 6: return (double)(uint16_t)v;
+	case 7: return (double)(int16_t)(uint16_t)v;
+	case 8: return (double)(uint8_t)v;
+	case 9: return (double)(int8_t)(uint8_t)v;
+	default: return 0.0;
+	}
+}
+
 }   // namespace cm
 }   // namespace hry

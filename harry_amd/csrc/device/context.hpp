@@ -103,6 +103,7 @@ struct Context {
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
 	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
+	DevBuf d_sweep;   // hry_quant_sweep_build: its uploads (a mesh that is not resident), the blocks' records and the results (sweep.cpp)
 	DevBuf d_ingest;   // hry_mesh_from_device: status word, scans, the weld's keys and table (ingest.cpp)
 	DevBuf d_split;   // chunked encode in two kernels: per stream the place of its records and the streams' order, longest first (the records: d_rec_sym)
 	DevBuf d_pipe, d_nt_val, d_nt_planes;   // EncodePipeline: run tables and twin pairs of the batches; the polygons' triangle counts and their two byte planes
@@ -231,6 +232,28 @@ struct DistortionResult : DeviceResult {             // bufs: "error<l>" with HR
 	uint64_t uploaded_bytes = 0;
 };
 void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out);
+bool distortion_compares(const Mesh &m, size_t l);   // list l is one hry_distortion_build compares
+int distortion_position_list(const Mesh &m);         // the list whose first three POS components are the positions, or -1
+
+// sweep.cpp: the error of every quantisation width of m's unquantised components (include/harry_amd.h: hry_quant_sweep_build).
+// The result is the host table only
+struct SweepResult {
+	struct Comp {
+		int qmax = 0, type = 0;          // swept at 1 .. qmax bits; 0: not swept, `why` says why
+		std::string why;
+		double extent = 0;               // the shared extent (requant_plan's scale) as a double
+		std::vector<hry_comp_error> by_bits;   // [qmax], index bits - 1
+	};
+	std::vector<std::vector<Comp>> comp;   // per list and component
+	int pos_list = -1, pos_comp = -1;      // the position list and the first of its three components (-1: none)
+	std::vector<hry_pos_error> pos;        // [min of the three qmax], index bits - 1; empty: the three are not all swept
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out);   // (computes bounds where unset, as device_requant does)
+// host only: the smallest width whose record meets (metric, value), 0: none; and the requests that meet a set of tolerances
+int quant_pick(const hry_comp_error *by_bits, int n_bits, int metric, double extent, double value);
+std::vector<hry_quant> quant_choose(const SweepResult &s, const hry_tolerance *t, size_t nt);
 
 // order.cpp.  order_build: at the end of an encode with cx.want_order -- m's connectivity is in d_foff / d_org (conn_view), w is the
 // encode's walk; d_order_v / d_order_f: the walk's orders where the encode has them whole in HBM, else nullptr (they go up from w);

@@ -1,5 +1,6 @@
 // Rescaling of quantised values (structs/quant.h:98-112) and the dequantisation into a component's original type
-// (quant.h:180-212), on the device.  Shared by k_requant (kernels.hip, in place) and k_render_gather (render.hip, to f32).
+// (quant.h:180-212), on the device.  Shared by k_requant (kernels.hip, in place), k_render_gather (render.hip, to f32),
+// k_distortion_rows (distortion.hip) and k_quant_sweep (sweep.hip, every width in registers).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 
 #include "codec_math.hpp"
 #include "dev_types.hpp"
+#include "fan.hpp"
 
 namespace hry {
 namespace dev {
@@ -46,6 +48,39 @@ __device__ __forceinline__ uint64_t dequantise_bits(uint64_t q, const RequantCom
 	default: return 0;
 	}
 }
+
+// the raw bits of an unquantised component of type `type`, in the low bytes of the word
+__device__ __forceinline__ uint64_t load_raw(const uint8_t *slot, int type)
+{
+	switch (type) {
+	case 1: case 2: case 3: return ldg<uint64_t>(slot);
+	case 6: case 7: return ldg<uint16_t>(slot);
+	case 8: case 9: return ldg<uint8_t>(slot);
+	default: return ldg<uint32_t>(slot);
+	}
+}
+
+// an unquantised value (raw: load_raw of c.src_type) -> its c.dst_bits quantisation bits (quant.h:131-166), before the store
+// narrows them (stored_bits)
+__device__ __forceinline__ uint64_t quantise_raw(uint64_t raw, const RequantComp &c)
+{
+	const int lv = (1 << (uint32_t)c.dst_bits) - 1;   // levels of the destination; evaluated in int like the reference (quant.h:135)
+	switch (c.src_type) {
+	case 0: return cm::quantise_f32(cm::bits<float>((uint32_t)raw), cm::bits<float>((uint32_t)c.mn), cm::bits<float>((uint32_t)c.scale), c.dst_bits);
+	case 1: return (uint64_t)(rescale_fp<double>(cm::bits<double>(raw) - cm::bits<double>(c.mn), cm::bits<double>(c.scale), (double)lv) + 0.5);
+	case 2: return rescale_int<uint64_t>(raw - c.mn, c.scale, (uint64_t)lv);
+	case 3: return (uint64_t)rescale_int<int64_t>((int64_t)(raw - c.mn), (int64_t)c.scale, (int64_t)lv);   // (the distance to the minimum wraps)
+	case 4: return rescale_int<uint32_t>((uint32_t)raw - (uint32_t)c.mn, (uint32_t)c.scale, (uint32_t)lv);
+	case 5: return (uint64_t)rescale_int<int32_t>((int32_t)((uint32_t)raw - (uint32_t)c.mn), (int32_t)c.scale, (int32_t)lv);
+	case 6: return rescale_int<uint16_t>((uint16_t)((uint16_t)raw - (uint16_t)c.mn), (uint16_t)c.scale, (uint16_t)lv);
+	case 7: return (uint64_t)rescale_int<int16_t>((int16_t)((int16_t)(uint16_t)raw - (int16_t)c.mn), (int16_t)c.scale, (int16_t)lv);
+	case 8: return rescale_int<uint8_t>((uint8_t)((uint8_t)raw - (uint8_t)c.mn), (uint8_t)c.scale, (uint8_t)lv);
+	case 9: return (uint64_t)rescale_int<int8_t>((int8_t)((int8_t)(uint8_t)raw - (int8_t)c.mn), (int8_t)c.scale, (int8_t)lv);
+	default: return 0;
+	}
+}
+// what a slot keeps of q at `bits` quantisation bits: its storage type is u8 up to 8 bits, u16 up to 16, u32 above (mixing.h:101-108)
+__device__ __forceinline__ uint64_t stored_bits(uint64_t q, int bits) { return bits <= 8 ? (uint8_t)q : bits <= 16 ? (uint16_t)q : (uint32_t)q; }
 
 }   // namespace dev
 }   // namespace hry

@@ -146,5 +146,17 @@ struct DistFold {
 	int32_t n, pad;
 };
 
+// sweep.hip: one swept (unquantised) component of a list -- rc as requant_plan gives it (offset, type, minimum, shared extent; the
+// bits are the kernel's) -- swept at 1 .. qmax bits; its record of width q is slot + q - 1 of the list's ns
+struct SweepComp { RequantComp rc; int32_t qmax; uint32_t slot; };
+// one list of a sweep: job j < n is component c[j]; job n (pos >= 0) the positions, components c[pos .. pos + 2] at one width
+struct SweepList {
+	const uint8_t *rec;
+	DistPart *part;      // [blocks][ns]
+	uint32_t rows, stride, ns, pos_slot;
+	int32_t n, pos, pos_qmax, pad;
+	SweepComp c[kMaxComp];
+};
+
 }   // namespace dev
 }   // namespace hry

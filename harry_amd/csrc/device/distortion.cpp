@@ -31,6 +31,9 @@ int position_list(const Mesh &m)
 
 }   // namespace
 
+bool distortion_compares(const Mesh &m, size_t l) { return compared(m, l); }
+int distortion_position_list(const Mesh &m) { return position_list(m); }
+
 void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out)
 {
 	if (flags & ~(uint32_t)HRY_DISTORTION_ROWS) throw Error(HRY_E_ARG, "unknown distortion flag");

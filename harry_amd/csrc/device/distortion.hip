@@ -9,6 +9,7 @@
 //                      and is not followed.
 //   k_distortion_fold  one block per list: lane t joins its contiguous span of the blocks' records, the lanes join pairwise in
 //                      LDS -- always neighbours, so everything stays in block order.
+// (The statistics and their joins: dist_reduce.hpp, shared with sweep.hip.)
 // Every join is written out in one fixed order that depends on the row count alone: no floating-point atomics, the same bits
 // from run to run.  e*e is rounded on its own (-ffp-contract=off).
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "codec_math.hpp"
 #include "dequant.hpp"
 #include "dev_types.hpp"
+#include "dist_reduce.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
 
@@ -24,12 +26,12 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kNone = kDistNone;
 constexpr int kLanes = 256, kWaves = kLanes / 64, kRowsPerLane = (int)(kDistBlockRows / kLanes);
 static_assert(kRowsPerLane * kLanes == (int)kDistBlockRows, "a block's rows are a multiple of its lanes");
 
-// the component's value after hry_requant(clear) -- quantised ones through dequantise_bits, the others as stored -- as a double:
-// floats widen exactly, 64-bit integers round to nearest
+// the component's value after hry_requant(clear) -- quantised ones through dequantise_bits, the others as stored -- as a double
+// (value_f64, dist_reduce.hpp)
 __device__ __forceinline__ double component_f64(const uint8_t *slot, const RequantComp &c)
 {
 	uint64_t v;
@@ -42,58 +44,8 @@ __device__ __forceinline__ double component_f64(const uint8_t *slot, const Requa
 		default: q = ldg<uint64_t>(slot); break;
 		}
 		v = dequantise_bits(q, c);
-	} else {
-		switch (c.dst_type) {
-		case 1: case 2: case 3: v = ldg<uint64_t>(slot); break;
-		case 6: case 7: v = ldg<uint16_t>(slot); break;
-		case 8: case 9: v = ldg<uint8_t>(slot); break;
-		default: v = ldg<uint32_t>(slot); break;
-		}
-	}
-	switch (c.dst_type) {
-	case 0: return (double)cm::bits<float>((uint32_t)v);
-	case 1: return cm::bits<double>(v);
-	case 2: return (double)v;
-	case 3: return (double)(int64_t)v;
-	case 4: return (double)(uint32_t)v;
-	case 5: return (double)(int32_t)(uint32_t)v;
-	case 6: return (double)(uint16_t)v;
-	case 7: return (double)(int16_t)(uint16_t)v;
-	case 8: return (double)(uint8_t)v;
-	case 9: return (double)(int8_t)(uint8_t)v;
-	default: return 0.0;
-	}
-}
-__device__ __forceinline__ bool finite_f64(double x) { return (cm::bits<uint64_t>(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-
-template <typename P> __device__ __forceinline__ void clear(P &p)
-{
-	p.mx = 0.0; p.sum = 0.0; p.mn = cm::bits<double>(0x7ff0000000000000ull); p.mxa = cm::bits<double>(0xfff0000000000000ull);
-	p.row = kNone; p.compared = 0; p.skipped = 0; p.nonfinite = 0; p.changed = 0;
-}
-// the larger maximum, between equal ones the lower row (a part without a compared pair holds (0, kNone): any compared pair beats it)
-template <typename P> __device__ __forceinline__ void offer(P &p, double v, uint32_t row)
-{
-	if (v > p.mx || (v == p.mx && row < p.row)) { p.mx = v; p.row = row; }
-}
-// b's rows lie behind a's: a.sum + b.sum in that order
-template <typename P, typename Q> __device__ __forceinline__ void join(P &a, const Q &b)
-{
-	offer(a, b.mx, b.row);
-	a.sum = a.sum + b.sum;
-	a.mn = b.mn < a.mn ? b.mn : a.mn;
-	a.mxa = b.mxa > a.mxa ? b.mxa : a.mxa;
-	a.compared += b.compared; a.skipped += b.skipped; a.nonfinite += b.nonfinite; a.changed += b.changed;
-}
-__device__ __forceinline__ void wave_join(DistPart &p)
-{
-	for (int off = 32; off > 0; off >>= 1) {   // lane 0 ends with the lanes' parts joined in a fixed tree
-		DistPart o;
-		o.mx = __shfl_down(p.mx, off); o.sum = __shfl_down(p.sum, off); o.mn = __shfl_down(p.mn, off); o.mxa = __shfl_down(p.mxa, off);
-		o.row = __shfl_down(p.row, off); o.compared = __shfl_down(p.compared, off); o.skipped = __shfl_down(p.skipped, off);
-		o.nonfinite = __shfl_down(p.nonfinite, off); o.changed = __shfl_down(p.changed, off);
-		join(p, o);
-	}
+	} else v = load_raw(slot, c.dst_type);
+	return value_f64(v, c.dst_type);
 }
 
 }   // namespace
@@ -135,21 +87,11 @@ __global__ __launch_bounds__(256) void k_distortion_rows(DistList L, RequantPlan
 		for (int k = 0; k < kRowsPerLane; ++k) {
 			if (!mapped[k]) continue;
 			const double x = component_f64(ra[k] + ca.off, ca), y = component_f64(rb[k] + cb.off, cb);
-			if (finite_f64(x) && finite_f64(y)) {
-				const double e = y - x, sq = e * e;
-				offer(p, fabs(e), (uint32_t)(base + (uint64_t)k * kLanes + t));
-				p.sum = p.sum + sq;
-				p.mn = x < p.mn ? x : p.mn;
-				p.mxa = x > p.mxa ? x : p.mxa;
-				p.compared += 1;
-				p.changed += e != 0.0;
+			double sq;
+			if (tally(p, x, y, (uint32_t)(base + (uint64_t)k * kLanes + t), sq)) {
 				esq[k] = esq[k] + sq;
 				if (is_pos) d2[k] = c == L.pos ? sq : d2[k] + sq;   // (ex*ex + ey*ey) + ez*ez
-			} else {
-				p.nonfinite += 1;
-				p.changed += cm::bits<uint64_t>(x) != cm::bits<uint64_t>(y);
-				if (is_pos) pos_ok[k] = false;
-			}
+			} else if (is_pos) pos_ok[k] = false;
 		}
 		wave_join(p);
 		if (lane == 0) s_part[c][wave] = p;
@@ -175,36 +117,14 @@ __global__ __launch_bounds__(256) void k_distortion_rows(DistList L, RequantPlan
 	}
 	__syncthreads();
 	const uint32_t nslots = (uint32_t)pa.n + (L.pos >= 0 ? 1u : 0u);
-	if (t < nslots) {
-		DistPart p = s_part[t][0];
-		for (int w = 1; w < kWaves; ++w) join(p, s_part[t][w]);
-		p.pad[0] = p.pad[1] = p.pad[2] = 0;
-		L.part[(size_t)blockIdx.x * nslots + t] = p;
-	}
+	if (t < nslots) L.part[(size_t)blockIdx.x * nslots + t] = block_join<kWaves>(s_part[t]);
 }
 
 __global__ __launch_bounds__(256) void k_distortion_fold(DistFold f, DistFinal *out)
 {
 	__shared__ DistFinal s[kLanes];
-	const uint32_t t = threadIdx.x, l = blockIdx.x;
-	const DistPart *part = f.part[l];
-	const uint32_t nb = f.nblocks[l], ns = f.nslots[l];
-	const uint32_t per = (nb + kLanes - 1) / kLanes;
-	const uint32_t b0 = min(nb, t * per), b1 = min(nb, b0 + per);   // (nb < 2^22: t * per stays below 2^32)
-	for (uint32_t c = 0; c < ns; ++c) {
-		DistFinal a;
-		clear(a);
-		a.reserved = 0;
-		for (uint32_t b = b0; b < b1; ++b) join(a, part[(size_t)b * ns + c]);
-		s[t] = a;
-		__syncthreads();
-		for (uint32_t d = 1; d < (uint32_t)kLanes; d <<= 1) {
-			if ((t & (2 * d - 1)) == 0) join(s[t], s[t + d]);
-			__syncthreads();
-		}
-		if (t == 0) out[f.out_at[l] + c] = s[0];
-		__syncthreads();
-	}
+	const uint32_t l = blockIdx.x;
+	for (uint32_t c = 0; c < f.nslots[l]; ++c) fold_slot<kLanes>(f.part[l], f.nblocks[l], f.nslots[l], c, s, out + f.out_at[l] + c);
 }
 
 void launch_distortion_rows(hipStream_t st, const DistList &L, const RequantPlan &pa, const RequantPlan &pb, uint32_t *status)

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64) void k_bounds_final(const uint8_t *part_min, co
 // float / 1-2-4 byte integers, or an already quantised value (q -> q').  src and dst alias the same slot
 // (attr.h:95-98); the destination is written in its storage type into the low bytes of the slot.
 // ---------------------------------------------------------------------------------------------------------
-// (rescale_int / rescale_fp / dequantise_bits: dequant.hpp)
+// (rescale_int / rescale_fp / quantise_raw / dequantise_bits: dequant.hpp)
 __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, int stride, RequantPlan plan)
 {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
@@ -173,7 +173,6 @@ __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, i
 			const RequantComp &c = plan.c[k];
 			uint8_t *slot = r + c.off;
 			uint64_t q = 0;
-			const int lv = (1 << (uint32_t)c.dst_bits) - 1;   // levels of the destination; evaluated in int like the reference (quant.h:135)
 			if (c.src_bits) {   // already quantised: read the storage type (quant.h:121-129)
 				switch (c.src_type) {
 				case 8: q = ldg<uint8_t>(slot); break;
@@ -181,22 +180,9 @@ __global__ __launch_bounds__(256) void k_requant(uint8_t *rec, uint32_t count, i
 				case 4: q = ldg<uint32_t>(slot); break;
 				default: q = ldg<uint64_t>(slot); break;
 				}
+				const int lv = (1 << (uint32_t)c.dst_bits) - 1;   // levels of the destination; evaluated in int like the reference (quant.h:135)
 				if (c.dst_bits) q = rescale_int<uint64_t>(q, (uint64_t)((1 << (uint32_t)c.src_bits) - 1), (uint64_t)lv);   // q -> q' (quant.h:169-171)
-			} else {
-				switch (c.src_type) {   // quant.h:131-166
-				case 0: q = cm::quantise_f32(ldg<float>(slot), cm::bits<float>((uint32_t)c.mn), cm::bits<float>((uint32_t)c.scale), c.dst_bits); break;
-				case 1: q = (uint64_t)(rescale_fp<double>(ldg<double>(slot) - cm::bits<double>(c.mn), cm::bits<double>(c.scale), (double)lv) + 0.5); break;
-				case 2: q = rescale_int<uint64_t>(ldg<uint64_t>(slot) - c.mn, c.scale, (uint64_t)lv); break;
-				case 3: q = (uint64_t)rescale_int<int64_t>((int64_t)(ldg<uint64_t>(slot) - c.mn), (int64_t)c.scale, (int64_t)lv); break;   // (the distance to the minimum wraps)
-				case 4: q = rescale_int<uint32_t>(ldg<uint32_t>(slot) - (uint32_t)c.mn, (uint32_t)c.scale, (uint32_t)lv); break;
-				case 5: q = (uint64_t)rescale_int<int32_t>((int32_t)(ldg<uint32_t>(slot) - (uint32_t)c.mn), (int32_t)c.scale, (int32_t)lv); break;
-				case 6: q = rescale_int<uint16_t>((uint16_t)(ldg<uint16_t>(slot) - (uint16_t)c.mn), (uint16_t)c.scale, (uint16_t)lv); break;
-				case 7: q = (uint64_t)rescale_int<int16_t>((int16_t)(ldg<int16_t>(slot) - (int16_t)c.mn), (int16_t)c.scale, (int16_t)lv); break;
-				case 8: q = rescale_int<uint8_t>((uint8_t)(ldg<uint8_t>(slot) - (uint8_t)c.mn), (uint8_t)c.scale, (uint8_t)lv); break;
-				case 9: q = (uint64_t)rescale_int<int8_t>((int8_t)(ldg<int8_t>(slot) - (int8_t)c.mn), (int8_t)c.scale, (int8_t)lv); break;
-				default: break;
-				}
-			}
+			} else q = quantise_raw(load_raw(slot, c.src_type), c);   // quant.h:131-166
 			if (c.dst_bits) {
 				if (c.dst_bits <= 8) stg<uint8_t>(slot, (uint8_t)q);
 				else if (c.dst_bits <= 16) stg<uint16_t>(slot, (uint16_t)q);

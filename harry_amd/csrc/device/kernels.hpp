@@ -216,6 +216,12 @@ constexpr uint32_t kDistBlockRows = 1024;
 inline uint32_t distortion_blocks(uint32_t rows) { return (uint32_t)(((uint64_t)rows + kDistBlockRows - 1) / kDistBlockRows); }
 void launch_distortion_rows(hipStream_t st, const DistList &L, const RequantPlan &pa, const RequantPlan &pb, uint32_t *status);
 void launch_distortion_fold(hipStream_t st, const DistFold &f, DistFinal *out);
+// the error of every quantisation width of a list's unquantised components in one pass (sweep.hip; driver: sweep.cpp): blocks of
+// kDistBlockRows rows x jobs x groups of kSweepGroup widths leave one DistPart per block and (component, width) in L.part;
+// launch_quant_sweep_fold: one block per record of f's lists (nslots = a list's ns), the blocks' records in block order
+constexpr int kSweepGroup = 2, kSweepMaxBits = 30;
+void launch_quant_sweep(hipStream_t st, const SweepList &L);
+void launch_quant_sweep_fold(hipStream_t st, const DistFold &f, DistFinal *out);
 
 // meshes from device buffers (ingest.hip; driver: ingest.cpp).  The checks raise bits of err; total = sum of the degrees (64-bit),
 // degmask = the set of degrees present (bit d)

@@ -18,6 +18,7 @@
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
  *   hry_distortion_build (no counterpart: the per-component error of a decode against its source, reduced on the device)
+ *   hry_quant_sweep_build (no counterpart: that error at every quantisation width in one pass, and the width a tolerance needs)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -463,6 +464,66 @@ int  hry_distortion_get(const hry_distortion *d, const char *name, const void **
 int  hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device);
 int  hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes);
 void hry_distortion_free(hry_distortion *d);
+
+/* ---- a quantisation from a tolerance: the error at every bit width in one pass, on the device --------------------------
+ * hry_quant_sweep_build reads every unquantised component of m once and, in registers, takes each value through hry_requant's
+ * quantiser and the -c dequantiser at every width it can have: a table of hry_comp_error records per (list, component, bits).
+ * hry_quant_choose turns tolerances into the hry_quant requests that meet them, ready for hry_requant.
+ *   Swept: the lists hry_distortion_build compares; of them every component with 0 quantisation bits that hry_requant accepts, at
+ *     every width 1 .. qmax = min(30, 8 * sizeof(type)).  Not swept (hry_quant_sweep_bits 0, hry_last_error says why): a component
+ *     that is already quantised, one that hry_requant refuses (a constant integer component, a signed one over its type's whole
+ *     range), and the components of a list that is not compared.
+ *   Equivalence to the loop it replaces: with q = hry_mesh_clone(m), hry_requant(ctx, q, {l, c, bits}, 1, 0) and
+ *     hry_distortion_build(ctx, m, q, NULL, 0), the record of (l, c, bits) equals hry_distortion_component(l, c) of that build
+ *     field for field (skipped is 0), up to the association of sum_sq.  The arithmetic is hry_requant's own, not a closed form:
+ *     floats are evaluated in float, integers through the reference's wrapping rescale, the extent is shared over an
+ *     interpretation group.  The table therefore need not be monotone in bits.
+ *   Positions: for the position list of hry_distortion_build, when its three position components are all swept, one hry_pos_error
+ *     per width 1 .. the least of their qmax: what that build's hry_distortion_position gives with all three quantised to `bits`.
+ *   max_abs, argmax, a_min, a_max and the counters are exact.  sum_sq has the same bits from run to run and whether m was resident
+ *     or uploaded: a reduction tree fixed by the row count alone, no floating-point atomics.
+ *   Bounds: where a list of m has none they are computed first, exactly as hry_requant does (m becomes ctx's resident mesh, and
+ *     what ctx held of a decode is gone).  With the bounds known nothing is disturbed: when m is ctx's resident mesh
+ *     (hry_mesh_resident) its records are read in place, otherwise they go up into the build's own working buffer
+ *     (uploaded_bytes); the resident mesh and the buffers of a decode stay what they were.
+ *   Refusals: a partial mesh, a list without its records: HRY_E_ARG; more than 16 lists, more than 32 components in a compared
+ *     list: HRY_E_UNSUPPORTED.  *out stays NULL and ctx stays usable.
+ *   The handle holds the host table only: no device memory.  It may outlive the context.
+ *   hry_quant_sweep_bits       qmax of component c of list l; 0: not swept (hry_last_error: why); a bad l or c: HRY_E_ARG
+ *   hry_quant_sweep_component  the record at `bits`; bits outside 1 .. qmax, a bad l or c: HRY_E_ARG; not swept: HRY_E_UNSUPPORTED
+ *   hry_quant_sweep_position   the positions' record at `bits` (outside 1 .. the least qmax of the three: HRY_E_ARG); list -1,
+ *                              everything else 0: the mesh has no positions, or they are not all swept
+ *   hry_quant_sweep_stat       device_ms: the two kernels, by events; uploaded_bytes: the records that went up
+ * hry_quant_choose, host only, on the table.  Per component that a tolerance names the request is the SMALLEST bits whose record
+ * meets every tolerance on that component AT THAT WIDTH -- the table need not be monotone, so a wider width is not promised to:
+ *     HRY_TOL_MAX_ABS   max_abs <= value
+ *     HRY_TOL_MAX_REL   max_abs <= value * extent; extent: the component's shared extent (the scale hry_requant divides by), as a double
+ *     HRY_TOL_RMS       sqrt(sum_sq / compared) <= value; not met when compared == 0
+ *     HRY_TOL_POS_DIST  comp must be -1 and list the position list: one width for the three position components, max_dist <= value
+ *   comp -1: every swept component of the list.  Requests come in the order the tolerances first name their components; *n_out is
+ *   their number, also when cap is too small (HRY_E_ARG, nothing written).  No width meets the tolerances: the request is bits 0
+ *   (the component stays lossless) -- but for HRY_DOUBLE, which cannot be coded lossless: HRY_E_UNSUPPORTED, naming list and component.
+ *   A negative or NaN value, an unknown metric, a bad list or component, POS_DIST on another list or with a comp: HRY_E_ARG.  A
+ *   component named that was not swept (positions that were not): HRY_E_UNSUPPORTED with the stored reason.
+ * hry_quant_pick, host only, needs no device and no handle: the smallest bits in 1 .. n_bits whose record by_bits[bits - 1] meets
+ *   (metric, value), 0: none does; HRY_TOL_POS_DIST, a negative or NaN value, n_bits < 0: HRY_E_ARG. */
+typedef struct hry_sweep hry_sweep;
+int  hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out);
+int  hry_quant_sweep_bits(const hry_sweep *s, int l, int c);
+int  hry_quant_sweep_component(const hry_sweep *s, int l, int c, int bits, hry_comp_error *out);
+int  hry_quant_sweep_position(const hry_sweep *s, int bits, hry_pos_error *out);
+int  hry_quant_sweep_stat(const hry_sweep *s, double *device_ms, uint64_t *uploaded_bytes);
+void hry_quant_sweep_free(hry_sweep *s);
+enum { HRY_TOL_MAX_ABS = 0, HRY_TOL_MAX_REL = 1, HRY_TOL_RMS = 2, HRY_TOL_POS_DIST = 3 };
+typedef struct hry_tolerance {
+    int32_t list;
+    int32_t comp;          /* -1: every swept component of the list */
+    int32_t metric;        /* HRY_TOL_* */
+    int32_t reserved;
+    double  value;
+} hry_tolerance;
+int  hry_quant_choose(const hry_sweep *s, const hry_tolerance *t, size_t nt, hry_quant *out, size_t cap, size_t *n_out);
+int  hry_quant_pick(const hry_comp_error *by_bits /* [n_bits], index bits - 1 */, int n_bits, int metric, double extent, double value);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
