@@ -207,6 +207,17 @@ def load():
     L.hry_quant_sweep_free.argtypes = [vp]
     L.hry_quant_choose.restype = C.c_int; L.hry_quant_choose.argtypes = [vp, C.POINTER(Tolerance), sz, C.POINTER(Quant), sz, C.POINTER(sz)]
     L.hry_quant_pick.restype = C.c_int; L.hry_quant_pick.argtypes = [C.POINTER(CompError), C.c_int, C.c_int, C.c_double, C.c_double]
+    L.hry_rate_sweep_build.restype = C.c_int; L.hry_rate_sweep_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hry_rate_sweep_coded.restype = C.c_uint32; L.hry_rate_sweep_coded.argtypes = [vp]
+    L.hry_rate_sweep_bits.restype = C.c_int; L.hry_rate_sweep_bits.argtypes = [vp, C.c_int, C.c_int]
+    L.hry_rate_sweep_planes.restype = C.c_int; L.hry_rate_sweep_planes.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.hry_rate_sweep_hist.restype = C.c_int; L.hry_rate_sweep_hist.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
+    L.hry_rate_sweep_bytes.restype = C.c_int; L.hry_rate_sweep_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.hry_rate_sweep_stat.restype = C.c_int; L.hry_rate_sweep_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hry_rate_sweep_free.argtypes = [vp]
+    L.hry_rate_hist_bytes.restype = C.c_int; L.hry_rate_hist_bytes.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    L.hry_rate_pick.restype = C.c_int; L.hry_rate_pick.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_double]
+    L.hry_rate_choose.restype = C.c_int; L.hry_rate_choose.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     if L.hry_abi_version() != 6:
         raise ImportError(f"{LIB_PATH} has ABI version {L.hry_abi_version()}, this binding expects 6: rebuild it")
     _lib = L

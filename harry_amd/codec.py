@@ -594,6 +594,14 @@ class Codec:
         nat.check(nat.load().hry_quant_sweep_build(self.h, mesh.h, C.byref(h)))
         return QuantSweep(h)
 
+    def rate_sweep(self, mesh: Mesh) -> "RateSweep":
+        """hry_rate_sweep_build: the byte-plane histograms of the residual codes of list 1's components at every quantisation width,
+        in one pass over the coding order; RateSweep.choose turns a byte budget into a width.  Walks `mesh` and leaves it resident,
+        as write_hry does"""
+        h = C.c_void_p()
+        nat.check(nat.load().hry_rate_sweep_build(self.h, mesh.h, C.byref(h)))
+        return RateSweep(h)
+
     def resident(self, mesh: Mesh) -> bool:
         """hry_mesh_resident: this context holds the mesh's records and connectivity in HBM (an encode uploads nothing for it)"""
         return bool(nat.load().hry_mesh_resident(self.h, mesh.h))
@@ -856,6 +864,89 @@ class QuantSweep:
         d, up = C.c_double(), C.c_uint64()
         nat.check(nat.load().hry_quant_sweep_stat(self.h, C.byref(d), C.byref(up)))
         return {"device_ms": d.value, "uploaded_bytes": up.value}
+
+
+def rate_hist_bytes(hist) -> float:
+    """hry_rate_hist_bytes: the zeroth-order entropy of a 256-bin histogram, in bytes"""
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (256,):
+        raise HryError(nat.E_ARG, "a histogram has 256 bins")
+    out = C.c_double()
+    nat.check(nat.load().hry_rate_hist_bytes(h.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out)))
+    return out.value
+
+
+def rate_pick(bytes_by_bits, budget: float, n_bits: int | None = None) -> int:
+    """hry_rate_pick: the largest width in 1 .. n_bits whose entry (index bits - 1) is at most `budget`; 0: none"""
+    t = np.ascontiguousarray(bytes_by_bits, np.float64).reshape(-1)
+    n = len(t) if n_bits is None else n_bits
+    buf = t if len(t) else np.zeros(1)
+    bits = nat.load().hry_rate_pick(buf.ctypes.data_as(C.POINTER(C.c_double)), n, float(budget))
+    if bits < 0:
+        nat.check(bits)
+    return bits
+
+
+class RateSweep:
+    """The coded size at every quantisation width (include/harry_amd.h: hry_rate_sweep_build): per component of list 1 and width the
+    histogram of every byte plane of its residual codes -- np.bincount of the encoder's "vplanes" stage after a requant of a clone
+    to that width; width 0: the component as it stands.  A host table: valid until close(), whatever becomes of the codec."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def close(self):
+        if getattr(self, "h", None):
+            nat.load().hry_rate_sweep_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def coded(self) -> int:
+        """coded vertices: what every histogram sums to"""
+        return int(nat.load().hry_rate_sweep_coded(self.h))
+
+    def bits(self, l: int, c: int) -> int:
+        """the widest width component c of list l was swept at; 0: it was not swept (reason(l, c) says why)"""
+        n = nat.load().hry_rate_sweep_bits(self.h, l, c)
+        if n < 0:
+            nat.check(n)
+        return n
+
+    def reason(self, l: int, c: int) -> str:
+        return "" if self.bits(l, c) else nat.load().hry_last_error().decode(errors="replace")
+
+    def planes(self, l: int, c: int, bits: int) -> int:
+        n = nat.load().hry_rate_sweep_planes(self.h, l, c, bits)
+        if n < 0:
+            nat.check(n)
+        return n
+
+    def hist(self, l: int, c: int, bits: int) -> np.ndarray:
+        """[planes, 256] uint32: the histograms of the component's byte planes at `bits` (0: as it stands)"""
+        out = np.zeros((self.planes(l, c, bits), 256), np.uint32)
+        for p in range(out.shape[0]):
+            nat.check(nat.load().hry_rate_sweep_hist(self.h, l, c, bits, p, out[p].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def bytes(self, l: int, c: int, bits: int) -> float:
+        """the entropy of the component's planes at `bits`, in bytes: an estimate of its share of the payload"""
+        out = C.c_double()
+        nat.check(nat.load().hry_rate_sweep_bytes(self.h, l, c, bits, C.byref(out)))
+        return out.value
+
+    def choose(self, l: int, c: int, budget: float):
+        """(bits, bytes): the largest common width of component c of list l (-1: every swept one) whose estimate fits `budget`; bits 0: none"""
+        bits, est = C.c_int(), C.c_double()
+        nat.check(nat.load().hry_rate_choose(self.h, l, c, float(budget), C.byref(bits), C.byref(est)))
+        return bits.value, est.value
+
+    def stat(self) -> dict:
+        """device_ms (the kernel, by events), walk_ms (the host's walk), uploaded_bytes (a mesh that was not resident)"""
+        d, w, up = C.c_double(), C.c_double(), C.c_uint64()
+        nat.check(nat.load().hry_rate_sweep_stat(self.h, C.byref(d), C.byref(w), C.byref(up)))
+        return {"device_ms": d.value, "walk_ms": w.value, "uploaded_bytes": up.value}
 
 
 class MultiCodec:

@@ -15,6 +15,7 @@ struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
+struct hry_rate_sweep { RateResult s; };
 struct hry_walk {
 	WalkResult w; uint32_t info[2]; std::vector<uint8_t> vplanes, fplanes; std::vector<uint32_t> seg_start, seg_level;
 	mutable std::vector<uint8_t> op_sym, op_class;   // unpacked from w.op_sc on first request
@@ -826,6 +827,79 @@ int hry_quant_pick(const hry_comp_error *by_bits, int n_bits, int metric, double
 	int bits = 0;
 	const int rc = guarded([&] { bits = quant_pick(by_bits, n_bits, metric, extent, value); });
 	return rc == HRY_OK ? bits : rc;
+}
+
+// ---- the coded size of list 1's components at every quantisation width, and a width from a byte budget (rate.cpp).  The build
+// walks the mesh and makes it resident, as hry_encode does
+int hry_rate_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_rate_sweep **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	touched(ctx); touched(m);
+	return guarded([&] {
+		std::unique_ptr<hry_rate_sweep> s(new hry_rate_sweep());
+		rate_sweep_build(ctx->cx, m->m, s->s);
+		*out = s.release();
+	});
+}
+uint32_t hry_rate_sweep_coded(const hry_rate_sweep *s) { return s ? s->s.coded : 0; }
+int hry_rate_sweep_bits(const hry_rate_sweep *s, int l, int c)
+{
+	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (l < 0 || (size_t)l >= s->s.comp.size()) { g_last_error = "Invalid list index"; return HRY_E_ARG; }
+	if (c < 0 || (size_t)c >= s->s.comp[l].size()) { g_last_error = "Invalid attribute index"; return HRY_E_ARG; }
+	const RateResult::Comp &C = s->s.comp[l][c];
+	if (!C.qmax) g_last_error = C.why;
+	return C.qmax;
+}
+int hry_rate_sweep_planes(const hry_rate_sweep *s, int l, int c, int bits)
+{
+	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
+	int np = 0;
+	const int rc = guarded([&] { np = rate_planes(s->s, l, c, bits); });
+	return rc == HRY_OK ? np : rc;
+}
+int hry_rate_sweep_hist(const hry_rate_sweep *s, int l, int c, int bits, int plane, uint32_t out[256])
+{
+	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] {
+		const int np = rate_planes(s->s, l, c, bits);
+		if (plane < 0 || plane >= np) throw Error(HRY_E_ARG, "Invalid byte plane");
+		memcpy(out, rate_row(s->s.comp[l][c], bits) + (size_t)plane * 256, 256 * sizeof(uint32_t));
+	});
+}
+int hry_rate_sweep_bytes(const hry_rate_sweep *s, int l, int c, int bits, double *out)
+{
+	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { *out = rate_bytes(s->s, l, c, bits); });
+}
+int hry_rate_sweep_stat(const hry_rate_sweep *s, double *device_ms, double *walk_ms, uint64_t *uploaded_bytes)
+{
+	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = s->s.device_ms;
+	if (walk_ms) *walk_ms = s->s.walk_ms;
+	if (uploaded_bytes) *uploaded_bytes = s->s.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_rate_sweep_free(hry_rate_sweep *s) { delete s; }
+int hry_rate_hist_bytes(const uint32_t hist[256], double *out)
+{
+	if (!hist || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	*out = rate_hist_bytes(hist);
+	return HRY_OK;
+}
+int hry_rate_pick(const double *bytes_by_bits, int n_bits, double budget)
+{
+	int bits = 0;
+	const int rc = guarded([&] { bits = rate_pick(bytes_by_bits, n_bits, budget); });
+	return rc == HRY_OK ? bits : rc;
+}
+int hry_rate_choose(const hry_rate_sweep *s, int l, int c, double budget, int *bits, double *bytes)
+{
+	if (bits) *bits = 0;
+	if (bytes) *bytes = 0.0;
+	if (!s || !bits) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { *bits = rate_choose(s->s, l, c, budget, bytes); });
 }
 
 // ---- meshes from device buffers (ingest.cpp)

@@ -18,7 +18,12 @@
 // shared extent; the mesh is swept once -- hry_quant_sweep_build -- and the smallest width that meets the tolerance is applied,
 // "Chosen: list L attr C bits Q max M" per component; with -c the mesh is cleared first, swept, and every width is applied to the
 // cleared values; without -a every component of the list is named, as by -q, and one that cannot take a tolerance -- quantised
-// already and no -c, a constant integer -- ends the run with its reason).
+// already and no -c, a constant integer -- ends the run with its reason), --max-bytes N (a byte budget for the written .hry in place
+// of -q, bound to the preceding -l / -a: ONE common width for the named component, or every swept component of the list, such that
+// the file is at most N bytes.  The mesh -- after the other quantisations -- is swept once, hry_rate_sweep_build; hry_rate_choose
+// picks the starting width from N minus the fixed part, which is 0 before the first encode and afterwards the real size minus the
+// estimate at the width just encoded; then real encodes step down until the file fits and up while the next width still fits:
+// "Budget: list L attr C bits Q estimated E bytes" per component and "Budget: output S of N bytes after K encodes").
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -27,6 +32,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <thread>
 
 #include <fcntl.h>
@@ -51,10 +57,12 @@ const std::chrono::steady_clock::time_point g_start = std::chrono::steady_clock:
 long long since_start_ms() { return (long long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - g_start).count(); }
 struct QuantArg { int l, o, q; };
 struct ToleranceArg { int l, o, metric; double value; };
+struct BudgetArg { int l = -1, o = -1; long long bytes = -1; };   // bytes < 0: none
 struct Args {
 	std::string in, out, fmt, profile;   // profile empty: compat, unless --gpus / --shards ask for the sharded container
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
+	BudgetArg budget;
 	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
@@ -66,7 +74,8 @@ const Opt kOpts[] = {
 	{ 0, "ply-ascii", "PLY writer: Use ASCII format", false }, { 0, "ply-packed", "PLY writer: quantised values in their declared width", false }, { 0, "profile", "compat (reference stream, default) or chunked", true },
 	{ 0, "chunk", "chunked: symbols per chunk", true }, { 0, "device", "GPU index (first one with --gpus)", true }, { 0, "gpus", "N device contexts, one worker thread each", true },
 	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false },
-	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true } };
+	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true },
+	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true } };
 
 void usage(const char *argv0)
 {
@@ -154,6 +163,25 @@ Args parse(int argc, const char **argv)
 			a.tolerance.push_back(ToleranceArg{ cur_l, cur_a, n == "max-error" ? HRY_TOL_MAX_ABS : HRY_TOL_MAX_REL, v });
 			cur_a = -1;
 		}
+		else if (n == "max-bytes") {
+			if (!have_l) arg_error(argv[0], "--max-bytes needs a preceding -l");
+			if (a.budget.bytes >= 0) arg_error(argv[0], "Invalid option: --max-bytes given twice");
+			char *end = nullptr;
+			const long long v = strtoll(val.c_str(), &end, 10);
+			if (val.empty() || *end || v < 0) arg_error(argv[0], "Invalid budget");
+			a.budget.l = cur_l; a.budget.o = cur_a; a.budget.bytes = v;
+			cur_a = -1;
+		}
+	}
+	if (a.budget.bytes >= 0) {
+		const BudgetArg &b = a.budget;
+		for (const QuantArg &q : a.quant)
+			if (b.l == q.l && (b.o == q.o || b.o == -1 || q.o == -1))
+				arg_error(argv[0], "Invalid option: list " + std::to_string(b.l) + " attr " + std::to_string(b.o == -1 ? q.o : b.o) + " has both -q and a budget");
+		for (const ToleranceArg &t : a.tolerance)
+			if (b.l == t.l && (b.o == t.o || b.o == -1 || t.o == -1))
+				arg_error(argv[0], "Invalid option: list " + std::to_string(b.l) + " attr " + std::to_string(b.o == -1 ? t.o : b.o) + " has both a tolerance and a budget");
+		if (a.gpus > 1 || a.shards > 1) arg_error(argv[0], "--max-bytes sweeps and encodes the whole mesh on one context: not with --gpus / --shards");
 	}
 	for (const ToleranceArg &t : a.tolerance)
 		for (const QuantArg &q : a.quant)
@@ -237,17 +265,90 @@ struct Handles {   // released on every path
 	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
 	hry_distortion *dist = nullptr;
 	hry_sweep *sweep = nullptr;
+	hry_rate_sweep *rate = nullptr;
+	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
 	std::vector<uint8_t*> bufs;
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
 		if (dist) hry_distortion_free(dist);
 		if (sweep) hry_quant_sweep_free(sweep);
+		if (rate) hry_rate_sweep_free(rate);
+		if (trial) hry_mesh_free(trial);
 		if (before) hry_mesh_free(before);
 		if (mesh) hry_mesh_free(mesh);
 		for (hry_ctx *c : cx) hry_ctx_destroy(c);
 	}
 };
+
+// --max-bytes: the widest common width of the budget's components whose .hry (options o) is at most the budget; the container
+// comes back in *out (released with h.bufs)
+void encode_within_budget(Handles &h, const BudgetArg &b, const hry_opts &o, uint8_t **out, size_t *out_len)
+{
+	ok(hry_rate_sweep_build(h.cx[0], h.mesh, &h.rate));
+	std::vector<int> comps;
+	if (b.l < 0 || b.l >= hry_mesh_nlists(h.mesh)) throw std::runtime_error("Invalid list index");
+	if (b.o == -1) { for (int c = 0; c < hry_list_ncomp(h.mesh, b.l); ++c) if (hry_rate_sweep_bits(h.rate, b.l, c) > 0) comps.push_back(c); }
+	else comps.push_back(b.o);
+	int qmax = 0;
+	for (int c : comps) {
+		const int q = hry_rate_sweep_bits(h.rate, b.l, c);
+		if (q < 0) throw std::runtime_error(hry_last_error());
+		if (q == 0) throw std::runtime_error("list " + std::to_string(b.l) + " attr " + std::to_string(c) + " cannot take a budget: " + hry_last_error());
+		qmax = qmax ? std::min(qmax, q) : q;
+	}
+	if (comps.empty()) {
+		std::string why = "it has no components";
+		if (hry_list_ncomp(h.mesh, b.l) > 0 && hry_rate_sweep_bits(h.rate, b.l, 0) == 0) why = hry_last_error();
+		throw std::runtime_error("list " + std::to_string(b.l) + " has no component that can take a budget: " + why);
+	}
+	auto estimate = [&](int bits) {
+		double sum = 0;
+		for (int c : comps) { double e = 0; ok(hry_rate_sweep_bytes(h.rate, b.l, c, bits, &e)); sum += e; }
+		return sum;
+	};
+	std::map<int, std::pair<uint8_t*, size_t>> coded;   // width -> its container
+	auto size_at = [&](int bits) {
+		auto it = coded.find(bits);
+		if (it != coded.end()) return it->second.second;
+		if (!(h.trial = hry_mesh_clone(h.mesh))) throw std::runtime_error(hry_last_error());
+		std::vector<hry_quant> q;
+		for (int c : comps) q.push_back(hry_quant{ b.l, c, bits });
+		ok(hry_requant(h.cx[0], h.trial, q.data(), q.size(), 0));
+		uint8_t *p = nullptr;
+		size_t n = 0;
+		ok(hry_encode(h.cx[0], h.trial, &o, &p, &n));
+		h.bufs.push_back(p);
+		hry_mesh_free(h.trial); h.trial = nullptr;
+		coded[bits] = std::make_pair(p, n);
+		return n;
+	};
+	const size_t N = (size_t)b.bytes;
+	auto start = [&](double fixed) {   // hry_rate_choose on what the budget leaves beside the fixed part; nothing fits: 1 bit
+		int bits = 0;
+		const double left = (double)N - fixed;
+		if (left >= 0) ok(hry_rate_choose(h.rate, b.l, b.o, left, &bits, nullptr));
+		return std::max(1, std::min(bits, qmax));
+	};
+	int bits = start(0.0);
+	const size_t first = size_at(bits);
+	bits = start((double)first - estimate(bits));
+	while (size_at(bits) > N) {
+		if (bits == 1) throw std::runtime_error("--max-bytes " + std::to_string(N) + ": the output is " + std::to_string(size_at(1)) + " bytes at 1 bit");
+		--bits;
+	}
+	while (bits < qmax && size_at(bits + 1) <= N) ++bits;
+	for (int c : comps) {
+		double e = 0;
+		ok(hry_rate_sweep_bytes(h.rate, b.l, c, bits, &e));
+		char line[160];
+		snprintf(line, sizeof line, "Budget: list %d attr %d bits %d estimated %.0f bytes", b.l, c, bits, e);
+		std::cout << line << std::endl;
+	}
+	std::cout << "Budget: output " << coded[bits].second << " of " << N << " bytes after " << coded.size() << " encodes" << std::endl;
+	*out = coded[bits].first; *out_len = coded[bits].second;
+	hry_rate_sweep_free(h.rate); h.rate = nullptr;
+}
 
 int run(const Args &args)
 {
@@ -315,6 +416,9 @@ int run(const Args &args)
 	// whole mesh never sits on one device
 	const bool quant_in_encode = sharded && type == "hry";
 	if (!args.tolerance.empty() && quant_in_encode) throw std::runtime_error("--max-error sweeps the whole mesh on one context: not with --gpus / --shards");
+	const bool budget = args.budget.bytes >= 0;
+	if (budget && quant_in_encode) throw std::runtime_error("--max-bytes sweeps and encodes the whole mesh on one context: not with --gpus / --shards");
+	if (budget && type != "hry") throw std::runtime_error("--max-bytes is a budget for a .hry output");
 	const bool quant_phase = (!q.empty() || !args.tolerance.empty() || args.clearquant) && !quant_in_encode;
 	if (quant_phase) {
 		std::cout << "Quantization..." << std::endl;
@@ -383,10 +487,11 @@ int run(const Args &args)
 			std::cout << "  " << st.n_shards << " shard(s) of " << st.n_components << " component(s) on " << st.n_contexts << " context(s), " << std::min(n_ctx, std::max(1, n_dev))
 			          << " device(s): plan " << (long long)st.plan_ms << " ms, extract " << (long long)st.extract_ms << " ms, bounds " << (long long)(st.bounds_ms + st.combine_ms)
 			          << " ms, quantization " << (long long)st.quant_ms << " ms, encode " << (long long)st.encode_ms << " ms, merge " << (long long)st.merge_ms << " ms" << std::endl;
-		} else ok(hry_encode(h.cx[0], h.mesh, &o, &out, &out_len));
+		} else if (budget) encode_within_budget(h, args.budget, o, &out, &out_len);
+		else ok(hry_encode(h.cx[0], h.mesh, &o, &out, &out_len));
 	} else if (type == "ply") ok(hry_mesh_to_ply(h.mesh, (args.ply_ascii ? HRY_PLY_ASCII : 0) | (args.ply_packed ? HRY_PLY_PACKED : 0), &out, &out_len));
 	else ok(hry_mesh_to_obj(h.mesh, 0, &out, &out_len));
-	h.bufs.push_back(out);
+	if (!budget) h.bufs.push_back(out);   // (a budget's containers are in h.bufs already)
 	write_file(args.out, out, out_len);
 	Clock::time_point t3 = Clock::now();
 	std::cout << "Writing output took " << ms(t2, t3) << " ms." << std::endl;

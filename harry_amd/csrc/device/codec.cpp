@@ -467,6 +467,23 @@ void upload_repaired_twins(Context &cx, const Mesh &host, const WalkResult &w, b
 	dev::launch_scatter_u32(cx.stream, cx.d_patch.as<uint32_t>(), (uint32_t)np, cx.d_twin.as<uint32_t>());
 }
 
+// The front half of the vertex attributes' pass, after the walk of a resident mesh: the coding order of the vertices into
+// d_order_v, and what the walk repaired into the resident twins (encoder.h:150,193-198) -- they are current otherwise ...
+void upload_coding_order(Context &cx, const Mesh &m, const WalkResult &w)
+{
+	const size_t vc = w.order_v.size();
+	cx.d_order_v.ensure(std::max<size_t>(vc * 4, 16));
+	cx.d_rank.ensure(std::max<size_t>((size_t)m.nv * 4, 16));
+	if (vc) HIP_OK(hipMemcpyAsync(cx.d_order_v.p, w.order_v.data(), vc * 4, hipMemcpyHostToDevice, cx.stream));
+	upload_repaired_twins(cx, m, w);
+}
+// ... and the traversal rank of every vertex from it (kNoRank: never coded) into d_rank
+void rank_coding_order(Context &cx, const Mesh &m, uint32_t vc)
+{
+	HIP_OK(hipMemsetAsync(cx.d_rank.p, 0xff, (size_t)m.nv * 4, cx.stream));
+	launch_rank(cx.stream, cx.d_order_v.as<uint32_t>(), vc, cx.conn_view().org, cx.d_rank.as<uint32_t>());
+}
+
 void device_requant(Context &cx, Mesh &m, const hry_quant *q, size_t nq, bool clear)
 {
 	HIP_OK(hipSetDevice(cx.device));
@@ -634,13 +651,9 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	// ---- H2D
 	auto t_h2d = Clock::now();
 	HIP_OK(hipEventRecord(cx.ev[0], cx.stream));
-	cx.d_order_v.ensure(std::max<size_t>((size_t)vc * 4, 16));
 	cx.d_order_f.ensure(std::max<size_t>((size_t)fc * 4, 16));
-	cx.d_rank.ensure(std::max<size_t>((size_t)m.nv * 4, 16));
-	if (vc) HIP_OK(hipMemcpyAsync(cx.d_order_v.p, w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
 	if (fc) HIP_OK(hipMemcpyAsync(cx.d_order_f.p, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
-	// the resident copy of the twins is current unless the walk repaired some (non-manifold edges, consumed neighbours)
-	upload_repaired_twins(cx, m, w);   // (encoder.h:150,193-198)
+	upload_coding_order(cx, m, w);
 	// connectivity groups: values + positions, packed back to back
 	size_t ngrp = 0;
 	for (int g = 0; g < G_COUNT; ++g) ngrp += w.grp_val[g].size();
@@ -729,8 +742,7 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	// ---- device: prediction + residuals + planes
 	ConnView cv = cx.conn_view();
 	HIP_OK(hipEventRecord(cx.ev[1], cx.stream));
-	HIP_OK(hipMemsetAsync(cx.d_rank.p, 0xff, (size_t)m.nv * 4, cx.stream));
-	launch_rank(cx.stream, cx.d_order_v.as<uint32_t>(), vc, cv.org, cx.d_rank.as<uint32_t>());
+	rank_coding_order(cx, m, vc);
 	launch_predict_vtx(cx.stream, cv, cx.d_order_v.as<uint32_t>(), vc, cx.d_rank.as<uint32_t>(), cx.d_rec[1].as<uint8_t>(), ldv, cx.d_vplanes.as<uint8_t>());
 	launch_face_planes(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, cx.d_rec[0].as<uint8_t>(), ldf, cx.d_fplanes.as<uint8_t>());
 	HIP_OK(hipEventRecord(cx.ev[2], cx.stream));

@@ -172,6 +172,10 @@ std::vector<std::vector<uint8_t>> requant_targets(const Mesh &m, const hry_quant
 dev::RequantPlan requant_plan(const AttrList &L, const std::vector<uint8_t> &to);
 // the twins the walk repaired (cbm/encoder.h:150,193-198) into the resident copy: the few entries it names, else the whole array
 void upload_repaired_twins(Context &cx, const Mesh &host, const WalkResult &w, bool patches_only = false);
+// the front half of the vertex attributes' pass (codec.cpp; shared by encode_compat and rate_sweep_build): the walk's order_v into
+// d_order_v with its repaired twins; then the rank of every vertex in it into d_rank
+void upload_coding_order(Context &cx, const Mesh &m, const WalkResult &w);
+void rank_coding_order(Context &cx, const Mesh &m, uint32_t vc);
 uint64_t test_extra(const char *name);   // HRY_TEST_EXTRA_SYMBOLS / _BITS: counted on top of a reference stream's own (tests of the format's limits)
 void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out);
 // A shard coded where it lies in the whole mesh (sharded.cpp: the in-process executor): the mesh handed to encode_chunked is a
@@ -250,10 +254,37 @@ struct SweepResult {
 	double device_ms = 0;
 	uint64_t uploaded_bytes = 0;
 };
+int swept_widths(const Mesh &m, size_t l, int c, dev::RequantComp &rc, std::string &why);   // 1 .. the result; 0: not swept, why says why
 void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out);   // (computes bounds where unset, as device_requant does)
 // host only: the smallest width whose record meets (metric, value), 0: none; and the requests that meet a set of tolerances
 int quant_pick(const hry_comp_error *by_bits, int n_bits, int metric, double extent, double value);
 std::vector<hry_quant> quant_choose(const SweepResult &s, const hry_tolerance *t, size_t nt);
+
+// rate.cpp: the byte-plane histograms of list 1's residual codes at every quantisation width (include/harry_amd.h:
+// hry_rate_sweep_build).  The result is the host table only
+struct RateResult {
+	struct Comp {
+		int qmax = 0, type = 0;          // swept at 1 .. qmax bits; 0: not swept, `why` says why
+		bool row0 = false;               // the component as it stands is counted; else why0 says why not
+		int planes0 = 0;                 // ... in that many byte planes
+		std::string why, why0;
+		std::vector<uint32_t> hist;      // rows of 4 x 256 counters: as it stands (two rows, eight planes), then one per width (rate_row)
+	};
+	std::vector<std::vector<Comp>> comp;   // per list and component
+	uint32_t coded = 0;
+	double device_ms = 0, walk_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+void rate_sweep_build(Context &cx, Mesh &m, RateResult &out);
+// host only.  rate_hist_bytes: the zeroth-order entropy of a histogram in bytes; rate_planes: byte planes of a component at `bits`;
+// rate_bytes: the sum over the planes of one row; rate_pick: the LARGEST width whose bytes fit the budget, 0: none;
+// rate_choose: one common width for component c of list l (-1: every swept one)
+double rate_hist_bytes(const uint32_t *hist);
+const uint32_t *rate_row(const RateResult::Comp &C, int bits);   // the planes of one row, 256 counters each
+int rate_planes(const RateResult &s, int l, int c, int bits);
+double rate_bytes(const RateResult &s, int l, int c, int bits);
+int rate_pick(const double *bytes_by_bits, int n_bits, double budget);
+int rate_choose(const RateResult &s, int l, int c, double budget, double *bytes);
 
 // order.cpp.  order_build: at the end of an encode with cx.want_order -- m's connectivity is in d_foff / d_org (conn_view), w is the
 // encode's walk; d_order_v / d_order_f: the walk's orders where the encode has them whole in HBM, else nullptr (they go up from w);

@@ -158,5 +158,19 @@ struct SweepList {
 	SweepComp c[kMaxComp];
 };
 
+// rate.hip: one component of list 1 in a rate sweep.  rc.off / rc.src_type (the original type) / rc.mn / rc.scale as requant_plan
+// gives them; swept at 1 .. qmax bits (0: not swept); row0: the component as it stands is counted too, in its storage type stype0 at
+// quant0 bits.  The table is made of rows of kRatePlanes x 256 counters; the component's are slot .. slot + qmax + 1: two for row 0
+// (kRatePlanes0 planes: a lossless 64-bit integer has eight), then row slot + 1 + bits for every width
+constexpr int kRatePlanes = 4, kRatePlanes0 = 8;
+struct RateComp { RequantComp rc; int32_t qmax, row0; uint32_t slot; uint8_t stype0, quant0, pad[2]; };
+struct RateList {
+	const uint8_t *rec;
+	uint32_t *table;     // [rows][kRatePlanes][256], zeroed
+	uint32_t stride;
+	int32_t n;
+	RateComp c[kMaxComp];
+};
+
 }   // namespace dev
 }   // namespace hry

@@ -9,6 +9,7 @@
 #include "dev_types.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
+#include "predict.hpp"
 #include "wave.hpp"
 
 namespace hry {
@@ -18,35 +19,6 @@ namespace dev {
 // helpers
 // ---------------------------------------------------------------------------------------------------------
 __constant__ int c_type_size[11] = { 4, 8, 8, 8, 4, 4, 2, 2, 1, 1, 0 };
-
-// prediction of one component (attrcode.h:182-208): mean of candidate predictions in fan order (double / int64),
-// integers take the mean, floats the candidate nearest to the mean (strict <, first wins).
-template <typename T>
-__device__ __forceinline__ T predict_component(const Topo &tp, const uint32_t *rank, const uint8_t *rec, int stride, int off, int q,
-                                               uint32_t e, uint32_t my_rank, uint32_t lo, const uint32_t *attr_of)
-{
-	typedef typename cm::wide<T>::type W;
-	W acc = 0;
-	uint32_t n = 0;
-	auto value = [&](uint32_t v) { return ldg<T>(rec + (size_t)(attr_of ? attr_of[v] : v) * stride + off); };
-	fan_candidates(tp, rank, e, my_rank, lo, [&](uint32_t v0, uint32_t v1, uint32_t vo) {
-		acc = acc + (W)cm::parallelogram<T>(value(v0), value(v1), value(vo), q);
-		++n;
-	});
-	if (n == 0) return T(0);
-	T avg = (T)cm::mean_of(acc, (W)n);
-	if constexpr (!cm::is_fp<T>::value) return avg;
-	else {
-		T best = 3.402823466e+38f;   // numeric_limits<float>::max()
-		fan_candidates(tp, rank, e, my_rank, lo, [&](uint32_t v0, uint32_t v1, uint32_t vo) {
-			T p = cm::parallelogram<T>(value(v0), value(v1), value(vo), q);
-			T db = avg > best ? avg - best : best - avg;
-			T dp = avg > p ? avg - p : p - avg;
-			best = db < dp ? best : p;
-		});
-		return best;
-	}
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // k_bounds: per-component min / max with the reference's initial values and first-wins ties
@@ -239,14 +211,11 @@ __global__ __launch_bounds__(256) void k_rank_runs(RunTable rt, const uint32_t *
 // vertex (attrcode.h:209-225 vtx, :321-344 vtx_post; io.h:90-94; models.h:168-173).  Output: SoA byte planes,
 // plane p holds byte p of every vertex' residual record in coding order (coalesced for the model kernels).
 // ---------------------------------------------------------------------------------------------------------
-// The fan is walked ONCE per vertex: the (at most kEncCand) candidate triples that pass the rank filter are kept as vertex
-// ids in LDS and every component is evaluated from them -- the mean, and for floats the nearest-to-the-mean selection, which
-// the reference evaluates in a second sweep over the same candidates (attrcode.h:182-208).  A fan with more candidates
-// (high-valence vertices) takes predict_component, which walks again per component.
+// The fan is walked ONCE per vertex and every component is evaluated from the candidates kept in LDS; a fan with more than kEncCand
+// candidates walks again per component (predict.hpp, shared with k_rate_sweep).
 // Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2: virtual block (b % 8) * per + b / 8 gives every
 // XCD one contiguous range of the coding order, so the connectivity / rank / record lines its wavefronts gather are shared
 // inside one L2 instead of being fetched by all eight.
-constexpr int kEncCand = 8;
 // coded vertex k of n (n = the stride of the byte planes)
 __device__ __forceinline__ void predict_vertex(const ConnView &cv, const uint32_t *order_v, uint32_t k, uint32_t n, const uint32_t *rank,
                                                const uint8_t *rec, const ListDesc &ld, uint8_t *planes, uint32_t (*s_cand)[256])
@@ -254,43 +223,14 @@ __device__ __forceinline__ void predict_vertex(const ConnView &cv, const uint32_
 	Topo tp{ cv };
 	const uint32_t e = order_v[k];
 	const uint32_t v = cv.org[e];
-	int nc = 0;
-	fan_candidates(tp, rank, e, k, 0, [&](uint32_t v0, uint32_t v1, uint32_t vo) {
-		if (nc < kEncCand) { s_cand[3 * nc][threadIdx.x] = v0; s_cand[3 * nc + 1][threadIdx.x] = v1; s_cand[3 * nc + 2][threadIdx.x] = vo; }
-		++nc;
-	});
+	const int nc = keep_candidates(tp, rank, e, k, s_cand);
 	for (int c = 0; c < ld.ncomp; ++c) {
 		with_stype(ld.stype[c], [&](auto tag) {
 			typedef decltype(tag) T;
-			typedef typename cm::wide<T>::type W;
 			const int off = ld.off[c], q = ld.quant[c];
 			auto value = [&](uint32_t x) { return ldg<T>(rec + (size_t)x * ld.stride + off); };
-			T pred;
-			if (nc > kEncCand) pred = predict_component<T>(tp, rank, rec, ld.stride, off, q, e, k, 0, nullptr);
-			else if (nc == 0) pred = T(0);
-			else {
-				T p[kEncCand];
-				W acc = 0;
-#pragma unroll
-				for (int i = 0; i < kEncCand; ++i)
-					if (i < nc) {
-						p[i] = cm::parallelogram<T>(value(s_cand[3 * i][threadIdx.x]), value(s_cand[3 * i + 1][threadIdx.x]), value(s_cand[3 * i + 2][threadIdx.x]), q);
-						acc = acc + (W)p[i];   // fan order (the float mean is a double sum in candidate order)
-					}
-				const T avg = (T)cm::mean_of(acc, (W)nc);
-				if constexpr (!cm::is_fp<T>::value) pred = avg;
-				else {
-					T best = 3.402823466e+38f;   // numeric_limits<float>::max()
-#pragma unroll
-					for (int i = 0; i < kEncCand; ++i)
-						if (i < nc) {
-							T db = avg > best ? avg - best : best - avg;
-							T dp = avg > p[i] ? avg - p[i] : p[i] - avg;
-							best = db < dp ? best : p[i];
-						}
-					pred = best;
-				}
-			}
+			const T pred = nc > kEncCand ? predict_walked<T>(tp, rank, q, e, k, 0, value)
+			                             : predict_kept<T>(nc, q, [&](int s) { return value(s_cand[s][threadIdx.x]); });
 			T raw = value(v);
 			auto code = cm::residual_bits<T>(raw, pred, q);
 			for (int b = 0; b < (int)sizeof(T); ++b) planes[(size_t)(ld.plane[c] + b) * n + k] = (uint8_t)(code >> (8 * b));

@@ -223,6 +223,11 @@ constexpr int kSweepGroup = 2, kSweepMaxBits = 30;
 void launch_quant_sweep(hipStream_t st, const SweepList &L);
 void launch_quant_sweep_fold(hipStream_t st, const DistFold &f, DistFinal *out);
 
+// the byte-plane histograms of the residual codes of list 1's components at every quantisation width (rate.hip; driver: rate.cpp):
+// blocks of kRateBlock coded vertices x groups of table rows (row = width, 0: as it stands); L.table is zeroed before
+constexpr int kRateBlock = 256;
+void launch_rate_sweep(hipStream_t st, const ConnView &cv, const uint32_t *order_v, uint32_t n, const uint32_t *rank, const RateList &L);
+
 // meshes from device buffers (ingest.hip; driver: ingest.cpp).  The checks raise bits of err; total = sum of the degrees (64-bit),
 // degmask = the set of degrees present (bit d)
 constexpr uint32_t kIngestBadDegree = 1, kIngestBadIndex = 2;

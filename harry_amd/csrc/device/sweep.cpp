@@ -34,6 +34,24 @@ void check_tolerance_value(double value)
 
 }   // namespace
 
+// Which widths component c of list l (bounds known) is swept at: 1 .. the result, 0: none and `why` says why.  The test is
+// hry_requant's own, requant_plan on that one component; rc: what it gives (offset, minimum, shared extent), the bits left to the
+// kernel.  One statement for the error sweep and the rate sweep (rate.cpp)
+int swept_widths(const Mesh &m, size_t l, int c, dev::RequantComp &rc, std::string &why)
+{
+	const AttrList &L = m.lists[l];
+	if (!distortion_compares(m, l)) { why = "list " + std::to_string(l) + " is not compared (no target, or beyond the PLY layout's two lists)"; return 0; }
+	if (L.quant[c]) { why = "already quantised"; return 0; }
+	std::vector<uint8_t> to = L.quant;
+	to[c] = 1;
+	RequantPlan one;
+	try { one = requant_plan(L, to); } catch (const Error &e) { why = e.what(); return 0; }
+	if (one.n != 1) throw Error(HRY_E_INTERNAL, "sweep: the plan of one component");
+	rc = one.c[0];
+	rc.src_bits = 0; rc.dst_bits = 0; rc.src_type = rc.dst_type = L.type[c];
+	return std::min(kSweepMaxBits, 8 * (int)kTypeSize[L.type[c]]);
+}
+
 void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 {
 	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
@@ -62,18 +80,12 @@ void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 		for (int c = 0; c < L.ncomp(); ++c) {
 			SweepResult::Comp &C = out.comp[l][c];
 			C.type = L.type[c];
-			if (!distortion_compares(m, l)) { C.why = "list " + std::to_string(l) + " is not compared (no target, or beyond the PLY layout's two lists)"; continue; }
-			if (L.quant[c]) { C.why = "already quantised"; continue; }
-			std::vector<uint8_t> to = L.quant;
-			to[c] = 1;
-			RequantPlan one;
-			try { one = requant_plan(L, to); } catch (const Error &e) { C.why = e.what(); continue; }
-			if (one.n != 1) throw Error(HRY_E_INTERNAL, "sweep: the plan of one component");
-			C.qmax = std::min(kSweepMaxBits, 8 * (int)kTypeSize[L.type[c]]);
-			C.extent = cm::value_f64(one.c[0].scale, (int)L.type[c]);
+			RequantComp rc;
+			C.qmax = swept_widths(m, l, c, rc, C.why);
+			if (!C.qmax) continue;
+			C.extent = cm::value_f64(rc.scale, (int)L.type[c]);
 			SweepComp &sc = J.c[J.n];
-			sc.rc = one.c[0];
-			sc.rc.src_bits = 0; sc.rc.dst_bits = 0; sc.rc.src_type = sc.rc.dst_type = L.type[c];
+			sc.rc = rc;
 			sc.qmax = C.qmax; sc.slot = J.ns;
 			J.ns += (uint32_t)C.qmax;
 			job_of[l][c] = J.n++;

@@ -19,6 +19,7 @@
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
  *   hry_distortion_build (no counterpart: the per-component error of a decode against its source, reduced on the device)
  *   hry_quant_sweep_build (no counterpart: that error at every quantisation width in one pass, and the width a tolerance needs)
+ *   hry_rate_sweep_build (no counterpart: the coded size of the vertex attributes at every width in one pass, and the width a byte budget buys)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -524,6 +525,57 @@ typedef struct hry_tolerance {
 } hry_tolerance;
 int  hry_quant_choose(const hry_sweep *s, const hry_tolerance *t, size_t nt, hry_quant *out, size_t cap, size_t *n_out);
 int  hry_quant_pick(const hry_comp_error *by_bits /* [n_bits], index bits - 1 */, int n_bits, int metric, double extent, double value);
+
+/* ---- the coded size at every quantisation width ------------------------------------------------
+ * The other column of a lossy encode: what every width of a vertex attribute costs in bytes, from one pass over the coding order,
+ * where the loop it replaces clones, requantises and encodes the mesh once per width.
+ * hry_rate_sweep_build: PLY layout only -- general bindings are HRY_E_UNSUPPORTED with that reason, a partial mesh HRY_E_ARG.  Only
+ *   list 1, the vertex list, is swept (face records are coded against a zero prediction): for a component of another list
+ *   hry_rate_sweep_bits is 0 and the reason is stored.  Widths 1 .. qmax are swept for exactly the components of list 1 that
+ *   hry_quant_sweep_bits reports as swept, with the same qmax (one test serves both).  Row bits == 0 is the component as it stands: it
+ *   is there for every component of list 1 that hry_encode codes as stored, quantised ones included; a lossless HRY_DOUBLE has none
+ *   (HRY_E_UNSUPPORTED with the encoder's own text).
+ *   The table is the encoder's, not a model of it: hist(l, c, bits, p)[s] is the number of coded vertices whose byte p of the
+ *   residual code of component c equals s, the code being the one hry_encode writes into its "vplanes" stage for a clone q =
+ *   hry_mesh_clone(m) after hry_requant(ctx, q, {l, c, bits}, 1, 0) -- for row 0, for m itself -- in either profile (the planes are
+ *   the same).  Planes of a component are counted from its first plane; there are sizeof(storage type) of them: u8 up to 8 bits, u16
+ *   up to 16, u32 above.  The components of a vertex are predicted independently, so the table of c also holds when other components
+ *   are quantised at the same time.  Counts are exact, and every histogram sums to hry_rate_sweep_coded: the length of the walk's
+ *   "order_v", not the vertex count -- vertices no face names are not coded.  A mesh without faces: coded == 0, all histograms zero,
+ *   all bytes 0, no error.
+ *   The walk is the encoder's own (hry_walk_run_plain's loop): it leaves m's twins exactly as hry_encode leaves them; m becomes ctx's
+ *   resident mesh as by hry_mesh_upload if it was not; bounds are computed first where missing, as hry_requant does.  Nothing else of
+ *   m changes: hry_encode(m) afterwards gives the bytes it gave before.  The handle holds the host table only and may outlive the
+ *   context; on any refusal *out stays NULL and ctx stays usable.
+ * hry_rate_sweep_planes: the byte planes of (l, c) at that width: 1, 2 or 4 (row 0: of the storage type as it stands, 8 for a lossless
+ *   64-bit integer); a bad list,
+ *   component or width: HRY_E_ARG; a component or row that is not there: HRY_E_UNSUPPORTED with the stored reason.  _hist and _bytes
+ *   refuse the same way, _hist a plane outside [0, planes) with HRY_E_ARG.
+ * hry_rate_hist_bytes, host only: with n = sum(hist), (sum over s in ascending order with hist[s] > 0 of hist[s] * log2(n / hist[s]))
+ *   / 8, summed in double; 0 when n == 0 or one symbol holds everything (such a plane carries no information and the container does
+ *   not store it).
+ * hry_rate_sweep_bytes: the sum of hry_rate_hist_bytes over the component's planes in plane order.  An ESTIMATE of the attribute
+ *   payload and nothing else: not the models' adaptation, the chunks' priors, the directory or the connectivity.
+ * hry_rate_pick, host only: the LARGEST bits in 1 .. n_bits with bytes_by_bits[bits - 1] <= budget, 0: none -- the mirror of
+ *   hry_quant_pick.  The table need not be monotone: nothing is promised about narrower widths.  A negative or NaN budget, n_bits < 0:
+ *   HRY_E_ARG.
+ * hry_rate_choose: hry_rate_pick over the per-width sums of hry_rate_sweep_bytes of the named components (c -1: every swept component
+ *   of l, ONE common width), at widths up to the least of their qmax; *bits 0: none fits; *bytes (may be NULL): the sum at *bits.  A
+ *   named component that is not swept, or a list without a swept one: HRY_E_UNSUPPORTED with the stored reason.
+ * hry_rate_sweep_stat: device_ms (the sweep kernel, by events), walk_ms (the host's walk), uploaded_bytes (a mesh that was not
+ *   resident; where the bounds had to be computed first the mesh went up for them, and this is 0). */
+typedef struct hry_rate_sweep hry_rate_sweep;
+int      hry_rate_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_rate_sweep **out);
+uint32_t hry_rate_sweep_coded(const hry_rate_sweep *s);                       /* coded vertices = symbols per plane */
+int      hry_rate_sweep_bits(const hry_rate_sweep *s, int l, int c);          /* qmax; 0: not swept (hry_last_error: why) */
+int      hry_rate_sweep_planes(const hry_rate_sweep *s, int l, int c, int bits);
+int      hry_rate_sweep_hist(const hry_rate_sweep *s, int l, int c, int bits, int plane, uint32_t out[256]);
+int      hry_rate_sweep_bytes(const hry_rate_sweep *s, int l, int c, int bits, double *out);
+int      hry_rate_sweep_stat(const hry_rate_sweep *s, double *device_ms, double *walk_ms, uint64_t *uploaded_bytes);
+void     hry_rate_sweep_free(hry_rate_sweep *s);
+int      hry_rate_hist_bytes(const uint32_t hist[256], double *out);
+int      hry_rate_pick(const double *bytes_by_bits /* [n_bits], index bits - 1 */, int n_bits, double budget);
+int      hry_rate_choose(const hry_rate_sweep *s, int l, int c, double budget, int *bits, double *bytes);
 
 /* ---- one mesh over several GPUs ---------------------------------------------------- */
 /* The reference has no multi-device path; what a split must honour is its numbering: vertices, faces and half-edges of the
