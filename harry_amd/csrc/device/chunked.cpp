@@ -731,14 +731,7 @@ void encode_chunked(Context &cx, Mesh &m, int chunk_syms, ByteSink &out, const I
 		launch_predict_vtx(cx.stream, cv, cx.d_order_v.as<uint32_t>(), vc, cx.d_rank.as<uint32_t>(), cx.d_rec[1].as<uint8_t>(), ldv, cx.d_vplanes.as<uint8_t>());
 		launch_face_planes(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, cx.d_rec[0].as<uint8_t>(), ldf, cx.d_fplanes.as<uint8_t>());
 	}
-	{
-		size_t poff = 0;
-		for (int g = 0; g < G_COUNT; ++g) {
-			uint32_t n = (uint32_t)w.grp_val[g].size();
-			if (!(g == G_NUMTRI && nt_piped)) launch_split_bytes(cx.stream, cx.d_grp_val.as<uint32_t>() + goff[g], n, kGroupBytes[g], cx.d_connplanes.as<uint8_t>() + poff);
-			poff += (size_t)n * kGroupBytes[g];
-		}
-	}
+	split_conn_groups(cx, w, !nt_piped);
 	{
 		uint32_t base[8], o = 0;
 		for (int k = 0; k < 8; ++k) { base[k] = o; o += (uint32_t)op_plane_n[k]; }

@@ -654,88 +654,17 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	cx.d_order_f.ensure(std::max<size_t>((size_t)fc * 4, 16));
 	if (fc) HIP_OK(hipMemcpyAsync(cx.d_order_f.p, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
 	upload_coding_order(cx, m, w);
-	// connectivity groups: values + positions, packed back to back
-	size_t ngrp = 0;
-	for (int g = 0; g < G_COUNT; ++g) ngrp += w.grp_val[g].size();
-	const size_t nop = w.op_sc.size();
-	cx.d_grp_val.ensure(std::max<size_t>(ngrp * 4, 16));
-	cx.d_grp_pos.ensure(std::max<size_t>(ngrp * 4, 16));
-	// operations as the walk wrote them (symbol | order class << 3) + where the connectivity groups sit between them: the
-	// device evaluates the operation model and places the records (k_opmodel_*)
-	std::vector<uint32_t> op_thr, op_cum;
-	op_position_table(w, op_thr, op_cum);
-	const size_t op_bytes = (nop + 15) & ~(size_t)15, ngr = op_thr.size();
-	cx.d_op.ensure(std::max<size_t>(op_bytes + ngr * 8 + dev::op_model_scratch_bytes((uint32_t)nop) + 64, 64));
-	size_t goff[G_COUNT + 1] = { 0 };
-	for (int g = 0; g < G_COUNT; ++g) {
-		size_t n = w.grp_val[g].size();
-		goff[g + 1] = goff[g] + n;
-		if (!n) continue;
-		HIP_OK(hipMemcpyAsync(cx.d_grp_val.as<uint32_t>() + goff[g], w.grp_val[g].data(), n * 4, hipMemcpyHostToDevice, cx.stream));
-		HIP_OK(hipMemcpyAsync(cx.d_grp_pos.as<uint32_t>() + goff[g], w.grp_pos[g].data(), n * 4, hipMemcpyHostToDevice, cx.stream));
-	}
-	uint8_t *d_opsc = cx.d_op.as<uint8_t>();
-	uint32_t *d_opthr = (uint32_t*)(d_opsc + op_bytes), *d_opcum = d_opthr + ngr;
-	void *d_opscratch = d_opcum + ngr;
-	if (nop) HIP_OK(hipMemcpyAsync(d_opsc, w.op_sc.data(), nop, hipMemcpyHostToDevice, cx.stream));
-	if (ngr) {
-		HIP_OK(hipMemcpyAsync(d_opthr, op_thr.data(), ngr * 4, hipMemcpyHostToDevice, cx.stream));
-		HIP_OK(hipMemcpyAsync(d_opcum, op_cum.data(), ngr * 4, hipMemcpyHostToDevice, cx.stream));
-	}
+	const ConnSymbols cs = upload_conn_symbols(cx, w);
 
 	// ---- model jobs: every byte plane with its initial counts (models.h:197-218, model.h:38-55)
-	std::vector<uint32_t> inits;   // 256-entry tables
-	auto add_init = [&](const std::vector<uint32_t> &t) { uint32_t id = (uint32_t)(inits.size() / 256); inits.insert(inits.end(), t.begin(), t.end()); return id; };
-	std::vector<uint32_t> ones(256, 1), iop_init(256, 0), nt0(256, 0), nt1(256, 0);
-	for (int i = 0; i < 9; ++i) iop_init[i] = 1;
-	for (size_t d = 3; d < m.have_degree.size(); ++d) if (m.have_degree[d]) { ++nt0[(d - 2) & 0xff]; ++nt1[(d - 2) >> 8]; }
-	const uint32_t id_ones = add_init(ones), id_iop = add_init(iop_init), id_nt0 = add_init(nt0), id_nt1 = add_init(nt1);
-	auto total_of = [&](uint32_t id) { uint32_t s = 0; for (int i = 0; i < 256; ++i) s += inits[(size_t)id * 256 + i]; return s; };
-
-	size_t conn_plane_bytes = 0;
-	for (int g = 0; g < G_COUNT; ++g) conn_plane_bytes += w.grp_val[g].size() * kGroupBytes[g];
-	cx.d_connplanes.ensure(std::max<size_t>(conn_plane_bytes, 16));
 	cx.d_vplanes.ensure(std::max<size_t>((size_t)vc * ldv.nplanes, 16));
 	cx.d_fplanes.ensure(std::max<size_t>((size_t)fc * ldf.nplanes, 16));
-	cx.d_init.ensure(inits.size() * 4);
-	HIP_OK(hipMemcpyAsync(cx.d_init.p, inits.data(), inits.size() * 4, hipMemcpyHostToDevice, cx.stream));
-
-	struct JobH { PlaneJob j; uint32_t init_id; };
-	std::vector<PlaneJob> jobs;
-	std::vector<ChunkRef> chunks;
-	uint32_t max_total = 2 + std::max(vc, fc);
-	auto add_job = [&](const uint8_t *sym, uint32_t n, uint32_t init_id, const uint32_t *pos_tab, uint32_t pos_add, uint32_t pos_base, uint32_t pos_stride) {
-		if (!n) return;
-		PlaneJob j{};
-		j.sym = sym; j.n = n; j.init = cx.d_init.as<uint32_t>() + (size_t)init_id * 256; j.t0 = total_of(init_id);
-		j.pos_tab = pos_tab; j.pos_add = pos_add; j.pos_base = pos_base; j.pos_stride = pos_stride;
-		j.chunk0 = (uint32_t)chunks.size();
-		for (uint32_t f = 0; f < n; f += kChunk) chunks.push_back(ChunkRef{ (uint32_t)jobs.size(), f });
-		jobs.push_back(j);
-		max_total = std::max(max_total, j.t0 + n);
-	};
-	{
-		size_t poff = 0;
-		for (int g = 0; g < G_COUNT; ++g) {
-			uint32_t n = (uint32_t)w.grp_val[g].size();
-			for (int b = 0; b < kGroupBytes[g]; ++b) {
-				uint32_t init_id = g == G_IOP ? id_iop : g == G_NUMTRI ? (b == 0 ? id_nt0 : id_nt1) : id_ones;
-				add_job(cx.d_connplanes.as<uint8_t>() + poff + (size_t)b * n, n, init_id, cx.d_grp_pos.as<uint32_t>() + goff[g], (uint32_t)b, 0, 0);
-			}
-			poff += (size_t)n * kGroupBytes[g];
-		}
-	}
-	for (int p = 0; p < ldv.nplanes; ++p) add_job(cx.d_vplanes.as<uint8_t>() + (size_t)p * vc, vc, id_ones, nullptr, 0, base_v + 1 + p, sv);
-	for (int p = 0; p < ldf.nplanes; ++p) add_job(cx.d_fplanes.as<uint8_t>() + (size_t)p * fc, fc, id_ones, nullptr, 0, base_f + 1 + p, sf);
-	max_total = std::max<uint32_t>(max_total, (uint32_t)nop + 8);   // the operation model's total: 7 + the operations so far
-	cx.d_jobs.ensure(std::max<size_t>(jobs.size() * sizeof(PlaneJob), 16));
-	cx.d_chunks.ensure(std::max<size_t>(chunks.size() * sizeof(ChunkRef), 16));
-	cx.d_hist.ensure(std::max<size_t>(chunks.size() * 256 * 4, 16));
-	if (!jobs.empty()) HIP_OK(hipMemcpyAsync(cx.d_jobs.p, jobs.data(), jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice, cx.stream));
-	if (!chunks.empty()) HIP_OK(hipMemcpyAsync(cx.d_chunks.p, chunks.data(), chunks.size() * sizeof(ChunkRef), hipMemcpyHostToDevice, cx.stream));
-	cx.ensure_magic(max_total + 1);
-	cx.d_rec_sym.ensure(std::max<size_t>((size_t)ns * sizeof(SymRec), 16));
-	cx.d_sym_l.ensure(std::max<size_t>((size_t)ns * 4, 16));
+	ModelJobs J(cx, m);
+	J.max_total = 2 + std::max(vc, fc);
+	J.add_conn(w, cs);
+	for (int p = 0; p < ldv.nplanes; ++p) J.add(cx.d_vplanes.as<uint8_t>() + (size_t)p * vc, vc, INIT_ONES, nullptr, 0, base_v + 1 + p, sv);
+	for (int p = 0; p < ldf.nplanes; ++p) J.add(cx.d_fplanes.as<uint8_t>() + (size_t)p * fc, fc, INIT_ONES, nullptr, 0, base_f + 1 + p, sf);
+	J.send(cs, ns);
 	HIP_OK(hipStreamSynchronize(cx.stream));
 	cx.timing.h2d_ms = ms_since(t_h2d);
 
@@ -747,21 +676,13 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	launch_face_planes(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, cx.d_rec[0].as<uint8_t>(), ldf, cx.d_fplanes.as<uint8_t>());
 	HIP_OK(hipEventRecord(cx.ev[2], cx.stream));
 	// ---- device: models -> per-symbol records in global stream order
-	{
-		size_t poff = 0;
-		for (int g = 0; g < G_COUNT; ++g) {
-			uint32_t n = (uint32_t)w.grp_val[g].size();
-			launch_split_bytes(cx.stream, cx.d_grp_val.as<uint32_t>() + goff[g], n, kGroupBytes[g], cx.d_connplanes.as<uint8_t>() + poff);
-			poff += (size_t)n * kGroupBytes[g];
-		}
-	}
+	launch_conn_models(cx, w, cs);
 	const MagicEnt *magic = cx.d_magic.as<MagicEnt>();
 	SymRec *rec = cx.d_rec_sym.as<SymRec>();
 	uint32_t *sym_l = cx.d_sym_l.as<uint32_t>();
-	launch_op_model(cx.stream, d_opsc, (uint32_t)nop, d_opthr, d_opcum, (uint32_t)ngr, d_opscratch, magic, rec, sym_l);
 	launch_type_records(cx.stream, vc, base_v, sv, magic, rec, sym_l);
 	launch_type_records(cx.stream, fc, base_f, sf, magic, rec, sym_l);
-	launch_model(cx.stream, cx.d_jobs.as<PlaneJob>(), (uint32_t)jobs.size(), cx.d_chunks.as<ChunkRef>(), (uint32_t)chunks.size(), cx.d_hist.as<uint32_t>(), magic, rec, sym_l);
+	J.run();
 
 	if (cx.keep_stages) {
 		cx.stage_put_host("order_v", w.order_v.data(), (size_t)vc * 4);
@@ -776,22 +697,11 @@ void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 		cx.stage_put_host("layout", lay, sizeof lay);
 	}
 
-	// ---- device: serial recurrence, big-number low register, carries; D2H
-	std::vector<uint8_t> payload;
-	auto t_fin = Clock::now();
-	finish_stream(cx, ns, payload);
-	(void)t_fin;
-	out.insert(out.end(), payload.begin(), payload.end());
-	cx.stage_put_host("payload", payload.data(), payload.size());
-	if (cx.want_order) order_build(cx, m, w, cx.d_order_v.as<uint32_t>(), cx.d_order_f.as<uint32_t>());   // HRY_FLAG_ORDER (order.cpp)
-
-	cx.timing.k_predict_ms = cx.elapsed(1, 2);
-	cx.timing.k_model_ms = cx.elapsed(2, 3);
-	cx.timing.k_rchain_ms = cx.elapsed(3, 4);
-	cx.timing.device_ms = cx.elapsed(1, 5);
-	cx.timing.n_symbols = ns;
-	cx.timing.payload_bytes = payload.size();
-	cx.timing.total_ms = ms_since(t_all);
+	finish_compat_stream(cx, ns, t_all, out);
+	if (cx.want_order) {   // HRY_FLAG_ORDER (order.cpp); the maps' build counts into the encode's time
+		order_build(cx, m, w, cx.d_order_v.as<uint32_t>(), cx.d_order_f.as<uint32_t>());
+		cx.timing.total_ms = ms_since(t_all);
+	}
 }
 
 }   // namespace hry

@@ -178,6 +178,38 @@ void upload_coding_order(Context &cx, const Mesh &m, const WalkResult &w);
 void rank_coding_order(Context &cx, const Mesh &m, uint32_t vc);
 uint64_t test_extra(const char *name);   // HRY_TEST_EXTRA_SYMBOLS / _BITS: counted on top of a reference stream's own (tests of the format's limits)
 void encode_compat(Context &cx, Mesh &m, std::vector<uint8_t> &out);
+// ---- compat_stream.cpp: what encode_compat and encode_general share of the reference stream
+// the connectivity symbols of a walk on the device: group g's values and positions at d_grp_val / d_grp_pos + goff[g] (room for
+// their byte planes in d_connplanes), in d_op the operation bytes, op_position_table's thr / cum and the operation model's scratch
+struct ConnSymbols {
+	size_t goff[G_COUNT + 1];
+	uint32_t nop, ngr;
+	uint8_t *d_opsc;
+	uint32_t *d_opthr, *d_opcum;
+	void *d_opscratch;
+};
+ConnSymbols upload_conn_symbols(Context &cx, const WalkResult &w);
+// the groups' values in d_grp_val -> their byte planes in d_connplanes (numtri false: but for the polygons' triangle counts --
+// chunked.cpp: its pipeline has split them already)
+void split_conn_groups(Context &cx, const WalkResult &w, bool numtri = true);
+void launch_conn_models(Context &cx, const WalkResult &w, const ConnSymbols &cs);   // split_conn_groups, then the operation model's records
+// the model jobs of one stream: every byte plane with its initial counts (an INIT_* kind of build_init_tables) and the position of
+// its symbols in the stream -- pos_tab[j] + pos_add, or with no table pos_base + j * pos_stride; empty planes are skipped
+struct ModelJobs {
+	Context &cx;
+	std::vector<uint32_t> inits;
+	uint32_t total[INIT_KINDS] = {};
+	std::vector<dev::PlaneJob> jobs;
+	std::vector<dev::ChunkRef> chunks;
+	uint32_t max_total = 2;   // the largest total a model of the stream reaches: the reciprocal table covers it
+	ModelJobs(Context &cx, const Mesh &m);
+	void add(const uint8_t *sym, uint32_t n, int init, const uint32_t *pos_tab, uint32_t pos_add, uint32_t pos_base = 0, uint32_t pos_stride = 0);
+	void add_conn(const WalkResult &w, const ConnSymbols &cs);   // the planes of the connectivity groups
+	void send(const ConnSymbols &cs, uint32_t ns);               // tables, jobs and chunks -> HBM; reciprocals and the records of ns symbols sized
+	void run();                                                  // launch_model on the jobs
+};
+// finish_stream, the payload behind what `out` holds, the timing record of an encode that began at t_all
+void finish_compat_stream(Context &cx, uint32_t ns, Clock::time_point t_all, std::vector<uint8_t> &out);
 // A shard coded where it lies in the whole mesh (sharded.cpp: the in-process executor): the mesh handed to encode_chunked is a
 // SKELETON -- the shard's sizes, the lists' formats and bounds, its runs, no arrays; the context's connectivity and record arrays
 // are those of the whole mesh in the whole mesh's numbering, filled over the shard's index intervals; the walk goes over the

@@ -96,31 +96,122 @@ static GenView gen_view(const Context &cx, const Mesh &m)
 
 namespace {
 
-// a device arena filled from host vectors in one go
+// a device arena filled from host vectors in one go: the pieces first, room for what kernels compute behind them; a piece or a
+// room given a pointer of the caller's has it set to its place on the device by send()
 struct Arena {
 	struct Piece { const void *p; size_t bytes, at; };
+	struct Slot { void *ptr; size_t at; };   // ptr: the caller's pointer variable
 	std::vector<Piece> pieces;
-	size_t bytes = 0;
-	size_t add(const void *p, size_t n)
+	std::vector<Slot> slots;
+	size_t bytes = 0, filled = 0;   // the whole arena / its pieces
+	size_t room(size_t n)
 	{
 		const size_t at = (bytes + 15) & ~(size_t)15;
-		pieces.push_back(Piece{ p, n, at });
 		bytes = at + n;
 		return at;
 	}
+	template <typename T> void room(size_t n, T *&ptr) { slots.push_back(Slot{ &ptr, room(n) }); }
+	size_t add(const void *p, size_t n)
+	{
+		pieces.push_back(Piece{ p, n, room(n) });
+		filled = bytes;
+		return pieces.back().at;
+	}
 	template <typename V> size_t add(const V &v) { return add(v.data(), v.size() * sizeof(typename V::value_type)); }
+	template <typename V, typename T> void add(const V &v, T *&ptr) { slots.push_back(Slot{ &ptr, add(v) }); }
 	// the pieces -> the context's pinned block -> HBM, behind everything on the stream; no wait: the block is the context's, and the
 	// context's next call finds the stream drained.  (Until round 5 a pageable vector that grew piece by piece, its copy, and a wait
 	// for it because the vector went out of scope: 4 of the 11 ms of a 180 000-triangle scene's encode.)
 	void send(Context &cx, void *dst)
 	{
-		if (!bytes) return;
-		cx.h_gen.ensure(bytes);
+		for (const Slot &s : slots) { void *at = (uint8_t*)dst + s.at; memcpy(s.ptr, &at, sizeof at); }
+		if (!filled) return;
+		cx.h_gen.ensure(filled);
 		uint8_t *h = cx.h_gen.as<uint8_t>();
 		for (const Piece &q : pieces) if (q.bytes) memcpy(h + q.at, q.p, q.bytes);
-		HIP_OK(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, cx.stream));
+		HIP_OK(hipMemcpyAsync(dst, h, filled, hipMemcpyHostToDevice, cx.stream));
 	}
 };
+
+// what the stream says about one list, on the device (in cx.d_gen): the kinds of its references, the distances in creation order
+// and in the vertices' own names as 32-bit values, the records coded as data (which, at which half-edge / face, at which slot);
+// *_pos: every symbol's position in the ONE sequence of the reference stream (the container has none); gh, lh, data: room for
+// the distances' byte planes and the residuals' byte planes
+struct ListSyms {
+	uint32_t nt = 0, ng = 0, nlh = 0, nd = 0, nbytes = 0;
+	uint8_t *type_sym = nullptr, *d_slot = nullptr;
+	uint32_t *gh_vals = nullptr, *lh_vals = nullptr, *d_idx = nullptr, *d_he = nullptr;
+	uint32_t *type_pos = nullptr, *gh_pos = nullptr, *lh_pos = nullptr, *d_pos = nullptr;
+	uint8_t *gh = nullptr, *lh = nullptr, *data = nullptr;
+};
+struct RegionSyms { uint8_t *rv = nullptr, *rf = nullptr; uint32_t *rv_pos = nullptr, *rf_pos = nullptr; uint32_t n_rv = 0, n_rf = 0; };
+
+// collect_events' arrays -> the arena (pinned, one copy, no wait: Arena::send), with room behind for the planes the kernels make
+void send_events(Context &cx, const Events &E, bool positions, std::vector<ListSyms> &ls, RegionSyms &rg)
+{
+	Arena A;
+	ls.assign(E.ls.size(), ListSyms());
+	for (size_t l = 0; l < ls.size(); ++l) {
+		const ListStream &S = E.ls[l];
+		ListSyms &L = ls[l];
+		L.nt = (uint32_t)S.type_sym.size(); L.ng = (uint32_t)S.gh_val.size(); L.nlh = (uint32_t)S.lh_val.size(); L.nd = (uint32_t)S.d_idx.size(); L.nbytes = S.nbytes;
+		A.add(S.type_sym, L.type_sym); if (positions) A.add(S.type_pos, L.type_pos);
+		// (the distances go up as 32-bit values and are split into their byte planes on the device, like the connectivity groups:
+		// the host's byte loops were a millisecond of an 80 000-triangle scene)
+		A.add(S.gh_val, L.gh_vals); if (positions) A.add(S.gh_pos, L.gh_pos);
+		A.add(S.lh_val, L.lh_vals); if (positions) A.add(S.lh_pos, L.lh_pos);
+		if (positions) A.add(S.d_pos, L.d_pos);
+		A.add(S.d_idx, L.d_idx); A.add(S.d_he, L.d_he); A.add(S.d_slot, L.d_slot);
+	}
+	rg.n_rv = (uint32_t)E.rv_sym.size(); rg.n_rf = (uint32_t)E.rf_sym.size();
+	A.add(E.rv_sym, rg.rv); if (positions) A.add(E.rv_pos, rg.rv_pos);
+	A.add(E.rf_sym, rg.rf); if (positions) A.add(E.rf_pos, rg.rf_pos);
+	for (ListSyms &L : ls) { A.room((size_t)L.nd * L.nbytes, L.data); A.room((size_t)L.ng * 4, L.gh); A.room((size_t)L.nlh * 2, L.lh); }
+	cx.d_gen.ensure(std::max<size_t>(A.bytes, 16));
+	A.send(cx, cx.d_gen.p);
+}
+// the distances of every list -> their byte planes
+void split_histories(Context &cx, const std::vector<ListSyms> &ls)
+{
+	for (const ListSyms &L : ls) {
+		launch_split_bytes(cx.stream, L.gh_vals, L.ng, 4, L.gh);
+		launch_split_bytes(cx.stream, L.lh_vals, L.nlh, 2, L.lh);
+	}
+}
+// ranks of vertices and faces along the coding order, then the residuals of every list's records coded as data
+void general_residuals(Context &cx, const Mesh &m, uint32_t vc, uint32_t fc, const std::vector<ListSyms> &ls)
+{
+	cx.d_rank.ensure(std::max<size_t>((size_t)m.nv * 4 + (size_t)m.nf * 4, 16));
+	const uint32_t *d_rank = cx.d_rank.as<uint32_t>();
+	uint32_t *d_frank = cx.d_rank.as<uint32_t>() + m.nv;
+	const ConnView cv = cx.conn_view();
+	const GenView gv = gen_view(cx, m);
+	rank_coding_order(cx, m, vc);
+	launch_face_rank(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, d_frank);
+	for (size_t l = 0; l < ls.size(); ++l) {
+		const ListSyms &L = ls[l];
+		if (!L.nd || !L.nbytes) continue;
+		const ListDesc ld = make_list_desc(m.lists[l]);
+		const uint8_t *rec = cx.d_rec[l].as<uint8_t>();
+		if (m.lists[l].target == 1) launch_gen_vtx_resid(cx.stream, cv, gv, d_rank, L.d_he, L.d_slot, L.d_idx, L.nd, rec, ld, L.data);
+		else if (m.lists[l].target == 2) launch_gen_corner_resid(cx.stream, cv, gv, d_frank, L.d_he, L.d_slot, L.d_idx, L.nd, rec, ld, L.data);
+		else launch_gen_face_resid(cx.stream, L.d_idx, L.nd, rec, ld, L.data);
+	}
+}
+// where a plane of general_plane_layout lies, with the positions of its symbols in the reference stream (pos[j] + g.byte)
+struct PlaneAt { const uint8_t *sym; uint32_t n; const uint32_t *pos; };
+PlaneAt plane_at(const GenPlane &g, const std::vector<ListSyms> &ls, const RegionSyms &rg)
+{
+	if (g.what == GP_REGV) return PlaneAt{ rg.rv, rg.n_rv, rg.rv_pos };
+	if (g.what == GP_REGF) return PlaneAt{ rg.rf, rg.n_rf, rg.rf_pos };
+	const ListSyms &L = ls[g.list];
+	switch (g.what) {
+	case GP_TYPE: return PlaneAt{ L.type_sym, L.nt, L.type_pos };
+	case GP_GHIST: return PlaneAt{ L.gh + (size_t)g.byte * L.ng, L.ng, L.gh_pos };
+	case GP_LHIST: return PlaneAt{ L.lh + (size_t)g.byte * L.nlh, L.nlh, L.lh_pos };
+	default: return PlaneAt{ L.data + (size_t)g.byte * L.nd, L.nd, L.d_pos };
+	}
+}
 
 }   // namespace
 
@@ -147,175 +238,41 @@ void encode_general(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 	const uint32_t ns = E.end_pos;
 	const uint32_t vc = (uint32_t)w.order_v.size(), fc = (uint32_t)w.order_f.size();
 
-	// ---- H2D: orders, repaired twins, connectivity groups (as codec.cpp), then everything collect_events produced
+	// ---- H2D: orders, repaired twins, connectivity symbols, then everything collect_events produced
 	auto t_h2d = Clock::now();
 	HIP_OK(hipEventRecord(cx.ev[0], cx.stream));
 	cx.d_order_v.ensure(std::max<size_t>((size_t)vc * 4, 16));
 	cx.d_order_f.ensure(std::max<size_t>((size_t)fc * 4, 16));
-	cx.d_rank.ensure(std::max<size_t>((size_t)m.nv * 4 + (size_t)m.nf * 4, 16));
-	uint32_t *d_rank = cx.d_rank.as<uint32_t>(), *d_frank = d_rank + m.nv;
 	if (vc) HIP_OK(hipMemcpyAsync(cx.d_order_v.p, w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
 	if (fc) HIP_OK(hipMemcpyAsync(cx.d_order_f.p, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
 	upload_repaired_twins(cx, m, w);
-	size_t ngrp = 0;
-	for (int g = 0; g < G_COUNT; ++g) ngrp += w.grp_val[g].size();
-	const size_t nop = w.op_sc.size();
-	cx.d_grp_val.ensure(std::max<size_t>(ngrp * 4, 16));
-	cx.d_grp_pos.ensure(std::max<size_t>(ngrp * 4, 16));
-	// operations as the walk wrote them (symbol | order class << 3) + where the connectivity groups sit between them: the
-	// device evaluates the operation model and places the records (k_opmodel_*)
-	std::vector<uint32_t> op_thr, op_cum;
-	op_position_table(w, op_thr, op_cum);
-	const size_t op_bytes = (nop + 15) & ~(size_t)15, ngr = op_thr.size();
-	cx.d_op.ensure(std::max<size_t>(op_bytes + ngr * 8 + dev::op_model_scratch_bytes((uint32_t)nop) + 64, 64));
-	size_t goff[G_COUNT + 1] = { 0 };
-	for (int g = 0; g < G_COUNT; ++g) {
-		size_t n = w.grp_val[g].size();
-		goff[g + 1] = goff[g] + n;
-		if (!n) continue;
-		HIP_OK(hipMemcpyAsync(cx.d_grp_val.as<uint32_t>() + goff[g], w.grp_val[g].data(), n * 4, hipMemcpyHostToDevice, cx.stream));
-		HIP_OK(hipMemcpyAsync(cx.d_grp_pos.as<uint32_t>() + goff[g], w.grp_pos[g].data(), n * 4, hipMemcpyHostToDevice, cx.stream));
-	}
-	uint8_t *d_opsc = cx.d_op.as<uint8_t>();
-	uint32_t *d_opthr = (uint32_t*)(d_opsc + op_bytes), *d_opcum = d_opthr + ngr;
-	void *d_opscratch = d_opcum + ngr;
-	if (nop) HIP_OK(hipMemcpyAsync(d_opsc, w.op_sc.data(), nop, hipMemcpyHostToDevice, cx.stream));
-	if (ngr) {
-		HIP_OK(hipMemcpyAsync(d_opthr, op_thr.data(), ngr * 4, hipMemcpyHostToDevice, cx.stream));
-		HIP_OK(hipMemcpyAsync(d_opcum, op_cum.data(), ngr * 4, hipMemcpyHostToDevice, cx.stream));
-	}
-
-	// initial count tables (models.h:197-218)
-	std::vector<uint32_t> inits;
-	auto add_init = [&](const std::vector<uint32_t> &t) { uint32_t id = (uint32_t)(inits.size() / 256); inits.insert(inits.end(), t.begin(), t.end()); return id; };
-	std::vector<uint32_t> ones(256, 1), iop_init(256, 0), nt0(256, 0), nt1(256, 0), ty2(256, 0), ty3(256, 0), rv(256, 0), rf(256, 0);
-	for (int i = 0; i < 9; ++i) iop_init[i] = 1;
-	for (size_t d = 3; d < m.have_degree.size(); ++d) if (m.have_degree[d]) { ++nt0[(d - 2) & 0xff]; ++nt1[(d - 2) >> 8]; }
-	ty2[0] = ty2[1] = 1; ty3[0] = ty3[1] = ty3[2] = 1;
-	for (int r = 0; r < m.bind.nregs_vtx(); ++r) ++rv[r];
-	for (int r = 0; r < m.bind.nregs_face(); ++r) ++rf[r];
-	const uint32_t id_ones = add_init(ones), id_iop = add_init(iop_init), id_nt0 = add_init(nt0), id_nt1 = add_init(nt1),
-	               id_ty2 = add_init(ty2), id_ty3 = add_init(ty3), id_rv = add_init(rv), id_rf = add_init(rf);
-	auto total_of = [&](uint32_t id) { uint32_t s = 0; for (int i = 0; i < 256; ++i) s += inits[(size_t)id * 256 + i]; return s; };
-	cx.d_init.ensure(inits.size() * 4);
-	HIP_OK(hipMemcpyAsync(cx.d_init.p, inits.data(), inits.size() * 4, hipMemcpyHostToDevice, cx.stream));
-
+	const ConnSymbols cs = upload_conn_symbols(cx, w);
 	// the arena: symbol planes the host made, position tables, event tables; then room for the residual planes the kernels make
-	Arena A;
-	struct ListAt { size_t type_sym, type_pos, gh_vals, gh_planes, gh_pos, lh_vals, lh_planes, lh_pos, d_pos, d_idx, d_he, d_slot, planes; };
-	std::vector<ListAt> at(m.lists.size());
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		const ListStream &S = E.ls[l];
-		ListAt &T = at[l];
-		T.type_sym = A.add(S.type_sym); T.type_pos = A.add(S.type_pos);
-		// (the distances go up as 32-bit values and are split into their byte planes on the device, like the connectivity groups:
-		// the host's byte loops were a millisecond of an 80 000-triangle scene)
-		T.gh_vals = A.add(S.gh_val); T.gh_pos = A.add(S.gh_pos);
-		T.lh_vals = A.add(S.lh_val); T.lh_pos = A.add(S.lh_pos);
-		T.d_pos = A.add(S.d_pos); T.d_idx = A.add(S.d_idx); T.d_he = A.add(S.d_he); T.d_slot = A.add(S.d_slot);
-	}
-	const size_t rv_sym = A.add(E.rv_sym), rv_pos = A.add(E.rv_pos), rf_sym = A.add(E.rf_sym), rf_pos = A.add(E.rf_pos);
-	size_t arena_bytes = (A.bytes + 15) & ~(size_t)15;
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		at[l].planes = arena_bytes; arena_bytes += ((size_t)E.ls[l].d_pos.size() * E.ls[l].nbytes + 15) & ~(size_t)15;
-		at[l].gh_planes = arena_bytes; arena_bytes += (E.ls[l].gh_val.size() * 4 + 15) & ~(size_t)15;
-		at[l].lh_planes = arena_bytes; arena_bytes += (E.ls[l].lh_val.size() * 2 + 15) & ~(size_t)15;
-	}
-	cx.d_gen.ensure(std::max<size_t>(arena_bytes, 16));
-	A.send(cx, cx.d_gen.p);
-	uint8_t *arena = cx.d_gen.as<uint8_t>();
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		launch_split_bytes(cx.stream, (const uint32_t*)(arena + at[l].gh_vals), (uint32_t)E.ls[l].gh_val.size(), 4, arena + at[l].gh_planes);
-		launch_split_bytes(cx.stream, (const uint32_t*)(arena + at[l].lh_vals), (uint32_t)E.ls[l].lh_val.size(), 2, arena + at[l].lh_planes);
-	}
+	std::vector<ListSyms> ls;
+	RegionSyms rg;
+	send_events(cx, E, true, ls, rg);
+	split_histories(cx, ls);
 
-	size_t conn_plane_bytes = 0;
-	for (int g = 0; g < G_COUNT; ++g) conn_plane_bytes += w.grp_val[g].size() * kGroupBytes[g];
-	cx.d_connplanes.ensure(std::max<size_t>(conn_plane_bytes, 16));
-
-	// ---- model jobs
-	std::vector<PlaneJob> jobs;
-	std::vector<ChunkRef> chunks;
-	uint32_t max_total = 2;
-	auto add_job = [&](const uint8_t *sym, uint32_t n, uint32_t init_id, const uint32_t *pos_tab, uint32_t pos_add) {
-		if (!n) return;
-		PlaneJob j{};
-		j.sym = sym; j.n = n; j.init = cx.d_init.as<uint32_t>() + (size_t)init_id * 256; j.t0 = total_of(init_id);
-		j.pos_tab = pos_tab; j.pos_add = pos_add; j.pos_base = 0; j.pos_stride = 0;
-		j.chunk0 = (uint32_t)chunks.size();
-		for (uint32_t f = 0; f < n; f += kChunk) chunks.push_back(ChunkRef{ (uint32_t)jobs.size(), f });
-		jobs.push_back(j);
-		max_total = std::max(max_total, j.t0 + n);
-	};
-	{
-		size_t poff = 0;
-		for (int g = 0; g < G_COUNT; ++g) {
-			uint32_t n = (uint32_t)w.grp_val[g].size();
-			for (int k = 0; k < kGroupBytes[g]; ++k) {
-				uint32_t init_id = g == G_IOP ? id_iop : g == G_NUMTRI ? (k == 0 ? id_nt0 : id_nt1) : id_ones;
-				add_job(cx.d_connplanes.as<uint8_t>() + poff + (size_t)k * n, n, init_id, cx.d_grp_pos.as<uint32_t>() + goff[g], (uint32_t)k);
-			}
-			poff += (size_t)n * kGroupBytes[g];
-		}
+	// ---- model jobs: the connectivity's, then the planes in the order of the layout (regions; per list kinds, history, per-vertex
+	// history at corner lists, data).  collect_events makes no region symbols for one region and no per-vertex distances but at
+	// corner lists: what the layout leaves out is empty
+	ModelJobs J(cx, m);
+	J.add_conn(w, cs);
+	for (const GenPlane &g : general_plane_layout(m)) {
+		const PlaneAt p = plane_at(g, ls, rg);
+		J.add(p.sym, p.n, g.init, p.pos, (uint32_t)g.byte);
 	}
-	add_job(arena + rv_sym, (uint32_t)E.rv_sym.size(), id_rv, (const uint32_t*)(arena + rv_pos), 0);
-	add_job(arena + rf_sym, (uint32_t)E.rf_sym.size(), id_rf, (const uint32_t*)(arena + rf_pos), 0);
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		const ListStream &S = E.ls[l];
-		const ListAt &T = at[l];
-		add_job(arena + T.type_sym, (uint32_t)S.type_sym.size(), m.lists[l].target == 2 ? id_ty3 : id_ty2, (const uint32_t*)(arena + T.type_pos), 0);
-		for (int k = 0; k < 4; ++k) add_job(arena + T.gh_planes + (size_t)k * S.gh_val.size(), (uint32_t)S.gh_val.size(), id_ones, (const uint32_t*)(arena + T.gh_pos), (uint32_t)k);
-		for (int k = 0; k < 2; ++k) add_job(arena + T.lh_planes + (size_t)k * S.lh_val.size(), (uint32_t)S.lh_val.size(), id_ones, (const uint32_t*)(arena + T.lh_pos), (uint32_t)k);
-		const uint32_t nd = (uint32_t)S.d_pos.size();
-		for (uint32_t k = 0; k < S.nbytes; ++k) add_job(arena + T.planes + (size_t)k * nd, nd, id_ones, (const uint32_t*)(arena + T.d_pos), k);
-	}
-	max_total = std::max<uint32_t>(max_total, (uint32_t)nop + 8);   // the operation model's total: 7 + the operations so far
-	cx.d_jobs.ensure(std::max<size_t>(jobs.size() * sizeof(PlaneJob), 16));
-	cx.d_chunks.ensure(std::max<size_t>(chunks.size() * sizeof(ChunkRef), 16));
-	cx.d_hist.ensure(std::max<size_t>(chunks.size() * 256 * 4, 16));
-	if (!jobs.empty()) HIP_OK(hipMemcpyAsync(cx.d_jobs.p, jobs.data(), jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice, cx.stream));
-	if (!chunks.empty()) HIP_OK(hipMemcpyAsync(cx.d_chunks.p, chunks.data(), chunks.size() * sizeof(ChunkRef), hipMemcpyHostToDevice, cx.stream));
-	cx.ensure_magic(max_total + 1);
-	cx.d_rec_sym.ensure(std::max<size_t>((size_t)ns * sizeof(SymRec), 16));
-	cx.d_sym_l.ensure(std::max<size_t>((size_t)ns * 4, 16));
+	J.send(cs, ns);
 	HIP_OK(hipStreamSynchronize(cx.stream));
 	cx.timing.h2d_ms = ms_since(t_h2d);
 
 	// ---- device: residuals of the records coded as data
-	ConnView cv = cx.conn_view();
-	const GenView gv = gen_view(cx, m);
 	HIP_OK(hipEventRecord(cx.ev[1], cx.stream));
-	HIP_OK(hipMemsetAsync(d_rank, 0xff, (size_t)m.nv * 4, cx.stream));
-	launch_rank(cx.stream, cx.d_order_v.as<uint32_t>(), vc, cv.org, d_rank);
-	launch_face_rank(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, d_frank);
-	for (size_t l = 0; l < m.lists.size(); ++l) {
-		const ListStream &S = E.ls[l];
-		const ListAt &T = at[l];
-		const uint32_t nd = (uint32_t)S.d_pos.size();
-		if (!nd || !S.nbytes) continue;
-		const ListDesc ld = make_list_desc(m.lists[l]);
-		const uint32_t *he = (const uint32_t*)(arena + T.d_he), *idx = (const uint32_t*)(arena + T.d_idx);
-		const uint8_t *slot = arena + T.d_slot;
-		const uint8_t *rec = cx.d_rec[l].as<uint8_t>();
-		if (m.lists[l].target == 1) launch_gen_vtx_resid(cx.stream, cv, gv, d_rank, he, slot, idx, nd, rec, ld, arena + T.planes);
-		else if (m.lists[l].target == 2) launch_gen_corner_resid(cx.stream, cv, gv, d_frank, he, slot, idx, nd, rec, ld, arena + T.planes);
-		else launch_gen_face_resid(cx.stream, idx, nd, rec, ld, arena + T.planes);
-	}
+	general_residuals(cx, m, vc, fc, ls);
 	HIP_OK(hipEventRecord(cx.ev[2], cx.stream));
 	// ---- device: models -> per-symbol records in stream order
-	{
-		size_t poff = 0;
-		for (int g = 0; g < G_COUNT; ++g) {
-			uint32_t n = (uint32_t)w.grp_val[g].size();
-			launch_split_bytes(cx.stream, cx.d_grp_val.as<uint32_t>() + goff[g], n, kGroupBytes[g], cx.d_connplanes.as<uint8_t>() + poff);
-			poff += (size_t)n * kGroupBytes[g];
-		}
-	}
-	const MagicEnt *magic = cx.d_magic.as<MagicEnt>();
-	SymRec *rec = cx.d_rec_sym.as<SymRec>();
-	uint32_t *sym_l = cx.d_sym_l.as<uint32_t>();
-	launch_op_model(cx.stream, d_opsc, (uint32_t)nop, d_opthr, d_opcum, (uint32_t)ngr, d_opscratch, magic, rec, sym_l);
-	launch_model(cx.stream, cx.d_jobs.as<PlaneJob>(), (uint32_t)jobs.size(), cx.d_chunks.as<ChunkRef>(), (uint32_t)chunks.size(), cx.d_hist.as<uint32_t>(), magic, rec, sym_l);
+	launch_conn_models(cx, w, cs);
+	J.run();
 
 	if (cx.keep_stages) {
 		cx.stage_put_host("order_v", w.order_v.data(), (size_t)vc * 4);
@@ -323,22 +280,13 @@ void encode_general(Context &cx, Mesh &m, std::vector<uint8_t> &out)
 		cx.stage_put("rec", cx.d_rec_sym.p, (size_t)ns * sizeof(SymRec));
 		cx.stage_put("sym_l", cx.d_sym_l.p, (size_t)ns * 4);
 	}
-	std::vector<uint8_t> payload;
-	finish_stream(cx, ns, payload);
-	out.insert(out.end(), payload.begin(), payload.end());
+	finish_compat_stream(cx, ns, t_all, out);
 	if (cx.want_order) {   // HRY_FLAG_ORDER (order.cpp): the creation order of every list's records is the host's (collect_events), uploaded with the arena above
 		cx.order_lists.assign(m.lists.size(), OrderListSource{});
-		for (size_t l = 0; l < m.lists.size(); ++l) cx.order_lists[l] = OrderListSource{ (const uint32_t*)(arena + at[l].d_idx), (uint32_t)E.ls[l].d_idx.size() };
+		for (size_t l = 0; l < m.lists.size(); ++l) cx.order_lists[l] = OrderListSource{ ls[l].d_idx, ls[l].nd };
 		order_build(cx, m, w, cx.d_order_v.as<uint32_t>(), cx.d_order_f.as<uint32_t>());
+		cx.timing.total_ms = ms_since(t_all);   // (the maps' build counts into the encode's time)
 	}
-
-	cx.timing.k_predict_ms = cx.elapsed(1, 2);
-	cx.timing.k_model_ms = cx.elapsed(2, 3);
-	cx.timing.k_rchain_ms = cx.elapsed(3, 4);
-	cx.timing.device_ms = cx.elapsed(1, 5);
-	cx.timing.n_symbols = ns;
-	cx.timing.payload_bytes = payload.size();
-	cx.timing.total_ms = ms_since(t_all);
 }
 
 // Device part of a decode with general bindings: connectivity, bindings and the lists (holding residual codes in record layout,
@@ -395,8 +343,7 @@ static void reconstruct_general(Context &cx, Mesh &m, const OrderVec &order_v, c
 	ConnView cv = cx.conn_view();
 	const GenView gv = gen_view(cx, m);
 	HIP_OK(hipEventRecord(cx.ev[3], cx.stream));
-	HIP_OK(hipMemsetAsync(cx.d_rank.p, 0xff, (size_t)m.nv * 4, cx.stream));
-	launch_rank(cx.stream, cx.d_order_v.as<uint32_t>(), vc, cv.org, cx.d_rank.as<uint32_t>());
+	rank_coding_order(cx, m, vc);
 	for (const GenChainJob &j : lead)
 		launch_gen_sources(cx.stream, j.kind, cv, gv, cx.d_rank.as<uint32_t>(), j.ev_he, j.ev_slot, j.n, const_cast<uint32_t*>(j.src), const_cast<uint8_t*>(j.nsrc));
 	for (size_t l = 0; l < nl; ++l) {   // face lists: no prediction (attrcode.h:245-270)
@@ -466,52 +413,21 @@ void general_planes_encode(Context &cx, Mesh &m, const WalkResult &w, std::vecto
 {
 	const uint32_t vc = (uint32_t)w.order_v.size(), fc = (uint32_t)w.order_f.size();
 	const size_t nl = m.lists.size();
-	struct Lst { uint32_t nt = 0, ng = 0, nlh = 0, nd = 0, nbytes = 0; const uint8_t *type_sym = nullptr, *d_slot = nullptr; const uint32_t *gh_vals = nullptr, *lh_vals = nullptr, *d_idx = nullptr, *d_he = nullptr;
-	             uint8_t *gh = nullptr, *lh = nullptr, *data = nullptr; };
-	std::vector<Lst> ls(nl);
-	const uint8_t *rv = nullptr, *rf = nullptr;
-	uint32_t n_rv = 0, n_rf = 0;
+	std::vector<ListSyms> ls;
+	RegionSyms reg;
 	ConnView cv = cx.conn_view();
 	const GenView gv = gen_view(cx, m);
 	const Bindings &b = m.bind;
 	static const bool host_events_env = env_on("HRY_HOST_EVENTS");
 	bool host_events = host_events_env;
-	Events E;   // (the host's arrays live until the arena has been copied into pinned memory: Arena::send)
 again:
 	if (host_events) {
 		const auto t_events = Clock::now();
+		Events E;   // (the host's arrays live until the arena has been copied into pinned memory: Arena::send)
 		collect_events(m, w, 0, false, E);
 		cx.timing.host_walk_ms += ms_since(t_events);   // (host bookkeeping along the coding order, like the walk: it was missing from the record)
 		if (trace_on()) fprintf(stderr, "[hry enc] %8.3f ms  which record every element names (host)\n", ms_since(t_events));
-		Arena A;
-		struct At { size_t type_sym, gh_vals, gh, lh_vals, lh, d_idx, d_he, d_slot, planes; };
-		std::vector<At> at(nl);
-		for (size_t l = 0; l < nl; ++l) {
-			const ListStream &S = E.ls[l];
-			At &T = at[l];
-			T.type_sym = A.add(S.type_sym);
-			T.gh_vals = A.add(S.gh_val); T.lh_vals = A.add(S.lh_val);   // (32-bit values: split into byte planes on the device)
-			T.d_idx = A.add(S.d_idx); T.d_he = A.add(S.d_he); T.d_slot = A.add(S.d_slot);
-		}
-		const size_t rv_at = A.add(E.rv_sym), rf_at = A.add(E.rf_sym);
-		size_t arena_bytes = (A.bytes + 15) & ~(size_t)15;
-		for (size_t l = 0; l < nl; ++l) {
-			at[l].planes = arena_bytes; arena_bytes += ((size_t)E.ls[l].d_idx.size() * E.ls[l].nbytes + 15) & ~(size_t)15;
-			at[l].gh = arena_bytes; arena_bytes += (E.ls[l].gh_val.size() * 4 + 15) & ~(size_t)15;
-			at[l].lh = arena_bytes; arena_bytes += (E.ls[l].lh_val.size() * 2 + 15) & ~(size_t)15;
-		}
-		cx.d_gen.ensure(std::max<size_t>(arena_bytes, 16));
-		A.send(cx, cx.d_gen.p);
-		uint8_t *arena = cx.d_gen.as<uint8_t>();
-		for (size_t l = 0; l < nl; ++l) {
-			const ListStream &S = E.ls[l];
-			Lst &L = ls[l];
-			L.nt = (uint32_t)S.type_sym.size(); L.ng = (uint32_t)S.gh_val.size(); L.nlh = (uint32_t)S.lh_val.size(); L.nd = (uint32_t)S.d_idx.size(); L.nbytes = S.nbytes;
-			L.type_sym = arena + at[l].type_sym; L.gh_vals = (const uint32_t*)(arena + at[l].gh_vals); L.lh_vals = (const uint32_t*)(arena + at[l].lh_vals);
-			L.d_idx = (const uint32_t*)(arena + at[l].d_idx); L.d_he = (const uint32_t*)(arena + at[l].d_he); L.d_slot = arena + at[l].d_slot;
-			L.gh = arena + at[l].gh; L.lh = arena + at[l].lh; L.data = arena + at[l].planes;
-		}
-		rv = arena + rv_at; rf = arena + rf_at; n_rv = (uint32_t)E.rv_sym.size(); n_rf = (uint32_t)E.rf_sym.size();
+		send_events(cx, E, false, ls, reg);
 	} else {
 		// ---- on the device.  Most references a list can get, without a pass over the orders: every coded element at every slot
 		// of the region with the most slots for it (corner lists: every half-edge)
@@ -536,10 +452,6 @@ again:
 		std::vector<int32_t> off_f(b.off_facelist.begin(), b.off_facelist.end()), off_v(b.off_vtxlist.begin(), b.off_vtxlist.end()), off_c(b.off_cornerlist.begin(), b.off_cornerlist.end());
 		const size_t a_off_f = A.add(off_f), a_off_v = A.add(off_v), a_off_c = A.add(off_c);
 		const size_t a_lf = A.add(b.reg_facelist), a_lv = A.add(b.reg_vtxlist), a_lc = A.add(b.reg_cornerlist);
-		size_t bytes = (A.bytes + 15) & ~(size_t)15;
-		auto take = [&](size_t n) { const size_t at = bytes; bytes += (n + 15) & ~(size_t)15; return at; };
-		struct At { size_t type_sym, gh_vals, lh_vals, d_idx, d_he, d_slot, gh, lh, planes, ws; };
-		std::vector<At> at(nl);
 		// (the vertices' names at the corner slots are shared by the corner lists: at most every half-edge at every corner slot)
 		uint32_t most_corner_slots = 0;
 		bool any_corner = false;
@@ -547,20 +459,25 @@ again:
 		for (size_t l = 0; l < nl; ++l) any_corner |= m.lists[l].target == 2 && max_refs[l] != 0;
 		if ((uint64_t)m.ne() * most_corner_slots >= (1ull << 31) || (uint64_t)b.nb_corner * m.nv >= (1ull << 31)) throw Error(HRY_E_UNSUPPORTED, "more than 2^31 corner references");
 		const uint32_t corner_refs_max = any_corner ? m.ne() * most_corner_slots : 0u, head_words = any_corner ? (uint32_t)b.nb_corner * m.nv : 0u;
+		ls.assign(nl, ListSyms());
+		std::vector<uint8_t*> ws(nl, nullptr);
 		for (size_t l = 0; l < nl; ++l) {
 			const size_t r = max_refs[l];
 			const uint32_t n_order = m.lists[l].target == 1 ? vc : fc;
-			ls[l].nbytes = (uint32_t)m.lists[l].coded_bytes();
-			at[l].type_sym = take(r); at[l].gh_vals = take(r * 4); at[l].lh_vals = take(m.lists[l].target == 2 ? r * 4 : 0);
-			at[l].d_idx = take(r * 4); at[l].d_he = take(r * 4); at[l].d_slot = take(r);
-			at[l].gh = take(r * 4); at[l].lh = take(m.lists[l].target == 2 ? r * 2 : 0); at[l].planes = take(r * ls[l].nbytes);
-			at[l].ws = take(r ? dev::events_list_workspace_bytes(n_order, (uint32_t)r, m.lists[l].count) : 0);
+			ListSyms &L = ls[l];
+			L.nbytes = (uint32_t)m.lists[l].coded_bytes();
+			A.room(r, L.type_sym); A.room(r * 4, L.gh_vals); A.room(m.lists[l].target == 2 ? r * 4 : 0, L.lh_vals);
+			A.room(r * 4, L.d_idx); A.room(r * 4, L.d_he); A.room(r, L.d_slot);
+			A.room(r * 4, L.gh); A.room(m.lists[l].target == 2 ? r * 2 : 0, L.lh); A.room(r * L.nbytes, L.data);
+			A.room(r ? dev::events_list_workspace_bytes(n_order, (uint32_t)r, m.lists[l].count) : 0, ws[l]);
 		}
-		const size_t a_counts = take((nl * 4 + 4) * 4), a_rv = take(vc), a_rf = take(fc), a_names = take(dev::events_names_workspace_bytes(fc, corner_refs_max, head_words));
+		const size_t a_counts = A.room((nl * 4 + 4) * 4);
+		A.room(vc, reg.rv); A.room(fc, reg.rf);
+		const size_t a_names = A.room(dev::events_names_workspace_bytes(fc, corner_refs_max, head_words));
 		// (the arena is sized from upper bounds -- every half-edge times the most slots a region binds to the list -- where the
 		// host's loop needs the actual counts: a scene whose bounds do not fit the device's memory takes the host's loop)
 		bool no_room = false;
-		try { cx.d_gen.ensure(std::max<size_t>(bytes, 16)); } catch (const Error &) { (void)hipGetLastError(); no_room = true; }
+		try { cx.d_gen.ensure(std::max<size_t>(A.bytes, 16)); } catch (const Error &) { (void)hipGetLastError(); no_room = true; }
 		if (no_room) { host_events = true; goto again; }
 		A.send(cx, cx.d_gen.p);
 		uint8_t *arena = cx.d_gen.as<uint8_t>();
@@ -575,14 +492,14 @@ again:
 				if (tg == 3) { if (!phase) HIP_OK(hipMemsetAsync(d_counts + 4 * l, 0, 16, cx.stream)); continue; }
 				const uint32_t *order = tg == 1 ? cx.d_order_v.as<uint32_t>() : cx.d_order_f.as<uint32_t>();
 				const uint32_t n_order = tg == 1 ? vc : fc;
+				ListSyms &L = ls[l];
 				if (!phase) dev::launch_list_refs(cx.stream, tg, (uint32_t)l, m.lists[l].count, cv, gv, rg, order, n_order, max_refs[l], m.nv, fc, corner_refs_max, head_words, arena + a_names,
-				                                  arena + at[l].ws, d_counts + 4 * l, d_err);
-				else dev::launch_list_kinds(cx.stream, tg, m.lists[l].count, cv, n_order, max_refs[l], m.nv, fc, corner_refs_max, head_words, arena + a_names, arena + at[l].ws, arena + at[l].type_sym,
-				                            (uint32_t*)(arena + at[l].gh_vals), (uint32_t*)(arena + at[l].lh_vals), (uint32_t*)(arena + at[l].d_idx), (uint32_t*)(arena + at[l].d_he),
-				                            arena + at[l].d_slot, d_counts + 4 * l, d_err);
+				                                  ws[l], d_counts + 4 * l, d_err);
+				else dev::launch_list_kinds(cx.stream, tg, m.lists[l].count, cv, n_order, max_refs[l], m.nv, fc, corner_refs_max, head_words, arena + a_names, ws[l], L.type_sym,
+				                            L.gh_vals, L.lh_vals, L.d_idx, L.d_he, L.d_slot, d_counts + 4 * l, d_err);
 			}
-		if (b.nregs_vtx() > 1) { dev::launch_region_symbols(cx.stream, 1, cv, gv, cx.d_order_v.as<uint32_t>(), vc, arena + a_rv); rv = arena + a_rv; n_rv = vc; }
-		if (b.nregs_face() > 1) { dev::launch_region_symbols(cx.stream, 0, cv, gv, cx.d_order_f.as<uint32_t>(), fc, arena + a_rf); rf = arena + a_rf; n_rf = fc; }
+		if (b.nregs_vtx() > 1) { dev::launch_region_symbols(cx.stream, 1, cv, gv, cx.d_order_v.as<uint32_t>(), vc, reg.rv); reg.n_rv = vc; }
+		if (b.nregs_face() > 1) { dev::launch_region_symbols(cx.stream, 0, cv, gv, cx.d_order_f.as<uint32_t>(), fc, reg.rf); reg.n_rf = fc; }
 		// how many of every kind: the one thing the host needs (the planes' lengths)
 		cx.h_small.ensure(std::max<size_t>((nl * 4 + 4) * 4, 4096));
 		uint32_t *h_counts = cx.h_small.as<uint32_t>();
@@ -593,46 +510,20 @@ again:
 		if (err & 1u) throw Error(HRY_E_ARG, "an element names a record outside its list");
 		if (err & 2u) throw Error(HRY_E_UNSUPPORTED, "more than 65536 different records of one list at one vertex (io.h:104 codes 16 bits)");
 		for (size_t l = 0; l < nl; ++l) {
-			Lst &L = ls[l];
+			ListSyms &L = ls[l];
 			L.nt = h_counts[4 * l]; L.ng = h_counts[4 * l + 1]; L.nlh = h_counts[4 * l + 2]; L.nd = h_counts[4 * l + 3];
 			if (L.nt > max_refs[l] || (uint64_t)L.ng + L.nlh + L.nd != L.nt) throw Error(HRY_E_INTERNAL, "references on the device: the kinds do not add up");
-			L.type_sym = arena + at[l].type_sym; L.gh_vals = (const uint32_t*)(arena + at[l].gh_vals); L.lh_vals = (const uint32_t*)(arena + at[l].lh_vals);
-			L.d_idx = (const uint32_t*)(arena + at[l].d_idx); L.d_he = (const uint32_t*)(arena + at[l].d_he); L.d_slot = arena + at[l].d_slot;
-			L.gh = arena + at[l].gh; L.lh = arena + at[l].lh; L.data = arena + at[l].planes;
 		}
 	}
 	if (cx.want_order) {   // HRY_FLAG_ORDER (order.cpp): every list's records in creation order stay where they are in the arena until the encode ends
 		cx.order_lists.assign(nl, OrderListSource{});
 		for (size_t l = 0; l < nl; ++l) cx.order_lists[l] = OrderListSource{ ls[l].d_idx, ls[l].nd };
 	}
-	for (size_t l = 0; l < nl; ++l) {
-		launch_split_bytes(cx.stream, ls[l].gh_vals, ls[l].ng, 4, ls[l].gh);
-		launch_split_bytes(cx.stream, ls[l].lh_vals, ls[l].nlh, 2, ls[l].lh);
-	}
-	cx.d_rank.ensure(std::max<size_t>((size_t)m.nv * 4 + (size_t)m.nf * 4, 16));
-	uint32_t *d_rank = cx.d_rank.as<uint32_t>(), *d_frank = d_rank + m.nv;
-	HIP_OK(hipMemsetAsync(d_rank, 0xff, (size_t)m.nv * 4, cx.stream));
-	launch_rank(cx.stream, cx.d_order_v.as<uint32_t>(), vc, cv.org, d_rank);
-	launch_face_rank(cx.stream, cv, cx.d_order_f.as<uint32_t>(), fc, d_frank);
-	for (size_t l = 0; l < nl; ++l) {
-		const Lst &L = ls[l];
-		if (!L.nd || !L.nbytes) continue;
-		const ListDesc ld = make_list_desc(m.lists[l]);
-		const uint8_t *rec = cx.d_rec[l].as<uint8_t>();
-		if (m.lists[l].target == 1) launch_gen_vtx_resid(cx.stream, cv, gv, d_rank, L.d_he, L.d_slot, L.d_idx, L.nd, rec, ld, L.data);
-		else if (m.lists[l].target == 2) launch_gen_corner_resid(cx.stream, cv, gv, d_frank, L.d_he, L.d_slot, L.d_idx, L.nd, rec, ld, L.data);
-		else launch_gen_face_resid(cx.stream, L.d_idx, L.nd, rec, ld, L.data);
-	}
+	split_histories(cx, ls);
+	general_residuals(cx, m, vc, fc, ls);
 	for (const GenPlane &g : general_plane_layout(m)) {
-		const Lst *L = g.list >= 0 ? &ls[g.list] : nullptr;
-		switch (g.what) {
-		case GP_REGV: planes.push_back(PlaneRef{ rv, n_rv, g.init }); break;
-		case GP_REGF: planes.push_back(PlaneRef{ rf, n_rf, g.init }); break;
-		case GP_TYPE: planes.push_back(PlaneRef{ L->type_sym, L->nt, g.init }); break;
-		case GP_GHIST: planes.push_back(PlaneRef{ L->gh + (size_t)g.byte * L->ng, L->ng, g.init }); break;
-		case GP_LHIST: planes.push_back(PlaneRef{ L->lh + (size_t)g.byte * L->nlh, L->nlh, g.init }); break;
-		default: planes.push_back(PlaneRef{ L->data + (size_t)g.byte * L->nd, L->nd, g.init }); break;
-		}
+		const PlaneAt p = plane_at(g, ls, reg);
+		planes.push_back(PlaneRef{ p.sym, p.n, g.init });
 	}
 }
 

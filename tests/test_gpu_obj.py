@@ -6,6 +6,8 @@ Reference: formats/obj/reader.rl:108-299, writer.cc:20-132, formats/hry/attrcode
 import hashlib
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -132,6 +134,32 @@ def test_chunked_container_of_general_bindings(cx, name, tag, chunk, monkeypatch
     same_decoded(cx.read_hry(got), ref)
     monkeypatch.setenv("HRY_GENERIC_VERTEX", "1")
     same_decoded(cx.read_hry(got), ref)
+
+
+def test_host_events_branch_writes_the_device_branch_s_containers(cx):
+    """general_planes_encode names the records on the device, or (HRY_HOST_EVENTS, a hub, no room) with the host's loop; both lay
+    their symbols out through the same views and run the same residual pass.  The switch is read once per process: a fresh child
+    (tests/tools/obj_containers.py) codes every small fixture in every variant with the host's loop, at chunk_syms 0 and 256; each
+    container must hash like this process' (device branch) and like the oracle's at the same chunk size"""
+    env = dict(os.environ, HRY_HOST_EVENTS="1", HRY_TRACE="1")
+    r = subprocess.run([sys.executable, os.path.join(util.ROOT, "tests", "tools", "obj_containers.py")], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "which record every element names (host)" in r.stderr   # the child did take the host's loop
+    child = {tuple(ln.split()[:3]): ln.split()[3:] for ln in r.stdout.splitlines()}
+    assert len(child) == 2 * len(SMALL)
+    for name, tag in SMALL:
+        quant, clear = util.flags_to_quant(MAN["small"][name]["variants"][tag]["flags"])
+        for chunk in (0, 256):
+            m = hc.Mesh.from_obj(_read(name + ".obj"), OBJ)
+            o = op.Mesh.from_obj(_read(name + ".obj"), OBJ)
+            if quant or clear:
+                cx.requant(m, quant, clear)
+                o.requant(quant, clear)
+            got = cx.write_hry(m, profile=hc.PROFILE_CHUNKED, chunk_syms=chunk)
+            chunk_syms = hc.container_info(got)["chunk_syms"]
+            want = [str(chunk_syms), hashlib.sha256(got).hexdigest()]
+            assert child[(name, tag, str(chunk))] == want, (name, tag, chunk)
+            assert hashlib.sha256(o.encode_chunked(chunk_syms).data).hexdigest() == want[1], (name, tag, chunk)
 
 
 def test_chunked_container_larger_scenes(cx):
