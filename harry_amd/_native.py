@@ -56,6 +56,12 @@ class PosError(C.Structure):
     _fields_ = [("max_dist", C.c_double), ("sum_sq_dist", C.c_double), ("compared", C.c_uint64), ("argmax", C.c_uint32), ("list", C.c_int32)]
 
 
+class NormalError(C.Structure):
+    """hry_normal_error: the faces' normal deviation (hry_distortion_normals, hry_quant_sweep_normals)"""
+    _fields_ = [("max_chord", C.c_double), ("sum_sq_chord", C.c_double), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("degenerate", C.c_uint64), ("collapsed", C.c_uint64), ("argmax", C.c_uint32), ("list", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("host_walk_ms", C.c_double), ("h2d_ms", C.c_double), ("device_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("total_ms", C.c_double), ("k_rchain_ms", C.c_double), ("k_model_ms", C.c_double), ("k_predict_ms", C.c_double),
@@ -84,8 +90,9 @@ FLAG_ORDER = 16
 NO_ELEMENT = 0xFFFFFFFF
 ORDER_TO_DECODED, ORDER_TO_SOURCE = 0, 1
 INGEST_WELD = 1
-DISTORTION_ROWS = 1
-TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST = 0, 1, 2, 3
+DISTORTION_ROWS, DISTORTION_NORMALS = 1, 4
+SWEEP_NORMALS = 1
+TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST, TOL_NORMAL_CHORD = 0, 1, 2, 3, 4
 
 _lib = None
 
@@ -195,6 +202,11 @@ def load():
     L.hry_distortion_component.restype = C.c_int; L.hry_distortion_component.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CompError)]
     L.hry_distortion_position.restype = C.c_int; L.hry_distortion_position.argtypes = [vp, C.POINTER(PosError)]
     L.hry_distortion_position_component.restype = C.c_int; L.hry_distortion_position_component.argtypes = [vp]
+    L.hry_distortion_normals.restype = C.c_int; L.hry_distortion_normals.argtypes = [vp, C.POINTER(NormalError)]
+    L.hry_quant_sweep_build_ex.restype = C.c_int; L.hry_quant_sweep_build_ex.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.hry_quant_sweep_normals.restype = C.c_int; L.hry_quant_sweep_normals.argtypes = [vp, C.c_int, C.POINTER(NormalError)]
+    L.hry_chord_angle.restype = C.c_int; L.hry_chord_angle.argtypes = [C.c_double, C.POINTER(C.c_double)]
+    L.hry_angle_chord.restype = C.c_int; L.hry_angle_chord.argtypes = [C.c_double, C.POINTER(C.c_double)]
     L.hry_distortion_get.restype = C.c_int; L.hry_distortion_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.hry_distortion_copy.restype = C.c_int; L.hry_distortion_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_distortion_stat.restype = C.c_int; L.hry_distortion_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]

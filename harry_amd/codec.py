@@ -582,16 +582,25 @@ class Codec:
         """hry_distortion_build: the error of `other` against `src`, component by component, on the device.  order: the numbering
         maps of the encode that relates them (write_hry(..., return_order=True)), None: row i against row i.  rows: also one error
         value per row of every compared list ("error<l>", float32 in HBM)"""
+        return self.distortion_ex(src, other, order, rows)
+
+    def distortion_ex(self, src: Mesh, other: Mesh, order: "Order | None" = None, rows: bool = False, normals: bool = False) -> "Distortion":
+        """distortion with the build's further flags.  normals: also the angle between each face's normal before and after
+        (HRY_DISTORTION_NORMALS: Distortion.normals; with rows the per-face buffer "normal_error")"""
         h = C.c_void_p()
         nat.check(nat.load().hry_distortion_build(self.h, src.h, other.h, order.h if order is not None else None,
-                                                  nat.DISTORTION_ROWS if rows else 0, C.byref(h)))
+                                                  (nat.DISTORTION_ROWS if rows else 0) | (nat.DISTORTION_NORMALS if normals else 0), C.byref(h)))
         return Distortion(self, h)
 
-    def quant_sweep(self, mesh: Mesh) -> "QuantSweep":
-        """hry_quant_sweep_build: the error of every quantisation width of every unquantised component of `mesh`, in one pass on the
-        device; QuantSweep.choose turns tolerances into the requests for requant"""
+    def quant_sweep(self, mesh: Mesh, normals: bool = False) -> "QuantSweep":
+        """hry_quant_sweep_build(_ex): the error of every quantisation width of every unquantised component of `mesh`, in one pass on
+        the device; QuantSweep.choose turns tolerances into the requests for requant.  normals: also the faces' normal deviation at
+        every width of the positions (QuantSweep.normals, the "normal_chord" metric)"""
         h = C.c_void_p()
-        nat.check(nat.load().hry_quant_sweep_build(self.h, mesh.h, C.byref(h)))
+        if normals:
+            nat.check(nat.load().hry_quant_sweep_build_ex(self.h, mesh.h, nat.SWEEP_NORMALS, C.byref(h)))
+        else:
+            nat.check(nat.load().hry_quant_sweep_build(self.h, mesh.h, C.byref(h)))
         return QuantSweep(h)
 
     def rate_sweep(self, mesh: Mesh) -> "RateSweep":
@@ -628,6 +637,29 @@ class Codec:
         p, n = C.c_void_p(), C.c_size_t()
         nat.check(nat.load().hry_range_encode_lht(self.h, lht.ctypes.data, len(lht), C.byref(p), C.byref(n)))
         return nat.take_bytes(p, n.value)
+
+
+def chord_angle(chord: float) -> float:
+    """hry_chord_angle: the angle in radians between two unit normals whose difference has length `chord`: 2 asin(min(chord / 2, 1))"""
+    out = C.c_double()
+    nat.check(nat.load().hry_chord_angle(float(chord), C.byref(out)))
+    return out.value
+
+
+def angle_chord(radians: float) -> float:
+    """hry_angle_chord: 2 sin(radians / 2), the chord a tolerance on the angle between normals is stated in"""
+    out = C.c_double()
+    nat.check(nat.load().hry_angle_chord(float(radians), C.byref(out)))
+    return out.value
+
+
+def _normal_record(e) -> dict:
+    """hry_normal_error as a dict, plus max_angle_deg = the angle of max_chord and rms_angle_deg, DEFINED as the angle of the rms chord,
+    chord_angle(sqrt(sum_sq_chord / compared)) -- not the rms of the angles; both 0 when nothing was compared"""
+    out = {k: getattr(e, k) for k, _ in e._fields_}
+    out["max_angle_deg"] = math.degrees(chord_angle(e.max_chord)) if e.compared else 0.0
+    out["rms_angle_deg"] = math.degrees(chord_angle(math.sqrt(e.sum_sq_chord / e.compared))) if e.compared else 0.0
+    return out
 
 
 class _NamedBuffers:
@@ -772,6 +804,17 @@ class Distortion(_NamedBuffers):
                 out["psnr"] = 20.0 * math.log10(out["diagonal"] / out["rms"]) if out["diagonal"] > 0 else -math.inf
         return out
 
+    def normals(self) -> dict:
+        """hry_normal_error of a build with normals=True (Codec.distortion_ex): the chord between each face's unit normal before and after (max_chord,
+        sum_sq_chord, argmax) and the five face classes, plus max_angle_deg and rms_angle_deg -- the rms is defined as
+        chord_angle(sqrt(sum_sq_chord / compared)), the angle of the rms chord.  list -1: no normals; "reason" says why"""
+        e = nat.NormalError()
+        nat.check(nat.load().hry_distortion_normals(self.h, C.byref(e)))
+        out = _normal_record(e)
+        if e.list < 0:
+            out["reason"] = nat.load().hry_last_error().decode(errors="replace")
+        return out
+
     def rows(self, name: str) -> int:
         """rows of a per-row buffer; 0: there is no such buffer"""
         return super().rows(name)
@@ -800,7 +843,8 @@ class QuantSweep:
     Distortion.component gives after a requant of a clone to that width, and per width the positions' displacement.  A host table:
     valid until close(), whatever becomes of the codec."""
 
-    METRICS = {"max_abs": nat.TOL_MAX_ABS, "max_rel": nat.TOL_MAX_REL, "rms": nat.TOL_RMS, "pos_dist": nat.TOL_POS_DIST}
+    METRICS = {"max_abs": nat.TOL_MAX_ABS, "max_rel": nat.TOL_MAX_REL, "rms": nat.TOL_RMS, "pos_dist": nat.TOL_POS_DIST,
+               "normal_chord": nat.TOL_NORMAL_CHORD}
 
     def __init__(self, handle):
         self.h = handle
@@ -843,8 +887,19 @@ class QuantSweep:
         out["rms"] = math.sqrt(p.sum_sq_dist / p.compared) if p.compared else 0.0
         return out
 
+    def normals(self, bits: int) -> dict:
+        """hry_normal_error with the three position components at `bits` (a sweep built with normals=True; otherwise HryError, "not
+        swept"), plus max_angle_deg and rms_angle_deg as Distortion.normals defines them; list -1: not swept, "reason" says why"""
+        e = nat.NormalError()
+        nat.check(nat.load().hry_quant_sweep_normals(self.h, bits, C.byref(e)))
+        out = _normal_record(e)
+        if e.list < 0:
+            out["reason"] = nat.load().hry_last_error().decode(errors="replace")
+        return out
+
     def choose(self, tolerances) -> list:
-        """tolerances: iterable of (list, component or -1, metric, value); metric: "max_abs", "max_rel", "rms", "pos_dist" or a
+        """tolerances: iterable of (list, component or -1, metric, value); metric: "max_abs", "max_rel", "rms", "pos_dist",
+        "normal_chord" (value: angle_chord of the largest angle between a face's normals, list the position list, component -1) or a
         nat.TOL_* number.  Returns [(list, component, bits), ...] for Codec.requant: per named component the smallest width that
         meets its tolerances, 0 (lossless) when none does"""
         ts = []

@@ -1,5 +1,7 @@
 // C ABI of libharry_amd.so (include/harry_amd.h).  Thin: argument checks, exception -> status translation.
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -732,6 +734,13 @@ int hry_distortion_position(const hry_distortion *d, hry_pos_error *out)
 	return HRY_OK;
 }
 int hry_distortion_position_component(const hry_distortion *d) { return d ? d->d.pos_comp : -1; }
+int hry_distortion_normals(const hry_distortion *d, hry_normal_error *out)
+{
+	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	*out = d->d.nrm;
+	if (out->list < 0) g_last_error = d->d.nrm_why;
+	return HRY_OK;
+}
 int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows)
 {
 	if (!d || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
@@ -754,7 +763,8 @@ void hry_distortion_free(hry_distortion *d) { delete d; }
 
 // ---- the error of every quantisation width, and widths from tolerances (sweep.cpp).  With the bounds known it leaves the
 // resident mesh and the decode's buffers alone, like hry_distortion_build; without, it computes them as hry_requant does
-int hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out)
+int hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out) { return hry_quant_sweep_build_ex(ctx, m, 0, out); }
+int hry_quant_sweep_build_ex(hry_ctx *ctx, hry_mesh *m, uint32_t flags, hry_sweep **out)
 {
 	if (out) *out = nullptr;
 	if (!ctx || !m || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
@@ -762,7 +772,7 @@ int hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out)
 	for (const AttrList &L : m->m.lists) if (!L.have_bounds && L.ncomp() && !m->m.partial) { touched(ctx); touched(m); break; }
 	return guarded([&] {
 		std::unique_ptr<hry_sweep> s(new hry_sweep());
-		quant_sweep_build(ctx->cx, m->m, s->s);
+		quant_sweep_build(ctx->cx, m->m, flags, s->s);
 		*out = s.release();
 	});
 }
@@ -801,6 +811,34 @@ int hry_quant_sweep_position(const hry_sweep *s, int bits, hry_pos_error *out)
 	}
 	if (bits < 1 || (size_t)bits > s->s.pos.size()) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
 	*out = s->s.pos[bits - 1];
+	return HRY_OK;
+}
+int hry_quant_sweep_normals(const hry_sweep *s, int bits, hry_normal_error *out)
+{
+	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (!s->s.nrm_asked) { g_last_error = "the normals were not swept: the sweep was built without HRY_SWEEP_NORMALS"; return HRY_E_UNSUPPORTED; }
+	if (s->s.nrm.empty()) {
+		if (bits < 1 || bits > 30) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
+		*out = hry_normal_error{ 0, 0, 0, 0, 0, 0, 0, 0, -1 };
+		g_last_error = s->s.nrm_why;
+		return HRY_OK;
+	}
+	if (bits < 1 || (size_t)bits > s->s.nrm.size()) { g_last_error = "Invalid quantization bits"; return HRY_E_ARG; }
+	*out = s->s.nrm[bits - 1];
+	return HRY_OK;
+}
+int hry_chord_angle(double chord, double *radians)
+{
+	if (!radians) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (!(chord >= 0.0)) { g_last_error = "a chord is a number that is not negative"; return HRY_E_ARG; }
+	*radians = 2.0 * std::asin(std::min(chord / 2.0, 1.0));
+	return HRY_OK;
+}
+int hry_angle_chord(double radians, double *chord)
+{
+	if (!chord) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (!(radians >= 0.0) || radians > 3.14159265358979323846) { g_last_error = "an angle between normals lies in [0, pi]"; return HRY_E_ARG; }
+	*chord = 2.0 * std::sin(radians / 2.0);
 	return HRY_OK;
 }
 int hry_quant_sweep_stat(const hry_sweep *s, double *device_ms, uint64_t *uploaded_bytes)

@@ -23,7 +23,13 @@
 // the file is at most N bytes.  The mesh -- after the other quantisations -- is swept once, hry_rate_sweep_build; hry_rate_choose
 // picks the starting width from N minus the fixed part, which is 0 before the first encode and afterwards the real size minus the
 // estimate at the width just encoded; then real encodes step down until the file fits and up while the next width still fits:
-// "Budget: list L attr C bits Q estimated E bytes" per component and "Budget: output S of N bytes after K encodes").
+// "Budget: list L attr C bits Q estimated E bytes" per component and "Budget: output S of N bytes after K encodes"),
+// --max-normal-angle DEG (in place of -q for the position components of the preceding -l, which must be the position list; no -a: the
+// smallest width at which no face's normal turns by more than DEG degrees and no face loses its normal -- the same sweep with
+// HRY_SWEEP_NORMALS, HRY_TOL_NORMAL_CHORD; "Chosen: list L attr C bits Q max-angle A deg" per position component; same refusals and
+// -c handling as --max-error); --report then adds, after its Distortion: lines and when the mesh has positions and faces,
+// "Normals: faces F max-angle A deg rms R deg collapsed K degenerate G" (hry_distortion_build with HRY_DISTORTION_NORMALS; rms: the
+// angle of the rms chord).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -75,7 +81,8 @@ const Opt kOpts[] = {
 	{ 0, "chunk", "chunked: symbols per chunk", true }, { 0, "device", "GPU index (first one with --gpus)", true }, { 0, "gpus", "N device contexts, one worker thread each", true },
 	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false },
 	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true },
-	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true } };
+	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true },
+	{ 0, "max-normal-angle", "Position bits from the largest turn of a face normal, degrees", true } };
 
 void usage(const char *argv0)
 {
@@ -163,6 +170,13 @@ Args parse(int argc, const char **argv)
 			a.tolerance.push_back(ToleranceArg{ cur_l, cur_a, n == "max-error" ? HRY_TOL_MAX_ABS : HRY_TOL_MAX_REL, v });
 			cur_a = -1;
 		}
+		else if (n == "max-normal-angle") {
+			if (!have_l) arg_error(argv[0], "--max-normal-angle needs a preceding -l");
+			if (cur_a != -1) arg_error(argv[0], "Invalid option: --max-normal-angle names the position components itself: no -a");
+			const double v = to_double(argv[0], val);
+			if (!(v >= 0.0) || v > 180.0) arg_error(argv[0], "Invalid tolerance");
+			a.tolerance.push_back(ToleranceArg{ cur_l, -1, HRY_TOL_NORMAL_CHORD, v });
+		}
 		else if (n == "max-bytes") {
 			if (!have_l) arg_error(argv[0], "--max-bytes needs a preceding -l");
 			if (a.budget.bytes >= 0) arg_error(argv[0], "Invalid option: --max-bytes given twice");
@@ -185,7 +199,7 @@ Args parse(int argc, const char **argv)
 	}
 	for (const ToleranceArg &t : a.tolerance)
 		for (const QuantArg &q : a.quant)
-			if (t.l == q.l && (t.o == q.o || t.o == -1 || q.o == -1))
+			if (t.l == q.l && t.metric == HRY_TOL_NORMAL_CHORD ? q.o == -1 : t.l == q.l && (t.o == q.o || t.o == -1 || q.o == -1))   // (an angle against -q on a named component: when the position components are known)
 				arg_error(argv[0], "Invalid option: list " + std::to_string(t.l) + " attr " + std::to_string(t.o == -1 ? q.o : t.o) + " has both -q and a tolerance");
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
@@ -415,7 +429,7 @@ int run(const Args &args)
 	// a sharded .hry quantises shard by shard on the workers (the bounds of the whole mesh are combined from the shards'): the
 	// whole mesh never sits on one device
 	const bool quant_in_encode = sharded && type == "hry";
-	if (!args.tolerance.empty() && quant_in_encode) throw std::runtime_error("--max-error sweeps the whole mesh on one context: not with --gpus / --shards");
+	if (!args.tolerance.empty() && quant_in_encode) throw std::runtime_error("--max-error / --max-normal-angle sweep the whole mesh on one context: not with --gpus / --shards");
 	const bool budget = args.budget.bytes >= 0;
 	if (budget && quant_in_encode) throw std::runtime_error("--max-bytes sweeps and encodes the whole mesh on one context: not with --gpus / --shards");
 	if (budget && type != "hry") throw std::runtime_error("--max-bytes is a budget for a .hry output");
@@ -429,11 +443,20 @@ int run(const Args &args)
 			// it is cleared here, on its own, and every width -- chosen or explicit -- is then applied to the cleared values, so what is
 			// applied is what was swept (a direct q -> q' rescale of a quantised source truncates: up to a whole step, not the table's)
 			if (args.clearquant) { ok(hry_requant(h.cx[0], h.mesh, nullptr, 0, 1)); cleared = true; }
-			ok(hry_quant_sweep_build(h.cx[0], h.mesh, &h.sweep));
-			std::vector<hry_tolerance> tol;
+			bool angles = false;
+			for (const ToleranceArg &t : args.tolerance) angles = angles || t.metric == HRY_TOL_NORMAL_CHORD;
+			ok(hry_quant_sweep_build_ex(h.cx[0], h.mesh, angles ? HRY_SWEEP_NORMALS : 0u, &h.sweep));
+			std::vector<hry_tolerance> tol, tol_angle;
 			// a tolerance without -a names every component of its list, as -q does: one that cannot take it (quantised already, a
 			// constant integer) is an error with its reason, where the library's comp -1 would leave it out
 			for (const ToleranceArg &t : args.tolerance) {
+				if (t.metric == HRY_TOL_NORMAL_CHORD) {   // degrees -> the chord the table is in; the library names the three components
+					double chord = 0.0;
+					ok(hry_angle_chord(t.value * (3.14159265358979323846 / 180.0), &chord));
+					tol.push_back(hry_tolerance{ t.l, -1, t.metric, 0, chord });
+					tol_angle.push_back(tol.back());
+					continue;
+				}
 				const bool all = t.o == -1 && t.l >= 0 && t.l < hry_mesh_nlists(h.mesh);
 				if (!all) tol.push_back(hry_tolerance{ t.l, t.o, t.metric, 0, t.value });
 				else for (int c = 0; c < hry_list_ncomp(h.mesh, t.l); ++c) tol.push_back(hry_tolerance{ t.l, c, t.metric, 0, t.value });
@@ -441,14 +464,29 @@ int run(const Args &args)
 			size_t n = 0;
 			std::vector<hry_quant> chosen((size_t)16 * 32);
 			ok(hry_quant_choose(h.sweep, tol.data(), tol.size(), chosen.data(), chosen.size(), &n));
+			size_t n_angle = 0;   // the components an angle names: the position components
+			std::vector<hry_quant> by_angle((size_t)16 * 32);
+			if (!tol_angle.empty()) ok(hry_quant_choose(h.sweep, tol_angle.data(), tol_angle.size(), by_angle.data(), by_angle.size(), &n_angle));
 			for (size_t i = 0; i < n; ++i) {
-				hry_comp_error e{};
-				if (chosen[i].bits) ok(hry_quant_sweep_component(h.sweep, chosen[i].list, chosen[i].comp, chosen[i].bits, &e));
+				bool angle = false;
+				for (size_t k = 0; k < n_angle; ++k) angle = angle || (by_angle[k].list == chosen[i].list && by_angle[k].comp == chosen[i].comp);
 				char line[160];
-				snprintf(line, sizeof line, "Chosen: list %d attr %d bits %d max %.9g", chosen[i].list, chosen[i].comp, chosen[i].bits, e.max_abs);
+				if (angle) {
+					for (const hry_quant &x : q)
+						if (x.list == chosen[i].list && (x.comp == -1 || x.comp == chosen[i].comp))
+							throw std::runtime_error("list " + std::to_string(x.list) + " attr " + std::to_string(chosen[i].comp) + " has both -q and --max-normal-angle");
+					hry_normal_error ne{};
+					double rad = 0.0;
+					if (chosen[i].bits) { ok(hry_quant_sweep_normals(h.sweep, chosen[i].bits, &ne)); ok(hry_chord_angle(ne.max_chord, &rad)); }
+					snprintf(line, sizeof line, "Chosen: list %d attr %d bits %d max-angle %.9g deg", chosen[i].list, chosen[i].comp, chosen[i].bits, rad * (180.0 / 3.14159265358979323846));
+				} else {
+					hry_comp_error e{};
+					if (chosen[i].bits) ok(hry_quant_sweep_component(h.sweep, chosen[i].list, chosen[i].comp, chosen[i].bits, &e));
+					snprintf(line, sizeof line, "Chosen: list %d attr %d bits %d max %.9g", chosen[i].list, chosen[i].comp, chosen[i].bits, e.max_abs);
+				}
 				std::cout << line << std::endl;
-				q.push_back(chosen[i]);
 			}
+			for (size_t i = 0; i < n; ++i) q.push_back(chosen[i]);
 			hry_quant_sweep_free(h.sweep); h.sweep = nullptr;
 		}
 		ok(hry_requant(h.cx[0], h.mesh, q.data(), q.size(), args.clearquant && !cleared ? 1 : 0));   // validation and texts of main.cc:74-91 inside
@@ -456,7 +494,7 @@ int run(const Args &args)
 	Clock::time_point t2 = Clock::now();
 	if (quant_phase) std::cout << "Quantization took " << ms(t1, t2) << " ms." << std::endl;
 	if (h.before) {
-		ok(hry_distortion_build(h.cx[0], h.before, h.mesh, nullptr, 0, &h.dist));
+		ok(hry_distortion_build(h.cx[0], h.before, h.mesh, nullptr, HRY_DISTORTION_NORMALS, &h.dist));
 		for (int l = 0; l < hry_mesh_nlists(h.mesh); ++l)
 			for (int c = 0; c < hry_list_ncomp(h.mesh, l); ++c) {
 				hry_comp_error e;
@@ -466,6 +504,18 @@ int run(const Args &args)
 				         e.compared ? std::sqrt(e.sum_sq / (double)e.compared) : 0.0, (unsigned long long)e.changed);
 				std::cout << line << std::endl;
 			}
+		hry_normal_error ne{};
+		if (hry_distortion_normals(h.dist, &ne) == HRY_OK && ne.list >= 0) {   // (a mesh with positions and faces)
+			double mx = 0.0, rms = 0.0;
+			ok(hry_chord_angle(ne.max_chord, &mx));
+			if (ne.compared) ok(hry_chord_angle(std::sqrt(ne.sum_sq_chord / (double)ne.compared), &rms));
+			const double deg = 180.0 / 3.14159265358979323846;
+			char line[256];
+			snprintf(line, sizeof line, "Normals: faces %llu max-angle %.9g deg rms %.9g deg collapsed %llu degenerate %llu",
+			         (unsigned long long)(ne.compared + ne.skipped + ne.nonfinite + ne.degenerate + ne.collapsed), mx * deg, rms * deg,
+			         (unsigned long long)ne.collapsed, (unsigned long long)ne.degenerate);
+			std::cout << line << std::endl;
+		}
 		hry_distortion_free(h.dist); h.dist = nullptr;
 		hry_mesh_free(h.before); h.before = nullptr;
 		t2 = Clock::now();   // (the report is no part of the writing phase)

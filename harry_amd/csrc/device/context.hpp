@@ -264,8 +264,24 @@ struct DistortionResult : DeviceResult {             // bufs: "error<l>" with HR
 	std::vector<std::vector<hry_comp_error>> comp;   // per list; empty: the list is not compared
 	hry_pos_error pos{};
 	int pos_comp = -1;                               // the first of the three position components in list pos.list
+	hry_normal_error nrm{ 0, 0, 0, 0, 0, 0, 0, 0, -1 };   // HRY_DISTORTION_NORMALS: the faces' normal deviation; list -1: nrm_why says why not
+	std::string nrm_why = "HRY_DISTORTION_NORMALS was not set";
 	double device_ms = 0;
 	uint64_t uploaded_bytes = 0;
+};
+// the normal deviation can be taken over m's faces (normal_sweep.hip): a position list, faces, the PLY layout; why: why not
+bool normals_comparable(const Mesh &m, std::string &why);
+// m's connectivity for k_normal_sweep / k_distortion_normals: every face a triangle (no face offsets are read)
+bool all_triangles(const Mesh &m);
+// general bindings: the record of the position list pl that every vertex names, by one k_rows_of pass into a build's working buffer.
+// reserve() while sizing (tables_there: m is the resident mesh -- its binding tables are read in place where the context holds
+// them), launch() on the stream: the table's device address, nullptr in the PLY layout (row v is vertex v)
+struct VertexRows {
+	bool general = false, in_place = false;
+	std::vector<int32_t> slot;   // per vertex region: the slot that binds pl
+	size_t w_slot = 0, w_vreg = 0, w_vattr = 0, w_idx = 0;
+	void reserve(const Context &cx, const Mesh &m, int pl, bool tables_there, Carve &W);
+	const uint32_t *launch(Context &cx, const Mesh &m, int pl, const Carve &W, void *wb, uint64_t &uploaded) const;
 };
 void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out);
 bool distortion_compares(const Mesh &m, size_t l);   // list l is one hry_distortion_build compares
@@ -283,11 +299,14 @@ struct SweepResult {
 	std::vector<std::vector<Comp>> comp;   // per list and component
 	int pos_list = -1, pos_comp = -1;      // the position list and the first of its three components (-1: none)
 	std::vector<hry_pos_error> pos;        // [min of the three qmax], index bits - 1; empty: the three are not all swept
+	bool nrm_asked = false;                // built with HRY_SWEEP_NORMALS
+	std::vector<hry_normal_error> nrm;     // [pos.size()], index bits - 1; empty: nrm_why says why
+	std::string nrm_why;
 	double device_ms = 0;
 	uint64_t uploaded_bytes = 0;
 };
 int swept_widths(const Mesh &m, size_t l, int c, dev::RequantComp &rc, std::string &why);   // 1 .. the result; 0: not swept, why says why
-void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out);   // (computes bounds where unset, as device_requant does)
+void quant_sweep_build(Context &cx, Mesh &m, uint32_t flags, SweepResult &out);   // flags: HRY_SWEEP_*; (computes bounds where unset, as device_requant does)
 // host only: the smallest width whose record meets (metric, value), 0: none; and the requests that meet a set of tolerances
 int quant_pick(const hry_comp_error *by_bits, int n_bits, int metric, double extent, double value);
 std::vector<hry_quant> quant_choose(const SweepResult &s, const hry_tolerance *t, size_t nt);

@@ -60,6 +60,24 @@ __device__ __forceinline__ uint64_t load_raw(const uint8_t *slot, int type)
 	}
 }
 
+// the component's value after hry_requant(clear) -- quantised ones through dequantise_bits, the others as stored -- as a double
+// (k_distortion_rows, k_distortion_normals)
+__device__ __forceinline__ double component_f64(const uint8_t *slot, const RequantComp &c)
+{
+	uint64_t v;
+	if (c.src_bits) {
+		uint64_t q;
+		switch (c.src_type) {   // storage type of the quantised value (quant.h:121-129)
+		case 8: q = ldg<uint8_t>(slot); break;
+		case 6: q = ldg<uint16_t>(slot); break;
+		case 4: q = ldg<uint32_t>(slot); break;
+		default: q = ldg<uint64_t>(slot); break;
+		}
+		v = dequantise_bits(q, c);
+	} else v = load_raw(slot, c.dst_type);
+	return cm::value_f64(v, c.dst_type);
+}
+
 // an unquantised value (raw: load_raw of c.src_type) -> its c.dst_bits quantisation bits (quant.h:131-166), before the store
 // narrows them (stored_bits)
 __device__ __forceinline__ uint64_t quantise_raw(uint64_t raw, const RequantComp &c)
@@ -81,6 +99,18 @@ __device__ __forceinline__ uint64_t quantise_raw(uint64_t raw, const RequantComp
 }
 // what a slot keeps of q at `bits` quantisation bits: its storage type is u8 up to 8 bits, u16 up to 16, u32 above (mixing.h:101-108)
 __device__ __forceinline__ uint64_t stored_bits(uint64_t q, int bits) { return bits <= 8 ? (uint8_t)q : bits <= 16 ? (uint16_t)q : (uint32_t)q; }
+
+// what hry_requant to q bits followed by the -c dequantisation makes of the unquantised value raw, as a double (k_quant_sweep,
+// k_normal_sweep).  T: the component's type at compile time, or -1: c's
+template <int T> __device__ __forceinline__ double value_at(uint64_t raw, const RequantComp &c, int q)
+{
+	RequantComp k = c;
+	if (T >= 0) { k.src_type = T; k.dst_type = T; }
+	k.src_bits = 0; k.dst_bits = q;
+	const uint64_t stored = stored_bits(quantise_raw(raw, k), q);
+	k.src_bits = q; k.dst_bits = 0;
+	return cm::value_f64(dequantise_bits(stored, k), k.dst_type);
+}
 
 }   // namespace dev
 }   // namespace hry

@@ -158,6 +158,47 @@ struct SweepList {
 	SweepComp c[kMaxComp];
 };
 
+// normal_sweep.hip: what one block leaves per slot for the faces' normal deviation (mx = the largest chord, sum = the squared
+// chords), and what k_normal_fold makes of the blocks' records -- the layout of hry_normal_error (include/harry_amd.h)
+struct alignas(16) NormPart {
+	double mx, sum;
+	uint32_t row, compared, skipped, nonfinite, degenerate, collapsed, pad[2];
+};   // 48 bytes
+struct NormFinal {
+	double mx, sum;
+	uint64_t compared, skipped, nonfinite, degenerate, collapsed;
+	uint32_t row;
+	int32_t list;
+};   // 64 bytes
+// the faces of a mesh and where a corner's position lies: corner k names vertex org[k], whose record in the position list is row
+// rows[v] (rows == nullptr: row v; kNoRank: none).  foff == nullptr: every face is a triangle (corner c belongs to face c / 3)
+struct NormalFaces {
+	const uint32_t *org, *foff, *rows;
+	uint32_t nf, ne, nv, nrows;   // nrows: records of the position list
+};
+// k_normal_sweep: the three position components (rc as in SweepComp, consecutive in a record of `stride` bytes at rec) at every
+// width 1 .. qmax; block b's record of width q is part[b * qmax + q - 1].  type: the components' common type, -1: they differ
+struct NormalSweep {
+	NormalFaces F;
+	const uint8_t *rec;
+	NormPart *part;
+	uint32_t stride;
+	int32_t qmax, type, pad;
+	RequantComp c[3];
+};
+// k_distortion_normals: positions of a (components ca of a record at a + row * sa) against b's at row map[row] (map == nullptr: the
+// same row; an entry at or above b_rows is never followed: k_distortion_rows has raised the status word for it); err: the per-face
+// buffer, or nullptr
+struct NormalPair {
+	NormalFaces F;
+	const uint8_t *a, *b;
+	const uint32_t *map;
+	float *err;
+	NormPart *part;      // [blocks]
+	uint32_t b_rows, sa, sb, pad;
+	RequantComp ca[3], cb[3];
+};
+
 // rate.hip: one component of list 1 in a rate sweep.  rc.off / rc.src_type (the original type) / rc.mn / rc.scale as requant_plan
 // gives them; swept at 1 .. qmax bits (0: not swept); row0: the component as it stands is counted too, in its storage type stype0 at
 // quant0 bits.  The table is made of rows of kRatePlanes x 256 counters; the component's are slot .. slot + qmax + 1: two for row 0

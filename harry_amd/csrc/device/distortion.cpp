@@ -3,6 +3,8 @@
 // tests), the records of the context's resident mesh, and the numbering maps of the encode (a handle of their own).  What is not
 // goes up into the build's own working buffer (d_distortion), next to the blocks' partial records, the results and the status word:
 // neither the encoder's resident_token nor the decode's render_token is read for anything but the test, and neither is written.
+// With HRY_DISTORTION_NORMALS the faces' normal deviation is taken over a's faces as well (normal_sweep.hip): a's
+// connectivity is read in d_org / d_foff when a is the resident mesh, otherwise it goes up with the records.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,9 +36,67 @@ int position_list(const Mesh &m)
 bool distortion_compares(const Mesh &m, size_t l) { return compared(m, l); }
 int distortion_position_list(const Mesh &m) { return position_list(m); }
 
+bool normals_comparable(const Mesh &m, std::string &why)
+{
+	if (position_list(m) < 0) { why = "normals: no vertex list with three position components"; return false; }
+	if (!m.nf) { why = "normals: the mesh has no faces"; return false; }
+	if (m.face_off.size() != (size_t)m.nf + 1 || m.org.size() < m.ne()) { why = "normals: mesh without its connectivity"; return false; }
+	if (m.general) {
+		const Bindings &b = m.bind;
+		const int pl = position_list(m);
+		for (int r = 0; r < b.nregs_vtx(); ++r) {
+			bool bound = false;
+			for (int a = 0; a < b.nvtxlists(r); ++a) bound |= b.vtxlist(r, a) == pl;
+			if (!bound) { why = "normals: a vertex region that does not bind the position list"; return false; }
+		}
+		if (b.vtx_reg.size() < m.nv || b.vtx_attr.size() < (size_t)m.nv * b.nb_vtx) { why = "normals: mesh without its binding tables"; return false; }
+	}
+	return true;
+}
+void VertexRows::reserve(const Context &cx, const Mesh &m, int pl, bool tables_there, Carve &W)
+{
+	general = m.general;
+	if (!general) return;
+	const Bindings &b = m.bind;
+	slot.assign((size_t)std::max(b.nregs_vtx(), 1), -1);
+	for (int r = 0; r < b.nregs_vtx(); ++r)
+		for (int a = 0; a < b.nvtxlists(r); ++a) if (b.vtxlist(r, a) == pl) slot[r] = a;
+	in_place = tables_there && cx.gen_token != 0 && cx.gen_token == m.device_token && cx.d_vreg.cap >= (size_t)m.nv * 2 && cx.d_vattr.cap >= (size_t)m.nv * b.nb_vtx * 4;
+	w_slot = W.reserve(slot.size() * 4);
+	w_vreg = W.reserve(in_place ? 0 : (size_t)m.nv * 2);
+	w_vattr = W.reserve(in_place ? 0 : (size_t)m.nv * b.nb_vtx * 4);
+	w_idx = W.reserve((size_t)m.nv * 4);
+}
+const uint32_t *VertexRows::launch(Context &cx, const Mesh &m, int pl, const Carve &W, void *wb, uint64_t &uploaded) const
+{
+	if (!general) return nullptr;
+	const Bindings &b = m.bind;
+	hipStream_t st = cx.stream;
+	HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_slot), slot.data(), slot.size() * 4, hipMemcpyHostToDevice, st));
+	RowsView v{};
+	v.slot = W.ptr<int32_t>(wb, w_slot); v.count = m.lists[pl].count;
+	v.nowner = m.nv; v.nregs = (uint32_t)b.nregs_vtx(); v.nb = (uint32_t)b.nb_vtx; v.nelem = m.nv;
+	if (in_place) { v.reg = cx.d_vreg.as<uint16_t>(); v.attr = cx.d_vattr.as<uint32_t>(); }
+	else {
+		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_vreg), b.vtx_reg.data(), (size_t)m.nv * 2, hipMemcpyHostToDevice, st));
+		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_vattr), b.vtx_attr.data(), (size_t)m.nv * b.nb_vtx * 4, hipMemcpyHostToDevice, st));
+		uploaded += (uint64_t)m.nv * 2 + (uint64_t)m.nv * b.nb_vtx * 4;
+		v.reg = W.ptr<uint16_t>(wb, w_vreg); v.attr = W.ptr<uint32_t>(wb, w_vattr);
+	}
+	uint32_t *idx = W.ptr<uint32_t>(wb, w_idx);
+	launch_rows_of(st, v, m.nv, idx);
+	return idx;
+}
+bool all_triangles(const Mesh &m)
+{
+	bool tri = (uint64_t)m.ne() == 3ull * m.nf;
+	for (size_t d = 4; d < m.have_degree.size(); ++d) tri = tri && !m.have_degree[d];
+	return tri;
+}
+
 void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResult *o, uint32_t flags, DistortionResult &out)
 {
-	if (flags & ~(uint32_t)HRY_DISTORTION_ROWS) throw Error(HRY_E_ARG, "unknown distortion flag");
+	if (flags & ~(uint32_t)(HRY_DISTORTION_ROWS | HRY_DISTORTION_NORMALS)) throw Error(HRY_E_ARG, "unknown distortion flag");
 	const bool want_rows = (flags & HRY_DISTORTION_ROWS) != 0;
 	if (a.partial || b.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
 	if (a.lists.size() != b.lists.size()) throw Error(HRY_E_ARG, "the meshes have different numbers of lists");
@@ -74,12 +134,21 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 		if (pos_comp < 0 || pos_comp + 3 > a.lists[pl].ncomp()) throw Error(HRY_E_INTERNAL, "position components outside their list");
 	}
 
+	// ---- the faces' normal deviation (HRY_DISTORTION_NORMALS; normal_sweep.hip): a's faces, a's positions against b's at the mapped rows
+	out.nrm = hry_normal_error{ 0, 0, 0, 0, 0, 0, 0, 0, -1 };
+	bool want_normals = false;
+	if (flags & HRY_DISTORTION_NORMALS) want_normals = normals_comparable(a, out.nrm_why);
+	const uint32_t nf = a.nf, ne = a.ne();
+	const bool tri = want_normals && all_triangles(a);
+
 	HIP_OK(hipSetDevice(cx.device));
 	// ---- where the records are read: the decode's buffers (holds_decode), the resident mesh's, or uploads
 	bool b_res = holds_decode(cx, b);
 	for (size_t l = 0; l < nl && b_res; ++l) b_res = !compared(b, l) || decoded_records(cx, l).cap >= b.lists[l].data.size();
 	bool a_res = !b_res && cx.render_token == 0 && a.device_token != 0 && a.device_token == cx.resident_token;   // (d_rec holds one mesh at a time)
 	for (size_t l = 0; l < nl && a_res; ++l) a_res = !compared(a, l) || cx.d_rec[l].cap >= a.lists[l].data.size();
+	// (a's connectivity lies in d_org / d_foff when a is the resident mesh)
+	const bool conn_res = want_normals && a_res && cx.res_nf == nf && cx.res_ne == ne && cx.d_org.cap >= (size_t)ne * 4 && (tri || cx.d_foff.cap >= ((size_t)nf + 1) * 4);
 
 	Carve W;
 	size_t nslots_all = 0;
@@ -93,14 +162,20 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 		w_b[l] = W.reserve(b_res ? 0 : b.lists[l].data.size());
 		w_part[l] = W.reserve((size_t)distortion_blocks(a.lists[l].count) * nslots[l] * sizeof(DistPart));
 	}
+	const size_t w_org = W.reserve(want_normals && !conn_res ? (size_t)ne * 4 : 0), w_foff = W.reserve(want_normals && !conn_res && !tri ? ((size_t)nf + 1) * 4 : 0);
+	const size_t w_npart = W.reserve(want_normals ? (size_t)distortion_blocks(nf) * sizeof(NormPart) : 0);
+	VertexRows vrows;
+	if (want_normals) vrows.reserve(cx, a, pl, a_res, W);
 	const size_t res_bytes = nslots_all * sizeof(DistFinal);
-	const size_t w_res = W.reserve(res_bytes + 8);   // the results, then the status word: one copy brings both down
+	static_assert(sizeof(NormFinal) == sizeof(hry_normal_error) && sizeof(NormFinal) == 64, "the normals' record is an hry_normal_error");
+	const size_t w_res = W.reserve(res_bytes + 8 + (want_normals ? sizeof(NormFinal) : 0));   // the results, the status word, the normals' record: one copy brings all down
 	cx.d_distortion.ensure(W.total);
 	void *wb = cx.d_distortion.p;
 
 	Carve O;
 	std::vector<size_t> o_err(nl, 0);
 	if (want_rows) for (size_t l = 0; l < nl; ++l) if (compared(a, l)) o_err[l] = O.reserve((size_t)a.lists[l].count * 4);
+	const size_t o_nerr = O.reserve(want_rows && want_normals ? (size_t)nf * 4 : 0);
 	out.block.alloc(cx.device, std::max<size_t>(O.total, 16));   // (without HRY_DISTORTION_ROWS there is no piece)
 
 	hipStream_t st = cx.stream;
@@ -133,13 +208,34 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 		fold.part[k] = J.part; fold.nblocks[k] = distortion_blocks(A.count); fold.nslots[k] = (uint32_t)nslots[l]; fold.out_at[k] = (uint32_t)slot_at[l];
 	}
 
+	NormalPair N{};
+	if (want_normals) {
+		if (conn_res) { N.F.org = cx.d_org.as<uint32_t>(); N.F.foff = tri ? nullptr : cx.d_foff.as<uint32_t>(); }
+		else {
+			put(w_org, a.org.data(), (size_t)ne * 4);
+			N.F.org = W.ptr<uint32_t>(wb, w_org);
+			if (!tri) { put(w_foff, a.face_off.data(), ((size_t)nf + 1) * 4); N.F.foff = W.ptr<uint32_t>(wb, w_foff); }
+		}
+		const AttrList &A = a.lists[pl], &B = b.lists[pl];
+		for (size_t k = 0; k < jobs.size(); ++k) if (job_list[k] == (size_t)pl) { N.a = jobs[k].a; N.b = jobs[k].b; }
+		N.F.rows = nullptr; N.F.nf = nf; N.F.ne = ne; N.F.nv = general ? a.nv : A.count; N.F.nrows = A.count;
+		N.map = map[pl]; N.err = want_rows ? O.ptr<float>(out.block.p, o_nerr) : nullptr;
+		N.part = W.ptr<NormPart>(wb, w_npart);
+		N.b_rows = B.count; N.sa = (uint32_t)A.stride(); N.sb = (uint32_t)B.stride();
+		for (int c = 0; c < 3; ++c) { N.ca[c] = pa[pl].c[pos_comp + c]; N.cb[c] = pb[pl].c[pos_comp + c]; }
+	}
 	TimedEvent ev[2];
 	HIP_OK(hipEventRecord(ev[0], st));
 	for (size_t k = 0; k < jobs.size(); ++k) launch_distortion_rows(st, jobs[k], pa[job_list[k]], pb[job_list[k]], d_status);
 	launch_distortion_fold(st, fold, (DistFinal*)d_res);
+	if (want_normals) {
+		N.F.rows = vrows.launch(cx, a, pl, W, wb, up);
+		launch_distortion_normals(st, N);
+		launch_normal_fold(st, N.part, distortion_blocks(nf), 1, (NormFinal*)(d_res + res_bytes + 8));
+	}
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(ev[1], st));
-	std::vector<uint8_t> res(res_bytes + 8);
+	std::vector<uint8_t> res(res_bytes + 8 + (want_normals ? sizeof(NormFinal) : 0));
 	HIP_OK(hipMemcpyAsync(res.data(), d_res, res.size(), hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
 	uint32_t status = 0;
@@ -171,6 +267,12 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 			out.pos.max_dist = f.mx; out.pos.sum_sq_dist = f.sum; out.pos.compared = f.compared; out.pos.argmax = f.row; out.pos.list = pl;
 		}
 		if (want_rows) out.bufs.push_back(NamedBuf{ "error" + std::to_string(l), O.ptr<void>(out.block.p, o_err[l]), a.lists[l].count, 1, HRY_FLOAT });
+	}
+	if (want_normals) {
+		memcpy(&out.nrm, res.data() + res_bytes + 8, sizeof out.nrm);
+		out.nrm.list = pl;
+		out.nrm_why.clear();
+		if (want_rows) out.bufs.push_back(NamedBuf{ "normal_error", O.ptr<void>(out.block.p, o_nerr), nf, 1, HRY_FLOAT });
 	}
 	out.device_ms = (double)ms;
 	out.uploaded_bytes = up;

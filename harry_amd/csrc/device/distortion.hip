@@ -30,24 +30,6 @@ constexpr uint32_t kNone = kDistNone;
 constexpr int kLanes = 256, kWaves = kLanes / 64, kRowsPerLane = (int)(kDistBlockRows / kLanes);
 static_assert(kRowsPerLane * kLanes == (int)kDistBlockRows, "a block's rows are a multiple of its lanes");
 
-// the component's value after hry_requant(clear) -- quantised ones through dequantise_bits, the others as stored -- as a double
-// (value_f64, dist_reduce.hpp)
-__device__ __forceinline__ double component_f64(const uint8_t *slot, const RequantComp &c)
-{
-	uint64_t v;
-	if (c.src_bits) {
-		uint64_t q;
-		switch (c.src_type) {   // storage type of the quantised value (quant.h:121-129)
-		case 8: q = ldg<uint8_t>(slot); break;
-		case 6: q = ldg<uint16_t>(slot); break;
-		case 4: q = ldg<uint32_t>(slot); break;
-		default: q = ldg<uint64_t>(slot); break;
-		}
-		v = dequantise_bits(q, c);
-	} else v = load_raw(slot, c.dst_type);
-	return value_f64(v, c.dst_type);
-}
-
 }   // namespace
 
 __global__ __launch_bounds__(256) void k_distortion_rows(DistList L, RequantPlan pa, RequantPlan pb, uint32_t *status)

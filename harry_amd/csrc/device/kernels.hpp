@@ -223,6 +223,15 @@ constexpr int kSweepGroup = 2, kSweepMaxBits = 30;
 void launch_quant_sweep(hipStream_t st, const SweepList &L);
 void launch_quant_sweep_fold(hipStream_t st, const DistFold &f, DistFinal *out);
 
+// the faces' normal deviation (normal_sweep.hip; drivers: sweep.cpp, distortion.cpp).  launch_normal_sweep: blocks of
+// kDistBlockRows faces x groups of kNormalGroup widths leave one NormPart per block and width in S.part; launch_distortion_normals:
+// one NormPart per block in P.part; launch_normal_fold: one block per slot, the blocks' records in block order, into out[slot].
+// kNormalGroup is a measured choice
+constexpr int kNormalGroup = 2;
+void launch_normal_sweep(hipStream_t st, const NormalSweep &S);
+void launch_distortion_normals(hipStream_t st, const NormalPair &P);
+void launch_normal_fold(hipStream_t st, const NormPart *part, uint32_t nblocks, uint32_t nslots, NormFinal *out);
+
 // the byte-plane histograms of the residual codes of list 1's components at every quantisation width (rate.hip; driver: rate.cpp):
 // blocks of kRateBlock coded vertices x groups of table rows (row = width, 0: as it stands); L.table is zeroed before
 constexpr int kRateBlock = 256;

@@ -3,6 +3,8 @@
 // the records of the context's resident mesh are read in place, anything else goes up into the build's own working buffer
 // (d_sweep), next to the blocks' partial records and the results: neither resident_token nor render_token is read for anything but
 // the test, and neither is written -- unless the mesh has no bounds yet: then they are computed as hry_requant computes them.
+// With HRY_SWEEP_NORMALS the faces' normal deviation at every width of the positions rides along (normal_sweep.hip):
+// the connectivity is read in d_org / d_foff of the resident mesh or goes up too, and its records come down behind the table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -52,8 +54,10 @@ int swept_widths(const Mesh &m, size_t l, int c, dev::RequantComp &rc, std::stri
 	return std::min(kSweepMaxBits, 8 * (int)kTypeSize[L.type[c]]);
 }
 
-void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
+void quant_sweep_build(Context &cx, Mesh &m, uint32_t flags, SweepResult &out)
 {
+	if (flags & ~(uint32_t)HRY_SWEEP_NORMALS) throw Error(HRY_E_ARG, "unknown sweep flag");
+	const bool want_normals = (flags & HRY_SWEEP_NORMALS) != 0;
 	if (m.partial) throw Error(HRY_E_ARG, "partially decoded mesh (a share of a sharded container): only its runs are real");
 	if (m.lists.size() > (size_t)kMaxLists) throw Error(HRY_E_UNSUPPORTED, "more than 16 attribute lists");
 	const size_t nl = m.lists.size();
@@ -106,10 +110,20 @@ void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 		}
 		out.pos_list = pl; out.pos_comp = pc;
 	}
+	// ---- the faces' normal deviation at every width of the positions (HRY_SWEEP_NORMALS; normal_sweep.hip)
+	out.nrm_asked = want_normals; out.nrm.clear(); out.nrm_why.clear();
+	int nrm_qmax = 0;
+	if (want_normals) {
+		if (pl < 0 || jobs[pl].pos < 0) out.nrm_why = "the positions were not swept: their three components are not all swept";
+		else if (normals_comparable(m, out.nrm_why)) nrm_qmax = jobs[pl].pos_qmax;
+	}
+	const uint32_t nf = m.nf, ne = m.ne();
+	const bool tri = nrm_qmax && all_triangles(m);
 
 	// ---- where the records are read: the resident mesh's, or uploads (d_rec holds one mesh at a time)
 	bool res = cx.render_token == 0 && m.device_token != 0 && m.device_token == cx.resident_token;
 	for (size_t l = 0; l < nl && res; ++l) res = !jobs[l].ns || cx.d_rec[l].cap >= m.lists[l].data.size();
+	if (nrm_qmax && res) res = cx.res_nf == nf && cx.res_ne == ne && cx.d_org.cap >= (size_t)ne * 4 && (tri || cx.d_foff.cap >= ((size_t)nf + 1) * 4);
 	Carve W;
 	size_t ns_all = 0;
 	std::vector<size_t> w_rec(nl), w_part(nl), slot_at(nl, 0);
@@ -122,7 +136,12 @@ void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 	}
 	out.device_ms = 0; out.uploaded_bytes = 0;
 	if (!ns_all) return;
-	const size_t res_bytes = ns_all * sizeof(DistFinal);
+	const size_t w_org = W.reserve(nrm_qmax && !res ? (size_t)ne * 4 : 0), w_foff = W.reserve(nrm_qmax && !res && !tri ? ((size_t)nf + 1) * 4 : 0);
+	const size_t w_npart = W.reserve(nrm_qmax ? (size_t)distortion_blocks(nf) * nrm_qmax * sizeof(NormPart) : 0);
+	VertexRows vrows;
+	if (nrm_qmax) vrows.reserve(cx, m, pl, res, W);
+	static_assert(sizeof(DistFinal) % 8 == 0 && sizeof(NormFinal) == sizeof(hry_normal_error) && sizeof(NormFinal) == 64, "the normals' records follow the table");
+	const size_t dist_bytes = ns_all * sizeof(DistFinal), res_bytes = dist_bytes + (size_t)nrm_qmax * sizeof(NormFinal);   // one copy brings both down
 	const size_t w_res = W.reserve(res_bytes);
 	cx.d_sweep.ensure(W.total);
 	void *wb = cx.d_sweep.p;
@@ -145,10 +164,34 @@ void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 		const int k = fold.n++;
 		fold.part[k] = J.part; fold.nblocks[k] = distortion_blocks(L.count); fold.nslots[k] = J.ns; fold.out_at[k] = (uint32_t)slot_at[l];
 	}
+	NormalSweep N{};
+	if (nrm_qmax) {
+		const SweepList &J = jobs[pl];
+		if (res) { N.F.org = cx.d_org.as<uint32_t>(); N.F.foff = tri ? nullptr : cx.d_foff.as<uint32_t>(); }
+		else {
+			HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_org), m.org.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
+			up += (size_t)ne * 4;
+			N.F.org = W.ptr<uint32_t>(wb, w_org);
+			if (!tri) {
+				HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_foff), m.face_off.data(), ((size_t)nf + 1) * 4, hipMemcpyHostToDevice, st));
+				up += ((size_t)nf + 1) * 4;
+				N.F.foff = W.ptr<uint32_t>(wb, w_foff);
+			}
+		}
+		N.F.rows = nullptr; N.F.nf = nf; N.F.ne = ne; N.F.nv = m.general ? m.nv : J.rows; N.F.nrows = J.rows;
+		N.rec = J.rec; N.part = W.ptr<NormPart>(wb, w_npart); N.stride = J.stride; N.qmax = nrm_qmax;
+		for (int a = 0; a < 3; ++a) N.c[a] = J.c[J.pos + a].rc;
+		N.type = N.c[0].dst_type == N.c[1].dst_type && N.c[1].dst_type == N.c[2].dst_type ? N.c[0].dst_type : -1;
+	}
 	TimedEvent ev[2];
 	HIP_OK(hipEventRecord(ev[0], st));
 	for (size_t l = 0; l < nl; ++l) if (jobs[l].ns) launch_quant_sweep(st, jobs[l]);
 	launch_quant_sweep_fold(st, fold, W.ptr<DistFinal>(wb, w_res));
+	if (nrm_qmax) {
+		N.F.rows = vrows.launch(cx, m, pl, W, wb, up);
+		launch_normal_sweep(st, N);
+		launch_normal_fold(st, N.part, distortion_blocks(nf), (uint32_t)nrm_qmax, (NormFinal*)(W.ptr<uint8_t>(wb, w_res) + dist_bytes));
+	}
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(ev[1], st));
 	std::vector<uint8_t> tab(res_bytes);
@@ -181,6 +224,11 @@ void quant_sweep_build(Context &cx, Mesh &m, SweepResult &out)
 			}
 		}
 	}
+	if (nrm_qmax) {
+		out.nrm.resize(nrm_qmax);
+		memcpy(out.nrm.data(), tab.data() + dist_bytes, (size_t)nrm_qmax * sizeof(hry_normal_error));
+		for (hry_normal_error &e : out.nrm) e.list = pl;
+	}
 	out.device_ms = (double)ms;
 	out.uploaded_bytes = up;
 }
@@ -205,13 +253,21 @@ std::vector<hry_quant> quant_choose(const SweepResult &s, const hry_tolerance *t
 	for (size_t i = 0; i < nt; ++i) {
 		const hry_tolerance &T = t[i];
 		check_tolerance_value(T.value);
-		if (T.metric < HRY_TOL_MAX_ABS || T.metric > HRY_TOL_POS_DIST) throw Error(HRY_E_ARG, "unknown tolerance metric");
+		if (T.metric < HRY_TOL_MAX_ABS || T.metric > HRY_TOL_NORMAL_CHORD) throw Error(HRY_E_ARG, "unknown tolerance metric");
 		if (T.list < 0 || (size_t)T.list >= s.comp.size()) throw Error(HRY_E_ARG, "Invalid list index");
 		const std::vector<SweepResult::Comp> &C = s.comp[T.list];
 		if (T.metric == HRY_TOL_POS_DIST) {
 			if (T.comp != -1) throw Error(HRY_E_ARG, "HRY_TOL_POS_DIST names the position list with comp -1");
 			if (T.list != s.pos_list) throw Error(HRY_E_ARG, "list " + std::to_string(T.list) + " is not the position list");
 			if (s.pos.empty()) throw Error(HRY_E_UNSUPPORTED, "the positions were not swept: their three components are not all swept");
+			for (int a = 0; a < 3; ++a) want(T.list, s.pos_comp + a, &T);
+			continue;
+		}
+		if (T.metric == HRY_TOL_NORMAL_CHORD) {
+			if (T.comp != -1) throw Error(HRY_E_ARG, "HRY_TOL_NORMAL_CHORD names the position list with comp -1");
+			if (T.list != s.pos_list) throw Error(HRY_E_ARG, "list " + std::to_string(T.list) + " is not the position list");
+			if (!s.nrm_asked) throw Error(HRY_E_UNSUPPORTED, "the normals were not swept: the sweep was built without HRY_SWEEP_NORMALS");
+			if (s.nrm.empty()) throw Error(HRY_E_UNSUPPORTED, "the normals were not swept: " + s.nrm_why);
 			for (int a = 0; a < 3; ++a) want(T.list, s.pos_comp + a, &T);
 			continue;
 		}
@@ -231,7 +287,8 @@ std::vector<hry_quant> quant_choose(const SweepResult &s, const hry_tolerance *t
 			bool ok = true;
 			for (const hry_tolerance *T : w.tol)
 				ok = ok && (T->metric == HRY_TOL_POS_DIST ? q <= (int)s.pos.size() && s.pos[q - 1].max_dist <= T->value
-				                                           : meets(C.by_bits[q - 1], T->metric, C.extent, T->value));
+				            : T->metric == HRY_TOL_NORMAL_CHORD ? q <= (int)s.nrm.size() && s.nrm[q - 1].max_chord <= T->value && s.nrm[q - 1].collapsed == 0
+				                                                : meets(C.by_bits[q - 1], T->metric, C.extent, T->value));
 			if (ok) bits = q;
 		}
 		if (!bits && C.type == C_DOUBLE)

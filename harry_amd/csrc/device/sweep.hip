@@ -30,18 +30,6 @@ namespace {
 constexpr int kLanes = 256, kWaves = kLanes / 64, kRowsPerLane = (int)(kDistBlockRows / kLanes);
 static_assert(kRowsPerLane * kLanes == (int)kDistBlockRows, "a block's rows are a multiple of its lanes");
 
-// what hry_requant to q bits followed by the -c dequantisation makes of the unquantised value raw, as a double.  T: the
-// component's type at compile time, or -1: c's
-template <int T> __device__ __forceinline__ double value_at(uint64_t raw, const RequantComp &c, int q)
-{
-	RequantComp k = c;
-	if (T >= 0) { k.src_type = T; k.dst_type = T; }
-	k.src_bits = 0; k.dst_bits = q;
-	const uint64_t stored = stored_bits(quantise_raw(raw, k), q);
-	k.src_bits = q; k.dst_bits = 0;
-	return value_f64(dequantise_bits(stored, k), k.dst_type);
-}
-
 template <int T> __device__ __forceinline__ void sweep_component(const SweepList &L, const SweepComp &sc, int q0, DistPart (&p)[kSweepGroup])
 {
 	const uint64_t base = (uint64_t)blockIdx.x * kDistBlockRows;

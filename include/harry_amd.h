@@ -20,6 +20,7 @@
  *   hry_distortion_build (no counterpart: the per-component error of a decode against its source, reduced on the device)
  *   hry_quant_sweep_build (no counterpart: that error at every quantisation width in one pass, and the width a tolerance needs)
  *   hry_rate_sweep_build (no counterpart: the coded size of the vertex attributes at every width in one pass, and the width a byte budget buys)
+ *   hry_quant_sweep_build_ex / hry_distortion_normals (no counterpart: the angle a quantisation tilts each face's normal by, after the fact and at every width)
  *
  * Plain pointers and sizes only; no C++/torch types.  All functions return HRY_OK (0) or a negative error
  * code; hry_last_error() returns the message of the calling thread's last failure (the reference throws
@@ -466,6 +467,63 @@ int  hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name
 int  hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes);
 void hry_distortion_free(hry_distortion *d);
 
+/* ---- the shading error of a quantisation: the normal deviation per face -------------------------------
+ * Quantised positions tilt small faces long before the displacement of a vertex is visible, and at low widths faces collapse to a
+ * line or a point.  One quantity, reported after the fact by hry_distortion_build (HRY_DISTORTION_NORMALS) and before the fact, at
+ * every width, by hry_quant_sweep_build_ex (HRY_SWEEP_NORMALS):
+ *   Positions: P[v] = the first three POS components of the position list (hry_distortion_build's: list 1 in the PLY layout, the
+ *     lowest-numbered vertex-target list with three POS components with general bindings), each taken as hry_distortion_build takes
+ *     a value: what hry_requant(clear = 1) leaves in the original type, widened to double.
+ *   Row of vertex v in the position list: v in the PLY layout; with general bindings the record v's region binds (one k_rows_of pass,
+ *     as in hry_render_build) -- every vertex region must bind the list, otherwise the normals part is absent with
+ *     hry_render_build_ex's reason, "normals: a vertex region that does not bind the position list".
+ *   Face normal: face f has corners c_0 .. c_(d-1); N_f, a x b and |a| are those of hry_render_build_ex's normals contract: N_f = the
+ *     sum over k = 1 .. d-2 of (P[c_k] - P[c_0]) x (P[c_(k+1)] - P[c_0]) in that order, a x b = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ *     a.x*b.y - a.y*b.x), |a| = sqrt(a.x*a.x + a.y*a.y + a.z*a.z), every operation an individually rounded IEEE double operation in
+ *     the written order; n = N / |N|, one division per component.
+ *   Chord: N_x from the source's positions, N_y from the other side's; d = n_y - n_x per component, c2 = (d.x*d.x + d.y*d.y) + d.z*d.z,
+ *     chord = sqrt(c2) = 2 sin(theta / 2) for the angle theta between the normals.  The chord, not the angle, is the device's
+ *     quantity: it needs only + - * / sqrt (the same bits anywhere) and is monotone in the angle on [0, pi].
+ *   Classes: every face falls in exactly one, tested in this order -- skipped: a corner's row maps to HRY_NO_ELEMENT (or lies outside
+ *     the tables: nothing is read there); nonfinite: a corner position component is NaN or infinite on either side; degenerate: |N_x|
+ *     is 0 or not finite (the source face has no normal); collapsed: |N_y| is 0 or not finite (the quantisation took the normal
+ *     away); compared: everything else.  The five counters sum to the face count.
+ *   max_chord, argmax and the counters are exact.  sum_sq_chord adds the individually rounded c2 in a tree fixed by the face count
+ *     alone, without floating-point atomics: the same bits from run to run, resident or uploaded.
+ * hry_chord_angle / hry_angle_chord, host only: 2 * asin(min(chord / 2, 1)) radians, and 2 * sin(radians / 2).  A negative or NaN
+ *   argument, an angle above pi: HRY_E_ARG. */
+typedef struct hry_normal_error {
+    double   max_chord;    /* largest chord over the compared faces; 0 when there is none */
+    double   sum_sq_chord; /* sum of c2 over the compared faces */
+    uint64_t compared, skipped, nonfinite, degenerate, collapsed;
+    uint32_t argmax;       /* lowest face attaining max_chord; HRY_NO_ELEMENT when compared == 0 */
+    int32_t  list;         /* the position list; -1 (everything else 0): no normals, hry_last_error says why */
+} hry_normal_error;        /* 64 bytes */
+int  hry_chord_angle(double chord, double *radians);
+int  hry_angle_chord(double radians, double *chord);
+/* hry_distortion_build with HRY_DISTORTION_NORMALS: face f of a is taken twice, N_x from a's positions, N_y from b's at the mapped
+ *   rows -- the "vertex" / "list<l>" map the build checks into its status word anyway.  Only a's connectivity is read, so b's
+ *   numbering of faces never matters.  With HRY_DISTORTION_ROWS too the handle carries "normal_error", f32 [faces]: (float) chord of a
+ *   compared face, 0 elsewhere.  a's connectivity is read in place when a is ctx's resident mesh, otherwise it goes up and counts in
+ *   uploaded_bytes; an all-triangle mesh reads no face offsets.
+ *   Refusals: a mesh without a position list of three POS components, without faces, or with a vertex region that does not bind
+ *   the list gives list -1 with the reason -- it never fails a build that would have succeeded without the flag.
+ * hry_distortion_normals: the record; list -1 also when the flag was not set. */
+#define HRY_DISTORTION_NORMALS 4u   /* also the normal deviation per face (hry_distortion_normals) */
+int  hry_distortion_normals(const hry_distortion *d, hry_normal_error *out);
+/* hry_quant_sweep_build_ex with HRY_SWEEP_NORMALS: where the positions are swept (hry_quant_sweep_position has rows 1 .. pos_qmax),
+ *   one record per width: field for field what hry_distortion_normals gives for q = hry_mesh_clone(m), hry_requant(ctx, q, {the three
+ *   position components at bits}, 3, 0), hry_distortion_build(ctx, m, q, NULL, HRY_DISTORTION_NORMALS) -- up to the association of
+ *   sum_sq_chord.  Residency follows the sweep's: the resident mesh's records and connectivity are read in place, otherwise they go
+ *   up into the build's working buffer.  Flags 0 is hry_quant_sweep_build, launch for launch; unknown bits: HRY_E_ARG.
+ * hry_quant_sweep_normals: the record at `bits` (outside 1 .. pos_qmax: HRY_E_ARG).  A sweep built without the flag:
+ *   HRY_E_UNSUPPORTED, "the normals were not swept".  Built with it where the normals could not be swept (positions not all swept, no
+ *   faces, a vertex region that does not bind the position list): HRY_OK, list -1, hry_last_error says why.
+ * HRY_TOL_NORMAL_CHORD in hry_quant_choose: comp must be -1 and list the position list, like HRY_TOL_POS_DIST; one width for the three
+ *   position components, met at `bits` when max_chord <= value AND collapsed == 0 at that width (a face that lost its normal has no
+ *   angle to be within).  A sweep built without the flag, or whose normals were not swept: HRY_E_UNSUPPORTED. */
+#define HRY_SWEEP_NORMALS 1u       /* (hry_quant_sweep_build_ex and hry_quant_sweep_normals: declared with the sweep, below) */
+
 /* ---- a quantisation from a tolerance: the error at every bit width in one pass, on the device --------------------------
  * hry_quant_sweep_build reads every unquantised component of m once and, in registers, takes each value through hry_requant's
  * quantiser and the -c dequantiser at every width it can have: a table of hry_comp_error records per (list, component, bits).
@@ -510,12 +568,15 @@ void hry_distortion_free(hry_distortion *d);
  *   (metric, value), 0: none does; HRY_TOL_POS_DIST, a negative or NaN value, n_bits < 0: HRY_E_ARG. */
 typedef struct hry_sweep hry_sweep;
 int  hry_quant_sweep_build(hry_ctx *ctx, hry_mesh *m, hry_sweep **out);
+int  hry_quant_sweep_build_ex(hry_ctx *ctx, hry_mesh *m, uint32_t flags /* HRY_SWEEP_* */, hry_sweep **out);
+int  hry_quant_sweep_normals(const hry_sweep *s, int bits, hry_normal_error *out);
 int  hry_quant_sweep_bits(const hry_sweep *s, int l, int c);
 int  hry_quant_sweep_component(const hry_sweep *s, int l, int c, int bits, hry_comp_error *out);
 int  hry_quant_sweep_position(const hry_sweep *s, int bits, hry_pos_error *out);
 int  hry_quant_sweep_stat(const hry_sweep *s, double *device_ms, uint64_t *uploaded_bytes);
 void hry_quant_sweep_free(hry_sweep *s);
 enum { HRY_TOL_MAX_ABS = 0, HRY_TOL_MAX_REL = 1, HRY_TOL_RMS = 2, HRY_TOL_POS_DIST = 3 };
+enum { HRY_TOL_NORMAL_CHORD = 4 };   /* hry_quant_choose on a sweep with HRY_SWEEP_NORMALS (section 7h, above) */
 typedef struct hry_tolerance {
     int32_t list;
     int32_t comp;          /* -1: every swept component of the list */
