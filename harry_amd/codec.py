@@ -432,6 +432,67 @@ class Codec:
             return t
         return self._render(mesh, fill, self._render_flags(normals, face_normals))
 
+    # ---- edges and adjacency of a render build (include/harry_amd.h: hry_edges_build)
+    EDGES_FIXED = ("edges", "tri_edges", "edge_offsets", "edge_sides", "tri_neighbours")
+    EDGES_GEOMETRY = ("edge_length", "edge_cot", "edge_cos")
+
+    def _edges(self, mesh: Mesh, fill, geometry: bool) -> dict:
+        """render build, edges build from it, free the render, hand every buffer to fill(name, rows, width, type, handle), free the handle"""
+        L = nat.load()
+        r, e = C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_edges_build(self.h, mesh.h, r, nat.EDGES_GEOMETRY if geometry else 0, C.byref(e)))
+        finally:
+            L.hry_render_free(r)
+        try:
+            out = {}
+            for name in self.EDGES_FIXED + (self.EDGES_GEOMETRY if geometry else ()):
+                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                nat.check(L.hry_edges_get(e, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                if width.value:
+                    out[name] = fill(name, rows.value, width.value, typ.value, e)
+            d, up, s = C.c_double(), C.c_uint64(), (C.c_uint64 * 4)()
+            nat.check(L.hry_edges_stat(e, C.byref(d), C.byref(up)))
+            nat.check(L.hry_edges_summary(e, s))
+            self._edges_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges": int(s[0]), "boundary": int(s[1]), "manifold": int(s[2]),
+                                "nonmanifold": int(s[3])}
+            return out
+        finally:
+            L.hry_edges_free(e)
+
+    def edges_numpy(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """unique edges and adjacency of the mesh's render build (hry_edges_build), copied to host arrays: edges u32 [E, 2], tri_edges
+        u32 [T, 3], edge_offsets u32 [E + 1], edge_sides u32 [3 T], tri_neighbours u32 [T, 3] (NO_ELEMENT: none); geometry: also
+        edge_length, edge_cot, edge_cos f32 [E] (edge_cos 2.0: the edge does not join two triangles with normals)"""
+        def fill(name, rows, width, typ, e):
+            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
+            if rows:
+                nat.check(nat.load().hry_edges_copy(self.h, e, name.encode(), a.ctypes.data, 0))
+            return a
+        return self._edges(mesh, fill, geometry)
+
+    def edges(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: int32 (NO_ELEMENT reads -1) and float32"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+        dtypes = {0: torch.float32, 4: torch.int32}
+        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:   # (every u32 value but NO_ELEMENT is below one of them)
+            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+
+        def fill(name, rows, width, typ, e):
+            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
+            if rows:
+                nat.check(nat.load().hry_edges_copy(self.h, e, name.encode(), t.data_ptr(), 1))
+            return t
+        return self._edges(mesh, fill, geometry)
+
+    def edges_stat(self) -> dict:
+        """of the last edges / edges_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_edges_summary's counts: edges (E),
+        boundary (one side), manifold (two), nonmanifold (more)"""
+        return dict(getattr(self, "_edges_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the
@@ -637,6 +698,20 @@ class Codec:
         p, n = C.c_void_p(), C.c_size_t()
         nat.check(nat.load().hry_range_encode_lht(self.h, lht.ctypes.data, len(lht), C.byref(p), C.byref(n)))
         return nat.take_bytes(p, n.value)
+
+
+def laplacian(edges, weights, n: int):
+    """the symmetric n x n torch.sparse_coo_tensor L of an edge list: L[a, b] = L[b, a] = -w for every edge (a, b) with weight w, and
+    on the diagonal the row sums of the weights, so that every row of L sums to 0 (edges / edge_cot of Codec.edges: the cotangent
+    Laplacian; weights of ones: the graph Laplacian).  Self-edges (a == b) contribute nothing.  Plain torch, coalesced"""
+    import torch
+    e = edges.to(torch.int64)
+    a, b = e[:, 0], e[:, 1]
+    w = weights.to(torch.float32)
+    w = torch.where(a == b, torch.zeros_like(w), w)
+    rows = torch.cat([a, b, a, b])
+    cols = torch.cat([b, a, a, b])
+    return torch.sparse_coo_tensor(torch.stack([rows, cols]), torch.cat([-w, -w, w, w]), (n, n)).coalesce()
 
 
 def chord_angle(chord: float) -> float:

@@ -15,6 +15,7 @@ struct hry_mesh { Mesh m; };
 struct hry_plan { ShardPlan p; };
 struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
+struct hry_edges { EdgesResult e; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -670,6 +671,47 @@ int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_b
 	return HRY_OK;
 }
 void hry_render_free(hry_render *r) { delete r; }
+
+// ---- unique edges and adjacency of a render build (edges.cpp).  Like hry_render_build it leaves the decode's token alone
+int hry_edges_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_edges **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !r || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	order_lost(ctx);
+	return guarded([&] {
+		std::unique_ptr<hry_edges> e(new hry_edges());
+		edges_build(ctx->cx, m->m, r->r, flags, e->e);
+		*out = e.release();
+	});
+}
+uint64_t hry_edges_count(const hry_edges *e) { return e ? e->e.summary[0] : 0; }
+int hry_edges_get(const hry_edges *e, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
+{
+	if (!e || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const NamedBuf *b = result_get(e->e, name, dev, rows, false);
+	if (width) *width = b ? b->width : 0;
+	if (type) *type = b ? b->type : 0;
+	return HRY_OK;
+}
+int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !e || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { result_copy(ctx->cx, e->e, name, "edge buffer", dst, dst_is_device != 0, true); });
+}
+int hry_edges_summary(const hry_edges *e, uint64_t out[4])
+{
+	if (!e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	for (int i = 0; i < 4; ++i) out[i] = e->e.summary[i];
+	return HRY_OK;
+}
+int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!e) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = e->e.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = e->e.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_edges_free(hry_edges *e) { delete e; }
 
 // ---- numbering maps of an encode (order.cpp)
 int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)

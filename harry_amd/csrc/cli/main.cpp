@@ -29,7 +29,10 @@
 // HRY_SWEEP_NORMALS, HRY_TOL_NORMAL_CHORD; "Chosen: list L attr C bits Q max-angle A deg" per position component; same refusals and
 // -c handling as --max-error); --report then adds, after its Distortion: lines and when the mesh has positions and faces,
 // "Normals: faces F max-angle A deg rms R deg collapsed K degenerate G" (hry_distortion_build with HRY_DISTORTION_NORMALS; rms: the
-// angle of the rms chord).
+// angle of the rms chord); --topology (with or without OUTPUT: after the quantisation phase one line, "Topology: vertices V faces F
+// triangles T edges E boundary B manifold M nonmanifold N euler X" -- hry_render_build, hry_edges_build and hry_edges_summary: E the
+// unique edges of the fan triangles over the decoded vertices, B / M / N those with one, two and more sides, X = V - E + F, which is
+// the Euler characteristic for all-triangle meshes; without OUTPUT the run ends there).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -69,7 +72,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -82,7 +85,8 @@ const Opt kOpts[] = {
 	{ 0, "shards", "chunked: code as N shards (default: one per context)", true }, { 0, "report", "Print the error of the quantization per component", false },
 	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true },
 	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true },
-	{ 0, "max-normal-angle", "Position bits from the largest turn of a face normal, degrees", true } };
+	{ 0, "max-normal-angle", "Position bits from the largest turn of a face normal, degrees", true },
+	{ 0, "topology", "Print edge counts and V - E + F (OUTPUT may be left out)", false } };
 
 void usage(const char *argv0)
 {
@@ -163,6 +167,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "shards") a.shards = to_int(argv[0], val);
 		else if (n == "gpus") a.gpus = to_int(argv[0], val);
 		else if (n == "report") a.report = true;
+		else if (n == "topology") a.topology = true;
 		else if (n == "max-error" || n == "max-error-rel") {
 			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
 			const double v = to_double(argv[0], val);
@@ -204,9 +209,11 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < 2) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
-	a.in = pos[0]; a.out = pos[1];
+	a.in = pos[0];
+	if (pos.size() > 1) a.out = pos[1];
+	else if (a.budget.bytes >= 0) arg_error(argv[0], "--max-bytes is a budget for an OUTPUT");
 	return a;
 }
 
@@ -278,6 +285,8 @@ struct Handles {   // released on every path
 	std::vector<hry_ctx*> cx;   // [0]: the context of every single-device step
 	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
 	hry_distortion *dist = nullptr;
+	hry_render *render = nullptr;   // --topology
+	hry_edges *edges = nullptr;
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -285,6 +294,8 @@ struct Handles {   // released on every path
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
+		if (edges) hry_edges_free(edges);
+		if (render) hry_render_free(render);
 		if (dist) hry_distortion_free(dist);
 		if (sweep) hry_quant_sweep_free(sweep);
 		if (rate) hry_rate_sweep_free(rate);
@@ -519,6 +530,23 @@ int run(const Args &args)
 		hry_distortion_free(h.dist); h.dist = nullptr;
 		hry_mesh_free(h.before); h.before = nullptr;
 		t2 = Clock::now();   // (the report is no part of the writing phase)
+	}
+
+	if (args.topology) {
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		uint64_t s[4];
+		ok(hry_edges_summary(h.edges, s));
+		const long long V = hry_mesh_nv(h.mesh), F = hry_mesh_nf(h.mesh);
+		std::cout << "Topology: vertices " << V << " faces " << F << " triangles " << hry_mesh_ntri(h.mesh) << " edges " << s[0] << " boundary " << s[1] << " manifold " << s[2]
+		          << " nonmanifold " << s[3] << " euler " << V - (long long)s[0] + F << std::endl;
+		hry_edges_free(h.edges); h.edges = nullptr;
+		hry_render_free(h.render); h.render = nullptr;
+		t2 = Clock::now();   // (no part of the writing phase)
+		if (args.out.empty()) {
+			if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
+			return EXIT_SUCCESS;
+		}
 	}
 
 	std::cout << "Writing output..." << std::endl;

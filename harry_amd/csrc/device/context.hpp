@@ -102,6 +102,7 @@ struct Context {
 	// chunked profile
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
+	DevBuf d_edges;    // hry_edges_build: the numbering's table and working arrays, counters, the list of long segments (edges.cpp)
 	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
 	DevBuf d_sweep;   // hry_quant_sweep_build: its uploads (a mesh that is not resident), the blocks' records and the results (sweep.cpp)
 	DevBuf d_ingest;   // hry_mesh_from_device: status word, scans, the weld's keys and table (ingest.cpp)
@@ -253,6 +254,17 @@ bool place_segment(Context &cx, const Mesh &seg, const std::vector<ShardRun> &ru
 bool holds_decode(const Context &cx, const Mesh &m);
 inline const DevBuf &decoded_records(const Context &cx, size_t l) { return cx.render_whole ? cx.d_whole_rec[l] : cx.d_rec[l]; }
 void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out);   // flags: HRY_RENDER_*
+// the list whose first three POS components are the positions the normals (and the edges' geometry) are computed from; `what`
+// opens the refusals' text (HRY_E_UNSUPPORTED)
+size_t render_position_list(const Mesh &m, const char *what);   // (render.cpp: position_list)
+
+// edges.cpp: unique edges and adjacency of a render build's triangles (include/harry_amd.h: hry_edges_build); the result owns its memory
+struct EdgesResult : DeviceResult {
+	uint64_t summary[4] = {};   // E, edges with one side, with two, with more
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out);   // flags: HRY_EDGES_*
 
 // every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
 // quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG

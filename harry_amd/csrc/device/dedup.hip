@@ -1,6 +1,6 @@
-// First-occurrence numbering on the device: every item gets the id of its key, ids numbered by the key's first item.  Two users:
-// the render build's unweld (corners -> output vertices, render.cpp) and the ingest's weld (rows -> records, ingest.cpp).  Kernels,
-// wave64, an item per lane:
+// First-occurrence numbering on the device: every item gets the id of its key, ids numbered by the key's first item.  Three users:
+// the render build's unweld (corners -> output vertices, render.cpp), the ingest's weld (rows -> records, ingest.cpp) and the edges
+// of a render build (triangle sides -> edges, edges.cpp).  Kernels, wave64, an item per lane:
 //   k_dedup_insert<Key>  every item into an open-addressing table of item indices (at least 2 n slots, linear probing)
 //   k_dedup_find<Key>    per item the first item of its key; per wavefront of 64 items the mask of first items and their count
 //   k_scan_counts        exclusive scan of the wavefront counts by one block (scan.hip: launch_scan_counts)
@@ -89,6 +89,37 @@ struct WeldKey {
 	}
 };
 
+// edges: the key of side s is the unordered pair of the decoded vertices it joins, lo <= hi (an index outside vsrc stands for itself
+// above every vertex: no render build writes one)
+struct EdgeKey {
+	using View = EdgeView;
+	const EdgeView &u;
+	uint32_t lo, hi;
+	static __device__ __forceinline__ uint32_t vertex_of(const EdgeView &u, uint32_t i) { return i < u.nout ? u.vsrc[i] : kNone; }
+	static __device__ __forceinline__ void ends(const EdgeView &u, uint32_t s, uint32_t &lo, uint32_t &hi)
+	{
+		const uint32_t t = s / 3, k = s - 3 * t;
+		const uint32_t a = vertex_of(u, u.indices[s]), b = vertex_of(u, u.indices[3 * t + (k == 2 ? 0 : k + 1)]);
+		lo = min(a, b); hi = max(a, b);
+	}
+	__device__ __forceinline__ EdgeKey(const EdgeView &u, uint32_t s) : u(u) { ends(u, s, lo, hi); }
+	__device__ __forceinline__ uint32_t hash() const
+	{
+		uint32_t h = lo * 0x9e3779b1u;   // the two ends through murmur3's finaliser, one after the other
+		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+		h ^= hi + 0x7f4a7c15u + (h << 6) + (h >> 2);
+		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+		return h;
+	}
+	__device__ __forceinline__ bool same(uint32_t e) const
+	{
+		if (e >= u.n) return false;
+		uint32_t l, h;
+		ends(u, e, l, h);
+		return l == lo && h == hi;
+	}
+};
+
 template <class Key>
 __global__ __launch_bounds__(256) void k_dedup_insert(typename Key::View u)
 {
@@ -158,19 +189,22 @@ __global__ __launch_bounds__(256) void k_iota(uint32_t n, uint32_t *out)
 }
 
 // ---- launchers
-void DedupPlan::reserve(Carve &W, uint32_t items)
+void DedupPlan::reserve(Carve &W, uint32_t items, bool with_ids)
 {
 	n = items; nw = (uint32_t)(((uint64_t)n + 63) / 64);
 	size_t slots = 64;
 	while (slots < 2 * (size_t)n) slots <<= 1;
 	mask = (uint32_t)(slots - 1);
 	at_table = W.reserve(slots * 4); at_first_of = W.reserve((size_t)n * 4); at_masks = W.reserve((size_t)nw * 8);
-	at_counts = W.reserve((size_t)nw * 4); at_wave_start = W.reserve(((size_t)nw + 1) * 4); at_ids = W.reserve((size_t)n * 4);
+	at_counts = W.reserve((size_t)nw * 4); at_wave_start = W.reserve(((size_t)nw + 1) * 4);
+	own_ids = with_ids;
+	if (own_ids) at_ids = W.reserve((size_t)n * 4);
 }
 void DedupPlan::bind(const Carve &W, void *base)
 {
 	table = W.ptr<uint32_t>(base, at_table); first_of = W.ptr<uint32_t>(base, at_first_of); masks = W.ptr<uint64_t>(base, at_masks);
-	counts = W.ptr<uint32_t>(base, at_counts); wave_start = W.ptr<uint32_t>(base, at_wave_start); ids = W.ptr<uint32_t>(base, at_ids);
+	counts = W.ptr<uint32_t>(base, at_counts); wave_start = W.ptr<uint32_t>(base, at_wave_start);
+	if (own_ids) ids = W.ptr<uint32_t>(base, at_ids);
 }
 template <class Key>
 static void dedup_count(hipStream_t st, typename Key::View u, const DedupPlan &p)
@@ -183,6 +217,7 @@ static void dedup_count(hipStream_t st, typename Key::View u, const DedupPlan &p
 }
 void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p) { dedup_count<UnweldKey>(st, u, p); }
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p) { dedup_count<WeldKey>(st, u, p); }
+void launch_dedup_count(hipStream_t st, EdgeView u, const DedupPlan &p) { dedup_count<EdgeKey>(st, u, p); }
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via, uint32_t *via_out)
 {
 	if (p.n) hipLaunchKernelGGL(k_dedup_assign, dim3(blocks_for(p.n, 256)), dim3(256), 0, st, p.n, (const uint32_t*)p.first_of, (const uint64_t*)p.masks,

@@ -48,6 +48,24 @@ struct UnweldView {
 	uint32_t n, nf, nregs, nlists, nb_corner, mask;   // n: corners
 	uint32_t *table;
 };
+// dedup.hip (EdgeKey): the sides of a render build's triangles (edges.cpp).  Side s = 3 t + k joins indices[s] to
+// indices[3 t + (k + 1) % 3]; its key is the unordered pair of their vertex_source entries.  nout: rows of vsrc; n (sides), mask and
+// table are the launcher's, from its DedupPlan
+struct EdgeView {
+	const uint32_t *indices, *vsrc;
+	uint32_t n, nout, mask;
+	uint32_t *table;
+};
+// edges.hip: what the kernels behind the numbering read and write.  indices / vsrc as above; tri_edges[n]: the edge of every side;
+// offsets[ne + 1] / sides[n]: the CSR of the edges' sides; pos: float rows of pos_stride floats whose first three are an output
+// vertex's position, nullptr: no geometry (length / cot / cos are not written)
+struct EdgesView {
+	const uint32_t *indices, *vsrc, *tri_edges;
+	uint32_t *offsets, *sides, *edges, *neighbours;
+	const float *pos;
+	float *length, *cot, *cos;
+	uint32_t n, nout, ne, pos_stride;
+};
 // render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]
 // (or of the element) -> slot[region] (-1: unbound) -> attr[element * nb + slot]
 struct RowsView {

@@ -176,13 +176,15 @@ struct DedupPlan {
 	size_t at_table = 0, at_first_of = 0, at_masks = 0, at_counts = 0, at_wave_start = 0, at_ids = 0;   // pieces of the Carve
 	size_t table_bytes() const { return ((size_t)mask + 1) * 4; }
 	const uint32_t *total() const { return wave_start + nw; }
-	void reserve(Carve &W, uint32_t items);
+	bool own_ids = true;
+	void reserve(Carve &W, uint32_t items, bool with_ids = true);   // with_ids false: the caller points `ids` at n words of its own after bind()
 	void bind(const Carve &W, void *base);
 };
 // insert, find, scan over the keys of u; the launcher takes u's table, mask and item count from the plan.  Fills first_of, masks,
 // counts, wave_start
 void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p);
+void launch_dedup_count(hipStream_t st, EdgeView u, const DedupPlan &p);   // the sides of a render build's triangles (edges.cpp)
 // p.ids[i] = id of item i; per id below nout: first_item[id] = its first item, via_out[id] = via[that item] (via == nullptr: none)
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via = nullptr, uint32_t *via_out = nullptr);
 void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
@@ -207,6 +209,12 @@ void launch_face_normals(hipStream_t st, const NrmView &n, double *fn, float *fa
 void launch_vertex_normals(hipStream_t st, const NrmView &n, const double *fn, uint32_t *count, uint32_t *fill, uint32_t *start, uint32_t *sums, uint32_t *seg,
                            uint32_t *hubs, float *out);
 void launch_normals_expand(hipStream_t st, const float *vn, const uint32_t *vsrc, uint32_t nout, uint32_t nv, float *out);   // out[u] = vn[vsrc[u]]
+
+// edges of a render build (edges.hip; driver: edges.cpp), behind the numbering of the sides (v.tri_edges).  count: v.ne zeroed
+// counters (the scatter's cursors afterwards); sums: scan_sums_words(v.ne); hubs: 1 + edges_hub_capacity(v.n) words, the first
+// zeroed; classes: 3 zeroed counters -- edges with one side, with two, with more.  Every row of every buffer of v is written
+uint32_t edges_hub_capacity(uint32_t nsides);
+void launch_edges(hipStream_t st, const EdgesView &v, uint32_t *count, uint32_t *sums, uint32_t *hubs, uint32_t *classes);
 
 // per-component error of one mesh against another (distortion.hip; driver: distortion.cpp).  launch_distortion_rows: one DistPart
 // per block of kDistBlockRows rows and slot (pa.n components, then the positions when L.pos >= 0) into L.part; a map entry at or

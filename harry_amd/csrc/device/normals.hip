@@ -21,6 +21,7 @@
 
 #include "dev_types.hpp"
 #include "kernels.hpp"
+#include "seg_sort.hpp"
 
 namespace hry {
 namespace dev {
@@ -144,13 +145,6 @@ __global__ __launch_bounds__(256) void k_nrm_vertices(NrmView n, const uint32_t 
 	write_unit(s, out + (size_t)v * 3);
 }
 
-__device__ __forceinline__ void order_pair(uint32_t *a, uint64_t i, uint64_t p, uint64_t len)
-{
-	if (p >= len) return;   // (beyond the segment: a virtual +infinity, which stays where it is)
-	const uint32_t x = a[i], y = a[p];
-	if (x > y) { a[i] = y; a[p] = x; }
-}
-
 __global__ __launch_bounds__(256) void k_nrm_hubs(NrmView n, const uint32_t *start, uint32_t *seg, const double *fn, const uint32_t *hubs, uint32_t hub_cap, float *out)
 {
 	__shared__ double part[3 * 256];
@@ -162,22 +156,7 @@ __global__ __launch_bounds__(256) void k_nrm_hubs(NrmView n, const uint32_t *sta
 		if (e < b || e > n.ne) continue;
 		const uint64_t len = e - b;
 		uint32_t *a = seg + b;
-		// bitonic sort with every comparison ascending (mirror, then halving strides), so that the end of the segment needs no padding
-		for (uint64_t k = 2; (k >> 1) < len; k <<= 1) {
-			const uint64_t half = k >> 1, pairs = ((len + k - 1) / k) * half;
-			for (uint64_t t = tid; t < pairs; t += 256) {
-				const uint64_t base = (t / half) * k, j = t % half;
-				order_pair(a, base + j, base + k - 1 - j, len);
-			}
-			__syncthreads();
-			for (uint64_t j = k >> 2; j > 0; j >>= 1) {
-				for (uint64_t t = tid; t < pairs; t += 256) {
-					const uint64_t i = (t / j) * 2 * j + t % j;
-					order_pair(a, i, i + j, len);
-				}
-				__syncthreads();
-			}
-		}
+		block_sort_segment(a, len, tid);
 		const uint64_t chunk = (len + 255) / 256, lo = min(len, tid * chunk), hi = min(len, lo + chunk);
 		D3 s{ 0.0, 0.0, 0.0 };
 		for (uint64_t i = lo; i < hi; ++i) add_corner(n, fn, v, a[i], s);

@@ -47,27 +47,29 @@ bool rendered(const AttrList &L) { return L.ncomp() > 0 && L.target <= 2; }
 dev::RequantPlan dequant_plan(const AttrList &L) { return gather_plan(L); }
 
 // the list whose first three POS components (mixing.h interpretation 0) are the positions the normals are computed from
-static size_t position_list(const Mesh &m)
+static size_t position_list(const Mesh &m, const std::string &what = "normals")
 {
 	auto npos = [](const AttrList &L) { return L.interp_len.empty() ? 0 : L.interp_len[0]; };
 	if (!m.general) {
-		if (m.lists.size() < 2 || npos(m.lists[1]) < 3) throw Error(HRY_E_UNSUPPORTED, "normals: the vertex list has fewer than three position components");
+		if (m.lists.size() < 2 || npos(m.lists[1]) < 3) throw Error(HRY_E_UNSUPPORTED, what + ": the vertex list has fewer than three position components");
 		return 1;
 	}
 	size_t pl = m.lists.size();
 	for (size_t l = 0; l < m.lists.size(); ++l) {
 		if (m.lists[l].target != 1 || npos(m.lists[l]) < 3) continue;
-		if (pl != m.lists.size()) throw Error(HRY_E_UNSUPPORTED, "normals: several vertex lists with three position components");
+		if (pl != m.lists.size()) throw Error(HRY_E_UNSUPPORTED, what + ": several vertex lists with three position components");
 		pl = l;
 	}
-	if (pl == m.lists.size()) throw Error(HRY_E_UNSUPPORTED, "normals: no vertex list with three position components");
+	if (pl == m.lists.size()) throw Error(HRY_E_UNSUPPORTED, what + ": no vertex list with three position components");
 	for (int r = 0; r < m.bind.nregs_vtx(); ++r) {
 		bool bound = false;
 		for (int a = 0; a < m.bind.nvtxlists(r); ++a) bound |= (size_t)m.bind.vtxlist(r, a) == pl;
-		if (!bound) throw Error(HRY_E_UNSUPPORTED, "normals: a vertex region that does not bind the position list");
+		if (!bound) throw Error(HRY_E_UNSUPPORTED, what + ": a vertex region that does not bind the position list");
 	}
 	return pl;
 }
+
+size_t render_position_list(const Mesh &m, const char *what) { return position_list(m, what); }
 
 void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 {

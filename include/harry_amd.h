@@ -14,6 +14,7 @@
  *   hry_decode          <- hry::reader::read(std::istream&, mesh::Mesh&)          formats/hry/reader.h:19, reader.cc:179-193
  *   hry_bounds          <- quant::set_bounds(Attrs&)                              structs/quant.h:30-44 (called by ply/reader.cc:428)
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
+ *   hry_edges_build     (no counterpart: unique edges, adjacency and per-edge geometry of a render build, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -267,6 +268,52 @@ void hry_render_free(hry_render *r);
 #define HRY_RENDER_FACE_NORMALS   2u   /* buffer "face_normals" f32 [nf, 3] */
 #define HRY_RENDER_ANGLE_WEIGHTED 4u   /* vertex normals weighted by corner angle instead of face area */
 int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_render **out);
+
+/* ---- edges and adjacency of a render build -------------------------------------------------------------------------------
+ * hry_edges_build derives, on ctx's device, what a consumer of "indices" derives next: the unique edges, the triangles that meet at
+ * each, the triangle across each side and -- with HRY_EDGES_GEOMETRY -- length, cotangent weight and the cosine between the two
+ * triangles.  r is a render build of m on ctx's device; the build reads r's "indices", "vertex_source" and position list where they
+ * lie in HBM: nothing is uploaded (uploaded_bytes is 0), the handle owns its memory like the other results, and r may be freed
+ * afterwards.  Let T be the triangles, I = indices, vs = vertex_source.
+ * Sides: side s = 3 t + k (k = 0, 1, 2) of triangle t joins I[t][k] to I[t][(k + 1) % 3].  Its key is the unordered pair of DECODED
+ *   vertices { vs[I[t][k]], vs[I[t][(k + 1) % 3]] }: a uv or normal seam of an unwelded mesh is one edge, not two boundaries (in the
+ *   PLY layout vs is the identity).  No side is left out: one whose two ends are the same decoded vertex is an edge like any other.
+ * Edges are numbered in order of the first side of their key, ascending s: deterministic, whatever order atomics complete in.
+ * Buffers by name, E = hry_edges_count:
+ *   "edges"           u32 [E, 2]  the output vertices of the edge's first side, ordered so that vs[row[0]] <= vs[row[1]] (ties keep
+ *                                 the side's order)
+ *   "tri_edges"       u32 [T, 3]  the edge of side (t, k)
+ *   "edge_offsets"    u32 [E + 1] CSR offsets into "edge_sides"
+ *   "edge_sides"      u32 [3 T]   the sides of edge e, in ascending s, at [edge_offsets[e], edge_offsets[e + 1])
+ *   "tri_neighbours"  u32 [T, 3]  the triangle of the other side where the edge of side (t, k) has exactly two sides, else HRY_NO_ELEMENT
+ * and with HRY_EDGES_GEOMETRY, from P[u] = the first three position components of output vertex u, read as the floats of r's
+ * "list<l>" buffer and widened to double (l: the position list by the rule of the normals above, with the same HRY_E_UNSUPPORTED
+ * refusals); every operation an individually rounded IEEE double operation in the written order, a . b = (a.x b.x + a.y b.y) + a.z b.z,
+ * a x b and |a| as in the normals' contract, no floating-point atomics:
+ *   "edge_length"     f32 [E]     (float)|P[b] - P[a]| for edges[e] = (a, b)
+ *   "edge_cot"        f32 [E]     (float)(0.5 * S): S starts from +0 and adds, over the edge's sides in ascending s, one after the other,
+ *                                 c = (u . v) / |u x v| with u = P[from] - P[o], v = P[to] - P[o], o the triangle's third corner; c counts
+ *                                 as 0 where |u x v| is 0 or not finite, or where c is not finite
+ *   "edge_cos"        f32 [E]     an edge with exactly two sides s0 < s1 in triangles t0, t1: (float)(n_t0 . n_t1), N_t = (P1 - P0) x (P2 - P0),
+ *                                 n_t = N_t / |N_t| per component; negated when both sides run from the same decoded vertex to the same
+ *                                 decoded vertex (the triangles are wound against each other).  Exactly 2.0f ("none") where the edge does
+ *                                 not have two sides, or where either |N_t| is 0 or not finite
+ * The sum of a long segment is the same plain left-to-right one: the bits depend on r alone.
+ * Refusals: null arguments, unknown flag bits, an r whose U / T / nf do not fit m or that lives on another device: HRY_E_ARG; 3 T > 2^31:
+ * HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable.
+ *   hry_edges_get / _copy / _stat  as hry_render_get / _copy / _stat (an absent or empty buffer: *rows 0, *dev NULL; _copy refuses a
+ *                        context on another device); device_ms: the kernels, by events
+ *   hry_edges_summary    out = { E, edges with one side (boundary), with two (manifold), with more }: a device reduction over
+ *                        "edge_offsets" during the build, no buffer is downloaded for it */
+typedef struct hry_edges hry_edges;
+#define HRY_EDGES_GEOMETRY 1u   /* buffers "edge_length", "edge_cot", "edge_cos" f32 [E] */
+int hry_edges_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_edges **out);
+uint64_t hry_edges_count(const hry_edges *e);                     /* E */
+int hry_edges_get(const hry_edges *e, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst, int dst_is_device);
+int hry_edges_summary(const hry_edges *e, uint64_t out[4]);
+int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes);
+void hry_edges_free(hry_edges *e);
 
 /* ---- meshes from device buffers --------------------------------------------------------------------------------------
  * hry_mesh_from_device is hry_mesh_from_arrays for data that already lives on ctx's device (the other direction of

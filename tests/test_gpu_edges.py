@@ -1,0 +1,404 @@
+"""Edges and adjacency of a render build (include/harry_amd.h: hry_edges_build; kernels: harry_amd/csrc/device/edges.hip and the
+EdgeKey numbering of dedup.hip) against the numpy restatement of tests/edges_ref.py.  Index buffers are compared with array_equal;
+float buffers are expected bit-equal to the float64 restatement rounded once to float32, with one float32 step of slack per value
+(a double sqrt or division that is not correctly rounded); every comparison prints how many values are not bit-equal."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from harry_amd import _native as nat
+from harry_amd import cli
+from harry_amd import codec as hc
+from harry_amd import meshgen as mg
+from harry_amd import objgen as og
+from tests import edges_ref as er
+from tests import util
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(util.ROOT, "tests", "golden")
+NONE = er.NO_ELEMENT
+
+
+@pytest.fixture(scope="module")
+def cx():
+    c = hc.Codec(0)
+    yield c
+    c.close()
+
+
+def mesh_of(m):
+    return hc.Mesh.from_arrays(m.verts, m.degrees, m.indices)
+
+
+def xyz_mesh(pos, tris):
+    pos = np.asarray(pos, np.float32)
+    v = np.zeros(len(pos), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    v["x"], v["y"], v["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    tris = np.asarray(tris, np.uint32).reshape(-1, 3)
+    return hc.Mesh.from_arrays(v, np.full(len(tris), 3, np.uint8), tris.reshape(-1))
+
+
+def position_list(mesh):
+    ls = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and len(mesh.list_fmt(l)) >= 3]
+    assert len(ls) == 1
+    return ls[0]
+
+
+def restated(cx, mesh, geometry=True):
+    """the restatement from the mesh's render build, and the render build"""
+    rn = cx.render_numpy(mesh)
+    return er.build(rn["indices"], rn["vertex_source"], rn[f"list{position_list(mesh)}"][:, :3] if geometry else None), rn
+
+
+def compare(got, want, label=""):
+    for k in er.FIXED:
+        assert got[k].dtype == np.uint32 and got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), k
+    for k in er.GEOMETRY:
+        if k in got:
+            assert got[k].dtype == np.float32
+            differ, steps = er.float_steps(got[k], want[k])
+            print(label, k, "values not bit-equal:", differ, "of", got[k].size, "largest distance in float32 steps:", steps)
+            assert steps <= 1, (k, differ, steps)
+
+
+def check(cx, mesh, label="", geometry=True):
+    """both builds against the restatement, the summary and the stat; returns (buffers with geometry, restatement)"""
+    want, _ = restated(cx, mesh, geometry)
+    plain = cx.edges_numpy(mesh)
+    st = cx.edges_stat()
+    assert sorted(plain) == sorted(er.FIXED) and st["uploaded_bytes"] == 0 and st["device_ms"] > 0
+    assert (st["edges"], st["boundary"], st["manifold"], st["nonmanifold"]) == want["summary"]
+    compare(plain, want, label)
+    if not geometry:
+        return plain, want
+    got = cx.edges_numpy(mesh, geometry=True)
+    assert sorted(got) == sorted(er.FIXED + er.GEOMETRY)
+    compare(got, want, label)
+    return got, want
+
+
+def same_bytes(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
+
+
+def segment(r, e):
+    return r["edge_sides"][r["edge_offsets"][e]:r["edge_offsets"][e + 1]]
+
+
+# ---- 1. against the restatement, with and without geometry
+def strip(ntri):
+    """the first ntri triangles of a two-row grid"""
+    m = mg.grid(ntri // 2 + 2, 2)
+    tris = m.indices.reshape(-1, 3)[:ntri]
+    assert len(tris) == ntri
+    return mg.Mesh(m.verts, np.full(ntri, 3, np.uint8), tris.reshape(-1))
+
+
+MESHES = {
+    "torus_tri": lambda: mg.torus(24, 16),
+    "torus_mixed": lambda: mg.torus(24, 16, polys="mixed"),
+    "grid_quads": lambda: mg.grid(9, 8, quads=True),
+    "icosphere": lambda: mg.icosphere(2),
+    "nonmanifold": lambda: mg.with_nonmanifold(mg.torus(12, 10)),
+    "soup": lambda: mg.soup(),
+    "strip21": lambda: strip(21),      # 3 T = 63, 66: either side of a wavefront of 64 sides
+    "strip22": lambda: strip(22),
+    "strip85": lambda: strip(85),      # 3 T = 255, 258: either side of a block of 256
+    "strip86": lambda: strip(86),
+}
+
+
+@pytest.mark.parametrize("name", sorted(MESHES))
+def test_against_restatement(cx, name):
+    got, want = check(cx, mesh_of(MESHES[name]()), name)
+    E = len(got["edges"])
+    assert E > 0 and got["edge_offsets"][-1] == got["edge_sides"].size == got["tri_edges"].size
+    if name == "torus_mixed":
+        assert got["tri_edges"].shape[0] > mesh_of(MESHES[name]()).nf    # polygons: their fan diagonals are edges
+    if name == "grid_quads":
+        assert want["summary"][1] == 2 * (8 + 7)                         # the grid's rim
+    if name == "nonmanifold":
+        assert want["summary"][3] > 0
+
+
+def test_single_triangle(cx):
+    got, _ = check(cx, xyz_mesh([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 1, 2]]))
+    assert np.array_equal(got["edges"], [[0, 1], [1, 2], [0, 2]]) and (got["tri_neighbours"] == NONE).all() and (got["edge_cos"] == 2.0).all()
+    assert np.array_equal(got["edge_cot"], np.array([0.5, 0, 0.5], np.float32))
+
+
+# ---- 2. long segments: either side of the lane path's bound (32 sides) and of a 256-thread workgroup
+def book(pages):
+    """`pages` triangles round one shared edge (the spine 0 - 1), with a strip of ordinary triangles behind them"""
+    a = 2 * np.pi * np.arange(pages) / pages
+    pos = np.concatenate([[[0, 0, 0], [0, 0, 1]], np.stack([np.cos(a), np.sin(a), 0.5 + 0.25 * np.cos(3 * a)], axis=1)])
+    # alternate the winding so that the spine's sides run both ways
+    tris = [(0, 1, 2 + i) if i % 3 else (1, 0, 2 + i) for i in range(pages)]
+    tail = mg.grid(6, 2)
+    tpos = np.stack([tail.verts["x"] + 5, tail.verts["y"], tail.verts["z"]], axis=1)
+    tris = np.concatenate([np.array(tris), tail.indices.reshape(-1, 3) + len(pos)])
+    return xyz_mesh(np.concatenate([pos, tpos]), tris)
+
+
+@pytest.mark.parametrize("pages", [40, 300])
+def test_book(cx, pages):
+    mesh = book(pages)
+    got, want = check(cx, mesh, f"book{pages}")
+    lens = np.diff(want["edge_offsets"].astype(np.int64))
+    assert lens.max() == pages and (lens == pages).sum() == 1     # the case is there: from_arrays kept the spine whole
+    e = int(np.argmax(lens))
+    seg = segment(got, e)
+    assert len(seg) == pages and (np.diff(seg.astype(np.int64)) > 0).all()
+    assert (got["tri_neighbours"].reshape(-1)[seg] == NONE).all() and got["edge_cos"][e] == 2.0
+    assert er.float_steps(got["edge_cot"][e:e + 1], want["edge_cot"][e:e + 1])[1] <= 1 and got["edge_cot"][e] != 0   # the sequential sum
+    assert cx.edges_stat()["nonmanifold"] == 1
+    same_bytes(cx.edges_numpy(mesh, geometry=True), got)
+
+
+# ---- 3. seams: an unwelded mesh's uv / normal seams are edges, not boundaries
+def scene_mesh(which):
+    if which == "smooth":
+        with open(os.path.join(GOLD, "obj", "smooth.obj"), "rb") as f:
+            return hc.Mesh.from_obj(f.read(), os.path.join(GOLD, "obj"))
+    return hc.Mesh.from_obj(og.scene(mg.torus(24, 26, polys="mixed"), normals="smooth", tex="atlas", charts=5).obj, "")
+
+
+@pytest.mark.parametrize("which", ["smooth", "atlas"])
+def test_seams(cx, which):
+    mesh = scene_mesh(which)
+    got, want = check(cx, mesh, which)
+    rn = cx.render_numpy(mesh)
+    vs = rn["vertex_source"]
+    assert len(vs) > mesh.nv                                       # the render build has split vertices
+    P = np.zeros((mesh.nv, 3), np.float32)
+    P[vs] = rn[f"list{position_list(mesh)}"][:, :3]
+    deg = np.diff(mesh.face_offsets().astype(np.int64))
+    v = np.zeros(mesh.nv, np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    v["x"], v["y"], v["z"] = P[:, 0], P[:, 1], P[:, 2]
+    welded = hc.Mesh.from_arrays(v, deg.astype(np.uint8), mesh.org())
+    split = cx.edges_stat()
+    w = cx.edges_numpy(welded)
+    for k in ("edges", "boundary", "manifold", "nonmanifold"):     # the seams are not boundaries: the welded mesh's counts
+        assert cx.edges_stat()[k] == split[k], k
+    # every row names output vertices whose decoded vertices are the key, and the welded mesh's rows are those decoded vertices
+    rows = vs[got["edges"]]
+    assert (rows[:, 0] <= rows[:, 1]).all() and len(np.unique(rows, axis=0)) == len(rows)
+    assert np.array_equal(rows, w["edges"]) and np.array_equal(got["tri_edges"], w["tri_edges"]) and np.array_equal(got["edge_sides"], w["edge_sides"])
+    # what torch's unique over the output vertices' pairs would call boundary: more than there are
+    I = rn["indices"].astype(np.int64)
+    pairs = np.sort(np.stack([I.reshape(-1), I[:, [1, 2, 0]].reshape(-1)], axis=1), axis=1)
+    _, cnt = np.unique(pairs, axis=0, return_counts=True)
+    assert (cnt == 1).sum() > split["boundary"]
+
+
+# ---- 4. decoded meshes: resident or not, the same bytes
+@pytest.mark.parametrize("profile", [hc.PROFILE_COMPAT, hc.PROFILE_CHUNKED], ids=["compat", "chunked"])
+@pytest.mark.parametrize("bits", [0, 12], ids=["lossless", "q12"])
+def test_decoded(cx, profile, bits):
+    m = mesh_of(mg.torus(24, 16, polys="mixed"))
+    if bits:
+        cx.requant(m, [(1, -1, bits)])
+    dec = cx.read_hry(cx.write_hry(m, profile=profile))
+    first = cx.edges_numpy(dec, geometry=True)          # straight after the decode
+    cx.bounds(mesh_of(mg.grid(4, 4)))                   # another call touches the context
+    again = cx.edges_numpy(dec, geometry=True)
+    same_bytes(first, again)
+    want, _ = restated(cx, dec)
+    compare(first, want, f"decoded profile {profile} bits {bits}")
+
+
+# ---- 5. determinism
+def test_two_builds_same_bytes(cx):
+    for mesh in (mesh_of(mg.with_nonmanifold(mg.torus(12, 10))), mesh_of(mg.torus(40, 30, polys="mixed"))):
+        same_bytes(cx.edges_numpy(mesh, geometry=True), cx.edges_numpy(mesh, geometry=True))
+
+
+# ---- 6. degenerate triangles (integer-lattice coordinates: every product and sum is exact)
+def edge_of(r, a, b):
+    hit = np.flatnonzero(((r["edges"][:, 0] == a) & (r["edges"][:, 1] == b)) | ((r["edges"][:, 0] == b) & (r["edges"][:, 1] == a)))
+    assert len(hit) == 1, (a, b)
+    return int(hit[0])
+
+
+def test_degenerate(cx):
+    pos = [[0, 0, 0], [2, 0, 0], [0, 2, 0], [4, 0, 0], [2, 2, 3], [np.nan, 1, 1]]
+    # good, a repeated index, three collinear corners, good, good against the collinear one, a NaN corner
+    tris = [[0, 1, 2], [0, 1, 1], [0, 1, 3], [1, 4, 2], [3, 1, 4], [1, 2, 5]]
+    got, want = check(cx, xyz_mesh(pos, tris), "degenerate")
+    cot, cs = got["edge_cot"], got["edge_cos"]
+    assert not np.isnan(cot).any() and np.isnan(got["edge_length"]).sum() == 2     # NaN stays in the lengths of the two edges at vertex 5
+    e01 = edge_of(got, 0, 1)
+    assert np.array_equal(segment(got, e01), [0, 3, 5, 6]) and cs[e01] == 2.0
+    assert cot[e01] == 0.5                        # triangle 0 adds cot 45 degrees = 1; the repeated index and the collinear corners add exactly 0
+    e11 = edge_of(got, 1, 1)
+    assert np.array_equal(segment(got, e11), [4]) and cs[e11] == 2.0 and cot[e11].view(np.uint32) == 0 and got["edge_length"][e11] == 0
+    e13 = edge_of(got, 1, 3)
+    assert len(segment(got, e13)) == 2 and cs[e13] == 2.0      # two sides, but the collinear triangle has no normal
+    e12 = edge_of(got, 1, 2)
+    assert len(segment(got, e12)) == 3 and cs[e12] == 2.0 and cot[e12] == np.float32(0.5 * (9.0 / np.sqrt(88.0)))   # the NaN corner adds exactly 0
+    e14 = edge_of(got, 1, 4)
+    assert len(segment(got, e14)) == 2 and -1.0 <= cs[e14] <= 1.0
+    assert (cs[np.isnan(got["edge_length"])] == 2.0).all()
+
+
+# ---- 7. refusals
+def raw_build(cx, mesh, render_of, flags):
+    """hry_edges_build of `mesh` with a render build of `render_of`: (status, handle value, error text)"""
+    L = nat.load()
+    r, e = C.c_void_p(), C.c_void_p(1)
+    nat.check(L.hry_render_build(cx.h, render_of.h, C.byref(r)))
+    try:
+        rc = L.hry_edges_build(cx.h, mesh.h, r, flags, C.byref(e))
+        text = L.hry_last_error() if rc else b""
+        if rc == 0:
+            L.hry_edges_free(e)
+        return rc, (e.value if rc else None), text
+    finally:
+        L.hry_render_free(r)
+
+
+def test_refusals(cx):
+    good = xyz_mesh([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 1, 2]])
+    other = mesh_of(mg.torus(12, 10))
+    flat = np.zeros(3, np.dtype([("x", "<f4"), ("y", "<f4")]))
+    flat["x"], flat["y"] = [0, 1, 0], [0, 0, 1]
+    xy = hc.Mesh.from_arrays(flat, np.array([3], np.uint8), np.array([0, 1, 2], np.uint32))
+
+    def usable():
+        assert raw_build(cx, good, good, 1)[0] == 0
+        check(cx, good)
+
+    for flags in (2, 1 | 4, 0x80000000):
+        rc, h, text = raw_build(cx, good, good, flags)
+        assert rc == nat.E_ARG and not h and text
+        usable()
+    rc, h, text = raw_build(cx, good, other, 0)            # a render of another mesh
+    assert rc == nat.E_ARG and not h and text
+    usable()
+    rc, h, text = raw_build(cx, xy, xy, 1)                 # geometry without a z
+    assert rc == nat.E_UNSUPPORTED and not h and b"position" in text
+    usable()
+    assert raw_build(cx, xy, xy, 0)[0] == 0                # ... the topology alone builds
+    got, want = check(cx, xy, geometry=False)
+    assert want["summary"] == (3, 3, 0, 0)
+    with pytest.raises(hc.HryError):
+        cx.edges_numpy(xy, geometry=True)
+    usable()
+    L = nat.load()
+    r = C.c_void_p()
+    nat.check(L.hry_render_build(cx.h, good.h, C.byref(r)))
+    e = C.c_void_p(1)
+    assert L.hry_edges_build(cx.h, good.h, None, 0, C.byref(e)) == nat.E_ARG and not e.value
+    assert L.hry_edges_build(cx.h, good.h, r, 0, None) == nat.E_ARG
+    L.hry_render_free(r)
+    usable()
+
+
+def test_handle_outlives_render_and_get(cx):
+    """the handle owns its memory (the render is freed before any buffer is read), and hry_edges_get describes the buffers"""
+    mesh = mesh_of(mg.torus(12, 10))
+    L = nat.load()
+    r, e = C.c_void_p(), C.c_void_p()
+    nat.check(L.hry_render_build(cx.h, mesh.h, C.byref(r)))
+    nat.check(L.hry_edges_build(cx.h, mesh.h, r, 1, C.byref(e)))
+    L.hry_render_free(r)
+    try:
+        E, T = L.hry_edges_count(e), mesh.ntri
+        assert E == 3 * T // 2
+        shapes = {"edges": (E, 2, 4), "tri_edges": (T, 3, 4), "edge_offsets": (E + 1, 1, 4), "edge_sides": (3 * T, 1, 4), "tri_neighbours": (T, 3, 4),
+                  "edge_length": (E, 1, 0), "edge_cot": (E, 1, 0), "edge_cos": (E, 1, 0), "no_such": (0, 0, 0)}
+        for name, want in shapes.items():
+            dev, rows, width, typ = C.c_void_p(), C.c_uint64(), C.c_int(), C.c_int()
+            nat.check(L.hry_edges_get(e, name.encode(), C.byref(dev), C.byref(rows), C.byref(width), C.byref(typ)))
+            assert (rows.value, width.value, typ.value) == want and bool(dev.value) == (name != "no_such"), name
+        off = np.empty(E + 1, np.uint32)
+        nat.check(L.hry_edges_copy(cx.h, e, b"edge_offsets", off.ctypes.data, 0))
+        assert np.array_equal(off, 2 * np.arange(E + 1))
+        assert L.hry_edges_copy(cx.h, e, b"no_such", off.ctypes.data, 0) == nat.E_ARG
+        s = (C.c_uint64 * 4)()
+        nat.check(L.hry_edges_summary(e, s))
+        assert list(s) == [E, 0, E, 0]
+    finally:
+        L.hry_edges_free(e)
+
+
+# ---- 8. the summary on the command line
+def topology_line(*args):
+    r = subprocess.run([cli.HARRY] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("Topology:")]
+    assert len(lines) == 1, r.stdout
+    w = lines[0].split()
+    assert w[1::2] == ["vertices", "faces", "triangles", "edges", "boundary", "manifold", "nonmanifold", "euler"], lines[0]
+    return dict(zip(w[1::2], map(int, w[2::2]))), r.stdout
+
+
+def test_topology_option(cx, tmp_path):
+    cases = {"torus": mg.torus(24, 16), "icosphere": mg.icosphere(2), "grid": mg.grid(9, 8, quads=True)}
+    for name, m in cases.items():
+        (tmp_path / f"{name}.ply").write_bytes(m.to_ply())
+    t, out = topology_line(tmp_path / "torus.ply", "--topology")
+    assert t == {"vertices": 384, "faces": 768, "triangles": 768, "edges": 1152, "boundary": 0, "manifold": 1152, "nonmanifold": 0, "euler": 0}
+    assert "Writing output" not in out
+    plain = subprocess.run([cli.HARRY, str(tmp_path / "icosphere.ply"), str(tmp_path / "plain.hry")], capture_output=True, text=True, timeout=300)
+    t, out = topology_line(tmp_path / "icosphere.ply", tmp_path / "ico.hry", "--topology")
+    assert t["euler"] == 2 and t["boundary"] == 0 and t["nonmanifold"] == 0 and t["edges"] == 3 * t["triangles"] // 2
+    assert (tmp_path / "ico.hry").read_bytes() == (tmp_path / "plain.hry").read_bytes()
+    keep = lambda text: [l for l in text.splitlines() if not l.startswith("Topology:") and " took " not in l and "time" not in l]
+    assert keep(out) == keep(plain.stdout)                  # the other output is unchanged
+    t, _ = topology_line(tmp_path / "ico.hry", "--topology")   # a .hry input: the decoded mesh, read where the decode left it
+    assert t["euler"] == 2
+    want, _ = restated(cx, mesh_of(cases["grid"]), geometry=False)
+    t, _ = topology_line(tmp_path / "grid.ply", "--topology")
+    assert (t["edges"], t["boundary"], t["manifold"], t["nonmanifold"]) == want["summary"] and t["boundary"] == 30
+    assert t["faces"] == 56 and t["triangles"] == 112
+    r = subprocess.run([cli.HARRY, str(tmp_path / "grid.ply")], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "Too few non-optional arguments" in r.stderr    # without --topology the output stays mandatory
+
+
+# ---- 9. torch: Codec.edges and laplacian
+TORCH_CHILD = r"""
+import sys
+import numpy as np
+import torch
+torch.cuda.init()   # a PyTorch program: torch holds the device before the codec starts
+sys.path.insert(0, sys.argv[1])
+from harry_amd import codec as hc
+from harry_amd import meshgen as mg
+m = mg.icosphere(2)
+mesh = hc.Mesh.from_arrays(m.verts, m.degrees, m.indices)
+c = hc.Codec(0)
+ref = c.edges_numpy(mesh, geometry=True)
+got = c.edges(mesh, geometry=True)
+assert sorted(got) == sorted(ref)
+for k, t in got.items():
+    assert t.device == torch.device("cuda", 0) and t.dtype == (torch.float32 if ref[k].dtype == np.float32 else torch.int32), k
+    assert tuple(t.shape) == ref[k].shape and np.array_equal(t.cpu().numpy().view(np.uint8), ref[k].view(np.uint8)), k
+assert sorted(c.edges(mesh)) == sorted(c.edges_numpy(mesh)) and "edge_cot" not in c.edges(mesh)
+assert c.edges_stat()["edges"] == len(ref["edges"]) and c.edges_stat()["uploaded_bytes"] == 0
+L = hc.laplacian(got["edges"], got["edge_cot"], mesh.nv)
+D = L.to_dense().cpu().numpy().astype(np.float64)
+W = np.zeros((mesh.nv, mesh.nv))
+W[ref["edges"][:, 0], ref["edges"][:, 1]] = ref["edge_cot"]
+W = W + W.T
+want = np.diag(W.sum(axis=1)) - W
+assert L.is_sparse and L.shape == (mesh.nv, mesh.nv) and np.array_equal(D, D.T)
+assert np.abs(D - want).max() <= 1e-5 and np.abs(D.sum(axis=1)).max() <= 1e-4
+G = hc.laplacian(got["edges"], torch.ones(len(ref["edges"]), device="cuda"), mesh.nv).to_dense().cpu().numpy()
+assert sorted(set(np.diag(G).tolist())) == [5.0, 6.0] and (G.sum(axis=1) == 0).all()   # an icosphere's valences
+c.close()
+print("torch ok")
+"""
+
+
+def test_torch_tensors_and_laplacian():
+    pytest.importorskip("torch")
+    r = subprocess.run([sys.executable, "-c", TORCH_CHILD, util.ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "torch ok" in r.stdout, r.stdout + r.stderr
