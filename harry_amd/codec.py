@@ -493,6 +493,72 @@ class Codec:
         boundary (one side), manifold (two), nonmanifold (more)"""
         return dict(getattr(self, "_edges_stat", {}))
 
+    # ---- shells of a render build (include/harry_amd.h: hry_shells_build)
+    SHELLS_FIXED = ("tri_shell", "face_shell", "edge_shell", "shell_first", "shell_counts")
+    SHELLS_GEOMETRY = ("shell_measures",)
+    SHELLS_SUMMARY = ("shells", "closed", "nonmanifold", "misoriented", "loops", "largest")
+
+    def _shells(self, mesh: Mesh, fill, geometry: bool) -> dict:
+        """render build, edges build, shells build from them, free the first two, hand every buffer to fill(name, rows, width, type,
+        handle), free the handle"""
+        L = nat.load()
+        r, e, s = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
+            try:
+                nat.check(L.hry_shells_build(self.h, mesh.h, r, e, nat.SHELLS_GEOMETRY if geometry else 0, C.byref(s)))
+            finally:
+                L.hry_edges_free(e)
+        finally:
+            L.hry_render_free(r)
+        try:
+            out = {}
+            for name in self.SHELLS_FIXED + (self.SHELLS_GEOMETRY if geometry else ()):
+                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                nat.check(L.hry_shells_get(s, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                if width.value:
+                    out[name] = fill(name, rows.value, width.value, typ.value, s)
+            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
+            nat.check(L.hry_shells_stat(s, C.byref(d), C.byref(up)))
+            nat.check(L.hry_shells_summary(s, t))
+            self._shells_stat = {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(self.SHELLS_SUMMARY)}}
+            return out
+        finally:
+            L.hry_shells_free(s)
+
+    def shells_numpy(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """the shells of the mesh's render build (hry_shells_build), copied to host arrays: tri_shell u32 [T], face_shell u32 [nf],
+        edge_shell u32 [E], shell_first u32 [S], shell_counts u32 [S, 8] (triangles, faces, vertices, edges, boundary, nonmanifold,
+        misoriented, loops); geometry: also shell_measures f32 [S, 8] (area, signed volume, min x y z, max x y z)"""
+        def fill(name, rows, width, typ, s):
+            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
+            if rows:
+                nat.check(nat.load().hry_shells_copy(self.h, s, name.encode(), a.ctypes.data, 0))
+            return a
+        return self._shells(mesh, fill, geometry)
+
+    def shells(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: int32 (NO_ELEMENT reads -1) and float32"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+        dtypes = {0: torch.float32, 4: torch.int32}
+        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:   # (every u32 value but NO_ELEMENT is below one of them)
+            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+
+        def fill(name, rows, width, typ, s):
+            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
+            if rows:
+                nat.check(nat.load().hry_shells_copy(self.h, s, name.encode(), t.data_ptr(), 1))
+            return t
+        return self._shells(mesh, fill, geometry)
+
+    def shells_stat(self) -> dict:
+        """of the last shells / shells_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_shells_summary's counts: shells (S),
+        closed, nonmanifold, misoriented (shells), loops (over all shells), largest (triangles of the largest shell)"""
+        return dict(getattr(self, "_shells_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the

@@ -16,6 +16,7 @@ struct hry_plan { ShardPlan p; };
 struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_edges { EdgesResult e; };
+struct hry_shells { ShellsResult s; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -712,6 +713,47 @@ int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_byt
 	return HRY_OK;
 }
 void hry_edges_free(hry_edges *e) { delete e; }
+
+// ---- shells of a render build behind its edges build (shells.cpp).  Like hry_edges_build it leaves the decode's token alone
+int hry_shells_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_shells **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !r || !e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	order_lost(ctx);
+	return guarded([&] {
+		std::unique_ptr<hry_shells> s(new hry_shells());
+		shells_build(ctx->cx, m->m, r->r, e->e, flags, s->s);
+		*out = s.release();
+	});
+}
+uint64_t hry_shells_count(const hry_shells *s) { return s ? s->s.summary[0] : 0; }
+int hry_shells_get(const hry_shells *s, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
+{
+	if (!s || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const NamedBuf *b = result_get(s->s, name, dev, rows, false);
+	if (width) *width = b ? b->width : 0;
+	if (type) *type = b ? b->type : 0;
+	return HRY_OK;
+}
+int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !s || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { result_copy(ctx->cx, s->s, name, "shell buffer", dst, dst_is_device != 0, true); });
+}
+int hry_shells_summary(const hry_shells *s, uint64_t out[6])
+{
+	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	for (int i = 0; i < 6; ++i) out[i] = s->s.summary[i];
+	return HRY_OK;
+}
+int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = s->s.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = s->s.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_shells_free(hry_shells *s) { delete s; }
 
 // ---- numbering maps of an encode (order.cpp)
 int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)

@@ -32,7 +32,10 @@
 // angle of the rms chord); --topology (with or without OUTPUT: after the quantisation phase one line, "Topology: vertices V faces F
 // triangles T edges E boundary B manifold M nonmanifold N euler X" -- hry_render_build, hry_edges_build and hry_edges_summary: E the
 // unique edges of the fan triangles over the decoded vertices, B / M / N those with one, two and more sides, X = V - E + F, which is
-// the Euler characteristic for all-triangle meshes; without OUTPUT the run ends there).
+// the Euler characteristic for all-triangle meshes; without OUTPUT the run ends there); --shells (with or without OUTPUT, after
+// --topology's line: "Shells: shells S closed C nonmanifold N misoriented M loops L largest K", then for the first 16 shells
+// "Shell: I triangles T vertices V edges E boundary B loops L euler X genus G" -- hry_shells_build, hry_shells_summary and the first rows
+// of "shell_counts"; X = V - E + T of the shell, G = (2 - X - L) / 2, or - where the shell has non-manifold or misoriented edges).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -72,7 +75,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -86,7 +89,8 @@ const Opt kOpts[] = {
 	{ 0, "max-error", "Quantization bits from the largest error allowed", true }, { 0, "max-error-rel", "... as a fraction of the extent", true },
 	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true },
 	{ 0, "max-normal-angle", "Position bits from the largest turn of a face normal, degrees", true },
-	{ 0, "topology", "Print edge counts and V - E + F (OUTPUT may be left out)", false } };
+	{ 0, "topology", "Print edge counts and V - E + F (OUTPUT may be left out)", false },
+	{ 0, "shells", "Print the connected shells, their counts, loops and genus (OUTPUT may be left out)", false } };
 
 void usage(const char *argv0)
 {
@@ -168,6 +172,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "gpus") a.gpus = to_int(argv[0], val);
 		else if (n == "report") a.report = true;
 		else if (n == "topology") a.topology = true;
+		else if (n == "shells") a.shells = true;
 		else if (n == "max-error" || n == "max-error-rel") {
 			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
 			const double v = to_double(argv[0], val);
@@ -209,7 +214,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -285,8 +290,9 @@ struct Handles {   // released on every path
 	std::vector<hry_ctx*> cx;   // [0]: the context of every single-device step
 	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
 	hry_distortion *dist = nullptr;
-	hry_render *render = nullptr;   // --topology
+	hry_render *render = nullptr;   // --topology, --shells
 	hry_edges *edges = nullptr;
+	hry_shells *shells = nullptr;
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -294,6 +300,7 @@ struct Handles {   // released on every path
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
+		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
 		if (dist) hry_distortion_free(dist);
@@ -543,10 +550,33 @@ int run(const Args &args)
 		hry_edges_free(h.edges); h.edges = nullptr;
 		hry_render_free(h.render); h.render = nullptr;
 		t2 = Clock::now();   // (no part of the writing phase)
-		if (args.out.empty()) {
-			if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
-			return EXIT_SUCCESS;
+	}
+	if (args.shells) {
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		ok(hry_shells_build(h.cx[0], h.mesh, h.render, h.edges, 0, &h.shells));
+		uint64_t s[6];
+		ok(hry_shells_summary(h.shells, s));
+		std::cout << "Shells: shells " << s[0] << " closed " << s[1] << " nonmanifold " << s[2] << " misoriented " << s[3] << " loops " << s[4] << " largest " << s[5] << std::endl;
+		const uint64_t shown = std::min<uint64_t>(s[0], 16);
+		std::vector<uint32_t> c(8 * s[0]);   // (the whole buffer comes down: the handle copies buffers, not rows)
+		if (s[0]) ok(hry_shells_copy(h.cx[0], h.shells, "shell_counts", c.data(), 0));
+		for (uint64_t i = 0; i < shown; ++i) {
+			const uint32_t *k = &c[8 * i];   // triangles, faces, vertices, edges, boundary, nonmanifold, misoriented, loops
+			const long long euler = (long long)k[2] - (long long)k[3] + (long long)k[0];
+			std::cout << "Shell: " << i << " triangles " << k[0] << " vertices " << k[2] << " edges " << k[3] << " boundary " << k[4] << " loops " << k[7] << " euler " << euler << " genus ";
+			if (k[5] || k[6]) std::cout << "-";
+			else std::cout << (2 - euler - (long long)k[7]) / 2;
+			std::cout << std::endl;
 		}
+		hry_shells_free(h.shells); h.shells = nullptr;
+		hry_edges_free(h.edges); h.edges = nullptr;
+		hry_render_free(h.render); h.render = nullptr;
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells) && args.out.empty()) {
+		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
+		return EXIT_SUCCESS;
 	}
 
 	std::cout << "Writing output..." << std::endl;

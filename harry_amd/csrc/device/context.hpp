@@ -103,6 +103,7 @@ struct Context {
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
 	DevBuf d_edges;    // hry_edges_build: the numbering's table and working arrays, counters, the list of long segments (edges.cpp)
+	DevBuf d_shells;   // hry_shells_build: the union-finds, the pairs' numbering, the chunks' partial sums and their segments (shells.cpp)
 	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
 	DevBuf d_sweep;   // hry_quant_sweep_build: its uploads (a mesh that is not resident), the blocks' records and the results (sweep.cpp)
 	DevBuf d_ingest;   // hry_mesh_from_device: status word, scans, the weld's keys and table (ingest.cpp)
@@ -265,6 +266,19 @@ struct EdgesResult : DeviceResult {
 	uint64_t uploaded_bytes = 0;
 };
 void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out);   // flags: HRY_EDGES_*
+// r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise (edges.cpp)
+void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r);
+// the float rows of r's position list, from its first position component; stride: floats a row.  `what` as render_position_list's
+const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride);
+
+// shells.cpp: the shells of a render build's triangles behind its edges build (include/harry_amd.h: hry_shells_build); the result
+// owns its memory
+struct ShellsResult : DeviceResult {
+	uint64_t summary[6] = {};   // S, closed, nonmanifold, misoriented shells, loops, triangles of the largest
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out);   // flags: HRY_SHELLS_*
 
 // every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
 // quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG

@@ -66,6 +66,35 @@ struct EdgesView {
 	float *length, *cot, *cos;
 	uint32_t n, nout, ne, pos_stride;
 };
+// dedup.hip (ShellVertexKey): the 3 T corners of a render build's triangles (shells.cpp).  The key of corner c is the pair (shell of
+// its triangle, decoded vertex vsrc[indices[c]]): the same decoded vertex within the same shell.  n (corners), mask and table are
+// the launcher's, from its DedupPlan
+struct ShellVertexView {
+	const uint32_t *indices, *vsrc, *tri_shell;
+	uint32_t n, nout, mask;
+	uint32_t *table;
+};
+// shells.hip: what the kernels read of the render and edges builds and what they write.  n = 3 T sides, ne edges, ns shells (0
+// until they are counted); offsets[ne + 1] / sides[n]: the CSR of the edges' sides, every segment ascending; counts: ns rows of 8;
+// pos as in EdgesView, nullptr: no measures
+struct ShellsView {
+	const uint32_t *indices, *vsrc, *tri_face, *tri_edges, *offsets, *sides;
+	uint32_t *tri_shell, *face_shell, *edge_shell, *first, *counts;
+	const float *pos;
+	float *measures;
+	uint32_t n, ntri, nout, nf, ne, ns, pos_stride;
+};
+// the working arrays of shells.hip, laid out by shells.cpp: par / flag [T], num [T + 1], sums: scan_sums_words(T) (it serves the
+// scan over the T flags and the one over the ns <= T counters); pair_id / pair_first_of: the ids and first_of of the corners'
+// numbering [3 T]; slot [3 T] filled with 0xff; loop_par [ne]; summary: 8 zeroed words; and for the measures partial [T] pairs of
+// doubles, pcount [ns] zeroed, pstart [ns + 1], pseg [T], box_lo / box_hi [ns, 3] filled with 0xff / 0, hubs: 1 +
+// shells_hub_capacity(T) words, the first zeroed
+struct ShellsWork {
+	uint32_t *par, *flag, *num, *sums, *pair_id, *slot, *loop_par, *summary;
+	const uint32_t *pair_first_of;
+	double *partial;
+	uint32_t *pcount, *pstart, *pseg, *box_lo, *box_hi, *hubs;
+};
 // render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]
 // (or of the element) -> slot[region] (-1: unbound) -> attr[element * nb + slot]
 struct RowsView {

@@ -11,10 +11,8 @@ namespace hry {
 
 using namespace dev;
 
-void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out)
+void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r)
 {
-	if (flags & ~(uint32_t)HRY_EDGES_GEOMETRY) throw Error(HRY_E_ARG, "unknown edges flag");
-	const bool geometry = flags & HRY_EDGES_GEOMETRY;
 	if (r.block.device != cx.device) throw Error(HRY_E_ARG, "the render buffers live on another device than the context's");
 	// ---- is r a render build of m?  T, nf and U as render_build computes them
 	bool unweld = false;
@@ -27,17 +25,29 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	                  (r.find("corner_source") != nullptr) == unweld;
 	if (!fits) throw Error(HRY_E_ARG, "the render buffers are not a render build of this mesh (vertices, triangles or faces differ)");
 	if (3 * ntri > (1ull << 31)) throw Error(HRY_E_UNSUPPORTED, "more than 2^31 triangle sides");
+}
+
+const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride)
+{
+	const size_t pl = render_position_list(m, what);
+	const NamedBuf *b_pos = r.find("list" + std::to_string(pl));
+	const size_t at = (size_t)m.lists[pl].interp_off[0];
+	if (!b_pos || b_pos->rows != r.nverts || b_pos->type != HRY_FLOAT || (size_t)b_pos->width < at + 3) throw Error(HRY_E_ARG, "the render buffers do not hold this mesh's position list");
+	stride = (uint32_t)b_pos->width;
+	return (const float*)b_pos->p + at;
+}
+
+void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out)
+{
+	if (flags & ~(uint32_t)HRY_EDGES_GEOMETRY) throw Error(HRY_E_ARG, "unknown edges flag");
+	const bool geometry = flags & HRY_EDGES_GEOMETRY;
+	require_render_of(cx, m, r);
+	const uint64_t ntri = m.ntri();
+	const uint32_t nout = r.nverts;
+	const NamedBuf *b_idx = r.find("indices"), *b_vsrc = r.find("vertex_source");
 	const uint32_t n = (uint32_t)(3 * ntri);
-	const float *pos = nullptr;
 	uint32_t pos_stride = 0;
-	if (geometry) {
-		const size_t pl = render_position_list(m, "edges");
-		const NamedBuf *b_pos = r.find("list" + std::to_string(pl));
-		const size_t at = (size_t)m.lists[pl].interp_off[0];
-		if (!b_pos || b_pos->rows != nout || b_pos->type != HRY_FLOAT || (size_t)b_pos->width < at + 3) throw Error(HRY_E_ARG, "the render buffers do not hold this mesh's position list");
-		pos = (const float*)b_pos->p + at;
-		pos_stride = (uint32_t)b_pos->width;
-	}
+	const float *pos = geometry ? render_positions(m, r, "edges", pos_stride) : nullptr;
 	HIP_OK(hipSetDevice(cx.device));
 
 	// ---- the working buffer: the numbering of the sides (dedup.hip); per edge a counter (E <= 3 T of them); the scan's sums; the

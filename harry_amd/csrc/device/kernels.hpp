@@ -185,6 +185,7 @@ struct DedupPlan {
 void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, EdgeView u, const DedupPlan &p);   // the sides of a render build's triangles (edges.cpp)
+void launch_dedup_count(hipStream_t st, ShellVertexView u, const DedupPlan &p);   // the corners of its triangles by (shell, decoded vertex) (shells.cpp)
 // p.ids[i] = id of item i; per id below nout: first_item[id] = its first item, via_out[id] = via[that item] (via == nullptr: none)
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via = nullptr, uint32_t *via_out = nullptr);
 void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
@@ -215,6 +216,18 @@ void launch_normals_expand(hipStream_t st, const float *vn, const uint32_t *vsrc
 // zeroed; classes: 3 zeroed counters -- edges with one side, with two, with more.  Every row of every buffer of v is written
 uint32_t edges_hub_capacity(uint32_t nsides);
 void launch_edges(hipStream_t st, const EdgesView &v, uint32_t *count, uint32_t *sums, uint32_t *hubs, uint32_t *classes);
+
+// shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
+// triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the
+// outputs allocated, counts zeroed, face_shell filled with 0xff): tri_shell, face_shell, shell_first, the triangle and face columns.
+// launch_shells_counts, behind the numbering of the corners by (shell, decoded vertex) (w.pair_id, w.pair_first_of): edge_shell, the
+// other six columns, and the five reductions of the summary behind S (w.summary: closed, nonmanifold, misoriented, loops, largest).
+// launch_shells_measures: shell_measures
+uint32_t shells_hub_capacity(uint32_t ntri);
+void launch_shells_roots(hipStream_t st, const ShellsView &v, const ShellsWork &w);
+void launch_shells_label(hipStream_t st, const ShellsView &v, const ShellsWork &w);
+void launch_shells_counts(hipStream_t st, const ShellsView &v, const ShellsWork &w);
+void launch_shells_measures(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 
 // per-component error of one mesh against another (distortion.hip; driver: distortion.cpp).  launch_distortion_rows: one DistPart
 // per block of kDistBlockRows rows and slot (pa.n components, then the positions when L.pos >= 0) into L.part; a map entry at or

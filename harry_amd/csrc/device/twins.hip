@@ -13,6 +13,7 @@
 #include "dev_types.hpp"
 #include "fan.hpp"
 #include "kernels.hpp"
+#include "union_find.hpp"
 #include "wave.hpp"
 
 namespace hry {
@@ -107,37 +108,13 @@ void launch_twins(hipStream_t st, const ConnView &cv, uint32_t nv, uint32_t *twi
 // as the walks themselves.  Data-parallel integer work over 300 M half-edges and 50 M vertices with random access into tables
 // of a few hundred megabytes: atomics on label / vertex words, per-component sums aggregated per wavefront first (faces and
 // vertices of one component are neighbours in memory: a wavefront holds one or two components).
-//   k_cc_init / k_cc_hook / k_cc_flatten   lock-free union-find, the root of a set is its smallest face (what the host's is)
+//   k_cc_init / k_cc_hook / k_cc_flatten   lock-free union-find (union_find.hpp), the root of a set is its smallest face (what the host's is)
 //   k_cc_roots + k_scan_*                  dense component numbers in face order of the roots
 //   k_cc_face_stats                        faces, half-edges, face interval, smallest key of the start-face sequence per component
 //   k_cc_vertex_first / _ties / _tie_pairs / _stats   the first component (coding order) at every vertex, components tied by a
 //                                          shared vertex (noted as pairs, then a second union-find over components), new
 //                                          vertices and vertex interval
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t uf_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t uf_find(uint32_t *par, uint32_t x)
-{
-	// parents only ever decrease and a face that has got a parent never becomes a root again: a stale read is a valid (higher)
-	// ancestor, and the halving store -- a plain one -- can only replace an ancestor by another ancestor
-	uint32_t p = uf_load(par + x);
-	while (p != x) {
-		const uint32_t g = uf_load(par + p);
-		if (g != p) __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		x = p; p = g;
-	}
-	return x;
-}
-__device__ __forceinline__ void uf_unite(uint32_t *par, uint32_t a, uint32_t b)
-{
-	for (;;) {
-		a = uf_find(par, a); b = uf_find(par, b);
-		if (a == b) return;
-		if (a > b) { const uint32_t t = a; a = b; b = t; }
-		const uint32_t old = atomicCAS(par + b, b, a);   // b is a root still: it hangs under the smaller root
-		if (old == b) return;
-		b = old;
-	}
-}
 __global__ __launch_bounds__(256) void k_cc_init(uint32_t *label, uint32_t n)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -151,16 +128,6 @@ __global__ __launch_bounds__(256) void k_cc_init(uint32_t *label, uint32_t n)
 // union-find in HBM, where a set now arrives as one root per workgroup instead of face by face.  (One pass over HBM: 19.0 ms for
 // the 78.5 M faces of the configs[3] mesh, its searches and compare-and-swaps all in the L2.)
 constexpr uint32_t kHookFaces = 16384, kHookThreads = 1024;   // 64 KB of parents in LDS: two workgroups a compute unit
-__device__ __forceinline__ uint32_t lds_find(uint32_t *par, uint32_t x)
-{
-	uint32_t p = __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-	while (p != x) {
-		const uint32_t g = __hip_atomic_load(par + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		if (g != p) __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		x = p; p = g;
-	}
-	return x;
-}
 __global__ __launch_bounds__(kHookThreads) void k_cc_hook_local(ConnView cv, uint32_t *label)
 {
 	__shared__ uint32_t par[kHookFaces];

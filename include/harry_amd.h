@@ -15,6 +15,7 @@
  *   hry_bounds          <- quant::set_bounds(Attrs&)                              structs/quant.h:30-44 (called by ply/reader.cc:428)
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
  *   hry_edges_build     (no counterpart: unique edges, adjacency and per-edge geometry of a render build, as device buffers)
+ *   hry_shells_build    (no counterpart: connected shells of a render build, their counts, loops, area, volume and box, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -314,6 +315,65 @@ int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst
 int hry_edges_summary(const hry_edges *e, uint64_t out[4]);
 int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes);
 void hry_edges_free(hry_edges *e);
+
+/* ---- shells of a render build ----------------------------------------------------------------------------------------------
+ * hry_shells_build derives, on ctx's device, the connected pieces of the triangles and what is asked of each next: its counts, its
+ * boundary loops and -- with HRY_SHELLS_GEOMETRY -- area, signed volume and box.  r is a render build of m and e an edges build of
+ * (m, r), both on ctx's device; the build reads r's "indices", "vertex_source", "tri_face" and e's "tri_edges", "edges",
+ * "edge_offsets", "edge_sides" where they lie in HBM, with geometry also the float rows of r's position list: nothing is uploaded
+ * (uploaded_bytes is 0), the handle owns its memory like the other results, and r and e may be freed afterwards.  Let T be the
+ * triangles, I = indices, vs = vertex_source, E = hry_edges_count(e).
+ * Shells: two triangles belong to one shell when a chain of triangles joins them in which consecutive ones have a side on the same
+ *   edge of e.  An edge with two or more sides joins all its sides, non-manifold ones included; sharing only a vertex does not join
+ *   (two spheres touching at a point are two shells).  Edges are keyed by DECODED vertices, so a uv or normal seam does not cut a
+ *   shell.  Shells are numbered by their lowest triangle, ascending: shell 0 holds triangle 0; deterministic, whatever order atomics
+ *   complete in.  Isolated vertices belong to no shell.
+ * Buffers by name, S = hry_shells_count:
+ *   "tri_shell"       u32 [T]     the shell of every triangle
+ *   "face_shell"      u32 [nf]    the shell of every face (its fan triangles share their diagonals: one shell); HRY_NO_ELEMENT for a
+ *                                 face without a triangle
+ *   "edge_shell"      u32 [E]     the shell of the edge's sides
+ *   "shell_first"     u32 [S]     the shell's lowest triangle
+ *   "shell_counts"    u32 [S, 8]  triangles, faces, vertices, edges, boundary, nonmanifold, misoriented, loops:
+ *                                 vertices: the distinct DECODED vertices vs[I[t][k]] its triangles name (a vertex where two shells
+ *                                 touch counts in both); boundary: its edges with one side; nonmanifold: with more than two;
+ *                                 misoriented: with exactly two sides that both run from the same decoded vertex to the same decoded
+ *                                 vertex (the condition under which "edge_cos" is negated); loops: the components of its boundary
+ *                                 edges, two of them joined where they share a decoded vertex -- on a manifold shell the number of
+ *                                 boundary cycles.  Boundary edges of different shells are never joined, also where the shells touch
+ *   Euler number of a row: vertices - edges + triangles.  (The "Topology:" line of the command line prints V - E + FACES over the
+ *   whole mesh, which differs on polygon meshes.)  Genus of a row with nonmanifold = 0 and misoriented = 0:
+ *   (2 - euler - loops) / 2; other rows have none.
+ * and with HRY_SHELLS_GEOMETRY, from P[u] = the position of output vertex u, read as for the edges' geometry (the same list, the same
+ * HRY_E_UNSUPPORTED refusals) and widened to double; every operation an individually rounded IEEE double operation in the written
+ * order, a . b, a x b and |a| as in the edges' and normals' contracts, no floating-point atomics:
+ *   "shell_measures"  f32 [S, 8]  area, signed volume, min x, min y, min z, max x, max y, max z
+ *     area   = (float)(0.5 * sum of |(P1 - P0) x (P2 - P0)|), Pk = P[I[t][k]], over the shell's triangles
+ *     volume = (float)(sum of a . (b x c) / 6 -- the sum divided once), a, b, c = P0 - O, P1 - O, P2 - O with O = P[I[shell_first][0]]:
+ *              a mesh far from the origin does not cancel.  Positive for a closed shell whose triangles are wound counter-clockwise
+ *              seen from outside
+ *     A term that is not finite counts as +0.  Order of the sums: chunk c is the triangles [256 c, 256 c + 256); the shell's partial of
+ *     a chunk starts from +0 and adds the terms of its triangles in the chunk in ascending t; the shell's sum starts from +0 and adds
+ *     the partials of the chunks that hold one of its triangles in ascending c.  The bits depend on (r, e) alone.
+ *     box: per coordinate the least and greatest FINITE float over the output vertices the shell's triangles name, -0 below +0; a
+ *     coordinate without a finite value gets +inf and -inf
+ * T = 0: S = 0 and every buffer is empty.
+ * Refusals: null arguments, unknown flag bits, an r or e that does not fit (T, nf, U, E, rows of "tri_edges" / "edge_offsets" /
+ * "edge_sides") or lives on another device: HRY_E_ARG; geometry without three position components: HRY_E_UNSUPPORTED; *out stays
+ * NULL and ctx stays usable.
+ *   hry_shells_get / _copy / _stat  as hry_edges_get / _copy / _stat
+ *   hry_shells_summary   out = { S, closed shells (boundary = 0 and nonmanifold = 0), shells with nonmanifold > 0, shells with
+ *                        misoriented > 0, loops over all shells, triangles of the largest shell }: device reductions during the
+ *                        build, no buffer is downloaded for them */
+typedef struct hry_shells hry_shells;
+#define HRY_SHELLS_GEOMETRY 1u   /* buffer "shell_measures" f32 [S, 8] */
+int hry_shells_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_shells **out);
+uint64_t hry_shells_count(const hry_shells *s);                   /* S */
+int hry_shells_get(const hry_shells *s, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *dst, int dst_is_device);
+int hry_shells_summary(const hry_shells *s, uint64_t out[6]);
+int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes);
+void hry_shells_free(hry_shells *s);
 
 /* ---- meshes from device buffers --------------------------------------------------------------------------------------
  * hry_mesh_from_device is hry_mesh_from_arrays for data that already lives on ctx's device (the other direction of
