@@ -94,6 +94,7 @@ DISTORTION_ROWS, DISTORTION_NORMALS = 1, 4
 SWEEP_NORMALS = 1
 EDGES_GEOMETRY = 1
 SHELLS_GEOMETRY = 1
+ORIENT_MAJORITY, ORIENT_OUTWARD = 1, 2
 TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST, TOL_NORMAL_CHORD = 0, 1, 2, 3, 4
 
 _lib = None
@@ -203,6 +204,15 @@ def load():
     L.hry_shells_summary.restype = C.c_int; L.hry_shells_summary.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.hry_shells_stat.restype = C.c_int; L.hry_shells_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_shells_free.argtypes = [vp]
+    L.hry_orient_build.restype = C.c_int; L.hry_orient_build.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.hry_orient_count.restype = C.c_uint64; L.hry_orient_count.argtypes = [vp]
+    L.hry_orient_get.restype = C.c_int
+    L.hry_orient_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hry_orient_copy.restype = C.c_int; L.hry_orient_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
+    L.hry_orient_summary.restype = C.c_int; L.hry_orient_summary.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.hry_orient_stat.restype = C.c_int; L.hry_orient_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.hry_orient_free.argtypes = [vp]
+    L.hry_mesh_flip_faces.restype = C.c_int; L.hry_mesh_flip_faces.argtypes = [vp, vp, C.POINTER(vp)]
     L.hry_mesh_from_device.restype = C.c_int
     L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),
                                        C.c_int, C.c_int, vp, C.POINTER(vp)]

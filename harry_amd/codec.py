@@ -89,6 +89,18 @@ class Mesh:
             raise MemoryError("hry_mesh_clone")
         return Mesh(C.c_void_p(h))
 
+    def flip_faces(self, face_flip) -> "Mesh":
+        """a clone in which every face f with face_flip[f] != 0, (v0, v1, ..., vk-1), is (v0, vk-1, ..., v1); per-corner records follow
+        their corners (hry_mesh_flip_faces).  face_flip: nf values, for instance "face_flip" of Codec.orient / orient_numpy"""
+        if hasattr(face_flip, "detach"):   # a torch tensor
+            face_flip = face_flip.detach().cpu().numpy()
+        flags = np.ascontiguousarray(np.asarray(face_flip).reshape(-1) != 0, dtype=np.uint32)
+        if len(flags) != self.nf:
+            raise HryError(nat.E_ARG, "face_flip needs one value per face")
+        h = C.c_void_p()
+        nat.check(nat.load().hry_mesh_flip_faces(self.h, flags.ctypes.data, C.byref(h)))
+        return Mesh(h)
+
     # ---- accessors
     nv = property(lambda s: nat.load().hry_mesh_nv(s.h))
     nf = property(lambda s: nat.load().hry_mesh_nf(s.h))
@@ -558,6 +570,76 @@ class Codec:
         """of the last shells / shells_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_shells_summary's counts: shells (S),
         closed, nonmanifold, misoriented (shells), loops (over all shells), largest (triangles of the largest shell)"""
         return dict(getattr(self, "_shells_stat", {}))
+
+    # ---- a consistent winding per patch of a render build (include/harry_amd.h: hry_orient_build)
+    ORIENT_FIXED = ("tri_patch", "tri_flip", "face_flip", "oriented_indices", "patch_first", "patch_counts")
+    ORIENT_OUTWARD = ("patch_measures",)
+    ORIENT_SUMMARY = ("patches", "orientable", "flipped", "inverted", "against", "remaining")
+
+    def _orient(self, mesh: Mesh, fill, majority: bool, outward: bool) -> dict:
+        """render build, edges build, orient build from them, free the first two, hand every buffer to fill(name, rows, width, type,
+        handle), free the handle"""
+        L = nat.load()
+        r, e, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        flags = (nat.ORIENT_MAJORITY if majority else 0) | (nat.ORIENT_OUTWARD if outward else 0)
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
+            try:
+                nat.check(L.hry_orient_build(self.h, mesh.h, r, e, flags, C.byref(o)))
+            finally:
+                L.hry_edges_free(e)
+        finally:
+            L.hry_render_free(r)
+        try:
+            out = {}
+            for name in self.ORIENT_FIXED + (self.ORIENT_OUTWARD if outward else ()):
+                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                nat.check(L.hry_orient_get(o, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                if width.value:
+                    out[name] = fill(name, rows.value, width.value, typ.value, o)
+            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
+            nat.check(L.hry_orient_stat(o, C.byref(d), C.byref(up)))
+            nat.check(L.hry_orient_summary(o, t))
+            self._orient_stat = {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(self.ORIENT_SUMMARY)}}
+            return out
+        finally:
+            L.hry_orient_free(o)
+
+    def orient_numpy(self, mesh: Mesh, majority: bool = False, outward: bool = False) -> dict:
+        """which triangles of the mesh's render build to turn for a consistent winding per patch (hry_orient_build), copied to host
+        arrays: tri_patch u32 [T], tri_flip u32 [T], face_flip u32 [nf], oriented_indices u32 [T, 3], patch_first u32 [P], patch_counts
+        u32 [P, 8] (triangles, faces, flipped, flipped_faces, against, open, orientable, inverted); majority: the smaller side of every
+        patch is flipped; outward: closed patches enclose a positive volume, and patch_measures f32 [P, 8] (area, signed volume, min x y
+        z, max x y z).  mesh.flip_faces(face_flip) is the oriented mesh"""
+        def fill(name, rows, width, typ, o):
+            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
+            if rows:
+                nat.check(nat.load().hry_orient_copy(self.h, o, name.encode(), a.ctypes.data, 0))
+            return a
+        return self._orient(mesh, fill, majority, outward)
+
+    def orient(self, mesh: Mesh, majority: bool = False, outward: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: int32 and float32"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.device)
+        dtypes = {0: torch.float32, 4: torch.int32}
+        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:
+            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+
+        def fill(name, rows, width, typ, o):
+            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
+            if rows:
+                nat.check(nat.load().hry_orient_copy(self.h, o, name.encode(), t.data_ptr(), 1))
+            return t
+        return self._orient(mesh, fill, majority, outward)
+
+    def orient_stat(self) -> dict:
+        """of the last orient / orient_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_orient_summary's counts: patches (P),
+        orientable (patches), flipped (triangles), inverted (patches), against (edges), remaining (against edges in patches that cannot
+        be oriented)"""
+        return dict(getattr(self, "_orient_stat", {}))
 
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):

@@ -17,6 +17,7 @@ struct hry_render { RenderResult r; };
 struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_edges { EdgesResult e; };
 struct hry_shells { ShellsResult s; };
+struct hry_orient { OrientResult o; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -754,6 +755,56 @@ int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_b
 	return HRY_OK;
 }
 void hry_shells_free(hry_shells *s) { delete s; }
+
+// ---- a consistent winding per patch of a render build behind its edges build (orient.cpp).  It leaves the decode's token alone
+int hry_orient_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_orient **out)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !m || !r || !e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	order_lost(ctx);
+	return guarded([&] {
+		std::unique_ptr<hry_orient> o(new hry_orient());
+		orient_build(ctx->cx, m->m, r->r, e->e, flags, o->o);
+		*out = o.release();
+	});
+}
+uint64_t hry_orient_count(const hry_orient *o) { return o ? o->o.summary[0] : 0; }
+int hry_orient_get(const hry_orient *o, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
+{
+	if (!o || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
+	const NamedBuf *b = result_get(o->o, name, dev, rows, false);
+	if (width) *width = b ? b->width : 0;
+	if (type) *type = b ? b->type : 0;
+	return HRY_OK;
+}
+int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *dst, int dst_is_device)
+{
+	if (!ctx || !o || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { result_copy(ctx->cx, o->o, name, "orientation buffer", dst, dst_is_device != 0, true); });
+}
+int hry_orient_summary(const hry_orient *o, uint64_t out[6])
+{
+	if (!o || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	for (int i = 0; i < 6; ++i) out[i] = o->o.summary[i];
+	return HRY_OK;
+}
+int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!o) { g_last_error = "null argument"; return HRY_E_ARG; }
+	if (device_ms) *device_ms = o->o.device_ms;
+	if (uploaded_bytes) *uploaded_bytes = o->o.uploaded_bytes;
+	return HRY_OK;
+}
+void hry_orient_free(hry_orient *o) { delete o; }
+int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
+{
+	if (out) *out = nullptr;
+	if (!m || !face_flip || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] {
+		std::unique_ptr<Mesh> c(mesh_flip_faces(m->m, face_flip));
+		*out = new hry_mesh{ std::move(*c) };
+	});
+}
 
 // ---- numbering maps of an encode (order.cpp)
 int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)

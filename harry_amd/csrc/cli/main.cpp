@@ -35,7 +35,10 @@
 // the Euler characteristic for all-triangle meshes; without OUTPUT the run ends there); --shells (with or without OUTPUT, after
 // --topology's line: "Shells: shells S closed C nonmanifold N misoriented M loops L largest K", then for the first 16 shells
 // "Shell: I triangles T vertices V edges E boundary B loops L euler X genus G" -- hry_shells_build, hry_shells_summary and the first rows
-// of "shell_counts"; X = V - E + T of the shell, G = (2 - X - L) / 2, or - where the shell has non-manifold or misoriented edges).
+// of "shell_counts"; X = V - E + T of the shell, G = (2 - X - L) / 2, or - where the shell has non-manifold or misoriented edges);
+// --orient / --orient-outward (with or without OUTPUT, after those lines, which keep describing the source mesh: "Orientation: patches
+// P orientable O flipped F inverted I against A remaining R" -- hry_orient_build with HRY_ORIENT_MAJORITY, and HRY_ORIENT_OUTWARD for
+// the second, and hry_orient_summary; with OUTPUT and F > 0 the mesh that is written is hry_mesh_flip_faces(mesh, "face_flip")).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -75,7 +78,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -90,7 +93,9 @@ const Opt kOpts[] = {
 	{ 0, "max-bytes", "Quantization bits from the largest .hry allowed", true },
 	{ 0, "max-normal-angle", "Position bits from the largest turn of a face normal, degrees", true },
 	{ 0, "topology", "Print edge counts and V - E + F (OUTPUT may be left out)", false },
-	{ 0, "shells", "Print the connected shells, their counts, loops and genus (OUTPUT may be left out)", false } };
+	{ 0, "shells", "Print the connected shells, their counts, loops and genus (OUTPUT may be left out)", false },
+	{ 0, "orient", "Wind the faces of every patch consistently, the smaller side turned (OUTPUT may be left out)", false },
+	{ 0, "orient-outward", "... and closed patches so that they enclose a positive volume", false } };
 
 void usage(const char *argv0)
 {
@@ -173,6 +178,8 @@ Args parse(int argc, const char **argv)
 		else if (n == "report") a.report = true;
 		else if (n == "topology") a.topology = true;
 		else if (n == "shells") a.shells = true;
+		else if (n == "orient") a.orient = true;
+		else if (n == "orient-outward") a.orient = a.orient_outward = true;
 		else if (n == "max-error" || n == "max-error-rel") {
 			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
 			const double v = to_double(argv[0], val);
@@ -214,7 +221,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -290,9 +297,10 @@ struct Handles {   // released on every path
 	std::vector<hry_ctx*> cx;   // [0]: the context of every single-device step
 	hry_mesh *mesh = nullptr, *before = nullptr;   // before: --report's clone of the mesh as it was read
 	hry_distortion *dist = nullptr;
-	hry_render *render = nullptr;   // --topology, --shells
+	hry_render *render = nullptr;   // --topology, --shells, --orient
 	hry_edges *edges = nullptr;
 	hry_shells *shells = nullptr;
+	hry_orient *orient = nullptr;   // --orient, --orient-outward
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -300,6 +308,7 @@ struct Handles {   // released on every path
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
+		if (orient) hry_orient_free(orient);
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
@@ -574,7 +583,26 @@ int run(const Args &args)
 		hry_render_free(h.render); h.render = nullptr;
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells) && args.out.empty()) {
+	if (args.orient) {
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		ok(hry_orient_build(h.cx[0], h.mesh, h.render, h.edges, HRY_ORIENT_MAJORITY | (args.orient_outward ? HRY_ORIENT_OUTWARD : 0u), &h.orient));
+		uint64_t s[6];
+		ok(hry_orient_summary(h.orient, s));
+		std::cout << "Orientation: patches " << s[0] << " orientable " << s[1] << " flipped " << s[2] << " inverted " << s[3] << " against " << s[4] << " remaining " << s[5] << std::endl;
+		if (s[2] && !args.out.empty()) {   // (nothing flipped: the mesh is written as it is)
+			std::vector<uint32_t> flip(hry_mesh_nf(h.mesh));
+			ok(hry_orient_copy(h.cx[0], h.orient, "face_flip", flip.data(), 0));
+			hry_mesh *turned = nullptr;
+			ok(hry_mesh_flip_faces(h.mesh, flip.data(), &turned));
+			hry_mesh_free(h.mesh); h.mesh = turned;
+		}
+		hry_orient_free(h.orient); h.orient = nullptr;
+		hry_edges_free(h.edges); h.edges = nullptr;
+		hry_render_free(h.render); h.render = nullptr;
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells || args.orient) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

@@ -103,6 +103,7 @@ struct Context {
 	DevBuf d_cjobs, d_cscratch, d_csizes, d_coffs, d_cout, d_csyms, d_patch;
 	DevBuf d_render;   // hry_render_build: its uploads (a mesh that is not resident) and working arrays (render.cpp)
 	DevBuf d_edges;    // hry_edges_build: the numbering's table and working arrays, counters, the list of long segments (edges.cpp)
+	DevBuf d_orient;   // hry_orient_build: the double cover's union-find, the scan, the patches' turns, the measures' working arrays (orient.cpp)
 	DevBuf d_shells;   // hry_shells_build: the union-finds, the pairs' numbering, the chunks' partial sums and their segments (shells.cpp)
 	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
 	DevBuf d_sweep;   // hry_quant_sweep_build: its uploads (a mesh that is not resident), the blocks' records and the results (sweep.cpp)
@@ -279,6 +280,18 @@ struct ShellsResult : DeviceResult {
 	uint64_t uploaded_bytes = 0;
 };
 void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out);   // flags: HRY_SHELLS_*
+// e is an edges build of (m, r) on cx's device, r a render build of m: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise (shells.cpp)
+struct EdgesFit { const NamedBuf *tri_edges, *offsets, *sides; uint32_t ne; };
+EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e);
+
+// orient.cpp: a consistent winding per patch of a render build's triangles behind its edges build (include/harry_amd.h:
+// hry_orient_build); the result owns its memory
+struct OrientResult : DeviceResult {
+	uint64_t summary[6] = {};   // P, orientable patches, flipped triangles, inverted patches, against edges, against edges remaining
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, OrientResult &out);   // flags: HRY_ORIENT_*
 
 // every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
 // quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG

@@ -95,6 +95,19 @@ struct ShellsWork {
 	double *partial;
 	uint32_t *pcount, *pstart, *pseg, *box_lo, *box_hi, *hubs;
 };
+// orient.hip: what the kernels read of the render and edges builds and what they write.  n = 3 T sides, ne edges, np patches (0
+// until they are counted); counts: np rows of 8; oriented: T rows of 3
+struct OrientView {
+	const uint32_t *indices, *vsrc, *tri_face, *tri_edges, *offsets, *sides;
+	uint32_t *tri_patch, *tri_flip, *face_flip, *oriented, *first, *counts;
+	float *measures;
+	uint32_t n, ntri, nout, nf, ne, np;
+};
+// the working arrays of orient.hip, laid out by orient.cpp: par [2 T] (the double cover: node 2 t is triangle t as wound, 2 t + 1
+// turned), flag [T], num [T + 1], sums: scan_sums_words(T), turn [np] zeroed, summary: 8 zeroed words
+struct OrientWork {
+	uint32_t *par, *flag, *num, *sums, *turn, *summary;
+};
 // render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]
 // (or of the element) -> slot[region] (-1: unbound) -> attr[element * nb + slot]
 struct RowsView {

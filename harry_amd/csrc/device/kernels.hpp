@@ -229,6 +229,17 @@ void launch_shells_label(hipStream_t st, const ShellsView &v, const ShellsWork &
 void launch_shells_counts(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 void launch_shells_measures(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 
+// consistent winding per patch of a render build (orient.hip; driver: orient.cpp), behind its edges build.  launch_orient_roots: the
+// union-find over the orientation double cover, the root flags and their scan: w.num[T] = the number of patches, on the device.
+// launch_orient_flips (v.np known, the outputs allocated, counts / face_flip / w.turn zeroed): every integer buffer, the flips
+// relative to each patch's lowest triangle, inverted by majority where asked.  launch_orient_outward, behind launch_shells_measures
+// over the patches and oriented_indices (v.measures): closed orientable patches of negative volume turned as a whole.
+// launch_orient_summary: the five reductions of the summary behind P (w.summary: orientable, flipped, inverted, against, remaining)
+void launch_orient_roots(hipStream_t st, const OrientView &v, const OrientWork &w);
+void launch_orient_flips(hipStream_t st, const OrientView &v, const OrientWork &w, bool majority);
+void launch_orient_outward(hipStream_t st, const OrientView &v, const OrientWork &w);
+void launch_orient_summary(hipStream_t st, const OrientView &v, const OrientWork &w);
+
 // per-component error of one mesh against another (distortion.hip; driver: distortion.cpp).  launch_distortion_rows: one DistPart
 // per block of kDistBlockRows rows and slot (pa.n components, then the positions when L.pos >= 0) into L.part; a map entry at or
 // above L.b_rows raises *status (nothing is read there).  launch_distortion_fold: the blocks' records in block order, one block per

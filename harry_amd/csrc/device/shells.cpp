@@ -11,10 +11,8 @@ namespace hry {
 
 using namespace dev;
 
-void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out)
+EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e)
 {
-	if (flags & ~(uint32_t)HRY_SHELLS_GEOMETRY) throw Error(HRY_E_ARG, "unknown shells flag");
-	const bool geometry = flags & HRY_SHELLS_GEOMETRY;
 	require_render_of(cx, m, r);
 	if (e.block.device != cx.device) throw Error(HRY_E_ARG, "the edge buffers live on another device than the context's");
 	const uint64_t ntri = m.ntri(), ne64 = e.summary[0];
@@ -24,7 +22,17 @@ void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 	const bool fits = b_te && b_ed && b_off && b_sides && b_te->rows == ntri && b_te->width == 3 && b_ed->rows == ne64 && b_off->rows == ne64 + 1 &&
 	                  b_sides->rows == n && ne64 <= n && (n == 0) == (ne64 == 0);
 	if (!fits) throw Error(HRY_E_ARG, "the edge buffers are not an edges build of this mesh's render build (triangles or edges differ)");
-	const uint32_t ne = (uint32_t)ne64, nf = (uint32_t)m.nf;
+	return EdgesFit{ b_te, b_off, b_sides, (uint32_t)ne64 };
+}
+
+void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out)
+{
+	if (flags & ~(uint32_t)HRY_SHELLS_GEOMETRY) throw Error(HRY_E_ARG, "unknown shells flag");
+	const bool geometry = flags & HRY_SHELLS_GEOMETRY;
+	const EdgesFit fit = require_edges_of(cx, m, r, e);
+	const NamedBuf *b_te = fit.tri_edges, *b_off = fit.offsets, *b_sides = fit.sides;
+	const uint64_t ntri = m.ntri();
+	const uint32_t n = (uint32_t)(3 * ntri), ne = fit.ne, nf = (uint32_t)m.nf;
 	uint32_t pos_stride = 0;
 	const float *pos = geometry ? render_positions(m, r, "shells", pos_stride) : nullptr;
 	HIP_OK(hipSetDevice(cx.device));

@@ -15,7 +15,7 @@
 //                              A slot belongs to one shell's vertex: loops of two shells that touch at a point stay apart
 //   k_sh_edges                 a lane per edge: edges, boundary, nonmanifold, misoriented, loops (a boundary edge that is a root)
 //   k_sh_summary               a lane per shell: the five reductions of hry_shells_summary behind S
-// Every per-shell count is an integer atomic, aggregated per wavefront first (wave_count): neighbouring triangles, edges and corners
+// Every per-shell count is an integer atomic, aggregated per wavefront first (WaveCounter, wave_counter.hpp): neighbouring triangles, edges and corners
 // mostly share a shell, so a wavefront sends one atomic per column.
 // Measures (every floating-point operation an individually rounded IEEE double operation in a fixed order: -ffp-contract=off; no
 // floating-point atomics; the bits depend on the render and edges builds alone):
@@ -39,6 +39,7 @@
 #include "seg_sort.hpp"
 #include "union_find.hpp"
 #include "wave.hpp"
+#include "wave_counter.hpp"
 
 namespace hry {
 namespace dev {
@@ -74,41 +75,6 @@ __device__ __forceinline__ uint32_t float_key(float f)
 	return b & 0x80000000u ? ~b : b | 0x80000000u;
 }
 __device__ __forceinline__ float key_float(uint32_t k) { return __uint_as_float(k & 0x80000000u ? k & 0x7fffffffu : ~k); }
-
-// counts[shell][col[i]] += the lanes with valid && add[i], for every shell the wavefront holds.  The sums of the shell met last stay
-// in registers (everything here is uniform over the wavefront) over the kTiles tiles of 256 items a block takes one after the other,
-// and go out as one atomic per column when another shell is met and at the end: with one shell of a million triangles every
-// wavefront would otherwise queue at the same eight words.  Every lane of the wavefront calls add() and flush()
-constexpr uint32_t kTiles = 8;
-template <int N>
-struct WaveCounter {
-	uint32_t shell = kNoElement, acc[N] = {};
-	__device__ __forceinline__ void flush(uint32_t *counts, const uint32_t (&col)[N])
-	{
-		if (shell == kNoElement || (threadIdx.x & 63) != 0) return;
-#pragma unroll
-		for (int i = 0; i < N; ++i) if (acc[i]) atomicAdd(&counts[(size_t)shell * 8 + col[i]], acc[i]);
-	}
-	__device__ __forceinline__ void add(uint32_t *counts, uint32_t ns, bool valid, uint32_t sh, const bool (&add)[N], const uint32_t (&col)[N])
-	{
-		valid = valid && sh < ns;
-		unsigned long long todo = __ballot(valid);
-		while (todo) {
-			const int leader = __ffsll((long long)todo) - 1;
-			const uint32_t s0 = (uint32_t)__shfl((int)sh, leader, 64);
-			const bool mine = valid && sh == s0;
-			if (s0 != shell) {
-				flush(counts, col);
-				shell = s0;
-#pragma unroll
-				for (int i = 0; i < N; ++i) acc[i] = 0;
-			}
-#pragma unroll
-			for (int i = 0; i < N; ++i) acc[i] += (uint32_t)__popcll(__ballot(mine && add[i]));
-			todo &= ~__ballot(mine);
-		}
-	}
-};
 
 // the sides of edge e: false for an edge the buffers do not hold
 __device__ __forceinline__ bool edge_segment(const ShellsView &v, uint32_t e, uint32_t &b, uint32_t &len)

@@ -33,6 +33,9 @@ void ensure_twins(const Mesh &m);
 // the half-edges whose smaller endpoint is one of the given vertices, matched on the host (the device leaves hubs with more
 // than a few dozen such half-edges to it); every other entry of m.twin is final already
 void match_twins_at(Mesh &m, const uint32_t *vertices, uint32_t n);
+// flip_faces.cpp: a clone of m in which every face f with face_flip[f] != 0, (v0, v1, ..., vk-1), is (v0, vk-1, ..., v1); the origins and
+// the corners' record rows follow their corners, the twins are pending, no device / render / order token.  A partial mesh: HRY_E_ARG
+Mesh *mesh_flip_faces(const Mesh &m, const uint32_t *face_flip);
 void print_component(std::string &o, const AttrList &L, const uint8_t *rec, int c);   // one value as the reference prints it (mixing.h:340-359)
 
 // ---- obj_io.cpp (formats/obj/reader.rl:108-299, writer.cc:20-132): meshes with general bindings (mesh.hpp Bindings)

@@ -16,6 +16,7 @@
  *   hry_render_build    (no counterpart: the mesh as render-ready device buffers, after the reference's -c dequantisation)
  *   hry_edges_build     (no counterpart: unique edges, adjacency and per-edge geometry of a render build, as device buffers)
  *   hry_shells_build    (no counterpart: connected shells of a render build, their counts, loops, area, volume and box, as device buffers)
+ *   hry_orient_build    (no counterpart: which triangles of a render build to turn for a consistent winding per patch, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -374,6 +375,69 @@ int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *d
 int hry_shells_summary(const hry_shells *s, uint64_t out[6]);
 int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes);
 void hry_shells_free(hry_shells *s);
+
+/* ---- a consistent winding per patch of a render build --------------------------------------------------------------------------
+ * hry_orient_build says, on ctx's device, which triangles to turn so that neighbours agree, which pieces cannot be oriented at all
+ * and -- with HRY_ORIENT_OUTWARD -- which way is outward.  r is a render build of m and e an edges build of (m, r), both on ctx's
+ * device; the build reads r's "indices", "vertex_source", "tri_face" and e's "tri_edges", "edge_offsets", "edge_sides" where they lie
+ * in HBM, with OUTWARD also the float rows of r's position list: nothing is uploaded (uploaded_bytes is 0), the handle owns its
+ * memory like the other results, and r and e may be freed afterwards.  Let T be the triangles, I = indices, vs = vertex_source.
+ * Joining edge: an edge of e with exactly two sides, in two different triangles, whose two ends are different decoded vertices.  It
+ *   is AGAINST when both sides run from the same decoded vertex to the same decoded vertex (the shells' "misoriented" condition),
+ *   else ALONG.  Edges with one side or more than two, and edges whose ends coincide, relate nothing.
+ * Same-face rule: triangles t and t + 1 with the same tri_face are always related ALONG, whatever their diagonal's edge looks like:
+ *   a face never splits and one flip per face is well defined.
+ * Patches: two triangles are in one patch when a chain of joining edges and same-face relations connects them.  Patches are
+ *   numbered by their lowest triangle, ascending: patch 0 holds triangle 0; deterministic, whatever order atomics complete in.  A
+ *   patch is a subset of a shell: non-manifold edges join shells but not patches.
+ * Orientable: a patch whose triangles can be given flips f[t] in {0, 1} with f[t0] ^ f[t1] = (against ? 1 : 0) over every relation.
+ *   The relative flips put f = 0 at the patch's lowest triangle.  A patch that is not orientable (a Moebius strip, a Klein bottle)
+ *   has f = 0 everywhere.
+ * HRY_ORIENT_MAJORITY: in an orientable patch with 2 * flipped > triangles every f is inverted; on a tie the lowest triangle keeps
+ *   its winding.
+ * HRY_ORIENT_OUTWARD: needs three position components -- P[u], the position of output vertex u, read as for the edges' geometry (the
+ *   same list, the same HRY_E_UNSUPPORTED refusals).  Applied after MAJORITY: an orientable patch with open = 0 whose float volume
+ *   (below) is < 0 is inverted; a volume of 0 or NaN leaves it.
+ * Buffers by name, P = hry_orient_count:
+ *   "tri_patch"         u32 [T]     the patch of every triangle
+ *   "tri_flip"          u32 [T]     0 / 1, final
+ *   "face_flip"         u32 [nf]    the flip of the face's triangles; 0 for a face without a triangle
+ *   "oriented_indices"  u32 [T, 3]  I[t], or (I[t][0], I[t][2], I[t][1]) where tri_flip[t]
+ *   "patch_first"       u32 [P]     the patch's lowest triangle
+ *   "patch_counts"      u32 [P, 8]  triangles, faces, flipped (triangles, final), flipped_faces, against (joining edges that are
+ *                                   against in the source), open (sides of its triangles whose edge is not a joining edge),
+ *                                   orientable (0 / 1), inverted (0 / 1: turned as a whole by OUTWARD)
+ * and with HRY_ORIENT_OUTWARD:
+ *   "patch_measures"    f32 [P, 8]  area, signed volume, min x, min y, min z, max x, max y, max z: "shell_measures" of
+ *                                   hry_shells_build word for word, with patches for shells -- the same double operations, the
+ *                                   same chunks of 256 triangles, the same order of the sums, the same box.  Before the outward step
+ *                                   it reads the triangles as "oriented_indices" (relative flips, then majority if asked);
+ *                                   O = P[corner 0 of the patch's lowest triangle], which a flip leaves unchanged.  The volume of an
+ *                                   inverted patch is then negated, which is exact
+ * T = 0: P = 0 and every buffer is empty.
+ * Refusals: null arguments, unknown flag bits, an r or e that does not fit (as hry_shells_build) or lives on another device:
+ * HRY_E_ARG; OUTWARD without three position components: HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable.
+ *   hry_orient_get / _copy / _stat  as hry_shells_get / _copy / _stat
+ *   hry_orient_summary   out = { P, orientable patches, flipped triangles, inverted patches, against edges, against edges
+ *                        remaining (those in patches that are not orientable) }: device reductions during the build, no buffer is
+ *                        downloaded for them */
+typedef struct hry_orient hry_orient;
+#define HRY_ORIENT_MAJORITY 1u   /* the smaller side of every orientable patch is flipped */
+#define HRY_ORIENT_OUTWARD  2u   /* closed orientable patches enclose a positive volume; buffer "patch_measures" f32 [P, 8] */
+int hry_orient_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_orient **out);
+uint64_t hry_orient_count(const hry_orient *o);                   /* P */
+int hry_orient_get(const hry_orient *o, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *dst, int dst_is_device);
+int hry_orient_summary(const hry_orient *o, uint64_t out[6]);
+int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes);
+void hry_orient_free(hry_orient *o);
+
+/* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
+ * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
+ * and with general bindings the corners' record rows.  The clone's half-edge twins are matched afresh when first needed; it has no
+ * device, render or order token.  Applying it twice with the same flags gives the original arrays.  A partial mesh or a null
+ * argument: HRY_E_ARG, *out stays NULL */
+int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out);
 
 /* ---- meshes from device buffers --------------------------------------------------------------------------------------
  * hry_mesh_from_device is hry_mesh_from_arrays for data that already lives on ctx's device (the other direction of
