@@ -16,6 +16,7 @@ from harry_amd import codec as hc
 from harry_amd import meshgen as mg
 from harry_amd import objgen as og
 from tests import edges_ref as er
+from tests import seam_meshes as sm
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -137,14 +138,8 @@ def test_single_triangle(cx):
 # ---- 2. long segments: either side of the lane path's bound (32 sides) and of a 256-thread workgroup
 def book(pages):
     """`pages` triangles round one shared edge (the spine 0 - 1), with a strip of ordinary triangles behind them"""
-    a = 2 * np.pi * np.arange(pages) / pages
-    pos = np.concatenate([[[0, 0, 0], [0, 0, 1]], np.stack([np.cos(a), np.sin(a), 0.5 + 0.25 * np.cos(3 * a)], axis=1)])
-    # alternate the winding so that the spine's sides run both ways
-    tris = [(0, 1, 2 + i) if i % 3 else (1, 0, 2 + i) for i in range(pages)]
-    tail = mg.grid(6, 2)
-    tpos = np.stack([tail.verts["x"] + 5, tail.verts["y"], tail.verts["z"]], axis=1)
-    tris = np.concatenate([np.array(tris), tail.indices.reshape(-1, 3) + len(pos)])
-    return xyz_mesh(np.concatenate([pos, tpos]), tris)
+    pos, _, idx = sm.book(pages)
+    return xyz_mesh(pos, idx)
 
 
 @pytest.mark.parametrize("pages", [40, 300])

@@ -1,0 +1,216 @@
+"""The edges, shells and orient builds and the vertex normals at the sizes where their kernels change strategy: the designed meshes of
+tests/seam_meshes.py (pinned on the restatements by tests/test_seams_cpu.py), each through the full comparison of the build's own
+test file -- check() of test_gpu_edges.py, test_gpu_shells.py, test_gpu_orient.py and test_gpu_render_normals.py: the restatement of
+the same run's render buffers, integer buffers with array_equal, float buffers within one float32 step with the count of values
+that are not bit-equal printed, the summary and the stat -- and a second build for its bytes.  Every case asserts its condition again
+on the render buffers, so that a render build that numbered things differently cannot empty it.  The seams, by the names and values
+of the constants in the .hip files:
+  orient.hip   kCoverTris = 4096: k_or_hook_local unites in LDS, k_or_hook what leaves a tile -- its same-face statement included
+  shells.hip   kHookTris = 8192 likewise; kSegMax = 32 partials for a lane of k_sh_sums, more for a workgroup of k_sh_hubs, which
+               adds them in tiles of 256 and fills the slots of chunks without the shell with kNoElement
+  edges.hip    kEdgeSegMax = 32 sides for a lane of k_edge_rows, more for k_edge_hubs and the 256-thread sort of seg_sort.hpp
+  normals.hip  kNrmSegMax = 32 corners for a lane, more for k_nrm_hubs
+  wave_counter.hpp and the per-label kernels: a lane per shell or patch, 64 to a wavefront, 256 to a block, 1024 flags to a scan block"""
+import numpy as np
+import pytest
+
+from harry_amd import codec as hc
+from tests import edges_ref as er
+from tests import orient_ref as orf
+from tests import seam_meshes as sm
+from tests import test_gpu_edges as tge
+from tests import test_gpu_orient as tgo
+from tests import test_gpu_render_normals as tgn
+from tests import test_gpu_shells as tgs
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def cx():
+    c = hc.Codec(0)
+    yield c
+    c.close()
+
+
+def rendered(cx, mesh):
+    """the render buffers the conditions are counted on, and their edges restated"""
+    rn = cx.render_numpy(mesh)
+    return rn["indices"], rn["vertex_source"], rn["tri_face"], er.build(rn["indices"], rn["vertex_source"])
+
+
+def edges_checked(cx, mesh, label):
+    got, want = tge.check(cx, mesh, label)
+    tge.same_bytes(got, cx.edges_numpy(mesh, geometry=True))
+    return got, want
+
+
+def shells_checked(cx, mesh, label):
+    got, want = tgs.check(cx, mesh, label)
+    tgs.same_bytes(got, cx.shells_numpy(mesh, geometry=True))
+    return got, want
+
+
+def orient_checked(cx, mesh, label):
+    """all four (majority, outward) combinations, a second build of each included (check() of test_gpu_orient.py)"""
+    return tgo.check(cx, mesh, label)
+
+
+# ---- orient: kCoverTris = 4096
+@pytest.mark.parametrize("name", sorted(sm.FANS))
+def test_fan_on_seam(cx, name):
+    """k_or_hook's same-face statement is the only thing that joins the fan: every diagonal has four sides"""
+    degree, lead, tile = sm.FANS[name]
+    mesh = tgo.mesh_of(sm.fan_on_seam(degree, lead, tile))
+    I, vs, tf, e = rendered(cx, mesh)
+    one_face, fan, joining = sm.fan_on_seam_counts(I, vs, tf, e, tile)
+    assert one_face and joining == 0 and fan.tolist() == list(range(tile - lead, tile - lead + degree - 2))
+    got, _ = orient_checked(cx, mesh, f"fan_on_seam {name}")
+    for g in got.values():
+        assert len(set(g["tri_patch"][fan].tolist())) == 1
+        assert g["patch_counts"][g["tri_patch"][fan[0]]].tolist() == [degree - 2, 1, 0, 0, 0, 3 * (degree - 2), 1, 0]
+    shells_checked(cx, mesh, f"fan_on_seam {name}")
+
+
+@pytest.mark.parametrize("name", sorted(sm.TWO_TILES))
+def test_one_patch_over_two_tiles(cx, name):
+    """whether 2 t0 + 1 hangs under 2 t0 is decided across two workgroups' tiles: Moebius and Klein, and their orientable twins"""
+    make, (patches, orientable, inverted) = sm.TWO_TILES[name]
+    mesh = tgo.mesh_of(make())
+    I, vs, tf, e = rendered(cx, mesh)
+    pairs, _ = sm.orient_pairs(I, vs, tf, e)
+    assert sm.COVER_TRIS < len(I) <= 2 * sm.COVER_TRIS and sm.leaving(pairs, sm.COVER_TRIS) >= 2
+    got, want = orient_checked(cx, mesh, name)
+    assert want()["summary"][:2] == (patches, orientable)
+    for g in got.values():
+        c = tgo.counts(g)
+        assert c.shape == (1, 8) and c[0, tgo.COL["orientable"]] == orientable and c[0, tgo.COL["triangles"]] == len(I)
+        if not orientable:
+            assert not g["tri_flip"].any()
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["ascending", "reversed"])
+@pytest.mark.parametrize("ntri", sm.ORIENT_STRIPS)
+def test_orient_strips(cx, ntri, reverse):
+    clean = sm.strip(ntri, reverse)
+    turned, flags = orf.random_turns(clean)
+    mesh = tgo.mesh_of(turned)
+    I, vs, tf, e = rendered(cx, mesh)
+    pairs, _ = sm.orient_pairs(I, vs, tf, e)
+    assert len(I) == ntri and sm.leaving(pairs, sm.COVER_TRIS) == (ntri - 1) // sm.COVER_TRIS
+    got, _ = orient_checked(cx, mesh, f"strip {ntri} reversed={reverse}")
+    g = got[(True, False)]
+    assert tgo.counts(g).shape == (1, 8) and np.array_equal(g["face_flip"] != 0, flags) and np.array_equal(g["oriented_indices"].reshape(-1), clean[2])
+
+
+# ---- shells: kHookTris = 8192, kSegMax = 32, tiles of 256 partials
+def one_strip(cx, ntri, reverse):
+    mesh = tgo.mesh_of(sm.strip(ntri, reverse))
+    got, _ = shells_checked(cx, mesh, f"strip {ntri} reversed={reverse}")
+    _, _, _, e = rendered(cx, mesh)
+    entries, span = sm.chunk_entries(got["tri_shell"])
+    assert entries.tolist() == span.tolist() == [-(-ntri // sm.CHUNK)] and sm.leaving(sm.shell_pairs(e), sm.HOOK_TRIS) == (ntri - 1) // sm.HOOK_TRIS
+    assert got["shell_counts"][0, 0] == ntri and got["shell_measures"][0, 0] > 0
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["ascending", "reversed"])
+@pytest.mark.parametrize("ntri", sm.SHELL_STRIPS)
+def test_shell_strips(cx, ntri, reverse):
+    """either side of a tile of k_sh_hook_local; 8192 and 8193 triangles are 32 and 33 partials, either side of kSegMax"""
+    one_strip(cx, ntri, reverse)
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["ascending", "reversed"])
+def test_long_strip(cx, reverse):
+    """258 partials: the second tile of 256 of k_sh_hubs' left-to-right sum.  (Its other branch, span > kHubLds = 8192 chunks and the
+    sort of the segment, needs 2.1 M triangles, whose restatement takes tens of seconds: not covered.)"""
+    one_strip(cx, sm.LONG_STRIP, reverse)
+
+
+def test_shuffled_torus(cx):
+    """24 576 triangles in a hostile order: most unions of both hooks are the second pass's, and the first-occurrence numbering of
+    dedup.hip runs over many blocks -- the edges build, the shells build with geometry and the orient build, each in full"""
+    mesh = tgo.mesh_of(sm.shuffled_torus())
+    I, vs, tf, e = rendered(cx, mesh)
+    sp, (op, _) = sm.shell_pairs(e), sm.orient_pairs(I, vs, tf, e)
+    assert len(I) == 24576 and 2 * sm.leaving(sp, sm.HOOK_TRIS) >= len(sp) == 36864 and 2 * sm.leaving(op, sm.COVER_TRIS) >= len(op) == 36864
+    ge, _ = edges_checked(cx, mesh, "shuffled torus")
+    gs, _ = shells_checked(cx, mesh, "shuffled torus")
+    go, _ = orient_checked(cx, mesh, "shuffled torus")
+    assert len(ge["edges"]) == 36864 and gs["shell_counts"].tolist() == [[24576, 24576, 12288, 36864, 0, 0, 0, 0]]
+    for (maj, outw), g in go.items():   # one closed orientable patch, wound inwards as generated: OUTWARD turns all of it
+        c = tgo.counts(g)
+        assert c.shape == (1, 8) and c[0, [0, 1, 4, 5, 6]].tolist() == [24576, 24576, 0, 0, 1] and c[0, tgo.COL["inverted"]] == int(outw)
+        assert g["tri_flip"].sum() == (24576 if outw else 0)
+
+
+def test_alternating_blocks(cx):
+    """more than kSegMax partials with gaps between their chunks: k_sh_hubs meets slots without the shell"""
+    mesh = tgo.mesh_of(sm.alternating_blocks())
+    got, _ = shells_checked(cx, mesh, "alternating blocks")
+    entries, span = sm.chunk_entries(got["tri_shell"])
+    assert (entries > sm.SEG_MAX).all() and (span > entries).all() and entries.tolist() == [40, 40] and span.tolist() == [79, 79]
+    assert got["shell_measures"][1, 2] >= 50 > got["shell_measures"][0, 5]
+
+
+def test_confetti(cx):
+    """3000 shells and patches: every lane of a wavefront a label of its own, more labels than a block of the per-label kernels has
+    threads and more root flags than a scan block holds"""
+    mesh = tgo.mesh_of(sm.confetti())
+    gs, _ = shells_checked(cx, mesh, "confetti")
+    go, _ = orient_checked(cx, mesh, "confetti")
+    n = len(gs["shell_first"])
+    assert n == 3000 > sm.SCAN_BLOCK > sm.LABEL_BLOCK and sm.labels_per_wavefront(gs["tri_shell"]) == sm.WAVE
+    for g in go.values():
+        assert len(g["patch_first"]) == n and sm.labels_per_wavefront(g["tri_patch"]) == sm.WAVE
+
+
+def test_interleaved_strips(cx):
+    """64 labels in every wavefront, each recurring in every tile of the WaveCounter kernels and every chunk of the partial sums"""
+    turned, flags = orf.random_turns(sm.interleaved_strips())
+    mesh = tgo.mesh_of(turned)
+    gs, _ = shells_checked(cx, mesh, "interleaved strips")
+    go, _ = orient_checked(cx, mesh, "interleaved strips")
+    entries, span = sm.chunk_entries(gs["tri_shell"])
+    assert len(entries) == sm.WAVE and sm.labels_per_wavefront(gs["tri_shell"]) == sm.WAVE and (entries == len(flags) // sm.CHUNK).all()
+    for g in go.values():
+        assert len(g["patch_first"]) == sm.WAVE and sm.labels_per_wavefront(g["tri_patch"]) == sm.WAVE
+    assert np.array_equal(gs["tri_shell"], go[(True, True)]["tri_patch"])
+
+
+# ---- edges and normals: kEdgeSegMax = kNrmSegMax = 32, the 256-thread sort
+def long_segments(cx, mesh, label, pages, many):
+    ge, we = edges_checked(cx, mesh, label)
+    lens = sm.segment_lengths(ge)
+    assert lens.max() == pages and (lens == pages).sum() == many and (lens > sm.SEG_MAX).sum() == (many if pages > sm.SEG_MAX else 0)
+    for e in np.flatnonzero(lens == pages):
+        seg = tge.segment(ge, e)
+        assert (np.diff(seg.astype(np.int64)) > 0).all() and (ge["tri_neighbours"].reshape(-1)[seg] == tge.NONE).all() and ge["edge_cos"][e] == 2.0
+        assert ge["edge_cot"][e] != 0                                                   # the sequential sum of the spine
+    assert cx.edges_stat()["nonmanifold"] == many
+    gs, _ = shells_checked(cx, mesh, label)
+    assert gs["shell_counts"][:, tgs.COL["nonmanifold"]].sum() == many
+
+
+@pytest.mark.parametrize("pages", sm.BOOK_PAGES)
+def test_books(cx, pages):
+    long_segments(cx, tgo.mesh_of(sm.book(pages)), f"book {pages}", pages, 1)
+
+
+def test_shelf(cx):
+    """several listed edges in one build"""
+    long_segments(cx, tgo.mesh_of(sm.shelf()), "shelf 20 x 33", 33, 20)
+
+
+def test_hub_discs(cx):
+    """vertices of 31 .. 34 and 255 .. 257 corners: either side of the lane path of k_nrm_hubs and of a block"""
+    mesh = tgo.mesh_of(sm.hub_discs())
+    I, vs, tf, e = rendered(cx, mesh)
+    corners = sm.corners_per_vertex(I, vs, mesh.nv)
+    assert sorted(corners[corners > 8].tolist()) == sm.HUB_VALENCES
+    first = tgn.check(cx, mesh)
+    for mode in tgn.MODES:
+        tgn.same_bits(cx.render_numpy(mesh, normals=mode, face_normals=True), first[mode])
+    edges_checked(cx, mesh, "hub discs")
+    gs, _ = shells_checked(cx, mesh, "hub discs")
+    assert gs["shell_counts"][:, tgs.COL["boundary"]].tolist() == sm.HUB_VALENCES

@@ -17,6 +17,7 @@ from harry_amd import codec as hc
 from harry_amd import meshgen as mg
 from harry_amd import objgen as og
 from tests import edges_ref as er
+from tests import seam_meshes as sm
 from tests import shells_ref as sr
 from tests import util
 
@@ -173,13 +174,8 @@ def test_long_strip(cx, reverse):
 
 def book(pages):
     """`pages` triangles round one shared edge, with a strip of ordinary triangles behind them (the edges test's hub)"""
-    a = 2 * np.pi * np.arange(pages) / pages
-    pos = np.concatenate([[[0, 0, 0], [0, 0, 1]], np.stack([np.cos(a), np.sin(a), 0.5 + 0.25 * np.cos(3 * a)], axis=1)])
-    tris = [(0, 1, 2 + i) if i % 3 else (1, 0, 2 + i) for i in range(pages)]
-    tail = mg.grid(6, 2)
-    tpos = np.stack([tail.verts["x"] + 5, tail.verts["y"], tail.verts["z"]], axis=1)
-    tris = np.concatenate([np.array(tris), tail.indices.reshape(-1, 3) + len(pos)])
-    return xyz_mesh(np.concatenate([pos, tpos]), tris)
+    pos, _, idx = sm.book(pages)
+    return xyz_mesh(pos, idx)
 
 
 def test_book(cx):
