@@ -188,30 +188,16 @@ def load():
     L.hry_render_copy.restype = C.c_int; L.hry_render_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_render_free.argtypes = [vp]
-    L.hry_edges_build.restype = C.c_int; L.hry_edges_build.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
-    L.hry_edges_count.restype = C.c_uint64; L.hry_edges_count.argtypes = [vp]
-    L.hry_edges_get.restype = C.c_int
-    L.hry_edges_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.hry_edges_copy.restype = C.c_int; L.hry_edges_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
-    L.hry_edges_summary.restype = C.c_int; L.hry_edges_summary.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.hry_edges_stat.restype = C.c_int; L.hry_edges_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-    L.hry_edges_free.argtypes = [vp]
-    L.hry_shells_build.restype = C.c_int; L.hry_shells_build.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)]
-    L.hry_shells_count.restype = C.c_uint64; L.hry_shells_count.argtypes = [vp]
-    L.hry_shells_get.restype = C.c_int
-    L.hry_shells_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.hry_shells_copy.restype = C.c_int; L.hry_shells_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
-    L.hry_shells_summary.restype = C.c_int; L.hry_shells_summary.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.hry_shells_stat.restype = C.c_int; L.hry_shells_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-    L.hry_shells_free.argtypes = [vp]
-    L.hry_orient_build.restype = C.c_int; L.hry_orient_build.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(vp)]
-    L.hry_orient_count.restype = C.c_uint64; L.hry_orient_count.argtypes = [vp]
-    L.hry_orient_get.restype = C.c_int
-    L.hry_orient_get.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.hry_orient_copy.restype = C.c_int; L.hry_orient_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
-    L.hry_orient_summary.restype = C.c_int; L.hry_orient_summary.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.hry_orient_stat.restype = C.c_int; L.hry_orient_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-    L.hry_orient_free.argtypes = [vp]
+    for fam, inputs in (("edges", [vp]), ("shells", [vp, vp]), ("orient", [vp, vp])):   # the builds behind a render build: its handle(s) in
+        def fn(what, restype, argtypes):
+            f = getattr(L, f"hry_{fam}_{what}"); f.restype = restype; f.argtypes = argtypes
+        fn("build", C.c_int, [vp, vp] + inputs + [C.c_uint32, C.POINTER(vp)])
+        fn("count", C.c_uint64, [vp])
+        fn("get", C.c_int, [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        fn("copy", C.c_int, [vp, vp, C.c_char_p, vp, C.c_int])
+        fn("summary", C.c_int, [vp, C.POINTER(C.c_uint64)])
+        fn("stat", C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
+        fn("free", None, [vp])
     L.hry_mesh_flip_faces.restype = C.c_int; L.hry_mesh_flip_faces.argtypes = [vp, vp, C.POINTER(vp)]
     L.hry_mesh_from_device.restype = C.c_int
     L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),

@@ -444,48 +444,51 @@ class Codec:
             return t
         return self._render(mesh, fill, self._render_flags(normals, face_normals))
 
-    # ---- edges and adjacency of a render build (include/harry_amd.h: hry_edges_build)
-    EDGES_FIXED = ("edges", "tri_edges", "edge_offsets", "edge_sides", "tri_neighbours")
-    EDGES_GEOMETRY = ("edge_length", "edge_cot", "edge_cos")
-
-    def _edges(self, mesh: Mesh, fill, geometry: bool) -> dict:
-        """render build, edges build from it, free the render, hand every buffer to fill(name, rows, width, type, handle), free the handle"""
+    # ---- the builds behind a render build: edges, shells, orient (include/harry_amd.h: hry_edges_build, hry_shells_build, hry_orient_build)
+    def _topology(self, mesh: Mesh, family: str, flags: int, names, summary, fill) -> dict:
+        """the chain of builds that ends in `family` -- render, edges, then shells or orient from both -- freeing every input handle in
+        reverse order whatever happens; then every named buffer of the last handle that exists goes to fill(family, name, rows, width,
+        type, handle), its stat and summary (keys: `summary`) into self._<family>_stat, and the last handle is freed"""
         L = nat.load()
-        r, e = C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        held = []   # (family, handle) of the chain so far
+
+        def build(fam, *args):
+            h = C.c_void_p()
+            nat.check(getattr(L, f"hry_{fam}_build")(self.h, mesh.h, *args, C.byref(h)))
+            held.append((fam, h))
+            return h
         try:
-            nat.check(L.hry_edges_build(self.h, mesh.h, r, nat.EDGES_GEOMETRY if geometry else 0, C.byref(e)))
+            r = build("render")
+            e = build("edges", r, flags if family == "edges" else 0)
+            if family != "edges":
+                build(family, r, e, flags)
+            h = held.pop()[1]
         finally:
-            L.hry_render_free(r)
+            for fam, x in reversed(held):
+                getattr(L, f"hry_{fam}_free")(x)
         try:
             out = {}
-            for name in self.EDGES_FIXED + (self.EDGES_GEOMETRY if geometry else ()):
+            for name in names:
                 rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                nat.check(L.hry_edges_get(e, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
                 if width.value:
-                    out[name] = fill(name, rows.value, width.value, typ.value, e)
-            d, up, s = C.c_double(), C.c_uint64(), (C.c_uint64 * 4)()
-            nat.check(L.hry_edges_stat(e, C.byref(d), C.byref(up)))
-            nat.check(L.hry_edges_summary(e, s))
-            self._edges_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges": int(s[0]), "boundary": int(s[1]), "manifold": int(s[2]),
-                                "nonmanifold": int(s[3])}
+                    out[name] = fill(family, name, rows.value, width.value, typ.value, h)
+            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * len(summary))()
+            nat.check(getattr(L, f"hry_{family}_stat")(h, C.byref(d), C.byref(up)))
+            nat.check(getattr(L, f"hry_{family}_summary")(h, t))
+            setattr(self, f"_{family}_stat", {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(summary)}})
             return out
         finally:
-            L.hry_edges_free(e)
+            getattr(L, f"hry_{family}_free")(h)
 
-    def edges_numpy(self, mesh: Mesh, geometry: bool = False) -> dict:
-        """unique edges and adjacency of the mesh's render build (hry_edges_build), copied to host arrays: edges u32 [E, 2], tri_edges
-        u32 [T, 3], edge_offsets u32 [E + 1], edge_sides u32 [3 T], tri_neighbours u32 [T, 3] (NO_ELEMENT: none); geometry: also
-        edge_length, edge_cot, edge_cos f32 [E] (edge_cos 2.0: the edge does not join two triangles with normals)"""
-        def fill(name, rows, width, typ, e):
-            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
-            if rows:
-                nat.check(nat.load().hry_edges_copy(self.h, e, name.encode(), a.ctypes.data, 0))
-            return a
-        return self._edges(mesh, fill, geometry)
+    def _fill_numpy(self, family, name, rows, width, typ, h):
+        a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
+        if rows:
+            nat.check(getattr(nat.load(), f"hry_{family}_copy")(self.h, h, name.encode(), a.ctypes.data, 0))
+        return a
 
-    def edges(self, mesh: Mesh, geometry: bool = False) -> dict:
-        """the same buffers as torch tensors on this codec's device, copied device to device: int32 (NO_ELEMENT reads -1) and float32"""
+    def _fill_torch(self, mesh: Mesh):
+        """the fill that copies device to device into tensors on this codec's device: int32 (NO_ELEMENT reads -1) and float32"""
         import torch   # only here: the rest of the package does not need torch
         dev = torch.device("cuda", self.device)
         dtypes = {0: torch.float32, 4: torch.int32}
@@ -493,12 +496,31 @@ class Codec:
             raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
         torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
 
-        def fill(name, rows, width, typ, e):
+        def fill(family, name, rows, width, typ, h):
             t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
             if rows:
-                nat.check(nat.load().hry_edges_copy(self.h, e, name.encode(), t.data_ptr(), 1))
+                nat.check(getattr(nat.load(), f"hry_{family}_copy")(self.h, h, name.encode(), t.data_ptr(), 1))
             return t
-        return self._edges(mesh, fill, geometry)
+        return fill
+
+    # ---- edges and adjacency of a render build (include/harry_amd.h: hry_edges_build)
+    EDGES_FIXED = ("edges", "tri_edges", "edge_offsets", "edge_sides", "tri_neighbours")
+    EDGES_GEOMETRY = ("edge_length", "edge_cot", "edge_cos")
+    EDGES_SUMMARY = ("edges", "boundary", "manifold", "nonmanifold")
+
+    def _edges(self, mesh: Mesh, fill, geometry: bool) -> dict:
+        return self._topology(mesh, "edges", nat.EDGES_GEOMETRY if geometry else 0, self.EDGES_FIXED + (self.EDGES_GEOMETRY if geometry else ()),
+                              self.EDGES_SUMMARY, fill)
+
+    def edges_numpy(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """unique edges and adjacency of the mesh's render build (hry_edges_build), copied to host arrays: edges u32 [E, 2], tri_edges
+        u32 [T, 3], edge_offsets u32 [E + 1], edge_sides u32 [3 T], tri_neighbours u32 [T, 3] (NO_ELEMENT: none); geometry: also
+        edge_length, edge_cot, edge_cos f32 [E] (edge_cos 2.0: the edge does not join two triangles with normals)"""
+        return self._edges(mesh, self._fill_numpy, geometry)
+
+    def edges(self, mesh: Mesh, geometry: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: int32 (NO_ELEMENT reads -1) and float32"""
+        return self._edges(mesh, self._fill_torch(mesh), geometry)
 
     def edges_stat(self) -> dict:
         """of the last edges / edges_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_edges_summary's counts: edges (E),
@@ -511,60 +533,18 @@ class Codec:
     SHELLS_SUMMARY = ("shells", "closed", "nonmanifold", "misoriented", "loops", "largest")
 
     def _shells(self, mesh: Mesh, fill, geometry: bool) -> dict:
-        """render build, edges build, shells build from them, free the first two, hand every buffer to fill(name, rows, width, type,
-        handle), free the handle"""
-        L = nat.load()
-        r, e, s = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
-            try:
-                nat.check(L.hry_shells_build(self.h, mesh.h, r, e, nat.SHELLS_GEOMETRY if geometry else 0, C.byref(s)))
-            finally:
-                L.hry_edges_free(e)
-        finally:
-            L.hry_render_free(r)
-        try:
-            out = {}
-            for name in self.SHELLS_FIXED + (self.SHELLS_GEOMETRY if geometry else ()):
-                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                nat.check(L.hry_shells_get(s, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                if width.value:
-                    out[name] = fill(name, rows.value, width.value, typ.value, s)
-            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
-            nat.check(L.hry_shells_stat(s, C.byref(d), C.byref(up)))
-            nat.check(L.hry_shells_summary(s, t))
-            self._shells_stat = {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(self.SHELLS_SUMMARY)}}
-            return out
-        finally:
-            L.hry_shells_free(s)
+        return self._topology(mesh, "shells", nat.SHELLS_GEOMETRY if geometry else 0, self.SHELLS_FIXED + (self.SHELLS_GEOMETRY if geometry else ()),
+                              self.SHELLS_SUMMARY, fill)
 
     def shells_numpy(self, mesh: Mesh, geometry: bool = False) -> dict:
         """the shells of the mesh's render build (hry_shells_build), copied to host arrays: tri_shell u32 [T], face_shell u32 [nf],
         edge_shell u32 [E], shell_first u32 [S], shell_counts u32 [S, 8] (triangles, faces, vertices, edges, boundary, nonmanifold,
         misoriented, loops); geometry: also shell_measures f32 [S, 8] (area, signed volume, min x y z, max x y z)"""
-        def fill(name, rows, width, typ, s):
-            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
-            if rows:
-                nat.check(nat.load().hry_shells_copy(self.h, s, name.encode(), a.ctypes.data, 0))
-            return a
-        return self._shells(mesh, fill, geometry)
+        return self._shells(mesh, self._fill_numpy, geometry)
 
     def shells(self, mesh: Mesh, geometry: bool = False) -> dict:
         """the same buffers as torch tensors on this codec's device, copied device to device: int32 (NO_ELEMENT reads -1) and float32"""
-        import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.device)
-        dtypes = {0: torch.float32, 4: torch.int32}
-        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:   # (every u32 value but NO_ELEMENT is below one of them)
-            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-
-        def fill(name, rows, width, typ, s):
-            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
-            if rows:
-                nat.check(nat.load().hry_shells_copy(self.h, s, name.encode(), t.data_ptr(), 1))
-            return t
-        return self._shells(mesh, fill, geometry)
+        return self._shells(mesh, self._fill_torch(mesh), geometry)
 
     def shells_stat(self) -> dict:
         """of the last shells / shells_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_shells_summary's counts: shells (S),
@@ -577,34 +557,8 @@ class Codec:
     ORIENT_SUMMARY = ("patches", "orientable", "flipped", "inverted", "against", "remaining")
 
     def _orient(self, mesh: Mesh, fill, majority: bool, outward: bool) -> dict:
-        """render build, edges build, orient build from them, free the first two, hand every buffer to fill(name, rows, width, type,
-        handle), free the handle"""
-        L = nat.load()
-        r, e, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
         flags = (nat.ORIENT_MAJORITY if majority else 0) | (nat.ORIENT_OUTWARD if outward else 0)
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
-            try:
-                nat.check(L.hry_orient_build(self.h, mesh.h, r, e, flags, C.byref(o)))
-            finally:
-                L.hry_edges_free(e)
-        finally:
-            L.hry_render_free(r)
-        try:
-            out = {}
-            for name in self.ORIENT_FIXED + (self.ORIENT_OUTWARD if outward else ()):
-                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                nat.check(L.hry_orient_get(o, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                if width.value:
-                    out[name] = fill(name, rows.value, width.value, typ.value, o)
-            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
-            nat.check(L.hry_orient_stat(o, C.byref(d), C.byref(up)))
-            nat.check(L.hry_orient_summary(o, t))
-            self._orient_stat = {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(self.ORIENT_SUMMARY)}}
-            return out
-        finally:
-            L.hry_orient_free(o)
+        return self._topology(mesh, "orient", flags, self.ORIENT_FIXED + (self.ORIENT_OUTWARD if outward else ()), self.ORIENT_SUMMARY, fill)
 
     def orient_numpy(self, mesh: Mesh, majority: bool = False, outward: bool = False) -> dict:
         """which triangles of the mesh's render build to turn for a consistent winding per patch (hry_orient_build), copied to host
@@ -612,28 +566,11 @@ class Codec:
         u32 [P, 8] (triangles, faces, flipped, flipped_faces, against, open, orientable, inverted); majority: the smaller side of every
         patch is flipped; outward: closed patches enclose a positive volume, and patch_measures f32 [P, 8] (area, signed volume, min x y
         z, max x y z).  mesh.flip_faces(face_flip) is the oriented mesh"""
-        def fill(name, rows, width, typ, o):
-            a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
-            if rows:
-                nat.check(nat.load().hry_orient_copy(self.h, o, name.encode(), a.ctypes.data, 0))
-            return a
-        return self._orient(mesh, fill, majority, outward)
+        return self._orient(mesh, self._fill_numpy, majority, outward)
 
     def orient(self, mesh: Mesh, majority: bool = False, outward: bool = False) -> dict:
         """the same buffers as torch tensors on this codec's device, copied device to device: int32 and float32"""
-        import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.device)
-        dtypes = {0: torch.float32, 4: torch.int32}
-        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:
-            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-
-        def fill(name, rows, width, typ, o):
-            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
-            if rows:
-                nat.check(nat.load().hry_orient_copy(self.h, o, name.encode(), t.data_ptr(), 1))
-            return t
-        return self._orient(mesh, fill, majority, outward)
+        return self._orient(mesh, self._fill_torch(mesh), majority, outward)
 
     def orient_stat(self) -> dict:
         """of the last orient / orient_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_orient_summary's counts: patches (P),

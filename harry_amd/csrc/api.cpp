@@ -7,6 +7,7 @@
 #include <new>
 
 #include "device/context.hpp"
+#include "device/result_build.hpp"
 
 using namespace hry;
 
@@ -67,6 +68,58 @@ static uint8_t *dup_bytes(const std::vector<uint8_t> &v)
 	if (!v.empty()) memcpy(p, v.data(), v.size());
 	return p;
 }
+
+// ---- what the result handles share (context.hpp: DeviceResult; result_build.hpp).  r: the handle's result, nullptr for a null
+// handle.  handle_get: *rows 0: no such buffer; *dev: its address, of a buffer without rows only where empty_has_address
+// (hry_render_get gives it, the others give NULL: DESIGN.md 7e)
+static int null_argument() { g_last_error = "null argument"; return HRY_E_ARG; }
+static int handle_get(const DeviceResult *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type, bool empty_has_address)
+{
+	if (!r || !name || !rows) return null_argument();
+	const NamedBuf *b = r->find(name);
+	*rows = b ? b->rows : 0;
+	if (dev) *dev = b && (b->rows || empty_has_address) ? b->p : nullptr;
+	if (width) *width = b ? b->width : 0;
+	if (type) *type = b ? b->type : 0;
+	return HRY_OK;
+}
+// what: what the handle calls a buffer, for the refusals; same_device: refuse a result on another device than the context's
+static int handle_copy(hry_ctx *ctx, const DeviceResult *r, const char *name, const char *what, void *dst, int dst_is_device, bool same_device)
+{
+	if (!ctx || !r || !name) return null_argument();
+	return guarded([&] { result_copy(ctx->cx, *r, name, what, dst, dst_is_device != 0, same_device); });
+}
+template <class R> static int handle_stat(const R *r, double *device_ms, uint64_t *uploaded_bytes)
+{
+	if (!r) return null_argument();
+	if (device_ms) *device_ms = r->device_ms;
+	if (uploaded_bytes) *uploaded_bytes = r->uploaded_bytes;
+	return HRY_OK;
+}
+static int handle_summary(const TopologyResult *r, uint64_t *out, int n)
+{
+	if (!r || !out) return null_argument();
+	for (int i = 0; i < n; ++i) out[i] = r->summary[i];
+	return HRY_OK;
+}
+// a fresh handle H filled by build(H&); *out is NULL after every failure.  The builds leave the decode's token alone
+template <class H, class F> static int handle_build(hry_ctx *ctx, bool have_arguments, H **out, F build)
+{
+	if (out) *out = nullptr;
+	if (!ctx || !have_arguments || !out) return null_argument();
+	order_lost(ctx);
+	return guarded([&] {
+		std::unique_ptr<H> h(new H());
+		build(*h);
+		*out = h.release();
+	});
+}
+static const RenderResult *result_of(const hry_render *r) { return r ? &r->r : nullptr; }
+static const TopologyResult *result_of(const hry_edges *e) { return e ? &e->e : nullptr; }
+static const TopologyResult *result_of(const hry_shells *s) { return s ? &s->s : nullptr; }
+static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o : nullptr; }
+static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
+static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
 
 extern "C" {
 
@@ -627,174 +680,53 @@ int hry_range_encode_lht(hry_ctx *ctx, const uint64_t *lht, size_t n, uint8_t **
 	});
 }
 
-// ---- the named buffers of a result handle (context.hpp: DeviceResult).  *rows 0: no such buffer; *dev: its address, of a buffer
-// without rows only where empty_has_address (hry_render_get gives it, the other two give NULL: DESIGN.md 7e)
-static const NamedBuf *result_get(const DeviceResult &r, const char *name, const void **dev, uint64_t *rows, bool empty_has_address)
-{
-	const NamedBuf *b = r.find(name);
-	*rows = b ? b->rows : 0;
-	if (dev) *dev = b && (b->rows || empty_has_address) ? b->p : nullptr;
-	return b;
-}
-
 // ---- render-ready device buffers (render.cpp)
 int hry_render_build(hry_ctx *ctx, const hry_mesh *m, hry_render **out) { return hry_render_build_ex(ctx, m, 0, out); }
 int hry_render_build_ex(hry_ctx *ctx, const hry_mesh *m, uint32_t flags, hry_render **out)
 {
-	if (!ctx || !m || !out) { g_last_error = "null argument"; if (out) *out = nullptr; return HRY_E_ARG; }
-	*out = nullptr;
-	order_lost(ctx);
-	return guarded([&] {
-		std::unique_ptr<hry_render> r(new hry_render());
-		render_build(ctx->cx, m->m, flags, r->r);
-		*out = r.release();
-	});
+	return handle_build(ctx, m != nullptr, out, [&](hry_render &r) { render_build(ctx->cx, m->m, flags, r.r); });
 }
 uint32_t hry_render_nverts(const hry_render *r) { return r ? r->r.nverts : 0; }
 uint64_t hry_render_ntris(const hry_render *r) { return r ? r->r.ntris : 0; }
-int hry_render_get(const hry_render *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
-{
-	if (!r || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const NamedBuf *b = result_get(r->r, name, dev, rows, true);
-	if (width) *width = b ? b->width : 0;
-	if (type) *type = b ? b->type : 0;
-	return HRY_OK;
-}
-int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !r || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, r->r, name, "render buffer", dst, dst_is_device != 0, false); });
-}
-int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes)
-{
-	if (!r) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (device_ms) *device_ms = r->r.device_ms;
-	if (uploaded_bytes) *uploaded_bytes = r->r.uploaded_bytes;
-	return HRY_OK;
-}
+int hry_render_get(const hry_render *r, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(r), name, dev, rows, width, type, true); }
+int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(r), name, "render buffer", dst, dst_is_device, false); }
+int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(r), device_ms, uploaded_bytes); }
 void hry_render_free(hry_render *r) { delete r; }
 
-// ---- unique edges and adjacency of a render build (edges.cpp).  Like hry_render_build it leaves the decode's token alone
+// ---- unique edges and adjacency of a render build (edges.cpp)
 int hry_edges_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_edges **out)
 {
-	if (out) *out = nullptr;
-	if (!ctx || !m || !r || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	order_lost(ctx);
-	return guarded([&] {
-		std::unique_ptr<hry_edges> e(new hry_edges());
-		edges_build(ctx->cx, m->m, r->r, flags, e->e);
-		*out = e.release();
-	});
+	return handle_build(ctx, m && r, out, [&](hry_edges &e) { edges_build(ctx->cx, m->m, r->r, flags, e.e); });
 }
 uint64_t hry_edges_count(const hry_edges *e) { return e ? e->e.summary[0] : 0; }
-int hry_edges_get(const hry_edges *e, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
-{
-	if (!e || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const NamedBuf *b = result_get(e->e, name, dev, rows, false);
-	if (width) *width = b ? b->width : 0;
-	if (type) *type = b ? b->type : 0;
-	return HRY_OK;
-}
-int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !e || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, e->e, name, "edge buffer", dst, dst_is_device != 0, true); });
-}
-int hry_edges_summary(const hry_edges *e, uint64_t out[4])
-{
-	if (!e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	for (int i = 0; i < 4; ++i) out[i] = e->e.summary[i];
-	return HRY_OK;
-}
-int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes)
-{
-	if (!e) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (device_ms) *device_ms = e->e.device_ms;
-	if (uploaded_bytes) *uploaded_bytes = e->e.uploaded_bytes;
-	return HRY_OK;
-}
+int hry_edges_get(const hry_edges *e, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(e), name, dev, rows, width, type, false); }
+int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(e), name, "edge buffer", dst, dst_is_device, true); }
+int hry_edges_summary(const hry_edges *e, uint64_t out[4]) { return handle_summary(result_of(e), out, 4); }
+int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(e), device_ms, uploaded_bytes); }
 void hry_edges_free(hry_edges *e) { delete e; }
 
-// ---- shells of a render build behind its edges build (shells.cpp).  Like hry_edges_build it leaves the decode's token alone
+// ---- shells of a render build behind its edges build (shells.cpp)
 int hry_shells_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_shells **out)
 {
-	if (out) *out = nullptr;
-	if (!ctx || !m || !r || !e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	order_lost(ctx);
-	return guarded([&] {
-		std::unique_ptr<hry_shells> s(new hry_shells());
-		shells_build(ctx->cx, m->m, r->r, e->e, flags, s->s);
-		*out = s.release();
-	});
+	return handle_build(ctx, m && r && e, out, [&](hry_shells &s) { shells_build(ctx->cx, m->m, r->r, e->e, flags, s.s); });
 }
 uint64_t hry_shells_count(const hry_shells *s) { return s ? s->s.summary[0] : 0; }
-int hry_shells_get(const hry_shells *s, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
-{
-	if (!s || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const NamedBuf *b = result_get(s->s, name, dev, rows, false);
-	if (width) *width = b ? b->width : 0;
-	if (type) *type = b ? b->type : 0;
-	return HRY_OK;
-}
-int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !s || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, s->s, name, "shell buffer", dst, dst_is_device != 0, true); });
-}
-int hry_shells_summary(const hry_shells *s, uint64_t out[6])
-{
-	if (!s || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	for (int i = 0; i < 6; ++i) out[i] = s->s.summary[i];
-	return HRY_OK;
-}
-int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes)
-{
-	if (!s) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (device_ms) *device_ms = s->s.device_ms;
-	if (uploaded_bytes) *uploaded_bytes = s->s.uploaded_bytes;
-	return HRY_OK;
-}
+int hry_shells_get(const hry_shells *s, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(s), name, dev, rows, width, type, false); }
+int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(s), name, "shell buffer", dst, dst_is_device, true); }
+int hry_shells_summary(const hry_shells *s, uint64_t out[6]) { return handle_summary(result_of(s), out, 6); }
+int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(s), device_ms, uploaded_bytes); }
 void hry_shells_free(hry_shells *s) { delete s; }
 
-// ---- a consistent winding per patch of a render build behind its edges build (orient.cpp).  It leaves the decode's token alone
+// ---- a consistent winding per patch of a render build behind its edges build (orient.cpp)
 int hry_orient_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_orient **out)
 {
-	if (out) *out = nullptr;
-	if (!ctx || !m || !r || !e || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	order_lost(ctx);
-	return guarded([&] {
-		std::unique_ptr<hry_orient> o(new hry_orient());
-		orient_build(ctx->cx, m->m, r->r, e->e, flags, o->o);
-		*out = o.release();
-	});
+	return handle_build(ctx, m && r && e, out, [&](hry_orient &o) { orient_build(ctx->cx, m->m, r->r, e->e, flags, o.o); });
 }
 uint64_t hry_orient_count(const hry_orient *o) { return o ? o->o.summary[0] : 0; }
-int hry_orient_get(const hry_orient *o, const char *name, const void **dev, uint64_t *rows, int *width, int *type)
-{
-	if (!o || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	const NamedBuf *b = result_get(o->o, name, dev, rows, false);
-	if (width) *width = b ? b->width : 0;
-	if (type) *type = b ? b->type : 0;
-	return HRY_OK;
-}
-int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !o || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, o->o, name, "orientation buffer", dst, dst_is_device != 0, true); });
-}
-int hry_orient_summary(const hry_orient *o, uint64_t out[6])
-{
-	if (!o || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	for (int i = 0; i < 6; ++i) out[i] = o->o.summary[i];
-	return HRY_OK;
-}
-int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes)
-{
-	if (!o) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (device_ms) *device_ms = o->o.device_ms;
-	if (uploaded_bytes) *uploaded_bytes = o->o.uploaded_bytes;
-	return HRY_OK;
-}
+int hry_orient_get(const hry_orient *o, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(o), name, dev, rows, width, type, false); }
+int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(o), name, "orientation buffer", dst, dst_is_device, true); }
+int hry_orient_summary(const hry_orient *o, uint64_t out[6]) { return handle_summary(result_of(o), out, 6); }
+int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(o), device_ms, uploaded_bytes); }
 void hry_orient_free(hry_orient *o) { delete o; }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
@@ -822,17 +754,8 @@ int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)
 		*out = o.release();
 	});
 }
-int hry_order_get(const hry_order *o, const char *name, const void **dev, uint64_t *rows)
-{
-	if (!o || !o->o || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	result_get(*o->o, name, dev, rows, false);
-	return HRY_OK;
-}
-int hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !o || !o->o || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, *o->o, name, "numbering map", dst, dst_is_device != 0, true); });
-}
+int hry_order_get(const hry_order *o, const char *name, const void **dev, uint64_t *rows) { return handle_get(result_of(o), name, dev, rows, nullptr, nullptr, false); }
+int hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(o), name, "numbering map", dst, dst_is_device, true); }
 int hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
                     uint64_t row_bytes, uint64_t dst_rows)
 {
@@ -845,14 +768,7 @@ void hry_order_free(hry_order *o) { delete o; }
 // alone: b stays what the context holds, for this build and for a render build after it
 int hry_distortion_build(hry_ctx *ctx, const hry_mesh *a, const hry_mesh *b, const hry_order *o, uint32_t flags, hry_distortion **out)
 {
-	if (out) *out = nullptr;
-	if (!ctx || !a || !b || !out || (o && !o->o)) { g_last_error = "null argument"; return HRY_E_ARG; }
-	order_lost(ctx);
-	return guarded([&] {
-		std::unique_ptr<hry_distortion> d(new hry_distortion());
-		distortion_build(ctx->cx, a->m, b->m, o ? o->o.get() : nullptr, flags, d->d);
-		*out = d.release();
-	});
+	return handle_build(ctx, a && b && !(o && !o->o), out, [&](hry_distortion &d) { distortion_build(ctx->cx, a->m, b->m, result_of(o), flags, d.d); });
 }
 int hry_distortion_component(const hry_distortion *d, int l, int c, hry_comp_error *out)
 {
@@ -876,24 +792,9 @@ int hry_distortion_normals(const hry_distortion *d, hry_normal_error *out)
 	if (out->list < 0) g_last_error = d->d.nrm_why;
 	return HRY_OK;
 }
-int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows)
-{
-	if (!d || !name || !rows) { g_last_error = "null argument"; return HRY_E_ARG; }
-	result_get(d->d, name, dev, rows, false);
-	return HRY_OK;
-}
-int hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device)
-{
-	if (!ctx || !d || !name) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { result_copy(ctx->cx, d->d, name, "distortion buffer", dst, dst_is_device != 0, true); });
-}
-int hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes)
-{
-	if (!d) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (device_ms) *device_ms = d->d.device_ms;
-	if (uploaded_bytes) *uploaded_bytes = d->d.uploaded_bytes;
-	return HRY_OK;
-}
+int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows) { return handle_get(result_of(d), name, dev, rows, nullptr, nullptr, false); }
+int hry_distortion_copy(hry_ctx *ctx, const hry_distortion *d, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(d), name, "distortion buffer", dst, dst_is_device, true); }
+int hry_distortion_stat(const hry_distortion *d, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(d), device_ms, uploaded_bytes); }
 void hry_distortion_free(hry_distortion *d) { delete d; }
 
 // ---- the error of every quantisation width, and widths from tolerances (sweep.cpp).  With the bounds known it leaves the

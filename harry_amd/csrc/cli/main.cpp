@@ -305,13 +305,24 @@ struct Handles {   // released on every path
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
 	std::vector<uint8_t*> bufs;
-	~Handles()
+	// the render build of the mesh and the edges build behind it; what was built from them goes with them
+	void build_adjacency()
 	{
-		for (uint8_t *b : bufs) hry_free(b);
+		ok(hry_render_build(cx[0], mesh, &render));
+		ok(hry_edges_build(cx[0], mesh, render, 0, &edges));
+	}
+	void drop_adjacency()
+	{
 		if (orient) hry_orient_free(orient);
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
+		orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
+	}
+	~Handles()
+	{
+		for (uint8_t *b : bufs) hry_free(b);
+		drop_adjacency();
 		if (dist) hry_distortion_free(dist);
 		if (sweep) hry_quant_sweep_free(sweep);
 		if (rate) hry_rate_sweep_free(rate);
@@ -549,20 +560,17 @@ int run(const Args &args)
 	}
 
 	if (args.topology) {
-		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
-		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		h.build_adjacency();
 		uint64_t s[4];
 		ok(hry_edges_summary(h.edges, s));
 		const long long V = hry_mesh_nv(h.mesh), F = hry_mesh_nf(h.mesh);
 		std::cout << "Topology: vertices " << V << " faces " << F << " triangles " << hry_mesh_ntri(h.mesh) << " edges " << s[0] << " boundary " << s[1] << " manifold " << s[2]
 		          << " nonmanifold " << s[3] << " euler " << V - (long long)s[0] + F << std::endl;
-		hry_edges_free(h.edges); h.edges = nullptr;
-		hry_render_free(h.render); h.render = nullptr;
+		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
 	if (args.shells) {
-		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
-		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		h.build_adjacency();
 		ok(hry_shells_build(h.cx[0], h.mesh, h.render, h.edges, 0, &h.shells));
 		uint64_t s[6];
 		ok(hry_shells_summary(h.shells, s));
@@ -578,14 +586,11 @@ int run(const Args &args)
 			else std::cout << (2 - euler - (long long)k[7]) / 2;
 			std::cout << std::endl;
 		}
-		hry_shells_free(h.shells); h.shells = nullptr;
-		hry_edges_free(h.edges); h.edges = nullptr;
-		hry_render_free(h.render); h.render = nullptr;
+		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
 	if (args.orient) {
-		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
-		ok(hry_edges_build(h.cx[0], h.mesh, h.render, 0, &h.edges));
+		h.build_adjacency();
 		ok(hry_orient_build(h.cx[0], h.mesh, h.render, h.edges, HRY_ORIENT_MAJORITY | (args.orient_outward ? HRY_ORIENT_OUTWARD : 0u), &h.orient));
 		uint64_t s[6];
 		ok(hry_orient_summary(h.orient, s));
@@ -597,9 +602,7 @@ int run(const Args &args)
 			ok(hry_mesh_flip_faces(h.mesh, flip.data(), &turned));
 			hry_mesh_free(h.mesh); h.mesh = turned;
 		}
-		hry_orient_free(h.orient); h.orient = nullptr;
-		hry_edges_free(h.edges); h.edges = nullptr;
-		hry_render_free(h.render); h.render = nullptr;
+		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
 	if ((args.topology || args.shells || args.orient) && args.out.empty()) {

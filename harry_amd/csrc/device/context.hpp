@@ -260,38 +260,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 // opens the refusals' text (HRY_E_UNSUPPORTED)
 size_t render_position_list(const Mesh &m, const char *what);   // (render.cpp: position_list)
 
-// edges.cpp: unique edges and adjacency of a render build's triangles (include/harry_amd.h: hry_edges_build); the result owns its memory
-struct EdgesResult : DeviceResult {
-	uint64_t summary[4] = {};   // E, edges with one side, with two, with more
-	double device_ms = 0;
-	uint64_t uploaded_bytes = 0;
-};
-void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out);   // flags: HRY_EDGES_*
-// r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise (edges.cpp)
-void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r);
-// the float rows of r's position list, from its first position component; stride: floats a row.  `what` as render_position_list's
-const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride);
-
-// shells.cpp: the shells of a render build's triangles behind its edges build (include/harry_amd.h: hry_shells_build); the result
-// owns its memory
-struct ShellsResult : DeviceResult {
-	uint64_t summary[6] = {};   // S, closed, nonmanifold, misoriented shells, loops, triangles of the largest
-	double device_ms = 0;
-	uint64_t uploaded_bytes = 0;
-};
-void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out);   // flags: HRY_SHELLS_*
-// e is an edges build of (m, r) on cx's device, r a render build of m: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise (shells.cpp)
-struct EdgesFit { const NamedBuf *tri_edges, *offsets, *sides; uint32_t ne; };
-EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e);
-
-// orient.cpp: a consistent winding per patch of a render build's triangles behind its edges build (include/harry_amd.h:
-// hry_orient_build); the result owns its memory
-struct OrientResult : DeviceResult {
-	uint64_t summary[6] = {};   // P, orientable patches, flipped triangles, inverted patches, against edges, against edges remaining
-	double device_ms = 0;
-	uint64_t uploaded_bytes = 0;
-};
-void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, OrientResult &out);   // flags: HRY_ORIENT_*
+// (the edges, shells and orient builds behind a render build: result_build.hpp)
 
 // every component of list L as hry_requant(clear) would leave it, for a kernel that reads the records in place (render.cpp): the
 // quantised ones dequantised, the others as they are.  More than 32 components: HRY_E_UNSUPPORTED; quantised without bounds: HRY_E_ARG

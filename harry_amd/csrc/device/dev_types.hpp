@@ -1,6 +1,8 @@
-// Plain structs shared between host launch code and HIP kernels.
+// Plain structs shared between host launch code and HIP kernels (the adjacency of a render build's triangles: tri_adjacency.hpp).
 #pragma once
 #include <cstdint>
+
+#include "tri_adjacency.hpp"
 
 namespace hry {
 namespace dev {
@@ -74,39 +76,46 @@ struct ShellVertexView {
 	uint32_t n, nout, mask;
 	uint32_t *table;
 };
-// shells.hip: what the kernels read of the render and edges builds and what they write.  n = 3 T sides, ne edges, ns shells (0
-// until they are counted); offsets[ne + 1] / sides[n]: the CSR of the edges' sides, every segment ascending; counts: ns rows of 8;
-// pos as in EdgesView, nullptr: no measures
-struct ShellsView {
-	const uint32_t *indices, *vsrc, *tri_face, *tri_edges, *offsets, *sides;
+// shells.hip: the adjacency it reads (tri_adjacency.hpp) and what it writes.  ns shells (0 until they are counted); counts: ns rows of 8
+struct ShellsView : TriAdjacency {
 	uint32_t *tri_shell, *face_shell, *edge_shell, *first, *counts;
-	const float *pos;
-	float *measures;
-	uint32_t n, ntri, nout, nf, ne, ns, pos_stride;
+	uint32_t ns;
 };
 // the working arrays of shells.hip, laid out by shells.cpp: par / flag [T], num [T + 1], sums: scan_sums_words(T) (it serves the
-// scan over the T flags and the one over the ns <= T counters); pair_id / pair_first_of: the ids and first_of of the corners'
-// numbering [3 T]; slot [3 T] filled with 0xff; loop_par [ne]; summary: 8 zeroed words; and for the measures partial [T] pairs of
-// doubles, pcount [ns] zeroed, pstart [ns + 1], pseg [T], box_lo / box_hi [ns, 3] filled with 0xff / 0, hubs: 1 +
-// shells_hub_capacity(T) words, the first zeroed
+// scan over the T flags and the measures' over the ns <= T counters); pair_id / pair_first_of: the ids and first_of of the corners'
+// numbering [3 T]; slot [3 T] filled with 0xff; loop_par [ne]; summary: 8 zeroed words
 struct ShellsWork {
 	uint32_t *par, *flag, *num, *sums, *pair_id, *slot, *loop_par, *summary;
 	const uint32_t *pair_first_of;
-	double *partial;
-	uint32_t *pcount, *pstart, *pseg, *box_lo, *box_hi, *hubs;
 };
-// orient.hip: what the kernels read of the render and edges builds and what they write.  n = 3 T sides, ne edges, np patches (0
-// until they are counted); counts: np rows of 8; oriented: T rows of 3
-struct OrientView {
-	const uint32_t *indices, *vsrc, *tri_face, *tri_edges, *offsets, *sides;
+// orient.hip: the adjacency it reads and what it writes.  np patches (0 until they are counted); counts: np rows of 8; oriented: T
+// rows of 3; measures: np rows of 8 as measures.hip leaves them, nullptr: none
+struct OrientView : TriAdjacency {
 	uint32_t *tri_patch, *tri_flip, *face_flip, *oriented, *first, *counts;
 	float *measures;
-	uint32_t n, ntri, nout, nf, ne, np;
+	uint32_t np;
 };
 // the working arrays of orient.hip, laid out by orient.cpp: par [2 T] (the double cover: node 2 t is triangle t as wound, 2 t + 1
 // turned), flag [T], num [T + 1], sums: scan_sums_words(T), turn [np] zeroed, summary: 8 zeroed words
 struct OrientWork {
 	uint32_t *par, *flag, *num, *sums, *turn, *summary;
+};
+// measures.hip: exactly what its kernels read and write.  indices: ntri rows of 3 output vertices; label[ntri]: the shell or patch
+// of every triangle, below nl; first[nl]: the lowest triangle of every label; pos: float rows of pos_stride floats whose first three
+// are an output vertex's position (nout rows); measures: nl rows of 8 (area, signed volume, min x y z, max x y z)
+struct MeasuresView {
+	const uint32_t *indices, *label, *first;
+	const float *pos;
+	float *measures;
+	uint32_t ntri, nout, nl, pos_stride;
+};
+// ... and their scratch (kernels.hpp: measures_reserve / measures_bind / measures_clear): flag [T] and sums, scan_sums_words(T),
+// lent by the caller; partial [T] pairs of doubles, pcount [nl] zeroed, pstart [nl + 1], pseg [T], box_lo / box_hi [nl, 3] filled
+// with 0xff / 0, hubs: 1 + shells_hub_capacity(T) words, the first zeroed
+struct MeasuresWork {
+	uint32_t *flag, *sums;
+	double *partial;
+	uint32_t *pcount, *pstart, *pseg, *box_lo, *box_hi, *hubs;
 };
 // render.hip: which record of one list every output row names.  Row u -> element src[u] (or u) -> the region of efc[element]
 // (or of the element) -> slot[region] (-1: unbound) -> attr[element * nb + slot]

@@ -4,38 +4,11 @@
 // which list that is and what the render's sizes must be.  The decode's token and the encoder's resident mesh are left alone.
 #include <hip/hip_runtime.h>
 
-#include "context.hpp"
-#include "kernels.hpp"
+#include "result_build.hpp"
 
 namespace hry {
 
 using namespace dev;
-
-void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r)
-{
-	if (r.block.device != cx.device) throw Error(HRY_E_ARG, "the render buffers live on another device than the context's");
-	// ---- is r a render build of m?  T, nf and U as render_build computes them
-	bool unweld = false;
-	if (m.general) for (int g = 0; g < m.bind.nregs_face(); ++g) unweld |= m.bind.ncornerlists(g) > 0;
-	const uint64_t ntri = m.ntri();
-	const uint32_t nout = r.nverts;
-	const NamedBuf *b_idx = r.find("indices"), *b_vsrc = r.find("vertex_source"), *b_face = r.find("tri_face"), *b_reg = r.find("face_region");
-	const bool fits = b_idx && b_vsrc && b_face && r.ntris == ntri && b_idx->rows == ntri && b_idx->width == 3 && b_face->rows == ntri && b_vsrc->rows == nout &&
-	                  (unweld ? (m.ne() ? nout >= 1 && nout <= m.ne() : nout == 0) : nout == m.nv) && (!m.general || (b_reg && b_reg->rows == m.nf)) &&
-	                  (r.find("corner_source") != nullptr) == unweld;
-	if (!fits) throw Error(HRY_E_ARG, "the render buffers are not a render build of this mesh (vertices, triangles or faces differ)");
-	if (3 * ntri > (1ull << 31)) throw Error(HRY_E_UNSUPPORTED, "more than 2^31 triangle sides");
-}
-
-const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride)
-{
-	const size_t pl = render_position_list(m, what);
-	const NamedBuf *b_pos = r.find("list" + std::to_string(pl));
-	const size_t at = (size_t)m.lists[pl].interp_off[0];
-	if (!b_pos || b_pos->rows != r.nverts || b_pos->type != HRY_FLOAT || (size_t)b_pos->width < at + 3) throw Error(HRY_E_ARG, "the render buffers do not hold this mesh's position list");
-	stride = (uint32_t)b_pos->width;
-	return (const float*)b_pos->p + at;
-}
 
 void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out)
 {
@@ -61,39 +34,35 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	void *wb = cx.d_edges.p;
 	D.bind(W, wb);
 	hipStream_t st = cx.stream;
-	TimedEvent ev[4];
+	StretchTimer timer;
 
 	EdgeView u{};
 	u.indices = (const uint32_t*)b_idx->p; u.vsrc = (const uint32_t*)b_vsrc->p; u.nout = nout;
 	if (n) HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));   // (the fills lie outside the events, as in render.cpp)
-	HIP_OK(hipEventRecord(ev[0], st));
+	timer.mark(st);
 	if (n) launch_dedup_count(st, u, D);
-	HIP_OK(hipEventRecord(ev[1], st));
+	timer.mark(st);
 	uint32_t ne = 0;
 	if (n) HIP_OK(hipMemcpyAsync(&ne, D.total(), 4, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
 	if (ne > n || (n && !ne)) throw Error(HRY_E_INTERNAL, "edges: the numbering does not fit the sides");
 
 	// ---- the outputs, in one allocation
-	Carve O;
-	struct Plan { const char *name; uint64_t rows; int width, type; size_t slot; };
-	std::vector<Plan> plan;
-	auto add = [&](const char *name, uint64_t rows, int width, int type) { plan.push_back(Plan{ name, rows, width, type, O.reserve((size_t)rows * width * 4) }); };
-	add("edges", ne, 2, HRY_UINT);
-	add("tri_edges", ntri, 3, HRY_UINT);
-	add("edge_offsets", (uint64_t)ne + 1, 1, HRY_UINT);
-	add("edge_sides", n, 1, HRY_UINT);
-	add("tri_neighbours", ntri, 3, HRY_UINT);
-	if (geometry) { add("edge_length", ne, 1, HRY_FLOAT); add("edge_cot", ne, 1, HRY_FLOAT); add("edge_cos", ne, 1, HRY_FLOAT); }
-	out.block.alloc(cx.device, O.total);
-	for (const Plan &p : plan) out.bufs.push_back(NamedBuf{ p.name, O.ptr<void>(out.block.p, p.slot), p.rows, p.width, p.type });
+	OutputPlan plan;
+	plan.add("edges", ne, 2, HRY_UINT);
+	plan.add("tri_edges", ntri, 3, HRY_UINT);
+	plan.add("edge_offsets", (uint64_t)ne + 1, 1, HRY_UINT);
+	plan.add("edge_sides", n, 1, HRY_UINT);
+	plan.add("tri_neighbours", ntri, 3, HRY_UINT);
+	if (geometry) { plan.add("edge_length", ne, 1, HRY_FLOAT); plan.add("edge_cot", ne, 1, HRY_FLOAT); plan.add("edge_cos", ne, 1, HRY_FLOAT); }
+	plan.alloc(cx.device, out);
 	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
 
 	uint32_t *count = W.ptr<uint32_t>(wb, w_count), *classes = W.ptr<uint32_t>(wb, w_classes);
 	if (ne) HIP_OK(hipMemsetAsync(count, 0, (size_t)ne * 4, st));
 	HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_hubs), 0, 4, st));
 	HIP_OK(hipMemsetAsync(classes, 0, 16, st));
-	HIP_OK(hipEventRecord(ev[2], st));
+	timer.mark(st);
 	D.ids = dst("tri_edges");   // the numbering's ids are the buffer itself
 	launch_dedup_assign(st, D, 0, nullptr);
 	EdgesView v{};
@@ -105,14 +74,11 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 		v.length = (float*)dst("edge_length"); v.cot = (float*)dst("edge_cot"); v.cos = (float*)dst("edge_cos");
 	}
 	launch_edges(st, v, count, W.ptr<uint32_t>(wb, w_sums), W.ptr<uint32_t>(wb, w_hubs), classes);
-	HIP_OK(hipEventRecord(ev[3], st));
+	timer.mark(st);
 	uint32_t cls[3] = {};
 	HIP_OK(hipMemcpyAsync(cls, classes, 12, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
-	float a = 0, c = 0;
-	HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-	HIP_OK(hipEventElapsedTime(&c, ev[2], ev[3]));
-	out.device_ms = (double)a + (double)c;
+	out.device_ms = timer.ms();
 	out.uploaded_bytes = 0;
 	out.summary[0] = ne; out.summary[1] = cls[0]; out.summary[2] = cls[1]; out.summary[3] = cls[2];
 }

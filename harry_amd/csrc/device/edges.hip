@@ -26,7 +26,6 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kNoElement = 0xffffffffu;
 constexpr uint32_t kEdgeSegMax = 32;
 
 struct D3 { double x, y, z; };

@@ -221,24 +221,30 @@ void launch_edges(hipStream_t st, const EdgesView &v, uint32_t *count, uint32_t 
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the
 // outputs allocated, counts zeroed, face_shell filled with 0xff): tri_shell, face_shell, shell_first, the triangle and face columns.
 // launch_shells_counts, behind the numbering of the corners by (shell, decoded vertex) (w.pair_id, w.pair_first_of): edge_shell, the
-// other six columns, and the five reductions of the summary behind S (w.summary: closed, nonmanifold, misoriented, loops, largest).
-// launch_shells_measures: shell_measures
-uint32_t shells_hub_capacity(uint32_t ntri);
+// other six columns, and the five reductions of the summary behind S (w.summary: closed, nonmanifold, misoriented, loops, largest)
 void launch_shells_roots(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 void launch_shells_label(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 void launch_shells_counts(hipStream_t st, const ShellsView &v, const ShellsWork &w);
-void launch_shells_measures(hipStream_t st, const ShellsView &v, const ShellsWork &w);
 
 // consistent winding per patch of a render build (orient.hip; driver: orient.cpp), behind its edges build.  launch_orient_roots: the
 // union-find over the orientation double cover, the root flags and their scan: w.num[T] = the number of patches, on the device.
 // launch_orient_flips (v.np known, the outputs allocated, counts / face_flip / w.turn zeroed): every integer buffer, the flips
-// relative to each patch's lowest triangle, inverted by majority where asked.  launch_orient_outward, behind launch_shells_measures
-// over the patches and oriented_indices (v.measures): closed orientable patches of negative volume turned as a whole.
+// relative to each patch's lowest triangle, inverted by majority where asked.  launch_orient_outward, behind launch_measures over
+// the patches and oriented_indices (v.measures): closed orientable patches of negative volume turned as a whole.
 // launch_orient_summary: the five reductions of the summary behind P (w.summary: orientable, flipped, inverted, against, remaining)
 void launch_orient_roots(hipStream_t st, const OrientView &v, const OrientWork &w);
 void launch_orient_flips(hipStream_t st, const OrientView &v, const OrientWork &w, bool majority);
 void launch_orient_outward(hipStream_t st, const OrientView &v, const OrientWork &w);
 void launch_orient_summary(hipStream_t st, const OrientView &v, const OrientWork &w);
+
+// area, signed volume and box per label -- a shell, a patch -- of a render build's triangles (measures.hip; drivers: shells.cpp,
+// orient.cpp).  The scratch: measures_reserve its seven arrays in a Carve for T triangles (the first piece comes back),
+// measures_bind them behind the allocation, with the caller's flag [T] and sums (free by then), measures_clear them for nl labels
+uint32_t shells_hub_capacity(uint32_t ntri);
+size_t measures_reserve(Carve &W, uint32_t ntri);
+MeasuresWork measures_bind(const Carve &W, void *base, size_t first, uint32_t *flag, uint32_t *sums);
+void measures_clear(hipStream_t st, const MeasuresWork &w, uint32_t nl);
+void launch_measures(hipStream_t st, const MeasuresView &v, const MeasuresWork &w);
 
 // per-component error of one mesh against another (distortion.hip; driver: distortion.cpp).  launch_distortion_rows: one DistPart
 // per block of kDistBlockRows rows and slot (pa.n components, then the positions when L.pos >= 0) into L.part; a map entry at or

@@ -1,22 +1,22 @@
 // Consistent winding of a render build's triangles, patch by patch (driver: orient.cpp; contract: include/harry_amd.h,
-// hry_orient_build; DESIGN.md 7a, "Orientation").  The adjacency is the edges build's, as in shells.hip.  A relation joins two
-// triangles and says whether they agree (along) or one of them has to be turned (against): a joining edge -- exactly two sides, in
+// hry_orient_build; DESIGN.md 7a, "Orientation").  The adjacency is the edges build's (tri_adjacency.hpp), as in shells.hip.  A
+// relation joins two triangles and says whether they agree (along) or one of them has to be turned (against): a joining edge -- exactly two sides, in
 // two triangles, between two different decoded vertices -- or two consecutive fan triangles of one face, which are always along.
 // The unknown flips are found by a union-find over the orientation double cover: node 2 t is triangle t as wound, node 2 t + 1 the
 // same triangle turned.  Along unites (2 a, 2 b) and (2 a + 1, 2 b + 1), against (2 a, 2 b + 1) and (2 a + 1, 2 b).  The root of a set
 // is its smallest member (union_find.hpp), so with t0 the lowest triangle of t's patch find(2 t) is 2 t0 or 2 t0 + 1 -- the low bit
 // is t's flip relative to t0 -- and the patch cannot be oriented iff 2 t0 + 1 hangs under 2 t0.  No parity travels through a
 // concurrent path compression and nothing depends on the order atomics complete in.  wave64, 256 threads a block.
-//   k_or_hook_local / k_or_hook  the relations of a side (its joining edge, taken by the edge's second side) and of a triangle (the
-//                              next triangle of its face) -- first inside a workgroup's 4096 triangles (8192 nodes) in LDS, then, for
-//                              those that leave them, in HBM
-//   k_or_roots + k_scan_*      root flags of the even nodes and their exclusive scan: dense patch numbers in order of the lowest triangle
+//   k_hook_local / k_hook<CoverGraph>  (hook.hpp) the relations of a side (its joining edge, taken by the edge's second side) and of a
+//                              triangle (the next triangle of its face) -- first inside a workgroup's 4096 triangles (8192 nodes) in
+//                              LDS, then, for those that leave them, in HBM
+//   k_hook_roots + k_scan_*    root flags of the even nodes and their exclusive scan: dense patch numbers in order of the lowest triangle
 //   k_or_label                 a lane per triangle: walks 2 t to its root (the unions are over): tri_patch, the relative flip,
 //                              patch_first, orientable; triangles, faces and relatively flipped triangles per patch
 //   k_or_decide                a lane per patch, HRY_ORIENT_MAJORITY: more than half flipped turns the patch
 //   k_or_apply                 a lane per triangle: tri_flip, face_flip, oriented_indices; flipped faces per patch
 //   k_or_sides                 a lane per side: open sides and against edges per patch
-//   (launch_shells_measures of shells.hip, over the patches and oriented_indices: patch_measures)
+//   (launch_measures of measures.hip, over the patches and oriented_indices: patch_measures)
 //   k_or_outward               a lane per patch, HRY_ORIENT_OUTWARD: a closed orientable patch of negative volume is inverted
 //   k_or_turn                  a lane per triangle: the triangles of the inverted patches turned once more
 //   k_or_summary               a lane per patch: the five reductions of hry_orient_summary behind P
@@ -24,8 +24,8 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_types.hpp"
+#include "hook.hpp"
 #include "kernels.hpp"
-#include "union_find.hpp"
 #include "wave.hpp"
 #include "wave_counter.hpp"
 
@@ -34,105 +34,45 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kNoElement = 0xffffffffu;
 enum : uint32_t { kColTri, kColFace, kColFlipped, kColFlippedFaces, kColAgainst, kColOpen, kColOrientable, kColInverted };
 
-__device__ __forceinline__ uint32_t vertex_of(const OrientView &v, uint32_t u) { return u < v.nout ? v.vsrc[u] : kNoElement; }
-__device__ __forceinline__ uint32_t next_corner(uint32_t s) { return s % 3 == 2 ? s - 2 : s + 1; }
-
 // the two sides s0 < s1 of the edge of side s, where it has exactly two, in two triangles, and s is one of them
-__device__ __forceinline__ bool edge_pair(const OrientView &v, uint32_t s, uint32_t &s0, uint32_t &s1)
+__device__ __forceinline__ bool edge_pair(const TriAdjacency &v, uint32_t s, uint32_t &s0, uint32_t &s1)
 {
-	const uint32_t e = v.tri_edges[s];
-	if (e >= v.ne) return false;
-	const uint32_t b = v.offsets[e], end = v.offsets[e + 1];
-	if (end > v.n || end < 2 || b != end - 2) return false;   // one side, or more than two
+	uint32_t b, end;
+	if (!side_segment(v, v.tri_edges[s], b, end) || end < 2 || b != end - 2) return false;   // one side, or more than two
 	s0 = v.sides[b]; s1 = v.sides[b + 1];
 	return s0 < v.n && s1 < v.n && s0 / 3 != s1 / 3 && (s == s0 || s == s1);
 }
-// ... do they join?  false: the ends coincide.  against: both run from the same decoded vertex to the same
-__device__ __forceinline__ bool pair_joins(const OrientView &v, uint32_t s0, uint32_t s1, bool &against)
+// ... do they join?  false: the ends of the edge coincide.  against: both run the same way
+__device__ __forceinline__ bool pair_joins(const TriAdjacency &v, uint32_t s0, uint32_t s1, bool &against)
 {
-	const uint32_t a0 = vertex_of(v, v.indices[s0]), b0 = vertex_of(v, v.indices[next_corner(s0)]);
-	if (a0 == b0) return false;
-	against = a0 == vertex_of(v, v.indices[s1]) && b0 == vertex_of(v, v.indices[next_corner(s1)]);
+	if (vertex_of(v, v.indices[s0]) == vertex_of(v, v.indices[next_corner(s0)])) return false;
+	against = same_direction(v, s0, s1);
 	return true;
 }
 // is the edge of side s a joining edge?
-__device__ __forceinline__ bool joining_edge(const OrientView &v, uint32_t s, uint32_t &s0, uint32_t &s1, bool &against)
+__device__ __forceinline__ bool joining_edge(const TriAdjacency &v, uint32_t s, uint32_t &s0, uint32_t &s1, bool &against)
 {
 	return edge_pair(v, s, s0, s1) && pair_joins(v, s0, s1, against);
 }
 
-// the relation side s is in charge of: the joining edge it is the second side of (a first side stops before the vertices)
-__device__ __forceinline__ bool side_relation(const OrientView &v, uint32_t s, uint32_t &other, bool &against)
-{
-	uint32_t s0, s1;
-	if (!edge_pair(v, s, s0, s1) || s != s1 || !pair_joins(v, s0, s1, against)) return false;
-	other = s0 / 3;
-	return true;
-}
-// ... triangle t is in charge of: the next triangle of its face, along
-__device__ __forceinline__ bool same_face_next(const OrientView &v, uint32_t t) { return t + 1 < v.ntri && v.tri_face[t] == v.tri_face[t + 1]; }
-
 }   // namespace
 
-constexpr uint32_t kCoverTris = 4096, kCoverThreads = 1024;   // 8192 nodes: 32 KB of parents in LDS
-__device__ __forceinline__ void lds_relate(uint32_t *l_par, uint32_t a, uint32_t b, bool against)
-{
-	lds_unite(l_par, 2 * a, 2 * b + (against ? 1u : 0u));
-	lds_unite(l_par, 2 * a + 1, 2 * b + (against ? 0u : 1u));
-}
-__device__ __forceinline__ void uf_relate(uint32_t *par, uint32_t a, uint32_t b, bool against)
-{
-	uf_unite(par, 2 * a, 2 * b + (against ? 1u : 0u));
-	uf_unite(par, 2 * a + 1, 2 * b + (against ? 0u : 1u));
-}
-
-// Every word of par is written here (as k_sh_hook_local of shells.hip, over twice the nodes)
-__global__ __launch_bounds__(kCoverThreads) void k_or_hook_local(OrientView v, uint32_t *par)
-{
-	__shared__ uint32_t l_par[2 * kCoverTris];
-	const uint32_t base = blockIdx.x * kCoverTris;
-	for (uint32_t i = threadIdx.x; i < 2 * kCoverTris; i += kCoverThreads) l_par[i] = i;
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < kCoverTris; i += kCoverThreads) {
-		const uint32_t t = base + i;
-		if (t >= v.ntri) break;
-		for (uint32_t k = 0; k < 3; ++k) {
-			uint32_t o;
-			bool against;
-			if (!side_relation(v, 3 * t + k, o, against)) continue;
-			if (o >= v.ntri || o - base >= kCoverTris) continue;   // it leaves the workgroup's triangles: the second pass
-			lds_relate(l_par, i, o - base, against);
-		}
-		if (i + 1 < kCoverTris && same_face_next(v, t)) lds_relate(l_par, i, i + 1, false);
+// the double cover, two nodes a triangle (hook.hpp)
+struct CoverGraph {
+	static constexpr uint32_t kNodes = 2;
+	// the relation side s is in charge of: the joining edge it is the second side of (a first side stops before the vertices)
+	static __device__ __forceinline__ bool side_relation(const TriAdjacency &v, uint32_t s, uint32_t &other, bool &against)
+	{
+		uint32_t s0, s1;
+		if (!edge_pair(v, s, s0, s1) || s != s1 || !pair_joins(v, s0, s1, against)) return false;
+		other = s0 / 3;
+		return true;
 	}
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < 2 * kCoverTris; i += kCoverThreads) {   // (the unions are over: a root read is final)
-		if (base + i / 2 >= v.ntri) break;
-		uint32_t x = i, q = l_par[x];
-		while (q != x) { x = q; q = l_par[x]; }
-		par[2 * (size_t)base + i] = 2 * base + x;   // (2 base is even: a node keeps its low bit)
-	}
-}
-
-__global__ __launch_bounds__(256) void k_or_hook(OrientView v, uint32_t *par)
-{
-	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-	if (s >= v.n) return;
-	const uint32_t t = s / 3, base = t - t % kCoverTris;
-	uint32_t o;
-	bool against;
-	if (side_relation(v, s, o, against) && o < v.ntri && o - base >= kCoverTris) uf_relate(par, t, o, against);
-	if (s % 3 == 0 && t + 1 - base >= kCoverTris && same_face_next(v, t)) uf_relate(par, t, t + 1, false);
-}
-
-__global__ __launch_bounds__(256) void k_or_roots(const uint32_t *par, uint32_t ntri, uint32_t *flag)
-{
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < ntri) flag[t] = par[2 * (size_t)t] == 2 * t ? 1u : 0u;
-}
+	// ... triangle t is in charge of: the next triangle of its face, along
+	static __device__ __forceinline__ bool next_relation(const TriAdjacency &v, uint32_t t) { return t + 1 < v.ntri && v.tri_face[t] == v.tri_face[t + 1]; }
+};
 
 // (the unions are over: the walk reads final parents with plain loads and stores nothing into par)
 __global__ __launch_bounds__(256) void k_or_label(OrientView v, const uint32_t *par, const uint32_t *num)
@@ -271,15 +211,7 @@ __global__ __launch_bounds__(256) void k_or_summary(const uint32_t *counts, uint
 }
 
 // ---- launchers
-void launch_orient_roots(hipStream_t st, const OrientView &v, const OrientWork &w)
-{
-	if (v.ntri) {
-		hipLaunchKernelGGL(k_or_hook_local, dim3(blocks_for(v.ntri, kCoverTris)), dim3(kCoverThreads), 0, st, v, w.par);
-		hipLaunchKernelGGL(k_or_hook, dim3(blocks_for(v.n, 256)), dim3(256), 0, st, v, w.par);
-		hipLaunchKernelGGL(k_or_roots, dim3(blocks_for(v.ntri, 256)), dim3(256), 0, st, (const uint32_t*)w.par, v.ntri, w.flag);
-	}
-	launch_excl_scan(st, w.flag, v.ntri, w.sums, w.num);
-}
+void launch_orient_roots(hipStream_t st, const OrientView &v, const OrientWork &w) { launch_hook_roots<CoverGraph>(st, v, w.par, w.flag, w.sums, w.num); }
 
 void launch_orient_flips(hipStream_t st, const OrientView &v, const OrientWork &w, bool majority)
 {

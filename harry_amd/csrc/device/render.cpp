@@ -12,8 +12,7 @@
 #include <atomic>
 #include <cstring>
 
-#include "context.hpp"
-#include "kernels.hpp"
+#include "result_build.hpp"
 
 namespace hry {
 
@@ -203,7 +202,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	put(w_small, small.data(), small.size() * 4);
 	const int32_t *d_small = W.ptr<int32_t>(wb, w_small);
 
-	TimedEvent ev[4];
+	StretchTimer timer;
 
 	// ---- unweld: the number of output vertices comes down before the outputs are allocated (no corners: none).  The events
 	// enclose kernels only: the table's fill and every copy lie outside them
@@ -215,34 +214,28 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 		u.nf = nf; u.nregs = (uint32_t)b.nregs_face(); u.nlists = ncl; u.nb_corner = (uint32_t)b.nb_corner;
 		HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));   // (launch_dedup_count gives u the plan's table, mask and count)
 	}
-	HIP_OK(hipEventRecord(ev[0], st));
+	timer.mark(st);
 	if (unweld && ne) {
 		launch_edge_faces(st, foff, nf, eface);
 		launch_dedup_count(st, u, D);
 	}
-	HIP_OK(hipEventRecord(ev[1], st));
+	timer.mark(st);
 	if (unweld && ne) HIP_OK(hipMemcpyAsync(&nout, D.total(), 4, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
 	if (nout > ne && unweld) throw Error(HRY_E_INTERNAL, "unweld: more output vertices than corners");
 
 	// ---- the outputs, in one allocation
-	Carve O;
-	struct Plan { std::string name; uint64_t rows; int width, type; size_t slot; };
-	std::vector<Plan> plan;
-	auto add = [&](const std::string &name, uint64_t rows, int width, int type) {
-		plan.push_back(Plan{ name, rows, width, type, O.reserve((size_t)rows * width * (type == HRY_USHORT ? 2 : 4)) });
-	};
-	add("indices", ntri, 3, HRY_UINT);
-	add("tri_face", ntri, 1, HRY_UINT);
-	add("vertex_source", nout, 1, HRY_UINT);
-	if (unweld) add("corner_source", nout, 1, HRY_UINT);
-	if (general) add("face_region", nf, 1, HRY_USHORT);
+	OutputPlan plan;
+	plan.add("indices", ntri, 3, HRY_UINT);
+	plan.add("tri_face", ntri, 1, HRY_UINT);
+	plan.add("vertex_source", nout, 1, HRY_UINT);
+	if (unweld) plan.add("corner_source", nout, 1, HRY_UINT);
+	if (general) plan.add("face_region", nf, 1, HRY_USHORT);
 	for (size_t l = 0; l < nl; ++l)
-		if (rendered(m.lists[l])) add("list" + std::to_string(l), m.lists[l].target == 0 ? nf : nout, m.lists[l].ncomp(), HRY_FLOAT);
-	if (want_vn) add("normals", nout, 3, HRY_FLOAT);
-	if (want_fn) add("face_normals", nf, 3, HRY_FLOAT);
-	out.block.alloc(cx.device, O.total);
-	for (const Plan &p : plan) out.bufs.push_back(NamedBuf{ p.name, O.ptr<void>(out.block.p, p.slot), p.rows, p.width, p.type });
+		if (rendered(m.lists[l])) plan.add("list" + std::to_string(l), m.lists[l].target == 0 ? nf : nout, m.lists[l].ncomp(), HRY_FLOAT);
+	if (want_vn) plan.add("normals", nout, 3, HRY_FLOAT);
+	if (want_fn) plan.add("face_normals", nf, 3, HRY_FLOAT);
+	plan.alloc(cx.device, out);
 	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
 
 	if (want_vn && nv) {   // (the counters' fill lies outside the events, like the table's)
@@ -250,7 +243,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nfill), 0, (size_t)nv * 4, st));
 		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nhubs), 0, 4, st));
 	}
-	HIP_OK(hipEventRecord(ev[2], st));
+	timer.mark(st);
 	uint32_t *vsrc = dst("vertex_source");
 	if (unweld && ne) launch_dedup_assign(st, D, nout, dst("corner_source"), org, vsrc);   // vertex_source = org of the first corner
 	else if (!unweld) launch_iota(st, nv, vsrc);
@@ -300,13 +293,10 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 			if (unweld) launch_normals_expand(st, vn, vsrc, nout, nv, (float*)dst("normals"));
 		}
 	}
-	HIP_OK(hipEventRecord(ev[3], st));
+	timer.mark(st);
 	if (general && nf) HIP_OK(hipMemcpyAsync(dst("face_region"), freg, (size_t)nf * 2, hipMemcpyDeviceToDevice, st));
 	HIP_OK(hipStreamSynchronize(st));
-	float a = 0, c = 0;
-	HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-	HIP_OK(hipEventElapsedTime(&c, ev[2], ev[3]));
-	out.device_ms = (double)a + (double)c;
+	out.device_ms = timer.ms();
 	out.uploaded_bytes = up;
 	out.nverts = nout;
 	out.ntris = ntri;

@@ -1,0 +1,63 @@
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp): the
+// plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
+// that one build is the build of another (result_build.cpp).
+#pragma once
+#include "context.hpp"
+#include "kernels.hpp"
+
+namespace hry {
+
+// the named buffers of one result: add() every one while sizing, then alloc() the one block the handle owns and name its pieces
+struct OutputPlan {
+	struct Plan { std::string name; uint64_t rows; int width, type; size_t slot; };
+	Carve O;
+	std::vector<Plan> plan;
+	void add(const std::string &name, uint64_t rows, int width, int type) { plan.push_back(Plan{ name, rows, width, type, O.reserve((size_t)rows * width * (type == HRY_USHORT ? 2 : 4)) }); }
+	void alloc(int device, DeviceResult &out)
+	{
+		out.block.alloc(device, O.total);
+		for (const Plan &p : plan) out.bufs.push_back(NamedBuf{ p.name, O.ptr<void>(out.block.p, p.slot), p.rows, p.width, p.type });
+	}
+};
+
+// A build runs in two stretches, with a few bytes coming down between them: mark() before and behind each, ms() their sum once the
+// stream has been waited for.  The events enclose kernels only: the fills and copies lie outside them
+struct StretchTimer {
+	TimedEvent ev[4];
+	int marks = 0;
+	void mark(hipStream_t st) { HIP_OK(hipEventRecord(ev[marks++], st)); }
+	double ms()
+	{
+		float a = 0, c = 0;
+		HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+		HIP_OK(hipEventElapsedTime(&c, ev[2], ev[3]));
+		return (double)a + (double)c;
+	}
+};
+
+// edges.cpp, shells.cpp, orient.cpp: the builds behind a render build (include/harry_amd.h: hry_edges_build, hry_shells_build,
+// hry_orient_build); the result owns its memory.  summary: E, edges with one side, with two, with more / S, closed, nonmanifold,
+// misoriented shells, loops, triangles of the largest / P, orientable patches, flipped triangles, inverted patches, against edges,
+// against edges remaining
+struct TopologyResult : DeviceResult {
+	uint64_t summary[6] = {};
+	double device_ms = 0;
+	uint64_t uploaded_bytes = 0;
+};
+typedef TopologyResult EdgesResult, ShellsResult, OrientResult;
+void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out);   // flags: HRY_EDGES_*
+void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out);   // flags: HRY_SHELLS_*
+void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, OrientResult &out);   // flags: HRY_ORIENT_*
+
+// ---- result_build.cpp
+// r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise
+void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r);
+// the float rows of r's position list, from its first position component; stride: floats a row.  `what` as render_position_list's
+const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride);
+// e is an edges build of (m, r) on cx's device, r a render build of m: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise
+struct EdgesFit { const NamedBuf *tri_edges, *offsets, *sides; uint32_t ne; };
+EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e);
+// ... and what the kernels behind both read of them (tri_adjacency.hpp)
+dev::TriAdjacency tri_adjacency_of(const RenderResult &r, const EdgesFit &fit, const Mesh &m);
+
+}   // namespace hry

@@ -1,5 +1,6 @@
-// The lock-free union-find of the device code (twins.hip: k_cc_*, the components of the encoder's faces; shells.hip: the shells of a
-// render build and the loops of their boundaries).  par[i] == i: i is a root; the root of a set is its smallest member, whatever
+// The lock-free union-find of the device code (twins.hip: k_cc_*, the components of the encoder's faces; hook.hpp: the shells of a
+// render build for shells.hip and the orientation double cover of its patches for orient.hip; shells.hip: the loops of the shells'
+// boundaries).  par[i] == i: i is a root; the root of a set is its smallest member, whatever
 // order the atomics complete in.  Device-only; every parent word is read and written with agent-scope atomics.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// The wavefront-aggregated counter of the per-label counts (shells.hip: shell_counts; orient.hip: patch_counts).  Device-only.
+// The wavefront-aggregated counter of the per-label counts (shells.hip: shell_counts; orient.hip: patch_counts; the labels' measures
+// are measures.hip's, the adjacency both read tri_adjacency.hpp).  Device-only.
 #pragma once
 #include <hip/hip_runtime.h>
 

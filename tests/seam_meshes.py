@@ -11,10 +11,10 @@ from harry_amd import meshgen as mg
 from tests import orient_ref as orf
 from tests import shells_ref as sr
 
-COVER_TRIS = 4096    # orient.hip: kCoverTris, the triangles a workgroup of k_or_hook_local unites in LDS
-HOOK_TRIS = 8192     # shells.hip: kHookTris, ... of k_sh_hook_local
-CHUNK = 256          # shells.hip: kShellChunk, the triangles of one partial sum
-SEG_MAX = 32         # shells.hip: kSegMax; edges.hip: kEdgeSegMax; normals.hip: kNrmSegMax -- a lane above, a workgroup beyond
+COVER_TRIS = 4096    # orient.hip: a tile of k_hook_local<CoverGraph> (hook.hpp), the triangles a workgroup unites in LDS
+HOOK_TRIS = 8192     # shells.hip: ... of k_hook_local<ShellGraph>
+CHUNK = 256          # measures.hip: kShellChunk, the triangles of one partial sum
+SEG_MAX = 32         # measures.hip: kSegMax; edges.hip: kEdgeSegMax; normals.hip: kNrmSegMax -- a lane above, a workgroup beyond
 SORT_BLOCK = 256     # seg_sort.hpp: the threads of block_sort_segment; k_sh_hubs' tile of partials
 WAVE = 64
 LABEL_BLOCK = 256    # the threads of a block of the per-label kernels (k_sh_summary, k_or_decide, k_or_outward, k_sh_sums)

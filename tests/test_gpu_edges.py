@@ -18,6 +18,7 @@ from harry_amd import objgen as og
 from tests import edges_ref as er
 from tests import seam_meshes as sm
 from tests import util
+from tests.util import position_list, same_bytes, xyz_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -34,20 +35,6 @@ def cx():
 
 def mesh_of(m):
     return hc.Mesh.from_arrays(m.verts, m.degrees, m.indices)
-
-
-def xyz_mesh(pos, tris):
-    pos = np.asarray(pos, np.float32)
-    v = np.zeros(len(pos), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
-    v["x"], v["y"], v["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    tris = np.asarray(tris, np.uint32).reshape(-1, 3)
-    return hc.Mesh.from_arrays(v, np.full(len(tris), 3, np.uint8), tris.reshape(-1))
-
-
-def position_list(mesh):
-    ls = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and len(mesh.list_fmt(l)) >= 3]
-    assert len(ls) == 1
-    return ls[0]
 
 
 def restated(cx, mesh, geometry=True):
@@ -81,12 +68,6 @@ def check(cx, mesh, label="", geometry=True):
     assert sorted(got) == sorted(er.FIXED + er.GEOMETRY)
     compare(got, want, label)
     return got, want
-
-
-def same_bytes(a, b):
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
 
 
 def segment(r, e):

@@ -17,7 +17,9 @@ from harry_amd import meshgen as mg
 from harry_amd import objgen as og
 from tests import edges_ref as er
 from tests import orient_ref as orf
+from tests import shells_ref as sr
 from tests import util
+from tests.util import position_list, same_bytes, xyz
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +34,6 @@ def cx():
     c.close()
 
 
-def xyz(pos):
-    v = np.zeros(len(pos), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
-    v["x"], v["y"], v["z"] = np.asarray(pos, np.float32).T
-    return v
-
-
 def mesh_of(mesh):
     pos, deg, idx = mesh
     return hc.Mesh.from_arrays(xyz(pos), np.asarray(deg, np.uint8), np.asarray(idx, np.uint32))
@@ -45,18 +41,6 @@ def mesh_of(mesh):
 
 def gen_arrays(m):
     return np.stack([m.verts["x"], m.verts["y"], m.verts["z"]], axis=1), m.degrees, m.indices
-
-
-def position_list(mesh):
-    ls = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and len(mesh.list_fmt(l)) >= 3]
-    assert len(ls) == 1
-    return ls[0]
-
-
-def same_bytes(a, b):
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
 
 
 def compare(got, want, label=""):
@@ -234,6 +218,30 @@ def test_large_torus(cx, size, order):
     assert counts(g).shape == (1, 8) and counts(g)[0, COL["orientable"]] == 1 and np.array_equal(g["face_flip"] != 0, flags)
     assert np.array_equal(g["oriented_indices"].reshape(-1), clean[2])
     assert counts(got[(True, True)])[0, COL["open"]] == 0
+
+
+# ---- 6b. both builds run the measures over the same triangles (measures.hip): where the winding stage turns nothing, the patches'
+# measures are the shells' bit for bit
+@pytest.mark.parametrize("name", ["icosphere", "tori"])
+def test_patch_measures_are_shell_measures(cx, name):
+    """a closed manifold mesh wound consistently: patches are shells, nothing is turned before the outward stage, which negates the
+    volume of a patch it inverts (exactly) and touches nothing else.  icosphere(2): 320 triangles, one 256-triangle chunk seam inside
+    one shell; multi_component(3, 8, 6): three shells within and across chunks (wound inwards: all three are inverted)"""
+    m = {"icosphere": lambda: mg.icosphere(2), "tori": lambda: mg.multi_component(3, 8, 6)}[name]()
+    ref = orf.of_mesh(m)   # (the restatement, on the host: the premise)
+    assert not ref["tri_flip"].any() and len(ref["patch_first"]) == len(sr.of_mesh(m, geometry=False)["shell_first"])
+    mesh = mesh_of(gen_arrays(m))
+    o, s = cx.orient_numpy(mesh, outward=True), cx.shells_numpy(mesh, geometry=True)
+    assert cx.orient_stat()["patches"] == cx.shells_stat()["shells"] == len(ref["patch_first"])
+    assert np.array_equal(o["tri_patch"], s["tri_shell"]) and np.array_equal(o["patch_first"], s["shell_first"])
+    c = counts(o)
+    inverted = c[:, COL["inverted"]] != 0
+    assert np.array_equal(c[:, COL["flipped"]], np.where(inverted, c[:, COL["triangles"]], 0))   # whole inverted patches, nothing else
+    pm, sm = o["patch_measures"].view(np.uint32), s["shell_measures"].view(np.uint32)
+    assert pm.shape == sm.shape == (len(c), 8)
+    assert np.array_equal(pm[:, 0], sm[:, 0]) and np.array_equal(pm[:, 2:], sm[:, 2:])            # area and box: the same bits
+    assert np.array_equal(pm[:, 1] & 0x7fffffff, sm[:, 1] & 0x7fffffff)                            # volume: the same magnitude
+    assert np.array_equal((pm[:, 1] ^ sm[:, 1]) >> 31 != 0, inverted)                              # ... the sign: where inverted
 
 
 # ---- 7. no triangles

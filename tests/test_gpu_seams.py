@@ -5,8 +5,9 @@ the same run's render buffers, integer buffers with array_equal, float buffers w
 that are not bit-equal printed, the summary and the stat -- and a second build for its bytes.  Every case asserts its condition again
 on the render buffers, so that a render build that numbered things differently cannot empty it.  The seams, by the names and values
 of the constants in the .hip files:
-  orient.hip   kCoverTris = 4096: k_or_hook_local unites in LDS, k_or_hook what leaves a tile -- its same-face statement included
-  shells.hip   kHookTris = 8192 likewise; kSegMax = 32 partials for a lane of k_sh_sums, more for a workgroup of k_sh_hubs, which
+  hook.hpp     kHookParents = 8192 parents in LDS.  orient.hip (CoverGraph, two nodes a triangle): tiles of 4096 triangles, k_hook_local
+               unites in LDS, k_hook what leaves a tile -- its same-face statement included.  shells.hip (ShellGraph, one): 8192 likewise
+  measures.hip kSegMax = 32 partials for a lane of k_sh_sums, more for a workgroup of k_sh_hubs, which
                adds them in tiles of 256 and fills the slots of chunks without the shell with kNoElement
   edges.hip    kEdgeSegMax = 32 sides for a lane of k_edge_rows, more for k_edge_hubs and the 256-thread sort of seg_sort.hpp
   normals.hip  kNrmSegMax = 32 corners for a lane, more for k_nrm_hubs

@@ -159,3 +159,31 @@ def oracle_shard(shard, whole_oracle):
     o.set_degrees(whole_oracle.degrees())
     o.set_shard(whole_oracle.nv, whole_oracle.nf, whole_oracle.ne, shard.shard_elements(2), shard.runs())
     return o
+
+
+# ---- shared by the tests of the builds behind a render build (test_gpu_edges / _shells / _orient / _seams)
+def xyz(pos):
+    """vertex records x y z (f32) from an [n, 3] array"""
+    pos = np.asarray(pos, np.float32)
+    v = np.zeros(len(pos), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    v["x"], v["y"], v["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    return v
+
+
+def xyz_mesh(pos, tris):
+    """a triangle mesh from positions [n, 3] and triangles [T, 3]"""
+    from harry_amd import codec as hc
+    tris = np.asarray(tris, np.uint32).reshape(-1, 3)
+    return hc.Mesh.from_arrays(xyz(pos), np.full(len(tris), 3, np.uint8), tris.reshape(-1))
+
+
+def position_list(mesh):
+    ls = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and len(mesh.list_fmt(l)) >= 3]
+    assert len(ls) == 1
+    return ls[0]
+
+
+def same_bytes(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
