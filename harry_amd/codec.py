@@ -578,6 +578,62 @@ class Codec:
         be oriented)"""
         return dict(getattr(self, "_orient_stat", {}))
 
+    # ---- tangent frames of a render build (include/harry_amd.h: hry_tangents_build)
+    TANGENTS_SUMMARY = ("framed", "unframed", "mirrored", "mixed", "degenerate")
+
+    def _tangents(self, mesh: Mesh, normals, weights, bitangents: bool, fill) -> dict:
+        """the render build with the normals asked for, the tangents build behind it; "tangents", "bitangents" and the render's
+        "indices" and "vertex_source" go to fill(family, name, rows, width, type, handle); both handles are freed whatever happens"""
+        if normals not in ("area", "angle", "stored"):
+            raise ValueError('normals is one of "area", "angle", "stored"')
+        if weights not in ("area", "angle"):
+            raise ValueError('weights is one of "area", "angle"')
+        L = nat.load()
+        stored = normals == "stored"
+        flags = ((nat.TANGENTS_ANGLE_WEIGHTED if weights == "angle" else 0) | (nat.TANGENTS_STORED_NORMALS if stored else 0) |
+                 (nat.TANGENTS_BITANGENTS if bitangents else 0))
+        r, t = C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build_ex(self.h, mesh.h, 0 if stored else self._render_flags(normals, False), C.byref(r)))
+        try:
+            nat.check(L.hry_tangents_build(self.h, mesh.h, r, flags, C.byref(t)))
+            try:
+                out = {}
+                for family, h, names in (("tangents", t, ("tangents", "bitangents")), ("render", r, ("indices", "vertex_source"))):
+                    for name in names:
+                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                        nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                        if width.value:
+                            out[name] = fill(family, name, rows.value, width.value, typ.value, h)
+                d, up, rd, rup, s = C.c_double(), C.c_uint64(), C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
+                nat.check(L.hry_tangents_stat(t, C.byref(d), C.byref(up)))
+                nat.check(L.hry_render_stat(r, C.byref(rd), C.byref(rup)))
+                nat.check(L.hry_tangents_summary(t, s))
+                self._tangents_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "render_device_ms": rd.value, "render_uploaded_bytes": rup.value,
+                                       **{k: int(s[i]) for i, k in enumerate(self.TANGENTS_SUMMARY)}}
+                return out
+            finally:
+                L.hry_tangents_free(t)
+        finally:
+            L.hry_render_free(r)
+
+    def tangents_numpy(self, mesh: Mesh, normals: str = "area", weights: str = "area", bitangents: bool = False) -> dict:
+        """a tangent frame per output vertex of the mesh's render build (hry_tangents_build), copied to host arrays: tangents f32 [U, 4]
+        (unit tangent, handedness +1 / -1; a zero row: no frame), bitangents f32 [U, 3] where asked for, and the render build's
+        indices u32 [T, 3] and vertex_source u32 [U] they go with.  normals: "area" / "angle": computed on the device with those
+        weights, "stored": the file's (nx ny nz, OBJ vn); weights: "area": uv-area weights, "angle": unit directions weighted by the
+        corner's angle"""
+        return self._tangents(mesh, normals, weights, bitangents, self._fill_numpy)
+
+    def tangents(self, mesh: Mesh, normals: str = "area", weights: str = "area", bitangents: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: float32 and int32"""
+        return self._tangents(mesh, normals, weights, bitangents, self._fill_torch(mesh))
+
+    def tangents_stat(self) -> dict:
+        """of the last tangents / tangents_numpy: device_ms (the kernels), uploaded_bytes (0), and hry_tangents_summary's counts: framed,
+        unframed (vertices with a zero row), mirrored (w = -1), mixed (both signs of the uv determinant meet) vertices, degenerate
+        (uv-degenerate triangles); render_device_ms / render_uploaded_bytes: hry_render_stat of the render build it was built behind"""
+        return dict(getattr(self, "_tangents_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the

@@ -19,6 +19,7 @@ struct hry_order { std::unique_ptr<OrderResult> o; };
 struct hry_edges { EdgesResult e; };
 struct hry_shells { ShellsResult s; };
 struct hry_orient { OrientResult o; };
+struct hry_tangents { TangentsResult t; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -118,6 +119,7 @@ static const RenderResult *result_of(const hry_render *r) { return r ? &r->r : n
 static const TopologyResult *result_of(const hry_edges *e) { return e ? &e->e : nullptr; }
 static const TopologyResult *result_of(const hry_shells *s) { return s ? &s->s : nullptr; }
 static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o : nullptr; }
+static const TopologyResult *result_of(const hry_tangents *t) { return t ? &t->t : nullptr; }
 static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
 static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
 
@@ -256,6 +258,11 @@ int hry_list_stride(const hry_mesh *m, int l) { return m->m.lists[l].stride(); }
 int hry_list_type(const hry_mesh *m, int l, int c) { return m->m.lists[l].type[c]; }
 int hry_list_quant(const hry_mesh *m, int l, int c) { return m->m.lists[l].quant[c]; }
 int hry_list_offset(const hry_mesh *m, int l, int c) { return m->m.lists[l].offset[c]; }
+int hry_list_interp_ncomp(const hry_mesh *m, int l, int interp)
+{
+	if (!m || l < 0 || (size_t)l >= m->m.lists.size() || interp < 0 || (size_t)interp >= m->m.lists[l].interp_len.size()) return 0;
+	return m->m.lists[l].interp_len[interp];
+}
 const uint8_t *hry_list_data(const hry_mesh *m, int l) { return m->m.lists[l].data.data(); }
 const uint8_t *hry_list_min(const hry_mesh *m, int l) { return m->m.lists[l].have_bounds ? m->m.lists[l].bmin.data() : nullptr; }
 const uint8_t *hry_list_max(const hry_mesh *m, int l) { return m->m.lists[l].have_bounds ? m->m.lists[l].bmax.data() : nullptr; }
@@ -728,6 +735,18 @@ int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *d
 int hry_orient_summary(const hry_orient *o, uint64_t out[6]) { return handle_summary(result_of(o), out, 6); }
 int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(o), device_ms, uploaded_bytes); }
 void hry_orient_free(hry_orient *o) { delete o; }
+
+// ---- tangent frames of a render build (tangents.cpp)
+int hry_tangents_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_tangents **out)
+{
+	return handle_build(ctx, m && r, out, [&](hry_tangents &t) { tangents_build(ctx->cx, m->m, r->r, flags, t.t); });
+}
+uint64_t hry_tangents_count(const hry_tangents *t) { return t ? t->t.summary[0] : 0; }
+int hry_tangents_get(const hry_tangents *t, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(t), name, dev, rows, width, type, false); }
+int hry_tangents_copy(hry_ctx *ctx, const hry_tangents *t, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(t), name, "tangent buffer", dst, dst_is_device, true); }
+int hry_tangents_summary(const hry_tangents *t, uint64_t out[6]) { return handle_summary(result_of(t), out, 6); }
+int hry_tangents_stat(const hry_tangents *t, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(t), device_ms, uploaded_bytes); }
+void hry_tangents_free(hry_tangents *t) { delete t; }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
 	if (out) *out = nullptr;

@@ -38,7 +38,11 @@
 // of "shell_counts"; X = V - E + T of the shell, G = (2 - X - L) / 2, or - where the shell has non-manifold or misoriented edges);
 // --orient / --orient-outward (with or without OUTPUT, after those lines, which keep describing the source mesh: "Orientation: patches
 // P orientable O flipped F inverted I against A remaining R" -- hry_orient_build with HRY_ORIENT_MAJORITY, and HRY_ORIENT_OUTWARD for
-// the second, and hry_orient_summary; with OUTPUT and F > 0 the mesh that is written is hry_mesh_flip_faces(mesh, "face_flip")).
+// the second, and hry_orient_summary; with OUTPUT and F > 0 the mesh that is written is hry_mesh_flip_faces(mesh, "face_flip"));
+// --tangents (with or without OUTPUT, after those lines: "Tangents: vertices U framed F unframed Z mirrored M mixed X degenerate D" --
+// hry_tangents_build over a render build of the mesh and hry_tangents_summary; the normals are the file's where the mesh has a
+// normal list, HRY_TANGENTS_STORED_NORMALS, and the area-weighted ones of HRY_RENDER_VERTEX_NORMALS otherwise; a mesh without
+// texture coordinates ends with the library's refusal).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -78,7 +82,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false;
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -95,7 +99,8 @@ const Opt kOpts[] = {
 	{ 0, "topology", "Print edge counts and V - E + F (OUTPUT may be left out)", false },
 	{ 0, "shells", "Print the connected shells, their counts, loops and genus (OUTPUT may be left out)", false },
 	{ 0, "orient", "Wind the faces of every patch consistently, the smaller side turned (OUTPUT may be left out)", false },
-	{ 0, "orient-outward", "... and closed patches so that they enclose a positive volume", false } };
+	{ 0, "orient-outward", "... and closed patches so that they enclose a positive volume", false },
+	{ 0, "tangents", "Print how many vertices get a tangent frame from positions, uv and normals (OUTPUT may be left out)", false } };
 
 void usage(const char *argv0)
 {
@@ -180,6 +185,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "shells") a.shells = true;
 		else if (n == "orient") a.orient = true;
 		else if (n == "orient-outward") a.orient = a.orient_outward = true;
+		else if (n == "tangents") a.tangents = true;
 		else if (n == "max-error" || n == "max-error-rel") {
 			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
 			const double v = to_double(argv[0], val);
@@ -221,7 +227,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells || a.orient ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -301,6 +307,7 @@ struct Handles {   // released on every path
 	hry_edges *edges = nullptr;
 	hry_shells *shells = nullptr;
 	hry_orient *orient = nullptr;   // --orient, --orient-outward
+	hry_tangents *tangents = nullptr;   // --tangents, over a render build of its own
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -313,11 +320,12 @@ struct Handles {   // released on every path
 	}
 	void drop_adjacency()
 	{
+		if (tangents) hry_tangents_free(tangents);
 		if (orient) hry_orient_free(orient);
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
-		orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
+		tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
 	}
 	~Handles()
 	{
@@ -605,7 +613,18 @@ int run(const Args &args)
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells || args.orient) && args.out.empty()) {
+	if (args.tangents) {
+		bool stored = false;   // a normal list: a vertex or corner list with three NORMAL components
+		for (int l = 0; l < hry_mesh_nlists(h.mesh); ++l) stored |= (hry_list_target(h.mesh, l) == 1 || hry_list_target(h.mesh, l) == 2) && hry_list_interp_ncomp(h.mesh, l, 1) >= 3;
+		ok(hry_render_build_ex(h.cx[0], h.mesh, stored ? 0u : HRY_RENDER_VERTEX_NORMALS, &h.render));
+		ok(hry_tangents_build(h.cx[0], h.mesh, h.render, stored ? HRY_TANGENTS_STORED_NORMALS : 0u, &h.tangents));
+		uint64_t s[6];
+		ok(hry_tangents_summary(h.tangents, s));
+		std::cout << "Tangents: vertices " << hry_render_nverts(h.render) << " framed " << s[0] << " unframed " << s[1] << " mirrored " << s[2] << " mixed " << s[3] << " degenerate " << s[4] << std::endl;
+		h.drop_adjacency();
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells || args.orient || args.tangents) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

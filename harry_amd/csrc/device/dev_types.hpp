@@ -135,6 +135,24 @@ struct NrmView {
 	int32_t angle;
 };
 
+// tangents.hip: what the tangent frames of a render build read and write.  indices[n]: the n = 3 T index slots; pos / uv / nrm: float
+// rows of *_stride floats per output vertex (nout rows) whose first three / two / three are its position, texture coordinates and
+// normal; angle: corner-angle weights; tangents: nout rows of 4; bitangents: nout rows of 3, nullptr: none
+struct TanView {
+	const uint32_t *indices;
+	const float *pos, *uv, *nrm;
+	float *tangents, *bitangents;
+	uint32_t n, nout, pos_stride, uv_stride, nrm_stride;
+	int32_t angle;
+};
+// ... and their working arrays, laid out by tangents.cpp: terms [T] rows of 6 doubles, sign [T], count [nout] zeroed (the scatter's
+// cursors afterwards), start [nout + 1], sums: scan_sums_words(nout), seg [n], hubs: 1 + tangents_hub_capacity(n) words, the first
+// zeroed, classes: 4 zeroed counters -- framed, mirrored, mixed vertices, uv-degenerate triangles
+struct TanWork {
+	double *terms;
+	uint32_t *sign, *count, *start, *sums, *seg, *hubs, *classes;
+};
+
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
 struct RunPlace {

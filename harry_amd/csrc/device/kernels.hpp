@@ -217,6 +217,11 @@ void launch_normals_expand(hipStream_t st, const float *vn, const uint32_t *vsrc
 uint32_t edges_hub_capacity(uint32_t nsides);
 void launch_edges(hipStream_t st, const EdgesView &v, uint32_t *count, uint32_t *sums, uint32_t *hubs, uint32_t *classes);
 
+// tangent frames of a render build (tangents.hip; driver: tangents.cpp).  The working arrays and what is zeroed: TanWork
+// (dev_types.hpp).  Every row of v.tangents and, where given, v.bitangents is written
+uint32_t tangents_hub_capacity(uint32_t nslots);
+void launch_tangents(hipStream_t st, const TanView &v, const TanWork &w);
+
 // shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the
 // outputs allocated, counts zeroed, face_shell filled with 0xff): tri_shell, face_shell, shell_first, the triangle and face columns.

@@ -32,6 +32,28 @@ const float *render_positions(const Mesh &m, const RenderResult &r, const char *
 	return (const float*)b_pos->p + at;
 }
 
+const float *render_attribute(const Mesh &m, const RenderResult &r, int interp, int ncomp, const char *what, const char *noun, uint32_t &stride)
+{
+	auto len = [&](const AttrList &L) { return (size_t)interp < L.interp_len.size() ? L.interp_len[interp] : 0; };
+	const std::string need = std::string(ncomp == 2 ? "two " : "three ") + noun + " components";
+	size_t al = m.lists.size();
+	if (!m.general) {
+		if (m.lists.size() >= 2 && len(m.lists[1]) >= ncomp) al = 1;
+	} else
+		for (size_t l = 0; l < m.lists.size(); ++l) {
+			if ((m.lists[l].target != 1 && m.lists[l].target != 2) || len(m.lists[l]) < ncomp) continue;
+			if (al != m.lists.size()) throw Error(HRY_E_UNSUPPORTED, std::string(what) + ": several vertex or corner lists with " + need);
+			al = l;
+		}
+	if (al == m.lists.size()) throw Error(HRY_E_UNSUPPORTED, std::string(what) + ": no vertex or corner list with " + need);
+	const NamedBuf *b = r.find("list" + std::to_string(al));
+	const size_t at = (size_t)m.lists[al].interp_off[interp];
+	if (!b || b->rows != r.nverts || b->type != HRY_FLOAT || (size_t)b->width < at + ncomp)
+		throw Error(HRY_E_ARG, std::string("the render buffers do not hold this mesh's list of ") + noun + " components");
+	stride = (uint32_t)b->width;
+	return (const float*)b->p + at;
+}
+
 EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e)
 {
 	require_render_of(cx, m, r);

@@ -1,4 +1,4 @@
-// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp): the
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp): the
 // plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
 // that one build is the build of another (result_build.cpp).
 #pragma once
@@ -48,12 +48,19 @@ typedef TopologyResult EdgesResult, ShellsResult, OrientResult;
 void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, EdgesResult &out);   // flags: HRY_EDGES_*
 void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, ShellsResult &out);   // flags: HRY_SHELLS_*
 void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, OrientResult &out);   // flags: HRY_ORIENT_*
+// tangents.cpp: the tangent frames of a render build (include/harry_amd.h: hry_tangents_build).  summary: framed vertices, vertices
+// with a zero row, mirrored, mixed, uv-degenerate triangles, 0
+typedef TopologyResult TangentsResult;
+void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, TangentsResult &out);   // flags: HRY_TANGENTS_*
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise
 void require_render_of(const Context &cx, const Mesh &m, const RenderResult &r);
 // the float rows of r's position list, from its first position component; stride: floats a row.  `what` as render_position_list's
 const float *render_positions(const Mesh &m, const RenderResult &r, const char *what, uint32_t &stride);
+// ... and of the one vertex- or corner-target list with at least ncomp components of interpretation `interp` (mixing.h ids: 16 TEX,
+// 1 NORMAL), from the first of them; PLY layout: list 1.  None or several: HRY_E_UNSUPPORTED, "<what>: no / several ... <noun> components"
+const float *render_attribute(const Mesh &m, const RenderResult &r, int interp, int ncomp, const char *what, const char *noun, uint32_t &stride);
 // e is an edges build of (m, r) on cx's device, r a render build of m: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise
 struct EdgesFit { const NamedBuf *tri_edges, *offsets, *sides; uint32_t ne; };
 EdgesFit require_edges_of(const Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e);

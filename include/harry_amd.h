@@ -17,6 +17,7 @@
  *   hry_edges_build     (no counterpart: unique edges, adjacency and per-edge geometry of a render build, as device buffers)
  *   hry_shells_build    (no counterpart: connected shells of a render build, their counts, loops, area, volume and box, as device buffers)
  *   hry_orient_build    (no counterpart: which triangles of a render build to turn for a consistent winding per patch, as device buffers)
+ *   hry_tangents_build  (no counterpart: a tangent frame per output vertex of a render build, from its positions, uv and normals, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -174,6 +175,7 @@ int hry_list_stride(const hry_mesh *m, int l);
 int hry_list_type(const hry_mesh *m, int l, int c);
 int hry_list_quant(const hry_mesh *m, int l, int c);
 int hry_list_offset(const hry_mesh *m, int l, int c);
+int hry_list_interp_ncomp(const hry_mesh *m, int l, int interp);   /* components of list l with interpretation `interp` (mixing.h ids: 0 POS, 1 NORMAL, 16 TEX); 0: none, or no such list */
 const uint8_t *hry_list_data(const hry_mesh *m, int l);
 const uint8_t *hry_list_min(const hry_mesh *m, int l);
 const uint8_t *hry_list_max(const hry_mesh *m, int l);
@@ -431,6 +433,63 @@ int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *d
 int hry_orient_summary(const hry_orient *o, uint64_t out[6]);
 int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes);
 void hry_orient_free(hry_orient *o);
+
+/* ---- tangent frames of a render build ---------------------------------------------------------------------------------------
+ * hry_tangents_build computes, on ctx's device, what a renderer needs before it can shade a textured mesh with a normal map: a
+ * tangent and a handedness per OUTPUT vertex.  r is a render build of m on ctx's device; the build reads r's "indices", the float
+ * rows of its position and uv lists and its "normals" (or, with HRY_TANGENTS_STORED_NORMALS, of its normal list) where they lie in
+ * HBM: nothing is uploaded (uploaded_bytes is 0), the handle owns its memory like the other results, and r may be freed afterwards.
+ * Let T be the triangles, U the output vertices, I = indices.
+ * Buffers by name:
+ *   "tangents"    f32 [U, 4]  (t.x, t.y, t.z, w): the unit tangent and the handedness, +1 or -1; (0, 0, 0, 0): no frame
+ *   "bitangents"  f32 [U, 3]  HRY_TANGENTS_BITANGENTS: w * (n x t); (0, 0, 0) where the tangent row is zero
+ * Inputs:
+ *   P[u]: the position of output vertex u, read as for the edges' geometry (the same list, the same HRY_E_UNSUPPORTED refusals).
+ *   uv[u]: the first two components of interpretation TEX (mixing.h id 16; PLY u v / tu tv, OBJ vt) of output vertex u, read as the
+ *     floats of r's "list<l>" buffer and widened to double.  l: the one vertex- or corner-target list with at least two TEX
+ *     components; in the PLY layout list 1, when it has them.  No such list, or several: HRY_E_UNSUPPORTED with a text that says
+ *     which.  An element whose region does not bind the list reads 0 there (as every "list<l>").
+ *   n[u]: the float row of r's "normals" -- a render build without it is refused with HRY_E_ARG and a text that names
+ *     HRY_RENDER_VERTEX_NORMALS -- or, with HRY_TANGENTS_STORED_NORMALS, the first three components of interpretation NORMAL (id 1;
+ *     PLY nx ny nz, OBJ vn) of the one vertex- or corner-target list that has three (none, or several: HRY_E_UNSUPPORTED).  Either
+ *     way the row is widened to double and divided by its length, per component, in double.
+ * Arithmetic: every operation is an individually rounded IEEE double operation, in the written order; a . b, a x b and |a| as in the
+ *   edges' and normals' contracts; there are no floating-point atomics.
+ * Per triangle t = (i0, i1, i2) of I:
+ *   e1 = P[i1] - P[i0], e2 = P[i2] - P[i0]; (a1, b1) = uv[i1] - uv[i0], (a2, b2) = uv[i2] - uv[i0];
+ *   det = a1 b2 - a2 b1; Tr = e1 b2 - e2 b1 and Br = e2 a1 - e1 a2, per component; both negated where det < 0.
+ *   The triangle is uv-degenerate, and contributes to no vertex, where det is 0 or not finite, where a component of Tr or Br is not
+ *   finite or, with HRY_TANGENTS_ANGLE_WEIGHTED, where |Tr| or |Br| is 0.  (A triangle of an element that binds no uv reads equal
+ *   uv at its corners: det is 0.)
+ *   Its terms at each of its three corners: Tr and Br themselves (default: uv-area weights, the counterpart of the normals' N_f), or
+ *   with HRY_TANGENTS_ANGLE_WEIGHTED theta * (Tr / |Tr|) and theta * (Br / |Br|), the quotients per component, theta =
+ *   atan2(|a x b|, a . b) with a = P[next corner] - P[corner], b = P[previous corner] - P[corner] within the triangle.
+ * Per output vertex u -- not per decoded vertex: a uv seam splits the frame, unlike the normals:
+ *   S_T and S_B start from +0 and add the terms of the index slots s = 3 t + k with I[t][k] == u, in ascending s, one after the other.
+ *   A vertex with more than 32 slots (n of them) instead sums 256 consecutive ranges of ceil(n / 256) slots each in that way and adds
+ *   the 256 partial sums in range order, as the normals do: an association n alone determines.
+ *   R = S_T - n (n . S_T) per component (the product first); t = R / |R|; w = -1 where (n x t) . S_B < 0, else +1.
+ *   tangents[u] = ((float)t, (float)w); bitangents[u] = (float)(w * (n x t)) per component.  Both rows are zeros where no triangle
+ *   contributed (an isolated vertex, uv-degenerate triangles only), or where |n| or |R| is 0 or not finite.
+ * Determinism: the bits of both buffers depend on r alone -- not on the run, on residency, or on the order atomics complete in.
+ * Refusals: null arguments, unknown flag bits, an r whose U / T / nf do not fit m or that lives on another device: HRY_E_ARG; 3 T > 2^31:
+ * HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable.
+ *   hry_tangents_count   output vertices that got a frame
+ *   hry_tangents_get / _copy / _stat  as hry_edges_get / _copy / _stat
+ *   hry_tangents_summary out = { framed vertices, vertices with a zero row, framed vertices with w = -1 (mirrored uv), vertices whose
+ *                        contributing triangles have both signs of det (mixed: the frame averages across a mirror seam),
+ *                        uv-degenerate triangles, 0 (reserved) }: device reductions during the build, no buffer is downloaded for them */
+typedef struct hry_tangents hry_tangents;
+#define HRY_TANGENTS_ANGLE_WEIGHTED 1u  /* unit directions weighted by the corner's angle instead of uv-area weights */
+#define HRY_TANGENTS_STORED_NORMALS 2u  /* n from the file's normal list (nx ny nz / OBJ vn) instead of r's "normals" */
+#define HRY_TANGENTS_BITANGENTS     4u  /* also buffer "bitangents" f32 [U, 3] */
+int hry_tangents_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_tangents **out);
+uint64_t hry_tangents_count(const hry_tangents *t);               /* output vertices that got a frame */
+int hry_tangents_get(const hry_tangents *t, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_tangents_copy(hry_ctx *ctx, const hry_tangents *t, const char *name, void *dst, int dst_is_device);
+int hry_tangents_summary(const hry_tangents *t, uint64_t out[6]);
+int hry_tangents_stat(const hry_tangents *t, double *device_ms, uint64_t *uploaded_bytes);
+void hry_tangents_free(hry_tangents *t);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
