@@ -96,6 +96,8 @@ EDGES_GEOMETRY = 1
 SHELLS_GEOMETRY = 1
 ORIENT_MAJORITY, ORIENT_OUTWARD = 1, 2
 TANGENTS_ANGLE_WEIGHTED, TANGENTS_STORED_NORMALS, TANGENTS_BITANGENTS = 1, 2, 4
+CREASES_ANGLE_WEIGHTED = 1
+CREASE_SMOOTH, CREASE_SHARP, CREASE_BOUNDARY, CREASE_NONMANIFOLD, CREASE_MISORIENTED, CREASE_DEGENERATE = 0, 1, 2, 3, 4, 5
 TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST, TOL_NORMAL_CHORD = 0, 1, 2, 3, 4
 
 _lib = None
@@ -133,7 +135,7 @@ def load():
     for n in ("ncomp", "stride"):
         f = getattr(L, "hry_list_" + n); f.restype = C.c_int; f.argtypes = [vp, C.c_int]
     L.hry_list_count.restype = C.c_uint32; L.hry_list_count.argtypes = [vp, C.c_int]
-    for n in ("type", "quant", "offset", "interp_ncomp"):
+    for n in ("type", "quant", "offset", "interp_ncomp", "interp_offset"):
         f = getattr(L, "hry_list_" + n); f.restype = C.c_int; f.argtypes = [vp, C.c_int, C.c_int]
     for n in ("data", "min", "max"):
         f = getattr(L, "hry_list_" + n); f.restype = u8p; f.argtypes = [vp, C.c_int]
@@ -189,7 +191,8 @@ def load():
     L.hry_render_copy.restype = C.c_int; L.hry_render_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_render_free.argtypes = [vp]
-    for fam, inputs in (("edges", [vp]), ("shells", [vp, vp]), ("orient", [vp, vp]), ("tangents", [vp])):   # the builds behind a render build: its handle(s) in
+    for fam, inputs in (("edges", [vp]), ("shells", [vp, vp]), ("orient", [vp, vp]), ("tangents", [vp]),
+                        ("creases", [vp, vp, C.c_double])):   # the builds behind a render build: its handle(s) in (creases: and the limit)
         def fn(what, restype, argtypes):
             f = getattr(L, f"hry_{fam}_{what}"); f.restype = restype; f.argtypes = argtypes
         fn("build", C.c_int, [vp, vp] + inputs + [C.c_uint32, C.POINTER(vp)])

@@ -634,6 +634,71 @@ class Codec:
         (uv-degenerate triangles); render_device_ms / render_uploaded_bytes: hry_render_stat of the render build it was built behind"""
         return dict(getattr(self, "_tangents_stat", {}))
 
+    # ---- hard edges and split normals of a render build (include/harry_amd.h: hry_creases_build)
+    CREASES_BUFFERS = ("indices", "render_vertex", "vertex_source", "normals", "slot_group", "edge_class")
+    CREASES_SUMMARY = ("vertices", "groups", "smooth", "sharp", "split", "other")
+
+    def _creases(self, mesh: Mesh, angle, cos_limit, weights, fill, gather) -> dict:
+        """the render build, its edges build with geometry, the creases build behind both; the creases' buffers go to fill(family, name,
+        rows, width, type, handle), and "positions" is gather(the render's position list filled the same way, its first position
+        component, render_vertex); all three handles are freed whatever happens"""
+        if weights not in ("area", "angle"):
+            raise ValueError('weights is one of "area", "angle"')
+        limit = float(math.cos(math.radians(angle)) if cos_limit is None else cos_limit)
+        L = nat.load()
+        r, e, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_edges_build(self.h, mesh.h, r, nat.EDGES_GEOMETRY, C.byref(e)))
+            try:
+                nat.check(L.hry_creases_build(self.h, mesh.h, r, e, limit, nat.CREASES_ANGLE_WEIGHTED if weights == "angle" else 0, C.byref(c)))
+                try:
+                    def buffer(family, h, name):
+                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                        nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                        return fill(family, name, rows.value, width.value, typ.value, h)
+                    out = {name: buffer("creases", c, name) for name in self.CREASES_BUFFERS}
+                    # the position list as the library chooses it (render.cpp: position_list): list 1, or the one vertex list with positions
+                    pl = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and L.hry_list_interp_ncomp(mesh.h, l, 0) >= 3][0]
+                    out["positions"] = gather(buffer("render", r, f"list{pl}"), L.hry_list_interp_offset(mesh.h, pl, 0), out["render_vertex"])
+                    d, up, ed, rd, rup, s = C.c_double(), C.c_uint64(), C.c_double(), C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
+                    nat.check(L.hry_creases_stat(c, C.byref(d), C.byref(up)))
+                    nat.check(L.hry_edges_stat(e, C.byref(ed), None))
+                    nat.check(L.hry_render_stat(r, C.byref(rd), C.byref(rup)))
+                    nat.check(L.hry_creases_summary(c, s))
+                    self._creases_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges_device_ms": ed.value, "render_device_ms": rd.value,
+                                          "render_uploaded_bytes": rup.value, "cos_limit": limit,
+                                          **{k: int(s[i]) for i, k in enumerate(self.CREASES_SUMMARY)}}
+                    return out
+                finally:
+                    L.hry_creases_free(c)
+            finally:
+                L.hry_edges_free(e)
+        finally:
+            L.hry_render_free(r)
+
+    def creases_numpy(self, mesh: Mesh, angle: float = 30.0, cos_limit=None, weights: str = "area") -> dict:
+        """the mesh's render build with its vertices split along hard edges (hry_creases_build), copied to host arrays: indices u32
+        [T, 3], render_vertex u32 [W], vertex_source u32 [W], normals f32 [W, 3], slot_group u32 [T, 3], edge_class u32 [E]
+        (nat.CREASE_*), and positions f32 [W, 3], the render build's position rows gathered by render_vertex.  angle: the crease angle
+        in degrees, an edge that folds more sharply is hard -- the limit is math.cos(math.radians(angle)); cos_limit: the limit
+        itself, exact at equality (<= -1: all smooth, > 1: flat shading); weights: "area": the triangles' areas, "angle": the
+        corners' angles"""
+        return self._creases(mesh, angle, cos_limit, weights, self._fill_numpy,
+                             lambda rows, at, rv: np.ascontiguousarray(rows.reshape(len(rows), -1)[rv.astype(np.int64), at:at + 3]))
+
+    def creases(self, mesh: Mesh, angle: float = 30.0, cos_limit=None, weights: str = "area") -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: float32 and int32"""
+        return self._creases(mesh, angle, cos_limit, weights, self._fill_torch(mesh),
+                             lambda rows, at, rv: rows.reshape(len(rows), -1)[rv.long(), at:at + 3].contiguous())
+
+    def creases_stat(self) -> dict:
+        """of the last creases / creases_numpy: device_ms (the kernels), uploaded_bytes (0), cos_limit (the limit used), and
+        hry_creases_summary's counts: vertices (W), groups (G), smooth, sharp (edges), split (decoded vertices with more than one
+        group), other (boundary, non-manifold, misoriented and degenerate edges); edges_device_ms: of the edges build before it;
+        render_device_ms / render_uploaded_bytes: hry_render_stat of the render build before both"""
+        return dict(getattr(self, "_creases_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the

@@ -20,6 +20,7 @@ struct hry_edges { EdgesResult e; };
 struct hry_shells { ShellsResult s; };
 struct hry_orient { OrientResult o; };
 struct hry_tangents { TangentsResult t; };
+struct hry_creases { CreasesResult c; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -120,6 +121,7 @@ static const TopologyResult *result_of(const hry_edges *e) { return e ? &e->e : 
 static const TopologyResult *result_of(const hry_shells *s) { return s ? &s->s : nullptr; }
 static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o : nullptr; }
 static const TopologyResult *result_of(const hry_tangents *t) { return t ? &t->t : nullptr; }
+static const TopologyResult *result_of(const hry_creases *c) { return c ? &c->c : nullptr; }
 static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
 static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
 
@@ -262,6 +264,11 @@ int hry_list_interp_ncomp(const hry_mesh *m, int l, int interp)
 {
 	if (!m || l < 0 || (size_t)l >= m->m.lists.size() || interp < 0 || (size_t)interp >= m->m.lists[l].interp_len.size()) return 0;
 	return m->m.lists[l].interp_len[interp];
+}
+int hry_list_interp_offset(const hry_mesh *m, int l, int interp)
+{
+	if (!hry_list_interp_ncomp(m, l, interp)) return -1;
+	return m->m.lists[l].interp_off[interp];
 }
 const uint8_t *hry_list_data(const hry_mesh *m, int l) { return m->m.lists[l].data.data(); }
 const uint8_t *hry_list_min(const hry_mesh *m, int l) { return m->m.lists[l].have_bounds ? m->m.lists[l].bmin.data() : nullptr; }
@@ -747,6 +754,18 @@ int hry_tangents_copy(hry_ctx *ctx, const hry_tangents *t, const char *name, voi
 int hry_tangents_summary(const hry_tangents *t, uint64_t out[6]) { return handle_summary(result_of(t), out, 6); }
 int hry_tangents_stat(const hry_tangents *t, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(t), device_ms, uploaded_bytes); }
 void hry_tangents_free(hry_tangents *t) { delete t; }
+
+// ---- hard edges and split normals of a render build (creases.cpp)
+int hry_creases_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, double cos_limit, uint32_t flags, hry_creases **out)
+{
+	return handle_build(ctx, m && r && e, out, [&](hry_creases &c) { creases_build(ctx->cx, m->m, r->r, e->e, cos_limit, flags, c.c); });
+}
+uint64_t hry_creases_count(const hry_creases *c) { return c ? c->c.summary[0] : 0; }
+int hry_creases_get(const hry_creases *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(c), name, dev, rows, width, type, false); }
+int hry_creases_copy(hry_ctx *ctx, const hry_creases *c, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(c), name, "crease buffer", dst, dst_is_device, true); }
+int hry_creases_summary(const hry_creases *c, uint64_t out[6]) { return handle_summary(result_of(c), out, 6); }
+int hry_creases_stat(const hry_creases *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
+void hry_creases_free(hry_creases *c) { delete c; }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
 	if (out) *out = nullptr;

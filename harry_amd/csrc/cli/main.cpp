@@ -42,7 +42,10 @@
 // --tangents (with or without OUTPUT, after those lines: "Tangents: vertices U framed F unframed Z mirrored M mixed X degenerate D" --
 // hry_tangents_build over a render build of the mesh and hry_tangents_summary; the normals are the file's where the mesh has a
 // normal list, HRY_TANGENTS_STORED_NORMALS, and the area-weighted ones of HRY_RENDER_VERTEX_NORMALS otherwise; a mesh without
-// texture coordinates ends with the library's refusal).
+// texture coordinates ends with the library's refusal);
+// --creases DEG (with or without OUTPUT, after those lines: "Creases: angle DEG vertices W groups G smooth S sharp H split V other O" --
+// hry_creases_build at cos(DEG degrees) over a render build of the mesh and its edges build with geometry, and hry_creases_summary;
+// it describes the mesh that is written: after --orient, the oriented one.  Nothing else about the output changes).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -82,7 +85,9 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false, creases = false;
+	double crease_angle = 0.0;
+	std::string crease_text;   // DEG as it was given
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
 };
 
@@ -100,7 +105,8 @@ const Opt kOpts[] = {
 	{ 0, "shells", "Print the connected shells, their counts, loops and genus (OUTPUT may be left out)", false },
 	{ 0, "orient", "Wind the faces of every patch consistently, the smaller side turned (OUTPUT may be left out)", false },
 	{ 0, "orient-outward", "... and closed patches so that they enclose a positive volume", false },
-	{ 0, "tangents", "Print how many vertices get a tangent frame from positions, uv and normals (OUTPUT may be left out)", false } };
+	{ 0, "tangents", "Print how many vertices get a tangent frame from positions, uv and normals (OUTPUT may be left out)", false },
+	{ 0, "creases", "Print how many vertices and hard edges a crease angle of DEG degrees gives (OUTPUT may be left out)", true } };
 
 void usage(const char *argv0)
 {
@@ -186,6 +192,11 @@ Args parse(int argc, const char **argv)
 		else if (n == "orient") a.orient = true;
 		else if (n == "orient-outward") a.orient = a.orient_outward = true;
 		else if (n == "tangents") a.tangents = true;
+		else if (n == "creases") {
+			a.crease_angle = to_double(argv[0], val);
+			if (std::isnan(a.crease_angle)) arg_error(argv[0], "Invalid angle");
+			a.creases = true; a.crease_text = val;
+		}
 		else if (n == "max-error" || n == "max-error-rel") {
 			if (!have_l) arg_error(argv[0], "--" + n + " needs a preceding -l");
 			const double v = to_double(argv[0], val);
@@ -227,7 +238,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -308,6 +319,7 @@ struct Handles {   // released on every path
 	hry_shells *shells = nullptr;
 	hry_orient *orient = nullptr;   // --orient, --orient-outward
 	hry_tangents *tangents = nullptr;   // --tangents, over a render build of its own
+	hry_creases *creases = nullptr;   // --creases, over a render build and an edges build with geometry of its own
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -320,12 +332,13 @@ struct Handles {   // released on every path
 	}
 	void drop_adjacency()
 	{
+		if (creases) hry_creases_free(creases);
 		if (tangents) hry_tangents_free(tangents);
 		if (orient) hry_orient_free(orient);
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
-		tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
+		creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
 	}
 	~Handles()
 	{
@@ -624,7 +637,17 @@ int run(const Args &args)
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells || args.orient || args.tangents) && args.out.empty()) {
+	if (args.creases) {
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_edges_build(h.cx[0], h.mesh, h.render, HRY_EDGES_GEOMETRY, &h.edges));
+		ok(hry_creases_build(h.cx[0], h.mesh, h.render, h.edges, std::cos(args.crease_angle * (3.14159265358979323846 / 180.0)), 0u, &h.creases));
+		uint64_t s[6];
+		ok(hry_creases_summary(h.creases, s));
+		std::cout << "Creases: angle " << args.crease_text << " vertices " << s[0] << " groups " << s[1] << " smooth " << s[2] << " sharp " << s[3] << " split " << s[4] << " other " << s[5] << std::endl;
+		h.drop_adjacency();
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells || args.orient || args.tangents || args.creases) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

@@ -1,7 +1,7 @@
-// First-occurrence numbering on the device: every item gets the id of its key, ids numbered by the key's first item.  Four users:
+// First-occurrence numbering on the device: every item gets the id of its key, ids numbered by the key's first item.  Five users:
 // the render build's unweld (corners -> output vertices, render.cpp), the ingest's weld (rows -> records, ingest.cpp), the edges
-// of a render build (triangle sides -> edges, edges.cpp) and the vertices of its shells (corners -> (shell, decoded vertex),
-// shells.cpp).  Kernels, wave64, an item per lane:
+// of a render build (triangle sides -> edges, edges.cpp), the vertices of its shells (corners -> (shell, decoded vertex),
+// shells.cpp) and its split vertices (index slots -> (output vertex, smooth group), creases.cpp).  Kernels, wave64, an item per lane:
 //   k_dedup_insert<Key>  every item into an open-addressing table of item indices (at least 2 n slots, linear probing)
 //   k_dedup_find<Key>    per item the first item of its key; per wavefront of 64 items the mask of first items and their count
 //   k_scan_counts        exclusive scan of the wavefront counts by one block (scan.hip: launch_scan_counts)
@@ -149,6 +149,23 @@ struct ShellVertexKey {
 	}
 };
 
+// creases: the key of slot s is (the output vertex it names, the root of its smooth group)
+struct CreaseKey {
+	using View = CreaseSlotView;
+	const CreaseSlotView &u;
+	uint32_t vertex, root;
+	__device__ __forceinline__ CreaseKey(const CreaseSlotView &u, uint32_t s) : u(u), vertex(u.indices[s]), root(u.root[s]) {}
+	__device__ __forceinline__ uint32_t hash() const
+	{
+		uint32_t h = root * 0x9e3779b1u;   // the root, then the vertex, through murmur3's finaliser
+		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+		h ^= vertex + 0x7f4a7c15u + (h << 6) + (h >> 2);
+		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+		return h;
+	}
+	__device__ __forceinline__ bool same(uint32_t e) const { return e < u.n && u.indices[e] == vertex && u.root[e] == root; }
+};
+
 template <class Key>
 __global__ __launch_bounds__(256) void k_dedup_insert(typename Key::View u)
 {
@@ -248,6 +265,7 @@ void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p) { dedu
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p) { dedup_count<WeldKey>(st, u, p); }
 void launch_dedup_count(hipStream_t st, EdgeView u, const DedupPlan &p) { dedup_count<EdgeKey>(st, u, p); }
 void launch_dedup_count(hipStream_t st, ShellVertexView u, const DedupPlan &p) { dedup_count<ShellVertexKey>(st, u, p); }
+void launch_dedup_count(hipStream_t st, CreaseSlotView u, const DedupPlan &p) { dedup_count<CreaseKey>(st, u, p); }
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via, uint32_t *via_out)
 {
 	if (p.n) hipLaunchKernelGGL(k_dedup_assign, dim3(blocks_for(p.n, 256)), dim3(256), 0, st, p.n, (const uint32_t*)p.first_of, (const uint64_t*)p.masks,

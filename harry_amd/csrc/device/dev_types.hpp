@@ -153,6 +153,36 @@ struct TanWork {
 	uint32_t *sign, *count, *start, *sums, *seg, *hubs, *classes;
 };
 
+// dedup.hip (CreaseKey): the 3 T index slots of a render build's triangles (creases.cpp).  The key of slot s is the pair (the output
+// vertex indices[s], the root root[s] of the slot's smooth group).  n (slots), mask and table are the launcher's
+struct CreaseSlotView {
+	const uint32_t *indices, *root;
+	uint32_t n, mask;
+	uint32_t *table;
+};
+// creases.hip: the adjacency it reads (tri_adjacency.hpp), the edges' cosines, the float rows of the positions (pos_stride floats per
+// output vertex) and what it writes.  nv: decoded vertices; ng groups and nw split vertices (0 until they are counted); angle:
+// corner-angle weights; ids: the slots' split vertices ("indices" of the result)
+struct CreaseView : TriAdjacency {
+	const float *edge_cos, *pos;
+	const uint32_t *ids;
+	uint32_t *edge_class, *slot_group, *render_vertex, *vertex_source;
+	float *normals;
+	double cos_limit;
+	uint32_t pos_stride, nv, ng, nw;
+	int32_t angle;
+};
+// ... and its working arrays, laid out by creases.cpp: par / root / flag [n], num [n + 1], sums: scan_sums_words(n) (it serves the
+// scan over the n flags and the one over the ng <= n counters); eclass [ne]; first_slot [n] (nw <= n used); terms [T] rows of 3
+// doubles; count: ng <= n zeroed counters (the scatter's cursors afterwards; they lie where flag lay); start [n + 1]; seg [n] (where
+// par lay); gnormal [n] rows of 3 floats (ng used); vgroups [nv] zeroed; hubs: 1 + creases_hub_capacity(n) words, the first zeroed;
+// classes: 4 zeroed counters -- SMOOTH, SHARP, other edges, decoded vertices with more than one group
+struct CreaseWork {
+	uint32_t *par, *root, *flag, *num, *sums, *eclass, *first_slot, *count, *start, *seg, *vgroups, *hubs, *classes;
+	double *terms;
+	float *gnormal;
+};
+
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
 struct RunPlace {

@@ -186,6 +186,7 @@ void launch_dedup_count(hipStream_t st, UnweldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, WeldView u, const DedupPlan &p);
 void launch_dedup_count(hipStream_t st, EdgeView u, const DedupPlan &p);   // the sides of a render build's triangles (edges.cpp)
 void launch_dedup_count(hipStream_t st, ShellVertexView u, const DedupPlan &p);   // the corners of its triangles by (shell, decoded vertex) (shells.cpp)
+void launch_dedup_count(hipStream_t st, CreaseSlotView u, const DedupPlan &p);   // their index slots by (output vertex, smooth group) (creases.cpp)
 // p.ids[i] = id of item i; per id below nout: first_item[id] = its first item, via_out[id] = via[that item] (via == nullptr: none)
 void launch_dedup_assign(hipStream_t st, const DedupPlan &p, uint32_t nout, uint32_t *first_item, const uint32_t *via = nullptr, uint32_t *via_out = nullptr);
 void launch_iota(hipStream_t st, uint32_t n, uint32_t *out);   // out[i] = i
@@ -221,6 +222,15 @@ void launch_edges(hipStream_t st, const EdgesView &v, uint32_t *count, uint32_t 
 // (dev_types.hpp).  Every row of v.tangents and, where given, v.bitangents is written
 uint32_t tangents_hub_capacity(uint32_t nslots);
 void launch_tangents(hipStream_t st, const TanView &v, const TanWork &w);
+
+// hard edges and split normals of a render build (creases.hip; driver: creases.cpp), behind its edges build with geometry.  The
+// working arrays and what is zeroed: CreaseWork (dev_types.hpp).  launch_creases_groups: w.eclass, the classes' counters, the
+// union-find over the slots, w.root and the scan of the root flags: w.num[n] = the number of groups, on the device.
+// launch_creases_normals (v.ng and v.nw known, the outputs allocated, v.ids and v.render_vertex numbered, w.first_slot filled):
+// every row of edge_class, slot_group, vertex_source and normals
+uint32_t creases_hub_capacity(uint32_t nslots);
+void launch_creases_groups(hipStream_t st, const CreaseView &v, const CreaseWork &w);
+void launch_creases_normals(hipStream_t st, const CreaseView &v, const CreaseWork &w);
 
 // shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the

@@ -1,4 +1,4 @@
-// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp): the
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp): the
 // plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
 // that one build is the build of another (result_build.cpp).
 #pragma once
@@ -52,6 +52,11 @@ void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 // with a zero row, mirrored, mixed, uv-degenerate triangles, 0
 typedef TopologyResult TangentsResult;
 void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, TangentsResult &out);   // flags: HRY_TANGENTS_*
+// creases.cpp: hard edges and split normals of a render build behind its edges build with geometry (include/harry_amd.h:
+// hry_creases_build).  summary: W split vertices, G groups, SMOOTH edges, SHARP edges, decoded vertices with more than one group,
+// edges of the other classes
+typedef TopologyResult CreasesResult;
+void creases_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, double cos_limit, uint32_t flags, CreasesResult &out);   // flags: HRY_CREASES_*
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise

@@ -18,6 +18,7 @@
  *   hry_shells_build    (no counterpart: connected shells of a render build, their counts, loops, area, volume and box, as device buffers)
  *   hry_orient_build    (no counterpart: which triangles of a render build to turn for a consistent winding per patch, as device buffers)
  *   hry_tangents_build  (no counterpart: a tangent frame per output vertex of a render build, from its positions, uv and normals, as device buffers)
+ *   hry_creases_build   (no counterpart: hard edges at a crease limit, vertices split along them and a normal per split vertex, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -176,6 +177,7 @@ int hry_list_type(const hry_mesh *m, int l, int c);
 int hry_list_quant(const hry_mesh *m, int l, int c);
 int hry_list_offset(const hry_mesh *m, int l, int c);
 int hry_list_interp_ncomp(const hry_mesh *m, int l, int interp);   /* components of list l with interpretation `interp` (mixing.h ids: 0 POS, 1 NORMAL, 16 TEX); 0: none, or no such list */
+int hry_list_interp_offset(const hry_mesh *m, int l, int interp);  /* the component of list l its first component of that interpretation is; -1: none, or no such list */
 const uint8_t *hry_list_data(const hry_mesh *m, int l);
 const uint8_t *hry_list_min(const hry_mesh *m, int l);
 const uint8_t *hry_list_max(const hry_mesh *m, int l);
@@ -490,6 +492,76 @@ int hry_tangents_copy(hry_ctx *ctx, const hry_tangents *t, const char *name, voi
 int hry_tangents_summary(const hry_tangents *t, uint64_t out[6]);
 int hry_tangents_stat(const hry_tangents *t, double *device_ms, uint64_t *uploaded_bytes);
 void hry_tangents_free(hry_tangents *t);
+
+/* ---- hard edges and split normals of a render build ---------------------------------------------------------------------------
+ * The normals of a render build are smooth everywhere: one per decoded vertex.  hry_creases_build takes a crease limit, splits every
+ * vertex where the surface folds more sharply than that, and gives each split vertex the normal of its own smooth fan -- on ctx's
+ * device.  r is a render build of m; e is an edges build of r WITH HRY_EDGES_GEOMETRY (without it: HRY_E_ARG, and the text names
+ * the flag).  The build reads r's "indices", "vertex_source", "tri_face" and the float rows of its position list, and e's
+ * "edge_offsets", "edge_sides" and "edge_cos", where they lie in HBM: nothing is uploaded (uploaded_bytes is 0), the handle owns one
+ * allocation like the other results, and r and e may be freed afterwards.
+ * Let T be the triangles, U the output vertices of r, E the edges, I = indices, vs = vertex_source; slot s = 3 t + k is corner k of
+ * triangle t, and side s runs from I[s] to the next corner of t.  P[u], a . b, a x b and |a| as in the edges' contract (the same
+ * position list, the same HRY_E_UNSUPPORTED refusals).  Every floating-point operation is an individually rounded IEEE double
+ * operation, in the written order; there are no floating-point atomics.
+ * The limit is a cosine, not an angle, so that the decision is exact at equality: a cube's edge_cos is exactly 0, while
+ * cos(radians(90)) is 6.1e-17.  cos_limit must not be NaN (HRY_E_ARG); every other value is legal: <= -1 makes every eligible edge
+ * smooth, > 1 makes every real edge sharp (flat shading).
+ * Buffers by name:
+ *   "edge_class"     u32 [E]     HRY_CREASE_*.  The first rule that applies:
+ *                                  BOUNDARY     the edge has one side
+ *                                  NONMANIFOLD  it has more than two
+ *                                  DEGENERATE   both ends of its first side are the same decoded vertex
+ *                                  MISORIENTED  both sides run from the same decoded vertex to the same decoded vertex
+ *                                  SMOOTH       both sides have the same tri_face: a fan diagonal of a polygon is never a crease
+ *                                  DEGENERATE   edge_cos is exactly 2.0f (a side's triangle has no normal)
+ *                                  SMOOTH       where (double)edge_cos[e] >= cos_limit, else SHARP
+ *   "slot_group"     u32 [T, 3]  the smooth group of every slot.  Across a SMOOTH edge with sides p < q, and for each of its two
+ *                                decoded end vertices v, the slot of p at v is united with the slot of q at v; the slot of side
+ *                                3 t + k at v is 3 t + k if vs[I[t][k]] == v, else 3 t + (k + 1) % 3.  Nothing else unites slots.
+ *                                A group is named by its smallest slot; groups are numbered 0 .. G-1 by ascending smallest slot
+ *   "indices"        u32 [T, 3]  the split vertex of every slot.  The key of slot s is (I[s], group of s); slots with equal keys
+ *                                share one split vertex; split vertices are numbered 0 .. W-1 by first occurrence over ascending s
+ *   "render_vertex"  u32 [W]     the output vertex of r a split vertex stands for: any "list<l>" row of r follows by a gather
+ *   "vertex_source"  u32 [W]     its decoded vertex, vs[render_vertex[w]]
+ *   "normals"        f32 [W, 3]  (float)(S_g / |S_g|) per component, g the group of w's slots; zeros where |S_g| is 0 or not finite
+ * A uv seam inside a smooth group therefore still gives two split vertices -- I differs -- with the same normal bits: the unweld
+ * does not crease shading, only the limit does.
+ * The term of slot (t, k): N_t = (P[I[t][1]] - P[I[t][0]]) x (P[I[t][2]] - P[I[t][0]]) (default: area weights), or with
+ * HRY_CREASES_ANGLE_WEIGHTED theta * (N_t / |N_t|), the quotient and the product per component, theta = atan2(|a x b|, a . b) with
+ * a = P[next corner] - P[corner], b = P[previous corner] - P[corner] within the triangle.  A triangle whose |N_t| is 0 or not finite
+ * contributes nothing.
+ * S_g starts from +0 and adds the terms of the group's slots in ascending s, one after the other.  A group of more than 32 slots (n
+ * of them) instead sums 256 consecutive ranges of ceil(n / 256) slots each in that way and adds the 256 partial sums in range
+ * order, as the normals do: an association n alone determines.
+ * (Where everything is smooth -- an oriented manifold triangle mesh and cos_limit <= -1 -- W = U, render_vertex is a permutation,
+ * render_vertex[indices] is r's "indices" -- equal to "indices" itself where r's vertices are numbered by first use -- and
+ * normals[w] has the bits of HRY_RENDER_VERTEX_NORMALS' row render_vertex[w] with the same weights.)
+ * Determinism: the bits of every buffer depend on r, e, cos_limit and the flags alone -- not on the run, on residency, or on the
+ * order atomics complete in.
+ * Refusals: null arguments, unknown flag bits, a NaN limit, an r or e that does not fit m or each other (U / T / nf / E) or that
+ * lives on another device, an e without geometry: HRY_E_ARG; 3 T > 2^31: HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable.
+ * Out of scope: writing split normals into an OBJ or PLY, a tangents build over split vertices, and crease-aware terms per polygon
+ * (the terms are the fan triangles').
+ *   hry_creases_count    W, the split vertices
+ *   hry_creases_get / _copy / _stat  as hry_edges_get / _copy / _stat
+ *   hry_creases_summary  out = { W, G, SMOOTH edges, SHARP edges, decoded vertices with more than one group, edges of the classes
+ *                        BOUNDARY .. DEGENERATE }: device reductions during the build, no buffer is downloaded for them */
+typedef struct hry_creases hry_creases;
+#define HRY_CREASES_ANGLE_WEIGHTED 1u   /* terms weighted by the corner's angle instead of triangle area */
+#define HRY_CREASE_SMOOTH      0u
+#define HRY_CREASE_SHARP       1u
+#define HRY_CREASE_BOUNDARY    2u
+#define HRY_CREASE_NONMANIFOLD 3u
+#define HRY_CREASE_MISORIENTED 4u
+#define HRY_CREASE_DEGENERATE  5u
+int hry_creases_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, double cos_limit, uint32_t flags, hry_creases **out);
+uint64_t hry_creases_count(const hry_creases *c);                 /* W: split output vertices */
+int hry_creases_get(const hry_creases *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_creases_copy(hry_ctx *ctx, const hry_creases *c, const char *name, void *dst, int dst_is_device);
+int hry_creases_summary(const hry_creases *c, uint64_t out[6]);
+int hry_creases_stat(const hry_creases *c, double *device_ms, uint64_t *uploaded_bytes);
+void hry_creases_free(hry_creases *c);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
