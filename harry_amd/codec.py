@@ -699,6 +699,76 @@ class Codec:
         render_device_ms / render_uploaded_bytes: hry_render_stat of the render build before both"""
         return dict(getattr(self, "_creases_stat", {}))
 
+    # ---- vertex areas and curvatures of a render build (include/harry_amd.h: hry_curvature_build)
+    CURVATURE_BUFFERS = ("vertex_class", "vertex_area", "angle_defect", "gaussian", "mean_normal", "mean")
+    CURVATURE_SUMMARY = ("vertices", "interior", "boundary", "irregular", "isolated", "degenerate")
+    CURVATURE_TOTALS = ("area", "defect", "mean_integral")
+
+    def _curvature(self, mesh: Mesh, fill) -> dict:
+        """the render build, its edges build, the curvature build behind both; the curvature's buffers go to fill(family, name, rows,
+        width, type, handle); all three handles are freed whatever happens"""
+        L = nat.load()
+        r, e, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
+            try:
+                nat.check(L.hry_curvature_build(self.h, mesh.h, r, e, 0, C.byref(c)))
+                try:
+                    out = {}
+                    for name in self.CURVATURE_BUFFERS:
+                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+                        nat.check(L.hry_curvature_get(c, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+                        out[name] = fill("curvature", name, rows.value, width.value, typ.value, c)
+                    d, up, ed, s, t = C.c_double(), C.c_uint64(), C.c_double(), (C.c_uint64 * 6)(), (C.c_double * 3)()
+                    nat.check(L.hry_curvature_stat(c, C.byref(d), C.byref(up)))
+                    nat.check(L.hry_edges_stat(e, C.byref(ed), None))
+                    nat.check(L.hry_curvature_summary(c, s))
+                    nat.check(L.hry_curvature_totals(c, t))
+                    self._curvature_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges_device_ms": ed.value,
+                                            **{k: int(s[i]) for i, k in enumerate(self.CURVATURE_SUMMARY)},
+                                            **{k: float(t[i]) for i, k in enumerate(self.CURVATURE_TOTALS)}}
+                    return out
+                finally:
+                    L.hry_curvature_free(c)
+            finally:
+                L.hry_edges_free(e)
+        finally:
+            L.hry_render_free(r)
+
+    def curvature_numpy(self, mesh: Mesh, principal: bool = False) -> dict:
+        """the discrete curvatures of the mesh's render build (hry_curvature_build), copied to host arrays of U rows, row u the value of
+        decoded vertex vertex_source[u]: vertex_class u32 [U] (nat.VERTEX_*: 0 isolated, 1 interior, 2 boundary, 3 irregular, 8 or-ed
+        in: no usable area), vertex_area f32 [U] (mixed Voronoi area), angle_defect f32 [U], gaussian f32 [U], mean_normal f32 [U, 3]
+        (the mean curvature vector H n), mean f32 [U] (positive where the surface is convex towards its normal).
+        principal: also "principal" f32 [U, 2] = (H + r, H - r) with r = sqrt(max(H * H - K, 0)), computed here in float32 from the
+        returned mean and gaussian.  It is no device buffer and has no bit contract: at umbilic points (a sphere) H * H - K cancels
+        and r is ill-conditioned, so a promise about its bits would not be an honest one"""
+        out = self._curvature(mesh, self._fill_numpy)
+        if principal:
+            h, k = out["mean"], out["gaussian"]
+            r = np.sqrt(np.maximum(h * h - k, np.float32(0)))
+            out["principal"] = np.stack([h + r, h - r], axis=1).astype(np.float32)
+        return out
+
+    def curvature(self, mesh: Mesh, principal: bool = False) -> dict:
+        """the same buffers as torch tensors on this codec's device, copied device to device: float32 and int32; "principal" in plain
+        torch, float32, with the same caveat"""
+        out = self._curvature(mesh, self._fill_torch(mesh))
+        if principal:
+            import torch   # only here: the rest of the package does not need torch
+            h, k = out["mean"], out["gaussian"]
+            r = torch.sqrt(torch.clamp(h * h - k, min=0))
+            out["principal"] = torch.stack([h + r, h - r], dim=1)
+        return out
+
+    def curvature_stat(self) -> dict:
+        """of the last curvature / curvature_numpy: device_ms (the kernels), uploaded_bytes (0), edges_device_ms (of the edges build
+        before it), hry_curvature_summary's counts over decoded vertices: vertices (D), interior, boundary, irregular, isolated,
+        degenerate (bit 8: no usable area), and hry_curvature_totals: area (the sum of the vertex areas), defect (of the angle defects:
+        2 pi times the Euler characteristic of a closed manifold mesh), mean_integral (of mean curvature times area)"""
+        return dict(getattr(self, "_curvature_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the

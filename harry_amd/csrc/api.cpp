@@ -21,6 +21,7 @@ struct hry_shells { ShellsResult s; };
 struct hry_orient { OrientResult o; };
 struct hry_tangents { TangentsResult t; };
 struct hry_creases { CreasesResult c; };
+struct hry_curvature { CurvatureResult c; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -122,6 +123,7 @@ static const TopologyResult *result_of(const hry_shells *s) { return s ? &s->s :
 static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o : nullptr; }
 static const TopologyResult *result_of(const hry_tangents *t) { return t ? &t->t : nullptr; }
 static const TopologyResult *result_of(const hry_creases *c) { return c ? &c->c : nullptr; }
+static const TopologyResult *result_of(const hry_curvature *c) { return c ? &c->c : nullptr; }
 static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
 static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
 
@@ -766,6 +768,24 @@ int hry_creases_copy(hry_ctx *ctx, const hry_creases *c, const char *name, void 
 int hry_creases_summary(const hry_creases *c, uint64_t out[6]) { return handle_summary(result_of(c), out, 6); }
 int hry_creases_stat(const hry_creases *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
 void hry_creases_free(hry_creases *c) { delete c; }
+
+// ---- vertex areas and curvatures of a render build (curvature.cpp)
+int hry_curvature_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_curvature **out)
+{
+	return handle_build(ctx, m && r && e, out, [&](hry_curvature &c) { curvature_build(ctx->cx, m->m, r->r, e->e, flags, c.c); });
+}
+uint64_t hry_curvature_count(const hry_curvature *c) { const NamedBuf *b = c ? c->c.find("vertex_class") : nullptr; return b ? b->rows : 0; }
+int hry_curvature_get(const hry_curvature *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(c), name, dev, rows, width, type, false); }
+int hry_curvature_copy(hry_ctx *ctx, const hry_curvature *c, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(c), name, "curvature buffer", dst, dst_is_device, true); }
+int hry_curvature_summary(const hry_curvature *c, uint64_t out[6]) { return handle_summary(result_of(c), out, 6); }
+int hry_curvature_totals(const hry_curvature *c, double out[3])
+{
+	if (!c || !out) return null_argument();
+	for (int i = 0; i < 3; ++i) out[i] = c->c.totals[i];
+	return HRY_OK;
+}
+int hry_curvature_stat(const hry_curvature *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
+void hry_curvature_free(hry_curvature *c) { delete c; }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
 	if (out) *out = nullptr;

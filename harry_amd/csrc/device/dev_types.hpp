@@ -183,6 +183,26 @@ struct CreaseWork {
 	float *gnormal;
 };
 
+// curvature.hip: the adjacency it reads (tri_adjacency.hpp), the float rows of the positions (pos_stride floats per output vertex)
+// and the six buffers it writes, nout rows each.  nv: decoded vertices
+struct CurvView : TriAdjacency {
+	const float *pos;
+	uint32_t *vertex_class;
+	float *area, *defect, *gaussian, *mean_normal, *mean;
+	uint32_t pos_stride, nv;
+};
+// ... and its working arrays, laid out by curvature.cpp: ends [nv] zeroed (bit 0: an end of an edge with one side, bit 1: of one with
+// more than two); count [nv] zeroed (the scatter's cursors afterwards); start [nv + 1]; sums: scan_sums_words(nv); seg [n]; hubs:
+// 1 + curvature_hub_capacity(n) words, the first zeroed; cls [nv] and rows [nv] rows of 7 floats: what the expansion copies (area,
+// defect, gaussian, mean_normal x y z, mean); terms [nv] rows of 3 doubles: what a vertex adds to the totals; fold_a / fold_b: the
+// rounds of the totals' reduction, ceil(nv / 256) and ceil(ceil(nv / 256) / 256) rows of 3 doubles; classes: 8 zeroed counters --
+// interior, boundary, irregular, isolated vertices, vertices with bit 8
+struct CurvWork {
+	uint32_t *ends, *count, *start, *sums, *seg, *hubs, *cls, *classes;
+	float *rows;
+	double *terms, *fold_a, *fold_b;
+};
+
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
 struct RunPlace {

@@ -232,6 +232,14 @@ uint32_t creases_hub_capacity(uint32_t nslots);
 void launch_creases_groups(hipStream_t st, const CreaseView &v, const CreaseWork &w);
 void launch_creases_normals(hipStream_t st, const CreaseView &v, const CreaseWork &w);
 
+// vertex areas and curvatures of a render build (curvature.hip; driver: curvature.cpp), behind its edges build.  The working arrays
+// and what is zeroed: CurvWork (dev_types.hpp).  Every row of the six buffers of v is written; returns where the totals' one row of
+// three doubles will lie on the device (nullptr: no decoded vertex).  curvature_fold_rows: the rows one round of the totals'
+// reduction leaves of `rows`
+uint32_t curvature_hub_capacity(uint32_t nslots);
+uint32_t curvature_fold_rows(uint32_t rows);
+const double *launch_curvature(hipStream_t st, const CurvView &v, const CurvWork &w);
+
 // shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the
 // outputs allocated, counts zeroed, face_shell filled with 0xff): tri_shell, face_shell, shell_first, the triangle and face columns.

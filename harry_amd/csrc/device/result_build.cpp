@@ -1,4 +1,4 @@
-// Is one result the build of another?  What edges.cpp asks of a render build and shells.cpp / orient.cpp / creases.cpp of a render
+// Is one result the build of another?  What edges.cpp asks of a render build and shells.cpp / orient.cpp / creases.cpp / curvature.cpp of a render
 // build and its edges build before a kernel reads them, and the adjacency the kernels of the last two then read (result_build.hpp).
 #include <hip/hip_runtime.h>
 

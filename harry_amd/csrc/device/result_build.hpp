@@ -1,4 +1,4 @@
-// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp): the
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp, curvature.cpp): the
 // plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
 // that one build is the build of another (result_build.cpp).
 #pragma once
@@ -57,6 +57,13 @@ void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t 
 // edges of the other classes
 typedef TopologyResult CreasesResult;
 void creases_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, double cos_limit, uint32_t flags, CreasesResult &out);   // flags: HRY_CREASES_*
+// curvature.cpp: vertex areas and curvatures of a render build behind its edges build (include/harry_amd.h: hry_curvature_build).
+// summary: D decoded vertices, interior, boundary, irregular, isolated, vertices with bit 8; totals: the sums of A_d, of the angle
+// defects and of H_d A_d
+struct CurvatureResult : TopologyResult {
+	double totals[3] = {};
+};
+void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, CurvatureResult &out);   // flags: none
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise

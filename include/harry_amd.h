@@ -19,6 +19,7 @@
  *   hry_orient_build    (no counterpart: which triangles of a render build to turn for a consistent winding per patch, as device buffers)
  *   hry_tangents_build  (no counterpart: a tangent frame per output vertex of a render build, from its positions, uv and normals, as device buffers)
  *   hry_creases_build   (no counterpart: hard edges at a crease limit, vertices split along them and a normal per split vertex, as device buffers)
+ *   hry_curvature_build (no counterpart: mixed Voronoi area, angle defect, Gaussian and mean curvature per vertex of a render build, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -562,6 +563,79 @@ int hry_creases_copy(hry_ctx *ctx, const hry_creases *c, const char *name, void 
 int hry_creases_summary(const hry_creases *c, uint64_t out[6]);
 int hry_creases_stat(const hry_creases *c, double *device_ms, uint64_t *uploaded_bytes);
 void hry_creases_free(hry_creases *c);
+
+/* ---- vertex areas and curvatures of a render build ------------------------------------------------------------------------------
+ * hry_curvature_build computes, on ctx's device, the discrete operators of Meyer, Desbrun, Schroeder and Barr per vertex: the mixed
+ * Voronoi area, the angle defect, the Gaussian curvature, the mean curvature vector and the mean curvature -- what "edge_cot" of the
+ * edges build is the weight of.  r is a render build of m; e is an edges build of r (HRY_EDGES_GEOMETRY is not needed).  The build
+ * reads r's "indices", "vertex_source" and the float rows of its position list, and e's "edge_offsets" and "edge_sides", where they
+ * lie in HBM: nothing is uploaded (uploaded_bytes is 0), the handle owns one allocation like the other results, and r and e may be
+ * freed afterwards.  flags must be 0.
+ * Let T be the triangles, U the output vertices of r, D = the decoded vertices of m, I = indices, vs = vertex_source; slot s = 3 t + k
+ * is corner k of triangle t and belongs to decoded vertex vs[I[t][k]].  P[u], a . b, a x b and |a| as in the edges' contract (the
+ * same position list, the same HRY_E_UNSUPPORTED refusals).  Every floating-point operation is an individually rounded IEEE double
+ * operation, in the written order; sums of products are evaluated left to right; there are no floating-point atomics.
+ * At slot s = 3 t + k, within triangle t:
+ *   o = P[I[t][k]], a = P[I[t][(k + 1) % 3]] - o, b = P[I[t][(k + 2) % 3]] - o;
+ *   x_k = |a x b|, d_k = a . b, c_k = d_k / x_k, counted as 0 where x_k is 0 or not finite or where c_k is not finite (the rule of
+ *   "edge_cot").  N_t = (P[I[t][1]] - P[I[t][0]]) x (P[I[t][2]] - P[I[t][0]]).
+ *   A triangle whose |N_t| is 0 or not finite contributes no terms at any of its slots.  A fan diagonal of a polygon is an edge like
+ *   any other: the quantities are those of the triangles as rendered.
+ * The terms of a slot of a usable triangle (indices of c are corners modulo 3: the angle opposite edge a is at corner k + 2):
+ *   angle        theta_s = atan2(x_k, d_k)
+ *   mixed area   with area_t = 0.5 * |N_t|: where any of d_0, d_1, d_2 is < 0 (an obtuse triangle), A_s = 0.5 * area_t where
+ *                d_k < 0 and 0.25 * area_t otherwise; else A_s = 0.125 * ((a . a) * c_{k+2} + (b . b) * c_{k+1})
+ *   Laplace      L_s = -(c_{k+2} * a + c_{k+1} * b), per component
+ *   normal       N_t
+ * The sums of decoded vertex d -- Theta_d, A_d, L_d (three components), S_d (three components) -- start from +0 and add the terms
+ * of d's slots in ascending s, one after the other.  A vertex with more than 32 slots (n of them) instead sums 256 consecutive
+ * ranges of ceil(n / 256) slots each in that way, each from +0, and adds the 256 partial sums in range order, as the normals and
+ * creases do: an association n alone determines.
+ * The class of d, from e: 0 isolated, d has no slot at all; 3 irregular, d is a decoded end (vs of either end of the first side) of
+ * an edge with more than two sides; 2 boundary, d is a decoded end of an edge with exactly one side and is not irregular; 1 interior,
+ * everything else.  8 is or-ed in where A_d is not usable, that is where A_d > 0 and finite fails -- which includes every isolated
+ * vertex: it reads 8.
+ * Buffers by name, U rows each; row u holds the value of decoded vertex vs[u], as "normals" does:
+ *   "vertex_class"  u32 [U]     as above
+ *   "vertex_area"   f32 [U]     (float)A_d; +0 where A_d is not usable
+ *   "angle_defect"  f32 [U]     (float)(tau - Theta_d), tau the double nearest 2 pi for classes 1 and 3 and the double nearest pi for
+ *                               class 2 (bit 8 aside); +0 for class 0
+ *   "gaussian"      f32 [U]     (float)((tau - Theta_d) / A_d); +0 where A_d is not usable
+ *   "mean_normal"   f32 [U, 3]  (float)(L_d / (4.0 * A_d)) per component, the product first: the mean curvature vector H n.  Zeros
+ *                               where A_d is not usable
+ *   "mean"          f32 [U]     (float)H_d, H_d = (L_d . S_d) / (|S_d| * (4.0 * A_d)): positive where the surface is convex towards
+ *                               its area-weighted normal.  Where |S_d| is 0 or not finite, H_d = |L_d| / (4.0 * A_d).  +0 where A_d
+ *                               is not usable
+ * Totals: the term row of d is (A_d, tau - Theta_d, H_d * A_d), or (+0, +0, +0) where d is of class 0 or has bit 8.  The rows are
+ * reduced in rounds, per column: a round replaces the rows by the sums of their consecutive chunks of 256 rows -- chunk c is the rows
+ * [256 c, 256 c + 256), its sum starts from +0 and adds them in ascending order -- and rounds follow, at least one, until one row
+ * is left.  D = 0: the totals are +0.
+ * Determinism: the bits of every buffer and of the totals depend on r and e alone -- not on the run, on residency, or on the order
+ * atomics complete in.
+ * Refusals: null arguments, any flag bit, an r or e that does not fit m or each other (U / T / nf / E) or that lives on another
+ * device: HRY_E_ARG; 3 T > 2^31, or a position list the normals' rule refuses: HRY_E_UNSUPPORTED; *out stays NULL and ctx stays
+ * usable.
+ * Out of scope: principal directions, curvature of polygon faces other than through their fan triangles, meshes on several devices.
+ *   hry_curvature_count    U, the rows
+ *   hry_curvature_get / _copy / _stat  as hry_creases_get / _copy / _stat
+ *   hry_curvature_summary  out = { D, interior, boundary, irregular, isolated (classes by their low three bits), vertices with bit
+ *                          8 }, counted over decoded vertices: device reductions during the build, no buffer is downloaded for them
+ *   hry_curvature_totals   out = { sum of A_d, sum of (tau - Theta_d), sum of H_d * A_d } as above.  The second divided by 2 pi is,
+ *                          on a closed manifold mesh, its Euler characteristic */
+typedef struct hry_curvature hry_curvature;
+#define HRY_VERTEX_ISOLATED   0u
+#define HRY_VERTEX_INTERIOR   1u
+#define HRY_VERTEX_BOUNDARY   2u
+#define HRY_VERTEX_IRREGULAR  3u
+#define HRY_VERTEX_DEGENERATE 8u   /* or-ed in: the vertex has no usable area */
+int hry_curvature_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_curvature **out);
+uint64_t hry_curvature_count(const hry_curvature *c);             /* U: the rows, output vertices of r */
+int hry_curvature_get(const hry_curvature *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_curvature_copy(hry_ctx *ctx, const hry_curvature *c, const char *name, void *dst, int dst_is_device);
+int hry_curvature_summary(const hry_curvature *c, uint64_t out[6]);
+int hry_curvature_totals(const hry_curvature *c, double out[3]);
+int hry_curvature_stat(const hry_curvature *c, double *device_ms, uint64_t *uploaded_bytes);
+void hry_curvature_free(hry_curvature *c);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
