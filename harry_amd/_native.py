@@ -159,6 +159,7 @@ def load():
     L.hry_plan_free.argtypes = [vp]
     L.hry_walk_run_shard.restype = C.c_int; L.hry_walk_run_shard.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.hry_analysis_check.restype = C.c_int; L.hry_analysis_check.argtypes = [vp, vp]
+    L.hry_analysis_tables.restype = C.c_int; L.hry_analysis_tables.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.hry_plan_ncomponents.restype = C.c_uint32; L.hry_plan_ncomponents.argtypes = [vp]
     L.hry_plan_ngroups.restype = C.c_uint32; L.hry_plan_ngroups.argtypes = [vp]
     L.hry_plan_triangles.restype = C.c_uint64; L.hry_plan_triangles.argtypes = [vp, C.c_int]

@@ -240,6 +240,31 @@ def _walk_arrays(w) -> dict:
         L.hry_walk_free(w)
 
 
+ANALYSIS_TABLES = ("ncomp", "by_rank", "seed", "n_faces", "n_halfedges", "fresh", "group", "face_lo", "face_hi", "vtx_lo", "vtx_hi", "comp", "spans")
+
+
+def _analysis_tables(ctx, mesh: Mesh, on_device: bool) -> dict:
+    L = nat.load()
+    w = C.c_void_p()
+    nat.check(L.hry_analysis_tables(ctx, mesh.h, int(on_device), C.byref(w)))
+    try:
+        out = {}
+        for name in ANALYSIS_TABLES + (("twin_over",) if on_device else ()):
+            p = C.c_void_p()
+            n = L.hry_walk_get(w, name.encode(), C.byref(p))
+            out[name] = np.frombuffer(C.string_at(p, n * 4), dtype=np.uint32).copy() if n else np.zeros(0, np.uint32)
+        out["spans"] = out["spans"].reshape(-1, 4)
+        return out
+    finally:
+        L.hry_walk_free(w)
+
+
+def analysis_tables_host(mesh: Mesh) -> dict:
+    """Host-only: the component analysis of `mesh` as numpy arrays by name (hry_analysis_tables without a context; matches the twins
+    on the host if they are pending)."""
+    return _analysis_tables(None, mesh, False)
+
+
 class ShardPlan:
     """Distribution of one mesh over n shards by groups of connected components (include/harry_amd.h, hry_shard_plan)."""
 
@@ -345,6 +370,13 @@ class Codec:
     def analysis_check(self, mesh: "Mesh") -> None:
         """Development / tests: the component analysis of `mesh` on the device against the host's, table by table (hry_analysis_check)."""
         nat.check(nat.load().hry_analysis_check(self.h, mesh.h))
+
+    def analysis_tables(self, mesh: "Mesh", where: str = "device") -> dict:
+        """Development / tests: the component analysis of `mesh` as numpy arrays by name (hry_analysis_tables), the device's (uploads the
+        mesh unless it is resident; with "twin_over", the path its twin matching took) or the host's."""
+        if where not in ("device", "host"):
+            raise ValueError("where: 'device' or 'host'")
+        return _analysis_tables(self.h if where == "device" else None, mesh, where == "device")
 
     __del__ = close
 

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
 
 #include "device/context.hpp"
@@ -31,6 +32,7 @@ struct hry_walk {
 	mutable std::vector<uint32_t> op_thr, op_cum;    // op_position_table, on first request
 	mutable bool have_table = false;
 	mutable std::vector<uint8_t> snap_section;       // the border snapshots as the chunked container's directory holds them, on first request
+	std::map<std::string, std::vector<uint32_t>> tables;   // hry_analysis_tables: the arrays of a component analysis by name
 	void table() const { if (!have_table) { op_position_table(w, op_thr, op_cum); have_table = true; } }
 	void snapshots() const
 	{
@@ -501,6 +503,31 @@ int hry_analysis_check(hry_ctx *ctx, hry_mesh *m)
 		same("by_rank", D.by_rank, H.by_rank);
 	});
 }
+int hry_analysis_tables(hry_ctx *ctx, hry_mesh *m, int on_device, hry_walk **out)
+{
+	if (!m || !out || (on_device && !ctx)) { g_last_error = "invalid argument"; return HRY_E_ARG; }
+	*out = nullptr;
+	if (on_device) touched(ctx);
+	touched(m);
+	return guarded([&] {
+		std::unique_ptr<hry_walk> w(new hry_walk());
+		check_codable(m->m);
+		if (m->m.general || !m->m.shard.seeds.empty()) throw Error(HRY_E_ARG, "analysis tables: a mesh in the PLY layout that is not a shard");
+		ComponentAnalysis A;
+		if (on_device) {
+			if (m->m.device_token == 0 || m->m.device_token != ctx->cx.resident_token) ctx->cx.upload_mesh(m->m);
+			device_component_analysis(ctx->cx, m->m, A, true);
+			w->tables["twin_over"] = { m->m.twin_over };
+		} else analyse_components(m->m, A);
+		auto &T = w->tables;
+		T["ncomp"] = { A.ncomp };
+		T["by_rank"] = A.by_rank; T["seed"] = A.seed; T["n_faces"] = A.n_faces; T["n_halfedges"] = A.n_halfedges; T["fresh"] = A.fresh; T["group"] = A.group;
+		T["face_lo"] = A.face_lo; T["face_hi"] = A.face_hi; T["vtx_lo"] = A.vtx_lo; T["vtx_hi"] = A.vtx_hi;
+		T["comp"].assign(A.comp.begin(), A.comp.end());
+		start_face_spans(m->m.nf, T["spans"]);
+		*out = w.release();
+	});
+}
 uint32_t hry_plan_ncomponents(const hry_plan *p) { return p ? p->p.A.ncomp : 0; }
 uint32_t hry_plan_ngroups(const hry_plan *p)
 {
@@ -622,6 +649,7 @@ size_t hry_walk_get(const hry_walk *w, const char *name, const void **ptr)
 		if (n.compare(4, 4, "_val") == 0) return ret(r.grp_val[g]);
 		if (n.compare(4, 4, "_pos") == 0) return ret(r.grp_pos[g]);
 	}
+	if (auto it = w->tables.find(n); it != w->tables.end()) return ret(it->second);
 	*ptr = nullptr;
 	return 0;
 }

@@ -3,7 +3,9 @@
 // mesh -- the connected components, their coding order (the reference's start-face sequence, writer.cc:40-46), how many faces,
 // half-edges and new vertices each brings and which of them share a vertex (cbm/encoder.h:79-113,187) -- so that the walk can run
 // on the host threads from its first component on, every component writing where it belongs.  Same tables as the host's, entry
-// for entry (tests/test_gpu_chunked.py compares them); only the per-face labels stay on the device.
+// for entry: hry_analysis_check compares the two inside the library (tests/test_gpu_chunked.py), hry_analysis_tables hands either
+// side's out, and tests/test_gpu_analysis.py compares both with a numpy restatement (tests/analysis_ref.py) on meshes designed for
+// the kernels' seams (tests/analysis_meshes.py).  The per-face labels stay on the device unless a test asks for them.
 #include <algorithm>
 #include <chrono>
 #include <numeric>
@@ -16,7 +18,8 @@ namespace hry {
 // A: every table of the analysis per coding rank (ComponentAnalysis: ncomp, by_rank, rank_of, seed, n_faces, n_halfedges, fresh, group,
 // face_lo / face_hi, vtx_lo / vtx_hi); A.comp and A.vertex_owner stay empty.  The mesh must be resident on cx with its twins.
 // A mesh of one component returns after the labelling with A.ncomp = 1 and no table.
-void device_component_analysis(Context &cx, const Mesh &m, ComponentAnalysis &A)
+// everything (tests, hry_analysis_tables): the tables of a mesh of one component too, and the labels copied down into A.comp.
+void device_component_analysis(Context &cx, const Mesh &m, ComponentAnalysis &A, bool everything)
 {
 	HIP_OK(hipSetDevice(cx.device));
 	const bool trace = trace_on();
@@ -42,7 +45,7 @@ void device_component_analysis(Context &cx, const Mesh &m, ComponentAnalysis &A)
 	mark("components labelled");
 	A = ComponentAnalysis();
 	A.ncomp = ncomp;
-	if (ncomp < 2) return;   // (one component: the caller walks it in the sequential loop and needs no table)
+	if (ncomp < (everything ? 1u : 2u)) return;   // (one component: the caller walks it in the sequential loop and needs no table)
 	// per-component tables behind the workspace's labels: 5 x u32 + 1 x u64 by component number, 5 x u32 by rank, the spans
 	const size_t words = (size_t)12 * ncomp + spans.size() + 8;
 	cx.d_small.ensure(words * 4 + 64);
@@ -60,6 +63,7 @@ void device_component_analysis(Context &cx, const Mesh &m, ComponentAnalysis &A)
 	std::vector<uint32_t> by_num((size_t)4 * ncomp);   // faces, half-edges, lowest face, highest face + 1, by component number
 	HIP_OK(hipMemcpyAsync(key.data(), d_key, (size_t)ncomp * 8, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipMemcpyAsync(by_num.data(), d_nfaces, (size_t)4 * ncomp * 4, hipMemcpyDeviceToHost, st));
+	if (everything) { A.comp.resize(nf); HIP_OK(hipMemcpyAsync(A.comp.data(), d_label, (size_t)nf * 4, hipMemcpyDeviceToHost, st)); }   // (component numbers since k_cc_face_stats)
 	// (the vertex words go to their neutral value meanwhile)
 	HIP_OK(hipMemsetAsync(ws.vfirst, 0xff, (size_t)nv * 4, st));
 	HIP_OK(hipMemsetAsync(d_fresh, 0, (size_t)ncomp * 4, st));

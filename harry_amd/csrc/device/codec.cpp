@@ -131,6 +131,7 @@ void Context::match_twins(Mesh &m)
 		HIP_OK(hipMemcpyAsync(m.twin.data(), d_twin.p, (size_t)ne * 4, hipMemcpyDeviceToHost, stream));
 		HIP_OK(hipMemcpyAsync(over.data(), d_over, over.size() * 4, hipMemcpyDeviceToHost, stream));
 		HIP_OK(hipStreamSynchronize(stream));
+		m.twin_over = over[0];
 		if (over[0] > dev::twin_overflow_capacity()) {   // a mesh of hubs: the host's matcher does all of it
 			m.twins_pending = true;
 			ensure_twins(m);

@@ -409,6 +409,14 @@ struct Emitter {
 	}
 };
 
+// The reference sends every corner of a component's start face that has no index yet (cbm/encoder.h:76-126) -- a vertex that the face
+// repeats among its first three corners twice, so its stream holds more vertices than the mesh.  Every array here and on the device
+// is sized by the mesh's vertices: such a mesh is refused (once per component: no cost).
+static inline void check_start_face(uint32_t a, uint32_t b, uint32_t c, const uint32_t *sent)
+{
+	if ((a == b && sent[a] == NONE32) || (b == c && sent[b] == NONE32) || (a == c && sent[a] == NONE32))
+		throw Error(HRY_E_UNSUPPORTED, "a component starts at a face that repeats a vertex: the reference codes that vertex twice, which is outside the supported subset");
+}
 // One connected component, starting at face f (encoder.h:68-214).  DEG > 0: every polygon has DEG edges and the face of a
 // half-edge is a division by a compile-time constant; DEG == 0: mixed degrees, table lookup.
 template <int DEG>
@@ -439,6 +447,7 @@ static void walk_component(Mesh &m, WalkState &st, const uint32_t *eface_tab, ui
 	uint32_t e0 = foff[f], e1 = nxt(e0), e2 = nxt(e1);
 	uint32_t a = org[e0], b = org[e1], c = org[e2];
 	int ntri = (int)(foff[f + 1] - foff[f]) - 2, curtri = 1;
+	check_start_face(a, b, c, sent);
 	unsigned mask = (sent[a] != NONE32 ? 4u : 0u) | (sent[b] != NONE32 ? 2u : 0u) | (sent[c] != NONE32 ? 1u : 0u);
 	switch (mask) {
 	case 7: em.iop(I_TRI111); em.vert(sent[a], seen[a]); em.vert(sent[b], seen[b]); em.vert(sent[c], seen[c]); em.numtri(ntri); break;
@@ -802,6 +811,7 @@ static WALK_INLINE void walk_lean(Mesh &m, WalkState &st, const uint32_t *eface_
 	e1 = e0 + 1; e2 = e0 + 2;
 	{
 		const uint32_t e[3] = { e0, e1, e2 }, v[3] = { org[e0], org[e1], org[e2] };
+		check_start_face(v[0], v[1], v[2], sent);
 		const unsigned mask = (sent[v[0]] != NONE32 ? 4u : 0u) | (sent[v[1]] != NONE32 ? 2u : 0u) | (sent[v[2]] != NONE32 ? 1u : 0u);
 		sink.begin(f, mask, next_id, e, v, ntri_to_code());
 		const StartCase &sc = kStartCases[mask];

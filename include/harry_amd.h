@@ -1113,6 +1113,15 @@ int hry_walk_run_shard(hry_mesh *m, const hry_plan *plan, int shard, hry_walk **
  * hry_encode of a large mesh computes on the device before its walk, analysis.cpp) by the device AND by the host, compared table by
  * table; 0 = equal (or fewer than two components), HRY_E_INTERNAL with the first difference otherwise.  Uploads the mesh. */
 int hry_analysis_check(hry_ctx *ctx, hry_mesh *m);
+/* development / tests: that analysis as arrays by name, from either side -- on_device 0: the host's (ctx may be NULL, no GPU is touched),
+ * 1: the device's (uploads the mesh unless it is resident; a mesh of one component gets its tables too, which an encode never asks
+ * for).  Read with hry_walk_get (u32), free with hry_walk_free: "ncomp" (one word); per coding rank "by_rank", "seed", "n_faces",
+ * "n_halfedges", "fresh", "group", "face_lo", "face_hi", "vtx_lo", "vtx_hi"; "comp" = the component number of every face (on the device
+ * the label words, copied down for this call only); "spans" = the start-face sequence of nf faces as (lowest face, highest face,
+ * position of the span's first face, 1 = ascending) sorted by the lowest face; on_device only: "twin_over" (one word) = how many
+ * vertices the device's twin matching left to the host when this mesh's twins were matched (0: none, up to 4096: those vertices
+ * were matched on the host, above: the host matched everything; 0xffffffff: the twins were never matched on a device). */
+int hry_analysis_tables(hry_ctx *ctx, hry_mesh *m, int on_device, hry_walk **out);
 size_t hry_walk_get(const hry_walk *w, const char *name, const void **ptr);
 void hry_walk_free(hry_walk *w);
 
