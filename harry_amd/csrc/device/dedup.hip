@@ -19,6 +19,7 @@
 // reads final values with plain loads.
 #include <hip/hip_runtime.h>
 
+#include "dedup_hash.hpp"
 #include "dev_types.hpp"
 #include "hip_handles.hpp"
 #include "kernels.hpp"
@@ -30,7 +31,8 @@ constexpr uint32_t kNone = 0xffffffffu;
 
 // ---------------------------------------------------------------------------------------------------------
 // Key policies: built once per item (view, item), they supply hash() and same(j): has item j this item's key?
-// The hashes decide the table's contention and probe lengths: part of the behaviour, bit for bit.
+// The hashes decide the table's contention and probe lengths: part of the behaviour, bit for bit.  Their arithmetic is in
+// dedup_hash.hpp, which host code compiles too.
 // ---------------------------------------------------------------------------------------------------------
 // unweld: the key of corner c is (org[c], then per corner-target list in list order the record c names, or kNone where the
 // region of c's face does not bind the list)
@@ -52,11 +54,8 @@ struct UnweldKey {
 	__device__ __forceinline__ UnweldKey(const UnweldView &u, uint32_t c) : u(u), c(c), r(region_of(u, c)) {}
 	__device__ __forceinline__ uint32_t hash() const
 	{
-		uint32_t h = 0x9e3779b9u;
-		for (uint32_t i = 0; i <= u.nlists; ++i) {   // murmur3's finaliser over the running value
-			h ^= key_part(u, c, r, i) + 0x7f4a7c15u + (h << 6) + (h >> 2);
-			h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		}
+		uint32_t h = dh::hash_parts_start();
+		for (uint32_t i = 0; i <= u.nlists; ++i) h = dh::hash_parts_step(h, key_part(u, c, r, i));   // murmur3's finaliser over the running value
 		return h;
 	}
 	__device__ __forceinline__ bool same(uint32_t e) const
@@ -75,10 +74,7 @@ struct WeldKey {
 	__device__ __forceinline__ WeldKey(const WeldView &u, uint32_t r) : u(u), a(u.rec + (size_t)r * u.stride) {}
 	__device__ __forceinline__ uint32_t hash() const
 	{
-		uint32_t h = 0x811c9dc5u;   // FNV-1a over the bytes, then murmur3's finaliser
-		for (uint32_t k = 0; k < u.stride; ++k) h = (h ^ a[k]) * 0x01000193u;
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		return h;
+		return dh::hash_bytes(a, u.stride);   // FNV-1a over the bytes, then murmur3's finaliser
 	}
 	__device__ __forceinline__ bool same(uint32_t e) const
 	{
@@ -105,13 +101,7 @@ struct EdgeKey {
 	}
 	__device__ __forceinline__ EdgeKey(const EdgeView &u, uint32_t s) : u(u) { ends(u, s, lo, hi); }
 	__device__ __forceinline__ uint32_t hash() const
-	{
-		uint32_t h = lo * 0x9e3779b1u;   // the two ends through murmur3's finaliser, one after the other
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		h ^= hi + 0x7f4a7c15u + (h << 6) + (h >> 2);
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		return h;
-	}
+	{ return dh::hash_edge(lo, hi); }   // the two ends through murmur3's finaliser, one after the other
 	__device__ __forceinline__ bool same(uint32_t e) const
 	{
 		if (e >= u.n) return false;
@@ -133,13 +123,7 @@ struct ShellVertexKey {
 	}
 	__device__ __forceinline__ ShellVertexKey(const ShellVertexView &u, uint32_t c) : u(u) { parts(u, c, shell, vertex); }
 	__device__ __forceinline__ uint32_t hash() const
-	{
-		uint32_t h = vertex * 0x9e3779b1u;   // the vertex, then the shell, through murmur3's finaliser
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		h ^= shell + 0x7f4a7c15u + (h << 6) + (h >> 2);
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		return h;
-	}
+	{ return dh::hash_shell_vertex(shell, vertex); }   // the vertex, then the shell, through murmur3's finaliser
 	__device__ __forceinline__ bool same(uint32_t e) const
 	{
 		if (e >= u.n) return false;
@@ -156,13 +140,7 @@ struct CreaseKey {
 	uint32_t vertex, root;
 	__device__ __forceinline__ CreaseKey(const CreaseSlotView &u, uint32_t s) : u(u), vertex(u.indices[s]), root(u.root[s]) {}
 	__device__ __forceinline__ uint32_t hash() const
-	{
-		uint32_t h = root * 0x9e3779b1u;   // the root, then the vertex, through murmur3's finaliser
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		h ^= vertex + 0x7f4a7c15u + (h << 6) + (h >> 2);
-		h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-		return h;
-	}
+	{ return dh::hash_crease(vertex, root); }   // the root, then the vertex, through murmur3's finaliser
 	__device__ __forceinline__ bool same(uint32_t e) const { return e < u.n && u.indices[e] == vertex && u.root[e] == root; }
 };
 
