@@ -99,6 +99,8 @@ TANGENTS_ANGLE_WEIGHTED, TANGENTS_STORED_NORMALS, TANGENTS_BITANGENTS = 1, 2, 4
 CREASES_ANGLE_WEIGHTED = 1
 CREASE_SMOOTH, CREASE_SHARP, CREASE_BOUNDARY, CREASE_NONMANIFOLD, CREASE_MISORIENTED, CREASE_DEGENERATE = 0, 1, 2, 3, 4, 5
 VERTEX_ISOLATED, VERTEX_INTERIOR, VERTEX_BOUNDARY, VERTEX_IRREGULAR, VERTEX_DEGENERATE = 0, 1, 2, 3, 8
+CAST_HOST = 1
+BVH_LEAF = 0x80000000   # a child word of "node_children" with this bit names a leaf
 TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST, TOL_NORMAL_CHORD = 0, 1, 2, 3, 4
 
 _lib = None
@@ -194,7 +196,7 @@ def load():
     L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_render_free.argtypes = [vp]
     for fam, inputs in (("edges", [vp]), ("shells", [vp, vp]), ("orient", [vp, vp]), ("tangents", [vp]),
-                        ("creases", [vp, vp, C.c_double]), ("curvature", [vp, vp])):   # the builds behind a render build: its handle(s) in (creases: and the limit)
+                        ("creases", [vp, vp, C.c_double]), ("curvature", [vp, vp]), ("bvh", [vp])):   # the builds behind a render build: its handle(s) in (creases: and the limit)
         def fn(what, restype, argtypes):
             f = getattr(L, f"hry_{fam}_{what}"); f.restype = restype; f.argtypes = argtypes
         fn("build", C.c_int, [vp, vp] + inputs + [C.c_uint32, C.POINTER(vp)])
@@ -205,6 +207,9 @@ def load():
         fn("stat", C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
         fn("free", None, [vp])
     L.hry_curvature_totals.restype = C.c_int; L.hry_curvature_totals.argtypes = [vp, C.POINTER(C.c_double)]
+    L.hry_bvh_cast.restype = C.c_int
+    L.hry_bvh_cast.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_double, C.c_double, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_double)]
     L.hry_mesh_flip_faces.restype = C.c_int; L.hry_mesh_flip_faces.argtypes = [vp, vp, C.POINTER(vp)]
     L.hry_mesh_from_device.restype = C.c_int
     L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),

@@ -801,6 +801,27 @@ class Codec:
         2 pi times the Euler characteristic of a closed manifold mesh), mean_integral (of mean curvature times area)"""
         return dict(getattr(self, "_curvature_stat", {}))
 
+    # ---- ray queries on a render build (include/harry_amd.h: hry_bvh_build, hry_bvh_cast)
+    def bvh(self, mesh: Mesh) -> "Bvh":
+        """a bounding-volume hierarchy over the triangles of the mesh's render build, built on the device (hry_bvh_build): an owning
+        object like Order, valid whatever the codec does later, until close().  The render build is freed before this returns"""
+        L = nat.load()
+        r, b = C.c_void_p(), C.c_void_p()
+        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
+        try:
+            nat.check(L.hry_bvh_build(self.h, mesh.h, r, 0, C.byref(b)))
+        finally:
+            L.hry_render_free(r)
+        out = Bvh(self, b)
+        self._bvh_stat = out.stat()
+        return out
+
+    def bvh_stat(self) -> dict:
+        """of the last bvh(): device_ms (the kernels), uploaded_bytes (0) and hry_bvh_summary's counts: triangles (T), leaves (L: the
+        live triangles), dead (T - L: a position that is not finite), distinct_codes, depth (internal nodes from the root to the
+        deepest leaf, at most 62)"""
+        return dict(getattr(self, "_bvh_stat", {}))
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the
@@ -1150,6 +1171,114 @@ class Order(_NamedBuffers):
     def to_source(self, t, kind: str = "vertex", out=None):
         """rows in decoded order -> rows in source order: result[i] = t[kind[i]], zero bytes where element i was never coded"""
         return self._apply(t, kind, nat.ORDER_TO_SOURCE, out)
+
+
+class Bvh:
+    """A bounding-volume hierarchy over the triangles of a render build (include/harry_amd.h: hry_bvh_build) and the closest-hit
+    ray cast over it (hry_bvh_cast).  The buffers lie in HBM; every bit of them depends on the render build alone, every bit of a
+    cast on them and the rays alone.  After a cast: hits (rays that hit), box_tests (box intervals the walk evaluated) and device_ms
+    (the kernel) of that cast."""
+
+    BUFFERS = ("leaf_tri", "leaf_code", "leaf_box", "leaf_positions", "node_children", "node_box", "scene_box")
+    SUMMARY = ("triangles", "leaves", "dead", "distinct_codes", "depth")
+
+    def __init__(self, codec: "Codec", handle):
+        self.codec, self.h = codec, handle
+        self.hits = self.box_tests = 0
+        self.device_ms = 0.0
+
+    def close(self):
+        if getattr(self, "h", None):
+            nat.load().hry_bvh_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def count(self) -> int:
+        """L: the leaves, the triangles with finite positions"""
+        return int(nat.load().hry_bvh_count(self.h))
+
+    def stat(self) -> dict:
+        L = nat.load()
+        d, up, s = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
+        nat.check(L.hry_bvh_stat(self.h, C.byref(d), C.byref(up)))
+        nat.check(L.hry_bvh_summary(self.h, s))
+        return {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(s[i]) for i, k in enumerate(self.SUMMARY)}}
+
+    def _buffers(self, make, dst_is_device: int) -> dict:
+        L = nat.load()
+        out = {}
+        for name in self.BUFFERS:
+            rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+            nat.check(L.hry_bvh_get(self.h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+            a, ptr = make((rows.value, width.value) if width.value > 1 else (rows.value,), typ.value)
+            if rows.value:
+                nat.check(L.hry_bvh_copy(self.codec.h, self.h, name.encode(), ptr(a), dst_is_device))
+            out[name] = a
+        return out
+
+    def buffers_numpy(self) -> dict:
+        """the seven buffers as host arrays: leaf_tri, leaf_code u32 [L], leaf_box f32 [L, 6], leaf_positions f32 [L, 9],
+        node_children u32 [L - 1, 2] (nat.BVH_LEAF set: a leaf), node_box f32 [L - 1, 6], scene_box f32 [1, 6]"""
+        return self._buffers(lambda shape, typ: (np.empty(shape, Codec._RENDER_NP[typ]), lambda a: a.ctypes.data), 0)
+
+    def buffers(self) -> dict:
+        """the same as torch tensors on the codec's device, copied device to device: float32 and int32 (a leaf's child word reads
+        negative)"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
+        return self._buffers(lambda shape, typ: (torch.empty(shape, dtype={0: torch.float32, 4: torch.int32}[typ], device=dev), lambda t: t.data_ptr()), 1)
+
+    def _cast(self, n, o_ptr, o_stride, d_ptr, d_stride, tmin, tmax, flags, tri_ptr, t_ptr, uv_ptr):
+        stat, ms = (C.c_uint64 * 2)(), C.c_double()
+        nat.check(nat.load().hry_bvh_cast(self.codec.h, self.h, n, o_ptr, o_stride, d_ptr, d_stride, float(tmin), float(tmax), flags, tri_ptr, t_ptr, uv_ptr,
+                                          stat, C.byref(ms)))
+        self.hits, self.box_tests, self.device_ms = int(stat[0]), int(stat[1]), ms.value
+
+    @staticmethod
+    def _rays(origins, dirs, rows_of):
+        """(n, origin stride, direction stride) in bytes for [n, 3] or [3] arrays whose xyz lie together; one origin or direction for
+        all rays has the stride 0"""
+        (no, so), (nd, sd) = rows_of(origins), rows_of(dirs)
+        counts = {c for c in (no, nd) if c not in (None, 1)}
+        if len(counts) > 1:
+            raise ValueError("origins and dirs: [n, 3] each, or [3] / [1, 3] for one value for all rays")
+        return (counts.pop() if counts else 1), (0 if no in (None, 1) else so), (0 if nd in (None, 1) else sd)
+
+    def cast(self, origins, dirs, tmin: float = 0.0, tmax: float = float("inf")) -> dict:
+        """the first triangle every ray meets within [tmin, tmax] (hry_bvh_cast).  origins, dirs: float32 torch tensors [n, 3] on the
+        codec's device, of any row stride (a view into a wider buffer, an expanded [1, 3]); [3]: one for all rays.  Returns tensors
+        there: "tri" int32 [n] (-1: the ray meets nothing), "t" float32 [n] (+inf), "uv" float32 [n, 2] (the barycentric
+        coordinates of the second and third corner)"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+
+        def prepared(t):
+            if t.dtype != torch.float32 or t.device != dev or t.dim() not in (1, 2) or t.shape[-1] != 3:
+                raise ValueError("rays: float32 tensors [n, 3] or [3] on the codec's device")
+            return t if t.stride(-1) == 1 and (t.dim() == 1 or t.stride(0) >= 0) else t.contiguous()
+
+        origins, dirs = prepared(origins), prepared(dirs)
+        n, so, sd = self._rays(origins, dirs, lambda t: (None, 0) if t.dim() == 1 else (t.shape[0], t.stride(0) * 4))
+        torch.cuda.current_stream(dev).synchronize()   # (the rays may still be in the making on torch's stream)
+        tri, t, uv = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n, 2), dtype=torch.float32, device=dev)
+        self._cast(n, origins.data_ptr(), so, dirs.data_ptr(), sd, tmin, tmax, 0, tri.data_ptr(), t.data_ptr(), uv.data_ptr())
+        return {"tri": tri, "t": t, "uv": uv}
+
+    def cast_numpy(self, origins, dirs, tmin: float = 0.0, tmax: float = float("inf")) -> dict:
+        """the same from and to host arrays (HRY_CAST_HOST: the library stages them); "tri" is uint32 with NO_ELEMENT for no hit"""
+        def prepared(a):
+            a = np.asarray(a, np.float32)
+            if a.ndim not in (1, 2) or a.shape[-1] != 3:
+                raise ValueError("rays: float32 arrays [n, 3] or [3]")
+            return a if a.strides[-1] == 4 and (a.ndim == 1 or (a.strides[0] >= 0 and a.strides[0] % 4 == 0)) else np.ascontiguousarray(a)
+
+        origins, dirs = prepared(origins), prepared(dirs)
+        n, so, sd = self._rays(origins, dirs, lambda a: (None, 0) if a.ndim == 1 else (a.shape[0], a.strides[0]))
+        tri, t, uv = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty((n, 2), np.float32)
+        self._cast(n, origins.ctypes.data, so, dirs.ctypes.data, sd, tmin, tmax, nat.CAST_HOST, tri.ctypes.data, t.ctypes.data, uv.ctypes.data)
+        return {"tri": tri, "t": t, "uv": uv}
 
 
 class Distortion(_NamedBuffers):

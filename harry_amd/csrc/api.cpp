@@ -23,6 +23,7 @@ struct hry_orient { OrientResult o; };
 struct hry_tangents { TangentsResult t; };
 struct hry_creases { CreasesResult c; };
 struct hry_curvature { CurvatureResult c; };
+struct hry_bvh { BvhResult b; };
 struct hry_distortion { DistortionResult d; };
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
@@ -126,6 +127,7 @@ static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o :
 static const TopologyResult *result_of(const hry_tangents *t) { return t ? &t->t : nullptr; }
 static const TopologyResult *result_of(const hry_creases *c) { return c ? &c->c : nullptr; }
 static const TopologyResult *result_of(const hry_curvature *c) { return c ? &c->c : nullptr; }
+static const TopologyResult *result_of(const hry_bvh *b) { return b ? &b->b : nullptr; }
 static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
 static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
 
@@ -814,6 +816,24 @@ int hry_curvature_totals(const hry_curvature *c, double out[3])
 }
 int hry_curvature_stat(const hry_curvature *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
 void hry_curvature_free(hry_curvature *c) { delete c; }
+
+// ---- the hierarchy over the triangles of a render build and the cast over it (bvh.cpp)
+int hry_bvh_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_bvh **out)
+{
+	return handle_build(ctx, m && r, out, [&](hry_bvh &b) { bvh_build(ctx->cx, m->m, r->r, flags, b.b); });
+}
+uint64_t hry_bvh_count(const hry_bvh *b) { const NamedBuf *l = b ? b->b.find("leaf_tri") : nullptr; return l ? l->rows : 0; }
+int hry_bvh_get(const hry_bvh *b, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(b), name, dev, rows, width, type, false); }
+int hry_bvh_copy(hry_ctx *ctx, const hry_bvh *b, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(b), name, "bvh buffer", dst, dst_is_device, true); }
+int hry_bvh_summary(const hry_bvh *b, uint64_t out[6]) { return handle_summary(result_of(b), out, 6); }
+int hry_bvh_stat(const hry_bvh *b, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(b), device_ms, uploaded_bytes); }
+void hry_bvh_free(hry_bvh *b) { delete b; }
+int hry_bvh_cast(hry_ctx *ctx, const hry_bvh *b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride, double tmin,
+                 double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t stat[2], double *device_ms)
+{
+	if (!ctx || !b || (n_rays && (!origins || !dirs || !hit_tri))) return null_argument();
+	return guarded([&] { bvh_cast(ctx->cx, b->b, n_rays, origins, origin_stride, dirs, dir_stride, tmin, tmax, flags, hit_tri, hit_t, hit_uv, stat, device_ms); });
+}
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
 	if (out) *out = nullptr;

@@ -49,7 +49,10 @@
 // --curvature (with or without OUTPUT, after those lines: "Curvature: vertices D interior I boundary B irregular N isolated Z
 // degenerate G area A defect X turns K mean-integral M" -- hry_curvature_build over a render build of the mesh and its edges build,
 // hry_curvature_summary and hry_curvature_totals; turns = defect / (2 pi), on a closed manifold mesh its Euler characteristic; it
-// describes the mesh that is written, like --creases.  Nothing else about the output changes).
+// describes the mesh that is written, like --creases.  Nothing else about the output changes);
+// --bvh (with or without OUTPUT, after those lines: "Bvh: triangles T leaves L dead Z distinct-codes C depth D" -- hry_bvh_build over a
+// render build of the mesh, and hry_bvh_summary; it describes the mesh that is written, like --creases.  Nothing else about the
+// output changes).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -89,7 +92,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false, creases = false, curvature = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false, creases = false, curvature = false, bvh = false;
 	double crease_angle = 0.0;
 	std::string crease_text;   // DEG as it was given
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
@@ -111,7 +114,8 @@ const Opt kOpts[] = {
 	{ 0, "orient-outward", "... and closed patches so that they enclose a positive volume", false },
 	{ 0, "tangents", "Print how many vertices get a tangent frame from positions, uv and normals (OUTPUT may be left out)", false },
 	{ 0, "creases", "Print how many vertices and hard edges a crease angle of DEG degrees gives (OUTPUT may be left out)", true },
-	{ 0, "curvature", "Print the vertex classes, the surface area, the total angle defect and the integral of the mean curvature (OUTPUT may be left out)", false } };
+	{ 0, "curvature", "Print the vertex classes, the surface area, the total angle defect and the integral of the mean curvature (OUTPUT may be left out)", false },
+	{ 0, "bvh", "Print the leaves, dead triangles, distinct codes and depth of a bounding-volume hierarchy over the triangles (OUTPUT may be left out)", false } };
 
 void usage(const char *argv0)
 {
@@ -198,6 +202,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "orient-outward") a.orient = a.orient_outward = true;
 		else if (n == "tangents") a.tangents = true;
 		else if (n == "curvature") a.curvature = true;
+		else if (n == "bvh") a.bvh = true;
 		else if (n == "creases") {
 			a.crease_angle = to_double(argv[0], val);
 			if (std::isnan(a.crease_angle)) arg_error(argv[0], "Invalid angle");
@@ -244,7 +249,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature || a.bvh ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -327,6 +332,7 @@ struct Handles {   // released on every path
 	hry_tangents *tangents = nullptr;   // --tangents, over a render build of its own
 	hry_creases *creases = nullptr;   // --creases, over a render build and an edges build with geometry of its own
 	hry_curvature *curvature = nullptr;   // --curvature, over a render build and an edges build of its own
+	hry_bvh *bvh = nullptr;   // --bvh, over a render build of its own
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -339,6 +345,7 @@ struct Handles {   // released on every path
 	}
 	void drop_adjacency()
 	{
+		if (bvh) hry_bvh_free(bvh);
 		if (curvature) hry_curvature_free(curvature);
 		if (creases) hry_creases_free(creases);
 		if (tangents) hry_tangents_free(tangents);
@@ -346,7 +353,7 @@ struct Handles {   // released on every path
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
-		curvature = nullptr; creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
+		bvh = nullptr; curvature = nullptr; creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
 	}
 	~Handles()
 	{
@@ -670,7 +677,16 @@ int run(const Args &args)
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature) && args.out.empty()) {
+	if (args.bvh) {
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_bvh_build(h.cx[0], h.mesh, h.render, 0u, &h.bvh));
+		uint64_t s[6];
+		ok(hry_bvh_summary(h.bvh, s));
+		std::cout << "Bvh: triangles " << s[0] << " leaves " << s[1] << " dead " << s[2] << " distinct-codes " << s[3] << " depth " << s[4] << std::endl;
+		h.drop_adjacency();
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature || args.bvh) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

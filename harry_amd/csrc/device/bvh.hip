@@ -1,0 +1,358 @@
+// A linear bounding-volume hierarchy over the triangles of a render build and the closest-hit ray cast over it (driver: bvh.cpp;
+// contract: include/harry_amd.h, hry_bvh_build and hry_bvh_cast; DESIGN.md "Bvh").  Every floating-point operation is an
+// individually rounded IEEE double operation in the written order (the tree is built with -ffp-contract=off); the boxes are float
+// minima and maxima, which are exact in any order; there are no floating-point atomics.  The bits of every buffer depend on the
+// render build alone, those of a cast on the hierarchy and the rays alone.
+// The build, first stretch (grids sized by T; the number of leaves L is a device word until the stretch ends):
+//   k_bvh_init      the counters and the empty scene box
+//   k_bvh_live      a lane per triangle: live (nine finite floats) or dead; the scene box by a wavefront minimum / maximum of ordered
+//                   words and one integer atomic per wavefront and bound (minima commute: the order decides nothing)
+//   k_scan_*        exclusive scan of the live flags: a live triangle's rank in ascending t, and L (scan.hip: launch_excl_scan)
+//   k_bvh_codes     a lane per triangle: the 30-bit code of a live one and its number, at its rank
+//   k_radix_*       four stable 8-bit passes by code (radix_sort.hpp): ascending (code, t)
+//   k_bvh_tree      a lane per internal node (Karras 2012): its range by two doubling / binary searches over the common prefixes of
+//                   the keys code * 2^32 + i, its split by a third, its two children and their parents
+//   k_bvh_depth     a lane per leaf: the internal nodes above it (at most 62: every level consumes one of the key's 62 significant
+//                   bits), their maximum; and the distinct codes (a ballot per wavefront)
+// Second stretch (L, the depth and the distinct codes have come down; the buffers are allocated):
+//   k_bvh_emit      a lane per leaf: its triangle, code, three positions and box; a lane per node: its children; the scene box
+//   k_bvh_fit       one launch per level, `depth` of them: a node whose children were finished by EARLIER launches takes the minimum
+//                   / maximum of their boxes and notes its round.  Nothing is handed over inside a launch: a node that reads the
+//                   round its child is writing in the same launch sees HRY_NO_ELEMENT or this round, and waits either way; what
+//                   it reads of an earlier launch is visible because that launch has ended (DESIGN.md "Bvh" says why not the
+//                   one-launch form with arrival counters)
+// The cast:
+//   k_bvh_cast      a ray per lane, a stack walk nearer child first.  The stack has kCastStack = 64 entries and cannot overflow: a pop
+//                   pushes at most the two children of a node, so it holds at most one entry per level and one more, and depth <= 62.
+//                   It lies in LDS interleaved by lane (a runtime-indexed private array would go to scratch): 64 entries * (a node
+//                   and the float below its near bound) * 64 lanes = 32 KiB a workgroup of one wavefront
+#include <hip/hip_runtime.h>
+
+#include "dev_types.hpp"
+#include "face_normal.hpp"
+#include "kernels.hpp"
+#include "radix_sort.hpp"
+#include "wave.hpp"
+
+namespace hry {
+namespace dev {
+
+namespace {
+
+constexpr uint32_t kNone = 0xffffffffu, kLeafBit = 0x80000000u;
+constexpr uint32_t kBvhBlock = 256, kCastBlock = 64, kCastStack = 64;
+constexpr uint32_t kWordL = 0, kWordDistinct = 1, kWordDepth = 2, kWordBox = 4;
+
+// floats as words whose unsigned order is the floats' order, -0 below +0: a total order, so the least of a set is one value
+__device__ __forceinline__ uint32_t ordered(float f) { const uint32_t u = __float_as_uint(f); return u & 0x80000000u ? ~u : u | 0x80000000u; }
+__device__ __forceinline__ float unordered(uint32_t w) { return __uint_as_float(w & 0x80000000u ? w ^ 0x80000000u : ~w); }
+__device__ __forceinline__ float least(float a, float b) { return ordered(b) < ordered(a) ? b : a; }
+__device__ __forceinline__ float greatest(float a, float b) { return ordered(b) > ordered(a) ? b : a; }
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < __builtin_inff(); }   // (false for NaN)
+__device__ __forceinline__ bool finite_d(double x) { return fabs(x) < __builtin_inf(); }
+__device__ __forceinline__ double dot_d(const D3 &a, const D3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+// the nine floats of triangle t; false: an index no render build writes, or a float that is not finite
+__device__ __forceinline__ bool triangle_of(const BvhWork &w, uint32_t t, float (&p)[9])
+{
+	bool live = true;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const uint32_t u = w.indices[3 * (size_t)t + k];
+		if (u >= w.nout) { p[3 * k] = p[3 * k + 1] = p[3 * k + 2] = __builtin_nanf(""); live = false; continue; }
+		const float *q = w.pos + (size_t)u * w.pos_stride;
+#pragma unroll
+		for (int c = 0; c < 3; ++c) { p[3 * k + c] = q[c]; live = live && finite_f(q[c]); }
+	}
+	return live;
+}
+
+__global__ void k_bvh_init(uint32_t *words)
+{
+	if (threadIdx.x < 4) words[threadIdx.x] = 0;
+	if (threadIdx.x < 3) { words[kWordBox + threadIdx.x] = ordered(__builtin_inff()); words[kWordBox + 3 + threadIdx.x] = ordered(-__builtin_inff()); }
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_live(BvhWork w)
+{
+	const uint32_t t = blockIdx.x * kBvhBlock + threadIdx.x;
+	float p[9];
+	const bool live = t < w.T && triangle_of(w, t, p);
+	if (t < w.T) w.flag[t] = live ? 1u : 0u;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const uint32_t lo = wave_min(live ? ordered(least(least(p[c], p[3 + c]), p[6 + c])) : ordered(__builtin_inff()));
+		const uint32_t hi = wave_max(live ? ordered(greatest(greatest(p[c], p[3 + c]), p[6 + c])) : ordered(-__builtin_inff()));
+		if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(&w.words[kWordBox + c], lo); atomicMax(&w.words[kWordBox + 3 + c], hi); }
+	}
+}
+
+__device__ __forceinline__ uint32_t cell_of(double c, float lo, float hi)
+{
+	if (hi == lo) return 0;
+	const double x = ((c - (double)lo) / ((double)hi - (double)lo)) * 1024.0;
+	return x >= 1023.0 ? 1023u : x > 0.0 ? (uint32_t)x : 0u;   // truncated toward zero, clamped to 0 .. 1023
+}
+__device__ __forceinline__ uint32_t spread3(uint32_t x)   // bit j to bit 3 j
+{
+	x = (x | (x << 16)) & 0x030000ffu;
+	x = (x | (x << 8)) & 0x0300f00fu;
+	x = (x | (x << 4)) & 0x030c30c3u;
+	return (x | (x << 2)) & 0x09249249u;
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_codes(BvhWork w)
+{
+	const uint32_t t = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (t >= w.T || !w.flag[t]) return;
+	float p[9];
+	triangle_of(w, t, p);
+	uint32_t cell[3];
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const double mid = (((double)p[c] + (double)p[3 + c]) + (double)p[6 + c]) / 3.0;
+		cell[c] = cell_of(mid, unordered(w.words[kWordBox + c]), unordered(w.words[kWordBox + 3 + c]));
+	}
+	const uint32_t i = w.at[t];
+	if (i >= w.T) return;   // (a rank is below L <= T)
+	w.code_a[i] = (spread3(cell[0]) << 2) | (spread3(cell[1]) << 1) | spread3(cell[2]);
+	w.tri_a[i] = t;
+}
+
+// the leading bits that the keys of leaves i and j share; -1 where j is no leaf.  The keys are distinct: they end in the leaf's number
+__device__ __forceinline__ int common_prefix(const uint32_t *code, uint32_t L, int64_t i, int64_t j)
+{
+	if (j < 0 || j >= (int64_t)L) return -1;
+	const unsigned long long a = ((unsigned long long)code[i] << 32) | (unsigned long long)i, b = ((unsigned long long)code[j] << 32) | (unsigned long long)j;
+	return __clzll((long long)(a ^ b));
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_tree(BvhWork w)
+{
+	const uint32_t L = w.words[kWordL], node = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (L < 2 || node >= L - 1) return;
+	const uint32_t *code = w.code_a;
+	const int64_t i = node;
+	const int64_t d = common_prefix(code, L, i, i + 1) > common_prefix(code, L, i, i - 1) ? 1 : -1;
+	const int floor_ = common_prefix(code, L, i, i - d);
+	int64_t reach = 2;
+	while (common_prefix(code, L, i, i + reach * d) > floor_) reach *= 2;
+	int64_t len = 0;
+	for (int64_t step = reach / 2; step >= 1; step /= 2)
+		if (common_prefix(code, L, i, i + (len + step) * d) > floor_) len += step;
+	const int64_t j = i + len * d;
+	const int within = common_prefix(code, L, i, j);
+	int64_t s = 0, step = len;
+	do {
+		step = (step + 1) / 2;
+		if (common_prefix(code, L, i, i + (s + step) * d) > within) s += step;
+	} while (step > 1);
+	const int64_t gamma = i + s * d + (d < 0 ? -1 : 0), a = i < j ? i : j, b = i < j ? j : i;
+	const uint32_t left = (uint32_t)gamma, right = (uint32_t)gamma + 1;
+	if (a == gamma) { w.children[2 * (size_t)node] = left | kLeafBit; w.leaf_parent[left] = node; }
+	else { w.children[2 * (size_t)node] = left; w.node_parent[left] = node; }
+	if (b == gamma + 1) { w.children[2 * (size_t)node + 1] = right | kLeafBit; w.leaf_parent[right] = node; }
+	else { w.children[2 * (size_t)node + 1] = right; w.node_parent[right] = node; }
+	if (node == 0) w.node_parent[0] = kNone;
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_depth(BvhWork w)
+{
+	const uint32_t L = w.words[kWordL], i = blockIdx.x * kBvhBlock + threadIdx.x;
+	const bool have = i < L;
+	uint32_t above = 0;
+	if (have && L >= 2)
+		for (uint32_t n = w.leaf_parent[i]; n != kNone && above < 64; n = w.node_parent[n]) ++above;   // (at most 62 levels)
+	above = wave_max(above);
+	const uint32_t first = (uint32_t)__popcll(__ballot(have && (i == 0 || w.code_a[i] != w.code_a[i - 1])));
+	if ((threadIdx.x & 63) == 0) {
+		if (above) atomicMax(&w.words[kWordDepth], above);
+		if (first) atomicAdd(&w.words[kWordDistinct], first);
+	}
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_emit(BvhWork w, BvhView v, uint32_t *round)
+{
+	const uint32_t i = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (i < 6) v.scene_box[i] = unordered(w.words[kWordBox + i]);
+	if (i >= v.L) return;
+	const uint32_t t = w.tri_a[i];
+	float p[9];
+	if (t < w.T) triangle_of(w, t, p);
+	else for (int k = 0; k < 9; ++k) p[k] = 0.0f;   // (no sort leaves such a number)
+	v.leaf_tri[i] = t;
+	v.leaf_code[i] = w.code_a[i];
+#pragma unroll
+	for (int k = 0; k < 9; ++k) v.leaf_positions[9 * (size_t)i + k] = p[k];
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		v.leaf_box[6 * (size_t)i + c] = least(least(p[c], p[3 + c]), p[6 + c]);
+		v.leaf_box[6 * (size_t)i + 3 + c] = greatest(greatest(p[c], p[3 + c]), p[6 + c]);
+	}
+	if (i + 1 < v.L) {
+		v.node_children[2 * (size_t)i] = w.children[2 * (size_t)i];
+		v.node_children[2 * (size_t)i + 1] = w.children[2 * (size_t)i + 1];
+		round[i] = kNone;
+	}
+}
+
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_fit(BvhView v, uint32_t *round, uint32_t r)
+{
+	const uint32_t i = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (i + 1 >= v.L || round[i] != kNone) return;
+	const uint32_t c0 = v.node_children[2 * (size_t)i], c1 = v.node_children[2 * (size_t)i + 1];
+	const uint32_t n0 = c0 & ~kLeafBit, n1 = c1 & ~kLeafBit;
+	if (n0 >= v.L || n1 >= v.L) return;   // (no tree names such a child)
+	// finished by an earlier launch?  A round written in this launch reads kNone or r: not below r either way
+	if (!(c0 & kLeafBit) && !(round[n0] < r)) return;
+	if (!(c1 & kLeafBit) && !(round[n1] < r)) return;
+	const float *b0 = (c0 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n0, *b1 = (c1 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n1;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		v.node_box[6 * (size_t)i + c] = least(b0[c], b1[c]);
+		v.node_box[6 * (size_t)i + 3 + c] = greatest(b0[3 + c], b1[3 + c]);
+	}
+	round[i] = r;
+}
+
+// ---- the cast
+struct Ray { D3 o, d, inv; double tmin, tmax; };
+
+// one axis of it: a direction of +-0 bounds nothing and fails the box where the origin lies outside [lo, hi]; otherwise n and f take
+// the axis' nearer and farther crossing
+__device__ __forceinline__ bool slab(double lo, double hi, double o, double d, double inv, double &n, double &f)
+{
+	if (d == 0.0) return !(o < lo || o > hi);
+	const double a = (lo - o) * inv, c = (hi - o) * inv;
+	const double nk = a < c ? a : c, fk = a < c ? c : a;
+	n = nk > n ? nk : n;
+	f = fk < f ? fk : f;
+	return true;
+}
+// the interval of a box for a valid ray (the one rule, for leaf and node boxes alike); false: the box fails
+__device__ __forceinline__ bool interval(const float *box, const Ray &ray, double &near, double &far)
+{
+	double n = -__builtin_inf(), f = __builtin_inf();
+	if (!slab((double)box[0], (double)box[3], ray.o.x, ray.d.x, ray.inv.x, n, f) || !slab((double)box[1], (double)box[4], ray.o.y, ray.d.y, ray.inv.y, n, f) ||
+	    !slab((double)box[2], (double)box[5], ray.o.z, ray.d.z, ray.inv.z, n, f))
+		return false;
+	const double n1 = n - fabs(n) * 0x1p-30, f1 = f + fabs(f) * 0x1p-30;
+	near = ray.tmin > n1 ? ray.tmin : n1;
+	far = ray.tmax < f1 ? ray.tmax : f1;
+	return near <= far;
+}
+
+struct Best { double tt, u, v; uint32_t tri; };
+
+// leaf `leaf`, whose own box has passed with [near, far]
+__device__ __forceinline__ void hit_leaf(const BvhView &v, uint32_t leaf, const Ray &ray, double near, double far, Best &best)
+{
+	const float *p = v.leaf_positions + 9 * (size_t)leaf;
+	const D3 p0{ (double)p[0], (double)p[1], (double)p[2] }, p1{ (double)p[3], (double)p[4], (double)p[5] }, p2{ (double)p[6], (double)p[7], (double)p[8] };
+	const D3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), pv = cross3(ray.d, e2);
+	const double det = dot_d(e1, pv);
+	const D3 s = sub3(ray.o, p0), q = cross3(s, e1);
+	const double u = dot_d(s, pv) / det, w = dot_d(ray.d, q) / det, tt = dot_d(e2, q) / det;
+	if (!(finite_d(det) && det != 0.0 && u >= 0.0 && w >= 0.0 && u + w <= 1.0 && near <= tt && tt <= far)) return;
+	const uint32_t t = v.leaf_tri[leaf];
+	if (tt < best.tt || (tt == best.tt && t < best.tri)) best = Best{ tt, u, w, t };
+}
+
+__global__ __launch_bounds__(kCastBlock) void k_bvh_cast(BvhView v, BvhCast c)
+{
+	__shared__ uint32_t s_node[kCastStack * kCastBlock];
+	__shared__ float s_near[kCastStack * kCastBlock];
+	const uint32_t lane = threadIdx.x;
+	unsigned long long hits = 0, tests = 0;
+	for (uint64_t base = (uint64_t)blockIdx.x * kCastBlock; base < c.n; base += (uint64_t)gridDim.x * kCastBlock) {
+		const uint64_t i = base + lane;
+		const bool have = i < c.n;
+		Best best{ __builtin_inf(), 0.0, 0.0, kNone };
+		uint32_t made = 0;
+		if (have) {
+			const float *po = (const float*)(c.o + i * c.o_stride), *pd = (const float*)(c.d + i * c.d_stride);
+			Ray ray;
+			ray.o = D3{ (double)po[0], (double)po[1], (double)po[2] };
+			ray.d = D3{ (double)pd[0], (double)pd[1], (double)pd[2] };
+			ray.inv = D3{ 1.0 / ray.d.x, 1.0 / ray.d.y, 1.0 / ray.d.z };
+			ray.tmin = c.tmin; ray.tmax = c.tmax;
+			const bool valid = finite_d(ray.o.x) && finite_d(ray.o.y) && finite_d(ray.o.z) && finite_d(ray.d.x) && finite_d(ray.d.y) && finite_d(ray.d.z) &&
+			                   !(ray.d.x == 0.0 && ray.d.y == 0.0 && ray.d.z == 0.0);
+			double near, far;
+			if (valid && v.L == 1) {
+				++made;
+				if (interval(v.leaf_box, ray, near, far)) hit_leaf(v, 0, ray, near, far, best);
+			} else if (valid && v.L > 1) {
+				uint32_t sp = 1;
+				s_node[lane] = 0; s_near[lane] = -__builtin_inff();
+				while (sp) {
+					--sp;
+					const uint32_t node = s_node[sp * kCastBlock + lane];
+					if ((double)s_near[sp * kCastBlock + lane] > best.tt || node + 1 >= v.L) continue;   // strict: an equal bound may hold a lower number
+					const uint32_t c0 = v.node_children[2 * (size_t)node], c1 = v.node_children[2 * (size_t)node + 1];
+					const uint32_t n0 = c0 & ~kLeafBit, n1 = c1 & ~kLeafBit;
+					if (n0 >= v.L || n1 >= v.L) continue;   // (no tree names such a child)
+					double near0, far0, near1, far1;
+					bool go0 = interval((c0 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n0, ray, near0, far0);
+					bool go1 = interval((c1 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n1, ray, near1, far1);
+					made += 2;
+					if (go0 && (c0 & kLeafBit)) { if (!(near0 > best.tt)) hit_leaf(v, n0, ray, near0, far0, best); go0 = false; }
+					if (go1 && (c1 & kLeafBit)) { if (!(near1 > best.tt)) hit_leaf(v, n1, ray, near1, far1, best); go1 = false; }
+					go0 = go0 && !(near0 > best.tt);
+					go1 = go1 && !(near1 > best.tt);
+					const bool first1 = go0 && go1 && near1 < near0;   // the nearer child is popped first: pushed last
+					const uint32_t na = first1 ? n1 : n0, nb = first1 ? n0 : n1;
+					const double ra = first1 ? near1 : near0, rb = first1 ? near0 : near1;
+					const bool ga = first1 ? go1 : go0, gb = first1 ? go0 : go1;
+					if (gb && sp < kCastStack) { s_node[sp * kCastBlock + lane] = nb; s_near[sp * kCastBlock + lane] = __double2float_rd(rb); ++sp; }
+					if (ga && sp < kCastStack) { s_node[sp * kCastBlock + lane] = na; s_near[sp * kCastBlock + lane] = __double2float_rd(ra); ++sp; }
+				}
+			}
+			const bool hit = best.tri != kNone;
+			c.hit_tri[i] = best.tri;
+			if (c.hit_t) c.hit_t[i] = hit ? (float)best.tt : __builtin_inff();
+			if (c.hit_uv) { c.hit_uv[2 * i] = hit ? (float)best.u : 0.0f; c.hit_uv[2 * i + 1] = hit ? (float)best.v : 0.0f; }
+		}
+		hits += (unsigned long long)__popcll(__ballot(have && best.tri != kNone));
+		tests += wave_sum((unsigned long long)made);
+	}
+	if (lane == 0 && c.stat) {
+		if (hits) atomicAdd(&c.stat[0], hits);
+		if (tests) atomicAdd(&c.stat[1], tests);
+	}
+}
+
+}   // namespace
+
+// ---- launchers (kernels.hpp)
+size_t bvh_radix_words(uint32_t T) { return radix_scratch_words(T); }
+void launch_bvh_first(hipStream_t st, const BvhWork &w)
+{
+	hipLaunchKernelGGL(k_bvh_init, dim3(1), dim3(64), 0, st, w.words);
+	if (!w.T) return;
+	const dim3 grid(blocks_for(w.T, kBvhBlock)), block(kBvhBlock);
+	hipLaunchKernelGGL(k_bvh_live, grid, block, 0, st, w);
+	launch_excl_scan(st, w.flag, w.T, w.sums, w.at, w.words + kWordL);
+	hipLaunchKernelGGL(k_bvh_codes, grid, block, 0, st, w);
+	launch_radix_sort(st, w.code_a, w.tri_a, w.code_b, w.tri_b, w.words + kWordL, w.T, 4, w.radix);   // (four passes: back in code_a / tri_a)
+	hipLaunchKernelGGL(k_bvh_tree, grid, block, 0, st, w);
+	hipLaunchKernelGGL(k_bvh_depth, grid, block, 0, st, w);
+}
+
+void launch_bvh_second(hipStream_t st, const BvhWork &w, const BvhView &v, uint32_t depth)
+{
+	uint32_t *round = w.flag;   // (the flags have served)
+	hipLaunchKernelGGL(k_bvh_emit, dim3(blocks_for(v.L ? v.L : 1, kBvhBlock)), dim3(kBvhBlock), 0, st, w, v, round);
+	if (v.L < 2) return;
+	for (uint32_t r = 1; r <= depth; ++r) hipLaunchKernelGGL(k_bvh_fit, dim3(blocks_for(v.L - 1, kBvhBlock)), dim3(kBvhBlock), 0, st, v, round, r);
+}
+
+uint32_t bvh_cast_block() { return kCastBlock; }
+void launch_bvh_cast(hipStream_t st, const BvhView &v, const BvhCast &c)
+{
+	if (!c.n) return;
+	hipLaunchKernelGGL(k_bvh_cast, dim3(grid_for(c.n, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
+}
+
+}   // namespace dev
+}   // namespace hry

@@ -203,6 +203,35 @@ struct CurvWork {
 	double *terms, *fold_a, *fold_b;
 };
 
+// bvh.hip: what the hierarchy's build reads of a render build -- the indices of its T triangles and the float rows of the positions
+// (pos_stride floats per output vertex, nout of them) -- and its working arrays, laid out by bvh.cpp, T entries each unless said:
+// flag (1: live) and at [T + 1] (its exclusive scan: a live triangle's rank); code_a / tri_a / code_b / tri_b: the sort's two sides;
+// children [T, 2]; leaf_parent / node_parent; sums: scan_sums_words(T); radix: radix_scratch_words(T) (radix_sort.hpp); words: 16
+// words -- [0] L, [1] distinct codes, [2] depth, [4 .. 9] the scene box as ordered words (k_bvh_init sets them)
+struct BvhWork {
+	const uint32_t *indices;
+	const float *pos;
+	uint32_t T, nout, pos_stride;
+	uint32_t *flag, *at, *code_a, *tri_a, *code_b, *tri_b, *children, *leaf_parent, *node_parent, *sums, *radix, *words;
+};
+// ... and the finished hierarchy: what the second stretch writes and the cast reads (L leaves, L - 1 nodes).  round [L - 1]: the
+// round of the box fit that finished a node, HRY_NO_ELEMENT before (working memory, not a buffer of the handle)
+struct BvhView {
+	uint32_t L;
+	uint32_t *leaf_tri, *leaf_code, *node_children;
+	float *leaf_box, *leaf_positions, *node_box, *scene_box;
+};
+// one cast: n rays, origin / direction of ray i at byte i * stride of o / d (stride 0: one for all); dense outputs, t and uv may be
+// null; stat: two zeroed 64-bit counters (rays that hit, box tests)
+struct BvhCast {
+	uint64_t n, o_stride, d_stride;
+	const uint8_t *o, *d;
+	double tmin, tmax;
+	uint32_t *hit_tri;
+	float *hit_t, *hit_uv;
+	unsigned long long *stat;
+};
+
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh
 struct RunPlace {

@@ -1,4 +1,4 @@
-// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp, curvature.cpp): the
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp, curvature.cpp, bvh.cpp): the
 // plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
 // that one build is the build of another (result_build.cpp).
 #pragma once
@@ -64,6 +64,13 @@ struct CurvatureResult : TopologyResult {
 	double totals[3] = {};
 };
 void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, CurvatureResult &out);   // flags: none
+// bvh.cpp: the hierarchy over the triangles of a render build and the cast over it (include/harry_amd.h: hry_bvh_build,
+// hry_bvh_cast).  summary: T, L, T - L, distinct codes, depth, 0.  The result reads nothing of the render build afterwards
+typedef TopologyResult BvhResult;
+void bvh_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, BvhResult &out);   // flags: none
+dev::BvhView bvh_view_of(const BvhResult &b);   // its seven buffers, as the kernels take them
+void bvh_cast(Context &cx, const BvhResult &b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride, double tmin,
+              double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t *stat, double *device_ms);   // flags: HRY_CAST_*
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise

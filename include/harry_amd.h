@@ -20,6 +20,7 @@
  *   hry_tangents_build  (no counterpart: a tangent frame per output vertex of a render build, from its positions, uv and normals, as device buffers)
  *   hry_creases_build   (no counterpart: hard edges at a crease limit, vertices split along them and a normal per split vertex, as device buffers)
  *   hry_curvature_build (no counterpart: mixed Voronoi area, angle defect, Gaussian and mean curvature per vertex of a render build, as device buffers)
+ *   hry_bvh_build, hry_bvh_cast (no counterpart: a bounding-volume hierarchy over the triangles of a render build and closest-hit ray queries against it, on the device)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -636,6 +637,86 @@ int hry_curvature_summary(const hry_curvature *c, uint64_t out[6]);
 int hry_curvature_totals(const hry_curvature *c, double out[3]);
 int hry_curvature_stat(const hry_curvature *c, double *device_ms, uint64_t *uploaded_bytes);
 void hry_curvature_free(hry_curvature *c);
+
+/* ---- ray queries on a render build: a bounding-volume hierarchy and a closest-hit cast ----------------------------------------------
+ * hry_bvh_build builds, on ctx's device, a linear bounding-volume hierarchy over the triangles of r, a render build of m, and
+ * hry_bvh_cast answers where rays first meet them.  The build reads r's "indices" and the float rows of its position list where they
+ * lie in HBM: nothing is uploaded (uploaded_bytes is 0), the handle owns one allocation like the other results and keeps its own copy
+ * of the positions it needs, so r may be freed afterwards.  flags must be 0.  The contract defines the result, not the way to it:
+ * every bit of every buffer depends on r alone, every bit of a cast on the hierarchy and the rays alone, and a program that tests
+ * every triangle against every ray by the rules below gets the same bits.
+ * Let T be the triangles of r and I = indices; P[u] as in the edges' contract (the same position list, the same HRY_E_UNSUPPORTED
+ * refusals).  "Least" and "greatest" of floats are taken in the floats' order with -0 below +0 (a total order: the result is one of
+ * the values, whatever the order of the comparisons).
+ * Live triangles: t is live when all nine floats of P[I[t][0]], P[I[t][1]], P[I[t][2]] are finite.  A dead triangle is in no leaf
+ *   and is never hit.  L: the live triangles.
+ * Boxes: the leaf box of t is, per axis, the least and the greatest of its three floats -- exact, no padding.  The scene box lo, hi
+ *   is the least and the greatest over the live triangles' leaf boxes.
+ * Code: in double, c_k = ((P0_k + P1_k) + P2_k) / 3.0; cell_k = 0 where hi_k == lo_k, otherwise ((c_k - lo_k) / (hi_k - lo_k)) *
+ *   1024.0 truncated toward zero and clamped to 0 .. 1023.  The 30-bit code interleaves the cells: bit 3 j + 2 is x's bit j, bit
+ *   3 j + 1 y's, bit 3 j z's.
+ * Leaves: the live triangles in ascending (code, t).  Leaf i has the key code_i * 2^32 + i; the keys are distinct.
+ * Tree: the binary radix tree of the keys, L - 1 internal nodes in Karras's numbering.  The root is internal node 0 and covers the
+ *   leaves [0, L - 1].  A node that covers [a, b] splits behind gamma, the largest j in [a, b) whose key shares more leading bits with
+ *   key_a than key_a shares with key_b.  Its left child covers [a, gamma]: leaf gamma where a == gamma, otherwise internal node gamma;
+ *   its right child covers [gamma + 1, b]: leaf gamma + 1 where gamma + 1 == b, otherwise internal node gamma + 1.  A child word has
+ *   bit 31 set for a leaf.  L = 1: no internal node, the leaf is the tree.  L = 0: everything is empty.
+ *   Every level consumes at least one of a key's 62 significant bits, so no leaf has more than 62 internal nodes above it.
+ * Node boxes: per axis the least / greatest of the two children's boxes.
+ * Buffers by name:
+ *   "leaf_tri"        u32 [L]         the triangle of leaf i
+ *   "leaf_code"       u32 [L]         its code
+ *   "leaf_box"        f32 [L, 6]      min x y z, max x y z
+ *   "leaf_positions"  f32 [L, 9]      its three positions (the cast reads these, not r)
+ *   "node_children"   u32 [L - 1, 2]  left, right
+ *   "node_box"        f32 [L - 1, 6]
+ *   "scene_box"       f32 [1, 6]      (+inf x 3, -inf x 3) where L = 0
+ * Refusals: null arguments, any flag bit, an r that does not fit m (U / T / nf) or that lives on another device: HRY_E_ARG;
+ * 3 T > 2^31, or a position list the normals' rule refuses: HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable.
+ *   hry_bvh_count    L, the leaves
+ *   hry_bvh_get / _copy / _stat  as hry_curvature_get / _copy / _stat
+ *   hry_bvh_summary  out = { T, L, T - L, distinct codes, depth, 0 }; depth: the largest number of internal nodes between the root
+ *                    and a leaf, both ends counted, 0 for L <= 1 and at most 62.  Device reductions during the build
+ *
+ * hry_bvh_cast: ray i reads three floats at origins + i * origin_stride bytes and three at dirs + i * dir_stride bytes; the strides
+ * are multiples of 4, and a stride of 0 means one value for all rays.  The outputs are dense: hit_tri [n_rays], hit_t [n_rays],
+ * hit_uv [n_rays, 2]; hit_t, hit_uv, stat and device_ms may be NULL.  Without flags the five pointers are memory of ctx's device,
+ * checked as hry_mesh_from_device checks its columns, read and written on hry_ctx_stream, and the call returns when the results are
+ * written; with HRY_CAST_HOST all five are host memory, staged by the library.
+ * All arithmetic is in double on the widened floats, every operation individually rounded in the written order; a . b =
+ * (a.x b.x + a.y b.y) + a.z b.z, a x b as in the normals' contract.  O, D: the ray's origin and direction.
+ * Valid ray: O and D finite and D != (0, 0, 0).  Any other ray misses.
+ * Interval of a box [lo, hi] for a valid ray -- the one rule, for leaf and node boxes alike.  An axis with D_k == 0 (-0 included):
+ *   the box fails where O_k < lo_k or O_k > hi_k, otherwise the axis sets no bound.  Another axis: inv = 1.0 / D_k, a = (lo_k - O_k) *
+ *   inv, c = (hi_k - O_k) * inv, n_k = min(a, c), f_k = max(a, c).  n is the largest n_k, f the least f_k; n' = n - |n| * 2^-30,
+ *   f' = f + |f| * 2^-30; near = max(tmin, n'), far = min(tmax, f').  The box passes when near <= far.  Everything here is finite
+ *   but tmin and tmax: no NaN arises.  Every step is monotone in lo downwards and in hi upwards, rounding included, so a box that
+ *   contains another has a near no greater and a far no smaller than the inner box's, exactly: a subtree whose box fails holds no
+ *   leaf whose box passes (DESIGN.md "Bvh").
+ * Hit of leaf triangle t: its own leaf box must pass, with the interval [near_t, far_t].  Then e1 = P1 - P0, e2 = P2 - P0, p = D x e2,
+ *   det = e1 . p, s = O - P0, q = s x e1, u = (s . p) / det, v = (D . q) / det, tt = (e2 . q) / det; t is accepted when det is finite
+ *   and not 0 (both facings count), u >= 0, v >= 0, u + v <= 1 and near_t <= tt <= far_t.  A NaN fails every comparison.
+ * Answer: the accepted triangle with the least tt, ties to the least triangle number: hit_tri = t, hit_t = (float)tt, hit_uv =
+ *   ((float)u, (float)v).  A miss gives HRY_NO_ELEMENT, +inf, (0, 0).
+ * Not promised: watertightness.  A ray through a shared edge or vertex may miss both triangles: u, v and u + v are rounded per
+ *   triangle.  (The widened boxes only keep the box clause from deciding such a ray; they do not close the gap.)
+ * stat = { rays that hit, box intervals evaluated }; the second depends on the walk (it is what a hierarchy saves over L tests a
+ *   ray) and is no part of the bit contract.  device_ms: the kernel.
+ * tmin > tmax is no error: every ray misses.  n_rays = 0 succeeds and touches nothing.
+ * Refusals (HRY_E_ARG): a null ctx or b; null hit_tri, origins or dirs with n_rays > 0; unknown flags; a stride that is not a
+ * multiple of 4; NaN tmin or tmax; a pointer that is not what the flags say, is misaligned, or whose rows extend past its allocation;
+ * a b on another device than ctx's. */
+typedef struct hry_bvh hry_bvh;
+#define HRY_CAST_HOST 1u   /* origins, dirs, hit_tri, hit_t and hit_uv are host memory */
+int hry_bvh_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_bvh **out);
+uint64_t hry_bvh_count(const hry_bvh *b);             /* L: the leaves, live triangles of r */
+int hry_bvh_get(const hry_bvh *b, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_bvh_copy(hry_ctx *ctx, const hry_bvh *b, const char *name, void *dst, int dst_is_device);
+int hry_bvh_summary(const hry_bvh *b, uint64_t out[6]);
+int hry_bvh_stat(const hry_bvh *b, double *device_ms, uint64_t *uploaded_bytes);
+void hry_bvh_free(hry_bvh *b);
+int hry_bvh_cast(hry_ctx *ctx, const hry_bvh *b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride,
+                 double tmin, double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t stat[2], double *device_ms);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
