@@ -354,6 +354,67 @@ def read_stream_host(data: bytes):
         L.hry_walk_free(w)
 
 
+class _Chain:
+    """The builds that lie behind one another on one codec and mesh (render, edges, ... : hry_<family>_build / _free).  build() keeps
+    the handle it returns, so a later step names the earlier ones; leaving the `with` block frees what is still held, the last
+    built first, each handle once, whatever happened.  lib: the native library, or anything with the same entry points"""
+
+    def __init__(self, codec, mesh, lib=None):
+        self.lib, self.codec, self.mesh = lib or nat.load(), codec, mesh
+        self.held = []   # (family, handle) in the order of the builds
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def build(self, family: str, *args, entry: str = ""):
+        """hry_<family>_build (or `entry`) of the codec and the mesh with `args` between them and the new handle"""
+        h = C.c_void_p()
+        nat.check(getattr(self.lib, entry or f"hry_{family}_build")(self.codec.h, self.mesh.h, *args, C.byref(h)))
+        self.held.append((family, h))
+        return h
+
+    def free(self, keep_last: bool = False):
+        """free every handle held in reverse order; keep_last: but the one built last -- the inputs of it go, it stays"""
+        last = self.held.pop() if keep_last else None
+        while self.held:
+            family, h = self.held.pop()   # (no longer held whatever the free does)
+            getattr(self.lib, f"hry_{family}_free")(h)
+        if last:
+            self.held.append(last)
+
+    def take(self):
+        """the handle built last, no longer the chain's to free"""
+        return self.held.pop()[1]
+
+
+def _read_buffers(lib, family: str, h, names, fill, skip_empty: bool = False) -> dict:
+    """{name: fill(family, name, rows, width, type, h)} of the named buffers of a handle (hry_<family>_get), in the order of `names`,
+    without those the handle does not have (width 0) and, with skip_empty, those without rows"""
+    out = {}
+    for name in names:
+        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
+        nat.check(getattr(lib, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
+        if width.value and (rows.value or not skip_empty):
+            out[name] = fill(family, name, rows.value, width.value, typ.value, h)
+    return out
+
+
+def _read_stat(lib, family: str, h, keys=None, extras=None) -> dict:
+    """device_ms and uploaded_bytes of a handle (hry_<family>_stat), then `extras`, then the words of its summary under `keys`
+    (hry_<family>_summary: 4 words for edges, 6 for the others; keys None: the family has none)"""
+    d, up = C.c_double(), C.c_uint64()
+    nat.check(getattr(lib, f"hry_{family}_stat")(h, C.byref(d), C.byref(up)))
+    out = {"device_ms": d.value, "uploaded_bytes": up.value, **(extras or {})}
+    if keys is not None:
+        s = (C.c_uint64 * (4 if family == "edges" else 6))()
+        nat.check(getattr(lib, f"hry_{family}_summary")(h, s))
+        out.update((k, int(s[i])) for i, k in enumerate(keys))
+    return out
+
+
 class Codec:
     """Device context (one HIP device, one stream).  Raises HryError(E_NODEVICE) without a GPU: no CPU fallback."""
 
@@ -431,109 +492,70 @@ class Codec:
         return flags | (cls.RENDER_FACE_NORMALS if face_normals else 0)
 
     def _render(self, mesh: Mesh, fill, flags: int = 0) -> dict:
-        """build, hand every buffer to fill(name, rows, width, type, handle), free the handle"""
-        L = nat.load()
-        r = C.c_void_p()
-        nat.check(L.hry_render_build_ex(self.h, mesh.h, flags, C.byref(r)) if flags else L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            out = {}
-            for name in self.RENDER_FIXED + tuple(f"list{l}" for l in range(mesh.nlists)) + (self.RENDER_NORMALS if flags else ()):
-                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                nat.check(L.hry_render_get(r, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                if rows.value:
-                    out[name] = fill(name, rows.value, width.value, typ.value, r)
-            d, up = C.c_double(), C.c_uint64()
-            nat.check(L.hry_render_stat(r, C.byref(d), C.byref(up)))
-            self._render_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "nverts": L.hry_render_nverts(r), "ntris": L.hry_render_ntris(r)}
+        """build, hand every buffer with rows to fill(family, name, rows, width, type, handle), free the handle"""
+        with _Chain(self, mesh) as chain:
+            r = chain.build("render", flags, entry="hry_render_build_ex") if flags else chain.build("render")
+            L = chain.lib
+            names = self.RENDER_FIXED + tuple(f"list{l}" for l in range(mesh.nlists)) + (self.RENDER_NORMALS if flags else ())
+            out = _read_buffers(L, "render", r, names, fill, skip_empty=True)
+            self._render_stat = _read_stat(L, "render", r, extras={"nverts": L.hry_render_nverts(r), "ntris": L.hry_render_ntris(r)})
             return out
-        finally:
-            L.hry_render_free(r)
 
     def render_numpy(self, mesh: Mesh, normals=None, face_normals: bool = False) -> dict:
         """the mesh as render-ready buffers (hry_render_build), copied to host arrays: indices u32 [T, 3], tri_face u32 [T],
         vertex_source u32 [U], corner_source u32 [U] (unwelded meshes), face_region u16 [nf] (general bindings), list<l> f32 [rows, ncomp].
         normals "area" / "angle": also normals f32 [U, 3], computed on the device from the positions (hry_render_build_ex), weighted
         by face area / corner angle; face_normals: also face_normals f32 [nf, 3]"""
-        def fill(name, rows, width, typ, r):
-            a = np.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), self._RENDER_NP[typ])
-            nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), a.ctypes.data, 0))
-            return a
-        return self._render(mesh, fill, self._render_flags(normals, face_normals))
+        return self._render(mesh, self._fill_numpy, self._render_flags(normals, face_normals))
 
     def render(self, mesh: Mesh, normals=None, face_normals: bool = False) -> dict:
         """the same buffers as torch tensors on this codec's device, copied device to device: indices / tri_face / vertex_source /
         corner_source int32, face_region int16, list<l> / normals / face_normals float32.  They stay valid after close()."""
-        import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.device)
-        dtypes = {0: torch.float32, 4: torch.int32, 6: torch.int16}
         if max(mesh.nv, mesh.ne, mesh.ntri) >= 2 ** 31:   # (every u32 value is below one of them: U <= max(nv, ne))
             raise HryError(nat.E_ARG, "vertex, corner or triangle numbers of this mesh do not fit int32 tensors")
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-
-        def fill(name, rows, width, typ, r):
-            t = torch.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), dtype=dtypes[typ], device=dev)
-            nat.check(nat.load().hry_render_copy(self.h, r, name.encode(), t.data_ptr(), 1))
-            return t
-        return self._render(mesh, fill, self._render_flags(normals, face_normals))
+        return self._render(mesh, self._torch_fill(), self._render_flags(normals, face_normals))
 
     # ---- the builds behind a render build: edges, shells, orient (include/harry_amd.h: hry_edges_build, hry_shells_build, hry_orient_build)
     def _topology(self, mesh: Mesh, family: str, flags: int, names, summary, fill) -> dict:
-        """the chain of builds that ends in `family` -- render, edges, then shells or orient from both -- freeing every input handle in
-        reverse order whatever happens; then every named buffer of the last handle that exists goes to fill(family, name, rows, width,
-        type, handle), its stat and summary (keys: `summary`) into self._<family>_stat, and the last handle is freed"""
-        L = nat.load()
-        held = []   # (family, handle) of the chain so far
-
-        def build(fam, *args):
-            h = C.c_void_p()
-            nat.check(getattr(L, f"hry_{fam}_build")(self.h, mesh.h, *args, C.byref(h)))
-            held.append((fam, h))
-            return h
-        try:
-            r = build("render")
-            e = build("edges", r, flags if family == "edges" else 0)
-            if family != "edges":
-                build(family, r, e, flags)
-            h = held.pop()[1]
-        finally:
-            for fam, x in reversed(held):
-                getattr(L, f"hry_{fam}_free")(x)
-        try:
-            out = {}
-            for name in names:
-                rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                if width.value:
-                    out[name] = fill(family, name, rows.value, width.value, typ.value, h)
-            d, up, t = C.c_double(), C.c_uint64(), (C.c_uint64 * len(summary))()
-            nat.check(getattr(L, f"hry_{family}_stat")(h, C.byref(d), C.byref(up)))
-            nat.check(getattr(L, f"hry_{family}_summary")(h, t))
-            setattr(self, f"_{family}_stat", {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(t[i]) for i, k in enumerate(summary)}})
+        """the chain of builds that ends in `family` -- render, edges, then shells or orient from both --; its inputs are freed, then
+        every named buffer the last handle has goes to fill(family, name, rows, width, type, handle) and its stat and summary (keys:
+        `summary`) into self._<family>_stat"""
+        with _Chain(self, mesh) as chain:
+            r = chain.build("render")
+            e = chain.build("edges", r, flags if family == "edges" else 0)
+            h = e if family == "edges" else chain.build(family, r, e, flags)
+            chain.free(keep_last=True)
+            out = _read_buffers(chain.lib, family, h, names, fill)
+            setattr(self, f"_{family}_stat", _read_stat(chain.lib, family, h, summary))
             return out
-        finally:
-            getattr(L, f"hry_{family}_free")(h)
 
     def _fill_numpy(self, family, name, rows, width, typ, h):
-        a = np.empty((rows, width) if width > 1 else (rows,), self._RENDER_NP[typ])
+        """the fill that copies into a host array: a row per row, [rows] where a row is one value (a render build's list<l>: [rows, 1])"""
+        a = np.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), self._RENDER_NP[typ])
         if rows:
             nat.check(getattr(nat.load(), f"hry_{family}_copy")(self.h, h, name.encode(), a.ctypes.data, 0))
         return a
 
-    def _fill_torch(self, mesh: Mesh):
-        """the fill that copies device to device into tensors on this codec's device: int32 (NO_ELEMENT reads -1) and float32"""
+    def _torch_fill(self):
+        """the fill that copies device to device into tensors on this codec's device, shaped as _fill_numpy's arrays: int32 (NO_ELEMENT
+        reads -1), int16 and float32"""
         import torch   # only here: the rest of the package does not need torch
         dev = torch.device("cuda", self.device)
-        dtypes = {0: torch.float32, 4: torch.int32}
-        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:   # (every u32 value but NO_ELEMENT is below one of them)
-            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
+        dtypes = {0: torch.float32, 4: torch.int32, 6: torch.int16}
         torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
 
         def fill(family, name, rows, width, typ, h):
-            t = torch.empty((rows, width) if width > 1 else (rows,), dtype=dtypes[typ], device=dev)
+            t = torch.empty((rows, width) if width > 1 or name.startswith("list") else (rows,), dtype=dtypes[typ], device=dev)
             if rows:
                 nat.check(getattr(nat.load(), f"hry_{family}_copy")(self.h, h, name.encode(), t.data_ptr(), 1))
             return t
         return fill
+
+    def _fill_torch(self, mesh: Mesh):
+        """_torch_fill for the builds behind a render build, whose buffers also number the triangles' sides"""
+        if max(mesh.nv, mesh.ne, 3 * mesh.ntri) >= 2 ** 31:   # (every u32 value but NO_ELEMENT is below one of them)
+            raise HryError(nat.E_ARG, "vertex, corner or side numbers of this mesh do not fit int32 tensors")
+        return self._torch_fill()
 
     # ---- edges and adjacency of a render build (include/harry_amd.h: hry_edges_build)
     EDGES_FIXED = ("edges", "tri_edges", "edge_offsets", "edge_sides", "tri_neighbours")
@@ -620,33 +642,22 @@ class Codec:
             raise ValueError('normals is one of "area", "angle", "stored"')
         if weights not in ("area", "angle"):
             raise ValueError('weights is one of "area", "angle"')
-        L = nat.load()
         stored = normals == "stored"
         flags = ((nat.TANGENTS_ANGLE_WEIGHTED if weights == "angle" else 0) | (nat.TANGENTS_STORED_NORMALS if stored else 0) |
                  (nat.TANGENTS_BITANGENTS if bitangents else 0))
-        r, t = C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build_ex(self.h, mesh.h, 0 if stored else self._render_flags(normals, False), C.byref(r)))
-        try:
-            nat.check(L.hry_tangents_build(self.h, mesh.h, r, flags, C.byref(t)))
-            try:
-                out = {}
-                for family, h, names in (("tangents", t, ("tangents", "bitangents")), ("render", r, ("indices", "vertex_source"))):
-                    for name in names:
-                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                        nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                        if width.value:
-                            out[name] = fill(family, name, rows.value, width.value, typ.value, h)
-                d, up, rd, rup, s = C.c_double(), C.c_uint64(), C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
-                nat.check(L.hry_tangents_stat(t, C.byref(d), C.byref(up)))
-                nat.check(L.hry_render_stat(r, C.byref(rd), C.byref(rup)))
-                nat.check(L.hry_tangents_summary(t, s))
-                self._tangents_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "render_device_ms": rd.value, "render_uploaded_bytes": rup.value,
-                                       **{k: int(s[i]) for i, k in enumerate(self.TANGENTS_SUMMARY)}}
-                return out
-            finally:
-                L.hry_tangents_free(t)
-        finally:
-            L.hry_render_free(r)
+        with _Chain(self, mesh) as chain:
+            r = chain.build("render", 0 if stored else self._render_flags(normals, False), entry="hry_render_build_ex")
+            t = chain.build("tangents", r, flags)
+            L = chain.lib
+            out = {**_read_buffers(L, "tangents", t, ("tangents", "bitangents"), fill), **_read_buffers(L, "render", r, ("indices", "vertex_source"), fill)}
+            self._tangents_stat = _read_stat(L, "tangents", t, self.TANGENTS_SUMMARY, self._render_times(L, r))
+            return out
+
+    @staticmethod
+    def _render_times(lib, r) -> dict:
+        """hry_render_stat of the render build another build lies behind, under that build's keys"""
+        s = _read_stat(lib, "render", r)
+        return {"render_device_ms": s["device_ms"], "render_uploaded_bytes": s["uploaded_bytes"]}
 
     def tangents_numpy(self, mesh: Mesh, normals: str = "area", weights: str = "area", bitangents: bool = False) -> dict:
         """a tangent frame per output vertex of the mesh's render build (hry_tangents_build), copied to host arrays: tangents f32 [U, 4]
@@ -677,37 +688,19 @@ class Codec:
         if weights not in ("area", "angle"):
             raise ValueError('weights is one of "area", "angle"')
         limit = float(math.cos(math.radians(angle)) if cos_limit is None else cos_limit)
-        L = nat.load()
-        r, e, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            nat.check(L.hry_edges_build(self.h, mesh.h, r, nat.EDGES_GEOMETRY, C.byref(e)))
-            try:
-                nat.check(L.hry_creases_build(self.h, mesh.h, r, e, limit, nat.CREASES_ANGLE_WEIGHTED if weights == "angle" else 0, C.byref(c)))
-                try:
-                    def buffer(family, h, name):
-                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                        nat.check(getattr(L, f"hry_{family}_get")(h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                        return fill(family, name, rows.value, width.value, typ.value, h)
-                    out = {name: buffer("creases", c, name) for name in self.CREASES_BUFFERS}
-                    # the position list as the library chooses it (render.cpp: position_list): list 1, or the one vertex list with positions
-                    pl = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and L.hry_list_interp_ncomp(mesh.h, l, 0) >= 3][0]
-                    out["positions"] = gather(buffer("render", r, f"list{pl}"), L.hry_list_interp_offset(mesh.h, pl, 0), out["render_vertex"])
-                    d, up, ed, rd, rup, s = C.c_double(), C.c_uint64(), C.c_double(), C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
-                    nat.check(L.hry_creases_stat(c, C.byref(d), C.byref(up)))
-                    nat.check(L.hry_edges_stat(e, C.byref(ed), None))
-                    nat.check(L.hry_render_stat(r, C.byref(rd), C.byref(rup)))
-                    nat.check(L.hry_creases_summary(c, s))
-                    self._creases_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges_device_ms": ed.value, "render_device_ms": rd.value,
-                                          "render_uploaded_bytes": rup.value, "cos_limit": limit,
-                                          **{k: int(s[i]) for i, k in enumerate(self.CREASES_SUMMARY)}}
-                    return out
-                finally:
-                    L.hry_creases_free(c)
-            finally:
-                L.hry_edges_free(e)
-        finally:
-            L.hry_render_free(r)
+        with _Chain(self, mesh) as chain:
+            r = chain.build("render")
+            e = chain.build("edges", r, nat.EDGES_GEOMETRY)
+            c = chain.build("creases", r, e, limit, nat.CREASES_ANGLE_WEIGHTED if weights == "angle" else 0)
+            L = chain.lib
+            out = _read_buffers(L, "creases", c, self.CREASES_BUFFERS, fill)
+            # the position list as the library chooses it (render.cpp: position_list): list 1, or the one vertex list with positions
+            pl = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and L.hry_list_interp_ncomp(mesh.h, l, 0) >= 3][0]
+            rows = _read_buffers(L, "render", r, (f"list{pl}",), fill)[f"list{pl}"]
+            out["positions"] = gather(rows, L.hry_list_interp_offset(mesh.h, pl, 0), out["render_vertex"])
+            extras = {"edges_device_ms": _read_stat(L, "edges", e)["device_ms"], **self._render_times(L, r), "cos_limit": limit}
+            self._creases_stat = _read_stat(L, "creases", c, self.CREASES_SUMMARY, extras)
+            return out
 
     def creases_numpy(self, mesh: Mesh, angle: float = 30.0, cos_limit=None, weights: str = "area") -> dict:
         """the mesh's render build with its vertices split along hard edges (hry_creases_build), copied to host arrays: indices u32
@@ -739,34 +732,17 @@ class Codec:
     def _curvature(self, mesh: Mesh, fill) -> dict:
         """the render build, its edges build, the curvature build behind both; the curvature's buffers go to fill(family, name, rows,
         width, type, handle); all three handles are freed whatever happens"""
-        L = nat.load()
-        r, e, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            nat.check(L.hry_edges_build(self.h, mesh.h, r, 0, C.byref(e)))
-            try:
-                nat.check(L.hry_curvature_build(self.h, mesh.h, r, e, 0, C.byref(c)))
-                try:
-                    out = {}
-                    for name in self.CURVATURE_BUFFERS:
-                        rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-                        nat.check(L.hry_curvature_get(c, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-                        out[name] = fill("curvature", name, rows.value, width.value, typ.value, c)
-                    d, up, ed, s, t = C.c_double(), C.c_uint64(), C.c_double(), (C.c_uint64 * 6)(), (C.c_double * 3)()
-                    nat.check(L.hry_curvature_stat(c, C.byref(d), C.byref(up)))
-                    nat.check(L.hry_edges_stat(e, C.byref(ed), None))
-                    nat.check(L.hry_curvature_summary(c, s))
-                    nat.check(L.hry_curvature_totals(c, t))
-                    self._curvature_stat = {"device_ms": d.value, "uploaded_bytes": up.value, "edges_device_ms": ed.value,
-                                            **{k: int(s[i]) for i, k in enumerate(self.CURVATURE_SUMMARY)},
-                                            **{k: float(t[i]) for i, k in enumerate(self.CURVATURE_TOTALS)}}
-                    return out
-                finally:
-                    L.hry_curvature_free(c)
-            finally:
-                L.hry_edges_free(e)
-        finally:
-            L.hry_render_free(r)
+        with _Chain(self, mesh) as chain:
+            r = chain.build("render")
+            e = chain.build("edges", r, 0)
+            c = chain.build("curvature", r, e, 0)
+            L = chain.lib
+            out = _read_buffers(L, "curvature", c, self.CURVATURE_BUFFERS, fill)
+            t = (C.c_double * 3)()
+            nat.check(L.hry_curvature_totals(c, t))
+            self._curvature_stat = {**_read_stat(L, "curvature", c, self.CURVATURE_SUMMARY, {"edges_device_ms": _read_stat(L, "edges", e)["device_ms"]}),
+                                    **{k: float(t[i]) for i, k in enumerate(self.CURVATURE_TOTALS)}}
+            return out
 
     def curvature_numpy(self, mesh: Mesh, principal: bool = False) -> dict:
         """the discrete curvatures of the mesh's render build (hry_curvature_build), copied to host arrays of U rows, row u the value of
@@ -805,13 +781,9 @@ class Codec:
     def bvh(self, mesh: Mesh) -> "Bvh":
         """a bounding-volume hierarchy over the triangles of the mesh's render build, built on the device (hry_bvh_build): an owning
         object like Order, valid whatever the codec does later, until close().  The render build is freed before this returns"""
-        L = nat.load()
-        r, b = C.c_void_p(), C.c_void_p()
-        nat.check(L.hry_render_build(self.h, mesh.h, C.byref(r)))
-        try:
-            nat.check(L.hry_bvh_build(self.h, mesh.h, r, 0, C.byref(b)))
-        finally:
-            L.hry_render_free(r)
+        with _Chain(self, mesh) as chain:
+            chain.build("bvh", chain.build("render"), 0)
+            b = chain.take()
         out = Bvh(self, b)
         self._bvh_stat = out.stat()
         return out
@@ -1068,9 +1040,10 @@ def _normal_record(e) -> dict:
 
 class _NamedBuffers:
     """A native handle whose buffers lie in HBM and are found by name (hry_<_PREFIX>_get / _copy / _free), rows of one
-    component of _NP / _TORCH each.  Order and Distortion say what each accessor gives for them"""
+    component of _NP / _TORCH each.  Order and Distortion say what each accessor gives for them.  _TYPED: the family's get also
+    gives a buffer's width and type, as those behind a render build do (Bvh, which reads its buffers with the Codec's fills)"""
 
-    _PREFIX, _NP, _TORCH = "", None, ""
+    _PREFIX, _NP, _TORCH, _TYPED = "", None, "", False
 
     def _fn(self, what: str):
         return getattr(nat.load(), f"hry_{self._PREFIX}_{what}")
@@ -1082,14 +1055,17 @@ class _NamedBuffers:
 
     __del__ = close
 
-    def rows(self, name: str) -> int:
+    def _get(self, name: str, dev=None) -> int:
         rows = C.c_uint64()
-        nat.check(self._fn("get")(self.h, name.encode(), None, C.byref(rows)))
+        nat.check(self._fn("get")(self.h, name.encode(), dev, C.byref(rows), *((None, None) if self._TYPED else ())))
         return rows.value
 
+    def rows(self, name: str) -> int:
+        return self._get(name)
+
     def data_ptr(self, name: str) -> int:
-        dev, rows = C.c_void_p(), C.c_uint64()
-        nat.check(self._fn("get")(self.h, name.encode(), C.byref(dev), C.byref(rows)))
+        dev = C.c_void_p()
+        self._get(name, C.byref(dev))
         return dev.value or 0
 
     def numpy(self, name: str) -> np.ndarray:
@@ -1173,7 +1149,7 @@ class Order(_NamedBuffers):
         return self._apply(t, kind, nat.ORDER_TO_SOURCE, out)
 
 
-class Bvh:
+class Bvh(_NamedBuffers):
     """A bounding-volume hierarchy over the triangles of a render build (include/harry_amd.h: hry_bvh_build) and the closest-hit
     ray cast over it (hry_bvh_cast).  The buffers lie in HBM; every bit of them depends on the render build alone, every bit of a
     cast on them and the rays alone.  After a cast: hits (rays that hit), box_tests (box intervals the walk evaluated) and device_ms
@@ -1181,54 +1157,37 @@ class Bvh:
 
     BUFFERS = ("leaf_tri", "leaf_code", "leaf_box", "leaf_positions", "node_children", "node_box", "scene_box")
     SUMMARY = ("triangles", "leaves", "dead", "distinct_codes", "depth")
+    _PREFIX, _TYPED = "bvh", True
 
     def __init__(self, codec: "Codec", handle):
         self.codec, self.h = codec, handle
         self.hits = self.box_tests = 0
         self.device_ms = 0.0
 
-    def close(self):
-        if getattr(self, "h", None):
-            nat.load().hry_bvh_free(self.h)
-            self.h = None
-
-    __del__ = close
-
     def count(self) -> int:
         """L: the leaves, the triangles with finite positions"""
         return int(nat.load().hry_bvh_count(self.h))
 
     def stat(self) -> dict:
-        L = nat.load()
-        d, up, s = C.c_double(), C.c_uint64(), (C.c_uint64 * 6)()
-        nat.check(L.hry_bvh_stat(self.h, C.byref(d), C.byref(up)))
-        nat.check(L.hry_bvh_summary(self.h, s))
-        return {"device_ms": d.value, "uploaded_bytes": up.value, **{k: int(s[i]) for i, k in enumerate(self.SUMMARY)}}
+        return _read_stat(nat.load(), "bvh", self.h, self.SUMMARY)
 
-    def _buffers(self, make, dst_is_device: int) -> dict:
-        L = nat.load()
-        out = {}
-        for name in self.BUFFERS:
-            rows, width, typ = C.c_uint64(), C.c_int(), C.c_int()
-            nat.check(L.hry_bvh_get(self.h, name.encode(), None, C.byref(rows), C.byref(width), C.byref(typ)))
-            a, ptr = make((rows.value, width.value) if width.value > 1 else (rows.value,), typ.value)
-            if rows.value:
-                nat.check(L.hry_bvh_copy(self.codec.h, self.h, name.encode(), ptr(a), dst_is_device))
-            out[name] = a
-        return out
+    def numpy(self, name: str) -> np.ndarray:
+        """one of the buffers as a host array, as buffers_numpy gives it"""
+        return _read_buffers(nat.load(), "bvh", self.h, (name,), self.codec._fill_numpy)[name]
+
+    def tensor(self, name: str):
+        """one of the buffers as a torch tensor on the codec's device, as buffers gives it"""
+        return _read_buffers(nat.load(), "bvh", self.h, (name,), self.codec._torch_fill())[name]
 
     def buffers_numpy(self) -> dict:
         """the seven buffers as host arrays: leaf_tri, leaf_code u32 [L], leaf_box f32 [L, 6], leaf_positions f32 [L, 9],
         node_children u32 [L - 1, 2] (nat.BVH_LEAF set: a leaf), node_box f32 [L - 1, 6], scene_box f32 [1, 6]"""
-        return self._buffers(lambda shape, typ: (np.empty(shape, Codec._RENDER_NP[typ]), lambda a: a.ctypes.data), 0)
+        return _read_buffers(nat.load(), "bvh", self.h, self.BUFFERS, self.codec._fill_numpy)
 
     def buffers(self) -> dict:
         """the same as torch tensors on the codec's device, copied device to device: float32 and int32 (a leaf's child word reads
         negative)"""
-        import torch   # only here: the rest of the package does not need torch
-        dev = torch.device("cuda", self.codec.device)
-        torch.cuda.current_stream(dev).synchronize()   # (memory torch hands out may still be in use by its own stream)
-        return self._buffers(lambda shape, typ: (torch.empty(shape, dtype={0: torch.float32, 4: torch.int32}[typ], device=dev), lambda t: t.data_ptr()), 1)
+        return _read_buffers(nat.load(), "bvh", self.h, self.BUFFERS, self.codec._torch_fill())
 
     def _cast(self, n, o_ptr, o_stride, d_ptr, d_stride, tmin, tmax, flags, tri_ptr, t_ptr, uv_ptr):
         stat, ms = (C.c_uint64 * 2)(), C.c_double()

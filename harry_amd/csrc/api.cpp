@@ -15,16 +15,18 @@ using namespace hry;
 struct hry_ctx { Context cx; explicit hry_ctx(int d) : cx(d) {} };
 struct hry_mesh { Mesh m; };
 struct hry_plan { ShardPlan p; };
-struct hry_render { RenderResult r; };
-struct hry_order { std::unique_ptr<OrderResult> o; };
-struct hry_edges { EdgesResult e; };
-struct hry_shells { ShellsResult s; };
-struct hry_orient { OrientResult o; };
-struct hry_tangents { TangentsResult t; };
-struct hry_creases { CreasesResult c; };
-struct hry_curvature { CurvatureResult c; };
-struct hry_bvh { BvhResult b; };
-struct hry_distortion { DistortionResult d; };
+// the handles of the results with named buffers: one template over the result type, the member is `r` in every family
+template <class R> struct ResultHandle { R r; };
+struct hry_render : ResultHandle<RenderResult> {};
+struct hry_edges : ResultHandle<EdgesResult> {};
+struct hry_shells : ResultHandle<ShellsResult> {};
+struct hry_orient : ResultHandle<OrientResult> {};
+struct hry_tangents : ResultHandle<TangentsResult> {};
+struct hry_creases : ResultHandle<CreasesResult> {};
+struct hry_curvature : ResultHandle<CurvatureResult> {};
+struct hry_bvh : ResultHandle<BvhResult> {};
+struct hry_distortion : ResultHandle<DistortionResult> {};
+struct hry_order : ResultHandle<std::unique_ptr<OrderResult>> {};   // (taken from the context whole: hry_order_take)
 struct hry_sweep { SweepResult s; };
 struct hry_rate_sweep { RateResult s; };
 struct hry_walk {
@@ -120,16 +122,9 @@ template <class H, class F> static int handle_build(hry_ctx *ctx, bool have_argu
 		*out = h.release();
 	});
 }
-static const RenderResult *result_of(const hry_render *r) { return r ? &r->r : nullptr; }
-static const TopologyResult *result_of(const hry_edges *e) { return e ? &e->e : nullptr; }
-static const TopologyResult *result_of(const hry_shells *s) { return s ? &s->s : nullptr; }
-static const TopologyResult *result_of(const hry_orient *o) { return o ? &o->o : nullptr; }
-static const TopologyResult *result_of(const hry_tangents *t) { return t ? &t->t : nullptr; }
-static const TopologyResult *result_of(const hry_creases *c) { return c ? &c->c : nullptr; }
-static const TopologyResult *result_of(const hry_curvature *c) { return c ? &c->c : nullptr; }
-static const TopologyResult *result_of(const hry_bvh *b) { return b ? &b->b : nullptr; }
-static const OrderResult *result_of(const hry_order *o) { return o ? o->o.get() : nullptr; }
-static const DistortionResult *result_of(const hry_distortion *d) { return d ? &d->d : nullptr; }
+template <class R> static const R *result_of(const ResultHandle<R> *h) { return h ? &h->r : nullptr; }
+static const OrderResult *result_of(const hry_order *o) { return o ? o->r.get() : nullptr; }
+static uint64_t rows_of(const DeviceResult *r, const char *name) { const NamedBuf *b = r ? r->find(name) : nullptr; return b ? b->rows : 0; }   // (0: no such buffer)
 
 extern "C" {
 
@@ -739,100 +734,76 @@ int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *d
 int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(r), device_ms, uploaded_bytes); }
 void hry_render_free(hry_render *r) { delete r; }
 
-// ---- unique edges and adjacency of a render build (edges.cpp)
+// ---- the seven families behind a render build.  Their get, copy, summary, stat and free are one line each: the family, what its
+// refusals call a buffer, the words of its summary.  What differs between them follows: build, count, and what only one has
+#define HRY_RESULT_FAMILY(fam, noun, nsummary) \
+	int hry_##fam##_get(const hry_##fam *h, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(h), name, dev, rows, width, type, false); } \
+	int hry_##fam##_copy(hry_ctx *ctx, const hry_##fam *h, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(h), name, noun, dst, dst_is_device, true); } \
+	int hry_##fam##_summary(const hry_##fam *h, uint64_t out[nsummary]) { return handle_summary(result_of(h), out, nsummary); } \
+	int hry_##fam##_stat(const hry_##fam *h, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(h), device_ms, uploaded_bytes); } \
+	void hry_##fam##_free(hry_##fam *h) { delete h; }
+HRY_RESULT_FAMILY(edges, "edge buffer", 4)
+HRY_RESULT_FAMILY(shells, "shell buffer", 6)
+HRY_RESULT_FAMILY(orient, "orientation buffer", 6)
+HRY_RESULT_FAMILY(tangents, "tangent buffer", 6)
+HRY_RESULT_FAMILY(creases, "crease buffer", 6)
+HRY_RESULT_FAMILY(curvature, "curvature buffer", 6)
+HRY_RESULT_FAMILY(bvh, "bvh buffer", 6)
+#undef HRY_RESULT_FAMILY
+
+// unique edges and adjacency of a render build (edges.cpp)
 int hry_edges_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_edges **out)
 {
-	return handle_build(ctx, m && r, out, [&](hry_edges &e) { edges_build(ctx->cx, m->m, r->r, flags, e.e); });
+	return handle_build(ctx, m && r, out, [&](hry_edges &h) { edges_build(ctx->cx, m->m, r->r, flags, h.r); });
 }
-uint64_t hry_edges_count(const hry_edges *e) { return e ? e->e.summary[0] : 0; }
-int hry_edges_get(const hry_edges *e, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(e), name, dev, rows, width, type, false); }
-int hry_edges_copy(hry_ctx *ctx, const hry_edges *e, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(e), name, "edge buffer", dst, dst_is_device, true); }
-int hry_edges_summary(const hry_edges *e, uint64_t out[4]) { return handle_summary(result_of(e), out, 4); }
-int hry_edges_stat(const hry_edges *e, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(e), device_ms, uploaded_bytes); }
-void hry_edges_free(hry_edges *e) { delete e; }
-
-// ---- shells of a render build behind its edges build (shells.cpp)
+uint64_t hry_edges_count(const hry_edges *e) { return e ? e->r.summary[0] : 0; }
+// shells of a render build behind its edges build (shells.cpp)
 int hry_shells_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_shells **out)
 {
-	return handle_build(ctx, m && r && e, out, [&](hry_shells &s) { shells_build(ctx->cx, m->m, r->r, e->e, flags, s.s); });
+	return handle_build(ctx, m && r && e, out, [&](hry_shells &h) { shells_build(ctx->cx, m->m, r->r, e->r, flags, h.r); });
 }
-uint64_t hry_shells_count(const hry_shells *s) { return s ? s->s.summary[0] : 0; }
-int hry_shells_get(const hry_shells *s, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(s), name, dev, rows, width, type, false); }
-int hry_shells_copy(hry_ctx *ctx, const hry_shells *s, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(s), name, "shell buffer", dst, dst_is_device, true); }
-int hry_shells_summary(const hry_shells *s, uint64_t out[6]) { return handle_summary(result_of(s), out, 6); }
-int hry_shells_stat(const hry_shells *s, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(s), device_ms, uploaded_bytes); }
-void hry_shells_free(hry_shells *s) { delete s; }
-
-// ---- a consistent winding per patch of a render build behind its edges build (orient.cpp)
+uint64_t hry_shells_count(const hry_shells *s) { return s ? s->r.summary[0] : 0; }
+// a consistent winding per patch of a render build behind its edges build (orient.cpp)
 int hry_orient_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_orient **out)
 {
-	return handle_build(ctx, m && r && e, out, [&](hry_orient &o) { orient_build(ctx->cx, m->m, r->r, e->e, flags, o.o); });
+	return handle_build(ctx, m && r && e, out, [&](hry_orient &h) { orient_build(ctx->cx, m->m, r->r, e->r, flags, h.r); });
 }
-uint64_t hry_orient_count(const hry_orient *o) { return o ? o->o.summary[0] : 0; }
-int hry_orient_get(const hry_orient *o, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(o), name, dev, rows, width, type, false); }
-int hry_orient_copy(hry_ctx *ctx, const hry_orient *o, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(o), name, "orientation buffer", dst, dst_is_device, true); }
-int hry_orient_summary(const hry_orient *o, uint64_t out[6]) { return handle_summary(result_of(o), out, 6); }
-int hry_orient_stat(const hry_orient *o, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(o), device_ms, uploaded_bytes); }
-void hry_orient_free(hry_orient *o) { delete o; }
-
-// ---- tangent frames of a render build (tangents.cpp)
+uint64_t hry_orient_count(const hry_orient *o) { return o ? o->r.summary[0] : 0; }
+// tangent frames of a render build (tangents.cpp)
 int hry_tangents_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_tangents **out)
 {
-	return handle_build(ctx, m && r, out, [&](hry_tangents &t) { tangents_build(ctx->cx, m->m, r->r, flags, t.t); });
+	return handle_build(ctx, m && r, out, [&](hry_tangents &h) { tangents_build(ctx->cx, m->m, r->r, flags, h.r); });
 }
-uint64_t hry_tangents_count(const hry_tangents *t) { return t ? t->t.summary[0] : 0; }
-int hry_tangents_get(const hry_tangents *t, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(t), name, dev, rows, width, type, false); }
-int hry_tangents_copy(hry_ctx *ctx, const hry_tangents *t, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(t), name, "tangent buffer", dst, dst_is_device, true); }
-int hry_tangents_summary(const hry_tangents *t, uint64_t out[6]) { return handle_summary(result_of(t), out, 6); }
-int hry_tangents_stat(const hry_tangents *t, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(t), device_ms, uploaded_bytes); }
-void hry_tangents_free(hry_tangents *t) { delete t; }
-
-// ---- hard edges and split normals of a render build (creases.cpp)
+uint64_t hry_tangents_count(const hry_tangents *t) { return t ? t->r.summary[0] : 0; }
+// hard edges and split normals of a render build (creases.cpp)
 int hry_creases_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, double cos_limit, uint32_t flags, hry_creases **out)
 {
-	return handle_build(ctx, m && r && e, out, [&](hry_creases &c) { creases_build(ctx->cx, m->m, r->r, e->e, cos_limit, flags, c.c); });
+	return handle_build(ctx, m && r && e, out, [&](hry_creases &h) { creases_build(ctx->cx, m->m, r->r, e->r, cos_limit, flags, h.r); });
 }
-uint64_t hry_creases_count(const hry_creases *c) { return c ? c->c.summary[0] : 0; }
-int hry_creases_get(const hry_creases *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(c), name, dev, rows, width, type, false); }
-int hry_creases_copy(hry_ctx *ctx, const hry_creases *c, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(c), name, "crease buffer", dst, dst_is_device, true); }
-int hry_creases_summary(const hry_creases *c, uint64_t out[6]) { return handle_summary(result_of(c), out, 6); }
-int hry_creases_stat(const hry_creases *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
-void hry_creases_free(hry_creases *c) { delete c; }
-
-// ---- vertex areas and curvatures of a render build (curvature.cpp)
+uint64_t hry_creases_count(const hry_creases *c) { return c ? c->r.summary[0] : 0; }
+// vertex areas and curvatures of a render build (curvature.cpp)
 int hry_curvature_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, const hry_edges *e, uint32_t flags, hry_curvature **out)
 {
-	return handle_build(ctx, m && r && e, out, [&](hry_curvature &c) { curvature_build(ctx->cx, m->m, r->r, e->e, flags, c.c); });
+	return handle_build(ctx, m && r && e, out, [&](hry_curvature &h) { curvature_build(ctx->cx, m->m, r->r, e->r, flags, h.r); });
 }
-uint64_t hry_curvature_count(const hry_curvature *c) { const NamedBuf *b = c ? c->c.find("vertex_class") : nullptr; return b ? b->rows : 0; }
-int hry_curvature_get(const hry_curvature *c, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(c), name, dev, rows, width, type, false); }
-int hry_curvature_copy(hry_ctx *ctx, const hry_curvature *c, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(c), name, "curvature buffer", dst, dst_is_device, true); }
-int hry_curvature_summary(const hry_curvature *c, uint64_t out[6]) { return handle_summary(result_of(c), out, 6); }
+uint64_t hry_curvature_count(const hry_curvature *c) { return rows_of(result_of(c), "vertex_class"); }
 int hry_curvature_totals(const hry_curvature *c, double out[3])
 {
 	if (!c || !out) return null_argument();
-	for (int i = 0; i < 3; ++i) out[i] = c->c.totals[i];
+	for (int i = 0; i < 3; ++i) out[i] = c->r.totals[i];
 	return HRY_OK;
 }
-int hry_curvature_stat(const hry_curvature *c, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(c), device_ms, uploaded_bytes); }
-void hry_curvature_free(hry_curvature *c) { delete c; }
-
-// ---- the hierarchy over the triangles of a render build and the cast over it (bvh.cpp)
+// the hierarchy over the triangles of a render build and the cast over it (bvh.cpp)
 int hry_bvh_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_bvh **out)
 {
-	return handle_build(ctx, m && r, out, [&](hry_bvh &b) { bvh_build(ctx->cx, m->m, r->r, flags, b.b); });
+	return handle_build(ctx, m && r, out, [&](hry_bvh &h) { bvh_build(ctx->cx, m->m, r->r, flags, h.r); });
 }
-uint64_t hry_bvh_count(const hry_bvh *b) { const NamedBuf *l = b ? b->b.find("leaf_tri") : nullptr; return l ? l->rows : 0; }
-int hry_bvh_get(const hry_bvh *b, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(b), name, dev, rows, width, type, false); }
-int hry_bvh_copy(hry_ctx *ctx, const hry_bvh *b, const char *name, void *dst, int dst_is_device) { return handle_copy(ctx, result_of(b), name, "bvh buffer", dst, dst_is_device, true); }
-int hry_bvh_summary(const hry_bvh *b, uint64_t out[6]) { return handle_summary(result_of(b), out, 6); }
-int hry_bvh_stat(const hry_bvh *b, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(b), device_ms, uploaded_bytes); }
-void hry_bvh_free(hry_bvh *b) { delete b; }
+uint64_t hry_bvh_count(const hry_bvh *b) { return rows_of(result_of(b), "leaf_tri"); }
 int hry_bvh_cast(hry_ctx *ctx, const hry_bvh *b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride, double tmin,
                  double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t stat[2], double *device_ms)
 {
 	if (!ctx || !b || (n_rays && (!origins || !dirs || !hit_tri))) return null_argument();
-	return guarded([&] { bvh_cast(ctx->cx, b->b, n_rays, origins, origin_stride, dirs, dir_stride, tmin, tmax, flags, hit_tri, hit_t, hit_uv, stat, device_ms); });
+	return guarded([&] { bvh_cast(ctx->cx, b->r, n_rays, origins, origin_stride, dirs, dir_stride, tmin, tmax, flags, hit_tri, hit_t, hit_uv, stat, device_ms); });
 }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
@@ -855,7 +826,7 @@ int hry_order_take(hry_ctx *ctx, const hry_mesh *m, hry_order **out)
 	}
 	return guarded([&] {
 		std::unique_ptr<hry_order> o(new hry_order());
-		o->o = std::move(ctx->cx.order);
+		o->r = std::move(ctx->cx.order);
 		ctx->cx.order_token = 0;
 		*out = o.release();
 	});
@@ -865,8 +836,8 @@ int hry_order_copy(hry_ctx *ctx, const hry_order *o, const char *name, void *dst
 int hry_order_apply(hry_ctx *ctx, const hry_order *o, const char *kind, int direction, const void *d_src, uint64_t src_stride, void *d_dst, uint64_t dst_stride,
                     uint64_t row_bytes, uint64_t dst_rows)
 {
-	if (!ctx || !o || !o->o || !kind || !d_src || !d_dst) { g_last_error = "null argument"; return HRY_E_ARG; }
-	return guarded([&] { order_apply(ctx->cx, *o->o, kind, direction, d_src, src_stride, d_dst, dst_stride, row_bytes, dst_rows); });
+	if (!ctx || !o || !o->r || !kind || !d_src || !d_dst) { g_last_error = "null argument"; return HRY_E_ARG; }
+	return guarded([&] { order_apply(ctx->cx, *o->r, kind, direction, d_src, src_stride, d_dst, dst_stride, row_bytes, dst_rows); });
 }
 void hry_order_free(hry_order *o) { delete o; }
 
@@ -874,28 +845,28 @@ void hry_order_free(hry_order *o) { delete o; }
 // alone: b stays what the context holds, for this build and for a render build after it
 int hry_distortion_build(hry_ctx *ctx, const hry_mesh *a, const hry_mesh *b, const hry_order *o, uint32_t flags, hry_distortion **out)
 {
-	return handle_build(ctx, a && b && !(o && !o->o), out, [&](hry_distortion &d) { distortion_build(ctx->cx, a->m, b->m, result_of(o), flags, d.d); });
+	return handle_build(ctx, a && b && !(o && !o->r), out, [&](hry_distortion &d) { distortion_build(ctx->cx, a->m, b->m, result_of(o), flags, d.r); });
 }
 int hry_distortion_component(const hry_distortion *d, int l, int c, hry_comp_error *out)
 {
 	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	if (l < 0 || (size_t)l >= d->d.comp.size() || d->d.comp[l].empty()) { g_last_error = "no such compared list"; return HRY_E_ARG; }
-	if (c < 0 || (size_t)c >= d->d.comp[l].size()) { g_last_error = "no such component"; return HRY_E_ARG; }
-	*out = d->d.comp[l][c];
+	if (l < 0 || (size_t)l >= d->r.comp.size() || d->r.comp[l].empty()) { g_last_error = "no such compared list"; return HRY_E_ARG; }
+	if (c < 0 || (size_t)c >= d->r.comp[l].size()) { g_last_error = "no such component"; return HRY_E_ARG; }
+	*out = d->r.comp[l][c];
 	return HRY_OK;
 }
 int hry_distortion_position(const hry_distortion *d, hry_pos_error *out)
 {
 	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	*out = d->d.pos;
+	*out = d->r.pos;
 	return HRY_OK;
 }
-int hry_distortion_position_component(const hry_distortion *d) { return d ? d->d.pos_comp : -1; }
+int hry_distortion_position_component(const hry_distortion *d) { return d ? d->r.pos_comp : -1; }
 int hry_distortion_normals(const hry_distortion *d, hry_normal_error *out)
 {
 	if (!d || !out) { g_last_error = "null argument"; return HRY_E_ARG; }
-	*out = d->d.nrm;
-	if (out->list < 0) g_last_error = d->d.nrm_why;
+	*out = d->r.nrm;
+	if (out->list < 0) g_last_error = d->r.nrm_why;
 	return HRY_OK;
 }
 int hry_distortion_get(const hry_distortion *d, const char *name, const void **dev, uint64_t *rows) { return handle_get(result_of(d), name, dev, rows, nullptr, nullptr, false); }

@@ -19,21 +19,17 @@ void bvh_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags
 	require_render_of(cx, m, r);
 	const uint32_t T = (uint32_t)m.ntri();
 	BvhWork w{};
-	w.indices = (const uint32_t*)r.find("indices")->p; w.T = T; w.nout = r.nverts;
+	w.indices = r.ptr<const uint32_t>("indices"); w.T = T; w.nout = r.nverts;
 	w.pos = render_positions(m, r, "bvh", w.pos_stride);
 	HIP_OK(hipSetDevice(cx.device));
 
 	// ---- the working buffer (BvhWork, dev_types.hpp)
 	Carve W;
-	const size_t w_flag = W.reserve((size_t)T * 4), w_at = W.reserve(((size_t)T + 1) * 4), w_code_a = W.reserve((size_t)T * 4), w_tri_a = W.reserve((size_t)T * 4);
-	const size_t w_code_b = W.reserve((size_t)T * 4), w_tri_b = W.reserve((size_t)T * 4), w_children = W.reserve((size_t)T * 8), w_lpar = W.reserve((size_t)T * 4);
-	const size_t w_npar = W.reserve((size_t)T * 4), w_sums = W.reserve(scan_sums_words(T) * 4), w_radix = W.reserve(bvh_radix_words(T) * 4), w_words = W.reserve(64);
+	W.take(w.flag, (size_t)T * 4); W.take(w.at, ((size_t)T + 1) * 4); W.take(w.code_a, (size_t)T * 4); W.take(w.tri_a, (size_t)T * 4);
+	W.take(w.code_b, (size_t)T * 4); W.take(w.tri_b, (size_t)T * 4); W.take(w.children, (size_t)T * 8); W.take(w.leaf_parent, (size_t)T * 4);
+	W.take(w.node_parent, (size_t)T * 4); W.take(w.sums, scan_sums_words(T) * 4); W.take(w.radix, bvh_radix_words(T) * 4); W.take(w.words, 64);
 	cx.d_bvh.ensure(W.total);
-	void *wb = cx.d_bvh.p;
-	w.flag = W.ptr<uint32_t>(wb, w_flag); w.at = W.ptr<uint32_t>(wb, w_at); w.code_a = W.ptr<uint32_t>(wb, w_code_a); w.tri_a = W.ptr<uint32_t>(wb, w_tri_a);
-	w.code_b = W.ptr<uint32_t>(wb, w_code_b); w.tri_b = W.ptr<uint32_t>(wb, w_tri_b); w.children = W.ptr<uint32_t>(wb, w_children);
-	w.leaf_parent = W.ptr<uint32_t>(wb, w_lpar); w.node_parent = W.ptr<uint32_t>(wb, w_npar); w.sums = W.ptr<uint32_t>(wb, w_sums);
-	w.radix = W.ptr<uint32_t>(wb, w_radix); w.words = W.ptr<uint32_t>(wb, w_words);
+	W.bind(cx.d_bvh.p);
 
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
@@ -72,10 +68,8 @@ void bvh_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags
 
 BvhView bvh_view_of(const BvhResult &b)
 {
-	auto words = [&](const char *name) { return (uint32_t*)b.find(name)->p; };
-	auto floats = [&](const char *name) { return (float*)b.find(name)->p; };
-	return BvhView{ (uint32_t)b.find("leaf_tri")->rows, words("leaf_tri"), words("leaf_code"), words("node_children"), floats("leaf_box"), floats("leaf_positions"),
-	                floats("node_box"), floats("scene_box") };
+	return BvhView{ (uint32_t)b.find("leaf_tri")->rows, b.ptr<uint32_t>("leaf_tri"), b.ptr<uint32_t>("leaf_code"), b.ptr<uint32_t>("node_children"), b.ptr<float>("leaf_box"),
+	                b.ptr<float>("leaf_positions"), b.ptr<float>("node_box"), b.ptr<float>("scene_box") };
 }
 
 namespace {
@@ -118,17 +112,18 @@ void bvh_cast(Context &cx, const BvhResult &b, uint64_t n, const float *origins,
 
 	// ---- the working buffer: the two counters; with HRY_CAST_HOST the staged rays and results behind them
 	Carve W;
-	const size_t w_stat = W.reserve(16), w_o = W.reserve(host ? o_bytes : 0), w_d = W.reserve(host ? d_bytes : 0), w_tri = W.reserve(host ? n * 4 : 0);
-	const size_t w_t = W.reserve(host && hit_t ? n * 4 : 0), w_uv = W.reserve(host && hit_uv ? n * 8 : 0);
-	cx.d_bvh.ensure(W.total);
-	void *wb = cx.d_bvh.p;
-	hipStream_t st = cx.stream;
 	BvhCast c{};
 	c.n = n; c.o_stride = origin_stride; c.d_stride = dir_stride; c.tmin = tmin; c.tmax = tmax;
-	c.stat = W.ptr<unsigned long long>(wb, w_stat);
+	uint8_t *s_o, *s_d;
+	uint32_t *s_tri;
+	float *s_t, *s_uv;
+	W.take(c.stat, 16); W.take(s_o, host ? o_bytes : 0); W.take(s_d, host ? d_bytes : 0); W.take(s_tri, host ? n * 4 : 0);
+	W.take(s_t, host && hit_t ? n * 4 : 0); W.take(s_uv, host && hit_uv ? n * 8 : 0);
+	cx.d_bvh.ensure(W.total);
+	W.bind(cx.d_bvh.p);
+	hipStream_t st = cx.stream;
 	if (host) {
-		c.o = W.ptr<uint8_t>(wb, w_o); c.d = W.ptr<uint8_t>(wb, w_d); c.hit_tri = W.ptr<uint32_t>(wb, w_tri);
-		c.hit_t = hit_t ? W.ptr<float>(wb, w_t) : nullptr; c.hit_uv = hit_uv ? W.ptr<float>(wb, w_uv) : nullptr;
+		c.o = s_o; c.d = s_d; c.hit_tri = s_tri; c.hit_t = hit_t ? s_t : nullptr; c.hit_uv = hit_uv ? s_uv : nullptr;
 		HIP_OK(hipMemcpyAsync((void*)c.o, origins, o_bytes, hipMemcpyHostToDevice, st));
 		HIP_OK(hipMemcpyAsync((void*)c.d, dirs, d_bytes, hipMemcpyHostToDevice, st));
 	} else {
@@ -138,8 +133,7 @@ void bvh_cast(Context &cx, const BvhResult &b, uint64_t n, const float *origins,
 	StretchTimer timer;
 	timer.mark(st);
 	launch_bvh_cast(st, bvh_view_of(b), c);
-	timer.mark(st);
-	timer.mark(st); timer.mark(st);   // (one stretch)
+	timer.mark(st);   // (one stretch)
 	unsigned long long counters[2] = {};
 	HIP_OK(hipMemcpyAsync(counters, c.stat, 16, hipMemcpyDeviceToHost, st));
 	if (host) {

@@ -34,6 +34,7 @@ struct DeviceResult {
 	DeviceBlock block;
 	std::vector<NamedBuf> bufs;
 	const NamedBuf *find(const std::string &name) const { for (const NamedBuf &b : bufs) if (b.name == name) return &b; return nullptr; }
+	template <typename T> T *ptr(const char *name) const { return (T*)find(name)->p; }   // of a buffer the result is known to have
 };
 // a named buffer of any of the three results to dst (device or host memory), on cx's stream, waited for (defined in render.cpp).
 // what: what the handle calls a buffer ("numbering map"), for the refusals.  same_device: refuse a result that lives on another

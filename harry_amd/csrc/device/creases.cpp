@@ -32,18 +32,15 @@ void creases_build(Context &cx, const Mesh &m, const RenderResult &r, const Edge
 	Carve W;
 	DedupPlan D;
 	D.reserve(W, n, false);   // (the ids are the output buffer indices)
-	const size_t w_par = W.reserve((size_t)n * 4), w_root = W.reserve((size_t)n * 4), w_flag = W.reserve((size_t)n * 4), w_num = W.reserve(((size_t)n + 1) * 4);
-	const size_t w_sums = W.reserve(scan_sums_words(n) * 4), w_eclass = W.reserve((size_t)ne * 4), w_first = W.reserve((size_t)n * 4), w_terms = W.reserve((size_t)T * 24);
-	const size_t w_start = W.reserve(((size_t)n + 1) * 4), w_gnormal = W.reserve((size_t)n * 12), w_vgroups = W.reserve((size_t)v.nv * 4);
-	const size_t w_hubs = W.reserve(((size_t)creases_hub_capacity(n) + 1) * 4), w_classes = W.reserve(16);
-	cx.d_creases.ensure(W.total);
-	void *wb = cx.d_creases.p;
-	D.bind(W, wb);
 	CreaseWork w{};
-	w.par = W.ptr<uint32_t>(wb, w_par); w.root = W.ptr<uint32_t>(wb, w_root); w.flag = W.ptr<uint32_t>(wb, w_flag); w.num = W.ptr<uint32_t>(wb, w_num);
-	w.sums = W.ptr<uint32_t>(wb, w_sums); w.eclass = W.ptr<uint32_t>(wb, w_eclass); w.first_slot = W.ptr<uint32_t>(wb, w_first); w.terms = W.ptr<double>(wb, w_terms);
-	w.count = w.flag; w.start = W.ptr<uint32_t>(wb, w_start); w.seg = w.par; w.gnormal = W.ptr<float>(wb, w_gnormal); w.vgroups = W.ptr<uint32_t>(wb, w_vgroups);
-	w.hubs = W.ptr<uint32_t>(wb, w_hubs); w.classes = W.ptr<uint32_t>(wb, w_classes);
+	W.take(w.par, (size_t)n * 4); W.take(w.root, (size_t)n * 4); W.take(w.flag, (size_t)n * 4); W.take(w.num, ((size_t)n + 1) * 4);
+	W.take(w.sums, scan_sums_words(n) * 4); W.take(w.eclass, (size_t)ne * 4); W.take(w.first_slot, (size_t)n * 4); W.take(w.terms, (size_t)T * 24);
+	W.take(w.start, ((size_t)n + 1) * 4); W.take(w.gnormal, (size_t)n * 12); W.take(w.vgroups, (size_t)v.nv * 4);
+	W.take(w.hubs, ((size_t)creases_hub_capacity(n) + 1) * 4); W.take(w.classes, 16);
+	cx.d_creases.ensure(W.total);
+	W.bind(cx.d_creases.p);
+	D.bind(W, cx.d_creases.p);
+	w.count = w.flag; w.seg = w.par;
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
 
@@ -75,9 +72,9 @@ void creases_build(Context &cx, const Mesh &m, const RenderResult &r, const Edge
 	plan.add("slot_group", T, 3, HRY_UINT);
 	plan.add("edge_class", ne, 1, HRY_UINT);
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+	auto dst = [&](const char *name) { return out.ptr<uint32_t>(name); };
 	v.edge_class = dst("edge_class"); v.slot_group = dst("slot_group"); v.render_vertex = dst("render_vertex"); v.vertex_source = dst("vertex_source");
-	v.normals = (float*)dst("normals"); v.ids = dst("indices"); v.ng = ng; v.nw = nw;
+	v.normals = out.ptr<float>("normals"); v.ids = dst("indices"); v.ng = ng; v.nw = nw;
 
 	if (ng) HIP_OK(hipMemsetAsync(w.count, 0, (size_t)ng * 4, st));
 	if (v.nv) HIP_OK(hipMemsetAsync(w.vgroups, 0, (size_t)v.nv * 4, st));

@@ -24,17 +24,13 @@ void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const Ed
 	// ---- the working buffer (CurvWork, dev_types.hpp)
 	Carve W;
 	const uint32_t fold1 = curvature_fold_rows(nv), fold2 = curvature_fold_rows(fold1);
-	const size_t w_terms = W.reserve((size_t)nv * 24), w_fold_a = W.reserve(((size_t)fold1 + 1) * 24), w_fold_b = W.reserve(((size_t)fold2 + 1) * 24);
-	const size_t w_ends = W.reserve((size_t)nv * 4), w_count = W.reserve((size_t)nv * 4), w_start = W.reserve(((size_t)nv + 1) * 4);
-	const size_t w_sums = W.reserve(scan_sums_words(nv) * 4), w_seg = W.reserve((size_t)n * 4), w_hubs = W.reserve(((size_t)curvature_hub_capacity(n) + 1) * 4);
-	const size_t w_cls = W.reserve((size_t)nv * 4), w_rows = W.reserve((size_t)nv * 28), w_classes = W.reserve(32);
-	cx.d_curvature.ensure(W.total);
-	void *wb = cx.d_curvature.p;
 	CurvWork w{};
-	w.terms = W.ptr<double>(wb, w_terms); w.fold_a = W.ptr<double>(wb, w_fold_a); w.fold_b = W.ptr<double>(wb, w_fold_b);
-	w.ends = W.ptr<uint32_t>(wb, w_ends); w.count = W.ptr<uint32_t>(wb, w_count); w.start = W.ptr<uint32_t>(wb, w_start); w.sums = W.ptr<uint32_t>(wb, w_sums);
-	w.seg = W.ptr<uint32_t>(wb, w_seg); w.hubs = W.ptr<uint32_t>(wb, w_hubs); w.cls = W.ptr<uint32_t>(wb, w_cls); w.rows = W.ptr<float>(wb, w_rows);
-	w.classes = W.ptr<uint32_t>(wb, w_classes);
+	W.take(w.terms, (size_t)nv * 24); W.take(w.fold_a, ((size_t)fold1 + 1) * 24); W.take(w.fold_b, ((size_t)fold2 + 1) * 24);
+	W.take(w.ends, (size_t)nv * 4); W.take(w.count, (size_t)nv * 4); W.take(w.start, ((size_t)nv + 1) * 4);
+	W.take(w.sums, scan_sums_words(nv) * 4); W.take(w.seg, (size_t)n * 4); W.take(w.hubs, ((size_t)curvature_hub_capacity(n) + 1) * 4);
+	W.take(w.cls, (size_t)nv * 4); W.take(w.rows, (size_t)nv * 28); W.take(w.classes, 32);
+	cx.d_curvature.ensure(W.total);
+	W.bind(cx.d_curvature.p);
 
 	// ---- the outputs, in one allocation
 	OutputPlan plan;
@@ -45,8 +41,8 @@ void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const Ed
 	plan.add("mean_normal", nout, 3, HRY_FLOAT);
 	plan.add("mean", nout, 1, HRY_FLOAT);
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (float*)out.find(name)->p; };
-	v.vertex_class = (uint32_t*)out.find("vertex_class")->p; v.area = dst("vertex_area"); v.defect = dst("angle_defect"); v.gaussian = dst("gaussian");
+	auto dst = [&](const char *name) { return out.ptr<float>(name); };
+	v.vertex_class = out.ptr<uint32_t>("vertex_class"); v.area = dst("vertex_area"); v.defect = dst("angle_defect"); v.gaussian = dst("gaussian");
 	v.mean_normal = dst("mean_normal"); v.mean = dst("mean");
 
 	hipStream_t st = cx.stream;
@@ -60,8 +56,7 @@ void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const Ed
 	HIP_OK(hipMemsetAsync(w.classes, 0, 32, st));
 	timer.mark(st);
 	const double *d_totals = launch_curvature(st, v, w);
-	timer.mark(st);
-	timer.mark(st); timer.mark(st);   // (one stretch: nothing comes down in between)
+	timer.mark(st);   // (one stretch: nothing comes down in between)
 	uint32_t cls[8] = {};
 	HIP_OK(hipMemcpyAsync(cls, w.classes, 32, hipMemcpyDeviceToHost, st));
 	if (d_totals) HIP_OK(hipMemcpyAsync(out.totals, d_totals, 24, hipMemcpyDeviceToHost, st));

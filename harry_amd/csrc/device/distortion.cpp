@@ -152,25 +152,30 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 
 	Carve W;
 	size_t nslots_all = 0;
-	std::vector<size_t> w_a(nl), w_b(nl), w_part(nl), slot_at(nl, 0), nslots(nl, 0);
+	std::vector<size_t> slot_at(nl, 0), nslots(nl, 0);
+	uint8_t *up_a[kMaxLists] = {}, *up_b[kMaxLists] = {}, *d_res;   // up_*: where a list's records go up, unless they are resident
+	DistPart *part[kMaxLists] = {};
+	uint32_t *up_org, *up_foff;
+	NormPart *npart;
 	for (size_t l = 0; l < nl; ++l) {
 		if (!compared(a, l)) continue;
 		nslots[l] = (size_t)a.lists[l].ncomp() + ((int)l == pl ? 1 : 0);
 		slot_at[l] = nslots_all;
 		nslots_all += nslots[l];
-		w_a[l] = W.reserve(a_res ? 0 : a.lists[l].data.size());
-		w_b[l] = W.reserve(b_res ? 0 : b.lists[l].data.size());
-		w_part[l] = W.reserve((size_t)distortion_blocks(a.lists[l].count) * nslots[l] * sizeof(DistPart));
+		W.take(up_a[l], a_res ? 0 : a.lists[l].data.size());
+		W.take(up_b[l], b_res ? 0 : b.lists[l].data.size());
+		W.take(part[l], (size_t)distortion_blocks(a.lists[l].count) * nslots[l] * sizeof(DistPart));
 	}
-	const size_t w_org = W.reserve(want_normals && !conn_res ? (size_t)ne * 4 : 0), w_foff = W.reserve(want_normals && !conn_res && !tri ? ((size_t)nf + 1) * 4 : 0);
-	const size_t w_npart = W.reserve(want_normals ? (size_t)distortion_blocks(nf) * sizeof(NormPart) : 0);
+	W.take(up_org, want_normals && !conn_res ? (size_t)ne * 4 : 0); W.take(up_foff, want_normals && !conn_res && !tri ? ((size_t)nf + 1) * 4 : 0);
+	W.take(npart, want_normals ? (size_t)distortion_blocks(nf) * sizeof(NormPart) : 0);
 	VertexRows vrows;
 	if (want_normals) vrows.reserve(cx, a, pl, a_res, W);
 	const size_t res_bytes = nslots_all * sizeof(DistFinal);
 	static_assert(sizeof(NormFinal) == sizeof(hry_normal_error) && sizeof(NormFinal) == 64, "the normals' record is an hry_normal_error");
-	const size_t w_res = W.reserve(res_bytes + 8 + (want_normals ? sizeof(NormFinal) : 0));   // the results, the status word, the normals' record: one copy brings all down
+	W.take(d_res, res_bytes + 8 + (want_normals ? sizeof(NormFinal) : 0));   // the results, the status word, the normals' record: one copy brings all down
 	cx.d_distortion.ensure(W.total);
 	void *wb = cx.d_distortion.p;
+	W.bind(wb);
 
 	Carve O;
 	std::vector<size_t> o_err(nl, 0);
@@ -180,12 +185,11 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 
 	hipStream_t st = cx.stream;
 	uint64_t up = 0;
-	auto put = [&](size_t i, const void *src, size_t bytes) {
+	auto put = [&](void *piece, const void *src, size_t bytes) {
 		if (!bytes) return;
-		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, i), src, bytes, hipMemcpyHostToDevice, st));
+		HIP_OK(hipMemcpyAsync(piece, src, bytes, hipMemcpyHostToDevice, st));
 		up += bytes;
 	};
-	uint8_t *d_res = W.ptr<uint8_t>(wb, w_res);
 	uint32_t *d_status = (uint32_t*)(d_res + res_bytes);
 	HIP_OK(hipMemsetAsync(d_status, 0, 8, st));
 	DistFold fold{};
@@ -195,11 +199,11 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 		if (!compared(a, l)) continue;
 		const AttrList &A = a.lists[l], &B = b.lists[l];
 		DistList J{};
-		if (a_res) J.a = cx.d_rec[l].as<uint8_t>(); else { put(w_a[l], A.data.data(), A.data.size()); J.a = W.ptr<uint8_t>(wb, w_a[l]); }
-		if (b_res) J.b = decoded_records(cx, l).as<uint8_t>(); else { put(w_b[l], B.data.data(), B.data.size()); J.b = W.ptr<uint8_t>(wb, w_b[l]); }
+		if (a_res) J.a = cx.d_rec[l].as<uint8_t>(); else { put(up_a[l], A.data.data(), A.data.size()); J.a = up_a[l]; }
+		if (b_res) J.b = decoded_records(cx, l).as<uint8_t>(); else { put(up_b[l], B.data.data(), B.data.size()); J.b = up_b[l]; }
 		J.map = map[l];
 		J.err = want_rows ? O.ptr<float>(out.block.p, o_err[l]) : nullptr;
-		J.part = W.ptr<DistPart>(wb, w_part[l]);
+		J.part = part[l];
 		J.rows = A.count; J.b_rows = B.count; J.sa = (uint32_t)A.stride(); J.sb = (uint32_t)B.stride();
 		J.pos = (int)l == pl ? pos_comp : -1;
 		jobs.push_back(J);
@@ -212,15 +216,15 @@ void distortion_build(Context &cx, const Mesh &a, const Mesh &b, const OrderResu
 	if (want_normals) {
 		if (conn_res) { N.F.org = cx.d_org.as<uint32_t>(); N.F.foff = tri ? nullptr : cx.d_foff.as<uint32_t>(); }
 		else {
-			put(w_org, a.org.data(), (size_t)ne * 4);
-			N.F.org = W.ptr<uint32_t>(wb, w_org);
-			if (!tri) { put(w_foff, a.face_off.data(), ((size_t)nf + 1) * 4); N.F.foff = W.ptr<uint32_t>(wb, w_foff); }
+			put(up_org, a.org.data(), (size_t)ne * 4);
+			N.F.org = up_org;
+			if (!tri) { put(up_foff, a.face_off.data(), ((size_t)nf + 1) * 4); N.F.foff = up_foff; }
 		}
 		const AttrList &A = a.lists[pl], &B = b.lists[pl];
 		for (size_t k = 0; k < jobs.size(); ++k) if (job_list[k] == (size_t)pl) { N.a = jobs[k].a; N.b = jobs[k].b; }
 		N.F.rows = nullptr; N.F.nf = nf; N.F.ne = ne; N.F.nv = general ? a.nv : A.count; N.F.nrows = A.count;
 		N.map = map[pl]; N.err = want_rows ? O.ptr<float>(out.block.p, o_nerr) : nullptr;
-		N.part = W.ptr<NormPart>(wb, w_npart);
+		N.part = npart;
 		N.b_rows = B.count; N.sa = (uint32_t)A.stride(); N.sb = (uint32_t)B.stride();
 		for (int c = 0; c < 3; ++c) { N.ca[c] = pa[pl].c[pos_comp + c]; N.cb[c] = pb[pl].c[pos_comp + c]; }
 	}

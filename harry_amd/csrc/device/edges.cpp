@@ -17,7 +17,6 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	require_render_of(cx, m, r);
 	const uint64_t ntri = m.ntri();
 	const uint32_t nout = r.nverts;
-	const NamedBuf *b_idx = r.find("indices"), *b_vsrc = r.find("vertex_source");
 	const uint32_t n = (uint32_t)(3 * ntri);
 	uint32_t pos_stride = 0;
 	const float *pos = geometry ? render_positions(m, r, "edges", pos_stride) : nullptr;
@@ -28,16 +27,16 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	Carve W;
 	DedupPlan D;
 	D.reserve(W, n, false);   // (the ids are the output buffer tri_edges)
-	const size_t w_count = W.reserve((size_t)n * 4), w_sums = W.reserve(scan_sums_words(n) * 4), w_hubs = W.reserve(((size_t)edges_hub_capacity(n) + 1) * 4);
-	const size_t w_classes = W.reserve(16);
+	uint32_t *count, *sums, *hubs, *classes;
+	W.take(count, (size_t)n * 4); W.take(sums, scan_sums_words(n) * 4); W.take(hubs, ((size_t)edges_hub_capacity(n) + 1) * 4); W.take(classes, 16);
 	cx.d_edges.ensure(W.total);
-	void *wb = cx.d_edges.p;
-	D.bind(W, wb);
+	W.bind(cx.d_edges.p);
+	D.bind(W, cx.d_edges.p);
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
 
 	EdgeView u{};
-	u.indices = (const uint32_t*)b_idx->p; u.vsrc = (const uint32_t*)b_vsrc->p; u.nout = nout;
+	u.indices = r.ptr<const uint32_t>("indices"); u.vsrc = r.ptr<const uint32_t>("vertex_source"); u.nout = nout;
 	if (n) HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));   // (the fills lie outside the events, as in render.cpp)
 	timer.mark(st);
 	if (n) launch_dedup_count(st, u, D);
@@ -56,11 +55,10 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	plan.add("tri_neighbours", ntri, 3, HRY_UINT);
 	if (geometry) { plan.add("edge_length", ne, 1, HRY_FLOAT); plan.add("edge_cot", ne, 1, HRY_FLOAT); plan.add("edge_cos", ne, 1, HRY_FLOAT); }
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+	auto dst = [&](const char *name) { return out.ptr<uint32_t>(name); };
 
-	uint32_t *count = W.ptr<uint32_t>(wb, w_count), *classes = W.ptr<uint32_t>(wb, w_classes);
 	if (ne) HIP_OK(hipMemsetAsync(count, 0, (size_t)ne * 4, st));
-	HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_hubs), 0, 4, st));
+	HIP_OK(hipMemsetAsync(hubs, 0, 4, st));
 	HIP_OK(hipMemsetAsync(classes, 0, 16, st));
 	timer.mark(st);
 	D.ids = dst("tri_edges");   // the numbering's ids are the buffer itself
@@ -71,9 +69,9 @@ void edges_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t fla
 	v.n = n; v.nout = nout; v.ne = ne;
 	if (geometry) {
 		v.pos = pos; v.pos_stride = pos_stride;
-		v.length = (float*)dst("edge_length"); v.cot = (float*)dst("edge_cot"); v.cos = (float*)dst("edge_cos");
+		v.length = out.ptr<float>("edge_length"); v.cot = out.ptr<float>("edge_cot"); v.cos = out.ptr<float>("edge_cos");
 	}
-	launch_edges(st, v, count, W.ptr<uint32_t>(wb, w_sums), W.ptr<uint32_t>(wb, w_hubs), classes);
+	launch_edges(st, v, count, sums, hubs, classes);
 	timer.mark(st);
 	uint32_t cls[3] = {};
 	HIP_OK(hipMemcpyAsync(cls, classes, 12, hipMemcpyDeviceToHost, st));

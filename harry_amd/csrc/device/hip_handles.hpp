@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/harry_amd.h"
@@ -110,14 +112,23 @@ struct DeviceBlock {
 	}
 };
 
-// one allocation in 256-byte aligned pieces: reserve() every piece while sizing, allocate `total` bytes, then ptr() into the block.
-// A piece of 0 bytes takes one unit all the same, so no two pieces share an address (nobody depends on the smallest piece's size)
+// one allocation in 256-byte aligned pieces: take(pointer, bytes) every piece while sizing, allocate `total` bytes, then bind(base)
+// points every pointer taken at its piece of the block -- a piece is stated once, with the pointer it is for.  The pointers are
+// written where they lay at take(): fields of the object the kernels get, not of a copy made in between.  reserve() / ptr() are
+// the same step in two halves, for pieces found by index (OutputPlan, DedupPlan, VertexRows, a piece per list).  A piece of 0
+// bytes takes one unit all the same, so no two pieces share an address (nobody depends on the smallest piece's size)
 struct Carve {
 	static constexpr size_t kAlign = 256;
 	std::vector<size_t> at;
+	std::vector<std::pair<void*, size_t>> taken;   // where a pointer lies, and its piece
 	size_t total = 0;
 	size_t reserve(size_t bytes) { at.push_back(total); total += (std::max<size_t>(bytes, 1) + kAlign - 1) & ~(kAlign - 1); return at.size() - 1; }
 	template <typename T> T *ptr(void *base, size_t i) const { return (T*)((uint8_t*)base + at[i]); }
+	template <typename T> void take(T *&pointer, size_t bytes) { taken.emplace_back((void*)&pointer, reserve(bytes)); }
+	void bind(void *base) const
+	{
+		for (const auto &t : taken) { void *p = ptr<void>(base, t.second); memcpy(t.first, &p, sizeof p); }   // (every object pointer has void*'s representation)
+	}
 };
 
 // pinned host memory, grow-only (persistent across calls: fresh pinned or pageable blocks cost a page fault per 4 KiB)

@@ -98,28 +98,29 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 	Carve W;   // the working arrays, pieces of d_ingest
 	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64);
 	const size_t status_bytes = sizeof(IngestStatus) + 8;   // (+ the number of welded vertices)
-	const size_t w_status = W.reserve(status_bytes);
-	const size_t w_fsum = W.reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = W.reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
-	const size_t w_keys = W.reserve(weld ? (size_t)nv * sv : 0);
+	IngestStatus *status;
+	uint32_t *fsum, *fstart, *frow;
+	uint8_t *keys;
+	W.take(status, status_bytes);
+	W.take(fsum, d_degrees ? (size_t)nwf * 4 : 0); W.take(fstart, d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	W.take(keys, weld ? (size_t)nv * sv : 0);
 	DedupPlan D;   // the weld's numbering of the rows (dedup.hip); D.ids: row -> output vertex
 	if (weld) D.reserve(W, nv);
-	const size_t w_frow = W.reserve(weld ? (size_t)nv * 4 : 0);
+	W.take(frow, weld ? (size_t)nv * 4 : 0);
 	cx.d_ingest.ensure(W.total);
-	void *wb = cx.d_ingest.p;
-	if (weld) D.bind(W, wb);
-	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
+	W.bind(cx.d_ingest.p);
+	if (weld) D.bind(W, cx.d_ingest.p);
 	uint32_t *d_nout = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
 
 	// ---- every kernel up to the checks, then ONE read-back of the status word (and the welded count)
-	launch_ingest_offsets(st, d_degrees, nf, W.ptr<uint32_t>(wb, w_fsum), W.ptr<uint32_t>(wb, w_fstart), cx.d_foff.as<uint32_t>(), status);
+	launch_ingest_offsets(st, d_degrees, nf, fsum, fstart, cx.d_foff.as<uint32_t>(), status);
 	const uint32_t *remap = nullptr;
 	if (weld) {
-		uint8_t *keys = W.ptr<uint8_t>(wb, w_keys);
 		launch_ingest_pack(st, pv, nv, nullptr, nv, keys);
 		HIP_OK(hipMemsetAsync(D.table, 0xff, D.table_bytes(), st));
 		launch_dedup_count(st, WeldView{ keys, (uint32_t)sv }, D);
-		launch_dedup_assign(st, D, nv, W.ptr<uint32_t>(wb, w_frow));
+		launch_dedup_assign(st, D, nv, frow);
 		if (nv) HIP_OK(hipMemcpyAsync(d_nout, D.total(), 4, hipMemcpyDeviceToDevice, st));
 		remap = D.ids;
 	} else launch_ingest_pack(st, pv, nv, nullptr, nv, cx.d_rec[1].as<uint8_t>());
@@ -139,7 +140,7 @@ Mesh *mesh_from_device(Context &cx, uint32_t nv, const hry_dev_column *vcols, in
 
 	// ---- welded: the records of the output vertices, gathered from the columns at each one's first row
 	if (weld) {
-		launch_ingest_pack(st, pv, nout, W.ptr<const uint32_t>(wb, w_frow), nv, cx.d_rec[1].as<uint8_t>());
+		launch_ingest_pack(st, pv, nout, frow, nv, cx.d_rec[1].as<uint8_t>());
 		if (d_remap && nv) HIP_OK(hipMemcpyAsync(d_remap, remap, (size_t)nv * 4, hipMemcpyDeviceToDevice, st));
 	}
 	m->nv = nout; m->nf = nf;
@@ -178,7 +179,8 @@ struct RowsIn {
 	int k = 0;                    // 0 pos, 1 tex, 2 nrm: d_remap's entry
 	uint32_t bad_bit = 0;
 	PackCols pack{};
-	size_t keys = 0, frow = 0;   // pieces of d_ingest (weld), with the numbering's
+	uint8_t *keys = nullptr;     // pieces of d_ingest (weld), with the numbering's
+	uint32_t *frow = nullptr;
 	DedupPlan dedup;
 };
 
@@ -269,34 +271,34 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	Carve W;   // the working arrays, pieces of d_ingest
 	const uint32_t nwf = (uint32_t)(((uint64_t)nf + 63) / 64);
 	const size_t status_bytes = sizeof(IngestStatus) + 16;   // (+ the records of the three lists after the weld, the face regions)
-	const size_t w_status = W.reserve(status_bytes);
-	const size_t w_fsum = W.reserve(d_degrees ? (size_t)nwf * 4 : 0), w_fstart = W.reserve(d_degrees ? ((size_t)nwf + 1) * 4 : 0);
-	const size_t w_mfirst = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0), w_mrank = W.reserve(d_face_material ? (size_t)kIngestMaterials * 4 : 0);
+	IngestStatus *status;
+	uint32_t *fsum, *fstart, *mfirst, *mrank;
+	W.take(status, status_bytes);
+	W.take(fsum, d_degrees ? (size_t)nwf * 4 : 0); W.take(fstart, d_degrees ? ((size_t)nwf + 1) * 4 : 0);
+	W.take(mfirst, d_face_material ? (size_t)kIngestMaterials * 4 : 0); W.take(mrank, d_face_material ? (size_t)kIngestMaterials * 4 : 0);
 	for (int l = 0; l < nl && weld; ++l) {   // every welded list has its own keys and table
 		RowsIn &R = in[l];
 		const uint32_t n = R.in->rows;
-		R.keys = W.reserve((size_t)n * R.pack.rec_stride);
+		W.take(R.keys, (size_t)n * R.pack.rec_stride);
 		R.dedup.reserve(W, n);
-		R.frow = W.reserve((size_t)n * 4);
+		W.take(R.frow, (size_t)n * 4);
 	}
 	cx.d_ingest.ensure(W.total);
-	void *wb = cx.d_ingest.p;
-	for (int l = 0; l < nl && weld; ++l) in[l].dedup.bind(W, wb);
-	IngestStatus *status = W.ptr<IngestStatus>(wb, w_status);
+	W.bind(cx.d_ingest.p);
+	for (int l = 0; l < nl && weld; ++l) in[l].dedup.bind(W, cx.d_ingest.p);
 	uint32_t *d_counts = (uint32_t*)((uint8_t*)status + sizeof(IngestStatus));   // [k]: records of list k after the weld; [3]: face regions
 	HIP_OK(hipMemsetAsync(status, 0, status_bytes, st));
 
 	// ---- every kernel up to the checks, then ONE read-back: the status word, the welded counts, the number of regions
-	launch_ingest_offsets(st, d_degrees, nf, W.ptr<uint32_t>(wb, w_fsum), W.ptr<uint32_t>(wb, w_fstart), cx.d_foff.as<uint32_t>(), status);
+	launch_ingest_offsets(st, d_degrees, nf, fsum, fstart, cx.d_foff.as<uint32_t>(), status);
 	for (int l = 0; l < nl; ++l) {
 		RowsIn &R = in[l];
 		const uint32_t n = R.in->rows;
 		if (!weld) { launch_ingest_pack(st, R.pack, n, nullptr, n, cx.d_rec[l].as<uint8_t>()); continue; }
-		uint8_t *keys = W.ptr<uint8_t>(wb, R.keys);
-		launch_ingest_pack(st, R.pack, n, nullptr, n, keys);
+		launch_ingest_pack(st, R.pack, n, nullptr, n, R.keys);
 		HIP_OK(hipMemsetAsync(R.dedup.table, 0xff, R.dedup.table_bytes(), st));
-		launch_dedup_count(st, WeldView{ keys, R.pack.rec_stride }, R.dedup);
-		launch_dedup_assign(st, R.dedup, n, W.ptr<uint32_t>(wb, R.frow));
+		launch_dedup_count(st, WeldView{ R.keys, R.pack.rec_stride }, R.dedup);
+		launch_dedup_assign(st, R.dedup, n, R.frow);
 		if (n) HIP_OK(hipMemcpyAsync(d_counts + R.k, R.dedup.total(), 4, hipMemcpyDeviceToDevice, st));
 	}
 	auto remap_of = [&](const RowsIn &R) { return weld ? (const uint32_t*)R.dedup.ids : nullptr; };
@@ -309,9 +311,9 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 	HIP_OK(hipMemsetAsync(cx.d_vreg.p, 0, std::max<size_t>((size_t)rows0 * 2, 16), st));   // one vertex region
 	launch_iota(st, rows0, cx.d_vattr.as<uint32_t>());                                // vertex v owns record v
 	if (d_face_material) {
-		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mfirst), 0xff, (size_t)kIngestMaterials * 4, st));
-		HIP_OK(hipMemsetAsync(W.ptr<void>(wb, w_mrank), 0, (size_t)kIngestMaterials * 4, st));
-		launch_ingest_regions(st, d_face_material, nf, W.ptr<uint32_t>(wb, w_mfirst), W.ptr<uint32_t>(wb, w_mrank), d_counts + 3, cx.d_freg.as<uint16_t>(), status);
+		HIP_OK(hipMemsetAsync(mfirst, 0xff, (size_t)kIngestMaterials * 4, st));
+		HIP_OK(hipMemsetAsync(mrank, 0, (size_t)kIngestMaterials * 4, st));
+		launch_ingest_regions(st, d_face_material, nf, mfirst, mrank, d_counts + 3, cx.d_freg.as<uint16_t>(), status);
 	} else HIP_OK(hipMemsetAsync(cx.d_freg.p, 0, std::max<size_t>((size_t)nf * 2, 16), st));
 	cx.h_small.ensure(4096);
 	HIP_OK(hipMemcpyAsync(cx.h_small.p, status, status_bytes, hipMemcpyDeviceToHost, st));
@@ -331,7 +333,7 @@ Mesh *mesh_from_device_corners(Context &cx, const hry_dev_rows *pos, const hry_d
 		if (nout > n) throw Error(HRY_E_INTERNAL, "weld: more records than rows");
 		m->lists[l].count = nout;
 		// ---- welded: the records of the output, gathered from the columns at each one's first row
-		if (weld) launch_ingest_pack(st, R.pack, nout, W.ptr<const uint32_t>(wb, R.frow), n, cx.d_rec[l].as<uint8_t>());
+		if (weld) launch_ingest_pack(st, R.pack, nout, R.frow, n, cx.d_rec[l].as<uint8_t>());
 		if (d_remap && d_remap[R.k] && n) {
 			if (weld) HIP_OK(hipMemcpyAsync(d_remap[R.k], R.dedup.ids, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
 			else launch_iota(st, n, d_remap[R.k]);

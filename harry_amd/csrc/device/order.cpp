@@ -48,24 +48,24 @@ void order_build(Context &cx, const Mesh &m, const WalkResult &w, const uint32_t
 
 	// ---- working arrays: the orders the encode did not leave whole in HBM, the coded faces' degrees, their scan
 	Carve W;
-	const size_t w_ov = W.reserve(d_order_v ? 0 : (size_t)vc * 4), w_of = W.reserve(d_order_f ? 0 : (size_t)fc * 4);
-	const size_t w_deg = W.reserve(mixed ? (size_t)fc * 4 : 0), w_doff = W.reserve(mixed ? ((size_t)fc + 1) * 4 : 0);
-	const size_t w_sums = W.reserve(mixed ? scan_sums_words(fc) * 4 : 0);
+	uint32_t *up_v, *up_f, *deg, *doff, *sums;
+	W.take(up_v, d_order_v ? 0 : (size_t)vc * 4); W.take(up_f, d_order_f ? 0 : (size_t)fc * 4);
+	W.take(deg, mixed ? (size_t)fc * 4 : 0); W.take(doff, mixed ? ((size_t)fc + 1) * 4 : 0); W.take(sums, mixed ? scan_sums_words(fc) * 4 : 0);
 	cx.d_order_ws.ensure(W.total);
-	void *ws = cx.d_order_ws.p;
+	W.bind(cx.d_order_ws.p);
 	if (!d_order_v) {
-		if (vc) HIP_OK(hipMemcpyAsync(W.ptr<void>(ws, w_ov), w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
-		d_order_v = W.ptr<uint32_t>(ws, w_ov);
+		if (vc) HIP_OK(hipMemcpyAsync(up_v, w.order_v.data(), (size_t)vc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_v = up_v;
 	}
 	if (!d_order_f) {
-		if (fc) HIP_OK(hipMemcpyAsync(W.ptr<void>(ws, w_of), w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
-		d_order_f = W.ptr<uint32_t>(ws, w_of);
+		if (fc) HIP_OK(hipMemcpyAsync(up_f, w.order_f.data(), (size_t)fc * 4, hipMemcpyHostToDevice, cx.stream));
+		d_order_f = up_f;
 	}
-	uint32_t *deg = mixed ? W.ptr<uint32_t>(ws, w_deg) : nullptr, *doff = mixed ? W.ptr<uint32_t>(ws, w_doff) : nullptr;
+	if (!mixed) deg = doff = nullptr;   // (one degree: nothing to count or to scan)
 
 	launch_order_vertex(cx.stream, d_order_v, vc, cv.org, nv, vertex, vertex_inv);
 	launch_order_face(cx.stream, cv, d_order_f, fc, face, face_inv, deg);
-	if (mixed && fc) launch_excl_scan(cx.stream, deg, fc, W.ptr<uint32_t>(ws, w_sums), doff);
+	if (mixed && fc) launch_excl_scan(cx.stream, deg, fc, sums, doff);
 	if (fc) launch_order_corner(cx.stream, cv, d_order_f, face, doff, corner, corner_inv);
 	if (m.general)
 		for (size_t l = 0; l < m.lists.size(); ++l) {

@@ -24,14 +24,13 @@ void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 
 	// ---- the working buffer
 	Carve W;
-	const size_t w_par = W.reserve((size_t)T * 8), w_flag = W.reserve((size_t)T * 4), w_num = W.reserve(((size_t)T + 1) * 4), w_sums = W.reserve(scan_sums_words(T) * 4);
-	const size_t w_turn = W.reserve((size_t)T * 4), w_summary = W.reserve(32);
+	OrientWork w{};
+	W.take(w.par, (size_t)T * 8); W.take(w.flag, (size_t)T * 4); W.take(w.num, ((size_t)T + 1) * 4); W.take(w.sums, scan_sums_words(T) * 4);
+	W.take(w.turn, (size_t)T * 4); W.take(w.summary, 32);
 	const size_t w_measures = outward ? measures_reserve(W, T) : 0;
 	cx.d_orient.ensure(W.total);
 	void *wb = cx.d_orient.p;
-	OrientWork w{};
-	w.par = W.ptr<uint32_t>(wb, w_par); w.flag = W.ptr<uint32_t>(wb, w_flag); w.num = W.ptr<uint32_t>(wb, w_num); w.sums = W.ptr<uint32_t>(wb, w_sums);
-	w.turn = W.ptr<uint32_t>(wb, w_turn); w.summary = W.ptr<uint32_t>(wb, w_summary);
+	W.bind(wb);
 	const MeasuresWork mw = outward ? measures_bind(W, wb, w_measures, w.flag, w.sums) : MeasuresWork{};
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
@@ -54,12 +53,12 @@ void orient_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 	plan.add("patch_counts", np, 8, HRY_UINT);
 	if (outward) plan.add("patch_measures", np, 8, HRY_FLOAT);
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+	auto dst = [&](const char *name) { return out.ptr<uint32_t>(name); };
 	v.tri_patch = dst("tri_patch"); v.tri_flip = dst("tri_flip"); v.face_flip = dst("face_flip"); v.oriented = dst("oriented_indices");
 	v.first = dst("patch_first"); v.counts = dst("patch_counts");
 	v.np = np;
 	if (outward) {   // the patches as the labels of the measures, over the triangles as oriented so far
-		v.measures = (float*)dst("patch_measures");
+		v.measures = out.ptr<float>("patch_measures");
 		g.indices = v.oriented; g.label = v.tri_patch; g.first = v.first; g.measures = v.measures;
 		g.ntri = T; g.nout = v.nout; g.nl = np;
 	}

@@ -135,19 +135,24 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 		resident = cx.d_freg.cap >= (size_t)nf * 2 && cx.d_vreg.cap >= (size_t)nv * 2 && cx.d_fattr.cap >= b.face_attr.size() * 4 &&
 		           cx.d_vattr.cap >= b.vtx_attr.size() * 4 && cx.d_cattr.cap >= b.corner_attr.size() * 4;
 
-	Carve W;   // the working buffer
-	const size_t w_foff = W.reserve(resident ? 0 : ((size_t)nf + 1) * 4), w_org = W.reserve(resident ? 0 : (size_t)ne * 4);
-	std::vector<size_t> w_rec(nl);
-	for (size_t l = 0; l < nl; ++l) w_rec[l] = W.reserve(resident || !rendered(m.lists[l]) ? 0 : m.lists[l].data.size());
+	// the working buffer: what goes up of a mesh that is not resident (up), the slot tables, the unweld's corner -> face table and
+	// numbering, the rows of a list with general bindings, the normals' arrays (n)
+	Carve W;
+	struct { uint32_t *foff, *org, *fattr, *vattr, *cattr; uint8_t *rec[kMaxLists]; uint16_t *freg, *vreg; } up{};
+	struct { double *fn; uint32_t *eface, *count, *fill, *start, *sums, *seg, *hubs; float *pos, *vn; } nw{};
+	int32_t *d_small;
+	uint32_t *eface, *idx;
+	W.take(up.foff, resident ? 0 : ((size_t)nf + 1) * 4); W.take(up.org, resident ? 0 : (size_t)ne * 4);
+	for (size_t l = 0; l < nl; ++l) W.take(up.rec[l], resident || !rendered(m.lists[l]) ? 0 : m.lists[l].data.size());
 	const bool tables = general && !resident;
-	const size_t w_freg = W.reserve(tables ? b.face_reg.size() * 2 : 0), w_vreg = W.reserve(tables ? b.vtx_reg.size() * 2 : 0);
-	const size_t w_fattr = W.reserve(tables ? b.face_attr.size() * 4 : 0), w_vattr = W.reserve(tables ? b.vtx_attr.size() * 4 : 0);
-	const size_t w_cattr = W.reserve(tables ? b.corner_attr.size() * 4 : 0);
-	const size_t w_small = W.reserve(small.size() * 4);
-	const size_t w_eface = W.reserve(unweld ? (size_t)ne * 4 : 0);
+	W.take(up.freg, tables ? b.face_reg.size() * 2 : 0); W.take(up.vreg, tables ? b.vtx_reg.size() * 2 : 0);
+	W.take(up.fattr, tables ? b.face_attr.size() * 4 : 0); W.take(up.vattr, tables ? b.vtx_attr.size() * 4 : 0);
+	W.take(up.cattr, tables ? b.corner_attr.size() * 4 : 0);
+	W.take(d_small, small.size() * 4);
+	W.take(eface, unweld ? (size_t)ne * 4 : 0);
 	DedupPlan D;   // the unweld's numbering of the corners (dedup.hip); D.ids: corner -> output vertex
 	if (unweld) D.reserve(W, ne);
-	const size_t w_idx = W.reserve(general ? (size_t)std::max(std::max(nf, nv), ne) * 4 : 0);
+	W.take(idx, general ? (size_t)std::max(std::max(nf, nv), ne) * 4 : 0);
 	// normals (normals.hip): N_f per face; per vertex its corners (counters, cursors, segment starts, the scan's sums, the segments,
 	// the list of hubs); a corner -> face table for mixed degrees (the unweld's where there is one); unwelded meshes: the position
 	// list per vertex and the normals per vertex
@@ -156,21 +161,21 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	all_tri &= (uint64_t)ne == 3ull * nf;
 	const bool n_eface = want_n && !all_tri && !unweld;
 	const size_t pos_w = want_n ? (size_t)m.lists[pl].ncomp() : 0;
-	const size_t w_fn = W.reserve(want_n ? (size_t)nf * 24 : 0), w_neface = W.reserve(n_eface ? (size_t)ne * 4 : 0);
-	const size_t w_ncount = W.reserve(want_vn ? (size_t)nv * 4 : 0), w_nfill = W.reserve(want_vn ? (size_t)nv * 4 : 0);
-	const size_t w_nstart = W.reserve(want_vn ? ((size_t)nv + 1) * 4 : 0), w_nsums = W.reserve(want_vn ? scan_sums_words(nv) * 4 : 0);
-	const size_t w_nseg = W.reserve(want_vn ? (size_t)ne * 4 : 0), w_nhubs = W.reserve(want_vn ? ((size_t)normals_hub_capacity(ne) + 1) * 4 : 0);
-	const size_t w_npos = W.reserve(want_n && unweld ? (size_t)nv * pos_w * 4 : 0), w_nvn = W.reserve(want_vn && unweld ? (size_t)nv * 12 : 0);
+	W.take(nw.fn, want_n ? (size_t)nf * 24 : 0); W.take(nw.eface, n_eface ? (size_t)ne * 4 : 0);
+	W.take(nw.count, want_vn ? (size_t)nv * 4 : 0); W.take(nw.fill, want_vn ? (size_t)nv * 4 : 0);
+	W.take(nw.start, want_vn ? ((size_t)nv + 1) * 4 : 0); W.take(nw.sums, want_vn ? scan_sums_words(nv) * 4 : 0);
+	W.take(nw.seg, want_vn ? (size_t)ne * 4 : 0); W.take(nw.hubs, want_vn ? ((size_t)normals_hub_capacity(ne) + 1) * 4 : 0);
+	W.take(nw.pos, want_n && unweld ? (size_t)nv * pos_w * 4 : 0); W.take(nw.vn, want_vn && unweld ? (size_t)nv * 12 : 0);
 	cx.d_render.ensure(W.total);
-	void *wb = cx.d_render.p;
-	if (unweld) D.bind(W, wb);
+	W.bind(cx.d_render.p);
+	if (unweld) D.bind(W, cx.d_render.p);
 
 	hipStream_t st = cx.stream;
-	uint64_t up = 0;
-	auto put = [&](size_t i, const void *src, size_t bytes) {
+	uint64_t uploaded = 0;
+	auto put = [&](void *piece, const void *src, size_t bytes) {
 		if (!bytes) return;
-		HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, i), src, bytes, hipMemcpyHostToDevice, st));
-		up += bytes;
+		HIP_OK(hipMemcpyAsync(piece, src, bytes, hipMemcpyHostToDevice, st));
+		uploaded += bytes;
 	};
 	const uint32_t *foff, *org;
 	const uint8_t *rec[kMaxLists] = {};
@@ -184,30 +189,27 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 			fattr = cx.d_fattr.as<uint32_t>(); vattr = cx.d_vattr.as<uint32_t>(); cattr = cx.d_cattr.as<uint32_t>();
 		}
 	} else {
-		put(w_foff, m.face_off.data(), ((size_t)nf + 1) * 4);
-		put(w_org, m.org.data(), (size_t)ne * 4);
-		foff = W.ptr<uint32_t>(wb, w_foff); org = W.ptr<uint32_t>(wb, w_org);
+		put(up.foff, m.face_off.data(), ((size_t)nf + 1) * 4);
+		put(up.org, m.org.data(), (size_t)ne * 4);
+		foff = up.foff; org = up.org;
 		for (size_t l = 0; l < nl; ++l) {
-			if (rendered(m.lists[l])) put(w_rec[l], m.lists[l].data.data(), m.lists[l].data.size());
-			rec[l] = W.ptr<uint8_t>(wb, w_rec[l]);
+			if (rendered(m.lists[l])) put(up.rec[l], m.lists[l].data.data(), m.lists[l].data.size());
+			rec[l] = up.rec[l];
 		}
 		if (general) {
-			put(w_freg, b.face_reg.data(), b.face_reg.size() * 2); put(w_vreg, b.vtx_reg.data(), b.vtx_reg.size() * 2);
-			put(w_fattr, b.face_attr.data(), b.face_attr.size() * 4); put(w_vattr, b.vtx_attr.data(), b.vtx_attr.size() * 4);
-			put(w_cattr, b.corner_attr.data(), b.corner_attr.size() * 4);
-			freg = W.ptr<uint16_t>(wb, w_freg); vreg = W.ptr<uint16_t>(wb, w_vreg);
-			fattr = W.ptr<uint32_t>(wb, w_fattr); vattr = W.ptr<uint32_t>(wb, w_vattr); cattr = W.ptr<uint32_t>(wb, w_cattr);
+			put(up.freg, b.face_reg.data(), b.face_reg.size() * 2); put(up.vreg, b.vtx_reg.data(), b.vtx_reg.size() * 2);
+			put(up.fattr, b.face_attr.data(), b.face_attr.size() * 4); put(up.vattr, b.vtx_attr.data(), b.vtx_attr.size() * 4);
+			put(up.cattr, b.corner_attr.data(), b.corner_attr.size() * 4);
+			freg = up.freg; vreg = up.vreg; fattr = up.fattr; vattr = up.vattr; cattr = up.cattr;
 		}
 	}
-	put(w_small, small.data(), small.size() * 4);
-	const int32_t *d_small = W.ptr<int32_t>(wb, w_small);
+	put(d_small, small.data(), small.size() * 4);
 
 	StretchTimer timer;
 
 	// ---- unweld: the number of output vertices comes down before the outputs are allocated (no corners: none).  The events
 	// enclose kernels only: the table's fill and every copy lie outside them
 	uint32_t nout = unweld ? 0 : nv;
-	uint32_t *eface = W.ptr<uint32_t>(wb, w_eface);
 	UnweldView u{};
 	if (unweld && ne) {
 		u.org = org; u.eface = eface; u.corner_attr = cattr; u.face_reg = freg; u.cslot = d_small + cslot_at;
@@ -236,19 +238,19 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 	if (want_vn) plan.add("normals", nout, 3, HRY_FLOAT);
 	if (want_fn) plan.add("face_normals", nf, 3, HRY_FLOAT);
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+	auto dst = [&](const char *name) { return out.ptr<uint32_t>(name); };
+	auto list_rows = [&](size_t l) { return out.ptr<float>(("list" + std::to_string(l)).c_str()); };
 
 	if (want_vn && nv) {   // (the counters' fill lies outside the events, like the table's)
-		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_ncount), 0, (size_t)nv * 4, st));
-		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nfill), 0, (size_t)nv * 4, st));
-		HIP_OK(hipMemsetAsync(W.ptr<uint32_t>(wb, w_nhubs), 0, 4, st));
+		HIP_OK(hipMemsetAsync(nw.count, 0, (size_t)nv * 4, st));
+		HIP_OK(hipMemsetAsync(nw.fill, 0, (size_t)nv * 4, st));
+		HIP_OK(hipMemsetAsync(nw.hubs, 0, 4, st));
 	}
 	timer.mark(st);
 	uint32_t *vsrc = dst("vertex_source");
 	if (unweld && ne) launch_dedup_assign(st, D, nout, dst("corner_source"), org, vsrc);   // vertex_source = org of the first corner
 	else if (!unweld) launch_iota(st, nv, vsrc);
 	launch_fan(st, foff, nf, ntri, unweld ? D.ids : org, ne, dst("tri_face"), dst("indices"));
-	uint32_t *idx = W.ptr<uint32_t>(wb, w_idx);
 	for (size_t l = 0; l < nl; ++l) {
 		const AttrList &L = m.lists[l];
 		if (!rendered(L)) continue;
@@ -264,7 +266,7 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 			launch_rows_of(st, v, rows, idx);
 			rows_idx = idx;
 		}
-		launch_render_gather(st, rec[l], L.stride(), L.count, rows_idx, rows, gather_plan(L), (float*)dst(("list" + std::to_string(l)).c_str()));
+		launch_render_gather(st, rec[l], L.stride(), L.count, rows_idx, rows, gather_plan(L), list_rows(l));
 	}
 	if (want_n) {
 		const AttrList &L = m.lists[pl];
@@ -277,27 +279,25 @@ void render_build(Context &cx, const Mesh &m, uint32_t flags, RenderResult &out)
 			v.slot = d_small + slot_at[pl]; v.count = L.count;
 			v.reg = vreg; v.nowner = nv; v.nregs = (uint32_t)b.nregs_vtx(); v.attr = vattr; v.nb = (uint32_t)b.nb_vtx; v.nelem = nv;
 			launch_rows_of(st, v, nv, idx);
-			launch_render_gather(st, rec[pl], L.stride(), L.count, idx, nv, gather_plan(L), W.ptr<float>(wb, w_npos));
-			n.pos = W.ptr<float>(wb, w_npos) + pos_at;
-		} else n.pos = (const float*)dst(("list" + std::to_string(pl)).c_str()) + pos_at;   // identity layout: row v is vertex v
+			launch_render_gather(st, rec[pl], L.stride(), L.count, idx, nv, gather_plan(L), nw.pos);
+			n.pos = nw.pos + pos_at;
+		} else n.pos = list_rows(pl) + pos_at;   // identity layout: row v is vertex v
 		if (!all_tri) {
-			if (n_eface) launch_edge_faces(st, foff, nf, W.ptr<uint32_t>(wb, w_neface));
-			n.eface = n_eface ? W.ptr<uint32_t>(wb, w_neface) : eface;
+			if (n_eface) launch_edge_faces(st, foff, nf, nw.eface);
+			n.eface = n_eface ? nw.eface : eface;
 		}
-		double *fn = W.ptr<double>(wb, w_fn);
-		launch_face_normals(st, n, fn, want_fn ? (float*)dst("face_normals") : nullptr);
+		launch_face_normals(st, n, nw.fn, want_fn ? out.ptr<float>("face_normals") : nullptr);
 		if (want_vn) {
-			float *vn = unweld ? W.ptr<float>(wb, w_nvn) : (float*)dst("normals");
-			launch_vertex_normals(st, n, fn, W.ptr<uint32_t>(wb, w_ncount), W.ptr<uint32_t>(wb, w_nfill), W.ptr<uint32_t>(wb, w_nstart), W.ptr<uint32_t>(wb, w_nsums),
-			                      W.ptr<uint32_t>(wb, w_nseg), W.ptr<uint32_t>(wb, w_nhubs), vn);
-			if (unweld) launch_normals_expand(st, vn, vsrc, nout, nv, (float*)dst("normals"));
+			float *vn = unweld ? nw.vn : out.ptr<float>("normals");
+			launch_vertex_normals(st, n, nw.fn, nw.count, nw.fill, nw.start, nw.sums, nw.seg, nw.hubs, vn);
+			if (unweld) launch_normals_expand(st, vn, vsrc, nout, nv, out.ptr<float>("normals"));
 		}
 	}
 	timer.mark(st);
 	if (general && nf) HIP_OK(hipMemcpyAsync(dst("face_region"), freg, (size_t)nf * 2, hipMemcpyDeviceToDevice, st));
 	HIP_OK(hipStreamSynchronize(st));
 	out.device_ms = timer.ms();
-	out.uploaded_bytes = up;
+	out.uploaded_bytes = uploaded;
 	out.nverts = nout;
 	out.ntris = ntri;
 }

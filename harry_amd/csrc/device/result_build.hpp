@@ -1,6 +1,8 @@
-// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp, creases.cpp, curvature.cpp, bvh.cpp): the
-// plan of a handle's named buffers, the timer of a build in two stretches, the result of the three topology builds and the checks
-// that one build is the build of another (result_build.cpp).
+// What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp,
+// creases.cpp, curvature.cpp, bvh.cpp): the plan of a handle's named buffers, the timer of a build in one stretch or
+// two, the one result type of the seven builds behind a render build and the checks that one build is the build of another
+// (result_build.cpp).  A driver states each working buffer once -- W.take(w.field, bytes), then W.bind(base) behind the allocation
+// (hip_handles.hpp: Carve) -- and fetches an output as out.ptr<T>("name") (context.hpp: DeviceResult).
 #pragma once
 #include "context.hpp"
 #include "kernels.hpp"
@@ -20,18 +22,21 @@ struct OutputPlan {
 	}
 };
 
-// A build runs in two stretches, with a few bytes coming down between them: mark() before and behind each, ms() their sum once the
-// stream has been waited for.  The events enclose kernels only: the fills and copies lie outside them
+// A build runs in one stretch, or in two with a few bytes coming down between them: mark() before and behind each (two marks or
+// four), ms() their sum once the stream has been waited for.  The events enclose kernels only: the fills and copies lie outside them
 struct StretchTimer {
 	TimedEvent ev[4];
 	int marks = 0;
 	void mark(hipStream_t st) { HIP_OK(hipEventRecord(ev[marks++], st)); }
 	double ms()
 	{
-		float a = 0, c = 0;
-		HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-		HIP_OK(hipEventElapsedTime(&c, ev[2], ev[3]));
-		return (double)a + (double)c;
+		double sum = 0;
+		for (int i = 0; i + 1 < marks; i += 2) {
+			float stretch = 0;
+			HIP_OK(hipEventElapsedTime(&stretch, ev[i], ev[i + 1]));
+			sum += (double)stretch;
+		}
+		return sum;
 	}
 };
 

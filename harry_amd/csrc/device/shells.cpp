@@ -25,16 +25,15 @@ void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 	Carve W;
 	DedupPlan D;
 	D.reserve(W, n, true);   // the corners by (shell, decoded vertex)
-	const size_t w_par = W.reserve((size_t)T * 4), w_flag = W.reserve((size_t)T * 4), w_num = W.reserve(((size_t)T + 1) * 4), w_sums = W.reserve(scan_sums_words(T) * 4);
-	const size_t w_slot = W.reserve((size_t)n * 4), w_loop = W.reserve((size_t)ne * 4), w_summary = W.reserve(32);
+	ShellsWork w{};
+	W.take(w.par, (size_t)T * 4); W.take(w.flag, (size_t)T * 4); W.take(w.num, ((size_t)T + 1) * 4); W.take(w.sums, scan_sums_words(T) * 4);
+	W.take(w.slot, (size_t)n * 4); W.take(w.loop_par, (size_t)ne * 4); W.take(w.summary, 32);
 	const size_t w_measures = geometry ? measures_reserve(W, T) : 0;
 	cx.d_shells.ensure(W.total);
 	void *wb = cx.d_shells.p;
+	W.bind(wb);
 	D.bind(W, wb);
-	ShellsWork w{};
-	w.par = W.ptr<uint32_t>(wb, w_par); w.flag = W.ptr<uint32_t>(wb, w_flag); w.num = W.ptr<uint32_t>(wb, w_num); w.sums = W.ptr<uint32_t>(wb, w_sums);
-	w.pair_id = D.ids; w.pair_first_of = D.first_of; w.slot = W.ptr<uint32_t>(wb, w_slot); w.loop_par = W.ptr<uint32_t>(wb, w_loop);
-	w.summary = W.ptr<uint32_t>(wb, w_summary);
+	w.pair_id = D.ids; w.pair_first_of = D.first_of;
 	const MeasuresWork mw = geometry ? measures_bind(W, wb, w_measures, w.flag, w.sums) : MeasuresWork{};
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
@@ -56,11 +55,11 @@ void shells_build(Context &cx, const Mesh &m, const RenderResult &r, const Edges
 	plan.add("shell_counts", ns, 8, HRY_UINT);
 	if (geometry) plan.add("shell_measures", ns, 8, HRY_FLOAT);
 	plan.alloc(cx.device, out);
-	auto dst = [&](const char *name) { return (uint32_t*)out.find(name)->p; };
+	auto dst = [&](const char *name) { return out.ptr<uint32_t>(name); };
 	v.tri_shell = dst("tri_shell"); v.face_shell = dst("face_shell"); v.edge_shell = dst("edge_shell"); v.first = dst("shell_first"); v.counts = dst("shell_counts");
 	v.ns = ns;
 	if (geometry) {   // the shells as the labels of the measures
-		g.indices = v.indices; g.label = v.tri_shell; g.first = v.first; g.measures = (float*)dst("shell_measures");
+		g.indices = v.indices; g.label = v.tri_shell; g.first = v.first; g.measures = out.ptr<float>("shell_measures");
 		g.ntri = T; g.nout = v.nout; g.nl = ns;
 	}
 

@@ -126,25 +126,31 @@ void quant_sweep_build(Context &cx, Mesh &m, uint32_t flags, SweepResult &out)
 	if (nrm_qmax && res) res = cx.res_nf == nf && cx.res_ne == ne && cx.d_org.cap >= (size_t)ne * 4 && (tri || cx.d_foff.cap >= ((size_t)nf + 1) * 4);
 	Carve W;
 	size_t ns_all = 0;
-	std::vector<size_t> w_rec(nl), w_part(nl), slot_at(nl, 0);
+	std::vector<size_t> slot_at(nl, 0);
+	std::vector<uint8_t*> up_rec(nl, nullptr);   // where a list's records go up, unless the mesh is resident (the vectors keep their size)
+	std::vector<DistPart*> part(nl, nullptr);
+	uint32_t *up_org, *up_foff;
+	uint8_t *d_res;
 	for (size_t l = 0; l < nl; ++l) {
 		if (!jobs[l].ns) continue;
 		slot_at[l] = ns_all;
 		ns_all += jobs[l].ns;
-		w_rec[l] = W.reserve(res ? 0 : m.lists[l].data.size());
-		w_part[l] = W.reserve((size_t)distortion_blocks(m.lists[l].count) * jobs[l].ns * sizeof(DistPart));
+		W.take(up_rec[l], res ? 0 : m.lists[l].data.size());
+		W.take(part[l], (size_t)distortion_blocks(m.lists[l].count) * jobs[l].ns * sizeof(DistPart));
 	}
 	out.device_ms = 0; out.uploaded_bytes = 0;
 	if (!ns_all) return;
-	const size_t w_org = W.reserve(nrm_qmax && !res ? (size_t)ne * 4 : 0), w_foff = W.reserve(nrm_qmax && !res && !tri ? ((size_t)nf + 1) * 4 : 0);
-	const size_t w_npart = W.reserve(nrm_qmax ? (size_t)distortion_blocks(nf) * nrm_qmax * sizeof(NormPart) : 0);
+	NormPart *npart;
+	W.take(up_org, nrm_qmax && !res ? (size_t)ne * 4 : 0); W.take(up_foff, nrm_qmax && !res && !tri ? ((size_t)nf + 1) * 4 : 0);
+	W.take(npart, nrm_qmax ?(size_t)distortion_blocks(nf) * nrm_qmax * sizeof(NormPart) : 0);
 	VertexRows vrows;
 	if (nrm_qmax) vrows.reserve(cx, m, pl, res, W);
 	static_assert(sizeof(DistFinal) % 8 == 0 && sizeof(NormFinal) == sizeof(hry_normal_error) && sizeof(NormFinal) == 64, "the normals' records follow the table");
 	const size_t dist_bytes = ns_all * sizeof(DistFinal), res_bytes = dist_bytes + (size_t)nrm_qmax * sizeof(NormFinal);   // one copy brings both down
-	const size_t w_res = W.reserve(res_bytes);
+	W.take(d_res, res_bytes);
 	cx.d_sweep.ensure(W.total);
 	void *wb = cx.d_sweep.p;
+	W.bind(wb);
 
 	hipStream_t st = cx.stream;
 	uint64_t up = 0;
@@ -155,11 +161,11 @@ void quant_sweep_build(Context &cx, Mesh &m, uint32_t flags, SweepResult &out)
 		const AttrList &L = m.lists[l];
 		if (res) J.rec = cx.d_rec[l].as<uint8_t>();
 		else {
-			if (!L.data.empty()) HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_rec[l]), L.data.data(), L.data.size(), hipMemcpyHostToDevice, st));
+			if (!L.data.empty()) HIP_OK(hipMemcpyAsync(up_rec[l], L.data.data(), L.data.size(), hipMemcpyHostToDevice, st));
 			up += L.data.size();
-			J.rec = W.ptr<uint8_t>(wb, w_rec[l]);
+			J.rec = up_rec[l];
 		}
-		J.part = W.ptr<DistPart>(wb, w_part[l]);
+		J.part = part[l];
 		J.rows = L.count; J.stride = (uint32_t)L.stride();
 		const int k = fold.n++;
 		fold.part[k] = J.part; fold.nblocks[k] = distortion_blocks(L.count); fold.nslots[k] = J.ns; fold.out_at[k] = (uint32_t)slot_at[l];
@@ -169,33 +175,33 @@ void quant_sweep_build(Context &cx, Mesh &m, uint32_t flags, SweepResult &out)
 		const SweepList &J = jobs[pl];
 		if (res) { N.F.org = cx.d_org.as<uint32_t>(); N.F.foff = tri ? nullptr : cx.d_foff.as<uint32_t>(); }
 		else {
-			HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_org), m.org.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
+			HIP_OK(hipMemcpyAsync(up_org, m.org.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
 			up += (size_t)ne * 4;
-			N.F.org = W.ptr<uint32_t>(wb, w_org);
+			N.F.org = up_org;
 			if (!tri) {
-				HIP_OK(hipMemcpyAsync(W.ptr<uint8_t>(wb, w_foff), m.face_off.data(), ((size_t)nf + 1) * 4, hipMemcpyHostToDevice, st));
+				HIP_OK(hipMemcpyAsync(up_foff, m.face_off.data(), ((size_t)nf + 1) * 4, hipMemcpyHostToDevice, st));
 				up += ((size_t)nf + 1) * 4;
-				N.F.foff = W.ptr<uint32_t>(wb, w_foff);
+				N.F.foff = up_foff;
 			}
 		}
 		N.F.rows = nullptr; N.F.nf = nf; N.F.ne = ne; N.F.nv = m.general ? m.nv : J.rows; N.F.nrows = J.rows;
-		N.rec = J.rec; N.part = W.ptr<NormPart>(wb, w_npart); N.stride = J.stride; N.qmax = nrm_qmax;
+		N.rec = J.rec; N.part = npart; N.stride = J.stride; N.qmax = nrm_qmax;
 		for (int a = 0; a < 3; ++a) N.c[a] = J.c[J.pos + a].rc;
 		N.type = N.c[0].dst_type == N.c[1].dst_type && N.c[1].dst_type == N.c[2].dst_type ? N.c[0].dst_type : -1;
 	}
 	TimedEvent ev[2];
 	HIP_OK(hipEventRecord(ev[0], st));
 	for (size_t l = 0; l < nl; ++l) if (jobs[l].ns) launch_quant_sweep(st, jobs[l]);
-	launch_quant_sweep_fold(st, fold, W.ptr<DistFinal>(wb, w_res));
+	launch_quant_sweep_fold(st, fold, (DistFinal*)d_res);
 	if (nrm_qmax) {
 		N.F.rows = vrows.launch(cx, m, pl, W, wb, up);
 		launch_normal_sweep(st, N);
-		launch_normal_fold(st, N.part, distortion_blocks(nf), (uint32_t)nrm_qmax, (NormFinal*)(W.ptr<uint8_t>(wb, w_res) + dist_bytes));
+		launch_normal_fold(st, N.part, distortion_blocks(nf), (uint32_t)nrm_qmax, (NormFinal*)(d_res + dist_bytes));
 	}
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(ev[1], st));
 	std::vector<uint8_t> tab(res_bytes);
-	HIP_OK(hipMemcpyAsync(tab.data(), W.ptr<uint8_t>(wb, w_res), res_bytes, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipMemcpyAsync(tab.data(), d_res, res_bytes, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
 	float ms = 0;
 	HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));

@@ -17,7 +17,7 @@ void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t 
 	const uint64_t ntri = m.ntri();
 	const uint32_t nout = r.nverts, n = (uint32_t)(3 * ntri);
 	TanView v{};
-	v.indices = (const uint32_t*)r.find("indices")->p; v.n = n; v.nout = nout; v.angle = (flags & HRY_TANGENTS_ANGLE_WEIGHTED) ? 1 : 0;
+	v.indices = r.ptr<const uint32_t>("indices"); v.n = n; v.nout = nout; v.angle = (flags & HRY_TANGENTS_ANGLE_WEIGHTED) ? 1 : 0;
 	v.pos = render_positions(m, r, "tangents", v.pos_stride);
 	v.uv = render_attribute(m, r, 16, 2, "tangents", "texture-coordinate", v.uv_stride);
 	if (flags & HRY_TANGENTS_STORED_NORMALS) v.nrm = render_attribute(m, r, 1, 3, "tangents", "normal", v.nrm_stride);
@@ -32,21 +32,20 @@ void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t 
 	// ---- the working buffer: per triangle its two terms and the word of its sign; per output vertex a counter and a segment start;
 	// the scan's sums; the segments; the list of long segments; the four class counters
 	Carve W;
-	const size_t w_terms = W.reserve((size_t)ntri * 48), w_sign = W.reserve((size_t)ntri * 4), w_count = W.reserve((size_t)nout * 4);
-	const size_t w_start = W.reserve(((size_t)nout + 1) * 4), w_sums = W.reserve(scan_sums_words(nout) * 4), w_seg = W.reserve((size_t)n * 4);
-	const size_t w_hubs = W.reserve(((size_t)tangents_hub_capacity(n) + 1) * 4), w_classes = W.reserve(16);
+	TanWork w{};
+	W.take(w.terms, (size_t)ntri * 48); W.take(w.sign, (size_t)ntri * 4); W.take(w.count, (size_t)nout * 4);
+	W.take(w.start, ((size_t)nout + 1) * 4); W.take(w.sums, scan_sums_words(nout) * 4); W.take(w.seg, (size_t)n * 4);
+	W.take(w.hubs, ((size_t)tangents_hub_capacity(n) + 1) * 4); W.take(w.classes, 16);
 	cx.d_tangents.ensure(W.total);
-	void *wb = cx.d_tangents.p;
-	const TanWork w{ W.ptr<double>(wb, w_terms), W.ptr<uint32_t>(wb, w_sign), W.ptr<uint32_t>(wb, w_count), W.ptr<uint32_t>(wb, w_start), W.ptr<uint32_t>(wb, w_sums),
-	                 W.ptr<uint32_t>(wb, w_seg), W.ptr<uint32_t>(wb, w_hubs), W.ptr<uint32_t>(wb, w_classes) };
+	W.bind(cx.d_tangents.p);
 
 	// ---- the outputs, in one allocation
 	OutputPlan plan;
 	plan.add("tangents", nout, 4, HRY_FLOAT);
 	if (flags & HRY_TANGENTS_BITANGENTS) plan.add("bitangents", nout, 3, HRY_FLOAT);
 	plan.alloc(cx.device, out);
-	v.tangents = (float*)out.find("tangents")->p;
-	if (flags & HRY_TANGENTS_BITANGENTS) v.bitangents = (float*)out.find("bitangents")->p;
+	v.tangents = out.ptr<float>("tangents");
+	if (flags & HRY_TANGENTS_BITANGENTS) v.bitangents = out.ptr<float>("bitangents");
 
 	hipStream_t st = cx.stream;
 	StretchTimer timer;
@@ -55,8 +54,7 @@ void tangents_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t 
 	HIP_OK(hipMemsetAsync(w.classes, 0, 16, st));
 	timer.mark(st);
 	launch_tangents(st, v, w);
-	timer.mark(st);
-	timer.mark(st); timer.mark(st);   // (one stretch: nothing comes down in between)
+	timer.mark(st);   // (one stretch: nothing comes down in between)
 	uint32_t cls[4] = {};
 	HIP_OK(hipMemcpyAsync(cls, w.classes, 16, hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));

@@ -170,6 +170,31 @@ int main()
 		check(ok, "every piece is 256-byte aligned, begins at or after the end of the one before, and has an address of its own");
 		check(c.total % 256 == 0 && c.total == (size_t)(c.ptr<uint8_t>(base, piece.back()) - base) + 256, "total is the end of the last piece");
 		check(c.total == 256 * (1 + 1 + 1 + 1 + 2 + 1 + 1 + 4 + 1 + 1), "an empty piece takes one unit, the others their size rounded up");
+
+		// take / bind: the same pieces in one statement each -- the addresses reserve / ptr hand out for the same sequence, whatever
+		// the pointers' types, reserve()d pieces in between included; nothing is written before bind()
+		struct Work { uint32_t *a = nullptr; double *b = nullptr; const uint8_t *k = nullptr; float *f = nullptr; unsigned long long *q = nullptr; uint32_t *z[5] = {}; } w;
+		Carve t;
+		t.take(w.a, sizes[0]); t.take(w.b, sizes[1]); t.take(w.k, sizes[2]); t.take(w.f, sizes[3]); t.take(w.q, sizes[4]);
+		const size_t between = t.reserve(sizes[5]);   // (a piece found by index, as DedupPlan's)
+		for (size_t i = 6; i < 10; ++i) t.take(w.z[i - 6], sizes[i]);
+		check(t.total == c.total && t.at == c.at && between == 5, "take lays the pieces out as reserve does");
+		check(!w.a && !w.b && !w.k && !w.f && !w.q && !w.z[0] && !w.z[3], "take writes no pointer");
+		t.bind(base);
+		const void *got[] = { w.a, w.b, w.k, w.f, w.q, t.ptr<void>(base, between), w.z[0], w.z[1], w.z[2], w.z[3] };
+		bool same = true, apart = true;
+		for (size_t i = 0; i < 10; ++i) {
+			same = same && got[i] == c.ptr<void>(base, piece[i]);
+			for (size_t j = 0; j < i; ++j) apart = apart && got[i] != got[j];
+		}
+		check(same, "bind hands out the addresses of reserve / ptr for the same sequence");
+		check(apart && w.z[4] == nullptr, "no two pieces share an address, and a pointer that was not taken is left alone");
+		alignas(256) static uint8_t other[16 * 256];
+		t.bind(other);
+		check((const uint8_t*)w.a == other && (const uint8_t*)w.z[3] == other + (c.ptr<uint8_t>(base, piece[9]) - base), "a second bind moves every pointer to the new block");
+		Carve none;
+		none.bind(base);
+		check(none.total == 0, "an empty carve binds nothing");
 	}
 	check(fake_hip::live.empty() && fake_hip::ranges.empty() && calls.find('!') == std::string::npos, "the counts balance at exit");
 	if (failures) return 1;
