@@ -100,6 +100,7 @@ CREASES_ANGLE_WEIGHTED = 1
 CREASE_SMOOTH, CREASE_SHARP, CREASE_BOUNDARY, CREASE_NONMANIFOLD, CREASE_MISORIENTED, CREASE_DEGENERATE = 0, 1, 2, 3, 4, 5
 VERTEX_ISOLATED, VERTEX_INTERIOR, VERTEX_BOUNDARY, VERTEX_IRREGULAR, VERTEX_DEGENERATE = 0, 1, 2, 3, 8
 CAST_HOST = 1
+NEAREST_HOST = 1
 BVH_LEAF = 0x80000000   # a child word of "node_children" with this bit names a leaf
 TOL_MAX_ABS, TOL_MAX_REL, TOL_RMS, TOL_POS_DIST, TOL_NORMAL_CHORD = 0, 1, 2, 3, 4
 
@@ -210,6 +211,8 @@ def load():
     L.hry_bvh_cast.restype = C.c_int
     L.hry_bvh_cast.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_double, C.c_double, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint64),
                                C.POINTER(C.c_double)]
+    L.hry_bvh_nearest.restype = C.c_int
+    L.hry_bvh_nearest.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_double, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     L.hry_mesh_flip_faces.restype = C.c_int; L.hry_mesh_flip_faces.argtypes = [vp, vp, C.POINTER(vp)]
     L.hry_mesh_from_device.restype = C.c_int
     L.hry_mesh_from_device.argtypes = [vp, C.c_uint32, C.POINTER(DevColumn), C.c_int, C.c_uint32, vp, vp, C.c_int, C.c_uint64, C.POINTER(DevColumn),

@@ -794,6 +794,44 @@ class Codec:
         deepest leaf, at most 62)"""
         return dict(getattr(self, "_bvh_stat", {}))
 
+    # ---- mesh-to-mesh deviation (include/harry_amd.h: hry_bvh_nearest)
+    def position_rows(self, mesh: Mesh) -> np.ndarray:
+        """the float rows [U, 3] of the positions of the mesh's render build (dequantised, one row per output vertex): a view into
+        the rows of its position list"""
+        L = nat.load()
+        rn = self.render_numpy(mesh)
+        (pl,) = [l for l in range(mesh.nlists) if mesh.list_target(l) == 1 and L.hry_list_interp_ncomp(mesh.h, l, 0) >= 3]
+        at = L.hry_list_interp_offset(mesh.h, pl, 0)
+        return rn[f"list{pl}"][:, at:at + 3]
+
+    def deviation(self, a: Mesh, b: Mesh) -> dict:
+        """the Metro-style deviation of two surfaces, sampled at their vertices: "forward" -- the position rows of a's render build
+        against the closest points of b's triangles --, "backward" -- b's rows against a's triangles --, each {"points", "answered"
+        (rows with finite positions, where the other mesh has a live triangle), "max", "rms"}, and "hausdorff", the larger max.
+        The squared distances are hry_bvh_nearest's; the square roots are taken here, rms = sqrt(the sum of d2 in index order /
+        answered), in double"""
+        def one_way(points, surface: "Bvh") -> dict:
+            d2 = surface.nearest_numpy(points)["d2"] if len(points) else np.zeros(0)
+            answered = np.isfinite(d2)
+            total = 0.0
+            for x in d2[answered].tolist():
+                total += x
+            k = int(answered.sum())
+            return {"points": len(points), "answered": k, "max": math.sqrt(surface.max_d2) if k else 0.0, "rms": math.sqrt(total / k) if k else 0.0}
+
+        pa, pb = self.position_rows(a), self.position_rows(b)
+        ba = self.bvh(a)
+        try:
+            bb = self.bvh(b)
+            try:
+                out = {"forward": one_way(pa, bb), "backward": one_way(pb, ba)}
+            finally:
+                bb.close()
+        finally:
+            ba.close()
+        out["hausdorff"] = max(out["forward"]["max"], out["backward"]["max"])
+        return out
+
     # ---- meshes from device buffers (include/harry_amd.h: hry_mesh_from_device)
     def mesh_from_tensors(self, indices, vertex, faces=None, degrees=None, weld: bool = False, return_remap: bool = False):
         """A mesh from torch tensors on this codec's device, equal to Mesh.from_arrays of the same values and resident here (the
@@ -1153,7 +1191,8 @@ class Bvh(_NamedBuffers):
     """A bounding-volume hierarchy over the triangles of a render build (include/harry_amd.h: hry_bvh_build) and the closest-hit
     ray cast over it (hry_bvh_cast).  The buffers lie in HBM; every bit of them depends on the render build alone, every bit of a
     cast on them and the rays alone.  After a cast: hits (rays that hit), box_tests (box intervals the walk evaluated) and device_ms
-    (the kernel) of that cast."""
+    (the kernel) of that cast.  nearest / nearest_numpy: the closest point of the triangles to every query point
+    (hry_bvh_nearest), every bit of it on the hierarchy and the points alone."""
 
     BUFFERS = ("leaf_tri", "leaf_code", "leaf_box", "leaf_positions", "node_children", "node_box", "scene_box")
     SUMMARY = ("triangles", "leaves", "dead", "distinct_codes", "depth")
@@ -1161,8 +1200,8 @@ class Bvh(_NamedBuffers):
 
     def __init__(self, codec: "Codec", handle):
         self.codec, self.h = codec, handle
-        self.hits = self.box_tests = 0
-        self.device_ms = 0.0
+        self.hits = self.box_tests = self.answered = self.bound_tests = 0
+        self.device_ms = self.max_d2 = 0.0
 
     def count(self) -> int:
         """L: the leaves, the triangles with finite positions"""
@@ -1238,6 +1277,45 @@ class Bvh(_NamedBuffers):
         tri, t, uv = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty((n, 2), np.float32)
         self._cast(n, origins.ctypes.data, so, dirs.ctypes.data, sd, tmin, tmax, nat.CAST_HOST, tri.ctypes.data, t.ctypes.data, uv.ctypes.data)
         return {"tri": tri, "t": t, "uv": uv}
+
+    def _nearest(self, n, q_ptr, q_stride, max_dist, flags, tri_ptr, d2_ptr, uv_ptr, point_ptr):
+        stat, ms = (C.c_uint64 * 3)(), C.c_double()
+        nat.check(nat.load().hry_bvh_nearest(self.codec.h, self.h, n, q_ptr, q_stride, float(max_dist), flags, tri_ptr, d2_ptr, uv_ptr, point_ptr, stat,
+                                             C.byref(ms)))
+        self.answered, self.bound_tests, self.device_ms = int(stat[0]), int(stat[1]), ms.value
+        self.max_d2 = float(np.uint64(stat[2]).view(np.float64))
+
+    def nearest(self, points, max_dist: float = float("inf")) -> dict:
+        """the closest point of the triangles to every query point within max_dist (hry_bvh_nearest).  points: a float32 torch
+        tensor [n, 3] on the codec's device, of any row stride (a view into a wider buffer, an expanded [1, 3]); [3]: one point.
+        Returns tensors there: "tri" int32 [n] (-1: nothing within max_dist), "d2" float64 [n] (the squared distance; +inf),
+        "uv" float32 [n, 2] (the barycentric coordinates of the second and third corner), "point" float32 [n, 3].  Afterwards:
+        answered, bound_tests, max_d2 (the largest d2 among the answered points, 0.0 without one) and device_ms"""
+        import torch   # only here: the rest of the package does not need torch
+        dev = torch.device("cuda", self.codec.device)
+        if points.dtype != torch.float32 or points.device != dev or points.dim() not in (1, 2) or points.shape[-1] != 3:
+            raise ValueError("points: a float32 tensor [n, 3] or [3] on the codec's device")
+        if not (points.stride(-1) == 1 and (points.dim() == 1 or points.stride(0) >= 0)):
+            points = points.contiguous()
+        n, stride = (1, 0) if points.dim() == 1 else (points.shape[0], points.stride(0) * 4)
+        torch.cuda.current_stream(dev).synchronize()   # (the points may still be in the making on torch's stream)
+        tri, d2 = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float64, device=dev)
+        uv, point = torch.empty((n, 2), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+        self._nearest(n, points.data_ptr(), stride, max_dist, 0, tri.data_ptr(), d2.data_ptr(), uv.data_ptr(), point.data_ptr())
+        return {"tri": tri, "d2": d2, "uv": uv, "point": point}
+
+    def nearest_numpy(self, points, max_dist: float = float("inf")) -> dict:
+        """the same from and to host arrays (HRY_NEAREST_HOST: the library stages them); "tri" is uint32 with NO_ELEMENT for an
+        unanswered point"""
+        points = np.asarray(points, np.float32)
+        if points.ndim not in (1, 2) or points.shape[-1] != 3:
+            raise ValueError("points: a float32 array [n, 3] or [3]")
+        if not (points.strides[-1] == 4 and (points.ndim == 1 or (points.strides[0] >= 0 and points.strides[0] % 4 == 0))):
+            points = np.ascontiguousarray(points)
+        n, stride = (1, 0) if points.ndim == 1 else (points.shape[0], points.strides[0])
+        tri, d2, uv, point = np.empty(n, np.uint32), np.empty(n, np.float64), np.empty((n, 2), np.float32), np.empty((n, 3), np.float32)
+        self._nearest(n, points.ctypes.data, stride, max_dist, nat.NEAREST_HOST, tri.ctypes.data, d2.ctypes.data, uv.ctypes.data, point.ctypes.data)
+        return {"tri": tri, "d2": d2, "uv": uv, "point": point}
 
 
 class Distortion(_NamedBuffers):

@@ -793,7 +793,7 @@ int hry_curvature_totals(const hry_curvature *c, double out[3])
 	for (int i = 0; i < 3; ++i) out[i] = c->r.totals[i];
 	return HRY_OK;
 }
-// the hierarchy over the triangles of a render build and the cast over it (bvh.cpp)
+// the hierarchy over the triangles of a render build, the cast and the closest-point query over it (bvh.cpp)
 int hry_bvh_build(hry_ctx *ctx, const hry_mesh *m, const hry_render *r, uint32_t flags, hry_bvh **out)
 {
 	return handle_build(ctx, m && r, out, [&](hry_bvh &h) { bvh_build(ctx->cx, m->m, r->r, flags, h.r); });
@@ -804,6 +804,12 @@ int hry_bvh_cast(hry_ctx *ctx, const hry_bvh *b, uint64_t n_rays, const float *o
 {
 	if (!ctx || !b || (n_rays && (!origins || !dirs || !hit_tri))) return null_argument();
 	return guarded([&] { bvh_cast(ctx->cx, b->r, n_rays, origins, origin_stride, dirs, dir_stride, tmin, tmax, flags, hit_tri, hit_t, hit_uv, stat, device_ms); });
+}
+int hry_bvh_nearest(hry_ctx *ctx, const hry_bvh *b, uint64_t n_points, const float *points, uint64_t point_stride, double max_dist, uint32_t flags, uint32_t *near_tri,
+                    double *near_d2, float *near_uv, float *near_point, uint64_t stat[3], double *device_ms)
+{
+	if (!ctx || !b || (n_points && (!points || !near_tri))) return null_argument();
+	return guarded([&] { bvh_nearest(ctx->cx, b->r, n_points, points, point_stride, max_dist, flags, near_tri, near_d2, near_uv, near_point, stat, device_ms); });
 }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {

@@ -52,7 +52,13 @@
 // describes the mesh that is written, like --creases.  Nothing else about the output changes);
 // --bvh (with or without OUTPUT, after those lines: "Bvh: triangles T leaves L dead Z distinct-codes C depth D" -- hry_bvh_build over a
 // render build of the mesh, and hry_bvh_summary; it describes the mesh that is written, like --creases.  Nothing else about the
-// output changes).
+// output changes);
+// --deviation OTHER (with or without OUTPUT, after those lines; OTHER is a .ply, .obj or .hry: "Deviation: forward points N answered
+// A max M rms R" -- the position rows of a render build of the mesh that is written against the closest points of OTHER's triangles,
+// hry_bvh_build over a render build of OTHER and hry_bvh_nearest; M the largest distance, R the square root of the mean squared
+// distance over the A rows that were answered --, "Deviation: backward ..." -- OTHER's rows against the triangles of the mesh that is
+// written --, and "Deviation: hausdorff H diagonal D relative H/D": H the larger M, D the diagonal of the scene box of the mesh that
+// is written.  Nothing else about the output changes: harry in.ply out.hry -l1 -q10 && harry out.hry --deviation in.ply).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -88,7 +94,7 @@ struct QuantArg { int l, o, q; };
 struct ToleranceArg { int l, o, metric; double value; };
 struct BudgetArg { int l = -1, o = -1; long long bytes = -1; };   // bytes < 0: none
 struct Args {
-	std::string in, out, fmt, profile;   // profile empty: compat, unless --gpus / --shards ask for the sharded container
+	std::string in, out, fmt, profile, deviation;   // profile empty: compat, unless --gpus / --shards ask for the sharded container
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
@@ -115,7 +121,8 @@ const Opt kOpts[] = {
 	{ 0, "tangents", "Print how many vertices get a tangent frame from positions, uv and normals (OUTPUT may be left out)", false },
 	{ 0, "creases", "Print how many vertices and hard edges a crease angle of DEG degrees gives (OUTPUT may be left out)", true },
 	{ 0, "curvature", "Print the vertex classes, the surface area, the total angle defect and the integral of the mean curvature (OUTPUT may be left out)", false },
-	{ 0, "bvh", "Print the leaves, dead triangles, distinct codes and depth of a bounding-volume hierarchy over the triangles (OUTPUT may be left out)", false } };
+	{ 0, "bvh", "Print the leaves, dead triangles, distinct codes and depth of a bounding-volume hierarchy over the triangles (OUTPUT may be left out)", false },
+	{ 0, "deviation", "Print the surface deviation, one-sided both ways and symmetric, against the mesh in FILE (OUTPUT may be left out)", true } };
 
 void usage(const char *argv0)
 {
@@ -203,6 +210,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "tangents") a.tangents = true;
 		else if (n == "curvature") a.curvature = true;
 		else if (n == "bvh") a.bvh = true;
+		else if (n == "deviation") { if (val.empty()) arg_error(argv[0], "Invalid file name"); a.deviation = val; }
 		else if (n == "creases") {
 			a.crease_angle = to_double(argv[0], val);
 			if (std::isnan(a.crease_angle)) arg_error(argv[0], "Invalid angle");
@@ -249,7 +257,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature || a.bvh ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature || a.bvh || !a.deviation.empty() ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -332,7 +340,10 @@ struct Handles {   // released on every path
 	hry_tangents *tangents = nullptr;   // --tangents, over a render build of its own
 	hry_creases *creases = nullptr;   // --creases, over a render build and an edges build with geometry of its own
 	hry_curvature *curvature = nullptr;   // --curvature, over a render build and an edges build of its own
-	hry_bvh *bvh = nullptr;   // --bvh, over a render build of its own
+	hry_bvh *bvh = nullptr;   // --bvh, --deviation, over a render build of its own
+	hry_mesh *other = nullptr;   // --deviation: the mesh to compare with, its render build and the hierarchy over it
+	hry_render *other_render = nullptr;
+	hry_bvh *other_bvh = nullptr;
 	hry_sweep *sweep = nullptr;
 	hry_rate_sweep *rate = nullptr;
 	hry_mesh *trial = nullptr;   // --max-bytes: the clone one width is encoded from
@@ -355,10 +366,18 @@ struct Handles {   // released on every path
 		if (render) hry_render_free(render);
 		bvh = nullptr; curvature = nullptr; creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
 	}
+	void drop_other()
+	{
+		if (other_bvh) hry_bvh_free(other_bvh);
+		if (other_render) hry_render_free(other_render);
+		if (other) hry_mesh_free(other);
+		other_bvh = nullptr; other_render = nullptr; other = nullptr;
+	}
 	~Handles()
 	{
 		for (uint8_t *b : bufs) hry_free(b);
 		drop_adjacency();
+		drop_other();
 		if (dist) hry_distortion_free(dist);
 		if (sweep) hry_quant_sweep_free(sweep);
 		if (rate) hry_rate_sweep_free(rate);
@@ -436,6 +455,36 @@ void encode_within_budget(Handles &h, const BudgetArg &b, const hry_opts &o, uin
 	std::cout << "Budget: output " << coded[bits].second << " of " << N << " bytes after " << coded.size() << " encodes" << std::endl;
 	*out = coded[bits].first; *out_len = coded[bits].second;
 	hry_rate_sweep_free(h.rate); h.rate = nullptr;
+}
+
+// --deviation: one direction.  The position rows of r, a render build of m, against the triangles of `surface`
+struct Deviation { uint64_t points = 0, answered = 0; double max = 0.0, rms = 0.0; };
+Deviation deviation_of(hry_ctx *cx, const hry_mesh *m, const hry_render *r, const hry_bvh *surface)
+{
+	int pl = -1;
+	for (int l = 0; l < hry_mesh_nlists(m) && pl < 0; ++l)
+		if (hry_list_target(m, l) == 1 && hry_list_interp_ncomp(m, l, 0) >= 3) pl = l;
+	if (pl < 0) throw std::runtime_error("deviation: no vertex list with three position components");
+	const std::string name = "list" + std::to_string(pl);
+	uint64_t rows = 0;
+	int width = 0, type = 0;
+	ok(hry_render_get(r, name.c_str(), nullptr, &rows, &width, &type));
+	Deviation d;
+	d.points = rows;
+	if (!rows) return d;
+	std::vector<float> values((size_t)rows * (size_t)width);
+	ok(hry_render_copy(cx, r, name.c_str(), values.data(), 0));
+	std::vector<uint32_t> tri(rows);
+	std::vector<double> d2(rows);
+	uint64_t stat[3] = {};
+	ok(hry_bvh_nearest(cx, surface, rows, values.data() + hry_list_interp_offset(m, pl, 0), (uint64_t)width * 4, HUGE_VAL, HRY_NEAREST_HOST, tri.data(), d2.data(), nullptr,
+	                   nullptr, stat, nullptr));
+	double sum = 0.0, largest = 0.0;
+	for (uint64_t i = 0; i < rows; ++i) if (tri[i] != HRY_NO_ELEMENT) sum += d2[i];   // in index order
+	memcpy(&largest, &stat[2], 8);
+	d.answered = stat[0];
+	if (d.answered) { d.max = std::sqrt(largest); d.rms = std::sqrt(sum / (double)d.answered); }
+	return d;
 }
 
 int run(const Args &args)
@@ -686,7 +735,35 @@ int run(const Args &args)
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature || args.bvh) && args.out.empty()) {
+	if (!args.deviation.empty()) {
+		MappedFile of(args.deviation);
+		if (of.size() >= 4 && of[0] == 0xfa && of[1] == 0xff && of[2] == 0xaf && of[3] == 0xaf) ok(hry_decode(h.cx[0], of.data(), of.size(), nullptr, &h.other));
+		else if (of.size() >= 3 && of[0] == 'p' && of[1] == 'l' && of[2] == 'y') ok(hry_mesh_from_ply(of.data(), of.size(), &h.other));
+		else if (ext_of(args.deviation) == ".obj") ok(hry_mesh_from_obj(of.data(), of.size(), args.deviation.substr(0, args.deviation.find_last_of("/\\")).c_str(), &h.other));
+		else throw std::runtime_error("Not a mesh file");
+		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
+		ok(hry_bvh_build(h.cx[0], h.mesh, h.render, 0u, &h.bvh));
+		ok(hry_render_build(h.cx[0], h.other, &h.other_render));
+		ok(hry_bvh_build(h.cx[0], h.other, h.other_render, 0u, &h.other_bvh));
+		const Deviation side[2] = { deviation_of(h.cx[0], h.mesh, h.render, h.other_bvh), deviation_of(h.cx[0], h.other, h.other_render, h.bvh) };
+		for (int k = 0; k < 2; ++k) {
+			char line[256];
+			snprintf(line, sizeof line, "Deviation: %s points %llu answered %llu max %.9g rms %.9g", k ? "backward" : "forward", (unsigned long long)side[k].points,
+			         (unsigned long long)side[k].answered, side[k].max, side[k].rms);
+			std::cout << line << std::endl;
+		}
+		float box[6];
+		ok(hry_bvh_copy(h.cx[0], h.bvh, "scene_box", box, 0));
+		const double dx = (double)box[3] - (double)box[0], dy = (double)box[4] - (double)box[1], dz = (double)box[5] - (double)box[2];
+		const double hausdorff = std::max(side[0].max, side[1].max), diagonal = hry_bvh_count(h.bvh) ? std::sqrt((dx * dx + dy * dy) + dz * dz) : 0.0;
+		char line[256];
+		snprintf(line, sizeof line, "Deviation: hausdorff %.9g diagonal %.9g relative %.9g", hausdorff, diagonal, diagonal > 0.0 ? hausdorff / diagonal : 0.0);
+		std::cout << line << std::endl;
+		h.drop_other();
+		h.drop_adjacency();
+		t2 = Clock::now();   // (no part of the writing phase)
+	}
+	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature || args.bvh || !args.deviation.empty()) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

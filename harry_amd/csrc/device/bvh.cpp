@@ -1,11 +1,13 @@
-// The hierarchy over the triangles of a render build, built where the render build lies in HBM, and the ray cast over it
-// (include/harry_amd.h: hry_bvh_build, hry_bvh_cast; kernels: bvh.hip; DESIGN.md "Bvh").  The build uploads nothing: it reads the
-// render result's indices and the float rows of its position list; sixty-four bytes come down between its two stretches (the number
-// of leaves sizes the buffers, the depth counts the launches of the box fit).  The result keeps its own copy of the leaves'
-// positions, so the render build may be freed.  The decode's token and the encoder's resident mesh are left alone.
+// The hierarchy over the triangles of a render build, built where the render build lies in HBM, and the ray cast and the closest-
+// point query over it (include/harry_amd.h: hry_bvh_build, hry_bvh_cast, hry_bvh_nearest; kernels: bvh.hip; DESIGN.md "Bvh").  The
+// build uploads nothing: it reads the render result's indices and the float rows of its position list; sixty-four bytes come down
+// between its two stretches (the number of leaves sizes the buffers, the depth counts the launches of the box fit).  The result
+// keeps its own copy of the leaves' positions, so the render build may be freed.  The decode's token and the encoder's resident
+// mesh are left alone.  The two queries share their checks and the staging of host arrays (QueryArrays, check_query, run_query).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <vector>
 
 #include "result_build.hpp"
 
@@ -75,12 +77,73 @@ BvhView bvh_view_of(const BvhResult &b)
 namespace {
 
 // memory the caller calls host memory: anything the runtime does not know as device memory
-void check_host_memory(const void *p, const char *what)
+void check_host_memory(const void *p, const char *what, const char *call)
 {
 	hipPointerAttribute_t a{};
 	const hipError_t e = hipPointerGetAttributes(&a, p);
 	if (e != hipSuccess) { (void)hipGetLastError(); return; }
-	if (a.type == hipMemoryTypeDevice) throw Error(HRY_E_ARG, std::string(what) + ": device memory in a cast with HRY_CAST_HOST");
+	if (a.type == hipMemoryTypeDevice) throw Error(HRY_E_ARG, std::string(what) + ": device memory in " + call);
+}
+
+// The caller's arrays of one query against a hierarchy (a cast, a closest-point query): what both check of them and how both stage
+// them.  Without the host flag every array is memory of cx's device and the kernel reads and writes it where it lies; with it
+// every array is host memory and has a piece of cx.d_bvh, filled before the kernel (inputs) or copied back behind it (outputs).
+// An optional array the caller left out is null on both sides.
+struct QueryArrays {
+	struct Item { const void *user; uint64_t bytes, align; const char *name; bool output; uint8_t *staged; };
+	const char *what, *host_call;   // "cast", "a cast with HRY_CAST_HOST"
+	bool host;
+	std::vector<Item> items;   // complete before take(): the pieces are bound where the items lie
+	void add(const void *user, uint64_t bytes, const char *name, bool output, uint64_t align = 4) { items.push_back(Item{ user, bytes, align, name, output, nullptr }); }
+	// every pointer aligned, and what the flags say it is; selects cx's device
+	void check(Context &cx) const
+	{
+		for (const Item &i : items)
+			if ((uintptr_t)i.user % i.align) throw Error(HRY_E_ARG, std::string(what) + ": a misaligned pointer");
+		HIP_OK(hipSetDevice(cx.device));
+		for (const Item &i : items) {
+			if (!i.user) continue;
+			if (host) check_host_memory(i.user, i.name, host_call);
+			else check_device_memory(cx, i.user, i.bytes, i.name);
+		}
+	}
+	void take(Carve &W) { for (Item &i : items) W.take(i.staged, host && i.user ? i.bytes : 0); }
+	template <typename T> T *dev(size_t k) const { const Item &i = items[k]; return (T*)(!i.user ? nullptr : host ? i.staged : (uint8_t*)i.user); }
+	void upload(hipStream_t st) const
+	{
+		if (!host) return;
+		for (const Item &i : items) if (i.user && !i.output) HIP_OK(hipMemcpyAsync(i.staged, i.user, i.bytes, hipMemcpyHostToDevice, st));
+	}
+	void download(hipStream_t st) const
+	{
+		if (!host) return;
+		for (const Item &i : items) if (i.user && i.output) HIP_OK(hipMemcpyAsync((void*)i.user, i.staged, i.bytes, hipMemcpyDeviceToHost, st));
+	}
+};
+
+// the refusals a query makes before it looks at its arrays
+void check_query(const Context &cx, const BvhResult &b, uint32_t flags, uint32_t known, uint64_t stride_bits, const char *what)
+{
+	if (flags & ~known) throw Error(HRY_E_ARG, std::string("unknown ") + what + " flag");
+	if (stride_bits % 4) throw Error(HRY_E_ARG, std::string(what) + ": a stride is not a multiple of 4");
+	if (b.block.device != cx.device) throw Error(HRY_E_ARG, "the hierarchy lives on another device than the context's");
+}
+
+// the kernel between two marks, the counters down, the staged results back: returns the kernel's milliseconds
+template <typename Launch>
+double run_query(Context &cx, const QueryArrays &io, unsigned long long *d_stat, unsigned long long *counters, size_t words, Launch launch)
+{
+	hipStream_t st = cx.stream;
+	io.upload(st);
+	HIP_OK(hipMemsetAsync(d_stat, 0, words * 8, st));
+	StretchTimer timer;
+	timer.mark(st);
+	launch(st);
+	timer.mark(st);   // (one stretch)
+	HIP_OK(hipMemcpyAsync(counters, d_stat, words * 8, hipMemcpyDeviceToHost, st));
+	io.download(st);
+	HIP_OK(hipStreamSynchronize(st));
+	return timer.ms();
 }
 
 }   // namespace
@@ -88,62 +151,61 @@ void check_host_memory(const void *p, const char *what)
 void bvh_cast(Context &cx, const BvhResult &b, uint64_t n, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride, double tmin, double tmax,
               uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t *stat, double *device_ms)
 {
-	if (flags & ~(uint32_t)HRY_CAST_HOST) throw Error(HRY_E_ARG, "unknown cast flag");
-	if (origin_stride % 4 || dir_stride % 4) throw Error(HRY_E_ARG, "cast: a stride is not a multiple of 4");
+	check_query(cx, b, flags, HRY_CAST_HOST, origin_stride | dir_stride, "cast");
 	if (std::isnan(tmin) || std::isnan(tmax)) throw Error(HRY_E_ARG, "cast: tmin or tmax is NaN");
-	if (b.block.device != cx.device) throw Error(HRY_E_ARG, "the hierarchy lives on another device than the context's");
 	if (stat) stat[0] = stat[1] = 0;
 	if (device_ms) *device_ms = 0.0;
 	if (!n) return;
 	if (n > (1ull << 40) / std::max<uint64_t>(std::max(origin_stride, dir_stride), 12)) throw Error(HRY_E_UNSUPPORTED, "cast: more than 2^40 bytes of rays");
-	const bool host = (flags & HRY_CAST_HOST) != 0;
-	const uint64_t o_bytes = (n - 1) * origin_stride + 12, d_bytes = (n - 1) * dir_stride + 12;
-	if (((uintptr_t)origins | (uintptr_t)dirs | (uintptr_t)hit_tri | (uintptr_t)hit_t | (uintptr_t)hit_uv) % 4) throw Error(HRY_E_ARG, "cast: a misaligned pointer");
-	HIP_OK(hipSetDevice(cx.device));
-	if (host) {
-		check_host_memory(origins, "origins"); check_host_memory(dirs, "dirs"); check_host_memory(hit_tri, "hit_tri");
-		if (hit_t) check_host_memory(hit_t, "hit_t");
-		if (hit_uv) check_host_memory(hit_uv, "hit_uv");
-	} else {
-		check_device_memory(cx, origins, o_bytes, "origins"); check_device_memory(cx, dirs, d_bytes, "dirs"); check_device_memory(cx, hit_tri, n * 4, "hit_tri");
-		if (hit_t) check_device_memory(cx, hit_t, n * 4, "hit_t");
-		if (hit_uv) check_device_memory(cx, hit_uv, n * 8, "hit_uv");
-	}
+	QueryArrays io{ "cast", "a cast with HRY_CAST_HOST", (flags & HRY_CAST_HOST) != 0, {} };
+	io.add(origins, (n - 1) * origin_stride + 12, "origins", false); io.add(dirs, (n - 1) * dir_stride + 12, "dirs", false);
+	io.add(hit_tri, n * 4, "hit_tri", true); io.add(hit_t, n * 4, "hit_t", true); io.add(hit_uv, n * 8, "hit_uv", true);
+	io.check(cx);
 
 	// ---- the working buffer: the two counters; with HRY_CAST_HOST the staged rays and results behind them
 	Carve W;
 	BvhCast c{};
 	c.n = n; c.o_stride = origin_stride; c.d_stride = dir_stride; c.tmin = tmin; c.tmax = tmax;
-	uint8_t *s_o, *s_d;
-	uint32_t *s_tri;
-	float *s_t, *s_uv;
-	W.take(c.stat, 16); W.take(s_o, host ? o_bytes : 0); W.take(s_d, host ? d_bytes : 0); W.take(s_tri, host ? n * 4 : 0);
-	W.take(s_t, host && hit_t ? n * 4 : 0); W.take(s_uv, host && hit_uv ? n * 8 : 0);
+	W.take(c.stat, 16);
+	io.take(W);
 	cx.d_bvh.ensure(W.total);
 	W.bind(cx.d_bvh.p);
-	hipStream_t st = cx.stream;
-	if (host) {
-		c.o = s_o; c.d = s_d; c.hit_tri = s_tri; c.hit_t = hit_t ? s_t : nullptr; c.hit_uv = hit_uv ? s_uv : nullptr;
-		HIP_OK(hipMemcpyAsync((void*)c.o, origins, o_bytes, hipMemcpyHostToDevice, st));
-		HIP_OK(hipMemcpyAsync((void*)c.d, dirs, d_bytes, hipMemcpyHostToDevice, st));
-	} else {
-		c.o = (const uint8_t*)origins; c.d = (const uint8_t*)dirs; c.hit_tri = hit_tri; c.hit_t = hit_t; c.hit_uv = hit_uv;
-	}
-	HIP_OK(hipMemsetAsync(c.stat, 0, 16, st));
-	StretchTimer timer;
-	timer.mark(st);
-	launch_bvh_cast(st, bvh_view_of(b), c);
-	timer.mark(st);   // (one stretch)
+	c.o = io.dev<const uint8_t>(0); c.d = io.dev<const uint8_t>(1); c.hit_tri = io.dev<uint32_t>(2); c.hit_t = io.dev<float>(3); c.hit_uv = io.dev<float>(4);
 	unsigned long long counters[2] = {};
-	HIP_OK(hipMemcpyAsync(counters, c.stat, 16, hipMemcpyDeviceToHost, st));
-	if (host) {
-		HIP_OK(hipMemcpyAsync(hit_tri, c.hit_tri, n * 4, hipMemcpyDeviceToHost, st));
-		if (hit_t) HIP_OK(hipMemcpyAsync(hit_t, c.hit_t, n * 4, hipMemcpyDeviceToHost, st));
-		if (hit_uv) HIP_OK(hipMemcpyAsync(hit_uv, c.hit_uv, n * 8, hipMemcpyDeviceToHost, st));
-	}
-	HIP_OK(hipStreamSynchronize(st));
+	const double ms = run_query(cx, io, c.stat, counters, 2, [&](hipStream_t st) { launch_bvh_cast(st, bvh_view_of(b), c); });
 	if (stat) { stat[0] = counters[0]; stat[1] = counters[1]; }
-	if (device_ms) *device_ms = timer.ms();
+	if (device_ms) *device_ms = ms;
+}
+
+void bvh_nearest(Context &cx, const BvhResult &b, uint64_t n, const float *points, uint64_t point_stride, double max_dist, uint32_t flags, uint32_t *near_tri,
+                 double *near_d2, float *near_uv, float *near_point, uint64_t *stat, double *device_ms)
+{
+	check_query(cx, b, flags, HRY_NEAREST_HOST, point_stride, "nearest");
+	if (std::isnan(max_dist)) throw Error(HRY_E_ARG, "nearest: max_dist is NaN");
+	if (!n) {
+		if (stat) stat[0] = stat[1] = stat[2] = 0;
+		if (device_ms) *device_ms = 0.0;
+		return;
+	}
+	if (n > (1ull << 40) / std::max<uint64_t>(point_stride, 12)) throw Error(HRY_E_UNSUPPORTED, "nearest: more than 2^40 bytes of points");
+	QueryArrays io{ "nearest", "a closest-point query with HRY_NEAREST_HOST", (flags & HRY_NEAREST_HOST) != 0, {} };
+	io.add(points, (n - 1) * point_stride + 12, "points", false); io.add(near_tri, n * 4, "near_tri", true); io.add(near_d2, n * 8, "near_d2", true, 8);
+	io.add(near_uv, n * 8, "near_uv", true); io.add(near_point, n * 12, "near_point", true);
+	io.check(cx);
+
+	// ---- the working buffer: the three counters; with HRY_NEAREST_HOST the staged points and results behind them
+	Carve W;
+	BvhNearest c{};
+	c.n = n; c.q_stride = point_stride; c.r2 = max_dist * max_dist; c.any = max_dist < 0.0 ? 0u : 1u;
+	W.take(c.stat, 24);
+	io.take(W);
+	cx.d_bvh.ensure(W.total);
+	W.bind(cx.d_bvh.p);
+	c.q = io.dev<const uint8_t>(0); c.near_tri = io.dev<uint32_t>(1); c.near_d2 = io.dev<double>(2); c.near_uv = io.dev<float>(3); c.near_point = io.dev<float>(4);
+	unsigned long long counters[3] = {};
+	const double ms = run_query(cx, io, c.stat, counters, 3, [&](hipStream_t st) { launch_bvh_nearest(st, bvh_view_of(b), c); });
+	if (stat) { stat[0] = counters[0]; stat[1] = counters[1]; stat[2] = counters[2]; }
+	if (device_ms) *device_ms = ms;
 }
 
 }   // namespace hry

@@ -1,8 +1,8 @@
-// A linear bounding-volume hierarchy over the triangles of a render build and the closest-hit ray cast over it (driver: bvh.cpp;
-// contract: include/harry_amd.h, hry_bvh_build and hry_bvh_cast; DESIGN.md "Bvh").  Every floating-point operation is an
+// A linear bounding-volume hierarchy over the triangles of a render build, the closest-hit ray cast and the closest-point query over
+// it (driver: bvh.cpp; contract: include/harry_amd.h, hry_bvh_build, hry_bvh_cast and hry_bvh_nearest; DESIGN.md "Bvh").  Every floating-point operation is an
 // individually rounded IEEE double operation in the written order (the tree is built with -ffp-contract=off); the boxes are float
 // minima and maxima, which are exact in any order; there are no floating-point atomics.  The bits of every buffer depend on the
-// render build alone, those of a cast on the hierarchy and the rays alone.
+// render build alone, those of a cast or a closest-point query on the hierarchy and the rays or points alone.
 // The build, first stretch (grids sized by T; the number of leaves L is a device word until the stretch ends):
 //   k_bvh_init      the counters and the empty scene box
 //   k_bvh_live      a lane per triangle: live (nine finite floats) or dead; the scene box by a wavefront minimum / maximum of ordered
@@ -26,6 +26,12 @@
 //                   pushes at most the two children of a node, so it holds at most one entry per level and one more, and depth <= 62.
 //                   It lies in LDS interleaved by lane (a runtime-indexed private array would go to scratch): 64 entries * (a node
 //                   and the float below its near bound) * 64 lanes = 32 KiB a workgroup of one wavefront
+// The closest point:
+//   k_bvh_nearest   a point per lane, the same stack and the same argument for its size: a node and the float below the bound of its
+//                   box (rounded down it is still a lower bound, FLT_MAX where the double is beyond the floats).  Both children's
+//                   bounds at a node, leaves answered at once, the nearer internal child popped first; whatever has a bound
+//                   strictly greater than the best d2_t so far is skipped -- sound because d2_t is clamped from below by the bound
+//                   of the triangle's own leaf box, and a box that contains another has a bound no greater (DESIGN.md "Bvh")
 #include <hip/hip_runtime.h>
 
 #include "dev_types.hpp"
@@ -322,6 +328,123 @@ __global__ __launch_bounds__(kCastBlock) void k_bvh_cast(BvhView v, BvhCast c)
 	}
 }
 
+// ---- the closest point
+// the bound of a box for a point (the one rule, for leaf and node boxes alike): the squared distance to the box, monotone in lo
+// downwards and in hi upwards, rounding included
+__device__ __forceinline__ double gap(double lo, double hi, double q)
+{
+	const double a = lo - q, c = q - hi, g = a > c ? a : c;
+	return g > 0.0 ? g : 0.0;
+}
+__device__ __forceinline__ double bound_of(const float *box, const D3 &q)
+{
+	const double gx = gap((double)box[0], (double)box[3], q.x), gy = gap((double)box[1], (double)box[4], q.y), gz = gap((double)box[2], (double)box[5], q.z);
+	return (gx * gx + gy * gy) + gz * gz;
+}
+// where on the segment (a, a + d) the point with s = q - a lies nearest: 0 for a segment without length, clamped to [0, 1]
+__device__ __forceinline__ double along(const D3 &s, const D3 &d)
+{
+	const double l = dot_d(d, d);
+	if (l == 0.0) return 0.0;
+	const double x = dot_d(s, d) / l;
+	return x < 0.0 ? 0.0 : x > 1.0 ? 1.0 : x;
+}
+
+struct Near { double d2, u, v; D3 c; uint32_t tri; };
+
+// leaf `leaf`, the bound of whose own box is b2
+__device__ __forceinline__ void near_leaf(const BvhView &v, uint32_t leaf, const D3 &q, double b2, Near &best)
+{
+	const float *p = v.leaf_positions + 9 * (size_t)leaf;
+	const D3 p0{ (double)p[0], (double)p[1], (double)p[2] }, p1{ (double)p[3], (double)p[4], (double)p[5] }, p2{ (double)p[6], (double)p[7], (double)p[8] };
+	const D3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), s = sub3(q, p0);
+	double d2 = __builtin_inf(), bu = 0.0, bv = 0.0;
+	D3 bc{ 0.0, 0.0, 0.0 };
+	const auto candidate = [&](double u, double w) {
+		const D3 c{ p0.x + (u * e1.x + w * e2.x), p0.y + (u * e1.y + w * e2.y), p0.z + (u * e1.z + w * e2.z) };
+		const D3 r = sub3(q, c);
+		const double d = dot_d(r, r);
+		if (d < d2) { d2 = d; bu = u; bv = w; bc = c; }   // the first with the least: a later one only when strictly less
+	};
+	const D3 n = cross3(e1, e2);
+	const double nn = dot_d(n, n);
+	if (nn > 0.0) {
+		const double u = dot_d(cross3(s, e2), n) / nn, w = dot_d(cross3(e1, s), n) / nn;
+		if (u >= 0.0 && w >= 0.0 && u + w <= 1.0) candidate(u, w);
+	}
+	const double sb = along(s, e1), sc = along(sub3(q, p1), sub3(p2, p1)), sd = along(sub3(q, p2), sub3(p0, p2));
+	candidate(sb, 0.0);
+	candidate(1.0 - sc, sc);
+	candidate(0.0, 1.0 - sd);
+	if (b2 > d2) d2 = b2;   // rounding of c can put d2 an ulp below the box's bound: the skipping rests on d2_t >= that bound
+	const uint32_t t = v.leaf_tri[leaf];
+	if (d2 < best.d2 || (d2 == best.d2 && t < best.tri)) best = Near{ d2, bu, bv, bc, t };
+}
+
+__global__ __launch_bounds__(kCastBlock) void k_bvh_nearest(BvhView v, BvhNearest c)
+{
+	__shared__ uint32_t s_node[kCastStack * kCastBlock];
+	__shared__ float s_bound[kCastStack * kCastBlock];
+	const uint32_t lane = threadIdx.x;
+	unsigned long long answered = 0, tests = 0, farthest = 0;
+	for (uint64_t base = (uint64_t)blockIdx.x * kCastBlock; base < c.n; base += (uint64_t)gridDim.x * kCastBlock) {
+		const uint64_t i = base + lane;
+		const bool have = i < c.n;
+		Near best{ c.r2, 0.0, 0.0, D3{ 0.0, 0.0, 0.0 }, kNone };   // an answer exactly at r2 is accepted: its number is below kNone
+		uint32_t made = 0;
+		if (have) {
+			const float *pq = (const float*)(c.q + i * c.q_stride);
+			const D3 q{ (double)pq[0], (double)pq[1], (double)pq[2] };
+			const bool valid = c.any && finite_d(q.x) && finite_d(q.y) && finite_d(q.z);
+			if (valid && v.L == 1) {
+				++made;
+				const double b = bound_of(v.leaf_box, q);
+				if (!(b > best.d2)) near_leaf(v, 0, q, b, best);
+			} else if (valid && v.L > 1) {
+				uint32_t sp = 1;
+				s_node[lane] = 0; s_bound[lane] = 0.0f;
+				while (sp) {
+					--sp;
+					const uint32_t node = s_node[sp * kCastBlock + lane];
+					if ((double)s_bound[sp * kCastBlock + lane] > best.d2 || node + 1 >= v.L) continue;   // strict: an equal bound may hold a lower number
+					const uint32_t c0 = v.node_children[2 * (size_t)node], c1 = v.node_children[2 * (size_t)node + 1];
+					const uint32_t n0 = c0 & ~kLeafBit, n1 = c1 & ~kLeafBit;
+					if (n0 + (c0 & kLeafBit ? 0u : 1u) >= v.L || n1 + (c1 & kLeafBit ? 0u : 1u) >= v.L) continue;   // (no tree names such a child: a leaf below L, a node below L - 1)
+					const double b0 = bound_of((c0 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n0, q);
+					const double b1 = bound_of((c1 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n1, q);
+					made += 2;
+					bool go0 = !(c0 & kLeafBit), go1 = !(c1 & kLeafBit);
+					if (!go0 && !(b0 > best.d2)) near_leaf(v, n0, q, b0, best);
+					if (!go1 && !(b1 > best.d2)) near_leaf(v, n1, q, b1, best);
+					go0 = go0 && !(b0 > best.d2);
+					go1 = go1 && !(b1 > best.d2);
+					const bool first1 = go0 && go1 && b1 < b0;   // the nearer child is popped first: pushed last
+					const uint32_t na = first1 ? n1 : n0, nb = first1 ? n0 : n1;
+					const double ra = first1 ? b1 : b0, rb = first1 ? b0 : b1;
+					const bool ga = first1 ? go1 : go0, gb = first1 ? go0 : go1;
+					if (gb && sp < kCastStack) { s_node[sp * kCastBlock + lane] = nb; s_bound[sp * kCastBlock + lane] = __double2float_rd(rb); ++sp; }
+					if (ga && sp < kCastStack) { s_node[sp * kCastBlock + lane] = na; s_bound[sp * kCastBlock + lane] = __double2float_rd(ra); ++sp; }
+				}
+			}
+			const bool hit = best.tri != kNone;
+			c.near_tri[i] = best.tri;
+			if (c.near_d2) c.near_d2[i] = hit ? best.d2 : __builtin_inf();
+			if (c.near_uv) { c.near_uv[2 * i] = hit ? (float)best.u : 0.0f; c.near_uv[2 * i + 1] = hit ? (float)best.v : 0.0f; }
+			if (c.near_point) { c.near_point[3 * i] = hit ? (float)best.c.x : 0.0f; c.near_point[3 * i + 1] = hit ? (float)best.c.y : 0.0f; c.near_point[3 * i + 2] = hit ? (float)best.c.z : 0.0f; }
+		}
+		const bool hit = have && best.tri != kNone;
+		answered += (unsigned long long)__popcll(__ballot(hit));
+		tests += wave_sum((unsigned long long)made);
+		// non-negative doubles order as their words: an integer maximum, whatever the order
+		farthest = max(farthest, wave_max(hit ? (unsigned long long)__double_as_longlong(best.d2) : 0ull));
+	}
+	if (lane == 0 && c.stat) {
+		if (answered) atomicAdd(&c.stat[0], answered);
+		if (tests) atomicAdd(&c.stat[1], tests);
+		if (farthest) atomicMax(&c.stat[2], farthest);
+	}
+}
+
 }   // namespace
 
 // ---- launchers (kernels.hpp)
@@ -352,6 +475,12 @@ void launch_bvh_cast(hipStream_t st, const BvhView &v, const BvhCast &c)
 {
 	if (!c.n) return;
 	hipLaunchKernelGGL(k_bvh_cast, dim3(grid_for(c.n, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
+}
+
+void launch_bvh_nearest(hipStream_t st, const BvhView &v, const BvhNearest &c)
+{
+	if (!c.n) return;
+	hipLaunchKernelGGL(k_bvh_nearest, dim3(grid_for(c.n, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
 }
 
 }   // namespace dev

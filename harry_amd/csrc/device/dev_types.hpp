@@ -231,6 +231,19 @@ struct BvhCast {
 	float *hit_t, *hit_uv;
 	unsigned long long *stat;
 };
+// one closest-point query: n points, point i at byte i * q_stride of q (stride 0: one for all); r2: the squared radius; any: 0 where
+// the radius is negative and no point is answered; dense outputs, all but near_tri may be null; stat: three zeroed 64-bit words
+// (points answered, bounds evaluated, the bits of the largest near_d2)
+struct BvhNearest {
+	uint64_t n, q_stride;
+	const uint8_t *q;
+	double r2;
+	uint32_t any;
+	uint32_t *near_tri;
+	double *near_d2;
+	float *near_uv, *near_point;
+	unsigned long long *stat;
+};
 
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh

@@ -244,11 +244,13 @@ const double *launch_curvature(hipStream_t st, const CurvView &v, const CurvWork
 // tree and its depth, everything in BvhWork (dev_types.hpp); w.words[0 .. 2] = L, distinct codes, depth afterwards.
 // launch_bvh_second (L and the depth known, the buffers of v allocated): every buffer of v, the node boxes in `depth` launches.
 // launch_bvh_cast: c.n rays against v; bvh_cast_block: the rays of one workgroup; bvh_radix_words: the words of w.radix for T triangles
+// launch_bvh_nearest: the closest point of v's triangles to each of c.n points, in workgroups of the cast's size
 size_t bvh_radix_words(uint32_t T);
 void launch_bvh_first(hipStream_t st, const BvhWork &w);
 void launch_bvh_second(hipStream_t st, const BvhWork &w, const BvhView &v, uint32_t depth);
 void launch_bvh_cast(hipStream_t st, const BvhView &v, const BvhCast &c);
 uint32_t bvh_cast_block();
+void launch_bvh_nearest(hipStream_t st, const BvhView &v, const BvhNearest &c);
 
 // shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the

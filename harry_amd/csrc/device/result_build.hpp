@@ -69,13 +69,15 @@ struct CurvatureResult : TopologyResult {
 	double totals[3] = {};
 };
 void curvature_build(Context &cx, const Mesh &m, const RenderResult &r, const EdgesResult &e, uint32_t flags, CurvatureResult &out);   // flags: none
-// bvh.cpp: the hierarchy over the triangles of a render build and the cast over it (include/harry_amd.h: hry_bvh_build,
-// hry_bvh_cast).  summary: T, L, T - L, distinct codes, depth, 0.  The result reads nothing of the render build afterwards
+// bvh.cpp: the hierarchy over the triangles of a render build, the cast and the closest-point query over it (include/harry_amd.h:
+// hry_bvh_build, hry_bvh_cast, hry_bvh_nearest).  summary: T, L, T - L, distinct codes, depth, 0.  The result reads nothing of the render build afterwards
 typedef TopologyResult BvhResult;
 void bvh_build(Context &cx, const Mesh &m, const RenderResult &r, uint32_t flags, BvhResult &out);   // flags: none
 dev::BvhView bvh_view_of(const BvhResult &b);   // its seven buffers, as the kernels take them
 void bvh_cast(Context &cx, const BvhResult &b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride, double tmin,
               double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t *stat, double *device_ms);   // flags: HRY_CAST_*
+void bvh_nearest(Context &cx, const BvhResult &b, uint64_t n_points, const float *points, uint64_t point_stride, double max_dist, uint32_t flags, uint32_t *near_tri,
+                 double *near_d2, float *near_uv, float *near_point, uint64_t *stat, double *device_ms);   // flags: HRY_NEAREST_*
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise

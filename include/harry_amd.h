@@ -21,6 +21,7 @@
  *   hry_creases_build   (no counterpart: hard edges at a crease limit, vertices split along them and a normal per split vertex, as device buffers)
  *   hry_curvature_build (no counterpart: mixed Voronoi area, angle defect, Gaussian and mean curvature per vertex of a render build, as device buffers)
  *   hry_bvh_build, hry_bvh_cast (no counterpart: a bounding-volume hierarchy over the triangles of a render build and closest-hit ray queries against it, on the device)
+ *   hry_bvh_nearest     (no counterpart: the closest point of that hierarchy's triangles to every query point, the query behind a mesh-to-mesh deviation)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -717,6 +718,51 @@ int hry_bvh_stat(const hry_bvh *b, double *device_ms, uint64_t *uploaded_bytes);
 void hry_bvh_free(hry_bvh *b);
 int hry_bvh_cast(hry_ctx *ctx, const hry_bvh *b, uint64_t n_rays, const float *origins, uint64_t origin_stride, const float *dirs, uint64_t dir_stride,
                  double tmin, double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t stat[2], double *device_ms);
+
+/* hry_bvh_nearest answers, for every query point, which triangle of the hierarchy lies closest within max_dist, how far and where
+ * on it.  Point i reads three floats at points + i * point_stride bytes; the stride is a multiple of 4, and 0 means one point for
+ * all.  The outputs are dense: near_tri [n_points], near_d2 [n_points] doubles, near_uv [n_points, 2], near_point [n_points, 3];
+ * near_d2, near_uv, near_point, stat and device_ms may be NULL.  The contract defines the result, not the way to it: every bit
+ * depends on the hierarchy and the points alone, and a program that tests every point against every leaf by the rules below gets
+ * the same bits.  All arithmetic is in double on the widened floats, every operation individually rounded in the written order;
+ * a . b and a x b as in the cast's contract.  Q: the point.
+ * Valid point: Q has three finite floats.  Any other point is unanswered.
+ * Radius: r2 = max_dist * max_dist.  A negative max_dist is no error: every point is unanswered.  +inf is allowed; NaN is refused.
+ * Bound of a box [lo, hi] -- the one rule, for leaf and node boxes alike: g_k = max(max(lo_k - Q_k, Q_k - hi_k), 0), b2 =
+ *   (g_x g_x + g_y g_y) + g_z g_z.  Every step is monotone in lo downwards and in hi upwards, rounding included, so a box that
+ *   contains another has a bound no greater, exactly.
+ * Segment (A, B): d = B - A, l = d . d, s = 0 where l == 0, otherwise ((Q - A) . d) / l clamped to [0, 1] (a value below 0 becomes
+ *   0, one above 1 becomes 1, any other stays).
+ * Candidates of leaf triangle t, with e1 = P1 - P0, e2 = P2 - P0 and s = Q - P0, in this order:
+ *   (a) the face: n = e1 x e2, nn = n . n; where nn > 0, u = ((s x e2) . n) / nn and v = ((e1 x s) . n) / nn, and the face is a
+ *       candidate when u >= 0, v >= 0 and u + v <= 1;
+ *   (b) segment (P0, P1) with (u, v) = (s, 0);  (c) segment (P1, P2) with (u, v) = (1 - s, s);  (d) segment (P2, P0) with (u, v) =
+ *       (0, 1 - s).
+ *   For each candidate C = P0 + (u e1 + v e2), per component, and d2 = (Q - C) . (Q - C).  The triangle takes the first candidate
+ *   with the least d2: a later candidate replaces an earlier one only when strictly less.  A NaN fails every comparison.  A
+ *   triangle without area answers as the segment or the point it is.
+ * The triangle's distance: d2_t = max(that d2, the bound of t's own leaf box).  Mathematically the bound never exceeds the
+ *   distance; the rounding of C can break that by an ulp, and with the clamp d2_t >= bound(leaf box) >= bound(every box above it)
+ *   holds exactly: a subtree whose bound is strictly greater than the best d2_t so far holds nothing better (an equal bound may
+ *   hold a lower triangle number; DESIGN.md "Bvh").
+ * Answer: among the triangles with d2_t <= r2 the one with the least d2_t, ties to the least triangle number: near_tri = t,
+ *   near_d2 = d2_t (the squared distance, as a double: the quantity compared; no square root enters the bit contract), near_uv =
+ *   ((float)u, (float)v), near_point = (float) of C's components.  An unanswered point gives HRY_NO_ELEMENT, +inf, (0, 0) and
+ *   (0, 0, 0).
+ * stat = { points answered, box bounds evaluated, the bits of the largest near_d2 among the answered points (0 where none was) }.
+ *   The third is an integer maximum of the doubles' words -- non-negative doubles order as their words, so the order decides
+ *   nothing; there are no floating-point atomics.  The second depends on the walk and is no part of the bit contract.
+ *   device_ms: the kernel.
+ * Pointers, staging and refusals as for hry_bvh_cast: without flags points and the four outputs are memory of ctx's device, with
+ *   HRY_NEAREST_HOST host memory staged by the library; near_d2 must be 8-byte aligned, the others 4-byte.  n_points = 0 succeeds
+ *   and touches nothing.  Refusals (HRY_E_ARG): a null ctx or b; null near_tri or points with n_points > 0; unknown flags; a stride
+ *   that is not a multiple of 4; NaN max_dist; a pointer that is not what the flags say, is misaligned, or whose rows extend past
+ *   its allocation; a b on another device than ctx's.  A refusal writes nothing and leaves ctx usable. */
+#define HRY_NEAREST_HOST 1u   /* points, near_tri, near_d2, near_uv and near_point are host memory */
+int hry_bvh_nearest(hry_ctx *ctx, const hry_bvh *b, uint64_t n_points, const float *points, uint64_t point_stride,
+                    double max_dist, uint32_t flags,
+                    uint32_t *near_tri, double *near_d2, float *near_uv, float *near_point,
+                    uint64_t stat[3], double *device_ms);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
