@@ -196,11 +196,13 @@ def load():
     L.hry_render_copy.restype = C.c_int; L.hry_render_copy.argtypes = [vp, vp, C.c_char_p, vp, C.c_int]
     L.hry_render_stat.restype = C.c_int; L.hry_render_stat.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.hry_render_free.argtypes = [vp]
-    for fam, inputs in (("edges", [vp]), ("shells", [vp, vp]), ("orient", [vp, vp]), ("tangents", [vp]),
-                        ("creases", [vp, vp, C.c_double]), ("curvature", [vp, vp]), ("bvh", [vp])):   # the builds behind a render build: its handle(s) in (creases: and the limit)
+    # the builds behind a render build.  inputs: what lies between the context and the flags -- the mesh and the handle(s) of the
+    # builds before it (creases: and the limit); intersections: the hierarchy alone
+    for fam, inputs in (("edges", [vp, vp]), ("shells", [vp, vp, vp]), ("orient", [vp, vp, vp]), ("tangents", [vp, vp]),
+                        ("creases", [vp, vp, vp, C.c_double]), ("curvature", [vp, vp, vp]), ("bvh", [vp, vp]), ("intersections", [vp])):
         def fn(what, restype, argtypes):
             f = getattr(L, f"hry_{fam}_{what}"); f.restype = restype; f.argtypes = argtypes
-        fn("build", C.c_int, [vp, vp] + inputs + [C.c_uint32, C.POINTER(vp)])
+        fn("build", C.c_int, [vp] + inputs + [C.c_uint32, C.POINTER(vp)])
         fn("count", C.c_uint64, [vp])
         fn("get", C.c_int, [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)])
         fn("copy", C.c_int, [vp, vp, C.c_char_p, vp, C.c_int])

@@ -794,6 +794,16 @@ class Codec:
         deepest leaf, at most 62)"""
         return dict(getattr(self, "_bvh_stat", {}))
 
+    # ---- self-intersections (include/harry_amd.h: hry_intersections_build)
+    def intersections(self, mesh: Mesh) -> "Intersections":
+        """the pairs of the mesh's triangles that pass through each other (Bvh.intersections): the render build and the hierarchy
+        over it are built and freed here, the result stays until close()"""
+        b = self.bvh(mesh)
+        try:
+            return b.intersections()
+        finally:
+            b.close()
+
     # ---- mesh-to-mesh deviation (include/harry_amd.h: hry_bvh_nearest)
     def position_rows(self, mesh: Mesh) -> np.ndarray:
         """the float rows [U, 3] of the positions of the mesh's render build (dequantised, one row per output vertex): a view into
@@ -1316,6 +1326,47 @@ class Bvh(_NamedBuffers):
         tri, d2, uv, point = np.empty(n, np.uint32), np.empty(n, np.float64), np.empty((n, 2), np.float32), np.empty((n, 3), np.float32)
         self._nearest(n, points.ctypes.data, stride, max_dist, nat.NEAREST_HOST, tri.ctypes.data, d2.ctypes.data, uv.ctypes.data, point.ctypes.data)
         return {"tri": tri, "d2": d2, "uv": uv, "point": point}
+
+    def intersections(self) -> "Intersections":
+        """the pairs of triangles that pass through each other (hry_intersections_build): an owning object of its own, which needs
+        neither this hierarchy nor the mesh afterwards"""
+        h = C.c_void_p()
+        nat.check(nat.load().hry_intersections_build(self.codec.h, self.h, 0, C.byref(h)))   # (one build over the hierarchy alone: no chain)
+        return Intersections(self.codec, h)
+
+
+class Intersections(_NamedBuffers):
+    """The pairs of triangles of a hierarchy of which an edge of one meets the other (include/harry_amd.h:
+    hry_intersections_build): "pairs" [P, 2] (t < s, ascending), "pair_shared" [P] (the corners they share by position: 0 or 1) and
+    "tri_pairs" [T] (the pairs every triangle is in).  The buffers lie in HBM; every bit of them depends on the hierarchy alone.
+    candidates: the pairs of leaves whose boxes overlap; tested: those of them that reach the segment tests; pairs: P;
+    triangles_hit: the triangles in a pair; box_tests: what the walk evaluated (the one figure that depends on the walk);
+    device_ms: the kernels"""
+
+    BUFFERS = ("pairs", "pair_shared", "tri_pairs")
+    SUMMARY = ("triangles", "candidates", "tested", "pairs", "triangles_hit", "box_tests")
+    _PREFIX, _TYPED = "intersections", True
+
+    def __init__(self, codec: "Codec", handle):
+        self.codec, self.h = codec, handle
+        st = self.stat()
+        self.triangles, self.candidates, self.tested, self.pairs, self.triangles_hit, self.box_tests = (st[k] for k in self.SUMMARY)
+        self.device_ms = st["device_ms"]
+
+    def count(self) -> int:
+        """P: the pairs"""
+        return int(nat.load().hry_intersections_count(self.h))
+
+    def stat(self) -> dict:
+        return _read_stat(nat.load(), "intersections", self.h, self.SUMMARY)
+
+    def buffers_numpy(self) -> dict:
+        """the three buffers as host arrays: pairs u32 [P, 2], pair_shared u32 [P], tri_pairs u32 [T]"""
+        return _read_buffers(nat.load(), "intersections", self.h, self.BUFFERS, self.codec._fill_numpy)
+
+    def buffers(self) -> dict:
+        """the same as int32 torch tensors on the codec's device, copied device to device"""
+        return _read_buffers(nat.load(), "intersections", self.h, self.BUFFERS, self.codec._torch_fill())
 
 
 class Distortion(_NamedBuffers):

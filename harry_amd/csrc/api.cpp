@@ -25,6 +25,7 @@ struct hry_tangents : ResultHandle<TangentsResult> {};
 struct hry_creases : ResultHandle<CreasesResult> {};
 struct hry_curvature : ResultHandle<CurvatureResult> {};
 struct hry_bvh : ResultHandle<BvhResult> {};
+struct hry_intersections : ResultHandle<IntersectionsResult> {};
 struct hry_distortion : ResultHandle<DistortionResult> {};
 struct hry_order : ResultHandle<std::unique_ptr<OrderResult>> {};   // (taken from the context whole: hry_order_take)
 struct hry_sweep { SweepResult s; };
@@ -734,7 +735,7 @@ int hry_render_copy(hry_ctx *ctx, const hry_render *r, const char *name, void *d
 int hry_render_stat(const hry_render *r, double *device_ms, uint64_t *uploaded_bytes) { return handle_stat(result_of(r), device_ms, uploaded_bytes); }
 void hry_render_free(hry_render *r) { delete r; }
 
-// ---- the seven families behind a render build.  Their get, copy, summary, stat and free are one line each: the family, what its
+// ---- the eight families behind a render build.  Their get, copy, summary, stat and free are one line each: the family, what its
 // refusals call a buffer, the words of its summary.  What differs between them follows: build, count, and what only one has
 #define HRY_RESULT_FAMILY(fam, noun, nsummary) \
 	int hry_##fam##_get(const hry_##fam *h, const char *name, const void **dev, uint64_t *rows, int *width, int *type) { return handle_get(result_of(h), name, dev, rows, width, type, false); } \
@@ -749,6 +750,7 @@ HRY_RESULT_FAMILY(tangents, "tangent buffer", 6)
 HRY_RESULT_FAMILY(creases, "crease buffer", 6)
 HRY_RESULT_FAMILY(curvature, "curvature buffer", 6)
 HRY_RESULT_FAMILY(bvh, "bvh buffer", 6)
+HRY_RESULT_FAMILY(intersections, "intersection buffer", 6)
 #undef HRY_RESULT_FAMILY
 
 // unique edges and adjacency of a render build (edges.cpp)
@@ -811,6 +813,12 @@ int hry_bvh_nearest(hry_ctx *ctx, const hry_bvh *b, uint64_t n_points, const flo
 	if (!ctx || !b || (n_points && (!points || !near_tri))) return null_argument();
 	return guarded([&] { bvh_nearest(ctx->cx, b->r, n_points, points, point_stride, max_dist, flags, near_tri, near_d2, near_uv, near_point, stat, device_ms); });
 }
+// ... and the pairs of its triangles that pass through each other: a build that reads the hierarchy alone
+int hry_intersections_build(hry_ctx *ctx, const hry_bvh *b, uint32_t flags, hry_intersections **out)
+{
+	return handle_build(ctx, b != nullptr, out, [&](hry_intersections &h) { intersections_build(ctx->cx, b->r, flags, h.r); });
+}
+uint64_t hry_intersections_count(const hry_intersections *i) { return i ? i->r.summary[3] : 0; }
 int hry_mesh_flip_faces(const hry_mesh *m, const uint32_t *face_flip, hry_mesh **out)
 {
 	if (out) *out = nullptr;

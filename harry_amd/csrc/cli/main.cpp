@@ -58,7 +58,11 @@
 // hry_bvh_build over a render build of OTHER and hry_bvh_nearest; M the largest distance, R the square root of the mean squared
 // distance over the A rows that were answered --, "Deviation: backward ..." -- OTHER's rows against the triangles of the mesh that is
 // written --, and "Deviation: hausdorff H diagonal D relative H/D": H the larger M, D the diagonal of the scene box of the mesh that
-// is written.  Nothing else about the output changes: harry in.ply out.hry -l1 -q10 && harry out.hry --deviation in.ply).
+// is written.  Nothing else about the output changes: harry in.ply out.hry -l1 -q10 && harry out.hry --deviation in.ply);
+// --intersections (with or without OUTPUT, after those lines: "Intersections: triangles T candidates C tested N pairs P triangles-hit H"
+// -- hry_bvh_build over a render build of the mesh, hry_intersections_build and hry_intersections_summary; it describes the mesh that
+// is written, like --bvh.  Nothing else about the output changes: harry in.ply out.hry -l1 -q10 && harry out.hry --intersections
+// against harry in.ply --intersections tells what the quantisation folded).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -98,7 +102,7 @@ struct Args {
 	std::vector<QuantArg> quant;
 	std::vector<ToleranceArg> tolerance;
 	BudgetArg budget;
-	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false, creases = false, curvature = false, bvh = false;
+	bool clearquant = false, ply_ascii = false, ply_packed = false, report = false, topology = false, shells = false, orient = false, orient_outward = false, tangents = false, creases = false, curvature = false, bvh = false, intersections = false;
 	double crease_angle = 0.0;
 	std::string crease_text;   // DEG as it was given
 	int chunk = 0, device = 0, shards = 0, gpus = 0;
@@ -122,7 +126,8 @@ const Opt kOpts[] = {
 	{ 0, "creases", "Print how many vertices and hard edges a crease angle of DEG degrees gives (OUTPUT may be left out)", true },
 	{ 0, "curvature", "Print the vertex classes, the surface area, the total angle defect and the integral of the mean curvature (OUTPUT may be left out)", false },
 	{ 0, "bvh", "Print the leaves, dead triangles, distinct codes and depth of a bounding-volume hierarchy over the triangles (OUTPUT may be left out)", false },
-	{ 0, "deviation", "Print the surface deviation, one-sided both ways and symmetric, against the mesh in FILE (OUTPUT may be left out)", true } };
+	{ 0, "deviation", "Print the surface deviation, one-sided both ways and symmetric, against the mesh in FILE (OUTPUT may be left out)", true },
+	{ 0, "intersections", "Print the triangle pairs that pass through each other: an edge of one meets the other (OUTPUT may be left out)", false } };
 
 void usage(const char *argv0)
 {
@@ -131,7 +136,7 @@ void usage(const char *argv0)
 		std::cout << "  ";
 		if (o.s) std::cout << '-' << o.s << ", "; else std::cout << "    ";
 		char buf[64];
-		snprintf(buf, sizeof buf, "--%-13s", o.l);
+		snprintf(buf, sizeof buf, "--%-13s%s", o.l, strlen(o.l) >= 13 ? " " : "");   // (a name that fills the column keeps a space behind it)
 		std::cout << buf << o.descr << std::endl;
 	}
 }
@@ -210,6 +215,7 @@ Args parse(int argc, const char **argv)
 		else if (n == "tangents") a.tangents = true;
 		else if (n == "curvature") a.curvature = true;
 		else if (n == "bvh") a.bvh = true;
+		else if (n == "intersections") a.intersections = true;
 		else if (n == "deviation") { if (val.empty()) arg_error(argv[0], "Invalid file name"); a.deviation = val; }
 		else if (n == "creases") {
 			a.crease_angle = to_double(argv[0], val);
@@ -257,7 +263,7 @@ Args parse(int argc, const char **argv)
 	if (a.gpus < 0 || a.shards < 0 || a.gpus > 64) arg_error(argv[0], "Invalid number of contexts / shards");
 	if ((a.gpus > 1 || a.shards > 1) && a.profile == "compat") arg_error(argv[0], "--gpus / --shards need --profile chunked: the reference's single stream does not shard");
 	if (a.profile.empty()) a.profile = a.gpus > 1 || a.shards > 1 ? "chunked" : "compat";
-	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature || a.bvh || !a.deviation.empty() ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
+	if (pos.size() < (a.topology || a.shells || a.orient || a.tangents || a.creases || a.curvature || a.bvh || !a.deviation.empty() || a.intersections ? 1u : 2u)) arg_error(argv[0], "Too few non-optional arguments");
 	if (pos.size() > 2) arg_error(argv[0], "Too much non-optional arguments");
 	a.in = pos[0];
 	if (pos.size() > 1) a.out = pos[1];
@@ -340,7 +346,8 @@ struct Handles {   // released on every path
 	hry_tangents *tangents = nullptr;   // --tangents, over a render build of its own
 	hry_creases *creases = nullptr;   // --creases, over a render build and an edges build with geometry of its own
 	hry_curvature *curvature = nullptr;   // --curvature, over a render build and an edges build of its own
-	hry_bvh *bvh = nullptr;   // --bvh, --deviation, over a render build of its own
+	hry_bvh *bvh = nullptr;   // --bvh, --deviation, --intersections, over a render build of its own
+	hry_intersections *intersections = nullptr;   // --intersections, over that hierarchy
 	hry_mesh *other = nullptr;   // --deviation: the mesh to compare with, its render build and the hierarchy over it
 	hry_render *other_render = nullptr;
 	hry_bvh *other_bvh = nullptr;
@@ -356,6 +363,7 @@ struct Handles {   // released on every path
 	}
 	void drop_adjacency()
 	{
+		if (intersections) hry_intersections_free(intersections);
 		if (bvh) hry_bvh_free(bvh);
 		if (curvature) hry_curvature_free(curvature);
 		if (creases) hry_creases_free(creases);
@@ -364,7 +372,7 @@ struct Handles {   // released on every path
 		if (shells) hry_shells_free(shells);
 		if (edges) hry_edges_free(edges);
 		if (render) hry_render_free(render);
-		bvh = nullptr; curvature = nullptr; creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
+		intersections = nullptr; bvh = nullptr; curvature = nullptr; creases = nullptr; tangents = nullptr; orient = nullptr; shells = nullptr; edges = nullptr; render = nullptr;
 	}
 	void drop_other()
 	{
@@ -726,14 +734,18 @@ int run(const Args &args)
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if (args.bvh) {
+	// --bvh, --deviation and --intersections read one hierarchy over one render build of the mesh: built by the first of them
+	// that runs, dropped behind the last
+	const auto hierarchy = [&] {
+		if (h.bvh) return;
 		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
 		ok(hry_bvh_build(h.cx[0], h.mesh, h.render, 0u, &h.bvh));
+	};
+	if (args.bvh) {
+		hierarchy();
 		uint64_t s[6];
 		ok(hry_bvh_summary(h.bvh, s));
 		std::cout << "Bvh: triangles " << s[0] << " leaves " << s[1] << " dead " << s[2] << " distinct-codes " << s[3] << " depth " << s[4] << std::endl;
-		h.drop_adjacency();
-		t2 = Clock::now();   // (no part of the writing phase)
 	}
 	if (!args.deviation.empty()) {
 		MappedFile of(args.deviation);
@@ -741,8 +753,7 @@ int run(const Args &args)
 		else if (of.size() >= 3 && of[0] == 'p' && of[1] == 'l' && of[2] == 'y') ok(hry_mesh_from_ply(of.data(), of.size(), &h.other));
 		else if (ext_of(args.deviation) == ".obj") ok(hry_mesh_from_obj(of.data(), of.size(), args.deviation.substr(0, args.deviation.find_last_of("/\\")).c_str(), &h.other));
 		else throw std::runtime_error("Not a mesh file");
-		ok(hry_render_build(h.cx[0], h.mesh, &h.render));
-		ok(hry_bvh_build(h.cx[0], h.mesh, h.render, 0u, &h.bvh));
+		hierarchy();
 		ok(hry_render_build(h.cx[0], h.other, &h.other_render));
 		ok(hry_bvh_build(h.cx[0], h.other, h.other_render, 0u, &h.other_bvh));
 		const Deviation side[2] = { deviation_of(h.cx[0], h.mesh, h.render, h.other_bvh), deviation_of(h.cx[0], h.other, h.other_render, h.bvh) };
@@ -760,10 +771,19 @@ int run(const Args &args)
 		snprintf(line, sizeof line, "Deviation: hausdorff %.9g diagonal %.9g relative %.9g", hausdorff, diagonal, diagonal > 0.0 ? hausdorff / diagonal : 0.0);
 		std::cout << line << std::endl;
 		h.drop_other();
+	}
+	if (args.intersections) {
+		hierarchy();
+		ok(hry_intersections_build(h.cx[0], h.bvh, 0u, &h.intersections));
+		uint64_t s[6];
+		ok(hry_intersections_summary(h.intersections, s));
+		std::cout << "Intersections: triangles " << s[0] << " candidates " << s[1] << " tested " << s[2] << " pairs " << s[3] << " triangles-hit " << s[4] << std::endl;
+	}
+	if (h.bvh) {
 		h.drop_adjacency();
 		t2 = Clock::now();   // (no part of the writing phase)
 	}
-	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature || args.bvh || !args.deviation.empty()) && args.out.empty()) {
+	if ((args.topology || args.shells || args.orient || args.tangents || args.creases || args.curvature || args.bvh || !args.deviation.empty() || args.intersections) && args.out.empty()) {
 		if (!env_on("HRY_ORDERLY_EXIT")) { std::cout.flush(); std::cerr.flush(); fflush(nullptr); _exit(EXIT_SUCCESS); }
 		return EXIT_SUCCESS;
 	}

@@ -4,6 +4,7 @@
 // between its two stretches (the number of leaves sizes the buffers, the depth counts the launches of the box fit).  The result
 // keeps its own copy of the leaves' positions, so the render build may be freed.  The decode's token and the encoder's resident
 // mesh are left alone.  The two queries share their checks and the staging of host arrays (QueryArrays, check_query, run_query).
+// The pairs of triangles that pass through each other (hry_intersections_build) are a build of their own over the hierarchy alone.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -206,6 +207,71 @@ void bvh_nearest(Context &cx, const BvhResult &b, uint64_t n, const float *point
 	const double ms = run_query(cx, io, c.stat, counters, 3, [&](hipStream_t st) { launch_bvh_nearest(st, bvh_view_of(b), c); });
 	if (stat) { stat[0] = counters[0]; stat[1] = counters[1]; stat[2] = counters[2]; }
 	if (device_ms) *device_ms = ms;
+}
+
+// The third query has a result of a size nobody knows beforehand, so it is a build in two stretches: the walk counts, sixty-four
+// bytes come down (C, N, the box tests and P; the scan's P and H behind them), the outputs are allocated, the same walk fills.  It
+// reads the hierarchy alone
+void intersections_build(Context &cx, const BvhResult &b, uint32_t flags, IntersectionsResult &out)
+{
+	if (flags) throw Error(HRY_E_ARG, "unknown intersections flag");
+	if (b.block.device != cx.device) throw Error(HRY_E_ARG, "the hierarchy lives on another device than the context's");
+	const BvhView v = bvh_view_of(b);
+	const uint32_t T = (uint32_t)b.summary[0], L = v.L;
+	HIP_OK(hipSetDevice(cx.device));
+
+	// ---- the working buffer of the first stretch: the eight words that come down, the leaves' counts and their scan
+	Carve W;
+	BvhPairs c{};
+	uint32_t *sums, *key_b = nullptr, *val_b = nullptr, *radix = nullptr;
+	c.T = T;
+	W.take(c.stat, 64); W.take(c.count, (size_t)L * 4); W.take(c.start, ((size_t)L + 1) * 4); W.take(sums, scan_sums_words(L) * 4);
+	const size_t first = W.total;
+	cx.d_bvh.ensure(first);
+	W.bind(cx.d_bvh.p);
+	c.words = (uint32_t*)(c.stat + 4);
+
+	hipStream_t st = cx.stream;
+	HIP_OK(hipMemsetAsync(c.stat, 0, 64, st));
+	StretchTimer timer;
+	timer.mark(st);
+	launch_bvh_pairs_count(st, v, c, sums);
+	timer.mark(st);
+	unsigned long long down[8] = {};
+	HIP_OK(hipMemcpyAsync(down, c.stat, 64, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	if (down[3] >= (1ull << 31)) throw Error(HRY_E_UNSUPPORTED, "intersections: 2^31 pairs or more");
+	const uint32_t P = (uint32_t)down[3];
+
+	// ---- ... and of the second behind it: the sort's two sides.  Where the buffer has to grow, the first stretch's pieces move along
+	// (without a pair nothing is sorted, and the buffer stays as it is)
+	if (P) {
+		W.take(c.key, (size_t)P * 4); W.take(c.val, (size_t)P * 4); W.take(key_b, (size_t)P * 4); W.take(val_b, (size_t)P * 4);
+		W.take(radix, bvh_pairs_radix_words(P) * 4);
+		grow_keeping(cx.d_bvh, W.total, first, st);
+		W.bind(cx.d_bvh.p);
+		c.words = (uint32_t*)(c.stat + 4);
+	}
+
+	// ---- the outputs, in one allocation
+	OutputPlan plan;
+	plan.add("pairs", P, 2, HRY_UINT);
+	plan.add("pair_shared", P, 1, HRY_UINT);
+	plan.add("tri_pairs", T, 1, HRY_UINT);
+	plan.alloc(cx.device, out);
+	c.fill = 1; c.P = P; c.tri_pairs = out.ptr<uint32_t>("tri_pairs");
+	if (T) HIP_OK(hipMemsetAsync(c.tri_pairs, 0, (size_t)T * 4, st));
+
+	timer.mark(st);
+	launch_bvh_pairs_fill(st, v, c, key_b, val_b, radix, out.ptr<uint32_t>("pairs"), out.ptr<uint32_t>("pair_shared"));
+	timer.mark(st);
+	uint32_t words[2] = {};
+	HIP_OK(hipMemcpyAsync(words, c.words, 8, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	if (words[0] != P) throw Error(HRY_E_INTERNAL, "intersections: the scan of the counts and their sum disagree");
+	out.device_ms = timer.ms();
+	out.uploaded_bytes = 0;
+	out.summary[0] = T; out.summary[1] = down[0]; out.summary[2] = down[1]; out.summary[3] = P; out.summary[4] = words[1]; out.summary[5] = down[2];
 }
 
 }   // namespace hry

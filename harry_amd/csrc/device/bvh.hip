@@ -1,5 +1,6 @@
 // A linear bounding-volume hierarchy over the triangles of a render build, the closest-hit ray cast and the closest-point query over
-// it (driver: bvh.cpp; contract: include/harry_amd.h, hry_bvh_build, hry_bvh_cast and hry_bvh_nearest; DESIGN.md "Bvh").  Every floating-point operation is an
+// it, and the pairs of its triangles that pass through each other (driver: bvh.cpp; contract: include/harry_amd.h, hry_bvh_build,
+// hry_bvh_cast, hry_bvh_nearest and hry_intersections_build; DESIGN.md "Bvh").  Every floating-point operation is an
 // individually rounded IEEE double operation in the written order (the tree is built with -ffp-contract=off); the boxes are float
 // minima and maxima, which are exact in any order; there are no floating-point atomics.  The bits of every buffer depend on the
 // render build alone, those of a cast or a closest-point query on the hierarchy and the rays or points alone.
@@ -32,6 +33,14 @@
 //                   bounds at a node, leaves answered at once, the nearer internal child popped first; whatever has a bound
 //                   strictly greater than the best d2_t so far is skipped -- sound because d2_t is clamped from below by the bound
 //                   of the triangle's own leaf box, and a box that contains another has a bound no greater (DESIGN.md "Bvh")
+// The pairs that pass through each other (hry_intersections_build), in two stretches:
+//   k_bvh_pairs     a leaf per lane, the same stack with node numbers alone (16 KiB): the lane's leaf box against both children's
+//                   boxes, leaves answered at once, internal children pushed.  Every pair of leaves whose boxes overlap is met from
+//                   both sides; the side of the lower triangle number answers it.  First it counts (a count per leaf; C, N, the
+//                   box tests and P as integer atomics of wavefront sums), the counts are scanned, P comes down; then the same
+//                   body fills each leaf's rows, (s, t | share << 31), and bumps tri_pairs
+//   k_radix_*, k_pairs_turn   two stable sorts, by s, then -- key and payload exchanged -- by t: ascending (t, s)
+//   k_pairs_emit    pairs and pair_shared from the sorted rows;  k_pairs_hit: H, the triangles with tri_pairs > 0
 #include <hip/hip_runtime.h>
 
 #include "dev_types.hpp"
@@ -250,18 +259,27 @@ __device__ __forceinline__ bool interval(const float *box, const Ray &ray, doubl
 
 struct Best { double tt, u, v; uint32_t tri; };
 
+// the line o + tt d against the triangle (p0, p1, p2) (Moeller, Trumbore), the one arithmetic of the cast's hit and of the segment
+// test of k_bvh_pairs: inside -- det is finite and not zero, u >= 0, w >= 0, u + w <= 1; the caller bounds tt
+struct Meet { double tt, u, w; bool inside; };
+__device__ __forceinline__ Meet meet_of(const D3 &o, const D3 &d, const D3 &p0, const D3 &p1, const D3 &p2)
+{
+	const D3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), pv = cross3(d, e2);
+	const double det = dot_d(e1, pv);
+	const D3 s = sub3(o, p0), q = cross3(s, e1);
+	const double u = dot_d(s, pv) / det, w = dot_d(d, q) / det, tt = dot_d(e2, q) / det;
+	return Meet{ tt, u, w, finite_d(det) && det != 0.0 && u >= 0.0 && w >= 0.0 && u + w <= 1.0 };
+}
+
 // leaf `leaf`, whose own box has passed with [near, far]
 __device__ __forceinline__ void hit_leaf(const BvhView &v, uint32_t leaf, const Ray &ray, double near, double far, Best &best)
 {
 	const float *p = v.leaf_positions + 9 * (size_t)leaf;
 	const D3 p0{ (double)p[0], (double)p[1], (double)p[2] }, p1{ (double)p[3], (double)p[4], (double)p[5] }, p2{ (double)p[6], (double)p[7], (double)p[8] };
-	const D3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), pv = cross3(ray.d, e2);
-	const double det = dot_d(e1, pv);
-	const D3 s = sub3(ray.o, p0), q = cross3(s, e1);
-	const double u = dot_d(s, pv) / det, w = dot_d(ray.d, q) / det, tt = dot_d(e2, q) / det;
-	if (!(finite_d(det) && det != 0.0 && u >= 0.0 && w >= 0.0 && u + w <= 1.0 && near <= tt && tt <= far)) return;
+	const Meet m = meet_of(ray.o, ray.d, p0, p1, p2);
+	if (!(m.inside && near <= m.tt && m.tt <= far)) return;
 	const uint32_t t = v.leaf_tri[leaf];
-	if (tt < best.tt || (tt == best.tt && t < best.tri)) best = Best{ tt, u, w, t };
+	if (m.tt < best.tt || (m.tt == best.tt && t < best.tri)) best = Best{ m.tt, m.u, m.w, t };
 }
 
 __global__ __launch_bounds__(kCastBlock) void k_bvh_cast(BvhView v, BvhCast c)
@@ -445,6 +463,158 @@ __global__ __launch_bounds__(kCastBlock) void k_bvh_nearest(BvhView v, BvhNeares
 	}
 }
 
+// ---- the pairs that pass through each other
+struct Tri3 { D3 p[3]; };
+__device__ __forceinline__ Tri3 corners_of(const BvhView &v, uint32_t leaf)
+{
+	const float *p = v.leaf_positions + 9 * (size_t)leaf;
+	return Tri3{ { D3{ (double)p[0], (double)p[1], (double)p[2] }, D3{ (double)p[3], (double)p[4], (double)p[5] }, D3{ (double)p[6], (double)p[7], (double)p[8] } } };
+}
+// a triangle with a normal, as near_leaf asks for its face candidate
+__device__ __forceinline__ bool proper(const Tri3 &a)
+{
+	const D3 n = cross3(sub3(a.p[1], a.p[0]), sub3(a.p[2], a.p[0]));
+	return dot_d(n, n) > 0.0;
+}
+__device__ __forceinline__ bool same_corner(const D3 &a, const D3 &b) { return a.x == b.x && a.y == b.y && a.z == b.z; }   // (the widened floats: -0 equals +0)
+// closed, on the floats: the one rule, for leaf and node boxes alike
+__device__ __forceinline__ bool boxes_meet(const float (&a)[6], const float *b)
+{
+	return a[0] <= b[3] && b[0] <= a[3] && a[1] <= b[4] && b[1] <= a[4] && a[2] <= b[5] && b[2] <= a[5];
+}
+// the segment (a, b) against a triangle: the cast's arithmetic with o = a, d = b - a, and 0 <= tt <= 1
+__device__ __forceinline__ bool meets(const D3 &a, const D3 &b, const Tri3 &tri)
+{
+	const Meet m = meet_of(a, sub3(b, a), tri.p[0], tri.p[1], tri.p[2]);
+	return m.inside && 0.0 <= m.tt && m.tt <= 1.0;
+}
+// two proper triangles: share (0 .. 3) and, where it is 0 or 1, whether an admitted edge of one meets the other -- all six edges
+// without a shared corner, with one the edge opposite it on either side.  Edge k is (P_k, P_(k + 1) % 3)
+__device__ __forceinline__ bool pass_through(const Tri3 &a, const Tri3 &b, uint32_t &share)
+{
+	int ka = -1, kb = -1;
+	share = 0;
+#pragma unroll
+	for (int i = 0; i < 3; ++i) {
+		bool shared = false;
+#pragma unroll
+		for (int j = 0; j < 3; ++j)
+			if (same_corner(a.p[i], b.p[j])) { shared = true; kb = j; }
+		if (shared) { ++share; ka = i; }
+	}
+	if (share > 1) return false;
+	const int ea = share ? (ka + 1) % 3 : -1, eb = share ? (kb + 1) % 3 : -1;   // the edge opposite corner k begins at corner k + 1
+	bool any = false;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		if (!any && (!share || k == ea)) any = meets(a.p[k], a.p[(k + 1) % 3], b);
+		if (!any && (!share || k == eb)) any = meets(b.p[k], b.p[(k + 1) % 3], a);
+	}
+	return any;
+}
+
+// A leaf per lane, in leaf order (neighbours in space: the leaves are sorted by code); the cast's stack, node numbers alone.  Every
+// leaf whose box meets the lane's is met -- its box lies inside every box above it --, so every pair is met from both sides, and
+// the side of the lower triangle number answers it.  c.fill == 0 counts (count[leaf], and C, N, the box tests and P as 64-bit sums),
+// c.fill == 1 walks again and writes the pairs where the scan of the counts says: one body, so both make the same decisions
+__global__ __launch_bounds__(kCastBlock) void k_bvh_pairs(BvhView v, BvhPairs c)
+{
+	__shared__ uint32_t s_node[kCastStack * kCastBlock];
+	const uint32_t lane = threadIdx.x;
+	unsigned long long boxes = 0, tested = 0, made = 0, found = 0;
+	for (uint64_t base = (uint64_t)blockIdx.x * kCastBlock; base < v.L; base += (uint64_t)gridDim.x * kCastBlock) {
+		const uint64_t i = base + lane;
+		uint32_t n_boxes = 0, n_tested = 0, n_made = 0, n_found = 0;
+		if (i < v.L && v.L > 1) {
+			const uint32_t t = v.leaf_tri[i];
+			const Tri3 mine = corners_of(v, (uint32_t)i);
+			const bool mine_proper = proper(mine);
+			float box[6];
+#pragma unroll
+			for (int k = 0; k < 6; ++k) box[k] = v.leaf_box[6 * i + k];
+			const uint64_t at = c.fill ? c.start[i] : 0;
+			const auto leaf = [&](uint32_t j) {
+				const uint32_t s = v.leaf_tri[j];
+				if (!(t < s)) return;   // (itself, or the other side's pair)
+				++n_boxes;
+				if (!mine_proper) return;
+				const Tri3 other = corners_of(v, j);
+				if (!proper(other)) return;
+				uint32_t share;
+				const bool through = pass_through(mine, other, share);
+				if (share > 1) return;
+				++n_tested;
+				if (!through) return;
+				if (c.fill && at + n_found < c.P && t < c.T && s < c.T) {
+					c.key[at + n_found] = s;
+					c.val[at + n_found] = t | (share << 31);
+					atomicAdd(&c.tri_pairs[t], 1u);
+					atomicAdd(&c.tri_pairs[s], 1u);
+				}
+				++n_found;
+			};
+			uint32_t sp = 1;
+			s_node[lane] = 0;
+			while (sp) {
+				--sp;
+				const uint32_t node = s_node[sp * kCastBlock + lane];
+				if (node + 1 >= v.L) continue;
+				const uint32_t c0 = v.node_children[2 * (size_t)node], c1 = v.node_children[2 * (size_t)node + 1];
+				const uint32_t n0 = c0 & ~kLeafBit, n1 = c1 & ~kLeafBit;
+				if (n0 + (c0 & kLeafBit ? 0u : 1u) >= v.L || n1 + (c1 & kLeafBit ? 0u : 1u) >= v.L) continue;   // (no tree names such a child: a leaf below L, a node below L - 1)
+				const bool go0 = boxes_meet(box, (c0 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n0);
+				const bool go1 = boxes_meet(box, (c1 & kLeafBit ? v.leaf_box : v.node_box) + 6 * (size_t)n1);
+				n_made += 2;
+				if (go0 && (c0 & kLeafBit)) leaf(n0);
+				if (go1 && (c1 & kLeafBit)) leaf(n1);
+				// The two guards -- a child beyond L above, a push beyond the stack here -- keep a hierarchy that hry_bvh_build did not
+				// make from reading or writing out of bounds, and nothing more: what they drop is dropped in both stretches alike,
+				// so the result would be short and no check would notice.  A hierarchy of hry_bvh_build reaches neither (depth <= 62)
+				if (go1 && !(c1 & kLeafBit) && sp < kCastStack) { s_node[sp * kCastBlock + lane] = n1; ++sp; }
+				if (go0 && !(c0 & kLeafBit) && sp < kCastStack) { s_node[sp * kCastBlock + lane] = n0; ++sp; }
+			}
+			if (!c.fill) c.count[i] = n_found;
+		} else if (i < v.L && !c.fill) c.count[i] = 0;
+		if (!c.fill) {
+			boxes += wave_sum((unsigned long long)n_boxes);
+			tested += wave_sum((unsigned long long)n_tested);
+			made += wave_sum((unsigned long long)n_made);
+			found += wave_sum((unsigned long long)n_found);
+		}
+	}
+	if (lane == 0 && !c.fill) {
+		if (boxes) atomicAdd(&c.stat[0], boxes);
+		if (tested) atomicAdd(&c.stat[1], tested);
+		if (made) atomicAdd(&c.stat[2], made);
+		if (found) atomicAdd(&c.stat[3], found);
+	}
+}
+
+// between the two sorts: (s, t | share << 31) becomes (t, s | share << 31)
+__global__ __launch_bounds__(kBvhBlock) void k_pairs_turn(uint32_t *key, uint32_t *val, uint32_t P)
+{
+	const uint32_t i = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (i >= P) return;
+	const uint32_t s = key[i], packed = val[i];
+	key[i] = packed & ~kLeafBit;
+	val[i] = s | (packed & kLeafBit);
+}
+__global__ __launch_bounds__(kBvhBlock) void k_pairs_emit(const uint32_t *key, const uint32_t *val, uint32_t P, uint32_t *pairs, uint32_t *pair_shared)
+{
+	const uint32_t i = blockIdx.x * kBvhBlock + threadIdx.x;
+	if (i >= P) return;
+	pairs[2 * (size_t)i] = key[i];
+	pairs[2 * (size_t)i + 1] = val[i] & ~kLeafBit;
+	pair_shared[i] = val[i] >> 31;
+}
+// H: the triangles in a pair, a ballot and one integer atomic per wavefront
+__global__ __launch_bounds__(kBvhBlock) void k_pairs_hit(const uint32_t *tri_pairs, uint32_t T, uint32_t *hit)
+{
+	const uint32_t t = blockIdx.x * kBvhBlock + threadIdx.x;
+	const uint32_t n = (uint32_t)__popcll(__ballot(t < T && tri_pairs[t] > 0));
+	if ((threadIdx.x & 63) == 0 && n) atomicAdd(hit, n);
+}
+
 }   // namespace
 
 // ---- launchers (kernels.hpp)
@@ -481,6 +651,32 @@ void launch_bvh_nearest(hipStream_t st, const BvhView &v, const BvhNearest &c)
 {
 	if (!c.n) return;
 	hipLaunchKernelGGL(k_bvh_nearest, dim3(grid_for(c.n, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
+}
+
+size_t bvh_pairs_radix_words(uint32_t P) { return radix_scratch_words(P); }
+void launch_bvh_pairs_count(hipStream_t st, const BvhView &v, const BvhPairs &c, uint32_t *sums)
+{
+	if (v.L) hipLaunchKernelGGL(k_bvh_pairs, dim3(grid_for(v.L, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
+	launch_excl_scan(st, c.count, v.L, sums, c.start, c.words);
+}
+
+void launch_bvh_pairs_fill(hipStream_t st, const BvhView &v, const BvhPairs &c, uint32_t *key_b, uint32_t *val_b, uint32_t *radix, uint32_t *pairs, uint32_t *pair_shared)
+{
+	if (c.P) {
+		hipLaunchKernelGGL(k_bvh_pairs, dim3(grid_for(v.L, kCastBlock)), dim3(kCastBlock), 0, st, v, c);
+		// two stable sorts, by s and then by t, of as many 8-bit passes as the triangle numbers have bytes
+		int passes = 1;
+		while (passes < 4 && ((uint64_t)c.T - 1) >> (8 * passes)) ++passes;
+		uint32_t *ka = c.key, *va = c.val, *kb = key_b, *vb = val_b;
+		const dim3 grid(blocks_for(c.P, kBvhBlock)), block(kBvhBlock);
+		for (int round = 0; round < 2; ++round) {
+			launch_radix_sort(st, ka, va, kb, vb, c.words, c.P, passes, radix);
+			if (passes & 1) { std::swap(ka, kb); std::swap(va, vb); }
+			if (round == 0) hipLaunchKernelGGL(k_pairs_turn, grid, block, 0, st, ka, va, c.P);
+		}
+		hipLaunchKernelGGL(k_pairs_emit, grid, block, 0, st, (const uint32_t*)ka, (const uint32_t*)va, c.P, pairs, pair_shared);
+	}
+	if (c.T) hipLaunchKernelGGL(k_pairs_hit, dim3(blocks_for(c.T, kBvhBlock)), dim3(kBvhBlock), 0, st, (const uint32_t*)c.tri_pairs, c.T, c.words + 1);
 }
 
 }   // namespace dev

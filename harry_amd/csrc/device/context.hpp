@@ -108,7 +108,7 @@ struct Context {
 	DevBuf d_tangents; // hry_tangents_build: the triangles' terms and signs, counters, segment starts, the segments, the list of long segments (tangents.cpp)
 	DevBuf d_creases;  // hry_creases_build: the slots' union-find, roots and scan, the numbering's table, the triangles' terms, the groups' segments and normals (creases.cpp)
 	DevBuf d_curvature;   // hry_curvature_build: the ends' flags, counters, segment starts, the segments, the list of long segments, the decoded vertices' rows and the totals' rounds (curvature.cpp)
-	DevBuf d_bvh;   // hry_bvh_build: the live flags and their scan, the sort's two sides and counters, the tree's children and parents; hry_bvh_cast / hry_bvh_nearest: the staged rays or points and results of a host query, the counters (bvh.cpp)
+	DevBuf d_bvh;   // hry_bvh_build: the live flags and their scan, the sort's two sides and counters, the tree's children and parents; hry_bvh_cast / hry_bvh_nearest: the staged rays or points and results of a host query, the counters; hry_intersections_build: the words that come down, the leaves' counts and their scan, the sort's two sides (bvh.cpp)
 	DevBuf d_shells;   // hry_shells_build: the union-finds, the pairs' numbering, the chunks' partial sums and their segments (shells.cpp)
 	DevBuf d_distortion;   // hry_distortion_build: its uploads (what is not resident), the blocks' records, results and status word (distortion.cpp)
 	DevBuf d_sweep;   // hry_quant_sweep_build: its uploads (a mesh that is not resident), the blocks' records and the results (sweep.cpp)

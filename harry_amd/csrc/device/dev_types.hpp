@@ -244,6 +244,15 @@ struct BvhNearest {
 	float *near_uv, *near_point;
 	unsigned long long *stat;
 };
+// the pairs of leaves that pass through each other, one walk of two: fill == 0 writes count [L] and adds to stat, four zeroed 64-bit
+// words (pairs of leaves whose boxes overlap, pairs that reach the segment tests, box tests of the walk, pairs found); fill == 1
+// reads start [L], the exclusive scan of count, and writes P rows of key (s) and val (t | share << 31) and bumps tri_pairs [T],
+// zeroed.  words: [0] P as the scan gave it (the sorts' length), [1] H, zeroed; T: the triangles of the render build
+struct BvhPairs {
+	uint32_t fill, P, T;
+	uint32_t *count, *start, *key, *val, *tri_pairs, *words;
+	unsigned long long *stat;
+};
 
 // render.hip: the runs of one segment of a sharded container, local first element (l*) and first element in the whole mesh (g*)
 // per run and kind (vertices, faces, half-edges); gn*: sizes of the whole mesh

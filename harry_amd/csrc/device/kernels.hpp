@@ -251,6 +251,12 @@ void launch_bvh_second(hipStream_t st, const BvhWork &w, const BvhView &v, uint3
 void launch_bvh_cast(hipStream_t st, const BvhView &v, const BvhCast &c);
 uint32_t bvh_cast_block();
 void launch_bvh_nearest(hipStream_t st, const BvhView &v, const BvhNearest &c);
+// launch_bvh_pairs_count (c.fill == 0): the walk of every leaf against the hierarchy, counting, and the scan of the counts into
+// c.start and c.words[0]; sums: scan_sums_words(v.L).  launch_bvh_pairs_fill (c.fill == 1, c.P known): the walk again, the two sorts
+// (key_b / val_b: the other side, P words each; radix: bvh_pairs_radix_words(P)), pairs and pair_shared, and H into c.words[1]
+size_t bvh_pairs_radix_words(uint32_t P);
+void launch_bvh_pairs_count(hipStream_t st, const BvhView &v, const BvhPairs &c, uint32_t *sums);
+void launch_bvh_pairs_fill(hipStream_t st, const BvhView &v, const BvhPairs &c, uint32_t *key_b, uint32_t *val_b, uint32_t *radix, uint32_t *pairs, uint32_t *pair_shared);
 
 // shells of a render build (shells.hip; driver: shells.cpp), behind its edges build.  launch_shells_roots: the union-find over the
 // triangles, the root flags and their scan: w.num[T] = the number of shells, on the device.  launch_shells_label (v.ns known, the

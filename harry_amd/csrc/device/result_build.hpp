@@ -1,10 +1,11 @@
 // What the builds that leave a result handle share on the host (render.cpp, edges.cpp, shells.cpp, orient.cpp, tangents.cpp,
 // creases.cpp, curvature.cpp, bvh.cpp): the plan of a handle's named buffers, the timer of a build in one stretch or
-// two, the one result type of the seven builds behind a render build and the checks that one build is the build of another
+// two, the one result type of the eight builds behind a render build and the checks that one build is the build of another
 // (result_build.cpp).  A driver states each working buffer once -- W.take(w.field, bytes), then W.bind(base) behind the allocation
 // (hip_handles.hpp: Carve) -- and fetches an output as out.ptr<T>("name") (context.hpp: DeviceResult).
 #pragma once
 #include "context.hpp"
+#include "grow_keeping.hpp"
 #include "kernels.hpp"
 
 namespace hry {
@@ -78,6 +79,11 @@ void bvh_cast(Context &cx, const BvhResult &b, uint64_t n_rays, const float *ori
               double tmax, uint32_t flags, uint32_t *hit_tri, float *hit_t, float *hit_uv, uint64_t *stat, double *device_ms);   // flags: HRY_CAST_*
 void bvh_nearest(Context &cx, const BvhResult &b, uint64_t n_points, const float *points, uint64_t point_stride, double max_dist, uint32_t flags, uint32_t *near_tri,
                  double *near_d2, float *near_uv, float *near_point, uint64_t *stat, double *device_ms);   // flags: HRY_NEAREST_*
+// ... and the pairs of its triangles that pass through each other (include/harry_amd.h: hry_intersections_build).  summary: T, C pairs
+// of leaves whose boxes overlap, N of them that reach the segment tests, P pairs, H triangles in a pair, the box tests of the walk.
+// It reads the hierarchy alone
+typedef TopologyResult IntersectionsResult;
+void intersections_build(Context &cx, const BvhResult &b, uint32_t flags, IntersectionsResult &out);   // flags: none
 
 // ---- result_build.cpp
 // r is a render build of m on cx's device, with at most 2^31 triangle sides: HRY_E_ARG / HRY_E_UNSUPPORTED otherwise

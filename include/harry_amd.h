@@ -22,6 +22,7 @@
  *   hry_curvature_build (no counterpart: mixed Voronoi area, angle defect, Gaussian and mean curvature per vertex of a render build, as device buffers)
  *   hry_bvh_build, hry_bvh_cast (no counterpart: a bounding-volume hierarchy over the triangles of a render build and closest-hit ray queries against it, on the device)
  *   hry_bvh_nearest     (no counterpart: the closest point of that hierarchy's triangles to every query point, the query behind a mesh-to-mesh deviation)
+ *   hry_intersections_build (no counterpart: the pairs of that hierarchy's triangles that pass through each other, as device buffers)
  *   hry_mesh_from_device (no counterpart: hry_mesh_from_arrays from device buffers, resident for the encoder, optional exact weld)
  *   hry_mesh_from_device_corners (no counterpart: the mesh hry_mesh_from_obj builds, from device buffers: corner lists, material regions)
  *   hry_order_take      (no counterpart: the permutation between the source's numbering and the decoder's, as device tables)
@@ -763,6 +764,55 @@ int hry_bvh_nearest(hry_ctx *ctx, const hry_bvh *b, uint64_t n_points, const flo
                     double max_dist, uint32_t flags,
                     uint32_t *near_tri, double *near_d2, float *near_uv, float *near_point,
                     uint64_t stat[3], double *device_ms);
+
+/* hry_intersections_build answers whether the surface passes through itself: the pairs of the hierarchy's triangles of which an
+ * edge of one meets the other.  It reads the hierarchy alone -- "leaf_tri", "leaf_box", "leaf_positions", "node_children",
+ * "node_box" --, so the mesh and the render build may have been freed.  The contract defines the result, not the way to it: every
+ * bit of the buffers depends on the hierarchy alone, and a program that tests every pair of leaves by the rules below gets the same
+ * bits.  All arithmetic is in double on the widened floats, every operation individually rounded in the written order; a . b and
+ * a x b as in the cast's contract.
+ * Proper triangle: a leaf triangle with n = (P1 - P0) x (P2 - P0) and n . n > 0, as the face candidate of hry_bvh_nearest asks.
+ *   Dead triangles are no leaves and are in no pair; an improper triangle (a segment, a point) is tested against nothing.
+ * Shared corners: two corners are the same when their three floats compare equal with == (so -0 equals +0): by position, not by
+ *   index -- an unwelded render build's neighbours share positions, not numbers.  share(t, s): the corners of t that are the same
+ *   as some corner of s; the corners of a proper triangle are distinct, so it is 0 .. 3 and share(t, s) = share(s, t).
+ * Segment against triangle: meets(A, B, tri) is the hit of hry_bvh_cast with O = A, D = B - A -- e1, e2, p, det, s, q, u, v, tt
+ *   as there --, true when det is finite and not 0, u >= 0, v >= 0, u + v <= 1 and 0 <= tt <= 1.  A NaN fails every comparison.
+ *   Edge k of a triangle is (P_k, P_(k + 1) % 3), in that direction.
+ * The unordered pair {t, s}, t < s, intersects when all of these hold:
+ *   1. their leaf boxes overlap, closed, on the floats: lo_t <= hi_s and lo_s <= hi_t on the three axes;
+ *   2. both are proper and share(t, s) <= 1;
+ *   3. an admitted edge of one meets the other.  With share = 0 all six edges are admitted; with share = 1 only the edge opposite
+ *      the shared corner, on either side: two tests (the edges through the shared corner touch the other triangle there and
+ *      nowhere else, unless the triangles are coplanar).  The OR of the tests does not depend on their order, and no test on
+ *      which triangle is called the first.
+ * What follows, and is no defect:
+ *   touching counts -- a corner on a face, an edge against an edge;
+ *   coplanar overlaps are not found: det = 0 fails every test;
+ *   pairs that share an edge or all three corners are never tested: a fold about a shared edge is what "edge_cos" of
+ *   hry_edges_build tells;
+ *   near-coplanar pairs are decided by the rounding -- deterministically, like everything else here.
+ * Buffers by name:
+ *   "pairs"        u32 [P, 2]  (t, s), t < s, triangle numbers of the render build, ascending lexicographically
+ *   "pair_shared"  u32 [P]     share(t, s): 0 or 1
+ *   "tri_pairs"    u32 [T]     in how many pairs triangle t is (a dead or improper one: 0)
+ *   hry_intersections_count    P
+ *   hry_intersections_get / _copy / _stat / _free  as hry_bvh_get / _copy / _stat / _free
+ *   hry_intersections_summary  out = { T, C, N, P, H, box tests }; C: the pairs of leaves t < s whose boxes overlap, improper and
+ *                    edge-sharing ones included; N: those of them with both proper and share <= 1, the pairs that reach meets; H:
+ *                    the triangles with tri_pairs > 0.  The sixth word, the box tests the walk made, is the one word that depends
+ *                    on the walk (it is what a hierarchy saves over L tests a leaf) and is no part of the bit contract.  Integer
+ *                    device reductions; there are no floating-point atomics.
+ * Refusals: null arguments ("null argument", before any device is touched), any flag bit, a b on another device than ctx's:
+ * HRY_E_ARG; P >= 2^31: HRY_E_UNSUPPORTED; *out stays NULL and ctx stays usable. */
+typedef struct hry_intersections hry_intersections;   /* a result handle like hry_bvh */
+int hry_intersections_build(hry_ctx *ctx, const hry_bvh *b, uint32_t flags, hry_intersections **out);   /* flags: none */
+uint64_t hry_intersections_count(const hry_intersections *i);   /* P: the pairs */
+int hry_intersections_get(const hry_intersections *i, const char *name, const void **dev, uint64_t *rows, int *width, int *type);
+int hry_intersections_copy(hry_ctx *ctx, const hry_intersections *i, const char *name, void *dst, int dst_is_device);
+int hry_intersections_summary(const hry_intersections *i, uint64_t out[6]);
+int hry_intersections_stat(const hry_intersections *i, double *device_ms, uint64_t *uploaded_bytes);
+void hry_intersections_free(hry_intersections *i);
 
 /* hry_mesh_flip_faces returns a clone of m in which every face f with face_flip[f] != 0 (nf host words, for instance "face_flip" of
  * hry_orient_build), (v0, v1, ..., vk-1), has become (v0, vk-1, ..., v1).  Every per-corner array follows its corner: the origins,
